@@ -20,7 +20,8 @@ N > 1: one process per GPU (torchrun), every rank streams its own clip (weak sca
 independent); the only exchange is the barrier/MAX around the timed region and a host (gloo) gather
 of the per-pair scalars -- no RCCL collective in the data path.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0; `ms_per_step` is the wall time of one timed step.  --dump-outputs DIR also writes what
+the last timed step computed as DIR/<name>.npy, so that two builds can be compared output for output.
 """
 import argparse
 import gc
@@ -318,6 +319,42 @@ def verify(runner, frames, W, H, B, seed, ctx):
     return golden_check.check_batch(gold, frames, recs, dots, lambda j: ctx.download_flow(slots[j]))
 
 
+DUMP_LIMIT = 64 << 20      # --dump-outputs: bytes of all arrays together
+DUMP_FLOW_BYTES = 32 << 20  # of which the flow sample takes at most this much
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as <out_dir>/<name>.npy (float32 / float64 only), at most DUMP_LIMIT bytes in all."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_LIMIT}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def last_step_outputs(runner, ctx, W, H):
+    """What the caller of the timed path receives from its LAST timed step: the pass-1 records and the pass-2 scalars of
+    every pair, plus the flow fields behind them (still resident in the step's slots) at a fixed, seeded sample of pixels
+    -- the same pixels for every pair and every run of the same arguments."""
+    recs, dots, slots = runner.results[-1]
+    B, N = len(slots), W * H
+    n_pix = min(N, DUMP_FLOW_BYTES // (B * 2 * 4))
+    pix = np.sort(np.random.default_rng(0).choice(N, n_pix, replace=False))
+    flow = np.stack([ctx.download_flow(s).reshape(N, 2)[pix] for s in slots])
+    return {
+        "argmax_x": np.array([r[0] for r in recs], np.float64),
+        "argmax_y": np.array([r[1] for r in recs], np.float64),
+        "max_divergence": np.array([r[2] for r in recs], np.float32),
+        "mean_magnitude": np.array([r[3] for r in recs], np.float32),
+        "cut": np.array([r[4] for r in recs], np.float64),
+        "radial": np.asarray(dots, np.float64),
+        "flow_sample": flow.astype(np.float32),            # (B, n_pix, 2): (dx, dy) at the sampled pixels
+        "flow_sample_index": pix.astype(np.float64),        # row-major pixel index y * W + x of each sample
+    }
+
+
 CHUNK_FRAMES = 3000   # the reference's default chunk: params["batch_size"] frames are decoded, paired and processed together (FF:2647, FF:1145-1153)
 
 
@@ -452,6 +489,11 @@ def one_clip(args, rank, world, local_rank, host_group, barrier, max_over_ranks,
         dt = time.perf_counter() - t0
     if world > 1:
         dt = max_over_ranks(dt)
+    if rank == 0 and args.dump_outputs:
+        # the timed call returns the whole clip's records and scalars on every rank
+        r = np.asarray(recs, np.float64).reshape(n_pairs, 3)
+        dump_outputs(args.dump_outputs, {"argmax_x": r[:, 0].copy(), "argmax_y": r[:, 1].copy(), "cut": r[:, 2].copy(),
+                                         "radial": np.asarray(dots, np.float64)})
     if rank == 0:
         # (a) the stream has period 16: pair j and pair j + 16 are the same images, and (away from the clip's ends, where the
         # smoothing window is clipped) have the same centre -> the same scalar, whichever rank computed them
@@ -555,7 +597,14 @@ def main():
     ap.add_argument("--profile-all", action="store_true",
                     help="HIP events around every kernel class in the TIMED region (adds ~0.2 ms/step); default: the "
                          "dominant kernel only, the other classes are timed in the separate kernel_classes pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (f32 / f64, at most "
+                         "64 MB): pass-1 records, pass-2 scalars and a fixed, seeded pixel sample of the flow fields")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # Started from a plain shell (`python bench.py --gpus N ...`, the driver's command): this process becomes the PARENT
@@ -689,6 +738,7 @@ def main():
         print("step ms:", " ".join(f"{v:.2f}" for v in d), file=sys.stderr)
     plain = not args.independent and args.zoom == 0.0
     checked, check_detail = verify(runner, frames, W, H, B, seed, ctx) if plain else (None, "non-default clip")
+    dumped = last_step_outputs(runner, ctx, W, H) if args.dump_outputs and rank == 0 else None
     results = runner.results
     graphs = ctx.graph_stats()
     ctx.close()
@@ -706,6 +756,12 @@ def main():
             bad = [f for f in flags if f[0] is False]
             checked = False if bad else (True if all(f[0] is True for f in flags) else None)
             check_detail = bad[0][1] if bad else f"{sum(f[0] is True for f in flags)} of {world} ranks have goldens for their clip; " + flags[0][1]
+            if dumped is not None:
+                # every rank's last timed step: (x, y, cut, radial) per pair, rank-major
+                dumped["ranks_last_step"] = np.stack([g[-B:] for g in gathered]).astype(np.float64)
+
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped)
 
     if rank == 0:
         pairs = world * args.steps * B

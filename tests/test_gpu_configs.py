@@ -396,6 +396,36 @@ def test_bench_prints_exactly_one_json_line():
     assert d["steps"] == 2 and d["n_gpus"] == 1 and d["checked"] is True
 
 
+def test_bench_dump_outputs_repeat_and_match_the_golden(tmp_path):
+    """--dump-outputs: two runs with the same arguments write the same arrays (bit for bit), --steps sets the number of
+    timed steps, and the dumped records / scalars of the last step are those of the oracle golden of that workload."""
+    import json
+    W, H, B = 256, 256, 64
+    dumps = []
+    for run, steps in enumerate((2, 3)):
+        d = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "1",
+                            "--width", str(W), "--height", str(H), "--batch", str(B), "--no-extras", "--no-cpu-baseline",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.split("\n") if l.strip()][0])
+        assert line["steps"] == steps and line["ms_per_step"] > 0 and line["checked"] is True, line["check_detail"]
+        assert sum(p.stat().st_size for p in d.iterdir()) <= 64 << 20
+        dumps.append({p.stem: np.load(p) for p in d.iterdir()})
+    a, b = dumps
+    assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    gold = golden_check.load_golden(W, H, B, 1)          # "checked" above: the run's frames are the golden's
+    assert a["argmax_x"].tolist() == gold["x"] and a["argmax_y"].tolist() == gold["y"]
+    assert a["max_divergence"].view(np.uint32).tolist() == gold["val_bits"] and a["cut"].astype(bool).tolist() == gold["cut"]
+    g = np.asarray(gold["dots"], np.float64)
+    assert np.all(np.abs(a["radial"] - g) <= 1e-4 * np.maximum(np.abs(g), np.mean(np.abs(g))))
+    # the flow sample holds the device's own flow: pair 0 against the oracle at the sampled pixels
+    fr = sine_translate_frames(2, W, H, seed=1)
+    pix = a["flow_sample_index"].astype(np.int64)
+    assert np.array_equal(a["flow_sample"][0], orc.farneback(fr[0], fr[1]).reshape(-1, 2)[pix])
+
+
 def test_non_default_options_change_no_bit():
     """tile_order = 1 (tile-major workgroup order), pyr_coarse = 0 (H + V kernel pairs for the coarse pyramid levels),
     copy_threads = 1 / 8 (staging copy split) and blur_min_wgs (automatic strip length of k_blur_solve, from a whole tile

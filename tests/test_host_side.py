@@ -429,6 +429,44 @@ def test_bench_helpers_without_a_gpu(tmp_path, monkeypatch):
     assert 0 <= c["max_abs_dflow_fast_vs_parity"] < 1e-2 and c["argmax_equal_fast_vs_parity"] in (True, False)
 
 
+def test_bench_dump_outputs_without_a_gpu(tmp_path):
+    """--dump-outputs: the last step's records, scalars and a seeded flow sample as f32 / f64 .npy files within 64 MB;
+    the sample is the same pixels on every call, and an oversized dump is refused before anything is written."""
+    import importlib
+    bench = importlib.import_module("bench")
+    W, H, B = 1920, 1080, 64
+    rng = np.random.default_rng(5)
+    flows = {s: rng.standard_normal((H, W, 2)).astype(np.float32) for s in range(2 * B)}
+
+    class Ctx:
+        def download_flow(self, slot):
+            return flows[slot]
+
+    class Runner:
+        results = [([(1, 2, np.float32(0.5), np.float32(1.5), True)] * B, [0.25] * B, list(range(B))),
+                   ([(3, 4, np.float32(0.75), np.float32(2.5), False)] * B, [0.125] * B, list(range(B, 2 * B)))]
+
+    a = bench.last_step_outputs(Runner(), Ctx(), W, H)
+    b = bench.last_step_outputs(Runner(), Ctx(), W, H)
+    assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
+    assert a["argmax_x"].tolist() == [3.0] * B and a["cut"].tolist() == [0.0] * B and a["radial"].tolist() == [0.125] * B
+    assert a["max_divergence"].dtype == np.float32 and a["mean_magnitude"].tolist() == [2.5] * B
+    pix = a["flow_sample_index"].astype(np.int64)
+    assert a["flow_sample"].shape == (B, len(pix), 2) and len(np.unique(pix)) == len(pix) and pix.max() < W * H
+    j = B // 2
+    assert np.array_equal(a["flow_sample"][j], flows[B + j].reshape(-1, 2)[pix])     # pair j of the LAST step
+    out = tmp_path / "dump"
+    bench.dump_outputs(str(out), a)
+    assert sorted(p.name for p in out.iterdir()) == sorted(k + ".npy" for k in a)
+    assert sum(p.stat().st_size for p in out.iterdir()) <= bench.DUMP_LIMIT
+    for k in a:
+        got = np.load(out / (k + ".npy"))
+        assert got.dtype in (np.float32, np.float64) and np.array_equal(got, a[k])
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_LIMIT // 8 + 1)})
+    assert not (tmp_path / "big").exists()
+
+
 _RANK_CHILD = r"""
 import json, os, sys, time
 rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
