@@ -19,7 +19,54 @@ EXPORTS = ["ffl_device_count", "ffl_create", "ffl_destroy", "ffl_last_error", "f
            "ffl_flow_pairs",
            "ffl_pass1_result", "ffl_pass1_results", "ffl_radial", "ffl_download_flow", "ffl_upload_flow", "ffl_submit_pair", "ffl_sync",
            "ffl_num_levels", "ffl_level_size", "ffl_download_frame", "ffl_debug_pair", "ffl_set_option", "ffl_ctx_set_option", "ffl_ctx_get_option", "ffl_graph_stats", "ffl_profile_enable",
-           "ffl_profile_read", "ffl_kernel_name", "ffl_device_mem_info", "ffl_estimate_bytes"]
+           "ffl_profile_read", "ffl_kernel_name", "ffl_device_mem_info", "ffl_estimate_bytes",
+           "ffl_dis_default_params", "ffl_dis_geometry", "ffl_flow_pairs_dis", "ffl_debug_dis_pair"]
+
+FLOWS = ("farneback", "dis")   # params["hip_flow"]: the reference's CPU/CUDA/OpenCL branch, or its "DNN" branch (FF:948-980)
+DIS_STAGES = {"pass1": 0, "pass2": 1, "dense": 2, "refined": 3, "images": 4}   # ffl_debug_dis_pair stages
+
+
+class DisParams(C.Structure):
+    """ffl_dis_params; the defaults are PRESET_FAST."""
+    _fields_ = [("finest_scale", C.c_int), ("patch_size", C.c_int), ("patch_stride", C.c_int),
+                ("grad_descent_iters", C.c_int), ("var_refine_iters", C.c_int), ("vr_alpha", C.c_float),
+                ("vr_gamma", C.c_float), ("vr_delta", C.c_float), ("use_mean_norm", C.c_int),
+                ("use_spatial_prop", C.c_int), ("stripes", C.c_int)]
+    FAST = dict(finest_scale=2, patch_size=8, patch_stride=4, grad_descent_iters=16, var_refine_iters=5, vr_alpha=20.0,
+                vr_gamma=10.0, vr_delta=5.0, use_mean_norm=1, use_spatial_prop=1, stripes=0)
+
+    def __init__(self, **over):
+        unknown = set(over) - set(self.FAST)
+        if unknown:
+            raise ValueError(f"unknown DIS parameter(s) {sorted(unknown)}; known: {sorted(self.FAST)}")
+        super().__init__(**{**self.FAST, **over})
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+def flow_choice(params):
+    """("farneback", None) or ("dis", DisParams) from a reference params dict: "hip_flow" picks the algorithm
+    (default "farneback"), "hip_dis" = {field: value} overrides single DIS parameters.  Unknown values raise ValueError, and so
+    does "hip_dis" without "hip_flow": "dis" (it would otherwise be ignored)."""
+    flow = params.get("hip_flow", "farneback")
+    if flow not in FLOWS:
+        raise ValueError(f"hip_flow must be one of {FLOWS}, got {flow!r}")
+    if flow == "farneback":
+        if params.get("hip_dis"):
+            raise ValueError('"hip_dis" overrides DIS parameters: it needs "hip_flow": "dis"')
+        return flow, None
+    return flow, DisParams(**dict(params.get("hip_dis") or {}))
+
+
+def dis_geometry(width, height, params=None):
+    """(coarsest, finest) DIS scales of a frame size; ValueError when the size or the parameters are not supported."""
+    c, f = C.c_int(), C.c_int()
+    p = params if params is not None else DisParams()
+    if load().ffl_dis_geometry(int(width), int(height), C.byref(p), C.byref(c), C.byref(f)) != FFL_OK:
+        raise ValueError(f"DIS does not support {width}x{height} with {p.as_dict()} (DESIGN.md appendix D2: patch_size 8, "
+                         "sides divisible by 2^coarsest)")
+    return c.value, f.value
 
 
 class FFLError(RuntimeError):
@@ -75,6 +122,11 @@ def load():
     L.ffl_graph_stats.argtypes = [vp, ip, ip, ip]
     L.ffl_device_mem_info.argtypes = [C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.ffl_estimate_bytes.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    dp_ = C.POINTER(DisParams)
+    L.ffl_dis_default_params.argtypes = [dp_]
+    L.ffl_dis_geometry.argtypes = [C.c_int, C.c_int, dp_, ip, ip]
+    L.ffl_flow_pairs_dis.argtypes = [vp, C.c_int, ip, ip, ip, C.c_int, dp_]
+    L.ffl_debug_dis_pair.argtypes = [vp, C.c_int, C.c_int, dp_, C.c_int, C.c_int, vp]
     _lib = L
     return L
 
@@ -235,6 +287,15 @@ class Context:
             raise FFLError("flow_pairs: the three slot lists must have one entry per pair")
         self._chk(self.L.ffl_flow_pairs(self._h, n, p0, p1, ps, int(bool(pov_mode))))
 
+    def flow_pairs_dis(self, fslot0, fslot1, flow_slots, pov_mode=False, params=None):
+        """ffl_flow_pairs_dis: DIS flow (params: DisParams, None = PRESET_FAST) + pass 1 for a batch of pairs."""
+        n = len(flow_slots)
+        (p0, k0), (p1, k1), (ps, ks) = _iarr(fslot0), _iarr(fslot1), _iarr(flow_slots)
+        if len(k0) != n or len(k1) != n:
+            raise FFLError("flow_pairs_dis: the three slot lists must have one entry per pair")
+        self._chk(self.L.ffl_flow_pairs_dis(self._h, n, p0, p1, ps, int(bool(pov_mode)),
+                                            None if params is None else C.byref(params)))
+
     def submit_pair(self, slot, prev, nxt, pov_mode=False):
         prev, nxt = np.ascontiguousarray(prev), np.ascontiguousarray(nxt)
         ch = 1 if prev.ndim == 2 else prev.shape[2]
@@ -321,6 +382,22 @@ class Context:
                                         d["flow"].ctypes.data))
         d["out"] = self.download_flow(0)
         return d
+
+    def debug_dis_pair(self, f0, f1, scale, stage, params=None):
+        """ffl_debug_dis_pair: one DIS pair, the field of (scale, stage) -- stage a DIS_STAGES name or number.  Patch
+        stages come back as (hs, ws, 2), dense ones as (lh, lw, 2), "images" as (2, lh, lw)."""
+        p = params if params is not None else DisParams()
+        st = DIS_STAGES.get(stage, stage)
+        lw, lh = self.width >> scale, self.height >> scale
+        if st in (0, 1):
+            shape = (1 + (lh - p.patch_size) // p.patch_stride, 1 + (lw - p.patch_size) // p.patch_stride, 2)
+        elif st == 4:
+            shape = (2, lh, lw)
+        else:
+            shape = (lh, lw, 2)
+        out = np.empty(shape, np.float32)
+        self._chk(self.L.ffl_debug_dis_pair(self._h, int(f0), int(f1), C.byref(p), int(scale), int(st), out.ctypes.data))
+        return out
 
     def profile_enable(self, classes=True):
         """classes: True (all), False/None (off) or an iterable of kernel-class names."""

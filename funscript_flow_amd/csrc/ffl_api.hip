@@ -1139,9 +1139,10 @@ static int enqueue_batch(ffl_ctx *c, ffl_ctx::Lane &L, const BatchTab &T, int n,
     return FFL_OK;
 }
 
-// One batch of pairs through the 4-scale Farneback schedule + pass-1 reductions, on compute lane `li`.
+// One batch of pairs through the 4-scale Farneback schedule (dis == nullptr) or the DIS path + pass-1 reductions, on
+// compute lane `li`.
 static int run_batch(ffl_ctx *c, int li, int n, const int *f0, const int *f1, const int *slots, int pov_mode,
-                     const DebugCapture *cap) {
+                     const DebugCapture *cap, const DisKParams *dis = nullptr) {
     ffl_ctx::Lane &L = c->lanes[li];
     hipStream_t st = L.st;
     const size_t N = c->N;
@@ -1181,8 +1182,13 @@ static int run_batch(ffl_ctx *c, int li, int n, const int *f0, const int *f1, co
     // stream order puts this copy behind the lane's previous batch, which reads the same device table
     HIPCHK(c, hipMemcpyAsync(L.d_tab, &T, sizeof(BatchTab), hipMemcpyHostToDevice, st));
 
-    const bool use_graph = c->opt.use_graph && !cap && c->prof_mask == 0 && c->opt.run_ahead == 0;
-    if (use_graph) {
+    const bool use_graph = c->opt.use_graph && !cap && !dis && c->prof_mask == 0 && c->opt.run_ahead == 0;
+    if (dis) {
+        // DIS batches launch eagerly (graphs stay keyed on Farneback batch shapes); scratch: the lane's first M buffer
+        ffl_launch_dis(&L.d_tab->ut, &L.d_tab->pt, n, c->d_gray, N, L.d_M[0], *dis, st);
+        ProfScope ps(c, FFL_K_PASS1, st);
+        ffl_launch_pass1(&L.d_tab->pt, n, c->w, c->h, pov_mode, L.d_pkey, L.d_psum, st);
+    } else if (use_graph) {
         ffl_ctx::Lane::GraphEntry *ge = nullptr;
         for (auto &g : L.graphs)
             if (g.n == n && g.nU == nU && g.pov == pov_mode && g.epoch == c->opt_epoch) ge = &g;
@@ -1278,6 +1284,130 @@ int ffl_flow_pairs(ffl_ctx *c, int n, const int *fslot0, const int *fslot1, cons
     HIPCHK(c, hipSetDevice(c->device));
     const int li = (int)(c->next_lane++ % c->lanes.size());
     return run_batch(c, li, n, fslot0, fslot1, flow_slots, pov_mode, nullptr);
+}
+
+// ---- DIS (kernels_dis.hip) ------------------------------------------------------------------
+
+int ffl_dis_default_params(ffl_dis_params *out) {
+    if (!out) return FFL_ERR_INVALID;
+    *out = ffl_dis_params{2, 8, 4, 16, 5, 20.0f, 10.0f, 5.0f, 1, 1, 0};
+    return FFL_OK;
+}
+
+// floats of one pair's scratch region in kernels_dis.hip (DIS_PAIR_REGION); pyramid offsets into `off` when given
+static size_t dis_pair_floats(int w, int h, int finest, int coarsest, size_t *off = nullptr, size_t *pyr = nullptr) {
+    size_t o = 0;
+    for (int s = finest; s <= coarsest; s++) {
+        if (off) off[s - finest] = o;
+        o += (size_t)(w >> s) * (h >> s);
+    }
+    if (pyr) *pyr = o;
+    return 4 * o + 20 * (size_t)(w >> finest) * (h >> finest);
+}
+
+// D2: the scales of a frame size; nullptr when supported, else the reason
+static const char *dis_geometry(int w, int h, const ffl_dis_params &p, int *coarsest) {
+    if (w < 1 || h < 1) return "empty frame";
+    if (p.patch_size != 8) return "only patch_size 8 is supported";
+    if (p.patch_stride < 1 || p.patch_stride > 8) return "patch_stride must be 1..8";
+    if (p.finest_scale < 0 || p.grad_descent_iters < 1 || p.var_refine_iters < 0 || p.stripes < 0)
+        return "finest_scale, var_refine_iters and stripes must be >= 0, grad_descent_iters >= 1";
+    const int mx = w > h ? w : h, mn = w < h ? w : h;
+    const int a = (int)(log2((double)mx / (4.0 * 8)) + 0.5), b = (int)log2((double)mn / 8);
+    const int cs = a < b ? a : b;
+    if (cs < p.finest_scale) return "the frame is too small for finest_scale";
+    if (cs - p.finest_scale + 1 > DIS_MAX_SCALES) return "too many scales";
+    if ((w % (1 << cs)) || (h % (1 << cs)))
+        return "width and height must be divisible by 2^coarsest (INTER_AREA reductions by exact integer factors only)";
+    for (int s = p.finest_scale; s <= cs; s++) {
+        const int lw = w >> s, lh = h >> s;
+        if ((lw - 8) % p.patch_stride || (lh - 8) % p.patch_stride) return "a scale is not a whole number of patch strides";
+        if ((1 + (lw - 8) / p.patch_stride) * (1 + (lh - 8) / p.patch_stride) > DIS_MAX_PATCHES) return "too many patches per scale";
+    }
+    // a pair's working set (4 pyramids of the scales + 20 planes of the finest scale, kernels_dis.hip) must fit the
+    // 5 * W * H floats per pair of a lane's first work buffer, which ffl_create sizes for Farneback
+    if (dis_pair_floats(w, h, p.finest_scale, cs) > (size_t)5 * w * h) return "the per-pair working set exceeds 5 * W * H floats";
+    *coarsest = cs;
+    return nullptr;
+}
+
+int ffl_dis_geometry(int width, int height, const ffl_dis_params *p, int *coarsest, int *finest) {
+    ffl_dis_params d;
+    ffl_dis_default_params(&d);
+    int cs = 0;
+    if (dis_geometry(width, height, p ? *p : d, &cs)) return FFL_ERR_INVALID;
+    if (coarsest) *coarsest = cs;
+    if (finest) *finest = (p ? *p : d).finest_scale;
+    return FFL_OK;
+}
+
+// kernel parameters of a DIS batch on this context, checked against the lane's scratch (ffl_create sizes nothing for DIS)
+static int dis_kparams(ffl_ctx *c, const ffl_dis_params *pp, int n, DisKParams *k) {
+    ffl_dis_params p;
+    ffl_dis_default_params(&p);
+    if (pp) p = *pp;
+    int cs = 0;
+    if (const char *why = dis_geometry(c->w, c->h, p, &cs))
+        return set_err(c, FFL_ERR_INVALID, "DIS at %dx%d: %s", c->w, c->h, why);
+    memset(k, 0, sizeof(*k));
+    k->w = c->w;
+    k->h = c->h;
+    k->finest = p.finest_scale;
+    k->coarsest = cs;
+    k->stride = p.patch_stride;
+    k->gd_iters = p.grad_descent_iters;
+    k->vr_iters = p.var_refine_iters;
+    k->mean_norm = p.use_mean_norm != 0;
+    k->spatial_prop = p.use_spatial_prop != 0;
+    k->stripes = p.stripes;
+    k->alpha = p.vr_alpha;
+    k->gamma = p.vr_gamma;
+    k->delta = p.vr_delta;
+    k->pair_floats = dis_pair_floats(c->w, c->h, p.finest_scale, cs, k->pyr_off, &k->pyr_floats);
+    const size_t have = 5 * c->N * (size_t)c->max_batch;  // one lane's d_M[0]; dis_geometry keeps a pair within 5 * N
+    if (k->pair_floats * (size_t)n > have)
+        return set_err(c, FFL_ERR_INVALID, "DIS at %dx%d, finest_scale %d: %d pairs need %zu floats of scratch, the lane has %zu",
+                       c->w, c->h, p.finest_scale, n, k->pair_floats * (size_t)n, have);
+    return FFL_OK;
+}
+
+int ffl_flow_pairs_dis(ffl_ctx *c, int n, const int *fslot0, const int *fslot1, const int *flow_slots, int pov_mode,
+                       const ffl_dis_params *p) {
+    if (!c) return FFL_ERR_INVALID;
+    CtxLock lk(c->mu);
+    int rc = check_pairs(c, n, fslot0, fslot1, flow_slots);
+    if (rc) return rc;
+    DisKParams k;
+    if ((rc = dis_kparams(c, p, n, &k))) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int li = (int)(c->next_lane++ % c->lanes.size());
+    return run_batch(c, li, n, fslot0, fslot1, flow_slots, pov_mode, nullptr, &k);
+}
+
+int ffl_debug_dis_pair(ffl_ctx *c, int f0, int f1, const ffl_dis_params *p, int scale, int stage, float *out) {
+    if (!c || !out) return FFL_ERR_INVALID;
+    CtxLock lk(c->mu);
+    int slot = 0;
+    int rc = check_pairs(c, 1, &f0, &f1, &slot);
+    if (rc) return rc;
+    DisKParams k;
+    if ((rc = dis_kparams(c, p, 1, &k))) return rc;
+    if (scale < k.finest || scale > k.coarsest || stage < 0 || stage > 4)
+        return set_err(c, FFL_ERR_INVALID, "DIS debug: scale %d (valid %d..%d) / stage %d (valid 0..4)", scale, k.finest, k.coarsest, stage);
+    const size_t lw = c->w >> scale, lh = c->h >> scale;
+    const size_t np = (size_t)(1 + (lw - 8) / k.stride) * (1 + (lh - 8) / k.stride);
+    const size_t floats = stage <= 1 ? 2 * np : 2 * lw * lh;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMalloc(&k.dbg, sizeof(float) * floats));
+    k.dbg_scale = scale;
+    k.dbg_stage = stage;
+    rc = run_batch(c, 0, 1, &f0, &f1, &slot, 0, nullptr, &k);
+    hipError_t e = rc ? hipSuccess : hipStreamSynchronize(c->lanes[0].st);
+    if (!rc && e == hipSuccess) e = hipMemcpy(out, k.dbg, sizeof(float) * floats, hipMemcpyDeviceToHost);
+    hipFree(k.dbg);
+    if (rc) return rc;
+    HIPCHK(c, e);
+    return FFL_OK;
 }
 
 int ffl_debug_pair(ffl_ctx *c, int f0, int f1, int level, int iter, float *I0, float *I1, float *R0, float *R1,

@@ -139,6 +139,23 @@ void ffl_launch_blur_solve_first(float *Mout, size_t M_stride, const float *R, s
                                  const PairTab *pt, int level, int nB, int lw, int lh, int pw, int ph, const FflOptions &opt,
                                  hipStream_t st);
 
+// ---- DIS (kernels_dis.hip) ----------------------------------------------------------------
+#define DIS_MAX_PATCHES 4096   // patch flows of one scale in LDS (float2 each)
+#define DIS_MAX_SCALES 12
+struct DisKParams {
+    int w, h, finest, coarsest, stride, gd_iters, vr_iters, mean_norm, spatial_prop, stripes;
+    float alpha, gamma, delta;
+    size_t pair_floats;              // per-pair scratch region (floats)
+    size_t pyr_floats;               // floats of one pyramid (scales finest..coarsest)
+    size_t pyr_off[DIS_MAX_SCALES];  // offset of scale finest + i inside a pyramid
+    float *dbg;                      // ffl_debug_dis_pair: pair 0's field of (dbg_scale, dbg_stage), else nullptr
+    int dbg_scale, dbg_stage;
+};
+// one workgroup per pair: pyramid, patch search, densification, refinement per scale, then the full-size field into
+// pt->flow[0][b]; `scratch` holds nB regions of p.pair_floats floats
+void ffl_launch_dis(const UTab *ut, const PairTab *pt, int nB, const uint8_t *gray, size_t gray_stride, float *scratch,
+                    const DisKParams &p, hipStream_t st);
+
 int ffl_pass1_blocks(int w, int h);
 // pass 1 of the level-0 flows pt->flow[0][b]; records go to pt->res[b]
 void ffl_launch_pass1(const PairTab *pt, int nB, int w, int h, int pov_mode, unsigned long long *pkey, double *psum,

@@ -14,6 +14,8 @@ rank under contiguous blocks (`process_chunk_sharded_halo`, the streaming form).
 """
 import numpy as np
 
+from . import _capi
+
 SMOOTH_RADIUS = 6  # FF:1206 range(1, 7)
 
 
@@ -78,14 +80,19 @@ class PairEngine:
     of pairs <= j+6 are known (or the chunk has ended), after which its flow slot is recycled.
     """
 
-    def __init__(self, ctx, upload=None, depth=None):
+    def __init__(self, ctx, upload=None, depth=None, flow="farneback", dis=None):
         """`upload(first_slot, frames)` puts a run of frames into consecutive frame slots; the default takes
         gray (or same-size BGR) operands, frontend.DecodedUploader takes frames as decoded (any size).
         `depth`: batches queued on the device before the oldest one's results are collected (default: 2 when the
         context has the slots for it -- 3B + 3 frame slots, 3B + 13 flow slots -- else 1).  With depth 2 the upload of
         batch s + 2 is already queued while batch s computes, so a slow transfer or a host hiccup does not idle the device;
         a third batch queued ahead measures within 1 % of two at 1080p and at 256x256 (profiles/r04_pcie_chunk_length.txt).
-        Results do not depend on it."""
+        Results do not depend on it.
+        `flow`: "farneback" (ffl_flow_pairs) or "dis" (ffl_flow_pairs_dis with the _capi.DisParams `dis`, None = PRESET_FAST)
+        for every batch the engine queues."""
+        if flow not in _capi.FLOWS:
+            raise ValueError(f"flow must be one of {_capi.FLOWS}, got {flow!r}")
+        self.flow, self.dis = flow, dis
         self.ctx = ctx
         self.upload = upload or ctx.upload_frames
         self.B = ctx.max_batch
@@ -102,21 +109,23 @@ class PairEngine:
             raise ValueError(f"context too small: need frame_slots >= 2B+2 = {2 * self.B + 2} and "
                              f"flow_slots >= 2B+13 = {min_flow_slots(self.B)}")
 
-    def pass1(self, frames, pair_lo, pair_hi, pov_mode=False, cut_threshold=7.0, on_batch=None):
+    def pass1(self, frames, pair_lo, pair_hi, pov_mode=False, cut_threshold=7.0, on_batch=None, algo=None):
         """Run pass 1 for pairs [pair_lo, pair_hi) of `frames`; flows stay resident in slot
         (j - pair_lo) % flow_slots.  Returns the list of (x, y, val, mean_mag, cut)."""
         fs = self.ctx.flow_slots
         return self.pass1_pairs(frames, range(pair_lo, pair_hi), lambda l: l % fs, pov_mode, cut_threshold,
-                                on_batch=(lambda ls, js, got: on_batch(js, got)) if on_batch else None)
+                                on_batch=(lambda ls, js, got: on_batch(js, got)) if on_batch else None, algo=algo)
 
-    def pass1_pairs(self, frames, pairs, slot_of, pov_mode=False, cut_threshold=7.0, on_batch=None):
+    def pass1_pairs(self, frames, pairs, slot_of, pov_mode=False, cut_threshold=7.0, on_batch=None, algo=None):
         """Pass 1 for an arbitrary ascending list of pair indices (pair j = frames[j], frames[j+1]) in batches of
         max_batch; the flow of the l-th listed pair stays resident in flow slot slot_of(l).  Frames go to the
         device once per run of batches that needs them: a ring over the frame slots, frames of the batch being
         assembled are never evicted, and runs of consecutive frames landing in consecutive slots go up with one
         H2D transfer.  (The library orders an upload into a recycled slot behind the batches that still read
-        it.)  on_batch(local_indices, pair_indices, records) is called per finished batch."""
+        it.)  on_batch(local_indices, pair_indices, records) is called per finished batch.  `algo` = (flow, dis) as
+        _capi.flow_choice returns it overrides the engine's own flow algorithm for this call only."""
         ctx, B, S = self.ctx, self.B, self.ctx.frame_slots
+        algo, dis = algo if algo is not None else (getattr(self, "flow", "farneback"), getattr(self, "dis", None))
         pairs = [int(j) for j in pairs]
         recs = [None] * len(pairs)
         resident, owner, state = {}, [None] * S, {"next": 0}
@@ -149,7 +158,11 @@ class PairEngine:
             ls = list(range(l0, min(l0 + B, len(pairs))))
             js = [pairs[l] for l in ls]
             stage(sorted({j for j in js} | {j + 1 for j in js}))
-            ctx.flow_pairs([resident[j] for j in js], [resident[j + 1] for j in js], [slot_of(l) for l in ls], pov_mode)
+            f0, f1, fl = [resident[j] for j in js], [resident[j + 1] for j in js], [slot_of(l) for l in ls]
+            if algo == "dis":
+                ctx.flow_pairs_dis(f0, f1, fl, pov_mode, dis)
+            else:
+                ctx.flow_pairs(f0, f1, fl, pov_mode)
             return ls, js
 
         release = getattr(frames, "release", None)  # prefetch.PrefetchRing views: frames may be recycled once consumed
@@ -173,8 +186,9 @@ class PairEngine:
             collect(*pending.pop(0))
         return recs
 
-    def process_chunk(self, frames, pov_mode=False, cut_threshold=7.0):
-        """One whole chunk on one GPU: returns (dots float64[n], records) with n = len(frames)-1."""
+    def process_chunk(self, frames, pov_mode=False, cut_threshold=7.0, algo=None):
+        """One whole chunk on one GPU: returns (dots float64[n], records) with n = len(frames)-1.  `algo`: see
+        pass1_pairs (None: the engine's own flow algorithm)."""
         ctx, B = self.ctx, self.B
         n = len(frames) - 1
         if n < 1:
@@ -204,7 +218,7 @@ class PairEngine:
             state["known"] = js[-1] + 1
             finalize(n if state["known"] == n else max(0, state["known"] - SMOOTH_RADIUS))
 
-        self.pass1(frames, 0, n, pov_mode, cut_threshold, on_batch)
+        self.pass1(frames, 0, n, pov_mode, cut_threshold, on_batch, algo=algo)
         finalize(n)
         return dots, recs_all
 
@@ -214,6 +228,9 @@ def frames_to_actions(engine, frames, fps, params):
     sampling to keyframes (FF:1127-1385) with the HIP pair engine in the middle.  `frames` holds every
     decoded frame (any sequence); chunking follows FF:1145-1153 (pairs never span chunks, F10)."""
     from . import postchain
+    # params["hip_flow"] / ["hip_dis"] pick the flow algorithm for this call (the engine itself is left as it is); without
+    # them the engine's own algorithm runs
+    algo = _capi.flow_choice(params) if ("hip_flow" in params or "hip_dis" in params) else None
     step, _, indices = postchain.sampling(fps, len(frames))
     bracket = int(params.get("batch_size", 3000.0))
     dots, cuts, frame_idx = [], [], []
@@ -222,7 +239,7 @@ def frames_to_actions(engine, frames, fps, params):
         if len(chunk) < 2:
             continue
         d, recs = engine.process_chunk([frames[i] for i in chunk], bool(params.get("pov_mode", False)),
-                                       float(params.get("cut_threshold", 7)))
+                                       float(params.get("cut_threshold", 7)), **({"algo": algo} if algo is not None else {}))
         dots += [float(v) for v in d]
         cuts += [bool(r[4]) for r in recs]
         frame_idx += chunk[:-1]

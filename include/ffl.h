@@ -24,6 +24,9 @@
  *                           for a batch (ProcessPoolExecutor.submit loop, FF:1232-1236)
  *   ffl_download_flow       the "flow" entry of that dict (tests / callers that want the array)
  *   ffl_submit_pair         precompute_wrapper((p0, p1), params)                    FF:1019-1021
+ *   ffl_flow_pairs_dis      cv2.DISOpticalFlow_create(cv2.DISOPTICAL_FLOW_PRESET_FAST).calc(p0, p1, None)
+ *                           + max_divergence + cartToPolar of the "DNN" backend     FF:948-980
+ *                           (rules restated in DESIGN.md appendix D; parity with cv2 itself is unpinned)
  *
  * Threading: a context is bound to one device and is internally stream-ordered.  Every entry point locks the
  * context, so calls may come from several host threads (an uploader, a submitter and a result collector working
@@ -150,6 +153,36 @@ int ffl_submit_pair(ffl_ctx *ctx, int slot, const uint8_t *prev, const uint8_t *
 
 /* Block until everything queued on the context has finished. */
 int ffl_sync(ffl_ctx *ctx);
+
+/* ---- DIS optical flow (the reference's "DNN" backend, FF:948-980; DESIGN.md "DIS path") ------------------------- */
+
+/* Parameters of the DIS path.  Everything that changes results is here (never in ffl_set_option). */
+typedef struct ffl_dis_params {
+    int finest_scale, patch_size, patch_stride, grad_descent_iters, var_refine_iters;
+    float vr_alpha, vr_gamma, vr_delta;
+    int use_mean_norm, use_spatial_prop, stripes; /* stripes: 0 = one patch row per stripe */
+} ffl_dis_params;
+
+/* PRESET_FAST: finest 2, patch 8, stride 4, 16 descent iterations, 5 refinement iterations, alpha 20, gamma 10,
+ * delta 5, mean normalisation and spatial propagation on, stripes 0. */
+int ffl_dis_default_params(ffl_dis_params *out);
+
+/* Scales of a width x height frame under p.  FFL_ERR_INVALID (with a message) when the size or the parameters are not
+ * supported: only patch_size 8; coarsest = min((int)(log2(max(W,H) / 32) + 0.5), (int)log2(min(W,H) / 8)) must be
+ * >= finest_scale, W and H divisible by 2^coarsest (every INTER_AREA reduction an exact integer factor), and every
+ * scale a whole number of patch strides.  256x256 and 512x512 are supported; 640x360 and 1920x1080 are not. */
+int ffl_dis_geometry(int width, int height, const ffl_dis_params *p, int *coarsest, int *finest);
+
+/* Queue DIS flow + the same pass-1 reductions as ffl_flow_pairs for n pairs (same slot tables, events and result
+ * calls; p == NULL: PRESET_FAST).  Asynchronous.  Batches are launched eagerly (never from a captured graph). */
+int ffl_flow_pairs_dis(ffl_ctx *ctx, int n, const int *fslot0, const int *fslot1, const int *flow_slots, int pov_mode,
+                       const ffl_dis_params *p);
+
+/* Test hook: run ONE DIS pair (frame slots f0, f1) and copy one intermediate of scale `scale` to `out`:
+ * stage 0 patch flows after pass 1, 1 after pass 2 (hs x ws x 2 floats), 2 the densified field, 3 the field after
+ * variational refinement (lh x lw x 2), 4 the two level images I0, I1 (2 x lh x lw).  The final flow goes to flow
+ * slot 0.  Synchronous. */
+int ffl_debug_dis_pair(ffl_ctx *ctx, int f0, int f1, const ffl_dis_params *p, int scale, int stage, float *out);
 
 /* ---- parity-test hooks (used by tests/ only) ------------------------------------------------ */
 
