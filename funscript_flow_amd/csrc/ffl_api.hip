@@ -16,6 +16,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
 #include <condition_variable>
 #include <mutex>
 #include <string>
@@ -51,12 +52,15 @@ static std::mutex g_opt_mu;
 // for correctness, since "later work of the same stream" is a conservative wait, but not for speed: with 131 or 132 frame
 // slots at B = 32 a slot's last-use handle of the OTHER lane went 33 batches without being refreshed, and from the moment
 // the lanes' 16-entry rings wrapped every upload waited for the batch in flight: 5.1 -> 8.9 ms per batch from batch 33 on,
-// profiles/r04_pcie_chunk_length.txt.)  So: take() waits on the host for the entry it is about to hand out again -- that
+// profiles/r04_pcie_chunk_length.txt.)  So: record() waits on the host for the entry it is about to hand out again -- that
 // operation is `size` operations old and practically always long finished -- which makes "stale" imply "completed", and
-// EvRef::get() answers nullptr for a stale reference: nothing to wait for.
+// EvRef::get() answers nullptr for a stale reference: nothing to wait for.  A ticket is handed out only once its entry has
+// been recorded, so no reference ever names an entry that still holds an older operation.
+struct EvRef;
 struct EvRing {
     std::vector<hipEvent_t> ev;
-    unsigned long long next = 0;  // tickets handed out so far
+    unsigned long long next = 0;     // tickets handed out so far
+    unsigned long long settled = 0;  // settle_next() has succeeded for every ticket below this
     hipError_t create(int n) {
         ev.assign(n, nullptr);
         for (auto &e : ev) {
@@ -70,12 +74,16 @@ struct EvRing {
             if (e) hipEventDestroy(e);
         ev.clear();
     }
-    // the entry the next take() hands out: its previous operation (`size` operations ago) must be over
-    hipError_t settle_next() { return next >= ev.size() ? hipEventSynchronize(ev[next % ev.size()]) : hipSuccess; }
-    hipEvent_t take(unsigned long long *ticket) {
-        *ticket = next;
-        return ev[next++ % ev.size()];
+    // the entry the next record() hands out: its previous operation (`size` operations ago) must be over.  Waits at most
+    // once per ticket, so a caller may settle early (run_batch, before it writes the entry's table) and record later.
+    hipError_t settle_next() {
+        if (next < ev.size() || next < settled) return hipSuccess;
+        const hipError_t r = hipEventSynchronize(ev[next % ev.size()]);
+        if (r == hipSuccess) settled = next + 1;
+        return r;
     }
+    // the next entry recorded on `st`; *out names it and `next` advances only once the record has succeeded
+    hipError_t record(hipStream_t st, EvRef *out);
 };
 struct EvRef {
     const EvRing *ring = nullptr;
@@ -83,6 +91,12 @@ struct EvRef {
     // the event to wait on, or nullptr when there is nothing (never set, or the entry has been handed out again: completed)
     hipEvent_t get() const { return (ring && ring->next - ticket <= ring->ev.size()) ? ring->ev[ticket % ring->ev.size()] : nullptr; }
 };
+inline hipError_t EvRing::record(hipStream_t st, EvRef *out) {
+    hipError_t r = settle_next();
+    if (r == hipSuccess) r = hipEventRecord(ev[next % ev.size()], st);
+    if (r == hipSuccess) *out = EvRef{this, next++};
+    return r;
+}
 static inline EvRef ev_latest(const EvRing &r) { return r.next ? EvRef{&r, r.next - 1} : EvRef{}; }
 
 struct ProfRec {
@@ -264,8 +278,7 @@ struct ffl_ctx {
     Pass1Result *h_res = nullptr;     // pinned [n_slots]
     Pass1Result *d_res = nullptr;     // device alias of h_res
     std::vector<EvRef> ev_slot_done;  // per flow slot: the batch (a lane's ring) or pass-2 / flow-upload call (post_ring) that used it last
-    std::vector<char> slot_state;     // 0 empty, 1 queued/ready
-    std::vector<char> slot_pov;
+    std::vector<char> slot_state;     // 1: queued/ready, 0: empty or its batch failed
     RadialTab *d_rtab = nullptr, *h_rtab = nullptr;    // pass-2 table (s_post; ffl_radial waits for the stream, so one copy)
     BatchTab *d_ptab = nullptr, *h_ptab = nullptr;     // ffl_upload_flow's one-pair table (s_post)
     double *d_rpsum = nullptr;                         // pass-2 partial sums (s_post)
@@ -285,19 +298,16 @@ struct ffl_ctx {
     int prof_launches[FFL_K_COUNT] = {0};
     double prof_ms[FFL_K_COUNT] = {0};
     std::string err;
-    // Every entry point takes this lock, so calls from several host threads are safe.  The calls a pipeline makes per
-    // batch do not hold it while they wait for the device or copy frames: ffl_pass1_result, ffl_download_flow, ffl_radial,
-    // ffl_upload_flow, ffl_sync and ffl_host_free drop it around their waits, ffl_upload_frames(_raw) around the staging
-    // memcpy -- so a thread collecting results does not hold up another one that is uploading frames or queueing the next
-    // batch (submit / pass1 / radial on distinct slots may come from different host threads).  Exceptions, all
-    // rare or measurement-only: ffl_flow_pairs waits under the lock when a lane has FFL_EV_RING batches queued (its table
-    // ring is full) or evicts a captured graph (the 17th batch shape of a lane); ffl_debug_pair and ffl_download_frame
-    // are test hooks and wait under it; ffl_profile_read collects its timing events under it.
-    // A wait that runs WITHOUT the lock only ever waits on EVENTS, never on a lane's stream: another thread may be inside
+    // Every entry point takes this lock, so calls from several host threads are safe (submit / pass1 / radial on
+    // distinct slots may come from different host threads).  The rule: a host wait for the device runs WITHOUT the lock,
+    // through wait_unlocked(), and only ever waits on EVENTS, never on a lane's stream -- another thread may be inside
     // hipStreamBeginCapture / EndCapture on that stream (a new batch shape), and synchronising a capturing stream is an
-    // error that also invalidates the capture; hipEventSynchronize on an event recorded outside the capture is legal.
+    // error that also invalidates the capture; hipEventSynchronize on an event recorded outside the capture is legal.  The
+    // staging memcpy of the uploads and the waits for streams `copy` and `post`, on which nothing is captured, also run
+    // without it.  A wait under the lock is rare or a test hook: a ring's settle_next() (its entry is FFL_EV_RING
+    // operations old), the eviction of a captured graph, ffl_debug_pair, ffl_download_frame and ffl_profile_read.
     // Two small locks order the users of shared single-copy resources among themselves; both are taken BEFORE `mu`, and
-    // up_mu before post_mu where a call needs both (ffl_sync):
+    // up_mu before post_mu where a call needs both (ffl_sync, which releases them before it waits):
     //   up_mu    uploaders: the per-slot staging areas, the copy pool and the raw-frame ring
     //   post_mu  users of stream `post` and its single pinned tables / result buffer (ffl_radial, ffl_upload_flow)
     mutable std::recursive_mutex mu;
@@ -508,6 +518,48 @@ struct WaitOnce {
     }
 };
 
+// The host wait of every entry point (the lock rule at ffl_ctx::mu): every non-null event of evs[0..n) is waited for
+// WITHOUT the context lock, which is held again on return.  A handle may be re-recorded meanwhile by another thread, but a
+// ring entry is only ever re-recorded for LATER work of its stream, so the wait stays sufficient.
+static int wait_unlocked(ffl_ctx *c, CtxLock &lk, const hipEvent_t *evs, int n) {
+    HIPCHK(c, hipSetDevice(c->device));
+    lk.unlock();
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < n && e == hipSuccess; i++)
+        if (evs[i]) e = hipEventSynchronize(evs[i]);
+    lk.lock();
+    if (e != hipSuccess) return set_err(c, FFL_ERR_HIP, "hipEventSynchronize failed: %s", hipGetErrorString(e));
+    return FFL_OK;
+}
+
+// Stream `copy` waits for the batches (of every lane) that may still read frame slot fs, before a transfer overwrites it.
+static int wait_frame_free(ffl_ctx *c, WaitOnce &wait_copy, int fs) {
+    const size_t nl = c->lanes.size();
+    for (size_t l = 0; l < nl; l++) HIPCHK(c, wait_copy(c->ev_last_use[(size_t)fs * nl + l].get()));
+    return FFL_OK;
+}
+
+// The end of an upload call: ONE event on stream `copy` for frame slots first..first+n-1.  A transfer into a slot may still
+// be in flight out of the slot's staging area; the new event is later on the same stream, so waiting on it covers that too.
+static int publish_frames(ffl_ctx *c, int first, int n) {
+    EvRef ev;
+    HIPCHK(c, c->up_ring.record(c->s_copy, &ev));  // the entry is 32 upload calls old: over long ago
+    for (int i = first; i < first + n; i++) {
+        c->ev_uploaded[i] = ev;
+        c->frame_valid[i] = 1;
+    }
+    return FFL_OK;
+}
+
+// Flow slots written by the operation `done` (a batch or ffl_upload_flow): reuse of a slot waits for it, and `ready`
+// says whether the slot holds a result once it has completed.
+static void publish_slots(ffl_ctx *c, int n, const int *slots, EvRef done, bool ready) {
+    for (int i = 0; i < n; i++) {
+        c->ev_slot_done[slots[i]] = done;
+        c->slot_state[slots[i]] = ready;
+    }
+}
+
 // ---- API -----------------------------------------------------------------------------------------
 extern "C" {
 
@@ -692,7 +744,6 @@ int ffl_create(int device, int width, int height, int n_frame_slots, int n_flow_
     CCHK(c->post_ring.create(FFL_EV_RING));
     c->ev_slot_done.assign(n_flow_slots, EvRef{});                        // set when a slot is queued
     c->slot_state.assign(n_flow_slots, 0);
-    c->slot_pov.assign(n_flow_slots, 0);
 #undef CCHK
     *out = c;
     return FFL_OK;
@@ -823,7 +874,7 @@ int ffl_upload_frames(ffl_ctx *c, int first, int n, const uint8_t *const *frames
         // must be ordered ahead of the transfer that overwrites its frame
         WaitOnce wait_copy(c->s_copy);
         for (int i = i0; i < i1; i++)
-            for (size_t l = 0; l < c->lanes.size(); l++) HIPCHK(c, wait_copy(c->ev_last_use[(size_t)(first + i) * c->lanes.size() + l].get()));
+            if (int rc = wait_frame_free(c, wait_copy, first + i)) return rc;
         uint8_t *gray = c->d_gray + (size_t)(first + i0) * N;
         const uint8_t *src = (direct ? frames[0] : stage0) + (size_t)i0 * fbytes;
         const int m = i1 - i0;
@@ -860,26 +911,16 @@ int ffl_upload_frames(ffl_ctx *c, int first, int n, const uint8_t *const *frames
                 hipEvent_t e = c->ev_uploaded[first + k].get();
                 if (e && (prev.empty() || prev.back() != e)) prev.push_back(e);
             }
-            lk.unlock();
-            hipError_t pe = hipSuccess;
-            for (auto e : prev)
-                if (pe == hipSuccess) pe = hipEventSynchronize(e);
-            if (pe == hipSuccess) c->pool.copy(stage0 + (size_t)i * fbytes, frames + i, j - i, stride_bytes, row, height, copy_threads);
-            lk.lock();
-            HIPCHK(c, pe);
-            int rc = send(i, j);
+            int rc = wait_unlocked(c, lk, prev.data(), (int)prev.size());
             if (rc) return rc;
+            lk.unlock();
+            c->pool.copy(stage0 + (size_t)i * fbytes, frames + i, j - i, stride_bytes, row, height, copy_threads);
+            lk.lock();
+            if ((rc = send(i, j))) return rc;
             i = j;
         }
     }
-    HIPCHK(c, c->up_ring.settle_next());  // 32 upload calls old: over long ago
-    EvRef ref{&c->up_ring, 0};
-    HIPCHK(c, hipEventRecord(c->up_ring.take(&ref.ticket), c->s_copy));
-    for (int i = 0; i < n; i++) {
-        c->ev_uploaded[first + i] = ref;
-        c->frame_valid[first + i] = 1;
-    }
-    return FFL_OK;
+    return publish_frames(c, first, n);
 }
 
 // Decoded frames -> gray frame slots through k_frontend (resize + crop + luma in one pass).  Frame by
@@ -916,11 +957,8 @@ int ffl_upload_frames_raw(ffl_ctx *c, int first, int n, const uint8_t *const *fr
     for (int i = 0; i < n; i++) {
         const int fs = first + i;
         auto &rb = c->raw[c->raw_next++ % FFL_RAW_RING];
-        if (rb.busy) {  // its previous frame has left both buffers (waited for without the context lock)
-            lk.unlock();
-            hipError_t be = hipEventSynchronize(rb.ev);
-            lk.lock();
-            HIPCHK(c, be);
+        if (rb.busy) {  // its previous frame has left both buffers
+            if (int rc = wait_unlocked(c, lk, &rb.ev, 1)) return rc;
         }
         if (rb.cap < fbytes) {
             hipFree(rb.d);
@@ -941,10 +979,9 @@ int ffl_upload_frames_raw(ffl_ctx *c, int first, int n, const uint8_t *const *fr
             c->pool.copy(rb.h, &data, 1, stride_bytes, fp.stride, sh, copy_threads);
             lk.lock();
         }
-        for (size_t l = 0; l < c->lanes.size(); l++) {  // batches still reading the slot's previous frame
-            hipEvent_t e = c->ev_last_use[(size_t)fs * c->lanes.size() + l].get();
-            if (e) HIPCHK(c, hipStreamWaitEvent(c->s_copy, e, 0));
-        }
+        // looked up under the lock, after the staging copy: a batch queued meanwhile is ordered ahead of the transfer
+        WaitOnce wait_copy(c->s_copy);
+        if (int rc = wait_frame_free(c, wait_copy, fs)) return rc;
         HIPCHK(c, hipMemcpyAsync(rb.d, direct ? data : rb.h, fbytes, hipMemcpyHostToDevice, c->s_copy));
         {
             ProfScope ps(c, FFL_K_FRONTEND, c->s_copy);
@@ -953,16 +990,7 @@ int ffl_upload_frames_raw(ffl_ctx *c, int first, int n, const uint8_t *const *fr
         HIPCHK(c, hipEventRecord(rb.ev, c->s_copy));
         rb.busy = true;
     }
-    HIPCHK(c, c->up_ring.settle_next());
-    EvRef ev{&c->up_ring, 0};
-    HIPCHK(c, hipEventRecord(c->up_ring.take(&ev.ticket), c->s_copy));
-    for (int i = 0; i < n; i++) {
-        // a gray upload into this slot may still be in flight out of the slot's own staging area; the new
-        // handle is later on the same stream, so waiting on it covers that transfer as well
-        c->ev_uploaded[first + i] = ev;
-        c->frame_valid[first + i] = 1;
-    }
-    return FFL_OK;
+    return publish_frames(c, first, n);
 }
 
 int ffl_upload_frame(ffl_ctx *c, int fslot, const uint8_t *data, int width, int height, int channels,
@@ -1139,17 +1167,59 @@ static int enqueue_batch(ffl_ctx *c, ffl_ctx::Lane &L, const BatchTab &T, int n,
     return FFL_OK;
 }
 
-// One batch of pairs through the 4-scale Farneback schedule (dis == nullptr) or the DIS path + pass-1 reductions, on
-// compute lane `li`.
-static int run_batch(ffl_ctx *c, int li, int n, const int *f0, const int *f1, const int *slots, int pov_mode,
-                     const DebugCapture *cap, const DisKParams *dis = nullptr) {
-    ffl_ctx::Lane &L = c->lanes[li];
+// The lane's captured graph of a batch shape under the current options (*ge), captured now if there is none yet; *ge stays
+// nullptr when this option epoch launches eagerly after a failed capture.  The capture records the kernels only: the
+// waits and the table copy are queued on the stream before it.
+static int batch_graph(ffl_ctx *c, ffl_ctx::Lane &L, const BatchTab &T, int n, int nU, int pov_mode,
+                       ffl_ctx::Lane::GraphEntry **ge) {
+    *ge = nullptr;
+    for (auto &g : L.graphs)
+        if (g.n == n && g.nU == nU && g.pov == pov_mode && g.epoch == c->opt_epoch) *ge = &g;
+    if (*ge || c->graph_bad_epoch == c->opt_epoch) return FFL_OK;
+    hipStream_t st = L.st;
+    ffl_ctx::Lane::GraphEntry g = {n, nU, pov_mode, c->opt_epoch, nullptr, nullptr};
+    hipError_t fail = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
+    if (fail == hipSuccess) {
+        const int rc = enqueue_batch(c, L, T, n, nU, pov_mode, nullptr);
+        fail = hipStreamEndCapture(st, &g.graph);  // always: the stream must leave capture mode
+        if (fail == hipSuccess && (rc != FFL_OK || !g.graph)) fail = hipErrorStreamCaptureInvalidated;
+        if (fail == hipSuccess) fail = hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0);
+    }
+    if (fail != hipSuccess) {
+        // nothing of the failed capture is kept (it would leak once per batch), the sticky error is cleared, and
+        // this context launches eagerly until the option set changes -- the batch itself is not lost
+        if (g.exec) hipGraphExecDestroy(g.exec);
+        if (g.graph) hipGraphDestroy(g.graph);
+        (void)hipGetLastError();
+        c->graph_bad_epoch = c->opt_epoch;
+        // never silent: counted (ffl_graph_stats, bench.py `config.graphs`) and said once per context on stderr
+        c->graph_failed++;
+        if (!c->graph_fail_reported) {
+            c->graph_fail_reported = true;
+            fprintf(stderr, "libffl_hip: hipGraph capture of a %d-pair batch failed (%s); this context launches its batches "
+                            "one kernel at a time until its options change (results are unaffected)\n", n, hipGetErrorString(fail));
+        }
+        return FFL_OK;
+    }
+    if (L.graphs.size() >= 16) {  // bounded cache: callers that vary the batch shape a lot re-capture
+        // a replay may still be queued: graph resources are released once the lane's stream has drained
+        HIPCHK(c, hipStreamSynchronize(st));
+        hipGraphExecDestroy(L.graphs.front().exec);
+        hipGraphDestroy(L.graphs.front().graph);
+        L.graphs.erase(L.graphs.begin());
+    }
+    L.graphs.push_back(g);
+    *ge = &L.graphs.back();
+    c->graph_captured++;
+    return FFL_OK;
+}
+
+// Fills the batch's table T (*nU unique frames) and queues the batch on the lane's stream: the waits for its frames and
+// recycled slots, the table copy, the launches.  Once the table is filled, a failure may leave part of the batch queued.
+static int queue_batch(ffl_ctx *c, ffl_ctx::Lane &L, BatchTab &T, int *nU_out, int n, const int *f0, const int *f1,
+                       const int *slots, int pov_mode, const DebugCapture *cap, const DisKParams *dis) {
     hipStream_t st = L.st;
     const size_t N = c->N;
-    // the batch's table: a pinned ring entry (its previous batch, FFL_EV_RING batches ago, must have consumed it)
-    const unsigned e = (unsigned)(L.ring.next % FFL_EV_RING);
-    HIPCHK(c, L.ring.settle_next());  // also frees the table entry: its batch, FFL_EV_RING batches ago, has consumed it
-    BatchTab &T = L.h_tab[e];
     int nU = 0;
     auto uidx = [&](int fs) {  // O(1) through the context's scratch map (a linear search cost 65 k compares per 256-pair batch)
         int &u = c->u_of_fslot[fs];
@@ -1174,86 +1244,54 @@ static int run_batch(ffl_ctx *c, int li, int n, const int *f0, const int *f1, co
     for (int k = c->levels + 1; k < FFL_MAX_LEVELS; k++)
         for (int i = 0; i < n; i++) T.pt.flow[k][i] = nullptr;
     for (int i = 0; i < nU; i++) c->u_of_fslot[T.ut.fslot[i]] = -1;  // the scratch map goes back to "empty"
+    *nU_out = nU;
     WaitOnce wait(st);
     for (int i = 0; i < nU; i++) HIPCHK(c, wait(c->ev_uploaded[T.ut.fslot[i]].get()));
     // a flow slot being recycled may still be read by the batch (other lane) or pass 2 that used it last
-    for (int i = 0; i < n; i++)
-        if (c->slot_state[slots[i]]) HIPCHK(c, wait(c->ev_slot_done[slots[i]].get()));
+    for (int i = 0; i < n; i++) HIPCHK(c, wait(c->ev_slot_done[slots[i]].get()));
     // stream order puts this copy behind the lane's previous batch, which reads the same device table
     HIPCHK(c, hipMemcpyAsync(L.d_tab, &T, sizeof(BatchTab), hipMemcpyHostToDevice, st));
 
-    const bool use_graph = c->opt.use_graph && !cap && !dis && c->prof_mask == 0 && c->opt.run_ahead == 0;
     if (dis) {
         // DIS batches launch eagerly (graphs stay keyed on Farneback batch shapes); scratch: the lane's first M buffer
         ffl_launch_dis(&L.d_tab->ut, &L.d_tab->pt, n, c->d_gray, N, L.d_M[0], *dis, st);
         ProfScope ps(c, FFL_K_PASS1, st);
         ffl_launch_pass1(&L.d_tab->pt, n, c->w, c->h, pov_mode, L.d_pkey, L.d_psum, st);
-    } else if (use_graph) {
-        ffl_ctx::Lane::GraphEntry *ge = nullptr;
-        for (auto &g : L.graphs)
-            if (g.n == n && g.nU == nU && g.pov == pov_mode && g.epoch == c->opt_epoch) ge = &g;
-        if (!ge && c->graph_bad_epoch != c->opt_epoch) {
-            ffl_ctx::Lane::GraphEntry g = {n, nU, pov_mode, c->opt_epoch, nullptr, nullptr};
-            hipError_t fail = hipSuccess;
-            fail = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-            bool ok = fail == hipSuccess;
-            if (ok) {
-                const int rc = enqueue_batch(c, L, T, n, nU, pov_mode, nullptr);
-                fail = hipStreamEndCapture(st, &g.graph);  // always: the stream must leave capture mode
-                if (fail == hipSuccess && (rc != FFL_OK || !g.graph)) fail = hipErrorStreamCaptureInvalidated;
-                if (fail == hipSuccess) fail = hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0);
-                ok = fail == hipSuccess;
-            }
-            if (ok) {
-                if (L.graphs.size() >= 16) {  // bounded cache: callers that vary the batch shape a lot re-capture
-                    // a replay may still be queued: graph resources are released once the lane's stream has drained
-                    HIPCHK(c, hipStreamSynchronize(st));
-                    hipGraphExecDestroy(L.graphs.front().exec);
-                    hipGraphDestroy(L.graphs.front().graph);
-                    L.graphs.erase(L.graphs.begin());
-                }
-                L.graphs.push_back(g);
-                ge = &L.graphs.back();
-                c->graph_captured++;
-            } else {
-                // nothing of the failed capture is kept (it would leak once per batch), the sticky error is cleared, and
-                // this context launches eagerly until the option set changes -- the batch itself is not lost
-                if (g.exec) hipGraphExecDestroy(g.exec);
-                if (g.graph) hipGraphDestroy(g.graph);
-                (void)hipGetLastError();
-                c->graph_bad_epoch = c->opt_epoch;
-                // never silent: counted (ffl_graph_stats, bench.py `config.graphs`) and said once per context on stderr
-                c->graph_failed++;
-                if (!c->graph_fail_reported) {
-                    c->graph_fail_reported = true;
-                    fprintf(stderr, "libffl_hip: hipGraph capture of a %d-pair batch failed (%s); this context launches its batches "
-                                    "one kernel at a time until its options change (results are unaffected)\n", n, hipGetErrorString(fail));
-                }
-            }
-        }
+    } else if (c->opt.use_graph && !cap && c->prof_mask == 0 && c->opt.run_ahead == 0) {
+        ffl_ctx::Lane::GraphEntry *ge;
+        if (int rc = batch_graph(c, L, T, n, nU, pov_mode, &ge)) return rc;
         if (ge) {
             HIPCHK(c, hipGraphLaunch(ge->exec, st));
             c->graph_replayed++;
-        } else {
-            int rc = enqueue_batch(c, L, T, n, nU, pov_mode, nullptr);
-            if (rc) return rc;
+        } else if (int rc = enqueue_batch(c, L, T, n, nU, pov_mode, nullptr)) {
+            return rc;
         }
-    } else {
-        int rc = enqueue_batch(c, L, T, n, nU, pov_mode, cap);
-        if (rc) return rc;
-    }
-    // ONE event per batch: it marks the slots' results as ready, the frames' last use and the lane's
-    // work buffers as free (a ring, so handles held by older slots only ever point to later work)
-    EvRef ev{&L.ring, 0};
-    HIPCHK(c, hipEventRecord(L.ring.take(&ev.ticket), st));
-    for (int i = 0; i < nU; i++) c->ev_last_use[(size_t)T.ut.fslot[i] * c->lanes.size() + li] = ev;
-    for (int i = 0; i < n; i++) {
-        c->ev_slot_done[slots[i]] = ev;
-        c->slot_state[slots[i]] = 1;
-        c->slot_pov[slots[i]] = (char)(pov_mode != 0);
+    } else if (int rc = enqueue_batch(c, L, T, n, nU, pov_mode, cap)) {
+        return rc;
     }
     HIPCHK(c, hipGetLastError());
     return FFL_OK;
+}
+
+// One batch of pairs through the 4-scale Farneback schedule (dis == nullptr) or the DIS path + pass-1 reductions, on
+// compute lane `li`.
+static int run_batch(ffl_ctx *c, int li, int n, const int *f0, const int *f1, const int *slots, int pov_mode,
+                     const DebugCapture *cap, const DisKParams *dis = nullptr) {
+    ffl_ctx::Lane &L = c->lanes[li];
+    // the batch's table is the pinned entry of the ring entry it will record; settling that entry frees the table (its
+    // batch, FFL_EV_RING batches ago, has consumed it), and the record below does not wait again
+    HIPCHK(c, L.ring.settle_next());
+    BatchTab &T = L.h_tab[L.ring.next % FFL_EV_RING];
+    int nU = 0;
+    const int rc = queue_batch(c, L, T, &nU, n, f0, f1, slots, pov_mode, cap, dis);
+    // ONE event per batch: it marks the slots' results as ready, the frames' last use and the lane's work buffers as free.
+    // Recorded after a failure too: later uploads, slot reuse and ffl_sync stay ordered behind whatever was queued, and the
+    // slots hold no result.
+    EvRef ev;
+    HIPCHK(c, L.ring.record(L.st, &ev));
+    for (int i = 0; i < nU; i++) c->ev_last_use[(size_t)T.ut.fslot[i] * c->lanes.size() + li] = ev;
+    publish_slots(c, n, slots, ev, rc == FFL_OK);
+    return rc;
 }
 
 static int check_pairs(ffl_ctx *c, int n, const int *f0, const int *f1, const int *slots) {
@@ -1274,16 +1312,6 @@ static int check_pairs(ffl_ctx *c, int n, const int *f0, const int *f1, const in
     for (int i = 0; i < n; i++) c->slot_mark[slots[i]] = 0;
     if (dup >= 0) return set_err(c, FFL_ERR_INVALID, "flow slot %d used twice in one batch", dup);
     return FFL_OK;
-}
-
-int ffl_flow_pairs(ffl_ctx *c, int n, const int *fslot0, const int *fslot1, const int *flow_slots, int pov_mode) {
-    if (!c) return FFL_ERR_INVALID;
-    CtxLock lk(c->mu);
-    int rc = check_pairs(c, n, fslot0, fslot1, flow_slots);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    const int li = (int)(c->next_lane++ % c->lanes.size());
-    return run_batch(c, li, n, fslot0, fslot1, flow_slots, pov_mode, nullptr);
 }
 
 // ---- DIS (kernels_dis.hip) ------------------------------------------------------------------
@@ -1371,17 +1399,27 @@ static int dis_kparams(ffl_ctx *c, const ffl_dis_params *pp, int n, DisKParams *
     return FFL_OK;
 }
 
-int ffl_flow_pairs_dis(ffl_ctx *c, int n, const int *fslot0, const int *fslot1, const int *flow_slots, int pov_mode,
-                       const ffl_dis_params *p) {
+// ffl_flow_pairs (dis == false) and ffl_flow_pairs_dis: a checked batch on the next compute lane
+static int submit_pairs(ffl_ctx *c, int n, const int *f0, const int *f1, const int *slots, int pov_mode, bool dis,
+                        const ffl_dis_params *p) {
     if (!c) return FFL_ERR_INVALID;
     CtxLock lk(c->mu);
-    int rc = check_pairs(c, n, fslot0, fslot1, flow_slots);
+    int rc = check_pairs(c, n, f0, f1, slots);
     if (rc) return rc;
     DisKParams k;
-    if ((rc = dis_kparams(c, p, n, &k))) return rc;
+    if (dis && (rc = dis_kparams(c, p, n, &k))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const int li = (int)(c->next_lane++ % c->lanes.size());
-    return run_batch(c, li, n, fslot0, fslot1, flow_slots, pov_mode, nullptr, &k);
+    return run_batch(c, li, n, f0, f1, slots, pov_mode, nullptr, dis ? &k : nullptr);
+}
+
+int ffl_flow_pairs(ffl_ctx *c, int n, const int *fslot0, const int *fslot1, const int *flow_slots, int pov_mode) {
+    return submit_pairs(c, n, fslot0, fslot1, flow_slots, pov_mode, false, nullptr);
+}
+
+int ffl_flow_pairs_dis(ffl_ctx *c, int n, const int *fslot0, const int *fslot1, const int *flow_slots, int pov_mode,
+                       const ffl_dis_params *p) {
+    return submit_pairs(c, n, fslot0, fslot1, flow_slots, pov_mode, true, p);
 }
 
 int ffl_debug_dis_pair(ffl_ctx *c, int f0, int f1, const ffl_dis_params *p, int scale, int stage, float *out) {
@@ -1428,28 +1466,7 @@ int ffl_debug_pair(ffl_ctx *c, int f0, int f1, int level, int iter, float *I0, f
 
 int ffl_pass1_result(ffl_ctx *c, int slot, float cut_threshold, int32_t *x, int32_t *y, float *div_val, float *mean_mag,
                      int *cut) {
-    if (!c) return FFL_ERR_INVALID;
-    CtxLock lk(c->mu);
-    if (slot < 0 || slot >= c->n_slots) return set_err(c, FFL_ERR_INVALID, "flow slot %d out of range", slot);
-    if (!c->slot_state[slot]) return set_err(c, FFL_ERR_STATE, "flow slot %d holds no result", slot);
-    HIPCHK(c, hipSetDevice(c->device));
-    {
-        // wait without the lock: the event handle is a ring entry that is only ever re-recorded for LATER work
-        // of the same lane, so waiting on it after another thread queued more batches is still sufficient
-        hipEvent_t ev = c->ev_slot_done[slot].get();
-        lk.unlock();
-        hipError_t e = ev ? hipEventSynchronize(ev) : hipSuccess;
-        lk.lock();
-        HIPCHK(c, e);
-    }
-    const Pass1Result &r = c->h_res[slot];
-    float mm = (float)(r.mag_sum / ((double)c->w * (double)c->h));
-    if (x) *x = r.x;
-    if (y) *y = r.y;
-    if (div_val) *div_val = r.div_val;
-    if (mean_mag) *mean_mag = mm;
-    if (cut) *cut = mm > cut_threshold ? 1 : 0;
-    return FFL_OK;
+    return ffl_pass1_results(c, 1, &slot, cut_threshold, x, y, div_val, mean_mag, cut);
 }
 
 int ffl_pass1_results(ffl_ctx *c, int n, const int *slots, float cut_threshold, int32_t *x, int32_t *y, float *div_val,
@@ -1458,36 +1475,17 @@ int ffl_pass1_results(ffl_ctx *c, int n, const int *slots, float cut_threshold, 
     CtxLock lk(c->mu);
     if (n < 0 || (n > 0 && !slots)) return set_err(c, FFL_ERR_INVALID, "ffl_pass1_results: bad arguments");
     // one lock, one wait per DISTINCT event (the slots of a batch share theirs), then the records: 256 one-slot calls
-    // cost 0.3 ms of host time per batch at the 256x256 operating point
-    hipEvent_t evs[16];
-    int ne = 0;
+    // cost 0.3 ms of host time per batch at the 256x256 operating point.  At most lanes x FFL_EV_RING + FFL_EV_RING
+    // events are live at a time (the lanes' rings and post_ring).
+    std::vector<hipEvent_t> evs;
     for (int i = 0; i < n; i++) {
         const int slot = slots[i];
         if (slot < 0 || slot >= c->n_slots) return set_err(c, FFL_ERR_INVALID, "flow slot %d out of range", slot);
         if (!c->slot_state[slot]) return set_err(c, FFL_ERR_STATE, "flow slot %d holds no result", slot);
         hipEvent_t e = c->ev_slot_done[slot].get();
-        bool seen = !e;
-        for (int k = 0; k < ne && !seen; k++) seen = evs[k] == e;
-        if (!seen) {
-            if (ne == 16) {  // more distinct events than a call normally names: wait for what has been collected, go on
-                lk.unlock();
-                hipError_t we = hipSuccess;
-                for (int k = 0; k < ne && we == hipSuccess; k++) we = hipEventSynchronize(evs[k]);
-                lk.lock();
-                HIPCHK(c, we);
-                ne = 0;
-            }
-            evs[ne++] = e;
-        }
+        if (e && std::find(evs.begin(), evs.end(), e) == evs.end()) evs.push_back(e);
     }
-    HIPCHK(c, hipSetDevice(c->device));
-    {
-        lk.unlock();  // the wait does not hold up uploads / submissions of other threads
-        hipError_t we = hipSuccess;
-        for (int k = 0; k < ne && we == hipSuccess; k++) we = hipEventSynchronize(evs[k]);
-        lk.lock();
-        HIPCHK(c, we);
-    }
+    if (int rc = wait_unlocked(c, lk, evs.data(), (int)evs.size())) return rc;
     const double npx = (double)c->w * (double)c->h;
     for (int i = 0; i < n; i++) {
         const Pass1Result &r = c->h_res[slots[i]];
@@ -1535,9 +1533,8 @@ int ffl_radial(ffl_ctx *c, int n, const int *slots, const double *cx, const doub
     {
         // the slots' "last use" now includes this pass 2: the wait below runs without the context lock, so another thread
         // may queue a batch that recycles one of these slots meanwhile -- it must run behind the kernel that reads them
-        HIPCHK(c, c->post_ring.settle_next());
-        EvRef ev{&c->post_ring, 0};
-        HIPCHK(c, hipEventRecord(c->post_ring.take(&ev.ticket), st));
+        EvRef ev;
+        HIPCHK(c, c->post_ring.record(st, &ev));
         for (int j = 0; j < m; j++) c->ev_slot_done[slots[map[j]]] = ev;
     }
     lk.unlock();  // the wait (for the batches the slots come from, then pass 2) does not hold up uploads / submissions
@@ -1554,14 +1551,8 @@ int ffl_download_flow(ffl_ctx *c, int slot, float *dst) {
     CtxLock lk(c->mu);
     if (slot < 0 || slot >= c->n_slots || !dst) return set_err(c, FFL_ERR_INVALID, "ffl_download_flow: bad arguments");
     if (!c->slot_state[slot]) return set_err(c, FFL_ERR_STATE, "flow slot %d holds no flow", slot);
-    HIPCHK(c, hipSetDevice(c->device));
-    {
-        hipEvent_t ev = c->ev_slot_done[slot].get();
-        lk.unlock();
-        hipError_t e = ev ? hipEventSynchronize(ev) : hipSuccess;
-        lk.lock();
-        HIPCHK(c, e);
-    }
+    hipEvent_t ev = c->ev_slot_done[slot].get();
+    if (int rc = wait_unlocked(c, lk, &ev, 1)) return rc;
     HIPCHK(c, hipMemcpy(dst, c->d_flow + (size_t)slot * 2 * c->N, sizeof(float) * 2 * c->N, hipMemcpyDeviceToHost));
     return FFL_OK;
 }
@@ -1571,16 +1562,13 @@ int ffl_upload_flow(ffl_ctx *c, int slot, const float *src, int pov_mode) {
     std::unique_lock<std::mutex> pl(c->post_mu);
     CtxLock lk(c->mu);
     if (slot < 0 || slot >= c->n_slots || !src) return set_err(c, FFL_ERR_INVALID, "ffl_upload_flow: bad arguments");
-    HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->s_post;
-    {
-        hipEvent_t ev = c->slot_state[slot] ? c->ev_slot_done[slot].get() : nullptr;
-        lk.unlock();
-        hipError_t e = ev ? hipEventSynchronize(ev) : hipSuccess;
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        lk.lock();
-        HIPCHK(c, e);
-    }
+    hipEvent_t ev = c->ev_slot_done[slot].get();  // the slot's last batch or pass 2 still reads or writes it
+    if (int rc = wait_unlocked(c, lk, &ev, 1)) return rc;
+    lk.unlock();
+    hipError_t se = hipStreamSynchronize(st);  // the previous call's pass 1 has consumed the pinned table
+    lk.lock();
+    HIPCHK(c, se);
     HIPCHK(c, hipMemcpy(c->d_flow + (size_t)slot * 2 * c->N, src, sizeof(float) * 2 * c->N, hipMemcpyHostToDevice));
     c->h_ptab->pt.flow[0][0] = c->d_flow + (size_t)slot * 2 * c->N;  // the stream was drained above: the pinned copy is free
     c->h_ptab->pt.res[0] = c->d_res + slot;
@@ -1589,11 +1577,9 @@ int ffl_upload_flow(ffl_ctx *c, int slot, const float *src, int pov_mode) {
         ProfScope ps(c, FFL_K_PASS1, st);
         ffl_launch_pass1(&c->d_ptab->pt, 1, c->w, c->h, pov_mode, c->d_ppkey, c->d_rpsum, st);
     }
-    HIPCHK(c, c->post_ring.settle_next());
-    c->ev_slot_done[slot] = EvRef{&c->post_ring, 0};
-    HIPCHK(c, hipEventRecord(c->post_ring.take(&c->ev_slot_done[slot].ticket), st));
-    c->slot_state[slot] = 1;
-    c->slot_pov[slot] = (char)(pov_mode != 0);
+    EvRef done;
+    HIPCHK(c, c->post_ring.record(st, &done));
+    publish_slots(c, 1, &slot, done, true);
     HIPCHK(c, hipGetLastError());
     return FFL_OK;
 }
@@ -1618,28 +1604,20 @@ int ffl_submit_pair(ffl_ctx *c, int slot, const uint8_t *prev, const uint8_t *ne
 int ffl_sync(ffl_ctx *c) {
     if (!c) return FFL_ERR_INVALID;
     // up_mu / post_mu: an upload or pass-2 call of another thread that is under way finishes queueing first, so the latest
-    // events of streams `copy` and `post` stand for everything those calls put there
+    // events of streams `copy` and `post` stand for everything those calls put there.  All three locks are released for
+    // the wait: it holds up no other thread.
     std::unique_lock<std::mutex> ul(c->up_mu);
     std::unique_lock<std::mutex> pl(c->post_mu);
     CtxLock lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    // Wait on EVENTS, never on the lane streams: without the lock another thread may be capturing a new batch shape on a
-    // lane's stream, and hipStreamSynchronize on a capturing stream fails and invalidates the capture.  Each handle is a
-    // ring entry that is only ever re-recorded for LATER work of its stream, so waiting on it stays sufficient.
     std::vector<hipEvent_t> evs;
-    if (hipEvent_t e = ev_latest(c->up_ring).get()) evs.push_back(e);
+    evs.push_back(ev_latest(c->up_ring).get());
     for (auto &rb : c->raw)
-        if (rb.busy && rb.ev) evs.push_back(rb.ev);
-    for (auto &L : c->lanes)
-        if (hipEvent_t e = ev_latest(L.ring).get()) evs.push_back(e);
-    if (hipEvent_t e = ev_latest(c->post_ring).get()) evs.push_back(e);
-    lk.unlock();
-    hipError_t e = hipSuccess;
-    for (auto ev : evs)
-        if (e == hipSuccess) e = hipEventSynchronize(ev);
-    lk.lock();
-    HIPCHK(c, e);
-    return FFL_OK;
+        if (rb.busy) evs.push_back(rb.ev);
+    for (auto &L : c->lanes) evs.push_back(ev_latest(L.ring).get());
+    evs.push_back(ev_latest(c->post_ring).get());
+    pl.unlock();
+    ul.unlock();
+    return wait_unlocked(c, lk, evs.data(), (int)evs.size());
 }
 
 // one knob of an option set; `live`: the set belongs to an existing context (its lane count is fixed)
@@ -1748,7 +1726,8 @@ int ffl_graph_stats(ffl_ctx *c, int *captured, int *replayed, int *capture_failu
 
 int ffl_profile_enable(ffl_ctx *c, unsigned class_mask) {
     if (!c) return FFL_ERR_INVALID;
-    ffl_sync(c);  // before the context lock: ffl_sync takes up_mu / post_mu first (lock order)
+    int rc = ffl_sync(c);  // before the context lock: ffl_sync takes up_mu / post_mu first (lock order)
+    if (rc) return rc;
     CtxLock lk(c->mu);
     prof_collect(c);
     c->prof_mask = class_mask;

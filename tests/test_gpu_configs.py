@@ -360,6 +360,31 @@ def test_graph_cache_is_bounded_and_shapes_may_vary_freely():
     assert np.array_equal(np.frombuffer(want[nmax][0], np.float32).reshape(h, w, 2), orc.farneback(fr[nmax - 1], fr[nmax]))
 
 
+def test_one_results_call_names_more_batch_events_than_sixteen():
+    """ffl_pass1_results waits once per DISTINCT event of the slots it names.  24 one-pair batches on two lanes leave 24
+    lane events live (12 per lane, each lane's ring holds 16): one call reads all 24 records, and they equal those of one
+    24-pair batch of the same pairs on a second context."""
+    w, h, n = 96, 64, 24
+    fr = sine_translate_frames(n + 1, w, h, seed=5, amp=(2.0, 1.5), period=9)
+    slots = list(range(n))
+    recs = []
+    try:
+        _capi.set_option("lanes", 2)
+        for one_pair_batches in (True, False):
+            with _capi.Context(w, h, max_batch=n, frame_slots=n + 1, flow_slots=n) as ctx:
+                ctx.upload_frames(0, list(fr))
+                if one_pair_batches:
+                    for j in range(n):
+                        ctx.flow_pairs([j], [j + 1], [j])
+                else:
+                    ctx.flow_pairs(list(range(n)), list(range(1, n + 1)), slots)
+                recs.append([tuple(r) for r in ctx.pass1_results(slots, 7.0)])
+    finally:
+        _capi.set_option("lanes", 2)
+    assert recs[0] == recs[1]
+    assert (recs[0][7][0], recs[0][7][1]) == orc.max_divergence_np(orc.farneback(fr[7], fr[8]))[:2]
+
+
 def test_largest_baseline_frame_5760x2880_whole():
     """The largest frame BASELINE names, taken whole (SURVEY App. C "5 whole frame": 16.6 Mpx, 332 MB per 5-plane
     field, 8.3 GB of algorithmic traffic per pair): one pair bit for bit against the oracle, reductions on the
