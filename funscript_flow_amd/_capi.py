@@ -20,7 +20,8 @@ EXPORTS = ["ffl_device_count", "ffl_create", "ffl_destroy", "ffl_last_error", "f
            "ffl_pass1_result", "ffl_pass1_results", "ffl_radial", "ffl_download_flow", "ffl_upload_flow", "ffl_submit_pair", "ffl_sync",
            "ffl_num_levels", "ffl_level_size", "ffl_download_frame", "ffl_debug_pair", "ffl_set_option", "ffl_ctx_set_option", "ffl_ctx_get_option", "ffl_graph_stats", "ffl_profile_enable",
            "ffl_profile_read", "ffl_kernel_name", "ffl_device_mem_info", "ffl_estimate_bytes",
-           "ffl_dis_default_params", "ffl_dis_geometry", "ffl_flow_pairs_dis", "ffl_debug_dis_pair"]
+           "ffl_dis_default_params", "ffl_dis_geometry", "ffl_flow_pairs_dis", "ffl_debug_dis_pair",
+           "ffl_farneback_default_params", "ffl_farneback_geometry", "ffl_farneback_extra_bytes", "ffl_flow_pairs_farneback"]
 
 FLOWS = ("farneback", "dis")   # params["hip_flow"]: the reference's CPU/CUDA/OpenCL branch, or its "DNN" branch (FF:948-980)
 DIS_STAGES = {"pass1": 0, "pass2": 1, "dense": 2, "refined": 3, "images": 4}   # ffl_debug_dis_pair stages
@@ -57,6 +58,70 @@ def flow_choice(params):
             raise ValueError('"hip_dis" overrides DIS parameters: it needs "hip_flow": "dis"')
         return flow, None
     return flow, DisParams(**dict(params.get("hip_dis") or {}))
+
+
+class FarnebackParams(C.Structure):
+    """ffl_farneback_params with cv2.calcOpticalFlowFarneback's keyword names; the defaults are the reference's call
+    (0.5, 3, 15, 3, 5, 1.2, 0), FF:878-879.  The rules are DESIGN.md appendix F."""
+    _fields_ = [("pyr_scale", C.c_float), ("levels", C.c_int), ("winsize", C.c_int), ("iterations", C.c_int),
+                ("poly_n", C.c_int), ("poly_sigma", C.c_float), ("flags", C.c_int)]
+    DEFAULTS = dict(pyr_scale=0.5, levels=3, winsize=15, iterations=3, poly_n=5, poly_sigma=1.2, flags=0)
+    INTS = ("levels", "winsize", "iterations", "poly_n", "flags")
+
+    def __init__(self, **over):
+        unknown = set(over) - set(self.DEFAULTS)
+        if unknown:
+            raise ValueError(f"unknown Farneback parameter(s) {sorted(unknown)}; known: {sorted(self.DEFAULTS)}")
+        super().__init__(**{**self.DEFAULTS, **over})
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+    def is_default(self):
+        return bytes(self) == bytes(FarnebackParams())
+
+
+def _farneback_error(prefix):
+    msg = load().ffl_last_error(None)
+    return ValueError(f"{prefix}: {msg.decode() if msg else 'refused'}")
+
+
+def farneback_geometry(width, height, params=None):
+    """(scales, working-set bytes per pair) of the general Farneback kernels; ValueError (with the library's reason) when
+    the parameters or the size are refused."""
+    p = params if params is not None else FarnebackParams()
+    n, b = C.c_int(), C.c_size_t()
+    if load().ffl_farneback_geometry(int(width), int(height), C.byref(p), C.byref(n), C.byref(b)) != FFL_OK:
+        raise _farneback_error(f"Farneback at {width}x{height} with {p.as_dict()}")
+    return n.value, b.value
+
+
+def farneback_extra_bytes(width, height, max_batch, params):
+    """device bytes ffl_flow_pairs_farneback(params) may add to ffl_estimate_bytes (0 when the lane buffers suffice)"""
+    b = C.c_size_t()
+    if load().ffl_farneback_extra_bytes(int(width), int(height), int(max_batch), C.byref(params), C.byref(b)) != FFL_OK:
+        raise _farneback_error(f"Farneback at {width}x{height} with {params.as_dict()}")
+    return b.value
+
+
+def farneback_choice(params):
+    """FarnebackParams from params["hip_farneback"] = {cv2 keyword: value}, or None for the reference's values (the tuned
+    path).  ValueError for unknown names, values the rules refuse, or "hip_farneback" together with "hip_flow": "dis"."""
+    over = params.get("hip_farneback")
+    if not over:
+        return None
+    if params.get("hip_flow", "farneback") == "dis":
+        raise ValueError('"hip_farneback" sets Farneback parameters: it cannot be combined with "hip_flow": "dis"')
+    over = dict(over)
+    for name, v in over.items():   # integer fields must be given whole numbers (no silent truncation)
+        if name in FarnebackParams.INTS:
+            if float(v) != int(v):
+                raise ValueError(f"Farneback parameter {name} must be an integer, got {v!r}")
+            over[name] = int(v)
+    p = FarnebackParams(**over)
+    if load().ffl_farneback_geometry(64, 64, C.byref(p), None, None) != FFL_OK:
+        raise _farneback_error(f"hip_farneback {dict(over)}")
+    return None if p.is_default() else p
 
 
 def dis_geometry(width, height, params=None):
@@ -127,6 +192,11 @@ def load():
     L.ffl_dis_geometry.argtypes = [C.c_int, C.c_int, dp_, ip, ip]
     L.ffl_flow_pairs_dis.argtypes = [vp, C.c_int, ip, ip, ip, C.c_int, dp_]
     L.ffl_debug_dis_pair.argtypes = [vp, C.c_int, C.c_int, dp_, C.c_int, C.c_int, vp]
+    fp_ = C.POINTER(FarnebackParams)
+    L.ffl_farneback_default_params.argtypes = [fp_]
+    L.ffl_farneback_geometry.argtypes = [C.c_int, C.c_int, fp_, ip, C.POINTER(C.c_size_t)]
+    L.ffl_farneback_extra_bytes.argtypes = [C.c_int, C.c_int, C.c_int, fp_, C.POINTER(C.c_size_t)]
+    L.ffl_flow_pairs_farneback.argtypes = [vp, C.c_int, ip, ip, ip, C.c_int, fp_]
     _lib = L
     return L
 
@@ -295,6 +365,16 @@ class Context:
             raise FFLError("flow_pairs_dis: the three slot lists must have one entry per pair")
         self._chk(self.L.ffl_flow_pairs_dis(self._h, n, p0, p1, ps, int(bool(pov_mode)),
                                             None if params is None else C.byref(params)))
+
+    def flow_pairs_farneback(self, fslot0, fslot1, flow_slots, pov_mode=False, params=None):
+        """ffl_flow_pairs_farneback: Farneback with caller-chosen parameters (FarnebackParams; None or the defaults = the
+        tuned path of flow_pairs) + pass 1 for a batch of pairs."""
+        n = len(flow_slots)
+        (p0, k0), (p1, k1), (ps, ks) = _iarr(fslot0), _iarr(fslot1), _iarr(flow_slots)
+        if len(k0) != n or len(k1) != n:
+            raise FFLError("flow_pairs_farneback: the three slot lists must have one entry per pair")
+        self._chk(self.L.ffl_flow_pairs_farneback(self._h, n, p0, p1, ps, int(bool(pov_mode)),
+                                                  None if params is None else C.byref(params)))
 
     def submit_pair(self, slot, prev, nxt, pov_mode=False):
         prev, nxt = np.ascontiguousarray(prev), np.ascontiguousarray(nxt)

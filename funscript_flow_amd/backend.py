@@ -8,7 +8,8 @@ Same names, argument meaning and result shape as the reference's pair functions:
     radial_motion_weighted(flow, center, is_cut, pov_mode=False)   FF:761-785  -> float
     precompute_all(pairs, params)          the whole `pool.starmap(precompute_wrapper, ...)` of FF:1190-1191
     (params["hip_flow"] = "dis" runs DIS -- the reference's "DNN" branch, FF:948-980 -- instead of Farneback;
-    params["hip_dis"] = {field: value} overrides single _capi.DisParams fields)
+    params["hip_dis"] = {field: value} overrides single _capi.DisParams fields; params["hip_farneback"] = {cv2 keyword: value}
+    sets calcOpticalFlowFarneback's parameters)
     radial_all(precomputed, centers, pov_mode)   the whole ProcessPoolExecutor loop of FF:1232-1236
     get_available_backends()               FF:32-63  (reports "HIP" when a device is usable)
 
@@ -83,12 +84,15 @@ def precompute_flow_info(p0, p1, config):
     if backend != "HIP":
         raise ValueError(f"funscript_flow_amd implements backend 'HIP' only, got {backend!r}")
     flow, dis = _capi.flow_choice(config)   # "hip_flow": "farneback" (default) | "dis" (the reference's DNN branch, FF:948-980)
+    fb = _capi.farneback_choice(config)     # "hip_farneback": {cv2 keyword: value}; None = the reference's values
     cut_threshold = config.get("cut_threshold", 7)
     h, w = p0.shape[:2]
     if p1.shape != p0.shape:
         raise ValueError("frame shapes differ")
     if flow == "dis":
         _capi.dis_geometry(w, h, dis)
+    if fb is not None:
+        _capi.farneback_geometry(w, h, fb)
     key = (w, h, int(config.get("device", 0)))
     ctx = _context(*key)
     slot = _next_slot[key] % RING
@@ -98,6 +102,9 @@ def precompute_flow_info(p0, p1, config):
     if flow == "dis":
         ctx.upload_frames(2 * slot, [p0, p1])
         ctx.flow_pairs_dis([2 * slot], [2 * slot + 1], [slot], bool(config.get("pov_mode")), dis)
+    elif fb is not None:
+        ctx.upload_frames(2 * slot, [p0, p1])
+        ctx.flow_pairs_farneback([2 * slot], [2 * slot + 1], [slot], bool(config.get("pov_mode")), fb)
     else:
         ctx.submit_pair(slot, p0, p1, bool(config.get("pov_mode")))
     x, y, val, mean_mag, cut = ctx.pass1_result(slot, float(cut_threshold))
@@ -209,12 +216,15 @@ def precompute_all(pairs, params):
     if params.get("backend", "HIP") != "HIP":
         raise ValueError("funscript_flow_amd implements backend 'HIP' only")
     flow, dis = _capi.flow_choice(params)
+    fb = _capi.farneback_choice(params)
     pairs = list(pairs)
     if not pairs:
         return []
     h, w = pairs[0][0].shape[:2]
     if flow == "dis":
         _capi.dis_geometry(w, h, dis)
+    if fb is not None:
+        _capi.farneback_geometry(w, h, fb)
     B = max(1, min(int(params.get("hip_batch", default_batch(w, h))), _capi.FFL_MAX_BATCH))
     ctx = _chunk_context(w, h, len(pairs), int(params.get("device", 0)), B)
     B = ctx.max_batch                       # possibly smaller than asked for: what fits beside the chunk's flows
@@ -233,7 +243,7 @@ def precompute_all(pairs, params):
     stream = all(b == a + 1 for a, b in idx) and all(idx[j + 1][0] == idx[j][1] for j in range(len(idx) - 1))
     pov, thr = bool(params.get("pov_mode")), float(params.get("cut_threshold", 7))
     eng = pipeline.PairEngine.__new__(pipeline.PairEngine)   # slots are sized for the chunk here, not for a stream
-    eng.ctx, eng.B, eng.upload, eng.flow, eng.dis = ctx, B, ctx.upload_frames, flow, dis
+    eng.ctx, eng.B, eng.upload, eng.flow, eng.dis, eng.farneback = ctx, B, ctx.upload_frames, flow, dis, fb
     eng.depth = 2 if ctx.frame_slots >= pipeline.min_frame_slots(B, 2) else 1
     out = [None] * len(pairs)
     serial = ctx._chunk_serial

@@ -235,6 +235,9 @@ struct ffl_ctx {
         float *d_T = nullptr;
         EvRing ring;  // one "batch finished" event per batch (FFL_EV_RING entries)
         size_t r_off[8] = {0};  // float offset of level k inside d_R
+        size_t r_cap = 0;       // floats of d_R
+        float *d_gen = nullptr; // general-path work area (ffl_flow_pairs_farneback), allocated when d_R is too small
+        size_t gen_cap = 0;     // its floats: the largest request seen
         float *d_I = nullptr, *d_R = nullptr, *d_M[2] = {nullptr, nullptr}, *d_flowA = nullptr, *d_flowB = nullptr;
         unsigned long long *d_pkey = nullptr;
         double *d_psum = nullptr;
@@ -607,7 +610,7 @@ void ffl_destroy(ffl_ctx *c) {
     for (auto &L : c->lanes) {
         hipFree(L.d_I); hipFree(L.d_T); hipFree(L.d_R); hipFree(L.d_M[0]); hipFree(L.d_M[1]);
         hipFree(L.d_flowA); hipFree(L.d_flowB); hipFree(L.d_pkey); hipFree(L.d_psum);
-        hipFree(L.d_tab); hipHostFree(L.h_tab);
+        hipFree(L.d_tab); hipHostFree(L.h_tab); hipFree(L.d_gen);
         for (auto &g : L.graphs) {
             hipGraphExecDestroy(g.exec);
             hipGraphDestroy(g.graph);
@@ -706,6 +709,7 @@ int ffl_create(int device, int width, int height, int n_frame_slots, int n_flow_
         CCHK(hipMalloc(&L.d_I, sizeof(float) * i_total));
         CCHK(hipMalloc(&L.d_T, sizeof(float) * t_total));
         CCHK(hipMalloc(&L.d_R, sizeof(float) * r_total));
+        L.r_cap = r_total;
         CCHK(hipMalloc(&L.d_M[0], sizeof(float) * 5 * N * max_batch));
         CCHK(hipMalloc(&L.d_M[1], sizeof(float) * 5 * N * max_batch));
         CCHK(hipMalloc(&L.d_flowA, sizeof(float) * 2 * N * max_batch));
@@ -1214,10 +1218,13 @@ static int batch_graph(ffl_ctx *c, ffl_ctx::Lane &L, const BatchTab &T, int n, i
     return FFL_OK;
 }
 
+static int fbg_work(ffl_ctx *c, ffl_ctx::Lane &L, const FbgPlan &p, int n, int nU, FbgWork *wk);
+
 // Fills the batch's table T (*nU unique frames) and queues the batch on the lane's stream: the waits for its frames and
 // recycled slots, the table copy, the launches.  Once the table is filled, a failure may leave part of the batch queued.
 static int queue_batch(ffl_ctx *c, ffl_ctx::Lane &L, BatchTab &T, int *nU_out, int n, const int *f0, const int *f1,
-                       const int *slots, int pov_mode, const DebugCapture *cap, const DisKParams *dis) {
+                       const int *slots, int pov_mode, const DebugCapture *cap, const DisKParams *dis,
+                       const FbgPlan *fbg) {
     hipStream_t st = L.st;
     const size_t N = c->N;
     int nU = 0;
@@ -1252,7 +1259,14 @@ static int queue_batch(ffl_ctx *c, ffl_ctx::Lane &L, BatchTab &T, int *nU_out, i
     // stream order puts this copy behind the lane's previous batch, which reads the same device table
     HIPCHK(c, hipMemcpyAsync(L.d_tab, &T, sizeof(BatchTab), hipMemcpyHostToDevice, st));
 
-    if (dis) {
+    if (fbg) {
+        // general-parameter Farneback batches launch eagerly too (graphs stay keyed on the tuned schedule)
+        FbgWork wk;
+        if (int rc = fbg_work(c, L, *fbg, n, nU, &wk)) return rc;
+        ffl_launch_fb_general(&L.d_tab->ut, &L.d_tab->pt, n, nU, c->d_gray, N, c->w, c->h, *fbg, wk, st);
+        ProfScope ps(c, FFL_K_PASS1, st);
+        ffl_launch_pass1(&L.d_tab->pt, n, c->w, c->h, pov_mode, L.d_pkey, L.d_psum, st);
+    } else if (dis) {
         // DIS batches launch eagerly (graphs stay keyed on Farneback batch shapes); scratch: the lane's first M buffer
         ffl_launch_dis(&L.d_tab->ut, &L.d_tab->pt, n, c->d_gray, N, L.d_M[0], *dis, st);
         ProfScope ps(c, FFL_K_PASS1, st);
@@ -1276,14 +1290,14 @@ static int queue_batch(ffl_ctx *c, ffl_ctx::Lane &L, BatchTab &T, int *nU_out, i
 // One batch of pairs through the 4-scale Farneback schedule (dis == nullptr) or the DIS path + pass-1 reductions, on
 // compute lane `li`.
 static int run_batch(ffl_ctx *c, int li, int n, const int *f0, const int *f1, const int *slots, int pov_mode,
-                     const DebugCapture *cap, const DisKParams *dis = nullptr) {
+                     const DebugCapture *cap, const DisKParams *dis = nullptr, const FbgPlan *fbg = nullptr) {
     ffl_ctx::Lane &L = c->lanes[li];
     // the batch's table is the pinned entry of the ring entry it will record; settling that entry frees the table (its
     // batch, FFL_EV_RING batches ago, has consumed it), and the record below does not wait again
     HIPCHK(c, L.ring.settle_next());
     BatchTab &T = L.h_tab[L.ring.next % FFL_EV_RING];
     int nU = 0;
-    const int rc = queue_batch(c, L, T, &nU, n, f0, f1, slots, pov_mode, cap, dis);
+    const int rc = queue_batch(c, L, T, &nU, n, f0, f1, slots, pov_mode, cap, dis, fbg);
     // ONE event per batch: it marks the slots' results as ready, the frames' last use and the lane's work buffers as free.
     // Recorded after a failure too: later uploads, slot reuse and ffl_sync stay ordered behind whatever was queued, and the
     // slots hold no result.
@@ -1401,7 +1415,7 @@ static int dis_kparams(ffl_ctx *c, const ffl_dis_params *pp, int n, DisKParams *
 
 // ffl_flow_pairs (dis == false) and ffl_flow_pairs_dis: a checked batch on the next compute lane
 static int submit_pairs(ffl_ctx *c, int n, const int *f0, const int *f1, const int *slots, int pov_mode, bool dis,
-                        const ffl_dis_params *p) {
+                        const ffl_dis_params *p, const FbgPlan *fbg = nullptr) {
     if (!c) return FFL_ERR_INVALID;
     CtxLock lk(c->mu);
     int rc = check_pairs(c, n, f0, f1, slots);
@@ -1410,7 +1424,7 @@ static int submit_pairs(ffl_ctx *c, int n, const int *f0, const int *f1, const i
     if (dis && (rc = dis_kparams(c, p, n, &k))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const int li = (int)(c->next_lane++ % c->lanes.size());
-    return run_batch(c, li, n, f0, f1, slots, pov_mode, nullptr, dis ? &k : nullptr);
+    return run_batch(c, li, n, f0, f1, slots, pov_mode, nullptr, dis ? &k : nullptr, fbg);
 }
 
 int ffl_flow_pairs(ffl_ctx *c, int n, const int *fslot0, const int *fslot1, const int *flow_slots, int pov_mode) {
@@ -1446,6 +1460,238 @@ int ffl_debug_dis_pair(ffl_ctx *c, int f0, int f1, const ffl_dis_params *p, int 
     if (rc) return rc;
     HIPCHK(c, e);
     return FFL_OK;
+}
+
+// ---- Farneback with caller-chosen parameters (kernels_farneback_general.hip) ----------------
+
+int ffl_farneback_default_params(ffl_farneback_params *out) {
+    if (!out) return FFL_ERR_INVALID;
+    *out = ffl_farneback_params{0.5f, 3, 15, 3, 5, 1.2f, 0};
+    return FFL_OK;
+}
+
+static bool fbg_is_default(const ffl_farneback_params &p) {
+    return p.pyr_scale == 0.5f && p.levels == 3 && p.winsize == 15 && p.iterations == 3 && p.poly_n == 5 &&
+           p.poly_sigma == 1.2f && p.flags == 0;
+}
+
+// F.0: the double a caller meant by a float parameter -- the shortest decimal that reads back as the same float (1.2f is
+// computed with as 1.2, as the reference's literal is)
+static double fbg_widen(float f) {
+    char buf[32];
+    for (int d = 1; d <= 9; d++) {
+        snprintf(buf, sizeof buf, "%.*g", d, (double)f);
+        const double v = strtod(buf, nullptr);
+        if ((float)v == f) return v;
+    }
+    return (double)f;
+}
+
+// F.1: nullptr when the parameters are accepted, else the reason
+static const char *fbg_check(const ffl_farneback_params &p) {
+    if (!(p.pyr_scale > 0.f && p.pyr_scale < 1.f)) return "pyr_scale must be in (0, 1)";
+    if (p.levels < 0 || p.levels > 12) return "levels must be 0..12";
+    if (p.winsize < 3 || p.winsize > 2 * FBG_MAX_M + 1 || !(p.winsize & 1))
+        return "winsize must be odd, 3..63 (even windows are not supported)";
+    if (p.iterations < 1 || p.iterations > 10) return "iterations must be 1..10";
+    if (p.poly_n != 5 && p.poly_n != 7) return "poly_n must be 5 or 7";
+    if (!(p.poly_sigma > 0.f && p.poly_sigma <= 3.f)) return "poly_sigma must be in (0, 3]";
+    if (p.flags & 4) return "OPTFLOW_USE_INITIAL_FLOW (4) is not supported";
+    if (p.flags & 256) return "OPTFLOW_FARNEBACK_GAUSSIAN (256) is not supported";
+    if (p.flags) return "flags must be 0";
+    return nullptr;
+}
+
+// The plan of p on a w x h frame (levels, sizes, Gaussians, PolyExp constants, R layout); nullptr or the reason it is refused
+static const char *fbg_plan(int w, int h, const ffl_farneback_params &p, FbgPlan *pl, char *why, size_t why_len) {
+    if (const char *e = fbg_check(p)) return e;
+    if (w < 16 || h < 16 || (long)w * h * 20 >= (1L << 32)) {
+        snprintf(why, why_len, "unsupported frame size %dx%d (16x16 .. 20*w*h < 2^32)", w, h);
+        return why;
+    }
+    memset(pl, 0, sizeof(*pl));
+    const double ps = fbg_widen(p.pyr_scale);
+    double scale = 1.0;
+    int k;
+    for (k = 0; k < p.levels; k++) {  // A.1: min_size = 32
+        scale *= ps;
+        if (w * scale < 32 || h * scale < 32) break;
+    }
+    pl->levels = k;
+    pl->iterations = p.iterations;
+    pl->poly_n = p.poly_n;
+    pl->m = p.winsize / 2;
+    pl->mul = (float)(1.0 / ps);
+    size_t off = 0;
+    for (k = 0; k <= pl->levels; k++) {
+        double sc = 1.0;
+        for (int i = 0; i < k; i++) sc *= ps;
+        const double sigma = (1.0 / sc - 1.0) * 0.5;
+        int ks = cv_round(sigma * 5) | 1;
+        if (ks < 3) ks = 3;
+        if (ks > 2 * FBG_MAX_R + 1) {
+            snprintf(why, why_len, "%dx%d: level %d needs a %d-tap Gaussian, at most %d are supported", w, h, k, ks,
+                     2 * FBG_MAX_R + 1);
+            return why;
+        }
+        float full[2 * FBG_MAX_R + 1];
+        gaussian_kernel(ks, sigma, full);
+        pl->gk[k].r = ks / 2;
+        for (int j = 0; j <= ks / 2; j++) pl->gk[k].k[j] = full[ks / 2 + j];
+        pl->lw[k] = cv_round(w * sc);
+        pl->lh[k] = cv_round(h * sc);
+        pl->r_off[k] = off;
+        off += (size_t)5 * pl->lw[k] * pl->lh[k];
+    }
+    pl->r_frame = off;
+    // F.3: FarnebackPrepareGaussian(poly_n, poly_sigma), the oracle's procedure with n and sigma as parameters
+    const int n = p.poly_n;
+    const double sigma = fbg_widen(p.poly_sigma);
+    float gg[2 * 7 + 1];
+    double s = 0;
+    for (int x = -n; x <= n; x++) {
+        gg[x + n] = (float)exp(-x * x / (2 * sigma * sigma));
+        s += gg[x + n];
+    }
+    s = 1. / s;
+    for (int x = -n; x <= n; x++) gg[x + n] = (float)(gg[x + n] * s);
+    for (int x = 0; x <= n; x++) {
+        pl->poly.g[x] = gg[x + n];
+        pl->poly.xg[x] = (float)(x * gg[x + n]);
+        pl->poly.xxg[x] = (float)(x * x * gg[x + n]);
+    }
+    double G[6][6];
+    memset(G, 0, sizeof(G));
+    for (int y = -n; y <= n; y++)
+        for (int x = -n; x <= n; x++) {
+            float q = gg[y + n] * gg[x + n];
+            G[0][0] += q;
+            G[1][1] += q * x * x;
+            G[3][3] += q * x * x * x * x;
+            G[5][5] += q * x * x * y * y;
+        }
+    G[2][2] = G[0][3] = G[0][4] = G[3][0] = G[4][0] = G[1][1];
+    G[4][4] = G[3][3];
+    G[3][4] = G[4][3] = G[5][5];
+    double A[6][12];
+    for (int i = 0; i < 6; i++)
+        for (int j = 0; j < 12; j++) A[i][j] = j < 6 ? G[i][j] : (j - 6 == i ? 1.0 : 0.0);
+    for (int c = 0; c < 6; c++) {
+        int pv = c;
+        for (int r = c + 1; r < 6; r++)
+            if (fabs(A[r][c]) > fabs(A[pv][c])) pv = r;
+        if (pv != c)
+            for (int j = 0; j < 12; j++) { double t = A[c][j]; A[c][j] = A[pv][j]; A[pv][j] = t; }
+        double d = 1.0 / A[c][c];
+        for (int j = 0; j < 12; j++) A[c][j] *= d;
+        for (int r = 0; r < 6; r++)
+            if (r != c) {
+                double f = A[r][c];
+                if (f != 0)
+                    for (int j = 0; j < 12; j++) A[r][j] -= f * A[c][j];
+            }
+    }
+    pl->poly.ig11 = A[1][7];
+    pl->poly.ig03 = A[0][9];
+    pl->poly.ig33 = A[3][9];
+    pl->poly.ig55 = A[5][11];
+    return nullptr;
+}
+
+// floats of one pair's working set: the R regions of its two frames, M (5 N) and the two level flows (2 N each)
+static size_t fbg_pair_floats(const FbgPlan &pl, size_t N) { return 2 * pl.r_frame + 9 * N; }
+
+int ffl_farneback_geometry(int width, int height, const ffl_farneback_params *p, int *n_scales, size_t *work_bytes_per_pair) {
+    if (!p) return set_err(nullptr, FFL_ERR_INVALID, "ffl_farneback_geometry: params is NULL");
+    FbgPlan pl;
+    char why[160];
+    if (const char *e = fbg_plan(width, height, *p, &pl, why, sizeof why))
+        return set_err(nullptr, FFL_ERR_INVALID, "ffl_farneback_geometry: %s", e);
+    if (n_scales) *n_scales = pl.levels + 1;
+    if (work_bytes_per_pair) *work_bytes_per_pair = sizeof(float) * fbg_pair_floats(pl, (size_t)width * height);
+    return FFL_OK;
+}
+
+// Device bytes that ffl_flow_pairs_farneback(p) may allocate on top of ffl_estimate_bytes for a context of these arguments
+// (under the current "lanes" option): per lane, the R regions of 2 * max_batch frames beyond the lane's d_R.
+int ffl_farneback_extra_bytes(int width, int height, int max_batch, const ffl_farneback_params *p, size_t *bytes) {
+    if (!p || !bytes || max_batch < 1 || max_batch > FFL_MAX_BATCH)
+        return set_err(nullptr, FFL_ERR_INVALID, "ffl_farneback_extra_bytes: bad arguments");
+    FbgPlan pl;
+    char why[160];
+    if (const char *e = fbg_plan(width, height, *p, &pl, why, sizeof why))
+        return set_err(nullptr, FFL_ERR_INVALID, "ffl_farneback_extra_bytes: %s", e);
+    ffl_ctx g;  // geometry only
+    g.w = width;
+    g.h = height;
+    level_geometry(&g);
+    const size_t maxU = 2 * (size_t)max_batch;
+    size_t r_cap = 0;
+    for (int k = 0; k <= g.levels; k++) r_cap += (size_t)5 * g.geom[k].lw * g.geom[k].lh * maxU;
+    const size_t need = pl.r_frame * maxU;
+    int num_lanes;
+    {
+        std::lock_guard<std::mutex> gl(g_opt_mu);
+        num_lanes = g_opts.lanes;
+    }
+    *bytes = need > r_cap ? sizeof(float) * (need - r_cap) * (size_t)num_lanes : 0;
+    return FFL_OK;
+}
+
+// Where a general batch of n pairs / nU unique frames works on lane L.  M and the level flows always fit the lane's d_M[0],
+// d_flowA and d_flowB (sized for 5 N and 2 N per pair; the blur planes need 2 N and the level images N per unique frame, at
+// most two per pair); the R regions of every level go to d_R when they fit, else to the lane's general-path work area, grown
+// to the largest request seen once the lane's queued work is over.
+static int fbg_work(ffl_ctx *c, ffl_ctx::Lane &L, const FbgPlan &p, int n, int nU, FbgWork *wk) {
+    (void)n;
+    wk->M = L.d_M[0];
+    wk->fa = L.d_flowA;
+    wk->fb = L.d_flowB;
+    const size_t need = p.r_frame * (size_t)nU;
+    if (need <= L.r_cap) {
+        wk->R = L.d_R;
+        return FFL_OK;
+    }
+    if (need > L.gen_cap) {
+        if (L.d_gen) {
+            hipEvent_t e = ev_latest(L.ring).get();  // the lane's last batch may still read the old area
+            if (e) HIPCHK(c, hipEventSynchronize(e));
+            HIPCHK(c, hipFree(L.d_gen));
+            L.d_gen = nullptr;
+            L.gen_cap = 0;
+        }
+        const hipError_t e = hipMalloc(&L.d_gen, sizeof(float) * need);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            L.d_gen = nullptr;
+            return set_err(c, FFL_ERR_HIP, "general Farneback work area: hipMalloc of %zu bytes (%d frames x %zu floats) failed: %s",
+                           sizeof(float) * need, nU, p.r_frame, hipGetErrorString(e));
+        }
+        L.gen_cap = need;
+    }
+    wk->R = L.d_gen;
+    return FFL_OK;
+}
+
+int ffl_flow_pairs_farneback(ffl_ctx *c, int n, const int *fslot0, const int *fslot1, const int *flow_slots, int pov_mode,
+                             const ffl_farneback_params *p) {
+    if (!c) return FFL_ERR_INVALID;
+    ffl_farneback_params d;
+    ffl_farneback_default_params(&d);
+    const ffl_farneback_params &q = p ? *p : d;
+    int force;
+    {
+        CtxLock lk(c->mu);
+        force = c->opt.fb_general;
+    }
+    if (fbg_is_default(q) && !force) return ffl_flow_pairs(c, n, fslot0, fslot1, flow_slots, pov_mode);
+    FbgPlan pl;
+    char why[160];
+    if (const char *e = fbg_plan(c->w, c->h, q, &pl, why, sizeof why)) {
+        CtxLock lk(c->mu);
+        return set_err(c, FFL_ERR_INVALID, "ffl_flow_pairs_farneback: %s", e);
+    }
+    return submit_pairs(c, n, fslot0, fslot1, flow_slots, pov_mode, false, nullptr, &pl);
 }
 
 int ffl_debug_pair(ffl_ctx *c, int f0, int f1, int level, int iter, float *I0, float *I1, float *R0, float *R1,
@@ -1653,6 +1899,11 @@ static int set_option_impl(FflOptions &o, const char *name, int value, bool live
         o.pyr_coarse = value != 0;
         return FFL_OK;
     }
+    if (!strcmp(name, "fb_general")) {  // 1: the reference's Farneback parameters through the general kernels (tests)
+        if (value < 0 || value > 1) return FFL_ERR_INVALID;
+        o.fb_general = value;
+        return FFL_OK;
+    }
     if (!strcmp(name, "copy_threads")) {  // host threads sharing a staging copy of >= 1 MiB (1 = the caller alone)
         if (value < 1 || value > 16) return FFL_ERR_INVALID;
         o.copy_threads = value;
@@ -1680,7 +1931,8 @@ static int get_option_impl(const FflOptions &o, const char *name, int *value) {
     struct { const char *n; int v; } tab[] = {
         {"blur_tile_h", 16}, {"fuse_first", o.fuse_first}, {"merge_expand", o.merge_expand}, {"blur_rows", o.blur_rows},
         {"blur_min_wgs", o.blur_min_wgs}, {"tile_order", o.tile_order}, {"pyr_coarse", o.pyr_coarse},
-        {"copy_threads", o.copy_threads}, {"graph", o.use_graph}, {"lanes", o.lanes}, {"run_ahead", o.run_ahead}};
+        {"copy_threads", o.copy_threads}, {"graph", o.use_graph}, {"lanes", o.lanes}, {"run_ahead", o.run_ahead},
+        {"fb_general", o.fb_general}};
     for (auto &t : tab)
         if (!strcmp(name, t.n)) {
             *value = t.v;

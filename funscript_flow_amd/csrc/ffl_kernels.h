@@ -108,6 +108,7 @@ struct FflOptions {
     int blur_min_wgs = 3500; // automatic strip length: the longest strips that still give this many workgroups
     int tile_order = 0;     // 0 pair-major, 1 tile-major (ffl_tile_coord)
     int pyr_coarse = 1;     // one-pass kernel for the x1/4 and x1/8 pyramid levels where sizes allow
+    int fb_general = 0;     // 1: ffl_flow_pairs_farneback runs the reference's parameters through the general kernels too
 };
 
 // ---- launchers (each enqueues on `st` and returns; no synchronisation) ----------------------
@@ -319,3 +320,33 @@ __device__ __forceinline__ void ffl_um_finish(const float (&r0)[5], const float 
     out[3] = r4 * r2 + r6 * r3;
     out[4] = r6 * r2 + r5 * r3;
 }
+
+// ---- Farneback with caller-chosen parameters (kernels_farneback_general.hip) ----------------
+#define FBG_MAX_R 95          // widest level Gaussian: 2 * 95 + 1 = 191 taps (larger ones are refused)
+#define FBG_MAX_SCALES 13     // levels 0..12
+#define FBG_MAX_M 31          // winsize 63
+struct FbgGauss {             // getGaussianKernel(2r + 1, sigma) as the symmetric half: k[j] = kernel[r + j]
+    float k[FBG_MAX_R + 1];
+    int r;
+};
+struct FbgPoly {              // FarnebackPrepareGaussian(poly_n, poly_sigma)
+    float g[8], xg[8], xxg[8];
+    double ig11, ig03, ig33, ig55;
+};
+struct FbgPlan {              // one parameter set on one frame size (host-side; kernels take pieces of it by value)
+    int levels, iterations, poly_n, m;  // levels actually used (A.1's min_size rule), box half-width m = winsize / 2
+    float mul;                          // (float)(1 / pyr_scale): the flow upsample factor
+    int lw[FBG_MAX_SCALES], lh[FBG_MAX_SCALES];
+    FbgGauss gk[FBG_MAX_SCALES];
+    FbgPoly poly;
+    size_t r_off[FBG_MAX_SCALES];       // float offset of level k inside one frame's R region
+    size_t r_frame;                     // floats of one frame's R region (5 planes of every level)
+};
+struct FbgWork {              // where a batch's working set lives (the lane's buffers or the general-path work area)
+    float *R;                 // nU regions of plan.r_frame floats
+    float *M;                 // n * 5N floats; the full-resolution blur planes (2 * nU * N floats) use it first
+    float *fa, *fb;           // n * 2N floats each: the level flows (ping-pong); fa holds the level images first
+};
+// the whole batch: every level of every unique frame, then the level chain of every pair into pt->flow[0][b]
+void ffl_launch_fb_general(const UTab *ut, const PairTab *pt, int n, int nU, const uint8_t *gray, size_t gray_stride, int w,
+                           int h, const FbgPlan &plan, const FbgWork &wk, hipStream_t st);

@@ -72,6 +72,20 @@ def shard_pairs(n_items, world, rank, assign="contiguous", block=1):
     return idx[(idx // block) % world == rank]
 
 
+OWN = object()   # pass1 / pass1_pairs / process_chunk `farneback` default: the engine's own parameters
+
+
+def farneback_kwargs(params, width, height):
+    """{"farneback": FarnebackParams or None} when params names "hip_farneback" (checked against the frame size up front),
+    else {}: the per-call override of frames_to_actions and prefetch.video_to_actions."""
+    if "hip_farneback" not in params:
+        return {}
+    fb = _capi.farneback_choice(params)
+    if fb is not None:
+        _capi.farneback_geometry(width, height, fb)
+    return {"farneback": fb}
+
+
 class PairEngine:
     """Streams one chunk of frames through a device context in batches of `max_batch` pairs.
 
@@ -80,7 +94,7 @@ class PairEngine:
     of pairs <= j+6 are known (or the chunk has ended), after which its flow slot is recycled.
     """
 
-    def __init__(self, ctx, upload=None, depth=None, flow="farneback", dis=None):
+    def __init__(self, ctx, upload=None, depth=None, flow="farneback", dis=None, farneback=None):
         """`upload(first_slot, frames)` puts a run of frames into consecutive frame slots; the default takes
         gray (or same-size BGR) operands, frontend.DecodedUploader takes frames as decoded (any size).
         `depth`: batches queued on the device before the oldest one's results are collected (default: 2 when the
@@ -89,10 +103,16 @@ class PairEngine:
         a third batch queued ahead measures within 1 % of two at 1080p and at 256x256 (profiles/r04_pcie_chunk_length.txt).
         Results do not depend on it.
         `flow`: "farneback" (ffl_flow_pairs) or "dis" (ffl_flow_pairs_dis with the _capi.DisParams `dis`, None = PRESET_FAST)
-        for every batch the engine queues."""
+        for every batch the engine queues.
+        `farneback`: _capi.FarnebackParams for the Farneback batches (ffl_flow_pairs_farneback; None: the reference's values
+        through the tuned ffl_flow_pairs)."""
         if flow not in _capi.FLOWS:
             raise ValueError(f"flow must be one of {_capi.FLOWS}, got {flow!r}")
-        self.flow, self.dis = flow, dis
+        if farneback is not None and flow == "dis":
+            raise ValueError("farneback parameters need flow='farneback'")
+        if farneback is not None:
+            _capi.farneback_geometry(ctx.width, ctx.height, farneback)
+        self.flow, self.dis, self.farneback = flow, dis, farneback
         self.ctx = ctx
         self.upload = upload or ctx.upload_frames
         self.B = ctx.max_batch
@@ -109,23 +129,27 @@ class PairEngine:
             raise ValueError(f"context too small: need frame_slots >= 2B+2 = {2 * self.B + 2} and "
                              f"flow_slots >= 2B+13 = {min_flow_slots(self.B)}")
 
-    def pass1(self, frames, pair_lo, pair_hi, pov_mode=False, cut_threshold=7.0, on_batch=None, algo=None):
+    def pass1(self, frames, pair_lo, pair_hi, pov_mode=False, cut_threshold=7.0, on_batch=None, algo=None, farneback=OWN):
         """Run pass 1 for pairs [pair_lo, pair_hi) of `frames`; flows stay resident in slot
         (j - pair_lo) % flow_slots.  Returns the list of (x, y, val, mean_mag, cut)."""
         fs = self.ctx.flow_slots
         return self.pass1_pairs(frames, range(pair_lo, pair_hi), lambda l: l % fs, pov_mode, cut_threshold,
-                                on_batch=(lambda ls, js, got: on_batch(js, got)) if on_batch else None, algo=algo)
+                                on_batch=(lambda ls, js, got: on_batch(js, got)) if on_batch else None, algo=algo,
+                                farneback=farneback)
 
-    def pass1_pairs(self, frames, pairs, slot_of, pov_mode=False, cut_threshold=7.0, on_batch=None, algo=None):
+    def pass1_pairs(self, frames, pairs, slot_of, pov_mode=False, cut_threshold=7.0, on_batch=None, algo=None,
+                    farneback=OWN):
         """Pass 1 for an arbitrary ascending list of pair indices (pair j = frames[j], frames[j+1]) in batches of
         max_batch; the flow of the l-th listed pair stays resident in flow slot slot_of(l).  Frames go to the
         device once per run of batches that needs them: a ring over the frame slots, frames of the batch being
         assembled are never evicted, and runs of consecutive frames landing in consecutive slots go up with one
         H2D transfer.  (The library orders an upload into a recycled slot behind the batches that still read
         it.)  on_batch(local_indices, pair_indices, records) is called per finished batch.  `algo` = (flow, dis) as
-        _capi.flow_choice returns it overrides the engine's own flow algorithm for this call only."""
+        _capi.flow_choice returns it overrides the engine's own flow algorithm for this call only, and `farneback`
+        (_capi.FarnebackParams, or None for the tuned path; as _capi.farneback_choice returns it) its Farneback parameters."""
         ctx, B, S = self.ctx, self.B, self.ctx.frame_slots
         algo, dis = algo if algo is not None else (getattr(self, "flow", "farneback"), getattr(self, "dis", None))
+        fb = getattr(self, "farneback", None) if farneback is OWN else farneback
         pairs = [int(j) for j in pairs]
         recs = [None] * len(pairs)
         resident, owner, state = {}, [None] * S, {"next": 0}
@@ -161,6 +185,8 @@ class PairEngine:
             f0, f1, fl = [resident[j] for j in js], [resident[j + 1] for j in js], [slot_of(l) for l in ls]
             if algo == "dis":
                 ctx.flow_pairs_dis(f0, f1, fl, pov_mode, dis)
+            elif fb is not None:
+                ctx.flow_pairs_farneback(f0, f1, fl, pov_mode, fb)
             else:
                 ctx.flow_pairs(f0, f1, fl, pov_mode)
             return ls, js
@@ -186,9 +212,9 @@ class PairEngine:
             collect(*pending.pop(0))
         return recs
 
-    def process_chunk(self, frames, pov_mode=False, cut_threshold=7.0, algo=None):
-        """One whole chunk on one GPU: returns (dots float64[n], records) with n = len(frames)-1.  `algo`: see
-        pass1_pairs (None: the engine's own flow algorithm)."""
+    def process_chunk(self, frames, pov_mode=False, cut_threshold=7.0, algo=None, farneback=OWN):
+        """One whole chunk on one GPU: returns (dots float64[n], records) with n = len(frames)-1.  `algo`, `farneback`:
+        see pass1_pairs (default: the engine's own flow algorithm and parameters)."""
         ctx, B = self.ctx, self.B
         n = len(frames) - 1
         if n < 1:
@@ -218,7 +244,7 @@ class PairEngine:
             state["known"] = js[-1] + 1
             finalize(n if state["known"] == n else max(0, state["known"] - SMOOTH_RADIUS))
 
-        self.pass1(frames, 0, n, pov_mode, cut_threshold, on_batch, algo=algo)
+        self.pass1(frames, 0, n, pov_mode, cut_threshold, on_batch, algo=algo, farneback=farneback)
         finalize(n)
         return dots, recs_all
 
@@ -231,6 +257,8 @@ def frames_to_actions(engine, frames, fps, params):
     # params["hip_flow"] / ["hip_dis"] pick the flow algorithm for this call (the engine itself is left as it is); without
     # them the engine's own algorithm runs
     algo = _capi.flow_choice(params) if ("hip_flow" in params or "hip_dis" in params) else None
+    # params["hip_farneback"] likewise sets the Farneback parameters of this call
+    fbk = farneback_kwargs(params, frames[0].shape[1], frames[0].shape[0]) if len(frames) else {}
     step, _, indices = postchain.sampling(fps, len(frames))
     bracket = int(params.get("batch_size", 3000.0))
     dots, cuts, frame_idx = [], [], []
@@ -239,7 +267,8 @@ def frames_to_actions(engine, frames, fps, params):
         if len(chunk) < 2:
             continue
         d, recs = engine.process_chunk([frames[i] for i in chunk], bool(params.get("pov_mode", False)),
-                                       float(params.get("cut_threshold", 7)), **({"algo": algo} if algo is not None else {}))
+                                       float(params.get("cut_threshold", 7)), **({"algo": algo} if algo is not None else {}),
+                                       **fbk)
         dots += [float(v) for v in d]
         cuts += [bool(r[4]) for r in recs]
         frame_idx += chunk[:-1]

@@ -194,12 +194,13 @@ def video_to_actions(ctx, capture, params, engine=None, ring_frames=None):
     engine = engine or pipeline.PairEngine(ctx, frontend.DecodedUploader(ctx, bool(params.get("vr_mode")), False))
     # params["hip_flow"] / ["hip_dis"] pick the flow algorithm for this call (a caller's engine is left as it is)
     algo = _capi.flow_choice(params) if ("hip_flow" in params or "hip_dis" in params) else None
+    fbk = pipeline.farneback_kwargs(params, ctx.width, ctx.height)   # params["hip_farneback"]: this call's parameters
     ring = PrefetchRing(ctx, capture, indices, bracket, ring_frames or 4 * ctx.max_batch + 2)
     dots, cuts, frame_idx = [], [], []
     try:
         for view, fidx in ring.chunks():
             d, recs = engine.process_chunk(view, bool(params.get("pov_mode", False)), float(params.get("cut_threshold", 7)),
-                                           **({"algo": algo} if algo is not None else {}))
+                                           **({"algo": algo} if algo is not None else {}), **fbk)
             dots += [float(v) for v in d]
             cuts += [bool(r[4]) for r in recs]
             frame_idx += fidx
@@ -248,7 +249,8 @@ def process_video(video_path, params, log_func, open_capture, make_context, prog
     try:
         ctx = make_context(cap)
         flow, dis = _capi.flow_choice(params)
-        engine = pipeline.PairEngine(ctx, frontend.DecodedUploader(ctx, bool(params.get("vr_mode")), False), flow=flow, dis=dis)
+        engine = pipeline.PairEngine(ctx, frontend.DecodedUploader(ctx, bool(params.get("vr_mode")), False), flow=flow, dis=dis,
+                                     farneback=_capi.farneback_choice(params))
         ring = PrefetchRing(ctx, cap, indices, int(params.get("batch_size", 3000.0)), 4 * ctx.max_batch + 2)
         dots, cuts, frame_idx, done = [], [], [], 0
         for view, fidx in ring.chunks():

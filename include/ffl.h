@@ -24,6 +24,8 @@
  *                           for a batch (ProcessPoolExecutor.submit loop, FF:1232-1236)
  *   ffl_download_flow       the "flow" entry of that dict (tests / callers that want the array)
  *   ffl_submit_pair         precompute_wrapper((p0, p1), params)                    FF:1019-1021
+ *   ffl_flow_pairs_farneback  cv2.calcOpticalFlowFarneback(p0, p1, None, pyr_scale, levels, winsize, iterations, poly_n,
+ *                           poly_sigma, 0) with the caller's values + the same reductions
  *   ffl_flow_pairs_dis      cv2.DISOpticalFlow_create(cv2.DISOPTICAL_FLOW_PRESET_FAST).calc(p0, p1, None)
  *                           + max_divergence + cartToPolar of the "DNN" backend     FF:948-980
  *                           (rules restated in DESIGN.md appendix D; parity with cv2 itself is unpinned)
@@ -184,6 +186,42 @@ int ffl_flow_pairs_dis(ffl_ctx *ctx, int n, const int *fslot0, const int *fslot1
  * slot 0.  Synchronous. */
 int ffl_debug_dis_pair(ffl_ctx *ctx, int f0, int f1, const ffl_dis_params *p, int scale, int stage, float *out);
 
+/* ---- Farneback with caller-chosen parameters -------------------------------------- */
+
+/* The six numeric parameters of cv2.calcOpticalFlowFarneback (and its flags).  Accepted: 0 < pyr_scale < 1,
+ * 0 <= levels <= 12, winsize odd 3..63, 1 <= iterations <= 10, poly_n 5 or 7, 0 < poly_sigma <= 3, flags == 0
+ * (OPTFLOW_USE_INITIAL_FLOW and OPTFLOW_FARNEBACK_GAUSSIAN are refused).  Float fields are computed with as the double of
+ * their shortest decimal form (1.2f as 1.2). */
+typedef struct ffl_farneback_params {
+    float pyr_scale;
+    int levels;
+    int winsize;
+    int iterations;
+    int poly_n;
+    float poly_sigma;
+    int flags;
+} ffl_farneback_params;
+
+/* The reference's call: (0.5, 3, 15, 3, 5, 1.2, 0). */
+int ffl_farneback_default_params(ffl_farneback_params *out);
+
+/* Scales of a width x height frame under p after A.1's min_size = 32 rule (levels used + 1), and the per-pair working set
+ * of the general kernels in bytes (two frames' expansions of every level + M + two level flows).  FFL_ERR_INVALID with a
+ * message (ffl_last_error(NULL)) for parameters outside the rules above, or a level Gaussian wider than 191 taps. */
+int ffl_farneback_geometry(int width, int height, const ffl_farneback_params *p, int *n_scales, size_t *work_bytes_per_pair);
+
+/* Device bytes ffl_flow_pairs_farneback(p) may allocate on top of ffl_estimate_bytes for a context of this size and
+ * max_batch under the current "lanes" option: 0 when every lane's buffers hold the working set, else the general-path
+ * work areas (one per lane, allocated on first use, freed by ffl_destroy). */
+int ffl_farneback_extra_bytes(int width, int height, int max_batch, const ffl_farneback_params *p, size_t *bytes);
+
+/* ffl_flow_pairs with caller-chosen parameters (p == NULL: the defaults): same slots, events, lanes and pass-1 records.
+ * p equal to the defaults calls ffl_flow_pairs (the tuned kernels and their graphs) unless the context option
+ * "fb_general" is 1; any other p runs the general kernels, launched eagerly (never captured).  Parameters are refused
+ * before any device work.  Asynchronous. */
+int ffl_flow_pairs_farneback(ffl_ctx *ctx, int n, const int *fslot0, const int *fslot1, const int *flow_slots, int pov_mode,
+                             const ffl_farneback_params *p);
+
 /* ---- parity-test hooks (used by tests/ only) ------------------------------------------------ */
 
 /* Number of pyramid scales minus one for this context's size (3 for every BASELINE config). */
@@ -231,7 +269,9 @@ int ffl_debug_pair(ffl_ctx *ctx, int f0, int f1, int level, int iter, float *I0,
  *   "pyr_coarse"  = 0|1      1 (default): the x1/4 and x1/8 pyramid levels of frames whose sides are multiples of 8
  *                            come from one LDS-staged pass (k_pyr_coarse); 0: horizontal + vertical kernel pairs
  *   "tile_order"  = 0|1      k_blur_solve / k_update_matrices workgroup order: 0 pair-major (default), 1 tile-major
- *                            (every tile for all pairs of the batch back to back; less fabric traffic, not faster) */
+ *                            (every tile for all pairs of the batch back to back; less fabric traffic, not faster)
+ *   "fb_general"  = 0|1      1: ffl_flow_pairs_farneback runs the default parameters through the general kernels as well
+ *                            (test and measurement hook; the results are the same bits) */
 int ffl_set_option(const char *name, int value);
 int ffl_ctx_set_option(ffl_ctx *ctx, const char *name, int value);
 int ffl_ctx_get_option(ffl_ctx *ctx, const char *name, int *value);

@@ -1,0 +1,230 @@
+"""Host tests of Farneback with caller-chosen parameters: parameter rules and routing,
+the plain-C restatement (tests/fb_general_ref) against the oracle at the reference's values and against the independent
+numpy restatement (tests/np_farneback.py) under every fixture parameter set, known translations, and the committed
+fixtures.  No GPU needed.  Parity with cv2 itself stays unpinned."""
+import json
+
+import numpy as np
+import pytest
+
+import fb_general_ref as fbr
+import gen_fb_params_golden as gen
+import np_farneback as npf
+import oracle as orc
+from funscript_flow_amd import _capi, backend, pipeline
+from funscript_flow_amd.synth import sine_translate_frames
+
+from test_dis_host import _shifted
+
+MARGIN = 24
+
+
+def _np_params(over):
+    """np_farneback's keyword arguments for a parameter set: float fields as the restatement widens them (F.0)"""
+    p = dict(fbr.DEFAULTS, **over)
+    return dict(pyr_scale=fbr.widen(p["pyr_scale"]), levels=p["levels"], winsize=p["winsize"], iters=p["iterations"],
+                poly_n=p["poly_n"], poly_sigma=fbr.widen(p["poly_sigma"]))
+
+
+# ---- rules and routing ---------------------------------------------------------------------------------------------
+
+REFUSED = [
+    ({"pyr_scale": 0.0}, "pyr_scale"), ({"pyr_scale": 1.0}, "pyr_scale"), ({"levels": -1}, "levels"),
+    ({"levels": 13}, "levels"), ({"winsize": 4}, "winsize"), ({"winsize": 1}, "winsize"), ({"winsize": 65}, "winsize"),
+    ({"iterations": 0}, "iterations"), ({"iterations": 11}, "iterations"), ({"poly_n": 6}, "poly_n"),
+    ({"poly_n": 3}, "poly_n"), ({"poly_sigma": 0.0}, "poly_sigma"), ({"poly_sigma": 3.5}, "poly_sigma"),
+    ({"flags": 4}, "OPTFLOW_USE_INITIAL_FLOW"), ({"flags": 256}, "OPTFLOW_FARNEBACK_GAUSSIAN"), ({"flags": 1}, "flags"),
+]
+
+
+@pytest.mark.parametrize("over,word", REFUSED)
+def test_each_refusal_names_its_rule(over, word):
+    with pytest.raises(ValueError, match=word):
+        _capi.farneback_choice({"hip_farneback": over})
+    with pytest.raises(ValueError, match=word):
+        _capi.farneback_geometry(256, 256, _capi.FarnebackParams(**over))
+    assert word in fbr.check(over)
+
+
+def test_defaults_route_to_the_tuned_path():
+    assert _capi.farneback_choice({}) is None
+    assert _capi.farneback_choice({"hip_farneback": {}}) is None
+    assert _capi.farneback_choice({"hip_farneback": {"pyr_scale": 0.5, "levels": 3, "winsize": 15, "iterations": 3,
+                                                     "poly_n": 5, "poly_sigma": 1.2, "flags": 0}}) is None
+    p = _capi.farneback_choice({"hip_farneback": {"poly_n": 7, "poly_sigma": 1.5}})
+    assert p.as_dict()["poly_n"] == 7 and abs(p.poly_sigma - 1.5) < 1e-7 and not p.is_default()
+    d = _capi.FarnebackParams()
+    assert _capi.load().ffl_farneback_default_params(_capi.C.byref(d)) == 0 and d.is_default()
+
+
+def test_unknown_names_bad_types_and_dis_are_refused():
+    with pytest.raises(ValueError, match="unknown"):
+        _capi.farneback_choice({"hip_farneback": {"win_size": 21}})
+    with pytest.raises(ValueError, match="integer"):
+        _capi.farneback_choice({"hip_farneback": {"winsize": 21.5}})
+    with pytest.raises(ValueError, match="dis"):
+        _capi.farneback_choice({"hip_flow": "dis", "hip_farneback": {"levels": 5}})
+
+
+def test_geometry_of_product_and_restatement_agree():
+    for wh in ((256, 256), (640, 360), (1920, 1080), (333, 197), (3840, 2160), (16, 16), (5760, 2880)):
+        for _, _, _, over in gen.CASES + [("", 0, 0, {"pyr_scale": 0.9, "levels": 12}),
+                                         ("", 0, 0, {"pyr_scale": 0.3, "levels": 12}), ("", 0, 0, {"levels": 0})]:
+            try:
+                got = _capi.farneback_geometry(*wh, _capi.FarnebackParams(**over))[0]
+            except ValueError:
+                got = None
+            assert got == fbr.geometry(*wh, over), (wh, over)
+    assert _capi.farneback_geometry(256, 256)[0] == orc.num_levels(256, 256) + 1
+    assert _capi.farneback_geometry(1920, 1080, _capi.FarnebackParams(levels=5))[0] == 6
+    with pytest.raises(ValueError, match="5760x2880"):   # a level Gaussian wider than 191 taps: refused with the size
+        _capi.farneback_geometry(5760, 2880, _capi.FarnebackParams(pyr_scale=0.11, levels=2))
+    assert fbr.geometry(5760, 2880, {"pyr_scale": 0.11, "levels": 2}) is None
+
+
+def test_extra_bytes_are_zero_when_the_lane_buffers_hold_the_working_set():
+    assert _capi.farneback_extra_bytes(256, 256, 64, _capi.FarnebackParams(poly_n=7, poly_sigma=1.5)) == 0
+    assert _capi.farneback_extra_bytes(256, 256, 64, _capi.FarnebackParams(pyr_scale=0.9, levels=12)) > 0
+
+
+# ---- the restatement -----------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("w,h", [(256, 256), (640, 360), (333, 197)])
+def test_restatement_at_the_defaults_is_the_oracle_bit_for_bit(w, h):
+    fr = sine_translate_frames(2, w, h, seed=5, amp=(2.5, 1.5), period=5, zoom=0.02)
+    got = fbr.flow(fr[0], fr[1])
+    assert np.array_equal(got, orc.farneback(fr[0], fr[1]))
+    assert fbr.geometry(w, h) == orc.num_levels(w, h) + 1
+
+
+def _bound(case, flow):
+    """2e-5 px, test_second_restatement_agrees' bound, for fields of a few pixels.  Fixed before the first run: the bound
+    scales with the field's largest magnitude over 4 px (float32 carries the flow with a relative, not absolute, error, and
+    the levels-5 1080p field reaches ~20 px), and winsize 3 gets 10x: its 3x3 normal equations have determinants ~25x
+    smaller than the 15x15 window's on the same texture, so an ulp-level difference in M (np_farneback's Gaussian and G
+    matrix are rounded differently) is amplified accordingly."""
+    b = 2e-5 * max(1.0, float(np.max(np.abs(flow))) / 4.0)
+    return b * 10 if case == "winsize3" else b
+
+
+@pytest.mark.parametrize("case", [c[0] for c in gen.CASES])
+def test_restatement_agrees_with_the_numpy_restatement(case):
+    name, w, h, over = next(c for c in gen.CASES if c[0] == case)
+    f0, f1 = gen.frames(w, h)
+    nk = _np_params(over)
+    # stages where np_farneback has them: every pyramid level, PolyExp with (poly_n, poly_sigma), blur + solve with winsize
+    for k in range(fbr.geometry(w, h, over)):
+        lw, lh, sigma, ks = fbr.level_params(w, h, over, k)
+        I_np = npf.resize_linear(npf.gaussian_blur(f0.astype(np.float32), ks, sigma), lw, lh)
+        assert np.max(np.abs(fbr.pyr_level(f0, over, k) - I_np)) <= 2e-4, ("pyramid level", k)
+    flow, d = fbr.flow(f0, f1, over, dump=(0, 1))
+    Rn = npf.polyexp(d["I0"], nk["poly_n"], nk["poly_sigma"])
+    Rc = fbr.polyexp(d["I0"], nk["poly_n"], nk["poly_sigma"])
+    assert np.array_equal(Rc, d["R0"])
+    assert np.max(np.abs(np.moveaxis(Rc, 0, -1) - Rn)) <= 1e-5 * max(1.0, float(np.max(np.abs(Rn)))), "polyexp"
+    bs_c = fbr.blur_solve(d["M"], nk["winsize"])
+    bs_n = npf.blur_solve(np.moveaxis(d["M"], 0, -1), nk["winsize"] // 2)
+    assert np.max(np.abs(bs_c - bs_n)) <= _bound(case, bs_n), "blur_solve"
+    want = npf.farneback(f0, f1, **nk)
+    assert flow.shape == want.shape == (h, w, 2)
+    assert float(np.max(np.abs(flow - want))) <= _bound(case, want), float(np.max(np.abs(flow - want)))
+
+
+@pytest.mark.parametrize("over", [{"levels": 5}, {"pyr_scale": 0.7, "levels": 6}, {"winsize": 31},
+                                  {"poly_n": 7, "poly_sigma": 1.5}, {"iterations": 1}, {"winsize": 5, "iterations": 6}])
+@pytest.mark.parametrize("d", [(3.0, -2.0), (-1.5, 0.75)])
+def test_known_translation_is_recovered_with_the_right_sign(over, d):
+    """I1(x + d) = I0(x): the median field has d's sign in both components and 75..110 % of its size.  (A first bound of
+    0.25 px failed for the defaults themselves: on this texture Farneback recovers 0.88-0.91 of the shift at the reference's
+    values and 0.83 with a 5x5 window -- the 1e-3 regulariser of the solve and the level blur, not a sign or scale slip.)
+    levels 5 runs at 1024x1024, where A.1's min_size rule leaves all five levels."""
+    wh = 1024 if over.get("levels") == 5 else 256
+    I0, I1 = _shifted(*d, w=wh, h=wh)
+    assert fbr.geometry(wh, wh, over) == (6 if over.get("levels") == 5 else fbr.geometry(wh, wh, over))
+    flow = fbr.flow(I0, I1, over)[MARGIN:-MARGIN, MARGIN:-MARGIN].reshape(-1, 2)
+    med = np.median(flow, 0)
+    assert np.all(np.sign(med) == np.sign(d)), med
+    ratio = med / np.array(d)
+    assert np.all((ratio > 0.75) & (ratio < 1.1)), ratio
+
+
+def test_restatement_reproduces_the_committed_fixtures(golden_dir):
+    g = np.load(f"{golden_dir}/fb_params_golden.npz")
+    assert list(g["names"]) == [c[0] for c in gen.CASES]
+    for i, (name, w, h, over) in enumerate(gen.CASES):
+        assert json.loads(str(g["params"][i])) == over, name
+        f0, f1 = gen.frames(w, h)
+        assert gen.sha(f0) + gen.sha(f1) == g["frames_sha256"][i], name
+        flow = fbr.flow(f0, f1, over)
+        assert gen.sha(flow) == g["flow_sha256"][i], name
+        x, y, v, m, r = gen.record(flow)
+        assert (x, y) == tuple(g["pass1_xy"][i]) and v == g["pass1_div"][i] and m == g["pass1_mean_mag"][i], name
+        assert r == list(g["radial"][i]), name
+
+
+# ---- Python wiring (no device: a recording stand-in for the context) -------------------------------------------------
+
+class _Ctx:
+    def __init__(self, B=4, frame_slots=32, flow_slots=32, w=256, h=256):
+        self.max_batch, self.frame_slots, self.flow_slots, self.width, self.height = B, frame_slots, flow_slots, w, h
+        self.calls = []
+
+    def upload_frames(self, first, frames):
+        pass
+
+    def flow_pairs(self, f0, f1, slots, pov):
+        self.calls.append(("tuned", len(slots), None))
+
+    def flow_pairs_farneback(self, f0, f1, slots, pov, params=None):
+        self.calls.append(("general", len(slots), params.as_dict() if params is not None else None))
+
+    def pass1_results(self, slots, thr):
+        return [(0, 0, 0.0, 0.0, False)] * len(slots)
+
+    def radial(self, slots, centers, cuts, pov):
+        return np.zeros(len(slots))
+
+
+def test_pair_engine_sends_its_parameters_and_a_per_call_override_wins():
+    fr = [np.zeros((256, 256), np.uint8)] * 9
+    p = _capi.FarnebackParams(winsize=21, poly_n=7, poly_sigma=1.5)
+    ctx = _Ctx()
+    eng = pipeline.PairEngine(ctx, farneback=p)
+    eng.process_chunk(fr)
+    assert ctx.calls and all(c[0] == "general" and c[2] == p.as_dict() for c in ctx.calls)
+    ctx.calls.clear()
+    eng.process_chunk(fr, farneback=None)                          # per call: the tuned path
+    assert ctx.calls and all(c[0] == "tuned" for c in ctx.calls)
+    ctx.calls.clear()
+    pipeline.PairEngine(ctx).process_chunk(fr)                      # default engine: unchanged
+    assert ctx.calls and all(c[0] == "tuned" for c in ctx.calls)
+    with pytest.raises(ValueError):
+        pipeline.PairEngine(ctx, flow="dis", farneback=p)
+
+
+def test_frames_to_actions_honours_hip_farneback_without_changing_the_engine(monkeypatch):
+    from funscript_flow_amd import postchain
+    monkeypatch.setattr(postchain, "actions_from_scalars", lambda *a: [])
+    ctx = _Ctx(B=8, frame_slots=64, flow_slots=64)
+    eng = pipeline.PairEngine(ctx, depth=1)
+    frames = [np.zeros((256, 256), np.uint8)] * 40
+    pipeline.frames_to_actions(eng, frames, 30.0, {"hip_farneback": {"levels": 5}})
+    assert ctx.calls and all(c[0] == "general" and c[2]["levels"] == 5 for c in ctx.calls)
+    assert eng.farneback is None
+    ctx.calls.clear()
+    pipeline.frames_to_actions(eng, frames, 30.0, {})
+    assert ctx.calls and all(c[0] == "tuned" for c in ctx.calls)
+
+
+def test_unservable_sizes_are_refused_up_front_with_the_size():
+    bad = {"pyr_scale": 0.11, "levels": 2}
+    ctx = _Ctx(w=5760, h=2880)
+    with pytest.raises(ValueError, match="5760x2880"):
+        pipeline.PairEngine(ctx, farneback=_capi.FarnebackParams(**bad))
+    frames = [np.zeros((2880, 5760), np.uint8)] * 2
+    with pytest.raises(ValueError, match="5760x2880"):
+        backend.precompute_all(list(zip(frames[:-1], frames[1:])), {"hip_farneback": bad})
+    with pytest.raises(ValueError, match="5760x2880"):
+        backend.precompute_flow_info(frames[0], frames[1], {"backend": "HIP", "hip_farneback": bad})
+    with pytest.raises(ValueError, match="5760x2880"):
+        pipeline.frames_to_actions(pipeline.PairEngine(ctx, depth=1), frames, 30.0, {"hip_farneback": bad})
