@@ -21,7 +21,11 @@ EXPORTS = ["ffl_device_count", "ffl_create", "ffl_destroy", "ffl_last_error", "f
            "ffl_num_levels", "ffl_level_size", "ffl_download_frame", "ffl_debug_pair", "ffl_set_option", "ffl_ctx_set_option", "ffl_ctx_get_option", "ffl_graph_stats", "ffl_profile_enable",
            "ffl_profile_read", "ffl_kernel_name", "ffl_device_mem_info", "ffl_estimate_bytes",
            "ffl_dis_default_params", "ffl_dis_geometry", "ffl_flow_pairs_dis", "ffl_debug_dis_pair",
-           "ffl_farneback_default_params", "ffl_farneback_geometry", "ffl_farneback_extra_bytes", "ffl_flow_pairs_farneback"]
+           "ffl_farneback_default_params", "ffl_farneback_geometry", "ffl_farneback_extra_bytes", "ffl_flow_pairs_farneback",
+           "ffl_upload_frames_yuv", "ffl_frontend_yuv_window"]
+
+# 4:2:0 layouts of ffl_upload_frames_yuv (FFL_YUV_I420, FFL_YUV_NV12): cv2's single-array (3h/2, w) uint8 frames
+YUV_LAYOUTS = {"i420": 0, "nv12": 1}
 
 FLOWS = ("farneback", "dis")   # params["hip_flow"]: the reference's CPU/CUDA/OpenCL branch, or its "DNN" branch (FF:948-980)
 DIS_STAGES = {"pass1": 0, "pass2": 1, "dense": 2, "refined": 3, "images": 4}   # ffl_debug_dis_pair stages
@@ -138,6 +142,31 @@ class FFLError(RuntimeError):
     pass
 
 
+def yuv_layout(layout):
+    """FFL_YUV_* code of "i420" / "nv12" (or of the code itself); ValueError for anything else"""
+    if isinstance(layout, str) and layout.lower() in YUV_LAYOUTS:
+        return YUV_LAYOUTS[layout.lower()]
+    if not isinstance(layout, str) and layout in YUV_LAYOUTS.values():
+        return int(layout)
+    raise ValueError(f"YUV layout must be one of {sorted(YUV_LAYOUTS)}, got {layout!r}")
+
+
+def frontend_yuv_window(src_size, layout, resize, crop, out_size, stride=None):
+    """((x, y, w, h), bytes per frame) of the source rectangle ffl_upload_frames_yuv transfers for a src_size = (w, h)
+    4:2:0 frame, resized to `resize` = (w, h) and cropped at `crop` = (x, y) to out_size = (w, h).
+    ValueError with the library's reason for what it refuses.  stride defaults to the source width; an int layout is
+    passed to the library as it is."""
+    sw, sh = int(src_size[0]), int(src_size[1])
+    win, b = (C.c_int * 4)(), C.c_size_t()
+    L = load()
+    code = layout if isinstance(layout, int) else yuv_layout(layout)
+    if L.ffl_frontend_yuv_window(sw, sh, code, int(sw if stride is None else stride), int(resize[0]),
+                                 int(resize[1]), int(crop[0]), int(crop[1]), int(out_size[0]), int(out_size[1]), win,
+                                 C.byref(b)) != FFL_OK:
+        raise ValueError(L.ffl_last_error(None).decode())
+    return tuple(win), b.value
+
+
 _lib = None
 
 
@@ -161,6 +190,9 @@ def load():
     L.ffl_upload_frames.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_ssize_t]
     L.ffl_upload_frames_raw.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.c_ssize_t, C.c_int,
                                         C.c_int, C.c_int, C.c_int, C.c_int]
+    L.ffl_upload_frames_yuv.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.c_ssize_t, C.c_int,
+                                        C.c_int, C.c_int, C.c_int, C.c_int]
+    L.ffl_frontend_yuv_window.argtypes = [C.c_int, C.c_int, C.c_int, C.c_ssize_t] + [C.c_int] * 6 + [ip, C.POINTER(C.c_size_t)]
     L.ffl_flow_pairs.argtypes = [vp, C.c_int, ip, ip, ip, C.c_int]
     L.ffl_pass1_result.argtypes = [vp, C.c_int, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                    C.POINTER(C.c_float), C.POINTER(C.c_float), ip]
@@ -323,14 +355,15 @@ class Context:
         self._chk(self.L.ffl_upload_frames(self._h, first_slot, len(fr), ptrs, f0.shape[1], f0.shape[0], ch,
                                            f0.strides[0]))
 
-    def pinned_frames(self, n, channels=1, size=None):
+    def pinned_frames(self, n, channels=1, size=None, yuv=False):
         """(n, height, width[, 3]) uint8 array in page-locked memory of this context (ffl_host_alloc): frames a
         decoder writes into consecutive entries go to the device without the staging copy.  Do not overwrite an
         entry before the batch that uses it has returned results (or ctx.sync()).  `size=(w, h)`: decoded source
-        frames of another size, for upload_frames_raw.  The memory belongs to the context: the array (and every
-        view of it) must not be touched after ctx.close()."""
+        frames of another size, for upload_frames_raw.  yuv=True: (n, 3h/2, w) 4:2:0 frames for upload_frames_yuv
+        (channels is ignored).  The memory belongs to the context: the array (and every view of it) must not be
+        touched after ctx.close()."""
         w, h = size if size is not None else (self.width, self.height)
-        shape = (n, h, w) + ((channels,) if channels != 1 else ())
+        shape = (n, h * 3 // 2, w) if yuv else (n, h, w) + ((channels,) if channels != 1 else ())
         nbytes = int(np.prod(shape))
         p = C.c_void_p()
         self._chk(self.L.ffl_host_alloc(self._h, nbytes, C.byref(p)))
@@ -349,6 +382,22 @@ class Context:
         self._chk(self.L.ffl_upload_frames_raw(self._h, first_slot, len(fr), ptrs, f0.shape[1], f0.shape[0],
                                                f0.strides[0], int(bool(rgb_order)), int(resize[0]), int(resize[1]),
                                                int(crop[0]), int(crop[1])))
+
+    def upload_frames_yuv(self, first_slot, frames, layout, resize, crop=(0, 0)):
+        """Decoded 4:2:0 frames -- (3h/2, w) uint8 arrays, cv2's single-array I420 / NV12 layout, layout "i420" or "nv12"
+        -- -> gray(resize(YUV2BGR(frame), resize)[crop window]) in consecutive slots.  Only the
+        source rectangle the window reads is transferred.  Rows must be contiguous (an NV12 row pitch may exceed w)."""
+        code = yuv_layout(layout)
+        fr = [f if (f.ndim == 2 and f.strides[1] == 1) else np.ascontiguousarray(f) for f in frames]
+        f0 = fr[0]
+        if any(f.dtype != np.uint8 or f.ndim != 2 or f.shape != f0.shape or f.strides[0] != f0.strides[0] for f in fr):
+            raise FFLError("upload_frames_yuv needs (3h/2, w) uint8 frames of one shape and row stride")
+        if f0.shape[0] % 3:
+            raise FFLError(f"upload_frames_yuv: a 4:2:0 frame has 3h/2 rows, got {f0.shape[0]}")
+        ptrs = (C.c_void_p * len(fr))(*[f.ctypes.data for f in fr])
+        self._chk(self.L.ffl_upload_frames_yuv(self._h, first_slot, len(fr), ptrs, f0.shape[1], f0.shape[0] * 2 // 3,
+                                               f0.strides[0], code, int(resize[0]), int(resize[1]), int(crop[0]),
+                                               int(crop[1])))
 
     def flow_pairs(self, fslot0, fslot1, flow_slots, pov_mode=False):
         n = len(flow_slots)

@@ -997,6 +997,174 @@ int ffl_upload_frames_raw(ffl_ctx *c, int first, int n, const uint8_t *const *fr
     return publish_frames(c, first, n);
 }
 
+// ---- 4:2:0 YUV input ---------------------------------------------------------------
+// Where the source rectangle of a YUV upload lies: the source rows / columns the crop window's first and last output
+// row / column map to (k_frontend_yuv's arithmetic; it is monotone in the output coordinate), widened by one pixel per side
+// and rounded out -- rows to even coordinates (chroma alignment), columns to multiples of 16 so that the rows of every
+// plane start aligned in the frame (a 2-D copy out of host memory whose rows start unaligned ran at 0.3 GB/s) --
+// and clamped to the frame.  The widening makes it a superset even if host and device round the coordinate arithmetic
+// differently; it is not tight to the last pixel.
+struct YuvWin {
+    int mode, x0, y0, w, h;  // k_frontend_yuv mode; window origin and size (all even)
+    double scale_x, scale_y;
+};
+
+static void yuv_span(int d0, int d1, int s, double scale, int mode, int align, int *lo, int *hi_excl) {
+    int a, b;  // first and last source coordinate the kernel loads (inclusive)
+    if (mode == FFL_FRONT_IDENTITY) {
+        a = d0; b = d1;
+    } else if (mode == FFL_FRONT_AREA2) {
+        a = 2 * d0; b = 2 * d1 + 1;
+    } else {
+        a = (int)floorf((float)((d0 + 0.5) * scale - 0.5));
+        b = (int)floorf((float)((d1 + 0.5) * scale - 0.5)) + 1;
+    }
+    a = std::min(std::max(a - 1, 0), s - 1) / align * align;
+    b = std::min(std::max(b + 1, 0), s - 1) + 1;
+    *lo = a;
+    *hi_excl = std::min((b + align - 1) / align * align, s);  // s is even
+}
+
+// Every refusal of the YUV path (messages name the rule); fn prefixes the message.
+static int yuv_window(ffl_ctx *c, const char *fn, int sw, int sh, int layout, ptrdiff_t stride, int rw, int rh, int crop_x,
+                      int crop_y, int ow, int oh, YuvWin *out) {
+    if (sw < 2 || sh < 2 || sw > 32768 || sh > 32768 || rw < 1 || rh < 1 || rw > 32768 || rh > 32768 || ow < 1 || oh < 1)
+        return set_err(c, FFL_ERR_INVALID, "%s: unsupported source %dx%d / resize %dx%d / output %dx%d", fn, sw, sh, rw, rh, ow, oh);
+    if ((sw & 1) || (sh & 1))
+        return set_err(c, FFL_ERR_INVALID, "%s: 4:2:0 needs an even width and height, source is %dx%d", fn, sw, sh);
+    if (layout != FFL_YUV_I420 && layout != FFL_YUV_NV12)
+        return set_err(c, FFL_ERR_INVALID, "%s: unknown layout %d (FFL_YUV_I420 0, FFL_YUV_NV12 1)", fn, layout);
+    if (layout == FFL_YUV_I420 && stride != (ptrdiff_t)sw)
+        return set_err(c, FFL_ERR_INVALID, "%s: I420 needs stride == width (contiguous U and V planes), got %td for width %d",
+                       fn, stride, sw);
+    if (layout == FFL_YUV_NV12 && stride < (ptrdiff_t)sw)
+        return set_err(c, FFL_ERR_INVALID, "%s: NV12 needs stride >= width, got %td for width %d", fn, stride, sw);
+    if (crop_x < 0 || crop_y < 0 || crop_x + ow > rw || crop_y + oh > rh)
+        return set_err(c, FFL_ERR_INVALID, "%s: crop window (%d, %d) + %dx%d does not fit the %dx%d resized frame", fn, crop_x,
+                       crop_y, ow, oh, rw, rh);
+    out->mode = (rw == sw && rh == sh) ? FFL_FRONT_IDENTITY : (sw == 2 * rw && sh == 2 * rh) ? FFL_FRONT_AREA2 : FFL_FRONT_GENERIC;
+    out->scale_x = 1. / ((double)rw / sw);
+    out->scale_y = 1. / ((double)rh / sh);
+    int x1, y1;
+    yuv_span(crop_x, crop_x + ow - 1, sw, out->scale_x, out->mode, 16, &out->x0, &x1);
+    yuv_span(crop_y, crop_y + oh - 1, sh, out->scale_y, out->mode, 2, &out->y0, &y1);
+    out->w = x1 - out->x0;
+    out->h = y1 - out->y0;
+    return FFL_OK;
+}
+
+int ffl_frontend_yuv_window(int src_w, int src_h, int layout, ptrdiff_t stride_bytes, int resize_w, int resize_h, int crop_x,
+                            int crop_y, int out_w, int out_h, int win[4], size_t *bytes) {
+    YuvWin yw;
+    if (int rc = yuv_window(nullptr, "ffl_frontend_yuv_window", src_w, src_h, layout, stride_bytes, resize_w, resize_h, crop_x,
+                            crop_y, out_w, out_h, &yw))
+        return rc;
+    if (win) {
+        win[0] = yw.x0; win[1] = yw.y0; win[2] = yw.w; win[3] = yw.h;
+    }
+    if (bytes) *bytes = (size_t)yw.w * yw.h * 3 / 2;
+    return FFL_OK;
+}
+
+// Decoded 4:2:0 frames -> gray frame slots through k_frontend_yuv.  Frame by frame, as ffl_upload_frames_raw: only the
+// window the crop samples travels -- out of ffl_host_alloc memory one 2-D copy per plane (when every plane's rows start
+// 4-byte aligned and are a multiple of 4 bytes long: unaligned ones take a slow path in the runtime's copy), otherwise
+// copied into the pinned ring buffer and sent as one transfer.  On the device the window is packed: Y (w x h), then U and V (w/2 x h/2 each,
+// I420) or the interleaved UV rows (w x h/2, NV12).
+int ffl_upload_frames_yuv(ffl_ctx *c, int first, int n, const uint8_t *const *frames, int sw, int sh, ptrdiff_t stride_bytes,
+                          int layout, int rw, int rh, int crop_x, int crop_y) {
+    if (!c) return FFL_ERR_INVALID;
+    std::unique_lock<std::mutex> ul(c->up_mu);
+    CtxLock lk(c->mu);
+    if (!frames || n < 1 || first < 0 || first + n > c->n_fslots)
+        return set_err(c, FFL_ERR_INVALID, "ffl_upload_frames_yuv: bad frame slot range %d..%d", first, first + n - 1);
+    YuvWin yw;
+    if (int rc = yuv_window(c, "ffl_upload_frames_yuv", sw, sh, layout, stride_bytes, rw, rh, crop_x, crop_y, c->w, c->h, &yw))
+        return rc;
+    for (int i = 0; i < n; i++)
+        if (!frames[i]) return set_err(c, FFL_ERR_INVALID, "ffl_upload_frames_yuv: frame %d is NULL", i);
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool nv12 = layout == FFL_YUV_NV12;
+    const size_t ybytes = (size_t)yw.w * yw.h, fbytes = ybytes * 3 / 2;
+    // the planes of the window: source offset and pitch inside the frame, row bytes, rows, offset in the packed window
+    struct Plane {
+        size_t src, dst;
+        ptrdiff_t pitch;
+        size_t row;
+        int rows;
+    } pl[3];
+    const size_t cw = (size_t)sw / 2, ch = (size_t)sh / 2;
+    pl[0] = {(size_t)yw.y0 * stride_bytes + yw.x0, 0, stride_bytes, (size_t)yw.w, yw.h};
+    int np = 3;
+    if (nv12) {
+        pl[1] = {(size_t)(sh + yw.y0 / 2) * stride_bytes + yw.x0, ybytes, stride_bytes, (size_t)yw.w, yw.h / 2};
+        np = 2;
+    } else {
+        const size_t u0 = (size_t)sh * sw + (size_t)(yw.y0 / 2) * cw + yw.x0 / 2;
+        pl[1] = {u0, ybytes, (ptrdiff_t)cw, (size_t)yw.w / 2, yw.h / 2};
+        pl[2] = {u0 + ch * cw, ybytes + ybytes / 4, (ptrdiff_t)cw, (size_t)yw.w / 2, yw.h / 2};
+    }
+    const size_t span = (size_t)stride_bytes * (sh + sh / 2 - 1) + sw;  // bytes of one frame array
+    FrontYuvParams fp;
+    fp.sw = sw; fp.sh = sh;
+    fp.wx = yw.x0; fp.wy = yw.y0;
+    fp.y_pitch = yw.w;
+    fp.c_pitch = nv12 ? yw.w : yw.w / 2;
+    fp.c_step = nv12 ? 2 : 1;
+    fp.cx = crop_x; fp.cy = crop_y; fp.ow = c->w; fp.oh = c->h;
+    fp.scale_x = yw.scale_x; fp.scale_y = yw.scale_y;
+    fp.mode = yw.mode;
+    for (int i = 0; i < n; i++) {
+        const int fs = first + i;
+        auto &rb = c->raw[c->raw_next++ % FFL_RAW_RING];
+        if (rb.busy) {  // its previous frame has left both buffers
+            if (int rc = wait_unlocked(c, lk, &rb.ev, 1)) return rc;
+        }
+        if (rb.cap < fbytes) {
+            hipFree(rb.d);
+            hipHostFree(rb.h);
+            rb.d = rb.h = nullptr;
+            rb.cap = 0;
+            HIPCHK(c, hipMalloc(&rb.d, fbytes));
+            HIPCHK(c, hipHostMalloc(&rb.h, fbytes, hipHostMallocDefault));
+            rb.cap = fbytes;
+        }
+        if (!rb.ev) HIPCHK(c, hipEventCreateWithFlags(&rb.ev, hipEventDisableTiming));
+        const uint8_t *data = frames[i];
+        bool direct = in_host_buf(c, data, span);
+        for (int k = 0; direct && k < np; k++)
+            direct = ((uintptr_t)(data + pl[k].src) | (size_t)pl[k].pitch | pl[k].row) % 4 == 0;
+        if (!direct) {
+            const int copy_threads = c->opt.copy_threads;
+            lk.unlock();  // the staging copy runs without the context lock (up_mu protects the ring and the pool)
+            const uint8_t *src[2] = {data + pl[0].src, nullptr};
+            c->pool.copy(rb.h, src, 1, pl[0].pitch, pl[0].row, pl[0].rows, copy_threads);
+            src[0] = data + pl[1].src;
+            if (!nv12) src[1] = data + pl[2].src;  // U and V are shaped alike and packed back to back: one shared copy
+            c->pool.copy(rb.h + pl[1].dst, src, nv12 ? 1 : 2, pl[1].pitch, pl[1].row, pl[1].rows, copy_threads);
+            lk.lock();
+        }
+        // looked up under the lock, after the staging copy: a batch queued meanwhile is ordered ahead of the transfer
+        WaitOnce wait_copy(c->s_copy);
+        if (int rc = wait_frame_free(c, wait_copy, fs)) return rc;
+        if (direct) {
+            for (int k = 0; k < np; k++)
+                HIPCHK(c, hipMemcpy2DAsync(rb.d + pl[k].dst, pl[k].row, data + pl[k].src, (size_t)pl[k].pitch, pl[k].row,
+                                           (size_t)pl[k].rows, hipMemcpyHostToDevice, c->s_copy));
+        } else {
+            HIPCHK(c, hipMemcpyAsync(rb.d, rb.h, fbytes, hipMemcpyHostToDevice, c->s_copy));
+        }
+        {
+            ProfScope ps(c, FFL_K_FRONTEND, c->s_copy);
+            const uint8_t *u = rb.d + ybytes, *v = nv12 ? u + 1 : u + ybytes / 4;
+            ffl_launch_frontend_yuv(rb.d, u, v, c->d_gray + (size_t)fs * c->N, fp, c->s_copy);
+        }
+        HIPCHK(c, hipEventRecord(rb.ev, c->s_copy));
+        rb.busy = true;
+    }
+    return publish_frames(c, first, n);
+}
+
 int ffl_upload_frame(ffl_ctx *c, int fslot, const uint8_t *data, int width, int height, int channels,
                      ptrdiff_t stride_bytes) {
     return ffl_upload_frames(c, fslot, 1, &data, width, height, channels, stride_bytes);

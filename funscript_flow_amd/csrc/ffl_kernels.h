@@ -67,6 +67,16 @@ struct FrontParams {  // k_frontend: decoded 3-channel frame -> gray crop window
     int mode, rgb;
 };
 
+struct FrontYuvParams {   // k_frontend_yuv: 4:2:0 source window -> gray crop window of the frame's (virtual) resize
+    int sw, sh;              // full source size: source coordinates and their clamps stay in these terms
+    int wx, wy;              // origin of the transferred window inside the frame (even: chroma-aligned)
+    int y_pitch, c_pitch;    // row pitch of the window's Y plane / chroma plane(s) on the device, bytes
+    int c_step;              // bytes between horizontally adjacent chroma samples: 1 (I420), 2 (NV12, V = U + 1)
+    int cx, cy, ow, oh;      // crop origin inside the resized image, output size
+    double scale_x, scale_y; // 1. / ((double)resize / src), formed on the host
+    int mode;
+};
+
 // merged launches: one 1-D grid cut into per-job block ranges
 #define FFL_MAX_JOBS 4
 enum { FFL_PYR_F1 = 0, FFL_PYR_F2, FFL_PYR_H4, FFL_PYR_H9, FFL_PYR_V4, FFL_PYR_V9 };
@@ -117,6 +127,8 @@ bool ffl_launch_pyr_multi(const uint8_t *gray_base, size_t gray_stride, const UT
                           int n, const FflOptions &opt, hipStream_t st);
 void ffl_launch_polyexp_multi(const PolyJob *levels, int n, int nU, PolyConsts pc, hipStream_t st);
 void ffl_launch_frontend(const uint8_t *src, uint8_t *gray, FrontParams p, hipStream_t st);
+void ffl_launch_frontend_yuv(const uint8_t *y, const uint8_t *u, const uint8_t *v, uint8_t *gray, FrontYuvParams p,
+                             hipStream_t st);
 void ffl_launch_gray(const uint8_t *bgr, uint8_t *gray, int n_pixels, hipStream_t st);
 size_t ffl_pyr_tmp_floats(int w, int h, int lw);  // per-frame size of the level's horizontal-pass buffer
 void ffl_launch_pyr_level(const uint8_t *gray_base, size_t gray_stride, const UTab *ut, int nU, int w, int h, int lw, int lh,

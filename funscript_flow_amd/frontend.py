@@ -8,6 +8,11 @@ Mirrors what the reference does on the host to every decoded frame (FF = Funscri
 
 One `ffl_upload_frames_raw` call does all of it (k_frontend): the frame is sent as decoded and only the
 crop window of the resized image is ever computed.  No CPU fallback: without the HIP library this raises.
+
+yuv="i420" | "nv12" takes a decoder's native 4:2:0 output instead -- (3h/2, w) uint8 arrays, as PyAV's yuv420p frames
+or an `ffmpeg -pix_fmt yuv420p|nv12` pipe deliver them -- through `ffl_upload_frames_yuv` (k_frontend_yuv): the
+colour conversion runs on the device and only the source rectangle the crop window reads crosses PCIe (DESIGN.md
+section 11, appendix Y).
 """
 from . import _capi
 
@@ -20,20 +25,35 @@ def geometry(width, height, vr_mode=False):
     return (width, height), (0, 0)
 
 
-def upload_decoded(ctx, first_slot, frames, vr_mode=False, rgb_order=False):
+def _check_yuv(yuv, rgb_order):
+    if yuv is None:
+        return None
+    if rgb_order:
+        raise ValueError("rgb_order applies to 3-channel frames: it cannot be combined with yuv")
+    _capi.yuv_layout(yuv)
+    return yuv
+
+
+def upload_decoded(ctx, first_slot, frames, vr_mode=False, rgb_order=False, yuv=None):
     """frames: (h, w, 3) uint8 arrays as cv2.VideoCapture.read returns them (BGR; pass rgb_order=True for
-    frames that already went through FF:182) -> frame slots first_slot.. of `ctx`."""
+    frames that already went through FF:182), or with yuv="i420" | "nv12" (3h/2, w) uint8 4:2:0 arrays
+    -> frame slots first_slot.. of `ctx`."""
+    yuv = _check_yuv(yuv, rgb_order)
     if not isinstance(ctx, _capi.Context):
         raise TypeError("upload_decoded needs a funscript_flow_amd._capi.Context")
     resize, crop = geometry(ctx.width, ctx.height, vr_mode)
-    ctx.upload_frames_raw(first_slot, list(frames), resize, crop, rgb_order)
+    if yuv is not None:
+        ctx.upload_frames_yuv(first_slot, list(frames), yuv, resize, crop)
+    else:
+        ctx.upload_frames_raw(first_slot, list(frames), resize, crop, rgb_order)
 
 
 class DecodedUploader:
-    """`upload` hook for pipeline.PairEngine: feeds it decoded frames instead of gray operands."""
+    """`upload` hook for pipeline.PairEngine: feeds it decoded frames instead of gray operands (yuv: see upload_decoded)."""
 
-    def __init__(self, ctx, vr_mode=False, rgb_order=False):
+    def __init__(self, ctx, vr_mode=False, rgb_order=False, yuv=None):
         self.ctx, self.vr_mode, self.rgb_order = ctx, bool(vr_mode), bool(rgb_order)
+        self.yuv = _check_yuv(yuv, self.rgb_order)
 
     def __call__(self, first_slot, frames):
-        upload_decoded(self.ctx, first_slot, frames, self.vr_mode, self.rgb_order)
+        upload_decoded(self.ctx, first_slot, frames, self.vr_mode, self.rgb_order, self.yuv)

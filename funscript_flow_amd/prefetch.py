@@ -49,7 +49,8 @@ class SequentialDecoder:
         return len(self.indices)
 
     def read_into(self, dst):
-        """Decode the next wanted frame into `dst` ((h, w, 3) uint8); returns its frame index, or None at the end."""
+        """Decode the next wanted frame into `dst` ((h, w, 3) uint8, or (3h/2, w) 4:2:0); returns its frame index, or None at
+        the end."""
         if self.k >= len(self.indices):
             return None
         want = self.indices[self.k]
@@ -104,9 +105,11 @@ class PrefetchRing:
         ring.close()
 
     `ctx` provides pinned_frames(n, channels=3, size=(w, h)) (a real Context, or anything with that method).
-    ring_frames must cover what the engine keeps in flight: two batches + the one being staged = 3 * B + 1."""
+    ring_frames must cover what the engine keeps in flight: two batches + the one being staged = 3 * B + 1.
+    yuv="i420" | "nv12": the capture's read() yields (3h/2, w) 4:2:0 frames (w, h still from CAP_PROP_FRAME_*), and the
+    slots come from pinned_frames(n, size=(w, h), yuv=True); consume them with frontend.DecodedUploader(ctx, yuv=...)."""
 
-    def __init__(self, ctx, capture, indices, bracket, ring_frames, frame_size=None):
+    def __init__(self, ctx, capture, indices, bracket, ring_frames, frame_size=None, yuv=None):
         self.decoder = SequentialDecoder(capture, indices)
         if frame_size is None:
             frame_size = (int(capture.get(CAP_PROP_FRAME_WIDTH)), int(capture.get(CAP_PROP_FRAME_HEIGHT)))
@@ -114,7 +117,13 @@ class PrefetchRing:
         if self.bracket < 2:
             raise ValueError("bracket (frames per chunk) must be >= 2")
         self.ring_frames = int(ring_frames)
-        self.slots = ctx.pinned_frames(self.ring_frames, channels=3, size=frame_size)
+        if yuv is None:
+            self.slots = ctx.pinned_frames(self.ring_frames, channels=3, size=frame_size)
+        else:
+            _capi.yuv_layout(yuv)
+            if frame_size[0] % 2 or frame_size[1] % 2:
+                raise ValueError(f"4:2:0 frames need an even width and height, the capture reports {frame_size}")
+            self.slots = ctx.pinned_frames(self.ring_frames, size=frame_size, yuv=True)
         self.cv = threading.Condition()
         self.decoded = 0       # stream positions [0, decoded) have been decoded (position = rank in `indices`)
         self.released = 0      # positions [0, released) may be overwritten
@@ -191,11 +200,14 @@ def video_to_actions(ctx, capture, params, engine=None, ring_frames=None):
     total, fps = int(capture.get(CAP_PROP_FRAME_COUNT)), float(capture.get(CAP_PROP_FPS))
     _, _, indices = postchain.sampling(fps, total)
     bracket = int(params.get("batch_size", 3000.0))
-    engine = engine or pipeline.PairEngine(ctx, frontend.DecodedUploader(ctx, bool(params.get("vr_mode")), False))
+    # params["hip_yuv"] = "i420" | "nv12": the capture yields 4:2:0 frames; a caller's engine must
+    # then have been built with frontend.DecodedUploader(ctx, yuv=...)
+    yuv = params.get("hip_yuv")
+    engine = engine or pipeline.PairEngine(ctx, frontend.DecodedUploader(ctx, bool(params.get("vr_mode")), False, yuv=yuv))
     # params["hip_flow"] / ["hip_dis"] pick the flow algorithm for this call (a caller's engine is left as it is)
     algo = _capi.flow_choice(params) if ("hip_flow" in params or "hip_dis" in params) else None
     fbk = pipeline.farneback_kwargs(params, ctx.width, ctx.height)   # params["hip_farneback"]: this call's parameters
-    ring = PrefetchRing(ctx, capture, indices, bracket, ring_frames or 4 * ctx.max_batch + 2)
+    ring = PrefetchRing(ctx, capture, indices, bracket, ring_frames or 4 * ctx.max_batch + 2, yuv=yuv)
     dots, cuts, frame_idx = [], [], []
     try:
         for view, fidx in ring.chunks():
@@ -249,9 +261,10 @@ def process_video(video_path, params, log_func, open_capture, make_context, prog
     try:
         ctx = make_context(cap)
         flow, dis = _capi.flow_choice(params)
-        engine = pipeline.PairEngine(ctx, frontend.DecodedUploader(ctx, bool(params.get("vr_mode")), False), flow=flow, dis=dis,
-                                     farneback=_capi.farneback_choice(params))
-        ring = PrefetchRing(ctx, cap, indices, int(params.get("batch_size", 3000.0)), 4 * ctx.max_batch + 2)
+        yuv = params.get("hip_yuv")   # "i420" | "nv12": open_capture's read() yields (3h/2, w) 4:2:0 frames
+        engine = pipeline.PairEngine(ctx, frontend.DecodedUploader(ctx, bool(params.get("vr_mode")), False, yuv=yuv), flow=flow,
+                                     dis=dis, farneback=_capi.farneback_choice(params))
+        ring = PrefetchRing(ctx, cap, indices, int(params.get("batch_size", 3000.0)), 4 * ctx.max_batch + 2, yuv=yuv)
         dots, cuts, frame_idx, done = [], [], [], 0
         for view, fidx in ring.chunks():
             if cancel_flag and cancel_flag():

@@ -15,6 +15,8 @@
  *   ffl_upload_frames_raw   the decoded frame's way to that operand: cv2.cvtColor(BGR2RGB) FF:182,
  *                           cv2.resize(frame, (256, 256)) FF:185-186 (non-VR) or cv2.resize(f, (512, 512))
  *                           + crop f[256:, :256] FF:1076-1079 (VR), cv2.cvtColor(RGB2GRAY) FF:1079/1082
+ *   ffl_upload_frames_yuv   the same operand from a decoder's native 4:2:0 output (I420 / NV12): the decoder's own
+ *                           YUV->BGR conversion before FF:182, then as ffl_upload_frames_raw
  *   ffl_flow_pairs          cv2.calcOpticalFlowFarneback(p0,p1,None,0.5,3,15,3,5,1.2,0)  FF:878-879
  *                           + max_divergence(flow)  FF:884 -> FF:748-758
  *                           + cv2.cartToPolar / np.mean                             FF:889-890
@@ -112,6 +114,38 @@ int ffl_upload_frames(ffl_ctx *ctx, int first_slot, int n, const uint8_t *const 
 int ffl_upload_frames_raw(ffl_ctx *ctx, int first_slot, int n, const uint8_t *const *frames, int src_width,
                           int src_height, ptrdiff_t stride_bytes, int rgb_order, int resize_width, int resize_height,
                           int crop_x, int crop_y);
+
+/* 4:2:0 layouts of ffl_upload_frames_yuv: cv2's single-array (H*3/2, W) uint8 frames.  I420: the Y plane, then U as
+ * (H/2) x (W/2) contiguous bytes, then V (PyAV's yuv420p, `ffmpeg -pix_fmt yuv420p`).  NV12: the Y plane, then H/2 rows of
+ * interleaved U,V (`ffmpeg -pix_fmt nv12`, hardware decoder surfaces). */
+#define FFL_YUV_I420 0
+#define FFL_YUV_NV12 1
+
+/* The YUV input front-end: n decoded 4:2:0 frames of src_width x src_height (both even; `layout` FFL_YUV_I420 with
+ * stride_bytes == src_width, or FFL_YUV_NV12 with stride_bytes >= src_width) go to the frame slots
+ * first_slot .. first_slot+n-1 as
+ *     gray( resize( cvtColor(frame, COLOR_YUV2BGR_I420 | COLOR_YUV2BGR_NV12), (resize_width, resize_height) )
+ *           [crop_y : crop_y+height, crop_x : crop_x+width] )
+ * -- the decoder's conversion of the reference's cv2.VideoCapture.read (FF:178), then FF:185-186 / FF:1076-1079 and
+ * FF:1079/1082 exactly as ffl_upload_frames_raw computes them.  The conversion is BT.601 limited range in OpenCV's
+ * 20-bit fixed point with nearest chroma; cv2.VideoCapture's own swscale conversion interpolates
+ * chroma, so these operands are not those of the BGR path for the same video.  Only the source rectangle the crop
+ * window reads (ffl_frontend_yuv_window) is transferred: out of ffl_host_alloc memory one 2-D copy per plane straight
+ * from the buffer (leave it alone until the transfer is over, as for ffl_upload_frames), from anywhere else through a
+ * staging copy made before the call returns.  Refused (FFL_ERR_INVALID, the message names the rule): odd sizes, an
+ * unknown layout, I420 with stride != width, NV12 with stride < width, a crop that does not fit, NULL frames, a bad
+ * slot range. */
+int ffl_upload_frames_yuv(ffl_ctx *ctx, int first_slot, int n, const uint8_t *const *frames, int src_width,
+                          int src_height, ptrdiff_t stride_bytes, int layout, int resize_width, int resize_height,
+                          int crop_x, int crop_y);
+
+/* The source rectangle ffl_upload_frames_yuv transfers for these arguments (out_w x out_h = the context's frame size):
+ * win = {x, y, width, height} in source pixels, all even, a superset of every pixel the kernel reads (first and last
+ * output row / column mapped back, widened by one pixel per side, rounded out to even, clamped to the frame); *bytes =
+ * the bytes one frame transfers (width * height * 3 / 2).  Either output may be NULL.  No device needed.  The same
+ * refusals as ffl_upload_frames_yuv (message through ffl_last_error(NULL)). */
+int ffl_frontend_yuv_window(int src_w, int src_h, int layout, ptrdiff_t stride_bytes, int resize_w, int resize_h,
+                            int crop_x, int crop_y, int out_w, int out_h, int win[4], size_t *bytes);
 
 /* Page-locked host memory owned by the context (freed by ffl_host_free or ffl_destroy).  A decoder that writes its
  * frames into such a buffer saves the library's staging copy: ffl_upload_frame(s) of tightly packed frames that lie
@@ -289,8 +323,8 @@ int ffl_profile_enable(ffl_ctx *ctx, unsigned class_mask);
 #define FFL_K_GRAY 0
 #define FFL_K_PYRAMID 1
 #define FFL_K_POLYEXP 2
-#define FFL_K_FRONTEND 3 /* k_frontend of ffl_upload_frames_raw (the x2 flow upsample, once class 3, runs
-                            inside k_update_matrices) */
+#define FFL_K_FRONTEND 3 /* k_frontend of ffl_upload_frames_raw and k_frontend_yuv of ffl_upload_frames_yuv (the x2
+                            flow upsample, once class 3, runs inside k_update_matrices) */
 #define FFL_K_UPDATE_MATRICES 4
 #define FFL_K_BLUR_SOLVE 5
 #define FFL_K_PASS1 6
