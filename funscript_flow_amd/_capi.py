@@ -2,6 +2,7 @@
 device is usable, loading / context creation raises."""
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 
@@ -22,10 +23,16 @@ EXPORTS = ["ffl_device_count", "ffl_create", "ffl_destroy", "ffl_last_error", "f
            "ffl_profile_read", "ffl_kernel_name", "ffl_device_mem_info", "ffl_estimate_bytes",
            "ffl_dis_default_params", "ffl_dis_geometry", "ffl_flow_pairs_dis", "ffl_debug_dis_pair",
            "ffl_farneback_default_params", "ffl_farneback_geometry", "ffl_farneback_extra_bytes", "ffl_flow_pairs_farneback",
-           "ffl_upload_frames_yuv", "ffl_frontend_yuv_window"]
+           "ffl_upload_frames_yuv", "ffl_frontend_yuv_window",
+           "ffl_dev_frame_check", "ffl_upload_frames_device", "ffl_export_flows"]
 
 # 4:2:0 layouts of ffl_upload_frames_yuv (FFL_YUV_I420, FFL_YUV_NV12): cv2's single-array (3h/2, w) uint8 frames
 YUV_LAYOUTS = {"i420": 0, "nv12": 1}
+
+# device-memory I/O (ffl_upload_frames_device / ffl_export_flows): FFL_DEV_* and FFL_FLOW_* codes
+DEV_FORMATS = {"gray": 0, "bgr": 1, "rgb": 2, "i420": 3, "nv12": 4}
+FLOW_LAYOUTS = {"nhwc": 0, "nchw": 1}
+FFL_ERR_INVALID, FFL_ERR_STATE = 1, 4
 
 FLOWS = ("farneback", "dis")   # params["hip_flow"]: the reference's CPU/CUDA/OpenCL branch, or its "DNN" branch (FF:948-980)
 DIS_STAGES = {"pass1": 0, "pass2": 1, "dense": 2, "refined": 3, "images": 4}   # ffl_debug_dis_pair stages
@@ -139,7 +146,128 @@ def dis_geometry(width, height, params=None):
 
 
 class FFLError(RuntimeError):
-    pass
+    """A refused or failed library call; `code` is the FFL_ERR_* status (None where Python refused it)."""
+    code = None
+
+
+class DevFrame(C.Structure):
+    """ffl_dev_frame: one frame in device memory, described by its planes (include/ffl.h).  device_frame() builds it;
+    width / height are the frame's size."""
+    _fields_ = [("plane", C.c_void_p * 3), ("pitch", C.c_ssize_t * 3), ("pixel_stride", C.c_ssize_t),
+                ("channel_stride", C.c_ssize_t)]
+
+
+def dev_format(fmt):
+    """FFL_DEV_* code of "gray" / "bgr" / "rgb" / "i420" / "nv12"; ValueError for anything else"""
+    if isinstance(fmt, str) and fmt.lower() in DEV_FORMATS:
+        return DEV_FORMATS[fmt.lower()]
+    raise ValueError(f"unknown device frame format {fmt!r}; known: {sorted(DEV_FORMATS)}")
+
+
+def flow_layout(layout):
+    """FFL_FLOW_* code of "nhwc" / "nchw"; ValueError for anything else"""
+    if isinstance(layout, str) and layout.lower() in FLOW_LAYOUTS:
+        return FLOW_LAYOUTS[layout.lower()]
+    raise ValueError(f"unknown flow layout {layout!r}; known: {sorted(FLOW_LAYOUTS)}")
+
+
+def _array_view(obj):
+    """(data pointer, shape, byte strides, typestr) of a device array.  torch tensors are read directly (the per-frame
+    cost of a batch of hundreds of views); anything else through __cuda_array_interface__ (v2 / v3), and DLPack producers
+    on a GPU through torch.from_dlpack.  Host arrays are refused: they go through the host upload calls."""
+    torch = sys.modules.get("torch")
+    if torch is not None and isinstance(obj, torch.Tensor):
+        if not obj.is_cuda:
+            raise ValueError("not device memory: a CPU tensor (host frames go through upload_frames / upload_frames_raw / "
+                             "upload_frames_yuv)")
+        es = obj.element_size()
+        ts = {torch.uint8: "|u1", torch.float32: "<f4"}.get(obj.dtype, str(obj.dtype))
+        return obj.data_ptr(), tuple(obj.shape), tuple(st * es for st in obj.stride()), ts
+    try:
+        cai = obj.__cuda_array_interface__
+    except AttributeError:
+        cai = None
+    if cai is None:
+        dev = getattr(obj, "__dlpack_device__", None)
+        if dev is not None and dev()[0] in (2, 10):   # kDLCUDA, kDLROCM
+            import torch
+            return _array_view(torch.from_dlpack(obj))
+        raise ValueError(f"not device memory: {type(obj).__name__} has no __cuda_array_interface__ (host frames go through "
+                         "upload_frames / upload_frames_raw / upload_frames_yuv)")
+    if cai.get("version", 2) not in (2, 3):
+        raise ValueError(f"__cuda_array_interface__ version {cai.get('version')} is not supported (2 or 3)")
+    if cai.get("mask") is not None:
+        raise ValueError("masked device arrays are not supported")
+    shape, ts = tuple(int(d) for d in cai["shape"]), cai["typestr"]
+    item = int(ts[2:]) if ts[2:].isdigit() else 1
+    strides = cai.get("strides")
+    if strides is None:   # C-contiguous
+        strides, acc = [], item
+        for d in reversed(shape):
+            strides.insert(0, acc)
+            acc *= d
+    return int(cai["data"][0]), shape, tuple(int(v) for v in strides), ts
+
+
+def _frame_row(obj, code):
+    """the 8 fields of ffl_dev_frame (plane[3], pitch[3], pixel_stride, channel_stride) and (width, height) of one frame"""
+    ptr, shape, st, ts = _array_view(obj)
+    if ts[1:] != "u1":
+        raise ValueError(f"device frames must be uint8 (typestr '|u1'), got {ts!r}")
+    if code == DEV_FORMATS["gray"]:
+        if len(shape) != 2:
+            raise ValueError(f"a gray frame is (h, w), got shape {shape}")
+        return (ptr, 0, 0, st[0], 0, 0, st[1], 0), (shape[1], shape[0])
+    if code in (DEV_FORMATS["bgr"], DEV_FORMATS["rgb"]):
+        if len(shape) == 3 and shape[2] in (3, 4):      # HWC packed (BGRA: channel 3 is never read)
+            return (ptr, 0, 0, st[0], 0, 0, st[1], st[2]), (shape[1], shape[0])
+        if len(shape) == 3 and shape[0] == 3:           # CHW planar
+            return (ptr, 0, 0, st[1], 0, 0, st[2], st[0]), (shape[2], shape[1])
+        raise ValueError(f"a 3-channel frame is (h, w, 3|4) or (3, h, w), got shape {shape}")
+    if len(shape) != 2 or shape[0] % 3:
+        raise ValueError(f"a 4:2:0 frame is one (3h/2, w) array, got shape {shape}")
+    if st[1] != 1:
+        raise ValueError(f"4:2:0 rows must be contiguous (column stride 1), got {st[1]}")
+    w, h, pitch = shape[1], shape[0] * 2 // 3, st[0]
+    if code == DEV_FORMATS["nv12"]:
+        return (ptr, ptr + h * pitch, 0, pitch, pitch, 0, 1, 0), (w, h)
+    if pitch != w:
+        raise ValueError(f"I420 needs contiguous rows (row pitch == width), got pitch {pitch} for width {w}")
+    u = ptr + h * w
+    return (ptr, u, u + (h // 2) * (w // 2), w, w // 2, w // 2, 1, 0), (w, h)
+
+
+def device_frame(obj, fmt):
+    """DevFrame (ffl_dev_frame + .width, .height) of a device array: any object with __cuda_array_interface__ (v2 / v3,
+    typestr "|u1", byte strides) -- torch tensors included -- or a GPU DLPack producer.  fmt "gray": (h, w); "bgr" / "rgb":
+    (h, w, 3) or (h, w, 4) packed, or (3, h, w) planar, any strides; "i420" / "nv12": cv2's single (3h/2, w) array (an
+    NV12 row pitch may exceed w).  ValueError names what is refused."""
+    row, (w, h) = _frame_row(obj, dev_format(fmt))
+    f = DevFrame((C.c_void_p * 3)(*row[:3]), (C.c_ssize_t * 3)(*row[3:6]), row[6], row[7])
+    f.width, f.height = w, h
+    return f
+
+
+def dev_frame_check(fmt, frame, resize, crop, out_size):
+    """ffl_dev_frame_check for a DevFrame: ValueError with the library's rule when it refuses (pure host check)."""
+    L = load()
+    if L.ffl_dev_frame_check(dev_format(fmt), frame.width, frame.height, C.byref(frame), int(resize[0]), int(resize[1]),
+                             int(crop[0]), int(crop[1]), int(out_size[0]), int(out_size[1])) != FFL_OK:
+        raise ValueError(L.ffl_last_error(None).decode())
+
+
+def stream_handle(stream, device=0):
+    """hipStream_t of `stream` as an int: None = torch's current stream on `device` when torch is already imported (else
+    0, the null stream); a torch.cuda.Stream; or an int as it is."""
+    if stream is None:
+        torch = sys.modules.get("torch")
+        return int(torch.cuda.current_stream(device).cuda_stream) if torch is not None else 0
+    if isinstance(stream, int):
+        return stream
+    handle = getattr(stream, "cuda_stream", None)
+    if handle is None:
+        raise TypeError(f"stream must be None, an int or a torch.cuda.Stream, got {type(stream).__name__}")
+    return int(handle)
 
 
 def yuv_layout(layout):
@@ -229,6 +357,9 @@ def load():
     L.ffl_farneback_geometry.argtypes = [C.c_int, C.c_int, fp_, ip, C.POINTER(C.c_size_t)]
     L.ffl_farneback_extra_bytes.argtypes = [C.c_int, C.c_int, C.c_int, fp_, C.POINTER(C.c_size_t)]
     L.ffl_flow_pairs_farneback.argtypes = [vp, C.c_int, ip, ip, ip, C.c_int, fp_]
+    L.ffl_dev_frame_check.argtypes = [C.c_int, C.c_int, C.c_int, vp] + [C.c_int] * 6
+    L.ffl_upload_frames_device.argtypes = [vp, C.c_int, C.c_int, vp] + [C.c_int] * 7 + [C.c_uint64]
+    L.ffl_export_flows.argtypes = [vp, C.c_int, ip, vp, C.c_int, C.c_ssize_t, C.c_uint64]
     _lib = L
     return L
 
@@ -312,7 +443,9 @@ class Context:
 
     def _chk(self, rc):
         if rc != FFL_OK:
-            raise FFLError(f"ffl error {rc}: {self.L.ffl_last_error(self._h).decode()}")
+            e = FFLError(f"ffl error {rc}: {self.L.ffl_last_error(self._h).decode()}")
+            e.code = rc
+            raise e
 
     # ---- frames -------------------------------------------------------------------------------
     def upload_frame(self, fslot, frame):
@@ -398,6 +531,81 @@ class Context:
         self._chk(self.L.ffl_upload_frames_yuv(self._h, first_slot, len(fr), ptrs, f0.shape[1], f0.shape[0] * 2 // 3,
                                                f0.strides[0], code, int(resize[0]), int(resize[1]), int(crop[0]),
                                                int(crop[1])))
+
+    def upload_frames_device(self, first_slot, frames, fmt, resize=None, crop=(0, 0), stream=None):
+        """Device-resident frames -> gray(resize(frame, resize)[crop window]) in consecutive slots without a host round
+        trip (ffl_upload_frames_device): the bytes upload_frames_raw / upload_frames_yuv /
+        upload_frames give for the same pixels.  `frames`: a sequence of device arrays (see device_frame) or one array with
+        a leading frame axis, all of one size; fmt one of DEV_FORMATS; resize None = the source size.  The frames are read
+        after the work queued on `stream` (stream_handle) and `stream` waits for the read: the caller may overwrite or free
+        them in its order on that stream, with no host synchronisation."""
+        code = dev_format(fmt)
+        rows, size = self._device_rows(frames, code)
+        descs = np.ascontiguousarray(rows, np.int64)
+        rw, rh = (size if resize is None else resize)
+        self._chk(self.L.ffl_upload_frames_device(self._h, int(first_slot), len(descs), descs.ctypes.data, code, size[0], size[1],
+                                                  int(rw), int(rh), int(crop[0]), int(crop[1]),
+                                                  stream_handle(stream, self.device)))
+
+    @staticmethod
+    def _device_rows(frames, code):
+        """ffl_dev_frame rows of a frame sequence or of one batched array, and the common (width, height)"""
+        nd = 3 if code in (DEV_FORMATS["bgr"], DEV_FORMATS["rgb"]) else 2
+        view = None
+        if not isinstance(frames, (list, tuple)):
+            try:
+                view = _array_view(frames)
+            except ValueError:
+                view = None                                  # another kind of sequence: frame by frame below
+        if view is not None and len(view[1]) == nd + 1:     # one (n, ...) array: frame i starts i * stride[0] bytes in
+            ptr, shp, st, ts = view
+            class _One:   # frame 0's view; the others are offsets of it
+                __cuda_array_interface__ = {"version": 2, "data": (ptr, False), "shape": shp[1:], "strides": st[1:], "typestr": ts}
+            row, size = _frame_row(_One(), code)
+            rows = np.tile(np.asarray(row, np.int64), (shp[0], 1))
+            for k in range(3):
+                if row[k]:
+                    rows[:, k] += np.arange(shp[0], dtype=np.int64) * st[0]
+            return rows, size
+        rows, size = [], None
+        for f in frames:
+            row, sz = _frame_row(f, code)
+            if size is not None and sz != size:
+                raise ValueError(f"upload_frames_device needs frames of one size, got {size} and {sz}")
+            rows.append(row)
+            size = sz
+        if not rows:
+            raise ValueError("upload_frames_device: no frames")
+        return rows, size
+
+    def export_flows(self, flow_slots, out=None, layout="nhwc", stream=None):
+        """The flow fields of flow_slots into device memory without a host round trip (ffl_export_flows): `out` a float32
+        device array of (n, H, W, 2) ("nhwc", cv2's layout) or (n, 2, H, W) ("nchw"), each item contiguous, items any
+        stride apart -- or None for a new torch tensor.  Bit for bit what download_flow returns.  Ordered after the batches
+        that produced the slots and the work queued on `stream`; `stream` waits for the export.  Returns `out`."""
+        code = flow_layout(layout)
+        (ps, slots) = _iarr(flow_slots)
+        n, H, W = len(slots), self.height, self.width
+        shape = (n, H, W, 2) if code == 0 else (n, 2, H, W)
+        handle = stream_handle(stream, self.device)
+        if out is None:
+            import torch
+            dev = torch.device("cuda", self.device)
+            if handle == torch.cuda.current_stream(dev).cuda_stream:
+                out = torch.empty(shape, dtype=torch.float32, device=dev)
+            else:   # allocated in the order of the stream that writes it
+                with torch.cuda.stream(torch.cuda.ExternalStream(handle, device=dev)):
+                    out = torch.empty(shape, dtype=torch.float32, device=dev)
+        ptr, shp, st, ts = _array_view(out)
+        if ts[1:] != "f4":
+            raise ValueError(f"export_flows needs a float32 output, got typestr {ts!r}")
+        if tuple(shp) != shape:
+            raise ValueError(f"export_flows: output shape {tuple(shp)} is not {shape} ({layout})")
+        inner = [4 * int(np.prod(shape[k + 1:])) for k in range(1, 4)]
+        if any(st[k] != inner[k - 1] for k in range(1, 4) if shape[k] > 1):
+            raise ValueError(f"export_flows: every item of the output must be contiguous, strides are {st}")
+        self._chk(self.L.ffl_export_flows(self._h, n, ps, ptr, code, st[0], handle))
+        return out
 
     def flow_pairs(self, fslot0, fslot1, flow_slots, pov_mode=False):
         n = len(flow_slots)

@@ -273,7 +273,12 @@ struct ffl_ctx {
     };
     RawBuf raw[FFL_RAW_RING];
     unsigned raw_next = 0;
-    EvRing post_ring;  // events of ffl_upload_flow and ffl_radial (stream `post`), FFL_EV_RING entries
+    EvRing post_ring;  // events of ffl_upload_flow, ffl_radial and ffl_export_flows (stream `post`), FFL_EV_RING entries
+    // device-memory I/O (ffl_upload_frames_device / ffl_export_flows), allocated on first use: the event recorded on the
+    // caller's stream (waited for at once, so one is enough), and the per-call frame descriptor tables -- a pinned copy
+    // per up_ring entry (n_fslots descriptors each) and the device table k_frontend_dev reads (stream `copy`)
+    hipEvent_t ev_caller = nullptr;
+    DevFrameDesc *h_dtab = nullptr, *d_dtab = nullptr;
     // flow slots
     float *d_flow = nullptr;          // [n_slots][2N]
     // Result records live in pinned, device-mapped host memory: the reduction kernels store their
@@ -601,6 +606,8 @@ void ffl_destroy(ffl_ctx *c) {
     for (auto &hb : c->host_bufs) hipHostFree(hb.first);
     c->up_ring.destroy();
     c->post_ring.destroy();
+    if (c->ev_caller) hipEventDestroy(c->ev_caller);
+    hipFree(c->d_dtab); hipHostFree(c->h_dtab);
     hipFree(c->d_gray); hipFree(c->d_bgr); hipHostFree(c->h_stage_gray); hipHostFree(c->h_stage_bgr);
     for (auto &rb : c->raw) {
         hipFree(rb.d);
@@ -1968,6 +1975,255 @@ int ffl_download_flow(ffl_ctx *c, int slot, float *dst) {
     hipEvent_t ev = c->ev_slot_done[slot].get();
     if (int rc = wait_unlocked(c, lk, &ev, 1)) return rc;
     HIPCHK(c, hipMemcpy(dst, c->d_flow + (size_t)slot * 2 * c->N, sizeof(float) * 2 * c->N, hipMemcpyDeviceToHost));
+    return FFL_OK;
+}
+
+// ---- device-memory I/O -------------------------------------------------------------------------
+// Every geometry rule of a device frame (ffl.h, ffl_dev_frame_check); fn and frame index prefix the message.
+static int dev_frame_check(ffl_ctx *c, const char *fn, int idx, int fmt, int sw, int sh, const ffl_dev_frame *f, int rw, int rh,
+                           int cx, int cy, int ow, int oh) {
+    if (!f) return set_err(c, FFL_ERR_INVALID, "%s: frame %d: NULL descriptor", fn, idx);
+    if (fmt < FFL_DEV_GRAY || fmt > FFL_DEV_NV12)
+        return set_err(c, FFL_ERR_INVALID, "%s: unknown format %d (FFL_DEV_GRAY 0, BGR 1, RGB 2, I420 3, NV12 4)", fn, fmt);
+    if (sw < 1 || sh < 1 || sw > 32768 || sh > 32768 || rw < 1 || rh < 1 || rw > 32768 || rh > 32768 || ow < 1 || oh < 1)
+        return set_err(c, FFL_ERR_INVALID, "%s: unsupported source %dx%d / resize %dx%d / output %dx%d", fn, sw, sh, rw, rh, ow, oh);
+    const bool yuv = fmt == FFL_DEV_I420 || fmt == FFL_DEV_NV12;
+    if (fmt == FFL_DEV_GRAY && (rw != sw || rh != sh))
+        return set_err(c, FFL_ERR_INVALID, "%s: gray frames are copied as they are: a resize (%dx%d -> %dx%d) is refused", fn, sw, sh,
+                       rw, rh);
+    if (fmt == FFL_DEV_GRAY && (sw != ow || sh != oh))
+        return set_err(c, FFL_ERR_INVALID, "%s: a gray frame must be the context size %dx%d, got %dx%d", fn, ow, oh, sw, sh);
+    if (yuv && ((sw & 1) || (sh & 1)))
+        return set_err(c, FFL_ERR_INVALID, "%s: 4:2:0 needs an even width and height, source is %dx%d", fn, sw, sh);
+    if (cx < 0 || cy < 0 || cx + ow > rw || cy + oh > rh)
+        return set_err(c, FFL_ERR_INVALID, "%s: crop window (%d, %d) + %dx%d does not fit the %dx%d resized frame", fn, cx, cy, ow,
+                       oh, rw, rh);
+    const ptrdiff_t big = (ptrdiff_t)1 << 40;
+    const ptrdiff_t p0 = f->pitch[0], ps = f->pixel_stride, cs = f->channel_stride;
+    if (!f->plane[0] || (yuv && !f->plane[1]) || (fmt == FFL_DEV_I420 && !f->plane[2]))
+        return set_err(c, FFL_ERR_INVALID, "%s: frame %d: a plane the format reads is NULL", fn, idx);
+    if (yuv) {
+        const ptrdiff_t p1 = f->pitch[1], p2 = fmt == FFL_DEV_I420 ? f->pitch[2] : p1;
+        const ptrdiff_t cmin = fmt == FFL_DEV_I420 ? sw / 2 : sw;
+        if (p0 < 0 || p1 < 0 || p2 < 0) return set_err(c, FFL_ERR_INVALID, "%s: frame %d: negative stride", fn, idx);
+        if (p0 < sw || p0 > big) return set_err(c, FFL_ERR_INVALID, "%s: frame %d: Y pitch %td too small for a row of %d pixels", fn, idx, p0, sw);
+        if (p1 < cmin || p2 < cmin || p1 > big || p2 > big)
+            return set_err(c, FFL_ERR_INVALID, "%s: frame %d: chroma pitch %td / %td too small for a row of %td bytes", fn, idx, p1, p2, cmin);
+        return FFL_OK;
+    }
+    if (p0 < 0 || ps < 0 || cs < 0) return set_err(c, FFL_ERR_INVALID, "%s: frame %d: negative stride", fn, idx);
+    if (p0 > big || ps > big || cs > big) return set_err(c, FFL_ERR_INVALID, "%s: frame %d: stride beyond 2^40", fn, idx);
+    if (ps < 1) return set_err(c, FFL_ERR_INVALID, "%s: frame %d: pixel stride %td too small (>= 1)", fn, idx, ps);
+    if (fmt == FFL_DEV_GRAY) {
+        if (p0 < (ptrdiff_t)(sw - 1) * ps + 1)
+            return set_err(c, FFL_ERR_INVALID, "%s: frame %d: pitch %td too small for %d pixels %td bytes apart", fn, idx, p0, sw, ps);
+        return FFL_OK;
+    }
+    if (cs < 1) return set_err(c, FFL_ERR_INVALID, "%s: frame %d: channel stride %td too small (>= 1)", fn, idx, cs);
+    if (ps >= 3 * cs) {  // packed: the three channels of a pixel lie within its pixel stride
+        if (p0 < (ptrdiff_t)(sw - 1) * ps + 2 * cs + 1)
+            return set_err(c, FFL_ERR_INVALID, "%s: frame %d: pitch %td too small for %d pixels %td bytes apart (channel stride %td)",
+                           fn, idx, p0, sw, ps, cs);
+    } else {  // planar: every channel plane ends before the next begins
+        if (p0 < (ptrdiff_t)(sw - 1) * ps + 1)
+            return set_err(c, FFL_ERR_INVALID, "%s: frame %d: pitch %td too small for %d pixels %td bytes apart", fn, idx, p0, sw, ps);
+        if (cs < p0 * sh)
+            return set_err(c, FFL_ERR_INVALID,
+                           "%s: frame %d: channel stride %td too small: neither packed (pixel stride %td >= 3 * channel stride) "
+                           "nor planar (channel stride >= pitch * height = %td)", fn, idx, cs, ps, p0 * sh);
+    }
+    return FFL_OK;
+}
+
+// bytes of each plane a checked frame spans from plane[k] (0: unused)
+static void dev_frame_extents(int fmt, int sw, int sh, const ffl_dev_frame *f, size_t ext[3]) {
+    ext[0] = ext[1] = ext[2] = 0;
+    if (fmt == FFL_DEV_I420 || fmt == FFL_DEV_NV12) {
+        ext[0] = (size_t)(sh - 1) * f->pitch[0] + sw;
+        if (fmt == FFL_DEV_NV12) {
+            ext[1] = (size_t)(sh / 2 - 1) * f->pitch[1] + sw;
+        } else {
+            ext[1] = (size_t)(sh / 2 - 1) * f->pitch[1] + sw / 2;
+            ext[2] = (size_t)(sh / 2 - 1) * f->pitch[2] + sw / 2;
+        }
+    } else {
+        ext[0] = (size_t)(sh - 1) * f->pitch[0] + (size_t)(sw - 1) * f->pixel_stride + 1 +
+                 (fmt == FFL_DEV_GRAY ? 0 : 2 * (size_t)f->channel_stride);
+    }
+}
+
+// [p, p + bytes) must be device memory of the context's device inside one allocation
+static int dev_mem_check(ffl_ctx *c, const char *fn, const char *what, const void *p, size_t bytes) {
+    hipPointerAttribute_t a;
+    hipError_t e = hipPointerGetAttributes(&a, p);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return set_err(c, FFL_ERR_INVALID, "%s: %s is not device memory (unknown to HIP); host frames go through "
+                                           "ffl_upload_frames, ffl_upload_frames_raw or ffl_upload_frames_yuv", fn, what);
+    }
+    if (a.type == hipMemoryTypeHost)
+        return set_err(c, FFL_ERR_INVALID, "%s: %s is page-locked host memory (ffl_host_alloc / hipHostMalloc); host frames go "
+                                           "through ffl_upload_frames, ffl_upload_frames_raw or ffl_upload_frames_yuv", fn, what);
+    if (a.type != hipMemoryTypeDevice)
+        return set_err(c, FFL_ERR_INVALID, "%s: %s is not device memory (memory type %d); host frames go through "
+                                           "ffl_upload_frames, ffl_upload_frames_raw or ffl_upload_frames_yuv", fn, what, (int)a.type);
+    if (a.device != c->device)
+        return set_err(c, FFL_ERR_INVALID, "%s: %s is memory of device %d, the context is on device %d", fn, what, a.device, c->device);
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return set_err(c, FFL_ERR_INVALID, "%s: %s: hipMemGetAddressRange failed (%s)", fn, what, hipGetErrorString(e));
+    }
+    if ((const char *)p + bytes > (const char *)base + size)
+        return set_err(c, FFL_ERR_INVALID, "%s: %s spans %zu bytes, %zu more than its allocation holds", fn, what, bytes,
+                       (size_t)((const char *)p + bytes - ((const char *)base + size)));
+    return FFL_OK;
+}
+
+// the first HIP call made on a caller's stream: device-memory I/O is never captured into anyone's graph
+static int refuse_capturing(ffl_ctx *c, const char *fn, hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    const hipError_t e = hipStreamIsCapturing(st, &cs);
+    if (e == hipErrorStreamCaptureImplicit) cs = hipStreamCaptureStatusActive;  // the null stream while a global capture runs
+    else if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return set_err(c, FFL_ERR_HIP, "%s: hipStreamIsCapturing failed: %s", fn, hipGetErrorString(e));
+    }
+    if (cs != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        return set_err(c, FFL_ERR_STATE, "%s: the stream is capturing a graph; device-memory I/O is never captured (call it "
+                                         "before or after the capture)", fn);
+    }
+    return FFL_OK;
+}
+
+int ffl_dev_frame_check(int format, int sw, int sh, const ffl_dev_frame *f, int rw, int rh, int cx, int cy, int out_w, int out_h) {
+    return dev_frame_check(nullptr, "ffl_dev_frame_check", 0, format, sw, sh, f, rw, rh, cx, cy, out_w, out_h);
+}
+
+// Device frames -> gray frame slots through ONE k_frontend_dev launch on stream `copy`, ordered after the caller's queued
+// work and before the caller's later work (the stream contract of ffl.h).  The descriptors travel in the pinned table of
+// the up_ring entry the call records (publish_frames), copied to the device table on the same stream.
+int ffl_upload_frames_device(ffl_ctx *c, int first, int n, const ffl_dev_frame *frames, int fmt, int sw, int sh, int rw, int rh,
+                             int cx, int cy, uint64_t stream) {
+    static const char *fn = "ffl_upload_frames_device";
+    if (!c) return FFL_ERR_INVALID;
+    std::unique_lock<std::mutex> ul(c->up_mu);
+    CtxLock lk(c->mu);
+    if (!frames || n < 1 || first < 0 || first + n > c->n_fslots)
+        return set_err(c, FFL_ERR_INVALID, "%s: bad frame slot range %d..%d", fn, first, first + n - 1);
+    for (int i = 0; i < n; i++)
+        if (int rc = dev_frame_check(c, fn, i, fmt, sw, sh, &frames[i], rw, rh, cx, cy, c->w, c->h)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t cst = (hipStream_t)(uintptr_t)stream;
+    if (int rc = refuse_capturing(c, fn, cst)) return rc;
+    static const char *names[3] = {"plane 0", "plane 1", "plane 2"};
+    for (int i = 0; i < n; i++) {
+        size_t ext[3];
+        dev_frame_extents(fmt, sw, sh, &frames[i], ext);
+        for (int k = 0; k < 3; k++)
+            if (ext[k])
+                if (int rc = dev_mem_check(c, fn, names[k], frames[i].plane[k], ext[k])) return rc;
+    }
+    const size_t ring = c->up_ring.ev.size();
+    if (!c->ev_caller) HIPCHK(c, hipEventCreateWithFlags(&c->ev_caller, hipEventDisableTiming));
+    if (!c->d_dtab) {
+        HIPCHK(c, hipMalloc(&c->d_dtab, sizeof(DevFrameDesc) * c->n_fslots));
+        HIPCHK(c, hipHostMalloc(&c->h_dtab, sizeof(DevFrameDesc) * c->n_fslots * ring, hipHostMallocDefault));
+    }
+    // the pinned table of the entry publish_frames records below: settled, so its copy of 32 calls ago has been consumed
+    HIPCHK(c, c->up_ring.settle_next());
+    DevFrameDesc *T = c->h_dtab + (size_t)(c->up_ring.next % ring) * c->n_fslots;
+    const bool yuv = fmt == FFL_DEV_I420 || fmt == FFL_DEV_NV12;
+    for (int i = 0; i < n; i++) {
+        const ffl_dev_frame &f = frames[i];
+        DevFrameDesc &d = T[i];
+        d.p0 = (const uint8_t *)f.plane[0];
+        d.pitch0 = f.pitch[0];
+        d.ps = f.pixel_stride;
+        d.cs = f.channel_stride;
+        d.p1 = d.p2 = nullptr;
+        d.pitch1 = d.pitch2 = 0;
+        d.c_step = 1;
+        if (fmt == FFL_DEV_I420) {
+            d.p1 = (const uint8_t *)f.plane[1]; d.pitch1 = f.pitch[1];
+            d.p2 = (const uint8_t *)f.plane[2]; d.pitch2 = f.pitch[2];
+        } else if (fmt == FFL_DEV_NV12) {
+            d.p1 = (const uint8_t *)f.plane[1]; d.pitch1 = f.pitch[1];
+            d.p2 = d.p1 + 1; d.pitch2 = f.pitch[1];
+            d.c_step = 2;
+        }
+        d.fslot = first + i;
+    }
+    DevFrontParams p;
+    p.kind = fmt == FFL_DEV_GRAY ? FFL_DEVK_GRAY : yuv ? FFL_DEVK_YUV : FFL_DEVK_BGR;
+    p.rgb = fmt == FFL_DEV_RGB;
+    p.sw = sw; p.sh = sh;
+    p.cx = cx; p.cy = cy; p.ow = c->w; p.oh = c->h;
+    p.scale_x = 1. / ((double)rw / sw);
+    p.scale_y = 1. / ((double)rh / sh);
+    p.mode = (rw == sw && rh == sh) ? FFL_FRONT_IDENTITY : (sw == 2 * rw && sh == 2 * rh) ? FFL_FRONT_AREA2 : FFL_FRONT_GENERIC;
+    // stream `copy` waits for the producer's queued work and for the batches that still read the slots
+    HIPCHK(c, hipEventRecord(c->ev_caller, cst));
+    WaitOnce wait_copy(c->s_copy);
+    HIPCHK(c, wait_copy(c->ev_caller));
+    for (int i = 0; i < n; i++)
+        if (int rc = wait_frame_free(c, wait_copy, first + i)) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_dtab, T, sizeof(DevFrameDesc) * n, hipMemcpyHostToDevice, c->s_copy));
+    {
+        ProfScope ps(c, FFL_K_FRONTEND, c->s_copy);
+        ffl_launch_frontend_dev(c->d_dtab, n, c->d_gray, c->N, p, c->s_copy);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (int rc = publish_frames(c, first, n)) return rc;
+    // the caller's later work (overwriting the sources, the allocator reusing them) runs after the frames have been read
+    HIPCHK(c, hipStreamWaitEvent(cst, ev_latest(c->up_ring).get(), 0));
+    return FFL_OK;
+}
+
+// Flow slots -> caller device memory on stream `post`, ordered after the batches that produced them and the caller's
+// queued work, and before the caller's later work; the export becomes the slots' last use.
+int ffl_export_flows(ffl_ctx *c, int n, const int *slots, float *dst, int layout, ptrdiff_t item_stride, uint64_t stream) {
+    static const char *fn = "ffl_export_flows";
+    if (!c) return FFL_ERR_INVALID;
+    std::unique_lock<std::mutex> pl(c->post_mu);  // stream `post` and post_ring, as ffl_radial / ffl_upload_flow
+    CtxLock lk(c->mu);
+    if (n < 1 || !slots || !dst) return set_err(c, FFL_ERR_INVALID, "%s: bad arguments", fn);
+    if (layout != FFL_FLOW_NHWC && layout != FFL_FLOW_NCHW)
+        return set_err(c, FFL_ERR_INVALID, "%s: unknown layout %d (FFL_FLOW_NHWC 0, FFL_FLOW_NCHW 1)", fn, layout);
+    const size_t item = sizeof(float) * 2 * c->N;
+    if ((uintptr_t)dst % 4 || item_stride % 4)
+        return set_err(c, FFL_ERR_INVALID, "%s: dst and the item stride (%td) must be multiples of 4 bytes", fn, item_stride);
+    if (n > 1 && (size_t)(item_stride < 0 ? -item_stride : item_stride) < item)
+        return set_err(c, FFL_ERR_INVALID, "%s: item stride %td is smaller than one flow field (%zu bytes)", fn, item_stride, item);
+    for (int i = 0; i < n; i++) {
+        if (slots[i] < 0 || slots[i] >= c->n_slots) return set_err(c, FFL_ERR_INVALID, "%s: flow slot %d out of range", fn, slots[i]);
+        if (!c->slot_state[slots[i]]) return set_err(c, FFL_ERR_STATE, "%s: flow slot %d holds no flow", fn, slots[i]);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t cst = (hipStream_t)(uintptr_t)stream;
+    if (int rc = refuse_capturing(c, fn, cst)) return rc;
+    const ptrdiff_t span = (ptrdiff_t)(n - 1) * item_stride;
+    const char *lo = (const char *)dst + (span < 0 ? span : 0);
+    if (int rc = dev_mem_check(c, fn, "dst", lo, (size_t)(span < 0 ? -span : span) + item)) return rc;
+    if (!c->ev_caller) HIPCHK(c, hipEventCreateWithFlags(&c->ev_caller, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(c->ev_caller, cst));
+    WaitOnce wait_post(c->s_post);
+    HIPCHK(c, wait_post(c->ev_caller));
+    for (int i = 0; i < n; i++) HIPCHK(c, wait_post(c->ev_slot_done[slots[i]].get()));
+    for (int i0 = 0; i0 < n; i0 += FFL_MAXB) {
+        const int m = n - i0 < FFL_MAXB ? n - i0 : FFL_MAXB;
+        ExportTab t;
+        for (int i = 0; i < m; i++) t.slot[i] = slots[i0 + i];
+        ffl_launch_export_flows(c->d_flow, t, m, c->N, (char *)dst + (ptrdiff_t)i0 * item_stride, item_stride, layout, c->s_post);
+    }
+    HIPCHK(c, hipGetLastError());
+    EvRef ev;
+    HIPCHK(c, c->post_ring.record(c->s_post, &ev));
+    for (int i = 0; i < n; i++) c->ev_slot_done[slots[i]] = ev;  // a batch recycling a slot waits for the export
+    HIPCHK(c, hipStreamWaitEvent(cst, ev.get(), 0));
     return FFL_OK;
 }
 

@@ -77,6 +77,28 @@ struct FrontYuvParams {   // k_frontend_yuv: 4:2:0 source window -> gray crop wi
     int mode;
 };
 
+// k_frontend_dev (ffl_upload_frames_device): frames read in place from caller device memory.  One descriptor per frame in
+// a device table (stream-ordered copy on stream `copy`); everything the frames of one call share is a kernel argument.
+enum { FFL_DEVK_GRAY = 0, FFL_DEVK_BGR = 1, FFL_DEVK_YUV = 2 };
+struct DevFrameDesc {
+    const uint8_t *p0, *p1, *p2;  // packed / first channel / Y; chroma: U and V (NV12: p2 = p1 + 1)
+    long long pitch0, pitch1, pitch2;
+    long long ps, cs;             // plane 0: bytes between horizontal neighbours / between the channels of a pixel
+    int c_step;                   // 4:2:0: bytes between horizontally adjacent chroma samples (1 I420, 2 NV12)
+    int fslot;                    // destination frame slot
+};
+struct DevFrontParams {
+    int kind, rgb;               // FFL_DEVK_*; rgb: channel 0 is R
+    int sw, sh;                  // source size
+    int cx, cy, ow, oh;          // crop origin inside the resized image, output size
+    double scale_x, scale_y;     // 1. / ((double)resize / src), formed on the host
+    int mode;                    // FFL_FRONT_*
+};
+// k_export_flows: the flow slots of one launch (at most FFL_MAXB) travel as a kernel argument
+struct ExportTab {
+    int slot[FFL_MAXB];
+};
+
 // merged launches: one 1-D grid cut into per-job block ranges
 #define FFL_MAX_JOBS 4
 enum { FFL_PYR_F1 = 0, FFL_PYR_F2, FFL_PYR_H4, FFL_PYR_H9, FFL_PYR_V4, FFL_PYR_V9 };
@@ -129,6 +151,10 @@ void ffl_launch_polyexp_multi(const PolyJob *levels, int n, int nU, PolyConsts p
 void ffl_launch_frontend(const uint8_t *src, uint8_t *gray, FrontParams p, hipStream_t st);
 void ffl_launch_frontend_yuv(const uint8_t *y, const uint8_t *u, const uint8_t *v, uint8_t *gray, FrontYuvParams p,
                              hipStream_t st);
+void ffl_launch_frontend_dev(const DevFrameDesc *tab, int n, uint8_t *gray_base, size_t N, DevFrontParams p, hipStream_t st);
+// n (<= FFL_MAXB) flow slots of `flow` (2N floats each) -> dst + i * item_stride bytes; layout 0 (H, W, 2), 1 (2, H, W)
+void ffl_launch_export_flows(const float *flow, const ExportTab &tab, int n, size_t N, char *dst, long long item_stride,
+                             int layout, hipStream_t st);
 void ffl_launch_gray(const uint8_t *bgr, uint8_t *gray, int n_pixels, hipStream_t st);
 size_t ffl_pyr_tmp_floats(int w, int h, int lw);  // per-frame size of the level's horizontal-pass buffer
 void ffl_launch_pyr_level(const uint8_t *gray_base, size_t gray_stride, const UTab *ut, int nU, int w, int h, int lw, int lh,

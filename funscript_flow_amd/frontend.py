@@ -13,6 +13,9 @@ yuv="i420" | "nv12" takes a decoder's native 4:2:0 output instead -- (3h/2, w) u
 or an `ffmpeg -pix_fmt yuv420p|nv12` pipe deliver them -- through `ffl_upload_frames_yuv` (k_frontend_yuv): the
 colour conversion runs on the device and only the source rectangle the crop window reads crosses PCIe (DESIGN.md
 section 11, appendix Y).
+
+DeviceUploader takes frames that are already in device memory (torch tensors, a GPU decoder's DLPack surfaces) through
+`ffl_upload_frames_device` (k_frontend_dev): the same operands with no host round trip.
 """
 from . import _capi
 
@@ -57,3 +60,20 @@ class DecodedUploader:
 
     def __call__(self, first_slot, frames):
         upload_decoded(self.ctx, first_slot, frames, self.vr_mode, self.rgb_order, self.yuv)
+
+
+class DeviceUploader:
+    """`upload` hook for pipeline.PairEngine taking device-resident frames: a sequence of device
+    arrays, or one (n, h, w[, c]) array, in format `fmt` ("gray", "bgr", "rgb", "i420", "nv12"; see _capi.device_frame)
+    with geometry()'s resize and crop.  `stream`: see _capi.stream_handle (None: torch's current stream at each call)."""
+
+    def __init__(self, ctx, fmt="bgr", vr_mode=False, stream=None):
+        _capi.dev_format(fmt)
+        if not isinstance(ctx, _capi.Context):
+            raise TypeError("DeviceUploader needs a funscript_flow_amd._capi.Context")
+        self.ctx, self.fmt, self.vr_mode, self.stream = ctx, fmt, bool(vr_mode), stream
+        self.resize, self.crop = geometry(ctx.width, ctx.height, self.vr_mode)
+
+    def __call__(self, first_slot, frames):
+        resize = None if self.fmt == "gray" and not self.vr_mode else self.resize   # gray: the context size, as it is
+        self.ctx.upload_frames_device(first_slot, frames, self.fmt, resize, self.crop, self.stream)

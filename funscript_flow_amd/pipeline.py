@@ -212,13 +212,23 @@ class PairEngine:
             collect(*pending.pop(0))
         return recs
 
-    def process_chunk(self, frames, pov_mode=False, cut_threshold=7.0, algo=None, farneback=OWN):
+    def process_chunk(self, frames, pov_mode=False, cut_threshold=7.0, algo=None, farneback=OWN, flows_out=None):
         """One whole chunk on one GPU: returns (dots float64[n], records) with n = len(frames)-1.  `algo`, `farneback`:
-        see pass1_pairs (default: the engine's own flow algorithm and parameters)."""
+        see pass1_pairs (default: the engine's own flow algorithm and parameters).  `flows_out`: a float32 device array of
+        (n, H, W, 2) or (n, 2, H, W) that receives every pair's flow field (Context.export_flows, on torch's current stream)
+        as its batch finishes, before its slots can be recycled; records and dots are unchanged."""
         ctx, B = self.ctx, self.B
         n = len(frames) - 1
         if n < 1:
             return np.zeros(0), []
+        layout = None
+        if flows_out is not None:
+            shp = tuple(flows_out.shape)
+            layout = ("nhwc" if shp == (n, ctx.height, ctx.width, 2) else
+                      "nchw" if shp == (n, 2, ctx.height, ctx.width) else None)
+            if layout is None:
+                raise ValueError(f"flows_out must be ({n}, {ctx.height}, {ctx.width}, 2) or ({n}, 2, {ctx.height}, "
+                                 f"{ctx.width}), got {shp}")
         dots = np.zeros(n, np.float64)
         psum = np.zeros((n + 1, 2), np.int64)  # prefix sums of pos_center: window means are exact integer
         cuts = np.zeros(n, bool)               # sums / counts, bit-identical to np.mean over the window
@@ -237,6 +247,8 @@ class PairEngine:
 
         def on_batch(js, got):
             j0 = js[0]
+            if layout is not None:   # before finalize: pass 2 below lets later batches recycle these slots
+                ctx.export_flows([j % ctx.flow_slots for j in js], flows_out[j0:js[-1] + 1], layout)
             recs_all[j0:js[-1] + 1] = got
             p = np.array([(r[0], r[1]) for r in got], np.int64)
             psum[j0 + 1:js[-1] + 2] = psum[j0] + np.cumsum(p, axis=0)

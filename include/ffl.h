@@ -25,6 +25,8 @@
  *   ffl_radial              radial_motion_weighted(flow, center, is_cut, pov_mode)  FF:761-785
  *                           for a batch (ProcessPoolExecutor.submit loop, FF:1232-1236)
  *   ffl_download_flow       the "flow" entry of that dict (tests / callers that want the array)
+ *   ffl_upload_frames_device  ffl_upload_frames_raw / _yuv / ffl_upload_frames for frames already in device memory (a GPU
+ *                           decoder's surfaces, torch tensors); ffl_export_flows: ffl_download_flow into device memory
  *   ffl_submit_pair         precompute_wrapper((p0, p1), params)                    FF:1019-1021
  *   ffl_flow_pairs_farneback  cv2.calcOpticalFlowFarneback(p0, p1, None, pyr_scale, levels, winsize, iterations, poly_n,
  *                           poly_sigma, 0) with the caller's values + the same reductions
@@ -146,6 +148,71 @@ int ffl_upload_frames_yuv(ffl_ctx *ctx, int first_slot, int n, const uint8_t *co
  * refusals as ffl_upload_frames_yuv (message through ffl_last_error(NULL)). */
 int ffl_frontend_yuv_window(int src_w, int src_h, int layout, ptrdiff_t stride_bytes, int resize_w, int resize_h,
                             int crop_x, int crop_y, int out_w, int out_h, int win[4], size_t *bytes);
+
+/* ---- device-memory I/O ------------------------------------------------------------------------
+ * Frames that already live in device memory (a GPU decoder's surfaces, torch tensors) go to frame slots without a round
+ * trip through the host, and flow fields go from flow slots into caller device memory.  Same operands, same fields.
+ *
+ * A frame is described by its planes.  Byte offset of channel c of pixel (x, y) in plane 0:
+ *     y * pitch[0] + x * pixel_stride + c * channel_stride
+ * packed HWC BGR: pixel_stride 3, channel_stride 1 (BGRA: 4, 1 -- channel 3 is never read); planar CHW: pixel_stride 1,
+ * channel_stride = the distance of the planes.  4:2:0 (pixel_stride and channel_stride unused): plane 0 = Y (pitch[0]),
+ * I420: plane 1 = U, plane 2 = V (each (h/2) x (w/2) with its own pitch); NV12: plane 1 = the interleaved UV rows
+ * (pitch[1]); plane 2 unused. */
+typedef struct ffl_dev_frame {
+    const void *plane[3];
+    ptrdiff_t pitch[3];
+    ptrdiff_t pixel_stride;
+    ptrdiff_t channel_stride;
+} ffl_dev_frame;
+#define FFL_DEV_GRAY 0 /* 1 channel; the context's size, copied as it is (no resize, no crop) */
+#define FFL_DEV_BGR 1  /* 3 channels, B first (cv2's order) */
+#define FFL_DEV_RGB 2  /* 3 channels, R first */
+#define FFL_DEV_I420 3
+#define FFL_DEV_NV12 4
+#define FFL_FLOW_NHWC 0 /* (n, H, W, 2): cv2's layout, u and v interleaved */
+#define FFL_FLOW_NCHW 1 /* (n, 2, H, W): the u plane, then the v plane */
+
+/* The geometry rules of ffl_upload_frames_device for one frame (out_w x out_h = the context's frame size).  Pure host
+ * check: no device or context needed.  FFL_ERR_INVALID with the rule in ffl_last_error(NULL): an unknown format; a size
+ * outside 1..32768; negative strides, or a pitch / pixel stride / channel stride too small for the extent (packed: pixel
+ * stride >= 3 * channel stride >= 3 and pitch >= (w - 1) * pixel stride + 2 * channel stride + 1; planar: channel stride
+ * >= pitch * h and pitch >= (w - 1) * pixel stride + 1; 4:2:0: pitch[0] >= w, I420 chroma pitches >= w / 2, NV12
+ * pitch[1] >= w); odd 4:2:0 sizes; gray with a resize, a crop or a size other than the context's; a crop window that does
+ * not fit the resized frame; a NULL plane the format needs. */
+int ffl_dev_frame_check(int format, int src_w, int src_h, const ffl_dev_frame *f, int resize_w, int resize_h, int crop_x,
+                        int crop_y, int out_w, int out_h);
+
+/* n device-resident frames (format FFL_DEV_*, each src_w x src_h) -> frame slots first_slot .. first_slot+n-1, as
+ *   gray( resize(frame, (resize_w, resize_h)) [crop_y : crop_y+height, crop_x : crop_x+width] )
+ * with exactly the bytes of the host paths for the same pixels: ffl_upload_frames_raw's rules for BGR / RGB,
+ * ffl_upload_frames_yuv's (appendix Y) for I420 / NV12, ffl_upload_frames' copy for gray.  Every frame is checked
+ * (ffl_dev_frame_check) and every plane it reads must be device memory of the context's device, all of it inside one
+ * allocation (hipPointerGetAttributes, hipMemGetAddressRange); page-locked host memory -- ffl_host_alloc's included -- is
+ * refused: it belongs to the host upload calls.  Refusals happen before any device work.
+ * Stream contract (`stream` is a hipStream_t as an integer; 0 = the null stream):
+ *   - a stream that is capturing a graph is refused with FFL_ERR_STATE; that check is the first HIP call made on it;
+ *   - the frames are read after the work queued on `stream` before the call (an event recorded on `stream`, waited for by
+ *     the library's upload stream), by ONE k_frontend_dev launch for all n frames;
+ *   - `stream` is made to wait (hipStreamWaitEvent) for that launch: work queued on it afterwards -- overwriting the
+ *     sources, or the caching allocator reusing them -- runs after the frames have been read;
+ *   - frame slots are published and their previous readers waited for as ffl_upload_frames_raw does it;
+ *   - the host never waits for the device, except where the slot-reuse rules of the host uploads make it wait too.
+ * Nothing of this call is ever captured into the library's graphs. */
+int ffl_upload_frames_device(ffl_ctx *ctx, int first_slot, int n, const ffl_dev_frame *frames, int format, int src_w,
+                             int src_h, int resize_w, int resize_h, int crop_x, int crop_y, uint64_t stream);
+
+/* The finished flow fields of flow_slots[0..n) -> dst + i * item_stride_bytes, as (H, W, 2) float32 (FFL_FLOW_NHWC) or as
+ * (2, H, W) float32 (FFL_FLOW_NCHW); each item is contiguous, items may be anywhere apart (|stride| >= 8 * W * H bytes).
+ * dst must be 4-byte aligned device memory of the context's device with the whole extent in one allocation; the stride a
+ * multiple of 4 (16-byte aligned items take the 16-byte path).  Refused: a slot out of range (FFL_ERR_INVALID) or holding
+ * no flow (FFL_ERR_STATE), an unknown layout, a capturing `stream` (FFL_ERR_STATE, the first HIP call made on it).
+ * Stream contract: the library's stream waits for the batches that produced the slots and for the work queued on
+ * `stream` before the call (dst may still be being read), writes dst (k_export_flows), and `stream` is made to wait for
+ * that.  The export counts as a use of the slots: a later batch that recycles one of them waits for it on the device.
+ * The host never waits. */
+int ffl_export_flows(ffl_ctx *ctx, int n, const int *flow_slots, float *dst, int layout, ptrdiff_t item_stride_bytes,
+                     uint64_t stream);
 
 /* Page-locked host memory owned by the context (freed by ffl_host_free or ffl_destroy).  A decoder that writes its
  * frames into such a buffer saves the library's staging copy: ffl_upload_frame(s) of tightly packed frames that lie
