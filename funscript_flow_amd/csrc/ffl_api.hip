@@ -278,7 +278,7 @@ struct ffl_ctx {
     // caller's stream (waited for at once, so one is enough), and the per-call frame descriptor tables -- a pinned copy
     // per up_ring entry (n_fslots descriptors each) and the device table k_frontend_dev reads (stream `copy`)
     hipEvent_t ev_caller = nullptr;
-    DevFrameDesc *h_dtab = nullptr, *d_dtab = nullptr;
+    FrameDesc *h_dtab = nullptr, *d_dtab = nullptr;
     // flow slots
     float *d_flow = nullptr;          // [n_slots][2N]
     // Result records live in pinned, device-mapped host memory: the reduction kernels store their
@@ -566,6 +566,71 @@ static void publish_slots(ffl_ctx *c, int n, const int *slots, EvRef done, bool 
         c->ev_slot_done[slots[i]] = done;
         c->slot_state[slots[i]] = ready;
     }
+}
+
+// The geometry rules of every front-end path: source, resize and output sizes within 32768, the crop window inside the
+// resized frame.  Fills the geometry, resize mode and scales of *p (the caller sets kind and rgb); fn prefixes the message.
+static int front_geometry(ffl_ctx *c, const char *fn, int sw, int sh, int rw, int rh, int cx, int cy, int ow, int oh,
+                          FrontParams *p) {
+    if (sw < 1 || sh < 1 || sw > 32768 || sh > 32768 || rw < 1 || rh < 1 || rw > 32768 || rh > 32768 || ow < 1 || oh < 1)
+        return set_err(c, FFL_ERR_INVALID, "%s: unsupported source %dx%d / resize %dx%d / output %dx%d", fn, sw, sh, rw, rh, ow, oh);
+    if (cx < 0 || cy < 0 || cx + ow > rw || cy + oh > rh)
+        return set_err(c, FFL_ERR_INVALID, "%s: crop window (%d, %d) + %dx%d does not fit the %dx%d resized frame", fn, cx, cy, ow,
+                       oh, rw, rh);
+    p->sw = sw; p->sh = sh;
+    p->cx = cx; p->cy = cy; p->ow = ow; p->oh = oh;
+    p->scale_x = 1. / ((double)rw / sw);
+    p->scale_y = 1. / ((double)rh / sh);
+    p->mode = (rw == sw && rh == sh) ? FFL_FRONT_IDENTITY : (sw == 2 * rw && sh == 2 * rh) ? FFL_FRONT_AREA2 : FFL_FRONT_GENERIC;
+    return FFL_OK;
+}
+
+// The frame-by-frame loop of ffl_upload_frames_raw and ffl_upload_frames_yuv, called with up_mu and the context lock held.
+// Frame i takes the next buffer pair of the raw-frame ring; direct(i) says whether its fbytes go to the device straight
+// out of caller memory (send_direct(i, d)) or are first staged into the pinned buffer (stage(i, h, copy_threads), run
+// WITHOUT the context lock) and sent as one transfer; one k_frontend launch then reads desc(d) into frame slot first + i.
+template <class Direct, class Stage, class SendDirect, class Desc>
+static int upload_staged(ffl_ctx *c, CtxLock &lk, int first, int n, size_t fbytes, const FrontParams &fp, Direct direct,
+                         Stage stage, SendDirect send_direct, Desc desc) {
+    for (int i = 0; i < n; i++) {
+        const int fs = first + i;
+        auto &rb = c->raw[c->raw_next++ % FFL_RAW_RING];
+        if (rb.busy) {  // its previous frame has left both buffers
+            if (int rc = wait_unlocked(c, lk, &rb.ev, 1)) return rc;
+        }
+        if (rb.cap < fbytes) {
+            hipFree(rb.d);
+            hipHostFree(rb.h);
+            rb.d = rb.h = nullptr;
+            rb.cap = 0;
+            HIPCHK(c, hipMalloc(&rb.d, fbytes));
+            HIPCHK(c, hipHostMalloc(&rb.h, fbytes, hipHostMallocDefault));
+            rb.cap = fbytes;
+        }
+        if (!rb.ev) HIPCHK(c, hipEventCreateWithFlags(&rb.ev, hipEventDisableTiming));
+        const bool dir = direct(i);
+        if (!dir) {
+            const int copy_threads = c->opt.copy_threads;
+            lk.unlock();  // the staging copy runs without the context lock (up_mu protects the ring and the pool)
+            stage(i, rb.h, copy_threads);
+            lk.lock();
+        }
+        // looked up under the lock, after the staging copy: a batch queued meanwhile is ordered ahead of the transfer
+        WaitOnce wait_copy(c->s_copy);
+        if (int rc = wait_frame_free(c, wait_copy, fs)) return rc;
+        if (dir) {
+            if (int rc = send_direct(i, rb.d)) return rc;
+        } else {
+            HIPCHK(c, hipMemcpyAsync(rb.d, rb.h, fbytes, hipMemcpyHostToDevice, c->s_copy));
+        }
+        {
+            ProfScope ps(c, FFL_K_FRONTEND, c->s_copy);
+            ffl_launch_frontend(desc(rb.d), c->d_gray + (size_t)fs * c->N, fp, c->s_copy);
+        }
+        HIPCHK(c, hipEventRecord(rb.ev, c->s_copy));
+        rb.busy = true;
+    }
+    return publish_frames(c, first, n);
 }
 
 // ---- API -----------------------------------------------------------------------------------------
@@ -939,81 +1004,49 @@ int ffl_upload_frames(ffl_ctx *c, int first, int n, const uint8_t *const *frames
 // cost, so there is nothing to gain from batching the launches.
 int ffl_upload_frames_raw(ffl_ctx *c, int first, int n, const uint8_t *const *frames, int sw, int sh,
                           ptrdiff_t stride_bytes, int rgb_order, int rw, int rh, int crop_x, int crop_y) {
+    static const char *fn = "ffl_upload_frames_raw";
     if (!c) return FFL_ERR_INVALID;
     std::unique_lock<std::mutex> ul(c->up_mu);
     CtxLock lk(c->mu);
     if (!frames || n < 1 || first < 0 || first + n > c->n_fslots)
-        return set_err(c, FFL_ERR_INVALID, "ffl_upload_frames_raw: bad frame slot range %d..%d", first, first + n - 1);
-    if (sw < 1 || sh < 1 || sw > 32768 || sh > 32768 || rw < 1 || rh < 1 || rw > 32768 || rh > 32768)
-        return set_err(c, FFL_ERR_INVALID, "ffl_upload_frames_raw: unsupported source %dx%d / resize %dx%d", sw, sh, rw, rh);
-    if (stride_bytes < (ptrdiff_t)sw * 3)
-        return set_err(c, FFL_ERR_INVALID, "ffl_upload_frames_raw: stride %td < row bytes %d", stride_bytes, sw * 3);
-    if (crop_x < 0 || crop_y < 0 || crop_x + c->w > rw || crop_y + c->h > rh)
-        return set_err(c, FFL_ERR_INVALID,
-                       "ffl_upload_frames_raw: crop window (%d, %d) + %dx%d does not fit the %dx%d resized frame", crop_x,
-                       crop_y, c->w, c->h, rw, rh);
-    for (int i = 0; i < n; i++)
-        if (!frames[i]) return set_err(c, FFL_ERR_INVALID, "ffl_upload_frames_raw: frame %d is NULL", i);
-    HIPCHK(c, hipSetDevice(c->device));
+        return set_err(c, FFL_ERR_INVALID, "%s: bad frame slot range %d..%d", fn, first, first + n - 1);
     FrontParams fp;
-    fp.sw = sw; fp.sh = sh;
-    fp.stride = (size_t)sw * 3;
-    fp.cx = crop_x; fp.cy = crop_y; fp.ow = c->w; fp.oh = c->h;
-    fp.scale_x = 1. / ((double)rw / sw);
-    fp.scale_y = 1. / ((double)rh / sh);
-    fp.mode = (rw == sw && rh == sh) ? FFL_FRONT_IDENTITY
-              : (sw == 2 * rw && sh == 2 * rh) ? FFL_FRONT_AREA2 : FFL_FRONT_GENERIC;
+    if (int rc = front_geometry(c, fn, sw, sh, rw, rh, crop_x, crop_y, c->w, c->h, &fp)) return rc;
+    if (stride_bytes < (ptrdiff_t)sw * 3)
+        return set_err(c, FFL_ERR_INVALID, "%s: stride %td < row bytes %d", fn, stride_bytes, sw * 3);
+    for (int i = 0; i < n; i++)
+        if (!frames[i]) return set_err(c, FFL_ERR_INVALID, "%s: frame %d is NULL", fn, i);
+    HIPCHK(c, hipSetDevice(c->device));
+    fp.kind = FFL_SRC_BGR;
     fp.rgb = rgb_order != 0;
-    const size_t fbytes = fp.stride * sh;
-    for (int i = 0; i < n; i++) {
-        const int fs = first + i;
-        auto &rb = c->raw[c->raw_next++ % FFL_RAW_RING];
-        if (rb.busy) {  // its previous frame has left both buffers
-            if (int rc = wait_unlocked(c, lk, &rb.ev, 1)) return rc;
-        }
-        if (rb.cap < fbytes) {
-            hipFree(rb.d);
-            hipHostFree(rb.h);
-            rb.d = rb.h = nullptr;
-            rb.cap = 0;
-            HIPCHK(c, hipMalloc(&rb.d, fbytes));
-            HIPCHK(c, hipHostMalloc(&rb.h, fbytes, hipHostMallocDefault));
-            rb.cap = fbytes;
-        }
-        if (!rb.ev) HIPCHK(c, hipEventCreateWithFlags(&rb.ev, hipEventDisableTiming));
-        const uint8_t *data = frames[i];
-        // a tightly packed frame in ffl_host_alloc memory goes to the device straight out of it
-        const bool direct = (size_t)stride_bytes == fp.stride && in_host_buf(c, data, fbytes);
-        if (!direct) {
-            const int copy_threads = c->opt.copy_threads;
-            lk.unlock();  // the staging copy runs without the context lock (up_mu protects the ring and the pool)
-            c->pool.copy(rb.h, &data, 1, stride_bytes, fp.stride, sh, copy_threads);
-            lk.lock();
-        }
-        // looked up under the lock, after the staging copy: a batch queued meanwhile is ordered ahead of the transfer
-        WaitOnce wait_copy(c->s_copy);
-        if (int rc = wait_frame_free(c, wait_copy, fs)) return rc;
-        HIPCHK(c, hipMemcpyAsync(rb.d, direct ? data : rb.h, fbytes, hipMemcpyHostToDevice, c->s_copy));
-        {
-            ProfScope ps(c, FFL_K_FRONTEND, c->s_copy);
-            ffl_launch_frontend(rb.d, c->d_gray + (size_t)fs * c->N, fp, c->s_copy);
-        }
-        HIPCHK(c, hipEventRecord(rb.ev, c->s_copy));
-        rb.busy = true;
-    }
-    return publish_frames(c, first, n);
+    const size_t row = (size_t)sw * 3, fbytes = row * sh;
+    // a tightly packed frame in ffl_host_alloc memory goes to the device straight out of it
+    auto direct = [&](int i) { return (size_t)stride_bytes == row && in_host_buf(c, frames[i], fbytes); };
+    auto stage = [&](int i, uint8_t *h, int threads) { c->pool.copy(h, frames + i, 1, stride_bytes, row, sh, threads); };
+    auto send_direct = [&](int i, uint8_t *d) -> int {
+        HIPCHK(c, hipMemcpyAsync(d, frames[i], fbytes, hipMemcpyHostToDevice, c->s_copy));
+        return FFL_OK;
+    };
+    auto desc = [&](const uint8_t *d) {
+        FrameDesc s = {};
+        s.p0 = d;
+        s.pitch0 = row;
+        s.ps = 3;
+        s.cs = 1;
+        return s;
+    };
+    return upload_staged(c, lk, first, n, fbytes, fp, direct, stage, send_direct, desc);
 }
 
 // ---- 4:2:0 YUV input ---------------------------------------------------------------
 // Where the source rectangle of a YUV upload lies: the source rows / columns the crop window's first and last output
-// row / column map to (k_frontend_yuv's arithmetic; it is monotone in the output coordinate), widened by one pixel per side
+// row / column map to (k_frontend's arithmetic; it is monotone in the output coordinate), widened by one pixel per side
 // and rounded out -- rows to even coordinates (chroma alignment), columns to multiples of 16 so that the rows of every
 // plane start aligned in the frame (a 2-D copy out of host memory whose rows start unaligned ran at 0.3 GB/s) --
 // and clamped to the frame.  The widening makes it a superset even if host and device round the coordinate arithmetic
 // differently; it is not tight to the last pixel.
 struct YuvWin {
-    int mode, x0, y0, w, h;  // k_frontend_yuv mode; window origin and size (all even)
-    double scale_x, scale_y;
+    int x0, y0, w, h;  // window origin and size (all even)
 };
 
 static void yuv_span(int d0, int d1, int s, double scale, int mode, int align, int *lo, int *hi_excl) {
@@ -1032,11 +1065,10 @@ static void yuv_span(int d0, int d1, int s, double scale, int mode, int align, i
     *hi_excl = std::min((b + align - 1) / align * align, s);  // s is even
 }
 
-// Every refusal of the YUV path (messages name the rule); fn prefixes the message.
+// Every refusal of the YUV path (messages name the rule); fn prefixes the message.  Fills the geometry of *fp and the
+// window.
 static int yuv_window(ffl_ctx *c, const char *fn, int sw, int sh, int layout, ptrdiff_t stride, int rw, int rh, int crop_x,
-                      int crop_y, int ow, int oh, YuvWin *out) {
-    if (sw < 2 || sh < 2 || sw > 32768 || sh > 32768 || rw < 1 || rh < 1 || rw > 32768 || rh > 32768 || ow < 1 || oh < 1)
-        return set_err(c, FFL_ERR_INVALID, "%s: unsupported source %dx%d / resize %dx%d / output %dx%d", fn, sw, sh, rw, rh, ow, oh);
+                      int crop_y, int ow, int oh, FrontParams *fp, YuvWin *out) {
     if ((sw & 1) || (sh & 1))
         return set_err(c, FFL_ERR_INVALID, "%s: 4:2:0 needs an even width and height, source is %dx%d", fn, sw, sh);
     if (layout != FFL_YUV_I420 && layout != FFL_YUV_NV12)
@@ -1046,15 +1078,10 @@ static int yuv_window(ffl_ctx *c, const char *fn, int sw, int sh, int layout, pt
                        fn, stride, sw);
     if (layout == FFL_YUV_NV12 && stride < (ptrdiff_t)sw)
         return set_err(c, FFL_ERR_INVALID, "%s: NV12 needs stride >= width, got %td for width %d", fn, stride, sw);
-    if (crop_x < 0 || crop_y < 0 || crop_x + ow > rw || crop_y + oh > rh)
-        return set_err(c, FFL_ERR_INVALID, "%s: crop window (%d, %d) + %dx%d does not fit the %dx%d resized frame", fn, crop_x,
-                       crop_y, ow, oh, rw, rh);
-    out->mode = (rw == sw && rh == sh) ? FFL_FRONT_IDENTITY : (sw == 2 * rw && sh == 2 * rh) ? FFL_FRONT_AREA2 : FFL_FRONT_GENERIC;
-    out->scale_x = 1. / ((double)rw / sw);
-    out->scale_y = 1. / ((double)rh / sh);
+    if (int rc = front_geometry(c, fn, sw, sh, rw, rh, crop_x, crop_y, ow, oh, fp)) return rc;
     int x1, y1;
-    yuv_span(crop_x, crop_x + ow - 1, sw, out->scale_x, out->mode, 16, &out->x0, &x1);
-    yuv_span(crop_y, crop_y + oh - 1, sh, out->scale_y, out->mode, 2, &out->y0, &y1);
+    yuv_span(crop_x, crop_x + ow - 1, sw, fp->scale_x, fp->mode, 16, &out->x0, &x1);
+    yuv_span(crop_y, crop_y + oh - 1, sh, fp->scale_y, fp->mode, 2, &out->y0, &y1);
     out->w = x1 - out->x0;
     out->h = y1 - out->y0;
     return FFL_OK;
@@ -1062,9 +1089,10 @@ static int yuv_window(ffl_ctx *c, const char *fn, int sw, int sh, int layout, pt
 
 int ffl_frontend_yuv_window(int src_w, int src_h, int layout, ptrdiff_t stride_bytes, int resize_w, int resize_h, int crop_x,
                             int crop_y, int out_w, int out_h, int win[4], size_t *bytes) {
+    FrontParams fp;
     YuvWin yw;
     if (int rc = yuv_window(nullptr, "ffl_frontend_yuv_window", src_w, src_h, layout, stride_bytes, resize_w, resize_h, crop_x,
-                            crop_y, out_w, out_h, &yw))
+                            crop_y, out_w, out_h, &fp, &yw))
         return rc;
     if (win) {
         win[0] = yw.x0; win[1] = yw.y0; win[2] = yw.w; win[3] = yw.h;
@@ -1073,24 +1101,27 @@ int ffl_frontend_yuv_window(int src_w, int src_h, int layout, ptrdiff_t stride_b
     return FFL_OK;
 }
 
-// Decoded 4:2:0 frames -> gray frame slots through k_frontend_yuv.  Frame by frame, as ffl_upload_frames_raw: only the
+// Decoded 4:2:0 frames -> gray frame slots through k_frontend.  Frame by frame, as ffl_upload_frames_raw: only the
 // window the crop samples travels -- out of ffl_host_alloc memory one 2-D copy per plane (when every plane's rows start
 // 4-byte aligned and are a multiple of 4 bytes long: unaligned ones take a slow path in the runtime's copy), otherwise
 // copied into the pinned ring buffer and sent as one transfer.  On the device the window is packed: Y (w x h), then U and V (w/2 x h/2 each,
 // I420) or the interleaved UV rows (w x h/2, NV12).
 int ffl_upload_frames_yuv(ffl_ctx *c, int first, int n, const uint8_t *const *frames, int sw, int sh, ptrdiff_t stride_bytes,
                           int layout, int rw, int rh, int crop_x, int crop_y) {
+    static const char *fn = "ffl_upload_frames_yuv";
     if (!c) return FFL_ERR_INVALID;
     std::unique_lock<std::mutex> ul(c->up_mu);
     CtxLock lk(c->mu);
     if (!frames || n < 1 || first < 0 || first + n > c->n_fslots)
-        return set_err(c, FFL_ERR_INVALID, "ffl_upload_frames_yuv: bad frame slot range %d..%d", first, first + n - 1);
+        return set_err(c, FFL_ERR_INVALID, "%s: bad frame slot range %d..%d", fn, first, first + n - 1);
+    FrontParams fp;
     YuvWin yw;
-    if (int rc = yuv_window(c, "ffl_upload_frames_yuv", sw, sh, layout, stride_bytes, rw, rh, crop_x, crop_y, c->w, c->h, &yw))
-        return rc;
+    if (int rc = yuv_window(c, fn, sw, sh, layout, stride_bytes, rw, rh, crop_x, crop_y, c->w, c->h, &fp, &yw)) return rc;
     for (int i = 0; i < n; i++)
-        if (!frames[i]) return set_err(c, FFL_ERR_INVALID, "ffl_upload_frames_yuv: frame %d is NULL", i);
+        if (!frames[i]) return set_err(c, FFL_ERR_INVALID, "%s: frame %d is NULL", fn, i);
     HIPCHK(c, hipSetDevice(c->device));
+    fp.kind = FFL_SRC_YUV;
+    fp.rgb = 0;
     const bool nv12 = layout == FFL_YUV_NV12;
     const size_t ybytes = (size_t)yw.w * yw.h, fbytes = ybytes * 3 / 2;
     // the planes of the window: source offset and pitch inside the frame, row bytes, rows, offset in the packed window
@@ -1112,64 +1143,37 @@ int ffl_upload_frames_yuv(ffl_ctx *c, int first, int n, const uint8_t *const *fr
         pl[2] = {u0 + ch * cw, ybytes + ybytes / 4, (ptrdiff_t)cw, (size_t)yw.w / 2, yw.h / 2};
     }
     const size_t span = (size_t)stride_bytes * (sh + sh / 2 - 1) + sw;  // bytes of one frame array
-    FrontYuvParams fp;
-    fp.sw = sw; fp.sh = sh;
-    fp.wx = yw.x0; fp.wy = yw.y0;
-    fp.y_pitch = yw.w;
-    fp.c_pitch = nv12 ? yw.w : yw.w / 2;
-    fp.c_step = nv12 ? 2 : 1;
-    fp.cx = crop_x; fp.cy = crop_y; fp.ow = c->w; fp.oh = c->h;
-    fp.scale_x = yw.scale_x; fp.scale_y = yw.scale_y;
-    fp.mode = yw.mode;
-    for (int i = 0; i < n; i++) {
-        const int fs = first + i;
-        auto &rb = c->raw[c->raw_next++ % FFL_RAW_RING];
-        if (rb.busy) {  // its previous frame has left both buffers
-            if (int rc = wait_unlocked(c, lk, &rb.ev, 1)) return rc;
-        }
-        if (rb.cap < fbytes) {
-            hipFree(rb.d);
-            hipHostFree(rb.h);
-            rb.d = rb.h = nullptr;
-            rb.cap = 0;
-            HIPCHK(c, hipMalloc(&rb.d, fbytes));
-            HIPCHK(c, hipHostMalloc(&rb.h, fbytes, hipHostMallocDefault));
-            rb.cap = fbytes;
-        }
-        if (!rb.ev) HIPCHK(c, hipEventCreateWithFlags(&rb.ev, hipEventDisableTiming));
-        const uint8_t *data = frames[i];
-        bool direct = in_host_buf(c, data, span);
-        for (int k = 0; direct && k < np; k++)
-            direct = ((uintptr_t)(data + pl[k].src) | (size_t)pl[k].pitch | pl[k].row) % 4 == 0;
-        if (!direct) {
-            const int copy_threads = c->opt.copy_threads;
-            lk.unlock();  // the staging copy runs without the context lock (up_mu protects the ring and the pool)
-            const uint8_t *src[2] = {data + pl[0].src, nullptr};
-            c->pool.copy(rb.h, src, 1, pl[0].pitch, pl[0].row, pl[0].rows, copy_threads);
-            src[0] = data + pl[1].src;
-            if (!nv12) src[1] = data + pl[2].src;  // U and V are shaped alike and packed back to back: one shared copy
-            c->pool.copy(rb.h + pl[1].dst, src, nv12 ? 1 : 2, pl[1].pitch, pl[1].row, pl[1].rows, copy_threads);
-            lk.lock();
-        }
-        // looked up under the lock, after the staging copy: a batch queued meanwhile is ordered ahead of the transfer
-        WaitOnce wait_copy(c->s_copy);
-        if (int rc = wait_frame_free(c, wait_copy, fs)) return rc;
-        if (direct) {
-            for (int k = 0; k < np; k++)
-                HIPCHK(c, hipMemcpy2DAsync(rb.d + pl[k].dst, pl[k].row, data + pl[k].src, (size_t)pl[k].pitch, pl[k].row,
-                                           (size_t)pl[k].rows, hipMemcpyHostToDevice, c->s_copy));
-        } else {
-            HIPCHK(c, hipMemcpyAsync(rb.d, rb.h, fbytes, hipMemcpyHostToDevice, c->s_copy));
-        }
-        {
-            ProfScope ps(c, FFL_K_FRONTEND, c->s_copy);
-            const uint8_t *u = rb.d + ybytes, *v = nv12 ? u + 1 : u + ybytes / 4;
-            ffl_launch_frontend_yuv(rb.d, u, v, c->d_gray + (size_t)fs * c->N, fp, c->s_copy);
-        }
-        HIPCHK(c, hipEventRecord(rb.ev, c->s_copy));
-        rb.busy = true;
-    }
-    return publish_frames(c, first, n);
+    auto direct = [&](int i) {
+        bool ok = in_host_buf(c, frames[i], span);
+        for (int k = 0; ok && k < np; k++) ok = ((uintptr_t)(frames[i] + pl[k].src) | (size_t)pl[k].pitch | pl[k].row) % 4 == 0;
+        return ok;
+    };
+    auto stage = [&](int i, uint8_t *h, int threads) {
+        const uint8_t *src[2] = {frames[i] + pl[0].src, nullptr};
+        c->pool.copy(h, src, 1, pl[0].pitch, pl[0].row, pl[0].rows, threads);
+        src[0] = frames[i] + pl[1].src;
+        if (!nv12) src[1] = frames[i] + pl[2].src;  // U and V are shaped alike and packed back to back: one shared copy
+        c->pool.copy(h + pl[1].dst, src, nv12 ? 1 : 2, pl[1].pitch, pl[1].row, pl[1].rows, threads);
+    };
+    auto send_direct = [&](int i, uint8_t *d) -> int {
+        for (int k = 0; k < np; k++)
+            HIPCHK(c, hipMemcpy2DAsync(d + pl[k].dst, pl[k].row, frames[i] + pl[k].src, (size_t)pl[k].pitch, pl[k].row,
+                                       (size_t)pl[k].rows, hipMemcpyHostToDevice, c->s_copy));
+        return FFL_OK;
+    };
+    auto desc = [&](const uint8_t *d) {  // the window's planes: their origin in the frame is (x0, y0)
+        FrameDesc s = {};
+        s.p0 = d;
+        s.p1 = d + ybytes;
+        s.p2 = nv12 ? s.p1 + 1 : s.p1 + ybytes / 4;
+        s.pitch0 = yw.w;
+        s.pitch1 = s.pitch2 = nv12 ? yw.w : yw.w / 2;
+        s.c_step = nv12 ? 2 : 1;
+        s.wx = yw.x0;
+        s.wy = yw.y0;
+        return s;
+    };
+    return upload_staged(c, lk, first, n, fbytes, fp, direct, stage, send_direct, desc);
 }
 
 int ffl_upload_frame(ffl_ctx *c, int fslot, const uint8_t *data, int width, int height, int channels,
@@ -1979,14 +1983,13 @@ int ffl_download_flow(ffl_ctx *c, int slot, float *dst) {
 }
 
 // ---- device-memory I/O -------------------------------------------------------------------------
-// Every geometry rule of a device frame (ffl.h, ffl_dev_frame_check); fn and frame index prefix the message.
+// Every geometry rule of a device frame (ffl.h, ffl_dev_frame_check); fn and frame index prefix the message.  Fills the
+// geometry of *p.
 static int dev_frame_check(ffl_ctx *c, const char *fn, int idx, int fmt, int sw, int sh, const ffl_dev_frame *f, int rw, int rh,
-                           int cx, int cy, int ow, int oh) {
+                           int cx, int cy, int ow, int oh, FrontParams *p) {
     if (!f) return set_err(c, FFL_ERR_INVALID, "%s: frame %d: NULL descriptor", fn, idx);
     if (fmt < FFL_DEV_GRAY || fmt > FFL_DEV_NV12)
         return set_err(c, FFL_ERR_INVALID, "%s: unknown format %d (FFL_DEV_GRAY 0, BGR 1, RGB 2, I420 3, NV12 4)", fn, fmt);
-    if (sw < 1 || sh < 1 || sw > 32768 || sh > 32768 || rw < 1 || rh < 1 || rw > 32768 || rh > 32768 || ow < 1 || oh < 1)
-        return set_err(c, FFL_ERR_INVALID, "%s: unsupported source %dx%d / resize %dx%d / output %dx%d", fn, sw, sh, rw, rh, ow, oh);
     const bool yuv = fmt == FFL_DEV_I420 || fmt == FFL_DEV_NV12;
     if (fmt == FFL_DEV_GRAY && (rw != sw || rh != sh))
         return set_err(c, FFL_ERR_INVALID, "%s: gray frames are copied as they are: a resize (%dx%d -> %dx%d) is refused", fn, sw, sh,
@@ -1995,9 +1998,7 @@ static int dev_frame_check(ffl_ctx *c, const char *fn, int idx, int fmt, int sw,
         return set_err(c, FFL_ERR_INVALID, "%s: a gray frame must be the context size %dx%d, got %dx%d", fn, ow, oh, sw, sh);
     if (yuv && ((sw & 1) || (sh & 1)))
         return set_err(c, FFL_ERR_INVALID, "%s: 4:2:0 needs an even width and height, source is %dx%d", fn, sw, sh);
-    if (cx < 0 || cy < 0 || cx + ow > rw || cy + oh > rh)
-        return set_err(c, FFL_ERR_INVALID, "%s: crop window (%d, %d) + %dx%d does not fit the %dx%d resized frame", fn, cx, cy, ow,
-                       oh, rw, rh);
+    if (int rc = front_geometry(c, fn, sw, sh, rw, rh, cx, cy, ow, oh, p)) return rc;
     const ptrdiff_t big = (ptrdiff_t)1 << 40;
     const ptrdiff_t p0 = f->pitch[0], ps = f->pixel_stride, cs = f->channel_stride;
     if (!f->plane[0] || (yuv && !f->plane[1]) || (fmt == FFL_DEV_I420 && !f->plane[2]))
@@ -2100,7 +2101,8 @@ static int refuse_capturing(ffl_ctx *c, const char *fn, hipStream_t st) {
 }
 
 int ffl_dev_frame_check(int format, int sw, int sh, const ffl_dev_frame *f, int rw, int rh, int cx, int cy, int out_w, int out_h) {
-    return dev_frame_check(nullptr, "ffl_dev_frame_check", 0, format, sw, sh, f, rw, rh, cx, cy, out_w, out_h);
+    FrontParams p;
+    return dev_frame_check(nullptr, "ffl_dev_frame_check", 0, format, sw, sh, f, rw, rh, cx, cy, out_w, out_h, &p);
 }
 
 // Device frames -> gray frame slots through ONE k_frontend_dev launch on stream `copy`, ordered after the caller's queued
@@ -2114,8 +2116,9 @@ int ffl_upload_frames_device(ffl_ctx *c, int first, int n, const ffl_dev_frame *
     CtxLock lk(c->mu);
     if (!frames || n < 1 || first < 0 || first + n > c->n_fslots)
         return set_err(c, FFL_ERR_INVALID, "%s: bad frame slot range %d..%d", fn, first, first + n - 1);
+    FrontParams p;
     for (int i = 0; i < n; i++)
-        if (int rc = dev_frame_check(c, fn, i, fmt, sw, sh, &frames[i], rw, rh, cx, cy, c->w, c->h)) return rc;
+        if (int rc = dev_frame_check(c, fn, i, fmt, sw, sh, &frames[i], rw, rh, cx, cy, c->w, c->h, &p)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t cst = (hipStream_t)(uintptr_t)stream;
     if (int rc = refuse_capturing(c, fn, cst)) return rc;
@@ -2130,22 +2133,21 @@ int ffl_upload_frames_device(ffl_ctx *c, int first, int n, const ffl_dev_frame *
     const size_t ring = c->up_ring.ev.size();
     if (!c->ev_caller) HIPCHK(c, hipEventCreateWithFlags(&c->ev_caller, hipEventDisableTiming));
     if (!c->d_dtab) {
-        HIPCHK(c, hipMalloc(&c->d_dtab, sizeof(DevFrameDesc) * c->n_fslots));
-        HIPCHK(c, hipHostMalloc(&c->h_dtab, sizeof(DevFrameDesc) * c->n_fslots * ring, hipHostMallocDefault));
+        HIPCHK(c, hipMalloc(&c->d_dtab, sizeof(FrameDesc) * c->n_fslots));
+        HIPCHK(c, hipHostMalloc(&c->h_dtab, sizeof(FrameDesc) * c->n_fslots * ring, hipHostMallocDefault));
     }
     // the pinned table of the entry publish_frames records below: settled, so its copy of 32 calls ago has been consumed
     HIPCHK(c, c->up_ring.settle_next());
-    DevFrameDesc *T = c->h_dtab + (size_t)(c->up_ring.next % ring) * c->n_fslots;
+    FrameDesc *T = c->h_dtab + (size_t)(c->up_ring.next % ring) * c->n_fslots;
     const bool yuv = fmt == FFL_DEV_I420 || fmt == FFL_DEV_NV12;
     for (int i = 0; i < n; i++) {
         const ffl_dev_frame &f = frames[i];
-        DevFrameDesc &d = T[i];
+        FrameDesc &d = T[i];
+        d = FrameDesc();
         d.p0 = (const uint8_t *)f.plane[0];
         d.pitch0 = f.pitch[0];
         d.ps = f.pixel_stride;
         d.cs = f.channel_stride;
-        d.p1 = d.p2 = nullptr;
-        d.pitch1 = d.pitch2 = 0;
         d.c_step = 1;
         if (fmt == FFL_DEV_I420) {
             d.p1 = (const uint8_t *)f.plane[1]; d.pitch1 = f.pitch[1];
@@ -2157,21 +2159,15 @@ int ffl_upload_frames_device(ffl_ctx *c, int first, int n, const ffl_dev_frame *
         }
         d.fslot = first + i;
     }
-    DevFrontParams p;
-    p.kind = fmt == FFL_DEV_GRAY ? FFL_DEVK_GRAY : yuv ? FFL_DEVK_YUV : FFL_DEVK_BGR;
+    p.kind = fmt == FFL_DEV_GRAY ? FFL_SRC_GRAY : yuv ? FFL_SRC_YUV : FFL_SRC_BGR;
     p.rgb = fmt == FFL_DEV_RGB;
-    p.sw = sw; p.sh = sh;
-    p.cx = cx; p.cy = cy; p.ow = c->w; p.oh = c->h;
-    p.scale_x = 1. / ((double)rw / sw);
-    p.scale_y = 1. / ((double)rh / sh);
-    p.mode = (rw == sw && rh == sh) ? FFL_FRONT_IDENTITY : (sw == 2 * rw && sh == 2 * rh) ? FFL_FRONT_AREA2 : FFL_FRONT_GENERIC;
     // stream `copy` waits for the producer's queued work and for the batches that still read the slots
     HIPCHK(c, hipEventRecord(c->ev_caller, cst));
     WaitOnce wait_copy(c->s_copy);
     HIPCHK(c, wait_copy(c->ev_caller));
     for (int i = 0; i < n; i++)
         if (int rc = wait_frame_free(c, wait_copy, first + i)) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_dtab, T, sizeof(DevFrameDesc) * n, hipMemcpyHostToDevice, c->s_copy));
+    HIPCHK(c, hipMemcpyAsync(c->d_dtab, T, sizeof(FrameDesc) * n, hipMemcpyHostToDevice, c->s_copy));
     {
         ProfScope ps(c, FFL_K_FRONTEND, c->s_copy);
         ffl_launch_frontend_dev(c->d_dtab, n, c->d_gray, c->N, p, c->s_copy);

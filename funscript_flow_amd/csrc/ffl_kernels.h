@@ -58,38 +58,20 @@ struct Pass1Result {  // written by k_pass1_final, mirrored to pinned host memor
     double mag_sum;   // sum of sqrt(u^2+v^2) over the image (mean = mag_sum / (w*h))
 };
 
+// The input front-end (k_frontend, k_frontend_dev): a decoded frame -> the gray crop window of its (virtual) resize.
 enum { FFL_FRONT_GENERIC = 0, FFL_FRONT_AREA2 = 1, FFL_FRONT_IDENTITY = 2 };
-struct FrontParams {  // k_frontend: decoded 3-channel frame -> gray crop window of its (virtual) resize
-    int sw, sh;              // source size
-    size_t stride;           // source row pitch in bytes (device copy)
-    int cx, cy, ow, oh;      // crop origin inside the resized image, output size
-    double scale_x, scale_y; // 1. / ((double)resize / src), formed on the host
-    int mode, rgb;
-};
-
-struct FrontYuvParams {   // k_frontend_yuv: 4:2:0 source window -> gray crop window of the frame's (virtual) resize
-    int sw, sh;              // full source size: source coordinates and their clamps stay in these terms
-    int wx, wy;              // origin of the transferred window inside the frame (even: chroma-aligned)
-    int y_pitch, c_pitch;    // row pitch of the window's Y plane / chroma plane(s) on the device, bytes
-    int c_step;              // bytes between horizontally adjacent chroma samples: 1 (I420), 2 (NV12, V = U + 1)
-    int cx, cy, ow, oh;      // crop origin inside the resized image, output size
-    double scale_x, scale_y; // 1. / ((double)resize / src), formed on the host
-    int mode;
-};
-
-// k_frontend_dev (ffl_upload_frames_device): frames read in place from caller device memory.  One descriptor per frame in
-// a device table (stream-ordered copy on stream `copy`); everything the frames of one call share is a kernel argument.
-enum { FFL_DEVK_GRAY = 0, FFL_DEVK_BGR = 1, FFL_DEVK_YUV = 2 };
-struct DevFrameDesc {
+enum { FFL_SRC_GRAY = 0, FFL_SRC_BGR = 1, FFL_SRC_YUV = 2, FFL_SRC_ANY = -1 };  // ANY: the kernels' own use
+struct FrameDesc {  // where one source frame's bytes lie on the device
     const uint8_t *p0, *p1, *p2;  // packed / first channel / Y; chroma: U and V (NV12: p2 = p1 + 1)
     long long pitch0, pitch1, pitch2;
     long long ps, cs;             // plane 0: bytes between horizontal neighbours / between the channels of a pixel
     int c_step;                   // 4:2:0: bytes between horizontally adjacent chroma samples (1 I420, 2 NV12)
-    int fslot;                    // destination frame slot
+    int wx, wy;                   // origin of the window the planes hold inside the frame (even; 0, 0: the whole frame)
+    int fslot;                    // k_frontend_dev: destination frame slot
 };
-struct DevFrontParams {
-    int kind, rgb;               // FFL_DEVK_*; rgb: channel 0 is R
-    int sw, sh;                  // source size
+struct FrontParams {  // what the frames of one launch share
+    int kind, rgb;               // FFL_SRC_*; rgb: channel 0 is R
+    int sw, sh;                  // full source size: source coordinates and their clamps stay in these terms
     int cx, cy, ow, oh;          // crop origin inside the resized image, output size
     double scale_x, scale_y;     // 1. / ((double)resize / src), formed on the host
     int mode;                    // FFL_FRONT_*
@@ -148,10 +130,9 @@ struct FflOptions {
 bool ffl_launch_pyr_multi(const uint8_t *gray_base, size_t gray_stride, const UTab *ut, int nU, int w, int h, const PyrJob *levels,
                           int n, const FflOptions &opt, hipStream_t st);
 void ffl_launch_polyexp_multi(const PolyJob *levels, int n, int nU, PolyConsts pc, hipStream_t st);
-void ffl_launch_frontend(const uint8_t *src, uint8_t *gray, FrontParams p, hipStream_t st);
-void ffl_launch_frontend_yuv(const uint8_t *y, const uint8_t *u, const uint8_t *v, uint8_t *gray, FrontYuvParams p,
-                             hipStream_t st);
-void ffl_launch_frontend_dev(const DevFrameDesc *tab, int n, uint8_t *gray_base, size_t N, DevFrontParams p, hipStream_t st);
+// host paths: one frame, its descriptor a kernel argument; device path: n frames, descriptors tab[0..n) in device memory
+void ffl_launch_frontend(const FrameDesc &d, uint8_t *gray, const FrontParams &p, hipStream_t st);
+void ffl_launch_frontend_dev(const FrameDesc *tab, int n, uint8_t *gray_base, size_t N, const FrontParams &p, hipStream_t st);
 // n (<= FFL_MAXB) flow slots of `flow` (2N floats each) -> dst + i * item_stride bytes; layout 0 (H, W, 2), 1 (2, H, W)
 void ffl_launch_export_flows(const float *flow, const ExportTab &tab, int n, size_t N, char *dst, long long item_stride,
                              int layout, hipStream_t st);

@@ -260,3 +260,77 @@ void ffl_launch_radial(const RadialTab *rt, int nB, int w, int h, int pov_mode, 
     hipLaunchKernelGGL(k_radial, dim3(nblk, nB), dim3(P1_THREADS), 0, st, rt, w, h, pov_mode, wytab, psum);
     hipLaunchKernelGGL(k_radial_final, dim3(nB), dim3(P1_THREADS), 0, st, w, h, nblk, psum, out);
 }
+
+// ---- flow export -----------------------------------------------------------------------------
+// k_export_flows gathers flow slots into caller memory: (H, W, 2) with 16-byte copies, or (2, H, W) de-interleaved with
+// 16-byte loads and stores on both sides.  Pure bandwidth.
+// grid = (blocks per item, items); a lane handles FFL_EXP_UNROLL units of one item, 256 units apart.  Units: NHWC vec one
+// float4 (2 pixels), NCHW vec 4 pixels (two float4 in, one float4 per plane out), scalar paths one pixel.
+#define FFL_EXP_UNROLL 4
+
+__global__ __launch_bounds__(256) void k_export_flows(const float *__restrict__ flow, ExportTab tab, size_t N,
+                                                      char *__restrict__ dst, long long item_stride, int layout, int vec) {
+    const float *src = flow + (size_t)tab.slot[blockIdx.y] * 2 * N;
+    char *out = dst + (long long)blockIdx.y * item_stride;
+    const size_t base = (size_t)blockIdx.x * (256 * FFL_EXP_UNROLL) + threadIdx.x;
+    if (layout == 0) {
+        if (vec) {  // 2N floats = N / 2 float4
+            const float4 *s4 = (const float4 *)src;
+            float4 *o4 = (float4 *)out;
+            const size_t units = N / 2;
+#pragma unroll
+            for (int k = 0; k < FFL_EXP_UNROLL; k++) {
+                const size_t u = base + (size_t)k * 256;
+                if (u < units) o4[u] = s4[u];
+            }
+        } else {
+            const float2 *s2 = (const float2 *)src;
+            float *o = (float *)out;
+#pragma unroll
+            for (int k = 0; k < FFL_EXP_UNROLL; k++) {
+                const size_t u = base + (size_t)k * 256;
+                if (u < N) {
+                    const float2 f = s2[u];
+                    o[2 * u] = f.x;
+                    o[2 * u + 1] = f.y;
+                }
+            }
+        }
+    } else {
+        float *ou = (float *)out, *ov = ou + N;
+        if (vec) {  // N % 4 == 0: 4 pixels = two float4 in, one float4 to each plane
+            const float4 *s4 = (const float4 *)src;
+            const size_t units = N / 4;
+#pragma unroll
+            for (int k = 0; k < FFL_EXP_UNROLL; k++) {
+                const size_t u = base + (size_t)k * 256;
+                if (u < units) {
+                    const float4 a = s4[2 * u], b = s4[2 * u + 1];
+                    ((float4 *)ou)[u] = make_float4(a.x, a.z, b.x, b.z);
+                    ((float4 *)ov)[u] = make_float4(a.y, a.w, b.y, b.w);
+                }
+            }
+        } else {
+            const float2 *s2 = (const float2 *)src;
+#pragma unroll
+            for (int k = 0; k < FFL_EXP_UNROLL; k++) {
+                const size_t u = base + (size_t)k * 256;
+                if (u < N) {
+                    const float2 f = s2[u];
+                    ou[u] = f.x;
+                    ov[u] = f.y;
+                }
+            }
+        }
+    }
+}
+
+void ffl_launch_export_flows(const float *flow, const ExportTab &tab, int n, size_t N, char *dst, long long item_stride,
+                             int layout, hipStream_t st) {
+    // 16-byte paths: every item base (and the v plane) 16-byte aligned; slot bases are (8N bytes apart) when N is even
+    const bool aligned = ((uintptr_t)dst | (unsigned long long)item_stride) % 16 == 0;
+    const int vec = aligned && (layout == 0 ? N % 2 == 0 : N % 4 == 0);
+    const size_t units = vec ? (layout == 0 ? N / 2 : N / 4) : N;
+    dim3 grid((unsigned)((units + 256 * FFL_EXP_UNROLL - 1) / (256 * FFL_EXP_UNROLL)), n);
+    hipLaunchKernelGGL(k_export_flows, grid, dim3(256), 0, st, flow, tab, N, dst, item_stride, layout, vec);
+}

@@ -10,7 +10,7 @@ One `ffl_upload_frames_raw` call does all of it (k_frontend): the frame is sent 
 crop window of the resized image is ever computed.  No CPU fallback: without the HIP library this raises.
 
 yuv="i420" | "nv12" takes a decoder's native 4:2:0 output instead -- (3h/2, w) uint8 arrays, as PyAV's yuv420p frames
-or an `ffmpeg -pix_fmt yuv420p|nv12` pipe deliver them -- through `ffl_upload_frames_yuv` (k_frontend_yuv): the
+or an `ffmpeg -pix_fmt yuv420p|nv12` pipe deliver them -- through `ffl_upload_frames_yuv` (k_frontend): the
 colour conversion runs on the device and only the source rectangle the crop window reads crosses PCIe (DESIGN.md
 section 11, appendix Y).
 

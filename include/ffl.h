@@ -390,8 +390,8 @@ int ffl_profile_enable(ffl_ctx *ctx, unsigned class_mask);
 #define FFL_K_GRAY 0
 #define FFL_K_PYRAMID 1
 #define FFL_K_POLYEXP 2
-#define FFL_K_FRONTEND 3 /* k_frontend of ffl_upload_frames_raw and k_frontend_yuv of ffl_upload_frames_yuv (the x2
-                            flow upsample, once class 3, runs inside k_update_matrices) */
+#define FFL_K_FRONTEND 3 /* k_frontend of ffl_upload_frames_raw and ffl_upload_frames_yuv, k_frontend_dev of
+                            ffl_upload_frames_device (the x2 flow upsample, once class 3, runs inside k_update_matrices) */
 #define FFL_K_UPDATE_MATRICES 4
 #define FFL_K_BLUR_SOLVE 5
 #define FFL_K_PASS1 6

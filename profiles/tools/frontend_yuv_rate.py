@@ -1,6 +1,6 @@
 """Rate of the 4:2:0 front-end (ffl_upload_frames_yuv) against the BGR one (ffl_upload_frames_raw):
 decoded frames/s with the H2D transfer included (host clock around a synchronised run of uploads), bytes each frame
-sends, and the mean launch time of k_frontend / k_frontend_yuv (HIP events), for BGR, I420 and NV12, staged (pageable
+sends, and the mean launch time of k_frontend (HIP events), for BGR, I420 and NV12, staged (pageable
 arrays) and zero-copy (frames in the context's page-locked memory), at 1080p -> 256², 4K -> 256² and 5760x2880 VR -> 256².
 
     python profiles/tools/frontend_yuv_rate.py [--reps 5] [--frames 16] [--out file.json] [--only-yuv]
@@ -38,7 +38,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only-yuv", action="store_true", help="skip the BGR rows (for a kernel trace of k_frontend_yuv)")
+    ap.add_argument("--only-yuv", action="store_true", help="skip the BGR rows (for a kernel trace of k_frontend on 4:2:0 frames)")
     a = ap.parse_args()
     out = []
     for sw, sh, vr in SOURCES:

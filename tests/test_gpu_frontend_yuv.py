@@ -1,4 +1,4 @@
-"""GPU parity of the 4:2:0 front-end (k_frontend_yuv behind ffl_upload_frames_yuv) against the numpy
+"""GPU parity of the 4:2:0 front-end (k_frontend behind ffl_upload_frames_yuv) against the numpy
 restatement of appendix Y composed with the oracle's resize and luma (tests/yuv_ref.py).  Integer work: bit-exact.  Both
 transfer paths (a staging copy out of pageable arrays; 2-D copies straight out of ffl_host_alloc memory) are covered."""
 import ctypes as C
