@@ -24,7 +24,8 @@ EXPORTS = ["ffl_device_count", "ffl_create", "ffl_destroy", "ffl_last_error", "f
            "ffl_dis_default_params", "ffl_dis_geometry", "ffl_flow_pairs_dis", "ffl_debug_dis_pair",
            "ffl_farneback_default_params", "ffl_farneback_geometry", "ffl_farneback_extra_bytes", "ffl_flow_pairs_farneback",
            "ffl_upload_frames_yuv", "ffl_frontend_yuv_window",
-           "ffl_dev_frame_check", "ffl_upload_frames_device", "ffl_export_flows"]
+           "ffl_dev_frame_check", "ffl_upload_frames_device", "ffl_export_flows",
+           "ffl_dev_flow_check", "ffl_import_flows"]
 
 # 4:2:0 layouts of ffl_upload_frames_yuv (FFL_YUV_I420, FFL_YUV_NV12): cv2's single-array (3h/2, w) uint8 frames
 YUV_LAYOUTS = {"i420": 0, "nv12": 1}
@@ -33,6 +34,8 @@ YUV_LAYOUTS = {"i420": 0, "nv12": 1}
 DEV_FORMATS = {"gray": 0, "bgr": 1, "rgb": 2, "i420": 3, "nv12": 4}
 FLOW_LAYOUTS = {"nhwc": 0, "nchw": 1}
 FFL_ERR_INVALID, FFL_ERR_STATE = 1, 4
+# flow import (ffl_import_flows): FFL_F32, FFL_F16, FFL_BF16 by __cuda_array_interface__ typestr
+FLOW_DTYPES = {"<f4": 0, "<f2": 1, "bfloat16": 2}
 
 FLOWS = ("farneback", "dis")   # params["hip_flow"]: the reference's CPU/CUDA/OpenCL branch, or its "DNN" branch (FF:948-980)
 DIS_STAGES = {"pass1": 0, "pass2": 1, "dense": 2, "refined": 3, "images": 4}   # ffl_debug_dis_pair stages
@@ -256,6 +259,58 @@ def dev_frame_check(fmt, frame, resize, crop, out_size):
         raise ValueError(L.ffl_last_error(None).decode())
 
 
+class DevFlow(C.Structure):
+    """ffl_dev_flow: n flow fields in device memory; item i, pixel (x, y), component c is at
+    base + i * item_stride + y * row_pitch + x * pixel_stride + c * channel_stride (bytes, include/ffl.h)."""
+    _fields_ = [("base", C.c_void_p), ("item_stride", C.c_ssize_t), ("row_pitch", C.c_ssize_t), ("pixel_stride", C.c_ssize_t),
+                ("channel_stride", C.c_ssize_t)]
+
+
+def _flow_view(obj):
+    """(data pointer, shape, byte strides, typestr) of a device flow array; torch tensors are read directly (the only way
+    to pass bfloat16, typestr "bfloat16"), anything else through __cuda_array_interface__."""
+    torch = sys.modules.get("torch")
+    if torch is not None and isinstance(obj, torch.Tensor):
+        if not obj.is_cuda:
+            raise ValueError("not device memory: a CPU tensor (host flow fields go through upload_flow)")
+        ts = {torch.float32: "<f4", torch.float16: "<f2", torch.bfloat16: "bfloat16"}.get(obj.dtype, str(obj.dtype))
+        es = obj.element_size()
+        return obj.data_ptr(), tuple(obj.shape), tuple(st * es for st in obj.stride()), ts
+    if getattr(obj, "__cuda_array_interface__", None) is None:
+        raise ValueError(f"not device memory: {type(obj).__name__} has no __cuda_array_interface__ (host flow fields go "
+                         "through upload_flow)")
+    return _array_view(obj)
+
+
+def device_flows(obj, width, height):
+    """(DevFlow, dtype code, n) of a device array of flow fields: a torch tensor (float32, float16 or bfloat16) or an
+    object with __cuda_array_interface__ ("<f4", "<f2"), shaped (n, H, W, 2), (n, 2, H, W) or a single (H, W, 2), any
+    non-negative strides.  ValueError names what is refused: host memory, another dtype, another size or shape."""
+    ptr, shape, st, ts = _flow_view(obj)
+    if ts not in FLOW_DTYPES:
+        raise ValueError(f"dtype {ts!r} is not supported: flow fields are float32, float16 or bfloat16 (float64 is not "
+                         "accepted; convert it first)")
+    W, H = int(width), int(height)
+    if len(shape) == 3 and shape[2] == 2:
+        if shape[:2] != (H, W):
+            raise ValueError(f"size: a field of {shape[1]}x{shape[0]} does not match the context's {W}x{H} (no resizing)")
+        return DevFlow(ptr, 0, st[0], st[1], st[2]), FLOW_DTYPES[ts], 1
+    if len(shape) == 4 and shape[3] == 2 and shape[1:3] == (H, W):
+        return DevFlow(ptr, st[0], st[1], st[2], st[3]), FLOW_DTYPES[ts], shape[0]
+    if len(shape) == 4 and shape[1] == 2 and shape[2:] == (H, W):
+        return DevFlow(ptr, st[0], st[2], st[3], st[1]), FLOW_DTYPES[ts], shape[0]
+    if len(shape) == 4 and 2 in (shape[1], shape[3]):
+        raise ValueError(f"size: fields of shape {shape} do not match the context's {W}x{H} (no resizing)")
+    raise ValueError(f"shape: flow fields are (n, H, W, 2), (n, 2, H, W) or (H, W, 2), got {shape}")
+
+
+def dev_flow_check(dtype, n, width, height, desc):
+    """ffl_dev_flow_check: ValueError with the library's rule when it refuses (pure host check)."""
+    L = load()
+    if L.ffl_dev_flow_check(int(dtype), int(n), int(width), int(height), C.byref(desc)) != FFL_OK:
+        raise ValueError(L.ffl_last_error(None).decode())
+
+
 def stream_handle(stream, device=0):
     """hipStream_t of `stream` as an int: None = torch's current stream on `device` when torch is already imported (else
     0, the null stream); a torch.cuda.Stream; or an int as it is."""
@@ -360,6 +415,8 @@ def load():
     L.ffl_dev_frame_check.argtypes = [C.c_int, C.c_int, C.c_int, vp] + [C.c_int] * 6
     L.ffl_upload_frames_device.argtypes = [vp, C.c_int, C.c_int, vp] + [C.c_int] * 7 + [C.c_uint64]
     L.ffl_export_flows.argtypes = [vp, C.c_int, ip, vp, C.c_int, C.c_ssize_t, C.c_uint64]
+    L.ffl_dev_flow_check.argtypes = [C.c_int] * 4 + [vp]
+    L.ffl_import_flows.argtypes = [vp, C.c_int, ip, vp, C.c_int, C.c_int, C.c_uint64]
     _lib = L
     return L
 
@@ -606,6 +663,24 @@ class Context:
             raise ValueError(f"export_flows: every item of the output must be contiguous, strides are {st}")
         self._chk(self.L.ffl_export_flows(self._h, n, ps, ptr, code, st[0], handle))
         return out
+
+    def import_flows(self, flows, flow_slots, pov_mode=False, stream=None):
+        """Caller flow fields in device memory -> flow_slots, with their pass-1 records (ffl_import_flows, DESIGN.md section
+        13): upload_flow for every field in one launch, without the host.  `flows`: see device_flows (one field per slot).
+        Each record equals upload_flow's for the float32 widening of the field.  The fields are read after the work queued
+        on `stream` (None: torch's current stream) and `stream` waits for the read: the caller may overwrite or free them in
+        its order on that stream.  Results are read with pass1_results; radial, export_flows and download_flow work on
+        the slots as on any other."""
+        desc, dt, n = device_flows(flows, self.width, self.height)
+        if len(flow_slots) != n:
+            raise ValueError(f"import_flows: {n} fields for {len(flow_slots)} flow slots")
+        self.import_flows_desc(desc, dt, flow_slots, pov_mode, stream)
+
+    def import_flows_desc(self, desc, dtype, flow_slots, pov_mode=False, stream=None):
+        """import_flows for a DevFlow descriptor and FLOW_DTYPES code as device_flows returns them (one field per slot)."""
+        ps, slots = _iarr(flow_slots)
+        self._chk(self.L.ffl_import_flows(self._h, len(slots), ps, C.byref(desc), int(dtype), int(bool(pov_mode)),
+                                          stream_handle(stream, self.device)))
 
     def flow_pairs(self, fslot0, fslot1, flow_slots, pov_mode=False):
         n = len(flow_slots)

@@ -279,6 +279,11 @@ struct ffl_ctx {
     // per up_ring entry (n_fslots descriptors each) and the device table k_frontend_dev reads (stream `copy`)
     hipEvent_t ev_caller = nullptr;
     FrameDesc *h_dtab = nullptr, *d_dtab = nullptr;
+    // ffl_import_flows, allocated on first use (stream `post`): the slot / record table k_import_pass1 fills for
+    // k_pass1_final, and pass-1 partials for max_batch fields
+    PairTab *d_itab = nullptr;
+    unsigned long long *d_ikey = nullptr;
+    double *d_isum = nullptr;
     // flow slots
     float *d_flow = nullptr;          // [n_slots][2N]
     // Result records live in pinned, device-mapped host memory: the reduction kernels store their
@@ -698,6 +703,7 @@ void ffl_destroy(ffl_ctx *c) {
     hipFree(c->d_flow);
     hipHostFree(c->h_res);
     hipFree(c->d_rpsum); hipFree(c->d_ppkey); hipHostFree(c->h_radial);
+    hipFree(c->d_itab); hipFree(c->d_ikey); hipFree(c->d_isum);
     hipFree(c->d_rtab); hipHostFree(c->h_rtab); hipFree(c->d_ptab); hipHostFree(c->h_ptab); hipFree(c->d_wytab);
     if (c->s_copy) hipStreamDestroy(c->s_copy);
     if (c->s_post) hipStreamDestroy(c->s_post);
@@ -2054,20 +2060,20 @@ static void dev_frame_extents(int fmt, int sw, int sh, const ffl_dev_frame *f, s
 }
 
 // [p, p + bytes) must be device memory of the context's device inside one allocation
-static int dev_mem_check(ffl_ctx *c, const char *fn, const char *what, const void *p, size_t bytes) {
+static const char *kHostFrames = "host frames go through ffl_upload_frames, ffl_upload_frames_raw or ffl_upload_frames_yuv";
+static int dev_mem_check(ffl_ctx *c, const char *fn, const char *what, const void *p, size_t bytes,
+                         const char *host_hint = kHostFrames) {
     hipPointerAttribute_t a;
     hipError_t e = hipPointerGetAttributes(&a, p);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        return set_err(c, FFL_ERR_INVALID, "%s: %s is not device memory (unknown to HIP); host frames go through "
-                                           "ffl_upload_frames, ffl_upload_frames_raw or ffl_upload_frames_yuv", fn, what);
+        return set_err(c, FFL_ERR_INVALID, "%s: %s is not device memory (unknown to HIP); %s", fn, what, host_hint);
     }
     if (a.type == hipMemoryTypeHost)
-        return set_err(c, FFL_ERR_INVALID, "%s: %s is page-locked host memory (ffl_host_alloc / hipHostMalloc); host frames go "
-                                           "through ffl_upload_frames, ffl_upload_frames_raw or ffl_upload_frames_yuv", fn, what);
+        return set_err(c, FFL_ERR_INVALID, "%s: %s is page-locked host memory (ffl_host_alloc / hipHostMalloc); %s", fn, what,
+                       host_hint);
     if (a.type != hipMemoryTypeDevice)
-        return set_err(c, FFL_ERR_INVALID, "%s: %s is not device memory (memory type %d); host frames go through "
-                                           "ffl_upload_frames, ffl_upload_frames_raw or ffl_upload_frames_yuv", fn, what, (int)a.type);
+        return set_err(c, FFL_ERR_INVALID, "%s: %s is not device memory (memory type %d); %s", fn, what, (int)a.type, host_hint);
     if (a.device != c->device)
         return set_err(c, FFL_ERR_INVALID, "%s: %s is memory of device %d, the context is on device %d", fn, what, a.device, c->device);
     hipDeviceptr_t base = nullptr;
@@ -2223,6 +2229,100 @@ int ffl_export_flows(ffl_ctx *c, int n, const int *slots, float *dst, int layout
     return FFL_OK;
 }
 
+// ---- flow import -------------------------------------------------------------------------------
+// Every geometry rule of a device flow descriptor (ffl.h, ffl_dev_flow_check).  *mode: the load path of k_import_pass1
+// (FFL_IMP_*); *bytes: the extent of all n items from f->base.
+static int dev_flow_check(ffl_ctx *c, const char *fn, int dtype, int n, int w, int h, const ffl_dev_flow *f, int *mode,
+                          size_t *bytes) {
+    if (!f) return set_err(c, FFL_ERR_INVALID, "%s: NULL descriptor", fn);
+    if (dtype != FFL_F32 && dtype != FFL_F16 && dtype != FFL_BF16)
+        return set_err(c, FFL_ERR_INVALID, "%s: unknown dtype %d (FFL_F32 0, FFL_F16 1, FFL_BF16 2)", fn, dtype);
+    if (n < 1) return set_err(c, FFL_ERR_INVALID, "%s: n = %d fields (>= 1)", fn, n);
+    if (w < 2 || h < 2 || w > 32768 || h > 32768) return set_err(c, FFL_ERR_INVALID, "%s: size %dx%d outside 2..32768", fn, w, h);
+    if (!f->base) return set_err(c, FFL_ERR_INVALID, "%s: NULL base", fn);
+    const ptrdiff_t e = dtype == FFL_F32 ? 4 : 2, big = (ptrdiff_t)1 << 40;
+    const ptrdiff_t it = f->item_stride, pitch = f->row_pitch, ps = f->pixel_stride, cs = f->channel_stride;
+    if (it < 0 || pitch < 0 || ps < 0 || cs < 0)
+        return set_err(c, FFL_ERR_INVALID, "%s: negative stride (item %td, row %td, pixel %td, channel %td)", fn, it, pitch, ps, cs);
+    if (it > big || pitch > big || ps > big || cs > big) return set_err(c, FFL_ERR_INVALID, "%s: stride beyond 2^40", fn);
+    if ((uintptr_t)f->base % e || it % e || pitch % e || ps % e || cs % e)
+        return set_err(c, FFL_ERR_INVALID, "%s: misaligned: base and strides (item %td, row %td, pixel %td, channel %td) must be "
+                                           "multiples of the element size %td", fn, it, pitch, ps, cs, e);
+    // one component: pixels of a row apart, rows one after the other (a transposed view is refused)
+    if (ps < e) return set_err(c, FFL_ERR_INVALID, "%s: overlap: pixel stride %td below the element size %td", fn, ps, e);
+    const ptrdiff_t row = (ptrdiff_t)(w - 1) * ps + e, plane = (ptrdiff_t)(h - 1) * pitch + row;
+    if (pitch < row) return set_err(c, FFL_ERR_INVALID, "%s: overlap: row pitch %td too small for %d pixels %td bytes apart", fn, pitch, w, ps);
+    // u and v: interleaved inside a pixel, planar (v plane after the u plane), or row-planar (v row after the u row)
+    const bool pixel = cs >= e && cs + e <= ps, planar = cs >= plane, rows = cs >= row && cs + row <= pitch;
+    if (!pixel && !planar && !rows)
+        return set_err(c, FFL_ERR_INVALID, "%s: overlap: channel stride %td makes u and v overlap (interleaved: %td <= channel "
+                                           "stride <= pixel stride - %td; planar: >= %td; row-planar: %td .. row pitch - %td)",
+                       fn, cs, e, e, plane, row, row);
+    *bytes = (size_t)(n - 1) * (size_t)it + (size_t)(plane + cs);
+    const bool al4 = (uintptr_t)f->base % 4 == 0 && pitch % 4 == 0 && it % 4 == 0;
+    *mode = (ps == 2 * e && cs == e && (e == 4 || al4)) ? FFL_IMP_NHWC : (e == 4 && ps == 4) ? FFL_IMP_NCHW : FFL_IMP_ANY;
+    return FFL_OK;
+}
+
+int ffl_dev_flow_check(int dtype, int n, int width, int height, const ffl_dev_flow *f) {
+    int mode;
+    size_t bytes;
+    return dev_flow_check(nullptr, "ffl_dev_flow_check", dtype, n, width, height, f, &mode, &bytes);
+}
+
+// Caller device fields -> flow slots + their pass-1 records through ONE k_import_pass1 launch on stream `post`, ordered
+// after the caller's queued work and the slots' last users, and before the caller's later work (the stream contract of
+// ffl.h).  Slot indices travel as a kernel argument; nothing waits on the host beyond post_ring's own settling.
+int ffl_import_flows(ffl_ctx *c, int n, const int *slots, const ffl_dev_flow *f, int dtype, int pov_mode, uint64_t stream) {
+    static const char *fn = "ffl_import_flows";
+    if (!c) return FFL_ERR_INVALID;
+    std::unique_lock<std::mutex> pl(c->post_mu);  // stream `post` and post_ring, as ffl_radial / ffl_export_flows
+    CtxLock lk(c->mu);
+    if (n < 1 || n > c->max_batch)
+        return set_err(c, FFL_ERR_INVALID, "%s: n = %d fields outside 1..%d (the context's max_batch)", fn, n, c->max_batch);
+    if (!slots) return set_err(c, FFL_ERR_INVALID, "%s: NULL flow_slots", fn);
+    std::vector<char> seen(c->n_slots, 0);
+    for (int i = 0; i < n; i++) {
+        if (slots[i] < 0 || slots[i] >= c->n_slots) return set_err(c, FFL_ERR_INVALID, "%s: flow slot %d out of range", fn, slots[i]);
+        if (seen[slots[i]]) return set_err(c, FFL_ERR_INVALID, "%s: flow slot %d repeated in one call", fn, slots[i]);
+        seen[slots[i]] = 1;
+    }
+    int mode;
+    size_t bytes;
+    if (int rc = dev_flow_check(c, fn, dtype, n, c->w, c->h, f, &mode, &bytes)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t cst = (hipStream_t)(uintptr_t)stream;
+    if (int rc = refuse_capturing(c, fn, cst)) return rc;
+    if (int rc = dev_mem_check(c, fn, "the flow fields", f->base, bytes, "host flow fields go through ffl_upload_flow")) return rc;
+    if (!c->ev_caller) HIPCHK(c, hipEventCreateWithFlags(&c->ev_caller, hipEventDisableTiming));
+    if (!c->d_itab) {
+        HIPCHK(c, hipMalloc(&c->d_itab, sizeof(PairTab)));
+        HIPCHK(c, hipMalloc(&c->d_ikey, sizeof(unsigned long long) * c->p1_blocks * c->max_batch));
+        HIPCHK(c, hipMalloc(&c->d_isum, sizeof(double) * c->p1_blocks * c->max_batch));
+    }
+    // stream `post` waits for the producer's queued work and for the last users of the slots (a batch, a pass 2, an export)
+    HIPCHK(c, hipEventRecord(c->ev_caller, cst));
+    WaitOnce wait_post(c->s_post);
+    HIPCHK(c, wait_post(c->ev_caller));
+    for (int i = 0; i < n; i++) HIPCHK(c, wait_post(c->ev_slot_done[slots[i]].get()));
+    const ImportArgs a{(const char *)f->base, (long long)f->item_stride, (long long)f->row_pitch, (long long)f->pixel_stride,
+                       (long long)f->channel_stride, c->d_flow, c->d_res};
+    ExportTab t;
+    for (int i = 0; i < n; i++) t.slot[i] = slots[i];
+    {
+        ProfScope ps(c, FFL_K_PASS1, c->s_post);
+        ffl_launch_import_pass1(a, t, n, dtype, mode, c->w, c->h, pov_mode ? 1 : 0, c->opt.import_fused, c->d_itab, c->d_ikey,
+                                c->d_isum, c->s_post);
+    }
+    HIPCHK(c, hipGetLastError());
+    EvRef done;
+    HIPCHK(c, c->post_ring.record(c->s_post, &done));
+    publish_slots(c, n, slots, done, true);
+    // the caller's later work (overwriting or freeing the sources) runs after the fields have been read
+    HIPCHK(c, hipStreamWaitEvent(cst, done.get(), 0));
+    return FFL_OK;
+}
+
 int ffl_upload_flow(ffl_ctx *c, int slot, const float *src, int pov_mode) {
     if (!c) return FFL_ERR_INVALID;
     std::unique_lock<std::mutex> pl(c->post_mu);
@@ -2324,6 +2424,11 @@ static int set_option_impl(FflOptions &o, const char *name, int value, bool live
         o.fb_general = value;
         return FFL_OK;
     }
+    if (!strcmp(name, "import_fused")) {  // ffl_import_flows: 1 (default) one fused launch, 0 conversion kernel + pass 1
+        if (value < 0 || value > 1) return FFL_ERR_INVALID;
+        o.import_fused = value;
+        return FFL_OK;
+    }
     if (!strcmp(name, "copy_threads")) {  // host threads sharing a staging copy of >= 1 MiB (1 = the caller alone)
         if (value < 1 || value > 16) return FFL_ERR_INVALID;
         o.copy_threads = value;
@@ -2352,7 +2457,7 @@ static int get_option_impl(const FflOptions &o, const char *name, int *value) {
         {"blur_tile_h", 16}, {"fuse_first", o.fuse_first}, {"merge_expand", o.merge_expand}, {"blur_rows", o.blur_rows},
         {"blur_min_wgs", o.blur_min_wgs}, {"tile_order", o.tile_order}, {"pyr_coarse", o.pyr_coarse},
         {"copy_threads", o.copy_threads}, {"graph", o.use_graph}, {"lanes", o.lanes}, {"run_ahead", o.run_ahead},
-        {"fb_general", o.fb_general}};
+        {"fb_general", o.fb_general}, {"import_fused", o.import_fused}};
     for (auto &t : tab)
         if (!strcmp(name, t.n)) {
             *value = t.v;

@@ -81,6 +81,18 @@ struct ExportTab {
     int slot[FFL_MAXB];
 };
 
+// ffl_import_flows (k_import_pass1): item b, pixel (x, y), component c lies at base + b*item + y*pitch + x*ps + c*cs
+enum { FFL_IMP_F32 = 0, FFL_IMP_F16 = 1, FFL_IMP_BF16 = 2 };   // = FFL_F32, FFL_F16, FFL_BF16 of include/ffl.h
+enum { FFL_IMP_ANY = 0,    // element by element
+       FFL_IMP_NHWC = 1,   // ps = 2 * element, cs = element; 16-bit: base and pitch also 4-byte aligned
+       FFL_IMP_NCHW = 2 }; // float32, ps = 4
+struct ImportArgs {
+    const char *base;
+    long long item, pitch, ps, cs;   // bytes
+    float *flow;                     // the context's flow slots (2N floats each)
+    Pass1Result *res;                // their records
+};
+
 // merged launches: one 1-D grid cut into per-job block ranges
 #define FFL_MAX_JOBS 4
 enum { FFL_PYR_F1 = 0, FFL_PYR_F2, FFL_PYR_H4, FFL_PYR_H9, FFL_PYR_V4, FFL_PYR_V9 };
@@ -123,6 +135,7 @@ struct FflOptions {
     int tile_order = 0;     // 0 pair-major, 1 tile-major (ffl_tile_coord)
     int pyr_coarse = 1;     // one-pass kernel for the x1/4 and x1/8 pyramid levels where sizes allow
     int fb_general = 0;     // 1: ffl_flow_pairs_farneback runs the reference's parameters through the general kernels too
+    int import_fused = 1;   // ffl_import_flows: 1 k_import_pass1 (conversion + pass 1 in one read), 0 conversion, then pass 1
 };
 
 // ---- launchers (each enqueues on `st` and returns; no synchronisation) ----------------------
@@ -136,6 +149,10 @@ void ffl_launch_frontend_dev(const FrameDesc *tab, int n, uint8_t *gray_base, si
 // n (<= FFL_MAXB) flow slots of `flow` (2N floats each) -> dst + i * item_stride bytes; layout 0 (H, W, 2), 1 (2, H, W)
 void ffl_launch_export_flows(const float *flow, const ExportTab &tab, int n, size_t N, char *dst, long long item_stride,
                              int layout, hipStream_t st);
+// n (<= FFL_MAXB) caller fields -> flow slots tab.slot[0..n) + their pass-1 records (through pt, which the import fills);
+// fused = 0: the two-launch form (conversion kernel, then ffl_launch_pass1); dtype FFL_IMP_*, mode FFL_IMP_* (host-checked)
+void ffl_launch_import_pass1(const ImportArgs &a, const ExportTab &tab, int n, int dtype, int mode, int w, int h, int pov_mode,
+                             int fused, PairTab *pt, unsigned long long *pkey, double *psum, hipStream_t st);
 void ffl_launch_gray(const uint8_t *bgr, uint8_t *gray, int n_pixels, hipStream_t st);
 size_t ffl_pyr_tmp_floats(int w, int h, int lw);  // per-frame size of the level's horizontal-pass buffer
 void ffl_launch_pyr_level(const uint8_t *gray_base, size_t gray_stride, const UTab *ut, int nU, int w, int h, int lw, int lh,

@@ -64,15 +64,25 @@ __device__ __forceinline__ double ffl_wave_sum_f64(double v) {
     return v;
 }
 
+// Where pass 1 reads its field.  load(yc, xa) is the 16-byte window of pixels (xa, xa + 1) of row yc as float4 (u, v, u,
+// v); store() hands over the pixels a lane owns (the importing loader writes them into their flow slot).
+struct P1SlotSrc {   // a flow slot: (h, w, 2) float32, one 16-byte load
+    const float2 *flow;
+    int w;
+    __device__ __forceinline__ float4 load(int yc, int xa) const {
+        return ffl_gload4(flow, 8u * ((unsigned)yc * (unsigned)w + (unsigned)xa));  // < 2^32: ffl_create
+    }
+    __device__ __forceinline__ void store(int, int, float2, float2, bool, bool) const {}
+};
+
 // key = (bits(|div|) << 32) | (0xFFFFFFFF - flat index): the maximum key is the largest |div| and,
 // among equals, the smallest row-major index -- np.argmax's first-occurrence rule, order independent.
-__global__ __launch_bounds__(P1_THREADS) void k_pass1(const PairTab *__restrict__ pt, int w, int h, int pov_mode,
-                                                      unsigned long long *__restrict__ pkey,
-                                                      double *__restrict__ psum) {
-    __shared__ unsigned long long skey[P1_THREADS / 64];
-    __shared__ double ssum[P1_THREADS / 64];
-    const int b = blockIdx.y;
-    const float2 *flow = reinterpret_cast<const float2 *>(pt->flow[0][b]);
+// The body of k_pass1 and k_import_pass1: one summation order whatever the source, so an imported field's record is
+// bit-identical to the record of the same float32 field in a slot.
+template <class Src>
+__device__ __forceinline__ void ffl_pass1_body(const Src &src, int w, int h, int pov_mode, int b,
+                                               unsigned long long *__restrict__ pkey, double *__restrict__ psum,
+                                               unsigned long long *skey, double *ssum) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int nstrips = (w + P1_STRIP - 1) / P1_STRIP, ngroups = (h + P1_RG - 1) / P1_RG;
     const int wid = blockIdx.x * (P1_THREADS / 64) + wv;  // wave-uniform
@@ -94,7 +104,7 @@ __global__ __launch_bounds__(P1_THREADS) void k_pass1(const PairTab *__restrict_
 #pragma unroll
             for (int r = 0; r < P1_G + 2; r++) {
                 const int yc = min(max(y0 + g - 1 + r, 0), h - 1);   // clamped: rows past the end repeat row h-1
-                raw[r] = ffl_gload4(flow, 8u * ((unsigned)yc * (unsigned)w + (unsigned)xa));  // < 2^32: ffl_create
+                raw[r] = src.load(yc, xa);
             }
 #pragma unroll
             for (int r = 0; r < P1_G; r++) {
@@ -104,6 +114,7 @@ __global__ __launch_bounds__(P1_THREADS) void k_pass1(const PairTab *__restrict_
                 const float2 c0 = first0 ? make_float2(tc.x, tc.y) : make_float2(tc.z, tc.w), c1 = first1 ? make_float2(tc.x, tc.y) : make_float2(tc.z, tc.w);
                 const float2 dn0 = first0 ? make_float2(td.x, td.y) : make_float2(td.z, td.w), dn1 = first1 ? make_float2(td.x, td.y) : make_float2(td.z, td.w);
                 const bool row_ok = y < h;
+                src.store(y, x, c0, c1, ok0 && row_ok, ok1 && row_ok);
                 sum += (ok0 && row_ok) ? (double)sqrtf(c0.x * c0.x + c0.y * c0.y) : 0.0;
                 sum += (ok1 && row_ok) ? (double)sqrtf(c1.x * c1.x + c1.y * c1.y) : 0.0;
                 if (!pov_mode) {
@@ -136,6 +147,16 @@ __global__ __launch_bounds__(P1_THREADS) void k_pass1(const PairTab *__restrict_
         pkey[(size_t)b * gridDim.x + blockIdx.x] = key;
         psum[(size_t)b * gridDim.x + blockIdx.x] = sum;
     }
+}
+
+__global__ __launch_bounds__(P1_THREADS) void k_pass1(const PairTab *__restrict__ pt, int w, int h, int pov_mode,
+                                                      unsigned long long *__restrict__ pkey,
+                                                      double *__restrict__ psum) {
+    __shared__ unsigned long long skey[P1_THREADS / 64];
+    __shared__ double ssum[P1_THREADS / 64];
+    const int b = blockIdx.y;
+    const P1SlotSrc src{reinterpret_cast<const float2 *>(pt->flow[0][b]), w};
+    ffl_pass1_body(src, w, h, pov_mode, b, pkey, psum, skey, ssum);
 }
 
 __global__ __launch_bounds__(P1_THREADS) void k_pass1_final(const PairTab *__restrict__ pt, int w, int h, int pov_mode,
@@ -333,4 +354,136 @@ void ffl_launch_export_flows(const float *flow, const ExportTab &tab, int n, siz
     const size_t units = vec ? (layout == 0 ? N / 2 : N / 4) : N;
     dim3 grid((unsigned)((units + 256 * FFL_EXP_UNROLL - 1) / (256 * FFL_EXP_UNROLL)), n);
     hipLaunchKernelGGL(k_export_flows, grid, dim3(256), 0, st, flow, tab, N, dst, item_stride, layout, vec);
+}
+
+// ---- flow import -----------------------------------------------------------------------------
+// k_import_pass1 reads n caller fields once: every pixel is widened to float32, stored into its flow slot by the lane that
+// owns it in pass 1's walk (halo loads never store), and fed to the pass-1 body in k_pass1's order, so the partials -- and
+// after k_pass1_final the records -- are bit-identical to ffl_upload_flow's for the float32 widening of the field.
+template <int DT>
+__device__ __forceinline__ float ffl_widen_bits(unsigned short bits) {  // exact: every f16 / bf16 value is a float32
+    if (DT == FFL_IMP_BF16) return __uint_as_float((unsigned)bits << 16);
+    return (float)__builtin_bit_cast(_Float16, bits);
+}
+
+template <int DT, int MODE>
+struct P1ImportSrc {
+    const char *item;          // the field's (0, 0, u)
+    long long pitch, ps, cs;   // bytes
+    float *slot;               // its flow slot
+    int w;
+    // the element at byte offset `off` of row `row`, widened
+    __device__ __forceinline__ float elem(const char *row, long long off) const {
+        if (DT == FFL_IMP_F32) return *(const FFL_GLOBAL float *)(row + off);
+        return ffl_widen_bits<DT>(*(const FFL_GLOBAL unsigned short *)(row + off));
+    }
+    __device__ __forceinline__ float4 load(int yc, int xa) const {
+        const char *row = item + (long long)yc * pitch;   // wave-uniform
+        if (MODE == FFL_IMP_NHWC && DT == FFL_IMP_F32) {  // (u, v, u, v): one 16-byte load
+            const ffl_v4f v = *(const FFL_GLOBAL ffl_v4f *)(row + (long long)xa * 8);
+            return make_float4(v.x, v.y, v.z, v.w);
+        } else if (MODE == FFL_IMP_NHWC) {                // 16-bit (u, v, u, v): one 8-byte load (4-byte aligned)
+            const ffl_v2f v = *(const FFL_GLOBAL ffl_v2f *)(row + (long long)xa * 4);
+            const unsigned a = __float_as_uint(v.x), b = __float_as_uint(v.y);
+            return make_float4(ffl_widen_bits<DT>(a & 0xFFFFu), ffl_widen_bits<DT>(a >> 16), ffl_widen_bits<DT>(b & 0xFFFFu),
+                               ffl_widen_bits<DT>(b >> 16));
+        } else if (MODE == FFL_IMP_NCHW && DT == FFL_IMP_F32) {  // (u, u) and (v, v): one 8-byte load per plane
+            const ffl_v2f u = *(const FFL_GLOBAL ffl_v2f *)(row + (long long)xa * 4);
+            const ffl_v2f v = *(const FFL_GLOBAL ffl_v2f *)(row + cs + (long long)xa * 4);
+            return make_float4(u.x, v.x, u.y, v.y);
+        } else {                                          // any strides: element by element
+            const long long o = (long long)xa * ps;
+            return make_float4(elem(row, o), elem(row, o + cs), elem(row, o + ps), elem(row, o + ps + cs));
+        }
+    }
+    __device__ __forceinline__ void store(int y, int x, float2 c0, float2 c1, bool s0, bool s1) const {
+        // signed: x = -1 (the halo pixel of strip 0) forms an address one pixel before the slot that only s1 offsets past
+        char *p = (char *)slot + 8 * ((long long)y * w + x);
+        if (s0 && s1) {
+            ffl_v4f v = {c0.x, c0.y, c1.x, c1.y};
+            *(FFL_GLOBAL ffl_v4f *)p = v;
+        } else if (s0) {
+            ffl_v2f v = {c0.x, c0.y};
+            *(FFL_GLOBAL ffl_v2f *)p = v;
+        } else if (s1) {
+            ffl_v2f v = {c1.x, c1.y};
+            *(FFL_GLOBAL ffl_v2f *)(p + 8) = v;
+        }
+    }
+};
+
+// workgroup (0, b) also names item b's slot and record in `pt` for k_pass1_final (read after this launch, same stream)
+__device__ __forceinline__ void ffl_import_publish(const ImportArgs &a, const ExportTab &tab, size_t N, PairTab *pt, int b) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        pt->flow[0][b] = a.flow + (size_t)tab.slot[b] * 2 * N;
+        pt->res[b] = a.res + tab.slot[b];
+    }
+}
+
+template <int DT, int MODE>
+__global__ __launch_bounds__(P1_THREADS) void k_import_pass1(const ImportArgs a, const ExportTab tab, int w, int h,
+                                                             int pov_mode, PairTab *__restrict__ pt,
+                                                             unsigned long long *__restrict__ pkey,
+                                                             double *__restrict__ psum) {
+    __shared__ unsigned long long skey[P1_THREADS / 64];
+    __shared__ double ssum[P1_THREADS / 64];
+    const int b = blockIdx.y;
+    const size_t N = (size_t)w * h;
+    ffl_import_publish(a, tab, N, pt, b);
+    const P1ImportSrc<DT, MODE> src{a.base + (long long)b * a.item, a.pitch, a.ps, a.cs, a.flow + (size_t)tab.slot[b] * 2 * N, w};
+    ffl_pass1_body(src, w, h, pov_mode, b, pkey, psum, skey, ssum);
+}
+
+// The two-launch form (ffl_ctx option import_fused = 0, the A/B of DESIGN.md section 13): a plain conversion into the
+// slots, then ffl_launch_pass1 over them.  A lane converts FFL_EXP_UNROLL pixels of one item, 256 pixels apart.
+template <int DT, int MODE>
+__global__ __launch_bounds__(256) void k_import_convert(const ImportArgs a, const ExportTab tab, int w, int h,
+                                                        PairTab *__restrict__ pt) {
+    const int b = blockIdx.y;
+    const size_t N = (size_t)w * h;
+    ffl_import_publish(a, tab, N, pt, b);
+    const P1ImportSrc<DT, MODE> src{a.base + (long long)b * a.item, a.pitch, a.ps, a.cs, nullptr, w};
+    float *slot = a.flow + (size_t)tab.slot[b] * 2 * N;
+    const unsigned base = blockIdx.x * (256 * FFL_EXP_UNROLL) + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < FFL_EXP_UNROLL; k++) {
+        const unsigned i = base + k * 256u;
+        if (i < N) {
+            const int y = i / (unsigned)w, x = i - y * w;
+            const char *row = src.item + (long long)y * a.pitch;
+            const long long o = (long long)x * a.ps;
+            ffl_v2f v = {src.elem(row, o), src.elem(row, o + a.cs)};
+            *(FFL_GLOBAL ffl_v2f *)((char *)slot + 8u * i) = v;
+        }
+    }
+}
+
+template <int DT, int MODE>
+static void ffl_import_launch(const ImportArgs &a, const ExportTab &tab, int n, int w, int h, int pov_mode, int fused,
+                              PairTab *pt, unsigned long long *pkey, double *psum, hipStream_t st) {
+    const int nblk = (ffl_strip_waves(w, h, P1_STRIP) + 3) / 4;
+    if (fused) {
+        hipLaunchKernelGGL((k_import_pass1<DT, MODE>), dim3(nblk, n), dim3(P1_THREADS), 0, st, a, tab, w, h, pov_mode, pt,
+                           pkey, psum);
+        hipLaunchKernelGGL(k_pass1_final, dim3(n), dim3(P1_THREADS), 0, st, pt, w, h, pov_mode, nblk, pkey, psum);
+    } else {
+        const size_t N = (size_t)w * h;
+        hipLaunchKernelGGL((k_import_convert<DT, MODE>), dim3((unsigned)((N + 256 * FFL_EXP_UNROLL - 1) / (256 * FFL_EXP_UNROLL)), n),
+                           dim3(256), 0, st, a, tab, w, h, pt);
+        ffl_launch_pass1(pt, n, w, h, pov_mode, pkey, psum, st);
+    }
+}
+
+void ffl_launch_import_pass1(const ImportArgs &a, const ExportTab &tab, int n, int dtype, int mode, int w, int h, int pov_mode,
+                             int fused, PairTab *pt, unsigned long long *pkey, double *psum, hipStream_t st) {
+#define FFL_IMP_CASE(DT, MODE)                                                                                   \
+    if (dtype == DT && mode == MODE) return ffl_import_launch<DT, MODE>(a, tab, n, w, h, pov_mode, fused, pt, pkey, psum, st);
+    FFL_IMP_CASE(FFL_IMP_F32, FFL_IMP_NHWC)
+    FFL_IMP_CASE(FFL_IMP_F32, FFL_IMP_NCHW)
+    FFL_IMP_CASE(FFL_IMP_F32, FFL_IMP_ANY)
+    FFL_IMP_CASE(FFL_IMP_F16, FFL_IMP_NHWC)
+    FFL_IMP_CASE(FFL_IMP_F16, FFL_IMP_ANY)
+    FFL_IMP_CASE(FFL_IMP_BF16, FFL_IMP_NHWC)
+    FFL_IMP_CASE(FFL_IMP_BF16, FFL_IMP_ANY)
+#undef FFL_IMP_CASE
 }

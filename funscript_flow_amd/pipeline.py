@@ -229,36 +229,121 @@ class PairEngine:
             if layout is None:
                 raise ValueError(f"flows_out must be ({n}, {ctx.height}, {ctx.width}, 2) or ({n}, 2, {ctx.height}, "
                                  f"{ctx.width}), got {shp}")
-        dots = np.zeros(n, np.float64)
-        psum = np.zeros((n + 1, 2), np.int64)  # prefix sums of pos_center: window means are exact integer
-        cuts = np.zeros(n, bool)               # sums / counts, bit-identical to np.mean over the window
-        state = {"known": 0, "done": 0}
-        recs_all = [None] * n
-
-        def finalize(limit):
-            while state["done"] < limit:
-                j0, j1 = state["done"], min(state["done"] + B, limit)
-                js = np.arange(j0, j1)
-                lo, hi = np.maximum(0, js - SMOOTH_RADIUS), np.minimum(n, js + SMOOTH_RADIUS + 1)
-                cs = (psum[hi] - psum[lo]) / (hi - lo)[:, None]
-                out = ctx.radial(list(js % ctx.flow_slots), cs, cuts[j0:j1], pov_mode)
-                dots[j0:j1] = out
-                state["done"] = j1
+        post = _ChunkPost(ctx, n, B, pov_mode)
 
         def on_batch(js, got):
-            j0 = js[0]
-            if layout is not None:   # before finalize: pass 2 below lets later batches recycle these slots
-                ctx.export_flows([j % ctx.flow_slots for j in js], flows_out[j0:js[-1] + 1], layout)
-            recs_all[j0:js[-1] + 1] = got
-            p = np.array([(r[0], r[1]) for r in got], np.int64)
-            psum[j0 + 1:js[-1] + 2] = psum[j0] + np.cumsum(p, axis=0)
-            cuts[j0:js[-1] + 1] = [r[4] for r in got]
-            state["known"] = js[-1] + 1
-            finalize(n if state["known"] == n else max(0, state["known"] - SMOOTH_RADIUS))
+            if layout is not None:   # before pass 2 below lets later batches recycle these slots
+                ctx.export_flows([j % ctx.flow_slots for j in js], flows_out[js[0]:js[-1] + 1], layout)
+            post.add(js, got)
 
         self.pass1(frames, 0, n, pov_mode, cut_threshold, on_batch, algo=algo, farneback=farneback)
-        finalize(n)
-        return dots, recs_all
+        return post.finish()
+
+    def process_flows(self, flows, pov_mode=False, cut_threshold=7.0):
+        """One whole chunk from flow fields the caller computed: returns (dots float64[n], records), the contract of
+        process_chunk.  `flows` holds the chunk's n pair fields in device memory: one array (n, H, W, 2) or (n, 2, H, W)
+        (float32, float16 or bfloat16, any strides; see _capi.device_flows) or a sequence of such arrays (single (H, W, 2)
+        fields included), in pair order.  They are imported B at a time into the slot ring (Context.import_flows, on
+        torch's current stream) with `depth` batches in flight; the +-6 window and pass 2 are process_chunk's own."""
+        ctx, B, fs = self.ctx, self.B, self.ctx.flow_slots
+        segs = []   # (descriptor, dtype, first pair, count): one per source array
+        n = 0
+        for a in (flows if isinstance(flows, (list, tuple)) else [flows]):
+            desc, dt, k = _capi.device_flows(a, ctx.width, ctx.height)
+            segs.append((desc, dt, n, k))
+            n += k
+        if n < 1:
+            return np.zeros(0), []
+        post = _ChunkPost(ctx, n, B, pov_mode)
+
+        def enqueue(j0):
+            j1 = min(j0 + B, n)
+            for desc, dt, first, k in segs:
+                lo, hi = max(j0, first), min(j1, first + k)
+                if lo >= hi:
+                    continue
+                part = _capi.DevFlow(desc.base + (lo - first) * desc.item_stride, desc.item_stride, desc.row_pitch,
+                                     desc.pixel_stride, desc.channel_stride)
+                ctx.import_flows_desc(part, dt, [j % fs for j in range(lo, hi)], pov_mode)
+            return list(range(j0, j1))
+
+        def collect(js):
+            post.add(js, ctx.pass1_results([j % fs for j in js], cut_threshold))
+
+        pending = []
+        for j0 in range(0, n, B):
+            pending.append(enqueue(j0))
+            if len(pending) > self.depth:
+                collect(pending.pop(0))
+        while pending:
+            collect(pending.pop(0))
+        return post.finish()
+
+
+class _ChunkPost:
+    """The +-6 centre window and pass 2 of one chunk of n pairs (FF:1203-1236), shared by process_chunk and process_flows:
+    add() takes a finished batch's pass-1 records in pair order and issues pass 2, B pairs per call, for every pair whose
+    window is complete; finish() issues the rest and returns (dots, records).  Window means are exact integer prefix
+    sums / counts, bit-identical to np.mean over the window."""
+
+    def __init__(self, ctx, n, B, pov_mode):
+        self.ctx, self.n, self.B, self.pov_mode = ctx, n, B, pov_mode
+        self.dots = np.zeros(n, np.float64)
+        self.psum = np.zeros((n + 1, 2), np.int64)   # prefix sums of pos_center
+        self.cuts = np.zeros(n, bool)
+        self.recs = [None] * n
+        self.done = 0
+
+    def _finalize(self, limit):
+        ctx, n, B = self.ctx, self.n, self.B
+        while self.done < limit:
+            j0, j1 = self.done, min(self.done + B, limit)
+            js = np.arange(j0, j1)
+            lo, hi = np.maximum(0, js - SMOOTH_RADIUS), np.minimum(n, js + SMOOTH_RADIUS + 1)
+            cs = (self.psum[hi] - self.psum[lo]) / (hi - lo)[:, None]
+            self.dots[j0:j1] = ctx.radial(list(js % ctx.flow_slots), cs, self.cuts[j0:j1], self.pov_mode)
+            self.done = j1
+
+    def add(self, js, got):
+        j0, j1 = js[0], js[-1] + 1
+        self.recs[j0:j1] = got
+        p = np.array([(r[0], r[1]) for r in got], np.int64)
+        self.psum[j0 + 1:j1 + 1] = self.psum[j0] + np.cumsum(p, axis=0)
+        self.cuts[j0:j1] = [r[4] for r in got]
+        self._finalize(self.n if j1 == self.n else max(0, j1 - SMOOTH_RADIUS))
+
+    def finish(self):
+        self._finalize(self.n)
+        return self.dots, self.recs
+
+
+def pair_plan(fps, total_frames, params):
+    """The sampled frame indices of every chunk frames_to_actions processes for a video of total_frames frames
+    (FF:1127-1153; pairs never span chunks): chunk k's pairs are (plan[k][i], plan[k][i + 1]).  A caller with its own flow
+    estimator computes those pairs' fields and hands them to flows_to_actions."""
+    from . import postchain
+    _, _, indices = postchain.sampling(fps, total_frames)
+    bracket = int(params.get("batch_size", 3000.0))
+    return [indices[cs:cs + bracket] for cs in range(0, len(indices), bracket) if len(indices[cs:cs + bracket]) >= 2]
+
+
+def flows_to_actions(engine, chunk_flows, fps, total_frames, params):
+    """.funscript actions from flow fields the caller computed: chunk_flows[k] holds the len(plan[k]) - 1 pair fields of
+    chunk k of pair_plan(fps, total_frames, params) in device memory (see PairEngine.process_flows).  Everything after
+    the flow -- pass 1, the +-6 window, pass 2, the post-chain -- is frames_to_actions' own."""
+    from . import postchain
+    plan = pair_plan(fps, total_frames, params)
+    if len(chunk_flows) != len(plan):
+        raise ValueError(f"flows_to_actions: {len(chunk_flows)} chunks of flows for a plan of {len(plan)} chunks")
+    dots, cuts, frame_idx = [], [], []
+    for chunk, flows in zip(plan, chunk_flows):
+        d, recs = engine.process_flows(flows, bool(params.get("pov_mode", False)), float(params.get("cut_threshold", 7)))
+        if len(d) != len(chunk) - 1:
+            raise ValueError(f"flows_to_actions: a chunk of {len(chunk)} frames needs {len(chunk) - 1} fields, got {len(d)}")
+        dots += [float(v) for v in d]
+        cuts += [bool(r[4]) for r in recs]
+        frame_idx += chunk[:-1]
+    return postchain.actions_from_scalars(dots, cuts, frame_idx, fps, params)
 
 
 def frames_to_actions(engine, frames, fps, params):
@@ -271,13 +356,8 @@ def frames_to_actions(engine, frames, fps, params):
     algo = _capi.flow_choice(params) if ("hip_flow" in params or "hip_dis" in params) else None
     # params["hip_farneback"] likewise sets the Farneback parameters of this call
     fbk = farneback_kwargs(params, frames[0].shape[1], frames[0].shape[0]) if len(frames) else {}
-    step, _, indices = postchain.sampling(fps, len(frames))
-    bracket = int(params.get("batch_size", 3000.0))
     dots, cuts, frame_idx = [], [], []
-    for cs in range(0, len(indices), bracket):
-        chunk = indices[cs:cs + bracket]
-        if len(chunk) < 2:
-            continue
+    for chunk in pair_plan(fps, len(frames), params):
         d, recs = engine.process_chunk([frames[i] for i in chunk], bool(params.get("pov_mode", False)),
                                        float(params.get("cut_threshold", 7)), **({"algo": algo} if algo is not None else {}),
                                        **fbk)

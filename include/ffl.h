@@ -27,6 +27,8 @@
  *   ffl_download_flow       the "flow" entry of that dict (tests / callers that want the array)
  *   ffl_upload_frames_device  ffl_upload_frames_raw / _yuv / ffl_upload_frames for frames already in device memory (a GPU
  *                           decoder's surfaces, torch tensors); ffl_export_flows: ffl_download_flow into device memory
+ *   ffl_import_flows        ffl_upload_flow for n fields already in device memory (float32, float16 or bfloat16, any
+ *                           strides): the reductions of FF:884-894 on a flow the caller computed
  *   ffl_submit_pair         precompute_wrapper((p0, p1), params)                    FF:1019-1021
  *   ffl_flow_pairs_farneback  cv2.calcOpticalFlowFarneback(p0, p1, None, pyr_scale, levels, winsize, iterations, poly_n,
  *                           poly_sigma, 0) with the caller's values + the same reductions
@@ -212,6 +214,44 @@ int ffl_upload_frames_device(ffl_ctx *ctx, int first_slot, int n, const ffl_dev_
  * that.  The export counts as a use of the slots: a later batch that recycles one of them waits for it on the device.
  * The host never waits. */
 int ffl_export_flows(ffl_ctx *ctx, int n, const int *flow_slots, float *dst, int layout, ptrdiff_t item_stride_bytes,
+                     uint64_t stream);
+
+/* n flow fields in device memory, as the caller's flow estimator left them: item i, pixel (x, y), component c (0 = u,
+ * 1 = v) is at  base + i*item_stride + y*row_pitch + x*pixel_stride + c*channel_stride  (bytes).  This covers (n, H, W, 2)
+ * (cv2's layout), (n, 2, H, W), sliced views with a padded row pitch and channels-last views. */
+typedef struct ffl_dev_flow {
+    const void *base;
+    ptrdiff_t item_stride, row_pitch, pixel_stride, channel_stride;
+} ffl_dev_flow;
+#define FFL_F32 0
+#define FFL_F16 1  /* IEEE half */
+#define FFL_BF16 2
+
+/* The geometry rules of ffl_import_flows for n width x height fields.  Pure host check: no device or context needed.
+ * FFL_ERR_INVALID with the rule in ffl_last_error(NULL): an unknown dtype; n < 1; a size outside 2..32768; a NULL base;
+ * negative strides or strides beyond 2^40; misaligned: a base or stride that is not a multiple of the element size;
+ * overlap: pixel stride < element size, row pitch < (width - 1) * pixel stride + element size (transposed views are
+ * refused), or a channel stride that makes u and v overlap -- it must be interleaved (element size <= channel stride <=
+ * pixel stride - element size), planar (>= the extent of one component plane) or row-planar (the v row after the u row,
+ * inside the row pitch).  Items may be any non-negative distance apart. */
+int ffl_dev_flow_check(int dtype, int n, int width, int height, const ffl_dev_flow *f);
+
+/* n caller fields (dtype FFL_F32 / FFL_F16 / FFL_BF16, the context's size) -> flow slots flow_slots[0..n), as float32, and
+ * their pass-1 records: ffl_upload_flow for every field at once, without the host.  Each record is bit-identical to
+ * ffl_upload_flow's for the float32 widening of the field (the widening is exact); results, radial, export and download
+ * then work on the slots as on any other.  pov_mode as in ffl_flow_pairs.  Refused before any device work, each with its
+ * rule in ffl_last_error: n outside 1..max_batch; a slot out of range or repeated; any rule of ffl_dev_flow_check; memory
+ * that is not device memory of the context's device, or an extent outside one allocation (page-locked host memory,
+ * ffl_host_alloc's included, belongs to ffl_upload_flow); a capturing `stream` (FFL_ERR_STATE).
+ * Stream contract (`stream` is a hipStream_t as an integer; 0 = the null stream):
+ *   - a stream that is capturing a graph is refused with FFL_ERR_STATE; that check is the first HIP call made on it;
+ *   - the fields are read after the work queued on `stream` before the call and after the slots' last users (a batch, a
+ *     pass 2 or an export that still reads them), by ONE k_import_pass1 launch for all n fields;
+ *   - the slots are published as ffl_upload_flow publishes its slot;
+ *   - `stream` is made to wait for the launch: the caller may overwrite or free the sources straight after the call;
+ *   - the host never waits for the device, except where settling the library's event ring makes every call wait.
+ * Nothing of this call is ever captured into the library's graphs. */
+int ffl_import_flows(ffl_ctx *ctx, int n, const int *flow_slots, const ffl_dev_flow *f, int dtype, int pov_mode,
                      uint64_t stream);
 
 /* Page-locked host memory owned by the context (freed by ffl_host_free or ffl_destroy).  A decoder that writes its
