@@ -77,6 +77,11 @@ struct P1SlotSrc {   // a flow slot: (h, w, 2) float32, one 16-byte load
 
 // key = (bits(|div|) << 32) | (0xFFFFFFFF - flat index): the maximum key is the largest |div| and,
 // among equals, the smallest row-major index -- np.argmax's first-occurrence rule, order independent.
+// np.argmax ranks every NaN above every number and takes the first one, whatever its payload: a NaN |div| enters the
+// key as one bit pattern (above +inf), so among NaNs the index decides as it does among equal numbers.
+__device__ __forceinline__ unsigned ffl_key_bits(float absdiv) {
+    return absdiv != absdiv ? 0x7FC00000u : __float_as_uint(absdiv);
+}
 // The body of k_pass1 and k_import_pass1: one summation order whatever the source, so an imported field's record is
 // bit-identical to the record of the same float32 field in a slot.
 template <class Src>
@@ -124,11 +129,11 @@ __device__ __forceinline__ void ffl_pass1_body(const Src &src, int w, int h, int
                     const float d1 = fabsf(ffl_grad(up1.x, dn1.x, y, h) + ffl_grad(c0.y, right1, x + 1, w));
                     const unsigned i0 = (unsigned)y * (unsigned)w + (unsigned)x;
                     if (ok0 && row_ok) {
-                        const unsigned long long k = ((unsigned long long)__float_as_uint(d0) << 32) | (unsigned long long)(0xFFFFFFFFu - i0);
+                        const unsigned long long k = ((unsigned long long)ffl_key_bits(d0) << 32) | (unsigned long long)(0xFFFFFFFFu - i0);
                         key = k > key ? k : key;
                     }
                     if (ok1 && row_ok) {
-                        const unsigned long long k = ((unsigned long long)__float_as_uint(d1) << 32) | (unsigned long long)(0xFFFFFFFFu - (i0 + 1u));
+                        const unsigned long long k = ((unsigned long long)ffl_key_bits(d1) << 32) | (unsigned long long)(0xFFFFFFFFu - (i0 + 1u));
                         key = k > key ? k : key;
                     }
                 }

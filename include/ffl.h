@@ -269,7 +269,11 @@ int ffl_host_free(ffl_ctx *ctx, void *ptr);
 int ffl_flow_pairs(ffl_ctx *ctx, int n, const int *fslot0, const int *fslot1, const int *flow_slots, int pov_mode);
 
 /* Wait for the batch that produced `flow_slot` and return its pass-1 record (FF:898-907):
- * (x, y) = pos_center, div_val = val_pos, mean_mag, cut = mean_mag > cut_threshold. */
+ * (x, y) = pos_center, div_val = val_pos, mean_mag, cut = mean_mag > cut_threshold.
+ * Non-finite fields follow np.argmax(np.abs(div)) (FF:756): (x, y) is the FIRST pixel in row-major order whose divergence
+ * is NaN, whatever the NaN's payload or origin (an input NaN, inf - inf formed on the device); without a NaN it is the first
+ * maximum of |div|, +inf included.  div_val is then NaN / +-inf.  A field with a NaN has mean_mag = NaN and cut = 0 (NaN >
+ * threshold is false); ffl_radial of it is NaN, or 0.0 when called with is_cut. */
 int ffl_pass1_result(ffl_ctx *ctx, int flow_slot, float cut_threshold, int32_t *x, int32_t *y, float *div_val,
                      float *mean_mag, int *cut);
 

@@ -20,6 +20,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 import oracle as orc
+import post_ref as pr
 import golden_check
 from funscript_flow_amd import _capi, pipeline
 from funscript_flow_amd.synth import sine_translate_frames
@@ -52,6 +53,7 @@ def _check_reductions_on_own_flow(ctx, j, rec, flow):
     assert (rec[0], rec[1]) == (ox, oy) and np.float32(rec[2]).tobytes() == np.float32(ov).tobytes(), j
     rm = float(orc.mean_mag_np(flow))
     assert abs(float(rec[3]) - rm) <= 1e-4 * rm, j
+    pr.check_mean_mag(rec[3], flow)
 
 
 @pytest.mark.parametrize("lanes", [1, 2])
@@ -157,6 +159,7 @@ def test_config4_stereo_5760x2880_split_per_eye():
             got = ctx.radial([j], [c], [False], False)[0]
             want = float(orc.radial_np(f, c, False, False))
             assert abs(got - want) <= 1e-4 * max(abs(want), 1e-6 * EW)
+            pr.check_radial(got, f, c, False)
         assert not np.array_equal(left, right)
         # the same eye through a contiguous copy gives the same bits (the stride path changes nothing)
         ctx.upload_frame(0, np.ascontiguousarray(full[0][:, EW:]))
@@ -401,6 +404,7 @@ def test_largest_baseline_frame_5760x2880_whole():
     _check_reductions_on_own_flow(None, 0, rec, flow)
     want = float(orc.radial_np(flow, c, False, False))
     assert abs(got - want) <= 1e-4 * max(abs(want), 1e-6 * W)
+    pr.check_radial(got, flow, c, False)
 
 
 def test_bench_prints_exactly_one_json_line():
@@ -681,6 +685,8 @@ def test_long_chunk_outlives_the_event_rings():
         assert (want_recs[j][0], want_recs[j][1]) == orc.max_divergence_np(flow)[:2], j
         ref = float(orc.radial_np(flow, centers[j], want_recs[j][4], False))
         assert abs(want_dots[j] - ref) <= 1e-4 * max(abs(ref), 1e-3), j
+        if not want_recs[j][4]:
+            pr.check_radial(float(want_dots[j]), flow, centers[j], False)
 
 
 def test_staged_upload_of_many_frames_with_a_row_stride_is_shared_by_the_copy_threads():

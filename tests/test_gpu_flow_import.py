@@ -12,6 +12,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 import oracle as orc
+import post_ref as pr
 from funscript_flow_amd import _capi, pipeline
 from funscript_flow_amd.synth import sine_translate_frames
 
@@ -55,11 +56,14 @@ def test_goldens(post, name, layout):
         assert np.float32(v).tobytes() == np.float32(post[f"{name}.maxdiv_val"]).tobytes()
         ref_mm = float(orc.mean_mag_np(flow))
         assert abs(float(mm) - ref_mm) <= 1e-4 * max(ref_mm, 1e-30)
+        pr.check_mean_mag(mm, flow)
         assert np.array_equal(bits(ctx.download_flow(1)), bits(flow))
         scale = float(np.mean(np.abs(flow))) * max(h, w)
         for c, (gw, gp, gc) in zip(post[f"{name}.centers"], post[f"{name}.radial"]):
             assert abs(ctx.radial([1], [c], [False], False)[0] - gw) <= 1e-4 * max(abs(gw), 1e-6 * scale)
             assert abs(ctx.radial([1], [c], [False], True)[0] - gp) <= 1e-4 * max(abs(gp), 1e-6 * scale)
+            for pov in (False, True):
+                pr.check_radial(ctx.radial([1], [c], [False], pov)[0], flow, c, pov)
             assert ctx.radial([1], [c], [True], False)[0] == gc == 0.0
         # pov_mode as in upload_flow; the two-launch form gives the same records
         ctx.import_flows(t, [2], pov_mode=True)

@@ -11,6 +11,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 import oracle as orc
+import post_ref as pr
 from funscript_flow_amd import _capi
 from funscript_flow_amd.synth import gray_to_bgr, sine_translate_frames
 
@@ -58,6 +59,7 @@ def test_pair_end_to_end(w, h, seed):
             assert (x, y) == (ox, oy)
             assert np.float32(v).tobytes() == np.float32(ov).tobytes()
             assert abs(float(mm) - float(orc.mean_mag_np(ref))) <= 1e-4 * float(orc.mean_mag_np(ref))
+            pr.check_mean_mag(mm, ref)
             assert cut == bool(orc.mean_mag_np(ref) > 7)
             c = (w / 2.0 + 0.3, h / 2.0 - 0.7)
             for pov in (False, True):
@@ -65,6 +67,7 @@ def test_pair_end_to_end(w, h, seed):
                 want = float(orc.radial_np(ref, c, False, pov))
                 scale = max(abs(want), float(np.mean(np.abs(ref))) * max(w, h) * 1e-2)
                 assert abs(got - want) <= 1e-4 * scale
+                pr.check_radial(got, ref, c, pov)
             assert ctx.radial([j], [c], [True], False)[0] == 0.0
 
 
@@ -125,10 +128,13 @@ def test_post_path_matches_reference_goldens(post, name):
         assert np.float32(v).tobytes() == np.float32(post[f"{name}.maxdiv_val"]).tobytes()
         ref_mm = float(orc.mean_mag_np(flow))
         assert abs(float(mm) - ref_mm) <= 1e-4 * max(ref_mm, 1e-30)
+        pr.check_mean_mag(mm, flow)
         scale = float(np.mean(np.abs(flow))) * max(h, w)
         for c, (gw, gp, gc) in zip(post[f"{name}.centers"], post[f"{name}.radial"]):
             assert abs(ctx.radial([0], [c], [False], False)[0] - gw) <= 1e-4 * max(abs(gw), 1e-6 * scale)
             assert abs(ctx.radial([0], [c], [False], True)[0] - gp) <= 1e-4 * max(abs(gp), 1e-6 * scale)
+            for pov in (False, True):
+                pr.check_radial(ctx.radial([0], [c], [False], pov)[0], flow, c, pov)
             assert ctx.radial([0], [c], [True], False)[0] == gc == 0.0
         # POV pass 1: centre of the bottom edge, value 0 (FF:880-882)
         ctx.upload_flow(1, flow, pov_mode=True)
@@ -206,10 +212,12 @@ def test_small_and_awkward_sizes_bit_exact(w, h):
             assert (x, y) == (ox, oy) and np.float32(v).tobytes() == np.float32(ov).tobytes()
             rm = float(orc.mean_mag_np(ref))
             assert abs(float(mm) - rm) <= 1e-4 * max(rm, 1e-30)
+            pr.check_mean_mag(mm, ref)
             c = (0.37 * w, 0.61 * h)
             got = ctx.radial([j], [c], [False], False)[0]
             want = float(orc.radial_np(ref, c, False, False))
             assert abs(got - want) <= 1e-4 * max(abs(want), float(np.mean(np.abs(ref))) * max(w, h) * 1e-2)
+            pr.check_radial(got, ref, c, False)
 
 
 @pytest.mark.parametrize("w,h", [(320, 180), (250, 131), (96, 80), (17, 19), (640, 360), (1920, 1080)])
