@@ -143,8 +143,9 @@ def dis_geometry(width, height, params=None):
     c, f = C.c_int(), C.c_int()
     p = params if params is not None else DisParams()
     if load().ffl_dis_geometry(int(width), int(height), C.byref(p), C.byref(c), C.byref(f)) != FFL_OK:
+        msg = load().ffl_last_error(None)
         raise ValueError(f"DIS does not support {width}x{height} with {p.as_dict()} (DESIGN.md appendix D2: patch_size 8, "
-                         "sides divisible by 2^coarsest)")
+                         f"sides divisible by 2^coarsest): {msg.decode() if msg else 'refused'}")
     return c.value, f.value
 
 

@@ -1562,7 +1562,8 @@ int ffl_dis_geometry(int width, int height, const ffl_dis_params *p, int *coarse
     ffl_dis_params d;
     ffl_dis_default_params(&d);
     int cs = 0;
-    if (dis_geometry(width, height, p ? *p : d, &cs)) return FFL_ERR_INVALID;
+    if (const char *why = dis_geometry(width, height, p ? *p : d, &cs))
+        return set_err(nullptr, FFL_ERR_INVALID, "ffl_dis_geometry: DIS at %dx%d: %s", width, height, why);
     if (coarsest) *coarsest = cs;
     if (finest) *finest = (p ? *p : d).finest_scale;
     return FFL_OK;

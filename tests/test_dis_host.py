@@ -43,13 +43,33 @@ def test_identical_and_constant_frames_give_zero(vr):
     assert not dis_ref.flow(c, c.copy(), p).any()
 
 
+# Stated for the restatement alone at patch_stride 8 and finest_scale 3, where the band above does not hold for it (measured
+# on the CPU, no kernel involved; median px / share within 0.5 px, worst of both shifts and of 256x256, 320x192, 768x256):
+#   patch_stride 8   0.26 / 0.79   patches no longer overlap (stride = patch size), so densification averages one patch per
+#                                  pixel instead of four: a patch that settles a fraction of a pixel off is not outvoted
+#   finest_scale 3   0.32 / 0.88   the quantisation argument above at 1/8 size: a 0.5 px shift is 1/16 px of an integer-
+#                                  rounded 8x8 block mean, and the x8 upsample carries twice the residual of the x4 one
+# The band there is twice the median bound plus the same 0.05 px of slack the first one got, and three quarters within 0.5 px.
+LOOSE = (2 * 0.15 + 0.05, 0.75)
+TRANSLATION_CASES = [   # (width, height, overrides, (median bound, share within 0.5 px))
+    (256, 256, {}, (MEDIAN_TOL, FRACTION)),
+    (320, 192, {}, (MEDIAN_TOL, FRACTION)), (192, 320, {}, (MEDIAN_TOL, FRACTION)), (768, 256, {}, (MEDIAN_TOL, FRACTION)),
+    (256, 256, {"patch_stride": 2}, (MEDIAN_TOL, FRACTION)), (320, 192, {"patch_stride": 2}, (MEDIAN_TOL, FRACTION)),
+    (256, 256, {"patch_stride": 8}, LOOSE), (320, 192, {"patch_stride": 8}, LOOSE),
+    (256, 256, {"finest_scale": 3}, LOOSE), (320, 192, {"finest_scale": 3}, LOOSE), (768, 256, {"finest_scale": 3}, LOOSE),
+]
+
+
+@pytest.mark.parametrize("w,h,over,band", TRANSLATION_CASES,
+                         ids=[f"{w}x{h}" + "".join(f"-{k}{v}" for k, v in o.items()) for w, h, o, _ in TRANSLATION_CASES])
 @pytest.mark.parametrize("d", [(3.0, -2.0), (0.5, 0.25)])
-def test_global_translation_is_recovered_with_the_farneback_sign(d):
-    I0, I1 = _shifted(*d)
-    flow = dis_ref.flow(I0, I1)[MARGIN:-MARGIN, MARGIN:-MARGIN].reshape(-1, 2)
+def test_global_translation_is_recovered_with_the_farneback_sign(d, w, h, over, band):
+    I0, I1 = _shifted(*d, w=w, h=h)
+    flow = dis_ref.flow(I0, I1, dis_ref.fast_params(**over))[MARGIN:-MARGIN, MARGIN:-MARGIN].reshape(-1, 2)
     err = np.hypot(flow[:, 0] - d[0], flow[:, 1] - d[1])
-    assert np.median(err) < MEDIAN_TOL, np.median(err)
-    assert np.mean(err <= WITHIN) >= FRACTION, np.mean(err <= WITHIN)
+    assert np.median(err) < band[0], np.median(err)
+    assert np.mean(err <= WITHIN) >= band[1], np.mean(err <= WITHIN)
+    assert np.all(np.sign(np.median(flow, 0)) == np.sign(d))
     # I1(x + u) ~ I0(x): the sign of cv2's Farneback output, which the oracle shares
     fb = orc.farneback(I0, I1)[MARGIN:-MARGIN, MARGIN:-MARGIN].reshape(-1, 2)
     assert np.all(np.sign(np.median(fb, 0)) == np.sign(d))

@@ -1,6 +1,7 @@
 """GPU tests of the DIS path (ffl_flow_pairs_dis, the reference's "DNN" backend, FF:948-980): flows are bit-identical
-to the plain-C restatement (tests/dis_ref), pass-1 records exact, radial scalars within the 1e-4
-relative tolerance the other GPU tests use.  Parity with cv2.DISOpticalFlow itself is unpinned (no cv2 here)."""
+to the plain-C restatement (tests/dis_ref), pass-1 records exact, mean magnitudes and radial scalars
+within the 1e-4 relative tolerance of the first GPU tests and within the derived bounds of tests/post_ref.py.  Parity with
+cv2.DISOpticalFlow itself is unpinned (no cv2 here)."""
 import json
 import os
 
@@ -12,6 +13,7 @@ pytestmark = pytest.mark.gpu
 import dis_ref
 import gen_dis_golden
 import oracle as orc
+import post_ref as pr
 from funscript_flow_amd import _capi, backend, pipeline
 from funscript_flow_amd.synth import gray_to_bgr, sine_translate_frames
 
@@ -41,6 +43,7 @@ def _check_batch(ctx, pairs, p=None, pov=False):
             assert (x, y) == (ox, oy) and np.float32(v) == np.float32(ov)
         rm = float(orc.mean_mag_np(ref))
         assert abs(float(mm) - rm) <= 1e-4 * max(rm, 1e-6)
+        pr.check_mean_mag(mm, ref)
     return recs
 
 
@@ -62,6 +65,7 @@ def test_batches_bit_identical_to_restatement(B):
                 x, y, v, mm, _ = recs[i]
                 assert (x, y) == (ox, oy) and np.float32(v) == np.float32(ov), i
                 assert abs(float(mm) - rm) <= 1e-4 * max(rm, 1e-6), i
+                pr.check_mean_mag(mm, refs[i % len(cont)])
             assert ctx.graph_stats()["capture_failures"] == 0
         return
     with _capi.Context(w, h, frame_slots=2 * B, flow_slots=B, max_batch=B) as ctx:
@@ -88,6 +92,7 @@ def test_radial_matches_restatement_field():
             for i, (_, f0, f1) in enumerate(cont):
                 want = float(orc.radial_np(_ref_pair(f0, f1, None), c, False, pov))
                 assert abs(got[i] - want) <= 1e-4 * max(abs(want), 1e-3)
+                pr.check_radial(got[i], _ref_pair(f0, f1, None), c, pov)
 
 
 def test_parameter_variants_and_512():
@@ -177,6 +182,8 @@ def test_pair_engine_dis_recycles_slots_at_depth_2():
     for j in (0, 17, 38):
         want = float(orc.radial_np(_ref_pair(fr[j], fr[j + 1], None), centers[j], recs[j][4], False))
         assert abs(dots[j] - want) <= 1e-4 * max(abs(want), 1e-3)
+        assert not recs[j][4], j                  # a 3 % zoom is no cut: the exact check below runs for every sampled pair
+        pr.check_radial(dots[j], _ref_pair(fr[j], fr[j + 1], None), centers[j], False)
     assert ctx.graph_stats()["capture_failures"] == 0
     ctx.close()
 
@@ -191,12 +198,16 @@ def test_drop_ins_on_a_zoom_clip():
     centers = pipeline.smooth_centers(np.array([p["pos_center"] for p in pre]))
     dots = backend.radial_all(pre, centers)
     # the restatement-driven chain, on a sample of pairs (full pass-1 records for all of them)
-    rx = []
+    rx, exact = [], 0
     for j in range(len(pairs)):
         ref = _ref_pair(pairs[j][0], pairs[j][1], None)
         ox, oy, _ = orc.max_divergence_np(ref)
         assert (int(pre[j]["pos_center"][0]), int(pre[j]["pos_center"][1])) == (ox, oy), j
         rx.append(float(orc.radial_np(ref, centers[j], pre[j]["cut"], False)))
+        if j % 25 == 0 and not pre[j]["cut"]:
+            pr.check_radial(dots[j], ref, centers[j], False)
+            exact += 1
+    assert exact >= 12, exact                      # of the 24 sampled pairs; a cut's scalar is 0.0 by definition
     rx = np.array(rx)
     assert np.all(np.abs(np.array(dots) - rx) <= 1e-4 * np.maximum(np.abs(rx), 1e-3))
     # DIS against Farneback about one fixed centre (the argmax centres of two algorithms need not agree, so the per-pair
@@ -236,10 +247,12 @@ def test_committed_fixtures():
             assert (x, y) == tuple(g["pass1_xy"][k]) and np.float32(v) == g["pass1_div"][k], name
             want_mm = float(g["pass1_mean_mag"][k])
             assert abs(float(mm) - want_mm) <= 1e-4 * max(want_mm, 1e-6), name
+            pr.check_mean_mag(mm, flow)
             c = gen_dis_golden.center(w, h)
             for pov, want in zip((False, True), g["radial"][k]):
                 got = ctx.radial([0], [c], [False], pov)[0]
                 assert abs(got - want) <= 1e-4 * max(abs(want), 1e-3), (name, pov)
+                pr.check_radial(got, flow, c, pov)
             if "finest_" + name in g:
                 fin = ctx.debug_dis_pair(0, 1, 2, "refined", p)
                 assert np.array_equal(fin, g["finest_" + name]), name

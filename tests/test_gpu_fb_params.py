@@ -2,7 +2,7 @@
 general kernels are bit-identical to the oracle at the reference's values (forced through them with the context option
 "fb_general") and to the plain-C restatement (tests/fb_general_ref) under every fixture parameter set; pass-1 argmax records
 are exact, mean magnitudes and radial scalars within the tolerances the other GPU tests use (their reductions sum in another
-order).  Parity with cv2 itself is unpinned."""
+order) and within the derived bounds of tests/post_ref.py.  Parity with cv2 itself is unpinned."""
 import json
 
 import numpy as np
@@ -13,6 +13,7 @@ pytestmark = pytest.mark.gpu
 import fb_general_ref as fbr
 import gen_fb_params_golden as gen
 import oracle as orc
+import post_ref as pr
 from funscript_flow_amd import _capi, pipeline
 from funscript_flow_amd.synth import sine_translate_frames
 
@@ -51,6 +52,7 @@ def _check(ctx, frames, recs, want_of, pov=False):
         if not pov:
             assert (x, y) == (ox, oy) and np.float32(v) == np.float32(ov), j
         assert abs(float(mm) - rm) <= 1e-4 * max(rm, 1e-6), j
+        pr.check_mean_mag(mm, ref)
 
 
 @pytest.mark.parametrize("w,h,B", [(256, 256, 64), (640, 360, 8), (333, 197, 4), (1920, 1080, 32)])
@@ -82,10 +84,12 @@ def test_every_fixture_case_matches_the_restatement_and_the_fixtures(name, B, go
         assert gen.sha(ctx.download_flow(0)) == g["flow_sha256"][i]
         x, y, v, mm, _ = recs[0]
         assert (x, y) == tuple(g["pass1_xy"][i]) and np.float32(v) == g["pass1_div"][i]
+        ref0 = fbr.flow(frames[0], frames[1], over)          # the restatement's field of pair 0, not the device's own
         for k, pov in enumerate((False, True)):
             got = ctx.radial([0], [gen.gen_dis_golden.center(w, h)], [False], pov)[0]
             want = float(g["radial"][i][k])
             assert abs(got - want) <= 1e-6 * max(abs(want), 1e-9), (pov, got, want)
+            pr.check_radial(got, ref0, gen.gen_dis_golden.center(w, h), pov)
         # pov on: the same flow, no argmax record
         recs = _run(ctx, frames, p, pov=True)
         _check(ctx, frames, recs, lambda a, b: fbr.flow(a, b, over), pov=True)
