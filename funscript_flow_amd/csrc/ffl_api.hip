@@ -26,6 +26,34 @@
 #define FFL_EV_RING 16
 #define FFL_RAW_RING 4
 
+// Every runtime resource of a context belongs to one of these move-only handles (the only callers of hipFree, hipHostFree
+// and the *Destroy calls): a null handle destroys as a no-op, reset() frees now and reports what the runtime answered.
+// They read like the raw handle wherever one is expected; put() is the out-parameter of a create call.
+template <class H, class Arg, hipError_t (*Free)(Arg)>
+struct Owned {
+    H h = H();
+    Owned() = default;
+    explicit Owned(H take) : h(take) {}
+    Owned(Owned &&o) noexcept : h(o.release()) {}  // move-only: no copies are generated
+    Owned &operator=(Owned &&o) noexcept { std::swap(h, o.h); return *this; }  // o frees what *this held
+    ~Owned() { reset(); }
+    hipError_t reset() { return h ? Free(release()) : hipSuccess; }
+    H release() { H t = h; h = H(); return t; }
+    H *put() { reset(); return &h; }
+    operator H() const { return h; }
+    H operator->() const { return h; }
+};
+template <class T> struct DevBuf : Owned<T *, void *, hipFree> {  // hipMalloc'ed array of T
+    hipError_t alloc(size_t count) { return hipMalloc(this->put(), sizeof(T) * count); }
+};
+template <class T> struct PinBuf : Owned<T *, void *, hipHostFree> {  // page-locked host array of T
+    hipError_t alloc(size_t count, unsigned flags) { return hipHostMalloc(this->put(), sizeof(T) * count, flags); }
+};
+typedef Owned<hipEvent_t, hipEvent_t, hipEventDestroy> Event;
+typedef Owned<hipStream_t, hipStream_t, hipStreamDestroy> Stream;
+typedef Owned<hipGraph_t, hipGraph_t, hipGraphDestroy> Graph;
+typedef Owned<hipGraphExec_t, hipGraphExec_t, hipGraphExecDestroy> GraphExec;
+
 static thread_local std::string g_create_error = "";
 // The process-wide option set (ffl_set_option): the defaults of contexts created AFTERWARDS.  Every context copies it at
 // ffl_create (ffl_ctx::opt) and is from then on only changed through ffl_ctx_set_option, which bumps that context's own
@@ -58,21 +86,16 @@ static std::mutex g_opt_mu;
 // been recorded, so no reference ever names an entry that still holds an older operation.
 struct EvRef;
 struct EvRing {
-    std::vector<hipEvent_t> ev;
+    std::vector<Event> ev;
     unsigned long long next = 0;     // tickets handed out so far
     unsigned long long settled = 0;  // settle_next() has succeeded for every ticket below this
     hipError_t create(int n) {
-        ev.assign(n, nullptr);
+        ev = std::vector<Event>(n);
         for (auto &e : ev) {
-            hipError_t r = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+            hipError_t r = hipEventCreateWithFlags(e.put(), hipEventDisableTiming);
             if (r != hipSuccess) return r;
         }
         return hipSuccess;
-    }
-    void destroy() {
-        for (auto e : ev)
-            if (e) hipEventDestroy(e);
-        ev.clear();
     }
     // the entry the next record() hands out: its previous operation (`size` operations ago) must be over.  Waits at most
     // once per ticket, so a caller may settle early (run_batch, before it writes the entry's table) and record later.
@@ -89,7 +112,7 @@ struct EvRef {
     const EvRing *ring = nullptr;
     unsigned long long ticket = 0;
     // the event to wait on, or nullptr when there is nothing (never set, or the entry has been handed out again: completed)
-    hipEvent_t get() const { return (ring && ring->next - ticket <= ring->ev.size()) ? ring->ev[ticket % ring->ev.size()] : nullptr; }
+    hipEvent_t get() const { return (ring && ring->next - ticket <= ring->ev.size()) ? ring->ev[ticket % ring->ev.size()].h : nullptr; }
 };
 inline hipError_t EvRing::record(hipStream_t st, EvRef *out) {
     hipError_t r = settle_next();
@@ -109,6 +132,21 @@ struct LevelGeom {
     int lw, lh, ksize;
     double sigma;
     GaussKernel gk;
+};
+struct Geometry { int levels = 0; LevelGeom lv[8]; };  // level_geometry(width, height)
+
+// What a context of (width, height, n_frame_slots, n_flow_slots, max_batch) allocates, in elements (context_layout):
+// ffl_create allocates from it, ffl_estimate_bytes sums it and ffl_farneback_extra_bytes reads R.  The small tables (and the
+// 16 padding bytes of d_gray) are not listed: the estimate covers them with an allowance.
+struct Layout {
+    // per lane (the same for every lane)
+    size_t i_off[8], t_off[8], r_off[8];  // float offset of level k inside d_I / d_T (pyramid horizontal-pass buffer) / d_R
+    size_t I, T, R;                       // floats of d_I, d_T, d_R: all levels of the 2 * max_batch unique frames of a batch
+    size_t M, flow;                       // floats of each of d_M[0], d_M[1] / of each of d_flowA, d_flowB
+    size_t p1, tab;                       // pass-1 partial keys, and as many sums / entries of the pinned table ring h_tab
+    // per context
+    size_t gray, bgr;   // bytes of d_gray / d_bgr, and of their pinned staging areas
+    size_t slots, res;  // floats of d_flow / result records h_res
 };
 
 // Staging copies (caller's pageable ndarray -> pinned memory) bound the PCIe-inclusive rate from 3-channel frames:
@@ -210,53 +248,49 @@ struct CopyPool {
 };
 
 struct ffl_ctx {
-    int device = 0, w = 0, h = 0, levels = 0;
+    int device = 0, w = 0, h = 0;
     FflOptions opt;      // this context's own option set (copied from the process-wide defaults at ffl_create)
     int opt_epoch = 0;   // bumped by every applied ffl_ctx_set_option: a graph is only replayed under the options it was captured with
     int graph_captured = 0, graph_replayed = 0, graph_failed = 0;  // ffl_graph_stats
     CopyPool pool;
     int n_fslots = 0, n_slots = 0, max_batch = 0;
     size_t N = 0;
-    LevelGeom geom[8];
+    Geometry geo;
+    Layout lay;
     PolyConsts pc;
-    hipStream_t s_copy = nullptr, s_post = nullptr;  // uploads (+gray) / pass 2 and flow uploads
+    Stream s_copy, s_post;  // uploads (+gray) / pass 2 and flow uploads
     // Compute lanes: each ffl_flow_pairs batch runs on the next lane (stream + its own work buffers),
     // so consecutive batches execute concurrently and the device overlaps one batch's f64-bound box
     // filter with another's bandwidth-bound UpdateMatrices / PolyExp.
     struct Lane {
-        hipStream_t st = nullptr;
+        Stream st;
         // Frame-only work (pyramid + PolyExp of every level) runs ahead on `st_aux` and overlaps the
         // flow chain of the coarser levels, whose small grids leave most of the device idle; the
         // chain on `st` waits for ev_R[k] before touching level k.  R holds all levels at once.
-        hipStream_t st_aux[4] = {nullptr};
-        hipEvent_t ev_R[8] = {nullptr}, ev_fork = nullptr;
-        size_t i_off[8] = {0};  // float offset of level k inside d_I
-        size_t t_off[8] = {0};  // float offset of level k inside d_T (pyramid horizontal-pass buffer)
-        float *d_T = nullptr;
+        Stream st_aux[4];
+        Event ev_R[8], ev_fork;
         EvRing ring;  // one "batch finished" event per batch (FFL_EV_RING entries)
-        size_t r_off[8] = {0};  // float offset of level k inside d_R
-        size_t r_cap = 0;       // floats of d_R
-        float *d_gen = nullptr; // general-path work area (ffl_flow_pairs_farneback), allocated when d_R is too small
-        size_t gen_cap = 0;     // its floats: the largest request seen
-        float *d_I = nullptr, *d_R = nullptr, *d_M[2] = {nullptr, nullptr}, *d_flowA = nullptr, *d_flowB = nullptr;
-        unsigned long long *d_pkey = nullptr;
-        double *d_psum = nullptr;
+        DevBuf<float> d_gen;  // general-path work area (ffl_flow_pairs_farneback), allocated when d_R is too small
+        size_t gen_cap = 0;   // its floats: the largest request seen
+        DevBuf<float> d_I, d_T, d_R, d_M[2], d_flowA, d_flowB;  // Layout: I, T, R, M, flow
+        DevBuf<unsigned long long> d_pkey;
+        DevBuf<double> d_psum;
         // per-batch index tables: device copy + a ring of pinned host copies (entry e belongs to ring entry e)
-        BatchTab *d_tab = nullptr, *h_tab = nullptr;
+        DevBuf<BatchTab> d_tab; PinBuf<BatchTab> h_tab;
         struct GraphEntry {
             int n, nU, pov, epoch;
-            hipGraph_t graph;
-            hipGraphExec_t exec;
+            Graph graph;
+            GraphExec exec;
         };
         std::vector<GraphEntry> graphs;
     };
     std::vector<Lane> lanes;
     unsigned next_lane = 0;
     // frames
-    uint8_t *d_gray = nullptr;        // [n_fslots][N]
-    uint8_t *d_bgr = nullptr;         // [n_fslots][3N] staging for 3-channel uploads
-    uint8_t *h_stage_gray = nullptr;  // pinned [n_fslots][N]   (separate, so that runs of slots are contiguous)
-    uint8_t *h_stage_bgr = nullptr;   // pinned [n_fslots][3N]
+    DevBuf<uint8_t> d_gray;        // [n_fslots][N]
+    DevBuf<uint8_t> d_bgr;         // [n_fslots][3N] staging for 3-channel uploads
+    PinBuf<uint8_t> h_stage_gray;  // pinned [n_fslots][N]   (separate, so that runs of slots are contiguous)
+    PinBuf<uint8_t> h_stage_bgr;   // pinned [n_fslots][3N]
     std::vector<EvRef> ev_uploaded;  // per frame slot: the upload call that filled it (one event per call, up_ring)
     EvRing up_ring;                  // 2 * FFL_EV_RING entries
     std::vector<EvRef> ev_last_use;  // [frame slot * n_lanes + lane]: the last batch of that lane that read the slot
@@ -266,45 +300,46 @@ struct ffl_ctx {
     // ffl_upload_frames_raw: decoded source frames pass through a small ring of pinned + device buffers
     // (grown on demand to the largest source seen); `ev` = the frame's k_frontend has consumed the buffer
     struct RawBuf {
-        uint8_t *h = nullptr, *d = nullptr;
+        PinBuf<uint8_t> h;
+        DevBuf<uint8_t> d;
         size_t cap = 0;
-        hipEvent_t ev = nullptr;
+        Event ev;
         bool busy = false;
     };
     RawBuf raw[FFL_RAW_RING];
     unsigned raw_next = 0;
     EvRing post_ring;  // events of ffl_upload_flow, ffl_radial and ffl_export_flows (stream `post`), FFL_EV_RING entries
-    // device-memory I/O (ffl_upload_frames_device / ffl_export_flows), allocated on first use: the event recorded on the
-    // caller's stream (waited for at once, so one is enough), and the per-call frame descriptor tables -- a pinned copy
-    // per up_ring entry (n_fslots descriptors each) and the device table k_frontend_dev reads (stream `copy`)
-    hipEvent_t ev_caller = nullptr;
-    FrameDesc *h_dtab = nullptr, *d_dtab = nullptr;
+    // device-memory I/O (ffl_upload_frames_device / ffl_export_flows / ffl_import_flows): the event recorded on the
+    // caller's stream (waited for at once, so one is enough), and, allocated on first use, the per-call frame descriptor
+    // tables -- a pinned copy per up_ring entry (n_fslots descriptors each) and the device table k_frontend_dev reads (`copy`)
+    Event ev_caller;
+    PinBuf<FrameDesc> h_dtab; DevBuf<FrameDesc> d_dtab;
     // ffl_import_flows, allocated on first use (stream `post`): the slot / record table k_import_pass1 fills for
     // k_pass1_final, and pass-1 partials for max_batch fields
-    PairTab *d_itab = nullptr;
-    unsigned long long *d_ikey = nullptr;
-    double *d_isum = nullptr;
+    DevBuf<PairTab> d_itab;
+    DevBuf<unsigned long long> d_ikey;
+    DevBuf<double> d_isum;
     // flow slots
-    float *d_flow = nullptr;          // [n_slots][2N]
+    DevBuf<float> d_flow;             // [n_slots][2N]
     // Result records live in pinned, device-mapped host memory: the reduction kernels store their
     // 24-byte record straight into it (visible after the slot's event), so no D2H copies are queued.
-    Pass1Result *h_res = nullptr;     // pinned [n_slots]
+    PinBuf<Pass1Result> h_res;        // pinned [n_slots]
     Pass1Result *d_res = nullptr;     // device alias of h_res
     std::vector<EvRef> ev_slot_done;  // per flow slot: the batch (a lane's ring) or pass-2 / flow-upload call (post_ring) that used it last
     std::vector<char> slot_state;     // 1: queued/ready, 0: empty or its batch failed
-    RadialTab *d_rtab = nullptr, *h_rtab = nullptr;    // pass-2 table (s_post; ffl_radial waits for the stream, so one copy)
-    BatchTab *d_ptab = nullptr, *h_ptab = nullptr;     // ffl_upload_flow's one-pair table (s_post)
-    double *d_rpsum = nullptr;                         // pass-2 partial sums (s_post)
-    double *d_wytab = nullptr;                         // pass-2 row weights (h - y) / h and y / h
-    double *h_radial = nullptr, *d_radial = nullptr;   // pinned pass-2 results and their device alias
-    unsigned long long *d_ppkey = nullptr;                                 // ffl_upload_flow scratch (s_post)
+    DevBuf<RadialTab> d_rtab; PinBuf<RadialTab> h_rtab;  // pass-2 table (s_post; ffl_radial waits for the stream, so one copy)
+    DevBuf<BatchTab> d_ptab; PinBuf<BatchTab> h_ptab;    // ffl_upload_flow's one-pair table (s_post)
+    DevBuf<double> d_rpsum;                            // pass-2 partial sums (s_post)
+    DevBuf<double> d_wytab;                            // pass-2 row weights (h - y) / h and y / h
+    PinBuf<double> h_radial; double *d_radial = nullptr;  // pinned pass-2 results and their device alias
+    DevBuf<unsigned long long> d_ppkey;                // ffl_upload_flow scratch (s_post)
     int p1_blocks = 0;
     // profiling
     unsigned prof_mask = 0;   // bit k set: bracket every launch of kernel class k with HIP events
     // caller-visible page-locked buffers (ffl_host_alloc): uploads out of them skip the staging copy
-    std::vector<std::pair<uint8_t *, size_t>> host_bufs;
+    std::vector<std::pair<PinBuf<uint8_t>, size_t>> host_bufs;
     std::vector<ProfRec> prof_recs;
-    std::vector<hipEvent_t> prof_pool;   // recycled timing events
+    std::vector<Event> prof_pool;        // recycled timing events
     hipEvent_t prof_last_end = nullptr;  // end event of the latest timed launch, while nothing followed it
     int prof_last_cls = -1;
     hipStream_t prof_last_stream = nullptr;
@@ -341,13 +376,16 @@ static int set_err(ffl_ctx *c, int code, const char *fmt, ...) {
     return code;
 }
 
-#define HIPCHK(c, call)                                                                                   \
+// HIPCHK names the failing call by its text; a call made through a handle is reported AS the runtime call it makes
+#define HIPCHK_AS(c, what, call)                                                                          \
     do {                                                                                                  \
         hipError_t e_ = (call);                                                                           \
         if (e_ != hipSuccess)                                                                             \
-            return set_err(c, FFL_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, \
+            return set_err(c, FFL_ERR_HIP, "%s failed: %s (%s:%d)", what, hipGetErrorString(e_), __FILE__, \
                            __LINE__);                                                                     \
     } while (0)
+#define HIPCHK(c, call) HIPCHK_AS(c, #call, call)
+#define HIPCHK_ALLOC(c, fn, buf, ...) HIPCHK_AS(c, #fn "(" #buf ", " #__VA_ARGS__ ")", (buf).alloc(__VA_ARGS__))
 
 // ---- host-side constants (same published procedure as OpenCV's helpers) -------------------------
 static inline int cv_round(double v) { return (int)lrint(v); }
@@ -427,27 +465,46 @@ static void polyexp_prepare(PolyConsts *pc) {  // FarnebackPrepareGaussian(n = 5
     pc->ig55 = A[5][11];
 }
 
-static void level_geometry(ffl_ctx *c) {  // FarnebackOpticalFlowImpl::calc level logic
+static void level_geometry(int w, int h, Geometry *geo) {  // FarnebackOpticalFlowImpl::calc level logic
     int k;
     double scale = 1.0;
     for (k = 0; k < 3; k++) {
         scale *= 0.5;
-        if (c->w * scale < 32 || c->h * scale < 32) break;
+        if (w * scale < 32 || h * scale < 32) break;
     }
-    c->levels = k;
-    for (k = 0; k <= c->levels; k++) {
+    geo->levels = k;
+    for (k = 0; k <= geo->levels; k++) {
         double sc = 1.0;
         for (int i = 0; i < k; i++) sc *= 0.5;
-        LevelGeom &g = c->geom[k];
+        LevelGeom &g = geo->lv[k];
         g.sigma = (1.0 / sc - 1.0) * 0.5;
         int sm = cv_round(g.sigma * 5) | 1;
         g.ksize = sm < 3 ? 3 : sm;
-        g.lw = cv_round(c->w * sc);
-        g.lh = cv_round(c->h * sc);
+        g.lw = cv_round(w * sc);
+        g.lh = cv_round(h * sc);
         memset(&g.gk, 0, sizeof(g.gk));
         g.gk.ksize = g.ksize;
         gaussian_kernel(g.ksize, g.sigma, g.gk.k);
     }
+}
+
+static Layout context_layout(int w, int h, int n_frame_slots, int n_flow_slots, int max_batch) {
+    Geometry geo;
+    level_geometry(w, h, &geo);
+    const size_t N = (size_t)w * h, maxU = 2 * (size_t)max_batch;
+    Layout l = {};
+    for (int k = 0; k <= geo.levels; k++) {
+        const size_t plane = (size_t)geo.lv[k].lw * geo.lv[k].lh;
+        l.i_off[k] = l.I; l.t_off[k] = l.T; l.r_off[k] = l.R;
+        l.I += plane * maxU;
+        l.T += ffl_pyr_tmp_floats(w, h, geo.lv[k].lw) * maxU;
+        l.R += 5 * plane * maxU;
+    }
+    l.M = 5 * N * max_batch; l.flow = 2 * N * max_batch;
+    l.p1 = (size_t)ffl_pass1_blocks(w, h) * max_batch; l.tab = FFL_EV_RING;
+    l.gray = (size_t)n_frame_slots * N; l.bgr = (size_t)n_frame_slots * N * 3;
+    l.slots = 2 * N * n_flow_slots; l.res = n_flow_slots;
+    return l;
 }
 
 // ---- profiling helpers ---------------------------------------------------------------------------
@@ -455,14 +512,14 @@ static void level_geometry(ffl_ctx *c) {  // FarnebackOpticalFlowImpl::calc leve
 // launch itself).  Where the caller knows that timed launches of a class are queued back to back (the three
 // k_blur_solve iterations of a level) a launch starts at its predecessor's end event instead of recording one.
 static hipEvent_t prof_event(ffl_ctx *c) {
-    if (!c->prof_pool.empty()) {
-        hipEvent_t e = c->prof_pool.back();
+    Event e;  // leaves the pool until prof_collect hands it back
+    if (c->prof_pool.empty()) {
+        hipEventCreate(e.put());
+    } else {
+        e = std::move(c->prof_pool.back());
         c->prof_pool.pop_back();
-        return e;
     }
-    hipEvent_t e = nullptr;
-    hipEventCreate(&e);
-    return e;
+    return e.release();
 }
 
 struct ProfScope {
@@ -508,8 +565,8 @@ static void prof_collect(ffl_ctx *c) {
         c->prof_ms[r.cls] += ms;
     }
     for (auto &r : c->prof_recs) {
-        if (!r.shared_start) c->prof_pool.push_back(r.a);
-        c->prof_pool.push_back(r.b);
+        if (!r.shared_start) c->prof_pool.emplace_back(r.a);
+        c->prof_pool.emplace_back(r.b);
     }
     c->prof_recs.clear();
     c->prof_last_end = nullptr;
@@ -601,18 +658,19 @@ static int upload_staged(ffl_ctx *c, CtxLock &lk, int first, int n, size_t fbyte
         const int fs = first + i;
         auto &rb = c->raw[c->raw_next++ % FFL_RAW_RING];
         if (rb.busy) {  // its previous frame has left both buffers
-            if (int rc = wait_unlocked(c, lk, &rb.ev, 1)) return rc;
+            if (int rc = wait_unlocked(c, lk, &rb.ev.h, 1)) return rc;
         }
         if (rb.cap < fbytes) {
-            hipFree(rb.d);
-            hipHostFree(rb.h);
-            rb.d = rb.h = nullptr;
-            rb.cap = 0;
-            HIPCHK(c, hipMalloc(&rb.d, fbytes));
-            HIPCHK(c, hipHostMalloc(&rb.h, fbytes, hipHostMallocDefault));
+            rb.cap = 0;  // the old pair goes first: the two sizes need not fit side by side
+            rb.d.reset();
+            rb.h.reset();
+            DevBuf<uint8_t> d; PinBuf<uint8_t> h;  // into locals: a failed second allocation drops the first too, cap stays 0
+            HIPCHK_ALLOC(c, hipMalloc, d, fbytes);
+            HIPCHK_ALLOC(c, hipHostMalloc, h, fbytes, hipHostMallocDefault);
+            rb.d = std::move(d);
+            rb.h = std::move(h);
             rb.cap = fbytes;
         }
-        if (!rb.ev) HIPCHK(c, hipEventCreateWithFlags(&rb.ev, hipEventDisableTiming));
         const bool dir = direct(i);
         if (!dir) {
             const int copy_threads = c->opt.copy_threads;
@@ -672,42 +730,7 @@ void ffl_destroy(ffl_ctx *c) {
     if (c->s_copy) hipStreamSynchronize(c->s_copy);
     prof_collect(c);
     c->pool.shutdown();
-    for (auto e : c->prof_pool) hipEventDestroy(e);
-    for (auto &hb : c->host_bufs) hipHostFree(hb.first);
-    c->up_ring.destroy();
-    c->post_ring.destroy();
-    if (c->ev_caller) hipEventDestroy(c->ev_caller);
-    hipFree(c->d_dtab); hipHostFree(c->h_dtab);
-    hipFree(c->d_gray); hipFree(c->d_bgr); hipHostFree(c->h_stage_gray); hipHostFree(c->h_stage_bgr);
-    for (auto &rb : c->raw) {
-        hipFree(rb.d);
-        hipHostFree(rb.h);
-        if (rb.ev) hipEventDestroy(rb.ev);
-    }
-    for (auto &L : c->lanes) {
-        hipFree(L.d_I); hipFree(L.d_T); hipFree(L.d_R); hipFree(L.d_M[0]); hipFree(L.d_M[1]);
-        hipFree(L.d_flowA); hipFree(L.d_flowB); hipFree(L.d_pkey); hipFree(L.d_psum);
-        hipFree(L.d_tab); hipHostFree(L.h_tab); hipFree(L.d_gen);
-        for (auto &g : L.graphs) {
-            hipGraphExecDestroy(g.exec);
-            hipGraphDestroy(g.graph);
-        }
-        for (auto e : L.ev_R)
-            if (e) hipEventDestroy(e);
-        L.ring.destroy();
-        if (L.ev_fork) hipEventDestroy(L.ev_fork);
-        for (auto s : L.st_aux)
-            if (s) hipStreamDestroy(s);
-        if (L.st) hipStreamDestroy(L.st);
-    }
-    hipFree(c->d_flow);
-    hipHostFree(c->h_res);
-    hipFree(c->d_rpsum); hipFree(c->d_ppkey); hipHostFree(c->h_radial);
-    hipFree(c->d_itab); hipFree(c->d_ikey); hipFree(c->d_isum);
-    hipFree(c->d_rtab); hipHostFree(c->h_rtab); hipFree(c->d_ptab); hipHostFree(c->h_ptab); hipFree(c->d_wytab);
-    if (c->s_copy) hipStreamDestroy(c->s_copy);
-    if (c->s_post) hipStreamDestroy(c->s_post);
-    delete c;
+    delete c;  // every stream has been drained: the handles release in no particular order
 }
 
 int ffl_create(int device, int width, int height, int n_frame_slots, int n_flow_slots, int max_batch,
@@ -740,82 +763,69 @@ int ffl_create(int device, int width, int height, int n_frame_slots, int n_flow_
         c->opt = g_opts;
     }
     const int num_lanes = c->opt.lanes;  // fixed for the life of the context
-    level_geometry(c);
+    level_geometry(width, height, &c->geo);
+    const Layout &lay = c->lay = context_layout(width, height, n_frame_slots, n_flow_slots, max_batch);
     polyexp_prepare(&c->pc);
-#define CCHK(call)                                                                                       \
-    do {                                                                                                 \
-        hipError_t e_ = (call);                                                                          \
-        if (e_ != hipSuccess) {                                                                          \
-            int rc_ = set_err(nullptr, FFL_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_));      \
-            ffl_destroy(c);                                                                              \
-            (void)hipGetLastError(); /* the failure is reported HERE: do not leave it to poison a later call's check */ \
-            return rc_;                                                                                  \
-        }                                                                                                \
-    } while (0)
+    auto fail = [&](const char *what, hipError_t e) {  // works on a context that is built in part: null handles are no-ops
+        const int rc = set_err(nullptr, FFL_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+        ffl_destroy(c);
+        (void)hipGetLastError();  // the failure is reported HERE: do not leave it to poison a later call's check
+        return rc;
+    };
+#define CCHK_AS(what, call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return fail(what, e_); } while (0)
+#define CCHK(call) CCHK_AS(#call, call)
+#define ALLOC(fn, buf, ...) CCHK_AS(#fn "(" #buf ", " #__VA_ARGS__ ")", (buf).alloc(__VA_ARGS__))  // reported as the call it makes
     CCHK(hipSetDevice(device));
     // uploads and pass 2 are short and latency-critical (the host waits on pass 2): high priority, so
     // that they get their own hardware queues and are scheduled between a lane's queued kernels
     int prio_least = 0, prio_greatest = 0;
     CCHK(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-    CCHK(hipStreamCreateWithPriority(&c->s_copy, hipStreamNonBlocking, prio_greatest));
-    CCHK(hipStreamCreateWithPriority(&c->s_post, hipStreamNonBlocking, prio_greatest));
-    const size_t N = c->N;
-    const int maxU = 2 * max_batch;
-    CCHK(hipMalloc(&c->d_gray, (size_t)n_frame_slots * N + 16));  // +16: k_pyr_h fetches taps as aligned words
-    CCHK(hipMalloc(&c->d_bgr, (size_t)n_frame_slots * N * 3));
-    CCHK(hipHostMalloc(&c->h_stage_gray, (size_t)n_frame_slots * N, hipHostMallocDefault));
-    CCHK(hipHostMalloc(&c->h_stage_bgr, (size_t)n_frame_slots * N * 3, hipHostMallocDefault));
+    CCHK(hipStreamCreateWithPriority(c->s_copy.put(), hipStreamNonBlocking, prio_greatest));
+    CCHK(hipStreamCreateWithPriority(c->s_post.put(), hipStreamNonBlocking, prio_greatest));
+    ALLOC(hipMalloc, c->d_gray, lay.gray + 16);  // +16: k_pyr_h fetches taps as aligned words
+    ALLOC(hipMalloc, c->d_bgr, lay.bgr);
+    ALLOC(hipHostMalloc, c->h_stage_gray, lay.gray, hipHostMallocDefault);
+    ALLOC(hipHostMalloc, c->h_stage_bgr, lay.bgr, hipHostMallocDefault);
     c->p1_blocks = ffl_pass1_blocks(width, height);
     c->lanes.resize(num_lanes);
     for (auto &L : c->lanes) {
-        CCHK(hipStreamCreateWithFlags(&L.st, hipStreamNonBlocking));
+        CCHK(hipStreamCreateWithFlags(L.st.put(), hipStreamNonBlocking));
         // st_aux (run-ahead / fork-join schedules only) are created on first use: HIP multiplexes streams
         // onto a few hardware queues, and idle extra streams make the latency-critical `post` / `copy`
         // streams share a queue with a compute lane (pass 2 then waits behind whole queued batches)
-        CCHK(hipEventCreateWithFlags(&L.ev_fork, hipEventDisableTiming));
+        CCHK(hipEventCreateWithFlags(L.ev_fork.put(), hipEventDisableTiming));
         CCHK(L.ring.create(FFL_EV_RING));
-        size_t r_total = 0, i_total = 0, t_total = 0;
-        for (int k = 0; k <= c->levels; k++) {
-            CCHK(hipEventCreateWithFlags(&L.ev_R[k], hipEventDisableTiming));
-            L.r_off[k] = r_total;
-            L.i_off[k] = i_total;
-            L.t_off[k] = t_total;
-            t_total += ffl_pyr_tmp_floats(width, height, c->geom[k].lw) * maxU;
-            r_total += (size_t)5 * c->geom[k].lw * c->geom[k].lh * maxU;
-            i_total += (size_t)c->geom[k].lw * c->geom[k].lh * maxU;
-        }
-        CCHK(hipMalloc(&L.d_I, sizeof(float) * i_total));
-        CCHK(hipMalloc(&L.d_T, sizeof(float) * t_total));
-        CCHK(hipMalloc(&L.d_R, sizeof(float) * r_total));
-        L.r_cap = r_total;
-        CCHK(hipMalloc(&L.d_M[0], sizeof(float) * 5 * N * max_batch));
-        CCHK(hipMalloc(&L.d_M[1], sizeof(float) * 5 * N * max_batch));
-        CCHK(hipMalloc(&L.d_flowA, sizeof(float) * 2 * N * max_batch));
-        CCHK(hipMalloc(&L.d_flowB, sizeof(float) * 2 * N * max_batch));
-        CCHK(hipMalloc(&L.d_pkey, sizeof(unsigned long long) * c->p1_blocks * max_batch));
-        CCHK(hipMalloc(&L.d_psum, sizeof(double) * c->p1_blocks * max_batch));
-        CCHK(hipMalloc(&L.d_tab, sizeof(BatchTab)));
-        CCHK(hipHostMalloc(&L.h_tab, sizeof(BatchTab) * FFL_EV_RING, hipHostMallocDefault));
+        for (int k = 0; k <= c->geo.levels; k++) CCHK(hipEventCreateWithFlags(L.ev_R[k].put(), hipEventDisableTiming));
+        ALLOC(hipMalloc, L.d_I, lay.I);
+        ALLOC(hipMalloc, L.d_T, lay.T);
+        ALLOC(hipMalloc, L.d_R, lay.R);
+        for (auto &M : L.d_M) ALLOC(hipMalloc, M, lay.M);
+        ALLOC(hipMalloc, L.d_flowA, lay.flow);
+        ALLOC(hipMalloc, L.d_flowB, lay.flow);
+        ALLOC(hipMalloc, L.d_pkey, lay.p1);
+        ALLOC(hipMalloc, L.d_psum, lay.p1);
+        ALLOC(hipMalloc, L.d_tab, 1);
+        ALLOC(hipHostMalloc, L.h_tab, lay.tab, hipHostMallocDefault);
     }
-    CCHK(hipMalloc(&c->d_flow, sizeof(float) * 2 * N * n_flow_slots));
-    CCHK(hipHostMalloc(&c->h_res, sizeof(Pass1Result) * n_flow_slots, hipHostMallocMapped));
+    ALLOC(hipMalloc, c->d_flow, lay.slots);
+    ALLOC(hipHostMalloc, c->h_res, lay.res, hipHostMallocMapped);
     CCHK(hipHostGetDevicePointer((void **)&c->d_res, c->h_res, 0));
-    CCHK(hipMalloc(&c->d_rpsum, sizeof(double) * c->p1_blocks * FFL_MAXB));
+    ALLOC(hipMalloc, c->d_rpsum, (size_t)c->p1_blocks * FFL_MAXB);
     {
         std::vector<double> wy(2 * (size_t)height);
         for (int y = 0; y < height; y++) {
             wy[y] = (double)(height - y) / (double)height;
             wy[height + y] = (double)y / (double)height;
         }
-        CCHK(hipMalloc(&c->d_wytab, sizeof(double) * wy.size()));
+        ALLOC(hipMalloc, c->d_wytab, wy.size());
         CCHK(hipMemcpy(c->d_wytab, wy.data(), sizeof(double) * wy.size(), hipMemcpyHostToDevice));
     }
-    CCHK(hipMalloc(&c->d_rtab, sizeof(RadialTab)));
-    CCHK(hipHostMalloc(&c->h_rtab, sizeof(RadialTab), hipHostMallocDefault));
-    CCHK(hipMalloc(&c->d_ptab, sizeof(BatchTab)));
-    CCHK(hipHostMalloc(&c->h_ptab, sizeof(BatchTab), hipHostMallocDefault));
-    CCHK(hipMalloc(&c->d_ppkey, sizeof(unsigned long long) * c->p1_blocks));
-    CCHK(hipHostMalloc(&c->h_radial, sizeof(double) * FFL_MAXB, hipHostMallocMapped));
+    ALLOC(hipMalloc, c->d_rtab, 1);
+    ALLOC(hipHostMalloc, c->h_rtab, 1, hipHostMallocDefault);
+    ALLOC(hipMalloc, c->d_ptab, 1);
+    ALLOC(hipHostMalloc, c->h_ptab, 1, hipHostMallocDefault);
+    ALLOC(hipMalloc, c->d_ppkey, c->p1_blocks);
+    ALLOC(hipHostMalloc, c->h_radial, FFL_MAXB, hipHostMallocMapped);
     CCHK(hipHostGetDevicePointer((void **)&c->d_radial, c->h_radial, 0));
     c->ev_uploaded.assign(n_frame_slots, EvRef{});
     c->ev_last_use.assign((size_t)n_frame_slots * num_lanes, EvRef{});  // references into the lanes' rings
@@ -824,8 +834,12 @@ int ffl_create(int device, int width, int height, int n_frame_slots, int n_flow_
     c->slot_mark.assign(n_flow_slots, 0);
     CCHK(c->up_ring.create(2 * FFL_EV_RING));
     CCHK(c->post_ring.create(FFL_EV_RING));
+    CCHK(hipEventCreateWithFlags(c->ev_caller.put(), hipEventDisableTiming));
+    for (auto &rb : c->raw) CCHK(hipEventCreateWithFlags(rb.ev.put(), hipEventDisableTiming));
     c->ev_slot_done.assign(n_flow_slots, EvRef{});                        // set when a slot is queued
     c->slot_state.assign(n_flow_slots, 0);
+#undef ALLOC
+#undef CCHK_AS
 #undef CCHK
     *out = c;
     return FFL_OK;
@@ -844,49 +858,38 @@ int ffl_device_mem_info(int device, size_t *free_bytes, size_t *total_bytes) {
     return FFL_OK;
 }
 
+static int default_lanes() {
+    std::lock_guard<std::mutex> g(g_opt_mu);
+    return g_opts.lanes;
+}
+
 // What ffl_create(width, height, n_frame_slots, n_flow_slots, max_batch) allocates with the current "lanes" option: the
-// same sums as the hipMalloc / hipHostMalloc calls above (small tables rounded up to 1 MiB in total).  No device needed.
+// bytes of the layout ffl_create allocates from, plus 1 MiB each for the small tables it does not list.  No device needed.
 int ffl_estimate_bytes(int width, int height, int n_frame_slots, int n_flow_slots, int max_batch, size_t *device_bytes,
                        size_t *pinned_bytes) {
     if (width < 16 || height < 16 || (long)width * height * 20 >= (1L << 32) || n_frame_slots < 2 || n_flow_slots < 1 ||
         max_batch < 1 || max_batch > FFL_MAX_BATCH)
         return set_err(nullptr, FFL_ERR_INVALID, "ffl_estimate_bytes: bad geometry / slot counts");
-    ffl_ctx g;  // geometry only
-    g.w = width;
-    g.h = height;
-    level_geometry(&g);
-    const size_t N = (size_t)width * height, maxU = 2 * (size_t)max_batch;
-    size_t lane = 0;
-    for (int k = 0; k <= g.levels; k++) {
-        const size_t n = (size_t)g.geom[k].lw * g.geom[k].lh;
-        lane += sizeof(float) * maxU * (ffl_pyr_tmp_floats(width, height, g.geom[k].lw) + 5 * n + n);  // T, R, I
-    }
-    lane += sizeof(float) * N * max_batch * (5 + 5 + 2 + 2);                                            // M x 2, flow A / B
-    lane += (size_t)ffl_pass1_blocks(width, height) * max_batch * 16;
-    int num_lanes;
-    {
-        std::lock_guard<std::mutex> gl(g_opt_mu);
-        num_lanes = g_opts.lanes;
-    }
-    size_t dev = (size_t)num_lanes * lane + (size_t)n_frame_slots * N * 4 + sizeof(float) * 2 * N * n_flow_slots + ((size_t)1 << 20);
-    size_t pin = (size_t)n_frame_slots * N * 4 + sizeof(Pass1Result) * n_flow_slots + (size_t)num_lanes * sizeof(BatchTab) * FFL_EV_RING + ((size_t)1 << 20);
-    if (device_bytes) *device_bytes = dev;
-    if (pinned_bytes) *pinned_bytes = pin;
+    const Layout l = context_layout(width, height, n_frame_slots, n_flow_slots, max_batch);
+    const size_t lanes = default_lanes(), small = (size_t)1 << 20;
+    const size_t lane = sizeof(float) * (l.I + l.T + l.R + 2 * l.M + 2 * l.flow) + (sizeof(unsigned long long) + sizeof(double)) * l.p1;
+    if (device_bytes) *device_bytes = lanes * lane + l.gray + l.bgr + sizeof(float) * l.slots + small;
+    if (pinned_bytes) *pinned_bytes = l.gray + l.bgr + sizeof(Pass1Result) * l.res + lanes * sizeof(BatchTab) * l.tab + small;
     return FFL_OK;
 }
 
-int ffl_num_levels(const ffl_ctx *c) { return c ? c->levels : -1; }
+int ffl_num_levels(const ffl_ctx *c) { return c ? c->geo.levels : -1; }
 
 int ffl_level_size(const ffl_ctx *c, int level, int *out_wh) {
-    if (!c || !out_wh || level < 0 || level > c->levels) return FFL_ERR_INVALID;
-    out_wh[0] = c->geom[level].lw;
-    out_wh[1] = c->geom[level].lh;
+    if (!c || !out_wh || level < 0 || level > c->geo.levels) return FFL_ERR_INVALID;
+    out_wh[0] = c->geo.lv[level].lw;
+    out_wh[1] = c->geo.lv[level].lh;
     return FFL_OK;
 }
 
 static bool in_host_buf(const ffl_ctx *c, const uint8_t *p, size_t bytes) {
     for (auto &hb : c->host_bufs)
-        if (p >= hb.first && p + bytes <= hb.first + hb.second) return true;
+        if (p >= hb.first.h && p + bytes <= hb.first.h + hb.second) return true;
     return false;
 }
 
@@ -895,10 +898,10 @@ int ffl_host_alloc(ffl_ctx *c, size_t bytes, void **out) {
     CtxLock lk(c->mu);
     if (!out || bytes == 0) return set_err(c, FFL_ERR_INVALID, "ffl_host_alloc: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
-    uint8_t *p = nullptr;
-    HIPCHK(c, hipHostMalloc(&p, bytes, hipHostMallocDefault));
-    c->host_bufs.push_back({p, bytes});
-    *out = p;
+    PinBuf<uint8_t> p;
+    HIPCHK_ALLOC(c, hipHostMalloc, p, bytes, hipHostMallocDefault);
+    *out = p.h;
+    c->host_bufs.emplace_back(std::move(p), bytes);
     return FFL_OK;
 }
 
@@ -907,7 +910,7 @@ int ffl_host_free(ffl_ctx *c, void *ptr) {
     std::unique_lock<std::mutex> ul(c->up_mu);  // no upload out of the buffer starts while it is being freed
     CtxLock lk(c->mu);
     bool mine = false;
-    for (auto &hb : c->host_bufs) mine |= hb.first == ptr;
+    for (auto &hb : c->host_bufs) mine |= hb.first.h == ptr;
     if (!mine) return set_err(c, FFL_ERR_INVALID, "ffl_host_free: not a buffer of this context");
     HIPCHK(c, hipSetDevice(c->device));
     lk.unlock();
@@ -915,9 +918,10 @@ int ffl_host_free(ffl_ctx *c, void *ptr) {
     lk.lock();
     HIPCHK(c, e);
     for (size_t i = 0; i < c->host_bufs.size(); i++)
-        if (c->host_bufs[i].first == ptr) {
-            HIPCHK(c, hipHostFree(ptr));
-            c->host_bufs.erase(c->host_bufs.begin() + i);
+        if (c->host_bufs[i].first.h == ptr) {
+            const hipError_t fe = c->host_bufs[i].first.reset();
+            c->host_bufs.erase(c->host_bufs.begin() + i);  // whatever the runtime answered: the handle is gone
+            HIPCHK_AS(c, "hipHostFree", fe);
             return FFL_OK;
         }
     return set_err(c, FFL_ERR_INVALID, "ffl_host_free: not a buffer of this context");
@@ -1214,16 +1218,16 @@ static int enqueue_batch(ffl_ctx *c, ffl_ctx::Lane &L, const BatchTab &T, int n,
     const PairTab *pt = &L.d_tab->pt;
     // frame-only expansion of level k (level image + PolyExp of the nU unique frames) on stream s
     auto expand_level = [&](int k, hipStream_t s) {
-        const LevelGeom &g = c->geom[k];
+        const LevelGeom &g = c->geo.lv[k];
         const size_t plane = (size_t)g.lw * g.lh;
         {
             ProfScope ps(c, FFL_K_PYRAMID, s);
-            ffl_launch_pyr_level(c->d_gray, N, ut, nU, c->w, c->h, g.lw, g.lh, g.gk, L.d_T + L.t_off[k],
-                                 ffl_pyr_tmp_floats(c->w, c->h, g.lw), L.d_I + L.i_off[k], plane, s);
+            ffl_launch_pyr_level(c->d_gray, N, ut, nU, c->w, c->h, g.lw, g.lh, g.gk, L.d_T + c->lay.t_off[k],
+                                 ffl_pyr_tmp_floats(c->w, c->h, g.lw), L.d_I + c->lay.i_off[k], plane, s);
         }
         {
             ProfScope ps(c, FFL_K_POLYEXP, s);
-            ffl_launch_polyexp(L.d_I + L.i_off[k], plane, L.d_R + L.r_off[k], 5 * plane, plane, nU, g.lw, g.lh, c->pc, s);
+            ffl_launch_polyexp(L.d_I + c->lay.i_off[k], plane, L.d_R + c->lay.r_off[k], 5 * plane, plane, nU, g.lw, g.lh, c->pc, s);
         }
     };
     // Frame-only expansion schedule (ffl_set_option "run_ahead"):
@@ -1236,40 +1240,40 @@ static int enqueue_batch(ffl_ctx *c, ffl_ctx::Lane &L, const BatchTab &T, int n,
     const int mode = cap ? 0 : c->opt.run_ahead;
     if (mode) {
         for (int k = 0; k < (mode == 2 ? 4 : 1); k++)
-            if (!L.st_aux[k]) HIPCHK(c, hipStreamCreateWithFlags(&L.st_aux[k], hipStreamNonBlocking));
+            if (!L.st_aux[k]) HIPCHK(c, hipStreamCreateWithFlags(L.st_aux[k].put(), hipStreamNonBlocking));
         HIPCHK(c, hipEventRecord(L.ev_fork, st));  // after the uploads and after the lane's previous batch
-        for (int k = c->levels; k >= 0; k--) {
+        for (int k = c->geo.levels; k >= 0; k--) {
             hipStream_t sa = L.st_aux[mode == 2 ? k : 0];
-            if (mode == 2 || k == c->levels) HIPCHK(c, hipStreamWaitEvent(sa, L.ev_fork, 0));
+            if (mode == 2 || k == c->geo.levels) HIPCHK(c, hipStreamWaitEvent(sa, L.ev_fork, 0));
             expand_level(k, sa);
             HIPCHK(c, hipEventRecord(L.ev_R[k], sa));
         }
         if (mode == 2)
-            for (int k = c->levels; k >= 0; k--) HIPCHK(c, hipStreamWaitEvent(st, L.ev_R[k], 0));
+            for (int k = c->geo.levels; k >= 0; k--) HIPCHK(c, hipStreamWaitEvent(st, L.ev_R[k], 0));
     }
     const bool run_ahead = mode == 1;
     bool expanded = mode != 0;
-    if (mode == 0 && c->opt.merge_expand && c->levels + 1 <= FFL_MAX_JOBS) {
+    if (mode == 0 && c->opt.merge_expand && c->geo.levels + 1 <= FFL_MAX_JOBS) {
         // serial schedule, merged form: the frame-only work of ALL levels up front in three launches
         // (pyramid phase A + B, PolyExp) instead of ten small ones whose ramps and tails leave the device idle
         PyrJob pj[FFL_MAX_JOBS];
         PolyJob qj[FFL_MAX_JOBS];
         int nj = 0;
-        for (int k = c->levels; k >= 0; k--, nj++) {
-            const LevelGeom &g = c->geom[k];
+        for (int k = c->geo.levels; k >= 0; k--, nj++) {
+            const LevelGeom &g = c->geo.lv[k];
             const size_t plane = (size_t)g.lw * g.lh;
             memset(&pj[nj], 0, sizeof(PyrJob));
             pj[nj].lw = g.lw;
             pj[nj].lh = g.lh;
             pj[nj].gk = g.gk;
-            pj[nj].tmp = L.d_T + L.t_off[k];
+            pj[nj].tmp = L.d_T + c->lay.t_off[k];
             pj[nj].tmp_stride = ffl_pyr_tmp_floats(c->w, c->h, g.lw);
-            pj[nj].I = L.d_I + L.i_off[k];
+            pj[nj].I = L.d_I + c->lay.i_off[k];
             pj[nj].I_stride = plane;
             memset(&qj[nj], 0, sizeof(PolyJob));
-            qj[nj].I = L.d_I + L.i_off[k];
+            qj[nj].I = L.d_I + c->lay.i_off[k];
             qj[nj].I_stride = plane;
-            qj[nj].R = L.d_R + L.r_off[k];
+            qj[nj].R = L.d_R + c->lay.r_off[k];
             qj[nj].R_stride = 5 * plane;
             qj[nj].plane = plane;
             qj[nj].w = g.lw;
@@ -1278,10 +1282,10 @@ static int enqueue_batch(ffl_ctx *c, ffl_ctx::Lane &L, const BatchTab &T, int n,
         {
             ProfScope ps(c, FFL_K_PYRAMID, st);
             if (!ffl_launch_pyr_multi(c->d_gray, N, ut, nU, c->w, c->h, pj, nj, c->opt, st))
-                for (int k = c->levels; k >= 0; k--) {  // a level outside the merged kinds: per-level kernels
-                    const LevelGeom &g = c->geom[k];
-                    ffl_launch_pyr_level(c->d_gray, N, ut, nU, c->w, c->h, g.lw, g.lh, g.gk, L.d_T + L.t_off[k],
-                                         ffl_pyr_tmp_floats(c->w, c->h, g.lw), L.d_I + L.i_off[k], (size_t)g.lw * g.lh, st);
+                for (int k = c->geo.levels; k >= 0; k--) {  // a level outside the merged kinds: per-level kernels
+                    const LevelGeom &g = c->geo.lv[k];
+                    ffl_launch_pyr_level(c->d_gray, N, ut, nU, c->w, c->h, g.lw, g.lh, g.gk, L.d_T + c->lay.t_off[k],
+                                         ffl_pyr_tmp_floats(c->w, c->h, g.lw), L.d_I + c->lay.i_off[k], (size_t)g.lw * g.lh, st);
                 }
         }
         {
@@ -1292,12 +1296,12 @@ static int enqueue_batch(ffl_ctx *c, ffl_ctx::Lane &L, const BatchTab &T, int n,
     }
 
     int pw = 0, ph = 0;
-    for (int k = c->levels; k >= 0; k--) {
-        const LevelGeom &g = c->geom[k];
+    for (int k = c->geo.levels; k >= 0; k--) {
+        const LevelGeom &g = c->geo.lv[k];
         const int lw = g.lw, lh = g.lh;
         const size_t plane = (size_t)lw * lh;
         const size_t I_stride = plane, R_stride = 5 * plane, M_stride = 5 * plane;
-        float *Rk = L.d_R + L.r_off[k];
+        float *Rk = L.d_R + c->lay.r_off[k];
         // the coarsest level starts from zero flow; nothing reads that field but UpdateMatrices (which is told
         // so) and the debug capture, so it is only materialised for the latter
         if (pw == 0 && cap)
@@ -1316,8 +1320,8 @@ static int enqueue_batch(ffl_ctx *c, ffl_ctx::Lane &L, const BatchTab &T, int n,
         bool captured = false;
         auto capture = [&]() -> int {
             HIPCHK(c, hipStreamSynchronize(st));
-            if (cap->I0) HIPCHK(c, hipMemcpy(cap->I0, L.d_I + L.i_off[k] + (size_t)T.pt.u0[0] * I_stride, sizeof(float) * plane, hipMemcpyDeviceToHost));
-            if (cap->I1) HIPCHK(c, hipMemcpy(cap->I1, L.d_I + L.i_off[k] + (size_t)T.pt.u1[0] * I_stride, sizeof(float) * plane, hipMemcpyDeviceToHost));
+            if (cap->I0) HIPCHK(c, hipMemcpy(cap->I0, L.d_I + c->lay.i_off[k] + (size_t)T.pt.u0[0] * I_stride, sizeof(float) * plane, hipMemcpyDeviceToHost));
+            if (cap->I1) HIPCHK(c, hipMemcpy(cap->I1, L.d_I + c->lay.i_off[k] + (size_t)T.pt.u1[0] * I_stride, sizeof(float) * plane, hipMemcpyDeviceToHost));
             if (cap->R0) HIPCHK(c, hipMemcpy(cap->R0, Rk + (size_t)T.pt.u0[0] * R_stride, sizeof(float) * 5 * plane, hipMemcpyDeviceToHost));
             if (cap->R1) HIPCHK(c, hipMemcpy(cap->R1, Rk + (size_t)T.pt.u1[0] * R_stride, sizeof(float) * 5 * plane, hipMemcpyDeviceToHost));
             if (cap->M) HIPCHK(c, hipMemcpy(cap->M, L.d_M[mi], sizeof(float) * 5 * plane, hipMemcpyDeviceToHost));
@@ -1366,19 +1370,19 @@ static int batch_graph(ffl_ctx *c, ffl_ctx::Lane &L, const BatchTab &T, int n, i
         if (g.n == n && g.nU == nU && g.pov == pov_mode && g.epoch == c->opt_epoch) *ge = &g;
     if (*ge || c->graph_bad_epoch == c->opt_epoch) return FFL_OK;
     hipStream_t st = L.st;
-    ffl_ctx::Lane::GraphEntry g = {n, nU, pov_mode, c->opt_epoch, nullptr, nullptr};
+    ffl_ctx::Lane::GraphEntry g = {n, nU, pov_mode, c->opt_epoch, Graph(), GraphExec()};
     hipError_t fail = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
     if (fail == hipSuccess) {
         const int rc = enqueue_batch(c, L, T, n, nU, pov_mode, nullptr);
-        fail = hipStreamEndCapture(st, &g.graph);  // always: the stream must leave capture mode
+        fail = hipStreamEndCapture(st, g.graph.put());  // always: the stream must leave capture mode
         if (fail == hipSuccess && (rc != FFL_OK || !g.graph)) fail = hipErrorStreamCaptureInvalidated;
-        if (fail == hipSuccess) fail = hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0);
+        if (fail == hipSuccess) fail = hipGraphInstantiate(g.exec.put(), g.graph, nullptr, nullptr, 0);
     }
     if (fail != hipSuccess) {
         // nothing of the failed capture is kept (it would leak once per batch), the sticky error is cleared, and
         // this context launches eagerly until the option set changes -- the batch itself is not lost
-        if (g.exec) hipGraphExecDestroy(g.exec);
-        if (g.graph) hipGraphDestroy(g.graph);
+        g.exec.reset();
+        g.graph.reset();
         (void)hipGetLastError();
         c->graph_bad_epoch = c->opt_epoch;
         // never silent: counted (ffl_graph_stats, bench.py `config.graphs`) and said once per context on stderr
@@ -1393,17 +1397,15 @@ static int batch_graph(ffl_ctx *c, ffl_ctx::Lane &L, const BatchTab &T, int n, i
     if (L.graphs.size() >= 16) {  // bounded cache: callers that vary the batch shape a lot re-capture
         // a replay may still be queued: graph resources are released once the lane's stream has drained
         HIPCHK(c, hipStreamSynchronize(st));
-        hipGraphExecDestroy(L.graphs.front().exec);
-        hipGraphDestroy(L.graphs.front().graph);
         L.graphs.erase(L.graphs.begin());
     }
-    L.graphs.push_back(g);
+    L.graphs.push_back(std::move(g));
     *ge = &L.graphs.back();
     c->graph_captured++;
     return FFL_OK;
 }
 
-static int fbg_work(ffl_ctx *c, ffl_ctx::Lane &L, const FbgPlan &p, int n, int nU, FbgWork *wk);
+static int fbg_work(ffl_ctx *c, ffl_ctx::Lane &L, const FbgPlan &p, int nU, FbgWork *wk);
 
 // Fills the batch's table T (*nU unique frames) and queues the batch on the lane's stream: the waits for its frames and
 // recycled slots, the table copy, the launches.  Once the table is filled, a failure may leave part of the batch queued.
@@ -1427,13 +1429,13 @@ static int queue_batch(ffl_ctx *c, ffl_ctx::Lane &L, BatchTab &T, int *nU_out, i
         T.pt.res[i] = c->d_res + slots[i];
     }
     // per level: the pair's flow field -- the lane's two ping-pong buffers, coarsest level in A; level 0 is the slot
-    for (int k = c->levels; k >= 0; k--) {
-        const size_t plane = (size_t)c->geom[k].lw * c->geom[k].lh;
-        float *buf = ((c->levels - k) & 1) ? L.d_flowB : L.d_flowA;
+    for (int k = c->geo.levels; k >= 0; k--) {
+        const size_t plane = (size_t)c->geo.lv[k].lw * c->geo.lv[k].lh;
+        float *buf = ((c->geo.levels - k) & 1) ? L.d_flowB : L.d_flowA;
         for (int i = 0; i < n; i++)
             T.pt.flow[k][i] = (k == 0) ? c->d_flow + (size_t)slots[i] * 2 * N : buf + (size_t)i * 2 * plane;
     }
-    for (int k = c->levels + 1; k < FFL_MAX_LEVELS; k++)
+    for (int k = c->geo.levels + 1; k < FFL_MAX_LEVELS; k++)
         for (int i = 0; i < n; i++) T.pt.flow[k][i] = nullptr;
     for (int i = 0; i < nU; i++) c->u_of_fslot[T.ut.fslot[i]] = -1;  // the scratch map goes back to "empty"
     *nU_out = nU;
@@ -1447,7 +1449,7 @@ static int queue_batch(ffl_ctx *c, ffl_ctx::Lane &L, BatchTab &T, int *nU_out, i
     if (fbg) {
         // general-parameter Farneback batches launch eagerly too (graphs stay keyed on the tuned schedule)
         FbgWork wk;
-        if (int rc = fbg_work(c, L, *fbg, n, nU, &wk)) return rc;
+        if (int rc = fbg_work(c, L, *fbg, nU, &wk)) return rc;
         ffl_launch_fb_general(&L.d_tab->ut, &L.d_tab->pt, n, nU, c->d_gray, N, c->w, c->h, *fbg, wk, st);
         ProfScope ps(c, FFL_K_PASS1, st);
         ffl_launch_pass1(&L.d_tab->pt, n, c->w, c->h, pov_mode, L.d_pkey, L.d_psum, st);
@@ -1636,15 +1638,15 @@ int ffl_debug_dis_pair(ffl_ctx *c, int f0, int f1, const ffl_dis_params *p, int 
     const size_t np = (size_t)(1 + (lw - 8) / k.stride) * (1 + (lh - 8) / k.stride);
     const size_t floats = stage <= 1 ? 2 * np : 2 * lw * lh;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMalloc(&k.dbg, sizeof(float) * floats));
+    DevBuf<float> dbg;
+    HIPCHK_ALLOC(c, hipMalloc, dbg, floats);
+    k.dbg = dbg;
     k.dbg_scale = scale;
     k.dbg_stage = stage;
     rc = run_batch(c, 0, 1, &f0, &f1, &slot, 0, nullptr, &k);
-    hipError_t e = rc ? hipSuccess : hipStreamSynchronize(c->lanes[0].st);
-    if (!rc && e == hipSuccess) e = hipMemcpy(out, k.dbg, sizeof(float) * floats, hipMemcpyDeviceToHost);
-    hipFree(k.dbg);
     if (rc) return rc;
-    HIPCHK(c, e);
+    HIPCHK(c, hipStreamSynchronize(c->lanes[0].st));
+    HIPCHK(c, hipMemcpy(out, k.dbg, sizeof(float) * floats, hipMemcpyDeviceToHost));
     return FFL_OK;
 }
 
@@ -1807,34 +1809,22 @@ int ffl_farneback_extra_bytes(int width, int height, int max_batch, const ffl_fa
     char why[160];
     if (const char *e = fbg_plan(width, height, *p, &pl, why, sizeof why))
         return set_err(nullptr, FFL_ERR_INVALID, "ffl_farneback_extra_bytes: %s", e);
-    ffl_ctx g;  // geometry only
-    g.w = width;
-    g.h = height;
-    level_geometry(&g);
-    const size_t maxU = 2 * (size_t)max_batch;
-    size_t r_cap = 0;
-    for (int k = 0; k <= g.levels; k++) r_cap += (size_t)5 * g.geom[k].lw * g.geom[k].lh * maxU;
-    const size_t need = pl.r_frame * maxU;
-    int num_lanes;
-    {
-        std::lock_guard<std::mutex> gl(g_opt_mu);
-        num_lanes = g_opts.lanes;
-    }
-    *bytes = need > r_cap ? sizeof(float) * (need - r_cap) * (size_t)num_lanes : 0;
+    const size_t r_cap = context_layout(width, height, 2, 1, max_batch).R;  // R does not depend on the slot counts
+    const size_t need = pl.r_frame * 2 * (size_t)max_batch;
+    *bytes = need > r_cap ? sizeof(float) * (need - r_cap) * (size_t)default_lanes() : 0;
     return FFL_OK;
 }
 
-// Where a general batch of n pairs / nU unique frames works on lane L.  M and the level flows always fit the lane's d_M[0],
+// Where a general batch of nU unique frames works on lane L.  M and the level flows always fit the lane's d_M[0],
 // d_flowA and d_flowB (sized for 5 N and 2 N per pair; the blur planes need 2 N and the level images N per unique frame, at
 // most two per pair); the R regions of every level go to d_R when they fit, else to the lane's general-path work area, grown
 // to the largest request seen once the lane's queued work is over.
-static int fbg_work(ffl_ctx *c, ffl_ctx::Lane &L, const FbgPlan &p, int n, int nU, FbgWork *wk) {
-    (void)n;
+static int fbg_work(ffl_ctx *c, ffl_ctx::Lane &L, const FbgPlan &p, int nU, FbgWork *wk) {
     wk->M = L.d_M[0];
     wk->fa = L.d_flowA;
     wk->fb = L.d_flowB;
     const size_t need = p.r_frame * (size_t)nU;
-    if (need <= L.r_cap) {
+    if (need <= c->lay.R) {
         wk->R = L.d_R;
         return FFL_OK;
     }
@@ -1842,14 +1832,13 @@ static int fbg_work(ffl_ctx *c, ffl_ctx::Lane &L, const FbgPlan &p, int n, int n
         if (L.d_gen) {
             hipEvent_t e = ev_latest(L.ring).get();  // the lane's last batch may still read the old area
             if (e) HIPCHK(c, hipEventSynchronize(e));
-            HIPCHK(c, hipFree(L.d_gen));
-            L.d_gen = nullptr;
             L.gen_cap = 0;
+            HIPCHK_AS(c, "hipFree", L.d_gen.reset());
         }
-        const hipError_t e = hipMalloc(&L.d_gen, sizeof(float) * need);
+        const hipError_t e = L.d_gen.alloc(need);
         if (e != hipSuccess) {
             (void)hipGetLastError();
-            L.d_gen = nullptr;
+            L.d_gen.release();  // nothing was allocated
             return set_err(c, FFL_ERR_HIP, "general Farneback work area: hipMalloc of %zu bytes (%d frames x %zu floats) failed: %s",
                            sizeof(float) * need, nU, p.r_frame, hipGetErrorString(e));
         }
@@ -1887,7 +1876,7 @@ int ffl_debug_pair(ffl_ctx *c, int f0, int f1, int level, int iter, float *I0, f
     int slot = 0;
     int rc = check_pairs(c, 1, &f0, &f1, &slot);
     if (rc) return rc;
-    if (level < 0 || level > c->levels || iter < 0 || iter > 3) return set_err(c, FFL_ERR_INVALID, "bad level/iter");
+    if (level < 0 || level > c->geo.levels || iter < 0 || iter > 3) return set_err(c, FFL_ERR_INVALID, "bad level/iter");
     HIPCHK(c, hipSetDevice(c->device));
     DebugCapture cap = {level, iter, I0, I1, R0, R1, M, flow};
     rc = run_batch(c, 0, 1, &f0, &f1, &slot, 0, &cap);
@@ -2090,8 +2079,11 @@ static int dev_mem_check(ffl_ctx *c, const char *fn, const char *what, const voi
     return FFL_OK;
 }
 
-// the first HIP call made on a caller's stream: device-memory I/O is never captured into anyone's graph
-static int refuse_capturing(ffl_ctx *c, const char *fn, hipStream_t st) {
+// The stream contract of the device-memory calls (ffl.h): caller_stream() names the caller's stream and refuses it while it
+// captures (the first HIP call made on it: device-memory I/O is never captured into anyone's graph); caller_join() orders the
+// library's stream behind it; at its end a call makes the caller's stream wait for the library's event in turn.
+static int caller_stream(ffl_ctx *c, const char *fn, uint64_t stream, hipStream_t *cst) {
+    hipStream_t st = *cst = (hipStream_t)(uintptr_t)stream;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     const hipError_t e = hipStreamIsCapturing(st, &cs);
     if (e == hipErrorStreamCaptureImplicit) cs = hipStreamCaptureStatusActive;  // the null stream while a global capture runs
@@ -2104,6 +2096,13 @@ static int refuse_capturing(ffl_ctx *c, const char *fn, hipStream_t st) {
         return set_err(c, FFL_ERR_STATE, "%s: the stream is capturing a graph; device-memory I/O is never captured (call it "
                                          "before or after the capture)", fn);
     }
+    return FFL_OK;
+}
+
+// the stream `wait` is for (`copy` or `post`) waits for the work the caller has queued on cst
+static int caller_join(ffl_ctx *c, hipStream_t cst, WaitOnce &wait) {
+    HIPCHK(c, hipEventRecord(c->ev_caller, cst));
+    HIPCHK(c, wait(c->ev_caller));
     return FFL_OK;
 }
 
@@ -2127,8 +2126,8 @@ int ffl_upload_frames_device(ffl_ctx *c, int first, int n, const ffl_dev_frame *
     for (int i = 0; i < n; i++)
         if (int rc = dev_frame_check(c, fn, i, fmt, sw, sh, &frames[i], rw, rh, cx, cy, c->w, c->h, &p)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t cst = (hipStream_t)(uintptr_t)stream;
-    if (int rc = refuse_capturing(c, fn, cst)) return rc;
+    hipStream_t cst;
+    if (int rc = caller_stream(c, fn, stream, &cst)) return rc;
     static const char *names[3] = {"plane 0", "plane 1", "plane 2"};
     for (int i = 0; i < n; i++) {
         size_t ext[3];
@@ -2138,10 +2137,12 @@ int ffl_upload_frames_device(ffl_ctx *c, int first, int n, const ffl_dev_frame *
                 if (int rc = dev_mem_check(c, fn, names[k], frames[i].plane[k], ext[k])) return rc;
     }
     const size_t ring = c->up_ring.ev.size();
-    if (!c->ev_caller) HIPCHK(c, hipEventCreateWithFlags(&c->ev_caller, hipEventDisableTiming));
     if (!c->d_dtab) {
-        HIPCHK(c, hipMalloc(&c->d_dtab, sizeof(FrameDesc) * c->n_fslots));
-        HIPCHK(c, hipHostMalloc(&c->h_dtab, sizeof(FrameDesc) * c->n_fslots * ring, hipHostMallocDefault));
+        DevBuf<FrameDesc> d; PinBuf<FrameDesc> h;  // all or nothing: the context takes them once both exist, else the next call retries
+        HIPCHK_ALLOC(c, hipMalloc, d, c->n_fslots);
+        HIPCHK_ALLOC(c, hipHostMalloc, h, c->n_fslots * ring, hipHostMallocDefault);
+        c->d_dtab = std::move(d);
+        c->h_dtab = std::move(h);
     }
     // the pinned table of the entry publish_frames records below: settled, so its copy of 32 calls ago has been consumed
     HIPCHK(c, c->up_ring.settle_next());
@@ -2169,9 +2170,8 @@ int ffl_upload_frames_device(ffl_ctx *c, int first, int n, const ffl_dev_frame *
     p.kind = fmt == FFL_DEV_GRAY ? FFL_SRC_GRAY : yuv ? FFL_SRC_YUV : FFL_SRC_BGR;
     p.rgb = fmt == FFL_DEV_RGB;
     // stream `copy` waits for the producer's queued work and for the batches that still read the slots
-    HIPCHK(c, hipEventRecord(c->ev_caller, cst));
     WaitOnce wait_copy(c->s_copy);
-    HIPCHK(c, wait_copy(c->ev_caller));
+    if (int rc = caller_join(c, cst, wait_copy)) return rc;
     for (int i = 0; i < n; i++)
         if (int rc = wait_frame_free(c, wait_copy, first + i)) return rc;
     HIPCHK(c, hipMemcpyAsync(c->d_dtab, T, sizeof(FrameDesc) * n, hipMemcpyHostToDevice, c->s_copy));
@@ -2206,15 +2206,13 @@ int ffl_export_flows(ffl_ctx *c, int n, const int *slots, float *dst, int layout
         if (!c->slot_state[slots[i]]) return set_err(c, FFL_ERR_STATE, "%s: flow slot %d holds no flow", fn, slots[i]);
     }
     HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t cst = (hipStream_t)(uintptr_t)stream;
-    if (int rc = refuse_capturing(c, fn, cst)) return rc;
+    hipStream_t cst;
+    if (int rc = caller_stream(c, fn, stream, &cst)) return rc;
     const ptrdiff_t span = (ptrdiff_t)(n - 1) * item_stride;
     const char *lo = (const char *)dst + (span < 0 ? span : 0);
     if (int rc = dev_mem_check(c, fn, "dst", lo, (size_t)(span < 0 ? -span : span) + item)) return rc;
-    if (!c->ev_caller) HIPCHK(c, hipEventCreateWithFlags(&c->ev_caller, hipEventDisableTiming));
-    HIPCHK(c, hipEventRecord(c->ev_caller, cst));
     WaitOnce wait_post(c->s_post);
-    HIPCHK(c, wait_post(c->ev_caller));
+    if (int rc = caller_join(c, cst, wait_post)) return rc;
     for (int i = 0; i < n; i++) HIPCHK(c, wait_post(c->ev_slot_done[slots[i]].get()));
     for (int i0 = 0; i0 < n; i0 += FFL_MAXB) {
         const int m = n - i0 < FFL_MAXB ? n - i0 : FFL_MAXB;
@@ -2292,19 +2290,21 @@ int ffl_import_flows(ffl_ctx *c, int n, const int *slots, const ffl_dev_flow *f,
     size_t bytes;
     if (int rc = dev_flow_check(c, fn, dtype, n, c->w, c->h, f, &mode, &bytes)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t cst = (hipStream_t)(uintptr_t)stream;
-    if (int rc = refuse_capturing(c, fn, cst)) return rc;
+    hipStream_t cst;
+    if (int rc = caller_stream(c, fn, stream, &cst)) return rc;
     if (int rc = dev_mem_check(c, fn, "the flow fields", f->base, bytes, "host flow fields go through ffl_upload_flow")) return rc;
-    if (!c->ev_caller) HIPCHK(c, hipEventCreateWithFlags(&c->ev_caller, hipEventDisableTiming));
     if (!c->d_itab) {
-        HIPCHK(c, hipMalloc(&c->d_itab, sizeof(PairTab)));
-        HIPCHK(c, hipMalloc(&c->d_ikey, sizeof(unsigned long long) * c->p1_blocks * c->max_batch));
-        HIPCHK(c, hipMalloc(&c->d_isum, sizeof(double) * c->p1_blocks * c->max_batch));
+        DevBuf<PairTab> tab; DevBuf<unsigned long long> key; DevBuf<double> sum;  // all or nothing, as d_dtab / h_dtab
+        HIPCHK_ALLOC(c, hipMalloc, tab, 1);
+        HIPCHK_ALLOC(c, hipMalloc, key, c->lay.p1);
+        HIPCHK_ALLOC(c, hipMalloc, sum, c->lay.p1);
+        c->d_itab = std::move(tab);
+        c->d_ikey = std::move(key);
+        c->d_isum = std::move(sum);
     }
     // stream `post` waits for the producer's queued work and for the last users of the slots (a batch, a pass 2, an export)
-    HIPCHK(c, hipEventRecord(c->ev_caller, cst));
     WaitOnce wait_post(c->s_post);
-    HIPCHK(c, wait_post(c->ev_caller));
+    if (int rc = caller_join(c, cst, wait_post)) return rc;
     for (int i = 0; i < n; i++) HIPCHK(c, wait_post(c->ev_slot_done[slots[i]].get()));
     const ImportArgs a{(const char *)f->base, (long long)f->item_stride, (long long)f->row_pitch, (long long)f->pixel_stride,
                        (long long)f->channel_stride, c->d_flow, c->d_res};

@@ -560,6 +560,54 @@ def test_create_that_exceeds_device_memory_fails_cleanly_and_leaves_the_device_u
     assert 1 <= B <= 32 and bytes_needed < free1
 
 
+def test_a_contexts_whole_life_leaves_no_device_memory_behind():
+    """Everything a context allocates AFTER ffl_create goes with it: the raw-frame ring (grown once), the descriptor
+    tables of the device upload, two captured graphs, the general Farneback work area, the import buffers, a pinned frame
+    buffer the caller never frees, the profiling events.  Three contexts in a row, 1080p, max_batch 8: after each close
+    the free device memory is back within 64 MiB of where it started (one lane's buffers alone are above 2 GB here, so
+    any array left behind shows).  The torch tensors exist before the starting value is read: the caching allocator
+    keeps what it once took."""
+    import torch
+    W, H, B = 1920, 1080, 8
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(11)
+    small = [rng.integers(0, 256, (H // 2, W // 2, 3), dtype=np.uint8) for _ in range(8)]
+    large = [rng.integers(0, 256, (H, W, 3), dtype=np.uint8) for _ in range(8)]
+    dev_frames = torch.from_numpy(rng.integers(0, 256, (2, H, W), dtype=np.uint8)).to(dev)
+    fields = torch.from_numpy(rng.standard_normal((2, H, W, 2)).astype(np.float32)).to(dev)
+    exported = torch.empty((2, H, W, 2), dtype=torch.float32, device=dev)
+    general = _capi.FarnebackParams(pyr_scale=0.8, levels=6)
+    # 2 x max_batch unique frames: the general path then needs exactly the extra bytes, so its work area IS allocated
+    assert _capi.farneback_extra_bytes(W, H, B, general) > 0
+    torch.cuda.synchronize(dev)
+    free0, _ = _capi.device_mem_info(0)
+    for life in range(3):
+        with _capi.Context(W, H, max_batch=B) as ctx:
+            assert ctx.frame_slots >= 18 and ctx.flow_slots >= 24
+            ctx.upload_frames_raw(0, small, (W, H))               # the ring's first buffers ...
+            ctx.upload_frames_raw(8, large, (W, H))               # ... and every one of them grown
+            ctx.upload_frames_device(16, dev_frames, "gray")
+            ctx.flow_pairs(list(range(8)), list(range(1, 9)), list(range(8)))           # two batch shapes: two graphs
+            ctx.flow_pairs([0, 1, 2], [1, 2, 3], [8, 9, 10])
+            ctx.flow_pairs_farneback(list(range(8)), list(range(8, 16)), list(range(11, 19)), params=general)
+            ctx.import_flows(fields, [19, 20])
+            ctx.export_flows([0, 1], exported)
+            pinned = ctx.pinned_frames(2)                         # never freed by the caller
+            pinned[:] = dev_frames.cpu().numpy()
+            ctx.upload_frames(16, list(pinned))
+            ctx.profile_enable(True)
+            ctx.flow_pairs([16], [17], [21])
+            assert len(ctx.pass1_results(list(range(22)))) == 22
+            ctx.profile_enable(False)
+            assert ctx.graph_stats()["capture_failures"] == 0
+            free_open, _ = _capi.device_mem_info(0)
+            assert free0 - free_open > 2 << 30, (free0, free_open)
+            del pinned
+        torch.cuda.synchronize(dev)
+        free1, _ = _capi.device_mem_info(0)
+        assert free1 >= free0 - (64 << 20), (life, free0, free1)
+
+
 def test_options_belong_to_a_context_not_to_the_process():
     """Two live contexts in one process (the shape of one process driving several GPUs): each keeps the option set it was
     created with, ffl_ctx_set_option changes ONE of them and makes only that one re-capture its graphs, "lanes" is fixed

@@ -541,6 +541,42 @@ def test_process_wide_option_defaults_without_a_device():
         _capi.set_option("blur_min_wgs", 3500)
 
 
+_ESTIMATE_BYTES = {  # (w, h, frame slots, flow slots, max_batch): ((device, pinned) at lanes 1, at lanes 2, at lanes 4)
+    (16, 16, 2, 1, 1): ((1081360, 1280024), (1110048, 1509400), (1167424, 1968152)),
+    (320, 180, 4, 15, 1): ((16888720, 2199912), (24895264, 2429288), (40908352, 2888040)),
+    (1001, 333, 10, 20, 4): ((256627048, 14611752), (445538920, 14841128), (823362664, 15299880)),
+    (256, 256, 514, 525, 256): ((2789261312, 136032568), (5167480832, 136261944), (9923919872, 136720696)),
+    (640, 360, 18, 29, 8): ((332368256, 17867448), (593646336, 18096824), (1116202496, 18555576)),
+    (1920, 1080, 66, 77, 32): ((11231805440, 548710200), (20637794304, 548939576), (39449772032, 549398328)),
+    (1920, 1080, 258, 256, 256): ((81635647488, 2141239296), (156883558400, 2141468672), (307379380224, 2141927424)),
+    (3840, 2160, 66, 77, 32): ((44924055040, 2191001400), (82547989504, 2191230776), (157795858432, 2191689528)),
+    (5760, 2880, 4, 15, 1): ((4608620896, 266699112), (6960116416, 266928488), (11663107456, 267387240)),
+}
+_FARNEBACK_EXTRA_BYTES = [  # (w, h, max_batch, parameters) -> device bytes at lanes 2
+    ((1920, 1080, 32, {"levels": 5}), 26112000),
+    ((1920, 1080, 32, {"pyr_scale": 0.8, "levels": 6}), 7045040640),
+    ((256, 256, 256, {"winsize": 63}), 0),
+    ((640, 360, 8, {"poly_n": 7, "pyr_scale": 0.75, "levels": 8}), 139128320),
+]
+
+
+def test_sizing_calls_return_the_pinned_byte_counts_without_a_device():
+    """ffl_estimate_bytes and ffl_farneback_extra_bytes need no device and are what callers size their contexts by (the
+    GPU suite only holds the estimate to 0.9 .. 1.02 of the measured allocation): the exact bytes, from the smallest legal
+    context to the largest, odd sizes and every lane count of interest.  The values are pinned: they change only together with
+    what ffl_create allocates."""
+    try:
+        for k, lanes in enumerate((1, 2, 4)):
+            _capi.set_option("lanes", lanes)
+            for args, want in _ESTIMATE_BYTES.items():
+                assert _capi.estimate_bytes(*args) == want[k], (args, lanes)
+        _capi.set_option("lanes", 2)
+        for (w, h, B, kw), want in _FARNEBACK_EXTRA_BYTES:
+            assert _capi.farneback_extra_bytes(w, h, B, _capi.FarnebackParams(**kw)) == want, (w, h, B, kw)
+    finally:
+        _capi.set_option("lanes", 2)
+
+
 def test_launcher_takes_its_ranks_down_when_it_is_terminated(tmp_path):
     """A driver that gives up on `bench.py --gpus N` sends the PARENT a SIGTERM: the rank processes must not outlive it
     (a rank left behind would keep a GPU and a rendezvous port busy for the next run)."""
