@@ -277,6 +277,11 @@ struct ffl_ctx {
         DevBuf<double> d_psum;
         // per-batch index tables: device copy + a ring of pinned host copies (entry e belongs to ring entry e)
         DevBuf<BatchTab> d_tab; PinBuf<BatchTab> h_tab;
+        // the frame-only work of every level on this lane's buffers, coarsest level first (the order of the merged
+        // launches): level k is entry geo.levels - k.  Filled once by ffl_create
+        PyrJob pyr[FFL_MAX_JOBS] = {};
+        PolyJob poly[FFL_MAX_JOBS] = {};
+        int n_jobs = 0;
         struct GraphEntry {
             int n, nU, pov, epoch;
             Graph graph;
@@ -750,6 +755,17 @@ int ffl_create(int device, int width, int height, int n_frame_slots, int n_flow_
         return set_err(nullptr, FFL_ERR_NO_DEVICE, "ffl_create: no HIP device available (this library has no CPU path)");
     if (device < 0 || device >= ndev)
         return set_err(nullptr, FFL_ERR_INVALID, "ffl_create: device %d out of range (0..%d)", device, ndev - 1);
+    // the level kernels serve what the reference's level rule yields for every accepted size; said here, where the
+    // geometry is fixed, should that rule ever change
+    Geometry geo;
+    level_geometry(width, height, &geo);
+    if (geo.levels + 1 > FFL_MAX_JOBS)
+        return set_err(nullptr, FFL_ERR_INVALID, "ffl_create: %d pyramid levels at %dx%d, the level tables hold %d", geo.levels + 1,
+                       width, height, FFL_MAX_JOBS);
+    for (int k = 0; k <= geo.levels; k++)
+        if (!ffl_pyr_level_ok(width, geo.lv[k].lw, geo.lv[k].ksize))
+            return set_err(nullptr, FFL_ERR_INVALID, "ffl_create: no pyramid kernel for level %d of %dx%d (%d columns, %d-tap blur)",
+                           k, width, height, geo.lv[k].lw, geo.lv[k].ksize);
     ffl_ctx *c = new ffl_ctx();
     c->device = device;
     c->w = width;
@@ -763,7 +779,7 @@ int ffl_create(int device, int width, int height, int n_frame_slots, int n_flow_
         c->opt = g_opts;
     }
     const int num_lanes = c->opt.lanes;  // fixed for the life of the context
-    level_geometry(width, height, &c->geo);
+    c->geo = geo;
     const Layout &lay = c->lay = context_layout(width, height, n_frame_slots, n_flow_slots, max_batch);
     polyexp_prepare(&c->pc);
     auto fail = [&](const char *what, hipError_t e) {  // works on a context that is built in part: null handles are no-ops
@@ -782,7 +798,7 @@ int ffl_create(int device, int width, int height, int n_frame_slots, int n_flow_
     CCHK(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
     CCHK(hipStreamCreateWithPriority(c->s_copy.put(), hipStreamNonBlocking, prio_greatest));
     CCHK(hipStreamCreateWithPriority(c->s_post.put(), hipStreamNonBlocking, prio_greatest));
-    ALLOC(hipMalloc, c->d_gray, lay.gray + 16);  // +16: k_pyr_h fetches taps as aligned words
+    ALLOC(hipMalloc, c->d_gray, lay.gray + 16);  // +16: the pyramid kernels fetch taps as aligned words
     ALLOC(hipMalloc, c->d_bgr, lay.bgr);
     ALLOC(hipHostMalloc, c->h_stage_gray, lay.gray, hipHostMallocDefault);
     ALLOC(hipHostMalloc, c->h_stage_bgr, lay.bgr, hipHostMallocDefault);
@@ -806,6 +822,20 @@ int ffl_create(int device, int width, int height, int n_frame_slots, int n_flow_
         ALLOC(hipMalloc, L.d_psum, lay.p1);
         ALLOC(hipMalloc, L.d_tab, 1);
         ALLOC(hipHostMalloc, L.h_tab, lay.tab, hipHostMallocDefault);
+        for (int k = geo.levels; k >= 0; k--, L.n_jobs++) {
+            const LevelGeom &g = geo.lv[k];
+            const size_t plane = (size_t)g.lw * g.lh;
+            PyrJob &P = L.pyr[L.n_jobs];
+            P.w = width; P.h = height; P.lw = g.lw; P.lh = g.lh;
+            P.sx = (double)width / g.lw; P.sy = (double)height / g.lh;
+            P.gk = g.gk;
+            P.tmp = L.d_T + lay.t_off[k]; P.tmp_stride = ffl_pyr_tmp_floats(width, height, g.lw);
+            P.I = L.d_I + lay.i_off[k]; P.I_stride = plane;
+            PolyJob &Q = L.poly[L.n_jobs];
+            Q.I = P.I; Q.I_stride = plane;
+            Q.R = L.d_R + lay.r_off[k]; Q.R_stride = 5 * plane; Q.plane = plane;
+            Q.w = g.lw; Q.h = g.lh;
+        }
     }
     ALLOC(hipMalloc, c->d_flow, lay.slots);
     ALLOC(hipHostMalloc, c->h_res, lay.res, hipHostMallocMapped);
@@ -1217,17 +1247,15 @@ static int enqueue_batch(ffl_ctx *c, ffl_ctx::Lane &L, const BatchTab &T, int n,
     const UTab *ut = &L.d_tab->ut;
     const PairTab *pt = &L.d_tab->pt;
     // frame-only expansion of level k (level image + PolyExp of the nU unique frames) on stream s
+    auto pyr_level = [&](int k, hipStream_t s) { ffl_launch_pyr_level(c->d_gray, N, ut, nU, L.pyr[c->geo.levels - k], s); };
     auto expand_level = [&](int k, hipStream_t s) {
-        const LevelGeom &g = c->geo.lv[k];
-        const size_t plane = (size_t)g.lw * g.lh;
         {
             ProfScope ps(c, FFL_K_PYRAMID, s);
-            ffl_launch_pyr_level(c->d_gray, N, ut, nU, c->w, c->h, g.lw, g.lh, g.gk, L.d_T + c->lay.t_off[k],
-                                 ffl_pyr_tmp_floats(c->w, c->h, g.lw), L.d_I + c->lay.i_off[k], plane, s);
+            pyr_level(k, s);
         }
         {
             ProfScope ps(c, FFL_K_POLYEXP, s);
-            ffl_launch_polyexp(L.d_I + c->lay.i_off[k], plane, L.d_R + c->lay.r_off[k], 5 * plane, plane, nU, g.lw, g.lh, c->pc, s);
+            ffl_launch_polyexp(L.poly[c->geo.levels - k], nU, c->pc, s);
         }
     };
     // Frame-only expansion schedule (ffl_set_option "run_ahead"):
@@ -1253,44 +1281,17 @@ static int enqueue_batch(ffl_ctx *c, ffl_ctx::Lane &L, const BatchTab &T, int n,
     }
     const bool run_ahead = mode == 1;
     bool expanded = mode != 0;
-    if (mode == 0 && c->opt.merge_expand && c->geo.levels + 1 <= FFL_MAX_JOBS) {
+    if (mode == 0 && c->opt.merge_expand) {
         // serial schedule, merged form: the frame-only work of ALL levels up front in three launches
         // (pyramid phase A + B, PolyExp) instead of ten small ones whose ramps and tails leave the device idle
-        PyrJob pj[FFL_MAX_JOBS];
-        PolyJob qj[FFL_MAX_JOBS];
-        int nj = 0;
-        for (int k = c->geo.levels; k >= 0; k--, nj++) {
-            const LevelGeom &g = c->geo.lv[k];
-            const size_t plane = (size_t)g.lw * g.lh;
-            memset(&pj[nj], 0, sizeof(PyrJob));
-            pj[nj].lw = g.lw;
-            pj[nj].lh = g.lh;
-            pj[nj].gk = g.gk;
-            pj[nj].tmp = L.d_T + c->lay.t_off[k];
-            pj[nj].tmp_stride = ffl_pyr_tmp_floats(c->w, c->h, g.lw);
-            pj[nj].I = L.d_I + c->lay.i_off[k];
-            pj[nj].I_stride = plane;
-            memset(&qj[nj], 0, sizeof(PolyJob));
-            qj[nj].I = L.d_I + c->lay.i_off[k];
-            qj[nj].I_stride = plane;
-            qj[nj].R = L.d_R + c->lay.r_off[k];
-            qj[nj].R_stride = 5 * plane;
-            qj[nj].plane = plane;
-            qj[nj].w = g.lw;
-            qj[nj].h = g.lh;
-        }
         {
             ProfScope ps(c, FFL_K_PYRAMID, st);
-            if (!ffl_launch_pyr_multi(c->d_gray, N, ut, nU, c->w, c->h, pj, nj, c->opt, st))
-                for (int k = c->geo.levels; k >= 0; k--) {  // a level outside the merged kinds: per-level kernels
-                    const LevelGeom &g = c->geo.lv[k];
-                    ffl_launch_pyr_level(c->d_gray, N, ut, nU, c->w, c->h, g.lw, g.lh, g.gk, L.d_T + c->lay.t_off[k],
-                                         ffl_pyr_tmp_floats(c->w, c->h, g.lw), L.d_I + c->lay.i_off[k], (size_t)g.lw * g.lh, st);
-                }
+            if (!ffl_launch_pyr_multi(c->d_gray, N, ut, nU, L.pyr, L.n_jobs, c->opt, st))
+                for (int k = c->geo.levels; k >= 0; k--) pyr_level(k, st);  // a level outside the merged kinds: per-level kernels
         }
         {
             ProfScope ps(c, FFL_K_POLYEXP, st);
-            ffl_launch_polyexp_multi(qj, nj, nU, c->pc, st);
+            ffl_launch_polyexp_multi(L.poly, L.n_jobs, nU, c->pc, st);
         }
         expanded = true;
     }

@@ -96,10 +96,10 @@ struct ImportArgs {
 // merged launches: one 1-D grid cut into per-job block ranges
 #define FFL_MAX_JOBS 4
 enum { FFL_PYR_F1 = 0, FFL_PYR_F2, FFL_PYR_H4, FFL_PYR_H9, FFL_PYR_V4, FFL_PYR_V9 };
-struct PyrJob {  // one level of the pyramid (caller fills lw, lh, gk, tmp, tmp_stride, I, I_stride)
+struct PyrJob {  // one level of the pyramid (caller fills w, h, lw, lh, sx, sy, gk, tmp, tmp_stride, I, I_stride)
     int kind, w, h, lw, lh;
     unsigned gx, gy, first, count;  // grid of one frame, first block of the job, tiles of the job (all frames)
-    double sx, sy;
+    double sx, sy;                  // (double)w / lw, (double)h / lh
     float *tmp, *I;
     size_t tmp_stride, I_stride;
     GaussKernel gk;
@@ -140,8 +140,8 @@ struct FflOptions {
 
 // ---- launchers (each enqueues on `st` and returns; no synchronisation) ----------------------
 // all pyramid levels in two launches; false (nothing launched) when a level needs the generic kernels
-bool ffl_launch_pyr_multi(const uint8_t *gray_base, size_t gray_stride, const UTab *ut, int nU, int w, int h, const PyrJob *levels,
-                          int n, const FflOptions &opt, hipStream_t st);
+bool ffl_launch_pyr_multi(const uint8_t *gray_base, size_t gray_stride, const UTab *ut, int nU, const PyrJob *levels, int n,
+                          const FflOptions &opt, hipStream_t st);
 void ffl_launch_polyexp_multi(const PolyJob *levels, int n, int nU, PolyConsts pc, hipStream_t st);
 // host paths: one frame, its descriptor a kernel argument; device path: n frames, descriptors tab[0..n) in device memory
 void ffl_launch_frontend(const FrameDesc &d, uint8_t *gray, const FrontParams &p, hipStream_t st);
@@ -155,10 +155,11 @@ void ffl_launch_import_pass1(const ImportArgs &a, const ExportTab &tab, int n, i
                              int fused, PairTab *pt, unsigned long long *pkey, double *psum, hipStream_t st);
 void ffl_launch_gray(const uint8_t *bgr, uint8_t *gray, int n_pixels, hipStream_t st);
 size_t ffl_pyr_tmp_floats(int w, int h, int lw);  // per-frame size of the level's horizontal-pass buffer
-void ffl_launch_pyr_level(const uint8_t *gray_base, size_t gray_stride, const UTab *ut, int nU, int w, int h, int lw, int lh,
-                          GaussKernel gk, float *tmp, size_t tmp_stride, float *I, size_t I_stride, hipStream_t st);
-void ffl_launch_polyexp(const float *I, size_t I_stride, float *R, size_t R_stride, size_t plane, int nU, int lw,
-                        int lh, PolyConsts pc, hipStream_t st);
+// one level on its own; ffl_pyr_level_ok: the level has one of the forms this serves (checked by ffl_create)
+bool ffl_pyr_level_ok(int w, int lw, int ksize);
+void ffl_launch_pyr_level(const uint8_t *gray_base, size_t gray_stride, const UTab *ut, int nU, const PyrJob &level,
+                          hipStream_t st);
+void ffl_launch_polyexp(const PolyJob &level, int nU, PolyConsts pc, hipStream_t st);
 // pw > 0: the level's initial flow = x2 bilinear upsample of pt.prev (pw x ph), used from registers (and written
 // to pt.flow only when store_flow != 0: nothing but the debug capture reads it);
 // pw == 0: the flow is read from pt.flow, or taken as zero without touching memory when zero_flow != 0

@@ -88,152 +88,19 @@ __device__ __forceinline__ void ffl_resize_coord_half(int d, int src, int &i0, i
     f = fx;
 }
 
-// Two plain streaming kernels per level, no LDS and no barriers (the earlier LDS-tiled version spent
-// its time in four dependent phases per workgroup and never filled the device at the coarse levels):
-//   k_pyr_h  one lane per (row y, output column d, lerp side q): horizontal blur of the full-resolution
-//            row at the sampled column -> tmp[y][d][q]            (float, symmetric form, REFLECT_101)
-//   k_pyr_v  one lane per output pixel: vertical blur of tmp at the (<= 2) sampled rows for the
-//            (<= 2) sampled columns, then the two lerps -> I
-// Samples whose lerp weight is exactly 0 are not evaluated: v*1 + s*0 == v for finite s >= 0.
-// R > 0: blur radius known at compile time (taps unrolled, coefficients in scalar registers);
-// R == 0: runtime radius.  nq = 2 when the level resamples in x (lw != w), else 1.
-// rows per lane of k_pyr_h: enough loads in flight to cover the memory latency without spilling
-// (a row costs 2R+1 byte loads)
+// Levels the fused and one-pass kernels below do not cover run as two plain streaming kernels, no LDS and no barriers
+// (the earlier LDS-tiled version spent its time in four dependent phases per workgroup and never filled the device at
+// the coarse levels).  All such levels resample in x (lw != w) and have a compile-time blur radius R:
+//   k_pyr_h2  one lane per (row y, output column d): horizontal blur of the full-resolution row at BOTH sampled
+//             columns (their 2R+2 source bytes overlap: one set of word loads) -> tmp[y][d][2], one 8-byte store
+//             (float, symmetric form, REFLECT_101; taps unrolled, coefficients in scalar registers)
+//   k_pyr_v2  one lane per output pixel: vertical blur of tmp at the (<= 2) sampled rows, whose 2R+2 distinct rows are
+//             fetched once, 8 bytes (both sides) per load, then the two lerps -> I
+// -- 10 / 20 loads per output pixel at R = 4 / 9 instead of the 36 / 76 of one lane per sample.  Samples whose lerp
+// weight is exactly 0 are not evaluated: v*1 + s*0 == v for finite s >= 0.  Lanes at the image border take the
+// per-sample form with reflected taps.
+// rows per lane of k_pyr_h2: enough loads in flight to cover the memory latency without spilling
 constexpr int ffl_pyr_rows(int R) { return R == 1 ? 16 : (R == 4 ? 8 : 4); }
-constexpr int ffl_pyr_vrows(int R) { return R == 1 ? 4 : 1; }  // output rows per lane of k_pyr_v
-template <int R>
-__global__ __launch_bounds__(256) void k_pyr_h(const uint8_t *__restrict__ gray_base, size_t gray_stride, const UTab *__restrict__ ut, int w,
-                                               int h, int lw, int nq, double sx, GaussKernel gk,
-                                               float *__restrict__ tmp, size_t tmp_stride) {
-    // each lane produces ROWS rows of its column (one workgroup per 256 outputs would be bound by the
-    // workgroup dispatch rate, not by memory)
-    constexpr int ROWS = ffl_pyr_rows(R);
-    const int i = blockIdx.x * 256 + threadIdx.x, u = blockIdx.z;
-    if (i >= lw * nq) return;
-    const int d = nq == 2 ? i >> 1 : i, q = nq == 2 ? (i & 1) : 0;
-    const int r = R > 0 ? R : (gk.ksize >> 1);
-    int x0, x1;
-    float fx;
-    ffl_resize_coord(d, w, sx, x0, x1, fx);
-    const bool on = q == 0 || fx != 0.f;
-    const int cx = q ? x1 : x0;
-    const bool interior = cx >= r && cx + r < w;
-    int xm[R > 0 ? R : 1], xp[R > 0 ? R : 1];  // reflected tap columns (border lanes, compile-time radius)
-    if (R > 0) {
-#pragma unroll
-        for (int t = 1; t <= R; t++) {
-            xm[t - 1] = ffl_reflect101(cx - t, w);
-            xp[t - 1] = ffl_reflect101(cx + t, w);
-        }
-    }
-    const uint8_t *img = gray_base + (size_t)ut->fslot[u] * gray_stride;
-    float *out = tmp + (size_t)u * tmp_stride + i;
-    const int ybase = blockIdx.y * ROWS;
-    // word-wise tap fetch needs 4-byte aligned rows (w % 4 == 0; frame slots are w*h apart) and all
-    // taps inside the row; the last word may reach <= 3 bytes past the taps, still inside the slot array
-    // (the gray buffer is allocated with 16 bytes of slack)
-    const int wfirst = cx - r, woff = wfirst & 3, wbase = wfirst - woff;
-    const bool wide = R > 0 && interior && (w & 3) == 0;
-    // fixed trip count, rows clamped for the loads and predicated for the store: the loop unrolls and
-    // the loads of all rows are in flight together (a rolled loop pays one memory latency per row)
-#pragma unroll
-    for (int k = 0; k < ROWS; k++) {
-        const int y = min(ybase + k, h - 1);
-        float acc = 0.f;
-        if (on) {
-            const uint8_t *row = img + (size_t)y * w;
-            if (R > 0 && wide) {
-                // interior lane: the 2R+1 taps sit in NW aligned 32-bit words -> NW loads instead of
-                // 2R+1 byte loads (the texture-address unit is paid per wave-instruction, not per byte),
-                // re-aligned with v_alignbyte, bytes converted with v_cvt_f32_ubyteN
-                constexpr int NW = (3 + 2 * R + 1 + 3) / 4;
-                const uint32_t *wp = reinterpret_cast<const uint32_t *>(row + wbase);
-                uint32_t wd[NW], a[NW];
-#pragma unroll
-                for (int q2 = 0; q2 < NW; q2++) wd[q2] = wp[q2];
-#pragma unroll
-                for (int q2 = 0; q2 < NW; q2++)
-                    a[q2] = q2 + 1 < NW ? __builtin_amdgcn_alignbyte(wd[q2 + 1], wd[q2], woff) : wd[q2] >> (8 * woff);
-                auto tap = [&](int j) { return (float)((a[j >> 2] >> (8 * (j & 3))) & 255u); };
-                acc = gk.k[R] * tap(R);
-#pragma unroll
-                for (int t = 1; t <= R; t++) acc = acc + gk.k[R + t] * (tap(R - t) + tap(R + t));
-            } else if (R > 0) {
-                acc = gk.k[r] * (float)row[cx];
-#pragma unroll
-                for (int t = 1; t <= R; t++) acc = acc + gk.k[R + t] * ((float)row[xm[t - 1]] + (float)row[xp[t - 1]]);
-            } else if (interior) {
-                acc = gk.k[r] * (float)row[cx];
-                for (int t = 1; t <= r; t++) acc = acc + gk.k[r + t] * ((float)row[cx - t] + (float)row[cx + t]);
-            } else {
-                acc = gk.k[r] * (float)row[cx];
-                for (int t = 1; t <= r; t++)
-                    acc = acc + gk.k[r + t] * ((float)row[ffl_reflect101(cx - t, w)] + (float)row[ffl_reflect101(cx + t, w)]);
-            }
-        }
-        if (ybase + k < h) out[(size_t)y * lw * nq] = acc;
-    }
-}
-
-template <int R>
-__global__ __launch_bounds__(256) void k_pyr_v(const float *__restrict__ tmp, size_t tmp_stride, int w, int h, int lw,
-                                               int lh, int nq, double sx, double sy, GaussKernel gk,
-                                               float *__restrict__ I, size_t I_stride) {
-    const int dx = blockIdx.x * 64 + (threadIdx.x & 63), u = blockIdx.z;
-    if (dx >= lw) return;
-    const int r = R > 0 ? R : (gk.ksize >> 1);
-    int x0, x1;
-    float a1;
-    ffl_resize_coord(dx, w, sx, x0, x1, a1);
-    const float a0 = 1.f - a1;
-    const size_t pitch = (size_t)lw * nq;
-    const float *col = tmp + (size_t)u * tmp_stride + (size_t)dx * nq;  // [row * pitch + q]
-    // 64 x (4 * ROWS) outputs per workgroup; fixed trip count + clamped rows so that the loop unrolls
-    // and every row's loads are in flight together
-    constexpr int ROWS = ffl_pyr_vrows(R);
-#pragma unroll
-    for (int k = 0; k < ROWS; k++) {
-    const int dyy = blockIdx.y * (4 * ROWS) + (threadIdx.x >> 6) + 4 * k;
-    const int dy = min(dyy, lh - 1);
-    int y0, y1;
-    float b1;
-    ffl_resize_coord(dy, h, sy, y0, y1, b1);
-    const float b0 = 1.f - b1;
-    float t[2] = {0.f, 0.f};
-#pragma unroll
-    for (int qy = 0; qy < 2; qy++) {
-        if (qy == 1 && b1 == 0.f) break;
-        const int cy = qy ? y1 : y0;
-        const bool interior = cy >= r && cy + r < h;
-        float v[2] = {0.f, 0.f};
-#pragma unroll
-        for (int q = 0; q < 2; q++) {
-            if (q == 1 && a1 == 0.f) break;
-            const float *p = col + q;
-            float acc = gk.k[r] * p[(size_t)cy * pitch];
-            if (interior) {
-#pragma unroll
-                for (int j = 1; j <= r; j++)
-                    acc = acc + gk.k[r + j] * (p[(size_t)(cy - j) * pitch] + p[(size_t)(cy + j) * pitch]);
-            } else {
-#pragma unroll
-                for (int j = 1; j <= r; j++)
-                    acc = acc + gk.k[r + j] * (p[(size_t)ffl_reflect101(cy - j, h) * pitch] +
-                                               p[(size_t)ffl_reflect101(cy + j, h) * pitch]);
-            }
-            v[q] = acc;
-        }
-        t[qy] = v[0] * a0 + v[1] * a1;
-    }
-    if (dyy < lh) I[(size_t)u * I_stride + (size_t)dy * lw + dx] = t[0] * b0 + t[1] * b1;
-    }
-}
-
-// Resampling levels (nq == 2), compile-time radius: one lane computes BOTH lerp sides of an output
-// column in k_pyr_h2 (their 2R+2 source bytes overlap: one set of word loads, one 8-byte store), and
-// k_pyr_v2 fetches the 2R+2 distinct rows its two vertical sums share once, 8 bytes (both sides) per
-// load -- 10 / 20 loads per output pixel at R = 4 / 9 instead of 36 / 76.  Same operations in the same
-// order as k_pyr_h / k_pyr_v; lanes at the image border fall back to the per-sample form.
 template <int R>
 __device__ __forceinline__ void k_pyr_h2_body(const unsigned bx, const unsigned by, const unsigned bz, const uint8_t *__restrict__ gray_base, size_t gray_stride, const UTab *__restrict__ ut, int w,
                                                 int h, int lw, double sx, GaussKernel gk, float *__restrict__ tmp,
@@ -245,7 +112,9 @@ __device__ __forceinline__ void k_pyr_h2_body(const unsigned bx, const unsigned 
     float fx;
     ffl_resize_coord(d, w, sx, x0, x1, fx);
     const bool on1 = fx != 0.f;
-    // both samples from one run of aligned words: taps x0-R .. x0+R+1 inside the row, x1 == x0 + 1
+    // both samples from one run of aligned words: taps x0-R .. x0+R+1 inside the row, x1 == x0 + 1.  The word-wise
+    // fetch needs 4-byte aligned rows (w % 4 == 0; frame slots are w*h apart); the last word may reach <= 3 bytes past
+    // the taps, still inside the slot array (the gray buffer is allocated with 16 bytes of slack)
     const bool wide = x1 == x0 + 1 && x0 >= R && x1 + R < w && (w & 3) == 0;
     const int wfirst = x0 - R, woff = wfirst & 3, wbase = wfirst - woff;
     int xm[2][R], xp[2][R];
@@ -265,6 +134,9 @@ __device__ __forceinline__ void k_pyr_h2_body(const unsigned bx, const unsigned 
         const uint8_t *row = img + (size_t)y * w;
         float acc0, acc1 = 0.f;
         if (wide) {
+            // the 2R+2 taps sit in NW aligned 32-bit words -> NW loads instead of 2R+2 byte loads (the texture-address
+            // unit is paid per wave-instruction, not per byte), re-aligned with v_alignbyte, bytes converted with
+            // v_cvt_f32_ubyteN
             constexpr int NW = (3 + 2 * R + 2 + 3) / 4;
             const uint32_t *wp = reinterpret_cast<const uint32_t *>(row + wbase);
             uint32_t wd[NW], a[NW];
@@ -364,7 +236,7 @@ __global__ __launch_bounds__(256) void k_pyr_v2(const float *__restrict__ tmp, s
 // (level 0) or S = 2 (level 1) decimation.  One lane produces FROWS consecutive output rows of one
 // output column: the S*FROWS + 2 source rows are fetched word-wise once, blurred horizontally in
 // registers, then combined vertically -- no intermediate plane, same operations in the same order as
-// k_pyr_h + k_pyr_v (for S = 2 the lerp weights are exactly 0.5, for S = 1 the lerps are identities).
+// k_pyr_h2 + k_pyr_v2 (for S = 2 the lerp weights are exactly 0.5, for S = 1 the lerps are identities).
 #define FFL_PYR_FROWS 4
 #ifndef FFL_FR1
 #define FFL_FR1 8  // output rows per lane of the fused 3-tap kernels, level 0 / level 1 (33 x 1080p frames: 4/2 136 us,
@@ -716,9 +588,9 @@ static int ffl_pyr_kind(int w, int h, int lw, int lh, int ksize) {
 }
 
 // (running the coarse kernel on a side stream beside the fine levels was tried: 5595 vs 5606 pairs/s, not kept)
-bool ffl_launch_pyr_multi(const uint8_t *gray_base, size_t gray_stride, const UTab *__restrict__ ut, int nU, int w, int h, const PyrJob *lv,
-                          int n, const FflOptions &opt, hipStream_t st) {
-    if (n > FFL_MAX_JOBS) return false;
+bool ffl_launch_pyr_multi(const uint8_t *gray_base, size_t gray_stride, const UTab *__restrict__ ut, int nU, const PyrJob *lv, int n,
+                          const FflOptions &opt, hipStream_t st) {
+    const int w = lv[0].w, h = lv[0].h;
     PyrJobs A = {}, B = {};
     unsigned ta = 0, tb = 0;
     for (int i = 0; i < n; i++)
@@ -737,10 +609,6 @@ bool ffl_launch_pyr_multi(const uint8_t *gray_base, size_t gray_stride, const UT
         if (i == skip0 || i == skip1) continue;
         const int kind = ffl_pyr_kind(w, h, lv[i].lw, lv[i].lh, lv[i].gk.ksize);
         PyrJob J = lv[i];
-        J.w = w;
-        J.h = h;
-        J.sx = (double)w / J.lw;
-        J.sy = (double)h / J.lh;
         J.kind = kind;
         if (kind == FFL_PYR_F1 || kind == FFL_PYR_F2) {
             const int fr = kind == FFL_PYR_F1 ? FFL_FR1 : FFL_FR2;
@@ -769,59 +637,55 @@ bool ffl_launch_pyr_multi(const uint8_t *gray_base, size_t gray_stride, const UT
     return true;
 }
 
-void ffl_launch_pyr_level(const uint8_t *gray_base, size_t gray_stride, const UTab *__restrict__ ut, int nU, int w, int h, int lw, int lh,
-                          GaussKernel gk, float *tmp, size_t tmp_stride, float *I, size_t I_stride, hipStream_t st) {
-    const int r = gk.ksize / 2, nq = lw != w ? 2 : 1;
-    const double sx = (double)w / lw, sy = (double)h / lh;
-    if (r == 1 && ((lw == w && lh == h) || (w == 2 * lw && h == 2 * lh)) && (lw & 3) == 0 && (w & 3) == 0) {
+// H + V kernel pair of a resampling level with blur radius R
+template <int R>
+static void ffl_launch_pyr_hv(const uint8_t *gray_base, size_t gray_stride, const UTab *ut, int nU, const PyrJob &J,
+                              hipStream_t st) {
+    dim3 gh((J.lw + 255) / 256, (J.h + ffl_pyr_rows(R) - 1) / ffl_pyr_rows(R), nU), gv((J.lw + 63) / 64, (J.lh + 3) / 4, nU);
+    hipLaunchKernelGGL(k_pyr_h2<R>, gh, dim3(256), 0, st, gray_base, gray_stride, ut, J.w, J.h, J.lw, J.sx, J.gk, J.tmp,
+                       J.tmp_stride);
+    hipLaunchKernelGGL(k_pyr_v2<R>, gv, dim3(256), 0, st, J.tmp, J.tmp_stride, J.w, J.h, J.lw, J.lh, J.sx, J.sy, J.gk, J.I,
+                       J.I_stride);
+}
+
+// The forms ffl_launch_pyr_level serves: a 3-tap blur, or a 9- / 19-tap blur on a level that resamples in x.  The level
+// rule of the reference yields nothing else (ksize 3, 3, 9, 19 for levels 0..3, and levels 2, 3 only exist for
+// w, h >= 128, where lw != w); ffl_create checks it where the geometry is fixed.
+bool ffl_pyr_level_ok(int w, int lw, int ksize) {
+    const int r = ksize / 2;
+    return r == 1 || ((r == 4 || r == 9) && lw != w);
+}
+
+void ffl_launch_pyr_level(const uint8_t *gray_base, size_t gray_stride, const UTab *ut, int nU, const PyrJob &J,
+                          hipStream_t st) {
+    const int w = J.w, h = J.h, lw = J.lw, lh = J.lh, r = J.gk.ksize / 2;
+    const bool exact1 = lw == w && lh == h, exact2 = w == 2 * lw && h == 2 * lh;
+    if (r == 1 && (exact1 || exact2) && (lw & 3) == 0 && (w & 3) == 0) {
         constexpr int FR1 = FFL_FR1, FR2 = FFL_FR2;  // output rows per lane
-        if (lw == w) {
+        if (exact1) {
             dim3 grid((lw / 4 + 255) / 256, (lh + FR1 - 1) / FR1, nU);
             hipLaunchKernelGGL((k_pyr_fused3x4<1, FR1>), grid, dim3(256), 0, st, gray_base, gray_stride, ut, w, h, lw, lh,
-                               gk, I, I_stride);
+                               J.gk, J.I, J.I_stride);
         } else {
             dim3 grid((lw / 4 + 255) / 256, (lh + FR2 - 1) / FR2, nU);
             hipLaunchKernelGGL((k_pyr_fused3x4<2, FR2>), grid, dim3(256), 0, st, gray_base, gray_stride, ut, w, h, lw, lh,
-                               gk, I, I_stride);
+                               J.gk, J.I, J.I_stride);
         }
-        return;
-    }
-    if (r == 1 && ((lw == w && lh == h) || (w == 2 * lw && h == 2 * lh))) {
+    } else if (r == 1 && (exact1 || exact2)) {
         dim3 grid((lw + 255) / 256, (lh + FFL_PYR_FROWS - 1) / FFL_PYR_FROWS, nU);
-        if (lw == w)
-            hipLaunchKernelGGL(k_pyr_fused3<1>, grid, dim3(256), 0, st, gray_base, gray_stride, ut, w, h, lw, lh, gk, I,
-                               I_stride);
+        if (exact1)
+            hipLaunchKernelGGL(k_pyr_fused3<1>, grid, dim3(256), 0, st, gray_base, gray_stride, ut, w, h, lw, lh, J.gk, J.I,
+                               J.I_stride);
         else
-            hipLaunchKernelGGL(k_pyr_fused3<2>, grid, dim3(256), 0, st, gray_base, gray_stride, ut, w, h, lw, lh, gk, I,
-                               I_stride);
-        return;
+            hipLaunchKernelGGL(k_pyr_fused3<2>, grid, dim3(256), 0, st, gray_base, gray_stride, ut, w, h, lw, lh, J.gk, J.I,
+                               J.I_stride);
+    } else if (r == 1) {  // level 1 of a frame with an odd width or height
+        ffl_launch_pyr_hv<1>(gray_base, gray_stride, ut, nU, J, st);
+    } else if (r == 4) {
+        ffl_launch_pyr_hv<4>(gray_base, gray_stride, ut, nU, J, st);
+    } else {
+        ffl_launch_pyr_hv<9>(gray_base, gray_stride, ut, nU, J, st);
     }
-#define FFL_PYR_LAUNCH2(RR)                                                                                         \
-    do {                                                                                                            \
-        dim3 gv((lw + 63) / 64, (lh + 3) / 4, nU);                                                                  \
-        dim3 gh((lw + 255) / 256, (h + ffl_pyr_rows(RR) - 1) / ffl_pyr_rows(RR), nU);                               \
-        hipLaunchKernelGGL(k_pyr_h2<RR>, gh, dim3(256), 0, st, gray_base, gray_stride, ut, w, h, lw, sx, gk, tmp,   \
-                           tmp_stride);                                                                             \
-        hipLaunchKernelGGL(k_pyr_v2<RR>, gv, dim3(256), 0, st, tmp, tmp_stride, w, h, lw, lh, sx, sy, gk, I,        \
-                           I_stride);                                                                               \
-    } while (0)
-    if (nq == 2 && r == 4) { FFL_PYR_LAUNCH2(4); return; }
-    if (nq == 2 && r == 9) { FFL_PYR_LAUNCH2(9); return; }
-#undef FFL_PYR_LAUNCH2
-#define FFL_PYR_LAUNCH(RR)                                                                                          \
-    do {                                                                                                            \
-        dim3 gv((lw + 63) / 64, (lh + 4 * ffl_pyr_vrows(RR) - 1) / (4 * ffl_pyr_vrows(RR)), nU);                    \
-        dim3 gh((lw * nq + 255) / 256, (h + ffl_pyr_rows(RR) - 1) / ffl_pyr_rows(RR), nU);                          \
-        hipLaunchKernelGGL(k_pyr_h<RR>, gh, dim3(256), 0, st, gray_base, gray_stride, ut, w, h, lw, nq, sx, gk, tmp, \
-                           tmp_stride);                                                                             \
-        hipLaunchKernelGGL(k_pyr_v<RR>, gv, dim3(256), 0, st, tmp, tmp_stride, w, h, lw, lh, nq, sx, sy, gk, I,      \
-                           I_stride);                                                                               \
-    } while (0)
-    if (r == 1) FFL_PYR_LAUNCH(1);
-    else if (r == 4) FFL_PYR_LAUNCH(4);
-    else if (r == 9) FFL_PYR_LAUNCH(9);
-    else FFL_PYR_LAUNCH(0);
-#undef FFL_PYR_LAUNCH
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1015,10 +879,9 @@ void ffl_launch_polyexp_multi(const PolyJob *jobs_in, int n, int nU, PolyConsts 
     hipLaunchKernelGGL(k_polyexp_multi, dim3(total), dim3(256), 0, st, jobs, pc);
 }
 
-void ffl_launch_polyexp(const float *I, size_t I_stride, float *R, size_t R_stride, size_t plane, int nU, int lw,
-                        int lh, PolyConsts pc, hipStream_t st) {
-    dim3 grid((lw + PE_TW - 1) / PE_TW, (lh + PE_TH - 1) / PE_TH, nU);
-    hipLaunchKernelGGL(k_polyexp, grid, dim3(256), 0, st, I, I_stride, R, R_stride, plane, lw, lh, pc);
+void ffl_launch_polyexp(const PolyJob &J, int nU, PolyConsts pc, hipStream_t st) {
+    dim3 grid((J.w + PE_TW - 1) / PE_TW, (J.h + PE_TH - 1) / PE_TH, nU);
+    hipLaunchKernelGGL(k_polyexp, grid, dim3(256), 0, st, J.I, J.I_stride, J.R, J.R_stride, J.plane, J.w, J.h, pc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1028,76 +891,36 @@ void ffl_launch_polyexp(const float *I, size_t I_stride, float *R, size_t R_stri
 // in XCD-aware panel order: the R1 rows y1, y1+1 gathered by vertically adjacent tiles are re-read
 // from L2.  usx / usy = (double)pw / w, (double)ph / h.
 // ------------------------------------------------------------------------------------------------
-// MODE 0: the flow field is read; 1: it is formed here (x2 upsample of the coarser level) and written; 2: it is
-// zero (coarsest level) and neither read nor written -- k_blur_solve overwrites it without reading it
-template <int MODE>
-__global__ __launch_bounds__(256) void k_update_matrices(const float *__restrict__ R, size_t R_stride, size_t plane,
-                                                         const PairTab *__restrict__ pt, int level,
-                                                         float *__restrict__ M, size_t M_stride, int w,
-                                                         int h, int pw, int ph, double usx, double usy, int store_flow,
-                                                         int nB, int order) {
-    // One pixel per lane, lanes along x (a wave = one 64-pixel tile row; wave q takes rows q, q+4, q+8, q+12), as the
-    // fused update of k_blur_solve: all four rows' flow vectors first, then R0 + the R1 corners of the lane's NEXT row
-    // are requested before the current row's arithmetic.  Dword loads for R0 / R1, 16-byte loads for the coarse flow
-    // (a wave64 8-byte load costs the vector-memory path three dword loads: profiles/tools/micro/vmem_issue.hip).
-    int b, tile_x, tile_y;
-    if (!ffl_tile_coord((w + 63) / 64, (h + 15) / 16, nB, order, b, tile_x, tile_y)) return;
-    const int lx = threadIdx.x & 63, x0 = tile_x * 64, x = min(x0 + lx, w - 1);
-    const bool xin = x0 + lx < w;
-    const float *R0 = R + (size_t)pt->u0[b] * R_stride, *R1 = R + (size_t)pt->u1[b] * R_stride;
-    float *flow = pt->flow[level][b];
-    const float *pf = pt->flow[min(level + 1, FFL_MAX_LEVELS - 1)][b];
-    float *Mb = M + (size_t)b * M_stride;
-    constexpr int NR = 4;
-    int yr[NR];
-#pragma unroll
-    for (int k = 0; k < NR; k++) yr[k] = tile_y * 16 + (threadIdx.x >> 6) + 4 * k;
-    float2 f[NR];
-    if (MODE == 1) {
-        const bool half_scale = usx == 0.5 && usy == 0.5;
-        int xa0, xa1;
-        float a1;
-        if (half_scale) ffl_resize_coord_half(x, pw, xa0, xa1, a1);
-        else ffl_resize_coord(x, pw, usx, xa0, xa1, a1);
-        const int xq = min(xa0, pw - 2);   // columns xq, xq + 1 lie inside the row; xa0 and xa1 are each one of them
-        const bool first0 = xa0 == xq, first1 = xa1 == xq;
-        const float a0 = 1.f - a1;
-        float4 c0[NR], c1[NR];
-        float b1[NR];
-#pragma unroll
-        for (int k = 0; k < NR; k++) {
-            int ya0, ya1;
-            const int y = min(yr[k], h - 1);
-            if (half_scale) ffl_resize_coord_half(y, ph, ya0, ya1, b1[k]);
-            else ffl_resize_coord(y, ph, usy, ya0, ya1, b1[k]);
-            c0[k] = ffl_gload4(pf, 8u * ((unsigned)ya0 * (unsigned)pw + xq));
-            c1[k] = ffl_gload4(pf, 8u * ((unsigned)ya1 * (unsigned)pw + xq));
-        }
-#pragma unroll
-        for (int k = 0; k < NR; k++) {
-            const float b0 = 1.f - b1[k];
-            const float2 p00 = first0 ? make_float2(c0[k].x, c0[k].y) : make_float2(c0[k].z, c0[k].w);
-            const float2 p01 = first1 ? make_float2(c0[k].x, c0[k].y) : make_float2(c0[k].z, c0[k].w);
-            const float2 p10 = first0 ? make_float2(c1[k].x, c1[k].y) : make_float2(c1[k].z, c1[k].w);
-            const float2 p11 = first1 ? make_float2(c1[k].x, c1[k].y) : make_float2(c1[k].z, c1[k].w);
-            float t0 = p00.x * a0 + p01.x * a1, t1 = p10.x * a0 + p11.x * a1;
-            f[k].x = (t0 * b0 + t1 * b1[k]) * 2.0f;
-            t0 = p00.y * a0 + p01.y * a1;
-            t1 = p10.y * a0 + p11.y * a1;
-            f[k].y = (t0 * b0 + t1 * b1[k]) * 2.0f;
-        }
-    } else if (MODE == 0) {
-#pragma unroll
-        for (int k = 0; k < NR; k++) {
-            const unsigned o = (unsigned)min(yr[k], h - 1) * (unsigned)w + (unsigned)x;
-            const FFL_GLOBAL float *q = (const FFL_GLOBAL float *)flow + 2u * o;
-            f[k] = make_float2(q[0], q[1]);
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < NR; k++) f[k] = make_float2(0.f, 0.f);
-    }
+// K3 for one pixel: the x2 upsample of the coarser level's flow.  c0 / c1 hold columns xq, xq + 1 of the coarse rows
+// ya0 / ya1; first0 / first1 say whether the lerp's column xa0 / xa1 is the first of the two; a1, b1 are the lerp weights.
+__device__ __forceinline__ float2 ffl_upsample2(const float4 c0, const float4 c1, bool first0, bool first1, float a1, float b1) {
+    const float a0 = 1.f - a1, b0 = 1.f - b1;
+    const float2 p00 = first0 ? make_float2(c0.x, c0.y) : make_float2(c0.z, c0.w);
+    const float2 p01 = first1 ? make_float2(c0.x, c0.y) : make_float2(c0.z, c0.w);
+    const float2 p10 = first0 ? make_float2(c1.x, c1.y) : make_float2(c1.z, c1.w);
+    const float2 p11 = first1 ? make_float2(c1.x, c1.y) : make_float2(c1.z, c1.w);
+    float2 f;
+    float t0 = p00.x * a0 + p01.x * a1, t1 = p10.x * a0 + p11.x * a1;
+    f.x = (t0 * b0 + t1 * b1) * 2.0f;
+    t0 = p00.y * a0 + p01.y * a1;
+    t1 = p10.y * a0 + p11.y * a1;
+    f.y = (t0 * b0 + t1 * b1) * 2.0f;
+    return f;
+}
+
+// The UpdateMatrices row pipeline of the standalone kernel and of k_blur_solve's fused update: one pixel per lane,
+// lanes along x (a wave = one 64-pixel tile row), the lane's NR rows ybase, ybase + 4, ..., double-buffered: R0 and the
+// R1 corners of the lane's NEXT row are requested before the current row's arithmetic, so only the first of the NR
+// round trips is exposed.  Dword loads for R0 / R1 (a wave64 8-byte load costs the vector-memory path three dword loads:
+// profiles/tools/micro/vmem_issue.hip).  No divergent branch touches a loaded value (ffl_um_finish uses selects), so the
+// waits are "all but the next row's 25", never "all".
+//   disp(k)      displacement of the lane's pixel in row ybase + 4k
+//   keep(o, f)   called for pixels inside the image with their plane offset and displacement, before M is written
+template <int NR, typename Disp, typename Keep>
+__device__ __forceinline__ void ffl_um_rows(const float *R0, const float *R1, float *M, size_t plane, int w, int h, int x,
+                                            bool xin, int ybase, Disp disp, Keep keep) {
     struct UmRow {
+        float2 f;
         float a00, a01, a10, a11;
         bool inside;
         float r0[5];
@@ -1105,12 +928,14 @@ __global__ __launch_bounds__(256) void k_update_matrices(const float *__restrict
     };
     auto issue = [&](int k) {
         UmRow S;
-        const int y = min(yr[k], h - 1);
+        const int y = min(ybase + 4 * k, h - 1);
+        S.f = disp(k);
         const unsigned o = (unsigned)y * (unsigned)w + (unsigned)x;
 #pragma unroll
         for (int c = 0; c < 5; c++) S.r0[c] = *ffl_at<float>(R0 + c * plane, o);
-        const UmLoc L = ffl_um_locate(w, h, x, y, f[k].x, f[k].y);
+        const UmLoc L = ffl_um_locate(w, h, x, y, S.f.x, S.f.y);
         S.a00 = L.a00; S.a01 = L.a01; S.a10 = L.a10; S.a11 = L.a11; S.inside = L.inside;
+        // branch-free gather: lanes that land outside read the (valid) corner of pixel (0, 0) and drop it
         const unsigned o1 = L.inside ? (unsigned)L.y1 * (unsigned)w + (unsigned)L.x1 : 0u;
 #pragma unroll
         for (int c = 0; c < 5; c++) {
@@ -1124,26 +949,83 @@ __global__ __launch_bounds__(256) void k_update_matrices(const float *__restrict
     for (int k = 0; k < NR; k++) {
         UmRow nxt;
         if (k + 1 < NR) nxt = issue(k + 1);
-        const bool in = xin && yr[k] < h;
-        const int y = min(yr[k], h - 1);
+        const bool in = xin && ybase + 4 * k < h;
+        const int y = min(ybase + 4 * k, h - 1);
         const unsigned o = (unsigned)y * (unsigned)w + (unsigned)x;
-        // the upsampled field is consumed right here; nothing downstream reads it (k_blur_solve overwrites the flow
-        // without reading it), so it only goes to memory for the debug capture
-        if (MODE == 1 && in && store_flow) {
-            flow[2u * o] = f[k].x;
-            flow[2u * o + 1u] = f[k].y;
-        }
+        if (in) keep(o, cur.f);
         float bb[5];
 #pragma unroll
         for (int c = 0; c < 5; c++) bb[c] = cur.a00 * cur.t[c].x + cur.a01 * cur.t[c].y + cur.a10 * cur.u[c].x + cur.a11 * cur.u[c].y;
         float m[5];
-        ffl_um_finish(cur.r0, bb, cur.inside, w, h, x, y, f[k].x, f[k].y, m);
+        ffl_um_finish(cur.r0, bb, cur.inside, w, h, x, y, cur.f.x, cur.f.y, m);
         if (in) {
 #pragma unroll
-            for (int c = 0; c < 5; c++) *ffl_at<float>(Mb + c * plane, o) = m[c];
+            for (int c = 0; c < 5; c++) *ffl_at<float>(M + c * plane, o) = m[c];
         }
         if (k + 1 < NR) cur = nxt;
     }
+}
+
+// MODE 0: the flow field is read; 1: it is formed here (x2 upsample of the coarser level) and written; 2: it is
+// zero (coarsest level) and neither read nor written -- k_blur_solve overwrites it without reading it
+template <int MODE>
+__global__ __launch_bounds__(256) void k_update_matrices(const float *__restrict__ R, size_t R_stride, size_t plane,
+                                                         const PairTab *__restrict__ pt, int level,
+                                                         float *__restrict__ M, size_t M_stride, int w,
+                                                         int h, int pw, int ph, double usx, double usy, int store_flow,
+                                                         int nB, int order) {
+    // Wave q takes rows q, q+4, q+8, q+12 of the tile (ffl_um_rows): all four rows' flow vectors first, then the row
+    // pipeline.  16-byte loads for the coarse flow.
+    int b, tile_x, tile_y;
+    if (!ffl_tile_coord((w + 63) / 64, (h + 15) / 16, nB, order, b, tile_x, tile_y)) return;
+    const int lx = threadIdx.x & 63, x0 = tile_x * 64, x = min(x0 + lx, w - 1);
+    const bool xin = x0 + lx < w;
+    const float *R0 = R + (size_t)pt->u0[b] * R_stride, *R1 = R + (size_t)pt->u1[b] * R_stride;
+    float *flow = pt->flow[level][b];
+    const float *pf = pt->flow[min(level + 1, FFL_MAX_LEVELS - 1)][b];
+    constexpr int NR = 4;
+    const int ybase = tile_y * 16 + (threadIdx.x >> 6);
+    float2 f[NR];
+    if (MODE == 1) {
+        const bool half_scale = usx == 0.5 && usy == 0.5;
+        int xa0, xa1;
+        float a1;
+        if (half_scale) ffl_resize_coord_half(x, pw, xa0, xa1, a1);
+        else ffl_resize_coord(x, pw, usx, xa0, xa1, a1);
+        const int xq = min(xa0, pw - 2);   // columns xq, xq + 1 lie inside the row; xa0 and xa1 are each one of them
+        float4 c0[NR], c1[NR];
+        float b1[NR];
+#pragma unroll
+        for (int k = 0; k < NR; k++) {
+            int ya0, ya1;
+            const int y = min(ybase + 4 * k, h - 1);
+            if (half_scale) ffl_resize_coord_half(y, ph, ya0, ya1, b1[k]);
+            else ffl_resize_coord(y, ph, usy, ya0, ya1, b1[k]);
+            c0[k] = ffl_gload4(pf, 8u * ((unsigned)ya0 * (unsigned)pw + xq));
+            c1[k] = ffl_gload4(pf, 8u * ((unsigned)ya1 * (unsigned)pw + xq));
+        }
+#pragma unroll
+        for (int k = 0; k < NR; k++) f[k] = ffl_upsample2(c0[k], c1[k], xa0 == xq, xa1 == xq, a1, b1[k]);
+    } else if (MODE == 0) {
+#pragma unroll
+        for (int k = 0; k < NR; k++) {
+            const unsigned o = (unsigned)min(ybase + 4 * k, h - 1) * (unsigned)w + (unsigned)x;
+            const FFL_GLOBAL float *q = (const FFL_GLOBAL float *)flow + 2u * o;
+            f[k] = make_float2(q[0], q[1]);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < NR; k++) f[k] = make_float2(0.f, 0.f);
+    }
+    // the upsampled field is consumed right here; nothing downstream reads it (k_blur_solve overwrites the flow without
+    // reading it), so it only goes to memory for the debug capture
+    ffl_um_rows<NR>(R0, R1, M + (size_t)b * M_stride, plane, w, h, x, xin, ybase, [&](int k) { return f[k]; },
+                    [&](unsigned o, float2 d) {
+                        if (MODE == 1 && store_flow) {
+                            flow[2u * o] = d.x;
+                            flow[2u * o + 1u] = d.y;
+                        }
+                    });
 }
 
 void ffl_launch_update_matrices(const float *R, size_t R_stride, size_t plane, const PairTab *pt, int level, int nB,
@@ -1151,15 +1033,10 @@ void ffl_launch_update_matrices(const float *R, size_t R_stride, size_t plane, c
                                 size_t M_stride, int lw, int lh, int pw, int ph, int zero_flow, int store_flow,
                                 const FflOptions &opt, hipStream_t st) {
     dim3 grid(ffl_tile_grid((lw + 63) / 64, (lh + 15) / 16, nB));
-    if (pw > 0)
-        hipLaunchKernelGGL(k_update_matrices<1>, grid, dim3(256), 0, st, R, R_stride, plane, pt, level, M, M_stride, lw, lh,
-                           pw, ph, (double)pw / lw, (double)ph / lh, store_flow, nB, opt.tile_order);
-    else if (zero_flow)
-        hipLaunchKernelGGL(k_update_matrices<2>, grid, dim3(256), 0, st, R, R_stride, plane, pt, level, M, M_stride, lw, lh, 0, 0,
-                           1.0, 1.0, 0, nB, opt.tile_order);
-    else
-        hipLaunchKernelGGL(k_update_matrices<0>, grid, dim3(256), 0, st, R, R_stride, plane, pt, level, M, M_stride, lw, lh, 0, 0,
-                           1.0, 1.0, 0, nB, opt.tile_order);
+    const auto k = pw > 0 ? k_update_matrices<1> : (zero_flow ? k_update_matrices<2> : k_update_matrices<0>);
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, st, R, R_stride, plane, pt, level, M, M_stride, lw, lh, pw, ph,
+                       pw > 0 ? (double)pw / lw : 1.0, pw > 0 ? (double)ph / lh : 1.0, pw > 0 ? store_flow : 0, nB,
+                       opt.tile_order);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1390,18 +1267,7 @@ __global__ __launch_bounds__(256, FIRST ? FFL_K5_WAVES_FIRST : FFL_K5_WAVES) voi
             const int inext = i + 256;
             const bool more = inext < N;
             float2 f = make_float2(0.f, 0.f);
-            if (FIRST == 1) {
-                const float a0 = 1.f - A.a1, b0 = 1.f - A.b1;
-                const float2 p00 = A.first0 ? make_float2(A.c0.x, A.c0.y) : make_float2(A.c0.z, A.c0.w);
-                const float2 p01 = A.first1 ? make_float2(A.c0.x, A.c0.y) : make_float2(A.c0.z, A.c0.w);
-                const float2 p10 = A.first0 ? make_float2(A.c1.x, A.c1.y) : make_float2(A.c1.z, A.c1.w);
-                const float2 p11 = A.first1 ? make_float2(A.c1.x, A.c1.y) : make_float2(A.c1.z, A.c1.w);
-                float t0 = p00.x * a0 + p01.x * A.a1, t1 = p10.x * a0 + p11.x * A.a1;
-                f.x = (t0 * b0 + t1 * A.b1) * 2.0f;
-                t0 = p00.y * a0 + p01.y * A.a1;
-                t1 = p10.y * a0 + p11.y * A.a1;
-                f.y = (t0 * b0 + t1 * A.b1) * 2.0f;
-            }
+            if (FIRST == 1) f = ffl_upsample2(A.c0, A.c1, A.first0, A.first1, A.a1, A.b1);
             float r0[5];
             {
                 const unsigned o = (unsigned)gy * (unsigned)w + (unsigned)gx;
@@ -1561,62 +1427,17 @@ __global__ __launch_bounds__(256, FIRST ? FFL_K5_WAVES_FIRST : FFL_K5_WAVES) voi
         __syncthreads();
         FFL_T(9)   // wait after the solve
         if (UPDATE) {
-            // One pixel per lane, lanes along x (a wave = one 64-pixel tile row, wave q takes rows q, q+4, q+8, q+12),
-            // double-buffered: the R0 values and R1 corners of the lane's next row are requested before the current
-            // row's arithmetic, so only the first of the four round trips is exposed.  No divergent branch touches a
-            // loaded value (ffl_um_finish uses selects), so the waits are "all but the next row's 25", never "all".
-            struct UmRow {
-                float2 f;
-                float a00, a01, a10, a11;
-                bool inside;
-                float r0[5];
-                ffl_f2u t[5], u[5];
-            };
+            // wave q takes rows q, q+4, q+8, q+12 of the tile, the displacements come from LDS (ffl_um_rows).  The
+            // displacement is consumed by the UpdateMatrices right here and the next iteration reads only M: the field
+            // itself is dead until the level's last iteration (8 B per pixel and launch not written; the debug capture
+            // asks for it)
             const int lx = tid & 63, x = min(x0 + lx, w - 1);
-            const bool xin = x0 + lx < w;
             const float2 *sF2 = reinterpret_cast<const float2 *>(sF4);
-            auto issue = [&](int k) {
-                UmRow S;
-                const int ly = (tid >> 6) + 4 * k;
-                const int y = min(y0 + ly, h - 1);
-                S.f = sF2[ly * FP + lx];
-                const unsigned o = (unsigned)y * (unsigned)w + (unsigned)x;
-#pragma unroll
-                for (int c = 0; c < 5; c++) S.r0[c] = *ffl_at<float>(R0 + c * plane, o);
-                const UmLoc L = ffl_um_locate(w, h, x, y, S.f.x, S.f.y);
-                S.a00 = L.a00; S.a01 = L.a01; S.a10 = L.a10; S.a11 = L.a11; S.inside = L.inside;
-                const unsigned o1 = L.inside ? (unsigned)L.y1 * (unsigned)w + (unsigned)L.x1 : 0u;
-#pragma unroll
-                for (int c = 0; c < 5; c++) {
-                    S.t[c] = ffl_ld_corner(R1 + c * plane, o1);
-                    S.u[c] = ffl_ld_corner(R1 + c * plane, o1 + (unsigned)w);
-                }
-                return S;
-            };
-            UmRow cur = issue(0);
-#pragma unroll
-            for (int k = 0; k < TH / 4; k++) {
-                UmRow nxt;
-                if (k + 1 < TH / 4) nxt = issue(k + 1);
-                const int ly = (tid >> 6) + 4 * k;
-                const bool in = xin && y0 + ly < h;
-                const int y = min(y0 + ly, h - 1);
-                const unsigned o = (unsigned)y * (unsigned)w + (unsigned)x;
-                // the displacement is consumed by the UpdateMatrices right here and the next iteration reads only M: the
-                // field itself is dead until the level's last iteration (8 B per pixel and launch not written; the debug
-                // capture asks for it)
-                if (in && store_flow) *reinterpret_cast<float2 *>(ffl_at<float>(reinterpret_cast<float *>(flow), 2u * o)) = cur.f;
-                float bb[5];
-#pragma unroll
-                for (int c = 0; c < 5; c++) bb[c] = cur.a00 * cur.t[c].x + cur.a01 * cur.t[c].y + cur.a10 * cur.u[c].x + cur.a11 * cur.u[c].y;
-                float m[5];
-                ffl_um_finish(cur.r0, bb, cur.inside, w, h, x, y, cur.f.x, cur.f.y, m);
-                if (in) {
-#pragma unroll
-                    for (int c = 0; c < 5; c++) *ffl_at<float>(Mo + c * plane, o) = m[c];
-                }
-                if (k + 1 < TH / 4) cur = nxt;
-            }
+            ffl_um_rows<TH / 4>(R0, R1, Mo, plane, w, h, x, x0 + lx < w, y0 + (tid >> 6),
+                                [&](int k) { return sF2[((tid >> 6) + 4 * k) * FP + lx]; },
+                                [&](unsigned o, float2 d) {
+                                    if (store_flow) *reinterpret_cast<float2 *>(ffl_at<float>(reinterpret_cast<float *>(flow), 2u * o)) = d;
+                                });
         } else {
             // the level's last iteration: only the field is written -- two adjacent pixels per lane, 16-byte stores
             // (512-B rows per wave), the workgroup covers 8 rows per pass
@@ -1670,18 +1491,24 @@ static int ffl_blur_rows_per_wg(int tiles_x, int tiles_y, int nB, int min_wgs) {
     return 1;
 }
 
-void ffl_launch_blur_solve(const float *Min, float *Mout, size_t M_stride, const float *R, size_t R_stride,
-                           size_t plane, const PairTab *pt, int level, int nB, int lw, int lh, int update, int store_flow,
-                           const FflOptions &opt, hipStream_t st) {
+// one k_blur_solve launch: the strip length and grid of the level, then kernel `k` (pw, ph: the coarser level's size
+// for the folded first iteration's upsample, else 0)
+template <typename K>
+static void ffl_launch_k5(K k, const float *Min, float *Mout, size_t M_stride, const float *R, size_t R_stride, size_t plane,
+                          const PairTab *pt, int level, int nB, int lw, int lh, int pw, int ph, int store_flow,
+                          const FflOptions &opt, hipStream_t st) {
     const int tiles_x = (lw + 63) / 64, tiles_y = (lh + 15) / 16;
     const int nrb = opt.blur_rows > 0 ? opt.blur_rows : ffl_blur_rows_per_wg(tiles_x, tiles_y, nB, opt.blur_min_wgs);
     dim3 grid(ffl_tile_grid(tiles_x, (tiles_y + nrb - 1) / nrb, nB));
-    if (update)
-        hipLaunchKernelGGL((k_blur_solve<true, 0>), grid, dim3(256), 0, st, Min, Mout, M_stride, R, R_stride, plane, pt, level, lw,
-                           lh, nrb, 0, 0, 1.0, 1.0, store_flow, nB, opt.tile_order);
-    else
-        hipLaunchKernelGGL((k_blur_solve<false, 0>), grid, dim3(256), 0, st, Min, Mout, M_stride, R, R_stride, plane, pt,
-                           level, lw, lh, nrb, 0, 0, 1.0, 1.0, 1, nB, opt.tile_order);
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, st, Min, Mout, M_stride, R, R_stride, plane, pt, level, lw, lh, nrb, pw, ph,
+                       pw > 0 ? (double)pw / lw : 1.0, pw > 0 ? (double)ph / lh : 1.0, store_flow, nB, opt.tile_order);
+}
+
+void ffl_launch_blur_solve(const float *Min, float *Mout, size_t M_stride, const float *R, size_t R_stride,
+                           size_t plane, const PairTab *pt, int level, int nB, int lw, int lh, int update, int store_flow,
+                           const FflOptions &opt, hipStream_t st) {
+    ffl_launch_k5(update ? k_blur_solve<true, 0> : k_blur_solve<false, 0>, Min, Mout, M_stride, R, R_stride, plane, pt, level,
+                  nB, lw, lh, 0, 0, update ? store_flow : 1, opt, st);
 }
 
 // first iteration of a level with the initial UpdateMatrices folded in (pw > 0: initial flow = x2 upsample of
@@ -1689,13 +1516,6 @@ void ffl_launch_blur_solve(const float *Min, float *Mout, size_t M_stride, const
 void ffl_launch_blur_solve_first(float *Mout, size_t M_stride, const float *R, size_t R_stride, size_t plane,
                                  const PairTab *pt, int level, int nB, int lw, int lh, int pw, int ph, const FflOptions &opt,
                                  hipStream_t st) {
-    const int tiles_x = (lw + 63) / 64, tiles_y = (lh + 15) / 16;
-    const int nrb = opt.blur_rows > 0 ? opt.blur_rows : ffl_blur_rows_per_wg(tiles_x, tiles_y, nB, opt.blur_min_wgs);
-    dim3 grid(ffl_tile_grid(tiles_x, (tiles_y + nrb - 1) / nrb, nB));
-    if (pw > 0)
-        hipLaunchKernelGGL((k_blur_solve<true, 1>), grid, dim3(256), 0, st, (const float *)nullptr, Mout, M_stride, R,
-                           R_stride, plane, pt, level, lw, lh, nrb, pw, ph, (double)pw / lw, (double)ph / lh, 0, nB, opt.tile_order);
-    else
-        hipLaunchKernelGGL((k_blur_solve<true, 2>), grid, dim3(256), 0, st, (const float *)nullptr, Mout, M_stride, R,
-                           R_stride, plane, pt, level, lw, lh, nrb, 0, 0, 1.0, 1.0, 0, nB, opt.tile_order);
+    ffl_launch_k5(pw > 0 ? k_blur_solve<true, 1> : k_blur_solve<true, 2>, (const float *)nullptr, Mout, M_stride, R, R_stride,
+                  plane, pt, level, nB, lw, lh, pw, ph, 0, opt, st);
 }

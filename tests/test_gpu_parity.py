@@ -278,3 +278,58 @@ def test_one_pass_coarse_pyramid_levels_bit_exact(w, h):
             want = orc.pyr_level(f, lvl)
             assert np.array_equal(got[1][lvl][key], want), (lvl, key, np.abs(got[1][lvl][key] - want).max())
             assert np.array_equal(got[0][lvl][key], want), (lvl, key)
+
+
+# ------------------------------------------------------------------ per-level launchers under every schedule
+# (258, 257): w % 4 != 0, so the merged pyramid launch refuses and every level is launched on its own -- level 0 by the
+# pixel-per-lane fused kernel, level 1 (129 x 128, h odd: inexact) by the R = 1 H + V pair, levels 2 and 3 (64 x 64,
+# 32 x 32) by the R = 4 / R = 9 pairs with byte-wise taps; the smallest shape with all four levels.  (130, 66): two levels.
+AWKWARD_SIZES = [(258, 257), (130, 66)]
+SCHEDULES = {"default": {}, "merge_expand=0": {"merge_expand": 0}, "run_ahead=1": {"run_ahead": 1},
+             "run_ahead=2": {"run_ahead": 2}}
+_awkward_cache = {}
+
+
+def awkward_case(w, h):
+    """frames and oracle flows of one size, computed once for all schedules"""
+    if (w, h) not in _awkward_cache:
+        fr = frames(3, w, h, seed=3 * w + h, amp=(2.5, 1.5), period=6)
+        fr.setflags(write=False)
+        _awkward_cache[(w, h)] = (fr, [orc.farneback(fr[j], fr[j + 1]) for j in range(2)])
+    return _awkward_cache[(w, h)]
+
+
+@pytest.mark.parametrize("sched", list(SCHEDULES))
+@pytest.mark.parametrize("w,h", AWKWARD_SIZES)
+def test_per_level_launches_every_schedule_bit_exact(w, h, sched):
+    """Sizes whose levels the merged launches do not take, under the serial merged, serial per-level, run-ahead and
+    fork/join schedules of the frame-only work: both flows of a 2-pair batch equal the oracle bit for bit."""
+    fr, want = awkward_case(w, h)
+    try:
+        for k, v in SCHEDULES[sched].items():
+            _capi.set_option(k, v)
+        with _capi.Context(w, h, max_batch=2, frame_slots=4, flow_slots=4) as ctx:
+            for i in range(3):
+                ctx.upload_frame(i, fr[i])
+            ctx.flow_pairs([0, 1], [1, 2], [0, 1])
+            got = [ctx.download_flow(0), ctx.download_flow(1)]
+    finally:
+        _capi.set_option("merge_expand", 1)
+        _capi.set_option("run_ahead", 0)
+    for j in range(2):
+        assert np.array_equal(got[j], want[j]), (j, np.abs(got[j] - want[j]).max())
+
+
+def test_per_level_pyramid_images_bit_exact():
+    """(258, 257), default options: the level images of both frames equal the oracle's pyr_level at every level."""
+    w, h = AWKWARD_SIZES[0]
+    fr, _ = awkward_case(w, h)
+    with _capi.Context(w, h, max_batch=1) as ctx:
+        ctx.upload_frame(0, fr[0])
+        ctx.upload_frame(1, fr[1])
+        assert ctx.num_levels() == 3
+        got = {lvl: ctx.debug_pair(0, 1, lvl, 0) for lvl in range(4)}
+    for lvl in range(4):
+        for key, f in (("I0", fr[0]), ("I1", fr[1])):
+            want = orc.pyr_level(f, lvl)
+            assert np.array_equal(got[lvl][key], want), (lvl, key, np.abs(got[lvl][key] - want).max())
