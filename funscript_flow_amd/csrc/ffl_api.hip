@@ -301,7 +301,7 @@ struct ffl_ctx {
     std::vector<EvRef> ev_last_use;  // [frame slot * n_lanes + lane]: the last batch of that lane that read the slot
     std::vector<char> frame_valid;
     std::vector<int> u_of_fslot;      // scratch of run_batch: frame slot -> index among the batch's unique frames (-1 outside)
-    std::vector<char> slot_mark;      // scratch of check_pairs: flow slot already named in this batch
+    std::vector<char> slot_mark;      // scratch of check_flow_slots: flow slot already named in this call
     // ffl_upload_frames_raw: decoded source frames pass through a small ring of pinned + device buffers
     // (grown on demand to the largest source seen); `ev` = the frame's k_frontend has consumed the buffer
     struct RawBuf {
@@ -313,7 +313,7 @@ struct ffl_ctx {
     };
     RawBuf raw[FFL_RAW_RING];
     unsigned raw_next = 0;
-    EvRing post_ring;  // events of ffl_upload_flow, ffl_radial and ffl_export_flows (stream `post`), FFL_EV_RING entries
+    EvRing post_ring;  // events of the calls that queue on stream `post` (publish_post), FFL_EV_RING entries
     // device-memory I/O (ffl_upload_frames_device / ffl_export_flows / ffl_import_flows): the event recorded on the
     // caller's stream (waited for at once, so one is enough), and, allocated on first use, the per-call frame descriptor
     // tables -- a pinned copy per up_ring entry (n_fslots descriptors each) and the device table k_frontend_dev reads (`copy`)
@@ -415,10 +415,11 @@ static void gaussian_kernel(int n, double sigma, float *out) {  // getGaussianKe
     for (int i = 0; i < n; i++) out[i] = (float)(out[i] * sum);
 }
 
-static void polyexp_prepare(PolyConsts *pc) {  // FarnebackPrepareGaussian(n = 5, sigma = 1.2)
-    const int n = FFL_POLY_N;
-    const double sigma = 1.2;
-    float gg[2 * FFL_POLY_N + 1];
+// FarnebackPrepareGaussian(n, sigma): g, xg, xxg for x = 0..n and the four entries of the inverse moment matrix that
+// PolyExp uses.  The one statement of the procedure: the tuned path calls it with (5, 1.2), the general path with the
+// caller's values, and `fb_general = 1` promises the same bits through either.
+static void farneback_prepare_gaussian(int n, double sigma, FbgPoly *out) {
+    float gg[2 * 7 + 1];
     double s = 0;
     for (int x = -n; x <= n; x++) {
         gg[x + n] = (float)exp(-x * x / (2 * sigma * sigma));
@@ -427,11 +428,9 @@ static void polyexp_prepare(PolyConsts *pc) {  // FarnebackPrepareGaussian(n = 5
     s = 1. / s;
     for (int x = -n; x <= n; x++) gg[x + n] = (float)(gg[x + n] * s);
     for (int x = 0; x <= n; x++) {
-        pc->g[x] = gg[x + n];
-        pc->xg[x] = (float)(x * gg[x + n]);
-        pc->xxg[x] = (float)(x * x * gg[x + n]);
-        pc->gd[x] = (double)pc->g[x];
-        pc->xxgd[x] = (double)pc->xxg[x];
+        out->g[x] = gg[x + n];
+        out->xg[x] = (float)(x * gg[x + n]);
+        out->xxg[x] = (float)(x * x * gg[x + n]);
     }
     double G[6][6];
     memset(G, 0, sizeof(G));
@@ -464,33 +463,76 @@ static void polyexp_prepare(PolyConsts *pc) {  // FarnebackPrepareGaussian(n = 5
                     for (int j = 0; j < 12; j++) A[r][j] -= f * A[c][j];
             }
     }
-    pc->ig11 = A[1][7];
-    pc->ig03 = A[0][9];
-    pc->ig33 = A[3][9];
-    pc->ig55 = A[5][11];
+    out->ig11 = A[1][7];
+    out->ig03 = A[0][9];
+    out->ig33 = A[3][9];
+    out->ig55 = A[5][11];
 }
 
-static void level_geometry(int w, int h, Geometry *geo) {  // FarnebackOpticalFlowImpl::calc level logic
+static void polyexp_prepare(PolyConsts *pc) {  // FarnebackPrepareGaussian(n = 5, sigma = 1.2)
+    FbgPoly q;
+    farneback_prepare_gaussian(FFL_POLY_N, 1.2, &q);
+    for (int x = 0; x <= FFL_POLY_N; x++) {
+        pc->g[x] = q.g[x];
+        pc->xg[x] = q.xg[x];
+        pc->xxg[x] = q.xxg[x];
+        pc->gd[x] = (double)pc->g[x];
+        pc->xxgd[x] = (double)pc->xxg[x];
+    }
+    pc->ig11 = q.ig11;
+    pc->ig03 = q.ig03;
+    pc->ig33 = q.ig33;
+    pc->ig55 = q.ig55;
+}
+
+// The level rule of FarnebackOpticalFlowImpl::calc for (pyr_scale, requested levels) on a w x h frame: how many coarser
+// levels there are (A.1: none below min_size = 32) and, per level, its size and the Gaussian it is smoothed with.
+struct LevelRule {
+    int levels;
+    int lw[FBG_MAX_SCALES], lh[FBG_MAX_SCALES], ksize[FBG_MAX_SCALES];
+    double sigma[FBG_MAX_SCALES];
+};
+static void level_rule(int w, int h, double pyr_scale, int levels, LevelRule *r) {
     int k;
     double scale = 1.0;
-    for (k = 0; k < 3; k++) {
-        scale *= 0.5;
+    for (k = 0; k < levels; k++) {
+        scale *= pyr_scale;
         if (w * scale < 32 || h * scale < 32) break;
     }
-    geo->levels = k;
-    for (k = 0; k <= geo->levels; k++) {
+    r->levels = k;
+    for (k = 0; k <= r->levels; k++) {
         double sc = 1.0;
-        for (int i = 0; i < k; i++) sc *= 0.5;
+        for (int i = 0; i < k; i++) sc *= pyr_scale;
+        r->sigma[k] = (1.0 / sc - 1.0) * 0.5;
+        const int sm = cv_round(r->sigma[k] * 5) | 1;
+        r->ksize[k] = sm < 3 ? 3 : sm;
+        r->lw[k] = cv_round(w * sc);
+        r->lh[k] = cv_round(h * sc);
+    }
+}
+
+static void level_geometry(int w, int h, Geometry *geo) {  // the reference's parameters: pyr_scale 0.5, levels 3
+    LevelRule r;
+    level_rule(w, h, 0.5, 3, &r);
+    geo->levels = r.levels;
+    for (int k = 0; k <= r.levels; k++) {
         LevelGeom &g = geo->lv[k];
-        g.sigma = (1.0 / sc - 1.0) * 0.5;
-        int sm = cv_round(g.sigma * 5) | 1;
-        g.ksize = sm < 3 ? 3 : sm;
-        g.lw = cv_round(w * sc);
-        g.lh = cv_round(h * sc);
+        g.lw = r.lw[k];
+        g.lh = r.lh[k];
+        g.ksize = r.ksize[k];
+        g.sigma = r.sigma[k];
         memset(&g.gk, 0, sizeof(g.gk));
         g.gk.ksize = g.ksize;
         gaussian_kernel(g.ksize, g.sigma, g.gk.k);
     }
+}
+
+// The sizes every sizing call and ffl_create accept.  Upper bound: the kernels index a pair's 5 M planes (20 bytes per
+// pixel) and a batch's pixels with 32-bit offsets -> 20 * w * h must stay below 2^32 (about 214 Mpx; 5760x2880 is 16.6 Mpx)
+#define FFL_FRAME_SIZE_RULE "unsupported frame size %dx%d (16x16 .. 20*w*h < 2^32)"
+static bool frame_size_ok(int w, int h) { return !(w < 16 || h < 16 || (long)w * h * 20 >= (1L << 32)); }
+static bool counts_ok(int n_frame_slots, int n_flow_slots, int max_batch) {
+    return n_frame_slots >= 2 && n_flow_slots >= 1 && max_batch >= 1 && max_batch <= FFL_MAX_BATCH;
 }
 
 static Layout context_layout(int w, int h, int n_frame_slots, int n_flow_slots, int max_batch) {
@@ -635,6 +677,44 @@ static void publish_slots(ffl_ctx *c, int n, const int *slots, EvRef done, bool 
     }
 }
 
+// The frame slots first..first+n-1 of an upload call and its table of n frames; `frames` (host pointers) when every
+// entry must be non-NULL too.  fn prefixes the message.
+static int check_frame_run(ffl_ctx *c, const char *fn, int first, int n, const void *table, const uint8_t *const *frames = nullptr) {
+    if (!table || n < 1 || first < 0 || first + n > c->n_fslots)
+        return set_err(c, FFL_ERR_INVALID, "%s: bad frame slot range %d..%d", fn, first, first + n - 1);
+    for (int i = 0; frames && i < n; i++)
+        if (!frames[i]) return set_err(c, FFL_ERR_INVALID, "%s: frame %d is NULL", fn, i);
+    return FFL_OK;
+}
+
+// The flow slots a call names: each in range, holding what the call reads (`holds`: "flow", "result", or nullptr when the
+// call only writes them), and -- when `repeat_rule` words the refusal -- none named twice (O(n) through the context's
+// scratch marks, which are cleared again on every path).  fn prefixes the message.
+static bool flow_slot_ok(const ffl_ctx *c, int slot) { return slot >= 0 && slot < c->n_slots; }
+static int check_flow_slots(ffl_ctx *c, const char *fn, int n, const int *slots, const char *holds, const char *repeat_rule) {
+    for (int i = 0; i < n; i++) {
+        if (!flow_slot_ok(c, slots[i])) return set_err(c, FFL_ERR_INVALID, "%s: flow slot %d out of range", fn, slots[i]);
+        if (holds && !c->slot_state[slots[i]]) return set_err(c, FFL_ERR_STATE, "%s: flow slot %d holds no %s", fn, slots[i], holds);
+    }
+    if (!repeat_rule) return FFL_OK;
+    int dup = -1;
+    for (int i = 0; i < n; i++) {
+        if (c->slot_mark[slots[i]] && dup < 0) dup = slots[i];
+        c->slot_mark[slots[i]] = 1;
+    }
+    for (int i = 0; i < n; i++) c->slot_mark[slots[i]] = 0;
+    if (dup >= 0) return set_err(c, FFL_ERR_INVALID, "%s: flow slot %d %s", fn, dup, repeat_rule);
+    return FFL_OK;
+}
+
+// Flow slots read or written by an operation queued on stream `post`: ONE event of post_ring becomes their last use
+// (*done), so that a batch recycling one of them runs behind it.  The slots hold a result once it has completed.
+static int publish_post(ffl_ctx *c, int n, const int *slots, EvRef *done) {
+    HIPCHK(c, c->post_ring.record(c->s_post, done));
+    publish_slots(c, n, slots, *done, true);
+    return FFL_OK;
+}
+
 // The geometry rules of every front-end path: source, resize and output sizes within 32768, the crop window inside the
 // resized frame.  Fills the geometry, resize mode and scales of *p (the caller sets kind and rgb); fn prefixes the message.
 static int front_geometry(ffl_ctx *c, const char *fn, int sw, int sh, int rw, int rh, int cx, int cy, int ow, int oh,
@@ -738,16 +818,99 @@ void ffl_destroy(ffl_ctx *c) {
     delete c;  // every stream has been drained: the handles release in no particular order
 }
 
+// The runtime resources of a context whose geometry, options and layout are set.  A failure is reported as the creation
+// error (the null context of HIPCHK): the half-built context does not outlive the call.
+static int create_resources(ffl_ctx *c) {
+    const int width = c->w, height = c->h, n_frame_slots = c->n_fslots, n_flow_slots = c->n_slots;
+    const int num_lanes = c->opt.lanes;  // fixed for the life of the context
+    const Geometry &geo = c->geo;
+    const Layout &lay = c->lay;
+    HIPCHK(nullptr, hipSetDevice(c->device));
+    // uploads and pass 2 are short and latency-critical (the host waits on pass 2): high priority, so
+    // that they get their own hardware queues and are scheduled between a lane's queued kernels
+    int prio_least = 0, prio_greatest = 0;
+    HIPCHK(nullptr, hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+    HIPCHK(nullptr, hipStreamCreateWithPriority(c->s_copy.put(), hipStreamNonBlocking, prio_greatest));
+    HIPCHK(nullptr, hipStreamCreateWithPriority(c->s_post.put(), hipStreamNonBlocking, prio_greatest));
+    HIPCHK_ALLOC(nullptr, hipMalloc, c->d_gray, lay.gray + 16);  // +16: the pyramid kernels fetch taps as aligned words
+    HIPCHK_ALLOC(nullptr, hipMalloc, c->d_bgr, lay.bgr);
+    HIPCHK_ALLOC(nullptr, hipHostMalloc, c->h_stage_gray, lay.gray, hipHostMallocDefault);
+    HIPCHK_ALLOC(nullptr, hipHostMalloc, c->h_stage_bgr, lay.bgr, hipHostMallocDefault);
+    c->p1_blocks = ffl_pass1_blocks(width, height);
+    c->lanes.resize(num_lanes);
+    for (auto &L : c->lanes) {
+        HIPCHK(nullptr, hipStreamCreateWithFlags(L.st.put(), hipStreamNonBlocking));
+        // st_aux (run-ahead / fork-join schedules only) are created on first use: HIP multiplexes streams
+        // onto a few hardware queues, and idle extra streams make the latency-critical `post` / `copy`
+        // streams share a queue with a compute lane (pass 2 then waits behind whole queued batches)
+        HIPCHK(nullptr, hipEventCreateWithFlags(L.ev_fork.put(), hipEventDisableTiming));
+        HIPCHK(nullptr, L.ring.create(FFL_EV_RING));
+        for (int k = 0; k <= geo.levels; k++) HIPCHK(nullptr, hipEventCreateWithFlags(L.ev_R[k].put(), hipEventDisableTiming));
+        HIPCHK_ALLOC(nullptr, hipMalloc, L.d_I, lay.I);
+        HIPCHK_ALLOC(nullptr, hipMalloc, L.d_T, lay.T);
+        HIPCHK_ALLOC(nullptr, hipMalloc, L.d_R, lay.R);
+        for (auto &M : L.d_M) HIPCHK_ALLOC(nullptr, hipMalloc, M, lay.M);
+        HIPCHK_ALLOC(nullptr, hipMalloc, L.d_flowA, lay.flow);
+        HIPCHK_ALLOC(nullptr, hipMalloc, L.d_flowB, lay.flow);
+        HIPCHK_ALLOC(nullptr, hipMalloc, L.d_pkey, lay.p1);
+        HIPCHK_ALLOC(nullptr, hipMalloc, L.d_psum, lay.p1);
+        HIPCHK_ALLOC(nullptr, hipMalloc, L.d_tab, 1);
+        HIPCHK_ALLOC(nullptr, hipHostMalloc, L.h_tab, lay.tab, hipHostMallocDefault);
+        for (int k = geo.levels; k >= 0; k--, L.n_jobs++) {
+            const LevelGeom &g = geo.lv[k];
+            const size_t plane = (size_t)g.lw * g.lh;
+            PyrJob &P = L.pyr[L.n_jobs];
+            P.w = width; P.h = height; P.lw = g.lw; P.lh = g.lh;
+            P.sx = (double)width / g.lw; P.sy = (double)height / g.lh;
+            P.gk = g.gk;
+            P.tmp = L.d_T + lay.t_off[k]; P.tmp_stride = ffl_pyr_tmp_floats(width, height, g.lw);
+            P.I = L.d_I + lay.i_off[k]; P.I_stride = plane;
+            PolyJob &Q = L.poly[L.n_jobs];
+            Q.I = P.I; Q.I_stride = plane;
+            Q.R = L.d_R + lay.r_off[k]; Q.R_stride = 5 * plane; Q.plane = plane;
+            Q.w = g.lw; Q.h = g.lh;
+        }
+    }
+    HIPCHK_ALLOC(nullptr, hipMalloc, c->d_flow, lay.slots);
+    HIPCHK_ALLOC(nullptr, hipHostMalloc, c->h_res, lay.res, hipHostMallocMapped);
+    HIPCHK(nullptr, hipHostGetDevicePointer((void **)&c->d_res, c->h_res, 0));
+    HIPCHK_ALLOC(nullptr, hipMalloc, c->d_rpsum, (size_t)c->p1_blocks * FFL_MAXB);
+    {
+        std::vector<double> wy(2 * (size_t)height);
+        for (int y = 0; y < height; y++) {
+            wy[y] = (double)(height - y) / (double)height;
+            wy[height + y] = (double)y / (double)height;
+        }
+        HIPCHK_ALLOC(nullptr, hipMalloc, c->d_wytab, wy.size());
+        HIPCHK(nullptr, hipMemcpy(c->d_wytab, wy.data(), sizeof(double) * wy.size(), hipMemcpyHostToDevice));
+    }
+    HIPCHK_ALLOC(nullptr, hipMalloc, c->d_rtab, 1);
+    HIPCHK_ALLOC(nullptr, hipHostMalloc, c->h_rtab, 1, hipHostMallocDefault);
+    HIPCHK_ALLOC(nullptr, hipMalloc, c->d_ptab, 1);
+    HIPCHK_ALLOC(nullptr, hipHostMalloc, c->h_ptab, 1, hipHostMallocDefault);
+    HIPCHK_ALLOC(nullptr, hipMalloc, c->d_ppkey, c->p1_blocks);
+    HIPCHK_ALLOC(nullptr, hipHostMalloc, c->h_radial, FFL_MAXB, hipHostMallocMapped);
+    HIPCHK(nullptr, hipHostGetDevicePointer((void **)&c->d_radial, c->h_radial, 0));
+    c->ev_uploaded.assign(n_frame_slots, EvRef{});
+    c->ev_last_use.assign((size_t)n_frame_slots * num_lanes, EvRef{});  // references into the lanes' rings
+    c->frame_valid.assign(n_frame_slots, 0);
+    c->u_of_fslot.assign(n_frame_slots, -1);
+    c->slot_mark.assign(n_flow_slots, 0);
+    HIPCHK(nullptr, c->up_ring.create(2 * FFL_EV_RING));
+    HIPCHK(nullptr, c->post_ring.create(FFL_EV_RING));
+    HIPCHK(nullptr, hipEventCreateWithFlags(c->ev_caller.put(), hipEventDisableTiming));
+    for (auto &rb : c->raw) HIPCHK(nullptr, hipEventCreateWithFlags(rb.ev.put(), hipEventDisableTiming));
+    c->ev_slot_done.assign(n_flow_slots, EvRef{});                        // set when a slot is queued
+    c->slot_state.assign(n_flow_slots, 0);
+    return FFL_OK;
+}
+
 int ffl_create(int device, int width, int height, int n_frame_slots, int n_flow_slots, int max_batch,
                ffl_ctx **out) {
     if (!out) return set_err(nullptr, FFL_ERR_INVALID, "ffl_create: out is NULL");
     *out = nullptr;
-    // upper bound: the kernels index a pair's 5 M planes (20 bytes per pixel) and a batch's pixels with 32-bit
-    // offsets -> 20 * w * h must stay below 2^32 (about 214 Mpx; 5760x2880 is 16.6 Mpx)
-    if (width < 16 || height < 16 || (long)width * height * 20 >= (1L << 32))
-        return set_err(nullptr, FFL_ERR_INVALID, "ffl_create: unsupported frame size %dx%d (16x16 .. 20*w*h < 2^32)", width,
-                       height);
-    if (n_frame_slots < 2 || n_flow_slots < 1 || max_batch < 1 || max_batch > FFL_MAX_BATCH)
+    if (!frame_size_ok(width, height)) return set_err(nullptr, FFL_ERR_INVALID, "ffl_create: " FFL_FRAME_SIZE_RULE, width, height);
+    if (!counts_ok(n_frame_slots, n_flow_slots, max_batch))
         return set_err(nullptr, FFL_ERR_INVALID, "ffl_create: bad slot/batch counts (%d, %d, %d)", n_frame_slots,
                        n_flow_slots, max_batch);
     int ndev = 0;
@@ -778,99 +941,14 @@ int ffl_create(int device, int width, int height, int n_frame_slots, int n_flow_
         std::lock_guard<std::mutex> g(g_opt_mu);
         c->opt = g_opts;
     }
-    const int num_lanes = c->opt.lanes;  // fixed for the life of the context
     c->geo = geo;
-    const Layout &lay = c->lay = context_layout(width, height, n_frame_slots, n_flow_slots, max_batch);
+    c->lay = context_layout(width, height, n_frame_slots, n_flow_slots, max_batch);
     polyexp_prepare(&c->pc);
-    auto fail = [&](const char *what, hipError_t e) {  // works on a context that is built in part: null handles are no-ops
-        const int rc = set_err(nullptr, FFL_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
-        ffl_destroy(c);
+    if (const int rc = create_resources(c)) {
+        ffl_destroy(c);           // works on a context that is built in part: null handles are no-ops
         (void)hipGetLastError();  // the failure is reported HERE: do not leave it to poison a later call's check
         return rc;
-    };
-#define CCHK_AS(what, call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return fail(what, e_); } while (0)
-#define CCHK(call) CCHK_AS(#call, call)
-#define ALLOC(fn, buf, ...) CCHK_AS(#fn "(" #buf ", " #__VA_ARGS__ ")", (buf).alloc(__VA_ARGS__))  // reported as the call it makes
-    CCHK(hipSetDevice(device));
-    // uploads and pass 2 are short and latency-critical (the host waits on pass 2): high priority, so
-    // that they get their own hardware queues and are scheduled between a lane's queued kernels
-    int prio_least = 0, prio_greatest = 0;
-    CCHK(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-    CCHK(hipStreamCreateWithPriority(c->s_copy.put(), hipStreamNonBlocking, prio_greatest));
-    CCHK(hipStreamCreateWithPriority(c->s_post.put(), hipStreamNonBlocking, prio_greatest));
-    ALLOC(hipMalloc, c->d_gray, lay.gray + 16);  // +16: the pyramid kernels fetch taps as aligned words
-    ALLOC(hipMalloc, c->d_bgr, lay.bgr);
-    ALLOC(hipHostMalloc, c->h_stage_gray, lay.gray, hipHostMallocDefault);
-    ALLOC(hipHostMalloc, c->h_stage_bgr, lay.bgr, hipHostMallocDefault);
-    c->p1_blocks = ffl_pass1_blocks(width, height);
-    c->lanes.resize(num_lanes);
-    for (auto &L : c->lanes) {
-        CCHK(hipStreamCreateWithFlags(L.st.put(), hipStreamNonBlocking));
-        // st_aux (run-ahead / fork-join schedules only) are created on first use: HIP multiplexes streams
-        // onto a few hardware queues, and idle extra streams make the latency-critical `post` / `copy`
-        // streams share a queue with a compute lane (pass 2 then waits behind whole queued batches)
-        CCHK(hipEventCreateWithFlags(L.ev_fork.put(), hipEventDisableTiming));
-        CCHK(L.ring.create(FFL_EV_RING));
-        for (int k = 0; k <= c->geo.levels; k++) CCHK(hipEventCreateWithFlags(L.ev_R[k].put(), hipEventDisableTiming));
-        ALLOC(hipMalloc, L.d_I, lay.I);
-        ALLOC(hipMalloc, L.d_T, lay.T);
-        ALLOC(hipMalloc, L.d_R, lay.R);
-        for (auto &M : L.d_M) ALLOC(hipMalloc, M, lay.M);
-        ALLOC(hipMalloc, L.d_flowA, lay.flow);
-        ALLOC(hipMalloc, L.d_flowB, lay.flow);
-        ALLOC(hipMalloc, L.d_pkey, lay.p1);
-        ALLOC(hipMalloc, L.d_psum, lay.p1);
-        ALLOC(hipMalloc, L.d_tab, 1);
-        ALLOC(hipHostMalloc, L.h_tab, lay.tab, hipHostMallocDefault);
-        for (int k = geo.levels; k >= 0; k--, L.n_jobs++) {
-            const LevelGeom &g = geo.lv[k];
-            const size_t plane = (size_t)g.lw * g.lh;
-            PyrJob &P = L.pyr[L.n_jobs];
-            P.w = width; P.h = height; P.lw = g.lw; P.lh = g.lh;
-            P.sx = (double)width / g.lw; P.sy = (double)height / g.lh;
-            P.gk = g.gk;
-            P.tmp = L.d_T + lay.t_off[k]; P.tmp_stride = ffl_pyr_tmp_floats(width, height, g.lw);
-            P.I = L.d_I + lay.i_off[k]; P.I_stride = plane;
-            PolyJob &Q = L.poly[L.n_jobs];
-            Q.I = P.I; Q.I_stride = plane;
-            Q.R = L.d_R + lay.r_off[k]; Q.R_stride = 5 * plane; Q.plane = plane;
-            Q.w = g.lw; Q.h = g.lh;
-        }
     }
-    ALLOC(hipMalloc, c->d_flow, lay.slots);
-    ALLOC(hipHostMalloc, c->h_res, lay.res, hipHostMallocMapped);
-    CCHK(hipHostGetDevicePointer((void **)&c->d_res, c->h_res, 0));
-    ALLOC(hipMalloc, c->d_rpsum, (size_t)c->p1_blocks * FFL_MAXB);
-    {
-        std::vector<double> wy(2 * (size_t)height);
-        for (int y = 0; y < height; y++) {
-            wy[y] = (double)(height - y) / (double)height;
-            wy[height + y] = (double)y / (double)height;
-        }
-        ALLOC(hipMalloc, c->d_wytab, wy.size());
-        CCHK(hipMemcpy(c->d_wytab, wy.data(), sizeof(double) * wy.size(), hipMemcpyHostToDevice));
-    }
-    ALLOC(hipMalloc, c->d_rtab, 1);
-    ALLOC(hipHostMalloc, c->h_rtab, 1, hipHostMallocDefault);
-    ALLOC(hipMalloc, c->d_ptab, 1);
-    ALLOC(hipHostMalloc, c->h_ptab, 1, hipHostMallocDefault);
-    ALLOC(hipMalloc, c->d_ppkey, c->p1_blocks);
-    ALLOC(hipHostMalloc, c->h_radial, FFL_MAXB, hipHostMallocMapped);
-    CCHK(hipHostGetDevicePointer((void **)&c->d_radial, c->h_radial, 0));
-    c->ev_uploaded.assign(n_frame_slots, EvRef{});
-    c->ev_last_use.assign((size_t)n_frame_slots * num_lanes, EvRef{});  // references into the lanes' rings
-    c->frame_valid.assign(n_frame_slots, 0);
-    c->u_of_fslot.assign(n_frame_slots, -1);
-    c->slot_mark.assign(n_flow_slots, 0);
-    CCHK(c->up_ring.create(2 * FFL_EV_RING));
-    CCHK(c->post_ring.create(FFL_EV_RING));
-    CCHK(hipEventCreateWithFlags(c->ev_caller.put(), hipEventDisableTiming));
-    for (auto &rb : c->raw) CCHK(hipEventCreateWithFlags(rb.ev.put(), hipEventDisableTiming));
-    c->ev_slot_done.assign(n_flow_slots, EvRef{});                        // set when a slot is queued
-    c->slot_state.assign(n_flow_slots, 0);
-#undef ALLOC
-#undef CCHK_AS
-#undef CCHK
     *out = c;
     return FFL_OK;
 }
@@ -897,8 +975,7 @@ static int default_lanes() {
 // bytes of the layout ffl_create allocates from, plus 1 MiB each for the small tables it does not list.  No device needed.
 int ffl_estimate_bytes(int width, int height, int n_frame_slots, int n_flow_slots, int max_batch, size_t *device_bytes,
                        size_t *pinned_bytes) {
-    if (width < 16 || height < 16 || (long)width * height * 20 >= (1L << 32) || n_frame_slots < 2 || n_flow_slots < 1 ||
-        max_batch < 1 || max_batch > FFL_MAX_BATCH)
+    if (!frame_size_ok(width, height) || !counts_ok(n_frame_slots, n_flow_slots, max_batch))
         return set_err(nullptr, FFL_ERR_INVALID, "ffl_estimate_bytes: bad geometry / slot counts");
     const Layout l = context_layout(width, height, n_frame_slots, n_flow_slots, max_batch);
     const size_t lanes = default_lanes(), small = (size_t)1 << 20;
@@ -965,16 +1042,13 @@ int ffl_upload_frames(ffl_ctx *c, int first, int n, const uint8_t *const *frames
     if (!c) return FFL_ERR_INVALID;
     std::unique_lock<std::mutex> ul(c->up_mu);
     CtxLock lk(c->mu);
-    if (!frames || n < 1 || first < 0 || first + n > c->n_fslots)
-        return set_err(c, FFL_ERR_INVALID, "ffl_upload_frames: bad frame slot range %d..%d", first, first + n - 1);
+    if (int rc = check_frame_run(c, "ffl_upload_frames", first, n, frames, frames)) return rc;
     if (width != c->w || height != c->h)
         return set_err(c, FFL_ERR_INVALID, "ffl_upload_frames: frame is %dx%d, context is %dx%d", width, height, c->w, c->h);
     if (channels != 1 && channels != 3)
         return set_err(c, FFL_ERR_INVALID, "ffl_upload_frames: channels must be 1 (gray) or 3 (BGR), got %d", channels);
     if (stride_bytes < (ptrdiff_t)width * channels)
         return set_err(c, FFL_ERR_INVALID, "ffl_upload_frames: stride %td < row bytes %d", stride_bytes, width * channels);
-    for (int i = 0; i < n; i++)
-        if (!frames[i]) return set_err(c, FFL_ERR_INVALID, "ffl_upload_frames: frame %d is NULL", i);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t N = c->N, row = (size_t)width * channels, fbytes = N * channels;
     uint8_t *stage0 = (channels == 1 ? c->h_stage_gray : c->h_stage_bgr) + (size_t)first * fbytes;
@@ -1048,14 +1122,11 @@ int ffl_upload_frames_raw(ffl_ctx *c, int first, int n, const uint8_t *const *fr
     if (!c) return FFL_ERR_INVALID;
     std::unique_lock<std::mutex> ul(c->up_mu);
     CtxLock lk(c->mu);
-    if (!frames || n < 1 || first < 0 || first + n > c->n_fslots)
-        return set_err(c, FFL_ERR_INVALID, "%s: bad frame slot range %d..%d", fn, first, first + n - 1);
+    if (int rc = check_frame_run(c, fn, first, n, frames, frames)) return rc;
     FrontParams fp;
     if (int rc = front_geometry(c, fn, sw, sh, rw, rh, crop_x, crop_y, c->w, c->h, &fp)) return rc;
     if (stride_bytes < (ptrdiff_t)sw * 3)
         return set_err(c, FFL_ERR_INVALID, "%s: stride %td < row bytes %d", fn, stride_bytes, sw * 3);
-    for (int i = 0; i < n; i++)
-        if (!frames[i]) return set_err(c, FFL_ERR_INVALID, "%s: frame %d is NULL", fn, i);
     HIPCHK(c, hipSetDevice(c->device));
     fp.kind = FFL_SRC_BGR;
     fp.rgb = rgb_order != 0;
@@ -1152,13 +1223,10 @@ int ffl_upload_frames_yuv(ffl_ctx *c, int first, int n, const uint8_t *const *fr
     if (!c) return FFL_ERR_INVALID;
     std::unique_lock<std::mutex> ul(c->up_mu);
     CtxLock lk(c->mu);
-    if (!frames || n < 1 || first < 0 || first + n > c->n_fslots)
-        return set_err(c, FFL_ERR_INVALID, "%s: bad frame slot range %d..%d", fn, first, first + n - 1);
+    if (int rc = check_frame_run(c, fn, first, n, frames, frames)) return rc;
     FrontParams fp;
     YuvWin yw;
     if (int rc = yuv_window(c, fn, sw, sh, layout, stride_bytes, rw, rh, crop_x, crop_y, c->w, c->h, &fp, &yw)) return rc;
-    for (int i = 0; i < n; i++)
-        if (!frames[i]) return set_err(c, FFL_ERR_INVALID, "%s: frame %d is NULL", fn, i);
     HIPCHK(c, hipSetDevice(c->device));
     fp.kind = FFL_SRC_YUV;
     fp.rgb = 0;
@@ -1447,16 +1515,15 @@ static int queue_batch(ffl_ctx *c, ffl_ctx::Lane &L, BatchTab &T, int *nU_out, i
     // stream order puts this copy behind the lane's previous batch, which reads the same device table
     HIPCHK(c, hipMemcpyAsync(L.d_tab, &T, sizeof(BatchTab), hipMemcpyHostToDevice, st));
 
-    if (fbg) {
-        // general-parameter Farneback batches launch eagerly too (graphs stay keyed on the tuned schedule)
-        FbgWork wk;
-        if (int rc = fbg_work(c, L, *fbg, nU, &wk)) return rc;
-        ffl_launch_fb_general(&L.d_tab->ut, &L.d_tab->pt, n, nU, c->d_gray, N, c->w, c->h, *fbg, wk, st);
-        ProfScope ps(c, FFL_K_PASS1, st);
-        ffl_launch_pass1(&L.d_tab->pt, n, c->w, c->h, pov_mode, L.d_pkey, L.d_psum, st);
-    } else if (dis) {
-        // DIS batches launch eagerly (graphs stay keyed on Farneback batch shapes); scratch: the lane's first M buffer
-        ffl_launch_dis(&L.d_tab->ut, &L.d_tab->pt, n, c->d_gray, N, L.d_M[0], *dis, st);
+    if (fbg || dis) {
+        // general-parameter Farneback and DIS batches launch eagerly (graphs stay keyed on the tuned schedule's batch shapes)
+        if (fbg) {
+            FbgWork wk;
+            if (int rc = fbg_work(c, L, *fbg, nU, &wk)) return rc;
+            ffl_launch_fb_general(&L.d_tab->ut, &L.d_tab->pt, n, nU, c->d_gray, N, c->w, c->h, *fbg, wk, st);
+        } else {
+            ffl_launch_dis(&L.d_tab->ut, &L.d_tab->pt, n, c->d_gray, N, L.d_M[0], *dis, st);  // scratch: the lane's first M buffer
+        }
         ProfScope ps(c, FFL_K_PASS1, st);
         ffl_launch_pass1(&L.d_tab->pt, n, c->w, c->h, pov_mode, L.d_pkey, L.d_psum, st);
     } else if (c->opt.use_graph && !cap && c->prof_mask == 0 && c->opt.run_ahead == 0) {
@@ -1504,16 +1571,8 @@ static int check_pairs(ffl_ctx *c, int n, const int *f0, const int *f1, const in
             return set_err(c, FFL_ERR_INVALID, "pair %d: frame slot out of range", i);
         if (!c->frame_valid[f0[i]] || !c->frame_valid[f1[i]])
             return set_err(c, FFL_ERR_STATE, "pair %d: frame slot was never uploaded", i);
-        if (slots[i] < 0 || slots[i] >= c->n_slots) return set_err(c, FFL_ERR_INVALID, "pair %d: flow slot out of range", i);
     }
-    int dup = -1;  // O(n) through the context's scratch marks
-    for (int i = 0; i < n; i++) {
-        if (c->slot_mark[slots[i]] && dup < 0) dup = slots[i];
-        c->slot_mark[slots[i]] = 1;
-    }
-    for (int i = 0; i < n; i++) c->slot_mark[slots[i]] = 0;
-    if (dup >= 0) return set_err(c, FFL_ERR_INVALID, "flow slot %d used twice in one batch", dup);
-    return FFL_OK;
+    return check_flow_slots(c, "ffl_flow_pairs", n, slots, nullptr, "used twice in one batch");
 }
 
 // ---- DIS (kernels_dis.hip) ------------------------------------------------------------------
@@ -1694,96 +1753,39 @@ static const char *fbg_check(const ffl_farneback_params &p) {
 // The plan of p on a w x h frame (levels, sizes, Gaussians, PolyExp constants, R layout); nullptr or the reason it is refused
 static const char *fbg_plan(int w, int h, const ffl_farneback_params &p, FbgPlan *pl, char *why, size_t why_len) {
     if (const char *e = fbg_check(p)) return e;
-    if (w < 16 || h < 16 || (long)w * h * 20 >= (1L << 32)) {
-        snprintf(why, why_len, "unsupported frame size %dx%d (16x16 .. 20*w*h < 2^32)", w, h);
+    if (!frame_size_ok(w, h)) {
+        snprintf(why, why_len, FFL_FRAME_SIZE_RULE, w, h);
         return why;
     }
     memset(pl, 0, sizeof(*pl));
     const double ps = fbg_widen(p.pyr_scale);
-    double scale = 1.0;
-    int k;
-    for (k = 0; k < p.levels; k++) {  // A.1: min_size = 32
-        scale *= ps;
-        if (w * scale < 32 || h * scale < 32) break;
-    }
-    pl->levels = k;
+    LevelRule r;
+    level_rule(w, h, ps, p.levels, &r);
+    pl->levels = r.levels;
     pl->iterations = p.iterations;
     pl->poly_n = p.poly_n;
     pl->m = p.winsize / 2;
     pl->mul = (float)(1.0 / ps);
     size_t off = 0;
-    for (k = 0; k <= pl->levels; k++) {
-        double sc = 1.0;
-        for (int i = 0; i < k; i++) sc *= ps;
-        const double sigma = (1.0 / sc - 1.0) * 0.5;
-        int ks = cv_round(sigma * 5) | 1;
-        if (ks < 3) ks = 3;
+    for (int k = 0; k <= pl->levels; k++) {
+        const int ks = r.ksize[k];
         if (ks > 2 * FBG_MAX_R + 1) {
             snprintf(why, why_len, "%dx%d: level %d needs a %d-tap Gaussian, at most %d are supported", w, h, k, ks,
                      2 * FBG_MAX_R + 1);
             return why;
         }
         float full[2 * FBG_MAX_R + 1];
-        gaussian_kernel(ks, sigma, full);
+        gaussian_kernel(ks, r.sigma[k], full);
         pl->gk[k].r = ks / 2;
         for (int j = 0; j <= ks / 2; j++) pl->gk[k].k[j] = full[ks / 2 + j];
-        pl->lw[k] = cv_round(w * sc);
-        pl->lh[k] = cv_round(h * sc);
+        pl->lw[k] = r.lw[k];
+        pl->lh[k] = r.lh[k];
         pl->r_off[k] = off;
         off += (size_t)5 * pl->lw[k] * pl->lh[k];
     }
     pl->r_frame = off;
-    // F.3: FarnebackPrepareGaussian(poly_n, poly_sigma), the oracle's procedure with n and sigma as parameters
-    const int n = p.poly_n;
-    const double sigma = fbg_widen(p.poly_sigma);
-    float gg[2 * 7 + 1];
-    double s = 0;
-    for (int x = -n; x <= n; x++) {
-        gg[x + n] = (float)exp(-x * x / (2 * sigma * sigma));
-        s += gg[x + n];
-    }
-    s = 1. / s;
-    for (int x = -n; x <= n; x++) gg[x + n] = (float)(gg[x + n] * s);
-    for (int x = 0; x <= n; x++) {
-        pl->poly.g[x] = gg[x + n];
-        pl->poly.xg[x] = (float)(x * gg[x + n]);
-        pl->poly.xxg[x] = (float)(x * x * gg[x + n]);
-    }
-    double G[6][6];
-    memset(G, 0, sizeof(G));
-    for (int y = -n; y <= n; y++)
-        for (int x = -n; x <= n; x++) {
-            float q = gg[y + n] * gg[x + n];
-            G[0][0] += q;
-            G[1][1] += q * x * x;
-            G[3][3] += q * x * x * x * x;
-            G[5][5] += q * x * x * y * y;
-        }
-    G[2][2] = G[0][3] = G[0][4] = G[3][0] = G[4][0] = G[1][1];
-    G[4][4] = G[3][3];
-    G[3][4] = G[4][3] = G[5][5];
-    double A[6][12];
-    for (int i = 0; i < 6; i++)
-        for (int j = 0; j < 12; j++) A[i][j] = j < 6 ? G[i][j] : (j - 6 == i ? 1.0 : 0.0);
-    for (int c = 0; c < 6; c++) {
-        int pv = c;
-        for (int r = c + 1; r < 6; r++)
-            if (fabs(A[r][c]) > fabs(A[pv][c])) pv = r;
-        if (pv != c)
-            for (int j = 0; j < 12; j++) { double t = A[c][j]; A[c][j] = A[pv][j]; A[pv][j] = t; }
-        double d = 1.0 / A[c][c];
-        for (int j = 0; j < 12; j++) A[c][j] *= d;
-        for (int r = 0; r < 6; r++)
-            if (r != c) {
-                double f = A[r][c];
-                if (f != 0)
-                    for (int j = 0; j < 12; j++) A[r][j] -= f * A[c][j];
-            }
-    }
-    pl->poly.ig11 = A[1][7];
-    pl->poly.ig03 = A[0][9];
-    pl->poly.ig33 = A[3][9];
-    pl->poly.ig55 = A[5][11];
+    // F.3: FarnebackPrepareGaussian(poly_n, poly_sigma)
+    farneback_prepare_gaussian(p.poly_n, fbg_widen(p.poly_sigma), &pl->poly);
     return nullptr;
 }
 
@@ -1899,12 +1901,10 @@ int ffl_pass1_results(ffl_ctx *c, int n, const int *slots, float cut_threshold, 
     // one lock, one wait per DISTINCT event (the slots of a batch share theirs), then the records: 256 one-slot calls
     // cost 0.3 ms of host time per batch at the 256x256 operating point.  At most lanes x FFL_EV_RING + FFL_EV_RING
     // events are live at a time (the lanes' rings and post_ring).
+    if (int rc = check_flow_slots(c, "ffl_pass1_results", n, slots, "result", nullptr)) return rc;
     std::vector<hipEvent_t> evs;
     for (int i = 0; i < n; i++) {
-        const int slot = slots[i];
-        if (slot < 0 || slot >= c->n_slots) return set_err(c, FFL_ERR_INVALID, "flow slot %d out of range", slot);
-        if (!c->slot_state[slot]) return set_err(c, FFL_ERR_STATE, "flow slot %d holds no result", slot);
-        hipEvent_t e = c->ev_slot_done[slot].get();
+        hipEvent_t e = c->ev_slot_done[slots[i]].get();
         if (e && std::find(evs.begin(), evs.end(), e) == evs.end()) evs.push_back(e);
     }
     if (int rc = wait_unlocked(c, lk, evs.data(), (int)evs.size())) return rc;
@@ -1927,14 +1927,13 @@ int ffl_radial(ffl_ctx *c, int n, const int *slots, const double *cx, const doub
     std::unique_lock<std::mutex> pl(c->post_mu);  // one pass-2 call at a time owns stream `post`, h_rtab and h_radial
     CtxLock lk(c->mu);
     if (n < 1 || n > FFL_MAXB || !slots || !cx || !cy || !out) return set_err(c, FFL_ERR_INVALID, "ffl_radial: bad arguments");
+    if (int rc = check_flow_slots(c, "ffl_radial", n, slots, "flow", nullptr)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     RadialTab &rt = *c->h_rtab;  // the previous call waited for s_post, so the pinned copy is free
     WaitOnce wait_post(c->s_post);
     int m = 0;
-    int map[FFL_MAXB];
+    int map[FFL_MAXB], used[FFL_MAXB];  // the slots pass 2 reads and their places in `out`
     for (int i = 0; i < n; i++) {
-        if (slots[i] < 0 || slots[i] >= c->n_slots) return set_err(c, FFL_ERR_INVALID, "flow slot %d out of range", slots[i]);
-        if (!c->slot_state[slots[i]]) return set_err(c, FFL_ERR_STATE, "flow slot %d holds no flow", slots[i]);
         if (is_cut && is_cut[i]) {  // FF:766-767: a cut returns 0.0 without looking at the flow
             out[i] = 0.0;
             continue;
@@ -1943,6 +1942,7 @@ int ffl_radial(ffl_ctx *c, int n, const int *slots, const double *cx, const doub
         rt.flow[m] = c->d_flow + (size_t)slots[i] * 2 * c->N;
         rt.cx[m] = cx[i];
         rt.cy[m] = cy[i];
+        used[m] = slots[i];
         map[m++] = i;
     }
     if (m == 0) return FFL_OK;
@@ -1952,13 +1952,10 @@ int ffl_radial(ffl_ctx *c, int n, const int *slots, const double *cx, const doub
         ProfScope ps(c, FFL_K_RADIAL, st);
         ffl_launch_radial(c->d_rtab, m, c->w, c->h, pov_mode, c->d_wytab, c->d_rpsum, c->d_radial, st);
     }
-    {
-        // the slots' "last use" now includes this pass 2: the wait below runs without the context lock, so another thread
-        // may queue a batch that recycles one of these slots meanwhile -- it must run behind the kernel that reads them
-        EvRef ev;
-        HIPCHK(c, c->post_ring.record(st, &ev));
-        for (int j = 0; j < m; j++) c->ev_slot_done[slots[map[j]]] = ev;
-    }
+    // the slots' "last use" now includes this pass 2: the wait below runs without the context lock, so another thread
+    // may queue a batch that recycles one of these slots meanwhile -- it must run behind the kernel that reads them
+    EvRef ev;
+    if (int rc = publish_post(c, m, used, &ev)) return rc;
     lk.unlock();  // the wait (for the batches the slots come from, then pass 2) does not hold up uploads / submissions
     hipError_t se = hipStreamSynchronize(st);  // k_radial_final stored into the mapped pinned buffer
     lk.lock();
@@ -1971,8 +1968,8 @@ int ffl_radial(ffl_ctx *c, int n, const int *slots, const double *cx, const doub
 int ffl_download_flow(ffl_ctx *c, int slot, float *dst) {
     if (!c) return FFL_ERR_INVALID;
     CtxLock lk(c->mu);
-    if (slot < 0 || slot >= c->n_slots || !dst) return set_err(c, FFL_ERR_INVALID, "ffl_download_flow: bad arguments");
-    if (!c->slot_state[slot]) return set_err(c, FFL_ERR_STATE, "flow slot %d holds no flow", slot);
+    if (!dst) return set_err(c, FFL_ERR_INVALID, "ffl_download_flow: bad arguments");
+    if (int rc = check_flow_slots(c, "ffl_download_flow", 1, &slot, "flow", nullptr)) return rc;
     hipEvent_t ev = c->ev_slot_done[slot].get();
     if (int rc = wait_unlocked(c, lk, &ev, 1)) return rc;
     HIPCHK(c, hipMemcpy(dst, c->d_flow + (size_t)slot * 2 * c->N, sizeof(float) * 2 * c->N, hipMemcpyDeviceToHost));
@@ -2121,8 +2118,7 @@ int ffl_upload_frames_device(ffl_ctx *c, int first, int n, const ffl_dev_frame *
     if (!c) return FFL_ERR_INVALID;
     std::unique_lock<std::mutex> ul(c->up_mu);
     CtxLock lk(c->mu);
-    if (!frames || n < 1 || first < 0 || first + n > c->n_fslots)
-        return set_err(c, FFL_ERR_INVALID, "%s: bad frame slot range %d..%d", fn, first, first + n - 1);
+    if (int rc = check_frame_run(c, fn, first, n, frames)) return rc;
     FrontParams p;
     for (int i = 0; i < n; i++)
         if (int rc = dev_frame_check(c, fn, i, fmt, sw, sh, &frames[i], rw, rh, cx, cy, c->w, c->h, &p)) return rc;
@@ -2202,10 +2198,7 @@ int ffl_export_flows(ffl_ctx *c, int n, const int *slots, float *dst, int layout
         return set_err(c, FFL_ERR_INVALID, "%s: dst and the item stride (%td) must be multiples of 4 bytes", fn, item_stride);
     if (n > 1 && (size_t)(item_stride < 0 ? -item_stride : item_stride) < item)
         return set_err(c, FFL_ERR_INVALID, "%s: item stride %td is smaller than one flow field (%zu bytes)", fn, item_stride, item);
-    for (int i = 0; i < n; i++) {
-        if (slots[i] < 0 || slots[i] >= c->n_slots) return set_err(c, FFL_ERR_INVALID, "%s: flow slot %d out of range", fn, slots[i]);
-        if (!c->slot_state[slots[i]]) return set_err(c, FFL_ERR_STATE, "%s: flow slot %d holds no flow", fn, slots[i]);
-    }
+    if (int rc = check_flow_slots(c, fn, n, slots, "flow", nullptr)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t cst;
     if (int rc = caller_stream(c, fn, stream, &cst)) return rc;
@@ -2223,8 +2216,7 @@ int ffl_export_flows(ffl_ctx *c, int n, const int *slots, float *dst, int layout
     }
     HIPCHK(c, hipGetLastError());
     EvRef ev;
-    HIPCHK(c, c->post_ring.record(c->s_post, &ev));
-    for (int i = 0; i < n; i++) c->ev_slot_done[slots[i]] = ev;  // a batch recycling a slot waits for the export
+    if (int rc = publish_post(c, n, slots, &ev)) return rc;  // a batch recycling a slot waits for the export
     HIPCHK(c, hipStreamWaitEvent(cst, ev.get(), 0));
     return FFL_OK;
 }
@@ -2281,12 +2273,7 @@ int ffl_import_flows(ffl_ctx *c, int n, const int *slots, const ffl_dev_flow *f,
     if (n < 1 || n > c->max_batch)
         return set_err(c, FFL_ERR_INVALID, "%s: n = %d fields outside 1..%d (the context's max_batch)", fn, n, c->max_batch);
     if (!slots) return set_err(c, FFL_ERR_INVALID, "%s: NULL flow_slots", fn);
-    std::vector<char> seen(c->n_slots, 0);
-    for (int i = 0; i < n; i++) {
-        if (slots[i] < 0 || slots[i] >= c->n_slots) return set_err(c, FFL_ERR_INVALID, "%s: flow slot %d out of range", fn, slots[i]);
-        if (seen[slots[i]]) return set_err(c, FFL_ERR_INVALID, "%s: flow slot %d repeated in one call", fn, slots[i]);
-        seen[slots[i]] = 1;
-    }
+    if (int rc = check_flow_slots(c, fn, n, slots, nullptr, "repeated in one call")) return rc;
     int mode;
     size_t bytes;
     if (int rc = dev_flow_check(c, fn, dtype, n, c->w, c->h, f, &mode, &bytes)) return rc;
@@ -2318,8 +2305,7 @@ int ffl_import_flows(ffl_ctx *c, int n, const int *slots, const ffl_dev_flow *f,
     }
     HIPCHK(c, hipGetLastError());
     EvRef done;
-    HIPCHK(c, c->post_ring.record(c->s_post, &done));
-    publish_slots(c, n, slots, done, true);
+    if (int rc = publish_post(c, n, slots, &done)) return rc;
     // the caller's later work (overwriting or freeing the sources) runs after the fields have been read
     HIPCHK(c, hipStreamWaitEvent(cst, done.get(), 0));
     return FFL_OK;
@@ -2329,7 +2315,7 @@ int ffl_upload_flow(ffl_ctx *c, int slot, const float *src, int pov_mode) {
     if (!c) return FFL_ERR_INVALID;
     std::unique_lock<std::mutex> pl(c->post_mu);
     CtxLock lk(c->mu);
-    if (slot < 0 || slot >= c->n_slots || !src) return set_err(c, FFL_ERR_INVALID, "ffl_upload_flow: bad arguments");
+    if (!flow_slot_ok(c, slot) || !src) return set_err(c, FFL_ERR_INVALID, "ffl_upload_flow: bad arguments");
     hipStream_t st = c->s_post;
     hipEvent_t ev = c->ev_slot_done[slot].get();  // the slot's last batch or pass 2 still reads or writes it
     if (int rc = wait_unlocked(c, lk, &ev, 1)) return rc;
@@ -2346,8 +2332,7 @@ int ffl_upload_flow(ffl_ctx *c, int slot, const float *src, int pov_mode) {
         ffl_launch_pass1(&c->d_ptab->pt, 1, c->w, c->h, pov_mode, c->d_ppkey, c->d_rpsum, st);
     }
     EvRef done;
-    HIPCHK(c, c->post_ring.record(st, &done));
-    publish_slots(c, 1, &slot, done, true);
+    if (int rc = publish_post(c, 1, &slot, &done)) return rc;
     HIPCHK(c, hipGetLastError());
     return FFL_OK;
 }
@@ -2357,7 +2342,7 @@ int ffl_submit_pair(ffl_ctx *c, int slot, const uint8_t *prev, const uint8_t *ne
     if (!c) return FFL_ERR_INVALID;
     // no lock around the three calls (each takes its own; holding `mu` here would invert the up_mu -> mu order): calls on
     // distinct slots from several threads interleave safely, n_fslots / n_slots are fixed at creation
-    if (slot < 0 || 2 * slot + 1 >= c->n_fslots || slot >= c->n_slots) {
+    if (!flow_slot_ok(c, slot) || 2 * slot + 1 >= c->n_fslots) {
         CtxLock lk(c->mu);
         return set_err(c, FFL_ERR_INVALID, "ffl_submit_pair: slot %d needs frame slots %d,%d and a flow slot", slot, 2 * slot, 2 * slot + 1);
     }
@@ -2388,84 +2373,30 @@ int ffl_sync(ffl_ctx *c) {
     return wait_unlocked(c, lk, evs.data(), (int)evs.size());
 }
 
-// one knob of an option set; `live`: the set belongs to an existing context (its lane count is fixed)
+// one knob of an option set, described by its row of kFflOptionRows; `live`: the set belongs to an existing context (its
+// lane count is fixed).  The two knobs that are more than a row: "blur_tile_h" is fixed at 16 (the box-sum order is
+// anchored to blocks of 16 rows) and is no member of the set; "lanes" is a property of a live context's buffers.
+static const char kFixedTileH[] = "blur_tile_h";
+static const FflOptionRow *option_row(const char *name) {
+    for (const FflOptionRow &r : kFflOptionRows)
+        if (!strcmp(name, r.name)) return &r;
+    return nullptr;
+}
+
 static int set_option_impl(FflOptions &o, const char *name, int value, bool live) {
-    if (!strcmp(name, "blur_tile_h")) {  // fixed: the box-sum order is anchored to blocks of 16 rows
-        return value == 16 ? FFL_OK : FFL_ERR_INVALID;
-    }
-    if (!strcmp(name, "fuse_first")) {  // minimum tiles x pairs of a level for the folded first launch; 0: never
-        if (value < 0) return FFL_ERR_INVALID;
-        o.fuse_first = value;
-        return FFL_OK;
-    }
-    if (!strcmp(name, "merge_expand")) {  // 1 (default): merged frame-expansion launches, 0: one set per level
-        o.merge_expand = value != 0;
-        return FFL_OK;
-    }
-    if (!strcmp(name, "blur_rows")) {  // tiles a k_blur_solve workgroup walks down: 0 automatic, 1..64
-        if (value < 0 || value > 64) return FFL_ERR_INVALID;
-        o.blur_rows = value;
-        return FFL_OK;
-    }
-    if (!strcmp(name, "blur_min_wgs")) {  // automatic strip length: the longest strips that still give this many workgroups
-        if (value < 1) return FFL_ERR_INVALID;
-        o.blur_min_wgs = value;
-        return FFL_OK;
-    }
-    if (!strcmp(name, "tile_order")) {  // 0 pair-major, 1 tile-major (ffl_tile_coord)
-        if (value < 0 || value > 1) return FFL_ERR_INVALID;
-        o.tile_order = value;
-        return FFL_OK;
-    }
-    if (!strcmp(name, "pyr_coarse")) {  // 1 (default): one-pass kernel for the two coarse pyramid levels, 0: H + V kernel pairs
-        o.pyr_coarse = value != 0;
-        return FFL_OK;
-    }
-    if (!strcmp(name, "fb_general")) {  // 1: the reference's Farneback parameters through the general kernels (tests)
-        if (value < 0 || value > 1) return FFL_ERR_INVALID;
-        o.fb_general = value;
-        return FFL_OK;
-    }
-    if (!strcmp(name, "import_fused")) {  // ffl_import_flows: 1 (default) one fused launch, 0 conversion kernel + pass 1
-        if (value < 0 || value > 1) return FFL_ERR_INVALID;
-        o.import_fused = value;
-        return FFL_OK;
-    }
-    if (!strcmp(name, "copy_threads")) {  // host threads sharing a staging copy of >= 1 MiB (1 = the caller alone)
-        if (value < 1 || value > 16) return FFL_ERR_INVALID;
-        o.copy_threads = value;
-        return FFL_OK;
-    }
-    if (!strcmp(name, "graph")) {  // 1 (default): replay a batch's launches from a captured hipGraph, 0: launch eagerly
-        o.use_graph = value != 0;
-        return FFL_OK;
-    }
-    if (!strcmp(name, "lanes")) {  // compute lanes: a property of the context's buffers, fixed at ffl_create
-        if (value < 1 || value > 4) return FFL_ERR_INVALID;
-        if (live) return value == o.lanes ? FFL_OK : FFL_ERR_STATE;
-        o.lanes = value;
-        return FFL_OK;
-    }
-    if (!strcmp(name, "run_ahead")) {  // frame-only expansion schedule: 0 serial, 1 run-ahead, 2 fork/join
-        if (value < 0 || value > 2) return FFL_ERR_INVALID;
-        o.run_ahead = value;
-        return FFL_OK;
-    }
-    return FFL_ERR_INVALID;
+    if (!strcmp(name, kFixedTileH)) return value == 16 ? FFL_OK : FFL_ERR_INVALID;
+    const FflOptionRow *r = option_row(name);
+    if (!r || value < r->lo || value > r->hi) return FFL_ERR_INVALID;
+    if (live && r->member == &FflOptions::lanes) return value == o.lanes ? FFL_OK : FFL_ERR_STATE;
+    o.*r->member = r->flag ? value != 0 : value;
+    return FFL_OK;
 }
 
 static int get_option_impl(const FflOptions &o, const char *name, int *value) {
-    struct { const char *n; int v; } tab[] = {
-        {"blur_tile_h", 16}, {"fuse_first", o.fuse_first}, {"merge_expand", o.merge_expand}, {"blur_rows", o.blur_rows},
-        {"blur_min_wgs", o.blur_min_wgs}, {"tile_order", o.tile_order}, {"pyr_coarse", o.pyr_coarse},
-        {"copy_threads", o.copy_threads}, {"graph", o.use_graph}, {"lanes", o.lanes}, {"run_ahead", o.run_ahead},
-        {"fb_general", o.fb_general}, {"import_fused", o.import_fused}};
-    for (auto &t : tab)
-        if (!strcmp(name, t.n)) {
-            *value = t.v;
-            return FFL_OK;
-        }
-    return FFL_ERR_INVALID;
+    const FflOptionRow *r = option_row(name);
+    if (!r && strcmp(name, kFixedTileH)) return FFL_ERR_INVALID;
+    *value = r ? o.*r->member : 16;
+    return FFL_OK;
 }
 
 int ffl_set_option(const char *name, int value) {

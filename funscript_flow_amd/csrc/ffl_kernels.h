@@ -10,6 +10,7 @@
 // one channel; the bilinear gather of R1 in UpdateMatrices then hits mostly-shared cache lines.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
 
 #define FFL_MAXB 256                 // pairs per batch (= FFL_MAX_BATCH of include/ffl.h)
@@ -136,6 +137,28 @@ struct FflOptions {
     int pyr_coarse = 1;     // one-pass kernel for the x1/4 and x1/8 pyramid levels where sizes allow
     int fb_general = 0;     // 1: ffl_flow_pairs_farneback runs the reference's parameters through the general kernels too
     int import_fused = 1;   // ffl_import_flows: 1 k_import_pass1 (conversion + pass 1 in one read), 0 conversion, then pass 1
+};
+// The knobs by name (host only; ffl_api.hip sets and reads them through this table): accepted values lo..hi, and `flag`
+// when any value is accepted and stored as != 0.  A new knob is a member above and a row here.
+struct FflOptionRow {
+    const char *name;
+    int FflOptions::*member;
+    int lo, hi;
+    bool flag;
+};
+inline constexpr FflOptionRow kFflOptionRows[] = {
+    {"lanes", &FflOptions::lanes, 1, 4, false},
+    {"run_ahead", &FflOptions::run_ahead, 0, 2, false},
+    {"fuse_first", &FflOptions::fuse_first, 0, INT_MAX, false},
+    {"merge_expand", &FflOptions::merge_expand, INT_MIN, INT_MAX, true},
+    {"graph", &FflOptions::use_graph, INT_MIN, INT_MAX, true},
+    {"copy_threads", &FflOptions::copy_threads, 1, 16, false},
+    {"blur_rows", &FflOptions::blur_rows, 0, 64, false},
+    {"blur_min_wgs", &FflOptions::blur_min_wgs, 1, INT_MAX, false},
+    {"tile_order", &FflOptions::tile_order, 0, 1, false},
+    {"pyr_coarse", &FflOptions::pyr_coarse, INT_MIN, INT_MAX, true},
+    {"fb_general", &FflOptions::fb_general, 0, 1, false},
+    {"import_fused", &FflOptions::import_fused, 0, 1, false},
 };
 
 // ---- launchers (each enqueues on `st` and returns; no synchronisation) ----------------------

@@ -55,6 +55,20 @@ def _check(ctx, frames, recs, want_of, pov=False):
         pr.check_mean_mag(mm, ref)
 
 
+@pytest.mark.parametrize("w,h,scales", [(16, 16, 1),      # no coarser level
+                                        (64, 64, 2),      # exactly one: 32 passes min_size, 16 does not
+                                        (63, 65, 1),      # 31.5 columns: just under that boundary on one side
+                                        (130, 66, 2),     # 65 x 33, then 32.5 x 16.5 is refused
+                                        (258, 257, 4)])   # 129 x 128 (128.5 rounds to even), 64 x 64, 32 x 32
+def test_context_level_geometry_equals_the_restatement_at_the_defaults(w, h, scales):
+    """The levels a context of the tuned path is built with (ffl_num_levels, ffl_level_size) are the ones the plain-C
+    restatement derives for the reference's parameters: the tuned and the general plan come from one level rule."""
+    assert fbr.geometry(w, h) == scales
+    with _capi.Context(w, h, max_batch=1) as ctx:
+        assert ctx.num_levels() == scales - 1
+        assert [ctx.level_size(k) for k in range(scales)] == [fbr.level_params(w, h, None, k)[:2] for k in range(scales)]
+
+
 @pytest.mark.parametrize("w,h,B", [(256, 256, 64), (640, 360, 8), (333, 197, 4), (1920, 1080, 32)])
 def test_general_kernels_at_the_defaults_equal_the_oracle(w, h, B):
     frames = _stream(w, h, B + 1)

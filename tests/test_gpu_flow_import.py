@@ -190,8 +190,11 @@ def test_device_refusals():
             ctx.import_flows(Cai(t.data_ptr(), (2, h, w, 2), (1 << 32, w * 8, 8, 4)), [0, 1])
         with pytest.raises(_capi.FFLError, match="outside 1..2"):
             ctx.import_flows(torch.zeros((3, h, w, 2), device=DEV), [0, 1, 2])
-        with pytest.raises(_capi.FFLError, match="repeated"):
-            ctx.import_flows(t, [1, 1])
+        for _ in range(2):                              # refused twice in a row, and the refusal leaves no mark behind:
+            with pytest.raises(_capi.FFLError, match="repeated"):
+                ctx.import_flows(t, [1, 1])
+        ctx.import_flows(t, [1, 2])                     # a legal import naming the same slot goes through
+        assert ctx.pass1_results([1, 2]) == uploaded_records(ctx, list(t.cpu().numpy()), 1)
         with pytest.raises(_capi.FFLError, match="out of range"):
             ctx.import_flows(t, [0, 4])
         with pytest.raises(ValueError, match="not supported"):

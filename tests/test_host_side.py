@@ -343,6 +343,13 @@ def test_create_rejects_bad_geometry_before_touching_a_device():
                      ({"width": 64, "height": 64, "max_batch": 0}, "bad slot/batch counts")):
         with pytest.raises(_capi.FFLError, match=frag):
             _capi.Context(**kw)
+    # the size rule is one rule: the sizing calls refuse what ffl_create refuses
+    for w, h in ((15, 64), (16384, 16384)):
+        with pytest.raises(_capi.FFLError, match="bad geometry"):
+            _capi.estimate_bytes(w, h, 4, 4, 1)
+        with pytest.raises(ValueError, match="unsupported frame size"):
+            _capi.farneback_geometry(w, h)
+    assert _capi.estimate_bytes(16, 16, 2, 1, 1) and _capi.farneback_geometry(16, 16) == (1, 4 * (2 * 5 + 9) * 256)
     assert _capi.FFL_MAX_BATCH == 256
     hdr = open(os.path.join(ROOT, "include", "ffl.h")).read()
     assert re.search(r"#define FFL_MAX_BATCH\s+256\b", hdr)
@@ -522,6 +529,19 @@ def test_bench_gpus_n_from_a_plain_shell_is_a_launcher(tmp_path):
     assert "needs a GPU" in r.stderr and "launch: rank" in r.stderr
 
 
+_OPTION_TABLE = {  # knob: (default, legal values, lowest accepted or None, highest accepted or None)
+    "fuse_first": (10000, (0, 1, 1 << 30), 0, None),
+    "blur_rows": (0, (64, 1, 0), 0, 64),
+    "blur_min_wgs": (3500, (1, 1 << 30), 1, None),
+    "tile_order": (0, (1, 0), 0, 1),
+    "fb_general": (0, (1, 0), 0, 1),
+    "import_fused": (1, (0, 1), 0, 1),
+    "copy_threads": (4, (1, 16), 1, 16),
+    "lanes": (2, (1, 4), 1, 4),
+    "run_ahead": (0, (2, 1, 0), 0, 2),
+}
+
+
 def test_process_wide_option_defaults_without_a_device():
     """ffl_set_option only sets the defaults new contexts start from (readable without a device); bad names / values are
     refused and leave the default alone."""
@@ -536,9 +556,30 @@ def test_process_wide_option_defaults_without_a_device():
         assert _capi.get_option("lanes") == 3
         with pytest.raises(_capi.FFLError):
             _capi.get_option("nope")
-    finally:
         _capi.set_option("lanes", 2)
         _capi.set_option("blur_min_wgs", 3500)
+        # every knob: a legal value round-trips, the first value outside a bounded range is refused and changes nothing
+        for name, (default, legal, lo, hi) in _OPTION_TABLE.items():
+            assert _capi.get_option(name) == default, name
+            for v in legal:
+                _capi.set_option(name, v)
+                assert _capi.get_option(name) == v, (name, v)
+            _capi.set_option(name, default)
+            for bad in ([] if lo is None else [lo - 1]) + ([] if hi is None else [hi + 1]):
+                with pytest.raises(_capi.FFLError):
+                    _capi.set_option(name, bad)
+                assert _capi.get_option(name) == default, (name, bad)
+        for name in ("merge_expand", "pyr_coarse", "graph"):       # stored as != 0
+            for v, want in ((7, 1), (0, 0), (-3, 1)):
+                _capi.set_option(name, v)
+                assert _capi.get_option(name) == want, (name, v)
+        _capi.set_option("blur_tile_h", 16)                          # fixed: only 16 is accepted, and it reads back 16
+        assert _capi.get_option("blur_tile_h") == 16
+    finally:
+        for name, (default, _, _, _) in _OPTION_TABLE.items():
+            _capi.set_option(name, default)
+        for name in ("merge_expand", "pyr_coarse", "graph"):
+            _capi.set_option(name, 1)
 
 
 _ESTIMATE_BYTES = {  # (w, h, frame slots, flow slots, max_batch): ((device, pinned) at lanes 1, at lanes 2, at lanes 4)
