@@ -23,6 +23,7 @@ EXPORTS = ["ffl_device_count", "ffl_create", "ffl_destroy", "ffl_last_error", "f
            "ffl_profile_read", "ffl_kernel_name", "ffl_device_mem_info", "ffl_estimate_bytes",
            "ffl_dis_default_params", "ffl_dis_geometry", "ffl_flow_pairs_dis", "ffl_debug_dis_pair",
            "ffl_farneback_default_params", "ffl_farneback_geometry", "ffl_farneback_extra_bytes", "ffl_flow_pairs_farneback",
+           "ffl_flow_pairs_farneback_ex",
            "ffl_upload_frames_yuv", "ffl_frontend_yuv_window",
            "ffl_dev_frame_check", "ffl_upload_frames_device", "ffl_export_flows",
            "ffl_dev_flow_check", "ffl_import_flows"]
@@ -136,6 +137,31 @@ def farneback_choice(params):
     if load().ffl_farneback_geometry(64, 64, C.byref(p), None, None) != FFL_OK:
         raise _farneback_error(f"hip_farneback {dict(over)}")
     return None if p.is_default() else p
+
+
+# the mode bits of ffl_flow_pairs_farneback_ex and the window names of params["hip_farneback_window"]
+FFL_FB_USE_INITIAL_FLOW, FFL_FB_GAUSSIAN_WINDOW = 4, 256
+FARNEBACK_WINDOWS = {"box": 0, "gaussian": FFL_FB_GAUSSIAN_WINDOW}
+
+
+def farneback_window(window):
+    """the mode bit of a window name; ValueError names the ones known"""
+    if window not in FARNEBACK_WINDOWS:
+        raise ValueError(f"Farneback window must be one of {tuple(FARNEBACK_WINDOWS)}, got {window!r}")
+    return FARNEBACK_WINDOWS[window]
+
+
+def farneback_mode(params):
+    """"box" (the default) or "gaussian" from params["hip_farneback_window"]: the window of the Farneback batches
+    (cv2.OPTFLOW_FARNEBACK_GAUSSIAN; "gaussian" always runs the general kernels, with "hip_farneback"'s numbers or the
+    reference's).  ValueError for any other name, or for the key together with "hip_flow": "dis"."""
+    if "hip_farneback_window" not in params:
+        return "box"
+    window = params["hip_farneback_window"]
+    farneback_window(window)
+    if params.get("hip_flow", "farneback") == "dis":
+        raise ValueError('"hip_farneback_window" sets the Farneback window: it cannot be combined with "hip_flow": "dis"')
+    return window
 
 
 def dis_geometry(width, height, params=None):
@@ -413,6 +439,7 @@ def load():
     L.ffl_farneback_geometry.argtypes = [C.c_int, C.c_int, fp_, ip, C.POINTER(C.c_size_t)]
     L.ffl_farneback_extra_bytes.argtypes = [C.c_int, C.c_int, C.c_int, fp_, C.POINTER(C.c_size_t)]
     L.ffl_flow_pairs_farneback.argtypes = [vp, C.c_int, ip, ip, ip, C.c_int, fp_]
+    L.ffl_flow_pairs_farneback_ex.argtypes = [vp, C.c_int, ip, ip, ip, C.c_int, fp_, C.c_uint]
     L.ffl_dev_frame_check.argtypes = [C.c_int, C.c_int, C.c_int, vp] + [C.c_int] * 6
     L.ffl_upload_frames_device.argtypes = [vp, C.c_int, C.c_int, vp] + [C.c_int] * 7 + [C.c_uint64]
     L.ffl_export_flows.argtypes = [vp, C.c_int, ip, vp, C.c_int, C.c_ssize_t, C.c_uint64]
@@ -699,15 +726,22 @@ class Context:
         self._chk(self.L.ffl_flow_pairs_dis(self._h, n, p0, p1, ps, int(bool(pov_mode)),
                                             None if params is None else C.byref(params)))
 
-    def flow_pairs_farneback(self, fslot0, fslot1, flow_slots, pov_mode=False, params=None):
+    def flow_pairs_farneback(self, fslot0, fslot1, flow_slots, pov_mode=False, params=None, window="box",
+                             initial_flow=False):
         """ffl_flow_pairs_farneback: Farneback with caller-chosen parameters (FarnebackParams; None or the defaults = the
-        tuned path of flow_pairs) + pass 1 for a batch of pairs."""
+        tuned path of flow_pairs) + pass 1 for a batch of pairs.  window "gaussian" and initial_flow (each pair starts from
+        the flow its flow slot already holds, then overwrites it) are the modes of ffl_flow_pairs_farneback_ex, which is
+        called only when one of them is set; either runs the general kernels."""
         n = len(flow_slots)
         (p0, k0), (p1, k1), (ps, ks) = _iarr(fslot0), _iarr(fslot1), _iarr(flow_slots)
         if len(k0) != n or len(k1) != n:
             raise FFLError("flow_pairs_farneback: the three slot lists must have one entry per pair")
-        self._chk(self.L.ffl_flow_pairs_farneback(self._h, n, p0, p1, ps, int(bool(pov_mode)),
-                                                  None if params is None else C.byref(params)))
+        mode = farneback_window(window) | (FFL_FB_USE_INITIAL_FLOW if initial_flow else 0)
+        pp = None if params is None else C.byref(params)
+        if mode:
+            self._chk(self.L.ffl_flow_pairs_farneback_ex(self._h, n, p0, p1, ps, int(bool(pov_mode)), pp, mode))
+        else:
+            self._chk(self.L.ffl_flow_pairs_farneback(self._h, n, p0, p1, ps, int(bool(pov_mode)), pp))
 
     def submit_pair(self, slot, prev, nxt, pov_mode=False):
         prev, nxt = np.ascontiguousarray(prev), np.ascontiguousarray(nxt)

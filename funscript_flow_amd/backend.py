@@ -9,7 +9,8 @@ Same names, argument meaning and result shape as the reference's pair functions:
     precompute_all(pairs, params)          the whole `pool.starmap(precompute_wrapper, ...)` of FF:1190-1191
     (params["hip_flow"] = "dis" runs DIS -- the reference's "DNN" branch, FF:948-980 -- instead of Farneback;
     params["hip_dis"] = {field: value} overrides single _capi.DisParams fields; params["hip_farneback"] = {cv2 keyword: value}
-    sets calcOpticalFlowFarneback's parameters)
+    sets calcOpticalFlowFarneback's parameters and params["hip_farneback_window"] = "gaussian" its
+    OPTFLOW_FARNEBACK_GAUSSIAN window)
     radial_all(precomputed, centers, pov_mode)   the whole ProcessPoolExecutor loop of FF:1232-1236
     get_available_backends()               FF:32-63  (reports "HIP" when a device is usable)
 
@@ -85,6 +86,7 @@ def precompute_flow_info(p0, p1, config):
         raise ValueError(f"funscript_flow_amd implements backend 'HIP' only, got {backend!r}")
     flow, dis = _capi.flow_choice(config)   # "hip_flow": "farneback" (default) | "dis" (the reference's DNN branch, FF:948-980)
     fb = _capi.farneback_choice(config)     # "hip_farneback": {cv2 keyword: value}; None = the reference's values
+    win = _capi.farneback_mode(config)      # "hip_farneback_window": "box" (default) | "gaussian"
     cut_threshold = config.get("cut_threshold", 7)
     h, w = p0.shape[:2]
     if p1.shape != p0.shape:
@@ -102,9 +104,10 @@ def precompute_flow_info(p0, p1, config):
     if flow == "dis":
         ctx.upload_frames(2 * slot, [p0, p1])
         ctx.flow_pairs_dis([2 * slot], [2 * slot + 1], [slot], bool(config.get("pov_mode")), dis)
-    elif fb is not None:
+    elif fb is not None or win != "box":
         ctx.upload_frames(2 * slot, [p0, p1])
-        ctx.flow_pairs_farneback([2 * slot], [2 * slot + 1], [slot], bool(config.get("pov_mode")), fb)
+        ctx.flow_pairs_farneback([2 * slot], [2 * slot + 1], [slot], bool(config.get("pov_mode")), fb,
+                                 **({"window": win} if win != "box" else {}))
     else:
         ctx.submit_pair(slot, p0, p1, bool(config.get("pov_mode")))
     x, y, val, mean_mag, cut = ctx.pass1_result(slot, float(cut_threshold))
@@ -217,6 +220,7 @@ def precompute_all(pairs, params):
         raise ValueError("funscript_flow_amd implements backend 'HIP' only")
     flow, dis = _capi.flow_choice(params)
     fb = _capi.farneback_choice(params)
+    win = _capi.farneback_mode(params)
     pairs = list(pairs)
     if not pairs:
         return []
@@ -244,6 +248,7 @@ def precompute_all(pairs, params):
     pov, thr = bool(params.get("pov_mode")), float(params.get("cut_threshold", 7))
     eng = pipeline.PairEngine.__new__(pipeline.PairEngine)   # slots are sized for the chunk here, not for a stream
     eng.ctx, eng.B, eng.upload, eng.flow, eng.dis, eng.farneback = ctx, B, ctx.upload_frames, flow, dis, fb
+    eng.window = win
     eng.depth = 2 if ctx.frame_slots >= pipeline.min_frame_slots(B, 2) else 1
     out = [None] * len(pairs)
     serial = ctx._chunk_serial

@@ -1668,6 +1668,11 @@ static int submit_pairs(ffl_ctx *c, int n, const int *f0, const int *f1, const i
     CtxLock lk(c->mu);
     int rc = check_pairs(c, n, f0, f1, slots);
     if (rc) return rc;
+    // F.8: a seeded batch reads its flow slots before it overwrites them.  The read runs behind each slot's last user like
+    // any recycled slot's write: queue_batch makes the lane's stream wait for the slot's ev_slot_done reference.
+    if (fbg && (fbg->mode & FFL_FB_USE_INITIAL_FLOW) &&
+        (rc = check_flow_slots(c, "ffl_flow_pairs_farneback_ex", n, slots, "flow", nullptr)))
+        return rc;
     DisKParams k;
     if (dis && (rc = dis_kparams(c, p, n, &k))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
@@ -1750,8 +1755,10 @@ static const char *fbg_check(const ffl_farneback_params &p) {
     return nullptr;
 }
 
-// The plan of p on a w x h frame (levels, sizes, Gaussians, PolyExp constants, R layout); nullptr or the reason it is refused
-static const char *fbg_plan(int w, int h, const ffl_farneback_params &p, FbgPlan *pl, char *why, size_t why_len) {
+// The plan of p on a w x h frame (levels, sizes, Gaussians, PolyExp constants, R layout) under the mode bits of
+// ffl_flow_pairs_farneback_ex, which has checked them (0 everywhere else: sizes and memory do not depend on them); nullptr or
+// the reason it is refused
+static const char *fbg_plan(int w, int h, const ffl_farneback_params &p, unsigned mode, FbgPlan *pl, char *why, size_t why_len) {
     if (const char *e = fbg_check(p)) return e;
     if (!frame_size_ok(w, h)) {
         snprintf(why, why_len, FFL_FRAME_SIZE_RULE, w, h);
@@ -1766,6 +1773,23 @@ static const char *fbg_plan(int w, int h, const ffl_farneback_params &p, FbgPlan
     pl->poly_n = p.poly_n;
     pl->m = p.winsize / 2;
     pl->mul = (float)(1.0 / ps);
+    pl->mode = mode;
+    // F.7: the Gaussian window's taps, sigma = 0.3 m
+    pl->win.m = pl->m;
+    const double wsig = pl->m * 0.3;
+    double wsum = 1.0;
+    pl->win.k[0] = 1.f;
+    for (int i = 1; i <= pl->m; i++) {
+        const float t = (float)exp(-(i * i) / (2 * wsig * wsig));
+        pl->win.k[i] = t;
+        wsum += t * 2;
+    }
+    wsum = 1. / wsum;
+    for (int i = 0; i <= pl->m; i++) pl->win.k[i] = (float)(pl->win.k[i] * wsum);
+    // F.8: the coarsest level's scale, by F.1's repeated multiplication
+    double sc = 1.0;
+    for (int i = 0; i < pl->levels; i++) sc *= ps;
+    pl->seed_scale = (float)sc;
     size_t off = 0;
     for (int k = 0; k <= pl->levels; k++) {
         const int ks = r.ksize[k];
@@ -1796,7 +1820,7 @@ int ffl_farneback_geometry(int width, int height, const ffl_farneback_params *p,
     if (!p) return set_err(nullptr, FFL_ERR_INVALID, "ffl_farneback_geometry: params is NULL");
     FbgPlan pl;
     char why[160];
-    if (const char *e = fbg_plan(width, height, *p, &pl, why, sizeof why))
+    if (const char *e = fbg_plan(width, height, *p, 0, &pl, why, sizeof why))
         return set_err(nullptr, FFL_ERR_INVALID, "ffl_farneback_geometry: %s", e);
     if (n_scales) *n_scales = pl.levels + 1;
     if (work_bytes_per_pair) *work_bytes_per_pair = sizeof(float) * fbg_pair_floats(pl, (size_t)width * height);
@@ -1810,7 +1834,7 @@ int ffl_farneback_extra_bytes(int width, int height, int max_batch, const ffl_fa
         return set_err(nullptr, FFL_ERR_INVALID, "ffl_farneback_extra_bytes: bad arguments");
     FbgPlan pl;
     char why[160];
-    if (const char *e = fbg_plan(width, height, *p, &pl, why, sizeof why))
+    if (const char *e = fbg_plan(width, height, *p, 0, &pl, why, sizeof why))
         return set_err(nullptr, FFL_ERR_INVALID, "ffl_farneback_extra_bytes: %s", e);
     const size_t r_cap = context_layout(width, height, 2, 1, max_batch).R;  // R does not depend on the slot counts
     const size_t need = pl.r_frame * 2 * (size_t)max_batch;
@@ -1865,9 +1889,31 @@ int ffl_flow_pairs_farneback(ffl_ctx *c, int n, const int *fslot0, const int *fs
     if (fbg_is_default(q) && !force) return ffl_flow_pairs(c, n, fslot0, fslot1, flow_slots, pov_mode);
     FbgPlan pl;
     char why[160];
-    if (const char *e = fbg_plan(c->w, c->h, q, &pl, why, sizeof why)) {
+    if (const char *e = fbg_plan(c->w, c->h, q, 0, &pl, why, sizeof why)) {
         CtxLock lk(c->mu);
         return set_err(c, FFL_ERR_INVALID, "ffl_flow_pairs_farneback: %s", e);
+    }
+    return submit_pairs(c, n, fslot0, fslot1, flow_slots, pov_mode, false, nullptr, &pl);
+}
+
+// mode == 0 is ffl_flow_pairs_farneback; any other mode runs the general kernels, at the default numbers too
+int ffl_flow_pairs_farneback_ex(ffl_ctx *c, int n, const int *fslot0, const int *fslot1, const int *flow_slots, int pov_mode,
+                                const ffl_farneback_params *p, unsigned mode) {
+    if (mode == 0) return ffl_flow_pairs_farneback(c, n, fslot0, fslot1, flow_slots, pov_mode, p);
+    if (const unsigned unknown = mode & ~(FFL_FB_USE_INITIAL_FLOW | FFL_FB_GAUSSIAN_WINDOW)) {
+        CtxLock lk;
+        if (c) lk = CtxLock(c->mu);
+        return set_err(c, FFL_ERR_INVALID, "ffl_flow_pairs_farneback_ex: unknown mode bit(s) 0x%x (known: "
+                       "FFL_FB_USE_INITIAL_FLOW 4, FFL_FB_GAUSSIAN_WINDOW 256)", unknown);
+    }
+    if (!c) return FFL_ERR_INVALID;
+    ffl_farneback_params d;
+    ffl_farneback_default_params(&d);
+    FbgPlan pl;
+    char why[160];
+    if (const char *e = fbg_plan(c->w, c->h, p ? *p : d, mode, &pl, why, sizeof why)) {
+        CtxLock lk(c->mu);
+        return set_err(c, FFL_ERR_INVALID, "ffl_flow_pairs_farneback_ex: %s", e);
     }
     return submit_pairs(c, n, fslot0, fslot1, flow_slots, pov_mode, false, nullptr, &pl);
 }

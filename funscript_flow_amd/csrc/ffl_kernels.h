@@ -393,9 +393,18 @@ struct FbgPoly {              // FarnebackPrepareGaussian(poly_n, poly_sigma)
     float g[8], xg[8], xxg[8];
     double ig11, ig03, ig33, ig55;
 };
+#define FBG_USE_INITIAL_FLOW 4u   // = FFL_FB_USE_INITIAL_FLOW, FFL_FB_GAUSSIAN_WINDOW of include/ffl.h
+#define FBG_GAUSSIAN_WINDOW 256u
+struct FbgWin {               // F.7: the Gaussian window's taps k[0..m] (m = winsize / 2, sigma = 0.3 m), host-computed
+    float k[FBG_MAX_M + 1];
+    int m;
+};
 struct FbgPlan {              // one parameter set on one frame size (host-side; kernels take pieces of it by value)
-    int levels, iterations, poly_n, m;  // levels actually used (A.1's min_size rule), box half-width m = winsize / 2
+    int levels, iterations, poly_n, m;  // levels actually used (A.1's min_size rule), window half-width m = winsize / 2
     float mul;                          // (float)(1 / pyr_scale): the flow upsample factor
+    unsigned mode;                      // FBG_* bits of ffl_flow_pairs_farneback_ex (0: box window, zero initial flow)
+    FbgWin win;                         // the window's taps when mode has FBG_GAUSSIAN_WINDOW
+    float seed_scale;                   // F.8: (float)pyr_scale^levels, the factor of the coarsest level's seeded flow
     int lw[FBG_MAX_SCALES], lh[FBG_MAX_SCALES];
     FbgGauss gk[FBG_MAX_SCALES];
     FbgPoly poly;

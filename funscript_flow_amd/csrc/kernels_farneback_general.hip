@@ -10,8 +10,12 @@
 //                                                ->  PolyExp<poly_n> (I -> R_k)
 //   per level k, coarse to fine (z = pair):      flow init (zero / upsample x 1/pyr_scale)  ->  UpdateMatrices
 //                                                ->  iterations x (box + solve [-> UpdateMatrices])
+// Under ffl_flow_pairs_farneback_ex's modes the window is the float Gaussian of F.7 (k_fbg_gauss_solve) and the coarsest
+// level starts from the pair's flow slot reduced by INTER_AREA (F.8, k_fbg_flow_area) instead of zero.
 // T and B live in the M area and I in flow buffer fa: none of them is live once the frames are expanded.
 #include "ffl_kernels.h"
+#include <float.h>
+#include <math.h>
 
 namespace {
 
@@ -277,8 +281,153 @@ __global__ __launch_bounds__(256) void k_fbg_box_solve(const PairTab *pt, const 
     }
 }
 
+static int cv_round(double v) { return (int)lrint(v); }  // cvRound: the whole-number ratios of F.8 (b)
+
 static size_t box_lds_bytes(int m) {
     return sizeof(double) * BS_H * (BS_W + 2 * m) + sizeof(float) * (BS_H + 2 * m) * (BS_W + 2 * m);
+}
+
+static size_t gauss_lds_bytes(int m) { return sizeof(float) * ((BS_H + 2 * m) + BS_H) * (BS_W + 2 * m); }
+
+// FarnebackUpdateFlow_GaussianBlur (F.7): the separable float Gaussian of the five M planes (rows of the window first, then
+// columns; REPLICATE) + the 2x2 solve in double, one 64 x 16 tile, channel by channel: M_c's (16 + 2m) x (64 + 2m)
+// neighbourhood in LDS, the vertical sums of 16 x (64 + 2m) positions in LDS (float), then the horizontal sums per output.
+// No 1 / winsize^2 scale: the taps sum to one.
+__global__ __launch_bounds__(256) void k_fbg_gauss_solve(const PairTab *pt, const float *M, size_t M_stride, float *flowbuf,
+                                                         size_t f_stride, bool slot, int w, int h, FbgWin win) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int m = win.m, TW = BS_W + 2 * m, TH = BS_H + 2 * m;
+    float *sM = reinterpret_cast<float *>(smem);  // [TH][TW]
+    float *sV = sM + TH * TW;                     // [BS_H][TW]
+    const int b = blockIdx.z, x0 = blockIdx.x * BS_W, y0 = blockIdx.y * BS_H;
+    const size_t pl = (size_t)w * h;
+    const float *Mb = M + (size_t)b * M_stride;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    float g[5][4];
+    for (int c = 0; c < 5; c++) {
+        const float *src = Mb + c * pl;
+        __syncthreads();  // the previous channel's horizontal sums are done with sV / sM
+        for (int i = threadIdx.x; i < TW * TH; i += blockDim.x) {
+            const int r = i / TW, cc = i - r * TW;
+            sM[i] = src[(size_t)clampi(y0 - m + r, 0, h - 1) * w + clampi(x0 - m + cc, 0, w - 1)];
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < TW * BS_H; i += blockDim.x) {
+            const int t = i / TW, cc = i - t * TW;
+            const float *col = sM + (t + m) * TW + cc;  // row y0 + t of the tile's LDS copy
+            float v = col[0] * win.k[0];
+            for (int j = 1; j <= m; j++) v = v + (col[j * TW] + col[-j * TW]) * win.k[j];
+            sV[i] = v;
+        }
+        __syncthreads();
+        for (int k = 0; k < 4; k++) {
+            const float *row = sV + (ty + 4 * k) * TW + tx + m;
+            float a = row[0] * win.k[0];
+            for (int j = 1; j <= m; j++) a = a + win.k[j] * (row[-j] + row[j]);
+            g[c][k] = a;
+        }
+    }
+    const int x = x0 + tx;
+    if (x >= w) return;
+    float *f = fbg_flow(pt, flowbuf, f_stride, b, slot);
+    for (int k = 0; k < 4; k++) {
+        const int y = y0 + ty + 4 * k;
+        if (y >= h) break;
+        const double g11 = g[0][k], g12 = g[1][k], g22 = g[2][k], h1 = g[3][k], h2 = g[4][k];
+        const double idet = 1. / (g11 * g22 - g12 * g12 + 1e-3);
+        f[((size_t)y * w + x) * 2] = (float)((g11 * h2 - g12 * h1) * idet);
+        f[((size_t)y * w + x) * 2 + 1] = (float)((g22 * h1 - g12 * h2) * idet);
+    }
+}
+
+// F.8 (c): the entries of destination index d on an axis of S source and D destination positions (s = S / D), in order:
+// an optional left partial cell (s1 - 1, al), the whole cells s1 .. s2 - 1 (af each), an optional right partial cell (s2, ar)
+struct FbgAreaAxis {
+    int s1, s2, n;
+    bool left, right;
+    float al, af, ar;
+};
+__device__ __forceinline__ FbgAreaAxis fbg_area_axis(int d, double s, int S) {
+    FbgAreaAxis a;
+    const double f1 = d * s, f2 = f1 + s, cw = fmin(s, S - f1);
+    int s1 = (int)ceil(f1), s2 = min((int)floor(f2), S - 1);
+    s1 = min(s1, s2);
+    a.s1 = s1;
+    a.s2 = s2;
+    a.left = s1 - f1 > 1e-3;
+    a.right = f2 - s2 > 1e-3;
+    a.al = (float)((s1 - f1) / cw);
+    a.af = (float)(1.0 / cw);
+    a.ar = (float)(fmin(fmin(f2 - s2, 1.0), cw) / cw);
+    a.n = (int)a.left + (s2 - s1) + (int)a.right;
+    return a;
+}
+__device__ __forceinline__ void fbg_area_entry(const FbgAreaAxis &a, int e, int S, int &idx, float &alpha) {
+    const int j = e - (int)a.left;
+    if (j < 0) {
+        idx = a.s1 - 1;
+        alpha = a.al;
+    } else if (j < a.s2 - a.s1) {
+        idx = a.s1 + j;
+        alpha = a.af;
+    } else {
+        idx = a.s2;
+        alpha = a.ar;
+    }
+    idx = clampi(idx, 0, S - 1);  // the rule keeps every index inside; this keeps the read inside whatever the rule gives
+}
+
+// F.8: the coarsest level's initial flow from the pair's full-resolution flow slot: resize(seed, lw x lh, INTER_AREA) *
+// scale.  ix, iy > 0: both ratios are whole numbers (1 x 1: the seed itself; else the ix x iy block sum, row-major, times
+// 1.f / (ix * iy)); ix = iy = 0: the per-axis coefficient entries, row sums first.
+__global__ __launch_bounds__(64) void k_fbg_flow_area(const PairTab *pt, float *cur, size_t stride, int w, int h, int lw,
+                                                      int lh, int ix, int iy, float scale) {
+    const int b = blockIdx.z, y = blockIdx.y, x = blockIdx.x * 64 + threadIdx.x;
+    if (x >= lw) return;
+    const float *seed = pt->flow[0][b];
+    float *f = cur + (size_t)b * stride + ((size_t)y * lw + x) * 2;
+    float s0 = 0.f, s1 = 0.f;
+    if (ix == 1 && iy == 1) {  // (a) the same size: the seed itself
+        s0 = seed[((size_t)y * w + x) * 2];
+        s1 = seed[((size_t)y * w + x) * 2 + 1];
+    } else if (ix > 0) {       // (b)
+        for (int j = 0; j < iy; j++) {
+            const float *row = seed + ((size_t)min(y * iy + j, h - 1) * w) * 2;
+            for (int i = 0; i < ix; i++) {
+                const int sx = min(x * ix + i, w - 1);
+                s0 = s0 + row[sx * 2];
+                s1 = s1 + row[sx * 2 + 1];
+            }
+        }
+        const float inv = 1.f / (ix * iy);
+        s0 = s0 * inv;
+        s1 = s1 * inv;
+    } else {                   // (c)
+        const FbgAreaAxis ax = fbg_area_axis(x, (double)w / lw, w), ay = fbg_area_axis(y, (double)h / lh, h);
+        for (int ey = 0; ey < ay.n; ey++) {
+            int sy;
+            float beta;
+            fbg_area_entry(ay, ey, h, sy, beta);
+            const float *row = seed + (size_t)sy * w * 2;
+            float b0 = 0.f, b1 = 0.f;
+            for (int ex = 0; ex < ax.n; ex++) {
+                int sx;
+                float alpha;
+                fbg_area_entry(ax, ex, w, sx, alpha);
+                b0 = b0 + row[sx * 2] * alpha;
+                b1 = b1 + row[sx * 2 + 1] * alpha;
+            }
+            if (ey == 0) {
+                s0 = beta * b0;
+                s1 = beta * b1;
+            } else {
+                s0 = s0 + beta * b0;
+                s1 = s1 + beta * b1;
+            }
+        }
+    }
+    f[0] = s0 * scale;
+    f[1] = s1 * scale;
 }
 
 }  // namespace
@@ -313,11 +462,26 @@ void ffl_launch_fb_general(const UTab *ut, const PairTab *pt, int n, int nU, con
         float *cur = ((plan.levels - k) & 1) ? wk.fb : wk.fa;
         const float *Rk = wk.R + plan.r_off[k];
         const dim3 pg((lw + 63) / 64, lh, n);
-        k_fbg_flow_init<<<pg, 64, 0, st>>>(pt, prev, cur, fs, slot, pw, ph, lw, lh, plan.mul);
+        if (k == plan.levels && (plan.mode & FBG_USE_INITIAL_FLOW)) {
+            // F.8: the coarsest level starts from the pair's flow slot.  With one scale the slot is the seed as it stands.
+            // Otherwise this read of the slot is queued here, on the stream that level 0 below writes the slot on, so it
+            // precedes that write; the slot's earlier writer is behind the batch's wait for ev_slot_done.
+            if (k > 0) {
+                const double sx = (double)w / lw, sy = (double)h / lh;
+                const int ix = cv_round(sx), iy = cv_round(sy);
+                const bool whole = fabs(sx - ix) < DBL_EPSILON && fabs(sy - iy) < DBL_EPSILON;
+                k_fbg_flow_area<<<pg, 64, 0, st>>>(pt, cur, fs, w, h, lw, lh, whole ? ix : 0, whole ? iy : 0, plan.seed_scale);
+            }
+        } else {
+            k_fbg_flow_init<<<pg, 64, 0, st>>>(pt, prev, cur, fs, slot, pw, ph, lw, lh, plan.mul);
+        }
         k_fbg_update_matrices<<<pg, 64, 0, st>>>(pt, Rk, plan.r_frame, cur, fs, slot, wk.M, 5 * N, lw, lh);
         const dim3 bg((lw + BS_W - 1) / BS_W, (lh + BS_H - 1) / BS_H, n);
         for (int it = 0; it < plan.iterations; it++) {
-            k_fbg_box_solve<<<bg, 256, box_lds_bytes(plan.m), st>>>(pt, wk.M, 5 * N, cur, fs, slot, lw, lh, plan.m);
+            if (plan.mode & FBG_GAUSSIAN_WINDOW)
+                k_fbg_gauss_solve<<<bg, 256, gauss_lds_bytes(plan.m), st>>>(pt, wk.M, 5 * N, cur, fs, slot, lw, lh, plan.win);
+            else
+                k_fbg_box_solve<<<bg, 256, box_lds_bytes(plan.m), st>>>(pt, wk.M, 5 * N, cur, fs, slot, lw, lh, plan.m);
             if (it < plan.iterations - 1)
                 k_fbg_update_matrices<<<pg, 64, 0, st>>>(pt, Rk, plan.r_frame, cur, fs, slot, wk.M, 5 * N, lw, lh);
         }

@@ -72,18 +72,22 @@ def shard_pairs(n_items, world, rank, assign="contiguous", block=1):
     return idx[(idx // block) % world == rank]
 
 
-OWN = object()   # pass1 / pass1_pairs / process_chunk `farneback` default: the engine's own parameters
+OWN = object()   # pass1 / pass1_pairs / process_chunk `farneback` and `window` default: the engine's own
 
 
 def farneback_kwargs(params, width, height):
-    """{"farneback": FarnebackParams or None} when params names "hip_farneback" (checked against the frame size up front),
-    else {}: the per-call override of frames_to_actions and prefetch.video_to_actions."""
-    if "hip_farneback" not in params:
-        return {}
-    fb = _capi.farneback_choice(params)
-    if fb is not None:
-        _capi.farneback_geometry(width, height, fb)
-    return {"farneback": fb}
+    """{"farneback": FarnebackParams or None} when params names "hip_farneback" (checked against the frame size up front)
+    and {"window": "box" | "gaussian"} when it names "hip_farneback_window", else {}: the per-call override of
+    frames_to_actions and prefetch.video_to_actions."""
+    kw = {}
+    if "hip_farneback_window" in params:
+        kw["window"] = _capi.farneback_mode(params)
+    if "hip_farneback" in params:
+        fb = _capi.farneback_choice(params)
+        if fb is not None:
+            _capi.farneback_geometry(width, height, fb)
+        kw["farneback"] = fb
+    return kw
 
 
 class PairEngine:
@@ -94,7 +98,7 @@ class PairEngine:
     of pairs <= j+6 are known (or the chunk has ended), after which its flow slot is recycled.
     """
 
-    def __init__(self, ctx, upload=None, depth=None, flow="farneback", dis=None, farneback=None):
+    def __init__(self, ctx, upload=None, depth=None, flow="farneback", dis=None, farneback=None, window="box"):
         """`upload(first_slot, frames)` puts a run of frames into consecutive frame slots; the default takes
         gray (or same-size BGR) operands, frontend.DecodedUploader takes frames as decoded (any size).
         `depth`: batches queued on the device before the oldest one's results are collected (default: 2 when the
@@ -105,14 +109,19 @@ class PairEngine:
         `flow`: "farneback" (ffl_flow_pairs) or "dis" (ffl_flow_pairs_dis with the _capi.DisParams `dis`, None = PRESET_FAST)
         for every batch the engine queues.
         `farneback`: _capi.FarnebackParams for the Farneback batches (ffl_flow_pairs_farneback; None: the reference's values
-        through the tuned ffl_flow_pairs)."""
+        through the tuned ffl_flow_pairs).
+        `window`: "box" or "gaussian" (cv2.OPTFLOW_FARNEBACK_GAUSSIAN) for the Farneback batches; "gaussian" runs the general
+        kernels, with `farneback`'s numbers or the reference's."""
         if flow not in _capi.FLOWS:
             raise ValueError(f"flow must be one of {_capi.FLOWS}, got {flow!r}")
         if farneback is not None and flow == "dis":
             raise ValueError("farneback parameters need flow='farneback'")
         if farneback is not None:
             _capi.farneback_geometry(ctx.width, ctx.height, farneback)
-        self.flow, self.dis, self.farneback = flow, dis, farneback
+        _capi.farneback_window(window)
+        if window != "box" and flow == "dis":
+            raise ValueError("a Farneback window needs flow='farneback'")
+        self.flow, self.dis, self.farneback, self.window = flow, dis, farneback, window
         self.ctx = ctx
         self.upload = upload or ctx.upload_frames
         self.B = ctx.max_batch
@@ -129,16 +138,17 @@ class PairEngine:
             raise ValueError(f"context too small: need frame_slots >= 2B+2 = {2 * self.B + 2} and "
                              f"flow_slots >= 2B+13 = {min_flow_slots(self.B)}")
 
-    def pass1(self, frames, pair_lo, pair_hi, pov_mode=False, cut_threshold=7.0, on_batch=None, algo=None, farneback=OWN):
+    def pass1(self, frames, pair_lo, pair_hi, pov_mode=False, cut_threshold=7.0, on_batch=None, algo=None, farneback=OWN,
+              window=OWN):
         """Run pass 1 for pairs [pair_lo, pair_hi) of `frames`; flows stay resident in slot
         (j - pair_lo) % flow_slots.  Returns the list of (x, y, val, mean_mag, cut)."""
         fs = self.ctx.flow_slots
         return self.pass1_pairs(frames, range(pair_lo, pair_hi), lambda l: l % fs, pov_mode, cut_threshold,
                                 on_batch=(lambda ls, js, got: on_batch(js, got)) if on_batch else None, algo=algo,
-                                farneback=farneback)
+                                farneback=farneback, window=window)
 
     def pass1_pairs(self, frames, pairs, slot_of, pov_mode=False, cut_threshold=7.0, on_batch=None, algo=None,
-                    farneback=OWN):
+                    farneback=OWN, window=OWN):
         """Pass 1 for an arbitrary ascending list of pair indices (pair j = frames[j], frames[j+1]) in batches of
         max_batch; the flow of the l-th listed pair stays resident in flow slot slot_of(l).  Frames go to the
         device once per run of batches that needs them: a ring over the frame slots, frames of the batch being
@@ -146,10 +156,12 @@ class PairEngine:
         H2D transfer.  (The library orders an upload into a recycled slot behind the batches that still read
         it.)  on_batch(local_indices, pair_indices, records) is called per finished batch.  `algo` = (flow, dis) as
         _capi.flow_choice returns it overrides the engine's own flow algorithm for this call only, and `farneback`
-        (_capi.FarnebackParams, or None for the tuned path; as _capi.farneback_choice returns it) its Farneback parameters."""
+        (_capi.FarnebackParams, or None for the tuned path; as _capi.farneback_choice returns it) its Farneback parameters,
+        `window` ("box" | "gaussian", as _capi.farneback_mode returns it) their window."""
         ctx, B, S = self.ctx, self.B, self.ctx.frame_slots
         algo, dis = algo if algo is not None else (getattr(self, "flow", "farneback"), getattr(self, "dis", None))
         fb = getattr(self, "farneback", None) if farneback is OWN else farneback
+        win = getattr(self, "window", "box") if window is OWN else window
         pairs = [int(j) for j in pairs]
         recs = [None] * len(pairs)
         resident, owner, state = {}, [None] * S, {"next": 0}
@@ -185,6 +197,8 @@ class PairEngine:
             f0, f1, fl = [resident[j] for j in js], [resident[j + 1] for j in js], [slot_of(l) for l in ls]
             if algo == "dis":
                 ctx.flow_pairs_dis(f0, f1, fl, pov_mode, dis)
+            elif win != "box":
+                ctx.flow_pairs_farneback(f0, f1, fl, pov_mode, fb, window=win)
             elif fb is not None:
                 ctx.flow_pairs_farneback(f0, f1, fl, pov_mode, fb)
             else:
@@ -212,9 +226,9 @@ class PairEngine:
             collect(*pending.pop(0))
         return recs
 
-    def process_chunk(self, frames, pov_mode=False, cut_threshold=7.0, algo=None, farneback=OWN, flows_out=None):
-        """One whole chunk on one GPU: returns (dots float64[n], records) with n = len(frames)-1.  `algo`, `farneback`:
-        see pass1_pairs (default: the engine's own flow algorithm and parameters).  `flows_out`: a float32 device array of
+    def process_chunk(self, frames, pov_mode=False, cut_threshold=7.0, algo=None, farneback=OWN, flows_out=None, window=OWN):
+        """One whole chunk on one GPU: returns (dots float64[n], records) with n = len(frames)-1.  `algo`, `farneback`,
+        `window`: see pass1_pairs (default: the engine's own flow algorithm, parameters and window).  `flows_out`: a float32 device array of
         (n, H, W, 2) or (n, 2, H, W) that receives every pair's flow field (Context.export_flows, on torch's current stream)
         as its batch finishes, before its slots can be recycled; records and dots are unchanged."""
         ctx, B = self.ctx, self.B
@@ -236,7 +250,7 @@ class PairEngine:
                 ctx.export_flows([j % ctx.flow_slots for j in js], flows_out[js[0]:js[-1] + 1], layout)
             post.add(js, got)
 
-        self.pass1(frames, 0, n, pov_mode, cut_threshold, on_batch, algo=algo, farneback=farneback)
+        self.pass1(frames, 0, n, pov_mode, cut_threshold, on_batch, algo=algo, farneback=farneback, window=window)
         return post.finish()
 
     def process_flows(self, flows, pov_mode=False, cut_threshold=7.0):
@@ -354,7 +368,7 @@ def frames_to_actions(engine, frames, fps, params):
     # params["hip_flow"] / ["hip_dis"] pick the flow algorithm for this call (the engine itself is left as it is); without
     # them the engine's own algorithm runs
     algo = _capi.flow_choice(params) if ("hip_flow" in params or "hip_dis" in params) else None
-    # params["hip_farneback"] likewise sets the Farneback parameters of this call
+    # params["hip_farneback"] / ["hip_farneback_window"] likewise set the Farneback parameters and window of this call
     fbk = farneback_kwargs(params, frames[0].shape[1], frames[0].shape[0]) if len(frames) else {}
     dots, cuts, frame_idx = [], [], []
     for chunk in pair_plan(fps, len(frames), params):

@@ -206,7 +206,7 @@ def video_to_actions(ctx, capture, params, engine=None, ring_frames=None):
     engine = engine or pipeline.PairEngine(ctx, frontend.DecodedUploader(ctx, bool(params.get("vr_mode")), False, yuv=yuv))
     # params["hip_flow"] / ["hip_dis"] pick the flow algorithm for this call (a caller's engine is left as it is)
     algo = _capi.flow_choice(params) if ("hip_flow" in params or "hip_dis" in params) else None
-    fbk = pipeline.farneback_kwargs(params, ctx.width, ctx.height)   # params["hip_farneback"]: this call's parameters
+    fbk = pipeline.farneback_kwargs(params, ctx.width, ctx.height)   # params["hip_farneback"], ["hip_farneback_window"]: this call's
     ring = PrefetchRing(ctx, capture, indices, bracket, ring_frames or 4 * ctx.max_batch + 2, yuv=yuv)
     dots, cuts, frame_idx = [], [], []
     try:
@@ -263,7 +263,7 @@ def process_video(video_path, params, log_func, open_capture, make_context, prog
         flow, dis = _capi.flow_choice(params)
         yuv = params.get("hip_yuv")   # "i420" | "nv12": open_capture's read() yields (3h/2, w) 4:2:0 frames
         engine = pipeline.PairEngine(ctx, frontend.DecodedUploader(ctx, bool(params.get("vr_mode")), False, yuv=yuv), flow=flow,
-                                     dis=dis, farneback=_capi.farneback_choice(params))
+                                     dis=dis, farneback=_capi.farneback_choice(params), window=_capi.farneback_mode(params))
         ring = PrefetchRing(ctx, cap, indices, int(params.get("batch_size", 3000.0)), 4 * ctx.max_batch + 2, yuv=yuv)
         dots, cuts, frame_idx, done = [], [], [], 0
         for view, fidx in ring.chunks():

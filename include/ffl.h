@@ -32,6 +32,8 @@
  *   ffl_submit_pair         precompute_wrapper((p0, p1), params)                    FF:1019-1021
  *   ffl_flow_pairs_farneback  cv2.calcOpticalFlowFarneback(p0, p1, None, pyr_scale, levels, winsize, iterations, poly_n,
  *                           poly_sigma, 0) with the caller's values + the same reductions
+ *   ffl_flow_pairs_farneback_ex  the same call with flags = OPTFLOW_FARNEBACK_GAUSSIAN and / or OPTFLOW_USE_INITIAL_FLOW
+ *                           (flow = the pair's flow slot) as its mode
  *   ffl_flow_pairs_dis      cv2.DISOpticalFlow_create(cv2.DISOPTICAL_FLOW_PRESET_FAST).calc(p0, p1, None)
  *                           + max_divergence + cartToPolar of the "DNN" backend     FF:948-980
  *                           (rules restated in DESIGN.md appendix D; parity with cv2 itself is unpinned)
@@ -335,8 +337,8 @@ int ffl_debug_dis_pair(ffl_ctx *ctx, int f0, int f1, const ffl_dis_params *p, in
 
 /* The six numeric parameters of cv2.calcOpticalFlowFarneback (and its flags).  Accepted: 0 < pyr_scale < 1,
  * 0 <= levels <= 12, winsize odd 3..63, 1 <= iterations <= 10, poly_n 5 or 7, 0 < poly_sigma <= 3, flags == 0
- * (OPTFLOW_USE_INITIAL_FLOW and OPTFLOW_FARNEBACK_GAUSSIAN are refused).  Float fields are computed with as the double of
- * their shortest decimal form (1.2f as 1.2). */
+ * (cv2's two flags are not fields of the parameters: they are the `mode` of ffl_flow_pairs_farneback_ex, and refused
+ * here).  Float fields are computed with as the double of their shortest decimal form (1.2f as 1.2). */
 typedef struct ffl_farneback_params {
     float pyr_scale;
     int levels;
@@ -366,6 +368,24 @@ int ffl_farneback_extra_bytes(int width, int height, int max_batch, const ffl_fa
  * before any device work.  Asynchronous. */
 int ffl_flow_pairs_farneback(ffl_ctx *ctx, int n, const int *fslot0, const int *fslot1, const int *flow_slots, int pov_mode,
                              const ffl_farneback_params *p);
+
+/* cv2's two flags that change what is computed, as the mode of a call. */
+#define FFL_FB_USE_INITIAL_FLOW 4u     /* cv2.OPTFLOW_USE_INITIAL_FLOW */
+#define FFL_FB_GAUSSIAN_WINDOW  256u   /* cv2.OPTFLOW_FARNEBACK_GAUSSIAN */
+
+/* ffl_flow_pairs_farneback under a mode.  mode == 0 is ffl_flow_pairs_farneback(p) itself (the defaults reach the tuned
+ * path, the same bits).  Any other mode runs the general kernels, at the default numbers too; a bit other than the two
+ * above is refused by name (FFL_ERR_INVALID).  p obeys the rules above unchanged: p->flags must be 0, winsize odd.
+ *   FFL_FB_GAUSSIAN_WINDOW   the winsize x winsize window is the separable float Gaussian of sigma = 0.3 * (winsize / 2)
+ *                            in place of the box.
+ *   FFL_FB_USE_INITIAL_FLOW  flow_slots[b] is in/out as cv2's `flow` argument: it must already hold a flow (an earlier
+ *                            batch's, ffl_upload_flow's or ffl_import_flows'; FFL_ERR_STATE before any device work when
+ *                            it holds none), is read as the pair's starting field (reduced by INTER_AREA to the
+ *                            coarsest level and scaled) behind its last writer, then overwritten with the result; its
+ *                            pass-1 record is replaced by this batch's.
+ * A mode adds no memory: ffl_farneback_geometry and ffl_farneback_extra_bytes hold for every mode.  Asynchronous. */
+int ffl_flow_pairs_farneback_ex(ffl_ctx *ctx, int n, const int *fslot0, const int *fslot1, const int *flow_slots,
+                                int pov_mode, const ffl_farneback_params *p, unsigned mode);
 
 /* ---- parity-test hooks (used by tests/ only) ------------------------------------------------ */
 

@@ -4,7 +4,10 @@ synchronised batches):
   * 256x256, B = 256: tuned ffl_flow_pairs; the defaults forced through the general kernels ("fb_general" = 1);
     poly_n 7 / poly_sigma 1.5 / winsize 21
   * 1920x1080, B = 32: tuned; defaults forced general; levels 5
-python profiles/tools/fb_general_rate.py [--reps R] [--batches K] [--only 256|1080] [--out result.json]"""
+--window W[,W...] measures the two windows of the general kernels instead: at each winsize W, the box
+(ffl_flow_pairs_farneback) against the Gaussian (ffl_flow_pairs_farneback_ex, FFL_FB_GAUSSIAN_WINDOW), other numbers at
+their defaults, alternating in one process.
+python profiles/tools/fb_general_rate.py [--reps R] [--batches K] [--only 256|1080] [--window 15,63] [--out result.json]"""
 import argparse
 import json
 import os
@@ -20,6 +23,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--batches", type=int, default=10)
 ap.add_argument("--only", default=None)
+ap.add_argument("--window", default=None, help="comma-separated winsizes: box against Gaussian window")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 
@@ -48,6 +52,21 @@ for tag, W, H, B, over in SETUPS:
         ctx.sync()
         return batches * B / (time.perf_counter() - t0)
 
+    if a.window:
+        r = {"size": [W, H], "batch": B}
+        ctx.set_option("fb_general", 1)   # winsize 15 is the default set: keep the box on the general kernels too
+        for ws in [int(v) for v in a.window.split(",")]:
+            q = _capi.FarnebackParams(winsize=ws)
+            rates = {"box": [], "gaussian": []}
+            for rep in range(a.reps):
+                for win in ("box", "gaussian"):
+                    rates[win].append(resident(lambda x, y, s: ctx.flow_pairs_farneback(x, y, s, False, q, window=win), a.batches))
+                print(f"{W}x{H} B={B} winsize {ws} rep {rep}: box {rates['box'][-1]:.0f}, gaussian {rates['gaussian'][-1]:.0f} "
+                      f"pairs/s", flush=True)
+            r[f"winsize{ws}"] = {**rates, "median": {k: float(np.median(v)) for k, v in rates.items()}}
+        ctx.close()
+        res[tag] = r
+        continue
     p = _capi.FarnebackParams(**over)
     d = _capi.FarnebackParams()
     r = {"size": [W, H], "batch": B, "params": over, "tuned": [], "general_defaults": [], "general_params": []}
