@@ -26,7 +26,7 @@ EXPORTS = ["ffl_device_count", "ffl_create", "ffl_destroy", "ffl_last_error", "f
            "ffl_flow_pairs_farneback_ex",
            "ffl_upload_frames_yuv", "ffl_frontend_yuv_window",
            "ffl_dev_frame_check", "ffl_upload_frames_device", "ffl_export_flows",
-           "ffl_dev_flow_check", "ffl_import_flows"]
+           "ffl_dev_flow_check", "ffl_import_flows", "ffl_radial_window"]
 
 # 4:2:0 layouts of ffl_upload_frames_yuv (FFL_YUV_I420, FFL_YUV_NV12): cv2's single-array (3h/2, w) uint8 frames
 YUV_LAYOUTS = {"i420": 0, "nv12": 1}
@@ -37,6 +37,12 @@ FLOW_LAYOUTS = {"nhwc": 0, "nchw": 1}
 FFL_ERR_INVALID, FFL_ERR_STATE = 1, 4
 # flow import (ffl_import_flows): FFL_F32, FFL_F16, FFL_BF16 by __cuda_array_interface__ typestr
 FLOW_DTYPES = {"<f4": 0, "<f2": 1, "bfloat16": 2}
+
+# ffl_radial_window: ffl_pass2_record as a numpy structured dtype, and FFL_MAX_RADIUS
+PASS2_DTYPE = np.dtype({"names": ["dot", "cx", "cy", "mean_mag", "div_val", "x", "y", "cut", "pad"],
+                        "formats": ["<f8", "<f8", "<f8", "<f4", "<f4", "<i4", "<i4", "<i4", "<i4"],
+                        "offsets": [0, 8, 16, 24, 28, 32, 36, 40, 44], "itemsize": 48})
+FFL_MAX_RADIUS = 32
 
 FLOWS = ("farneback", "dis")   # params["hip_flow"]: the reference's CPU/CUDA/OpenCL branch, or its "DNN" branch (FF:948-980)
 DIS_STAGES = {"pass1": 0, "pass2": 1, "dense": 2, "refined": 3, "images": 4}   # ffl_debug_dis_pair stages
@@ -237,6 +243,25 @@ def _array_view(obj):
             strides.insert(0, acc)
             acc *= d
     return int(cai["data"][0]), shape, tuple(int(v) for v in strides), ts
+
+
+def _device_span(obj):
+    """(data pointer, bytes) of a contiguous device array (see _array_view); ValueError for host memory or a strided view"""
+    ptr, shp, st, ts = _array_view(obj)
+    extent = obj.element_size() if hasattr(obj, "element_size") else int(ts[2:]) if ts[2:].isdigit() else 1
+    for d, b in zip(reversed(shp), reversed(st)):
+        if d > 1 and b != extent:
+            raise ValueError(f"a contiguous device buffer is needed: shape {tuple(shp)} has byte strides {tuple(st)}")
+        extent *= d
+    return ptr, extent
+
+
+class _DeviceSpan:
+    """`nbytes` bytes of device memory at `ptr` as an object with __cuda_array_interface__ (a piece of a larger buffer)"""
+
+    def __init__(self, ptr, nbytes):
+        self.__cuda_array_interface__ = {"version": 2, "data": (int(ptr), False), "shape": (int(nbytes),), "strides": None,
+                                         "typestr": "|u1"}
 
 
 def _frame_row(obj, code):
@@ -445,6 +470,7 @@ def load():
     L.ffl_export_flows.argtypes = [vp, C.c_int, ip, vp, C.c_int, C.c_ssize_t, C.c_uint64]
     L.ffl_dev_flow_check.argtypes = [C.c_int] * 4 + [vp]
     L.ffl_import_flows.argtypes = [vp, C.c_int, ip, vp, C.c_int, C.c_int, C.c_uint64]
+    L.ffl_radial_window.argtypes = [vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, C.c_uint64]
     _lib = L
     return L
 
@@ -775,6 +801,21 @@ class Context:
         pc, kc = _iarr(np.asarray(is_cut, bool))
         self._chk(self.L.ffl_radial(self._h, n, ps, px, py, pc, int(bool(pov_mode)), out.ctypes.data_as(C.POINTER(C.c_double))))
         return out.tolist()
+
+    def radial_window(self, seq_slots, first, n, out, radius=6, cut_threshold=7.0, pov_mode=False, stream=None):
+        """The centre window, the cut test and pass 2 on the device without a host round trip (ffl_radial_window, DESIGN.md
+        section 14): seq_slots are the flow slots of consecutive pairs in time order, items first .. first+n-1 of them go
+        to out[0..n) as PASS2_DTYPE records -- pass1_results, smooth_centers over the window clipped to seq_slots, and
+        radial, bit for bit.  `out`: device memory of at least n * 48 bytes (anything with __cuda_array_interface__, a
+        torch tensor included).  Ordered after the batches that produced the slots and the work queued on `stream` (None:
+        torch's current stream); `stream` waits for the records.  The host does not wait.  Returns `out`."""
+        ptr, extent = _device_span(out)   # the records are written back to back
+        if extent < int(n) * PASS2_DTYPE.itemsize:
+            raise ValueError(f"radial_window: out holds {extent} bytes, {int(n)} records need {int(n) * PASS2_DTYPE.itemsize}")
+        ps, ks = _iarr(seq_slots)
+        self._chk(self.L.ffl_radial_window(self._h, len(ks), ps, int(first), int(n), int(radius), float(cut_threshold),
+                                           int(bool(pov_mode)), ptr, stream_handle(stream, self.device)))
+        return out
 
     def download_frame(self, fslot):
         out = np.empty((self.height, self.width), np.uint8)

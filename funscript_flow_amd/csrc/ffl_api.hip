@@ -335,6 +335,7 @@ struct ffl_ctx {
     DevBuf<RadialTab> d_rtab; PinBuf<RadialTab> h_rtab;  // pass-2 table (s_post; ffl_radial waits for the stream, so one copy)
     DevBuf<BatchTab> d_ptab; PinBuf<BatchTab> h_ptab;    // ffl_upload_flow's one-pair table (s_post)
     DevBuf<double> d_rpsum;                            // pass-2 partial sums (s_post)
+    DevBuf<WindowItem> d_wtab;                         // ffl_radial_window's item table, FFL_MAXB entries (s_post)
     DevBuf<double> d_wytab;                            // pass-2 row weights (h - y) / h and y / h
     PinBuf<double> h_radial; double *d_radial = nullptr;  // pinned pass-2 results and their device alias
     DevBuf<unsigned long long> d_ppkey;                // ffl_upload_flow scratch (s_post)
@@ -885,6 +886,7 @@ static int create_resources(ffl_ctx *c) {
         HIPCHK(nullptr, hipMemcpy(c->d_wytab, wy.data(), sizeof(double) * wy.size(), hipMemcpyHostToDevice));
     }
     HIPCHK_ALLOC(nullptr, hipMalloc, c->d_rtab, 1);
+    HIPCHK_ALLOC(nullptr, hipMalloc, c->d_wtab, FFL_MAXB);
     HIPCHK_ALLOC(nullptr, hipHostMalloc, c->h_rtab, 1, hipHostMallocDefault);
     HIPCHK_ALLOC(nullptr, hipMalloc, c->d_ptab, 1);
     HIPCHK_ALLOC(nullptr, hipHostMalloc, c->h_ptab, 1, hipHostMallocDefault);
@@ -2264,6 +2266,57 @@ int ffl_export_flows(ffl_ctx *c, int n, const int *slots, float *dst, int layout
     EvRef ev;
     if (int rc = publish_post(c, n, slots, &ev)) return rc;  // a batch recycling a slot waits for the export
     HIPCHK(c, hipStreamWaitEvent(cst, ev.get(), 0));
+    return FFL_OK;
+}
+
+// The centre window, the cut test and pass 2 of items first .. first+n-1 of seq on stream `post`, ordered after the
+// producers of every seq slot and the caller's queued work, and before the caller's later work (the stream contract of
+// ffl.h).  The slot table travels as a kernel argument; the plan kernel's item table and the radial partials are single
+// device copies, safe because every user of them runs on stream `post`.  Nothing waits on the host beyond post_ring's own
+// settling.
+static_assert(sizeof(ffl_pass2_record) == 48 && sizeof(Pass2Record) == 48 && offsetof(ffl_pass2_record, cx) == offsetof(Pass2Record, cx) &&
+              offsetof(ffl_pass2_record, mean_mag) == offsetof(Pass2Record, mean_mag) && offsetof(ffl_pass2_record, x) == offsetof(Pass2Record, x) &&
+              offsetof(ffl_pass2_record, cut) == offsetof(Pass2Record, cut), "Pass2Record mirrors ffl_pass2_record");
+static_assert(FFL_MAX_RADIUS == FFL_WINDOW_MAX_RADIUS && FFL_MAX_BATCH == FFL_MAXB, "ffl.h and ffl_kernels.h agree");
+int ffl_radial_window(ffl_ctx *c, int n_seq, const int *seq, int first, int n, int radius, float cut_threshold, int pov_mode,
+                      ffl_pass2_record *out, uint64_t stream) {
+    static const char *fn = "ffl_radial_window";
+    if (!c) return FFL_ERR_INVALID;
+    std::unique_lock<std::mutex> pl(c->post_mu);  // stream `post`, post_ring and d_rpsum, as ffl_radial / ffl_export_flows
+    CtxLock lk(c->mu);
+    if (n < 1 || n > FFL_MAX_BATCH) return set_err(c, FFL_ERR_INVALID, "%s: n = %d items outside 1..%d (FFL_MAX_BATCH)", fn, n, FFL_MAX_BATCH);
+    const int max_seq = FFL_MAX_BATCH + 2 * FFL_MAX_RADIUS;
+    if (n_seq < 1 || n_seq > max_seq)
+        return set_err(c, FFL_ERR_INVALID, "%s: n_seq = %d slots outside 1..%d (FFL_MAX_BATCH + 2 * FFL_MAX_RADIUS)", fn, n_seq, max_seq);
+    if (first < 0 || first > n_seq - n)   // n and n_seq are in range: no overflow
+        return set_err(c, FFL_ERR_INVALID, "%s: first = %d, n = %d: the items lie outside seq 0..%d", fn, first, n, n_seq - 1);
+    if (radius < 0 || radius > FFL_MAX_RADIUS)
+        return set_err(c, FFL_ERR_INVALID, "%s: radius %d outside 0..%d (FFL_MAX_RADIUS)", fn, radius, FFL_MAX_RADIUS);
+    if (!seq) return set_err(c, FFL_ERR_INVALID, "%s: NULL seq_slots", fn);
+    if (!out) return set_err(c, FFL_ERR_INVALID, "%s: NULL out_dev", fn);
+    // a slot's state stands for its record and its flow alike, so one check covers the neighbours and the computed items
+    if (int rc = check_flow_slots(c, fn, n_seq, seq, "result", "repeated in one call")) return rc;
+    if ((uintptr_t)out % 8) return set_err(c, FFL_ERR_INVALID, "%s: out_dev must be 8-byte aligned", fn);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t cst;
+    if (int rc = caller_stream(c, fn, stream, &cst)) return rc;
+    if (int rc = dev_mem_check(c, fn, "out_dev", out, sizeof(ffl_pass2_record) * (size_t)n,
+                               "results in host memory come from ffl_pass1_results and ffl_radial"))
+        return rc;
+    WaitOnce wait_post(c->s_post);
+    if (int rc = caller_join(c, cst, wait_post)) return rc;
+    WindowSeq t;
+    for (int i = 0; i < n_seq; i++) {
+        HIPCHK(c, wait_post(c->ev_slot_done[seq[i]].get()));
+        t.slot[i] = seq[i];
+    }
+    // not timed under FFL_K_RADIAL: that class counts k_radial + k_radial_final pairs, one per ffl_radial call
+    ffl_launch_radial_window(t, n_seq, first, n, radius, cut_threshold, c->d_res, c->d_flow, c->w, c->h, pov_mode ? 1 : 0,
+                             c->d_wytab, c->d_wtab, c->d_rpsum, reinterpret_cast<Pass2Record *>(out), c->s_post);
+    HIPCHK(c, hipGetLastError());
+    EvRef done;
+    if (int rc = publish_post(c, n_seq, seq, &done)) return rc;  // a batch recycling a seq slot waits for this call
+    HIPCHK(c, hipStreamWaitEvent(cst, done.get(), 0));
     return FFL_OK;
 }
 

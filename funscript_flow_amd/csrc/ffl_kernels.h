@@ -229,6 +229,27 @@ struct RadialTab {  // device-resident like the batch tables
 void ffl_launch_radial(const RadialTab *rt, int nB, int w, int h, int pov_mode, const double *wytab, double *psum,
                        double *out, hipStream_t st);
 
+// ffl_radial_window (k_window_plan, k_radial_window, k_radial_window_final)
+#define FFL_WINDOW_MAX_RADIUS 32     // = FFL_MAX_RADIUS of include/ffl.h
+struct WindowSeq {   // the flow slots of the call's consecutive pairs; travels as a kernel argument (1280 bytes)
+    int slot[FFL_MAXB + 2 * FFL_WINDOW_MAX_RADIUS];
+};
+struct WindowItem {  // what k_window_plan leaves in device memory for the radial grid, one per computed item
+    const float *flow;
+    double cx, cy;
+    int cut, pad;
+};
+struct Pass2Record { // = ffl_pass2_record of include/ffl.h (ffl_api.hip asserts the layout)
+    double dot, cx, cy;
+    float mean_mag, div_val;
+    int x, y, cut, pad;
+};
+// items first .. first+n-1 of seq -> out[0..n): plan, radial grid, final (three launches); tab holds n WindowItems, psum
+// the radial partials of n items
+void ffl_launch_radial_window(const WindowSeq &seq, int n_seq, int first, int n, int radius, float cut_threshold,
+                              const Pass1Result *res, const float *flow, int w, int h, int pov_mode, const double *wytab,
+                              WindowItem *tab, double *psum, Pass2Record *out, hipStream_t st);
+
 // XCD-aware order of a 1-D run of `count` tiles: the l-th workgroup of the run (l and l+8 share an XCD under the
 // observed round-robin placement; the run must start at a multiple of 8) takes tile (l % 8) * chunk + l / 8, so every
 // XCD walks one contiguous piece of the run.  ffl_xcd_blocks(count) workgroups cover the run (up to 7 idle ones).

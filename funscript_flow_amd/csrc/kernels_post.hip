@@ -216,12 +216,11 @@ void ffl_launch_pass1(const PairTab *pt, int nB, int w, int h, int pov_mode, uns
 // context on the host (IEEE division, the value the device's division yields).  The row index is wave-uniform, so the
 // weight comes with a scalar load instead of a 15-instruction f64 division per lane and row -- the kernel had
 // hoisted all 16 of them and needed 198 VGPRs (2 waves per SIMD).
-__global__ __launch_bounds__(P1_THREADS) void k_radial(const RadialTab *__restrict__ rt, int w, int h, int pov_mode,
-                                                       const double *__restrict__ wytab, double *__restrict__ psum) {
-    __shared__ double ssum[P1_THREADS / 64];
-    const int b = blockIdx.y;
-    const float2 *flow = reinterpret_cast<const float2 *>(rt->flow[b]);
-    const double cx = rt->cx[b], cy = rt->cy[b];
+// The body of k_radial and k_radial_window: one per-lane order and one wave / workgroup reduction order whatever table
+// the field and its centre come from, so the two give the same bits for the same slot, centre and pov_mode.
+__device__ __forceinline__ void ffl_radial_body(const float2 *__restrict__ flow, double cx, double cy, int w, int h,
+                                                int pov_mode, int b, const double *__restrict__ wytab,
+                                                double *__restrict__ psum, double *ssum) {
     const double dw = (double)w;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int nstrips = (w + P2_STRIP - 1) / P2_STRIP, ngroups = (h + P1_RG - 1) / P1_RG;
@@ -264,10 +263,16 @@ __global__ __launch_bounds__(P1_THREADS) void k_radial(const RadialTab *__restri
     }
 }
 
-__global__ __launch_bounds__(P1_THREADS) void k_radial_final(int w, int h, int nblk, const double *__restrict__ psum,
-                                                             double *__restrict__ out) {
+__global__ __launch_bounds__(P1_THREADS) void k_radial(const RadialTab *__restrict__ rt, int w, int h, int pov_mode,
+                                                       const double *__restrict__ wytab, double *__restrict__ psum) {
     __shared__ double ssum[P1_THREADS / 64];
-    const int b = blockIdx.x;
+    const int b = blockIdx.y;
+    ffl_radial_body(reinterpret_cast<const float2 *>(rt->flow[b]), rt->cx[b], rt->cy[b], w, h, pov_mode, b, wytab, psum, ssum);
+}
+
+// The body of k_radial_final and k_radial_window_final: item b's nblk partials in one order; the mean is valid in thread 0.
+__device__ __forceinline__ double ffl_radial_final_body(int w, int h, int nblk, int b, const double *__restrict__ psum,
+                                                        double *ssum) {
     double sum = 0.0;
     for (int i = threadIdx.x; i < nblk; i += P1_THREADS) sum += psum[(size_t)b * nblk + i];
     sum = ffl_wave_sum_f64(sum);
@@ -276,8 +281,17 @@ __global__ __launch_bounds__(P1_THREADS) void k_radial_final(int w, int h, int n
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int i = 1; i < P1_THREADS / 64; i++) sum += ssum[i];
-        out[b] = sum / ((double)w * (double)h);
+        sum = sum / ((double)w * (double)h);
     }
+    return sum;
+}
+
+__global__ __launch_bounds__(P1_THREADS) void k_radial_final(int w, int h, int nblk, const double *__restrict__ psum,
+                                                             double *__restrict__ out) {
+    __shared__ double ssum[P1_THREADS / 64];
+    const int b = blockIdx.x;
+    const double mean = ffl_radial_final_body(w, h, nblk, b, psum, ssum);
+    if (threadIdx.x == 0) out[b] = mean;
 }
 
 void ffl_launch_radial(const RadialTab *rt, int nB, int w, int h, int pov_mode, const double *wytab, double *psum,
@@ -285,6 +299,94 @@ void ffl_launch_radial(const RadialTab *rt, int nB, int w, int h, int pov_mode, 
     int nblk = (ffl_strip_waves(w, h, P2_STRIP) + 3) / 4;
     hipLaunchKernelGGL(k_radial, dim3(nblk, nB), dim3(P1_THREADS), 0, st, rt, w, h, pov_mode, wytab, psum);
     hipLaunchKernelGGL(k_radial_final, dim3(nB), dim3(P1_THREADS), 0, st, w, h, nblk, psum, out);
+}
+
+// ---- pass 2 behind the batches, host-free (ffl_radial_window) ---------------------------------
+// Three launches per call.  k_window_plan: one thread per item forms the clipped centre window, mean_mag and cut out of the
+// pass-1 records and writes the device-resident WindowItem table plus every field of the record but `dot`.  The records
+// are mapped pinned memory: a workgroup stages the (x, y) of the <= 64 + 2 * radius records its items' windows span in
+// LDS, so the window costs one (x, y) read per record and workgroup instead of 2 * radius + 1 per item; each item then
+// reads mag_sum and div_val of its own record once more.  Nothing of a record is read by the radial grid.  k_radial_window: k_radial's body on that table; the workgroups of a cut item
+// leave on a wave-uniform branch before they load anything of the flow.  k_radial_window_final: k_radial_final's
+// reduction into `dot`, +0.0 for a cut item.
+#define W2_THREADS 64
+
+__global__ __launch_bounds__(W2_THREADS) void k_window_plan(const WindowSeq seq, int n_seq, int first, int n, int radius,
+                                                            float cut_threshold, double npx,
+                                                            const Pass1Result *__restrict__ res, const float *__restrict__ flow,
+                                                            size_t N, WindowItem *__restrict__ tab,
+                                                            Pass2Record *__restrict__ out) {
+    __shared__ int sx[W2_THREADS + 2 * FFL_WINDOW_MAX_RADIUS], sy[W2_THREADS + 2 * FFL_WINDOW_MAX_RADIUS];
+    const int i0 = blockIdx.x * W2_THREADS;                      // the workgroup's first item
+    const int j0 = first + i0, j1 = first + min(i0 + W2_THREADS, n) - 1;   // its items in seq, inclusive
+    const int lo = max(0, j0 - radius), hi = min(n_seq - 1, j1 + radius);  // the records their windows span
+    for (int k = lo + (int)threadIdx.x; k <= hi; k += W2_THREADS) {
+        const Pass1Result *r = res + seq.slot[k];
+        sx[k - lo] = r->x;
+        sy[k - lo] = r->y;
+    }
+    __syncthreads();
+    const int i = i0 + (int)threadIdx.x;
+    if (i >= n) return;
+    const int j = first + i, slot = seq.slot[j];
+    const int a = max(0, j - radius), b = min(n_seq - 1, j + radius);
+    long long tx = 0, ty = 0;                                    // exact integer sums (np.mean of the int64 pairs)
+    for (int k = a; k <= b; k++) {
+        tx += sx[k - lo];
+        ty += sy[k - lo];
+    }
+    const double cnt = (double)(b - a + 1);
+    const double cx = (double)tx / cnt, cy = (double)ty / cnt;   // one IEEE division each: pipeline.smooth_centers
+    const Pass1Result *r = res + slot;
+    const float mm = (float)(r->mag_sum / npx);                  // ffl_pass1_results' expressions
+    const int cut = mm > cut_threshold ? 1 : 0;                  // NaN > threshold is false
+    WindowItem it;
+    it.flow = flow + (size_t)slot * 2 * N;
+    it.cx = cx;
+    it.cy = cy;
+    it.cut = cut;
+    it.pad = 0;
+    tab[i] = it;
+    Pass2Record *o = out + i;
+    o->cx = cx;
+    o->cy = cy;
+    o->mean_mag = mm;
+    o->div_val = r->div_val;
+    o->x = sx[j - lo];
+    o->y = sy[j - lo];
+    o->cut = cut;
+    o->pad = 0;
+}
+
+__global__ __launch_bounds__(P1_THREADS) void k_radial_window(const WindowItem *__restrict__ tab, int w, int h, int pov_mode,
+                                                              const double *__restrict__ wytab, double *__restrict__ psum) {
+    __shared__ double ssum[P1_THREADS / 64];
+    const int b = blockIdx.y;
+    if (tab[b].cut) return;   // workgroup-uniform: FF:766-767, a cut is 0.0 without a look at the flow
+    ffl_radial_body(reinterpret_cast<const float2 *>(tab[b].flow), tab[b].cx, tab[b].cy, w, h, pov_mode, b, wytab, psum, ssum);
+}
+
+__global__ __launch_bounds__(P1_THREADS) void k_radial_window_final(const WindowItem *__restrict__ tab, int w, int h, int nblk,
+                                                                    const double *__restrict__ psum,
+                                                                    Pass2Record *__restrict__ out) {
+    __shared__ double ssum[P1_THREADS / 64];
+    const int b = blockIdx.x;
+    if (tab[b].cut) {         // its partials were never written
+        if (threadIdx.x == 0) out[b].dot = 0.0;
+        return;
+    }
+    const double mean = ffl_radial_final_body(w, h, nblk, b, psum, ssum);
+    if (threadIdx.x == 0) out[b].dot = mean;
+}
+
+void ffl_launch_radial_window(const WindowSeq &seq, int n_seq, int first, int n, int radius, float cut_threshold,
+                              const Pass1Result *res, const float *flow, int w, int h, int pov_mode, const double *wytab,
+                              WindowItem *tab, double *psum, Pass2Record *out, hipStream_t st) {
+    const int nblk = (ffl_strip_waves(w, h, P2_STRIP) + 3) / 4;
+    hipLaunchKernelGGL(k_window_plan, dim3((n + W2_THREADS - 1) / W2_THREADS), dim3(W2_THREADS), 0, st, seq, n_seq, first, n,
+                       radius, cut_threshold, (double)w * (double)h, res, flow, (size_t)w * h, tab, out);
+    hipLaunchKernelGGL(k_radial_window, dim3(nblk, n), dim3(P1_THREADS), 0, st, tab, w, h, pov_mode, wytab, psum);
+    hipLaunchKernelGGL(k_radial_window_final, dim3(n), dim3(P1_THREADS), 0, st, tab, w, h, nblk, psum, out);
 }
 
 // ---- flow export -----------------------------------------------------------------------------

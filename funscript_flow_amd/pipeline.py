@@ -46,6 +46,71 @@ def min_frame_slots(max_batch, depth=1):
     return (depth + 1) * (max_batch + 1)
 
 
+def window_calls(n_pairs, B, radius=SMOOTH_RADIUS):
+    """The Context.radial_window calls a streaming chunk of n_pairs pairs issues when its batches hold B pairs, as
+    (seq_lo, seq_hi, first, count, after_batch) tuples in issue order: pairs seq_lo .. seq_hi-1 are the call's seq, items
+    first .. first+count-1 of it (pairs seq_lo + first ...) are computed, and the call is issued once batch `after_batch`
+    (0-based) has been queued.  _ChunkPost._finalize's rule: a pair is issued once its +-radius window is complete -- or at
+    the chunk's end, where the window clips -- at most B pairs per call.  Every pair is issued exactly once; a call's seq
+    holds its items' whole clipped windows and at most B + 2 * radius pairs, none of them later than batch after_batch.
+    A pure function: no device."""
+    calls, done = [], 0
+    for k in range(-(-n_pairs // B)):
+        j1 = min((k + 1) * B, n_pairs)                       # pairs queued so far
+        limit = n_pairs if j1 == n_pairs else max(0, j1 - radius)
+        while done < limit:
+            c1 = min(done + B, limit)
+            lo, hi = max(0, done - radius), min(n_pairs, c1 + radius)
+            calls.append((lo, hi, done - lo, c1 - done, k))
+            done = c1
+    return calls
+
+
+def post_buffer(ctx, n):
+    """a device buffer for the n records of a chunk (torch uint8 on the context's device), as post_out= takes it"""
+    import torch
+    return torch.empty(n * _capi.PASS2_DTYPE.itemsize, dtype=torch.uint8, device=torch.device("cuda", ctx.device))
+
+
+def post_records(buf, n=None, device=None):
+    """The one device-to-host copy of a chunk whose pass 2 ran on the device (process_chunk / process_flows with
+    post_out=): (dots float64[n], records) in the form process_chunk returns them; n defaults to the records `buf` holds.
+    The copy runs on torch's current stream, behind the calls that filled `buf` there, and waits for them.  A torch
+    tensor names its own device; for any other __cuda_array_interface__ object `device` is the context's (default: torch's
+    current device)."""
+    import torch
+    if not isinstance(buf, torch.Tensor):
+        buf = torch.as_tensor(buf, device=torch.device("cuda", torch.cuda.current_device() if device is None else device))
+    raw = buf.contiguous().view(torch.uint8).reshape(-1)
+    n = raw.numel() // _capi.PASS2_DTYPE.itemsize if n is None else n
+    raw = raw[:n * _capi.PASS2_DTYPE.itemsize].cpu().numpy()
+    rec = np.frombuffer(raw.tobytes(), _capi.PASS2_DTYPE, n)
+    records = list(zip(rec["x"].tolist(), rec["y"].tolist(), list(rec["div_val"]), list(rec["mean_mag"]),
+                       (rec["cut"] != 0).tolist()))
+    return rec["dot"].astype(np.float64), records
+
+
+def _stream_event(ctx, stream=None):
+    """an event recorded on `stream` (None: torch's current stream of the context's device): query() / synchronize()"""
+    import torch
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(ctx.device) if stream is None else stream)
+    return ev
+
+
+def _side_stream(ctx):
+    """The context's stream for the window calls of a chunk, made to wait for the work queued on torch's current stream.
+    The calls make their stream wait for every batch they follow; on torch's current stream -- the default stream,
+    which the device uploads join too -- that wait cost 0.3 ms of the device's time per call at 256x256 (DESIGN.md
+    section 14), on a stream of their own nothing measurable."""
+    import torch
+    s = getattr(ctx, "_pass2_stream", None)
+    if s is None:
+        s = ctx._pass2_stream = torch.cuda.Stream(torch.device("cuda", ctx.device))
+    s.wait_stream(torch.cuda.current_stream(ctx.device))
+    return s
+
+
 def shard_range(n_items, world, rank):
     """Contiguous block [lo, hi) of rank `rank`; block sizes differ by at most one."""
     base, rem = divmod(n_items, world)
@@ -148,7 +213,7 @@ class PairEngine:
                                 farneback=farneback, window=window)
 
     def pass1_pairs(self, frames, pairs, slot_of, pov_mode=False, cut_threshold=7.0, on_batch=None, algo=None,
-                    farneback=OWN, window=OWN):
+                    farneback=OWN, window=OWN, queued=None):
         """Pass 1 for an arbitrary ascending list of pair indices (pair j = frames[j], frames[j+1]) in batches of
         max_batch; the flow of the l-th listed pair stays resident in flow slot slot_of(l).  Frames go to the
         device once per run of batches that needs them: a ring over the frame slots, frames of the batch being
@@ -157,7 +222,10 @@ class PairEngine:
         it.)  on_batch(local_indices, pair_indices, records) is called per finished batch.  `algo` = (flow, dis) as
         _capi.flow_choice returns it overrides the engine's own flow algorithm for this call only, and `farneback`
         (_capi.FarnebackParams, or None for the tuned path; as _capi.farneback_choice returns it) its Farneback parameters,
-        `window` ("box" | "gaussian", as _capi.farneback_mode returns it) their window."""
+        `window` ("box" | "gaussian", as _capi.farneback_mode returns it) their window.
+        `queued(local_indices, pair_indices)`: called straight after every batch has been QUEUED; the records are then never
+        collected (no pass1_results, no on_batch, no frame release -- the device pass 2 of process_chunk) and the list
+        returned holds None."""
         ctx, B, S = self.ctx, self.B, self.ctx.frame_slots
         algo, dis = algo if algo is not None else (getattr(self, "flow", "farneback"), getattr(self, "dis", None))
         fb = getattr(self, "farneback", None) if farneback is OWN else farneback
@@ -218,6 +286,10 @@ class PairEngine:
                 on_batch(ls, js, got)
 
         pending, depth = [], getattr(self, "depth", 1)
+        if queued is not None:
+            for l0 in range(0, len(pairs), B):
+                queued(*enqueue(l0))
+            return recs
         for l0 in range(0, len(pairs), B):
             pending.append(enqueue(l0))
             if len(pending) > depth:
@@ -226,15 +298,24 @@ class PairEngine:
             collect(*pending.pop(0))
         return recs
 
-    def process_chunk(self, frames, pov_mode=False, cut_threshold=7.0, algo=None, farneback=OWN, flows_out=None, window=OWN):
+    def process_chunk(self, frames, pov_mode=False, cut_threshold=7.0, algo=None, farneback=OWN, flows_out=None, window=OWN,
+                      post_out=None):
         """One whole chunk on one GPU: returns (dots float64[n], records) with n = len(frames)-1.  `algo`, `farneback`,
         `window`: see pass1_pairs (default: the engine's own flow algorithm, parameters and window).  `flows_out`: a float32 device array of
         (n, H, W, 2) or (n, 2, H, W) that receives every pair's flow field (Context.export_flows, on torch's current stream)
-        as its batch finishes, before its slots can be recycled; records and dots are unchanged."""
+        as its batch finishes, before its slots can be recycled; records and dots are unchanged.
+        `post_out`: device memory for n 48-byte records (_capi.PASS2_DTYPE), or True for a new buffer (post_buffer).  The centre window, the
+        cut test and pass 2 are then queued on the device behind each batch (Context.radial_window on torch's current
+        stream, the calls of window_calls); pass1_results is never called, nothing waits for the device, and the call
+        returns post_out, which post_records reads.  Frames out of a prefetch.PrefetchRing are the one exception: its
+        page-locked slots are read in place by the transfers, so they are released as events on the stream complete and
+        the call returns once the chunk's last batch has run."""
         ctx, B = self.ctx, self.B
         n = len(frames) - 1
         if n < 1:
-            return np.zeros(0), []
+            return (np.zeros(0), []) if post_out is None else (post_buffer(ctx, 0) if post_out is True else post_out)
+        if post_out is True:
+            post_out = post_buffer(ctx, n)
         layout = None
         if flows_out is not None:
             shp = tuple(flows_out.shape)
@@ -243,6 +324,34 @@ class PairEngine:
             if layout is None:
                 raise ValueError(f"flows_out must be ({n}, {ctx.height}, {ctx.width}, 2) or ({n}, 2, {ctx.height}, "
                                  f"{ctx.width}), got {shp}")
+        if post_out is not None:
+            post = _DevicePost(ctx, n, B, pov_mode, cut_threshold, post_out)
+            release = getattr(frames, "release", None)
+            marks = []   # (event, frames that have left the host once it completes), oldest first
+
+            def queued(ls, js):
+                if layout is not None:   # before the window calls below let later batches recycle these slots
+                    ctx.export_flows([j % ctx.flow_slots for j in js], flows_out[js[0]:js[-1] + 1], layout)
+                done = post.after_batch(js[0] // B)
+                if release is None:
+                    return
+                if not done:   # batches no longer than the window's radius: no call has waited for this one yet
+                    ctx.sync()
+                    release(js[-1] + 2)
+                    return
+                # an event behind the window call, hence behind the batches of pairs < done: frames <= done have left the host
+                marks.append((_stream_event(ctx, post.stream), done + 1))
+                while marks and (marks[0][0].query() or len(marks) > getattr(self, "depth", 1)):
+                    ev, upto = marks.pop(0)
+                    ev.synchronize()
+                    release(upto)
+
+            self.pass1_pairs(frames, range(n), lambda l: l % ctx.flow_slots, pov_mode, cut_threshold, algo=algo,
+                             farneback=farneback, window=window, queued=queued)
+            if marks:
+                marks[-1][0].synchronize()   # the ring's slots may be reused by the next chunk: every transfer is over
+            post.finish()
+            return post_out
         post = _ChunkPost(ctx, n, B, pov_mode)
 
         def on_batch(js, got):
@@ -253,12 +362,14 @@ class PairEngine:
         self.pass1(frames, 0, n, pov_mode, cut_threshold, on_batch, algo=algo, farneback=farneback, window=window)
         return post.finish()
 
-    def process_flows(self, flows, pov_mode=False, cut_threshold=7.0):
+    def process_flows(self, flows, pov_mode=False, cut_threshold=7.0, post_out=None):
         """One whole chunk from flow fields the caller computed: returns (dots float64[n], records), the contract of
         process_chunk.  `flows` holds the chunk's n pair fields in device memory: one array (n, H, W, 2) or (n, 2, H, W)
         (float32, float16 or bfloat16, any strides; see _capi.device_flows) or a sequence of such arrays (single (H, W, 2)
         fields included), in pair order.  They are imported B at a time into the slot ring (Context.import_flows, on
-        torch's current stream) with `depth` batches in flight; the +-6 window and pass 2 are process_chunk's own."""
+        torch's current stream) with `depth` batches in flight; the +-6 window and pass 2 are process_chunk's own.
+        `post_out`: as in process_chunk (a buffer, or True for a new one) -- pass 2 is queued on the device behind each
+        import, nothing waits, and the buffer is returned for post_records."""
         ctx, B, fs = self.ctx, self.B, self.ctx.flow_slots
         segs = []   # (descriptor, dtype, first pair, count): one per source array
         n = 0
@@ -266,9 +377,12 @@ class PairEngine:
             desc, dt, k = _capi.device_flows(a, ctx.width, ctx.height)
             segs.append((desc, dt, n, k))
             n += k
+        if post_out is True:
+            post_out = post_buffer(ctx, n)
         if n < 1:
-            return np.zeros(0), []
-        post = _ChunkPost(ctx, n, B, pov_mode)
+            return (np.zeros(0), []) if post_out is None else post_out
+        post = (_ChunkPost(ctx, n, B, pov_mode) if post_out is None else
+                _DevicePost(ctx, n, B, pov_mode, cut_threshold, post_out))
 
         def enqueue(j0):
             j1 = min(j0 + B, n)
@@ -284,6 +398,12 @@ class PairEngine:
         def collect(js):
             post.add(js, ctx.pass1_results([j % fs for j in js], cut_threshold))
 
+        if post_out is not None:
+            for j0 in range(0, n, B):
+                enqueue(j0)
+                post.after_batch(j0 // B)
+            post.finish()
+            return post_out
         pending = []
         for j0 in range(0, n, B):
             pending.append(enqueue(j0))
@@ -331,6 +451,44 @@ class _ChunkPost:
         return self.dots, self.recs
 
 
+class _DevicePost:
+    """_ChunkPost's schedule on the device: after_batch(k) queues the Context.radial_window calls window_calls lists for
+    batch k (pair j in flow slot j % flow_slots, its record at byte 48 * j of `out`) on a stream of their own
+    (_side_stream); finish() makes torch's current stream wait for them.  Nothing is read back."""
+
+    def __init__(self, ctx, n, B, pov_mode, cut_threshold, out):
+        self.ctx, self.pov_mode, self.cut_threshold = ctx, pov_mode, cut_threshold
+        self.base, nbytes = _capi._device_span(out)
+        if nbytes < n * _capi.PASS2_DTYPE.itemsize:
+            raise ValueError(f"post_out holds {nbytes} bytes, the chunk's {n} records need {n * _capi.PASS2_DTYPE.itemsize}")
+        self.stream = _side_stream(ctx)
+        self.calls = {}
+        for c in window_calls(n, B):
+            self.calls.setdefault(c[4], []).append(c)
+
+    def after_batch(self, k):
+        """queue batch k's calls; returns the number of leading pairs whose batches these calls have waited for (0: none)"""
+        ctx, fs, item, done = self.ctx, self.ctx.flow_slots, _capi.PASS2_DTYPE.itemsize, 0
+        for lo, hi, first, count, _ in self.calls.get(k, ()):
+            out = _capi._DeviceSpan(self.base + (lo + first) * item, count * item)
+            ctx.radial_window([j % fs for j in range(lo, hi)], first, count, out, SMOOTH_RADIUS, self.cut_threshold, self.pov_mode,
+                              self.stream)
+            done = hi
+        return done
+
+    def finish(self):
+        """the records are complete for work queued on torch's current stream from here on"""
+        if self.stream is not None:
+            import torch
+            torch.cuda.current_stream(self.ctx.device).wait_stream(self.stream)
+
+
+def _pass2_mode(params):
+    """params["hip_pass2"]: "device" runs the window, the cut test and pass 2 on the device with one read per chunk; any
+    other value, or none, is the host schedule"""
+    return params.get("hip_pass2") == "device"
+
+
 def pair_plan(fps, total_frames, params):
     """The sampled frame indices of every chunk frames_to_actions processes for a video of total_frames frames
     (FF:1127-1153; pairs never span chunks): chunk k's pairs are (plan[k][i], plan[k][i + 1]).  A caller with its own flow
@@ -351,13 +509,26 @@ def flows_to_actions(engine, chunk_flows, fps, total_frames, params):
         raise ValueError(f"flows_to_actions: {len(chunk_flows)} chunks of flows for a plan of {len(plan)} chunks")
     dots, cuts, frame_idx = [], [], []
     for chunk, flows in zip(plan, chunk_flows):
-        d, recs = engine.process_flows(flows, bool(params.get("pov_mode", False)), float(params.get("cut_threshold", 7)))
+        pov, thr = bool(params.get("pov_mode", False)), float(params.get("cut_threshold", 7))
+        if _pass2_mode(params):   # params["hip_pass2"] = "device": one buffer and one read per chunk
+            d, recs = post_records(engine.process_flows(flows, pov, thr, post_out=True))
+        else:
+            d, recs = engine.process_flows(flows, pov, thr)
         if len(d) != len(chunk) - 1:
             raise ValueError(f"flows_to_actions: a chunk of {len(chunk)} frames needs {len(chunk) - 1} fields, got {len(d)}")
         dots += [float(v) for v in d]
         cuts += [bool(r[4]) for r in recs]
         frame_idx += chunk[:-1]
     return postchain.actions_from_scalars(dots, cuts, frame_idx, fps, params)
+
+
+def _chunk_scalars(engine, frames, params, **kw):
+    """(dots, records) of one chunk under params: engine.process_chunk, or -- params["hip_pass2"] = "device" -- its device
+    pass 2 with one buffer and one read for the chunk"""
+    pov, thr = bool(params.get("pov_mode", False)), float(params.get("cut_threshold", 7))
+    if not _pass2_mode(params):
+        return engine.process_chunk(frames, pov, thr, **kw)
+    return post_records(engine.process_chunk(frames, pov, thr, post_out=True, **kw))
 
 
 def frames_to_actions(engine, frames, fps, params):
@@ -372,9 +543,7 @@ def frames_to_actions(engine, frames, fps, params):
     fbk = farneback_kwargs(params, frames[0].shape[1], frames[0].shape[0]) if len(frames) else {}
     dots, cuts, frame_idx = [], [], []
     for chunk in pair_plan(fps, len(frames), params):
-        d, recs = engine.process_chunk([frames[i] for i in chunk], bool(params.get("pov_mode", False)),
-                                       float(params.get("cut_threshold", 7)), **({"algo": algo} if algo is not None else {}),
-                                       **fbk)
+        d, recs = _chunk_scalars(engine, [frames[i] for i in chunk], params, **({"algo": algo} if algo is not None else {}), **fbk)
         dots += [float(v) for v in d]
         cuts += [bool(r[4]) for r in recs]
         frame_idx += chunk[:-1]

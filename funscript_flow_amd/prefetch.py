@@ -211,8 +211,8 @@ def video_to_actions(ctx, capture, params, engine=None, ring_frames=None):
     dots, cuts, frame_idx = [], [], []
     try:
         for view, fidx in ring.chunks():
-            d, recs = engine.process_chunk(view, bool(params.get("pov_mode", False)), float(params.get("cut_threshold", 7)),
-                                           **({"algo": algo} if algo is not None else {}), **fbk)
+            # params["hip_pass2"] = "device": the chunk's window, cut test and pass 2 on the device, one read per chunk
+            d, recs = pipeline._chunk_scalars(engine, view, params, **({"algo": algo} if algo is not None else {}), **fbk)
             dots += [float(v) for v in d]
             cuts += [bool(r[4]) for r in recs]
             frame_idx += fidx

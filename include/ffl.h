@@ -24,6 +24,8 @@
  *   ffl_pass1_result        the dict built at FF:898-907 (pos_center, val_pos, mean_mag, cut)
  *   ffl_radial              radial_motion_weighted(flow, center, is_cut, pov_mode)  FF:761-785
  *                           for a batch (ProcessPoolExecutor.submit loop, FF:1232-1236)
+ *   ffl_radial_window       the centre window of FF:1203-1214, the cut test of FF:898-907 and radial_motion_weighted
+ *                           FF:761-785 for a batch, behind the batches on the caller's stream: FF:1203-1236 without the host
  *   ffl_download_flow       the "flow" entry of that dict (tests / callers that want the array)
  *   ffl_upload_frames_device  ffl_upload_frames_raw / _yuv / ffl_upload_frames for frames already in device memory (a GPU
  *                           decoder's surfaces, torch tensors); ffl_export_flows: ffl_download_flow into device memory
@@ -43,7 +45,9 @@
  * on distinct slots).  The per-batch calls do not hold the context lock while they wait for the device or
  * copy frames into staging (ffl_pass1_result(s), ffl_download_flow, ffl_radial, ffl_upload_flow, ffl_sync,
  * ffl_host_free, ffl_upload_frames(_raw) all release it for that time, and wait on events only -- never on a stream
- * another thread may be capturing a graph on); uploads are serialised among themselves, pass-2 calls among themselves.
+ * another thread may be capturing a graph on); uploads are serialised among themselves, pass-2 calls among themselves
+ * (ffl_radial, ffl_radial_window, ffl_export_flows, ffl_import_flows and ffl_upload_flow share one stream; the three
+ * device-memory calls among them only queue work and never wait for it).
  * ffl_flow_pairs waits under the lock only when a lane already has 16 batches queued or evicts a captured graph; the
  * test / measurement hooks (ffl_debug_pair, ffl_download_frame, ffl_profile_read) wait under it.
  * ffl_last_error() returns the message of the context's most recent failing call by any thread.
@@ -288,6 +292,44 @@ int ffl_pass1_results(ffl_ctx *ctx, int n, const int *flow_slots, float cut_thre
 int ffl_radial(ffl_ctx *ctx, int n, const int *flow_slots, const double *cx, const double *cy, const int *is_cut,
                int pov_mode, double *out);
 
+/* One record of ffl_radial_window: what FF:1203-1236 yields for one pair.  48 bytes, 8-byte aligned. */
+typedef struct ffl_pass2_record {
+    double dot;                 /* radial_motion_weighted, FF:761-785; +0.0 when cut */
+    double cx, cy;              /* the window mean of pos_center, FF:1203-1214 */
+    float mean_mag, div_val;    /* as ffl_pass1_results */
+    int32_t x, y;               /* pos_center */
+    int32_t cut, pad;           /* mean_mag > cut_threshold; pad = 0 */
+} ffl_pass2_record;
+
+#define FFL_MAX_RADIUS 32   /* widest centre window of ffl_radial_window: 2 * 32 + 1 pairs */
+
+/* The centre window, the cut test and pass 2 on the device, behind the batches, without the host: ffl_pass1_results, the
+ * +-radius mean of FF:1203-1214 and ffl_radial in one call that only queues work.  seq_slots[0..n_seq) are the flow slots
+ * of consecutive pairs in time order; items first .. first+n-1 of them are computed into out_dev[0..n).
+ *   window   of item j: seq indices max(0, j - radius) .. min(n_seq - 1, j + radius).  It clips at the ends of seq, so a
+ *            chunk edge is expressed by where seq starts and ends.  cx, cy = (double)(exact integer sum of pos_center) /
+ *            (double)count: one IEEE division, np.mean's value.
+ *   cut      mean_mag = (float)(mag_sum / (width * height)) and cut = mean_mag > cut_threshold, the expressions of
+ *            ffl_pass1_results; a record with a NaN follows the rule above: cut = 0 and dot NaN.
+ *   dot      the bits ffl_radial returns for the same slot, centre and pov_mode (the same kernel body and reduction
+ *            order); a cut item gets +0.0 and none of its flow is read.
+ * Refused before any device work, each with its rule in ffl_last_error: n outside 1..FFL_MAX_BATCH; n_seq outside
+ * 1..FFL_MAX_BATCH + 2 * FFL_MAX_RADIUS; first < 0 or first + n > n_seq; radius outside 0..FFL_MAX_RADIUS; a slot out of
+ * range or repeated; a seq slot that holds no result, or a computed slot that holds no flow (FFL_ERR_STATE); out_dev that is
+ * not 8-byte aligned device memory of the context's device, or whose n records do not lie inside one allocation
+ * (page-locked host memory, ffl_host_alloc's included, belongs to ffl_radial); a capturing `stream` (FFL_ERR_STATE).
+ * Stream contract (`stream` is a hipStream_t as an integer; 0 = the null stream):
+ *   - a stream that is capturing a graph is refused with FFL_ERR_STATE; that check is the first HIP call made on it;
+ *   - the library's stream waits for the batch, import or upload that produced every seq slot and for the work queued on
+ *     `stream` before the call (out_dev may still be being read), then writes out_dev with three launches (k_window_plan,
+ *     k_radial_window, k_radial_window_final), and `stream` is made to wait for that;
+ *   - the call counts as a use of every seq slot, the neighbours whose records alone are read included: a later batch that
+ *     recycles one of them waits for it on the device;
+ *   - the host never waits for the device, except where settling the library's event ring makes every call wait.
+ * Nothing of this call is ever captured into the library's graphs. */
+int ffl_radial_window(ffl_ctx *ctx, int n_seq, const int *seq_slots, int first, int n, int radius, float cut_threshold,
+                      int pov_mode, ffl_pass2_record *out_dev, uint64_t stream);
+
 /* Copy a finished flow field to host memory as (height, width, 2) float32, cv2 layout. */
 int ffl_download_flow(ffl_ctx *ctx, int flow_slot, float *dst);
 
@@ -459,7 +501,7 @@ int ffl_profile_enable(ffl_ctx *ctx, unsigned class_mask);
 #define FFL_K_UPDATE_MATRICES 4
 #define FFL_K_BLUR_SOLVE 5
 #define FFL_K_PASS1 6
-#define FFL_K_RADIAL 7
+#define FFL_K_RADIAL 7   /* k_radial + k_radial_final of ffl_radial; ffl_radial_window's three launches belong to no class */
 #define FFL_K_COUNT 8
 /* Read and reset the accumulated (launch count, total milliseconds) of one kernel class.
  * Synchronises the context. */
