@@ -314,16 +314,12 @@ struct ffl_ctx {
     RawBuf raw[FFL_RAW_RING];
     unsigned raw_next = 0;
     EvRing post_ring;  // events of the calls that queue on stream `post` (publish_post), FFL_EV_RING entries
-    // device-memory I/O (ffl_upload_frames_device / ffl_export_flows / ffl_import_flows): the event recorded on the
-    // caller's stream (waited for at once, so one is enough), and, allocated on first use, the per-call frame descriptor
-    // tables -- a pinned copy per up_ring entry (n_fslots descriptors each) and the device table k_frontend_dev reads (`copy`)
+    // device-memory I/O (ffl_upload_frames_device / ffl_export_flows / ffl_import_flows / ffl_radial_window): the event
+    // recorded on the caller's stream (waited for at once, so one is enough), and, allocated on first use, the per-call
+    // frame descriptor tables -- a pinned copy per up_ring entry (n_fslots descriptors each) and the device table
+    // k_frontend_dev reads (`copy`)
     Event ev_caller;
     PinBuf<FrameDesc> h_dtab; DevBuf<FrameDesc> d_dtab;
-    // ffl_import_flows, allocated on first use (stream `post`): the slot / record table k_import_pass1 fills for
-    // k_pass1_final, and pass-1 partials for max_batch fields
-    DevBuf<PairTab> d_itab;
-    DevBuf<unsigned long long> d_ikey;
-    DevBuf<double> d_isum;
     // flow slots
     DevBuf<float> d_flow;             // [n_slots][2N]
     // Result records live in pinned, device-mapped host memory: the reduction kernels store their
@@ -332,13 +328,19 @@ struct ffl_ctx {
     Pass1Result *d_res = nullptr;     // device alias of h_res
     std::vector<EvRef> ev_slot_done;  // per flow slot: the batch (a lane's ring) or pass-2 / flow-upload call (post_ring) that used it last
     std::vector<char> slot_state;     // 1: queued/ready, 0: empty or its batch failed
-    DevBuf<RadialTab> d_rtab; PinBuf<RadialTab> h_rtab;  // pass-2 table (s_post; ffl_radial waits for the stream, so one copy)
-    DevBuf<BatchTab> d_ptab; PinBuf<BatchTab> h_ptab;    // ffl_upload_flow's one-pair table (s_post)
-    DevBuf<double> d_rpsum;                            // pass-2 partial sums (s_post)
-    DevBuf<WindowItem> d_wtab;                         // ffl_radial_window's item table, FFL_MAXB entries (s_post)
+    // Stream `post`'s tables and scratch: ONE copy of each, shared by ffl_upload_flow, ffl_import_flows, ffl_radial and
+    // ffl_radial_window.  That is safe because every kernel and copy that touches them is queued on stream `post`, by a
+    // call that holds post_mu while it queues: a user runs after the previous one has finished, so nothing read from a
+    // buffer was left there by another call and nothing is overwritten while it is still read.  The host writes only the
+    // two pinned tables, each while the stream holds no copy out of it: h_ptab after ffl_upload_flow has drained the
+    // stream, h_wtab by ffl_radial, the one call that copies it and that returns only once the stream has drained.
+    DevBuf<PairTab> d_ptab; PinBuf<PairTab> h_ptab;    // pass 1: flow[0][b] and res[b] of the call's items (host: item 0, ffl_upload_flow)
+    DevBuf<unsigned long long> d_pskey;                // pass-1 partial keys of max_batch items (lay.p1)
+    DevBuf<double> d_rpsum;                            // partial sums of either pass: p1_blocks per item, FFL_MAXB items (pass 2
+                                                       // takes up to FFL_MAXB whatever max_batch is, and never more blocks than pass 1)
+    DevBuf<WindowItem> d_wtab; PinBuf<WindowItem> h_wtab;  // pass-2 items, FFL_MAXB entries (host: ffl_radial; device: k_window_plan)
     DevBuf<double> d_wytab;                            // pass-2 row weights (h - y) / h and y / h
-    PinBuf<double> h_radial; double *d_radial = nullptr;  // pinned pass-2 results and their device alias
-    DevBuf<unsigned long long> d_ppkey;                // ffl_upload_flow scratch (s_post)
+    PinBuf<Pass2Record> h_radial; Pass2Record *d_radial = nullptr;  // ffl_radial's mapped pinned records (only `dot` is used) and their device alias
     int p1_blocks = 0;
     // profiling
     unsigned prof_mask = 0;   // bit k set: bracket every launch of kernel class k with HIP events
@@ -363,7 +365,7 @@ struct ffl_ctx {
     // Two small locks order the users of shared single-copy resources among themselves; both are taken BEFORE `mu`, and
     // up_mu before post_mu where a call needs both (ffl_sync, which releases them before it waits):
     //   up_mu    uploaders: the per-slot staging areas, the copy pool and the raw-frame ring
-    //   post_mu  users of stream `post` and its single pinned tables / result buffer (ffl_radial, ffl_upload_flow)
+    //   post_mu  users of stream `post`, its single tables, scratch and result buffer (see d_ptab)
     mutable std::recursive_mutex mu;
     std::mutex up_mu, post_mu;
     int graph_bad_epoch = -1;  // option epoch in which a graph capture failed: batches launch eagerly until it changes
@@ -885,12 +887,11 @@ static int create_resources(ffl_ctx *c) {
         HIPCHK_ALLOC(nullptr, hipMalloc, c->d_wytab, wy.size());
         HIPCHK(nullptr, hipMemcpy(c->d_wytab, wy.data(), sizeof(double) * wy.size(), hipMemcpyHostToDevice));
     }
-    HIPCHK_ALLOC(nullptr, hipMalloc, c->d_rtab, 1);
     HIPCHK_ALLOC(nullptr, hipMalloc, c->d_wtab, FFL_MAXB);
-    HIPCHK_ALLOC(nullptr, hipHostMalloc, c->h_rtab, 1, hipHostMallocDefault);
+    HIPCHK_ALLOC(nullptr, hipHostMalloc, c->h_wtab, FFL_MAXB, hipHostMallocDefault);
     HIPCHK_ALLOC(nullptr, hipMalloc, c->d_ptab, 1);
     HIPCHK_ALLOC(nullptr, hipHostMalloc, c->h_ptab, 1, hipHostMallocDefault);
-    HIPCHK_ALLOC(nullptr, hipMalloc, c->d_ppkey, c->p1_blocks);
+    HIPCHK_ALLOC(nullptr, hipMalloc, c->d_pskey, lay.p1);
     HIPCHK_ALLOC(nullptr, hipHostMalloc, c->h_radial, FFL_MAXB, hipHostMallocMapped);
     HIPCHK(nullptr, hipHostGetDevicePointer((void **)&c->d_radial, c->h_radial, 0));
     c->ev_uploaded.assign(n_frame_slots, EvRef{});
@@ -1972,12 +1973,12 @@ int ffl_pass1_results(ffl_ctx *c, int n, const int *slots, float cut_threshold, 
 int ffl_radial(ffl_ctx *c, int n, const int *slots, const double *cx, const double *cy, const int *is_cut, int pov_mode,
                double *out) {
     if (!c) return FFL_ERR_INVALID;
-    std::unique_lock<std::mutex> pl(c->post_mu);  // one pass-2 call at a time owns stream `post`, h_rtab and h_radial
+    std::unique_lock<std::mutex> pl(c->post_mu);  // one pass-2 call at a time owns stream `post`, h_wtab and h_radial
     CtxLock lk(c->mu);
     if (n < 1 || n > FFL_MAXB || !slots || !cx || !cy || !out) return set_err(c, FFL_ERR_INVALID, "ffl_radial: bad arguments");
     if (int rc = check_flow_slots(c, "ffl_radial", n, slots, "flow", nullptr)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    RadialTab &rt = *c->h_rtab;  // the previous call waited for s_post, so the pinned copy is free
+    WindowItem *tab = c->h_wtab;  // the previous call waited for s_post, so the pinned copy is free
     WaitOnce wait_post(c->s_post);
     int m = 0;
     int map[FFL_MAXB], used[FFL_MAXB];  // the slots pass 2 reads and their places in `out`
@@ -1987,18 +1988,16 @@ int ffl_radial(ffl_ctx *c, int n, const int *slots, const double *cx, const doub
             continue;
         }
         HIPCHK(c, wait_post(c->ev_slot_done[slots[i]].get()));
-        rt.flow[m] = c->d_flow + (size_t)slots[i] * 2 * c->N;
-        rt.cx[m] = cx[i];
-        rt.cy[m] = cy[i];
+        tab[m] = WindowItem{c->d_flow + (size_t)slots[i] * 2 * c->N, cx[i], cy[i], 0, 0};
         used[m] = slots[i];
         map[m++] = i;
     }
     if (m == 0) return FFL_OK;
     hipStream_t st = c->s_post;
     {
-        HIPCHK(c, hipMemcpyAsync(c->d_rtab, &rt, sizeof(RadialTab), hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->d_wtab, tab, sizeof(WindowItem) * m, hipMemcpyHostToDevice, st));
         ProfScope ps(c, FFL_K_RADIAL, st);
-        ffl_launch_radial(c->d_rtab, m, c->w, c->h, pov_mode, c->d_wytab, c->d_rpsum, c->d_radial, st);
+        ffl_launch_radial(c->d_wtab, m, c->w, c->h, pov_mode, c->d_wytab, c->d_rpsum, c->d_radial, st);
     }
     // the slots' "last use" now includes this pass 2: the wait below runs without the context lock, so another thread
     // may queue a batch that recycles one of these slots meanwhile -- it must run behind the kernel that reads them
@@ -2009,7 +2008,7 @@ int ffl_radial(ffl_ctx *c, int n, const int *slots, const double *cx, const doub
     lk.lock();
     HIPCHK(c, se);
     HIPCHK(c, hipGetLastError());
-    for (int j = 0; j < m; j++) out[map[j]] = c->h_radial[j];
+    for (int j = 0; j < m; j++) out[map[j]] = c->h_radial[j].dot;
     return FFL_OK;
 }
 
@@ -2152,6 +2151,30 @@ static int caller_join(ffl_ctx *c, hipStream_t cst, WaitOnce &wait) {
     return FFL_OK;
 }
 
+// The contract for a call that queues on stream `post` (the caller holds post_mu and the context lock, and has refused
+// what it can refuse without the device).  post_begin(): the caller's stream (*cst), the check of the call's one region of
+// caller memory, then stream `post` behind the caller's queued work and behind the last users of the n slots the call reads
+// or writes.  post_end(), after the launches: the call becomes those slots' last use, and the caller's later work runs
+// behind it.
+static int post_begin(ffl_ctx *c, const char *fn, uint64_t stream, hipStream_t *cst, const char *what, const void *p,
+                      size_t bytes, const char *host_hint, int n, const int *slots) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = caller_stream(c, fn, stream, cst)) return rc;
+    if (int rc = dev_mem_check(c, fn, what, p, bytes, host_hint)) return rc;
+    WaitOnce wait_post(c->s_post);
+    if (int rc = caller_join(c, *cst, wait_post)) return rc;
+    for (int i = 0; i < n; i++) HIPCHK(c, wait_post(c->ev_slot_done[slots[i]].get()));
+    return FFL_OK;
+}
+
+static int post_end(ffl_ctx *c, hipStream_t cst, int n, const int *slots) {
+    HIPCHK(c, hipGetLastError());
+    EvRef done;
+    if (int rc = publish_post(c, n, slots, &done)) return rc;  // a batch recycling one of the slots waits for this call
+    HIPCHK(c, hipStreamWaitEvent(cst, done.get(), 0));
+    return FFL_OK;
+}
+
 int ffl_dev_frame_check(int format, int sw, int sh, const ffl_dev_frame *f, int rw, int rh, int cx, int cy, int out_w, int out_h) {
     FrontParams p;
     return dev_frame_check(nullptr, "ffl_dev_frame_check", 0, format, sw, sh, f, rw, rh, cx, cy, out_w, out_h, &p);
@@ -2247,26 +2270,17 @@ int ffl_export_flows(ffl_ctx *c, int n, const int *slots, float *dst, int layout
     if (n > 1 && (size_t)(item_stride < 0 ? -item_stride : item_stride) < item)
         return set_err(c, FFL_ERR_INVALID, "%s: item stride %td is smaller than one flow field (%zu bytes)", fn, item_stride, item);
     if (int rc = check_flow_slots(c, fn, n, slots, "flow", nullptr)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
     hipStream_t cst;
-    if (int rc = caller_stream(c, fn, stream, &cst)) return rc;
     const ptrdiff_t span = (ptrdiff_t)(n - 1) * item_stride;
     const char *lo = (const char *)dst + (span < 0 ? span : 0);
-    if (int rc = dev_mem_check(c, fn, "dst", lo, (size_t)(span < 0 ? -span : span) + item)) return rc;
-    WaitOnce wait_post(c->s_post);
-    if (int rc = caller_join(c, cst, wait_post)) return rc;
-    for (int i = 0; i < n; i++) HIPCHK(c, wait_post(c->ev_slot_done[slots[i]].get()));
+    if (int rc = post_begin(c, fn, stream, &cst, "dst", lo, (size_t)(span < 0 ? -span : span) + item, kHostFrames, n, slots)) return rc;
     for (int i0 = 0; i0 < n; i0 += FFL_MAXB) {
         const int m = n - i0 < FFL_MAXB ? n - i0 : FFL_MAXB;
         ExportTab t;
         for (int i = 0; i < m; i++) t.slot[i] = slots[i0 + i];
         ffl_launch_export_flows(c->d_flow, t, m, c->N, (char *)dst + (ptrdiff_t)i0 * item_stride, item_stride, layout, c->s_post);
     }
-    HIPCHK(c, hipGetLastError());
-    EvRef ev;
-    if (int rc = publish_post(c, n, slots, &ev)) return rc;  // a batch recycling a slot waits for the export
-    HIPCHK(c, hipStreamWaitEvent(cst, ev.get(), 0));
-    return FFL_OK;
+    return post_end(c, cst, n, slots);
 }
 
 // The centre window, the cut test and pass 2 of items first .. first+n-1 of seq on stream `post`, ordered after the
@@ -2297,27 +2311,17 @@ int ffl_radial_window(ffl_ctx *c, int n_seq, const int *seq, int first, int n, i
     // a slot's state stands for its record and its flow alike, so one check covers the neighbours and the computed items
     if (int rc = check_flow_slots(c, fn, n_seq, seq, "result", "repeated in one call")) return rc;
     if ((uintptr_t)out % 8) return set_err(c, FFL_ERR_INVALID, "%s: out_dev must be 8-byte aligned", fn);
-    HIPCHK(c, hipSetDevice(c->device));
     hipStream_t cst;
-    if (int rc = caller_stream(c, fn, stream, &cst)) return rc;
-    if (int rc = dev_mem_check(c, fn, "out_dev", out, sizeof(ffl_pass2_record) * (size_t)n,
-                               "results in host memory come from ffl_pass1_results and ffl_radial"))
+    if (int rc = post_begin(c, fn, stream, &cst, "out_dev", out, sizeof(ffl_pass2_record) * (size_t)n,
+                            "results in host memory come from ffl_pass1_results and ffl_radial", n_seq, seq))
         return rc;
-    WaitOnce wait_post(c->s_post);
-    if (int rc = caller_join(c, cst, wait_post)) return rc;
     WindowSeq t;
-    for (int i = 0; i < n_seq; i++) {
-        HIPCHK(c, wait_post(c->ev_slot_done[seq[i]].get()));
-        t.slot[i] = seq[i];
-    }
-    // not timed under FFL_K_RADIAL: that class counts k_radial + k_radial_final pairs, one per ffl_radial call
-    ffl_launch_radial_window(t, n_seq, first, n, radius, cut_threshold, c->d_res, c->d_flow, c->w, c->h, pov_mode ? 1 : 0,
-                             c->d_wytab, c->d_wtab, c->d_rpsum, reinterpret_cast<Pass2Record *>(out), c->s_post);
-    HIPCHK(c, hipGetLastError());
-    EvRef done;
-    if (int rc = publish_post(c, n_seq, seq, &done)) return rc;  // a batch recycling a seq slot waits for this call
-    HIPCHK(c, hipStreamWaitEvent(cst, done.get(), 0));
-    return FFL_OK;
+    for (int i = 0; i < n_seq; i++) t.slot[i] = seq[i];
+    Pass2Record *rec = reinterpret_cast<Pass2Record *>(out);
+    // not timed under FFL_K_RADIAL: that class counts the k_radial + k_radial_final pairs of ffl_radial, one per call
+    ffl_launch_window_plan(t, n_seq, first, n, radius, cut_threshold, c->d_res, c->d_flow, c->w, c->h, c->d_wtab, rec, c->s_post);
+    ffl_launch_radial(c->d_wtab, n, c->w, c->h, pov_mode ? 1 : 0, c->d_wytab, c->d_rpsum, rec, c->s_post);
+    return post_end(c, cst, n_seq, seq);
 }
 
 // ---- flow import -------------------------------------------------------------------------------
@@ -2376,38 +2380,21 @@ int ffl_import_flows(ffl_ctx *c, int n, const int *slots, const ffl_dev_flow *f,
     int mode;
     size_t bytes;
     if (int rc = dev_flow_check(c, fn, dtype, n, c->w, c->h, f, &mode, &bytes)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t cst;
-    if (int rc = caller_stream(c, fn, stream, &cst)) return rc;
-    if (int rc = dev_mem_check(c, fn, "the flow fields", f->base, bytes, "host flow fields go through ffl_upload_flow")) return rc;
-    if (!c->d_itab) {
-        DevBuf<PairTab> tab; DevBuf<unsigned long long> key; DevBuf<double> sum;  // all or nothing, as d_dtab / h_dtab
-        HIPCHK_ALLOC(c, hipMalloc, tab, 1);
-        HIPCHK_ALLOC(c, hipMalloc, key, c->lay.p1);
-        HIPCHK_ALLOC(c, hipMalloc, sum, c->lay.p1);
-        c->d_itab = std::move(tab);
-        c->d_ikey = std::move(key);
-        c->d_isum = std::move(sum);
-    }
     // stream `post` waits for the producer's queued work and for the last users of the slots (a batch, a pass 2, an export)
-    WaitOnce wait_post(c->s_post);
-    if (int rc = caller_join(c, cst, wait_post)) return rc;
-    for (int i = 0; i < n; i++) HIPCHK(c, wait_post(c->ev_slot_done[slots[i]].get()));
+    hipStream_t cst;
+    if (int rc = post_begin(c, fn, stream, &cst, "the flow fields", f->base, bytes, "host flow fields go through ffl_upload_flow",
+                            n, slots))
+        return rc;
     const ImportArgs a{(const char *)f->base, (long long)f->item_stride, (long long)f->row_pitch, (long long)f->pixel_stride,
                        (long long)f->channel_stride, c->d_flow, c->d_res};
     ExportTab t;
     for (int i = 0; i < n; i++) t.slot[i] = slots[i];
     {
         ProfScope ps(c, FFL_K_PASS1, c->s_post);
-        ffl_launch_import_pass1(a, t, n, dtype, mode, c->w, c->h, pov_mode ? 1 : 0, c->opt.import_fused, c->d_itab, c->d_ikey,
-                                c->d_isum, c->s_post);
+        ffl_launch_import_pass1(a, t, n, dtype, mode, c->w, c->h, pov_mode ? 1 : 0, c->opt.import_fused, c->d_ptab, c->d_pskey,
+                                c->d_rpsum, c->s_post);
     }
-    HIPCHK(c, hipGetLastError());
-    EvRef done;
-    if (int rc = publish_post(c, n, slots, &done)) return rc;
-    // the caller's later work (overwriting or freeing the sources) runs after the fields have been read
-    HIPCHK(c, hipStreamWaitEvent(cst, done.get(), 0));
-    return FFL_OK;
+    return post_end(c, cst, n, slots);  // the caller's later work (overwriting or freeing the sources) runs after the fields have been read
 }
 
 int ffl_upload_flow(ffl_ctx *c, int slot, const float *src, int pov_mode) {
@@ -2423,12 +2410,12 @@ int ffl_upload_flow(ffl_ctx *c, int slot, const float *src, int pov_mode) {
     lk.lock();
     HIPCHK(c, se);
     HIPCHK(c, hipMemcpy(c->d_flow + (size_t)slot * 2 * c->N, src, sizeof(float) * 2 * c->N, hipMemcpyHostToDevice));
-    c->h_ptab->pt.flow[0][0] = c->d_flow + (size_t)slot * 2 * c->N;  // the stream was drained above: the pinned copy is free
-    c->h_ptab->pt.res[0] = c->d_res + slot;
-    HIPCHK(c, hipMemcpyAsync(c->d_ptab, c->h_ptab, sizeof(BatchTab), hipMemcpyHostToDevice, st));
+    c->h_ptab->flow[0][0] = c->d_flow + (size_t)slot * 2 * c->N;  // the stream was drained above: the pinned copy is free
+    c->h_ptab->res[0] = c->d_res + slot;
+    HIPCHK(c, hipMemcpyAsync(c->d_ptab, c->h_ptab, sizeof(PairTab), hipMemcpyHostToDevice, st));
     {
         ProfScope ps(c, FFL_K_PASS1, st);
-        ffl_launch_pass1(&c->d_ptab->pt, 1, c->w, c->h, pov_mode, c->d_ppkey, c->d_rpsum, st);
+        ffl_launch_pass1(c->d_ptab, 1, c->w, c->h, pov_mode, c->d_pskey, c->d_rpsum, st);
     }
     EvRef done;
     if (int rc = publish_post(c, 1, &slot, &done)) return rc;

@@ -221,20 +221,13 @@ int ffl_pass1_blocks(int w, int h);
 // pass 1 of the level-0 flows pt->flow[0][b]; records go to pt->res[b]
 void ffl_launch_pass1(const PairTab *pt, int nB, int w, int h, int pov_mode, unsigned long long *pkey, double *psum,
                       hipStream_t st);
-struct RadialTab {  // device-resident like the batch tables
-    const float *flow[FFL_MAXB];
-    double cx[FFL_MAXB], cy[FFL_MAXB];
-};
-// wytab: 2 * h doubles, [y] = (double)(h - y) / h, [h + y] = (double)y / h (the row weights of FF:780-783)
-void ffl_launch_radial(const RadialTab *rt, int nB, int w, int h, int pov_mode, const double *wytab, double *psum,
-                       double *out, hipStream_t st);
 
-// ffl_radial_window (k_window_plan, k_radial_window, k_radial_window_final)
+// pass 2 (k_radial, k_radial_final) and the plan of ffl_radial_window (k_window_plan)
 #define FFL_WINDOW_MAX_RADIUS 32     // = FFL_MAX_RADIUS of include/ffl.h
 struct WindowSeq {   // the flow slots of the call's consecutive pairs; travels as a kernel argument (1280 bytes)
     int slot[FFL_MAXB + 2 * FFL_WINDOW_MAX_RADIUS];
 };
-struct WindowItem {  // what k_window_plan leaves in device memory for the radial grid, one per computed item
+struct WindowItem {  // one item of the radial grid, in device memory: from the host (ffl_radial) or from k_window_plan
     const float *flow;
     double cx, cy;
     int cut, pad;
@@ -244,11 +237,14 @@ struct Pass2Record { // = ffl_pass2_record of include/ffl.h (ffl_api.hip asserts
     float mean_mag, div_val;
     int x, y, cut, pad;
 };
-// items first .. first+n-1 of seq -> out[0..n): plan, radial grid, final (three launches); tab holds n WindowItems, psum
-// the radial partials of n items
-void ffl_launch_radial_window(const WindowSeq &seq, int n_seq, int first, int n, int radius, float cut_threshold,
-                              const Pass1Result *res, const float *flow, int w, int h, int pov_mode, const double *wytab,
-                              WindowItem *tab, double *psum, Pass2Record *out, hipStream_t st);
+// items tab[0..n) -> out[i].dot (+0.0 for a cut item); psum holds the partials of n items, ffl_pass1_blocks(w, h) each at most
+// wytab: 2 * h doubles, [y] = (double)(h - y) / h, [h + y] = (double)y / h (the row weights of FF:780-783)
+void ffl_launch_radial(const WindowItem *tab, int n, int w, int h, int pov_mode, const double *wytab, double *psum,
+                       Pass2Record *out, hipStream_t st);
+// items first .. first+n-1 of seq -> tab[0..n) and every field of out[0..n) but `dot`
+void ffl_launch_window_plan(const WindowSeq &seq, int n_seq, int first, int n, int radius, float cut_threshold,
+                            const Pass1Result *res, const float *flow, int w, int h, WindowItem *tab, Pass2Record *out,
+                            hipStream_t st);
 
 // XCD-aware order of a 1-D run of `count` tiles: the l-th workgroup of the run (l and l+8 share an XCD under the
 // observed round-robin placement; the run must start at a multiple of 8) takes tile (l % 8) * chunk + l / 8, so every
@@ -300,7 +296,7 @@ __device__ __forceinline__ bool ffl_tile_coord(int tiles_x, int tiles_y, int nB,
     return true;
 }
 
-// A pointer read from a device-resident table (PairTab / RadialTab) is a generic pointer to the compiler: it
+// A pointer read from a device-resident table (PairTab / WindowItem) is a generic pointer to the compiler: it
 // emits flat_load with per-lane 64-bit address arithmetic and waits on two counters.  Every such pointer is a
 // hipMalloc'ed buffer, so its accesses go through these helpers, which name the global address space:
 // global_load, saddr form when the base is wave-uniform.  Vectors need 4-byte alignment only.

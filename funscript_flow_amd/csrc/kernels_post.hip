@@ -21,9 +21,10 @@
 static inline int ffl_strip_waves(int w, int h, int strip) {
     return ((w + strip - 1) / strip) * ((h + P1_RG - 1) / P1_RG);
 }
-int ffl_pass1_blocks(int w, int h) {  // workgroups (= partial results) per pair, the larger of the two passes
-    return (ffl_strip_waves(w, h, P1_STRIP) + 3) / 4;
-}
+// workgroups (= partial results) per item: four waves each.  Pass 1's count is the larger one (P1_STRIP < P2_STRIP), so
+// scratch sized by it serves both passes.
+int ffl_pass1_blocks(int w, int h) { return (ffl_strip_waves(w, h, P1_STRIP) + 3) / 4; }
+static inline int ffl_radial_blocks(int w, int h) { return (ffl_strip_waves(w, h, P2_STRIP) + 3) / 4; }
 
 // np.gradient along one axis: central difference /2 inside, one-sided at the ends (FF:754)
 __device__ __forceinline__ float ffl_grad(float lo, float hi, int idx, int n) {
@@ -206,7 +207,7 @@ __global__ __launch_bounds__(P1_THREADS) void k_pass1_final(const PairTab *__res
 
 void ffl_launch_pass1(const PairTab *pt, int nB, int w, int h, int pov_mode, unsigned long long *pkey, double *psum,
                       hipStream_t st) {
-    int nblk = (ffl_strip_waves(w, h, P1_STRIP) + 3) / 4;
+    const int nblk = ffl_pass1_blocks(w, h);
     hipLaunchKernelGGL(k_pass1, dim3(nblk, nB), dim3(P1_THREADS), 0, st, pt, w, h, pov_mode, pkey, psum);
     hipLaunchKernelGGL(k_pass1_final, dim3(nB), dim3(P1_THREADS), 0, st, pt, w, h, pov_mode, nblk, pkey, psum);
 }
@@ -216,8 +217,8 @@ void ffl_launch_pass1(const PairTab *pt, int nB, int w, int h, int pov_mode, uns
 // context on the host (IEEE division, the value the device's division yields).  The row index is wave-uniform, so the
 // weight comes with a scalar load instead of a 15-instruction f64 division per lane and row -- the kernel had
 // hoisted all 16 of them and needed 198 VGPRs (2 waves per SIMD).
-// The body of k_radial and k_radial_window: one per-lane order and one wave / workgroup reduction order whatever table
-// the field and its centre come from, so the two give the same bits for the same slot, centre and pov_mode.
+// The body of k_radial: one per-lane order and one wave / workgroup reduction order, so ffl_radial and ffl_radial_window
+// give the same bits for the same slot, centre and pov_mode.
 __device__ __forceinline__ void ffl_radial_body(const float2 *__restrict__ flow, double cx, double cy, int w, int h,
                                                 int pov_mode, int b, const double *__restrict__ wytab,
                                                 double *__restrict__ psum, double *ssum) {
@@ -263,14 +264,7 @@ __device__ __forceinline__ void ffl_radial_body(const float2 *__restrict__ flow,
     }
 }
 
-__global__ __launch_bounds__(P1_THREADS) void k_radial(const RadialTab *__restrict__ rt, int w, int h, int pov_mode,
-                                                       const double *__restrict__ wytab, double *__restrict__ psum) {
-    __shared__ double ssum[P1_THREADS / 64];
-    const int b = blockIdx.y;
-    ffl_radial_body(reinterpret_cast<const float2 *>(rt->flow[b]), rt->cx[b], rt->cy[b], w, h, pov_mode, b, wytab, psum, ssum);
-}
-
-// The body of k_radial_final and k_radial_window_final: item b's nblk partials in one order; the mean is valid in thread 0.
+// The body of k_radial_final: item b's nblk partials in one order; the mean is valid in thread 0.
 __device__ __forceinline__ double ffl_radial_final_body(int w, int h, int nblk, int b, const double *__restrict__ psum,
                                                         double *ssum) {
     double sum = 0.0;
@@ -286,29 +280,42 @@ __device__ __forceinline__ double ffl_radial_final_body(int w, int h, int nblk, 
     return sum;
 }
 
-__global__ __launch_bounds__(P1_THREADS) void k_radial_final(int w, int h, int nblk, const double *__restrict__ psum,
-                                                             double *__restrict__ out) {
+// The radial pair over a WindowItem table in device memory: ffl_radial copies one there, ffl_radial_window has
+// k_window_plan write it.  The workgroups of a cut item leave on a workgroup-uniform branch before they load anything of the
+// flow, and k_radial_final answers it +0.0.
+__global__ __launch_bounds__(P1_THREADS) void k_radial(const WindowItem *__restrict__ tab, int w, int h, int pov_mode,
+                                                       const double *__restrict__ wytab, double *__restrict__ psum) {
     __shared__ double ssum[P1_THREADS / 64];
-    const int b = blockIdx.x;
-    const double mean = ffl_radial_final_body(w, h, nblk, b, psum, ssum);
-    if (threadIdx.x == 0) out[b] = mean;
+    const int b = blockIdx.y;
+    if (tab[b].cut) return;   // workgroup-uniform: FF:766-767, a cut is 0.0 without a look at the flow
+    ffl_radial_body(reinterpret_cast<const float2 *>(tab[b].flow), tab[b].cx, tab[b].cy, w, h, pov_mode, b, wytab, psum, ssum);
 }
 
-void ffl_launch_radial(const RadialTab *rt, int nB, int w, int h, int pov_mode, const double *wytab, double *psum,
-                       double *out, hipStream_t st) {
-    int nblk = (ffl_strip_waves(w, h, P2_STRIP) + 3) / 4;
-    hipLaunchKernelGGL(k_radial, dim3(nblk, nB), dim3(P1_THREADS), 0, st, rt, w, h, pov_mode, wytab, psum);
-    hipLaunchKernelGGL(k_radial_final, dim3(nB), dim3(P1_THREADS), 0, st, w, h, nblk, psum, out);
+__global__ __launch_bounds__(P1_THREADS) void k_radial_final(const WindowItem *__restrict__ tab, int w, int h, int nblk,
+                                                             const double *__restrict__ psum, Pass2Record *__restrict__ out) {
+    __shared__ double ssum[P1_THREADS / 64];
+    const int b = blockIdx.x;
+    if (tab[b].cut) {         // its partials were never written
+        if (threadIdx.x == 0) out[b].dot = 0.0;
+        return;
+    }
+    const double mean = ffl_radial_final_body(w, h, nblk, b, psum, ssum);
+    if (threadIdx.x == 0) out[b].dot = mean;
+}
+
+void ffl_launch_radial(const WindowItem *tab, int n, int w, int h, int pov_mode, const double *wytab, double *psum,
+                       Pass2Record *out, hipStream_t st) {
+    const int nblk = ffl_radial_blocks(w, h);
+    hipLaunchKernelGGL(k_radial, dim3(nblk, n), dim3(P1_THREADS), 0, st, tab, w, h, pov_mode, wytab, psum);
+    hipLaunchKernelGGL(k_radial_final, dim3(n), dim3(P1_THREADS), 0, st, tab, w, h, nblk, psum, out);
 }
 
 // ---- pass 2 behind the batches, host-free (ffl_radial_window) ---------------------------------
-// Three launches per call.  k_window_plan: one thread per item forms the clipped centre window, mean_mag and cut out of the
+// k_window_plan, then the radial pair.  One thread per item forms the clipped centre window, mean_mag and cut out of the
 // pass-1 records and writes the device-resident WindowItem table plus every field of the record but `dot`.  The records
 // are mapped pinned memory: a workgroup stages the (x, y) of the <= 64 + 2 * radius records its items' windows span in
 // LDS, so the window costs one (x, y) read per record and workgroup instead of 2 * radius + 1 per item; each item then
-// reads mag_sum and div_val of its own record once more.  Nothing of a record is read by the radial grid.  k_radial_window: k_radial's body on that table; the workgroups of a cut item
-// leave on a wave-uniform branch before they load anything of the flow.  k_radial_window_final: k_radial_final's
-// reduction into `dot`, +0.0 for a cut item.
+// reads mag_sum and div_val of its own record once more.  Nothing of a record is read by the radial grid.
 #define W2_THREADS 64
 
 __global__ __launch_bounds__(W2_THREADS) void k_window_plan(const WindowSeq seq, int n_seq, int first, int n, int radius,
@@ -358,35 +365,11 @@ __global__ __launch_bounds__(W2_THREADS) void k_window_plan(const WindowSeq seq,
     o->pad = 0;
 }
 
-__global__ __launch_bounds__(P1_THREADS) void k_radial_window(const WindowItem *__restrict__ tab, int w, int h, int pov_mode,
-                                                              const double *__restrict__ wytab, double *__restrict__ psum) {
-    __shared__ double ssum[P1_THREADS / 64];
-    const int b = blockIdx.y;
-    if (tab[b].cut) return;   // workgroup-uniform: FF:766-767, a cut is 0.0 without a look at the flow
-    ffl_radial_body(reinterpret_cast<const float2 *>(tab[b].flow), tab[b].cx, tab[b].cy, w, h, pov_mode, b, wytab, psum, ssum);
-}
-
-__global__ __launch_bounds__(P1_THREADS) void k_radial_window_final(const WindowItem *__restrict__ tab, int w, int h, int nblk,
-                                                                    const double *__restrict__ psum,
-                                                                    Pass2Record *__restrict__ out) {
-    __shared__ double ssum[P1_THREADS / 64];
-    const int b = blockIdx.x;
-    if (tab[b].cut) {         // its partials were never written
-        if (threadIdx.x == 0) out[b].dot = 0.0;
-        return;
-    }
-    const double mean = ffl_radial_final_body(w, h, nblk, b, psum, ssum);
-    if (threadIdx.x == 0) out[b].dot = mean;
-}
-
-void ffl_launch_radial_window(const WindowSeq &seq, int n_seq, int first, int n, int radius, float cut_threshold,
-                              const Pass1Result *res, const float *flow, int w, int h, int pov_mode, const double *wytab,
-                              WindowItem *tab, double *psum, Pass2Record *out, hipStream_t st) {
-    const int nblk = (ffl_strip_waves(w, h, P2_STRIP) + 3) / 4;
+void ffl_launch_window_plan(const WindowSeq &seq, int n_seq, int first, int n, int radius, float cut_threshold,
+                            const Pass1Result *res, const float *flow, int w, int h, WindowItem *tab, Pass2Record *out,
+                            hipStream_t st) {
     hipLaunchKernelGGL(k_window_plan, dim3((n + W2_THREADS - 1) / W2_THREADS), dim3(W2_THREADS), 0, st, seq, n_seq, first, n,
                        radius, cut_threshold, (double)w * (double)h, res, flow, (size_t)w * h, tab, out);
-    hipLaunchKernelGGL(k_radial_window, dim3(nblk, n), dim3(P1_THREADS), 0, st, tab, w, h, pov_mode, wytab, psum);
-    hipLaunchKernelGGL(k_radial_window_final, dim3(n), dim3(P1_THREADS), 0, st, tab, w, h, nblk, psum, out);
 }
 
 // ---- flow export -----------------------------------------------------------------------------
@@ -568,7 +551,7 @@ __global__ __launch_bounds__(256) void k_import_convert(const ImportArgs a, cons
 template <int DT, int MODE>
 static void ffl_import_launch(const ImportArgs &a, const ExportTab &tab, int n, int w, int h, int pov_mode, int fused,
                               PairTab *pt, unsigned long long *pkey, double *psum, hipStream_t st) {
-    const int nblk = (ffl_strip_waves(w, h, P1_STRIP) + 3) / 4;
+    const int nblk = ffl_pass1_blocks(w, h);
     if (fused) {
         hipLaunchKernelGGL((k_import_pass1<DT, MODE>), dim3(nblk, n), dim3(P1_THREADS), 0, st, a, tab, w, h, pov_mode, pt,
                            pkey, psum);

@@ -322,7 +322,7 @@ typedef struct ffl_pass2_record {
  *   - a stream that is capturing a graph is refused with FFL_ERR_STATE; that check is the first HIP call made on it;
  *   - the library's stream waits for the batch, import or upload that produced every seq slot and for the work queued on
  *     `stream` before the call (out_dev may still be being read), then writes out_dev with three launches (k_window_plan,
- *     k_radial_window, k_radial_window_final), and `stream` is made to wait for that;
+ *     k_radial, k_radial_final), and `stream` is made to wait for that;
  *   - the call counts as a use of every seq slot, the neighbours whose records alone are read included: a later batch that
  *     recycles one of them waits for it on the device;
  *   - the host never waits for the device, except where settling the library's event ring makes every call wait.

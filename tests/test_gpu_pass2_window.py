@@ -185,6 +185,49 @@ def test_non_finite_fields():
             compare(ctx, [4, 5, 6, 7, 8], 1, 3, 1, 7.0, pov, nan_aware=True)
 
 
+# ---- one scratch set on stream `post` -----------------------------------------------------------------------------------
+def test_shared_post_scratch_between_users():
+    """ffl_upload_flow, ffl_import_flows, ffl_radial and ffl_radial_window share one pass-1 table, one key buffer, one sum
+    buffer and one item table on stream `post`.  At 253x33 pass 1 walks 3 strips x 3 row groups (3 workgroups per item)
+    and the radial pass 2 strips x 3 row groups (2 workgroups per item), so the two index the shared sums differently.
+    The calls follow one another with no host wait between the device-ordered ones; a second context runs the same calls,
+    each followed by sync(), and every record, dot and exported field must be the same bytes."""
+    w, h = 253, 33
+    f = random_fields(7, w, h, 91)
+    pos = [pr.argmax_ref(f[j])[:2] for j in range(4)]
+    cen = pipeline.smooth_centers(pos, 1)                         # the window's centres, without a look at the device
+
+    def run(ctx, wait):
+        done = ctx.sync if wait else (lambda: None)
+        a, b = dev(f[1:4]), dev(f[4:7])
+        out = torch.empty(4 * ITEM, dtype=torch.uint8, device=DEV)
+        ctx.upload_flow(0, f[0]); done()
+        ctx.import_flows(a, [1, 2, 3]); done()
+        ctx.radial_window([0, 1, 2, 3], 0, 4, out, 1); done()
+        ctx.import_flows(b, [4, 5, 6]); done()
+        dots = ctx.radial([0, 1, 2, 3], cen, [False] * 4); done()
+        exported = ctx.export_flows([4, 5, 6]); done()
+        recs = ctx.pass1_results(list(range(7)))
+        assert ctx.graph_stats()["capture_failures"] == 0
+        return {"window": out.cpu().numpy().tobytes(), "dots": np.asarray(dots, np.float64).tobytes(),
+                "exported": exported.cpu().numpy().tobytes(), "pass1": np.asarray(recs, np.float64).tobytes()}
+
+    got = []
+    for wait in (False, True):
+        with _capi.Context(w, h, max_batch=3, frame_slots=2, flow_slots=8) as ctx:
+            got.append(run(ctx, wait))
+    for key in got[0]:
+        assert got[0][key] == got[1][key], key
+    rec = np.frombuffer(got[0]["window"], _capi.PASS2_DTYPE, 4)
+    dots = np.frombuffer(got[0]["dots"], np.float64)
+    assert not rec["cut"].any() and rec["dot"].tobytes() == dots.tobytes()     # the two forms, same slots and centres
+    assert np.stack([rec["cx"], rec["cy"]], axis=1).tobytes() == cen.tobytes()
+    assert got[0]["exported"] == f[4:7].tobytes()
+    for j in range(4):
+        pr.check_radial(float(dots[j]), f[j], tuple(cen[j]), False)
+        pr.check_radial(float(rec["dot"][j]), f[j], tuple(cen[j]), False)
+
+
 # ---- stream contract --------------------------------------------------------------------------------------------------
 def test_stream_sentinel_and_reader(field_ctx):
     """`out` is filled by work queued on the stream before the call and read by work queued after it; no host
