@@ -25,11 +25,15 @@ EXPORTS = ["ffl_device_count", "ffl_create", "ffl_destroy", "ffl_last_error", "f
            "ffl_farneback_default_params", "ffl_farneback_geometry", "ffl_farneback_extra_bytes", "ffl_flow_pairs_farneback",
            "ffl_flow_pairs_farneback_ex",
            "ffl_upload_frames_yuv", "ffl_frontend_yuv_window",
+           "ffl_upload_frames_yuv16", "ffl_frontend_yuv16_window", "ffl_dev_frame_check16", "ffl_upload_frames_device16",
            "ffl_dev_frame_check", "ffl_upload_frames_device", "ffl_export_flows",
            "ffl_dev_flow_check", "ffl_import_flows", "ffl_radial_window"]
 
 # 4:2:0 layouts of ffl_upload_frames_yuv (FFL_YUV_I420, FFL_YUV_NV12): cv2's single-array (3h/2, w) uint8 frames
 YUV_LAYOUTS = {"i420": 0, "nv12": 1}
+# rule Y5: 9- to 16-bit samples in uint16 containers are a keyword of their own, depth=, beside the
+# layout -- "nv12" with depth=10 is P010, "i420" with depth=10 is yuv420p10le
+YUV_DEPTHS = range(8, 17)
 
 # device-memory I/O (ffl_upload_frames_device / ffl_export_flows): FFL_DEV_* and FFL_FLOW_* codes
 DEV_FORMATS = {"gray": 0, "bgr": 1, "rgb": 2, "i420": 3, "nv12": 4}
@@ -217,7 +221,7 @@ def _array_view(obj):
             raise ValueError("not device memory: a CPU tensor (host frames go through upload_frames / upload_frames_raw / "
                              "upload_frames_yuv)")
         es = obj.element_size()
-        ts = {torch.uint8: "|u1", torch.float32: "<f4"}.get(obj.dtype, str(obj.dtype))
+        ts = {torch.uint8: "|u1", torch.uint16: "<u2", torch.float32: "<f4"}.get(obj.dtype, str(obj.dtype))
         return obj.data_ptr(), tuple(obj.shape), tuple(st * es for st in obj.stride()), ts
     try:
         cai = obj.__cuda_array_interface__
@@ -264,11 +268,30 @@ class _DeviceSpan:
                                          "typestr": "|u1"}
 
 
-def _frame_row(obj, code):
-    """the 8 fields of ffl_dev_frame (plane[3], pitch[3], pixel_stride, channel_stride) and (width, height) of one frame"""
+def yuv_depth(depth, layout=None, msb=None):
+    """(depth, msb_aligned) of rule Y5 checked: depth 8 (plain uint8 frames) or 9..16; msb None = where decoders put the
+    bits -- high for "nv12" (P010 / P016), low for "i420" (yuv420p10le).  ValueError for anything else."""
+    if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)) or depth not in YUV_DEPTHS:
+        raise ValueError(f"depth must be 8 (uint8 frames) or 9..16 (uint16 frames), got {depth!r}")
+    if msb is None:
+        msb = layout is not None and (layout == YUV_LAYOUTS["nv12"] or str(layout).lower() == "nv12")
+    return int(depth), int(bool(msb))
+
+
+def _frame_row(obj, code, depth=8):
+    """the 8 fields of ffl_dev_frame (plane[3], pitch[3], pixel_stride, channel_stride) and (width, height) of one frame;
+    depth > 8: a 4:2:0 frame of uint16 samples (typestr "<u2", strides in bytes as everywhere)"""
     ptr, shape, st, ts = _array_view(obj)
-    if ts[1:] != "u1":
+    if depth > 8:
+        if code not in (DEV_FORMATS["i420"], DEV_FORMATS["nv12"]):
+            raise ValueError("depth > 8 applies to 4:2:0 frames (\"i420\", \"nv12\") only")
+        if ts != "<u2":
+            raise ValueError(f"depth={depth} needs uint16 frames (typestr '<u2'), got {ts!r}; uint8 frames are depth=8")
+    elif ts == "<u2":
+        raise ValueError("uint16 frames need their bit depth: pass depth=9..16 (depth=8 means uint8 frames)")
+    elif ts[1:] != "u1":
         raise ValueError(f"device frames must be uint8 (typestr '|u1'), got {ts!r}")
+    es = 2 if depth > 8 else 1
     if code == DEV_FORMATS["gray"]:
         if len(shape) != 2:
             raise ValueError(f"a gray frame is (h, w), got shape {shape}")
@@ -281,33 +304,37 @@ def _frame_row(obj, code):
         raise ValueError(f"a 3-channel frame is (h, w, 3|4) or (3, h, w), got shape {shape}")
     if len(shape) != 2 or shape[0] % 3:
         raise ValueError(f"a 4:2:0 frame is one (3h/2, w) array, got shape {shape}")
-    if st[1] != 1:
-        raise ValueError(f"4:2:0 rows must be contiguous (column stride 1), got {st[1]}")
+    if st[1] != es:
+        raise ValueError(f"4:2:0 rows must be contiguous (column stride {es}), got {st[1]}")
     w, h, pitch = shape[1], shape[0] * 2 // 3, st[0]
     if code == DEV_FORMATS["nv12"]:
         return (ptr, ptr + h * pitch, 0, pitch, pitch, 0, 1, 0), (w, h)
-    if pitch != w:
+    if pitch != w * es:
         raise ValueError(f"I420 needs contiguous rows (row pitch == width), got pitch {pitch} for width {w}")
-    u = ptr + h * w
-    return (ptr, u, u + (h // 2) * (w // 2), w, w // 2, w // 2, 1, 0), (w, h)
+    u, cw = ptr + h * pitch, w // 2 * es
+    return (ptr, u, u + (h // 2) * cw, pitch, cw, cw, 1, 0), (w, h)
 
 
-def device_frame(obj, fmt):
+def device_frame(obj, fmt, depth=8):
     """DevFrame (ffl_dev_frame + .width, .height) of a device array: any object with __cuda_array_interface__ (v2 / v3,
     typestr "|u1", byte strides) -- torch tensors included -- or a GPU DLPack producer.  fmt "gray": (h, w); "bgr" / "rgb":
     (h, w, 3) or (h, w, 4) packed, or (3, h, w) planar, any strides; "i420" / "nv12": cv2's single (3h/2, w) array (an
-    NV12 row pitch may exceed w).  ValueError names what is refused."""
-    row, (w, h) = _frame_row(obj, dev_format(fmt))
+    NV12 row pitch may exceed w), with depth=9..16 of uint16 samples (typestr "<u2", torch.uint16).  ValueError names what
+    is refused."""
+    row, (w, h) = _frame_row(obj, dev_format(fmt), yuv_depth(depth)[0])
     f = DevFrame((C.c_void_p * 3)(*row[:3]), (C.c_ssize_t * 3)(*row[3:6]), row[6], row[7])
     f.width, f.height = w, h
     return f
 
 
-def dev_frame_check(fmt, frame, resize, crop, out_size):
-    """ffl_dev_frame_check for a DevFrame: ValueError with the library's rule when it refuses (pure host check)."""
+def dev_frame_check(fmt, frame, resize, crop, out_size, depth=8):
+    """ffl_dev_frame_check (depth > 8: ffl_dev_frame_check16) for a DevFrame: ValueError with the library's rule when it
+    refuses (pure host check)."""
     L = load()
-    if L.ffl_dev_frame_check(dev_format(fmt), frame.width, frame.height, C.byref(frame), int(resize[0]), int(resize[1]),
-                             int(crop[0]), int(crop[1]), int(out_size[0]), int(out_size[1])) != FFL_OK:
+    geom = (frame.width, frame.height, C.byref(frame), int(resize[0]), int(resize[1]), int(crop[0]), int(crop[1]),
+            int(out_size[0]), int(out_size[1]))
+    rc = L.ffl_dev_frame_check(dev_format(fmt), *geom) if depth == 8 else L.ffl_dev_frame_check16(dev_format(fmt), int(depth), *geom)
+    if rc != FFL_OK:
         raise ValueError(L.ffl_last_error(None).decode())
 
 
@@ -386,18 +413,22 @@ def yuv_layout(layout):
     raise ValueError(f"YUV layout must be one of {sorted(YUV_LAYOUTS)}, got {layout!r}")
 
 
-def frontend_yuv_window(src_size, layout, resize, crop, out_size, stride=None):
+def frontend_yuv_window(src_size, layout, resize, crop, out_size, stride=None, depth=8):
     """((x, y, w, h), bytes per frame) of the source rectangle ffl_upload_frames_yuv transfers for a src_size = (w, h)
     4:2:0 frame, resized to `resize` = (w, h) and cropped at `crop` = (x, y) to out_size = (w, h).
-    ValueError with the library's reason for what it refuses.  stride defaults to the source width; an int layout is
-    passed to the library as it is."""
+    ValueError with the library's reason for what it refuses.  stride (bytes) defaults to a packed row; an int layout is
+    passed to the library as it is.  depth != 8: ffl_frontend_yuv16_window for uint16 samples, to which the depth goes
+    as it is -- the same rectangle in samples, twice the bytes."""
     sw, sh = int(src_size[0]), int(src_size[1])
     win, b = (C.c_int * 4)(), C.c_size_t()
     L = load()
     code = layout if isinstance(layout, int) else yuv_layout(layout)
-    if L.ffl_frontend_yuv_window(sw, sh, code, int(sw if stride is None else stride), int(resize[0]),
-                                 int(resize[1]), int(crop[0]), int(crop[1]), int(out_size[0]), int(out_size[1]), win,
-                                 C.byref(b)) != FFL_OK:
+    geom = (int(resize[0]), int(resize[1]), int(crop[0]), int(crop[1]), int(out_size[0]), int(out_size[1]), win, C.byref(b))
+    if depth == 8:
+        rc = L.ffl_frontend_yuv_window(sw, sh, code, int(sw if stride is None else stride), *geom)
+    else:
+        rc = L.ffl_frontend_yuv16_window(sw, sh, code, int(2 * sw if stride is None else stride), int(depth), *geom)
+    if rc != FFL_OK:
         raise ValueError(L.ffl_last_error(None).decode())
     return tuple(win), b.value
 
@@ -428,6 +459,8 @@ def load():
     L.ffl_upload_frames_yuv.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.c_ssize_t, C.c_int,
                                         C.c_int, C.c_int, C.c_int, C.c_int]
     L.ffl_frontend_yuv_window.argtypes = [C.c_int, C.c_int, C.c_int, C.c_ssize_t] + [C.c_int] * 6 + [ip, C.POINTER(C.c_size_t)]
+    L.ffl_upload_frames_yuv16.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.c_ssize_t] + [C.c_int] * 7
+    L.ffl_frontend_yuv16_window.argtypes = [C.c_int, C.c_int, C.c_int, C.c_ssize_t] + [C.c_int] * 7 + [ip, C.POINTER(C.c_size_t)]
     L.ffl_flow_pairs.argtypes = [vp, C.c_int, ip, ip, ip, C.c_int]
     L.ffl_pass1_result.argtypes = [vp, C.c_int, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                    C.POINTER(C.c_float), C.POINTER(C.c_float), ip]
@@ -467,6 +500,8 @@ def load():
     L.ffl_flow_pairs_farneback_ex.argtypes = [vp, C.c_int, ip, ip, ip, C.c_int, fp_, C.c_uint]
     L.ffl_dev_frame_check.argtypes = [C.c_int, C.c_int, C.c_int, vp] + [C.c_int] * 6
     L.ffl_upload_frames_device.argtypes = [vp, C.c_int, C.c_int, vp] + [C.c_int] * 7 + [C.c_uint64]
+    L.ffl_dev_frame_check16.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp] + [C.c_int] * 6
+    L.ffl_upload_frames_device16.argtypes = [vp, C.c_int, C.c_int, vp] + [C.c_int] * 9 + [C.c_uint64]
     L.ffl_export_flows.argtypes = [vp, C.c_int, ip, vp, C.c_int, C.c_ssize_t, C.c_uint64]
     L.ffl_dev_flow_check.argtypes = [C.c_int] * 4 + [vp]
     L.ffl_import_flows.argtypes = [vp, C.c_int, ip, vp, C.c_int, C.c_int, C.c_uint64]
@@ -599,20 +634,25 @@ class Context:
         self._chk(self.L.ffl_upload_frames(self._h, first_slot, len(fr), ptrs, f0.shape[1], f0.shape[0], ch,
                                            f0.strides[0]))
 
-    def pinned_frames(self, n, channels=1, size=None, yuv=False):
+    def pinned_frames(self, n, channels=1, size=None, yuv=False, depth=8):
         """(n, height, width[, 3]) uint8 array in page-locked memory of this context (ffl_host_alloc): frames a
         decoder writes into consecutive entries go to the device without the staging copy.  Do not overwrite an
         entry before the batch that uses it has returned results (or ctx.sync()).  `size=(w, h)`: decoded source
         frames of another size, for upload_frames_raw.  yuv=True: (n, 3h/2, w) 4:2:0 frames for upload_frames_yuv
-        (channels is ignored).  The memory belongs to the context: the array (and every view of it) must not be
-        touched after ctx.close()."""
+        (channels is ignored), uint16 ones with depth=9..16.  The memory belongs to the context: the array (and every
+        view of it) must not be touched after ctx.close()."""
         w, h = size if size is not None else (self.width, self.height)
         shape = (n, h * 3 // 2, w) if yuv else (n, h, w) + ((channels,) if channels != 1 else ())
-        nbytes = int(np.prod(shape))
+        dtype = np.uint8
+        if depth != 8:
+            if not yuv:
+                raise FFLError("pinned_frames: depth applies to 4:2:0 frames (yuv=True)")
+            dtype = np.uint16 if yuv_depth(depth)[0] > 8 else np.uint8
+        nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
         p = C.c_void_p()
         self._chk(self.L.ffl_host_alloc(self._h, nbytes, C.byref(p)))
         buf = (C.c_uint8 * nbytes).from_address(p.value)
-        return np.frombuffer(buf, np.uint8).reshape(shape)
+        return np.frombuffer(buf, dtype).reshape(shape)
 
     def upload_frames_raw(self, first_slot, frames, resize, crop=(0, 0), rgb_order=False):
         """Decoded (h, w, 3) uint8 frames -> gray(resize(frame, resize)[crop window]) in consecutive slots
@@ -627,39 +667,55 @@ class Context:
                                                f0.strides[0], int(bool(rgb_order)), int(resize[0]), int(resize[1]),
                                                int(crop[0]), int(crop[1])))
 
-    def upload_frames_yuv(self, first_slot, frames, layout, resize, crop=(0, 0)):
+    def upload_frames_yuv(self, first_slot, frames, layout, resize, crop=(0, 0), depth=8, msb=None):
         """Decoded 4:2:0 frames -- (3h/2, w) uint8 arrays, cv2's single-array I420 / NV12 layout, layout "i420" or "nv12"
         -- -> gray(resize(YUV2BGR(frame), resize)[crop window]) in consecutive slots.  Only the
-        source rectangle the window reads is transferred.  Rows must be contiguous (an NV12 row pitch may exceed w)."""
+        source rectangle the window reads is transferred.  Rows must be contiguous (an NV12 row pitch may exceed w).
+        depth=9..16: uint16 frames (yuv420p10le, P010, ...; ffl_upload_frames_yuv16), each sample reduced to 8 bits by
+        rule Y5; msb: whether the bits sit high in the 16 (None: high for "nv12", low for "i420")."""
         code = yuv_layout(layout)
-        fr = [f if (f.ndim == 2 and f.strides[1] == 1) else np.ascontiguousarray(f) for f in frames]
+        depth, msb = yuv_depth(depth, code, msb)
+        dt, es = (np.uint16, 2) if depth > 8 else (np.uint8, 1)
+        fr = [f if (f.ndim == 2 and f.strides[1] == f.itemsize) else np.ascontiguousarray(f) for f in frames]
         f0 = fr[0]
-        if any(f.dtype != np.uint8 or f.ndim != 2 or f.shape != f0.shape or f.strides[0] != f0.strides[0] for f in fr):
-            raise FFLError("upload_frames_yuv needs (3h/2, w) uint8 frames of one shape and row stride")
+        if any(f.dtype == np.uint8 for f in fr) and depth > 8:
+            raise FFLError(f"upload_frames_yuv: depth={depth} needs uint16 frames, got uint8 (uint8 frames are depth=8)")
+        if any(f.dtype == np.uint16 for f in fr) and depth == 8:
+            raise FFLError("upload_frames_yuv: uint16 frames need their bit depth: pass depth=9..16 (depth=8 means uint8 frames)")
+        if any(f.dtype != dt or f.ndim != 2 or f.shape != f0.shape or f.strides[0] != f0.strides[0] for f in fr):
+            raise FFLError(f"upload_frames_yuv needs (3h/2, w) {np.dtype(dt).name} frames of one shape and row stride")
         if f0.shape[0] % 3:
             raise FFLError(f"upload_frames_yuv: a 4:2:0 frame has 3h/2 rows, got {f0.shape[0]}")
         ptrs = (C.c_void_p * len(fr))(*[f.ctypes.data for f in fr])
-        self._chk(self.L.ffl_upload_frames_yuv(self._h, first_slot, len(fr), ptrs, f0.shape[1], f0.shape[0] * 2 // 3,
-                                               f0.strides[0], code, int(resize[0]), int(resize[1]), int(crop[0]),
-                                               int(crop[1])))
+        head = (self._h, first_slot, len(fr), ptrs, f0.shape[1], f0.shape[0] * 2 // 3, f0.strides[0], code)
+        geom = (int(resize[0]), int(resize[1]), int(crop[0]), int(crop[1]))
+        if es == 2:
+            self._chk(self.L.ffl_upload_frames_yuv16(*head, depth, msb, *geom))
+        else:
+            self._chk(self.L.ffl_upload_frames_yuv(*head, *geom))
 
-    def upload_frames_device(self, first_slot, frames, fmt, resize=None, crop=(0, 0), stream=None):
+    def upload_frames_device(self, first_slot, frames, fmt, resize=None, crop=(0, 0), stream=None, depth=8, msb=None):
         """Device-resident frames -> gray(resize(frame, resize)[crop window]) in consecutive slots without a host round
         trip (ffl_upload_frames_device): the bytes upload_frames_raw / upload_frames_yuv /
         upload_frames give for the same pixels.  `frames`: a sequence of device arrays (see device_frame) or one array with
         a leading frame axis, all of one size; fmt one of DEV_FORMATS; resize None = the source size.  The frames are read
         after the work queued on `stream` (stream_handle) and `stream` waits for the read: the caller may overwrite or free
-        them in its order on that stream, with no host synchronisation."""
+        them in its order on that stream, with no host synchronisation.  depth=9..16, msb: "i420" / "nv12" frames of
+        uint16 samples (torch.uint16, typestr "<u2"; ffl_upload_frames_device16), as upload_frames_yuv takes them."""
         code = dev_format(fmt)
-        rows, size = self._device_rows(frames, code)
+        depth, msb = yuv_depth(depth, fmt, msb)
+        rows, size = self._device_rows(frames, code, depth)
         descs = np.ascontiguousarray(rows, np.int64)
         rw, rh = (size if resize is None else resize)
-        self._chk(self.L.ffl_upload_frames_device(self._h, int(first_slot), len(descs), descs.ctypes.data, code, size[0], size[1],
-                                                  int(rw), int(rh), int(crop[0]), int(crop[1]),
-                                                  stream_handle(stream, self.device)))
+        head = (self._h, int(first_slot), len(descs), descs.ctypes.data, code)
+        geom = (size[0], size[1], int(rw), int(rh), int(crop[0]), int(crop[1]), stream_handle(stream, self.device))
+        if depth > 8:
+            self._chk(self.L.ffl_upload_frames_device16(*head, depth, msb, *geom))
+        else:
+            self._chk(self.L.ffl_upload_frames_device(*head, *geom))
 
     @staticmethod
-    def _device_rows(frames, code):
+    def _device_rows(frames, code, depth=8):
         """ffl_dev_frame rows of a frame sequence or of one batched array, and the common (width, height)"""
         nd = 3 if code in (DEV_FORMATS["bgr"], DEV_FORMATS["rgb"]) else 2
         view = None
@@ -672,7 +728,7 @@ class Context:
             ptr, shp, st, ts = view
             class _One:   # frame 0's view; the others are offsets of it
                 __cuda_array_interface__ = {"version": 2, "data": (ptr, False), "shape": shp[1:], "strides": st[1:], "typestr": ts}
-            row, size = _frame_row(_One(), code)
+            row, size = _frame_row(_One(), code, depth)
             rows = np.tile(np.asarray(row, np.int64), (shp[0], 1))
             for k in range(3):
                 if row[k]:
@@ -680,7 +736,7 @@ class Context:
             return rows, size
         rows, size = [], None
         for f in frames:
-            row, sz = _frame_row(f, code)
+            row, sz = _frame_row(f, code, depth)
             if size is not None and sz != size:
                 raise ValueError(f"upload_frames_device needs frames of one size, got {size} and {sz}")
             rows.append(row)

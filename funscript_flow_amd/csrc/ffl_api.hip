@@ -732,6 +732,7 @@ static int front_geometry(ffl_ctx *c, const char *fn, int sw, int sh, int rw, in
     p->scale_x = 1. / ((double)rw / sw);
     p->scale_y = 1. / ((double)rh / sh);
     p->mode = (rw == sw && rh == sh) ? FFL_FRONT_IDENTITY : (sw == 2 * rw && sh == 2 * rh) ? FFL_FRONT_AREA2 : FFL_FRONT_GENERIC;
+    p->shift16 = p->round16 = 0;  // front_depth() sets them for 16-bit sources
     return FFL_OK;
 }
 
@@ -1179,19 +1180,33 @@ static void yuv_span(int d0, int d1, int s, double scale, int mode, int align, i
     *hi_excl = std::min((b + align - 1) / align * align, s);  // s is even
 }
 
+// Rule Y5 (appendix Y) as the kernels apply it: s = msb ? raw >> (16 - depth) : raw; v8 = min(255, (s + (1 << (depth - 9)))
+// >> (depth - 8)).  The alignment's shift folds into the rounding one exactly -- floor((floor(raw / A) + r) / B) =
+// floor((raw + r * A) / (A * B)) -- so high-aligned samples of every depth are (raw + 128) >> 8.
+static void front_depth(FrontParams *p, int depth, int msb) {
+    p->shift16 = msb ? 8 : depth - 8;
+    p->round16 = 1 << (p->shift16 - 1);
+}
+
 // Every refusal of the YUV path (messages name the rule); fn prefixes the message.  Fills the geometry of *fp and the
-// window.
-static int yuv_window(ffl_ctx *c, const char *fn, int sw, int sh, int layout, ptrdiff_t stride, int rw, int rh, int crop_x,
-                      int crop_y, int ow, int oh, FrontParams *fp, YuvWin *out) {
+// window.  es: bytes per sample (1; 2: the 16-bit frames of rule Y5, whose depth is checked here too); the stride is in
+// bytes, the window in samples.
+static int yuv_window(ffl_ctx *c, const char *fn, int sw, int sh, int layout, ptrdiff_t stride, int es, int depth, int rw, int rh,
+                      int crop_x, int crop_y, int ow, int oh, FrontParams *fp, YuvWin *out) {
+    const char *twice = es == 2 ? "2 * " : "";
+    if (es == 2 && (depth < 9 || depth > 16))
+        return set_err(c, FFL_ERR_INVALID, "%s: depth %d outside 9..16 (8-bit frames go through ffl_upload_frames_yuv)", fn, depth);
     if ((sw & 1) || (sh & 1))
         return set_err(c, FFL_ERR_INVALID, "%s: 4:2:0 needs an even width and height, source is %dx%d", fn, sw, sh);
     if (layout != FFL_YUV_I420 && layout != FFL_YUV_NV12)
         return set_err(c, FFL_ERR_INVALID, "%s: unknown layout %d (FFL_YUV_I420 0, FFL_YUV_NV12 1)", fn, layout);
-    if (layout == FFL_YUV_I420 && stride != (ptrdiff_t)sw)
-        return set_err(c, FFL_ERR_INVALID, "%s: I420 needs stride == width (contiguous U and V planes), got %td for width %d",
-                       fn, stride, sw);
-    if (layout == FFL_YUV_NV12 && stride < (ptrdiff_t)sw)
-        return set_err(c, FFL_ERR_INVALID, "%s: NV12 needs stride >= width, got %td for width %d", fn, stride, sw);
+    if (es == 2 && (stride & 1))
+        return set_err(c, FFL_ERR_INVALID, "%s: odd stride %td: rows of 16-bit samples start 2-byte aligned", fn, stride);
+    if (layout == FFL_YUV_I420 && stride != (ptrdiff_t)sw * es)
+        return set_err(c, FFL_ERR_INVALID, "%s: I420 needs stride == %swidth (contiguous U and V planes), got %td for width %d",
+                       fn, twice, stride, sw);
+    if (layout == FFL_YUV_NV12 && stride < (ptrdiff_t)sw * es)
+        return set_err(c, FFL_ERR_INVALID, "%s: NV12 needs stride >= %swidth, got %td for width %d", fn, twice, stride, sw);
     if (int rc = front_geometry(c, fn, sw, sh, rw, rh, crop_x, crop_y, ow, oh, fp)) return rc;
     int x1, y1;
     yuv_span(crop_x, crop_x + ow - 1, sw, fp->scale_x, fp->mode, 16, &out->x0, &x1);
@@ -1201,40 +1216,55 @@ static int yuv_window(ffl_ctx *c, const char *fn, int sw, int sh, int layout, pt
     return FFL_OK;
 }
 
-int ffl_frontend_yuv_window(int src_w, int src_h, int layout, ptrdiff_t stride_bytes, int resize_w, int resize_h, int crop_x,
-                            int crop_y, int out_w, int out_h, int win[4], size_t *bytes) {
+static int frontend_window(const char *fn, int src_w, int src_h, int layout, ptrdiff_t stride_bytes, int es, int depth, int resize_w,
+                           int resize_h, int crop_x, int crop_y, int out_w, int out_h, int win[4], size_t *bytes) {
     FrontParams fp;
     YuvWin yw;
-    if (int rc = yuv_window(nullptr, "ffl_frontend_yuv_window", src_w, src_h, layout, stride_bytes, resize_w, resize_h, crop_x,
-                            crop_y, out_w, out_h, &fp, &yw))
+    if (int rc = yuv_window(nullptr, fn, src_w, src_h, layout, stride_bytes, es, depth, resize_w, resize_h, crop_x, crop_y, out_w,
+                            out_h, &fp, &yw))
         return rc;
     if (win) {
         win[0] = yw.x0; win[1] = yw.y0; win[2] = yw.w; win[3] = yw.h;
     }
-    if (bytes) *bytes = (size_t)yw.w * yw.h * 3 / 2;
+    if (bytes) *bytes = (size_t)yw.w * yw.h * 3 / 2 * es;
     return FFL_OK;
 }
 
-// Decoded 4:2:0 frames -> gray frame slots through k_frontend.  Frame by frame, as ffl_upload_frames_raw: only the
-// window the crop samples travels -- out of ffl_host_alloc memory one 2-D copy per plane (when every plane's rows start
-// 4-byte aligned and are a multiple of 4 bytes long: unaligned ones take a slow path in the runtime's copy), otherwise
-// copied into the pinned ring buffer and sent as one transfer.  On the device the window is packed: Y (w x h), then U and V (w/2 x h/2 each,
-// I420) or the interleaved UV rows (w x h/2, NV12).
-int ffl_upload_frames_yuv(ffl_ctx *c, int first, int n, const uint8_t *const *frames, int sw, int sh, ptrdiff_t stride_bytes,
-                          int layout, int rw, int rh, int crop_x, int crop_y) {
-    static const char *fn = "ffl_upload_frames_yuv";
+int ffl_frontend_yuv_window(int src_w, int src_h, int layout, ptrdiff_t stride_bytes, int resize_w, int resize_h, int crop_x,
+                            int crop_y, int out_w, int out_h, int win[4], size_t *bytes) {
+    return frontend_window("ffl_frontend_yuv_window", src_w, src_h, layout, stride_bytes, 1, 8, resize_w, resize_h, crop_x, crop_y,
+                           out_w, out_h, win, bytes);
+}
+
+int ffl_frontend_yuv16_window(int src_w, int src_h, int layout, ptrdiff_t stride_bytes, int depth, int resize_w, int resize_h,
+                              int crop_x, int crop_y, int out_w, int out_h, int win[4], size_t *bytes) {
+    return frontend_window("ffl_frontend_yuv16_window", src_w, src_h, layout, stride_bytes, 2, depth, resize_w, resize_h, crop_x,
+                           crop_y, out_w, out_h, win, bytes);
+}
+
+// Decoded 4:2:0 frames -> gray frame slots through k_frontend: the body of ffl_upload_frames_yuv (es = 1) and
+// ffl_upload_frames_yuv16 (es = 2 bytes per sample, reduced by rule Y5).  Frame by frame, as ffl_upload_frames_raw: only
+// the window the crop samples travels -- out of ffl_host_alloc memory one 2-D copy per plane (when every plane's rows
+// start 4-byte aligned and are a multiple of 4 bytes long: unaligned ones take a slow path in the runtime's copy),
+// otherwise copied into the pinned ring buffer and sent as one transfer.  On the device the window is packed: Y (w x h),
+// then U and V (w/2 x h/2 each, I420) or the interleaved UV rows (w x h/2, NV12), es bytes per sample.
+static int upload_yuv(ffl_ctx *c, const char *fn, int first, int n, const uint8_t *const *frames, int sw, int sh,
+                      ptrdiff_t stride_bytes, int layout, int es, int depth, int msb, int rw, int rh, int crop_x, int crop_y) {
     if (!c) return FFL_ERR_INVALID;
     std::unique_lock<std::mutex> ul(c->up_mu);
     CtxLock lk(c->mu);
     if (int rc = check_frame_run(c, fn, first, n, frames, frames)) return rc;
     FrontParams fp;
     YuvWin yw;
-    if (int rc = yuv_window(c, fn, sw, sh, layout, stride_bytes, rw, rh, crop_x, crop_y, c->w, c->h, &fp, &yw)) return rc;
+    if (int rc = yuv_window(c, fn, sw, sh, layout, stride_bytes, es, depth, rw, rh, crop_x, crop_y, c->w, c->h, &fp, &yw)) return rc;
+    for (int i = 0; es == 2 && i < n; i++)
+        if ((uintptr_t)frames[i] & 1) return set_err(c, FFL_ERR_INVALID, "%s: frame %d is not 2-byte aligned", fn, i);
     HIPCHK(c, hipSetDevice(c->device));
-    fp.kind = FFL_SRC_YUV;
+    fp.kind = es == 2 ? FFL_SRC_YUV16 : FFL_SRC_YUV;
     fp.rgb = 0;
+    if (es == 2) front_depth(&fp, depth, msb);
     const bool nv12 = layout == FFL_YUV_NV12;
-    const size_t ybytes = (size_t)yw.w * yw.h, fbytes = ybytes * 3 / 2;
+    const size_t ybytes = (size_t)yw.w * yw.h * es, fbytes = ybytes * 3 / 2;
     // the planes of the window: source offset and pitch inside the frame, row bytes, rows, offset in the packed window
     struct Plane {
         size_t src, dst;
@@ -1242,18 +1272,19 @@ int ffl_upload_frames_yuv(ffl_ctx *c, int first, int n, const uint8_t *const *fr
         size_t row;
         int rows;
     } pl[3];
-    const size_t cw = (size_t)sw / 2, ch = (size_t)sh / 2;
-    pl[0] = {(size_t)yw.y0 * stride_bytes + yw.x0, 0, stride_bytes, (size_t)yw.w, yw.h};
+    const size_t cw = (size_t)sw / 2 * es, ch = (size_t)sh / 2;  // a chroma plane's row bytes (I420) and rows
+    const size_t wrow = (size_t)yw.w * es, x0 = (size_t)yw.x0 * es;
+    pl[0] = {(size_t)yw.y0 * stride_bytes + x0, 0, stride_bytes, wrow, yw.h};
     int np = 3;
     if (nv12) {
-        pl[1] = {(size_t)(sh + yw.y0 / 2) * stride_bytes + yw.x0, ybytes, stride_bytes, (size_t)yw.w, yw.h / 2};
+        pl[1] = {(size_t)(sh + yw.y0 / 2) * stride_bytes + x0, ybytes, stride_bytes, wrow, yw.h / 2};
         np = 2;
     } else {
-        const size_t u0 = (size_t)sh * sw + (size_t)(yw.y0 / 2) * cw + yw.x0 / 2;
-        pl[1] = {u0, ybytes, (ptrdiff_t)cw, (size_t)yw.w / 2, yw.h / 2};
-        pl[2] = {u0 + ch * cw, ybytes + ybytes / 4, (ptrdiff_t)cw, (size_t)yw.w / 2, yw.h / 2};
+        const size_t u0 = (size_t)sh * sw * es + (size_t)(yw.y0 / 2) * cw + x0 / 2;
+        pl[1] = {u0, ybytes, (ptrdiff_t)cw, wrow / 2, yw.h / 2};
+        pl[2] = {u0 + ch * cw, ybytes + ybytes / 4, (ptrdiff_t)cw, wrow / 2, yw.h / 2};
     }
-    const size_t span = (size_t)stride_bytes * (sh + sh / 2 - 1) + sw;  // bytes of one frame array
+    const size_t span = (size_t)stride_bytes * (sh + sh / 2 - 1) + (size_t)sw * es;  // bytes of one frame array
     auto direct = [&](int i) {
         bool ok = in_host_buf(c, frames[i], span);
         for (int k = 0; ok && k < np; k++) ok = ((uintptr_t)(frames[i] + pl[k].src) | (size_t)pl[k].pitch | pl[k].row) % 4 == 0;
@@ -1276,15 +1307,26 @@ int ffl_upload_frames_yuv(ffl_ctx *c, int first, int n, const uint8_t *const *fr
         FrameDesc s = {};
         s.p0 = d;
         s.p1 = d + ybytes;
-        s.p2 = nv12 ? s.p1 + 1 : s.p1 + ybytes / 4;
-        s.pitch0 = yw.w;
-        s.pitch1 = s.pitch2 = nv12 ? yw.w : yw.w / 2;
-        s.c_step = nv12 ? 2 : 1;
+        s.p2 = nv12 ? s.p1 + es : s.p1 + ybytes / 4;
+        s.pitch0 = wrow;
+        s.pitch1 = s.pitch2 = nv12 ? wrow : wrow / 2;
+        s.c_step = (nv12 ? 2 : 1) * es;
         s.wx = yw.x0;
         s.wy = yw.y0;
         return s;
     };
     return upload_staged(c, lk, first, n, fbytes, fp, direct, stage, send_direct, desc);
+}
+
+int ffl_upload_frames_yuv(ffl_ctx *c, int first, int n, const uint8_t *const *frames, int sw, int sh, ptrdiff_t stride_bytes,
+                          int layout, int rw, int rh, int crop_x, int crop_y) {
+    return upload_yuv(c, "ffl_upload_frames_yuv", first, n, frames, sw, sh, stride_bytes, layout, 1, 8, 0, rw, rh, crop_x, crop_y);
+}
+
+int ffl_upload_frames_yuv16(ffl_ctx *c, int first, int n, const uint16_t *const *frames, int sw, int sh, ptrdiff_t stride_bytes,
+                            int layout, int depth, int msb_aligned, int rw, int rh, int crop_x, int crop_y) {
+    return upload_yuv(c, "ffl_upload_frames_yuv16", first, n, (const uint8_t *const *)frames, sw, sh, stride_bytes, layout, 2,
+                      depth, msb_aligned != 0, rw, rh, crop_x, crop_y);
 }
 
 int ffl_upload_frame(ffl_ctx *c, int fslot, const uint8_t *data, int width, int height, int channels,
@@ -2024,14 +2066,20 @@ int ffl_download_flow(ffl_ctx *c, int slot, float *dst) {
 }
 
 // ---- device-memory I/O -------------------------------------------------------------------------
-// Every geometry rule of a device frame (ffl.h, ffl_dev_frame_check); fn and frame index prefix the message.  Fills the
-// geometry of *p.
-static int dev_frame_check(ffl_ctx *c, const char *fn, int idx, int fmt, int sw, int sh, const ffl_dev_frame *f, int rw, int rh,
-                           int cx, int cy, int ow, int oh, FrontParams *p) {
+// Every geometry rule of a device frame (ffl.h, ffl_dev_frame_check / ffl_dev_frame_check16); fn and frame index prefix the
+// message.  Fills the geometry of *p.  es: bytes per sample (2: the 16-bit 4:2:0 frames of rule Y5, whose depth is checked
+// here too).
+static int dev_frame_check(ffl_ctx *c, const char *fn, int idx, int fmt, int es, int depth, int sw, int sh, const ffl_dev_frame *f,
+                           int rw, int rh, int cx, int cy, int ow, int oh, FrontParams *p) {
     if (!f) return set_err(c, FFL_ERR_INVALID, "%s: frame %d: NULL descriptor", fn, idx);
     if (fmt < FFL_DEV_GRAY || fmt > FFL_DEV_NV12)
         return set_err(c, FFL_ERR_INVALID, "%s: unknown format %d (FFL_DEV_GRAY 0, BGR 1, RGB 2, I420 3, NV12 4)", fn, fmt);
     const bool yuv = fmt == FFL_DEV_I420 || fmt == FFL_DEV_NV12;
+    if (es == 2 && !yuv)
+        return set_err(c, FFL_ERR_INVALID, "%s: 16-bit frames are 4:2:0 only: format %d is neither FFL_DEV_I420 3 nor FFL_DEV_NV12 4",
+                       fn, fmt);
+    if (es == 2 && (depth < 9 || depth > 16))
+        return set_err(c, FFL_ERR_INVALID, "%s: depth %d outside 9..16 (8-bit frames go through ffl_upload_frames_device)", fn, depth);
     if (fmt == FFL_DEV_GRAY && (rw != sw || rh != sh))
         return set_err(c, FFL_ERR_INVALID, "%s: gray frames are copied as they are: a resize (%dx%d -> %dx%d) is refused", fn, sw, sh,
                        rw, rh);
@@ -2046,9 +2094,15 @@ static int dev_frame_check(ffl_ctx *c, const char *fn, int idx, int fmt, int sw,
         return set_err(c, FFL_ERR_INVALID, "%s: frame %d: a plane the format reads is NULL", fn, idx);
     if (yuv) {
         const ptrdiff_t p1 = f->pitch[1], p2 = fmt == FFL_DEV_I420 ? f->pitch[2] : p1;
-        const ptrdiff_t cmin = fmt == FFL_DEV_I420 ? sw / 2 : sw;
+        const ptrdiff_t cmin = (fmt == FFL_DEV_I420 ? sw / 2 : sw) * es;
         if (p0 < 0 || p1 < 0 || p2 < 0) return set_err(c, FFL_ERR_INVALID, "%s: frame %d: negative stride", fn, idx);
-        if (p0 < sw || p0 > big) return set_err(c, FFL_ERR_INVALID, "%s: frame %d: Y pitch %td too small for a row of %d pixels", fn, idx, p0, sw);
+        if (es == 2 && ((p0 | p1 | p2) & 1))
+            return set_err(c, FFL_ERR_INVALID, "%s: frame %d: odd pitch %td / %td / %td: rows of 16-bit samples start 2-byte aligned", fn,
+                           idx, p0, p1, p2);
+        if (es == 2 && (((uintptr_t)f->plane[0] | (uintptr_t)f->plane[1] | (fmt == FFL_DEV_I420 ? (uintptr_t)f->plane[2] : 0)) & 1))
+            return set_err(c, FFL_ERR_INVALID, "%s: frame %d: a plane of 16-bit samples is not 2-byte aligned", fn, idx);
+        if (p0 < (ptrdiff_t)sw * es || p0 > big)
+            return set_err(c, FFL_ERR_INVALID, "%s: frame %d: Y pitch %td too small for a row of %d pixels", fn, idx, p0, sw);
         if (p1 < cmin || p2 < cmin || p1 > big || p2 > big)
             return set_err(c, FFL_ERR_INVALID, "%s: frame %d: chroma pitch %td / %td too small for a row of %td bytes", fn, idx, p1, p2, cmin);
         return FFL_OK;
@@ -2078,15 +2132,16 @@ static int dev_frame_check(ffl_ctx *c, const char *fn, int idx, int fmt, int sw,
 }
 
 // bytes of each plane a checked frame spans from plane[k] (0: unused)
-static void dev_frame_extents(int fmt, int sw, int sh, const ffl_dev_frame *f, size_t ext[3]) {
+static void dev_frame_extents(int fmt, int es, int sw, int sh, const ffl_dev_frame *f, size_t ext[3]) {
     ext[0] = ext[1] = ext[2] = 0;
     if (fmt == FFL_DEV_I420 || fmt == FFL_DEV_NV12) {
-        ext[0] = (size_t)(sh - 1) * f->pitch[0] + sw;
+        const size_t row = (size_t)sw * es;  // es: bytes per sample
+        ext[0] = (size_t)(sh - 1) * f->pitch[0] + row;
         if (fmt == FFL_DEV_NV12) {
-            ext[1] = (size_t)(sh / 2 - 1) * f->pitch[1] + sw;
+            ext[1] = (size_t)(sh / 2 - 1) * f->pitch[1] + row;
         } else {
-            ext[1] = (size_t)(sh / 2 - 1) * f->pitch[1] + sw / 2;
-            ext[2] = (size_t)(sh / 2 - 1) * f->pitch[2] + sw / 2;
+            ext[1] = (size_t)(sh / 2 - 1) * f->pitch[1] + row / 2;
+            ext[2] = (size_t)(sh / 2 - 1) * f->pitch[2] + row / 2;
         }
     } else {
         ext[0] = (size_t)(sh - 1) * f->pitch[0] + (size_t)(sw - 1) * f->pixel_stride + 1 +
@@ -2095,7 +2150,8 @@ static void dev_frame_extents(int fmt, int sw, int sh, const ffl_dev_frame *f, s
 }
 
 // [p, p + bytes) must be device memory of the context's device inside one allocation
-static const char *kHostFrames = "host frames go through ffl_upload_frames, ffl_upload_frames_raw or ffl_upload_frames_yuv";
+static const char *kHostFrames = "host frames go through ffl_upload_frames, ffl_upload_frames_raw, ffl_upload_frames_yuv or "
+                                 "ffl_upload_frames_yuv16";
 static int dev_mem_check(ffl_ctx *c, const char *fn, const char *what, const void *p, size_t bytes,
                          const char *host_hint = kHostFrames) {
     hipPointerAttribute_t a;
@@ -2177,29 +2233,35 @@ static int post_end(ffl_ctx *c, hipStream_t cst, int n, const int *slots) {
 
 int ffl_dev_frame_check(int format, int sw, int sh, const ffl_dev_frame *f, int rw, int rh, int cx, int cy, int out_w, int out_h) {
     FrontParams p;
-    return dev_frame_check(nullptr, "ffl_dev_frame_check", 0, format, sw, sh, f, rw, rh, cx, cy, out_w, out_h, &p);
+    return dev_frame_check(nullptr, "ffl_dev_frame_check", 0, format, 1, 8, sw, sh, f, rw, rh, cx, cy, out_w, out_h, &p);
+}
+
+int ffl_dev_frame_check16(int format, int depth, int sw, int sh, const ffl_dev_frame *f, int rw, int rh, int cx, int cy, int out_w,
+                          int out_h) {
+    FrontParams p;
+    return dev_frame_check(nullptr, "ffl_dev_frame_check16", 0, format, 2, depth, sw, sh, f, rw, rh, cx, cy, out_w, out_h, &p);
 }
 
 // Device frames -> gray frame slots through ONE k_frontend_dev launch on stream `copy`, ordered after the caller's queued
-// work and before the caller's later work (the stream contract of ffl.h).  The descriptors travel in the pinned table of
-// the up_ring entry the call records (publish_frames), copied to the device table on the same stream.
-int ffl_upload_frames_device(ffl_ctx *c, int first, int n, const ffl_dev_frame *frames, int fmt, int sw, int sh, int rw, int rh,
-                             int cx, int cy, uint64_t stream) {
-    static const char *fn = "ffl_upload_frames_device";
+// work and before the caller's later work (the stream contract of ffl.h): the body of ffl_upload_frames_device (es = 1)
+// and ffl_upload_frames_device16 (es = 2 bytes per sample, reduced by rule Y5).  The descriptors travel in the pinned
+// table of the up_ring entry the call records (publish_frames), copied to the device table on the same stream.
+static int upload_device(ffl_ctx *c, const char *fn, int first, int n, const ffl_dev_frame *frames, int fmt, int es, int depth,
+                         int msb, int sw, int sh, int rw, int rh, int cx, int cy, uint64_t stream) {
     if (!c) return FFL_ERR_INVALID;
     std::unique_lock<std::mutex> ul(c->up_mu);
     CtxLock lk(c->mu);
     if (int rc = check_frame_run(c, fn, first, n, frames)) return rc;
     FrontParams p;
     for (int i = 0; i < n; i++)
-        if (int rc = dev_frame_check(c, fn, i, fmt, sw, sh, &frames[i], rw, rh, cx, cy, c->w, c->h, &p)) return rc;
+        if (int rc = dev_frame_check(c, fn, i, fmt, es, depth, sw, sh, &frames[i], rw, rh, cx, cy, c->w, c->h, &p)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t cst;
     if (int rc = caller_stream(c, fn, stream, &cst)) return rc;
     static const char *names[3] = {"plane 0", "plane 1", "plane 2"};
     for (int i = 0; i < n; i++) {
         size_t ext[3];
-        dev_frame_extents(fmt, sw, sh, &frames[i], ext);
+        dev_frame_extents(fmt, es, sw, sh, &frames[i], ext);
         for (int k = 0; k < 3; k++)
             if (ext[k])
                 if (int rc = dev_mem_check(c, fn, names[k], frames[i].plane[k], ext[k])) return rc;
@@ -2224,19 +2286,20 @@ int ffl_upload_frames_device(ffl_ctx *c, int first, int n, const ffl_dev_frame *
         d.pitch0 = f.pitch[0];
         d.ps = f.pixel_stride;
         d.cs = f.channel_stride;
-        d.c_step = 1;
+        d.c_step = es;
         if (fmt == FFL_DEV_I420) {
             d.p1 = (const uint8_t *)f.plane[1]; d.pitch1 = f.pitch[1];
             d.p2 = (const uint8_t *)f.plane[2]; d.pitch2 = f.pitch[2];
         } else if (fmt == FFL_DEV_NV12) {
             d.p1 = (const uint8_t *)f.plane[1]; d.pitch1 = f.pitch[1];
-            d.p2 = d.p1 + 1; d.pitch2 = f.pitch[1];
-            d.c_step = 2;
+            d.p2 = d.p1 + es; d.pitch2 = f.pitch[1];
+            d.c_step = 2 * es;
         }
         d.fslot = first + i;
     }
-    p.kind = fmt == FFL_DEV_GRAY ? FFL_SRC_GRAY : yuv ? FFL_SRC_YUV : FFL_SRC_BGR;
+    p.kind = fmt == FFL_DEV_GRAY ? FFL_SRC_GRAY : !yuv ? FFL_SRC_BGR : es == 2 ? FFL_SRC_YUV16 : FFL_SRC_YUV;
     p.rgb = fmt == FFL_DEV_RGB;
+    if (es == 2) front_depth(&p, depth, msb);
     // stream `copy` waits for the producer's queued work and for the batches that still read the slots
     WaitOnce wait_copy(c->s_copy);
     if (int rc = caller_join(c, cst, wait_copy)) return rc;
@@ -2252,6 +2315,17 @@ int ffl_upload_frames_device(ffl_ctx *c, int first, int n, const ffl_dev_frame *
     // the caller's later work (overwriting the sources, the allocator reusing them) runs after the frames have been read
     HIPCHK(c, hipStreamWaitEvent(cst, ev_latest(c->up_ring).get(), 0));
     return FFL_OK;
+}
+
+int ffl_upload_frames_device(ffl_ctx *c, int first, int n, const ffl_dev_frame *frames, int fmt, int sw, int sh, int rw, int rh,
+                             int cx, int cy, uint64_t stream) {
+    return upload_device(c, "ffl_upload_frames_device", first, n, frames, fmt, 1, 8, 0, sw, sh, rw, rh, cx, cy, stream);
+}
+
+int ffl_upload_frames_device16(ffl_ctx *c, int first, int n, const ffl_dev_frame *frames, int fmt, int depth, int msb_aligned,
+                               int sw, int sh, int rw, int rh, int cx, int cy, uint64_t stream) {
+    return upload_device(c, "ffl_upload_frames_device16", first, n, frames, fmt, 2, depth, msb_aligned != 0, sw, sh, rw, rh, cx, cy,
+                         stream);
 }
 
 // Flow slots -> caller device memory on stream `post`, ordered after the batches that produced them and the caller's

@@ -61,12 +61,13 @@ struct Pass1Result {  // written by k_pass1_final, mirrored to pinned host memor
 
 // The input front-end (k_frontend, k_frontend_dev): a decoded frame -> the gray crop window of its (virtual) resize.
 enum { FFL_FRONT_GENERIC = 0, FFL_FRONT_AREA2 = 1, FFL_FRONT_IDENTITY = 2 };
-enum { FFL_SRC_GRAY = 0, FFL_SRC_BGR = 1, FFL_SRC_YUV = 2, FFL_SRC_ANY = -1 };  // ANY: the kernels' own use
+enum { FFL_SRC_GRAY = 0, FFL_SRC_BGR = 1, FFL_SRC_YUV = 2, FFL_SRC_YUV16 = 3, FFL_SRC_ANY = -1 };  // YUV16: 4:2:0 in 16-bit
+                                                                                       // samples; ANY: the kernels' own use
 struct FrameDesc {  // where one source frame's bytes lie on the device
     const uint8_t *p0, *p1, *p2;  // packed / first channel / Y; chroma: U and V (NV12: p2 = p1 + 1)
     long long pitch0, pitch1, pitch2;
     long long ps, cs;             // plane 0: bytes between horizontal neighbours / between the channels of a pixel
-    int c_step;                   // 4:2:0: bytes between horizontally adjacent chroma samples (1 I420, 2 NV12)
+    int c_step;                   // 4:2:0: bytes between horizontally adjacent chroma samples (1 I420, 2 NV12; YUV16: 2, 4)
     int wx, wy;                   // origin of the window the planes hold inside the frame (even; 0, 0: the whole frame)
     int fslot;                    // k_frontend_dev: destination frame slot
 };
@@ -76,6 +77,7 @@ struct FrontParams {  // what the frames of one launch share
     int cx, cy, ow, oh;          // crop origin inside the resized image, output size
     double scale_x, scale_y;     // 1. / ((double)resize / src), formed on the host
     int mode;                    // FFL_FRONT_*
+    int shift16, round16;        // FFL_SRC_YUV16, rule Y5: v8 = min(255, (raw + round16) >> shift16)
 };
 // k_export_flows: the flow slots of one launch (at most FFL_MAXB) travel as a kernel argument
 struct ExportTab {

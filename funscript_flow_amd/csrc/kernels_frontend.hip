@@ -6,10 +6,10 @@
 // OpenCV's 8-bit fixed-point rules (11-bit lerp weights, 15-bit luma weights) -- integer work, so the
 // result is bit-identical to the two-pass CPU restatements in oracle/frontend_oracle.c and tests/yuv_ref.py.
 // The source is described by a FrameDesc: packed or planar BGR / RGB with any row pitch, pixel stride and channel stride,
-// 4:2:0 YUV (I420, NV12), or gray copied as it is.  Both entry points run the one per-pixel body; they differ only in
+// 4:2:0 YUV (I420, NV12) in 8-bit or 9- to 16-bit samples, or gray copied as it is.  Both entry points run the one per-pixel body; they differ only in
 // where the descriptor comes from:
-//   k_frontend      ffl_upload_frames_raw / ffl_upload_frames_yuv: one frame in a staging buffer, descriptor by value
-//   k_frontend_dev  ffl_upload_frames_device: one launch for n frames in caller memory, descriptor tab[blockIdx.z]
+//   k_frontend      ffl_upload_frames_raw / ffl_upload_frames_yuv / _yuv16: one frame in a staging buffer, descriptor by value
+//   k_frontend_dev  ffl_upload_frames_device / _device16: one launch for n frames in caller memory, descriptor tab[blockIdx.z]
 // Roofline: HBM / PCIe -- the kernel touches at most 12 source bytes per output pixel; on the host paths the frame's
 // H2D transfer is what bounds the path.
 #include "ffl_kernels.h"
@@ -23,14 +23,26 @@ __device__ __forceinline__ int ffl_sat_u8(int v) { return min(max(v, 0), 255); }
 
 // The three colour channels of source pixel (sx, sy) in the order the frame stores them (BGR, RGB, or B, G, R out of YUV).
 // (sx, sy) is in full-frame terms; the origin of the window the planes hold is only subtracted at the load.  K is the
-// source kind, or FFL_SRC_ANY: `kind`, tested here.  YUV: BT.601 limited range, OpenCV's 20-bit fixed point, nearest
-// chroma (appendix Y).
+// source kind, or FFL_SRC_ANY: p.kind, tested here.  YUV: BT.601 limited range, OpenCV's 20-bit fixed point, nearest
+// chroma (appendix Y).  YUV16: the same from 16-bit samples, each reduced to 8 bits at its load by rule Y5 -- round half
+// up with saturation; the alignment's own shift is folded into p.shift16 on the host, so one add and one shift do it.
 template <int K>
-__device__ __forceinline__ void ffl_front_fetch(const FrameDesc &d, int kind, int sx, int sy, int c3[3]) {
-    if ((K == FFL_SRC_ANY ? kind : K) == FFL_SRC_YUV) {
-        const int Y = d.p0[(long long)(sy - d.wy) * d.pitch0 + (sx - d.wx)];
+__device__ __forceinline__ void ffl_front_fetch(const FrameDesc &d, const FrontParams &p, int sx, int sy, int c3[3]) {
+    const int kind = K == FFL_SRC_ANY ? p.kind : K;
+    if (kind == FFL_SRC_YUV || kind == FFL_SRC_YUV16) {
         const long long cy = (sy >> 1) - (d.wy >> 1), cx = (long long)((sx >> 1) - (d.wx >> 1)) * d.c_step;
-        const int u = d.p1[cy * d.pitch1 + cx] - 128, v = d.p2[cy * d.pitch2 + cx] - 128;
+        int Y, u, v;
+        if (kind == FFL_SRC_YUV16) {  // pitches and c_step stay in bytes; every address is even
+            const int y16 = *(const uint16_t *)(d.p0 + (long long)(sy - d.wy) * d.pitch0 + 2LL * (sx - d.wx));
+            const int u16 = *(const uint16_t *)(d.p1 + cy * d.pitch1 + cx), v16 = *(const uint16_t *)(d.p2 + cy * d.pitch2 + cx);
+            Y = min((y16 + p.round16) >> p.shift16, 255);
+            u = min((u16 + p.round16) >> p.shift16, 255) - 128;
+            v = min((v16 + p.round16) >> p.shift16, 255) - 128;
+        } else {
+            Y = d.p0[(long long)(sy - d.wy) * d.pitch0 + (sx - d.wx)];
+            u = d.p1[cy * d.pitch1 + cx] - 128;
+            v = d.p2[cy * d.pitch2 + cx] - 128;
+        }
         const int yh = max(Y - 16, 0) * 1220542 + (1 << 19);
         c3[0] = ffl_sat_u8((yh + 2116026 * u) >> 20);
         c3[1] = ffl_sat_u8((yh - 852492 * v - 409993 * u) >> 20);
@@ -53,13 +65,13 @@ __device__ __forceinline__ void ffl_front_resample(const FrameDesc &d, const Fro
     const int dx = x + p.cx, dy = y + p.cy;  // position in the (virtual) resized image
     int v[3];
     if (p.mode == FFL_FRONT_IDENTITY) {
-        ffl_front_fetch<K>(d, p.kind, dx, dy, v);
+        ffl_front_fetch<K>(d, p, dx, dy, v);
     } else if (p.mode == FFL_FRONT_AREA2) {  // exact 2x2 down-scale: INTER_LINEAR is routed to INTER_AREA
         int s00[3], s01[3], s10[3], s11[3];
-        ffl_front_fetch<K>(d, p.kind, 2 * dx, 2 * dy, s00);
-        ffl_front_fetch<K>(d, p.kind, 2 * dx + 1, 2 * dy, s01);
-        ffl_front_fetch<K>(d, p.kind, 2 * dx, 2 * dy + 1, s10);
-        ffl_front_fetch<K>(d, p.kind, 2 * dx + 1, 2 * dy + 1, s11);
+        ffl_front_fetch<K>(d, p, 2 * dx, 2 * dy, s00);
+        ffl_front_fetch<K>(d, p, 2 * dx + 1, 2 * dy, s01);
+        ffl_front_fetch<K>(d, p, 2 * dx, 2 * dy + 1, s10);
+        ffl_front_fetch<K>(d, p, 2 * dx + 1, 2 * dy + 1, s11);
 #pragma unroll
         for (int c = 0; c < 3; c++) v[c] = (s00[c] + s01[c] + s10[c] + s11[c] + 2) >> 2;
     } else {
@@ -76,10 +88,10 @@ __device__ __forceinline__ void ffl_front_resample(const FrameDesc &d, const Fro
         const int b0 = ffl_sat_short_round((1.f - fy) * 2048.f), b1 = ffl_sat_short_round(fy * 2048.f);
         const int y0 = min(max(sy, 0), p.sh - 1), y1 = min(max(sy + 1, 0), p.sh - 1);
         int s00[3], s01[3], s10[3], s11[3];
-        ffl_front_fetch<K>(d, p.kind, sx, y0, s00);
-        ffl_front_fetch<K>(d, p.kind, sx1, y0, s01);
-        ffl_front_fetch<K>(d, p.kind, sx, y1, s10);
-        ffl_front_fetch<K>(d, p.kind, sx1, y1, s11);
+        ffl_front_fetch<K>(d, p, sx, y0, s00);
+        ffl_front_fetch<K>(d, p, sx1, y0, s01);
+        ffl_front_fetch<K>(d, p, sx, y1, s10);
+        ffl_front_fetch<K>(d, p, sx1, y1, s11);
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             const int h0 = s00[c] * a0 + s01[c] * a1;
@@ -96,6 +108,7 @@ __global__ __launch_bounds__(256) void k_frontend(FrameDesc d, uint8_t *__restri
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= p.ow || y >= p.oh) return;
     if (p.kind == FFL_SRC_YUV) ffl_front_resample<FFL_SRC_YUV>(d, p, gray, x, y);
+    else if (p.kind == FFL_SRC_YUV16) ffl_front_resample<FFL_SRC_YUV16>(d, p, gray, x, y);
     else ffl_front_resample<FFL_SRC_BGR>(d, p, gray, x, y);
 }
 

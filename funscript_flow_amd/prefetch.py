@@ -49,7 +49,7 @@ class SequentialDecoder:
         return len(self.indices)
 
     def read_into(self, dst):
-        """Decode the next wanted frame into `dst` ((h, w, 3) uint8, or (3h/2, w) 4:2:0); returns its frame index, or None at
+        """Decode the next wanted frame into `dst` ((h, w, 3) uint8, or (3h/2, w) 4:2:0 of uint8 / uint16); returns its frame index, or None at
         the end."""
         if self.k >= len(self.indices):
             return None
@@ -107,9 +107,11 @@ class PrefetchRing:
     `ctx` provides pinned_frames(n, channels=3, size=(w, h)) (a real Context, or anything with that method).
     ring_frames must cover what the engine keeps in flight: two batches + the one being staged = 3 * B + 1.
     yuv="i420" | "nv12": the capture's read() yields (3h/2, w) 4:2:0 frames (w, h still from CAP_PROP_FRAME_*), and the
-    slots come from pinned_frames(n, size=(w, h), yuv=True); consume them with frontend.DecodedUploader(ctx, yuv=...)."""
+    slots come from pinned_frames(n, size=(w, h), yuv=True); consume them with frontend.DecodedUploader(ctx, yuv=...).
+    depth=9..16 beside yuv: read() yields uint16 frames, and the slots come from pinned_frames(..., yuv=True, depth=depth)
+    -- the keyword is passed only then."""
 
-    def __init__(self, ctx, capture, indices, bracket, ring_frames, frame_size=None, yuv=None):
+    def __init__(self, ctx, capture, indices, bracket, ring_frames, frame_size=None, yuv=None, depth=8):
         self.decoder = SequentialDecoder(capture, indices)
         if frame_size is None:
             frame_size = (int(capture.get(CAP_PROP_FRAME_WIDTH)), int(capture.get(CAP_PROP_FRAME_HEIGHT)))
@@ -118,12 +120,15 @@ class PrefetchRing:
             raise ValueError("bracket (frames per chunk) must be >= 2")
         self.ring_frames = int(ring_frames)
         if yuv is None:
+            if depth != 8:
+                raise ValueError("depth describes 4:2:0 frames: it needs yuv=\"i420\" | \"nv12\"")
             self.slots = ctx.pinned_frames(self.ring_frames, channels=3, size=frame_size)
         else:
             _capi.yuv_layout(yuv)
+            depth, _ = _capi.yuv_depth(depth)
             if frame_size[0] % 2 or frame_size[1] % 2:
                 raise ValueError(f"4:2:0 frames need an even width and height, the capture reports {frame_size}")
-            self.slots = ctx.pinned_frames(self.ring_frames, size=frame_size, yuv=True)
+            self.slots = ctx.pinned_frames(self.ring_frames, size=frame_size, yuv=True, **({"depth": depth} if depth != 8 else {}))
         self.cv = threading.Condition()
         self.decoded = 0       # stream positions [0, decoded) have been decoded (position = rank in `indices`)
         self.released = 0      # positions [0, released) may be overwritten
@@ -193,6 +198,22 @@ class PrefetchRing:
         self.thread.join()
 
 
+def yuv_params(params):
+    """(params["hip_yuv"], the depth keywords of frontend.DecodedUploader): params["hip_yuv_depth"] and the optional
+    params["hip_yuv_msb"] travel only when they are set, so that without them nothing changes"""
+    deep = {}
+    if params.get("hip_yuv_depth") is not None:
+        deep["depth"] = int(params["hip_yuv_depth"])
+    if params.get("hip_yuv_msb") is not None:
+        deep["msb"] = bool(params["hip_yuv_msb"])
+    return params.get("hip_yuv"), deep
+
+
+def ring_depth(deep):
+    """the depth keyword of PrefetchRing out of yuv_params' keywords: only when the frames are not uint8"""
+    return {"depth": deep["depth"]} if deep.get("depth", 8) != 8 else {}
+
+
 def video_to_actions(ctx, capture, params, engine=None, ring_frames=None):
     """process_video's body from frame sampling to the action list (FF:1119-1385) on the HIP path, decoding
     included: sequential reads into the pinned ring, device front-end, two-pass pair engine, host post-chain."""
@@ -201,13 +222,14 @@ def video_to_actions(ctx, capture, params, engine=None, ring_frames=None):
     _, _, indices = postchain.sampling(fps, total)
     bracket = int(params.get("batch_size", 3000.0))
     # params["hip_yuv"] = "i420" | "nv12": the capture yields 4:2:0 frames; a caller's engine must
-    # then have been built with frontend.DecodedUploader(ctx, yuv=...)
-    yuv = params.get("hip_yuv")
-    engine = engine or pipeline.PairEngine(ctx, frontend.DecodedUploader(ctx, bool(params.get("vr_mode")), False, yuv=yuv))
+    # then have been built with frontend.DecodedUploader(ctx, yuv=...).  params["hip_yuv_depth"] = 9..16 and the optional
+    # params["hip_yuv_msb"]: those frames are uint16 (rule Y5)
+    yuv, deep = yuv_params(params)
+    engine = engine or pipeline.PairEngine(ctx, frontend.DecodedUploader(ctx, bool(params.get("vr_mode")), False, yuv=yuv, **deep))
     # params["hip_flow"] / ["hip_dis"] pick the flow algorithm for this call (a caller's engine is left as it is)
     algo = _capi.flow_choice(params) if ("hip_flow" in params or "hip_dis" in params) else None
     fbk = pipeline.farneback_kwargs(params, ctx.width, ctx.height)   # params["hip_farneback"], ["hip_farneback_window"]: this call's
-    ring = PrefetchRing(ctx, capture, indices, bracket, ring_frames or 4 * ctx.max_batch + 2, yuv=yuv)
+    ring = PrefetchRing(ctx, capture, indices, bracket, ring_frames or 4 * ctx.max_batch + 2, yuv=yuv, **ring_depth(deep))
     dots, cuts, frame_idx = [], [], []
     try:
         for view, fidx in ring.chunks():
@@ -261,10 +283,12 @@ def process_video(video_path, params, log_func, open_capture, make_context, prog
     try:
         ctx = make_context(cap)
         flow, dis = _capi.flow_choice(params)
-        yuv = params.get("hip_yuv")   # "i420" | "nv12": open_capture's read() yields (3h/2, w) 4:2:0 frames
-        engine = pipeline.PairEngine(ctx, frontend.DecodedUploader(ctx, bool(params.get("vr_mode")), False, yuv=yuv), flow=flow,
-                                     dis=dis, farneback=_capi.farneback_choice(params), window=_capi.farneback_mode(params))
-        ring = PrefetchRing(ctx, cap, indices, int(params.get("batch_size", 3000.0)), 4 * ctx.max_batch + 2, yuv=yuv)
+        yuv, deep = yuv_params(params)   # "i420" | "nv12": open_capture's read() yields (3h/2, w) 4:2:0 frames
+        engine = pipeline.PairEngine(ctx, frontend.DecodedUploader(ctx, bool(params.get("vr_mode")), False, yuv=yuv, **deep),
+                                     flow=flow, dis=dis, farneback=_capi.farneback_choice(params),
+                                     window=_capi.farneback_mode(params))
+        ring = PrefetchRing(ctx, cap, indices, int(params.get("batch_size", 3000.0)), 4 * ctx.max_batch + 2, yuv=yuv,
+                            **ring_depth(deep))
         dots, cuts, frame_idx, done = [], [], [], 0
         for view, fidx in ring.chunks():
             if cancel_flag and cancel_flag():

@@ -17,6 +17,8 @@
  *                           + crop f[256:, :256] FF:1076-1079 (VR), cv2.cvtColor(RGB2GRAY) FF:1079/1082
  *   ffl_upload_frames_yuv   the same operand from a decoder's native 4:2:0 output (I420 / NV12): the decoder's own
  *                           YUV->BGR conversion before FF:182, then as ffl_upload_frames_raw
+ *   ffl_upload_frames_yuv16 the same from 9- to 16-bit 4:2:0 (yuv420p10le, P010 / P016): each sample reduced to 8 bits at
+ *                           its load (appendix Y, rule Y5); ffl_upload_frames_device16 for such frames in device memory
  *   ffl_flow_pairs          cv2.calcOpticalFlowFarneback(p0,p1,None,0.5,3,15,3,5,1.2,0)  FF:878-879
  *                           + max_divergence(flow)  FF:884 -> FF:748-758
  *                           + cv2.cartToPolar / np.mean                             FF:889-890
@@ -157,6 +159,27 @@ int ffl_upload_frames_yuv(ffl_ctx *ctx, int first_slot, int n, const uint8_t *co
 int ffl_frontend_yuv_window(int src_w, int src_h, int layout, ptrdiff_t stride_bytes, int resize_w, int resize_h,
                             int crop_x, int crop_y, int out_w, int out_h, int win[4], size_t *bytes);
 
+/* High-bit-depth 4:2:0 (rule Y5): the same single-array layouts with uint16 little-endian samples,
+ * shape (H*3/2, W) counted in samples -- `ffmpeg -pix_fmt yuv420p10le|yuv420p12le` (FFL_YUV_I420, the significant bits
+ * low: msb_aligned 0) and P010 / P012 / P016 decoder surfaces (FFL_YUV_NV12, the significant bits high: msb_aligned 1).
+ * `depth` = 9..16 significant bits.  Every sample is reduced to 8 bits at its load, round half up with saturation,
+ *     s  = msb_aligned ? raw >> (16 - depth) : raw;      v8 = min(255, (s + (1 << (depth - 9))) >> (depth - 8))
+ * (defined for every 16-bit pattern: the bits below a high-aligned sample are ignored, a low-aligned sample >= 2^depth
+ * gives 255) and then converted exactly as ffl_upload_frames_yuv converts its bytes.  This is the library's own rule:
+ * swscale dithers such a reduction and cv2 has none.
+ * The contract of ffl_upload_frames_yuv otherwise, with the window (ffl_frontend_yuv16_window) travelling at 2 bytes per
+ * sample; stride_bytes is in BYTES.  Refused (FFL_ERR_INVALID, the message names the rule): depth outside 9..16, an odd
+ * stride_bytes, a frame pointer that is not 2-byte aligned, I420 with stride_bytes != 2 * width, NV12 with stride_bytes <
+ * 2 * width, and every refusal of ffl_upload_frames_yuv. */
+int ffl_upload_frames_yuv16(ffl_ctx *ctx, int first_slot, int n, const uint16_t *const *frames, int src_width,
+                            int src_height, ptrdiff_t stride_bytes, int layout, int depth, int msb_aligned,
+                            int resize_width, int resize_height, int crop_x, int crop_y);
+
+/* ffl_frontend_yuv_window for 16-bit frames: the same rectangle (in samples; columns rounded out to multiples of 16
+ * samples) for the same geometry, *bytes = width * height * 3.  The refusals of ffl_upload_frames_yuv16. */
+int ffl_frontend_yuv16_window(int src_w, int src_h, int layout, ptrdiff_t stride_bytes, int depth, int resize_w,
+                              int resize_h, int crop_x, int crop_y, int out_w, int out_h, int win[4], size_t *bytes);
+
 /* ---- device-memory I/O ------------------------------------------------------------------------
  * Frames that already live in device memory (a GPU decoder's surfaces, torch tensors) go to frame slots without a round
  * trip through the host, and flow fields go from flow slots into caller device memory.  Same operands, same fields.
@@ -209,6 +232,17 @@ int ffl_dev_frame_check(int format, int src_w, int src_h, const ffl_dev_frame *f
  * Nothing of this call is ever captured into the library's graphs. */
 int ffl_upload_frames_device(ffl_ctx *ctx, int first_slot, int n, const ffl_dev_frame *frames, int format, int src_w,
                              int src_h, int resize_w, int resize_h, int crop_x, int crop_y, uint64_t stream);
+
+/* The device-memory calls for 16-bit 4:2:0 frames (rule Y5, see ffl_upload_frames_yuv16): format FFL_DEV_I420 or
+ * FFL_DEV_NV12 only, the planes of ffl_dev_frame holding uint16 samples -- pitches in bytes, even and >= 2 * the samples of
+ * a row (Y: w, I420 chroma: w / 2, NV12 UV: w), every plane 2-byte aligned.  Otherwise the rules, the memory checks (extents
+ * in bytes), the stream contract and the single k_frontend_dev launch of ffl_dev_frame_check / ffl_upload_frames_device;
+ * the operands are those of ffl_upload_frames_yuv16 for the same samples. */
+int ffl_dev_frame_check16(int format, int depth, int src_w, int src_h, const ffl_dev_frame *f, int resize_w, int resize_h,
+                          int crop_x, int crop_y, int out_w, int out_h);
+int ffl_upload_frames_device16(ffl_ctx *ctx, int first_slot, int n, const ffl_dev_frame *frames, int format, int depth,
+                               int msb_aligned, int src_w, int src_h, int resize_w, int resize_h, int crop_x, int crop_y,
+                               uint64_t stream);
 
 /* The finished flow fields of flow_slots[0..n) -> dst + i * item_stride_bytes, as (H, W, 2) float32 (FFL_FLOW_NHWC) or as
  * (2, H, W) float32 (FFL_FLOW_NCHW); each item is contiguous, items may be anywhere apart (|stride| >= 8 * W * H bytes).
@@ -496,8 +530,8 @@ int ffl_profile_enable(ffl_ctx *ctx, unsigned class_mask);
 #define FFL_K_GRAY 0
 #define FFL_K_PYRAMID 1
 #define FFL_K_POLYEXP 2
-#define FFL_K_FRONTEND 3 /* k_frontend of ffl_upload_frames_raw and ffl_upload_frames_yuv, k_frontend_dev of
-                            ffl_upload_frames_device (the x2 flow upsample, once class 3, runs inside k_update_matrices) */
+#define FFL_K_FRONTEND 3 /* k_frontend of ffl_upload_frames_raw and ffl_upload_frames_yuv / _yuv16, k_frontend_dev of
+                            ffl_upload_frames_device / _device16 (the x2 flow upsample, once class 3, runs inside k_update_matrices) */
 #define FFL_K_UPDATE_MATRICES 4
 #define FFL_K_BLUR_SOLVE 5
 #define FFL_K_PASS1 6

@@ -1,7 +1,7 @@
 """Rates of device-memory I/O, timed with HIP events in one process, repetitions interleaved:
 
   ingest  frames/s of ffl_upload_frames_device from torch tensors into a 256x256 context, 64 frames per call: 1080p BGR,
-          4K BGR, 5760x2880 NV12 VR (event on the caller's stream before the call, and after it -- the call makes that
+          4K BGR, 5760x2880 NV12 VR, and that VR source as P010 (uint16, depth 10: ffl_upload_frames_device16) (event on the caller's stream before the call, and after it -- the call makes that
           stream wait for the ingest, so the interval ends when the frames are in their slots)
   export  GB/s of ffl_export_flows (bytes read + written) for 256 flows at 256x256 and 32 at 1080p, NHWC and NCHW
   chain   pairs/s of PairEngine.process_chunk at 256x256, B = 256, from device-resident gray frames (DeviceUploader)
@@ -39,14 +39,17 @@ def ingest(reps, out):
     n = 64
     g = torch.Generator(device=DEV).manual_seed(1)
     srcs = [("1920x1080 bgr", "bgr", (n, 1080, 1920, 3), False), ("3840x2160 bgr", "bgr", (n, 2160, 3840, 3), False),
-            ("5760x2880 nv12 vr", "nv12", (n, 4320, 5760), True)]
+            ("5760x2880 nv12 vr", "nv12", (n, 4320, 5760), True), ("5760x2880 p010 vr", "nv12", (n, 4320, 5760), True)]
     ctx = _capi.Context(256, 256, max_batch=1, frame_slots=n)
     data = {name: torch.randint(0, 256, shape, dtype=torch.uint8, device=DEV, generator=g) for name, _, shape, _ in srcs}
+    deep = {"5760x2880 p010 vr": {"depth": 10}}
+    for name in deep:   # ten random bits, high in the 16
+        data[name] = torch.randint(-32768, 32768, data[name].shape, dtype=torch.int16, device=DEV, generator=g).bitwise_and_(-64).view(torch.uint16)
     ms = {name: [] for name, *_ in srcs}
     for r in range(reps + 1):
         for name, fmt, shape, vr in srcs:
             resize, crop = frontend.geometry(256, 256, vr)
-            t = timed(lambda: ctx.upload_frames_device(0, data[name], fmt, resize, crop))
+            t = timed(lambda: ctx.upload_frames_device(0, data[name], fmt, resize, crop, **deep.get(name, {})))
             if r:
                 ms[name].append(t)
     for name, *_ in srcs:
