@@ -930,7 +930,7 @@ int ffl_create(int device, int width, int height, int n_frame_slots, int n_flow_
         return set_err(nullptr, FFL_ERR_INVALID, "ffl_create: %d pyramid levels at %dx%d, the level tables hold %d", geo.levels + 1,
                        width, height, FFL_MAX_JOBS);
     for (int k = 0; k <= geo.levels; k++)
-        if (!ffl_pyr_level_ok(width, geo.lv[k].lw, geo.lv[k].ksize))
+        if (!ffl_pyr_level_ok(width, height, geo.lv[k].lw, geo.lv[k].lh, geo.lv[k].ksize))
             return set_err(nullptr, FFL_ERR_INVALID, "ffl_create: no pyramid kernel for level %d of %dx%d (%d columns, %d-tap blur)",
                            k, width, height, geo.lv[k].lw, geo.lv[k].ksize);
     ffl_ctx *c = new ffl_ctx();

@@ -98,7 +98,9 @@ struct ImportArgs {
 
 // merged launches: one 1-D grid cut into per-job block ranges
 #define FFL_MAX_JOBS 4
-enum { FFL_PYR_F1 = 0, FFL_PYR_F2, FFL_PYR_H4, FFL_PYR_H9, FFL_PYR_V4, FFL_PYR_V9 };
+// kernel forms of a level: fused 3-tap x1 / x2, or the H and V passes of a pair of radius 4 / 9 / 1 (V = H + 2; the
+// radius-1 pair is launched per level only, k_pyr_multi has no case for it)
+enum { FFL_PYR_NONE = -1, FFL_PYR_F1 = 0, FFL_PYR_F2, FFL_PYR_H4, FFL_PYR_H9, FFL_PYR_V4, FFL_PYR_V9, FFL_PYR_H1 };
 struct PyrJob {  // one level of the pyramid (caller fills w, h, lw, lh, sx, sy, gk, tmp, tmp_stride, I, I_stride)
     int kind, w, h, lw, lh;
     unsigned gx, gy, first, count;  // grid of one frame, first block of the job, tiles of the job (all frames)
@@ -181,7 +183,7 @@ void ffl_launch_import_pass1(const ImportArgs &a, const ExportTab &tab, int n, i
 void ffl_launch_gray(const uint8_t *bgr, uint8_t *gray, int n_pixels, hipStream_t st);
 size_t ffl_pyr_tmp_floats(int w, int h, int lw);  // per-frame size of the level's horizontal-pass buffer
 // one level on its own; ffl_pyr_level_ok: the level has one of the forms this serves (checked by ffl_create)
-bool ffl_pyr_level_ok(int w, int lw, int ksize);
+bool ffl_pyr_level_ok(int w, int h, int lw, int lh, int ksize);
 void ffl_launch_pyr_level(const uint8_t *gray_base, size_t gray_stride, const UTab *ut, int nU, const PyrJob &level,
                           hipStream_t st);
 void ffl_launch_polyexp(const PolyJob &level, int nU, PolyConsts pc, hipStream_t st);
@@ -247,6 +249,30 @@ void ffl_launch_radial(const WindowItem *tab, int n, int w, int h, int pov_mode,
 void ffl_launch_window_plan(const WindowSeq &seq, int n_seq, int first, int n, int radius, float cut_threshold,
                             const Pass1Result *res, const float *flow, int w, int h, WindowItem *tab, Pass2Record *out,
                             hipStream_t st);
+
+// ---- index rules shared by the kernel files ----------------------------------------------------------------------
+__device__ __forceinline__ int ffl_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+__device__ __forceinline__ int ffl_reflect101(int p, int n) {  // BORDER_REFLECT_101
+    if (n == 1) return 0;
+    while (p < 0 || p >= n) p = p < 0 ? -p : 2 * (n - 1) - p;
+    return p;
+}
+
+// INTER_LINEAR coordinate rule of the oracle's resize tables, for destination index d.
+// `scale` = (double)src / dst (IEEE division: the same double the oracle forms)
+__device__ __forceinline__ void ffl_resize_coord(int d, int src, double scale, int &i0, int &i1, float &f) {
+    // (the x2 upsample of an even-sized level takes ffl_resize_coord_half of kernels_farneback.hip; useless while the
+    // phase waited for its loads, -1.5 % once it did not)
+    float fx = (float)((d + 0.5) * scale - 0.5);
+    int sx = (int)floorf(fx);
+    fx -= sx;
+    if (sx < 0) { sx = 0; fx = 0.f; }
+    if (sx >= src - 1) { sx = src - 1; fx = 0.f; }
+    i0 = sx;
+    i1 = sx + 1 < src ? sx + 1 : src - 1;
+    f = fx;
+}
 
 // XCD-aware order of a 1-D run of `count` tiles: the l-th workgroup of the run (l and l+8 share an XCD under the
 // observed round-robin placement; the run must start at a multiple of 8) takes tile (l % 8) * chunk + l / 8, so every

@@ -21,8 +21,6 @@
 #define DIS_OMEGA 1.6f
 #define DIS_SOR 5
 
-__device__ __forceinline__ int dis_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // D0: lane l ends with ((v_l + v_{l^32}) + ...) -- the same value in every lane (each step adds commutatively equal
 // pairs), equal to the restatement's t[0]
 __device__ __forceinline__ float dis_wave_sum(float v) {
@@ -32,8 +30,8 @@ __device__ __forceinline__ float dis_wave_sum(float v) {
 
 // D5
 __device__ __forceinline__ float dis_bilin(const float *__restrict__ I, int w, int h, int x0, int y0, float ax, float ay) {
-    const int c0 = dis_clampi(x0, 0, w - 1), c1 = dis_clampi(x0 + 1, 0, w - 1);
-    const int r0 = dis_clampi(y0, 0, h - 1), r1 = dis_clampi(y0 + 1, 0, h - 1);
+    const int c0 = ffl_clampi(x0, 0, w - 1), c1 = ffl_clampi(x0 + 1, 0, w - 1);
+    const int r0 = ffl_clampi(y0, 0, h - 1), r1 = ffl_clampi(y0 + 1, 0, h - 1);
     const float w00 = (1.0f - ax) * (1.0f - ay), w01 = ax * (1.0f - ay), w10 = (1.0f - ax) * ay, w11 = ax * ay;
     return ((w00 * I[r0 * w + c0] + w01 * I[r0 * w + c1]) + w10 * I[r1 * w + c0]) + w11 * I[r1 * w + c1];
 }
@@ -42,15 +40,15 @@ __device__ __forceinline__ float dis_bilin(const float *__restrict__ I, int w, i
 __device__ __forceinline__ float dis_deriv5(const float *__restrict__ f, int w, int h, int x, int y, int along_x) {
     float a, b, c, d;
     if (along_x) {
-        a = f[y * w + dis_clampi(x - 2, 0, w - 1)];
-        b = f[y * w + dis_clampi(x - 1, 0, w - 1)];
-        c = f[y * w + dis_clampi(x + 1, 0, w - 1)];
-        d = f[y * w + dis_clampi(x + 2, 0, w - 1)];
+        a = f[y * w + ffl_clampi(x - 2, 0, w - 1)];
+        b = f[y * w + ffl_clampi(x - 1, 0, w - 1)];
+        c = f[y * w + ffl_clampi(x + 1, 0, w - 1)];
+        d = f[y * w + ffl_clampi(x + 2, 0, w - 1)];
     } else {
-        a = f[dis_clampi(y - 2, 0, h - 1) * w + x];
-        b = f[dis_clampi(y - 1, 0, h - 1) * w + x];
-        c = f[dis_clampi(y + 1, 0, h - 1) * w + x];
-        d = f[dis_clampi(y + 2, 0, h - 1) * w + x];
+        a = f[ffl_clampi(y - 2, 0, h - 1) * w + x];
+        b = f[ffl_clampi(y - 1, 0, h - 1) * w + x];
+        c = f[ffl_clampi(y + 1, 0, h - 1) * w + x];
+        d = f[ffl_clampi(y + 2, 0, h - 1) * w + x];
     }
     return (((a - 8.0f * b) + 8.0f * c) - d) / 12.0f;
 }
@@ -270,8 +268,8 @@ __global__ __launch_bounds__(DIS_THREADS) void k_dis_prep(const UTab *__restrict
             #pragma unroll 1
             for (int k = tid; k < n; k += DIS_THREADS) {
                 const int y = k / lw, x = k - y * lw;
-                const int ym = dis_clampi(y - 1, 0, lh - 1), yp = dis_clampi(y + 1, 0, lh - 1);
-                const int xm = dis_clampi(x - 1, 0, lw - 1), xp = dis_clampi(x + 1, 0, lw - 1);
+                const int ym = ffl_clampi(y - 1, 0, lh - 1), yp = ffl_clampi(y + 1, 0, lh - 1);
+                const int xm = ffl_clampi(x - 1, 0, lw - 1), xp = ffl_clampi(x + 1, 0, lw - 1);
                 const float a = I[ym * lw + xm], bb = I[ym * lw + x], cc = I[ym * lw + xp];
                 const float d = I[y * lw + xm], ff = I[y * lw + xp];
                 const float g = I[yp * lw + xm], kk = I[yp * lw + x], l = I[yp * lw + xp];

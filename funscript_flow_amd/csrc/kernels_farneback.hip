@@ -4,10 +4,11 @@
 //
 // Kernel            bound      algorithmic bytes / level pixel
 //   k_gray          HBM        4 per full-res pixel (3 in, 1 out)
-//   k_pyr_*         HBM / LDS  1 per full-res pixel in + 4 per level pixel out ("k_pyr_level" class): fused 3-tap
-//                              kernels for the exact 1x / 2x levels (4 pixels per lane, inside k_pyr_multi), one
-//                              LDS-staged pass for the x1/4 and x1/8 levels together (k_pyr_coarse), H + V kernel
-//                              pairs for geometries those do not cover
+//   k_pyr_*         HBM / LDS  1 per full-res pixel in + 4 per level pixel out ("k_pyr_level" class): one fused 3-tap
+//                              body for the exact 1x / 2x levels (4 pixels per lane; its aligned form inside
+//                              k_pyr_multi, its unaligned form for w or lw not a multiple of 4), one LDS-staged pass
+//                              for the x1/4 and x1/8 levels together (k_pyr_coarse), H + V kernel pairs for
+//                              geometries those do not cover; ffl_pyr_form states which form a level takes
 //   k_polyexp       VALU(f64)  24  (4 in, 20 out), 11x11 separable through LDS, f64 accumulators, 4 pixels per
 //                              lane; all levels in one merged launch (k_polyexp_multi)
 //   k_update_mat    HBM        68  (R0 20 + R1 gather 20 + flow 8 -> M 20); also forms the level's
@@ -56,27 +57,8 @@ void ffl_launch_gray(const uint8_t *bgr, uint8_t *gray, int n_pixels, hipStream_
 // The blur is evaluated only at the (up to 4) full-resolution pixels each output samples:
 // horizontal pass first (float, symmetric form, REFLECT_101), then vertical, then the two lerps.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int ffl_reflect101(int p, int n) {
-    if (n == 1) return 0;
-    while (p < 0 || p >= n) p = p < 0 ? -p : 2 * (n - 1) - p;
-    return p;
-}
-
-// `scale` = (double)src / dst, formed once on the host (IEEE division: the same double the oracle forms)
-__device__ __forceinline__ void ffl_resize_coord(int d, int src, double scale, int &i0, int &i1, float &f) {
-    // (the x2 upsample of an even-sized level takes ffl_resize_coord_half below; useless while the phase waited for its
-    // loads, -1.5 % once it did not)
-    float fx = (float)((d + 0.5) * scale - 0.5);
-    int sx = (int)floorf(fx);
-    fx -= sx;
-    if (sx < 0) { sx = 0; fx = 0.f; }
-    if (sx >= src - 1) { sx = src - 1; fx = 0.f; }
-    i0 = sx;
-    i1 = sx + 1 < src ? sx + 1 : src - 1;
-    f = fx;
-}
-
-// the same for scale == 0.5 exactly (a x2 upsample of an even-sized level): (d + 0.5) * 0.5 - 0.5 = d/2 - 0.25 is exact in
+// (ffl_reflect101 and the INTER_LINEAR coordinate rule ffl_resize_coord: ffl_kernels.h)
+// ffl_resize_coord for scale == 0.5 exactly (a x2 upsample of an even-sized level): (d + 0.5) * 0.5 - 0.5 = d/2 - 0.25 is exact in
 // double and in float, so floor and fraction follow from the parity of d -- identical results without the f64 arithmetic
 __device__ __forceinline__ void ffl_resize_coord_half(int d, int src, int &i0, int &i1, float &f) {
     int sx = (d - 1) >> 1;
@@ -233,72 +215,18 @@ __global__ __launch_bounds__(256) void k_pyr_v2(const float *__restrict__ tmp, s
 }
 
 // Fused form for the two fine levels of every BASELINE size: 3-tap blur (R = 1) with an exact S = 1
-// (level 0) or S = 2 (level 1) decimation.  One lane produces FROWS consecutive output rows of one
-// output column: the S*FROWS + 2 source rows are fetched word-wise once, blurred horizontally in
-// registers, then combined vertically -- no intermediate plane, same operations in the same order as
+// (level 0) or S = 2 (level 1) decimation.  One lane produces FR consecutive output rows of four adjacent
+// output columns: the S*FR + 2 source rows are fetched once (the 4S + 2 source bytes of a row with ONE
+// 12- / 16-byte load), blurred horizontally in registers, then combined vertically, and the four results
+// leave with one 16-byte store -- no intermediate plane, same operations in the same order as
 // k_pyr_h2 + k_pyr_v2 (for S = 2 the lerp weights are exactly 0.5, for S = 1 the lerps are identities).
-#define FFL_PYR_FROWS 4
+// ALIGNED: w and lw are multiples of 4 (what k_pyr_multi takes).  Otherwise the last lane of a row may hold
+// fewer than four outputs, and rows only start dword-aligned, i.e. take the word-wise fetch, when w % 4 == 0.
 #ifndef FFL_FR1
-#define FFL_FR1 8  // output rows per lane of the fused 3-tap kernels, level 0 / level 1 (33 x 1080p frames: 4/2 136 us,
+#define FFL_FR1 8  // output rows per lane, level 0 / level 1 (33 x 1080p frames: 4/2 136 us,
 #define FFL_FR2 2  // 8/2 129, 12/2 136, 16/2 208, 8/4 256, 8/1 157, 2/2 175)
 #endif
-template <int S>
-__global__ __launch_bounds__(256) void k_pyr_fused3(const uint8_t *__restrict__ gray_base, size_t gray_stride, const UTab *__restrict__ ut,
-                                                    int w, int h, int lw, int lh, GaussKernel gk,
-                                                    float *__restrict__ I, size_t I_stride) {
-    constexpr int NR = S * FFL_PYR_FROWS + 2;  // source rows per lane
-    const int dx = blockIdx.x * 256 + threadIdx.x, u = blockIdx.z;
-    if (dx >= lw) return;
-    const uint8_t *img = gray_base + (size_t)ut->fslot[u] * gray_stride;
-    const int cx = S * dx;                       // first sampled column; S == 2 also samples cx + 1
-    const int first = cx - 1, woff = first & 3, wbase = first - woff;
-    const bool wide = first >= 0 && cx + S < w && (w & 3) == 0;  // taps cx-1 .. cx+S inside the row
-    const float k0 = gk.k[1], k1 = gk.k[2];
-    const int dy0 = blockIdx.y * FFL_PYR_FROWS;
-    float H0[NR], H1[NR];
-#pragma unroll
-    for (int j = 0; j < NR; j++) {
-        const int sy = ffl_reflect101(min(S * dy0 - 1 + j, h + 1), h);  // rows past the image are never used
-        const uint8_t *row = img + (size_t)sy * w;
-        float b[S + 2];
-        if (wide) {
-            const uint32_t *wp = reinterpret_cast<const uint32_t *>(row + wbase);
-            const uint32_t lo = wp[0], hi = wp[1];
-            const uint32_t a = __builtin_amdgcn_alignbyte(hi, lo, woff);  // bytes first .. first+3
-#pragma unroll
-            for (int t = 0; t < S + 2; t++) b[t] = (float)((a >> (8 * t)) & 255u);
-        } else {
-#pragma unroll
-            for (int t = 0; t < S + 2; t++) b[t] = (float)row[ffl_reflect101(first + t, w)];
-        }
-        H0[j] = k0 * b[1] + k1 * (b[0] + b[2]);
-        H1[j] = S == 2 ? k0 * b[2] + k1 * (b[1] + b[3]) : 0.f;
-    }
-#pragma unroll
-    for (int o = 0; o < FFL_PYR_FROWS; o++) {
-        const int dy = dy0 + o;
-        if (dy >= lh) break;
-        const int c = S * o + 1;  // local index of source row S*dy
-        float out;
-        if (S == 1) {
-            const float v00 = k0 * H0[c] + k1 * (H0[c - 1] + H0[c + 1]);
-            out = (v00 * 1.f + 0.f * 0.f) * 1.f + 0.f * 0.f;
-        } else {
-            const float v00 = k0 * H0[c] + k1 * (H0[c - 1] + H0[c + 1]);
-            const float v01 = k0 * H1[c] + k1 * (H1[c - 1] + H1[c + 1]);
-            const float v10 = k0 * H0[c + 1] + k1 * (H0[c] + H0[c + 2]);
-            const float v11 = k0 * H1[c + 1] + k1 * (H1[c] + H1[c + 2]);
-            const float t0 = v00 * 0.5f + v01 * 0.5f, t1 = v10 * 0.5f + v11 * 0.5f;
-            out = t0 * 0.5f + t1 * 0.5f;
-        }
-        I[(size_t)u * I_stride + (size_t)dy * lw + dx] = out;
-    }
-}
-
-// The same, four adjacent output pixels per lane (w and lw multiples of 4): the 4S + 2 source bytes of a
-// row come with ONE 12- / 16-byte load and the four results leave with one 16-byte store -- a sixth of
-// the vector-memory instructions of the pixel-per-lane kernel above, which spent its time issuing them.
-template <int S, int FR>
+template <int S, int FR, bool ALIGNED>
 __device__ __forceinline__ void k_pyr_fused3x4_body(const unsigned bx, const unsigned by, const unsigned bz, const uint8_t *__restrict__ gray_base, size_t gray_stride, const UTab *__restrict__ ut,
                                                       int w, int h, int lw, int lh, GaussKernel gk,
                                                       float *__restrict__ I, size_t I_stride) {
@@ -308,7 +236,8 @@ __device__ __forceinline__ void k_pyr_fused3x4_body(const unsigned bx, const uns
     if (dx >= lw) return;
     const uint8_t *img = gray_base + (size_t)ut->fslot[u] * gray_stride;
     const int cx = S * dx;  // first sampled column, a multiple of 4
-    const bool wide = cx >= 4 && cx + 4 * S + 4 <= w;  // the aligned words cx-4 .. cx+4S+3 are inside the row
+    // the aligned words cx-4 .. cx+4S+3 are inside the row
+    const bool wide = (ALIGNED || (w & 3) == 0) && cx >= 4 && cx + 4 * S + 4 <= w;
     const float k0 = gk.k[1], k1 = gk.k[2];
     const int dy0 = by * FR;
     float H[NR][4 * S];  // horizontal blur at columns cx .. cx+4S-1
@@ -332,7 +261,7 @@ __device__ __forceinline__ void k_pyr_fused3x4_body(const unsigned bx, const uns
 #pragma unroll
             for (int t = 0; t < 4 * S; t++) b[1 + t] = (float)((wd[1 + (t >> 2)] >> (8 * (t & 3))) & 255u);
             b[NBY - 1] = (float)(wd[S + 1] & 255u);  // column cx+4S
-        } else {
+        } else {  // (columns past the last output's taps, in a row's last lane, feed results that are not stored)
 #pragma unroll
             for (int t = 0; t < NBY; t++) b[t] = (float)row[ffl_reflect101(cx - 1 + t, w)];
         }
@@ -359,16 +288,23 @@ __device__ __forceinline__ void k_pyr_fused3x4_body(const unsigned bx, const uns
                 out[i] = t0 * 0.5f + t1 * 0.5f;
             }
         }
-        ffl_f4u t;
-        t.x = out[0]; t.y = out[1]; t.z = out[2]; t.w = out[3];
-        *reinterpret_cast<ffl_f4u *>(I + (size_t)u * I_stride + (size_t)dy * lw + dx) = t;
+        float *dst = I + (size_t)u * I_stride + (size_t)dy * lw + dx;
+        if (ALIGNED || dx + 3 < lw) {
+            ffl_f4u t;
+            t.x = out[0]; t.y = out[1]; t.z = out[2]; t.w = out[3];
+            *reinterpret_cast<ffl_f4u *>(dst) = t;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                if (dx + i < lw) dst[i] = out[i];
+        }
     }
 }
-template <int S, int FR>
+template <int S, int FR, bool ALIGNED>
 __global__ __launch_bounds__(256) void k_pyr_fused3x4(const uint8_t *__restrict__ gray_base, size_t gray_stride, const UTab *__restrict__ ut,
                                                       int w, int h, int lw, int lh, GaussKernel gk,
                                                       float *__restrict__ I, size_t I_stride) {
-    k_pyr_fused3x4_body<S, FR>(blockIdx.x, blockIdx.y, blockIdx.z, gray_base, gray_stride, ut, w, h, lw, lh, gk, I, I_stride);
+    k_pyr_fused3x4_body<S, FR, ALIGNED>(blockIdx.x, blockIdx.y, blockIdx.z, gray_base, gray_stride, ut, w, h, lw, lh, gk, I, I_stride);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -385,17 +321,88 @@ __global__ __launch_bounds__(256) void k_pyr_fused3x4(const uint8_t *__restrict_
 #define PC_TH 64
 #define PC_PW 36   // staged tile: dwords per row (columns X0-8 .. X0+135)
 #define PC_PH 76   // rows Y0-6 .. Y0+69
-#define PC_H2R 70  // level-2 H rows: Y0-3 .. Y0+66
-#define PC_H2P 66  // pitch of sH2 (64 sampled columns + pad)
-#define PC_H3P 34  // pitch of sH3 (32 sampled columns + pad)
+// One level of the tile, blur radius R and decimation S (4, 4 and 9, 8): output (dl, el) of the tile samples image columns
+// X0 + S*dl + S/2 - 1, + S/2 and rows Y0 + S*el + S/2 - 1, + S/2.  Everything below follows from the staged tile's origin.
+template <int R, int S>
+struct PcLevel {
+    static constexpr int NC = PC_TW / S;                 // output columns per tile (32 / 16)
+    static constexpr int NO = NC * (PC_TH / S);          // outputs per tile (512 / 128)
+    static constexpr int HROWS = PC_TH + 2 * R - S + 2;  // rows the horizontal pass forms (70 / 76),
+    static constexpr int HROW0 = S / 2 + 5 - R;          // the first of them from staged row HROW0 (3 / 0)
+    static constexpr int PITCH = 2 * NC + 2;             // floats of a row of H: both samples of every column + pad
+    static constexpr int B0 = S / 2 + 7 - R;             // staged byte of column 0's first tap (5 / 2)
+    static constexpr int ND = (B0 % 4 + 2 * R + 5) / 4;  // dwords holding the 2R + 2 taps of a column (3 / 6)
+    static_assert(HROW0 >= 0 && HROW0 + HROWS <= PC_PH && B0 >= 0 && (NC - 1) * (S / 4) + B0 / 4 + ND <= PC_PW, "tile halo");
+};
+// horizontal pass: column dl's two samples, their taps fetched as ND dwords from dword dl * (S/4) + B0/4 on -> sH[row][2*dl]
+// (fixed trip counts + a row predicate: the loops unroll and a lane's LDS reads are in flight together)
+template <int R, int S>
+__device__ __forceinline__ void k_pyr_coarse_h(const uint32_t (*sP)[PC_PW], float (*sH)[PcLevel<R, S>::PITCH], const GaussKernel &gk,
+                                               int tid) {
+    using L = PcLevel<R, S>;
+    constexpr int RSTEP = 256 / L::NC, TRIPS = (L::HROWS + RSTEP - 1) / RSTEP, UNROLL = R == 4 ? 3 : TRIPS;
+    constexpr int C = L::B0 % 4 + R;  // the first sample's centre among the fetched bytes (5 / 11); the second is the next
+    const int dl = tid % L::NC, rr = tid / L::NC;
+#pragma unroll UNROLL
+    for (int k = 0; k < TRIPS; k++) {
+        const int ry = rr + RSTEP * k;
+        if (ry < L::HROWS) {
+            const uint32_t *p = &sP[ry + L::HROW0][dl * (S / 4) + L::B0 / 4];
+            uint32_t d[L::ND];
+#pragma unroll
+            for (int q = 0; q < L::ND; q++) d[q] = p[q];
+            auto tap = [&](int j) { return (float)((d[j >> 2] >> (8 * (j & 3))) & 255u); };  // byte j of the fetched ones
+            float a0 = gk.k[R] * tap(C), a1 = gk.k[R] * tap(C + 1);
+#pragma unroll
+            for (int j = 1; j <= R; j++) {
+                a0 = a0 + gk.k[R + j] * (tap(C - j) + tap(C + j));
+                a1 = a1 + gk.k[R + j] * (tap(C + 1 - j) + tap(C + 1 + j));
+            }
+            *reinterpret_cast<float2 *>(&sH[ry][2 * dl]) = make_float2(a0, a1);
+        }
+    }
+}
+// vertical pass + lerps: outputs dealt tid + 256 * k; output row el reads H rows S*el .. S*el + 2R + 1 with the samples'
+// centres at R and R + 1; lerp weights are exactly 0.5 (a0 = 1 - a1 as in ffl_resize_coord's users)
+template <int R, int S>
+__device__ __forceinline__ void k_pyr_coarse_v(const float (*sH)[PcLevel<R, S>::PITCH], const GaussKernel &gk, int tid, int X0,
+                                               int Y0, int w, int h, float *__restrict__ I) {
+    using L = PcLevel<R, S>;
+    const float a1 = 0.5f, a0 = 1.f - a1, b1 = 0.5f, b0 = 1.f - b1;
+    const int lw = w / S, lh = h / S;
+#pragma unroll
+    for (int k = 0; k < (L::NO + 255) / 256; k++) {
+        const int o = tid + 256 * k, el = o / L::NC, dl = o % L::NC;
+        if (L::NO % 256 != 0 && o >= L::NO) break;
+        const int dx = X0 / S + dl, dy = Y0 / S + el;
+        float2 V[2 * R + 2];
+#pragma unroll
+        for (int j = 0; j < 2 * R + 2; j++) V[j] = *reinterpret_cast<const float2 *>(&sH[S * el + j][2 * dl]);
+        float tq[2];
+#pragma unroll
+        for (int qy = 0; qy < 2; qy++) {
+            const int c = R + qy;
+            float v0 = gk.k[R] * V[c].x, v1 = gk.k[R] * V[c].y;
+#pragma unroll
+            for (int j = 1; j <= R; j++) {
+                v0 = v0 + gk.k[R + j] * (V[c - j].x + V[c + j].x);
+                v1 = v1 + gk.k[R + j] * (V[c - j].y + V[c + j].y);
+            }
+            tq[qy] = v0 * a0 + v1 * a1;
+        }
+        if (dx < lw && dy < lh) I[(size_t)dy * lw + dx] = tq[0] * b0 + tq[1] * b1;
+    }
+}
 __global__ __launch_bounds__(256) void k_pyr_coarse(const uint8_t *__restrict__ gray_base, size_t gray_stride,
                                                     const UTab *__restrict__ ut, int w, int h, GaussKernel gk2,
                                                     GaussKernel gk3, float *__restrict__ I2, size_t I2_stride,
                                                     float *__restrict__ I3, size_t I3_stride, int tiles_x, int tiles_y,
                                                     int nU) {
+    using L2 = PcLevel<4, 4>;
+    using L3 = PcLevel<9, 8>;
     __shared__ __attribute__((aligned(8))) uint32_t sP[PC_PH][PC_PW];
-    __shared__ __attribute__((aligned(8))) float sH2[PC_H2R][PC_H2P];
-    __shared__ __attribute__((aligned(8))) float sH3[PC_PH][PC_H3P];
+    __shared__ __attribute__((aligned(8))) float sH2[L2::HROWS][L2::PITCH];
+    __shared__ __attribute__((aligned(8))) float sH3[L3::HROWS][L3::PITCH];
     const int tid = threadIdx.x;
     const unsigned per = (unsigned)tiles_x * tiles_y;
     unsigned tt;  // XCD-aware order: neighbouring tiles (which share the 19-tap halo) run on one XCD
@@ -434,106 +441,11 @@ __global__ __launch_bounds__(256) void k_pyr_coarse(const uint8_t *__restrict__ 
         }
     }
     __syncthreads();
-    // ---- horizontal pass, level 2 (radius 4): output column dl samples tile bytes 4*dl+9, 4*dl+10 (image columns
-    // 4d+1, 4d+2); taps of both = bytes 4*dl+5 .. 4*dl+14 = dwords dl+1 .. dl+3
-    // (fixed trip counts + a row predicate: the loops unroll and a lane's LDS reads are in flight together)
-    {
-        const int dl = tid & 31, rr = tid >> 5;
-#pragma unroll 3
-        for (int k = 0; k < (PC_H2R + 7) / 8; k++) {
-            const int ry = rr + 8 * k;
-            if (ry < PC_H2R) {
-                const uint32_t *p = &sP[ry + 3][dl + 1];
-                const uint32_t d0 = p[0], d1 = p[1], d2 = p[2];
-                auto tap = [&](int j) {  // byte j of the 12 fetched ones; the first sample's centre is byte 5
-                    const uint32_t wd = j < 4 ? d0 : (j < 8 ? d1 : d2);
-                    return (float)((wd >> (8 * (j & 3))) & 255u);
-                };
-                float a0 = gk2.k[4] * tap(5), a1 = gk2.k[4] * tap(6);
-#pragma unroll
-                for (int j = 1; j <= 4; j++) {
-                    a0 = a0 + gk2.k[4 + j] * (tap(5 - j) + tap(5 + j));
-                    a1 = a1 + gk2.k[4 + j] * (tap(6 - j) + tap(6 + j));
-                }
-                *reinterpret_cast<float2 *>(&sH2[ry][2 * dl]) = make_float2(a0, a1);
-            }
-        }
-    }
-    // ---- horizontal pass, level 3 (radius 9): output column dl samples tile bytes 8*dl+11, 8*dl+12 (image columns
-    // 8d+3, 8d+4); taps of both = bytes 8*dl+2 .. 8*dl+21 = dwords 2*dl .. 2*dl+5
-    {
-        const int dl = tid & 15, rr = tid >> 4;
-#pragma unroll
-        for (int k = 0; k < (PC_PH + 15) / 16; k++) {
-            const int ry = rr + 16 * k;
-            if (ry < PC_PH) {
-                const uint32_t *p = &sP[ry][2 * dl];
-                uint32_t d[6];
-#pragma unroll
-                for (int q = 0; q < 6; q++) d[q] = p[q];
-                auto tap = [&](int j) { return (float)((d[j >> 2] >> (8 * (j & 3))) & 255u); };  // byte j of the 24
-                float a0 = gk3.k[9] * tap(11), a1 = gk3.k[9] * tap(12);
-#pragma unroll
-                for (int j = 1; j <= 9; j++) {
-                    a0 = a0 + gk3.k[9 + j] * (tap(11 - j) + tap(11 + j));
-                    a1 = a1 + gk3.k[9 + j] * (tap(12 - j) + tap(12 + j));
-                }
-                *reinterpret_cast<float2 *>(&sH3[ry][2 * dl]) = make_float2(a0, a1);
-            }
-        }
-    }
+    k_pyr_coarse_h<4, 4>(sP, sH2, gk2, tid);
+    k_pyr_coarse_h<9, 8>(sP, sH3, gk3, tid);
     __syncthreads();
-    // ---- vertical pass + lerps, level 2: 32 x 16 outputs, two per lane.  Output row el samples image rows
-    // 4e+1, 4e+2 = sH2 rows 4*el+4, 4*el+5; lerp weights are exactly 0.5 (a0 = 1 - a1 as in ffl_resize_coord's users)
-    {
-        const float a1 = 0.5f, a0 = 1.f - a1, b1 = 0.5f, b0 = 1.f - b1;
-        const int lw2 = w >> 2, lh2 = h >> 2;
-#pragma unroll
-        for (int k = 0; k < 2; k++) {
-            const int o = tid + 256 * k, el = o >> 5, dl = o & 31;
-            const int dx = (X0 >> 2) + dl, dy = (Y0 >> 2) + el;
-            float2 V[10];  // sH2 rows 4*el .. 4*el+9
-#pragma unroll
-            for (int j = 0; j < 10; j++) V[j] = *reinterpret_cast<const float2 *>(&sH2[4 * el + j][2 * dl]);
-            float tq[2];
-#pragma unroll
-            for (int qy = 0; qy < 2; qy++) {
-                const int c = 4 + qy;
-                float v0 = gk2.k[4] * V[c].x, v1 = gk2.k[4] * V[c].y;
-#pragma unroll
-                for (int j = 1; j <= 4; j++) {
-                    v0 = v0 + gk2.k[4 + j] * (V[c - j].x + V[c + j].x);
-                    v1 = v1 + gk2.k[4 + j] * (V[c - j].y + V[c + j].y);
-                }
-                tq[qy] = v0 * a0 + v1 * a1;
-            }
-            if (dx < lw2 && dy < lh2) I2[(size_t)u * I2_stride + (size_t)dy * lw2 + dx] = tq[0] * b0 + tq[1] * b1;
-        }
-    }
-    // ---- level 3: 16 x 8 outputs on the first 128 lanes.  Output row el samples image rows 8e+3, 8e+4 = sH3 rows
-    // 8*el+9, 8*el+10
-    if (tid < 128) {
-        const float a1 = 0.5f, a0 = 1.f - a1, b1 = 0.5f, b0 = 1.f - b1;
-        const int lw3 = w >> 3, lh3 = h >> 3;
-        const int el = tid >> 4, dl = tid & 15;
-        const int dx = (X0 >> 3) + dl, dy = (Y0 >> 3) + el;
-        float2 V[20];  // sH3 rows 8*el .. 8*el+19
-#pragma unroll
-        for (int j = 0; j < 20; j++) V[j] = *reinterpret_cast<const float2 *>(&sH3[8 * el + j][2 * dl]);
-        float tq[2];
-#pragma unroll
-        for (int qy = 0; qy < 2; qy++) {
-            const int c = 9 + qy;
-            float v0 = gk3.k[9] * V[c].x, v1 = gk3.k[9] * V[c].y;
-#pragma unroll
-            for (int j = 1; j <= 9; j++) {
-                v0 = v0 + gk3.k[9 + j] * (V[c - j].x + V[c + j].x);
-                v1 = v1 + gk3.k[9 + j] * (V[c - j].y + V[c + j].y);
-            }
-            tq[qy] = v0 * a0 + v1 * a1;
-        }
-        if (dx < lw3 && dy < lh3) I3[(size_t)u * I3_stride + (size_t)dy * lw3 + dx] = tq[0] * b0 + tq[1] * b1;
-    }
+    k_pyr_coarse_v<4, 4>(sH2, gk2, tid, X0, Y0, w, h, I2 + (size_t)u * I2_stride);
+    k_pyr_coarse_v<9, 8>(sH3, gk3, tid, X0, Y0, w, h, I3 + (size_t)u * I3_stride);
 }
 
 // true when the x1/4 and x1/8 levels of a w x h frame can take the one-pass kernel
@@ -550,8 +462,6 @@ bool ffl_launch_pyr_coarse(const uint8_t *gray_base, size_t gray_stride, const U
     return true;
 }
 
-size_t ffl_pyr_tmp_floats(int w, int h, int lw) { return (size_t)h * lw * (lw != w ? 2 : 1); }
-
 // All levels' pyramid work in TWO launches (1-D grids cut into per-job ranges): phase A = the fused fine
 // levels + the horizontal passes of the resampling levels, phase B = their vertical passes.  Six small,
 // latency-bound launches (117 us back to back at 1080p) overlap inside two.
@@ -567,8 +477,8 @@ __global__ __launch_bounds__(256) void k_pyr_multi(const uint8_t *__restrict__ g
     const unsigned per = J.gx * J.gy;
     const unsigned bz = t / per, r = t - bz * per, by = r / J.gx, bx = r - by * J.gx;
     switch (J.kind) {
-        case FFL_PYR_F1: k_pyr_fused3x4_body<1, FFL_FR1>(bx, by, bz, gray_base, gray_stride, ut, J.w, J.h, J.lw, J.lh, J.gk, J.I, J.I_stride); break;
-        case FFL_PYR_F2: k_pyr_fused3x4_body<2, FFL_FR2>(bx, by, bz, gray_base, gray_stride, ut, J.w, J.h, J.lw, J.lh, J.gk, J.I, J.I_stride); break;
+        case FFL_PYR_F1: k_pyr_fused3x4_body<1, FFL_FR1, true>(bx, by, bz, gray_base, gray_stride, ut, J.w, J.h, J.lw, J.lh, J.gk, J.I, J.I_stride); break;
+        case FFL_PYR_F2: k_pyr_fused3x4_body<2, FFL_FR2, true>(bx, by, bz, gray_base, gray_stride, ut, J.w, J.h, J.lw, J.lh, J.gk, J.I, J.I_stride); break;
         case FFL_PYR_H4: k_pyr_h2_body<4>(bx, by, bz, gray_base, gray_stride, ut, J.w, J.h, J.lw, J.sx, J.gk, J.tmp, J.tmp_stride); break;
         case FFL_PYR_H9: k_pyr_h2_body<9>(bx, by, bz, gray_base, gray_stride, ut, J.w, J.h, J.lw, J.sx, J.gk, J.tmp, J.tmp_stride); break;
         case FFL_PYR_V4: k_pyr_v2_body<4>(bx, by, bz, J.tmp, J.tmp_stride, J.w, J.h, J.lw, J.lh, J.sx, J.sy, J.gk, J.I, J.I_stride); break;
@@ -576,16 +486,42 @@ __global__ __launch_bounds__(256) void k_pyr_multi(const uint8_t *__restrict__ g
     }
 }
 
-// kind of merged job a level maps to in phase A (-1: the level needs the generic per-level kernels)
-static int ffl_pyr_kind(int w, int h, int lw, int lh, int ksize) {
+// The form a level takes and its per-frame grids, stated once: a 3-tap blur with an exact x1 / x2 decimation runs fused;
+// any other 3-tap level (level 1 of a frame with an odd width or height), and a 9- / 19-tap blur on a level that resamples
+// in x, run as an H + V pair.  The level rule of the reference yields nothing else (ksize 3, 3, 9, 19 for levels 0..3, and
+// levels 2, 3 only exist for w, h >= 128, where lw != w); ffl_create checks it where the geometry is fixed.
+struct PyrForm {
+    int kind;         // FFL_PYR_F1 / F2, the H kind of a pair (FFL_PYR_H1 / H4 / H9), or FFL_PYR_NONE
+    bool aligned;     // w and lw multiples of 4: rows start dword-aligned and every lane of a fused kernel holds 4 outputs
+    bool merged;      // k_pyr_multi takes it
+    unsigned gx, gy;  // grid of one frame: the fused kernel's, or the H pass's
+    unsigned vx, vy;  // the V pass's (0: none)
+};
+static PyrForm ffl_pyr_form(int w, int h, int lw, int lh, int ksize) {
     const int r = ksize / 2;
-    if ((w & 3) || (lw & 3)) return -1;
-    if (r == 1 && lw == w && lh == h) return FFL_PYR_F1;
-    if (r == 1 && w == 2 * lw && h == 2 * lh) return FFL_PYR_F2;
-    if (lw != w && r == 4) return FFL_PYR_H4;
-    if (lw != w && r == 9) return FFL_PYR_H9;
-    return -1;
+    PyrForm f = {};
+    f.aligned = (w & 3) == 0 && (lw & 3) == 0;
+    if (r == 1 && lw == w && lh == h) f.kind = FFL_PYR_F1;
+    else if (r == 1 && w == 2 * lw && h == 2 * lh) f.kind = FFL_PYR_F2;
+    else if (r == 1) f.kind = FFL_PYR_H1;
+    else if (lw != w && (r == 4 || r == 9)) f.kind = r == 4 ? FFL_PYR_H4 : FFL_PYR_H9;
+    else f.kind = FFL_PYR_NONE;
+    f.merged = f.aligned && f.kind != FFL_PYR_H1 && f.kind != FFL_PYR_NONE;
+    if (f.kind == FFL_PYR_F1 || f.kind == FFL_PYR_F2) {
+        const int fr = f.kind == FFL_PYR_F1 ? FFL_FR1 : FFL_FR2;
+        f.gx = ((lw + 3) / 4 + 255) / 256;
+        f.gy = (lh + fr - 1) / fr;
+    } else if (f.kind != FFL_PYR_NONE) {
+        const int rows = ffl_pyr_rows(r);
+        f.gx = (lw + 255) / 256;
+        f.gy = (h + rows - 1) / rows;
+        f.vx = (lw + 63) / 64;
+        f.vy = (lh + 3) / 4;
+    }
+    return f;
 }
+size_t ffl_pyr_tmp_floats(int w, int h, int lw) { return (size_t)h * lw * (lw != w ? 2 : 1); }
+bool ffl_pyr_level_ok(int w, int h, int lw, int lh, int ksize) { return ffl_pyr_form(w, h, lw, lh, ksize).kind != FFL_PYR_NONE; }
 
 // (running the coarse kernel on a side stream beside the fine levels was tried: 5595 vs 5606 pairs/s, not kept)
 bool ffl_launch_pyr_multi(const uint8_t *gray_base, size_t gray_stride, const UTab *__restrict__ ut, int nU, const PyrJob *lv, int n,
@@ -593,8 +529,11 @@ bool ffl_launch_pyr_multi(const uint8_t *gray_base, size_t gray_stride, const UT
     const int w = lv[0].w, h = lv[0].h;
     PyrJobs A = {}, B = {};
     unsigned ta = 0, tb = 0;
-    for (int i = 0; i < n; i++)
-        if (ffl_pyr_kind(w, h, lv[i].lw, lv[i].lh, lv[i].gk.ksize) < 0) return false;
+    PyrForm form[FFL_MAX_JOBS];
+    for (int i = 0; i < n; i++) {
+        form[i] = ffl_pyr_form(w, h, lv[i].lw, lv[i].lh, lv[i].gk.ksize);
+        if (!form[i].merged) return false;
+    }
     // the x1/8 and x1/4 levels (radius 9 and 4) in one pass over the frame where the sizes allow it
     int skip0 = -1, skip1 = -1;
     if (opt.pyr_coarse)
@@ -607,21 +546,16 @@ bool ffl_launch_pyr_multi(const uint8_t *gray_base, size_t gray_stride, const UT
             }
     for (int i = 0; i < n; i++) {
         if (i == skip0 || i == skip1) continue;
-        const int kind = ffl_pyr_kind(w, h, lv[i].lw, lv[i].lh, lv[i].gk.ksize);
+        const PyrForm &f = form[i];
         PyrJob J = lv[i];
-        J.kind = kind;
-        if (kind == FFL_PYR_F1 || kind == FFL_PYR_F2) {
-            const int fr = kind == FFL_PYR_F1 ? FFL_FR1 : FFL_FR2;
-            J.gx = (J.lw / 4 + 255) / 256;
-            J.gy = (J.lh + fr - 1) / fr;
-        } else {
-            const int rows = ffl_pyr_rows(kind == FFL_PYR_H4 ? 4 : 9);
-            J.gx = (J.lw + 255) / 256;
-            J.gy = (h + rows - 1) / rows;
+        J.kind = f.kind;
+        J.gx = f.gx;
+        J.gy = f.gy;
+        if (f.vx) {
             PyrJob V = J;
-            V.kind = kind == FFL_PYR_H4 ? FFL_PYR_V4 : FFL_PYR_V9;
-            V.gx = (J.lw + 63) / 64;
-            V.gy = (J.lh + 3) / 4;
+            V.kind = f.kind + (FFL_PYR_V4 - FFL_PYR_H4);
+            V.gx = f.vx;
+            V.gy = f.vy;
             V.first = tb;
             V.count = V.gx * V.gy * (unsigned)nU;
             tb += ffl_xcd_blocks(V.count);
@@ -637,54 +571,32 @@ bool ffl_launch_pyr_multi(const uint8_t *gray_base, size_t gray_stride, const UT
     return true;
 }
 
-// H + V kernel pair of a resampling level with blur radius R
-template <int R>
-static void ffl_launch_pyr_hv(const uint8_t *gray_base, size_t gray_stride, const UTab *ut, int nU, const PyrJob &J,
-                              hipStream_t st) {
-    dim3 gh((J.lw + 255) / 256, (J.h + ffl_pyr_rows(R) - 1) / ffl_pyr_rows(R), nU), gv((J.lw + 63) / 64, (J.lh + 3) / 4, nU);
-    hipLaunchKernelGGL(k_pyr_h2<R>, gh, dim3(256), 0, st, gray_base, gray_stride, ut, J.w, J.h, J.lw, J.sx, J.gk, J.tmp,
-                       J.tmp_stride);
-    hipLaunchKernelGGL(k_pyr_v2<R>, gv, dim3(256), 0, st, J.tmp, J.tmp_stride, J.w, J.h, J.lw, J.lh, J.sx, J.sy, J.gk, J.I,
+// one level on its own: the fused kernel of its decimation S, or the H + V kernel pair of its blur radius R
+template <int S, int FR>
+static void ffl_launch_pyr_fused(const uint8_t *gray_base, size_t gray_stride, const UTab *ut, int nU, const PyrJob &J,
+                                 const PyrForm &f, hipStream_t st) {
+    const auto kern = f.aligned ? &k_pyr_fused3x4<S, FR, true> : &k_pyr_fused3x4<S, FR, false>;
+    hipLaunchKernelGGL(kern, dim3(f.gx, f.gy, nU), dim3(256), 0, st, gray_base, gray_stride, ut, J.w, J.h, J.lw, J.lh, J.gk, J.I,
                        J.I_stride);
 }
-
-// The forms ffl_launch_pyr_level serves: a 3-tap blur, or a 9- / 19-tap blur on a level that resamples in x.  The level
-// rule of the reference yields nothing else (ksize 3, 3, 9, 19 for levels 0..3, and levels 2, 3 only exist for
-// w, h >= 128, where lw != w); ffl_create checks it where the geometry is fixed.
-bool ffl_pyr_level_ok(int w, int lw, int ksize) {
-    const int r = ksize / 2;
-    return r == 1 || ((r == 4 || r == 9) && lw != w);
+template <int R>
+static void ffl_launch_pyr_hv(const uint8_t *gray_base, size_t gray_stride, const UTab *ut, int nU, const PyrJob &J,
+                              const PyrForm &f, hipStream_t st) {
+    hipLaunchKernelGGL(k_pyr_h2<R>, dim3(f.gx, f.gy, nU), dim3(256), 0, st, gray_base, gray_stride, ut, J.w, J.h, J.lw, J.sx,
+                       J.gk, J.tmp, J.tmp_stride);
+    hipLaunchKernelGGL(k_pyr_v2<R>, dim3(f.vx, f.vy, nU), dim3(256), 0, st, J.tmp, J.tmp_stride, J.w, J.h, J.lw, J.lh, J.sx,
+                       J.sy, J.gk, J.I, J.I_stride);
 }
-
 void ffl_launch_pyr_level(const uint8_t *gray_base, size_t gray_stride, const UTab *ut, int nU, const PyrJob &J,
                           hipStream_t st) {
-    const int w = J.w, h = J.h, lw = J.lw, lh = J.lh, r = J.gk.ksize / 2;
-    const bool exact1 = lw == w && lh == h, exact2 = w == 2 * lw && h == 2 * lh;
-    if (r == 1 && (exact1 || exact2) && (lw & 3) == 0 && (w & 3) == 0) {
-        constexpr int FR1 = FFL_FR1, FR2 = FFL_FR2;  // output rows per lane
-        if (exact1) {
-            dim3 grid((lw / 4 + 255) / 256, (lh + FR1 - 1) / FR1, nU);
-            hipLaunchKernelGGL((k_pyr_fused3x4<1, FR1>), grid, dim3(256), 0, st, gray_base, gray_stride, ut, w, h, lw, lh,
-                               J.gk, J.I, J.I_stride);
-        } else {
-            dim3 grid((lw / 4 + 255) / 256, (lh + FR2 - 1) / FR2, nU);
-            hipLaunchKernelGGL((k_pyr_fused3x4<2, FR2>), grid, dim3(256), 0, st, gray_base, gray_stride, ut, w, h, lw, lh,
-                               J.gk, J.I, J.I_stride);
-        }
-    } else if (r == 1 && (exact1 || exact2)) {
-        dim3 grid((lw + 255) / 256, (lh + FFL_PYR_FROWS - 1) / FFL_PYR_FROWS, nU);
-        if (exact1)
-            hipLaunchKernelGGL(k_pyr_fused3<1>, grid, dim3(256), 0, st, gray_base, gray_stride, ut, w, h, lw, lh, J.gk, J.I,
-                               J.I_stride);
-        else
-            hipLaunchKernelGGL(k_pyr_fused3<2>, grid, dim3(256), 0, st, gray_base, gray_stride, ut, w, h, lw, lh, J.gk, J.I,
-                               J.I_stride);
-    } else if (r == 1) {  // level 1 of a frame with an odd width or height
-        ffl_launch_pyr_hv<1>(gray_base, gray_stride, ut, nU, J, st);
-    } else if (r == 4) {
-        ffl_launch_pyr_hv<4>(gray_base, gray_stride, ut, nU, J, st);
-    } else {
-        ffl_launch_pyr_hv<9>(gray_base, gray_stride, ut, nU, J, st);
+    const PyrForm f = ffl_pyr_form(J.w, J.h, J.lw, J.lh, J.gk.ksize);
+    switch (f.kind) {
+        case FFL_PYR_F1: ffl_launch_pyr_fused<1, FFL_FR1>(gray_base, gray_stride, ut, nU, J, f, st); break;
+        case FFL_PYR_F2: ffl_launch_pyr_fused<2, FFL_FR2>(gray_base, gray_stride, ut, nU, J, f, st); break;
+        case FFL_PYR_H1: ffl_launch_pyr_hv<1>(gray_base, gray_stride, ut, nU, J, f, st); break;
+        case FFL_PYR_H4: ffl_launch_pyr_hv<4>(gray_base, gray_stride, ut, nU, J, f, st); break;
+        case FFL_PYR_H9: ffl_launch_pyr_hv<9>(gray_base, gray_stride, ut, nU, J, f, st); break;
+        default: break;  // FFL_PYR_NONE: ffl_create refuses such a geometry
     }
 }
 

@@ -24,13 +24,6 @@ constexpr int BV_W = 64, BV_H = 32;  // k_fbg_blur_v: 64 x 32 outputs per workgr
 constexpr int PE_W = 64, PE_H = 16;  // k_fbg_polyexp / k_fbg_box_solve tiles
 constexpr int BS_W = 64, BS_H = 16;
 
-__device__ __forceinline__ int reflect101(int p, int n) {
-    if (n == 1) return 0;
-    while (p < 0 || p >= n) p = p < 0 ? -p : 2 * (n - 1) - p;
-    return p;
-}
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // Gaussian, horizontal pass: one row segment of BH_W outputs, its 2r-wide halo staged in LDS (REFLECT_101)
 __global__ __launch_bounds__(256) void k_fbg_blur_h(const uint8_t *gray, size_t gray_stride, const UTab *ut, int w, int h,
                                                     FbgGauss gk, float *T, size_t T_stride) {
@@ -38,7 +31,7 @@ __global__ __launch_bounds__(256) void k_fbg_blur_h(const uint8_t *gray, size_t 
     float *s = reinterpret_cast<float *>(smem);
     const int u = blockIdx.z, y = blockIdx.y, x0 = blockIdx.x * BH_W, r = gk.r;
     const uint8_t *row = gray + (size_t)ut->fslot[u] * gray_stride + (size_t)y * w;
-    for (int i = threadIdx.x; i < BH_W + 2 * r; i += blockDim.x) s[i] = (float)row[reflect101(x0 - r + i, w)];
+    for (int i = threadIdx.x; i < BH_W + 2 * r; i += blockDim.x) s[i] = (float)row[ffl_reflect101(x0 - r + i, w)];
     __syncthreads();
     const int x = x0 + threadIdx.x;
     if (x >= w) return;
@@ -56,7 +49,7 @@ __global__ __launch_bounds__(256) void k_fbg_blur_v(const float *T, size_t strid
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const int x = min(x0 + tx, w - 1);
     const float *src = T + (size_t)u * stride;
-    for (int i = ty; i < rows; i += 4) s[i * BV_W + tx] = src[(size_t)reflect101(y0 - r + i, h) * w + x];
+    for (int i = ty; i < rows; i += 4) s[i * BV_W + tx] = src[(size_t)ffl_reflect101(y0 - r + i, h) * w + x];
     __syncthreads();
     if (x0 + tx >= w) return;
     for (int t = ty; t < BV_H && y0 + t < h; t += 4) {
@@ -67,19 +60,6 @@ __global__ __launch_bounds__(256) void k_fbg_blur_v(const float *T, size_t strid
     }
 }
 
-// INTER_LINEAR coordinate rule of the oracle's resize tables, for one destination index
-__device__ __forceinline__ void fbg_resize_coord(int src, int dst, int d, int &i0, int &i1, float &f) {
-    const double scale = (double)src / dst;
-    float fx = (float)((d + 0.5) * scale - 0.5);
-    int sx = (int)floorf(fx);
-    fx -= sx;
-    if (sx < 0) { sx = 0; fx = 0.f; }
-    if (sx >= src - 1) { sx = src - 1; fx = 0.f; }
-    i0 = sx;
-    i1 = sx + 1 < src ? sx + 1 : src - 1;
-    f = fx;
-}
-
 // blurred full-resolution frame -> level image (lw x lh)
 __global__ __launch_bounds__(64) void k_fbg_resize(const float *B, size_t B_stride, int w, int h, float *I, size_t I_stride,
                                                    int lw, int lh) {
@@ -87,8 +67,8 @@ __global__ __launch_bounds__(64) void k_fbg_resize(const float *B, size_t B_stri
     if (x >= lw) return;
     int x0, x1, y0, y1;
     float a1, b1;
-    fbg_resize_coord(w, lw, x, x0, x1, a1);
-    fbg_resize_coord(h, lh, y, y0, y1, b1);
+    ffl_resize_coord(x, w, (double)w / lw, x0, x1, a1);
+    ffl_resize_coord(y, h, (double)h / lh, y0, y1, b1);
     const float *r0 = B + (size_t)u * B_stride + (size_t)y0 * w, *r1 = B + (size_t)u * B_stride + (size_t)y1 * w;
     const float a0 = 1.f - a1, b0 = 1.f - b1;
     const float t0 = r0[x0] * a0 + r0[x1] * a1;
@@ -108,7 +88,7 @@ __global__ __launch_bounds__(256) void k_fbg_polyexp(const float *I, size_t I_st
     const float *src = I + (size_t)u * I_stride;
     for (int i = threadIdx.x; i < TW * TH; i += blockDim.x) {
         const int ty = i / TW, tx = i - ty * TW;
-        sI[ty][tx] = src[(size_t)clampi(y0 - N + ty, 0, h - 1) * w + clampi(x0 - N + tx, 0, w - 1)];
+        sI[ty][tx] = src[(size_t)ffl_clampi(y0 - N + ty, 0, h - 1) * w + ffl_clampi(x0 - N + tx, 0, w - 1)];
     }
     __syncthreads();
     for (int i = threadIdx.x; i < TW * PE_H; i += blockDim.x) {
@@ -177,8 +157,8 @@ __global__ __launch_bounds__(64) void k_fbg_flow_init(const PairTab *pt, const f
     }
     int x0, x1, y0, y1;
     float a1, b1;
-    fbg_resize_coord(pw, lw, x, x0, x1, a1);
-    fbg_resize_coord(ph, lh, y, y0, y1, b1);
+    ffl_resize_coord(x, pw, (double)pw / lw, x0, x1, a1);
+    ffl_resize_coord(y, ph, (double)ph / lh, y0, y1, b1);
     const float *p = prev + (size_t)b * stride;
     const float *r0 = p + (size_t)y0 * pw * 2, *r1 = p + (size_t)y1 * pw * 2;
     const float a0 = 1.f - a1, b0 = 1.f - b1;
@@ -251,7 +231,7 @@ __global__ __launch_bounds__(256) void k_fbg_box_solve(const PairTab *pt, const 
         __syncthreads();  // the previous channel's row sums are done with sV / sM
         for (int i = threadIdx.x; i < TW * TH; i += blockDim.x) {
             const int r = i / TW, cc = i - r * TW;
-            sM[i] = src[(size_t)clampi(y0 - m + r, 0, h - 1) * w + clampi(x0 - m + cc, 0, w - 1)];
+            sM[i] = src[(size_t)ffl_clampi(y0 - m + r, 0, h - 1) * w + ffl_clampi(x0 - m + cc, 0, w - 1)];
         }
         __syncthreads();
         for (int i = threadIdx.x; i < TW * BS_H; i += blockDim.x) {
@@ -309,7 +289,7 @@ __global__ __launch_bounds__(256) void k_fbg_gauss_solve(const PairTab *pt, cons
         __syncthreads();  // the previous channel's horizontal sums are done with sV / sM
         for (int i = threadIdx.x; i < TW * TH; i += blockDim.x) {
             const int r = i / TW, cc = i - r * TW;
-            sM[i] = src[(size_t)clampi(y0 - m + r, 0, h - 1) * w + clampi(x0 - m + cc, 0, w - 1)];
+            sM[i] = src[(size_t)ffl_clampi(y0 - m + r, 0, h - 1) * w + ffl_clampi(x0 - m + cc, 0, w - 1)];
         }
         __syncthreads();
         for (int i = threadIdx.x; i < TW * BS_H; i += blockDim.x) {
@@ -374,7 +354,7 @@ __device__ __forceinline__ void fbg_area_entry(const FbgAreaAxis &a, int e, int 
         idx = a.s2;
         alpha = a.ar;
     }
-    idx = clampi(idx, 0, S - 1);  // the rule keeps every index inside; this keeps the read inside whatever the rule gives
+    idx = ffl_clampi(idx, 0, S - 1);  // the rule keeps every index inside; this keeps the read inside whatever the rule gives
 }
 
 // F.8: the coarsest level's initial flow from the pair's full-resolution flow slot: resize(seed, lw x lh, INTER_AREA) *

@@ -195,7 +195,7 @@ def test_errors_are_loud():
         _capi.Context(8, 8)
 
 
-@pytest.mark.parametrize("w,h", [(16, 16), (17, 19), (31, 64), (64, 33), (65, 17), (127, 129), (130, 66), (20, 300), (300, 20)])
+@pytest.mark.parametrize("w,h", [(16, 16), (17, 19), (31, 64), (64, 33), (65, 17), (127, 129), (130, 66), (132, 68), (20, 300), (300, 20)])
 def test_small_and_awkward_sizes_bit_exact(w, h):
     """Sizes below one 64x16 tile, not multiples of 4 / 16 / 64, and extreme aspect ratios: every kernel's edge
     paths (clamped rows, partial tiles and strips, byte-wise pyramid taps, 1-strip reductions)."""
@@ -257,11 +257,14 @@ def test_strip_walk_bit_exact(rows, fuse):
         _capi.set_option("fuse_first", 10000)
 
 
-@pytest.mark.parametrize("w,h", [(256, 256), (392, 264), (640, 360), (1920, 1080)])
+@pytest.mark.parametrize("w,h", [(256, 256), (288, 264), (392, 264), (640, 360), (1920, 1080)])
 def test_one_pass_coarse_pyramid_levels_bit_exact(w, h):
     """k_pyr_coarse (x1/4 and x1/8 levels from one LDS-staged pass over the frame; sizes with w, h multiples of 8):
     level images of both frames against the oracle's pyr_level, incl. tiles cut by the right / bottom border and
-    the REFLECT_101 halo of every edge tile; the H + V kernel pairs (pyr_coarse = 0) give the same bits."""
+    the REFLECT_101 halo of every edge tile; the H + V kernel pairs (pyr_coarse = 0) give the same bits.
+    k_pyr_coarse only runs inside the merged launch, i.e. when every level's width is a multiple of 4 (w % 32 == 0):
+    (288, 264) is the smallest such frame with tiles cut on the right and at the bottom; (392, 264), whose x1/4 level is
+    98 wide, runs the H + V pairs under both settings."""
     fr = frames(2, w, h, seed=w + 3 * h, amp=(3.0, 2.0), period=6)
     got = {}
     try:
@@ -282,9 +285,12 @@ def test_one_pass_coarse_pyramid_levels_bit_exact(w, h):
 
 # ------------------------------------------------------------------ per-level launchers under every schedule
 # (258, 257): w % 4 != 0, so the merged pyramid launch refuses and every level is launched on its own -- level 0 by the
-# pixel-per-lane fused kernel, level 1 (129 x 128, h odd: inexact) by the R = 1 H + V pair, levels 2 and 3 (64 x 64,
-# 32 x 32) by the R = 4 / R = 9 pairs with byte-wise taps; the smallest shape with all four levels.  (130, 66): two levels.
-AWKWARD_SIZES = [(258, 257), (130, 66)]
+# unaligned x1 instantiation of the fused kernel (byte-wise taps, a two-pixel tail lane), level 1 (129 x 128, h odd:
+# inexact) by the R = 1 H + V pair, levels 2 and 3 (64 x 64, 32 x 32) by the R = 4 / R = 9 pairs with byte-wise taps; the
+# smallest shape with all four levels.  (130, 66): two levels, both unaligned with byte-wise taps.  (132, 68): w % 4 == 0
+# but lw = 66 is not -- level 0 by the aligned x1 instantiation, level 1 by the unaligned x2 one with the word-wise
+# fetch and a two-pixel tail lane whose taps pass the row's end.
+AWKWARD_SIZES = [(258, 257), (130, 66), (132, 68)]
 SCHEDULES = {"default": {}, "merge_expand=0": {"merge_expand": 0}, "run_ahead=1": {"run_ahead": 1},
              "run_ahead=2": {"run_ahead": 2}}
 _awkward_cache = {}
@@ -321,15 +327,16 @@ def test_per_level_launches_every_schedule_bit_exact(w, h, sched):
 
 
 def test_per_level_pyramid_images_bit_exact():
-    """(258, 257), default options: the level images of both frames equal the oracle's pyr_level at every level."""
-    w, h = AWKWARD_SIZES[0]
-    fr, _ = awkward_case(w, h)
-    with _capi.Context(w, h, max_batch=1) as ctx:
-        ctx.upload_frame(0, fr[0])
-        ctx.upload_frame(1, fr[1])
-        assert ctx.num_levels() == 3
-        got = {lvl: ctx.debug_pair(0, 1, lvl, 0) for lvl in range(4)}
-    for lvl in range(4):
-        for key, f in (("I0", fr[0]), ("I1", fr[1])):
-            want = orc.pyr_level(f, lvl)
-            assert np.array_equal(got[lvl][key], want), (lvl, key, np.abs(got[lvl][key] - want).max())
+    """(258, 257) and (132, 68), default options: the level images of both frames equal the oracle's pyr_level at every
+    level."""
+    for (w, h), levels in ((AWKWARD_SIZES[0], 3), (AWKWARD_SIZES[2], 1)):
+        fr, _ = awkward_case(w, h)
+        with _capi.Context(w, h, max_batch=1) as ctx:
+            ctx.upload_frame(0, fr[0])
+            ctx.upload_frame(1, fr[1])
+            assert ctx.num_levels() == levels
+            got = {lvl: ctx.debug_pair(0, 1, lvl, 0) for lvl in range(levels + 1)}
+        for lvl in range(levels + 1):
+            for key, f in (("I0", fr[0]), ("I1", fr[1])):
+                want = orc.pyr_level(f, lvl)
+                assert np.array_equal(got[lvl][key], want), (w, h, lvl, key, np.abs(got[lvl][key] - want).max())
