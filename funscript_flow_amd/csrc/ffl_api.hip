@@ -1397,14 +1397,19 @@ static int enqueue_batch(ffl_ctx *c, ffl_ctx::Lane &L, const BatchTab &T, int n,
     if (mode == 0 && c->opt.merge_expand) {
         // serial schedule, merged form: the frame-only work of ALL levels up front in three launches
         // (pyramid phase A + B, PolyExp) instead of ten small ones whose ramps and tails leave the device idle
+        // fuse_l0_blur: PolyExp forms level 0's image (the last job) from the gray frame, so nothing reads that level's I
+        // plane but the debug capture, and the pyramid leaves the level out unless one is running
+        const PyrJob *l0 = &L.pyr[L.n_jobs - 1];
+        const bool fuse_l0 = c->opt.fuse_l0_blur && ffl_polyexp_from_gray_ok(*l0);
+        const int skip_l0 = fuse_l0 && !cap;
         {
             ProfScope ps(c, FFL_K_PYRAMID, st);
-            if (!ffl_launch_pyr_multi(c->d_gray, N, ut, nU, L.pyr, L.n_jobs, c->opt, st))
-                for (int k = c->geo.levels; k >= 0; k--) pyr_level(k, st);  // a level outside the merged kinds: per-level kernels
+            if (!ffl_launch_pyr_multi(c->d_gray, N, ut, nU, L.pyr, L.n_jobs - skip_l0, c->opt, st))
+                for (int k = c->geo.levels; k >= skip_l0; k--) pyr_level(k, st);  // a level outside the merged kinds: per-level kernels
         }
         {
             ProfScope ps(c, FFL_K_POLYEXP, st);
-            ffl_launch_polyexp_multi(L.poly, L.n_jobs, nU, c->pc, st);
+            ffl_launch_polyexp_multi(L.poly, L.n_jobs, nU, c->pc, c->d_gray, N, ut, fuse_l0 ? l0 : nullptr, st);
         }
         expanded = true;
     }

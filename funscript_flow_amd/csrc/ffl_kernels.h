@@ -119,6 +119,8 @@ struct PolyJob {  // one level of PolyExp (caller fills I, I_stride, R, R_stride
     size_t I_stride, R_stride, plane;
     int w, h;
     unsigned gx, gy, first, count;
+    int from_gray;   // the image is formed from the gray frame (level 0's 3-tap blur, taps gk0 / gk1) instead of read from I
+    float gk0, gk1;
 };
 struct PolyJobs {
     PolyJob j[FFL_MAX_JOBS];
@@ -139,6 +141,7 @@ struct FflOptions {
     int blur_min_wgs = 3500; // automatic strip length: the longest strips that still give this many workgroups
     int tile_order = 0;     // 0 pair-major, 1 tile-major (ffl_tile_coord)
     int pyr_coarse = 1;     // one-pass kernel for the x1/4 and x1/8 pyramid levels where sizes allow
+    int fuse_l0_blur = 1;   // merged expansion: PolyExp forms level 0's image from the gray frame itself; its I plane is not written
     int fb_general = 0;     // 1: ffl_flow_pairs_farneback runs the reference's parameters through the general kernels too
     int import_fused = 1;   // ffl_import_flows: 1 k_import_pass1 (conversion + pass 1 in one read), 0 conversion, then pass 1
 };
@@ -161,6 +164,7 @@ inline constexpr FflOptionRow kFflOptionRows[] = {
     {"blur_min_wgs", &FflOptions::blur_min_wgs, 1, INT_MAX, false},
     {"tile_order", &FflOptions::tile_order, 0, 1, false},
     {"pyr_coarse", &FflOptions::pyr_coarse, INT_MIN, INT_MAX, true},
+    {"fuse_l0_blur", &FflOptions::fuse_l0_blur, INT_MIN, INT_MAX, true},
     {"fb_general", &FflOptions::fb_general, 0, 1, false},
     {"import_fused", &FflOptions::import_fused, 0, 1, false},
 };
@@ -169,7 +173,10 @@ inline constexpr FflOptionRow kFflOptionRows[] = {
 // all pyramid levels in two launches; false (nothing launched) when a level needs the generic kernels
 bool ffl_launch_pyr_multi(const uint8_t *gray_base, size_t gray_stride, const UTab *ut, int nU, const PyrJob *levels, int n,
                           const FflOptions &opt, hipStream_t st);
-void ffl_launch_polyexp_multi(const PolyJob *levels, int n, int nU, PolyConsts pc, hipStream_t st);
+// l0 != nullptr: the last level is level 0 and is formed from the gray frames (ffl_polyexp_from_gray_ok(*l0) must hold)
+bool ffl_polyexp_from_gray_ok(const PyrJob &l0);
+void ffl_launch_polyexp_multi(const PolyJob *levels, int n, int nU, PolyConsts pc, const uint8_t *gray_base, size_t gray_stride,
+                              const UTab *ut, const PyrJob *l0, hipStream_t st);
 // host paths: one frame, its descriptor a kernel argument; device path: n frames, descriptors tab[0..n) in device memory
 void ffl_launch_frontend(const FrameDesc &d, uint8_t *gray, const FrontParams &p, hipStream_t st);
 void ffl_launch_frontend_dev(const FrameDesc *tab, int n, uint8_t *gray_base, size_t N, const FrontParams &p, hipStream_t st);

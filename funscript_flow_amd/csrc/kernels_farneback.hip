@@ -10,7 +10,8 @@
 //                              for the x1/4 and x1/8 levels together (k_pyr_coarse), H + V kernel pairs for
 //                              geometries those do not cover; ffl_pyr_form states which form a level takes
 //   k_polyexp       VALU(f64)  24  (4 in, 20 out), 11x11 separable through LDS, f64 accumulators, 4 pixels per
-//                              lane; all levels in one merged launch (k_polyexp_multi)
+//                              lane; all levels in one merged launch (k_polyexp_multi), in which level 0's image is
+//                              formed from the gray frame by the tile loader: 1 in instead of 4, and no level-0 I plane
 //   k_update_mat    HBM        68  (R0 20 + R1 gather 20 + flow 8 -> M 20); also forms the level's
 //                              initial flow (x2 upsample of the coarser level, used from registers)
 //   k_blur_solve    HBM        28  (M 20 -> flow 8) [+68 when the next UpdateMatrices is fused; on large
@@ -83,6 +84,32 @@ __device__ __forceinline__ void ffl_resize_coord_half(int d, int src, int &i0, i
 // per-sample form with reflected taps.
 // rows per lane of k_pyr_h2: enough loads in flight to cover the memory latency without spilling
 constexpr int ffl_pyr_rows(int R) { return R == 1 ? 16 : (R == 4 ? 8 : 4); }
+
+// The 3-tap blur of the exact x1 / x2 levels, stated once: k_pyr_fused3x4_body and PolyExp's level-0 tile loader form the
+// same bits from it.  One pass of the separable blur in symmetric form (k0 the centre tap, m / p the two neighbours), and
+// level 0's two identity lerps as k_pyr_v2 evaluates them.
+__device__ __forceinline__ float ffl_blur3(float m, float c, float p, float k0, float k1) { return k0 * c + k1 * (m + p); }
+__device__ __forceinline__ float ffl_lerp_identity(float v) { return (v * 1.f + 0.f * 0.f) * 1.f + 0.f * 0.f; }
+
+// Sixteen gray bytes of a row from column X on as four words, REFLECT_101 outside the row.  `words`: rows start dword-aligned
+// and X and w are multiples of 4, so a dword is either inside the row or entirely outside; otherwise byte by byte.
+__device__ __forceinline__ void ffl_gray16_reflect101(const uint8_t *__restrict__ row, int X, int w, bool words, uint32_t (&v)[4]) {
+    struct __attribute__((packed, aligned(4))) u4 { uint32_t a, b, c, d; };
+    if (words && X >= 0 && X + 15 < w) {
+        const u4 t4 = *reinterpret_cast<const u4 *>(row + X);
+        v[0] = t4.a; v[1] = t4.b; v[2] = t4.c; v[3] = t4.d;
+    } else {
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const int Xc = X + 4 * c;
+            if (words && Xc >= 0 && Xc + 3 < w)
+                v[c] = *reinterpret_cast<const uint32_t *>(row + Xc);
+            else
+                v[c] = (uint32_t)row[ffl_reflect101(Xc, w)] | ((uint32_t)row[ffl_reflect101(Xc + 1, w)] << 8) |
+                       ((uint32_t)row[ffl_reflect101(Xc + 2, w)] << 16) | ((uint32_t)row[ffl_reflect101(Xc + 3, w)] << 24);
+        }
+    }
+}
 template <int R>
 __device__ __forceinline__ void k_pyr_h2_body(const unsigned bx, const unsigned by, const unsigned bz, const uint8_t *__restrict__ gray_base, size_t gray_stride, const UTab *__restrict__ ut, int w,
                                                 int h, int lw, double sx, GaussKernel gk, float *__restrict__ tmp,
@@ -266,7 +293,7 @@ __device__ __forceinline__ void k_pyr_fused3x4_body(const unsigned bx, const uns
             for (int t = 0; t < NBY; t++) b[t] = (float)row[ffl_reflect101(cx - 1 + t, w)];
         }
 #pragma unroll
-        for (int c = 0; c < 4 * S; c++) H[j][c] = k0 * b[c + 1] + k1 * (b[c] + b[c + 2]);
+        for (int c = 0; c < 4 * S; c++) H[j][c] = ffl_blur3(b[c], b[c + 1], b[c + 2], k0, k1);
     }
 #pragma unroll
     for (int o = 0; o < FR; o++) {
@@ -277,13 +304,12 @@ __device__ __forceinline__ void k_pyr_fused3x4_body(const unsigned bx, const uns
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             if (S == 1) {
-                const float v00 = k0 * H[c][i] + k1 * (H[c - 1][i] + H[c + 1][i]);
-                out[i] = (v00 * 1.f + 0.f * 0.f) * 1.f + 0.f * 0.f;
+                out[i] = ffl_lerp_identity(ffl_blur3(H[c - 1][i], H[c][i], H[c + 1][i], k0, k1));
             } else {
-                const float v00 = k0 * H[c][2 * i] + k1 * (H[c - 1][2 * i] + H[c + 1][2 * i]);
-                const float v01 = k0 * H[c][2 * i + 1] + k1 * (H[c - 1][2 * i + 1] + H[c + 1][2 * i + 1]);
-                const float v10 = k0 * H[c + 1][2 * i] + k1 * (H[c][2 * i] + H[c + 2][2 * i]);
-                const float v11 = k0 * H[c + 1][2 * i + 1] + k1 * (H[c][2 * i + 1] + H[c + 2][2 * i + 1]);
+                const float v00 = ffl_blur3(H[c - 1][2 * i], H[c][2 * i], H[c + 1][2 * i], k0, k1);
+                const float v01 = ffl_blur3(H[c - 1][2 * i + 1], H[c][2 * i + 1], H[c + 1][2 * i + 1], k0, k1);
+                const float v10 = ffl_blur3(H[c][2 * i], H[c + 1][2 * i], H[c + 2][2 * i], k0, k1);
+                const float v11 = ffl_blur3(H[c][2 * i + 1], H[c + 1][2 * i + 1], H[c + 2][2 * i + 1], k0, k1);
                 const float t0 = v00 * 0.5f + v01 * 0.5f, t1 = v10 * 0.5f + v11 * 0.5f;
                 out[i] = t0 * 0.5f + t1 * 0.5f;
             }
@@ -413,7 +439,6 @@ __global__ __launch_bounds__(256) void k_pyr_coarse(const uint8_t *__restrict__ 
     // ---- stage the tile: 16 bytes per lane and load (the row segment X0-8 .. X0+135 is 9 such pieces), fixed trip
     // count so that all loads of a lane are in flight together
     constexpr int PCQ = PC_PW / 4, NLOAD = (PC_PH * PCQ + 255) / 256;
-    struct __attribute__((packed, aligned(4))) u4 { uint32_t a, b, c, d; };
 #pragma unroll
     for (int k = 0; k < NLOAD; k++) {
         const int i = tid + 256 * k;
@@ -422,20 +447,7 @@ __global__ __launch_bounds__(256) void k_pyr_coarse(const uint8_t *__restrict__ 
             const int gy = ffl_reflect101(Y0 - 6 + ry, h), X = X0 - 8 + 16 * q;
             const uint8_t *row = img + (size_t)gy * w;
             uint32_t v[4];
-            if (X >= 0 && X + 15 < w) {
-                const u4 t4 = *reinterpret_cast<const u4 *>(row + X);
-                v[0] = t4.a; v[1] = t4.b; v[2] = t4.c; v[3] = t4.d;
-            } else {
-#pragma unroll
-                for (int c = 0; c < 4; c++) {
-                    const int Xc = X + 4 * c;
-                    if (Xc >= 0 && Xc + 3 < w)  // w % 4 == 0: a dword is either inside the row or entirely outside
-                        v[c] = *reinterpret_cast<const uint32_t *>(row + Xc);
-                    else
-                        v[c] = (uint32_t)row[ffl_reflect101(Xc, w)] | ((uint32_t)row[ffl_reflect101(Xc + 1, w)] << 8) |
-                               ((uint32_t)row[ffl_reflect101(Xc + 2, w)] << 16) | ((uint32_t)row[ffl_reflect101(Xc + 3, w)] << 24);
-                }
-            }
+            ffl_gray16_reflect101(row, X, w, true, v);  // w % 8 == 0
             *reinterpret_cast<uint2 *>(&sP[ry][4 * q]) = make_uint2(v[0], v[1]);
             *reinterpret_cast<uint2 *>(&sP[ry][4 * q + 2]) = make_uint2(v[2], v[3]);
         }
@@ -618,8 +630,18 @@ void ffl_launch_pyr_level(const uint8_t *gray_base, size_t gray_stride, const UT
 // f64 accumulators, LDS reads), not by memory: with four pixels per lane the 14 taps a lane needs per plane come with
 // four LDS reads (3 x 16 B + 8 B) instead of the 22 dword reads two pixels needed, the tile comes in with 16-byte
 // global loads, and results leave with 16-byte stores.  Per pixel the operations and their order are unchanged.
+//
+// Level 0's image is no resample: it is the 3-tap blur of the gray frame (k_pyr_fused3x4<1, ...>).  With gimg != nullptr
+// the tile is formed from the frame itself instead of being read from the I plane, which then is neither written nor
+// read: the u8 tile (+ one more pixel of halo for the blur's taps, REFLECT_101) is staged with 16-byte loads, blurred
+// horizontally into LDS and vertically into sI, at exactly the image positions the plain loader reads -- PolyExp's
+// REPLICATE clamp picks the position, the blur's reflection its taps.  Both stagings live in sV, which is dead until the
+// vertical part.  gk0 / gk1: the blur's centre and side tap.
+#define PE_UH (PE_TH + 2 * PE_N + 2)          // 28 staged u8 rows: y0-6 .. y0+21
+#define PE_UW (PE_LQ + 1)                     // 20 dwords: columns x0-8 .. x0+71 (tile column lx is byte lx + 3)
 __device__ __forceinline__ void k_polyexp_body(const unsigned bx, const unsigned by, const unsigned bz, const float *__restrict__ I, size_t I_stride, float *__restrict__ R,
-                                                 size_t R_stride, size_t plane, int w, int h, PolyConsts pc) {
+                                                 size_t R_stride, size_t plane, int w, int h, PolyConsts pc,
+                                                 const uint8_t *__restrict__ gimg = nullptr, float gk0 = 0.f, float gk1 = 0.f) {
     __shared__ __attribute__((aligned(16))) float sI[PE_TH + 2 * PE_N][PE_PITCH];
     __shared__ __attribute__((aligned(16))) float sV[3][PE_TH][PE_PITCH];
     const int tid = threadIdx.x;
@@ -630,22 +652,79 @@ __device__ __forceinline__ void k_polyexp_body(const unsigned bx, const unsigned
     // fixed trip counts (+ a bounds predicate) so that the loops unroll: a rolled loop issues one
     // global load, waits for it, stores it to LDS, and only then issues the next
     constexpr int N_IN = (PE_TH + 2 * PE_N) * PE_LQ, N_V = PE_TH * PE_LQ;
+    if (gimg) {
+        static_assert(PE_TW % 8 == 0 && PE_UW % 4 == 0 && 4 * PE_UW >= PE_PITCH + 4, "u8 tile: 16-byte pieces from x0 - 8 on");
+        static_assert(sizeof(uint32_t) * PE_UH * PE_UW <= sizeof(sV[0]) && sizeof(float) * PE_UH * PE_PITCH <= 2 * sizeof(sV[0]),
+                      "the u8 tile and its horizontal blur fit the dead sV");
+        uint32_t (*sU)[PE_UW] = reinterpret_cast<uint32_t (*)[PE_UW]>(&sV[0][0][0]);
+        float (*sH)[PE_PITCH] = reinterpret_cast<float (*)[PE_PITCH]>(&sV[1][0][0]);
+        const bool words = (w & 3) == 0;
+        if (tid < PE_UH * (PE_UW / 4)) {
+            const int r = tid / (PE_UW / 4), q = tid - r * (PE_UW / 4);
+            uint32_t v[4];
+            ffl_gray16_reflect101(gimg + (size_t)ffl_reflect101(y0 - PE_N - 1 + r, h) * w, x0 - 8 + 16 * q, w, words, v);
+            *reinterpret_cast<uint4 *>(&sU[r][4 * q]) = make_uint4(v[0], v[1], v[2], v[3]);
+        }
+        __syncthreads();
+        // horizontal blur of every staged row at the tile's (clamped) columns; tile column lx is byte lx + 3 of a staged row
+        constexpr int N_H = PE_UH * PE_LQ;
 #pragma unroll
-    for (int it = 0; it < (N_IN + 255) / 256; it++) {
-        const int i = tid + 256 * it;
-        if (i < N_IN) {
-            const int ly = i / PE_LQ, lx = 4 * (i - ly * PE_LQ);
-            const int gy = min(max(y0 + ly - PE_N, 0), h - 1), gx = x0 + lx - PE_N;
-            const float *row = img + (size_t)gy * w;
-            float4 t;
-            if (gx >= 0 && gx + 3 < w) {
-                const ffl_f4u q = *reinterpret_cast<const ffl_f4u *>(row + gx);
-                t = make_float4(q.x, q.y, q.z, q.w);
-            } else {  // REPLICATE border
-                t = make_float4(row[min(max(gx, 0), w - 1)], row[min(max(gx + 1, 0), w - 1)],
-                                row[min(max(gx + 2, 0), w - 1)], row[min(max(gx + 3, 0), w - 1)]);
+        for (int it = 0; it < (N_H + 255) / 256; it++) {
+            const int i = tid + 256 * it;
+            if (i < N_H) {
+                const int r = i / PE_LQ, lx = 4 * (i - r * PE_LQ), gx = x0 + lx - PE_N;
+                float b[4];
+                if (gx >= 0 && gx + 3 < w) {  // bytes lx+2 .. lx+7: the last two of one word and the next word
+                    const uint32_t d0 = sU[r][lx / 4], d1 = sU[r][lx / 4 + 1];
+                    const float t[6] = {(float)((d0 >> 16) & 255u), (float)(d0 >> 24), (float)(d1 & 255u),
+                                        (float)((d1 >> 8) & 255u), (float)((d1 >> 16) & 255u), (float)(d1 >> 24)};
+#pragma unroll
+                    for (int e = 0; e < 4; e++) b[e] = ffl_blur3(t[e], t[e + 1], t[e + 2], gk0, gk1);
+                } else {  // REPLICATE border
+                    const uint8_t *ub = reinterpret_cast<const uint8_t *>(sU[r]);
+#pragma unroll
+                    for (int e = 0; e < 4; e++) {
+                        const int c = min(max(gx + e, 0), w - 1) - (x0 - 8);
+                        b[e] = ffl_blur3((float)ub[c - 1], (float)ub[c], (float)ub[c + 1], gk0, gk1);
+                    }
+                }
+                *reinterpret_cast<float4 *>(&sH[r][lx]) = make_float4(b[0], b[1], b[2], b[3]);
             }
-            *reinterpret_cast<float4 *>(&sI[ly][lx]) = t;
+        }
+        __syncthreads();
+        // vertical blur at the tile's (clamped) rows: image row gy is staged row gy - (y0 - 6)
+#pragma unroll
+        for (int it = 0; it < (N_IN + 255) / 256; it++) {
+            const int i = tid + 256 * it;
+            if (i < N_IN) {
+                const int ly = i / PE_LQ, lx = 4 * (i - ly * PE_LQ);
+                const int r = min(max(y0 + ly - PE_N, 0), h - 1) - (y0 - PE_N - 1);
+                const float4 m = *reinterpret_cast<const float4 *>(&sH[r - 1][lx]);
+                const float4 c = *reinterpret_cast<const float4 *>(&sH[r][lx]);
+                const float4 p = *reinterpret_cast<const float4 *>(&sH[r + 1][lx]);
+                *reinterpret_cast<float4 *>(&sI[ly][lx]) =
+                    make_float4(ffl_lerp_identity(ffl_blur3(m.x, c.x, p.x, gk0, gk1)), ffl_lerp_identity(ffl_blur3(m.y, c.y, p.y, gk0, gk1)),
+                                ffl_lerp_identity(ffl_blur3(m.z, c.z, p.z, gk0, gk1)), ffl_lerp_identity(ffl_blur3(m.w, c.w, p.w, gk0, gk1)));
+            }
+        }
+    } else {
+#pragma unroll
+        for (int it = 0; it < (N_IN + 255) / 256; it++) {
+            const int i = tid + 256 * it;
+            if (i < N_IN) {
+                const int ly = i / PE_LQ, lx = 4 * (i - ly * PE_LQ);
+                const int gy = min(max(y0 + ly - PE_N, 0), h - 1), gx = x0 + lx - PE_N;
+                const float *row = img + (size_t)gy * w;
+                float4 t;
+                if (gx >= 0 && gx + 3 < w) {
+                    const ffl_f4u q = *reinterpret_cast<const ffl_f4u *>(row + gx);
+                    t = make_float4(q.x, q.y, q.z, q.w);
+                } else {  // REPLICATE border
+                    t = make_float4(row[min(max(gx, 0), w - 1)], row[min(max(gx + 1, 0), w - 1)],
+                                    row[min(max(gx + 2, 0), w - 1)], row[min(max(gx + 3, 0), w - 1)]);
+                }
+                *reinterpret_cast<float4 *>(&sI[ly][lx]) = t;
+            }
         }
     }
     __syncthreads();
@@ -759,7 +838,9 @@ __global__ __launch_bounds__(256) void k_polyexp(const float *__restrict__ I, si
 
 // All levels' PolyExp in ONE launch (a 1-D grid cut into per-level ranges): the coarse levels' small grids
 // run inside the level-0 launch instead of paying a launch ramp and tail each.
-__global__ __launch_bounds__(256) void k_polyexp_multi(PolyJobs jobs, PolyConsts pc) {
+// A job with from_gray forms its image from the gray frames (level 0: k_polyexp_body).
+__global__ __launch_bounds__(256) void k_polyexp_multi(PolyJobs jobs, PolyConsts pc, const uint8_t *__restrict__ gray_base,
+                                                       size_t gray_stride, const UTab *__restrict__ ut) {
     int i = 0;
 #pragma unroll
     for (int t = 1; t < FFL_MAX_JOBS; t++)
@@ -773,10 +854,15 @@ __global__ __launch_bounds__(256) void k_polyexp_multi(PolyJobs jobs, PolyConsts
     if (t >= J.count) return;
     const unsigned per = J.gx * J.gy;
     const unsigned bz = t / per, r = t - bz * per, by = r / J.gx, bx = r - by * J.gx;
-    k_polyexp_body(bx, by, bz, J.I, J.I_stride, J.R, J.R_stride, J.plane, J.w, J.h, pc);
+    const uint8_t *gimg = J.from_gray ? gray_base + (size_t)ut->fslot[bz] * gray_stride : nullptr;
+    k_polyexp_body(bx, by, bz, J.I, J.I_stride, J.R, J.R_stride, J.plane, J.w, J.h, pc, gimg, J.gk0, J.gk1);
 }
 
-void ffl_launch_polyexp_multi(const PolyJob *jobs_in, int n, int nU, PolyConsts pc, hipStream_t st) {
+// true when level l0 is what PolyExp's own loader forms: the 3-tap blur of the frame at full size
+bool ffl_polyexp_from_gray_ok(const PyrJob &l0) { return ffl_pyr_form(l0.w, l0.h, l0.lw, l0.lh, l0.gk.ksize).kind == FFL_PYR_F1; }
+
+void ffl_launch_polyexp_multi(const PolyJob *jobs_in, int n, int nU, PolyConsts pc, const uint8_t *gray_base, size_t gray_stride,
+                              const UTab *ut, const PyrJob *l0, hipStream_t st) {
     PolyJobs jobs = {};
     unsigned total = 0;
     for (int i = 0; i < n; i++) {
@@ -788,7 +874,12 @@ void ffl_launch_polyexp_multi(const PolyJob *jobs_in, int n, int nU, PolyConsts 
         total += jobs.j[i].count;
     }
     jobs.n = n;
-    hipLaunchKernelGGL(k_polyexp_multi, dim3(total), dim3(256), 0, st, jobs, pc);
+    if (l0) {  // the last job is level 0
+        jobs.j[n - 1].from_gray = 1;
+        jobs.j[n - 1].gk0 = l0->gk.k[1];
+        jobs.j[n - 1].gk1 = l0->gk.k[2];
+    }
+    hipLaunchKernelGGL(k_polyexp_multi, dim3(total), dim3(256), 0, st, jobs, pc, gray_base, gray_stride, ut);
 }
 
 void ffl_launch_polyexp(const PolyJob &J, int nU, PolyConsts pc, hipStream_t st) {

@@ -509,6 +509,9 @@ int ffl_debug_pair(ffl_ctx *ctx, int f0, int f1, int level, int iter, float *I0,
  *                            capture always launch one by one)
  *   "pyr_coarse"  = 0|1      1 (default): the x1/4 and x1/8 pyramid levels of frames whose sides are multiples of 8
  *                            come from one LDS-staged pass (k_pyr_coarse); 0: horizontal + vertical kernel pairs
+ *   "fuse_l0_blur" = 0|1     1 (default): in the merged expansion PolyExp forms level 0's image (the 3-tap blur of the
+ *                            gray frame) in its own tile loader and the level-0 image plane is neither written nor
+ *                            read; 0: the pyramid launch writes it (the debug capture always does)
  *   "tile_order"  = 0|1      k_blur_solve / k_update_matrices workgroup order: 0 pair-major (default), 1 tile-major
  *                            (every tile for all pairs of the batch back to back; less fabric traffic, not faster)
  *   "fb_general"  = 0|1      1: ffl_flow_pairs_farneback runs the default parameters through the general kernels as well
