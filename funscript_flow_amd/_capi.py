@@ -27,13 +27,20 @@ EXPORTS = ["ffl_device_count", "ffl_create", "ffl_destroy", "ffl_last_error", "f
            "ffl_upload_frames_yuv", "ffl_frontend_yuv_window",
            "ffl_upload_frames_yuv16", "ffl_frontend_yuv16_window", "ffl_dev_frame_check16", "ffl_upload_frames_device16",
            "ffl_dev_frame_check", "ffl_upload_frames_device", "ffl_export_flows",
-           "ffl_dev_flow_check", "ffl_import_flows", "ffl_radial_window"]
+           "ffl_dev_flow_check", "ffl_import_flows", "ffl_radial_window",
+           "ffl_upload_frames_raw_src", "ffl_upload_frames_yuv_src", "ffl_upload_frames_yuv16_src", "ffl_frontend_yuv_window_src",
+           "ffl_frontend_yuv16_window_src", "ffl_dev_frame_check_src", "ffl_dev_frame_check16_src",
+           "ffl_upload_frames_device_src", "ffl_upload_frames_device16_src"]
 
 # 4:2:0 layouts of ffl_upload_frames_yuv (FFL_YUV_I420, FFL_YUV_NV12): cv2's single-array (3h/2, w) uint8 frames
 YUV_LAYOUTS = {"i420": 0, "nv12": 1}
 # rule Y5: 9- to 16-bit samples in uint16 containers are a keyword of their own, depth=, beside the
 # layout -- "nv12" with depth=10 is P010, "i420" with depth=10 is yuv420p10le
 YUV_DEPTHS = range(8, 17)
+
+# stream metadata (ffl_source_info; DESIGN.md appendix Y, rules Y6 and Y7): the keywords rotate=, mirror=, yuv_range=
+ROTATIONS = (0, 90, 180, 270)
+YUV_RANGES = {"limited": 0, "full": 1}
 
 # device-memory I/O (ffl_upload_frames_device / ffl_export_flows): FFL_DEV_* and FFL_FLOW_* codes
 DEV_FORMATS = {"gray": 0, "bgr": 1, "rgb": 2, "i420": 3, "nv12": 4}
@@ -268,6 +275,30 @@ class _DeviceSpan:
                                          "typestr": "|u1"}
 
 
+class SourceInfo(C.Structure):
+    """ffl_source_info: display rotation, mirroring and colour range of a stream (include/ffl.h)"""
+    _fields_ = [("rotate", C.c_int), ("mirror", C.c_int), ("full_range", C.c_int)]
+
+
+def source_info(rotate=0, mirror=False, yuv_range="limited"):
+    """The stream metadata keywords checked (rules Y6 and Y7) -> a SourceInfo, or None when they
+    say nothing (the call then goes through the symbol without the _src suffix).  rotate: the clockwise rotation in
+    degrees that makes the stored frame upright (0, 90, 180, 270: what PyAV / ffprobe report as the display rotation);
+    mirror: a left-right flip after it; yuv_range: "limited" (16..235) or "full" (0..255, yuvj420p) for 4:2:0 frames.
+    There is no auto-detection, and a cv2.VideoCapture BGR frame is upright already: rotating it again is wrong.
+    ValueError for anything else; that full range needs a 4:2:0 source is the library's refusal."""
+    if isinstance(rotate, bool) or not isinstance(rotate, (int, np.integer)) or rotate not in ROTATIONS:
+        raise ValueError(f"rotate must be one of {ROTATIONS} (the clockwise rotation that makes the stored frame upright), "
+                         f"got {rotate!r}")
+    if not isinstance(mirror, (bool, np.bool_)) and mirror not in (0, 1):
+        raise ValueError(f"mirror must be False or True (a left-right flip after the rotation), got {mirror!r}")
+    if not isinstance(yuv_range, str) or yuv_range.lower() not in YUV_RANGES:
+        raise ValueError(f"yuv_range must be one of {sorted(YUV_RANGES)}, got {yuv_range!r}; the range is a keyword of its "
+                         "own: full-range yuvj420p is yuv=\"i420\", yuv_range=\"full\"")
+    info = SourceInfo(int(rotate), int(bool(mirror)), YUV_RANGES[yuv_range.lower()])
+    return info if (info.rotate or info.mirror or info.full_range) else None
+
+
 def yuv_depth(depth, layout=None, msb=None):
     """(depth, msb_aligned) of rule Y5 checked: depth 8 (plain uint8 frames) or 9..16; msb None = where decoders put the
     bits -- high for "nv12" (P010 / P016), low for "i420" (yuv420p10le).  ValueError for anything else."""
@@ -327,13 +358,20 @@ def device_frame(obj, fmt, depth=8):
     return f
 
 
-def dev_frame_check(fmt, frame, resize, crop, out_size, depth=8):
+def dev_frame_check(fmt, frame, resize, crop, out_size, depth=8, rotate=0, mirror=False, yuv_range="limited"):
     """ffl_dev_frame_check (depth > 8: ffl_dev_frame_check16) for a DevFrame: ValueError with the library's rule when it
-    refuses (pure host check)."""
+    refuses (pure host check).  rotate, mirror, yuv_range: see source_info (the _src siblings; resize and crop are then in
+    upright terms)."""
     L = load()
+    info = source_info(rotate, mirror, yuv_range)
     geom = (frame.width, frame.height, C.byref(frame), int(resize[0]), int(resize[1]), int(crop[0]), int(crop[1]),
             int(out_size[0]), int(out_size[1]))
-    rc = L.ffl_dev_frame_check(dev_format(fmt), *geom) if depth == 8 else L.ffl_dev_frame_check16(dev_format(fmt), int(depth), *geom)
+    if info is not None:
+        geom += (C.byref(info),)
+        rc = (L.ffl_dev_frame_check_src(dev_format(fmt), *geom) if depth == 8 else
+              L.ffl_dev_frame_check16_src(dev_format(fmt), int(depth), *geom))
+    else:
+        rc = L.ffl_dev_frame_check(dev_format(fmt), *geom) if depth == 8 else L.ffl_dev_frame_check16(dev_format(fmt), int(depth), *geom)
     if rc != FFL_OK:
         raise ValueError(L.ffl_last_error(None).decode())
 
@@ -413,21 +451,28 @@ def yuv_layout(layout):
     raise ValueError(f"YUV layout must be one of {sorted(YUV_LAYOUTS)}, got {layout!r}")
 
 
-def frontend_yuv_window(src_size, layout, resize, crop, out_size, stride=None, depth=8):
+def frontend_yuv_window(src_size, layout, resize, crop, out_size, stride=None, depth=8, rotate=0, mirror=False,
+                        yuv_range="limited"):
     """((x, y, w, h), bytes per frame) of the source rectangle ffl_upload_frames_yuv transfers for a src_size = (w, h)
     4:2:0 frame, resized to `resize` = (w, h) and cropped at `crop` = (x, y) to out_size = (w, h).
     ValueError with the library's reason for what it refuses.  stride (bytes) defaults to a packed row; an int layout is
     passed to the library as it is.  depth != 8: ffl_frontend_yuv16_window for uint16 samples, to which the depth goes
-    as it is -- the same rectangle in samples, twice the bytes."""
+    as it is -- the same rectangle in samples, twice the bytes.  rotate, mirror, yuv_range: see source_info (the _src
+    siblings): src_size and the rectangle stay in stored terms, resize and crop are in upright ones."""
     sw, sh = int(src_size[0]), int(src_size[1])
     win, b = (C.c_int * 4)(), C.c_size_t()
     L = load()
     code = layout if isinstance(layout, int) else yuv_layout(layout)
+    info = source_info(rotate, mirror, yuv_range)
     geom = (int(resize[0]), int(resize[1]), int(crop[0]), int(crop[1]), int(out_size[0]), int(out_size[1]), win, C.byref(b))
+    src = "_src" if info is not None else ""
+    if info is not None:
+        geom += (C.byref(info),)
     if depth == 8:
-        rc = L.ffl_frontend_yuv_window(sw, sh, code, int(sw if stride is None else stride), *geom)
+        rc = getattr(L, "ffl_frontend_yuv_window" + src)(sw, sh, code, int(sw if stride is None else stride), *geom)
     else:
-        rc = L.ffl_frontend_yuv16_window(sw, sh, code, int(2 * sw if stride is None else stride), int(depth), *geom)
+        rc = getattr(L, "ffl_frontend_yuv16_window" + src)(sw, sh, code, int(2 * sw if stride is None else stride), int(depth),
+                                                            *geom)
     if rc != FFL_OK:
         raise ValueError(L.ffl_last_error(None).decode())
     return tuple(win), b.value
@@ -506,6 +551,9 @@ def load():
     L.ffl_dev_flow_check.argtypes = [C.c_int] * 4 + [vp]
     L.ffl_import_flows.argtypes = [vp, C.c_int, ip, vp, C.c_int, C.c_int, C.c_uint64]
     L.ffl_radial_window.argtypes = [vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, C.c_uint64]
+    for name in EXPORTS:   # every _src sibling: the plain call's arguments plus const ffl_source_info *
+        if name.endswith("_src"):
+            getattr(L, name).argtypes = getattr(L, name[:-4]).argtypes + [vp]
     _lib = L
     return L
 
@@ -654,26 +702,37 @@ class Context:
         buf = (C.c_uint8 * nbytes).from_address(p.value)
         return np.frombuffer(buf, dtype).reshape(shape)
 
-    def upload_frames_raw(self, first_slot, frames, resize, crop=(0, 0), rgb_order=False):
+    def upload_frames_raw(self, first_slot, frames, resize, crop=(0, 0), rgb_order=False, rotate=0, mirror=False,
+                          yuv_range="limited"):
         """Decoded (h, w, 3) uint8 frames -> gray(resize(frame, resize)[crop window]) in consecutive slots
-        (cv2.resize / cv2.cvtColor 8-bit rules on the device; FF:182-186, FF:1076-1082)."""
+        (cv2.resize / cv2.cvtColor 8-bit rules on the device; FF:182-186, FF:1076-1082).  rotate, mirror: the frames are
+        stored unrotated (see source_info); resize and crop then describe the upright frame.  Frames out of
+        cv2.VideoCapture.read are upright already.  yuv_range other than "limited" is the library's refusal here."""
+        info = source_info(rotate, mirror, yuv_range)
         fr = [f if (f.ndim == 3 and f.strides[2] == 1 and f.strides[1] == 3) else np.ascontiguousarray(f) for f in frames]
         f0 = fr[0]
         if any(f.dtype != np.uint8 or f.ndim != 3 or f.shape != f0.shape or f.shape[2] != 3 or
                f.strides[0] != f0.strides[0] for f in fr):
             raise FFLError("upload_frames_raw needs (h, w, 3) uint8 frames of one shape and row stride")
         ptrs = (C.c_void_p * len(fr))(*[f.ctypes.data for f in fr])
-        self._chk(self.L.ffl_upload_frames_raw(self._h, first_slot, len(fr), ptrs, f0.shape[1], f0.shape[0],
-                                               f0.strides[0], int(bool(rgb_order)), int(resize[0]), int(resize[1]),
-                                               int(crop[0]), int(crop[1])))
+        args = (self._h, first_slot, len(fr), ptrs, f0.shape[1], f0.shape[0], f0.strides[0], int(bool(rgb_order)),
+                int(resize[0]), int(resize[1]), int(crop[0]), int(crop[1]))
+        if info is not None:
+            self._chk(self.L.ffl_upload_frames_raw_src(*args, C.byref(info)))
+        else:
+            self._chk(self.L.ffl_upload_frames_raw(*args))
 
-    def upload_frames_yuv(self, first_slot, frames, layout, resize, crop=(0, 0), depth=8, msb=None):
+    def upload_frames_yuv(self, first_slot, frames, layout, resize, crop=(0, 0), depth=8, msb=None, rotate=0, mirror=False,
+                          yuv_range="limited"):
         """Decoded 4:2:0 frames -- (3h/2, w) uint8 arrays, cv2's single-array I420 / NV12 layout, layout "i420" or "nv12"
         -- -> gray(resize(YUV2BGR(frame), resize)[crop window]) in consecutive slots.  Only the
         source rectangle the window reads is transferred.  Rows must be contiguous (an NV12 row pitch may exceed w).
         depth=9..16: uint16 frames (yuv420p10le, P010, ...; ffl_upload_frames_yuv16), each sample reduced to 8 bits by
-        rule Y5; msb: whether the bits sit high in the 16 (None: high for "nv12", low for "i420")."""
+        rule Y5; msb: whether the bits sit high in the 16 (None: high for "nv12", low for "i420").  rotate, mirror,
+        yuv_range: the stream's display rotation, mirroring and colour range (see source_info; rules Y6 and Y7); resize
+        and crop then describe the upright frame, and the rectangle that travels is still one of the stored frame."""
         code = yuv_layout(layout)
+        info = source_info(rotate, mirror, yuv_range)
         depth, msb = yuv_depth(depth, code, msb)
         dt, es = (np.uint16, 2) if depth > 8 else (np.uint8, 1)
         fr = [f if (f.ndim == 2 and f.strides[1] == f.itemsize) else np.ascontiguousarray(f) for f in frames]
@@ -689,30 +748,40 @@ class Context:
         ptrs = (C.c_void_p * len(fr))(*[f.ctypes.data for f in fr])
         head = (self._h, first_slot, len(fr), ptrs, f0.shape[1], f0.shape[0] * 2 // 3, f0.strides[0], code)
         geom = (int(resize[0]), int(resize[1]), int(crop[0]), int(crop[1]))
+        src = "_src" if info is not None else ""
+        if info is not None:
+            geom += (C.byref(info),)
         if es == 2:
-            self._chk(self.L.ffl_upload_frames_yuv16(*head, depth, msb, *geom))
+            self._chk(getattr(self.L, "ffl_upload_frames_yuv16" + src)(*head, depth, msb, *geom))
         else:
-            self._chk(self.L.ffl_upload_frames_yuv(*head, *geom))
+            self._chk(getattr(self.L, "ffl_upload_frames_yuv" + src)(*head, *geom))
 
-    def upload_frames_device(self, first_slot, frames, fmt, resize=None, crop=(0, 0), stream=None, depth=8, msb=None):
+    def upload_frames_device(self, first_slot, frames, fmt, resize=None, crop=(0, 0), stream=None, depth=8, msb=None,
+                             rotate=0, mirror=False, yuv_range="limited"):
         """Device-resident frames -> gray(resize(frame, resize)[crop window]) in consecutive slots without a host round
         trip (ffl_upload_frames_device): the bytes upload_frames_raw / upload_frames_yuv /
         upload_frames give for the same pixels.  `frames`: a sequence of device arrays (see device_frame) or one array with
         a leading frame axis, all of one size; fmt one of DEV_FORMATS; resize None = the source size.  The frames are read
         after the work queued on `stream` (stream_handle) and `stream` waits for the read: the caller may overwrite or free
         them in its order on that stream, with no host synchronisation.  depth=9..16, msb: "i420" / "nv12" frames of
-        uint16 samples (torch.uint16, typestr "<u2"; ffl_upload_frames_device16), as upload_frames_yuv takes them."""
+        uint16 samples (torch.uint16, typestr "<u2"; ffl_upload_frames_device16), as upload_frames_yuv takes them.
+        rotate, mirror, yuv_range: see source_info -- a GPU decoder's surfaces are stored unrotated; resize (None = the
+        upright source size) and crop then describe the upright frame."""
         code = dev_format(fmt)
         depth, msb = yuv_depth(depth, fmt, msb)
+        info = source_info(rotate, mirror, yuv_range)
         rows, size = self._device_rows(frames, code, depth)
         descs = np.ascontiguousarray(rows, np.int64)
-        rw, rh = (size if resize is None else resize)
+        rw, rh = ((size[::-1] if info is not None and info.rotate in (90, 270) else size) if resize is None else resize)
         head = (self._h, int(first_slot), len(descs), descs.ctypes.data, code)
         geom = (size[0], size[1], int(rw), int(rh), int(crop[0]), int(crop[1]), stream_handle(stream, self.device))
+        src = "_src" if info is not None else ""
+        if info is not None:
+            geom += (C.byref(info),)
         if depth > 8:
-            self._chk(self.L.ffl_upload_frames_device16(*head, depth, msb, *geom))
+            self._chk(getattr(self.L, "ffl_upload_frames_device16" + src)(*head, depth, msb, *geom))
         else:
-            self._chk(self.L.ffl_upload_frames_device(*head, *geom))
+            self._chk(getattr(self.L, "ffl_upload_frames_device" + src)(*head, *geom))
 
     @staticmethod
     def _device_rows(frames, code, depth=8):

@@ -718,21 +718,56 @@ static int publish_post(ffl_ctx *c, int n, const int *slots, EvRef *done) {
     return FFL_OK;
 }
 
-// The geometry rules of every front-end path: source, resize and output sizes within 32768, the crop window inside the
-// resized frame.  Fills the geometry, resize mode and scales of *p (the caller sets kind and rgb); fn prefixes the message.
-static int front_geometry(ffl_ctx *c, const char *fn, int sw, int sh, int rw, int rh, int cx, int cy, int ow, int oh,
-                          FrontParams *p) {
+// The geometry rules of every front-end path: the stream metadata (rules Y6 / Y7 of DESIGN.md appendix Y), source, resize
+// and output sizes within 32768, the crop window inside the resized frame.  The only place that turns the stored size
+// sw x sh into the upright one and that into the resize mode, the scales and the map of rule Y6: resize, crop, clamps and
+// scales are all in upright terms.  cls: what the source is (full range is a property of 4:2:0; a gray frame is copied as
+// it is, so its upright size is the output's).  Fills everything of *p but kind and rgb (the caller sets them) and the
+// 16-bit reduction (front_depth()); fn prefixes the message.  si NULL: no metadata.
+enum { FRONT_BGR = 0, FRONT_YUV = 1, FRONT_GRAY = 2 };
+static int front_geometry(ffl_ctx *c, const char *fn, int cls, int sw, int sh, const ffl_source_info *si, int rw, int rh, int cx,
+                          int cy, int ow, int oh, FrontParams *p) {
+    static const ffl_source_info none = {0, 0, 0};
+    if (!si) si = &none;
+    if (si->rotate != 0 && si->rotate != 90 && si->rotate != 180 && si->rotate != 270)
+        return set_err(c, FFL_ERR_INVALID, "%s: rotate %d is not one of 0, 90, 180, 270 (the clockwise rotation that makes the "
+                                           "stored frame upright)", fn, si->rotate);
+    if ((unsigned)si->mirror > 1u)
+        return set_err(c, FFL_ERR_INVALID, "%s: mirror %d is neither 0 nor 1", fn, si->mirror);
+    if ((unsigned)si->full_range > 1u)
+        return set_err(c, FFL_ERR_INVALID, "%s: full_range %d is neither 0 nor 1", fn, si->full_range);
+    if (si->full_range && cls != FRONT_YUV)
+        return set_err(c, FFL_ERR_INVALID, "%s: full_range describes 4:2:0 sources (I420, NV12): BGR, RGB and gray frames carry "
+                                           "no colour range", fn);
+    const int rot = si->rotate / 90;
+    const int uw = rot & 1 ? sh : sw, uh = rot & 1 ? sw : sh;  // the upright size
+    if (cls == FRONT_GRAY && (rw != uw || rh != uh))
+        return set_err(c, FFL_ERR_INVALID, "%s: gray frames are copied as they are: a resize (%dx%d -> %dx%d) is refused", fn, uw, uh,
+                       rw, rh);
+    if (cls == FRONT_GRAY && (uw != ow || uh != oh))
+        return set_err(c, FFL_ERR_INVALID, "%s: a gray frame must be the context size %dx%d, got %dx%d", fn, ow, oh, uw, uh);
     if (sw < 1 || sh < 1 || sw > 32768 || sh > 32768 || rw < 1 || rh < 1 || rw > 32768 || rh > 32768 || ow < 1 || oh < 1)
         return set_err(c, FFL_ERR_INVALID, "%s: unsupported source %dx%d / resize %dx%d / output %dx%d", fn, sw, sh, rw, rh, ow, oh);
     if (cx < 0 || cy < 0 || cx + ow > rw || cy + oh > rh)
         return set_err(c, FFL_ERR_INVALID, "%s: crop window (%d, %d) + %dx%d does not fit the %dx%d resized frame", fn, cx, cy, ow,
                        oh, rw, rh);
-    p->sw = sw; p->sh = sh;
+    p->sw = uw; p->sh = uh;
     p->cx = cx; p->cy = cy; p->ow = ow; p->oh = oh;
-    p->scale_x = 1. / ((double)rw / sw);
-    p->scale_y = 1. / ((double)rh / sh);
-    p->mode = (rw == sw && rh == sh) ? FFL_FRONT_IDENTITY : (sw == 2 * rw && sh == 2 * rh) ? FFL_FRONT_AREA2 : FFL_FRONT_GENERIC;
+    p->scale_x = 1. / ((double)rw / uw);
+    p->scale_y = 1. / ((double)rh / uh);
+    p->mode = (rw == uw && rh == uh) ? FFL_FRONT_IDENTITY : (uw == 2 * rw && uh == 2 * rh) ? FFL_FRONT_AREA2 : FFL_FRONT_GENERIC;
     p->shift16 = p->round16 = 0;  // front_depth() sets them for 16-bit sources
+    // rule Y6: the mirror first (ux <- uw - 1 - ux = mx * ux + m0), then the row of the table for the rotation
+    const int mx = si->mirror ? -1 : 1, m0 = si->mirror ? uw - 1 : 0;
+    p->ax = p->bx = p->cx0 = p->ay = p->by = p->cy0 = 0;
+    switch (rot) {
+    case 0: p->ax = mx; p->cx0 = m0; p->by = 1; break;                                          // S[uy][ux]
+    case 1: p->bx = 1; p->ay = -mx; p->cy0 = sh - 1 - m0; break;                                // S[sh - 1 - ux][uy]
+    case 2: p->ax = -mx; p->cx0 = sw - 1 - m0; p->by = -1; p->cy0 = sh - 1; break;              // S[sh - 1 - uy][sw - 1 - ux]
+    default: p->bx = -1; p->cx0 = sw - 1; p->ay = mx; p->cy0 = m0; break;                       // S[ux][sw - 1 - uy]
+    }
+    p->full = si->full_range;
+    p->src = rot != 0 || si->mirror || si->full_range;
     return FFL_OK;
 }
 
@@ -1120,15 +1155,14 @@ int ffl_upload_frames(ffl_ctx *c, int first, int n, const uint8_t *const *frames
 // Decoded frames -> gray frame slots through k_frontend (resize + crop + luma in one pass).  Frame by
 // frame: tight copy into a pinned ring buffer, H2D, kernel -- the 3 * src_w * src_h byte transfer is the
 // cost, so there is nothing to gain from batching the launches.
-int ffl_upload_frames_raw(ffl_ctx *c, int first, int n, const uint8_t *const *frames, int sw, int sh,
-                          ptrdiff_t stride_bytes, int rgb_order, int rw, int rh, int crop_x, int crop_y) {
-    static const char *fn = "ffl_upload_frames_raw";
+static int upload_raw(ffl_ctx *c, const char *fn, int first, int n, const uint8_t *const *frames, int sw, int sh,
+                      ptrdiff_t stride_bytes, int rgb_order, int rw, int rh, int crop_x, int crop_y, const ffl_source_info *si) {
     if (!c) return FFL_ERR_INVALID;
     std::unique_lock<std::mutex> ul(c->up_mu);
     CtxLock lk(c->mu);
     if (int rc = check_frame_run(c, fn, first, n, frames, frames)) return rc;
     FrontParams fp;
-    if (int rc = front_geometry(c, fn, sw, sh, rw, rh, crop_x, crop_y, c->w, c->h, &fp)) return rc;
+    if (int rc = front_geometry(c, fn, FRONT_BGR, sw, sh, si, rw, rh, crop_x, crop_y, c->w, c->h, &fp)) return rc;
     if (stride_bytes < (ptrdiff_t)sw * 3)
         return set_err(c, FFL_ERR_INVALID, "%s: stride %td < row bytes %d", fn, stride_bytes, sw * 3);
     HIPCHK(c, hipSetDevice(c->device));
@@ -1153,18 +1187,29 @@ int ffl_upload_frames_raw(ffl_ctx *c, int first, int n, const uint8_t *const *fr
     return upload_staged(c, lk, first, n, fbytes, fp, direct, stage, send_direct, desc);
 }
 
+int ffl_upload_frames_raw(ffl_ctx *c, int first, int n, const uint8_t *const *frames, int sw, int sh,
+                          ptrdiff_t stride_bytes, int rgb_order, int rw, int rh, int crop_x, int crop_y) {
+    return upload_raw(c, "ffl_upload_frames_raw", first, n, frames, sw, sh, stride_bytes, rgb_order, rw, rh, crop_x, crop_y, nullptr);
+}
+
+int ffl_upload_frames_raw_src(ffl_ctx *c, int first, int n, const uint8_t *const *frames, int sw, int sh, ptrdiff_t stride_bytes,
+                              int rgb_order, int rw, int rh, int crop_x, int crop_y, const ffl_source_info *si) {
+    return upload_raw(c, "ffl_upload_frames_raw", first, n, frames, sw, sh, stride_bytes, rgb_order, rw, rh, crop_x, crop_y, si);
+}
+
 // ---- 4:2:0 YUV input ---------------------------------------------------------------
-// Where the source rectangle of a YUV upload lies: the source rows / columns the crop window's first and last output
-// row / column map to (k_frontend's arithmetic; it is monotone in the output coordinate), widened by one pixel per side
-// and rounded out -- rows to even coordinates (chroma alignment), columns to multiples of 16 so that the rows of every
-// plane start aligned in the frame (a 2-D copy out of host memory whose rows start unaligned ran at 0.3 GB/s) --
+// Where the source rectangle of a YUV upload lies: the upright source rows / columns the crop window's first and last
+// output row / column map to (k_frontend's arithmetic; it is monotone in the output coordinate), widened by one pixel per
+// side and clamped to the upright frame (yuv_span); that span mapped through rule Y6 to the stored frame; and there
+// rounded out (yuv_round) -- rows to even coordinates (chroma alignment), columns to multiples of 16 so that the rows of
+// every plane start aligned in the frame (a 2-D copy out of host memory whose rows start unaligned ran at 0.3 GB/s) --
 // and clamped to the frame.  The widening makes it a superset even if host and device round the coordinate arithmetic
 // differently; it is not tight to the last pixel.
 struct YuvWin {
-    int x0, y0, w, h;  // window origin and size (all even)
+    int x0, y0, w, h;  // window origin and size in the STORED frame (all even)
 };
 
-static void yuv_span(int d0, int d1, int s, double scale, int mode, int align, int *lo, int *hi_excl) {
+static void yuv_span(int d0, int d1, int s, double scale, int mode, int *lo, int *hi) {
     int a, b;  // first and last source coordinate the kernel loads (inclusive)
     if (mode == FFL_FRONT_IDENTITY) {
         a = d0; b = d1;
@@ -1174,10 +1219,13 @@ static void yuv_span(int d0, int d1, int s, double scale, int mode, int align, i
         a = (int)floorf((float)((d0 + 0.5) * scale - 0.5));
         b = (int)floorf((float)((d1 + 0.5) * scale - 0.5)) + 1;
     }
-    a = std::min(std::max(a - 1, 0), s - 1) / align * align;
-    b = std::min(std::max(b + 1, 0), s - 1) + 1;
-    *lo = a;
-    *hi_excl = std::min((b + align - 1) / align * align, s);  // s is even
+    *lo = std::min(std::max(a - 1, 0), s - 1);
+    *hi = std::min(std::max(b + 1, 0), s - 1);
+}
+
+static void yuv_round(int lo, int hi, int s, int align, int *origin, int *size) {  // [lo, hi] inclusive; s is even
+    *origin = lo / align * align;
+    *size = std::min((hi + 1 + align - 1) / align * align, s) - *origin;
 }
 
 // Rule Y5 (appendix Y) as the kernels apply it: s = msb ? raw >> (16 - depth) : raw; v8 = min(255, (s + (1 << (depth - 9)))
@@ -1191,8 +1239,9 @@ static void front_depth(FrontParams *p, int depth, int msb) {
 // Every refusal of the YUV path (messages name the rule); fn prefixes the message.  Fills the geometry of *fp and the
 // window.  es: bytes per sample (1; 2: the 16-bit frames of rule Y5, whose depth is checked here too); the stride is in
 // bytes, the window in samples.
-static int yuv_window(ffl_ctx *c, const char *fn, int sw, int sh, int layout, ptrdiff_t stride, int es, int depth, int rw, int rh,
-                      int crop_x, int crop_y, int ow, int oh, FrontParams *fp, YuvWin *out) {
+static int yuv_window(ffl_ctx *c, const char *fn, int sw, int sh, int layout, ptrdiff_t stride, int es, int depth,
+                      const ffl_source_info *si, int rw, int rh, int crop_x, int crop_y, int ow, int oh, FrontParams *fp,
+                      YuvWin *out) {
     const char *twice = es == 2 ? "2 * " : "";
     if (es == 2 && (depth < 9 || depth > 16))
         return set_err(c, FFL_ERR_INVALID, "%s: depth %d outside 9..16 (8-bit frames go through ffl_upload_frames_yuv)", fn, depth);
@@ -1207,21 +1256,25 @@ static int yuv_window(ffl_ctx *c, const char *fn, int sw, int sh, int layout, pt
                        fn, twice, stride, sw);
     if (layout == FFL_YUV_NV12 && stride < (ptrdiff_t)sw * es)
         return set_err(c, FFL_ERR_INVALID, "%s: NV12 needs stride >= %swidth, got %td for width %d", fn, twice, stride, sw);
-    if (int rc = front_geometry(c, fn, sw, sh, rw, rh, crop_x, crop_y, ow, oh, fp)) return rc;
-    int x1, y1;
-    yuv_span(crop_x, crop_x + ow - 1, sw, fp->scale_x, fp->mode, 16, &out->x0, &x1);
-    yuv_span(crop_y, crop_y + oh - 1, sh, fp->scale_y, fp->mode, 2, &out->y0, &y1);
-    out->w = x1 - out->x0;
-    out->h = y1 - out->y0;
+    if (int rc = front_geometry(c, fn, FRONT_YUV, sw, sh, si, rw, rh, crop_x, crop_y, ow, oh, fp)) return rc;
+    int ux[2], uy[2];  // the upright span, inclusive
+    yuv_span(crop_x, crop_x + ow - 1, fp->sw, fp->scale_x, fp->mode, &ux[0], &ux[1]);
+    yuv_span(crop_y, crop_y + oh - 1, fp->sh, fp->scale_y, fp->mode, &uy[0], &uy[1]);
+    // rule Y6 is affine with one unit coefficient per stored axis: two opposite corners of the span bound its image
+    const int px[2] = {fp->ax * ux[0] + fp->bx * uy[0] + fp->cx0, fp->ax * ux[1] + fp->bx * uy[1] + fp->cx0};
+    const int py[2] = {fp->ay * ux[0] + fp->by * uy[0] + fp->cy0, fp->ay * ux[1] + fp->by * uy[1] + fp->cy0};
+    yuv_round(std::min(px[0], px[1]), std::max(px[0], px[1]), sw, 16, &out->x0, &out->w);
+    yuv_round(std::min(py[0], py[1]), std::max(py[0], py[1]), sh, 2, &out->y0, &out->h);
     return FFL_OK;
 }
 
-static int frontend_window(const char *fn, int src_w, int src_h, int layout, ptrdiff_t stride_bytes, int es, int depth, int resize_w,
-                           int resize_h, int crop_x, int crop_y, int out_w, int out_h, int win[4], size_t *bytes) {
+static int frontend_window(const char *fn, int src_w, int src_h, int layout, ptrdiff_t stride_bytes, int es, int depth,
+                           const ffl_source_info *si, int resize_w, int resize_h, int crop_x, int crop_y, int out_w, int out_h,
+                           int win[4], size_t *bytes) {
     FrontParams fp;
     YuvWin yw;
-    if (int rc = yuv_window(nullptr, fn, src_w, src_h, layout, stride_bytes, es, depth, resize_w, resize_h, crop_x, crop_y, out_w,
-                            out_h, &fp, &yw))
+    if (int rc = yuv_window(nullptr, fn, src_w, src_h, layout, stride_bytes, es, depth, si, resize_w, resize_h, crop_x, crop_y,
+                            out_w, out_h, &fp, &yw))
         return rc;
     if (win) {
         win[0] = yw.x0; win[1] = yw.y0; win[2] = yw.w; win[3] = yw.h;
@@ -1232,14 +1285,27 @@ static int frontend_window(const char *fn, int src_w, int src_h, int layout, ptr
 
 int ffl_frontend_yuv_window(int src_w, int src_h, int layout, ptrdiff_t stride_bytes, int resize_w, int resize_h, int crop_x,
                             int crop_y, int out_w, int out_h, int win[4], size_t *bytes) {
-    return frontend_window("ffl_frontend_yuv_window", src_w, src_h, layout, stride_bytes, 1, 8, resize_w, resize_h, crop_x, crop_y,
-                           out_w, out_h, win, bytes);
+    return frontend_window("ffl_frontend_yuv_window", src_w, src_h, layout, stride_bytes, 1, 8, nullptr, resize_w, resize_h, crop_x,
+                           crop_y, out_w, out_h, win, bytes);
+}
+
+int ffl_frontend_yuv_window_src(int src_w, int src_h, int layout, ptrdiff_t stride_bytes, int resize_w, int resize_h, int crop_x,
+                                int crop_y, int out_w, int out_h, int win[4], size_t *bytes, const ffl_source_info *si) {
+    return frontend_window("ffl_frontend_yuv_window", src_w, src_h, layout, stride_bytes, 1, 8, si, resize_w, resize_h, crop_x,
+                           crop_y, out_w, out_h, win, bytes);
 }
 
 int ffl_frontend_yuv16_window(int src_w, int src_h, int layout, ptrdiff_t stride_bytes, int depth, int resize_w, int resize_h,
                               int crop_x, int crop_y, int out_w, int out_h, int win[4], size_t *bytes) {
-    return frontend_window("ffl_frontend_yuv16_window", src_w, src_h, layout, stride_bytes, 2, depth, resize_w, resize_h, crop_x,
-                           crop_y, out_w, out_h, win, bytes);
+    return frontend_window("ffl_frontend_yuv16_window", src_w, src_h, layout, stride_bytes, 2, depth, nullptr, resize_w, resize_h,
+                           crop_x, crop_y, out_w, out_h, win, bytes);
+}
+
+int ffl_frontend_yuv16_window_src(int src_w, int src_h, int layout, ptrdiff_t stride_bytes, int depth, int resize_w, int resize_h,
+                                  int crop_x, int crop_y, int out_w, int out_h, int win[4], size_t *bytes,
+                                  const ffl_source_info *si) {
+    return frontend_window("ffl_frontend_yuv16_window", src_w, src_h, layout, stride_bytes, 2, depth, si, resize_w, resize_h,
+                           crop_x, crop_y, out_w, out_h, win, bytes);
 }
 
 // Decoded 4:2:0 frames -> gray frame slots through k_frontend: the body of ffl_upload_frames_yuv (es = 1) and
@@ -1249,14 +1315,16 @@ int ffl_frontend_yuv16_window(int src_w, int src_h, int layout, ptrdiff_t stride
 // otherwise copied into the pinned ring buffer and sent as one transfer.  On the device the window is packed: Y (w x h),
 // then U and V (w/2 x h/2 each, I420) or the interleaved UV rows (w x h/2, NV12), es bytes per sample.
 static int upload_yuv(ffl_ctx *c, const char *fn, int first, int n, const uint8_t *const *frames, int sw, int sh,
-                      ptrdiff_t stride_bytes, int layout, int es, int depth, int msb, int rw, int rh, int crop_x, int crop_y) {
+                      ptrdiff_t stride_bytes, int layout, int es, int depth, int msb, int rw, int rh, int crop_x, int crop_y,
+                      const ffl_source_info *si) {
     if (!c) return FFL_ERR_INVALID;
     std::unique_lock<std::mutex> ul(c->up_mu);
     CtxLock lk(c->mu);
     if (int rc = check_frame_run(c, fn, first, n, frames, frames)) return rc;
     FrontParams fp;
     YuvWin yw;
-    if (int rc = yuv_window(c, fn, sw, sh, layout, stride_bytes, es, depth, rw, rh, crop_x, crop_y, c->w, c->h, &fp, &yw)) return rc;
+    if (int rc = yuv_window(c, fn, sw, sh, layout, stride_bytes, es, depth, si, rw, rh, crop_x, crop_y, c->w, c->h, &fp, &yw))
+        return rc;
     for (int i = 0; es == 2 && i < n; i++)
         if ((uintptr_t)frames[i] & 1) return set_err(c, FFL_ERR_INVALID, "%s: frame %d is not 2-byte aligned", fn, i);
     HIPCHK(c, hipSetDevice(c->device));
@@ -1320,13 +1388,26 @@ static int upload_yuv(ffl_ctx *c, const char *fn, int first, int n, const uint8_
 
 int ffl_upload_frames_yuv(ffl_ctx *c, int first, int n, const uint8_t *const *frames, int sw, int sh, ptrdiff_t stride_bytes,
                           int layout, int rw, int rh, int crop_x, int crop_y) {
-    return upload_yuv(c, "ffl_upload_frames_yuv", first, n, frames, sw, sh, stride_bytes, layout, 1, 8, 0, rw, rh, crop_x, crop_y);
+    return upload_yuv(c, "ffl_upload_frames_yuv", first, n, frames, sw, sh, stride_bytes, layout, 1, 8, 0, rw, rh, crop_x, crop_y,
+                      nullptr);
+}
+
+int ffl_upload_frames_yuv_src(ffl_ctx *c, int first, int n, const uint8_t *const *frames, int sw, int sh, ptrdiff_t stride_bytes,
+                              int layout, int rw, int rh, int crop_x, int crop_y, const ffl_source_info *si) {
+    return upload_yuv(c, "ffl_upload_frames_yuv", first, n, frames, sw, sh, stride_bytes, layout, 1, 8, 0, rw, rh, crop_x, crop_y, si);
 }
 
 int ffl_upload_frames_yuv16(ffl_ctx *c, int first, int n, const uint16_t *const *frames, int sw, int sh, ptrdiff_t stride_bytes,
                             int layout, int depth, int msb_aligned, int rw, int rh, int crop_x, int crop_y) {
     return upload_yuv(c, "ffl_upload_frames_yuv16", first, n, (const uint8_t *const *)frames, sw, sh, stride_bytes, layout, 2,
-                      depth, msb_aligned != 0, rw, rh, crop_x, crop_y);
+                      depth, msb_aligned != 0, rw, rh, crop_x, crop_y, nullptr);
+}
+
+int ffl_upload_frames_yuv16_src(ffl_ctx *c, int first, int n, const uint16_t *const *frames, int sw, int sh, ptrdiff_t stride_bytes,
+                                int layout, int depth, int msb_aligned, int rw, int rh, int crop_x, int crop_y,
+                                const ffl_source_info *si) {
+    return upload_yuv(c, "ffl_upload_frames_yuv16", first, n, (const uint8_t *const *)frames, sw, sh, stride_bytes, layout, 2,
+                      depth, msb_aligned != 0, rw, rh, crop_x, crop_y, si);
 }
 
 int ffl_upload_frame(ffl_ctx *c, int fslot, const uint8_t *data, int width, int height, int channels,
@@ -2075,7 +2156,7 @@ int ffl_download_flow(ffl_ctx *c, int slot, float *dst) {
 // message.  Fills the geometry of *p.  es: bytes per sample (2: the 16-bit 4:2:0 frames of rule Y5, whose depth is checked
 // here too).
 static int dev_frame_check(ffl_ctx *c, const char *fn, int idx, int fmt, int es, int depth, int sw, int sh, const ffl_dev_frame *f,
-                           int rw, int rh, int cx, int cy, int ow, int oh, FrontParams *p) {
+                           const ffl_source_info *si, int rw, int rh, int cx, int cy, int ow, int oh, FrontParams *p) {
     if (!f) return set_err(c, FFL_ERR_INVALID, "%s: frame %d: NULL descriptor", fn, idx);
     if (fmt < FFL_DEV_GRAY || fmt > FFL_DEV_NV12)
         return set_err(c, FFL_ERR_INVALID, "%s: unknown format %d (FFL_DEV_GRAY 0, BGR 1, RGB 2, I420 3, NV12 4)", fn, fmt);
@@ -2085,14 +2166,12 @@ static int dev_frame_check(ffl_ctx *c, const char *fn, int idx, int fmt, int es,
                        fn, fmt);
     if (es == 2 && (depth < 9 || depth > 16))
         return set_err(c, FFL_ERR_INVALID, "%s: depth %d outside 9..16 (8-bit frames go through ffl_upload_frames_device)", fn, depth);
-    if (fmt == FFL_DEV_GRAY && (rw != sw || rh != sh))
-        return set_err(c, FFL_ERR_INVALID, "%s: gray frames are copied as they are: a resize (%dx%d -> %dx%d) is refused", fn, sw, sh,
-                       rw, rh);
-    if (fmt == FFL_DEV_GRAY && (sw != ow || sh != oh))
-        return set_err(c, FFL_ERR_INVALID, "%s: a gray frame must be the context size %dx%d, got %dx%d", fn, ow, oh, sw, sh);
     if (yuv && ((sw & 1) || (sh & 1)))
         return set_err(c, FFL_ERR_INVALID, "%s: 4:2:0 needs an even width and height, source is %dx%d", fn, sw, sh);
-    if (int rc = front_geometry(c, fn, sw, sh, rw, rh, cx, cy, ow, oh, p)) return rc;
+    // the metadata, gray's two rules (in upright terms) and the crop; everything below is about the stored planes
+    if (int rc = front_geometry(c, fn, fmt == FFL_DEV_GRAY ? FRONT_GRAY : yuv ? FRONT_YUV : FRONT_BGR, sw, sh, si, rw, rh, cx, cy, ow,
+                                oh, p))
+        return rc;
     const ptrdiff_t big = (ptrdiff_t)1 << 40;
     const ptrdiff_t p0 = f->pitch[0], ps = f->pixel_stride, cs = f->channel_stride;
     if (!f->plane[0] || (yuv && !f->plane[1]) || (fmt == FFL_DEV_I420 && !f->plane[2]))
@@ -2238,13 +2317,25 @@ static int post_end(ffl_ctx *c, hipStream_t cst, int n, const int *slots) {
 
 int ffl_dev_frame_check(int format, int sw, int sh, const ffl_dev_frame *f, int rw, int rh, int cx, int cy, int out_w, int out_h) {
     FrontParams p;
-    return dev_frame_check(nullptr, "ffl_dev_frame_check", 0, format, 1, 8, sw, sh, f, rw, rh, cx, cy, out_w, out_h, &p);
+    return dev_frame_check(nullptr, "ffl_dev_frame_check", 0, format, 1, 8, sw, sh, f, nullptr, rw, rh, cx, cy, out_w, out_h, &p);
+}
+
+int ffl_dev_frame_check_src(int format, int sw, int sh, const ffl_dev_frame *f, int rw, int rh, int cx, int cy, int out_w, int out_h,
+                            const ffl_source_info *si) {
+    FrontParams p;
+    return dev_frame_check(nullptr, "ffl_dev_frame_check", 0, format, 1, 8, sw, sh, f, si, rw, rh, cx, cy, out_w, out_h, &p);
 }
 
 int ffl_dev_frame_check16(int format, int depth, int sw, int sh, const ffl_dev_frame *f, int rw, int rh, int cx, int cy, int out_w,
                           int out_h) {
     FrontParams p;
-    return dev_frame_check(nullptr, "ffl_dev_frame_check16", 0, format, 2, depth, sw, sh, f, rw, rh, cx, cy, out_w, out_h, &p);
+    return dev_frame_check(nullptr, "ffl_dev_frame_check16", 0, format, 2, depth, sw, sh, f, nullptr, rw, rh, cx, cy, out_w, out_h, &p);
+}
+
+int ffl_dev_frame_check16_src(int format, int depth, int sw, int sh, const ffl_dev_frame *f, int rw, int rh, int cx, int cy, int out_w,
+                              int out_h, const ffl_source_info *si) {
+    FrontParams p;
+    return dev_frame_check(nullptr, "ffl_dev_frame_check16", 0, format, 2, depth, sw, sh, f, si, rw, rh, cx, cy, out_w, out_h, &p);
 }
 
 // Device frames -> gray frame slots through ONE k_frontend_dev launch on stream `copy`, ordered after the caller's queued
@@ -2252,14 +2343,14 @@ int ffl_dev_frame_check16(int format, int depth, int sw, int sh, const ffl_dev_f
 // and ffl_upload_frames_device16 (es = 2 bytes per sample, reduced by rule Y5).  The descriptors travel in the pinned
 // table of the up_ring entry the call records (publish_frames), copied to the device table on the same stream.
 static int upload_device(ffl_ctx *c, const char *fn, int first, int n, const ffl_dev_frame *frames, int fmt, int es, int depth,
-                         int msb, int sw, int sh, int rw, int rh, int cx, int cy, uint64_t stream) {
+                         int msb, int sw, int sh, int rw, int rh, int cx, int cy, uint64_t stream, const ffl_source_info *si) {
     if (!c) return FFL_ERR_INVALID;
     std::unique_lock<std::mutex> ul(c->up_mu);
     CtxLock lk(c->mu);
     if (int rc = check_frame_run(c, fn, first, n, frames)) return rc;
     FrontParams p;
     for (int i = 0; i < n; i++)
-        if (int rc = dev_frame_check(c, fn, i, fmt, es, depth, sw, sh, &frames[i], rw, rh, cx, cy, c->w, c->h, &p)) return rc;
+        if (int rc = dev_frame_check(c, fn, i, fmt, es, depth, sw, sh, &frames[i], si, rw, rh, cx, cy, c->w, c->h, &p)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t cst;
     if (int rc = caller_stream(c, fn, stream, &cst)) return rc;
@@ -2324,13 +2415,24 @@ static int upload_device(ffl_ctx *c, const char *fn, int first, int n, const ffl
 
 int ffl_upload_frames_device(ffl_ctx *c, int first, int n, const ffl_dev_frame *frames, int fmt, int sw, int sh, int rw, int rh,
                              int cx, int cy, uint64_t stream) {
-    return upload_device(c, "ffl_upload_frames_device", first, n, frames, fmt, 1, 8, 0, sw, sh, rw, rh, cx, cy, stream);
+    return upload_device(c, "ffl_upload_frames_device", first, n, frames, fmt, 1, 8, 0, sw, sh, rw, rh, cx, cy, stream, nullptr);
+}
+
+int ffl_upload_frames_device_src(ffl_ctx *c, int first, int n, const ffl_dev_frame *frames, int fmt, int sw, int sh, int rw, int rh,
+                                 int cx, int cy, uint64_t stream, const ffl_source_info *si) {
+    return upload_device(c, "ffl_upload_frames_device", first, n, frames, fmt, 1, 8, 0, sw, sh, rw, rh, cx, cy, stream, si);
 }
 
 int ffl_upload_frames_device16(ffl_ctx *c, int first, int n, const ffl_dev_frame *frames, int fmt, int depth, int msb_aligned,
                                int sw, int sh, int rw, int rh, int cx, int cy, uint64_t stream) {
     return upload_device(c, "ffl_upload_frames_device16", first, n, frames, fmt, 2, depth, msb_aligned != 0, sw, sh, rw, rh, cx, cy,
-                         stream);
+                         stream, nullptr);
+}
+
+int ffl_upload_frames_device16_src(ffl_ctx *c, int first, int n, const ffl_dev_frame *frames, int fmt, int depth, int msb_aligned,
+                                   int sw, int sh, int rw, int rh, int cx, int cy, uint64_t stream, const ffl_source_info *si) {
+    return upload_device(c, "ffl_upload_frames_device16", first, n, frames, fmt, 2, depth, msb_aligned != 0, sw, sh, rw, rh, cx, cy,
+                         stream, si);
 }
 
 // Flow slots -> caller device memory on stream `post`, ordered after the batches that produced them and the caller's

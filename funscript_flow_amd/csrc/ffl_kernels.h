@@ -68,16 +68,19 @@ struct FrameDesc {  // where one source frame's bytes lie on the device
     long long pitch0, pitch1, pitch2;
     long long ps, cs;             // plane 0: bytes between horizontal neighbours / between the channels of a pixel
     int c_step;                   // 4:2:0: bytes between horizontally adjacent chroma samples (1 I420, 2 NV12; YUV16: 2, 4)
-    int wx, wy;                   // origin of the window the planes hold inside the frame (even; 0, 0: the whole frame)
+    int wx, wy;                   // origin of the window the planes hold inside the STORED frame (even; 0, 0: the whole frame)
     int fslot;                    // k_frontend_dev: destination frame slot
 };
 struct FrontParams {  // what the frames of one launch share
     int kind, rgb;               // FFL_SRC_*; rgb: channel 0 is R
-    int sw, sh;                  // full source size: source coordinates and their clamps stay in these terms
+    int sw, sh;                  // full UPRIGHT source size (rule Y6): source coordinates and their clamps stay in these terms
     int cx, cy, ow, oh;          // crop origin inside the resized image, output size
     double scale_x, scale_y;     // 1. / ((double)resize / src), formed on the host
     int mode;                    // FFL_FRONT_*
     int shift16, round16;        // FFL_SRC_YUV16, rule Y5: v8 = min(255, (raw + round16) >> shift16)
+    int src;                     // the launch carries stream metadata: a map other than the identity, or full range
+    int ax, bx, cx0, ay, by, cy0;  // rule Y6: upright (x, y) is stored (ax x + bx y + cx0, ay x + by y + cy0)
+    int full;                    // rule Y7: full-range 4:2:0
 };
 // k_export_flows: the flow slots of one launch (at most FFL_MAXB) travel as a kernel argument
 struct ExportTab {

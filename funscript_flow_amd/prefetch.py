@@ -199,9 +199,19 @@ class PrefetchRing:
 
 
 def yuv_params(params):
-    """(params["hip_yuv"], the depth keywords of frontend.DecodedUploader): params["hip_yuv_depth"] and the optional
-    params["hip_yuv_msb"] travel only when they are set, so that without them nothing changes"""
+    """(params["hip_yuv"], the depth and stream-metadata keywords of frontend.DecodedUploader): params["hip_yuv_depth"],
+    the optional params["hip_yuv_msb"] and the stream's params["hip_rotate"] (0, 90, 180, 270), params["hip_mirror"] and
+    params["hip_yuv_range"] ("limited" | "full"; DESIGN.md appendix Y, rules Y6 and Y7) travel only when they are set,
+    so that without them nothing changes.  Nothing is read from the capture: the caller knows what its decoder delivers
+    (PyAV / ffprobe report the rotation and range; a cv2.VideoCapture BGR frame is upright already).  The pinned ring stays
+    sized by the stored frame."""
     deep = {}
+    if params.get("hip_rotate") is not None:
+        deep["rotate"] = int(params["hip_rotate"])
+    if params.get("hip_mirror") is not None:
+        deep["mirror"] = bool(params["hip_mirror"])
+    if params.get("hip_yuv_range") is not None:
+        deep["yuv_range"] = params["hip_yuv_range"]
     if params.get("hip_yuv_depth") is not None:
         deep["depth"] = int(params["hip_yuv_depth"])
     if params.get("hip_yuv_msb") is not None:

@@ -127,6 +127,35 @@ int ffl_upload_frames_raw(ffl_ctx *ctx, int first_slot, int n, const uint8_t *co
                           int src_height, ptrdiff_t stride_bytes, int rgb_order, int resize_width, int resize_height,
                           int crop_x, int crop_y);
 
+/* Stream metadata of the frames of one call (rules Y6 and Y7): what cv2.VideoCapture.read applies
+ * to every frame before the reference sees a pixel (FF:178) and a decoder's raw planes do not carry.
+ *   Y6  `rotate` in {0, 90, 180, 270} is the clockwise rotation that makes the stored src_width x src_height frame S
+ *       upright, `mirror` in {0, 1} a left-right flip applied after it: U = np.rot90(S, -rotate / 90), then U[:, ::-1].
+ *       Every rule of the call then applies to U: resize size, crop, resize mode, clamps and scales are in upright
+ *       terms (U is src_height x src_width for 90 / 270); src_width, src_height, strides, pitches, planes and the
+ *       transfer window stay in stored terms.  A pure index permutation: the operand is, bit for bit, that of the
+ *       upright frame.  4:2:0 chroma stays sample (x >> 1, y >> 1) of the stored planes.
+ *   Y7  `full_range` in {0, 1}, 4:2:0 sources only: 1 converts full-range ("JPEG", yuvj420p) samples with no offset and
+ *       no 255/219 gain, B = sat8((yh + 1858077 u) >> 20), G = sat8((yh - 748826 v - 360853 u) >> 20), R = sat8((yh +
+ *       1470104 v) >> 20) with yh = (Y << 20) + (1 << 19), u = U - 128, v = V - 128; 0 is appendix Y as it stands.  The
+ *       library's own rule: swscale's table conversion is not reproducible and cv2 has no full-range 4:2:0 code.
+ * Every front-end entry point has a sibling named with a _src suffix that takes its arguments plus this struct.  NULL or
+ * all zeros is the call without the suffix, bit for bit, with the same messages.  Refused before any device work with
+ * FFL_ERR_INVALID (the message names the rule): a rotate other than the four values, mirror or full_range outside 0 / 1,
+ * full_range on a source that is not 4:2:0, and every refusal of the plain call, those about resize and crop in upright
+ * terms.  A BGR frame out of cv2.VideoCapture.read is upright already: rotating it again is wrong. */
+typedef struct ffl_source_info {
+    int rotate;
+    int mirror;
+    int full_range;
+} ffl_source_info;
+
+/* ffl_upload_frames_raw for a stored frame with stream metadata (rule Y6 of ffl_source_info, FF:178): the operand of the
+ * upright frame.  The whole stored frame travels, as without metadata; full_range is refused (BGR carries no range). */
+int ffl_upload_frames_raw_src(ffl_ctx *ctx, int first_slot, int n, const uint8_t *const *frames, int src_width,
+                              int src_height, ptrdiff_t stride_bytes, int rgb_order, int resize_width, int resize_height,
+                              int crop_x, int crop_y, const ffl_source_info *src);
+
 /* 4:2:0 layouts of ffl_upload_frames_yuv: cv2's single-array (H*3/2, W) uint8 frames.  I420: the Y plane, then U as
  * (H/2) x (W/2) contiguous bytes, then V (PyAV's yuv420p, `ffmpeg -pix_fmt yuv420p`).  NV12: the Y plane, then H/2 rows of
  * interleaved U,V (`ffmpeg -pix_fmt nv12`, hardware decoder surfaces). */
@@ -159,6 +188,17 @@ int ffl_upload_frames_yuv(ffl_ctx *ctx, int first_slot, int n, const uint8_t *co
 int ffl_frontend_yuv_window(int src_w, int src_h, int layout, ptrdiff_t stride_bytes, int resize_w, int resize_h,
                             int crop_x, int crop_y, int out_w, int out_h, int win[4], size_t *bytes);
 
+/* ffl_upload_frames_yuv and ffl_frontend_yuv_window for stored frames with stream metadata (rules Y6 and Y7 of
+ * ffl_source_info: display rotation, mirroring and colour range, which cv2.VideoCapture.read applies at FF:178).  The
+ * window is still a rectangle of the STORED frame: the upright span of the plain call mapped through Y6, then rounded out
+ * on the stored axes (16 samples in x, 2 in y, all even, clamped); only it is transferred, under the same zero-copy rule. */
+int ffl_upload_frames_yuv_src(ffl_ctx *ctx, int first_slot, int n, const uint8_t *const *frames, int src_width,
+                              int src_height, ptrdiff_t stride_bytes, int layout, int resize_width, int resize_height,
+                              int crop_x, int crop_y, const ffl_source_info *src);
+int ffl_frontend_yuv_window_src(int src_w, int src_h, int layout, ptrdiff_t stride_bytes, int resize_w, int resize_h,
+                                int crop_x, int crop_y, int out_w, int out_h, int win[4], size_t *bytes,
+                                const ffl_source_info *src);
+
 /* High-bit-depth 4:2:0 (rule Y5): the same single-array layouts with uint16 little-endian samples,
  * shape (H*3/2, W) counted in samples -- `ffmpeg -pix_fmt yuv420p10le|yuv420p12le` (FFL_YUV_I420, the significant bits
  * low: msb_aligned 0) and P010 / P012 / P016 decoder surfaces (FFL_YUV_NV12, the significant bits high: msb_aligned 1).
@@ -179,6 +219,15 @@ int ffl_upload_frames_yuv16(ffl_ctx *ctx, int first_slot, int n, const uint16_t 
  * samples) for the same geometry, *bytes = width * height * 3.  The refusals of ffl_upload_frames_yuv16. */
 int ffl_frontend_yuv16_window(int src_w, int src_h, int layout, ptrdiff_t stride_bytes, int depth, int resize_w,
                               int resize_h, int crop_x, int crop_y, int out_w, int out_h, int win[4], size_t *bytes);
+
+/* The two 16-bit calls with stream metadata (rules Y6 and Y7 of ffl_source_info, FF:178): as ffl_upload_frames_yuv_src and
+ * ffl_frontend_yuv_window_src; rule Y5 reduces each sample first, unchanged, and Y7 then applies to the 8-bit values. */
+int ffl_upload_frames_yuv16_src(ffl_ctx *ctx, int first_slot, int n, const uint16_t *const *frames, int src_width,
+                                int src_height, ptrdiff_t stride_bytes, int layout, int depth, int msb_aligned,
+                                int resize_width, int resize_height, int crop_x, int crop_y, const ffl_source_info *src);
+int ffl_frontend_yuv16_window_src(int src_w, int src_h, int layout, ptrdiff_t stride_bytes, int depth, int resize_w,
+                                  int resize_h, int crop_x, int crop_y, int out_w, int out_h, int win[4], size_t *bytes,
+                                  const ffl_source_info *src);
 
 /* ---- device-memory I/O ------------------------------------------------------------------------
  * Frames that already live in device memory (a GPU decoder's surfaces, torch tensors) go to frame slots without a round
@@ -243,6 +292,22 @@ int ffl_dev_frame_check16(int format, int depth, int src_w, int src_h, const ffl
 int ffl_upload_frames_device16(ffl_ctx *ctx, int first_slot, int n, const ffl_dev_frame *frames, int format, int depth,
                                int msb_aligned, int src_w, int src_h, int resize_w, int resize_h, int crop_x, int crop_y,
                                uint64_t stream);
+
+/* The four device-memory calls for stored frames with stream metadata (rules Y6 and Y7 of ffl_source_info: the display
+ * rotation, mirroring and colour range cv2.VideoCapture.read applies at FF:178; a GPU decoder's surfaces carry neither).
+ * src_w, src_h, the pitches, the extents and the one-allocation-per-plane check stay on the stored frame; resize and crop
+ * are in upright terms, and an oriented gray frame's UPRIGHT size must be the context's.  Stream contract, slot publishing
+ * and the single k_frontend_dev launch are those of the plain calls. */
+int ffl_dev_frame_check_src(int format, int src_w, int src_h, const ffl_dev_frame *f, int resize_w, int resize_h, int crop_x,
+                            int crop_y, int out_w, int out_h, const ffl_source_info *src);
+int ffl_dev_frame_check16_src(int format, int depth, int src_w, int src_h, const ffl_dev_frame *f, int resize_w, int resize_h,
+                              int crop_x, int crop_y, int out_w, int out_h, const ffl_source_info *src);
+int ffl_upload_frames_device_src(ffl_ctx *ctx, int first_slot, int n, const ffl_dev_frame *frames, int format, int src_w,
+                                 int src_h, int resize_w, int resize_h, int crop_x, int crop_y, uint64_t stream,
+                                 const ffl_source_info *src);
+int ffl_upload_frames_device16_src(ffl_ctx *ctx, int first_slot, int n, const ffl_dev_frame *frames, int format, int depth,
+                                   int msb_aligned, int src_w, int src_h, int resize_w, int resize_h, int crop_x, int crop_y,
+                                   uint64_t stream, const ffl_source_info *src);
 
 /* The finished flow fields of flow_slots[0..n) -> dst + i * item_stride_bytes, as (H, W, 2) float32 (FFL_FLOW_NHWC) or as
  * (2, H, W) float32 (FFL_FLOW_NCHW); each item is contiguous, items may be anywhere apart (|stride| >= 8 * W * H bytes).
