@@ -28,6 +28,7 @@ EXPORTS = ["ffl_device_count", "ffl_create", "ffl_destroy", "ffl_last_error", "f
            "ffl_upload_frames_yuv16", "ffl_frontend_yuv16_window", "ffl_dev_frame_check16", "ffl_upload_frames_device16",
            "ffl_dev_frame_check", "ffl_upload_frames_device", "ffl_export_flows",
            "ffl_dev_flow_check", "ffl_import_flows", "ffl_radial_window",
+           "ffl_radial_axes", "ffl_radial_window_axes", "ffl_axes_extra_bytes",
            "ffl_upload_frames_raw_src", "ffl_upload_frames_yuv_src", "ffl_upload_frames_yuv16_src", "ffl_frontend_yuv_window_src",
            "ffl_frontend_yuv16_window_src", "ffl_dev_frame_check_src", "ffl_dev_frame_check16_src",
            "ffl_upload_frames_device_src", "ffl_upload_frames_device16_src"]
@@ -54,6 +55,13 @@ PASS2_DTYPE = np.dtype({"names": ["dot", "cx", "cy", "mean_mag", "div_val", "x",
                         "formats": ["<f8", "<f8", "<f8", "<f4", "<f4", "<i4", "<i4", "<i4", "<i4"],
                         "offsets": [0, 8, 16, 24, 28, 32, 36, 40, 44], "itemsize": 48})
 FFL_MAX_RADIUS = 32
+# the four motion components about the centre: FFL_AXIS_* in order, and ffl_axes_record -- a
+# PASS2_DTYPE record, then components 1..3 and `reserved`
+AXES = ("radial", "tangential", "shift_x", "shift_y")
+PASS2_AXES_DTYPE = np.dtype({"names": PASS2_DTYPE.names + AXES[1:] + ("reserved",),
+                             "formats": [PASS2_DTYPE.fields[k][0] for k in PASS2_DTYPE.names] + ["<f8"] * 4,
+                             "offsets": [PASS2_DTYPE.fields[k][1] for k in PASS2_DTYPE.names] + [48, 56, 64, 72],
+                             "itemsize": 80})
 
 FLOWS = ("farneback", "dis")   # params["hip_flow"]: the reference's CPU/CUDA/OpenCL branch, or its "DNN" branch (FF:948-980)
 DIS_STAGES = {"pass1": 0, "pass2": 1, "dense": 2, "refined": 3, "images": 4}   # ffl_debug_dis_pair stages
@@ -551,6 +559,9 @@ def load():
     L.ffl_dev_flow_check.argtypes = [C.c_int] * 4 + [vp]
     L.ffl_import_flows.argtypes = [vp, C.c_int, ip, vp, C.c_int, C.c_int, C.c_uint64]
     L.ffl_radial_window.argtypes = [vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, C.c_uint64]
+    L.ffl_radial_axes.argtypes = L.ffl_radial.argtypes
+    L.ffl_radial_window_axes.argtypes = L.ffl_radial_window.argtypes
+    L.ffl_axes_extra_bytes.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_size_t)]
     for name in EXPORTS:   # every _src sibling: the plain call's arguments plus const ffl_source_info *
         if name.endswith("_src"):
             getattr(L, name).argtypes = getattr(L, name[:-4]).argtypes + [vp]
@@ -593,6 +604,16 @@ def estimate_bytes(width, height, frame_slots, flow_slots, max_batch):
     if L.ffl_estimate_bytes(int(width), int(height), int(frame_slots), int(flow_slots), int(max_batch), C.byref(d), C.byref(p)) != FFL_OK:
         raise FFLError(f"ffl_estimate_bytes failed: {L.ffl_last_error(None).decode()}")
     return d.value, p.value
+
+
+def axes_extra_bytes(width, height):
+    """Device bytes the first radial_axes / radial_window_axes call of a Context of this size allocates (estimate_bytes does
+    not count them)."""
+    b = C.c_size_t()
+    L = load()
+    if L.ffl_axes_extra_bytes(int(width), int(height), C.byref(b)) != FFL_OK:
+        raise FFLError(f"ffl_axes_extra_bytes failed: {L.ffl_last_error(None).decode()}")
+    return b.value
 
 
 def _iarr(v):
@@ -918,14 +939,28 @@ class Context:
                                            v.ctypes.data_as(f32), mm.ctypes.data_as(f32), c.ctypes.data_as(C.POINTER(C.c_int))))
         return list(zip(x.tolist(), y.tolist(), list(v), list(mm), (c != 0).tolist()))
 
-    def radial(self, flow_slots, centers, is_cut, pov_mode=False):
+    def _radial(self, call, out, flow_slots, centers, is_cut, pov_mode):
         n = len(flow_slots)
-        out = np.empty(n, np.float64)
         cen = np.asarray(centers, np.float64).reshape(n, 2)
         (ps, ks), (px, kx), (py, ky) = _iarr(flow_slots), _darr(cen[:, 0]), _darr(cen[:, 1])
         pc, kc = _iarr(np.asarray(is_cut, bool))
-        self._chk(self.L.ffl_radial(self._h, n, ps, px, py, pc, int(bool(pov_mode)), out.ctypes.data_as(C.POINTER(C.c_double))))
-        return out.tolist()
+        self._chk(call(self._h, n, ps, px, py, pc, int(bool(pov_mode)), out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def radial(self, flow_slots, centers, is_cut, pov_mode=False):
+        return self._radial(self.L.ffl_radial, np.empty(len(flow_slots), np.float64), flow_slots, centers, is_cut, pov_mode).tolist()
+
+    def radial_axes(self, flow_slots, centers, is_cut, pov_mode=False):
+        """radial with the four components of AXES per item (ffl_radial_axes): float64[n, 4]; column 0
+        has the bits of radial()."""
+        return self._radial(self.L.ffl_radial_axes, np.empty((len(flow_slots), len(AXES)), np.float64), flow_slots, centers,
+                            is_cut, pov_mode)
+
+    def radial_window_axes(self, seq_slots, first, n, out, radius=6, cut_threshold=7.0, pov_mode=False, stream=None):
+        """radial_window with PASS2_AXES_DTYPE records (ffl_radial_window_axes): `out` is device memory of at least n * 80
+        bytes; a record's first 48 bytes are radial_window's, its further components the bits of radial_axes."""
+        return self._radial_window(self.L.ffl_radial_window_axes, "radial_window_axes", PASS2_AXES_DTYPE, seq_slots, first, n,
+                                   out, radius, cut_threshold, pov_mode, stream)
 
     def radial_window(self, seq_slots, first, n, out, radius=6, cut_threshold=7.0, pov_mode=False, stream=None):
         """The centre window, the cut test and pass 2 on the device without a host round trip (ffl_radial_window, DESIGN.md
@@ -934,12 +969,16 @@ class Context:
         radial, bit for bit.  `out`: device memory of at least n * 48 bytes (anything with __cuda_array_interface__, a
         torch tensor included).  Ordered after the batches that produced the slots and the work queued on `stream` (None:
         torch's current stream); `stream` waits for the records.  The host does not wait.  Returns `out`."""
+        return self._radial_window(self.L.ffl_radial_window, "radial_window", PASS2_DTYPE, seq_slots, first, n, out, radius,
+                                   cut_threshold, pov_mode, stream)
+
+    def _radial_window(self, call, name, dtype, seq_slots, first, n, out, radius, cut_threshold, pov_mode, stream):
         ptr, extent = _device_span(out)   # the records are written back to back
-        if extent < int(n) * PASS2_DTYPE.itemsize:
-            raise ValueError(f"radial_window: out holds {extent} bytes, {int(n)} records need {int(n) * PASS2_DTYPE.itemsize}")
+        if extent < int(n) * dtype.itemsize:
+            raise ValueError(f"{name}: out holds {extent} bytes, {int(n)} records need {int(n) * dtype.itemsize}")
         ps, ks = _iarr(seq_slots)
-        self._chk(self.L.ffl_radial_window(self._h, len(ks), ps, int(first), int(n), int(radius), float(cut_threshold),
-                                           int(bool(pov_mode)), ptr, stream_handle(stream, self.device)))
+        self._chk(call(self._h, len(ks), ps, int(first), int(n), int(radius), float(cut_threshold), int(bool(pov_mode)), ptr,
+                       stream_handle(stream, self.device)))
         return out
 
     def download_frame(self, fslot):

@@ -341,6 +341,12 @@ struct ffl_ctx {
     DevBuf<WindowItem> d_wtab; PinBuf<WindowItem> h_wtab;  // pass-2 items, FFL_MAXB entries (host: ffl_radial; device: k_window_plan)
     DevBuf<double> d_wytab;                            // pass-2 row weights (h - y) / h and y / h
     PinBuf<Pass2Record> h_radial; Pass2Record *d_radial = nullptr;  // ffl_radial's mapped pinned records (only `dot` is used) and their device alias
+    // The four-component calls (ffl_radial_axes, ffl_radial_window_axes) have partials and pinned
+    // records of their own, allocated by their first call (axes_scratch) and held to ffl_destroy: FFL_NAXES *
+    // ffl_radial_blocks doubles per item for FFL_MAXB items, under the single-copy rule above -- stream `post` alone
+    // touches them, so a single-component call queued between two of these never sees or disturbs them.
+    DevBuf<double> d_apsum;
+    PinBuf<AxesRecord> h_axes; AxesRecord *d_axes = nullptr;  // ffl_radial_axes' mapped pinned records and their device alias
     int p1_blocks = 0;
     // profiling
     unsigned prof_mask = 0;   // bit k set: bracket every launch of kernel class k with HIP events
@@ -2098,21 +2104,59 @@ int ffl_pass1_results(ffl_ctx *c, int n, const int *slots, float cut_threshold, 
     return FFL_OK;
 }
 
-int ffl_radial(ffl_ctx *c, int n, const int *slots, const double *cx, const double *cy, const int *is_cut, int pov_mode,
-               double *out) {
+// What the four-component calls add to a context (ffl_axes_extra_bytes sums it, axes_scratch allocates it).
+static size_t axes_psum_doubles(int w, int h) { return (size_t)FFL_NAXES * (size_t)ffl_radial_blocks(w, h) * FFL_MAXB; }
+
+int ffl_axes_extra_bytes(int width, int height, size_t *bytes) {
+    if (!bytes) return set_err(nullptr, FFL_ERR_INVALID, "ffl_axes_extra_bytes: bytes is NULL");
+    if (!frame_size_ok(width, height)) return set_err(nullptr, FFL_ERR_INVALID, "ffl_axes_extra_bytes: " FFL_FRAME_SIZE_RULE, width, height);
+    *bytes = sizeof(double) * axes_psum_doubles(width, height);  // + sizeof(AxesRecord) * FFL_MAXB of page-locked host memory
+    return FFL_OK;
+}
+
+// The first four-component call allocates their scratch (the caller holds post_mu and the context lock).
+static int axes_scratch(ffl_ctx *c, const char *fn) {
+    if (c->d_apsum && c->h_axes) return FFL_OK;
+    hipError_t e = c->d_apsum ? hipSuccess : c->d_apsum.alloc(axes_psum_doubles(c->w, c->h));
+    if (e != hipSuccess) c->d_apsum.release();  // nothing was allocated
+    if (e == hipSuccess && !c->h_axes) {
+        e = c->h_axes.alloc(FFL_MAXB, hipHostMallocMapped);
+        if (e != hipSuccess) c->h_axes.release();
+        else if ((e = hipHostGetDevicePointer((void **)&c->d_axes, c->h_axes, 0)) != hipSuccess) (void)c->h_axes.reset();
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return set_err(c, FFL_ERR_HIP, "%s: allocating the four-component scratch (%zu bytes + %zu page-locked) failed: %s", fn,
+                       sizeof(double) * axes_psum_doubles(c->w, c->h), sizeof(AxesRecord) * FFL_MAXB, hipGetErrorString(e));
+    }
+    return FFL_OK;
+}
+
+// The radial pair of either form over the items of c->d_wtab, into Pass2Record (axes = false) or AxesRecord records.
+static void launch_radial_pair(ffl_ctx *c, bool axes, int n, int pov_mode, void *rec) {
+    if (axes)
+        ffl_launch_radial_axes(c->d_wtab, n, c->w, c->h, pov_mode, c->d_wytab, c->d_apsum, (AxesRecord *)rec, c->s_post);
+    else
+        ffl_launch_radial(c->d_wtab, n, c->w, c->h, pov_mode, c->d_wytab, c->d_rpsum, (Pass2Record *)rec, c->s_post);
+}
+
+// ffl_radial (axes = false: out[i]) and ffl_radial_axes (out[i * FFL_N_AXES + component]): one protocol.
+static int radial_call(ffl_ctx *c, const char *fn, bool axes, int n, const int *slots, const double *cx, const double *cy,
+                       const int *is_cut, int pov_mode, double *out) {
     if (!c) return FFL_ERR_INVALID;
-    std::unique_lock<std::mutex> pl(c->post_mu);  // one pass-2 call at a time owns stream `post`, h_wtab and h_radial
+    std::unique_lock<std::mutex> pl(c->post_mu);  // one pass-2 call at a time owns stream `post`, h_wtab and h_radial / h_axes
     CtxLock lk(c->mu);
-    if (n < 1 || n > FFL_MAXB || !slots || !cx || !cy || !out) return set_err(c, FFL_ERR_INVALID, "ffl_radial: bad arguments");
-    if (int rc = check_flow_slots(c, "ffl_radial", n, slots, "flow", nullptr)) return rc;
+    if (n < 1 || n > FFL_MAXB || !slots || !cx || !cy || !out) return set_err(c, FFL_ERR_INVALID, "%s: bad arguments", fn);
+    if (int rc = check_flow_slots(c, fn, n, slots, "flow", nullptr)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
+    const int nc = axes ? FFL_N_AXES : 1;
     WindowItem *tab = c->h_wtab;  // the previous call waited for s_post, so the pinned copy is free
     WaitOnce wait_post(c->s_post);
     int m = 0;
     int map[FFL_MAXB], used[FFL_MAXB];  // the slots pass 2 reads and their places in `out`
     for (int i = 0; i < n; i++) {
         if (is_cut && is_cut[i]) {  // FF:766-767: a cut returns 0.0 without looking at the flow
-            out[i] = 0.0;
+            for (int k = 0; k < nc; k++) out[(size_t)i * nc + k] = 0.0;
             continue;
         }
         HIPCHK(c, wait_post(c->ev_slot_done[slots[i]].get()));
@@ -2121,23 +2165,46 @@ int ffl_radial(ffl_ctx *c, int n, const int *slots, const double *cx, const doub
         map[m++] = i;
     }
     if (m == 0) return FFL_OK;
+    if (axes)
+        if (int rc = axes_scratch(c, fn)) return rc;
     hipStream_t st = c->s_post;
     {
         HIPCHK(c, hipMemcpyAsync(c->d_wtab, tab, sizeof(WindowItem) * m, hipMemcpyHostToDevice, st));
         ProfScope ps(c, FFL_K_RADIAL, st);
-        ffl_launch_radial(c->d_wtab, m, c->w, c->h, pov_mode, c->d_wytab, c->d_rpsum, c->d_radial, st);
+        launch_radial_pair(c, axes, m, pov_mode, axes ? (void *)c->d_axes : (void *)c->d_radial);
     }
     // the slots' "last use" now includes this pass 2: the wait below runs without the context lock, so another thread
     // may queue a batch that recycles one of these slots meanwhile -- it must run behind the kernel that reads them
     EvRef ev;
     if (int rc = publish_post(c, m, used, &ev)) return rc;
     lk.unlock();  // the wait (for the batches the slots come from, then pass 2) does not hold up uploads / submissions
-    hipError_t se = hipStreamSynchronize(st);  // k_radial_final stored into the mapped pinned buffer
+    hipError_t se = hipStreamSynchronize(st);  // the final kernel stored into the mapped pinned buffer
     lk.lock();
     HIPCHK(c, se);
     HIPCHK(c, hipGetLastError());
-    for (int j = 0; j < m; j++) out[map[j]] = c->h_radial[j].dot;
+    for (int j = 0; j < m; j++) {
+        if (!axes) {
+            out[map[j]] = c->h_radial[j].dot;
+            continue;
+        }
+        const AxesRecord &r = c->h_axes[j];
+        double *o = out + (size_t)map[j] * FFL_N_AXES;
+        o[FFL_AXIS_RADIAL] = r.base.dot;
+        o[FFL_AXIS_TANGENTIAL] = r.tangential;
+        o[FFL_AXIS_SHIFT_X] = r.shift_x;
+        o[FFL_AXIS_SHIFT_Y] = r.shift_y;
+    }
     return FFL_OK;
+}
+
+int ffl_radial(ffl_ctx *c, int n, const int *slots, const double *cx, const double *cy, const int *is_cut, int pov_mode,
+               double *out) {
+    return radial_call(c, "ffl_radial", false, n, slots, cx, cy, is_cut, pov_mode, out);
+}
+
+int ffl_radial_axes(ffl_ctx *c, int n, const int *slots, const double *cx, const double *cy, const int *is_cut, int pov_mode,
+                    double *out) {
+    return radial_call(c, "ffl_radial_axes", true, n, slots, cx, cy, is_cut, pov_mode, out);
 }
 
 int ffl_download_flow(ffl_ctx *c, int slot, float *dst) {
@@ -2473,10 +2540,20 @@ static_assert(sizeof(ffl_pass2_record) == 48 && sizeof(Pass2Record) == 48 && off
               offsetof(ffl_pass2_record, mean_mag) == offsetof(Pass2Record, mean_mag) && offsetof(ffl_pass2_record, x) == offsetof(Pass2Record, x) &&
               offsetof(ffl_pass2_record, cut) == offsetof(Pass2Record, cut), "Pass2Record mirrors ffl_pass2_record");
 static_assert(FFL_MAX_RADIUS == FFL_WINDOW_MAX_RADIUS && FFL_MAX_BATCH == FFL_MAXB, "ffl.h and ffl_kernels.h agree");
-int ffl_radial_window(ffl_ctx *c, int n_seq, const int *seq, int first, int n, int radius, float cut_threshold, int pov_mode,
-                      ffl_pass2_record *out, uint64_t stream) {
-    static const char *fn = "ffl_radial_window";
+static_assert(sizeof(ffl_axes_record) == 80 && sizeof(AxesRecord) == 80 && offsetof(ffl_axes_record, base) == 0 &&
+              offsetof(AxesRecord, base) == 0 && offsetof(ffl_axes_record, tangential) == 48 &&
+              offsetof(ffl_axes_record, tangential) == offsetof(AxesRecord, tangential) &&
+              offsetof(ffl_axes_record, shift_x) == offsetof(AxesRecord, shift_x) &&
+              offsetof(ffl_axes_record, shift_y) == offsetof(AxesRecord, shift_y) &&
+              offsetof(ffl_axes_record, reserved) == offsetof(AxesRecord, reserved) && alignof(ffl_axes_record) == 8,
+              "AxesRecord mirrors ffl_axes_record");
+static_assert(FFL_N_AXES == FFL_NAXES && FFL_AXIS_RADIAL == 0 && FFL_AXIS_TANGENTIAL == 1 && FFL_AXIS_SHIFT_X == 2 &&
+              FFL_AXIS_SHIFT_Y == 3, "ffl.h and ffl_kernels.h agree on the components");
+// ffl_radial_window (axes = false: ffl_pass2_record) and ffl_radial_window_axes (ffl_axes_record): one protocol.
+static int radial_window_call(ffl_ctx *c, const char *fn, bool axes, int n_seq, const int *seq, int first, int n, int radius,
+                              float cut_threshold, int pov_mode, void *out, uint64_t stream) {
     if (!c) return FFL_ERR_INVALID;
+    const size_t rec_bytes = axes ? sizeof(ffl_axes_record) : sizeof(ffl_pass2_record);
     std::unique_lock<std::mutex> pl(c->post_mu);  // stream `post`, post_ring and d_rpsum, as ffl_radial / ffl_export_flows
     CtxLock lk(c->mu);
     if (n < 1 || n > FFL_MAX_BATCH) return set_err(c, FFL_ERR_INVALID, "%s: n = %d items outside 1..%d (FFL_MAX_BATCH)", fn, n, FFL_MAX_BATCH);
@@ -2493,16 +2570,29 @@ int ffl_radial_window(ffl_ctx *c, int n_seq, const int *seq, int first, int n, i
     if (int rc = check_flow_slots(c, fn, n_seq, seq, "result", "repeated in one call")) return rc;
     if ((uintptr_t)out % 8) return set_err(c, FFL_ERR_INVALID, "%s: out_dev must be 8-byte aligned", fn);
     hipStream_t cst;
-    if (int rc = post_begin(c, fn, stream, &cst, "out_dev", out, sizeof(ffl_pass2_record) * (size_t)n,
+    if (int rc = post_begin(c, fn, stream, &cst, "out_dev", out, rec_bytes * (size_t)n,
                             "results in host memory come from ffl_pass1_results and ffl_radial", n_seq, seq))
         return rc;
     WindowSeq t;
     for (int i = 0; i < n_seq; i++) t.slot[i] = seq[i];
-    Pass2Record *rec = reinterpret_cast<Pass2Record *>(out);
-    // not timed under FFL_K_RADIAL: that class counts the k_radial + k_radial_final pairs of ffl_radial, one per call
-    ffl_launch_window_plan(t, n_seq, first, n, radius, cut_threshold, c->d_res, c->d_flow, c->w, c->h, c->d_wtab, rec, c->s_post);
-    ffl_launch_radial(c->d_wtab, n, c->w, c->h, pov_mode ? 1 : 0, c->d_wytab, c->d_rpsum, rec, c->s_post);
+    if (axes)
+        if (int rc = axes_scratch(c, fn)) return rc;
+    // not timed under FFL_K_RADIAL: that class counts the radial pairs of ffl_radial / ffl_radial_axes, one per call
+    ffl_launch_window_plan(t, n_seq, first, n, radius, cut_threshold, c->d_res, c->d_flow, c->w, c->h, c->d_wtab, out,
+                           (int)rec_bytes, c->s_post);
+    launch_radial_pair(c, axes, n, pov_mode ? 1 : 0, out);
     return post_end(c, cst, n_seq, seq);
+}
+
+int ffl_radial_window(ffl_ctx *c, int n_seq, const int *seq, int first, int n, int radius, float cut_threshold, int pov_mode,
+                      ffl_pass2_record *out, uint64_t stream) {
+    return radial_window_call(c, "ffl_radial_window", false, n_seq, seq, first, n, radius, cut_threshold, pov_mode, out, stream);
+}
+
+int ffl_radial_window_axes(ffl_ctx *c, int n_seq, const int *seq, int first, int n, int radius, float cut_threshold, int pov_mode,
+                           ffl_axes_record *out, uint64_t stream) {
+    return radial_window_call(c, "ffl_radial_window_axes", true, n_seq, seq, first, n, radius, cut_threshold, pov_mode, out,
+                              stream);
 }
 
 // ---- flow import -------------------------------------------------------------------------------

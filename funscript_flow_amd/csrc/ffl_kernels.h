@@ -251,14 +251,27 @@ struct Pass2Record { // = ffl_pass2_record of include/ffl.h (ffl_api.hip asserts
     float mean_mag, div_val;
     int x, y, cut, pad;
 };
+struct AxesRecord {  // = ffl_axes_record of include/ffl.h (ffl_api.hip asserts the layout)
+    Pass2Record base;   // base.dot = component 0
+    double tangential, shift_x, shift_y, reserved;
+};
+#define FFL_NAXES 4                  // = FFL_N_AXES of include/ffl.h
+// workgroups (= partial results per component) of a pass-2 grid per item
+int ffl_radial_blocks(int w, int h);
 // items tab[0..n) -> out[i].dot (+0.0 for a cut item); psum holds the partials of n items, ffl_pass1_blocks(w, h) each at most
 // wytab: 2 * h doubles, [y] = (double)(h - y) / h, [h + y] = (double)y / h (the row weights of FF:780-783)
 void ffl_launch_radial(const WindowItem *tab, int n, int w, int h, int pov_mode, const double *wytab, double *psum,
                        Pass2Record *out, hipStream_t st);
-// items first .. first+n-1 of seq -> tab[0..n) and every field of out[0..n) but `dot`
+// The four-component form (k_radial_axes, k_radial_axes_final): items tab[0..n) -> out[i].base.dot,
+// tangential, shift_x, shift_y and reserved = +0.0 (all +0.0 for a cut item).  psum: FFL_NAXES * ffl_radial_blocks(w, h)
+// doubles per item, component c of item b at psum[(b * FFL_NAXES + c) * nblk ..]
+void ffl_launch_radial_axes(const WindowItem *tab, int n, int w, int h, int pov_mode, const double *wytab, double *psum,
+                            AxesRecord *out, hipStream_t st);
+// items first .. first+n-1 of seq -> tab[0..n) and every field but `dot` of the Pass2Record at the head of each of the n
+// records that start rec_stride bytes apart at out (sizeof(Pass2Record) or sizeof(AxesRecord))
 void ffl_launch_window_plan(const WindowSeq &seq, int n_seq, int first, int n, int radius, float cut_threshold,
-                            const Pass1Result *res, const float *flow, int w, int h, WindowItem *tab, Pass2Record *out,
-                            hipStream_t st);
+                            const Pass1Result *res, const float *flow, int w, int h, WindowItem *tab, void *out,
+                            int rec_stride, hipStream_t st);
 
 // ---- index rules shared by the kernel files ----------------------------------------------------------------------
 __device__ __forceinline__ int ffl_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }

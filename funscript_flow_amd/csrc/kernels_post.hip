@@ -13,6 +13,10 @@
 #endif
 #define P1_STRIP 126      // useful pixels of a pass-1 strip: 64 lanes x 2 pixels minus one halo pixel per side
 #define P2_STRIP 128      // pass 2 needs no halo
+#ifndef P2_AXES_G
+#define P2_AXES_G 2        // rows in flight per lane in k_radial_axes: 58 VGPRs, 8 waves per SIMD (8 rows, k_radial's: 160 VGPRs, 3 waves;
+                           // 1080p n = 32: 140 us with 8 rows, 122 with 4, 109 with 2 -- DESIGN.md section 15)
+#endif
 
 // Both passes walk the flow field in column strips: a wave owns 128 consecutive pixels of a row (two per
 // lane, one 16-byte load) and walks down P1_RG rows, so every pixel is read once with full-width loads,
@@ -24,7 +28,7 @@ static inline int ffl_strip_waves(int w, int h, int strip) {
 // workgroups (= partial results) per item: four waves each.  Pass 1's count is the larger one (P1_STRIP < P2_STRIP), so
 // scratch sized by it serves both passes.
 int ffl_pass1_blocks(int w, int h) { return (ffl_strip_waves(w, h, P1_STRIP) + 3) / 4; }
-static inline int ffl_radial_blocks(int w, int h) { return (ffl_strip_waves(w, h, P2_STRIP) + 3) / 4; }
+int ffl_radial_blocks(int w, int h) { return (ffl_strip_waves(w, h, P2_STRIP) + 3) / 4; }
 
 // np.gradient along one axis: central difference /2 inside, one-sided at the ends (FF:754)
 __device__ __forceinline__ float ffl_grad(float lo, float hi, int idx, int n) {
@@ -217,8 +221,12 @@ void ffl_launch_pass1(const PairTab *pt, int nB, int w, int h, int pov_mode, uns
 // context on the host (IEEE division, the value the device's division yields).  The row index is wave-uniform, so the
 // weight comes with a scalar load instead of a 15-instruction f64 division per lane and row -- the kernel had
 // hoisted all 16 of them and needed 198 VGPRs (2 waves per SIMD).
-// The body of k_radial: one per-lane order and one wave / workgroup reduction order, so ffl_radial and ffl_radial_window
-// give the same bits for the same slot, centre and pov_mode.
+// The body of k_radial (NC = 1) and k_radial_axes (NC = FFL_NAXES): one per-lane order and one wave / workgroup reduction
+// order for every component, so ffl_radial, ffl_radial_window and component 0 of their _axes forms give the same bits for
+// the same slot, centre and pov_mode.  Components 1..3 reuse the pixel's u, v, dx, dy and weights:
+// tangential ((v dx - u dy) wx) wy, shift_x (u wx) wy, shift_y (v wx) wy.  Component c of workgroup g of item b goes to
+// psum[(b * NC + c) * gridDim.x + g]; ssum holds NC * 4 doubles.  G: rows of the row group whose loads are in flight together.
+template <int NC, int G>
 __device__ __forceinline__ void ffl_radial_body(const float2 *__restrict__ flow, double cx, double cy, int w, int h,
                                                 int pov_mode, int b, const double *__restrict__ wytab,
                                                 double *__restrict__ psum, double *ssum) {
@@ -226,7 +234,9 @@ __device__ __forceinline__ void ffl_radial_body(const float2 *__restrict__ flow,
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int nstrips = (w + P2_STRIP - 1) / P2_STRIP, ngroups = (h + P1_RG - 1) / P1_RG;
     const int wid = blockIdx.x * (P1_THREADS / 64) + wv;  // wave-uniform
-    double sum = 0.0;
+    double sum[NC];
+#pragma unroll
+    for (int c = 0; c < NC; c++) sum[c] = 0.0;
     if (wid < nstrips * ngroups) {
         const int grp = wid / nstrips, strip = wid - grp * nstrips;
         const int x = strip * P2_STRIP + 2 * lane, y0 = grp * P1_RG;  // the lane's pixels: x, x+1
@@ -238,46 +248,73 @@ __device__ __forceinline__ void ffl_radial_body(const float2 *__restrict__ flow,
         // two groups of 8 rows: 8 row loads in flight per lane are enough to cover the latency, and the unrolled body
         // stays within 4 waves per SIMD (all 16 rows hoisted needed 191 VGPRs)
 #pragma unroll 1
-        for (int g = 0; g < P1_RG; g += 8) {
-            float2 f0[8], f1[8];
+        for (int g = 0; g < P1_RG; g += G) {
+            float2 f0[G], f1[G];
 #pragma unroll
-            for (int r = 0; r < 8; r++) ffl_load_pair(flow, w, h, x, y0 + g + r, f0[r], f1[r]);
+            for (int r = 0; r < G; r++) ffl_load_pair(flow, w, h, x, y0 + g + r, f0[r], f1[r]);
 #pragma unroll
-            for (int r = 0; r < 8; r++) {
+            for (int r = 0; r < G; r++) {
                 const int y = y0 + g + r;
                 const int yc = min(y, h - 1);  // rows past the image contribute nothing (predicated below)
                 const double dy = (double)y - cy;
                 const double wy = pov_mode ? 1.0 : (((double)y > cy) ? wytab[yc] : wytab[h + yc]);
                 const double t0 = ((double)f0[r].x * dx0 + (double)f0[r].y * dy) * wx0 * wy;
                 const double t1 = ((double)f1[r].x * dx1 + (double)f1[r].y * dy) * wx1 * wy;
-                sum += (ok0 && y < h) ? t0 : 0.0;
-                sum += (ok1 && y < h) ? t1 : 0.0;
+                sum[0] += (ok0 && y < h) ? t0 : 0.0;
+                sum[0] += (ok1 && y < h) ? t1 : 0.0;
+                if constexpr (NC > 1) {
+                    const double u0 = (double)f0[r].x, v0 = (double)f0[r].y, u1 = (double)f1[r].x, v1 = (double)f1[r].y;
+                    const double a0 = (v0 * dx0 - u0 * dy) * wx0 * wy, a1 = (v1 * dx1 - u1 * dy) * wx1 * wy;
+                    sum[1] += (ok0 && y < h) ? a0 : 0.0;
+                    sum[1] += (ok1 && y < h) ? a1 : 0.0;
+                    sum[2] += (ok0 && y < h) ? u0 * wx0 * wy : 0.0;
+                    sum[2] += (ok1 && y < h) ? u1 * wx1 * wy : 0.0;
+                    sum[3] += (ok0 && y < h) ? v0 * wx0 * wy : 0.0;
+                    sum[3] += (ok1 && y < h) ? v1 * wx1 * wy : 0.0;
+                }
             }
         }
     }
-    sum = ffl_wave_sum_f64(sum);
-    if (lane == 0) ssum[wv] = sum;
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        sum[c] = ffl_wave_sum_f64(sum[c]);
+        if (lane == 0) ssum[c * (P1_THREADS / 64) + wv] = sum[c];
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (int i = 1; i < P1_THREADS / 64; i++) sum += ssum[i];
-        psum[(size_t)b * gridDim.x + blockIdx.x] = sum;
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            for (int i = 1; i < P1_THREADS / 64; i++) sum[c] += ssum[c * (P1_THREADS / 64) + i];
+            psum[((size_t)b * NC + c) * gridDim.x + blockIdx.x] = sum[c];
+        }
     }
 }
 
-// The body of k_radial_final: item b's nblk partials in one order; the mean is valid in thread 0.
-__device__ __forceinline__ double ffl_radial_final_body(int w, int h, int nblk, int b, const double *__restrict__ psum,
-                                                        double *ssum) {
-    double sum = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += P1_THREADS) sum += psum[(size_t)b * nblk + i];
-    sum = ffl_wave_sum_f64(sum);
+// The body of k_radial_final (NC = 1) and k_radial_axes_final (NC = FFL_NAXES): each component's nblk partials of item b
+// in one order; the means are valid in thread 0.  ssum holds NC * 4 doubles.
+template <int NC>
+__device__ __forceinline__ void ffl_radial_final_body(int w, int h, int nblk, int b, const double *__restrict__ psum,
+                                                      double *ssum, double (&sum)[NC]) {
+#pragma unroll
+    for (int c = 0; c < NC; c++) sum[c] = 0.0;
+    for (int i = threadIdx.x; i < nblk; i += P1_THREADS) {
+#pragma unroll
+        for (int c = 0; c < NC; c++) sum[c] += psum[((size_t)b * NC + c) * nblk + i];
+    }
     int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) ssum[wv] = sum;
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        sum[c] = ffl_wave_sum_f64(sum[c]);
+        if (lane == 0) ssum[c * (P1_THREADS / 64) + wv] = sum[c];
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (int i = 1; i < P1_THREADS / 64; i++) sum += ssum[i];
-        sum = sum / ((double)w * (double)h);
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            for (int i = 1; i < P1_THREADS / 64; i++) sum[c] += ssum[c * (P1_THREADS / 64) + i];
+            sum[c] = sum[c] / ((double)w * (double)h);
+        }
     }
-    return sum;
 }
 
 // The radial pair over a WindowItem table in device memory: ffl_radial copies one there, ffl_radial_window has
@@ -288,7 +325,7 @@ __global__ __launch_bounds__(P1_THREADS) void k_radial(const WindowItem *__restr
     __shared__ double ssum[P1_THREADS / 64];
     const int b = blockIdx.y;
     if (tab[b].cut) return;   // workgroup-uniform: FF:766-767, a cut is 0.0 without a look at the flow
-    ffl_radial_body(reinterpret_cast<const float2 *>(tab[b].flow), tab[b].cx, tab[b].cy, w, h, pov_mode, b, wytab, psum, ssum);
+    ffl_radial_body<1, 8>(reinterpret_cast<const float2 *>(tab[b].flow), tab[b].cx, tab[b].cy, w, h, pov_mode, b, wytab, psum, ssum);
 }
 
 __global__ __launch_bounds__(P1_THREADS) void k_radial_final(const WindowItem *__restrict__ tab, int w, int h, int nblk,
@@ -299,8 +336,9 @@ __global__ __launch_bounds__(P1_THREADS) void k_radial_final(const WindowItem *_
         if (threadIdx.x == 0) out[b].dot = 0.0;
         return;
     }
-    const double mean = ffl_radial_final_body(w, h, nblk, b, psum, ssum);
-    if (threadIdx.x == 0) out[b].dot = mean;
+    double mean[1];
+    ffl_radial_final_body<1>(w, h, nblk, b, psum, ssum, mean);
+    if (threadIdx.x == 0) out[b].dot = mean[0];
 }
 
 void ffl_launch_radial(const WindowItem *tab, int n, int w, int h, int pov_mode, const double *wytab, double *psum,
@@ -310,19 +348,55 @@ void ffl_launch_radial(const WindowItem *tab, int n, int w, int h, int pov_mode,
     hipLaunchKernelGGL(k_radial_final, dim3(n), dim3(P1_THREADS), 0, st, tab, w, h, nblk, psum, out);
 }
 
+// The four-component pair: k_radial's grid, FFL_NAXES partials per workgroup, component-major per
+// item (see ffl_radial_body), so k_radial_axes_final reads each component's partials with consecutive lanes.  The records
+// are AxesRecord: whoever planned the item wrote the rest of `base`.
+__global__ __launch_bounds__(P1_THREADS) void k_radial_axes(const WindowItem *__restrict__ tab, int w, int h, int pov_mode,
+                                                            const double *__restrict__ wytab, double *__restrict__ psum) {
+    __shared__ double ssum[FFL_NAXES * (P1_THREADS / 64)];
+    const int b = blockIdx.y;
+    if (tab[b].cut) return;   // workgroup-uniform, as k_radial
+    ffl_radial_body<FFL_NAXES, P2_AXES_G>(reinterpret_cast<const float2 *>(tab[b].flow), tab[b].cx, tab[b].cy, w, h, pov_mode, b, wytab, psum,
+                               ssum);
+}
+
+__global__ __launch_bounds__(P1_THREADS) void k_radial_axes_final(const WindowItem *__restrict__ tab, int w, int h, int nblk,
+                                                                  const double *__restrict__ psum, AxesRecord *__restrict__ out) {
+    __shared__ double ssum[FFL_NAXES * (P1_THREADS / 64)];
+    const int b = blockIdx.x;
+    double mean[FFL_NAXES] = {0.0, 0.0, 0.0, 0.0};   // a cut item: its partials were never written
+    if (!tab[b].cut) ffl_radial_final_body<FFL_NAXES>(w, h, nblk, b, psum, ssum, mean);   // workgroup-uniform
+    if (threadIdx.x == 0) {
+        out[b].base.dot = mean[0];
+        out[b].tangential = mean[1];
+        out[b].shift_x = mean[2];
+        out[b].shift_y = mean[3];
+        out[b].reserved = 0.0;
+    }
+}
+
+void ffl_launch_radial_axes(const WindowItem *tab, int n, int w, int h, int pov_mode, const double *wytab, double *psum,
+                            AxesRecord *out, hipStream_t st) {
+    const int nblk = ffl_radial_blocks(w, h);
+    hipLaunchKernelGGL(k_radial_axes, dim3(nblk, n), dim3(P1_THREADS), 0, st, tab, w, h, pov_mode, wytab, psum);
+    hipLaunchKernelGGL(k_radial_axes_final, dim3(n), dim3(P1_THREADS), 0, st, tab, w, h, nblk, psum, out);
+}
+
 // ---- pass 2 behind the batches, host-free (ffl_radial_window) ---------------------------------
 // k_window_plan, then the radial pair.  One thread per item forms the clipped centre window, mean_mag and cut out of the
-// pass-1 records and writes the device-resident WindowItem table plus every field of the record but `dot`.  The records
+// pass-1 records and writes the device-resident WindowItem table plus every field of the record but `dot` (STRIDE: bytes
+// from one record to the next; each starts with a Pass2Record).  The records
 // are mapped pinned memory: a workgroup stages the (x, y) of the <= 64 + 2 * radius records its items' windows span in
 // LDS, so the window costs one (x, y) read per record and workgroup instead of 2 * radius + 1 per item; each item then
 // reads mag_sum and div_val of its own record once more.  Nothing of a record is read by the radial grid.
 #define W2_THREADS 64
 
+template <int STRIDE>
 __global__ __launch_bounds__(W2_THREADS) void k_window_plan(const WindowSeq seq, int n_seq, int first, int n, int radius,
                                                             float cut_threshold, double npx,
                                                             const Pass1Result *__restrict__ res, const float *__restrict__ flow,
                                                             size_t N, WindowItem *__restrict__ tab,
-                                                            Pass2Record *__restrict__ out) {
+                                                            char *__restrict__ out) {
     __shared__ int sx[W2_THREADS + 2 * FFL_WINDOW_MAX_RADIUS], sy[W2_THREADS + 2 * FFL_WINDOW_MAX_RADIUS];
     const int i0 = blockIdx.x * W2_THREADS;                      // the workgroup's first item
     const int j0 = first + i0, j1 = first + min(i0 + W2_THREADS, n) - 1;   // its items in seq, inclusive
@@ -354,7 +428,7 @@ __global__ __launch_bounds__(W2_THREADS) void k_window_plan(const WindowSeq seq,
     it.cut = cut;
     it.pad = 0;
     tab[i] = it;
-    Pass2Record *o = out + i;
+    Pass2Record *o = reinterpret_cast<Pass2Record *>(out + (size_t)i * STRIDE);
     o->cx = cx;
     o->cy = cy;
     o->mean_mag = mm;
@@ -366,10 +440,16 @@ __global__ __launch_bounds__(W2_THREADS) void k_window_plan(const WindowSeq seq,
 }
 
 void ffl_launch_window_plan(const WindowSeq &seq, int n_seq, int first, int n, int radius, float cut_threshold,
-                            const Pass1Result *res, const float *flow, int w, int h, WindowItem *tab, Pass2Record *out,
-                            hipStream_t st) {
-    hipLaunchKernelGGL(k_window_plan, dim3((n + W2_THREADS - 1) / W2_THREADS), dim3(W2_THREADS), 0, st, seq, n_seq, first, n,
-                       radius, cut_threshold, (double)w * (double)h, res, flow, (size_t)w * h, tab, out);
+                            const Pass1Result *res, const float *flow, int w, int h, WindowItem *tab, void *out,
+                            int rec_stride, hipStream_t st) {
+    const dim3 grid((n + W2_THREADS - 1) / W2_THREADS);
+    const double npx = (double)w * (double)h;
+    if (rec_stride == (int)sizeof(AxesRecord))
+        hipLaunchKernelGGL(k_window_plan<(int)sizeof(AxesRecord)>, grid, dim3(W2_THREADS), 0, st, seq, n_seq, first, n, radius,
+                           cut_threshold, npx, res, flow, (size_t)w * h, tab, (char *)out);
+    else
+        hipLaunchKernelGGL(k_window_plan<(int)sizeof(Pass2Record)>, grid, dim3(W2_THREADS), 0, st, seq, n_seq, first, n, radius,
+                           cut_threshold, npx, res, flow, (size_t)w * h, tab, (char *)out);
 }
 
 // ---- flow export -----------------------------------------------------------------------------

@@ -66,27 +66,35 @@ def window_calls(n_pairs, B, radius=SMOOTH_RADIUS):
     return calls
 
 
-def post_buffer(ctx, n):
+def _post_dtype(axes):
+    """the record of a chunk's device pass 2: 48 bytes, or the 80 bytes of the four-component form (axes=True)"""
+    return _capi.PASS2_AXES_DTYPE if axes else _capi.PASS2_DTYPE
+
+
+def post_buffer(ctx, n, axes=False):
     """a device buffer for the n records of a chunk (torch uint8 on the context's device), as post_out= takes it"""
     import torch
-    return torch.empty(n * _capi.PASS2_DTYPE.itemsize, dtype=torch.uint8, device=torch.device("cuda", ctx.device))
+    return torch.empty(n * _post_dtype(axes).itemsize, dtype=torch.uint8, device=torch.device("cuda", ctx.device))
 
 
-def post_records(buf, n=None, device=None):
+def post_records(buf, n=None, device=None, axes=False):
     """The one device-to-host copy of a chunk whose pass 2 ran on the device (process_chunk / process_flows with
     post_out=): (dots float64[n], records) in the form process_chunk returns them; n defaults to the records `buf` holds.
     The copy runs on torch's current stream, behind the calls that filled `buf` there, and waits for them.  A torch
     tensor names its own device; for any other __cuda_array_interface__ object `device` is the context's (default: torch's
-    current device)."""
+    current device).  axes=True: `buf` holds 80-byte records and the first item is comps float64[n, 4] (_capi.AXES)."""
     import torch
     if not isinstance(buf, torch.Tensor):
         buf = torch.as_tensor(buf, device=torch.device("cuda", torch.cuda.current_device() if device is None else device))
+    dt = _post_dtype(axes)
     raw = buf.contiguous().view(torch.uint8).reshape(-1)
-    n = raw.numel() // _capi.PASS2_DTYPE.itemsize if n is None else n
-    raw = raw[:n * _capi.PASS2_DTYPE.itemsize].cpu().numpy()
-    rec = np.frombuffer(raw.tobytes(), _capi.PASS2_DTYPE, n)
+    n = raw.numel() // dt.itemsize if n is None else n
+    raw = raw[:n * dt.itemsize].cpu().numpy()
+    rec = np.frombuffer(raw.tobytes(), dt, n)
     records = list(zip(rec["x"].tolist(), rec["y"].tolist(), list(rec["div_val"]), list(rec["mean_mag"]),
                        (rec["cut"] != 0).tolist()))
+    if axes:
+        return np.stack([rec["dot"]] + [rec[k] for k in _capi.AXES[1:]], axis=1).astype(np.float64), records
     return rec["dot"].astype(np.float64), records
 
 
@@ -299,7 +307,7 @@ class PairEngine:
         return recs
 
     def process_chunk(self, frames, pov_mode=False, cut_threshold=7.0, algo=None, farneback=OWN, flows_out=None, window=OWN,
-                      post_out=None):
+                      post_out=None, axes=False):
         """One whole chunk on one GPU: returns (dots float64[n], records) with n = len(frames)-1.  `algo`, `farneback`,
         `window`: see pass1_pairs (default: the engine's own flow algorithm, parameters and window).  `flows_out`: a float32 device array of
         (n, H, W, 2) or (n, 2, H, W) that receives every pair's flow field (Context.export_flows, on torch's current stream)
@@ -309,13 +317,16 @@ class PairEngine:
         stream, the calls of window_calls); pass1_results is never called, nothing waits for the device, and the call
         returns post_out, which post_records reads.  Frames out of a prefetch.PrefetchRing are the one exception: its
         page-locked slots are read in place by the transfers, so they are released as events on the stream complete and
-        the call returns once the chunk's last batch has run."""
+        the call returns once the chunk's last batch has run.
+        `axes`: True returns (comps float64[n, 4], records) -- the four components of _capi.AXES (Context.radial_axes;
+        column 0 has the bits of the dots) -- and with post_out a buffer of 80-byte records (_capi.PASS2_AXES_DTYPE,
+        post_records(..., axes=True))."""
         ctx, B = self.ctx, self.B
         n = len(frames) - 1
         if n < 1:
-            return (np.zeros(0), []) if post_out is None else (post_buffer(ctx, 0) if post_out is True else post_out)
+            return (_no_scalars(axes), []) if post_out is None else (post_buffer(ctx, 0, axes) if post_out is True else post_out)
         if post_out is True:
-            post_out = post_buffer(ctx, n)
+            post_out = post_buffer(ctx, n, axes)
         layout = None
         if flows_out is not None:
             shp = tuple(flows_out.shape)
@@ -325,7 +336,7 @@ class PairEngine:
                 raise ValueError(f"flows_out must be ({n}, {ctx.height}, {ctx.width}, 2) or ({n}, 2, {ctx.height}, "
                                  f"{ctx.width}), got {shp}")
         if post_out is not None:
-            post = _DevicePost(ctx, n, B, pov_mode, cut_threshold, post_out)
+            post = _DevicePost(ctx, n, B, pov_mode, cut_threshold, post_out, axes)
             release = getattr(frames, "release", None)
             marks = []   # (event, frames that have left the host once it completes), oldest first
 
@@ -352,7 +363,7 @@ class PairEngine:
                 marks[-1][0].synchronize()   # the ring's slots may be reused by the next chunk: every transfer is over
             post.finish()
             return post_out
-        post = _ChunkPost(ctx, n, B, pov_mode)
+        post = _ChunkPost(ctx, n, B, pov_mode, axes)
 
         def on_batch(js, got):
             if layout is not None:   # before pass 2 below lets later batches recycle these slots
@@ -362,14 +373,14 @@ class PairEngine:
         self.pass1(frames, 0, n, pov_mode, cut_threshold, on_batch, algo=algo, farneback=farneback, window=window)
         return post.finish()
 
-    def process_flows(self, flows, pov_mode=False, cut_threshold=7.0, post_out=None):
+    def process_flows(self, flows, pov_mode=False, cut_threshold=7.0, post_out=None, axes=False):
         """One whole chunk from flow fields the caller computed: returns (dots float64[n], records), the contract of
         process_chunk.  `flows` holds the chunk's n pair fields in device memory: one array (n, H, W, 2) or (n, 2, H, W)
         (float32, float16 or bfloat16, any strides; see _capi.device_flows) or a sequence of such arrays (single (H, W, 2)
         fields included), in pair order.  They are imported B at a time into the slot ring (Context.import_flows, on
         torch's current stream) with `depth` batches in flight; the +-6 window and pass 2 are process_chunk's own.
         `post_out`: as in process_chunk (a buffer, or True for a new one) -- pass 2 is queued on the device behind each
-        import, nothing waits, and the buffer is returned for post_records."""
+        import, nothing waits, and the buffer is returned for post_records.  `axes`: as in process_chunk."""
         ctx, B, fs = self.ctx, self.B, self.ctx.flow_slots
         segs = []   # (descriptor, dtype, first pair, count): one per source array
         n = 0
@@ -378,11 +389,11 @@ class PairEngine:
             segs.append((desc, dt, n, k))
             n += k
         if post_out is True:
-            post_out = post_buffer(ctx, n)
+            post_out = post_buffer(ctx, n, axes)
         if n < 1:
-            return (np.zeros(0), []) if post_out is None else post_out
-        post = (_ChunkPost(ctx, n, B, pov_mode) if post_out is None else
-                _DevicePost(ctx, n, B, pov_mode, cut_threshold, post_out))
+            return (_no_scalars(axes), []) if post_out is None else post_out
+        post = (_ChunkPost(ctx, n, B, pov_mode, axes) if post_out is None else
+                _DevicePost(ctx, n, B, pov_mode, cut_threshold, post_out, axes))
 
         def enqueue(j0):
             j1 = min(j0 + B, n)
@@ -414,15 +425,22 @@ class PairEngine:
         return post.finish()
 
 
+def _no_scalars(axes):
+    """the scalars of a chunk without pairs"""
+    return np.zeros((0, len(_capi.AXES))) if axes else np.zeros(0)
+
+
 class _ChunkPost:
     """The +-6 centre window and pass 2 of one chunk of n pairs (FF:1203-1236), shared by process_chunk and process_flows:
     add() takes a finished batch's pass-1 records in pair order and issues pass 2, B pairs per call, for every pair whose
     window is complete; finish() issues the rest and returns (dots, records).  Window means are exact integer prefix
-    sums / counts, bit-identical to np.mean over the window."""
+    sums / counts, bit-identical to np.mean over the window.  axes=True: pass 2 is Context.radial_axes and the dots are
+    float64[n, 4]."""
 
-    def __init__(self, ctx, n, B, pov_mode):
+    def __init__(self, ctx, n, B, pov_mode, axes=False):
         self.ctx, self.n, self.B, self.pov_mode = ctx, n, B, pov_mode
-        self.dots = np.zeros(n, np.float64)
+        self.radial = ctx.radial_axes if axes else ctx.radial
+        self.dots = np.zeros((n, len(_capi.AXES)) if axes else n, np.float64)
         self.psum = np.zeros((n + 1, 2), np.int64)   # prefix sums of pos_center
         self.cuts = np.zeros(n, bool)
         self.recs = [None] * n
@@ -435,7 +453,7 @@ class _ChunkPost:
             js = np.arange(j0, j1)
             lo, hi = np.maximum(0, js - SMOOTH_RADIUS), np.minimum(n, js + SMOOTH_RADIUS + 1)
             cs = (self.psum[hi] - self.psum[lo]) / (hi - lo)[:, None]
-            self.dots[j0:j1] = ctx.radial(list(js % ctx.flow_slots), cs, self.cuts[j0:j1], self.pov_mode)
+            self.dots[j0:j1] = self.radial(list(js % ctx.flow_slots), cs, self.cuts[j0:j1], self.pov_mode)
             self.done = j1
 
     def add(self, js, got):
@@ -454,13 +472,15 @@ class _ChunkPost:
 class _DevicePost:
     """_ChunkPost's schedule on the device: after_batch(k) queues the Context.radial_window calls window_calls lists for
     batch k (pair j in flow slot j % flow_slots, its record at byte 48 * j of `out`) on a stream of their own
-    (_side_stream); finish() makes torch's current stream wait for them.  Nothing is read back."""
+    (_side_stream); finish() makes torch's current stream wait for them.  Nothing is read back.  axes=True: the calls are
+    Context.radial_window_axes and the records 80 bytes."""
 
-    def __init__(self, ctx, n, B, pov_mode, cut_threshold, out):
+    def __init__(self, ctx, n, B, pov_mode, cut_threshold, out, axes=False):
         self.ctx, self.pov_mode, self.cut_threshold = ctx, pov_mode, cut_threshold
+        self.window, self.item = (ctx.radial_window_axes if axes else ctx.radial_window), _post_dtype(axes).itemsize
         self.base, nbytes = _capi._device_span(out)
-        if nbytes < n * _capi.PASS2_DTYPE.itemsize:
-            raise ValueError(f"post_out holds {nbytes} bytes, the chunk's {n} records need {n * _capi.PASS2_DTYPE.itemsize}")
+        if nbytes < n * self.item:
+            raise ValueError(f"post_out holds {nbytes} bytes, the chunk's {n} records need {n * self.item}")
         self.stream = _side_stream(ctx)
         self.calls = {}
         for c in window_calls(n, B):
@@ -468,11 +488,11 @@ class _DevicePost:
 
     def after_batch(self, k):
         """queue batch k's calls; returns the number of leading pairs whose batches these calls have waited for (0: none)"""
-        ctx, fs, item, done = self.ctx, self.ctx.flow_slots, _capi.PASS2_DTYPE.itemsize, 0
+        fs, item, done = self.ctx.flow_slots, self.item, 0
         for lo, hi, first, count, _ in self.calls.get(k, ()):
             out = _capi._DeviceSpan(self.base + (lo + first) * item, count * item)
-            ctx.radial_window([j % fs for j in range(lo, hi)], first, count, out, SMOOTH_RADIUS, self.cut_threshold, self.pov_mode,
-                              self.stream)
+            self.window([j % fs for j in range(lo, hi)], first, count, out, SMOOTH_RADIUS, self.cut_threshold, self.pov_mode,
+                        self.stream)
             done = hi
         return done
 
@@ -499,36 +519,103 @@ def pair_plan(fps, total_frames, params):
     return [indices[cs:cs + bracket] for cs in range(0, len(indices), bracket) if len(indices[cs:cs + bracket]) >= 2]
 
 
+def script_axes(params):
+    """params["hip_axes"], a dict from file suffix to component name (_capi.AXES), e.g. {"roll": "tangential", "sway":
+    "shift_x"}: [(suffix, column)] for the further scripts of frames_to_scripts / flows_to_scripts.  The library fixes no
+    mapping of its own -- which device axis a component drives is the caller's convention.  An empty suffix (the main
+    script's) and an unknown component are refused."""
+    out = []
+    for suffix, comp in dict(params.get("hip_axes") or {}).items():
+        if not isinstance(suffix, str) or not suffix:
+            raise ValueError(f"hip_axes: {suffix!r} is not a file suffix (the main script is the entry without one)")
+        if comp not in _capi.AXES:
+            raise ValueError(f"hip_axes[{suffix!r}]: unknown component {comp!r}, one of {_capi.AXES}")
+        out.append((suffix, _capi.AXES.index(comp)))
+    return out
+
+
+def _scripts_from_chunks(chunks, extra, fps, params):
+    """{suffix: actions} out of the chunks' (frame indices, comps float64[n, 4], records): "" from component 0 and one
+    entry per (suffix, column) of `extra`, each through the post-chain with the chunks' cuts"""
+    from . import postchain
+    cuts = [bool(r[4]) for _, _, recs in chunks for r in recs]
+    frame_idx = [i for idx, _, _ in chunks for i in idx]
+    comps = np.concatenate([np.asarray(c, np.float64).reshape(-1, len(_capi.AXES)) for _, c, _ in chunks] or
+                           [np.zeros((0, len(_capi.AXES)))], axis=0)
+    return {suffix: postchain.actions_from_scalars([float(v) for v in comps[:, col]], cuts, frame_idx, fps, params)
+            for suffix, col in [("", 0)] + extra}
+
+
+def _flow_scalars(engine, flows, params, axes=False):
+    """(dots or comps, records) of one chunk of caller flows under params (see _chunk_scalars)"""
+    pov, thr = bool(params.get("pov_mode", False)), float(params.get("cut_threshold", 7))
+    if _pass2_mode(params):   # params["hip_pass2"] = "device": one buffer and one read per chunk
+        return post_records(engine.process_flows(flows, pov, thr, post_out=True, **_axes_kw(axes)), **_axes_kw(axes))
+    return engine.process_flows(flows, pov, thr, **_axes_kw(axes))
+
+
+def _axes_kw(axes):
+    """axes=True only where it is asked for: an engine without the keyword keeps serving the single script"""
+    return {"axes": True} if axes else {}
+
+
+def _flow_chunks(engine, chunk_flows, fps, total_frames, params, axes, who):
+    plan = pair_plan(fps, total_frames, params)
+    if len(chunk_flows) != len(plan):
+        raise ValueError(f"{who}: {len(chunk_flows)} chunks of flows for a plan of {len(plan)} chunks")
+    out = []
+    for chunk, flows in zip(plan, chunk_flows):
+        d, recs = _flow_scalars(engine, flows, params, axes)
+        if len(d) != len(chunk) - 1:
+            raise ValueError(f"{who}: a chunk of {len(chunk)} frames needs {len(chunk) - 1} fields, got {len(d)}")
+        out.append((chunk[:-1], d, recs))
+    return out
+
+
 def flows_to_actions(engine, chunk_flows, fps, total_frames, params):
     """.funscript actions from flow fields the caller computed: chunk_flows[k] holds the len(plan[k]) - 1 pair fields of
     chunk k of pair_plan(fps, total_frames, params) in device memory (see PairEngine.process_flows).  Everything after
     the flow -- pass 1, the +-6 window, pass 2, the post-chain -- is frames_to_actions' own."""
     from . import postchain
-    plan = pair_plan(fps, total_frames, params)
-    if len(chunk_flows) != len(plan):
-        raise ValueError(f"flows_to_actions: {len(chunk_flows)} chunks of flows for a plan of {len(plan)} chunks")
     dots, cuts, frame_idx = [], [], []
-    for chunk, flows in zip(plan, chunk_flows):
-        pov, thr = bool(params.get("pov_mode", False)), float(params.get("cut_threshold", 7))
-        if _pass2_mode(params):   # params["hip_pass2"] = "device": one buffer and one read per chunk
-            d, recs = post_records(engine.process_flows(flows, pov, thr, post_out=True))
-        else:
-            d, recs = engine.process_flows(flows, pov, thr)
-        if len(d) != len(chunk) - 1:
-            raise ValueError(f"flows_to_actions: a chunk of {len(chunk)} frames needs {len(chunk) - 1} fields, got {len(d)}")
+    for idx, d, recs in _flow_chunks(engine, chunk_flows, fps, total_frames, params, False, "flows_to_actions"):
         dots += [float(v) for v in d]
         cuts += [bool(r[4]) for r in recs]
-        frame_idx += chunk[:-1]
+        frame_idx += idx
     return postchain.actions_from_scalars(dots, cuts, frame_idx, fps, params)
 
 
-def _chunk_scalars(engine, frames, params, **kw):
+def flows_to_scripts(engine, chunk_flows, fps, total_frames, params):
+    """flows_to_actions for multi-axis scripts: {suffix: actions}, "" being flows_to_actions' own script (component 0) and
+    one further entry per item of params["hip_axes"] (script_axes)."""
+    extra = script_axes(params)
+    return _scripts_from_chunks(_flow_chunks(engine, chunk_flows, fps, total_frames, params, True, "flows_to_scripts"), extra,
+                                fps, params)
+
+
+def _chunk_scalars(engine, frames, params, axes=False, **kw):
     """(dots, records) of one chunk under params: engine.process_chunk, or -- params["hip_pass2"] = "device" -- its device
-    pass 2 with one buffer and one read for the chunk"""
+    pass 2 with one buffer and one read for the chunk; axes=True: (comps float64[n, 4], records)"""
     pov, thr = bool(params.get("pov_mode", False)), float(params.get("cut_threshold", 7))
+    kw.update(_axes_kw(axes))
     if not _pass2_mode(params):
         return engine.process_chunk(frames, pov, thr, **kw)
-    return post_records(engine.process_chunk(frames, pov, thr, post_out=True, **kw))
+    return post_records(engine.process_chunk(frames, pov, thr, post_out=True, **kw), **_axes_kw(axes))
+
+
+def _frame_chunks(engine, frames, fps, params, axes):
+    """[(frame indices, dots or comps, records)] of every chunk of pair_plan under params"""
+    # params["hip_flow"] / ["hip_dis"] pick the flow algorithm for this call (the engine itself is left as it is); without
+    # them the engine's own algorithm runs
+    algo = _capi.flow_choice(params) if ("hip_flow" in params or "hip_dis" in params) else None
+    # params["hip_farneback"] / ["hip_farneback_window"] likewise set the Farneback parameters and window of this call
+    fbk = farneback_kwargs(params, frames[0].shape[1], frames[0].shape[0]) if len(frames) else {}
+    out = []
+    for chunk in pair_plan(fps, len(frames), params):
+        d, recs = _chunk_scalars(engine, [frames[i] for i in chunk], params, axes, **({"algo": algo} if algo is not None else {}),
+                                 **fbk)
+        out.append((chunk[:-1], d, recs))
+    return out
 
 
 def frames_to_actions(engine, frames, fps, params):
@@ -536,18 +623,21 @@ def frames_to_actions(engine, frames, fps, params):
     sampling to keyframes (FF:1127-1385) with the HIP pair engine in the middle.  `frames` holds every
     decoded frame (any sequence); chunking follows FF:1145-1153 (pairs never span chunks, F10)."""
     from . import postchain
-    # params["hip_flow"] / ["hip_dis"] pick the flow algorithm for this call (the engine itself is left as it is); without
-    # them the engine's own algorithm runs
-    algo = _capi.flow_choice(params) if ("hip_flow" in params or "hip_dis" in params) else None
-    # params["hip_farneback"] / ["hip_farneback_window"] likewise set the Farneback parameters and window of this call
-    fbk = farneback_kwargs(params, frames[0].shape[1], frames[0].shape[0]) if len(frames) else {}
     dots, cuts, frame_idx = [], [], []
-    for chunk in pair_plan(fps, len(frames), params):
-        d, recs = _chunk_scalars(engine, [frames[i] for i in chunk], params, **({"algo": algo} if algo is not None else {}), **fbk)
+    for idx, d, recs in _frame_chunks(engine, frames, fps, params, False):
         dots += [float(v) for v in d]
         cuts += [bool(r[4]) for r in recs]
-        frame_idx += chunk[:-1]
+        frame_idx += idx
     return postchain.actions_from_scalars(dots, cuts, frame_idx, fps, params)
+
+
+def frames_to_scripts(engine, frames, fps, params):
+    """frames_to_actions for multi-axis scripts: {suffix: actions}.  "" is the main script, from
+    component 0 -- action for action what frames_to_actions returns -- and every item of params["hip_axes"] (script_axes)
+    adds one from its component, through the same post-chain with the same cuts.  postchain.write_funscripts writes them
+    as base.funscript and base.<suffix>.funscript.  params["hip_pass2"] = "device" works as for the single script."""
+    extra = script_axes(params)
+    return _scripts_from_chunks(_frame_chunks(engine, frames, fps, params, True), extra, fps, params)
 
 
 def _shard_pass1(engine, frames, mine, pov_mode, cut_threshold):
@@ -578,15 +668,23 @@ def _merge_dots(parts, n):
     return dots
 
 
+def _no_sharded_axes(axes, who):
+    if axes:
+        raise ValueError(f"{who}: the sharded schedules compute the radial component alone; axes=True needs "
+                         "PairEngine.process_chunk / process_flows on one device")
+
+
 def process_chunk_sharded(engine, frames, rank, world, allgather, pov_mode=False, cut_threshold=7.0,
-                          assign="contiguous", block=1):
+                          assign="contiguous", block=1, axes=False):
     """Multi-GPU form of one chunk: rank r owns the pairs shard_pairs(n, world, r, assign, block).
 
     `engine` provides pass1(frames, pair_indices, pov_mode, cut_threshold) -> records (its l-th listed pair is
     local index l) and radial(local_indices, centers, cuts, pov_mode) -> floats on its own device;
     `allgather(obj)` returns the list of every rank's object (a host gather of ~32 B per pair: pair index, x, y,
     cut -- the only exchange).  Centres are smoothed over the WHOLE chunk (FF:1203-1214 needs pairs j+-6, which
-    cross shard edges under either assignment).  Returns the full dots array and the (n, 3) records on every rank."""
+    cross shard edges under either assignment).  Returns the full dots array and the (n, 3) records on every rank.
+    axes=True is refused: the sharded schedules keep the single component."""
+    _no_sharded_axes(axes, "process_chunk_sharded")
     n = len(frames) - 1
     mine = shard_pairs(n, world, rank, assign, block)
     allrecs = _merge_records(allgather(_shard_pass1(engine, frames, mine, pov_mode, cut_threshold)), n)
@@ -602,7 +700,7 @@ def halo_rows(rows, radius=SMOOTH_RADIUS):
     return rows if len(rows) <= 2 * radius else np.concatenate([rows[:radius], rows[-radius:]], axis=0)
 
 
-def process_chunk_sharded_halo(engine, frames, rank, world, allgather, pov_mode=False, cut_threshold=7.0):
+def process_chunk_sharded_halo(engine, frames, rank, world, allgather, pov_mode=False, cut_threshold=7.0, axes=False):
     """Streaming multi-GPU form of one chunk for CONTIGUOUS blocks: the only exchange between the passes is the halo.
 
     process_chunk_sharded gathers every pass-1 record of the chunk before any pass 2 starts, so all ranks idle until the
@@ -618,7 +716,8 @@ def process_chunk_sharded_halo(engine, frames, rank, world, allgather, pov_mode=
     `engine.pass1` is called with on_batch= when it accepts one (HipShardEngine does); an engine without it still gives
     the same numbers, only without the overlap.  Window means are exact integer sums / counts, so the result is
     bit-identical to process_chunk_sharded's and to a single-GPU process_chunk.  Returns (dots, (n, 3) records) on every
-    rank."""
+    rank.  axes=True is refused, as in process_chunk_sharded."""
+    _no_sharded_axes(axes, "process_chunk_sharded_halo")
     n = len(frames) - 1
     R = SMOOTH_RADIUS
     lo, hi = shard_range(n, world, rank)
@@ -681,10 +780,11 @@ def process_chunk_sharded_halo(engine, frames, rank, world, allgather, pov_mode=
     return all_dots, allrecs
 
 
-def process_chunk_local_ranks(engines, frames, pov_mode=False, cut_threshold=7.0, assign="contiguous", block=1):
+def process_chunk_local_ranks(engines, frames, pov_mode=False, cut_threshold=7.0, assign="contiguous", block=1, axes=False):
     """The same schedule with every rank driven from THIS process (one engine / context per device, or several
     contexts on one device): phase by phase, no process group.  Equivalent to world = len(engines) processes
-    running process_chunk_sharded."""
+    running process_chunk_sharded (axes=True is refused there and here)."""
+    _no_sharded_axes(axes, "process_chunk_local_ranks")
     n, world = len(frames) - 1, len(engines)
     mine = [shard_pairs(n, world, r, assign, block) for r in range(world)]
     allrecs = _merge_records([_shard_pass1(e, frames, m, pov_mode, cut_threshold) for e, m in zip(engines, mine)], n)
@@ -712,7 +812,8 @@ class HipShardEngine:
             raise ValueError(f"shard of {len(pair_indices)} pairs does not fit the context's {self.ctx.flow_slots} flow slots")
         return self.inner.pass1_pairs(frames, pair_indices, lambda l: l, pov_mode, cut_threshold, on_batch=on_batch)
 
-    def radial(self, local_indices, centers, cuts, pov_mode):
+    def radial(self, local_indices, centers, cuts, pov_mode, axes=False):
+        _no_sharded_axes(axes, "HipShardEngine.radial")
         out, B = [], self.ctx.max_batch
         for s in range(0, len(local_indices), B):
             sl = slice(s, s + B)

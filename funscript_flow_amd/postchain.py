@@ -118,3 +118,19 @@ def write_funscript(path, actions):
     """FF:1391-1394."""
     with open(path, "w") as f:
         json.dump({"version": "1.0", "actions": actions}, f, indent=2)
+
+
+def write_funscripts(base_path, scripts):
+    """The sibling files of a multi-axis script: scripts = {suffix: actions} as pipeline.frames_to_scripts returns it;
+    "" goes to base_path.funscript and every other suffix to base_path.<suffix>.funscript, each through write_funscript.
+    base_path is the video's path without its extension (a trailing ".funscript" is dropped).  Returns the paths written."""
+    base = str(base_path)
+    if base.endswith(".funscript"):
+        base = base[:-len(".funscript")]
+    paths = []
+    for suffix, actions in scripts.items():
+        if any(ch in suffix for ch in "/\\") or suffix.startswith("."):
+            raise ValueError(f"write_funscripts: {suffix!r} is not a file suffix")
+        paths.append(f"{base}.{suffix}.funscript" if suffix else f"{base}.funscript")
+        write_funscript(paths[-1], actions)
+    return paths

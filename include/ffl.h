@@ -28,6 +28,9 @@
  *                           for a batch (ProcessPoolExecutor.submit loop, FF:1232-1236)
  *   ffl_radial_window       the centre window of FF:1203-1214, the cut test of FF:898-907 and radial_motion_weighted
  *                           FF:761-785 for a batch, behind the batches on the caller's stream: FF:1203-1236 without the host
+ *   ffl_radial_axes, ffl_radial_window_axes  replace nothing: the reference reduces a field to its radial part alone.  They
+ *                           are ffl_radial / ffl_radial_window with the rotation about the centre and the weighted shift
+ *                           next to it, for multi-axis scripts
  *   ffl_download_flow       the "flow" entry of that dict (tests / callers that want the array)
  *   ffl_upload_frames_device  ffl_upload_frames_raw / _yuv / ffl_upload_frames for frames already in device memory (a GPU
  *                           decoder's surfaces, torch tensors); ffl_export_flows: ffl_download_flow into device memory
@@ -428,6 +431,46 @@ typedef struct ffl_pass2_record {
  * Nothing of this call is ever captured into the library's graphs. */
 int ffl_radial_window(ffl_ctx *ctx, int n_seq, const int *seq_slots, int first, int n, int radius, float cut_threshold,
                       int pov_mode, ffl_pass2_record *out_dev, uint64_t stream);
+
+/* ---- The four motion components about the centre ----
+ * Per pixel (x, y) of a field with flow (u, v), centre (cx, cy), dx = x - cx, dy = y - cy and the quadrant weights wx, wy
+ * of radial_motion_weighted (both 1 in pov_mode), all in float64 without contraction:
+ *   FFL_AXIS_RADIAL      ((u dx + v dy) wx) wy   ffl_radial's term: the bits of ffl_radial / ffl_radial_window
+ *   FFL_AXIS_TANGENTIAL  ((v dx - u dy) wx) wy   > 0: clockwise on screen (x to the right, y down)
+ *   FFL_AXIS_SHIFT_X     (u wx) wy
+ *   FFL_AXIS_SHIFT_Y     (v wx) wy
+ * each summed over the image in ffl_radial's order and divided once by (double)width * (double)height.  The weights are
+ * the radial term's own and are not normalised by their sum, as the reference does not normalise its dot.  A cut item is
+ * +0.0 in all four and none of its flow is read; a non-finite field gives each component the IEEE result of its own terms. */
+#define FFL_AXIS_RADIAL 0
+#define FFL_AXIS_TANGENTIAL 1
+#define FFL_AXIS_SHIFT_X 2
+#define FFL_AXIS_SHIFT_Y 3
+#define FFL_N_AXES 4
+
+/* One record of ffl_radial_window_axes.  80 bytes, 8-byte aligned. */
+typedef struct ffl_axes_record {
+    ffl_pass2_record base;      /* byte for byte what ffl_radial_window writes; base.dot = component FFL_AXIS_RADIAL */
+    double tangential, shift_x, shift_y;   /* components 1..3, the bits of ffl_radial_axes at (base.cx, base.cy) */
+    double reserved;            /* +0.0 */
+} ffl_axes_record;
+
+/* ffl_radial with four components per item: out[i * FFL_N_AXES + component], float64.  ffl_radial's contract otherwise:
+ * the same arguments, refusals and locks, is_cut[i] != 0 yields four 0.0 without touching the device, synchronous, timed
+ * under FFL_K_RADIAL.  The first four-component call of a context allocates what ffl_axes_extra_bytes reports. */
+int ffl_radial_axes(ffl_ctx *ctx, int n, const int *flow_slots, const double *cx, const double *cy, const int *is_cut,
+                    int pov_mode, double *out);
+
+/* ffl_radial_window with ffl_axes_record records: the same windows, cut test, refusals (out_dev must hold n records of 80
+ * bytes inside one allocation), stream contract and use of every seq slot; never captured, no host wait.  Its three
+ * launches are k_window_plan, k_radial_axes and k_radial_axes_final. */
+int ffl_radial_window_axes(ffl_ctx *ctx, int n_seq, const int *seq_slots, int first, int n, int radius, float cut_threshold,
+                           int pov_mode, ffl_axes_record *out_dev, uint64_t stream);
+
+/* Device memory the four-component calls add to a context of this size, allocated by the first such call and freed by
+ * ffl_destroy: FFL_N_AXES partial sums per workgroup of the radial grid for FFL_MAX_BATCH items (ffl_estimate_bytes does
+ * not count it; 20 KiB of page-locked records come with it).  Needs no device. */
+int ffl_axes_extra_bytes(int width, int height, size_t *bytes);
 
 /* Copy a finished flow field to host memory as (height, width, 2) float32, cv2 layout. */
 int ffl_download_flow(ffl_ctx *ctx, int flow_slot, float *dst);
