@@ -29,6 +29,7 @@ EXPORTS = ["ffl_device_count", "ffl_create", "ffl_destroy", "ffl_last_error", "f
            "ffl_dev_frame_check", "ffl_upload_frames_device", "ffl_export_flows",
            "ffl_dev_flow_check", "ffl_import_flows", "ffl_radial_window",
            "ffl_radial_axes", "ffl_radial_window_axes", "ffl_axes_extra_bytes",
+           "ffl_dev_weights_check", "ffl_pass1_weighted", "ffl_radial_window_axes_weighted", "ffl_weights_extra_bytes",
            "ffl_upload_frames_raw_src", "ffl_upload_frames_yuv_src", "ffl_upload_frames_yuv16_src", "ffl_frontend_yuv_window_src",
            "ffl_frontend_yuv16_window_src", "ffl_dev_frame_check_src", "ffl_dev_frame_check16_src",
            "ffl_upload_frames_device_src", "ffl_upload_frames_device16_src"]
@@ -436,6 +437,45 @@ def dev_flow_check(dtype, n, width, height, desc):
         raise ValueError(L.ffl_last_error(None).decode())
 
 
+class DevWeights(C.Structure):
+    """ffl_dev_weights: n weight maps (H, W) uint8 in device memory; item i, pixel (x, y) is at
+    base + i * item_stride + y * row_pitch + x (bytes, include/ffl.h); item_stride 0: one map for all items."""
+    _fields_ = [("base", C.c_void_p), ("item_stride", C.c_ssize_t), ("row_pitch", C.c_ssize_t)]
+
+
+def device_weights(obj, width, height):
+    """(DevWeights, n) of a torch device tensor of weight maps: uint8 or bool, (H, W) -- the static
+    mask, n = 0: one map for however many items a call has -- or (n, H, W) with any item and row strides and unit pixel
+    stride.  ValueError names what is refused: host memory, another dtype, another size or shape, a pixel stride."""
+    torch = sys.modules.get("torch")
+    if torch is None or not isinstance(obj, torch.Tensor):
+        raise ValueError(f"not device memory: weight maps are torch device tensors, got {type(obj).__name__}")
+    if obj.dtype not in (torch.uint8, torch.bool):
+        raise ValueError(f"dtype {obj.dtype} is not supported: weight maps are uint8 or bool")
+    shape, st = tuple(obj.shape), tuple(obj.stride())   # one byte per element
+    W, H = int(width), int(height)
+    if len(shape) not in (2, 3):
+        raise ValueError(f"shape: weight maps are (H, W) or (n, H, W), got {shape}")
+    if shape[-2:] != (H, W):
+        raise ValueError(f"size: a map of {shape[-1]}x{shape[-2]} does not match the context's {W}x{H} (no resizing)")
+    if st[-1] != 1:
+        raise ValueError(f"pixel stride: the pixels of a row must be contiguous, the stride is {st[-1]}")
+    if len(shape) == 3 and shape[0] < 1:
+        raise ValueError("shape: no maps (n = 0)")
+    if not obj.is_cuda:
+        raise ValueError("not device memory: a CPU tensor (weight maps live in device memory)")
+    if len(shape) == 2:
+        return DevWeights(obj.data_ptr(), 0, st[0]), 0
+    return DevWeights(obj.data_ptr(), st[0], st[1]), shape[0]
+
+
+def dev_weights_check(n, width, height, desc):
+    """ffl_dev_weights_check: ValueError with the library's rule when it refuses (pure host check)."""
+    L = load()
+    if L.ffl_dev_weights_check(int(n), int(width), int(height), None if desc is None else C.byref(desc)) != FFL_OK:
+        raise ValueError(L.ffl_last_error(None).decode())
+
+
 def stream_handle(stream, device=0):
     """hipStream_t of `stream` as an int: None = torch's current stream on `device` when torch is already imported (else
     0, the null stream); a torch.cuda.Stream; or an int as it is."""
@@ -562,6 +602,10 @@ def load():
     L.ffl_radial_axes.argtypes = L.ffl_radial.argtypes
     L.ffl_radial_window_axes.argtypes = L.ffl_radial_window.argtypes
     L.ffl_axes_extra_bytes.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+    L.ffl_dev_weights_check.argtypes = [C.c_int] * 3 + [vp]
+    L.ffl_pass1_weighted.argtypes = [vp, C.c_int, ip, vp, C.c_int, C.c_uint64]
+    L.ffl_radial_window_axes_weighted.argtypes = [vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, C.c_uint64]
+    L.ffl_weights_extra_bytes.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_size_t)]
     for name in EXPORTS:   # every _src sibling: the plain call's arguments plus const ffl_source_info *
         if name.endswith("_src"):
             getattr(L, name).argtypes = getattr(L, name[:-4]).argtypes + [vp]
@@ -613,6 +657,16 @@ def axes_extra_bytes(width, height):
     L = load()
     if L.ffl_axes_extra_bytes(int(width), int(height), C.byref(b)) != FFL_OK:
         raise FFLError(f"ffl_axes_extra_bytes failed: {L.ffl_last_error(None).decode()}")
+    return b.value
+
+
+def weights_extra_bytes(width, height):
+    """Device bytes the first pass1_weighted / radial_window_axes_weighted call of a Context of this size allocates
+    (estimate_bytes does not count them)."""
+    b = C.c_size_t()
+    L = load()
+    if L.ffl_weights_extra_bytes(int(width), int(height), C.byref(b)) != FFL_OK:
+        raise FFLError(f"ffl_weights_extra_bytes failed: {L.ffl_last_error(None).decode()}")
     return b.value
 
 
@@ -972,14 +1026,42 @@ class Context:
         return self._radial_window(self.L.ffl_radial_window, "radial_window", PASS2_DTYPE, seq_slots, first, n, out, radius,
                                    cut_threshold, pov_mode, stream)
 
-    def _radial_window(self, call, name, dtype, seq_slots, first, n, out, radius, cut_threshold, pov_mode, stream):
+    def _radial_window(self, call, name, dtype, seq_slots, first, n, out, radius, cut_threshold, pov_mode, stream, weights=()):
         ptr, extent = _device_span(out)   # the records are written back to back
         if extent < int(n) * dtype.itemsize:
             raise ValueError(f"{name}: out holds {extent} bytes, {int(n)} records need {int(n) * dtype.itemsize}")
         ps, ks = _iarr(seq_slots)
-        self._chk(call(self._h, len(ks), ps, int(first), int(n), int(radius), float(cut_threshold), int(bool(pov_mode)), ptr,
-                       stream_handle(stream, self.device)))
+        self._chk(call(self._h, len(ks), ps, int(first), int(n), int(radius), float(cut_threshold), int(bool(pov_mode)), *weights,
+                       ptr, stream_handle(stream, self.device)))
         return out
+
+    def _weights(self, name, weights, n):
+        """the DevWeights of a call with n items: a descriptor as it is, or a tensor through device_weights"""
+        if isinstance(weights, DevWeights):
+            return weights
+        desc, m = device_weights(weights, self.width, self.height)
+        if m not in (0, int(n)):
+            raise ValueError(f"{name}: {m} weight maps for {int(n)} items")
+        return desc
+
+    def pass1_weighted(self, flow_slots, weights, pov_mode=False, stream=None):
+        """The pass-1 records of flow_slots recomputed under per-pixel weight maps (ffl_pass1_weighted, DESIGN.md section
+        16): `weights` is a uint8 / bool device tensor, (H, W) for every slot or (n, H, W), one map per slot (or a
+        DevWeights).  The flow is only read; the records stay until the slot is written again.  Queued behind the work on
+        `stream` (None: torch's current stream), which waits for it; the host does not wait."""
+        ps, slots = _iarr(flow_slots)
+        desc = self._weights("pass1_weighted", weights, len(slots))
+        self._chk(self.L.ffl_pass1_weighted(self._h, len(slots), ps, C.byref(desc), int(bool(pov_mode)),
+                                            stream_handle(stream, self.device)))
+
+    def radial_window_axes_weighted(self, seq_slots, first, n, weights, out, radius=6, cut_threshold=7.0, pov_mode=False,
+                                    stream=None):
+        """radial_window_axes with every term weighted by the maps of the n computed items (ffl_radial_window_axes_weighted):
+        `weights` as in pass1_weighted, (H, W) or (n, H, W).  Windows, centres and the cut test come from the records the seq
+        slots hold.  An all-ones map gives the bytes of radial_window_axes."""
+        desc = self._weights("radial_window_axes_weighted", weights, n)
+        return self._radial_window(self.L.ffl_radial_window_axes_weighted, "radial_window_axes_weighted", PASS2_AXES_DTYPE,
+                                   seq_slots, first, n, out, radius, cut_threshold, pov_mode, stream, weights=(C.byref(desc),))
 
     def download_frame(self, fslot):
         out = np.empty((self.height, self.width), np.uint8)

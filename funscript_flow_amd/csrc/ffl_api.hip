@@ -347,6 +347,10 @@ struct ffl_ctx {
     // touches them, so a single-component call queued between two of these never sees or disturbs them.
     DevBuf<double> d_apsum;
     PinBuf<AxesRecord> h_axes; AxesRecord *d_axes = nullptr;  // ffl_radial_axes' mapped pinned records and their device alias
+    // The weighted calls (ffl_pass1_weighted, ffl_radial_window_axes_weighted): their partials --
+    // pass 1's SW per workgroup, pass 2's FFL_NAXES + 1 sums per workgroup -- allocated by their first call (weights_scratch)
+    // and held to ffl_destroy, under the single-copy rule above.
+    DevBuf<double> d_wpsum;
     int p1_blocks = 0;
     // profiling
     unsigned prof_mask = 0;   // bit k set: bracket every launch of kernel class k with HIP events
@@ -2094,7 +2098,7 @@ int ffl_pass1_results(ffl_ctx *c, int n, const int *slots, float cut_threshold, 
     const double npx = (double)c->w * (double)c->h;
     for (int i = 0; i < n; i++) {
         const Pass1Result &r = c->h_res[slots[i]];
-        const float mm = (float)(r.mag_sum / npx);
+        const float mm = (float)ffl_record_mean(r, npx);  // a record formed under a weight map holds its own quotient
         if (x) x[i] = r.x;
         if (y) y[i] = r.y;
         if (div_val) div_val[i] = r.div_val;
@@ -2359,15 +2363,22 @@ static int caller_join(ffl_ctx *c, hipStream_t cst, WaitOnce &wait) {
 }
 
 // The contract for a call that queues on stream `post` (the caller holds post_mu and the context lock, and has refused
-// what it can refuse without the device).  post_begin(): the caller's stream (*cst), the check of the call's one region of
-// caller memory, then stream `post` behind the caller's queued work and behind the last users of the n slots the call reads
+// what it can refuse without the device).  post_begin(): the caller's stream (*cst), the check of the call's nreg regions of
+// caller memory in order, then stream `post` behind the caller's queued work and behind the last users of the n slots the call reads
 // or writes.  post_end(), after the launches: the call becomes those slots' last use, and the caller's later work runs
 // behind it.
-static int post_begin(ffl_ctx *c, const char *fn, uint64_t stream, hipStream_t *cst, const char *what, const void *p,
-                      size_t bytes, const char *host_hint, int n, const int *slots) {
+struct PostRegion {
+    const char *what;
+    const void *p;
+    size_t bytes;
+    const char *host_hint;
+};
+static int post_begin(ffl_ctx *c, const char *fn, uint64_t stream, hipStream_t *cst, const PostRegion *reg, int nreg, int n,
+                      const int *slots) {
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = caller_stream(c, fn, stream, cst)) return rc;
-    if (int rc = dev_mem_check(c, fn, what, p, bytes, host_hint)) return rc;
+    for (int k = 0; k < nreg; k++)
+        if (int rc = dev_mem_check(c, fn, reg[k].what, reg[k].p, reg[k].bytes, reg[k].host_hint)) return rc;
     WaitOnce wait_post(c->s_post);
     if (int rc = caller_join(c, *cst, wait_post)) return rc;
     for (int i = 0; i < n; i++) HIPCHK(c, wait_post(c->ev_slot_done[slots[i]].get()));
@@ -2521,7 +2532,8 @@ int ffl_export_flows(ffl_ctx *c, int n, const int *slots, float *dst, int layout
     hipStream_t cst;
     const ptrdiff_t span = (ptrdiff_t)(n - 1) * item_stride;
     const char *lo = (const char *)dst + (span < 0 ? span : 0);
-    if (int rc = post_begin(c, fn, stream, &cst, "dst", lo, (size_t)(span < 0 ? -span : span) + item, kHostFrames, n, slots)) return rc;
+    const PostRegion reg{"dst", lo, (size_t)(span < 0 ? -span : span) + item, kHostFrames};
+    if (int rc = post_begin(c, fn, stream, &cst, &reg, 1, n, slots)) return rc;
     for (int i0 = 0; i0 < n; i0 += FFL_MAXB) {
         const int m = n - i0 < FFL_MAXB ? n - i0 : FFL_MAXB;
         ExportTab t;
@@ -2549,9 +2561,94 @@ static_assert(sizeof(ffl_axes_record) == 80 && sizeof(AxesRecord) == 80 && offse
               "AxesRecord mirrors ffl_axes_record");
 static_assert(FFL_N_AXES == FFL_NAXES && FFL_AXIS_RADIAL == 0 && FFL_AXIS_TANGENTIAL == 1 && FFL_AXIS_SHIFT_X == 2 &&
               FFL_AXIS_SHIFT_Y == 3, "ffl.h and ffl_kernels.h agree on the components");
-// ffl_radial_window (axes = false: ffl_pass2_record) and ffl_radial_window_axes (ffl_axes_record): one protocol.
+// ---- weight maps --------------------------------------------------------------------
+// Every geometry rule of a weight descriptor (ffl.h, ffl_dev_weights_check).  *bytes: the extent of all n maps from w->base.
+static int dev_weights_check(ffl_ctx *c, const char *fn, int n, int width, int height, const ffl_dev_weights *w, size_t *bytes) {
+    if (!w) return set_err(c, FFL_ERR_INVALID, "%s: NULL weight descriptor", fn);
+    if (!w->base) return set_err(c, FFL_ERR_INVALID, "%s: NULL weight base", fn);
+    if (n < 1) return set_err(c, FFL_ERR_INVALID, "%s: n = %d weight maps (>= 1)", fn, n);
+    if (width < 2 || height < 2 || width > 32768 || height > 32768)
+        return set_err(c, FFL_ERR_INVALID, "%s: weight map size %dx%d outside 2..32768", fn, width, height);
+    const ptrdiff_t it = w->item_stride, pitch = w->row_pitch, big = (ptrdiff_t)1 << 40;
+    if (it < 0 || pitch < 0) return set_err(c, FFL_ERR_INVALID, "%s: negative weight stride (item %td, row %td)", fn, it, pitch);
+    if (it > big || pitch > big) return set_err(c, FFL_ERR_INVALID, "%s: weight stride beyond 2^40", fn);
+    if (pitch < width) return set_err(c, FFL_ERR_INVALID, "%s: overlap: weight row pitch %td below the width %d", fn, pitch, width);
+    const ptrdiff_t map = (ptrdiff_t)(height - 1) * pitch + width;
+    if (it > 0 && it < map)
+        return set_err(c, FFL_ERR_INVALID, "%s: overlap: weight item stride %td below one map's extent %td (0: one map for all items)",
+                       fn, it, map);
+    *bytes = (size_t)(n - 1) * (size_t)it + (size_t)map;
+    return FFL_OK;
+}
+
+int ffl_dev_weights_check(int n, int width, int height, const ffl_dev_weights *w) {
+    size_t bytes;
+    return dev_weights_check(nullptr, "ffl_dev_weights_check", n, width, height, w, &bytes);
+}
+
+// What the weighted calls add to a context (ffl_weights_extra_bytes reports it, weights_scratch allocates it): one buffer for
+// whichever of the two runs -- pass 2's FFL_NAXES + 1 partials per workgroup of the radial grid, or pass 1's SW per
+// workgroup of its grid -- for FFL_MAXB items.
+static size_t weights_psum_doubles(int w, int h) {
+    const size_t p2 = (size_t)(FFL_NAXES + 1) * (size_t)ffl_radial_blocks(w, h), p1 = (size_t)ffl_pass1_blocks(w, h);
+    return (p2 > p1 ? p2 : p1) * FFL_MAXB;
+}
+
+int ffl_weights_extra_bytes(int width, int height, size_t *bytes) {
+    if (!bytes) return set_err(nullptr, FFL_ERR_INVALID, "ffl_weights_extra_bytes: bytes is NULL");
+    if (!frame_size_ok(width, height)) return set_err(nullptr, FFL_ERR_INVALID, "ffl_weights_extra_bytes: " FFL_FRAME_SIZE_RULE, width, height);
+    *bytes = sizeof(double) * weights_psum_doubles(width, height);
+    return FFL_OK;
+}
+
+// The first weighted call allocates their scratch (the caller holds post_mu and the context lock).
+static int weights_scratch(ffl_ctx *c, const char *fn) {
+    if (c->d_wpsum) return FFL_OK;
+    const hipError_t e = c->d_wpsum.alloc(weights_psum_doubles(c->w, c->h));
+    if (e != hipSuccess) {
+        c->d_wpsum.release();  // nothing was allocated
+        (void)hipGetLastError();
+        return set_err(c, FFL_ERR_HIP, "%s: allocating the weighted scratch (%zu bytes) failed: %s", fn,
+                       sizeof(double) * weights_psum_doubles(c->w, c->h), hipGetErrorString(e));
+    }
+    return FFL_OK;
+}
+
+static const char *kHostWeights = "weight maps live in device memory (torch / hipMalloc)";
+
+// The pass-1 records of n slots that hold a flow, recomputed under the maps by ONE k_pass1_weighted launch (plus its final
+// kernel) on stream `post`: ffl_import_flows' protocol, with the flow only read.
+int ffl_pass1_weighted(ffl_ctx *c, int n, const int *slots, const ffl_dev_weights *w, int pov_mode, uint64_t stream) {
+    static const char *fn = "ffl_pass1_weighted";
+    if (!c) return FFL_ERR_INVALID;
+    std::unique_lock<std::mutex> pl(c->post_mu);  // stream `post`, d_ptab and the partials, as ffl_import_flows
+    CtxLock lk(c->mu);
+    if (n < 1 || n > c->max_batch)
+        return set_err(c, FFL_ERR_INVALID, "%s: n = %d slots outside 1..%d (the context's max_batch)", fn, n, c->max_batch);
+    if (!slots) return set_err(c, FFL_ERR_INVALID, "%s: NULL flow_slots", fn);
+    if (int rc = check_flow_slots(c, fn, n, slots, "flow", "repeated in one call")) return rc;
+    size_t bytes;
+    if (int rc = dev_weights_check(c, fn, n, c->w, c->h, w, &bytes)) return rc;
+    hipStream_t cst;
+    const PostRegion reg{"the weight maps", w->base, bytes, kHostWeights};
+    if (int rc = post_begin(c, fn, stream, &cst, &reg, 1, n, slots)) return rc;
+    if (int rc = weights_scratch(c, fn)) return rc;
+    ExportTab t;
+    for (int i = 0; i < n; i++) t.slot[i] = slots[i];
+    const WeightArgs wa{(const char *)w->base, (long long)w->item_stride, (long long)w->row_pitch};
+    {
+        ProfScope ps(c, FFL_K_PASS1, c->s_post);
+        ffl_launch_pass1_weighted(wa, c->d_flow, c->d_res, t, n, c->w, c->h, pov_mode ? 1 : 0, c->d_ptab, c->d_pskey, c->d_rpsum,
+                                  c->d_wpsum, c->s_post);
+    }
+    return post_end(c, cst, n, slots);  // the caller may overwrite or free the maps straight after the call
+}
+
+// ffl_radial_window (axes = false: ffl_pass2_record) and ffl_radial_window_axes (ffl_axes_record): one protocol.  wts (with
+// axes): ffl_radial_window_axes_weighted, the maps of the n computed items as a second region of caller memory.
 static int radial_window_call(ffl_ctx *c, const char *fn, bool axes, int n_seq, const int *seq, int first, int n, int radius,
-                              float cut_threshold, int pov_mode, void *out, uint64_t stream) {
+                              float cut_threshold, int pov_mode, void *out, uint64_t stream,
+                              const ffl_dev_weights *wts = nullptr, bool weighted = false) {
     if (!c) return FFL_ERR_INVALID;
     const size_t rec_bytes = axes ? sizeof(ffl_axes_record) : sizeof(ffl_pass2_record);
     std::unique_lock<std::mutex> pl(c->post_mu);  // stream `post`, post_ring and d_rpsum, as ffl_radial / ffl_export_flows
@@ -2569,18 +2666,28 @@ static int radial_window_call(ffl_ctx *c, const char *fn, bool axes, int n_seq, 
     // a slot's state stands for its record and its flow alike, so one check covers the neighbours and the computed items
     if (int rc = check_flow_slots(c, fn, n_seq, seq, "result", "repeated in one call")) return rc;
     if ((uintptr_t)out % 8) return set_err(c, FFL_ERR_INVALID, "%s: out_dev must be 8-byte aligned", fn);
+    size_t wbytes = 0;
+    if (weighted)
+        if (int rc = dev_weights_check(c, fn, n, c->w, c->h, wts, &wbytes)) return rc;
     hipStream_t cst;
-    if (int rc = post_begin(c, fn, stream, &cst, "out_dev", out, rec_bytes * (size_t)n,
-                            "results in host memory come from ffl_pass1_results and ffl_radial", n_seq, seq))
-        return rc;
+    const PostRegion reg[2] = {{"out_dev", out, rec_bytes * (size_t)n, "results in host memory come from ffl_pass1_results and ffl_radial"},
+                               {"the weight maps", weighted ? wts->base : nullptr, wbytes, kHostWeights}};
+    if (int rc = post_begin(c, fn, stream, &cst, reg, weighted ? 2 : 1, n_seq, seq)) return rc;
     WindowSeq t;
     for (int i = 0; i < n_seq; i++) t.slot[i] = seq[i];
-    if (axes)
+    if (weighted) {
+        if (int rc = weights_scratch(c, fn)) return rc;
+    } else if (axes)
         if (int rc = axes_scratch(c, fn)) return rc;
     // not timed under FFL_K_RADIAL: that class counts the radial pairs of ffl_radial / ffl_radial_axes, one per call
     ffl_launch_window_plan(t, n_seq, first, n, radius, cut_threshold, c->d_res, c->d_flow, c->w, c->h, c->d_wtab, out,
                            (int)rec_bytes, c->s_post);
-    launch_radial_pair(c, axes, n, pov_mode ? 1 : 0, out);
+    if (weighted) {
+        const WeightArgs wa{(const char *)wts->base, (long long)wts->item_stride, (long long)wts->row_pitch};
+        ffl_launch_radial_axes_weighted(c->d_wtab, n, c->w, c->h, pov_mode ? 1 : 0, c->d_wytab, wa, c->d_wpsum, (AxesRecord *)out,
+                                        c->s_post);
+    } else
+        launch_radial_pair(c, axes, n, pov_mode ? 1 : 0, out);
     return post_end(c, cst, n_seq, seq);
 }
 
@@ -2593,6 +2700,12 @@ int ffl_radial_window_axes(ffl_ctx *c, int n_seq, const int *seq, int first, int
                            ffl_axes_record *out, uint64_t stream) {
     return radial_window_call(c, "ffl_radial_window_axes", true, n_seq, seq, first, n, radius, cut_threshold, pov_mode, out,
                               stream);
+}
+
+int ffl_radial_window_axes_weighted(ffl_ctx *c, int n_seq, const int *seq, int first, int n, int radius, float cut_threshold,
+                                    int pov_mode, const ffl_dev_weights *w, ffl_axes_record *out, uint64_t stream) {
+    return radial_window_call(c, "ffl_radial_window_axes_weighted", true, n_seq, seq, first, n, radius, cut_threshold, pov_mode, out,
+                              stream, w, true);
 }
 
 // ---- flow import -------------------------------------------------------------------------------
@@ -2653,9 +2766,8 @@ int ffl_import_flows(ffl_ctx *c, int n, const int *slots, const ffl_dev_flow *f,
     if (int rc = dev_flow_check(c, fn, dtype, n, c->w, c->h, f, &mode, &bytes)) return rc;
     // stream `post` waits for the producer's queued work and for the last users of the slots (a batch, a pass 2, an export)
     hipStream_t cst;
-    if (int rc = post_begin(c, fn, stream, &cst, "the flow fields", f->base, bytes, "host flow fields go through ffl_upload_flow",
-                            n, slots))
-        return rc;
+    const PostRegion reg{"the flow fields", f->base, bytes, "host flow fields go through ffl_upload_flow"};
+    if (int rc = post_begin(c, fn, stream, &cst, &reg, 1, n, slots)) return rc;
     const ImportArgs a{(const char *)f->base, (long long)f->item_stride, (long long)f->row_pitch, (long long)f->pixel_stride,
                        (long long)f->channel_stride, c->d_flow, c->d_res};
     ExportTab t;

@@ -55,9 +55,14 @@ struct BatchTab {
 struct Pass1Result {  // written by k_pass1_final, mirrored to pinned host memory
     int x, y;
     float div_val;
-    float pad;
-    double mag_sum;   // sum of sqrt(u^2+v^2) over the image (mean = mag_sum / (w*h))
+    int weighted;     // 0: an ordinary record.  1 (k_pass1_weighted_final): mag_sum is already the mean, see below
+    double mag_sum;   // sum of sqrt(u^2+v^2) over the image (mean = mag_sum / (w*h)); under a weight map the record carries
+                      // its own divisor by holding the quotient: (sum of mag * weight) / SW, +0.0 when SW == 0
 };
+// the mean magnitude of a record as a double, before its one rounding to float (npx = (double)w * (double)h)
+__host__ __device__ inline double ffl_record_mean(const Pass1Result &r, double npx) {
+    return r.weighted ? r.mag_sum : r.mag_sum / npx;
+}
 
 // The input front-end (k_frontend, k_frontend_dev): a decoded frame -> the gray crop window of its (virtual) resize.
 enum { FFL_FRONT_GENERIC = 0, FFL_FRONT_AREA2 = 1, FFL_FRONT_IDENTITY = 2 };
@@ -97,6 +102,12 @@ struct ImportArgs {
     long long item, pitch, ps, cs;   // bytes
     float *flow;                     // the context's flow slots (2N floats each)
     Pass1Result *res;                // their records
+};
+
+// weight maps: item b's (h, w) uint8 map starts at base + b * item, its rows pitch bytes apart
+struct WeightArgs {
+    const char *base;
+    long long item, pitch;   // bytes; item 0: one map for every item
 };
 
 // merged launches: one 1-D grid cut into per-job block ranges
@@ -267,6 +278,13 @@ void ffl_launch_radial(const WindowItem *tab, int n, int w, int h, int pov_mode,
 // doubles per item, component c of item b at psum[(b * FFL_NAXES + c) * nblk ..]
 void ffl_launch_radial_axes(const WindowItem *tab, int n, int w, int h, int pov_mode, const double *wytab, double *psum,
                             AxesRecord *out, hipStream_t st);
+// The weighted forms.  Pass 1: the records of flow slots tab.slot[0..n) of `flow`
+// recomputed under the maps `wa`; psw: one more double per workgroup and item next to pkey / psum.  Pass 2: the
+// four-component pair with (FFL_NAXES + 1) * ffl_radial_blocks(w, h) doubles of psum per item.
+void ffl_launch_pass1_weighted(const WeightArgs &wa, float *flow, Pass1Result *res, const ExportTab &tab, int n, int w, int h,
+                               int pov_mode, PairTab *pt, unsigned long long *pkey, double *psum, double *psw, hipStream_t st);
+void ffl_launch_radial_axes_weighted(const WindowItem *tab, int n, int w, int h, int pov_mode, const double *wytab,
+                                     const WeightArgs &wa, double *psum, AxesRecord *out, hipStream_t st);
 // items first .. first+n-1 of seq -> tab[0..n) and every field but `dot` of the Pass2Record at the head of each of the n
 // records that start rec_stride bytes apart at out (sizeof(Pass2Record) or sizeof(AxesRecord))
 void ffl_launch_window_plan(const WindowSeq &seq, int n_seq, int first, int n, int radius, float cut_threshold,

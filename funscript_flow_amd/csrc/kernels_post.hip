@@ -80,6 +80,24 @@ struct P1SlotSrc {   // a flow slot: (h, w, 2) float32, one 16-byte load
     __device__ __forceinline__ void store(int, int, float2, float2, bool, bool) const {}
 };
 
+// Whether and where a pass reads per-pixel weights.  WtNone compiles every weighted
+// statement of the bodies away: k_pass1, k_import_pass1, k_radial and k_radial_axes are the kernels they were.  WtBytes is
+// one item's (h, w) uint8 map with any base and row pitch: a lane reads the weight of each of its two pixels with a byte
+// load at the pixel's clamped (x, y), so no byte outside the `w` bytes of a row is read and nothing is asked of alignment
+// (pass 1's strips start at odd x).
+struct WtNone {
+    static constexpr bool on = false;
+    __device__ __forceinline__ unsigned load(int, int) const { return 1u; }
+};
+struct WtBytes {
+    static constexpr bool on = true;
+    const char *item;    // the map's (0, 0)
+    long long pitch;     // bytes
+    __device__ __forceinline__ unsigned load(int yc, int xc) const {   // 0 <= yc < h, 0 <= xc < w
+        return *(const FFL_GLOBAL unsigned char *)(item + (long long)yc * pitch + xc);
+    }
+};
+
 // key = (bits(|div|) << 32) | (0xFFFFFFFF - flat index): the maximum key is the largest |div| and,
 // among equals, the smallest row-major index -- np.argmax's first-occurrence rule, order independent.
 // np.argmax ranks every NaN above every number and takes the first one, whatever its payload: a NaN |div| enters the
@@ -89,15 +107,21 @@ __device__ __forceinline__ unsigned ffl_key_bits(float absdiv) {
 }
 // The body of k_pass1 and k_import_pass1: one summation order whatever the source, so an imported field's record is
 // bit-identical to the record of the same float32 field in a slot.
-template <class Src>
-__device__ __forceinline__ void ffl_pass1_body(const Src &src, int w, int h, int pov_mode, int b,
+// Wt::on (k_pass1_weighted, rules W1-W3): a pixel is a candidate of the argmax and a term of the sums only where its weight
+// is > 0 -- by the selects that already exclude halo pixels, so nothing of an excluded pixel's flow reaches a key or a sum;
+// its magnitude enters as (double)mag * (double)weight (exact) and SW = sum of the weights travels as one more float64
+// partial per workgroup (psw; ssw: 4 doubles of LDS).  The divergence itself is today's, from today's neighbours.
+template <class Src, class Wt>
+__device__ __forceinline__ void ffl_pass1_body(const Src &src, const Wt &wt, int w, int h, int pov_mode, int b,
                                                unsigned long long *__restrict__ pkey, double *__restrict__ psum,
-                                               unsigned long long *skey, double *ssum) {
+                                               unsigned long long *skey, double *ssum, double *__restrict__ psw = nullptr,
+                                               double *ssw = nullptr) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int nstrips = (w + P1_STRIP - 1) / P1_STRIP, ngroups = (h + P1_RG - 1) / P1_RG;
     const int wid = blockIdx.x * (P1_THREADS / 64) + wv;  // wave-uniform
     unsigned long long key = 0;
     double sum = 0.0;
+    [[maybe_unused]] double sw = 0.0;
     if (wid < nstrips * ngroups) {
         const int grp = wid / nstrips, strip = wid - grp * nstrips;
         const int x = strip * P1_STRIP - 1 + 2 * lane, y0 = grp * P1_RG;  // the lane's pixels: x, x+1
@@ -111,10 +135,17 @@ __device__ __forceinline__ void ffl_pass1_body(const Src &src, int w, int h, int
 #pragma unroll 1
         for (int g = 0; g < P1_RG; g += P1_G) {
             float4 raw[P1_G + 2];
+            [[maybe_unused]] unsigned q0[P1_G], q1[P1_G];   // the weights of the group's own rows (the halo rows need none)
 #pragma unroll
             for (int r = 0; r < P1_G + 2; r++) {
                 const int yc = min(max(y0 + g - 1 + r, 0), h - 1);   // clamped: rows past the end repeat row h-1
                 raw[r] = src.load(yc, xa);
+                if constexpr (Wt::on) {
+                    if (r >= 1 && r <= P1_G) {   // in flight with the flow rows
+                        q0[r - 1] = wt.load(yc, min(max(x, 0), w - 1));
+                        q1[r - 1] = wt.load(yc, min(max(x + 1, 0), w - 1));
+                    }
+                }
             }
 #pragma unroll
             for (int r = 0; r < P1_G; r++) {
@@ -125,19 +156,29 @@ __device__ __forceinline__ void ffl_pass1_body(const Src &src, int w, int h, int
                 const float2 dn0 = first0 ? make_float2(td.x, td.y) : make_float2(td.z, td.w), dn1 = first1 ? make_float2(td.x, td.y) : make_float2(td.z, td.w);
                 const bool row_ok = y < h;
                 src.store(y, x, c0, c1, ok0 && row_ok, ok1 && row_ok);
-                sum += (ok0 && row_ok) ? (double)sqrtf(c0.x * c0.x + c0.y * c0.y) : 0.0;
-                sum += (ok1 && row_ok) ? (double)sqrtf(c1.x * c1.x + c1.y * c1.y) : 0.0;
+                bool in0 = ok0 && row_ok, in1 = ok1 && row_ok;
+                if constexpr (Wt::on) {
+                    in0 = in0 && q0[r] > 0u;
+                    in1 = in1 && q1[r] > 0u;
+                    sum += in0 ? (double)sqrtf(c0.x * c0.x + c0.y * c0.y) * (double)q0[r] : 0.0;
+                    sum += in1 ? (double)sqrtf(c1.x * c1.x + c1.y * c1.y) * (double)q1[r] : 0.0;
+                    sw += in0 ? (double)q0[r] : 0.0;
+                    sw += in1 ? (double)q1[r] : 0.0;
+                } else {
+                    sum += in0 ? (double)sqrtf(c0.x * c0.x + c0.y * c0.y) : 0.0;
+                    sum += in1 ? (double)sqrtf(c1.x * c1.x + c1.y * c1.y) : 0.0;
+                }
                 if (!pov_mode) {
                     // horizontal neighbours: the adjacent lanes' pixels (clamped loads make x = 0 / w-1 see themselves)
                     const float left0 = __shfl_up(c1.y, 1, 64), right1 = __shfl_down(c0.y, 1, 64);
                     const float d0 = fabsf(ffl_grad(up0.x, dn0.x, y, h) + ffl_grad(left0, c1.y, x, w));
                     const float d1 = fabsf(ffl_grad(up1.x, dn1.x, y, h) + ffl_grad(c0.y, right1, x + 1, w));
                     const unsigned i0 = (unsigned)y * (unsigned)w + (unsigned)x;
-                    if (ok0 && row_ok) {
+                    if (in0) {
                         const unsigned long long k = ((unsigned long long)ffl_key_bits(d0) << 32) | (unsigned long long)(0xFFFFFFFFu - i0);
                         key = k > key ? k : key;
                     }
-                    if (ok1 && row_ok) {
+                    if (in1) {
                         const unsigned long long k = ((unsigned long long)ffl_key_bits(d1) << 32) | (unsigned long long)(0xFFFFFFFFu - (i0 + 1u));
                         key = k > key ? k : key;
                     }
@@ -147,15 +188,22 @@ __device__ __forceinline__ void ffl_pass1_body(const Src &src, int w, int h, int
     }
     key = ffl_wave_max_u64(key);
     sum = ffl_wave_sum_f64(sum);
-    if (lane == 0) { skey[wv] = key; ssum[wv] = sum; }
+    if constexpr (Wt::on) sw = ffl_wave_sum_f64(sw);
+    if (lane == 0) {
+        skey[wv] = key;
+        ssum[wv] = sum;
+        if constexpr (Wt::on) ssw[wv] = sw;
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int i = 1; i < P1_THREADS / 64; i++) {
             key = skey[i] > key ? skey[i] : key;
             sum += ssum[i];
+            if constexpr (Wt::on) sw += ssw[i];
         }
         pkey[(size_t)b * gridDim.x + blockIdx.x] = key;
         psum[(size_t)b * gridDim.x + blockIdx.x] = sum;
+        if constexpr (Wt::on) psw[(size_t)b * gridDim.x + blockIdx.x] = sw;
     }
 }
 
@@ -166,34 +214,50 @@ __global__ __launch_bounds__(P1_THREADS) void k_pass1(const PairTab *__restrict_
     __shared__ double ssum[P1_THREADS / 64];
     const int b = blockIdx.y;
     const P1SlotSrc src{reinterpret_cast<const float2 *>(pt->flow[0][b]), w};
-    ffl_pass1_body(src, w, h, pov_mode, b, pkey, psum, skey, ssum);
+    ffl_pass1_body(src, WtNone{}, w, h, pov_mode, b, pkey, psum, skey, ssum);
 }
 
-__global__ __launch_bounds__(P1_THREADS) void k_pass1_final(const PairTab *__restrict__ pt, int w, int h, int pov_mode,
-                                                            int nblk, const unsigned long long *__restrict__ pkey,
-                                                            const double *__restrict__ psum) {
-    __shared__ unsigned long long skey[P1_THREADS / 64];
-    __shared__ double ssum[P1_THREADS / 64];
+// The body of k_pass1_final and k_pass1_weighted_final: item b's nblk partials in one order, then its record.  The record
+// under a map (WT) is marked `weighted` and holds the quotient by SW instead of the sum (rule W5 when SW == 0).
+template <bool WT>
+__device__ __forceinline__ void ffl_pass1_final_body(const PairTab *__restrict__ pt, int w, int h, int pov_mode, int nblk,
+                                                     const unsigned long long *__restrict__ pkey,
+                                                     const double *__restrict__ psum, const double *__restrict__ psw,
+                                                     unsigned long long *skey, double *ssum, double *ssw) {
     const int b = blockIdx.x;
     unsigned long long key = 0;
     double sum = 0.0;
+    [[maybe_unused]] double sw = 0.0;
     for (int i = threadIdx.x; i < nblk; i += P1_THREADS) {
         unsigned long long k = pkey[(size_t)b * nblk + i];
         key = k > key ? k : key;
         sum += psum[(size_t)b * nblk + i];
+        if constexpr (WT) sw += psw[(size_t)b * nblk + i];
     }
     key = ffl_wave_max_u64(key);
     sum = ffl_wave_sum_f64(sum);
+    if constexpr (WT) sw = ffl_wave_sum_f64(sw);
     int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) { skey[wv] = key; ssum[wv] = sum; }
+    if (lane == 0) {
+        skey[wv] = key;
+        ssum[wv] = sum;
+        if constexpr (WT) ssw[wv] = sw;
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int i = 1; i < P1_THREADS / 64; i++) {
             key = skey[i] > key ? skey[i] : key;
             sum += ssum[i];
+            if constexpr (WT) sw += ssw[i];
         }
         Pass1Result r;
-        if (pov_mode) {  // FF:880-882: centre of the bottom edge, value 0
+        bool empty = false;
+        if constexpr (WT) empty = sw == 0.0;
+        if (empty) {  // rule W5: no candidate, no term; mag_sum / divisor = +0.0 without a division by zero
+            r.x = w / 2;
+            r.y = h / 2;
+            r.div_val = 0.f;
+        } else if (pov_mode) {  // FF:880-882: centre of the bottom edge, value 0
             r.x = w / 2;
             r.y = h - 1;
             r.div_val = 0.f;
@@ -203,10 +267,19 @@ __global__ __launch_bounds__(P1_THREADS) void k_pass1_final(const PairTab *__res
             r.x = idx - r.y * w;
             r.div_val = ffl_div_at(reinterpret_cast<const float2 *>(pt->flow[0][b]), w, h, r.x, r.y);
         }
-        r.pad = 0.f;
+        r.weighted = WT ? 1 : 0;
         r.mag_sum = sum;
+        if constexpr (WT) r.mag_sum = empty ? 0.0 : sum / (empty ? 1.0 : sw);   // one IEEE division; none by zero
         *pt->res[b] = r;
     }
+}
+
+__global__ __launch_bounds__(P1_THREADS) void k_pass1_final(const PairTab *__restrict__ pt, int w, int h, int pov_mode,
+                                                            int nblk, const unsigned long long *__restrict__ pkey,
+                                                            const double *__restrict__ psum) {
+    __shared__ unsigned long long skey[P1_THREADS / 64];
+    __shared__ double ssum[P1_THREADS / 64];
+    ffl_pass1_final_body<false>(pt, w, h, pov_mode, nblk, pkey, psum, nullptr, skey, ssum, nullptr);
 }
 
 void ffl_launch_pass1(const PairTab *pt, int nB, int w, int h, int pov_mode, unsigned long long *pkey, double *psum,
@@ -226,17 +299,21 @@ void ffl_launch_pass1(const PairTab *pt, int nB, int w, int h, int pov_mode, uns
 // the same slot, centre and pov_mode.  Components 1..3 reuse the pixel's u, v, dx, dy and weights:
 // tangential ((v dx - u dy) wx) wy, shift_x (u wx) wy, shift_y (v wx) wy.  Component c of workgroup g of item b goes to
 // psum[(b * NC + c) * gridDim.x + g]; ssum holds NC * 4 doubles.  G: rows of the row group whose loads are in flight together.
-template <int NC, int G>
-__device__ __forceinline__ void ffl_radial_body(const float2 *__restrict__ flow, double cx, double cy, int w, int h,
+// Wt::on (k_radial_axes_weighted, rule W4): every term is today's, times (double)weight once more, and enters its sum only
+// where the weight is > 0 (a select); SW = sum of the weights is one more component, index NC, so psum and ssum hold
+// NC + 1 of them per item and workgroup.
+template <int NC, int G, class Wt>
+__device__ __forceinline__ void ffl_radial_body(const float2 *__restrict__ flow, const Wt &wt, double cx, double cy, int w, int h,
                                                 int pov_mode, int b, const double *__restrict__ wytab,
                                                 double *__restrict__ psum, double *ssum) {
+    constexpr int NS = NC + (Wt::on ? 1 : 0);   // sums per lane
     const double dw = (double)w;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int nstrips = (w + P2_STRIP - 1) / P2_STRIP, ngroups = (h + P1_RG - 1) / P1_RG;
     const int wid = blockIdx.x * (P1_THREADS / 64) + wv;  // wave-uniform
-    double sum[NC];
+    double sum[NS];
 #pragma unroll
-    for (int c = 0; c < NC; c++) sum[c] = 0.0;
+    for (int c = 0; c < NS; c++) sum[c] = 0.0;
     if (wid < nstrips * ngroups) {
         const int grp = wid / nstrips, strip = wid - grp * nstrips;
         const int x = strip * P2_STRIP + 2 * lane, y0 = grp * P1_RG;  // the lane's pixels: x, x+1
@@ -250,8 +327,16 @@ __device__ __forceinline__ void ffl_radial_body(const float2 *__restrict__ flow,
 #pragma unroll 1
         for (int g = 0; g < P1_RG; g += G) {
             float2 f0[G], f1[G];
+            [[maybe_unused]] unsigned q0[G], q1[G];
 #pragma unroll
-            for (int r = 0; r < G; r++) ffl_load_pair(flow, w, h, x, y0 + g + r, f0[r], f1[r]);
+            for (int r = 0; r < G; r++) {
+                ffl_load_pair(flow, w, h, x, y0 + g + r, f0[r], f1[r]);
+                if constexpr (Wt::on) {   // the flow's clamps; in flight with the flow rows
+                    const int yq = min(y0 + g + r, h - 1);
+                    q0[r] = wt.load(yq, min(x, w - 1));
+                    q1[r] = wt.load(yq, min(x + 1, w - 1));
+                }
+            }
 #pragma unroll
             for (int r = 0; r < G; r++) {
                 const int y = y0 + g + r;
@@ -260,60 +345,83 @@ __device__ __forceinline__ void ffl_radial_body(const float2 *__restrict__ flow,
                 const double wy = pov_mode ? 1.0 : (((double)y > cy) ? wytab[yc] : wytab[h + yc]);
                 const double t0 = ((double)f0[r].x * dx0 + (double)f0[r].y * dy) * wx0 * wy;
                 const double t1 = ((double)f1[r].x * dx1 + (double)f1[r].y * dy) * wx1 * wy;
-                sum[0] += (ok0 && y < h) ? t0 : 0.0;
-                sum[0] += (ok1 && y < h) ? t1 : 0.0;
-                if constexpr (NC > 1) {
+                if constexpr (Wt::on) {
+                    static_assert(NC == FFL_NAXES, "the weighted form is the four-component one");
+                    const bool in0 = ok0 && y < h && q0[r] > 0u, in1 = ok1 && y < h && q1[r] > 0u;
+                    const double p0 = (double)q0[r], p1 = (double)q1[r];
                     const double u0 = (double)f0[r].x, v0 = (double)f0[r].y, u1 = (double)f1[r].x, v1 = (double)f1[r].y;
                     const double a0 = (v0 * dx0 - u0 * dy) * wx0 * wy, a1 = (v1 * dx1 - u1 * dy) * wx1 * wy;
-                    sum[1] += (ok0 && y < h) ? a0 : 0.0;
-                    sum[1] += (ok1 && y < h) ? a1 : 0.0;
-                    sum[2] += (ok0 && y < h) ? u0 * wx0 * wy : 0.0;
-                    sum[2] += (ok1 && y < h) ? u1 * wx1 * wy : 0.0;
-                    sum[3] += (ok0 && y < h) ? v0 * wx0 * wy : 0.0;
-                    sum[3] += (ok1 && y < h) ? v1 * wx1 * wy : 0.0;
+                    sum[0] += in0 ? t0 * p0 : 0.0;
+                    sum[0] += in1 ? t1 * p1 : 0.0;
+                    sum[1] += in0 ? a0 * p0 : 0.0;
+                    sum[1] += in1 ? a1 * p1 : 0.0;
+                    sum[2] += in0 ? u0 * wx0 * wy * p0 : 0.0;
+                    sum[2] += in1 ? u1 * wx1 * wy * p1 : 0.0;
+                    sum[3] += in0 ? v0 * wx0 * wy * p0 : 0.0;
+                    sum[3] += in1 ? v1 * wx1 * wy * p1 : 0.0;
+                    sum[NC] += in0 ? p0 : 0.0;
+                    sum[NC] += in1 ? p1 : 0.0;
+                } else {
+                    sum[0] += (ok0 && y < h) ? t0 : 0.0;
+                    sum[0] += (ok1 && y < h) ? t1 : 0.0;
+                    if constexpr (NC > 1) {
+                        const double u0 = (double)f0[r].x, v0 = (double)f0[r].y, u1 = (double)f1[r].x, v1 = (double)f1[r].y;
+                        const double a0 = (v0 * dx0 - u0 * dy) * wx0 * wy, a1 = (v1 * dx1 - u1 * dy) * wx1 * wy;
+                        sum[1] += (ok0 && y < h) ? a0 : 0.0;
+                        sum[1] += (ok1 && y < h) ? a1 : 0.0;
+                        sum[2] += (ok0 && y < h) ? u0 * wx0 * wy : 0.0;
+                        sum[2] += (ok1 && y < h) ? u1 * wx1 * wy : 0.0;
+                        sum[3] += (ok0 && y < h) ? v0 * wx0 * wy : 0.0;
+                        sum[3] += (ok1 && y < h) ? v1 * wx1 * wy : 0.0;
+                    }
                 }
             }
         }
     }
 #pragma unroll
-    for (int c = 0; c < NC; c++) {
+    for (int c = 0; c < NS; c++) {
         sum[c] = ffl_wave_sum_f64(sum[c]);
         if (lane == 0) ssum[c * (P1_THREADS / 64) + wv] = sum[c];
     }
     __syncthreads();
     if (threadIdx.x == 0) {
 #pragma unroll
-        for (int c = 0; c < NC; c++) {
+        for (int c = 0; c < NS; c++) {
             for (int i = 1; i < P1_THREADS / 64; i++) sum[c] += ssum[c * (P1_THREADS / 64) + i];
-            psum[((size_t)b * NC + c) * gridDim.x + blockIdx.x] = sum[c];
+            psum[((size_t)b * NS + c) * gridDim.x + blockIdx.x] = sum[c];
         }
     }
 }
 
 // The body of k_radial_final (NC = 1) and k_radial_axes_final (NC = FFL_NAXES): each component's nblk partials of item b
 // in one order; the means are valid in thread 0.  ssum holds NC * 4 doubles.
-template <int NC>
+// WT (k_radial_axes_weighted_final): NS = NC + 1 sums per item, the last one SW, which replaces the pixel count as the one
+// divisor; SW == 0 (rule W5) divides the all-zero sums by 1.0 instead, +0.0 without a division by zero.
+template <int NC, bool WT = false>
 __device__ __forceinline__ void ffl_radial_final_body(int w, int h, int nblk, int b, const double *__restrict__ psum,
-                                                      double *ssum, double (&sum)[NC]) {
+                                                      double *ssum, double (&sum)[NC + (WT ? 1 : 0)]) {
+    constexpr int NS = NC + (WT ? 1 : 0);
 #pragma unroll
-    for (int c = 0; c < NC; c++) sum[c] = 0.0;
+    for (int c = 0; c < NS; c++) sum[c] = 0.0;
     for (int i = threadIdx.x; i < nblk; i += P1_THREADS) {
 #pragma unroll
-        for (int c = 0; c < NC; c++) sum[c] += psum[((size_t)b * NC + c) * nblk + i];
+        for (int c = 0; c < NS; c++) sum[c] += psum[((size_t)b * NS + c) * nblk + i];
     }
     int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
-    for (int c = 0; c < NC; c++) {
+    for (int c = 0; c < NS; c++) {
         sum[c] = ffl_wave_sum_f64(sum[c]);
         if (lane == 0) ssum[c * (P1_THREADS / 64) + wv] = sum[c];
     }
     __syncthreads();
     if (threadIdx.x == 0) {
 #pragma unroll
-        for (int c = 0; c < NC; c++) {
+        for (int c = 0; c < NS; c++)
             for (int i = 1; i < P1_THREADS / 64; i++) sum[c] += ssum[c * (P1_THREADS / 64) + i];
-            sum[c] = sum[c] / ((double)w * (double)h);
-        }
+        double divisor = (double)w * (double)h;
+        if constexpr (WT) divisor = sum[NC] == 0.0 ? 1.0 : sum[NC];
+#pragma unroll
+        for (int c = 0; c < NC; c++) sum[c] = sum[c] / divisor;
     }
 }
 
@@ -325,7 +433,7 @@ __global__ __launch_bounds__(P1_THREADS) void k_radial(const WindowItem *__restr
     __shared__ double ssum[P1_THREADS / 64];
     const int b = blockIdx.y;
     if (tab[b].cut) return;   // workgroup-uniform: FF:766-767, a cut is 0.0 without a look at the flow
-    ffl_radial_body<1, 8>(reinterpret_cast<const float2 *>(tab[b].flow), tab[b].cx, tab[b].cy, w, h, pov_mode, b, wytab, psum, ssum);
+    ffl_radial_body<1, 8>(reinterpret_cast<const float2 *>(tab[b].flow), WtNone{}, tab[b].cx, tab[b].cy, w, h, pov_mode, b, wytab, psum, ssum);
 }
 
 __global__ __launch_bounds__(P1_THREADS) void k_radial_final(const WindowItem *__restrict__ tab, int w, int h, int nblk,
@@ -356,7 +464,7 @@ __global__ __launch_bounds__(P1_THREADS) void k_radial_axes(const WindowItem *__
     __shared__ double ssum[FFL_NAXES * (P1_THREADS / 64)];
     const int b = blockIdx.y;
     if (tab[b].cut) return;   // workgroup-uniform, as k_radial
-    ffl_radial_body<FFL_NAXES, P2_AXES_G>(reinterpret_cast<const float2 *>(tab[b].flow), tab[b].cx, tab[b].cy, w, h, pov_mode, b, wytab, psum,
+    ffl_radial_body<FFL_NAXES, P2_AXES_G>(reinterpret_cast<const float2 *>(tab[b].flow), WtNone{}, tab[b].cx, tab[b].cy, w, h, pov_mode, b, wytab, psum,
                                ssum);
 }
 
@@ -380,6 +488,44 @@ void ffl_launch_radial_axes(const WindowItem *tab, int n, int w, int h, int pov_
     const int nblk = ffl_radial_blocks(w, h);
     hipLaunchKernelGGL(k_radial_axes, dim3(nblk, n), dim3(P1_THREADS), 0, st, tab, w, h, pov_mode, wytab, psum);
     hipLaunchKernelGGL(k_radial_axes_final, dim3(n), dim3(P1_THREADS), 0, st, tab, w, h, nblk, psum, out);
+}
+
+// The weighted four-component pair: k_radial_axes' grid and bodies with the items' maps -- item b's
+// at wbase + b * witem, rows wpitch bytes apart -- and FFL_NAXES + 1 partials per workgroup.  A cut item reads neither its
+// flow nor its map (rule W6).
+__global__ __launch_bounds__(P1_THREADS) void k_radial_axes_weighted(const WindowItem *__restrict__ tab, int w, int h, int pov_mode,
+                                                                     const double *__restrict__ wytab, const char *__restrict__ wbase,
+                                                                     long long witem, long long wpitch, double *__restrict__ psum) {
+    __shared__ double ssum[(FFL_NAXES + 1) * (P1_THREADS / 64)];
+    const int b = blockIdx.y;
+    if (tab[b].cut) return;   // workgroup-uniform, as k_radial
+    const WtBytes wt{wbase + (long long)b * witem, wpitch};
+    ffl_radial_body<FFL_NAXES, P2_AXES_G>(reinterpret_cast<const float2 *>(tab[b].flow), wt, tab[b].cx, tab[b].cy, w, h, pov_mode, b, wytab,
+                                          psum, ssum);
+}
+
+__global__ __launch_bounds__(P1_THREADS) void k_radial_axes_weighted_final(const WindowItem *__restrict__ tab, int w, int h, int nblk,
+                                                                           const double *__restrict__ psum,
+                                                                           AxesRecord *__restrict__ out) {
+    __shared__ double ssum[(FFL_NAXES + 1) * (P1_THREADS / 64)];
+    const int b = blockIdx.x;
+    double mean[FFL_NAXES + 1] = {0.0, 0.0, 0.0, 0.0, 0.0};   // a cut item: its partials were never written
+    if (!tab[b].cut) ffl_radial_final_body<FFL_NAXES, true>(w, h, nblk, b, psum, ssum, mean);   // workgroup-uniform
+    if (threadIdx.x == 0) {
+        out[b].base.dot = mean[0];
+        out[b].tangential = mean[1];
+        out[b].shift_x = mean[2];
+        out[b].shift_y = mean[3];
+        out[b].reserved = 0.0;
+    }
+}
+
+void ffl_launch_radial_axes_weighted(const WindowItem *tab, int n, int w, int h, int pov_mode, const double *wytab,
+                                     const WeightArgs &wa, double *psum, AxesRecord *out, hipStream_t st) {
+    const int nblk = ffl_radial_blocks(w, h);
+    hipLaunchKernelGGL(k_radial_axes_weighted, dim3(nblk, n), dim3(P1_THREADS), 0, st, tab, w, h, pov_mode, wytab, wa.base, wa.item,
+                       wa.pitch, psum);
+    hipLaunchKernelGGL(k_radial_axes_weighted_final, dim3(n), dim3(P1_THREADS), 0, st, tab, w, h, nblk, psum, out);
 }
 
 // ---- pass 2 behind the batches, host-free (ffl_radial_window) ---------------------------------
@@ -419,7 +565,7 @@ __global__ __launch_bounds__(W2_THREADS) void k_window_plan(const WindowSeq seq,
     const double cnt = (double)(b - a + 1);
     const double cx = (double)tx / cnt, cy = (double)ty / cnt;   // one IEEE division each: pipeline.smooth_centers
     const Pass1Result *r = res + slot;
-    const float mm = (float)(r->mag_sum / npx);                  // ffl_pass1_results' expressions
+    const float mm = (float)ffl_record_mean(*r, npx);            // ffl_pass1_results' expressions
     const int cut = mm > cut_threshold ? 1 : 0;                  // NaN > threshold is false
     WindowItem it;
     it.flow = flow + (size_t)slot * 2 * N;
@@ -601,7 +747,7 @@ __global__ __launch_bounds__(P1_THREADS) void k_import_pass1(const ImportArgs a,
     const size_t N = (size_t)w * h;
     ffl_import_publish(a, tab, N, pt, b);
     const P1ImportSrc<DT, MODE> src{a.base + (long long)b * a.item, a.pitch, a.ps, a.cs, a.flow + (size_t)tab.slot[b] * 2 * N, w};
-    ffl_pass1_body(src, w, h, pov_mode, b, pkey, psum, skey, ssum);
+    ffl_pass1_body(src, WtNone{}, w, h, pov_mode, b, pkey, psum, skey, ssum);
 }
 
 // The two-launch form (ffl_ctx option import_fused = 0, the A/B of DESIGN.md section 13): a plain conversion into the
@@ -656,4 +802,37 @@ void ffl_launch_import_pass1(const ImportArgs &a, const ExportTab &tab, int n, i
     FFL_IMP_CASE(FFL_IMP_BF16, FFL_IMP_NHWC)
     FFL_IMP_CASE(FFL_IMP_BF16, FFL_IMP_ANY)
 #undef FFL_IMP_CASE
+}
+
+// ---- pass 1 under weight maps (ffl_pass1_weighted) ----------------------------------------------
+// k_pass1's walk over flow slots tab.slot[0..n) with item b's map at wa.base + b * wa.item; workgroup (0, b) names the slot
+// and its record in `pt` for the final kernel, as the import does.
+__global__ __launch_bounds__(P1_THREADS) void k_pass1_weighted(const ImportArgs a, const ExportTab tab, int w, int h, int pov_mode,
+                                                               PairTab *__restrict__ pt, unsigned long long *__restrict__ pkey,
+                                                               double *__restrict__ psum, double *__restrict__ psw) {
+    __shared__ unsigned long long skey[P1_THREADS / 64];
+    __shared__ double ssum[P1_THREADS / 64], ssw[P1_THREADS / 64];
+    const int b = blockIdx.y;
+    const size_t N = (size_t)w * h;
+    ffl_import_publish(a, tab, N, pt, b);
+    const P1SlotSrc src{reinterpret_cast<const float2 *>(a.flow + (size_t)tab.slot[b] * 2 * N), w};
+    const WtBytes wt{a.base + (long long)b * a.item, a.pitch};
+    ffl_pass1_body(src, wt, w, h, pov_mode, b, pkey, psum, skey, ssum, psw, ssw);
+}
+
+__global__ __launch_bounds__(P1_THREADS) void k_pass1_weighted_final(const PairTab *__restrict__ pt, int w, int h, int pov_mode,
+                                                                     int nblk, const unsigned long long *__restrict__ pkey,
+                                                                     const double *__restrict__ psum,
+                                                                     const double *__restrict__ psw) {
+    __shared__ unsigned long long skey[P1_THREADS / 64];
+    __shared__ double ssum[P1_THREADS / 64], ssw[P1_THREADS / 64];
+    ffl_pass1_final_body<true>(pt, w, h, pov_mode, nblk, pkey, psum, psw, skey, ssum, ssw);
+}
+
+void ffl_launch_pass1_weighted(const WeightArgs &wa, float *flow, Pass1Result *res, const ExportTab &tab, int n, int w, int h,
+                               int pov_mode, PairTab *pt, unsigned long long *pkey, double *psum, double *psw, hipStream_t st) {
+    const int nblk = ffl_pass1_blocks(w, h);
+    const ImportArgs a{wa.base, wa.item, wa.pitch, 1, 0, flow, res};
+    hipLaunchKernelGGL(k_pass1_weighted, dim3(nblk, n), dim3(P1_THREADS), 0, st, a, tab, w, h, pov_mode, pt, pkey, psum, psw);
+    hipLaunchKernelGGL(k_pass1_weighted_final, dim3(n), dim3(P1_THREADS), 0, st, pt, w, h, pov_mode, nblk, pkey, psum, psw);
 }

@@ -307,7 +307,7 @@ class PairEngine:
         return recs
 
     def process_chunk(self, frames, pov_mode=False, cut_threshold=7.0, algo=None, farneback=OWN, flows_out=None, window=OWN,
-                      post_out=None, axes=False):
+                      post_out=None, axes=False, weights=None):
         """One whole chunk on one GPU: returns (dots float64[n], records) with n = len(frames)-1.  `algo`, `farneback`,
         `window`: see pass1_pairs (default: the engine's own flow algorithm, parameters and window).  `flows_out`: a float32 device array of
         (n, H, W, 2) or (n, 2, H, W) that receives every pair's flow field (Context.export_flows, on torch's current stream)
@@ -320,9 +320,18 @@ class PairEngine:
         the call returns once the chunk's last batch has run.
         `axes`: True returns (comps float64[n, 4], records) -- the four components of _capi.AXES (Context.radial_axes;
         column 0 has the bits of the dots) -- and with post_out a buffer of 80-byte records (_capi.PASS2_AXES_DTYPE,
-        post_records(..., axes=True))."""
+        post_records(..., axes=True)).
+        `weights`: a per-pixel weight map, a uint8 / bool device tensor (H, W) for every pair or
+        (n, H, W), one map per pair.  The chunk then runs the device schedule: post_out defaults to a new buffer, the
+        records are the 80-byte form whatever `axes` says, and behind each batch Context.pass1_weighted is queued on its
+        slots, then its window calls as Context.radial_window_axes_weighted.  The flow (and flows_out) is unchanged."""
         ctx, B = self.ctx, self.B
         n = len(frames) - 1
+        maps = weights   # the tensor stays referenced while the calls that read it are queued
+        if weights is not None and n >= 1:
+            weights, axes, post_out = _chunk_weights(ctx, maps, n), True, True if post_out is None else post_out
+        elif weights is not None:
+            weights, axes, post_out = None, True, True if post_out is None else post_out
         if n < 1:
             return (_no_scalars(axes), []) if post_out is None else (post_buffer(ctx, 0, axes) if post_out is True else post_out)
         if post_out is True:
@@ -336,7 +345,7 @@ class PairEngine:
                 raise ValueError(f"flows_out must be ({n}, {ctx.height}, {ctx.width}, 2) or ({n}, 2, {ctx.height}, "
                                  f"{ctx.width}), got {shp}")
         if post_out is not None:
-            post = _DevicePost(ctx, n, B, pov_mode, cut_threshold, post_out, axes)
+            post = _DevicePost(ctx, n, B, pov_mode, cut_threshold, post_out, axes, weights)
             release = getattr(frames, "release", None)
             marks = []   # (event, frames that have left the host once it completes), oldest first
 
@@ -373,14 +382,15 @@ class PairEngine:
         self.pass1(frames, 0, n, pov_mode, cut_threshold, on_batch, algo=algo, farneback=farneback, window=window)
         return post.finish()
 
-    def process_flows(self, flows, pov_mode=False, cut_threshold=7.0, post_out=None, axes=False):
+    def process_flows(self, flows, pov_mode=False, cut_threshold=7.0, post_out=None, axes=False, weights=None):
         """One whole chunk from flow fields the caller computed: returns (dots float64[n], records), the contract of
         process_chunk.  `flows` holds the chunk's n pair fields in device memory: one array (n, H, W, 2) or (n, 2, H, W)
         (float32, float16 or bfloat16, any strides; see _capi.device_flows) or a sequence of such arrays (single (H, W, 2)
         fields included), in pair order.  They are imported B at a time into the slot ring (Context.import_flows, on
         torch's current stream) with `depth` batches in flight; the +-6 window and pass 2 are process_chunk's own.
         `post_out`: as in process_chunk (a buffer, or True for a new one) -- pass 2 is queued on the device behind each
-        import, nothing waits, and the buffer is returned for post_records.  `axes`: as in process_chunk."""
+        import, nothing waits, and the buffer is returned for post_records.  `axes`, `weights`: as in process_chunk (with
+        weights: the device schedule, 80-byte records, pass1_weighted behind each import)."""
         ctx, B, fs = self.ctx, self.B, self.ctx.flow_slots
         segs = []   # (descriptor, dtype, first pair, count): one per source array
         n = 0
@@ -388,12 +398,15 @@ class PairEngine:
             desc, dt, k = _capi.device_flows(a, ctx.width, ctx.height)
             segs.append((desc, dt, n, k))
             n += k
+        maps = weights   # the tensor stays referenced while the calls that read it are queued
+        if weights is not None:
+            weights, axes, post_out = _chunk_weights(ctx, maps, n), True, True if post_out is None else post_out
         if post_out is True:
             post_out = post_buffer(ctx, n, axes)
         if n < 1:
             return (_no_scalars(axes), []) if post_out is None else post_out
         post = (_ChunkPost(ctx, n, B, pov_mode, axes) if post_out is None else
-                _DevicePost(ctx, n, B, pov_mode, cut_threshold, post_out, axes))
+                _DevicePost(ctx, n, B, pov_mode, cut_threshold, post_out, axes, weights))
 
         def enqueue(j0):
             j1 = min(j0 + B, n)
@@ -428,6 +441,14 @@ class PairEngine:
 def _no_scalars(axes):
     """the scalars of a chunk without pairs"""
     return np.zeros((0, len(_capi.AXES))) if axes else np.zeros(0)
+
+
+def _chunk_weights(ctx, weights, n):
+    """the _capi.DevWeights of a chunk of n pairs: `weights` is one (H, W) map for every pair or (n, H, W), one per pair"""
+    desc, m = _capi.device_weights(weights, ctx.width, ctx.height)
+    if m not in (0, n):
+        raise ValueError(f"weights: {m} maps for a chunk of {n} pairs (one (H, W) map, or one per pair)")
+    return desc
 
 
 class _ChunkPost:
@@ -473,10 +494,13 @@ class _DevicePost:
     """_ChunkPost's schedule on the device: after_batch(k) queues the Context.radial_window calls window_calls lists for
     batch k (pair j in flow slot j % flow_slots, its record at byte 48 * j of `out`) on a stream of their own
     (_side_stream); finish() makes torch's current stream wait for them.  Nothing is read back.  axes=True: the calls are
-    Context.radial_window_axes and the records 80 bytes."""
+    Context.radial_window_axes and the records 80 bytes.  weights (a _capi.DevWeights of the chunk's pairs, with axes):
+    after_batch(k) first queues Context.pass1_weighted on batch k's slots, and its calls are
+    Context.radial_window_axes_weighted with the maps of their computed pairs."""
 
-    def __init__(self, ctx, n, B, pov_mode, cut_threshold, out, axes=False):
+    def __init__(self, ctx, n, B, pov_mode, cut_threshold, out, axes=False, weights=None):
         self.ctx, self.pov_mode, self.cut_threshold = ctx, pov_mode, cut_threshold
+        self.n, self.B, self.weights = n, B, weights
         self.window, self.item = (ctx.radial_window_axes if axes else ctx.radial_window), _post_dtype(axes).itemsize
         self.base, nbytes = _capi._device_span(out)
         if nbytes < n * self.item:
@@ -489,12 +513,24 @@ class _DevicePost:
     def after_batch(self, k):
         """queue batch k's calls; returns the number of leading pairs whose batches these calls have waited for (0: none)"""
         fs, item, done = self.ctx.flow_slots, self.item, 0
+        if self.weights is not None:   # the batch's records under the maps, before any window call reads them
+            j0, j1 = k * self.B, min((k + 1) * self.B, self.n)
+            self.ctx.pass1_weighted([j % fs for j in range(j0, j1)], self._maps(j0), self.pov_mode, self.stream)
         for lo, hi, first, count, _ in self.calls.get(k, ()):
             out = _capi._DeviceSpan(self.base + (lo + first) * item, count * item)
-            self.window([j % fs for j in range(lo, hi)], first, count, out, SMOOTH_RADIUS, self.cut_threshold, self.pov_mode,
-                        self.stream)
+            seq = [j % fs for j in range(lo, hi)]
+            if self.weights is not None:
+                self.ctx.radial_window_axes_weighted(seq, first, count, self._maps(lo + first), out, SMOOTH_RADIUS,
+                                                     self.cut_threshold, self.pov_mode, self.stream)
+            else:
+                self.window(seq, first, count, out, SMOOTH_RADIUS, self.cut_threshold, self.pov_mode, self.stream)
             done = hi
         return done
+
+    def _maps(self, j):
+        """the maps of pairs j, j + 1, ... (a static map: itself)"""
+        w = self.weights
+        return _capi.DevWeights(w.base + j * w.item_stride, w.item_stride, w.row_pitch)
 
     def finish(self):
         """the records are complete for work queued on torch's current stream from here on"""
@@ -546,9 +582,34 @@ def _scripts_from_chunks(chunks, extra, fps, params):
             for suffix, col in [("", 0)] + extra}
 
 
+def static_weights(engine, params):
+    """params["hip_weights"], an (H, W) uint8 / bool numpy array or torch tensor, as a device tensor on the engine's
+    device: the static weight map of every pair; None without the key."""
+    w = params.get("hip_weights")
+    if w is None:
+        return None
+    import torch
+    t = w if isinstance(w, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(w))
+    if t.dtype not in (torch.uint8, torch.bool):
+        raise ValueError(f"hip_weights: dtype {t.dtype} is not supported, weight maps are uint8 or bool")
+    ctx = engine.ctx
+    if tuple(t.shape) != (ctx.height, ctx.width):
+        raise ValueError(f"hip_weights: shape {tuple(t.shape)} is not (H, W) = ({ctx.height}, {ctx.width})")
+    return t.to(torch.device("cuda", ctx.device)).contiguous()
+
+
+def _weighted_scalars(buf, axes):
+    """(dots or comps, records) out of a weighted chunk's buffer of 80-byte records"""
+    comps, recs = post_records(buf, axes=True)
+    return (comps if axes else comps[:, 0]), recs
+
+
 def _flow_scalars(engine, flows, params, axes=False):
     """(dots or comps, records) of one chunk of caller flows under params (see _chunk_scalars)"""
     pov, thr = bool(params.get("pov_mode", False)), float(params.get("cut_threshold", 7))
+    wts = static_weights(engine, params)
+    if wts is not None:   # params["hip_weights"]: the device schedule under the static map
+        return _weighted_scalars(engine.process_flows(flows, pov, thr, weights=wts), axes)
     if _pass2_mode(params):   # params["hip_pass2"] = "device": one buffer and one read per chunk
         return post_records(engine.process_flows(flows, pov, thr, post_out=True, **_axes_kw(axes)), **_axes_kw(axes))
     return engine.process_flows(flows, pov, thr, **_axes_kw(axes))
@@ -597,6 +658,9 @@ def _chunk_scalars(engine, frames, params, axes=False, **kw):
     """(dots, records) of one chunk under params: engine.process_chunk, or -- params["hip_pass2"] = "device" -- its device
     pass 2 with one buffer and one read for the chunk; axes=True: (comps float64[n, 4], records)"""
     pov, thr = bool(params.get("pov_mode", False)), float(params.get("cut_threshold", 7))
+    wts = static_weights(engine, params)
+    if wts is not None:   # params["hip_weights"]: the device schedule under the static map
+        return _weighted_scalars(engine.process_chunk(frames, pov, thr, weights=wts, **kw), axes)
     kw.update(_axes_kw(axes))
     if not _pass2_mode(params):
         return engine.process_chunk(frames, pov, thr, **kw)

@@ -472,6 +472,58 @@ int ffl_radial_window_axes(ffl_ctx *ctx, int n_seq, const int *seq_slots, int fi
  * not count it; 20 KiB of page-locked records come with it).  Needs no device. */
 int ffl_axes_extra_bytes(int width, int height, size_t *bytes);
 
+/* ---- Per-pixel weight maps for pass 1 and the four-component pass 2 ----
+ * A map is height x width uint8 in device memory, the context's size; the pixels of a row are contiguous.  Item i of a
+ * call uses the map at  base + i*item_stride + y*row_pitch + x  (bytes); item_stride == 0: one map for all items (a static
+ * mask).  The flow itself is never touched.  The rules:
+ *   W1  the weight of a pixel is wt = (double)W[y][x], an integer 0..255.  W == 0 excludes the pixel by a select, never by
+ *       a multiplication: a NaN or inf in an excluded pixel's flow reaches no sum, key or record.  SW = sum of wt, exact.
+ *   W2  the divergence at a pixel is the unweighted one, from the same neighbours whatever their weights; only the pixel's
+ *       candidacy for the argmax needs W > 0.  Among candidates: the first NaN of |div| in row-major order, else the first
+ *       maximum (ffl_pass1_result's rule).
+ *   W3  mean_mag = (float)(sum of (double)mag * wt / SW), added in pass 1's order; cut = mean_mag > cut_threshold.
+ *   W4  each of the four components is (sum of term * wt) / SW: term is exactly the unweighted ((...) wx) wy, multiplied
+ *       once more by wt, added in ffl_radial's order and divided once by (double)SW.
+ *   W5  an empty map (SW == 0): the pass-1 record is x = width / 2, y = height / 2, div_val = +0.0, mean_mag = +0.0, cut = 0;
+ *       all four components are +0.0.  No division by zero is executed.
+ *   W6  a cut item gets +0.0 in all four components; neither its flow nor its map is read.
+ * An all-ones map gives the bits of the unweighted calls, in either pov_mode. */
+typedef struct ffl_dev_weights {
+    const void *base;
+    ptrdiff_t item_stride, row_pitch;   /* bytes */
+} ffl_dev_weights;
+
+/* The geometry rules of a weight descriptor for n maps of width x height.  Pure host check: no device or context needed.
+ * FFL_ERR_INVALID with the rule in ffl_last_error(NULL): a NULL descriptor or base; n < 1; a size outside 2..32768;
+ * negative strides or strides beyond 2^40; overlap: row_pitch < width, or 0 < item_stride < (height - 1) * row_pitch +
+ * width.  The maps span (n - 1) * item_stride + (height - 1) * row_pitch + width bytes from base. */
+int ffl_dev_weights_check(int n, int width, int height, const ffl_dev_weights *w);
+
+/* Recompute the pass-1 records of flow slots flow_slots[0..n) under the maps (rules W2, W3, W5); the flow is only read.  The
+ * records replace the slots' records until a later writer of the slot (a batch, ffl_upload_flow, ffl_import_flows) puts
+ * an ordinary record back; ffl_pass1_results and the window calls read whichever record the slot holds.  Refusals, stream
+ * contract and publishing are ffl_import_flows': n outside 1..max_batch; a slot out of range or repeated; a slot that
+ * holds no flow (FFL_ERR_STATE); any rule of ffl_dev_weights_check; maps that are not device memory of the context's
+ * device or do not lie inside one allocation (page-locked host memory is refused); a capturing `stream` (FFL_ERR_STATE).
+ * Queued on the library's stream behind the work queued on `stream` and the slots' last users -- one k_pass1_weighted
+ * launch for all n items plus its final kernel -- and `stream` waits for it; never captured; the host does not wait.  The
+ * first weighted call of a context allocates what ffl_weights_extra_bytes reports. */
+int ffl_pass1_weighted(ffl_ctx *ctx, int n, const int *flow_slots, const ffl_dev_weights *w, int pov_mode, uint64_t stream);
+
+/* ffl_radial_window_axes under rule W4: `w` describes the maps of the n computed items (item i of the call, seq index
+ * first + i); neighbours contribute their records only.  Windows, the centre mean and the cut test are
+ * ffl_radial_window's, from whatever records the seq slots hold -- normally those of ffl_pass1_weighted; unweighted ones
+ * are allowed.  The same refusals and stream contract, plus the map rules of ffl_pass1_weighted; out_dev is checked
+ * before the maps.  Its three launches are k_window_plan, k_radial_axes_weighted and k_radial_axes_weighted_final. */
+int ffl_radial_window_axes_weighted(ffl_ctx *ctx, int n_seq, const int *seq_slots, int first, int n, int radius,
+                                    float cut_threshold, int pov_mode, const ffl_dev_weights *w, ffl_axes_record *out_dev,
+                                    uint64_t stream);
+
+/* Device memory the weighted calls add to a context of this size, allocated by the first such call and freed by
+ * ffl_destroy: FFL_N_AXES + 1 partial sums per workgroup of the radial grid for FFL_MAX_BATCH items, which pass 1's one
+ * extra partial per workgroup shares (ffl_estimate_bytes does not count it).  Needs no device. */
+int ffl_weights_extra_bytes(int width, int height, size_t *bytes);
+
 /* Copy a finished flow field to host memory as (height, width, 2) float32, cv2 layout. */
 int ffl_download_flow(ffl_ctx *ctx, int flow_slot, float *dst);
 
