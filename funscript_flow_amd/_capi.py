@@ -30,9 +30,18 @@ EXPORTS = ["ffl_device_count", "ffl_create", "ffl_destroy", "ffl_last_error", "f
            "ffl_dev_flow_check", "ffl_import_flows", "ffl_radial_window",
            "ffl_radial_axes", "ffl_radial_window_axes", "ffl_axes_extra_bytes",
            "ffl_dev_weights_check", "ffl_pass1_weighted", "ffl_radial_window_axes_weighted", "ffl_weights_extra_bytes",
+           "ffl_cell_grid_check", "ffl_cell_stats", "ffl_radial_window_axes_centres", "ffl_cells_extra_bytes",
            "ffl_upload_frames_raw_src", "ffl_upload_frames_yuv_src", "ffl_upload_frames_yuv16_src", "ffl_frontend_yuv_window_src",
            "ffl_frontend_yuv16_window_src", "ffl_dev_frame_check_src", "ffl_dev_frame_check16_src",
            "ffl_upload_frames_device_src", "ffl_upload_frames_device16_src"]
+
+# the per-cell statistics grid and the variance centre: ffl_cell_record, ffl_grid_centre, FFL_MAX_CELLS
+FFL_MAX_CELLS = 64
+CELL_DTYPE = np.dtype({"names": ["mean_u", "mean_v", "mean_mag", "var_mag"], "formats": ["<f8"] * 4,
+                       "offsets": [0, 8, 16, 24], "itemsize": 32})
+GRID_CENTRE_DTYPE = np.dtype({"names": ["cx", "cy", "total_var", "cells", "empty"],
+                              "formats": ["<f8", "<f8", "<f8", "<i4", "<i4"], "offsets": [0, 8, 16, 24, 28], "itemsize": 32})
+CENTERS = ("variance",)   # params["hip_center"] / center=: estimators beside the default |div| argmax
 
 # 4:2:0 layouts of ffl_upload_frames_yuv (FFL_YUV_I420, FFL_YUV_NV12): cv2's single-array (3h/2, w) uint8 frames
 YUV_LAYOUTS = {"i420": 0, "nv12": 1}
@@ -606,6 +615,11 @@ def load():
     L.ffl_pass1_weighted.argtypes = [vp, C.c_int, ip, vp, C.c_int, C.c_uint64]
     L.ffl_radial_window_axes_weighted.argtypes = [vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, C.c_uint64]
     L.ffl_weights_extra_bytes.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+    L.ffl_cell_grid_check.argtypes = [C.c_int] * 3 + [ip, ip]
+    L.ffl_cell_stats.argtypes = [vp, C.c_int, ip, C.c_int, vp, vp, C.c_uint64]
+    L.ffl_radial_window_axes_centres.argtypes = [vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, C.c_ssize_t,
+                                                 vp, C.c_uint64]
+    L.ffl_cells_extra_bytes.argtypes = [C.c_int] * 3 + [C.POINTER(C.c_size_t)]
     for name in EXPORTS:   # every _src sibling: the plain call's arguments plus const ffl_source_info *
         if name.endswith("_src"):
             getattr(L, name).argtypes = getattr(L, name[:-4]).argtypes + [vp]
@@ -668,6 +682,42 @@ def weights_extra_bytes(width, height):
     if L.ffl_weights_extra_bytes(int(width), int(height), C.byref(b)) != FFL_OK:
         raise FFLError(f"ffl_weights_extra_bytes failed: {L.ffl_last_error(None).decode()}")
     return b.value
+
+
+def cell_grid(width, height, cells):
+    """(cell_w, cell_h) of a cells x cells grid on a width x height field (ffl_cell_grid_check; rule G1 of DESIGN.md section
+    17); FFLError with the rule where the grid is refused.  Needs no device."""
+    gw, gh = C.c_int(), C.c_int()
+    L = load()
+    rc = L.ffl_cell_grid_check(int(width), int(height), int(cells), C.byref(gw), C.byref(gh))
+    if rc != FFL_OK:
+        err = FFLError(f"ffl error {rc}: {L.ffl_last_error(None).decode()}")
+        err.code = rc
+        raise err
+    return gw.value, gh.value
+
+
+def cells_extra_bytes(width, height, cells):
+    """Device bytes the first cell_stats call of a Context allocates (estimate_bytes does not count them)."""
+    b = C.c_size_t()
+    L = load()
+    if L.ffl_cells_extra_bytes(int(width), int(height), int(cells), C.byref(b)) != FFL_OK:
+        raise FFLError(f"ffl_cells_extra_bytes failed: {L.ffl_last_error(None).decode()}")
+    return b.value
+
+
+def _centre_entries(centres, n_seq):
+    """(pointer, byte stride) of n_seq centres in device memory: a float64 (n_seq, 2) array, rows any multiple of 8 bytes
+    apart, or a contiguous buffer of n_seq GRID_CENTRE_DTYPE records"""
+    ptr, shp, st, ts = _array_view(centres)
+    if ts in ("<f8", "torch.float64") and len(shp) == 2:
+        if shp != (n_seq, 2) or st[1] != 8:
+            raise ValueError(f"centres: float64 shape {shp} with byte strides {st}, ({n_seq}, 2) with adjacent (cx, cy) is needed")
+        return ptr, (st[0] if n_seq > 1 else 16)
+    ptr, extent = _device_span(centres)
+    if extent < n_seq * GRID_CENTRE_DTYPE.itemsize:
+        raise ValueError(f"centres: {extent} bytes, {n_seq} centre records need {n_seq * GRID_CENTRE_DTYPE.itemsize}")
+    return ptr, GRID_CENTRE_DTYPE.itemsize
 
 
 def _iarr(v):
@@ -1062,6 +1112,35 @@ class Context:
         desc = self._weights("radial_window_axes_weighted", weights, n)
         return self._radial_window(self.L.ffl_radial_window_axes_weighted, "radial_window_axes_weighted", PASS2_AXES_DTYPE,
                                    seq_slots, first, n, out, radius, cut_threshold, pov_mode, stream, weights=(C.byref(desc),))
+
+    def cell_stats(self, flow_slots, cells=32, cells_out=None, centres_out=None, stream=None):
+        """The cells x cells grid of regional mean flow, mean magnitude and magnitude variance of every slot and / or its
+        centre of mass, the reference's center_of_mass_variance (ffl_cell_stats).  cells_out: device
+        memory for n * cells * cells CELL_DTYPE records (item-major, then row-major); centres_out: for n GRID_CENTRE_DTYPE
+        records; one of them at least.  The flow is only read.  Queued behind the work on `stream` (None: torch's current
+        stream), which waits for it; the host does not wait."""
+        ps, slots = _iarr(flow_slots)
+        n, ptrs = len(slots), []
+        for name, out, need in (("cells_out", cells_out, n * int(cells) * int(cells) * CELL_DTYPE.itemsize),
+                                ("centres_out", centres_out, n * GRID_CENTRE_DTYPE.itemsize)):
+            if out is None:
+                ptrs.append(None)
+                continue
+            ptr, extent = _device_span(out)
+            if extent < need:
+                raise ValueError(f"cell_stats: {name} holds {extent} bytes, the call's records need {need}")
+            ptrs.append(ptr)
+        self._chk(self.L.ffl_cell_stats(self._h, n, ps, int(cells), ptrs[0], ptrs[1], stream_handle(stream, self.device)))
+
+    def radial_window_axes_centres(self, seq_slots, first, n, centres, out, radius=6, cut_threshold=7.0, pov_mode=False,
+                                   stream=None):
+        """radial_window_axes about caller centres (ffl_radial_window_axes_centres): `centres` holds one centre per seq slot in
+        device memory, a float64 (n_seq, 2) tensor of (cx, cy) or a buffer of GRID_CENTRE_DTYPE records as cell_stats wrote
+        them; the window mean over them is rule G6 of DESIGN.md section 17.  Everything else of a record is
+        radial_window_axes'."""
+        ptr, stride = _centre_entries(centres, len(seq_slots))
+        return self._radial_window(self.L.ffl_radial_window_axes_centres, "radial_window_axes_centres", PASS2_AXES_DTYPE,
+                                   seq_slots, first, n, out, radius, cut_threshold, pov_mode, stream, weights=(ptr, stride))
 
     def download_frame(self, fslot):
         out = np.empty((self.height, self.width), np.uint8)

@@ -351,6 +351,9 @@ struct ffl_ctx {
     // pass 1's SW per workgroup, pass 2's FFL_NAXES + 1 sums per workgroup -- allocated by their first call (weights_scratch)
     // and held to ffl_destroy, under the single-copy rule above.
     DevBuf<double> d_wpsum;
+    // ffl_cell_stats: t_i and x_i of rule G5 per cell row, FFL_MAX_CELLS rows for FFL_MAXB items,
+    // allocated by its first call (cells_scratch) and held to ffl_destroy, under the single-copy rule above.
+    DevBuf<double> d_cellrow;
     int p1_blocks = 0;
     // profiling
     unsigned prof_mask = 0;   // bit k set: bracket every launch of kernel class k with HIP events
@@ -2644,11 +2647,15 @@ int ffl_pass1_weighted(ffl_ctx *c, int n, const int *slots, const ffl_dev_weight
     return post_end(c, cst, n, slots);  // the caller may overwrite or free the maps straight after the call
 }
 
+static const char *kHostCentres = "centres live in device memory (ffl_cell_stats' records, or a float64 (n_seq, 2) tensor)";
+
 // ffl_radial_window (axes = false: ffl_pass2_record) and ffl_radial_window_axes (ffl_axes_record): one protocol.  wts (with
-// axes): ffl_radial_window_axes_weighted, the maps of the n computed items as a second region of caller memory.
+// axes): ffl_radial_window_axes_weighted, the maps of the n computed items as a second region of caller memory.  centres
+// (with axes): ffl_radial_window_axes_centres, the n_seq caller centres as that second region.
 static int radial_window_call(ffl_ctx *c, const char *fn, bool axes, int n_seq, const int *seq, int first, int n, int radius,
                               float cut_threshold, int pov_mode, void *out, uint64_t stream,
-                              const ffl_dev_weights *wts = nullptr, bool weighted = false) {
+                              const ffl_dev_weights *wts = nullptr, bool weighted = false, const void *cen = nullptr,
+                              ptrdiff_t cstride = 0, bool centres = false) {
     if (!c) return FFL_ERR_INVALID;
     const size_t rec_bytes = axes ? sizeof(ffl_axes_record) : sizeof(ffl_pass2_record);
     std::unique_lock<std::mutex> pl(c->post_mu);  // stream `post`, post_ring and d_rpsum, as ffl_radial / ffl_export_flows
@@ -2669,10 +2676,18 @@ static int radial_window_call(ffl_ctx *c, const char *fn, bool axes, int n_seq, 
     size_t wbytes = 0;
     if (weighted)
         if (int rc = dev_weights_check(c, fn, n, c->w, c->h, wts, &wbytes)) return rc;
+    if (centres) {   // rule G6: n_seq entries, two doubles at the head of each
+        if (!cen) return set_err(c, FFL_ERR_INVALID, "%s: NULL centres_dev", fn);
+        if ((uintptr_t)cen % 8) return set_err(c, FFL_ERR_INVALID, "%s: centres_dev must be 8-byte aligned", fn);
+        if (cstride < 16 || cstride % 8 || cstride > ((ptrdiff_t)1 << 40))
+            return set_err(c, FFL_ERR_INVALID, "%s: centre stride %td: a multiple of 8 bytes, at least 16 (two doubles)", fn, cstride);
+    }
     hipStream_t cst;
+    const PostRegion second = centres ? PostRegion{"centres_dev", cen, (size_t)(n_seq - 1) * (size_t)cstride + 16, kHostCentres}
+                                      : PostRegion{"the weight maps", weighted ? wts->base : nullptr, wbytes, kHostWeights};
     const PostRegion reg[2] = {{"out_dev", out, rec_bytes * (size_t)n, "results in host memory come from ffl_pass1_results and ffl_radial"},
-                               {"the weight maps", weighted ? wts->base : nullptr, wbytes, kHostWeights}};
-    if (int rc = post_begin(c, fn, stream, &cst, reg, weighted ? 2 : 1, n_seq, seq)) return rc;
+                               second};
+    if (int rc = post_begin(c, fn, stream, &cst, reg, weighted || centres ? 2 : 1, n_seq, seq)) return rc;
     WindowSeq t;
     for (int i = 0; i < n_seq; i++) t.slot[i] = seq[i];
     if (weighted) {
@@ -2680,8 +2695,12 @@ static int radial_window_call(ffl_ctx *c, const char *fn, bool axes, int n_seq, 
     } else if (axes)
         if (int rc = axes_scratch(c, fn)) return rc;
     // not timed under FFL_K_RADIAL: that class counts the radial pairs of ffl_radial / ffl_radial_axes, one per call
-    ffl_launch_window_plan(t, n_seq, first, n, radius, cut_threshold, c->d_res, c->d_flow, c->w, c->h, c->d_wtab, out,
-                           (int)rec_bytes, c->s_post);
+    if (centres)
+        ffl_launch_window_plan_centres(t, n_seq, first, n, radius, cut_threshold, c->d_res, c->d_flow, c->w, c->h, cen,
+                                       (long long)cstride, c->d_wtab, (AxesRecord *)out, c->s_post);
+    else
+        ffl_launch_window_plan(t, n_seq, first, n, radius, cut_threshold, c->d_res, c->d_flow, c->w, c->h, c->d_wtab, out,
+                               (int)rec_bytes, c->s_post);
     if (weighted) {
         const WeightArgs wa{(const char *)wts->base, (long long)wts->item_stride, (long long)wts->row_pitch};
         ffl_launch_radial_axes_weighted(c->d_wtab, n, c->w, c->h, pov_mode ? 1 : 0, c->d_wytab, wa, c->d_wpsum, (AxesRecord *)out,
@@ -2706,6 +2725,97 @@ int ffl_radial_window_axes_weighted(ffl_ctx *c, int n_seq, const int *seq, int f
                                     int pov_mode, const ffl_dev_weights *w, ffl_axes_record *out, uint64_t stream) {
     return radial_window_call(c, "ffl_radial_window_axes_weighted", true, n_seq, seq, first, n, radius, cut_threshold, pov_mode, out,
                               stream, w, true);
+}
+
+int ffl_radial_window_axes_centres(ffl_ctx *c, int n_seq, const int *seq, int first, int n, int radius, float cut_threshold,
+                                   int pov_mode, const void *centres_dev, ptrdiff_t centre_stride_bytes, ffl_axes_record *out,
+                                   uint64_t stream) {
+    return radial_window_call(c, "ffl_radial_window_axes_centres", true, n_seq, seq, first, n, radius, cut_threshold, pov_mode, out,
+                              stream, nullptr, false, centres_dev, centre_stride_bytes, true);
+}
+
+// ---- per-cell statistics and the variance centre -----------------------------------
+static_assert(sizeof(ffl_cell_record) == 32 && sizeof(CellRecord) == 32 && offsetof(ffl_cell_record, mean_u) == offsetof(CellRecord, mean_u) &&
+              offsetof(ffl_cell_record, mean_v) == offsetof(CellRecord, mean_v) && offsetof(ffl_cell_record, mean_mag) == offsetof(CellRecord, mean_mag) &&
+              offsetof(ffl_cell_record, var_mag) == 24 && offsetof(CellRecord, var_mag) == 24 && alignof(ffl_cell_record) == 8,
+              "CellRecord mirrors ffl_cell_record");
+static_assert(sizeof(ffl_grid_centre) == 32 && sizeof(GridCentre) == 32 && offsetof(ffl_grid_centre, cx) == 0 && offsetof(GridCentre, cx) == 0 &&
+              offsetof(ffl_grid_centre, cy) == 8 && offsetof(GridCentre, cy) == 8 && offsetof(ffl_grid_centre, total_var) == offsetof(GridCentre, total_var) &&
+              offsetof(ffl_grid_centre, cells) == 24 && offsetof(GridCentre, cells) == 24 && offsetof(ffl_grid_centre, empty) == 28 &&
+              offsetof(GridCentre, empty) == 28 && alignof(ffl_grid_centre) == 8,
+              "GridCentre mirrors ffl_grid_centre");
+static_assert(FFL_MAX_CELLS == FFL_CELLS_MAX, "ffl.h and ffl_kernels.h agree");
+
+// rule G1 (FF:728-735): 1 <= cells <= FFL_MAX_CELLS and cells <= min(width, height)
+static int cell_grid_check(ffl_ctx *c, const char *fn, int width, int height, int cells, int *cell_w, int *cell_h) {
+    if (!frame_size_ok(width, height)) return set_err(c, FFL_ERR_INVALID, "%s: " FFL_FRAME_SIZE_RULE, fn, width, height);
+    if (cells < 1 || cells > FFL_MAX_CELLS)
+        return set_err(c, FFL_ERR_INVALID, "%s: rule G1: cells = %d outside 1..%d (FFL_MAX_CELLS)", fn, cells, FFL_MAX_CELLS);
+    if (cells > width || cells > height)
+        return set_err(c, FFL_ERR_INVALID, "%s: rule G1: cells = %d exceeds min(width, height) of %dx%d (a cell has at least one pixel)",
+                       fn, cells, width, height);
+    if (cell_w) *cell_w = width / cells;
+    if (cell_h) *cell_h = height / cells;
+    return FFL_OK;
+}
+
+int ffl_cell_grid_check(int width, int height, int cells, int *cell_w, int *cell_h) {
+    return cell_grid_check(nullptr, "ffl_cell_grid_check", width, height, cells, cell_w, cell_h);
+}
+
+// What ffl_cell_stats adds to a context: the row sums of rule G5, whatever the size and the grid.
+static size_t cells_row_doubles() { return (size_t)2 * FFL_MAX_CELLS * FFL_MAXB; }
+
+int ffl_cells_extra_bytes(int width, int height, int cells, size_t *bytes) {
+    if (!bytes) return set_err(nullptr, FFL_ERR_INVALID, "ffl_cells_extra_bytes: bytes is NULL");
+    if (int rc = cell_grid_check(nullptr, "ffl_cells_extra_bytes", width, height, cells, nullptr, nullptr)) return rc;
+    *bytes = sizeof(double) * cells_row_doubles();
+    return FFL_OK;
+}
+
+// The first ffl_cell_stats call allocates its scratch (the caller holds post_mu and the context lock).
+static int cells_scratch(ffl_ctx *c, const char *fn) {
+    if (c->d_cellrow) return FFL_OK;
+    const hipError_t e = c->d_cellrow.alloc(cells_row_doubles());
+    if (e != hipSuccess) {
+        c->d_cellrow.release();  // nothing was allocated
+        (void)hipGetLastError();
+        return set_err(c, FFL_ERR_HIP, "%s: allocating the cell-row scratch (%zu bytes) failed: %s", fn,
+                       sizeof(double) * cells_row_doubles(), hipGetErrorString(e));
+    }
+    return FFL_OK;
+}
+
+// The cells x cells statistics grid of n slots that hold a flow and / or its variance centre (FF:721-746), by one
+// k_cell_stats launch plus k_grid_centre on stream `post`: ffl_pass1_weighted's protocol, with the flow only read and no
+// pass-1 record touched.
+int ffl_cell_stats(ffl_ctx *c, int n, const int *slots, int cells, ffl_cell_record *cells_dev, ffl_grid_centre *centres_dev,
+                   uint64_t stream) {
+    static const char *fn = "ffl_cell_stats";
+    static const char *hint = "the grid's records are written to device memory (torch / hipMalloc)";
+    if (!c) return FFL_ERR_INVALID;
+    std::unique_lock<std::mutex> pl(c->post_mu);  // stream `post` and d_cellrow
+    CtxLock lk(c->mu);
+    if (n < 1 || n > c->max_batch)
+        return set_err(c, FFL_ERR_INVALID, "%s: n = %d slots outside 1..%d (the context's max_batch)", fn, n, c->max_batch);
+    if (!slots) return set_err(c, FFL_ERR_INVALID, "%s: NULL flow_slots", fn);
+    if (int rc = check_flow_slots(c, fn, n, slots, "flow", "repeated in one call")) return rc;
+    if (int rc = cell_grid_check(c, fn, c->w, c->h, cells, nullptr, nullptr)) return rc;
+    if (!cells_dev && !centres_dev) return set_err(c, FFL_ERR_INVALID, "%s: cells_dev and centres_dev are both NULL (one output at least)", fn);
+    if ((uintptr_t)cells_dev % 8 || (uintptr_t)centres_dev % 8)
+        return set_err(c, FFL_ERR_INVALID, "%s: cells_dev and centres_dev must be 8-byte aligned", fn);
+    PostRegion reg[2];
+    int nreg = 0;
+    if (cells_dev) reg[nreg++] = PostRegion{"cells_dev", cells_dev, sizeof(ffl_cell_record) * (size_t)n * cells * cells, hint};
+    if (centres_dev) reg[nreg++] = PostRegion{"centres_dev", centres_dev, sizeof(ffl_grid_centre) * (size_t)n, hint};
+    hipStream_t cst;
+    if (int rc = post_begin(c, fn, stream, &cst, reg, nreg, n, slots)) return rc;
+    if (int rc = cells_scratch(c, fn)) return rc;
+    ExportTab t;
+    for (int i = 0; i < n; i++) t.slot[i] = slots[i];
+    ffl_launch_cell_stats(c->d_flow, t, n, c->w, c->h, cells, (CellRecord *)cells_dev, (GridCentre *)centres_dev, c->d_cellrow,
+                          c->s_post);
+    return post_end(c, cst, n, slots);  // the caller may read, overwrite or free the outputs on `stream` straight after the call
 }
 
 // ---- flow import -------------------------------------------------------------------------------

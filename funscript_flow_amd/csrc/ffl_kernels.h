@@ -291,6 +291,26 @@ void ffl_launch_window_plan(const WindowSeq &seq, int n_seq, int first, int n, i
                             const Pass1Result *res, const float *flow, int w, int h, WindowItem *tab, void *out,
                             int rec_stride, hipStream_t st);
 
+// ffl_radial_window_axes_centres (rule G6): the plan with the window's centres read from n_seq entries
+// of device memory, two doubles (cx, cy) at the head of each, cstride bytes apart; the records are AxesRecord
+void ffl_launch_window_plan_centres(const WindowSeq &seq, int n_seq, int first, int n, int radius, float cut_threshold,
+                                    const Pass1Result *res, const float *flow, int w, int h, const void *cen, long long cstride,
+                                    WindowItem *tab, AxesRecord *out, hipStream_t st);
+
+// per-cell statistics and the variance centre (k_cell_stats, k_grid_centre)
+#define FFL_CELLS_MAX 64             // = FFL_MAX_CELLS of include/ffl.h
+struct CellRecord {  // = ffl_cell_record of include/ffl.h (ffl_api.hip asserts the layout)
+    double mean_u, mean_v, mean_mag, var_mag;
+};
+struct GridCentre {  // = ffl_grid_centre
+    double cx, cy, total_var;
+    int cells, empty;
+};
+// flow slots tab.slot[0..n) of `flow` under a G x G grid -> cells[(b * G + i) * G + j] (may be NULL) and centres[b] (may be
+// NULL); rowsum: 2 * G doubles per item (t_i, x_i of rule G5)
+void ffl_launch_cell_stats(const float *flow, const ExportTab &tab, int n, int w, int h, int G, CellRecord *cells,
+                           GridCentre *centres, double *rowsum, hipStream_t st);
+
 // ---- index rules shared by the kernel files ----------------------------------------------------------------------
 __device__ __forceinline__ int ffl_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 

@@ -5,6 +5,7 @@
 // Reductions are wave-shuffle -> LDS -> one partial per workgroup -> a small second kernel, so sums
 // are reproducible run to run (no float atomics).
 #include "ffl_kernels.h"
+#include <type_traits>
 
 #define P1_THREADS 256
 #define P1_RG 16          // rows a wave walks down (its row group)
@@ -537,33 +538,60 @@ void ffl_launch_radial_axes_weighted(const WindowItem *tab, int n, int w, int h,
 // reads mag_sum and div_val of its own record once more.  Nothing of a record is read by the radial grid.
 #define W2_THREADS 64
 
-template <int STRIDE>
-__global__ __launch_bounds__(W2_THREADS) void k_window_plan(const WindowSeq seq, int n_seq, int first, int n, int radius,
-                                                            float cut_threshold, double npx,
-                                                            const Pass1Result *__restrict__ res, const float *__restrict__ flow,
-                                                            size_t N, WindowItem *__restrict__ tab,
-                                                            char *__restrict__ out) {
-    __shared__ int sx[W2_THREADS + 2 * FFL_WINDOW_MAX_RADIUS], sy[W2_THREADS + 2 * FFL_WINDOW_MAX_RADIUS];
+// CEN (k_window_plan_centres, DESIGN.md section 17 rule G6): the window's centres are the caller's, two doubles at the head
+// of each of n_seq entries cstride bytes apart at cen, staged the same way and added in the order numpy adds the rows of
+// FF:1205-1213's list -- item j, then j - i before j + i for i = 1..radius.  x and y of the record are still the slot's.
+template <int STRIDE, bool CEN>
+__device__ __forceinline__ void ffl_window_plan_body(const WindowSeq &seq, int n_seq, int first, int n, int radius,
+                                                     float cut_threshold, double npx, const Pass1Result *__restrict__ res,
+                                                     const float *__restrict__ flow, size_t N, const char *__restrict__ cen,
+                                                     long long cstride, WindowItem *__restrict__ tab, char *__restrict__ out) {
+    using T = typename std::conditional<CEN, double, int>::type;
+    __shared__ T sx[W2_THREADS + 2 * FFL_WINDOW_MAX_RADIUS], sy[W2_THREADS + 2 * FFL_WINDOW_MAX_RADIUS];
     const int i0 = blockIdx.x * W2_THREADS;                      // the workgroup's first item
     const int j0 = first + i0, j1 = first + min(i0 + W2_THREADS, n) - 1;   // its items in seq, inclusive
     const int lo = max(0, j0 - radius), hi = min(n_seq - 1, j1 + radius);  // the records their windows span
     for (int k = lo + (int)threadIdx.x; k <= hi; k += W2_THREADS) {
-        const Pass1Result *r = res + seq.slot[k];
-        sx[k - lo] = r->x;
-        sy[k - lo] = r->y;
+        if constexpr (CEN) {
+            const double *c = reinterpret_cast<const double *>(cen + (long long)k * cstride);
+            sx[k - lo] = c[0];
+            sy[k - lo] = c[1];
+        } else {
+            const Pass1Result *r = res + seq.slot[k];
+            sx[k - lo] = r->x;
+            sy[k - lo] = r->y;
+        }
     }
     __syncthreads();
     const int i = i0 + (int)threadIdx.x;
     if (i >= n) return;
     const int j = first + i, slot = seq.slot[j];
     const int a = max(0, j - radius), b = min(n_seq - 1, j + radius);
-    long long tx = 0, ty = 0;                                    // exact integer sums (np.mean of the int64 pairs)
-    for (int k = a; k <= b; k++) {
-        tx += sx[k - lo];
-        ty += sy[k - lo];
-    }
     const double cnt = (double)(b - a + 1);
-    const double cx = (double)tx / cnt, cy = (double)ty / cnt;   // one IEEE division each: pipeline.smooth_centers
+    double cx, cy;
+    if constexpr (CEN) {
+        double ax = sx[j - lo], ay = sy[j - lo];
+        for (int d = 1; d <= radius; d++) {
+            if (j - d >= 0) {
+                ax += sx[j - d - lo];
+                ay += sy[j - d - lo];
+            }
+            if (j + d < n_seq) {
+                ax += sx[j + d - lo];
+                ay += sy[j + d - lo];
+            }
+        }
+        cx = ax / cnt;
+        cy = ay / cnt;
+    } else {
+        long long tx = 0, ty = 0;                                // exact integer sums (np.mean of the int64 pairs)
+        for (int k = a; k <= b; k++) {
+            tx += sx[k - lo];
+            ty += sy[k - lo];
+        }
+        cx = (double)tx / cnt;                                   // one IEEE division each: pipeline.smooth_centers
+        cy = (double)ty / cnt;
+    }
     const Pass1Result *r = res + slot;
     const float mm = (float)ffl_record_mean(*r, npx);            // ffl_pass1_results' expressions
     const int cut = mm > cut_threshold ? 1 : 0;                  // NaN > threshold is false
@@ -579,10 +607,34 @@ __global__ __launch_bounds__(W2_THREADS) void k_window_plan(const WindowSeq seq,
     o->cy = cy;
     o->mean_mag = mm;
     o->div_val = r->div_val;
-    o->x = sx[j - lo];
-    o->y = sy[j - lo];
+    if constexpr (CEN) {
+        o->x = r->x;
+        o->y = r->y;
+    } else {
+        o->x = sx[j - lo];
+        o->y = sy[j - lo];
+    }
     o->cut = cut;
     o->pad = 0;
+}
+
+template <int STRIDE>
+__global__ __launch_bounds__(W2_THREADS) void k_window_plan(const WindowSeq seq, int n_seq, int first, int n, int radius,
+                                                            float cut_threshold, double npx,
+                                                            const Pass1Result *__restrict__ res, const float *__restrict__ flow,
+                                                            size_t N, WindowItem *__restrict__ tab,
+                                                            char *__restrict__ out) {
+    ffl_window_plan_body<STRIDE, false>(seq, n_seq, first, n, radius, cut_threshold, npx, res, flow, N, nullptr, 0, tab, out);
+}
+
+__global__ __launch_bounds__(W2_THREADS) void k_window_plan_centres(const WindowSeq seq, int n_seq, int first, int n, int radius,
+                                                                    float cut_threshold, double npx,
+                                                                    const Pass1Result *__restrict__ res,
+                                                                    const float *__restrict__ flow, size_t N,
+                                                                    const char *__restrict__ cen, long long cstride,
+                                                                    WindowItem *__restrict__ tab, char *__restrict__ out) {
+    ffl_window_plan_body<(int)sizeof(AxesRecord), true>(seq, n_seq, first, n, radius, cut_threshold, npx, res, flow, N, cen, cstride,
+                                                        tab, out);
 }
 
 void ffl_launch_window_plan(const WindowSeq &seq, int n_seq, int first, int n, int radius, float cut_threshold,
@@ -596,6 +648,163 @@ void ffl_launch_window_plan(const WindowSeq &seq, int n_seq, int first, int n, i
     else
         hipLaunchKernelGGL(k_window_plan<(int)sizeof(Pass2Record)>, grid, dim3(W2_THREADS), 0, st, seq, n_seq, first, n, radius,
                            cut_threshold, npx, res, flow, (size_t)w * h, tab, (char *)out);
+}
+
+void ffl_launch_window_plan_centres(const WindowSeq &seq, int n_seq, int first, int n, int radius, float cut_threshold,
+                                    const Pass1Result *res, const float *flow, int w, int h, const void *cen, long long cstride,
+                                    WindowItem *tab, AxesRecord *out, hipStream_t st) {
+    hipLaunchKernelGGL(k_window_plan_centres, dim3((n + W2_THREADS - 1) / W2_THREADS), dim3(W2_THREADS), 0, st, seq, n_seq, first,
+                       n, radius, cut_threshold, (double)w * (double)h, res, flow, (size_t)w * h, (const char *)cen, cstride, tab,
+                       (char *)out);
+}
+
+// ---- per-cell statistics and the variance centre (ffl_cell_stats) ------------------
+// center_of_mass_variance (FF:721-746) and its intermediate grid.  A reduction segmented by cell: workgroup (i, b) owns cell
+// row i of item b and walks its G * gw columns in the 256-column blocks of rule G3, one column per lane.  A lane sums its
+// column's gh rows top to bottom (CS_G rows of loads in flight), the column sums go through LDS, and one lane per cell
+// segment of the block adds its columns left to right and then adds that block partial to the cell's sums, which stay in
+// LDS from block to block: ascending block order without scratch partials, atomics or a ticket.  After the last block one
+// lane per cell forms its record (rule G4) and lane 0 the row's t_i and x_i of rule G5, sequentially over j.
+// k_grid_centre (the second launch) adds the G rows of an item in order and writes its centre record.
+#define CS_THREADS 256   // = the column block of rule G3
+#ifndef CS_G
+#define CS_G 4           // rows whose loads are in flight together per lane (1080p n = 32, G = 32, gh = 33: 140 us with 4, 144 with 8,
+                         // 153 with 16 -- a group re-reads the cell's last row for the rows it has past the cell's end: 3, 7, 15 of them)
+#endif
+
+__global__ __launch_bounds__(CS_THREADS) void k_cell_stats(const float *__restrict__ flow, const ExportTab tab, int w, int h, int G,
+                                                           int gw, int gh, CellRecord *__restrict__ cells,
+                                                           double *__restrict__ rowsum) {
+    __shared__ double scol[CS_THREADS][4];      // the block's column sums: S_u, S_v, S_d, S_dd of a column side by side
+    __shared__ double scell[4][FFL_CELLS_MAX];  // the row's cell sums so far
+    __shared__ double svar[FFL_CELLS_MAX];
+    const int i = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
+    const float *f = flow + (size_t)tab.slot[b] * 2 * ((size_t)w * h);
+    const int y0 = i * gh, wc = G * gw;         // rows y0 .. y0 + gh - 1; columns >= wc belong to no cell (rule G1)
+    if (t < G) {
+#pragma unroll
+        for (int c = 0; c < 4; c++) scell[c][t] = 0.0;
+    }
+    const int nblk = (wc + CS_THREADS - 1) / CS_THREADS;
+#pragma unroll 1
+    for (int blk = 0; blk < nblk; blk++) {
+        const int x = blk * CS_THREADS + t;
+        const int xc = min(x, wc - 1);          // lanes past the last cell column repeat it; their sums are never read
+        const int j = xc / gw;
+        // K: the magnitude of the cell's top-left pixel (rule G2).  Byte offsets < 2^32: ffl_create
+        const float2 k2 = ffl_gload2(f, 8u * ((unsigned)y0 * (unsigned)w + (unsigned)(j * gw)));
+        const double K = (double)sqrtf(k2.x * k2.x + k2.y * k2.y);
+        double su = 0.0, sv = 0.0, sd = 0.0, sdd = 0.0;
+#pragma unroll 1
+        for (int g = 0; g < gh; g += CS_G) {
+            float2 p[CS_G];
+#pragma unroll
+            for (int r = 0; r < CS_G; r++) {    // rows past the cell repeat its last row (selected out below)
+                const int y = y0 + min(g + r, gh - 1);
+                p[r] = ffl_gload2(f, 8u * ((unsigned)y * (unsigned)w + (unsigned)xc));
+            }
+#pragma unroll
+            for (int r = 0; r < CS_G; r++) {
+                const bool in = g + r < gh;     // workgroup-uniform
+                const double d = (double)sqrtf(p[r].x * p[r].x + p[r].y * p[r].y) - K;
+                su += in ? (double)p[r].x : 0.0;
+                sv += in ? (double)p[r].y : 0.0;
+                sd += in ? d : 0.0;
+                sdd += in ? d * d : 0.0;
+            }
+        }
+        scol[t][0] = su;
+        scol[t][1] = sv;
+        scol[t][2] = sd;
+        scol[t][3] = sdd;
+        __syncthreads();
+        // the cells that have columns in this block: jf .. jl (at most FFL_CELLS_MAX = CS_THREADS / 4 of them), one lane per
+        // cell and sum.  The additions are sequential by rule G3; the LDS reads are not, so they go eight at a time.
+        const int xb = blk * CS_THREADS, xl = min(xb + CS_THREADS, wc);
+        const int jf = xb / gw, jl = (xl - 1) / gw;
+        const int seg = t >> 2, c = t & 3;
+        if (seg <= jl - jf) {
+            const int jc = jf + seg;
+            const int xs = max(jc * gw, xb) - xb, xe = min((jc + 1) * gw, xl) - xb;
+            double part = 0.0;
+            int k = xs;
+            for (; k + 8 <= xe; k += 8) {
+                double v[8];
+#pragma unroll
+                for (int r = 0; r < 8; r++) v[r] = scol[k + r][c];
+#pragma unroll
+                for (int r = 0; r < 8; r++) part += v[r];
+            }
+            for (; k < xe; k++) part += scol[k][c];
+            scell[c][jc] += part;
+        }
+        __syncthreads();
+    }
+    if (t < G) {
+        const float2 k2 = ffl_gload2(f, 8u * ((unsigned)y0 * (unsigned)w + (unsigned)(t * gw)));
+        const double K = (double)sqrtf(k2.x * k2.x + k2.y * k2.y);
+        const double n = (double)gh * (double)gw;
+        const double sd = scell[2][t];
+        double var = (scell[3][t] - sd * sd / n) / n;
+        var = var < 0.0 ? 0.0 : var;            // a NaN stays a NaN (rule G4)
+        svar[t] = var;
+        if (cells) {
+            CellRecord r;
+            r.mean_u = scell[0][t] / n;
+            r.mean_v = scell[1][t] / n;
+            r.mean_mag = K + sd / n;
+            r.var_mag = var;
+            cells[((size_t)b * G + i) * G + t] = r;
+        }
+    }
+    __syncthreads();
+    if (t < 2) {                                // lane 0: t_i, lane 1: x_i, each over j in order (rule G5)
+        double acc = 0.0;
+        int j = 0;
+        for (; j + 8 <= G; j += 8) {
+            double v[8];
+#pragma unroll
+            for (int r = 0; r < 8; r++) v[r] = svar[j + r];
+#pragma unroll
+            for (int r = 0; r < 8; r++) acc += t ? (double)(j + r) * v[r] : v[r];
+        }
+        for (; j < G; j++) acc += t ? (double)j * svar[j] : svar[j];
+        rowsum[((size_t)b * G + i) * 2 + t] = acc;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_grid_centre(const double *__restrict__ rowsum, int n, int w, int h, int G, int gw, int gh,
+                                                    GridCentre *__restrict__ out) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= n) return;
+    double T = 0.0, X = 0.0, Y = 0.0;
+    for (int i = 0; i < G; i++) {
+        const double ti = rowsum[((size_t)b * G + i) * 2], xi = rowsum[((size_t)b * G + i) * 2 + 1];
+        T += ti;
+        X += xi;
+        Y += (double)i * ti;
+    }
+    GridCentre r;
+    if (T == 0.0) {                             // FF:741-742; a NaN T takes the other branch and gives NaN centres
+        r.cx = (double)(w / 2);
+        r.cy = (double)(h / 2);
+        r.empty = 1;
+    } else {                                    // FF:744-745, left to right
+        r.cx = X * (double)gw / T + (double)gw / 2.0;
+        r.cy = Y * (double)gh / T + (double)gh / 2.0;
+        r.empty = 0;
+    }
+    r.total_var = T;
+    r.cells = G;
+    out[b] = r;
+}
+
+void ffl_launch_cell_stats(const float *flow, const ExportTab &tab, int n, int w, int h, int G, CellRecord *cells,
+                           GridCentre *centres, double *rowsum, hipStream_t st) {
+    const int gw = w / G, gh = h / G;
+    hipLaunchKernelGGL(k_cell_stats, dim3(G, n), dim3(CS_THREADS), 0, st, flow, tab, w, h, G, gw, gh, cells, rowsum);
+    if (centres)
+        hipLaunchKernelGGL(k_grid_centre, dim3((n + 63) / 64), dim3(64), 0, st, rowsum, n, w, h, G, gw, gh, centres);
 }
 
 // ---- flow export -----------------------------------------------------------------------------

@@ -98,6 +98,27 @@ def post_records(buf, n=None, device=None, axes=False):
     return rec["dot"].astype(np.float64), records
 
 
+def grid_buffer(ctx, n, cells=32):
+    """a device buffer for the n * cells * cells 32-byte cell records of a chunk (torch uint8 on the context's device), as
+    grid_out= takes it: pair j's grid at byte 32 * cells * cells * j"""
+    import torch
+    return torch.empty(n * cells * cells * _capi.CELL_DTYPE.itemsize, dtype=torch.uint8, device=torch.device("cuda", ctx.device))
+
+
+def grid_records(buf, cells=32, n=None, device=None):
+    """The cell records of a chunk run with grid_out= as a numpy array (n, cells, cells) of _capi.CELL_DTYPE (fields mean_u,
+    mean_v, mean_mag, var_mag; [j, i, k] is cell row i, column k of pair j).  The copy runs on torch's current stream, behind
+    the calls that filled `buf` there, and waits for them (see post_records for `device`)."""
+    import torch
+    if not isinstance(buf, torch.Tensor):
+        buf = torch.as_tensor(buf, device=torch.device("cuda", torch.cuda.current_device() if device is None else device))
+    item = cells * cells * _capi.CELL_DTYPE.itemsize
+    raw = buf.contiguous().view(torch.uint8).reshape(-1)
+    n = raw.numel() // item if n is None else n
+    raw = raw[:n * item].cpu().numpy()
+    return np.frombuffer(raw.tobytes(), _capi.CELL_DTYPE, n * cells * cells).reshape(n, cells, cells)
+
+
 def _stream_event(ctx, stream=None):
     """an event recorded on `stream` (None: torch's current stream of the context's device): query() / synchronize()"""
     import torch
@@ -307,7 +328,7 @@ class PairEngine:
         return recs
 
     def process_chunk(self, frames, pov_mode=False, cut_threshold=7.0, algo=None, farneback=OWN, flows_out=None, window=OWN,
-                      post_out=None, axes=False, weights=None):
+                      post_out=None, axes=False, weights=None, center=None, cells=32, grid_out=None):
         """One whole chunk on one GPU: returns (dots float64[n], records) with n = len(frames)-1.  `algo`, `farneback`,
         `window`: see pass1_pairs (default: the engine's own flow algorithm, parameters and window).  `flows_out`: a float32 device array of
         (n, H, W, 2) or (n, 2, H, W) that receives every pair's flow field (Context.export_flows, on torch's current stream)
@@ -324,9 +345,17 @@ class PairEngine:
         `weights`: a per-pixel weight map, a uint8 / bool device tensor (H, W) for every pair or
         (n, H, W), one map per pair.  The chunk then runs the device schedule: post_out defaults to a new buffer, the
         records are the 80-byte form whatever `axes` says, and behind each batch Context.pass1_weighted is queued on its
-        slots, then its window calls as Context.radial_window_axes_weighted.  The flow (and flows_out) is unchanged."""
+        slots, then its window calls as Context.radial_window_axes_weighted.  The flow (and flows_out) is unchanged.
+        `center`: "variance" takes every pass-2 term about the reference's center_of_mass_variance (FF:721-746) over a
+        `cells` x `cells` grid instead of the |div| argmax.  The chunk then runs the device schedule as
+        with weights: post_out defaults to a new buffer, the records are the 80-byte form, and behind each batch
+        Context.cell_stats is queued on its slots, then its window calls as Context.radial_window_axes_centres.  `grid_out`:
+        device memory (grid_buffer) that receives every pair's cells x cells cell records.  Not combined with `weights`."""
         ctx, B = self.ctx, self.B
         n = len(frames) - 1
+        grid = _chunk_grid(ctx, center, cells, grid_out, weights, n)
+        if grid is not None:
+            axes, post_out = True, True if post_out is None else post_out
         maps = weights   # the tensor stays referenced while the calls that read it are queued
         if weights is not None and n >= 1:
             weights, axes, post_out = _chunk_weights(ctx, maps, n), True, True if post_out is None else post_out
@@ -345,7 +374,7 @@ class PairEngine:
                 raise ValueError(f"flows_out must be ({n}, {ctx.height}, {ctx.width}, 2) or ({n}, 2, {ctx.height}, "
                                  f"{ctx.width}), got {shp}")
         if post_out is not None:
-            post = _DevicePost(ctx, n, B, pov_mode, cut_threshold, post_out, axes, weights)
+            post = _DevicePost(ctx, n, B, pov_mode, cut_threshold, post_out, axes, weights, grid)
             release = getattr(frames, "release", None)
             marks = []   # (event, frames that have left the host once it completes), oldest first
 
@@ -382,7 +411,8 @@ class PairEngine:
         self.pass1(frames, 0, n, pov_mode, cut_threshold, on_batch, algo=algo, farneback=farneback, window=window)
         return post.finish()
 
-    def process_flows(self, flows, pov_mode=False, cut_threshold=7.0, post_out=None, axes=False, weights=None):
+    def process_flows(self, flows, pov_mode=False, cut_threshold=7.0, post_out=None, axes=False, weights=None, center=None,
+                      cells=32, grid_out=None):
         """One whole chunk from flow fields the caller computed: returns (dots float64[n], records), the contract of
         process_chunk.  `flows` holds the chunk's n pair fields in device memory: one array (n, H, W, 2) or (n, 2, H, W)
         (float32, float16 or bfloat16, any strides; see _capi.device_flows) or a sequence of such arrays (single (H, W, 2)
@@ -390,7 +420,8 @@ class PairEngine:
         torch's current stream) with `depth` batches in flight; the +-6 window and pass 2 are process_chunk's own.
         `post_out`: as in process_chunk (a buffer, or True for a new one) -- pass 2 is queued on the device behind each
         import, nothing waits, and the buffer is returned for post_records.  `axes`, `weights`: as in process_chunk (with
-        weights: the device schedule, 80-byte records, pass1_weighted behind each import)."""
+        weights: the device schedule, 80-byte records, pass1_weighted behind each import).  `center`, `cells`, `grid_out`:
+        as in process_chunk (center="variance": the device schedule, 80-byte records, cell_stats behind each import)."""
         ctx, B, fs = self.ctx, self.B, self.ctx.flow_slots
         segs = []   # (descriptor, dtype, first pair, count): one per source array
         n = 0
@@ -399,6 +430,9 @@ class PairEngine:
             segs.append((desc, dt, n, k))
             n += k
         maps = weights   # the tensor stays referenced while the calls that read it are queued
+        grid = _chunk_grid(ctx, center, cells, grid_out, weights, n)
+        if grid is not None:
+            axes, post_out = True, True if post_out is None else post_out
         if weights is not None:
             weights, axes, post_out = _chunk_weights(ctx, maps, n), True, True if post_out is None else post_out
         if post_out is True:
@@ -406,7 +440,7 @@ class PairEngine:
         if n < 1:
             return (_no_scalars(axes), []) if post_out is None else post_out
         post = (_ChunkPost(ctx, n, B, pov_mode, axes) if post_out is None else
-                _DevicePost(ctx, n, B, pov_mode, cut_threshold, post_out, axes, weights))
+                _DevicePost(ctx, n, B, pov_mode, cut_threshold, post_out, axes, weights, grid))
 
         def enqueue(j0):
             j1 = min(j0 + B, n)
@@ -449,6 +483,41 @@ def _chunk_weights(ctx, weights, n):
     if m not in (0, n):
         raise ValueError(f"weights: {m} maps for a chunk of {n} pairs (one (H, W) map, or one per pair)")
     return desc
+
+
+def chunk_center(center):
+    """center= / params["hip_center"]: None (the |div| argmax of pass 1) or one of _capi.CENTERS"""
+    if center is not None and center not in _capi.CENTERS:
+        raise ValueError(f"center must be None or one of {_capi.CENTERS}, got {center!r}")
+    return center
+
+
+def _chunk_grid(ctx, center, cells, grid_out, weights, n):
+    """None without center=, else what _DevicePost needs for a chunk of n pairs about the variance centre: (cells, the chunk's
+    centre records -- a new device buffer of n 32-byte records -- and grid_out's base address or None)"""
+    if chunk_center(center) is None:
+        if grid_out is not None:
+            raise ValueError("grid_out needs center='variance'")
+        return None
+    if weights is not None:
+        raise ValueError("center='variance' together with weights= is not supported")
+    cells = int(cells)
+    _capi.cell_grid(ctx.width, ctx.height, cells)
+    import torch
+    centres = torch.empty(max(n, 1) * _capi.GRID_CENTRE_DTYPE.itemsize, dtype=torch.uint8, device=torch.device("cuda", ctx.device))
+    base = None
+    if grid_out is not None:
+        base, nbytes = _capi._device_span(grid_out)
+        need = n * cells * cells * _capi.CELL_DTYPE.itemsize
+        if nbytes < need:
+            raise ValueError(f"grid_out holds {nbytes} bytes, the chunk's {n} grids of {cells} x {cells} cells need {need}")
+    return cells, centres, base
+
+
+def _no_sharded_center(center, who):
+    if center is not None:
+        raise ValueError(f"{who}: the sharded schedules take their centres from the |div| argmax; center= needs "
+                         "PairEngine.process_chunk / process_flows on one device")
 
 
 class _ChunkPost:
@@ -496,11 +565,14 @@ class _DevicePost:
     (_side_stream); finish() makes torch's current stream wait for them.  Nothing is read back.  axes=True: the calls are
     Context.radial_window_axes and the records 80 bytes.  weights (a _capi.DevWeights of the chunk's pairs, with axes):
     after_batch(k) first queues Context.pass1_weighted on batch k's slots, and its calls are
-    Context.radial_window_axes_weighted with the maps of their computed pairs."""
+    Context.radial_window_axes_weighted with the maps of their computed pairs.  grid (_chunk_grid's, with axes): after_batch(k)
+    first queues Context.cell_stats on batch k's slots, which writes the pairs' centre records into a chunk-long buffer at
+    their absolute indices (and their cell records into grid_out), and its calls are Context.radial_window_axes_centres
+    with the centres of their seq read from that buffer -- a neighbour's recycled slot is never re-read for its centre."""
 
-    def __init__(self, ctx, n, B, pov_mode, cut_threshold, out, axes=False, weights=None):
+    def __init__(self, ctx, n, B, pov_mode, cut_threshold, out, axes=False, weights=None, grid=None):
         self.ctx, self.pov_mode, self.cut_threshold = ctx, pov_mode, cut_threshold
-        self.n, self.B, self.weights = n, B, weights
+        self.n, self.B, self.weights, self.grid = n, B, weights, grid
         self.window, self.item = (ctx.radial_window_axes if axes else ctx.radial_window), _post_dtype(axes).itemsize
         self.base, nbytes = _capi._device_span(out)
         if nbytes < n * self.item:
@@ -516,10 +588,22 @@ class _DevicePost:
         if self.weights is not None:   # the batch's records under the maps, before any window call reads them
             j0, j1 = k * self.B, min((k + 1) * self.B, self.n)
             self.ctx.pass1_weighted([j % fs for j in range(j0, j1)], self._maps(j0), self.pov_mode, self.stream)
+        if self.grid is not None:   # the batch's centres, before any window call reads them
+            cells, centres, gbase = self.grid
+            j0, j1 = k * self.B, min((k + 1) * self.B, self.n)
+            citem, gitem = _capi.GRID_CENTRE_DTYPE.itemsize, cells * cells * _capi.CELL_DTYPE.itemsize
+            self.ctx.cell_stats([j % fs for j in range(j0, j1)], cells,
+                                None if gbase is None else _capi._DeviceSpan(gbase + j0 * gitem, (j1 - j0) * gitem),
+                                _capi._DeviceSpan(centres.data_ptr() + j0 * citem, (j1 - j0) * citem), self.stream)
         for lo, hi, first, count, _ in self.calls.get(k, ()):
             out = _capi._DeviceSpan(self.base + (lo + first) * item, count * item)
             seq = [j % fs for j in range(lo, hi)]
-            if self.weights is not None:
+            if self.grid is not None:
+                citem = _capi.GRID_CENTRE_DTYPE.itemsize
+                self.ctx.radial_window_axes_centres(seq, first, count,
+                                                    _capi._DeviceSpan(self.grid[1].data_ptr() + lo * citem, (hi - lo) * citem), out,
+                                                    SMOOTH_RADIUS, self.cut_threshold, self.pov_mode, self.stream)
+            elif self.weights is not None:
                 self.ctx.radial_window_axes_weighted(seq, first, count, self._maps(lo + first), out, SMOOTH_RADIUS,
                                                      self.cut_threshold, self.pov_mode, self.stream)
             else:
@@ -598,6 +682,17 @@ def static_weights(engine, params):
     return t.to(torch.device("cuda", ctx.device)).contiguous()
 
 
+def center_kwargs(params):
+    """{"center": ..., "cells": ...} when params names "hip_center" (params["hip_center_cells"], default 32, its grid), else
+    {}: the keywords of process_chunk / process_flows.  Together with "hip_weights" it is refused."""
+    center = chunk_center(params.get("hip_center"))
+    if center is None:
+        return {}
+    if params.get("hip_weights") is not None:
+        raise ValueError("hip_center together with hip_weights is not supported")
+    return {"center": center, "cells": int(params.get("hip_center_cells", 32))}
+
+
 def _weighted_scalars(buf, axes):
     """(dots or comps, records) out of a weighted chunk's buffer of 80-byte records"""
     comps, recs = post_records(buf, axes=True)
@@ -607,6 +702,9 @@ def _weighted_scalars(buf, axes):
 def _flow_scalars(engine, flows, params, axes=False):
     """(dots or comps, records) of one chunk of caller flows under params (see _chunk_scalars)"""
     pov, thr = bool(params.get("pov_mode", False)), float(params.get("cut_threshold", 7))
+    cen = center_kwargs(params)
+    if cen:   # params["hip_center"]: the device schedule about that centre
+        return _weighted_scalars(engine.process_flows(flows, pov, thr, **cen), axes)
     wts = static_weights(engine, params)
     if wts is not None:   # params["hip_weights"]: the device schedule under the static map
         return _weighted_scalars(engine.process_flows(flows, pov, thr, weights=wts), axes)
@@ -658,6 +756,9 @@ def _chunk_scalars(engine, frames, params, axes=False, **kw):
     """(dots, records) of one chunk under params: engine.process_chunk, or -- params["hip_pass2"] = "device" -- its device
     pass 2 with one buffer and one read for the chunk; axes=True: (comps float64[n, 4], records)"""
     pov, thr = bool(params.get("pov_mode", False)), float(params.get("cut_threshold", 7))
+    cen = center_kwargs(params)
+    if cen:   # params["hip_center"]: the device schedule about that centre
+        return _weighted_scalars(engine.process_chunk(frames, pov, thr, **cen, **kw), axes)
     wts = static_weights(engine, params)
     if wts is not None:   # params["hip_weights"]: the device schedule under the static map
         return _weighted_scalars(engine.process_chunk(frames, pov, thr, weights=wts, **kw), axes)
@@ -739,7 +840,7 @@ def _no_sharded_axes(axes, who):
 
 
 def process_chunk_sharded(engine, frames, rank, world, allgather, pov_mode=False, cut_threshold=7.0,
-                          assign="contiguous", block=1, axes=False):
+                          assign="contiguous", block=1, axes=False, center=None):
     """Multi-GPU form of one chunk: rank r owns the pairs shard_pairs(n, world, r, assign, block).
 
     `engine` provides pass1(frames, pair_indices, pov_mode, cut_threshold) -> records (its l-th listed pair is
@@ -749,6 +850,7 @@ def process_chunk_sharded(engine, frames, rank, world, allgather, pov_mode=False
     cross shard edges under either assignment).  Returns the full dots array and the (n, 3) records on every rank.
     axes=True is refused: the sharded schedules keep the single component."""
     _no_sharded_axes(axes, "process_chunk_sharded")
+    _no_sharded_center(center, "process_chunk_sharded")
     n = len(frames) - 1
     mine = shard_pairs(n, world, rank, assign, block)
     allrecs = _merge_records(allgather(_shard_pass1(engine, frames, mine, pov_mode, cut_threshold)), n)
@@ -764,7 +866,8 @@ def halo_rows(rows, radius=SMOOTH_RADIUS):
     return rows if len(rows) <= 2 * radius else np.concatenate([rows[:radius], rows[-radius:]], axis=0)
 
 
-def process_chunk_sharded_halo(engine, frames, rank, world, allgather, pov_mode=False, cut_threshold=7.0, axes=False):
+def process_chunk_sharded_halo(engine, frames, rank, world, allgather, pov_mode=False, cut_threshold=7.0, axes=False,
+                               center=None):
     """Streaming multi-GPU form of one chunk for CONTIGUOUS blocks: the only exchange between the passes is the halo.
 
     process_chunk_sharded gathers every pass-1 record of the chunk before any pass 2 starts, so all ranks idle until the
@@ -782,6 +885,7 @@ def process_chunk_sharded_halo(engine, frames, rank, world, allgather, pov_mode=
     bit-identical to process_chunk_sharded's and to a single-GPU process_chunk.  Returns (dots, (n, 3) records) on every
     rank.  axes=True is refused, as in process_chunk_sharded."""
     _no_sharded_axes(axes, "process_chunk_sharded_halo")
+    _no_sharded_center(center, "process_chunk_sharded_halo")
     n = len(frames) - 1
     R = SMOOTH_RADIUS
     lo, hi = shard_range(n, world, rank)
@@ -844,11 +948,13 @@ def process_chunk_sharded_halo(engine, frames, rank, world, allgather, pov_mode=
     return all_dots, allrecs
 
 
-def process_chunk_local_ranks(engines, frames, pov_mode=False, cut_threshold=7.0, assign="contiguous", block=1, axes=False):
+def process_chunk_local_ranks(engines, frames, pov_mode=False, cut_threshold=7.0, assign="contiguous", block=1, axes=False,
+                              center=None):
     """The same schedule with every rank driven from THIS process (one engine / context per device, or several
     contexts on one device): phase by phase, no process group.  Equivalent to world = len(engines) processes
     running process_chunk_sharded (axes=True is refused there and here)."""
     _no_sharded_axes(axes, "process_chunk_local_ranks")
+    _no_sharded_center(center, "process_chunk_local_ranks")
     n, world = len(frames) - 1, len(engines)
     mine = [shard_pairs(n, world, r, assign, block) for r in range(world)]
     allrecs = _merge_records([_shard_pass1(e, frames, m, pov_mode, cut_threshold) for e, m in zip(engines, mine)], n)

@@ -31,6 +31,11 @@
  *   ffl_radial_axes, ffl_radial_window_axes  replace nothing: the reference reduces a field to its radial part alone.  They
  *                           are ffl_radial / ffl_radial_window with the rotation about the centre and the weighted shift
  *                           next to it, for multi-axis scripts
+ *   ffl_cell_stats          center_of_mass_variance(flow, num_cells)                FF:721-746
+ *                           for a batch, with its intermediate grid of regional mean flow, mean magnitude and variance
+ *                           
+ *   ffl_radial_window_axes_centres  ffl_radial_window_axes with the centre list of FF:1203-1214 read from device memory:
+ *                           the variance centres of ffl_cell_stats, or any other estimator's
  *   ffl_download_flow       the "flow" entry of that dict (tests / callers that want the array)
  *   ffl_upload_frames_device  ffl_upload_frames_raw / _yuv / ffl_upload_frames for frames already in device memory (a GPU
  *                           decoder's surfaces, torch tensors); ffl_export_flows: ffl_download_flow into device memory
@@ -523,6 +528,67 @@ int ffl_radial_window_axes_weighted(ffl_ctx *ctx, int n_seq, const int *seq_slot
  * ffl_destroy: FFL_N_AXES + 1 partial sums per workgroup of the radial grid for FFL_MAX_BATCH items, which pass 1's one
  * extra partial per workgroup shares (ffl_estimate_bytes does not count it).  Needs no device. */
 int ffl_weights_extra_bytes(int width, int height, size_t *bytes);
+
+/* ---- Per-cell flow statistics and the variance centre ----
+ * center_of_mass_variance(flow, num_cells) of FF:721-746 and the grid it is formed from, on resident flow fields.  With
+ * G = cells, gh = height / G and gw = width / G (integer divisions), cell (i, j) is rows i*gh .. (i+1)*gh-1 and columns
+ * j*gw .. (j+1)*gw-1, the reference's slicing at FF:728-735; pixels at x >= G*gw or y >= G*gh belong to no cell and are
+ * never read.  The rules:
+ *   G1  1 <= G <= FFL_MAX_CELLS and G <= min(width, height).
+ *   G2  per pixel m = sqrtf(u*u + v*v) in float32; K = m of the cell's top-left pixel; d = (double)m - (double)K; the cell
+ *       sums S_u, S_v, S_d and S_dd = sum of d*d are float64.
+ *   G3  a column of a cell is summed top to bottom; the columns of a cell inside one absolute 256-column block (x / 256)
+ *       left to right into a block partial; a cell's block partials in ascending block order.  Every sum starts at +0.0.
+ *   G4  with n = (double)(gh*gw): mean_u = S_u / n, mean_v = S_v / n, mean_mag = K + S_d / n, var_mag = (S_dd - S_d*S_d / n)
+ *       / n, a result < 0 replaced by +0.0 (a NaN stays a NaN); a constant cell has var_mag = +0.0 exactly.
+ *   G5  per cell row i, over j in order: t_i = sum var, x_i = sum (double)j*var; then over i in order T = sum t_i, X = sum
+ *       x_i, Y = sum (double)i*t_i.  T == 0: cx = width / 2, cy = height / 2 (integer divisions), empty = 1 (FF:741-742);
+ *       else cx = X*gw / T + gw / 2.0, cy = Y*gh / T + gh / 2.0, left to right (FF:744-745), empty = 0.  A NaN T gives NaN
+ *       centres.
+ *   G6  the window of ffl_radial_window_axes_centres over caller centres c[0..n_seq): acc = c[j]; for i = 1..radius: c[j-i] is
+ *       added if j-i >= 0, then c[j+i] if j+i < n_seq; the centre is acc / (double)count, x and y separately -- np.mean(
+ *       center_list, axis=0) of FF:1205-1213 in the order numpy adds the rows. */
+#define FFL_MAX_CELLS 64
+typedef struct ffl_cell_record {   /* 32 bytes; rule G4 */
+    double mean_u, mean_v, mean_mag, var_mag;
+} ffl_cell_record;
+typedef struct ffl_grid_centre {   /* 32 bytes; rule G5.  total_var = T */
+    double cx, cy, total_var;
+    int32_t cells, empty;
+} ffl_grid_centre;
+
+/* Rule G1 for a width x height frame, and the cell size (either pointer may be NULL).  Pure host check: no device or
+ * context needed.  FFL_ERR_INVALID with the rule in ffl_last_error(NULL). */
+int ffl_cell_grid_check(int width, int height, int cells, int *cell_w, int *cell_h);
+
+/* The cells x cells grid of flow slots flow_slots[0..n) (FF:728-737) and / or its centre of mass (FF:739-746).  cells_dev:
+ * n * cells * cells records, item-major then row-major, or NULL; centres_dev: n records, or NULL; not both NULL.  The flow
+ * is only read and no pass-1 record is touched.  Refused before any device work, each with its rule in the message: n
+ * outside 1..max_batch; a slot out of range or repeated; a slot that holds no flow (FFL_ERR_STATE); cells outside rule G1;
+ * both outputs NULL; an output that is not 8-byte aligned device memory of the context's device inside one allocation
+ * (page-locked host memory is refused); a capturing `stream` (FFL_ERR_STATE).  Queued on the library's stream behind the
+ * work queued on `stream` and the slots' last writers -- k_cell_stats for all n items, then k_grid_centre -- and `stream`
+ * waits for it; it counts as a use of the slots; never captured; the host does not wait.  The first call of a context
+ * allocates what ffl_cells_extra_bytes reports. */
+int ffl_cell_stats(ffl_ctx *ctx, int n, const int *flow_slots, int cells, ffl_cell_record *cells_dev,
+                   ffl_grid_centre *centres_dev, uint64_t stream);
+
+/* ffl_radial_window_axes about caller centres (FF:1203-1214 with another centre estimator): entry k of centres_dev, two
+ * doubles (cx, cy) at centres_dev + k * centre_stride_bytes, is the centre of seq item k, for all n_seq of them; the
+ * window mean is rule G6.  A stride of 32 reads ffl_grid_centre records as ffl_cell_stats left them, a stride of 16 a plain
+ * (n_seq, 2) float64 array.  mean_mag, cut, x, y and div_val of the records still come from the slots' pass-1 records;
+ * the four components, the cut rule and the stream contract are ffl_radial_window_axes'.  Further refusals: a NULL or
+ * misaligned centres_dev; a stride below 16 or no multiple of 8; centres that are not device memory of the context's
+ * device inside one allocation over (n_seq - 1) * stride + 16 bytes (page-locked host memory is refused); out_dev is
+ * checked before the centres.  Its three launches are k_window_plan_centres, k_radial_axes and k_radial_axes_final. */
+int ffl_radial_window_axes_centres(ffl_ctx *ctx, int n_seq, const int *seq_slots, int first, int n, int radius,
+                                   float cut_threshold, int pov_mode, const void *centres_dev, ptrdiff_t centre_stride_bytes,
+                                   ffl_axes_record *out_dev, uint64_t stream);
+
+/* Device memory ffl_cell_stats adds to a context, allocated by its first call and freed by ffl_destroy: the two row sums
+ * of rule G5 for FFL_MAX_CELLS rows of FFL_MAX_BATCH items (256 KiB whatever the size and the grid; the cell sums
+ * themselves stay in LDS; ffl_estimate_bytes does not count it).  Needs no device. */
+int ffl_cells_extra_bytes(int width, int height, int cells, size_t *bytes);
 
 /* Copy a finished flow field to host memory as (height, width, 2) float32, cv2 layout. */
 int ffl_download_flow(ffl_ctx *ctx, int flow_slot, float *dst);
