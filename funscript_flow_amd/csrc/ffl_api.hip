@@ -341,18 +341,19 @@ struct ffl_ctx {
     DevBuf<WindowItem> d_wtab; PinBuf<WindowItem> h_wtab;  // pass-2 items, FFL_MAXB entries (host: ffl_radial; device: k_window_plan)
     DevBuf<double> d_wytab;                            // pass-2 row weights (h - y) / h and y / h
     PinBuf<Pass2Record> h_radial; Pass2Record *d_radial = nullptr;  // ffl_radial's mapped pinned records (only `dot` is used) and their device alias
-    // The four-component calls (ffl_radial_axes, ffl_radial_window_axes) have partials and pinned
-    // records of their own, allocated by their first call (axes_scratch) and held to ffl_destroy: FFL_NAXES *
-    // ffl_radial_blocks doubles per item for FFL_MAXB items, under the single-copy rule above -- stream `post` alone
-    // touches them, so a single-component call queued between two of these never sees or disturbs them.
+    // The extra scratch of stream `post`, one buffer per row of kPostScratch: allocated by the first call that needs it
+    // (post_scratch) and held to ffl_destroy, under the single-copy rule above -- stream `post` alone touches them, so a call
+    // of another form queued between two users of a buffer never sees or disturbs it.
+    // The four-component calls (ffl_radial_axes, ffl_radial_window_axes, ffl_radial_window_axes_centres; DESIGN.md section
+    // 15): FFL_NAXES * ffl_radial_blocks partials per item.
     DevBuf<double> d_apsum;
-    PinBuf<AxesRecord> h_axes; AxesRecord *d_axes = nullptr;  // ffl_radial_axes' mapped pinned records and their device alias
-    // The weighted calls (ffl_pass1_weighted, ffl_radial_window_axes_weighted): their partials --
-    // pass 1's SW per workgroup, pass 2's FFL_NAXES + 1 sums per workgroup -- allocated by their first call (weights_scratch)
-    // and held to ffl_destroy, under the single-copy rule above.
+    // ffl_radial_axes' mapped pinned records and their device alias, allocated with d_apsum.
+    PinBuf<AxesRecord> h_axes;
+    AxesRecord *d_axes = nullptr;
+    // The weighted calls (ffl_pass1_weighted, ffl_radial_window_axes_weighted): pass 1's SW per
+    // workgroup, or pass 2's FFL_NAXES + 1 sums per workgroup.
     DevBuf<double> d_wpsum;
-    // ffl_cell_stats: t_i and x_i of rule G5 per cell row, FFL_MAX_CELLS rows for FFL_MAXB items,
-    // allocated by its first call (cells_scratch) and held to ffl_destroy, under the single-copy rule above.
+    // ffl_cell_stats: t_i and x_i of rule G5 per cell row, FFL_MAX_CELLS rows per item.
     DevBuf<double> d_cellrow;
     int p1_blocks = 0;
     // profiling
@@ -728,6 +729,19 @@ static int check_flow_slots(ffl_ctx *c, const char *fn, int n, const int *slots,
 static int publish_post(ffl_ctx *c, int n, const int *slots, EvRef *done) {
     HIPCHK(c, c->post_ring.record(c->s_post, done));
     publish_slots(c, n, slots, *done, true);
+    return FFL_OK;
+}
+
+// The opening of the calls that take a list of at most max_batch flow slots and hand it to a kernel as an ExportTab
+// (ffl_import_flows, ffl_pass1_weighted, ffl_cell_stats): 1 <= n <= max_batch, the list given, every slot in range and holding
+// `holds` (see check_flow_slots), none named twice; then *t is the list.  `what` names the items in the message.
+static int open_slot_list(ffl_ctx *c, const char *fn, const char *what, int n, const int *slots, const char *holds,
+                          ExportTab *t) {
+    if (n < 1 || n > c->max_batch)
+        return set_err(c, FFL_ERR_INVALID, "%s: n = %d %s outside 1..%d (the context's max_batch)", fn, n, what, c->max_batch);
+    if (!slots) return set_err(c, FFL_ERR_INVALID, "%s: NULL flow_slots", fn);
+    if (int rc = check_flow_slots(c, fn, n, slots, holds, "repeated in one call")) return rc;
+    for (int i = 0; i < n; i++) t->slot[i] = slots[i];
     return FFL_OK;
 }
 
@@ -2111,40 +2125,75 @@ int ffl_pass1_results(ffl_ctx *c, int n, const int *slots, float cut_threshold, 
     return FFL_OK;
 }
 
-// What the four-component calls add to a context (ffl_axes_extra_bytes sums it, axes_scratch allocates it).
-static size_t axes_psum_doubles(int w, int h) { return (size_t)FFL_NAXES * (size_t)ffl_radial_blocks(w, h) * FFL_MAXB; }
+// The extra scratch of stream `post` (the DevBuf<double> members of ffl_ctx under "extra scratch"): what a context gains with
+// the first four-component, weighted or ffl_cell_stats call, in doubles for FFL_MAXB items.  The ffl_*_extra_bytes entry points
+// report a row, post_scratch allocates it.
+enum { SCR_AXES = 0, SCR_WEIGHTS, SCR_CELLS };
+struct PostScratchRow {
+    size_t (*doubles)(int w, int h);
+    const char *name;               // in the message of a failed allocation
+    DevBuf<double> ffl_ctx::*buf;
+};
+static const PostScratchRow kPostScratch[] = {
+    {[](int w, int h) { return (size_t)FFL_NAXES * (size_t)ffl_radial_blocks(w, h) * FFL_MAXB; }, "four-component",
+     &ffl_ctx::d_apsum},
+    // one buffer for whichever of the two runs: pass 2's FFL_NAXES + 1 partials per workgroup of the radial grid, or pass 1's SW
+    // per workgroup of its grid
+    {[](int w, int h) {
+         const size_t p2 = (size_t)(FFL_NAXES + 1) * (size_t)ffl_radial_blocks(w, h), p1 = (size_t)ffl_pass1_blocks(w, h);
+         return (p2 > p1 ? p2 : p1) * FFL_MAXB;
+     }, "weighted", &ffl_ctx::d_wpsum},
+    // the row sums of rule G5, whatever the size and the grid
+    {[](int, int) { return (size_t)2 * FFL_MAX_CELLS * FFL_MAXB; }, "cell-row", &ffl_ctx::d_cellrow},
+};
 
-int ffl_axes_extra_bytes(int width, int height, size_t *bytes) {
-    if (!bytes) return set_err(nullptr, FFL_ERR_INVALID, "ffl_axes_extra_bytes: bytes is NULL");
-    if (!frame_size_ok(width, height)) return set_err(nullptr, FFL_ERR_INVALID, "ffl_axes_extra_bytes: " FFL_FRAME_SIZE_RULE, width, height);
-    *bytes = sizeof(double) * axes_psum_doubles(width, height);  // + sizeof(AxesRecord) * FFL_MAXB of page-locked host memory
+static int cell_grid_check(ffl_ctx *c, const char *fn, int width, int height, int cells, int *cell_w, int *cell_h);
+
+// cells: the grid of the SCR_CELLS row, whose size check is rule G1's
+static int post_scratch_bytes(const char *fn, int row, int width, int height, int cells, size_t *bytes) {
+    if (!bytes) return set_err(nullptr, FFL_ERR_INVALID, "%s: bytes is NULL", fn);
+    if (row == SCR_CELLS) {
+        if (int rc = cell_grid_check(nullptr, fn, width, height, cells, nullptr, nullptr)) return rc;
+    } else if (!frame_size_ok(width, height))
+        return set_err(nullptr, FFL_ERR_INVALID, "%s: " FFL_FRAME_SIZE_RULE, fn, width, height);
+    *bytes = sizeof(double) * kPostScratch[row].doubles(width, height);
     return FFL_OK;
 }
 
-// The first four-component call allocates their scratch (the caller holds post_mu and the context lock).
-static int axes_scratch(ffl_ctx *c, const char *fn) {
-    if (c->d_apsum && c->h_axes) return FFL_OK;
-    hipError_t e = c->d_apsum ? hipSuccess : c->d_apsum.alloc(axes_psum_doubles(c->w, c->h));
-    if (e != hipSuccess) c->d_apsum.release();  // nothing was allocated
-    if (e == hipSuccess && !c->h_axes) {
+int ffl_axes_extra_bytes(int width, int height, size_t *bytes) {   // + sizeof(AxesRecord) * FFL_MAXB of page-locked host memory
+    return post_scratch_bytes("ffl_axes_extra_bytes", SCR_AXES, width, height, 0, bytes);
+}
+
+int ffl_weights_extra_bytes(int width, int height, size_t *bytes) {
+    return post_scratch_bytes("ffl_weights_extra_bytes", SCR_WEIGHTS, width, height, 0, bytes);
+}
+
+int ffl_cells_extra_bytes(int width, int height, int cells, size_t *bytes) {
+    return post_scratch_bytes("ffl_cells_extra_bytes", SCR_CELLS, width, height, cells, bytes);
+}
+
+// The first call that needs a row allocates it (the caller holds post_mu and the context lock).  The axes row comes with
+// ffl_radial_axes' mapped pinned records.
+static int post_scratch(ffl_ctx *c, const char *fn, int row) {
+    const PostScratchRow &r = kPostScratch[row];
+    DevBuf<double> &buf = c->*r.buf;
+    if (buf && (row != SCR_AXES || c->h_axes)) return FFL_OK;
+    const size_t doubles = r.doubles(c->w, c->h);
+    hipError_t e = buf ? hipSuccess : buf.alloc(doubles);
+    if (e != hipSuccess) buf.release();  // nothing was allocated
+    if (e == hipSuccess && row == SCR_AXES && !c->h_axes) {
         e = c->h_axes.alloc(FFL_MAXB, hipHostMallocMapped);
         if (e != hipSuccess) c->h_axes.release();
         else if ((e = hipHostGetDevicePointer((void **)&c->d_axes, c->h_axes, 0)) != hipSuccess) (void)c->h_axes.reset();
     }
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        return set_err(c, FFL_ERR_HIP, "%s: allocating the four-component scratch (%zu bytes + %zu page-locked) failed: %s", fn,
-                       sizeof(double) * axes_psum_doubles(c->w, c->h), sizeof(AxesRecord) * FFL_MAXB, hipGetErrorString(e));
+        char pinned[48] = "";
+        if (row == SCR_AXES) snprintf(pinned, sizeof pinned, " + %zu page-locked", sizeof(AxesRecord) * FFL_MAXB);
+        return set_err(c, FFL_ERR_HIP, "%s: allocating the %s scratch (%zu bytes%s) failed: %s", fn, r.name,
+                       sizeof(double) * doubles, pinned, hipGetErrorString(e));
     }
     return FFL_OK;
-}
-
-// The radial pair of either form over the items of c->d_wtab, into Pass2Record (axes = false) or AxesRecord records.
-static void launch_radial_pair(ffl_ctx *c, bool axes, int n, int pov_mode, void *rec) {
-    if (axes)
-        ffl_launch_radial_axes(c->d_wtab, n, c->w, c->h, pov_mode, c->d_wytab, c->d_apsum, (AxesRecord *)rec, c->s_post);
-    else
-        ffl_launch_radial(c->d_wtab, n, c->w, c->h, pov_mode, c->d_wytab, c->d_rpsum, (Pass2Record *)rec, c->s_post);
 }
 
 // ffl_radial (axes = false: out[i]) and ffl_radial_axes (out[i * FFL_N_AXES + component]): one protocol.
@@ -2173,12 +2222,13 @@ static int radial_call(ffl_ctx *c, const char *fn, bool axes, int n, const int *
     }
     if (m == 0) return FFL_OK;
     if (axes)
-        if (int rc = axes_scratch(c, fn)) return rc;
+        if (int rc = post_scratch(c, fn, SCR_AXES)) return rc;
     hipStream_t st = c->s_post;
     {
         HIPCHK(c, hipMemcpyAsync(c->d_wtab, tab, sizeof(WindowItem) * m, hipMemcpyHostToDevice, st));
         ProfScope ps(c, FFL_K_RADIAL, st);
-        launch_radial_pair(c, axes, m, pov_mode, axes ? (void *)c->d_axes : (void *)c->d_radial);
+        ffl_launch_radial(c->d_wtab, m, c->w, c->h, pov_mode, c->d_wytab, RadialForm{nc, nullptr},
+                          axes ? c->d_apsum : c->d_rpsum, axes ? (void *)c->d_axes : (void *)c->d_radial, st);
     }
     // the slots' "last use" now includes this pass 2: the wait below runs without the context lock, so another thread
     // may queue a batch that recycles one of these slots meanwhile -- it must run behind the kernel that reads them
@@ -2589,34 +2639,6 @@ int ffl_dev_weights_check(int n, int width, int height, const ffl_dev_weights *w
     return dev_weights_check(nullptr, "ffl_dev_weights_check", n, width, height, w, &bytes);
 }
 
-// What the weighted calls add to a context (ffl_weights_extra_bytes reports it, weights_scratch allocates it): one buffer for
-// whichever of the two runs -- pass 2's FFL_NAXES + 1 partials per workgroup of the radial grid, or pass 1's SW per
-// workgroup of its grid -- for FFL_MAXB items.
-static size_t weights_psum_doubles(int w, int h) {
-    const size_t p2 = (size_t)(FFL_NAXES + 1) * (size_t)ffl_radial_blocks(w, h), p1 = (size_t)ffl_pass1_blocks(w, h);
-    return (p2 > p1 ? p2 : p1) * FFL_MAXB;
-}
-
-int ffl_weights_extra_bytes(int width, int height, size_t *bytes) {
-    if (!bytes) return set_err(nullptr, FFL_ERR_INVALID, "ffl_weights_extra_bytes: bytes is NULL");
-    if (!frame_size_ok(width, height)) return set_err(nullptr, FFL_ERR_INVALID, "ffl_weights_extra_bytes: " FFL_FRAME_SIZE_RULE, width, height);
-    *bytes = sizeof(double) * weights_psum_doubles(width, height);
-    return FFL_OK;
-}
-
-// The first weighted call allocates their scratch (the caller holds post_mu and the context lock).
-static int weights_scratch(ffl_ctx *c, const char *fn) {
-    if (c->d_wpsum) return FFL_OK;
-    const hipError_t e = c->d_wpsum.alloc(weights_psum_doubles(c->w, c->h));
-    if (e != hipSuccess) {
-        c->d_wpsum.release();  // nothing was allocated
-        (void)hipGetLastError();
-        return set_err(c, FFL_ERR_HIP, "%s: allocating the weighted scratch (%zu bytes) failed: %s", fn,
-                       sizeof(double) * weights_psum_doubles(c->w, c->h), hipGetErrorString(e));
-    }
-    return FFL_OK;
-}
-
 static const char *kHostWeights = "weight maps live in device memory (torch / hipMalloc)";
 
 // The pass-1 records of n slots that hold a flow, recomputed under the maps by ONE k_pass1_weighted launch (plus its final
@@ -2626,18 +2648,14 @@ int ffl_pass1_weighted(ffl_ctx *c, int n, const int *slots, const ffl_dev_weight
     if (!c) return FFL_ERR_INVALID;
     std::unique_lock<std::mutex> pl(c->post_mu);  // stream `post`, d_ptab and the partials, as ffl_import_flows
     CtxLock lk(c->mu);
-    if (n < 1 || n > c->max_batch)
-        return set_err(c, FFL_ERR_INVALID, "%s: n = %d slots outside 1..%d (the context's max_batch)", fn, n, c->max_batch);
-    if (!slots) return set_err(c, FFL_ERR_INVALID, "%s: NULL flow_slots", fn);
-    if (int rc = check_flow_slots(c, fn, n, slots, "flow", "repeated in one call")) return rc;
+    ExportTab t;
+    if (int rc = open_slot_list(c, fn, "slots", n, slots, "flow", &t)) return rc;
     size_t bytes;
     if (int rc = dev_weights_check(c, fn, n, c->w, c->h, w, &bytes)) return rc;
     hipStream_t cst;
     const PostRegion reg{"the weight maps", w->base, bytes, kHostWeights};
     if (int rc = post_begin(c, fn, stream, &cst, &reg, 1, n, slots)) return rc;
-    if (int rc = weights_scratch(c, fn)) return rc;
-    ExportTab t;
-    for (int i = 0; i < n; i++) t.slot[i] = slots[i];
+    if (int rc = post_scratch(c, fn, SCR_WEIGHTS)) return rc;
     const WeightArgs wa{(const char *)w->base, (long long)w->item_stride, (long long)w->row_pitch};
     {
         ProfScope ps(c, FFL_K_PASS1, c->s_post);
@@ -2649,15 +2667,22 @@ int ffl_pass1_weighted(ffl_ctx *c, int n, const int *slots, const ffl_dev_weight
 
 static const char *kHostCentres = "centres live in device memory (ffl_cell_stats' records, or a float64 (n_seq, 2) tensor)";
 
-// ffl_radial_window (axes = false: ffl_pass2_record) and ffl_radial_window_axes (ffl_axes_record): one protocol.  wts (with
-// axes): ffl_radial_window_axes_weighted, the maps of the n computed items as a second region of caller memory.  centres
-// (with axes): ffl_radial_window_axes_centres, the n_seq caller centres as that second region.
-static int radial_window_call(ffl_ctx *c, const char *fn, bool axes, int n_seq, const int *seq, int first, int n, int radius,
-                              float cut_threshold, int pov_mode, void *out, uint64_t stream,
-                              const ffl_dev_weights *wts = nullptr, bool weighted = false, const void *cen = nullptr,
-                              ptrdiff_t cstride = 0, bool centres = false) {
+// What a window call computes: ffl_radial_window (axes = false: ffl_pass2_record) or one of the three ffl_radial_window_axes*
+// (ffl_axes_record).  weighted / centred name the entry point, since a NULL descriptor or NULL centres_dev from the caller
+// is refused, not taken for another form.  Either brings a second region of caller memory: the maps of the n computed
+// items, or the n_seq centres.
+struct WindowForm {
+    bool axes, weighted, centred;
+    const ffl_dev_weights *wts;
+    const void *cen;
+    ptrdiff_t cstride;
+};
+
+// One protocol for the four.
+static int radial_window_call(ffl_ctx *c, const char *fn, const WindowForm &form, int n_seq, const int *seq, int first, int n,
+                              int radius, float cut_threshold, int pov_mode, void *out, uint64_t stream) {
     if (!c) return FFL_ERR_INVALID;
-    const size_t rec_bytes = axes ? sizeof(ffl_axes_record) : sizeof(ffl_pass2_record);
+    const size_t rec_bytes = form.axes ? sizeof(ffl_axes_record) : sizeof(ffl_pass2_record);
     std::unique_lock<std::mutex> pl(c->post_mu);  // stream `post`, post_ring and d_rpsum, as ffl_radial / ffl_export_flows
     CtxLock lk(c->mu);
     if (n < 1 || n > FFL_MAX_BATCH) return set_err(c, FFL_ERR_INVALID, "%s: n = %d items outside 1..%d (FFL_MAX_BATCH)", fn, n, FFL_MAX_BATCH);
@@ -2673,65 +2698,64 @@ static int radial_window_call(ffl_ctx *c, const char *fn, bool axes, int n_seq, 
     // a slot's state stands for its record and its flow alike, so one check covers the neighbours and the computed items
     if (int rc = check_flow_slots(c, fn, n_seq, seq, "result", "repeated in one call")) return rc;
     if ((uintptr_t)out % 8) return set_err(c, FFL_ERR_INVALID, "%s: out_dev must be 8-byte aligned", fn);
-    size_t wbytes = 0;
-    if (weighted)
+    PostRegion reg[2] = {
+        {"out_dev", out, rec_bytes * (size_t)n, "results in host memory come from ffl_pass1_results and ffl_radial"}};
+    int nreg = 1;
+    const ffl_dev_weights *wts = form.wts;
+    if (form.weighted) {
+        size_t wbytes;
         if (int rc = dev_weights_check(c, fn, n, c->w, c->h, wts, &wbytes)) return rc;
-    if (centres) {   // rule G6: n_seq entries, two doubles at the head of each
+        reg[nreg++] = PostRegion{"the weight maps", wts->base, wbytes, kHostWeights};
+    }
+    const void *cen = form.cen;
+    const ptrdiff_t cstride = form.cstride;
+    if (form.centred) {   // rule G6: n_seq entries, two doubles at the head of each
         if (!cen) return set_err(c, FFL_ERR_INVALID, "%s: NULL centres_dev", fn);
         if ((uintptr_t)cen % 8) return set_err(c, FFL_ERR_INVALID, "%s: centres_dev must be 8-byte aligned", fn);
         if (cstride < 16 || cstride % 8 || cstride > ((ptrdiff_t)1 << 40))
             return set_err(c, FFL_ERR_INVALID, "%s: centre stride %td: a multiple of 8 bytes, at least 16 (two doubles)", fn, cstride);
+        reg[nreg++] = PostRegion{"centres_dev", cen, (size_t)(n_seq - 1) * (size_t)cstride + 16, kHostCentres};
     }
     hipStream_t cst;
-    const PostRegion second = centres ? PostRegion{"centres_dev", cen, (size_t)(n_seq - 1) * (size_t)cstride + 16, kHostCentres}
-                                      : PostRegion{"the weight maps", weighted ? wts->base : nullptr, wbytes, kHostWeights};
-    const PostRegion reg[2] = {{"out_dev", out, rec_bytes * (size_t)n, "results in host memory come from ffl_pass1_results and ffl_radial"},
-                               second};
-    if (int rc = post_begin(c, fn, stream, &cst, reg, weighted || centres ? 2 : 1, n_seq, seq)) return rc;
+    if (int rc = post_begin(c, fn, stream, &cst, reg, nreg, n_seq, seq)) return rc;
     WindowSeq t;
     for (int i = 0; i < n_seq; i++) t.slot[i] = seq[i];
-    if (weighted) {
-        if (int rc = weights_scratch(c, fn)) return rc;
-    } else if (axes)
-        if (int rc = axes_scratch(c, fn)) return rc;
+    if (form.axes)
+        if (int rc = post_scratch(c, fn, form.weighted ? SCR_WEIGHTS : SCR_AXES)) return rc;
     // not timed under FFL_K_RADIAL: that class counts the radial pairs of ffl_radial / ffl_radial_axes, one per call
-    if (centres)
-        ffl_launch_window_plan_centres(t, n_seq, first, n, radius, cut_threshold, c->d_res, c->d_flow, c->w, c->h, cen,
-                                       (long long)cstride, c->d_wtab, (AxesRecord *)out, c->s_post);
-    else
-        ffl_launch_window_plan(t, n_seq, first, n, radius, cut_threshold, c->d_res, c->d_flow, c->w, c->h, c->d_wtab, out,
-                               (int)rec_bytes, c->s_post);
-    if (weighted) {
-        const WeightArgs wa{(const char *)wts->base, (long long)wts->item_stride, (long long)wts->row_pitch};
-        ffl_launch_radial_axes_weighted(c->d_wtab, n, c->w, c->h, pov_mode ? 1 : 0, c->d_wytab, wa, c->d_wpsum, (AxesRecord *)out,
-                                        c->s_post);
-    } else
-        launch_radial_pair(c, axes, n, pov_mode ? 1 : 0, out);
+    ffl_launch_window_plan(t, n_seq, first, n, radius, cut_threshold, c->d_res, c->d_flow, c->w, c->h, cen, (long long)cstride,
+                           c->d_wtab, out, (int)rec_bytes, c->s_post);
+    WeightArgs wa{};
+    if (form.weighted) wa = WeightArgs{(const char *)wts->base, (long long)wts->item_stride, (long long)wts->row_pitch};
+    const RadialForm rf{form.axes ? FFL_NAXES : 1, form.weighted ? &wa : nullptr};
+    double *psum = form.weighted ? c->d_wpsum : form.axes ? c->d_apsum : c->d_rpsum;
+    ffl_launch_radial(c->d_wtab, n, c->w, c->h, pov_mode ? 1 : 0, c->d_wytab, rf, psum, out, c->s_post);
     return post_end(c, cst, n_seq, seq);
 }
 
 int ffl_radial_window(ffl_ctx *c, int n_seq, const int *seq, int first, int n, int radius, float cut_threshold, int pov_mode,
                       ffl_pass2_record *out, uint64_t stream) {
-    return radial_window_call(c, "ffl_radial_window", false, n_seq, seq, first, n, radius, cut_threshold, pov_mode, out, stream);
+    return radial_window_call(c, "ffl_radial_window", {false, false, false, nullptr, nullptr, 0}, n_seq, seq, first, n, radius,
+                              cut_threshold, pov_mode, out, stream);
 }
 
 int ffl_radial_window_axes(ffl_ctx *c, int n_seq, const int *seq, int first, int n, int radius, float cut_threshold, int pov_mode,
                            ffl_axes_record *out, uint64_t stream) {
-    return radial_window_call(c, "ffl_radial_window_axes", true, n_seq, seq, first, n, radius, cut_threshold, pov_mode, out,
-                              stream);
+    return radial_window_call(c, "ffl_radial_window_axes", {true, false, false, nullptr, nullptr, 0}, n_seq, seq, first, n, radius,
+                              cut_threshold, pov_mode, out, stream);
 }
 
 int ffl_radial_window_axes_weighted(ffl_ctx *c, int n_seq, const int *seq, int first, int n, int radius, float cut_threshold,
                                     int pov_mode, const ffl_dev_weights *w, ffl_axes_record *out, uint64_t stream) {
-    return radial_window_call(c, "ffl_radial_window_axes_weighted", true, n_seq, seq, first, n, radius, cut_threshold, pov_mode, out,
-                              stream, w, true);
+    return radial_window_call(c, "ffl_radial_window_axes_weighted", {true, true, false, w, nullptr, 0}, n_seq, seq, first, n,
+                              radius, cut_threshold, pov_mode, out, stream);
 }
 
 int ffl_radial_window_axes_centres(ffl_ctx *c, int n_seq, const int *seq, int first, int n, int radius, float cut_threshold,
                                    int pov_mode, const void *centres_dev, ptrdiff_t centre_stride_bytes, ffl_axes_record *out,
                                    uint64_t stream) {
-    return radial_window_call(c, "ffl_radial_window_axes_centres", true, n_seq, seq, first, n, radius, cut_threshold, pov_mode, out,
-                              stream, nullptr, false, centres_dev, centre_stride_bytes, true);
+    return radial_window_call(c, "ffl_radial_window_axes_centres", {true, false, true, nullptr, centres_dev, centre_stride_bytes},
+                              n_seq, seq, first, n, radius, cut_threshold, pov_mode, out, stream);
 }
 
 // ---- per-cell statistics and the variance centre -----------------------------------
@@ -2763,29 +2787,6 @@ int ffl_cell_grid_check(int width, int height, int cells, int *cell_w, int *cell
     return cell_grid_check(nullptr, "ffl_cell_grid_check", width, height, cells, cell_w, cell_h);
 }
 
-// What ffl_cell_stats adds to a context: the row sums of rule G5, whatever the size and the grid.
-static size_t cells_row_doubles() { return (size_t)2 * FFL_MAX_CELLS * FFL_MAXB; }
-
-int ffl_cells_extra_bytes(int width, int height, int cells, size_t *bytes) {
-    if (!bytes) return set_err(nullptr, FFL_ERR_INVALID, "ffl_cells_extra_bytes: bytes is NULL");
-    if (int rc = cell_grid_check(nullptr, "ffl_cells_extra_bytes", width, height, cells, nullptr, nullptr)) return rc;
-    *bytes = sizeof(double) * cells_row_doubles();
-    return FFL_OK;
-}
-
-// The first ffl_cell_stats call allocates its scratch (the caller holds post_mu and the context lock).
-static int cells_scratch(ffl_ctx *c, const char *fn) {
-    if (c->d_cellrow) return FFL_OK;
-    const hipError_t e = c->d_cellrow.alloc(cells_row_doubles());
-    if (e != hipSuccess) {
-        c->d_cellrow.release();  // nothing was allocated
-        (void)hipGetLastError();
-        return set_err(c, FFL_ERR_HIP, "%s: allocating the cell-row scratch (%zu bytes) failed: %s", fn,
-                       sizeof(double) * cells_row_doubles(), hipGetErrorString(e));
-    }
-    return FFL_OK;
-}
-
 // The cells x cells statistics grid of n slots that hold a flow and / or its variance centre (FF:721-746), by one
 // k_cell_stats launch plus k_grid_centre on stream `post`: ffl_pass1_weighted's protocol, with the flow only read and no
 // pass-1 record touched.
@@ -2796,10 +2797,8 @@ int ffl_cell_stats(ffl_ctx *c, int n, const int *slots, int cells, ffl_cell_reco
     if (!c) return FFL_ERR_INVALID;
     std::unique_lock<std::mutex> pl(c->post_mu);  // stream `post` and d_cellrow
     CtxLock lk(c->mu);
-    if (n < 1 || n > c->max_batch)
-        return set_err(c, FFL_ERR_INVALID, "%s: n = %d slots outside 1..%d (the context's max_batch)", fn, n, c->max_batch);
-    if (!slots) return set_err(c, FFL_ERR_INVALID, "%s: NULL flow_slots", fn);
-    if (int rc = check_flow_slots(c, fn, n, slots, "flow", "repeated in one call")) return rc;
+    ExportTab t;
+    if (int rc = open_slot_list(c, fn, "slots", n, slots, "flow", &t)) return rc;
     if (int rc = cell_grid_check(c, fn, c->w, c->h, cells, nullptr, nullptr)) return rc;
     if (!cells_dev && !centres_dev) return set_err(c, FFL_ERR_INVALID, "%s: cells_dev and centres_dev are both NULL (one output at least)", fn);
     if ((uintptr_t)cells_dev % 8 || (uintptr_t)centres_dev % 8)
@@ -2810,9 +2809,7 @@ int ffl_cell_stats(ffl_ctx *c, int n, const int *slots, int cells, ffl_cell_reco
     if (centres_dev) reg[nreg++] = PostRegion{"centres_dev", centres_dev, sizeof(ffl_grid_centre) * (size_t)n, hint};
     hipStream_t cst;
     if (int rc = post_begin(c, fn, stream, &cst, reg, nreg, n, slots)) return rc;
-    if (int rc = cells_scratch(c, fn)) return rc;
-    ExportTab t;
-    for (int i = 0; i < n; i++) t.slot[i] = slots[i];
+    if (int rc = post_scratch(c, fn, SCR_CELLS)) return rc;
     ffl_launch_cell_stats(c->d_flow, t, n, c->w, c->h, cells, (CellRecord *)cells_dev, (GridCentre *)centres_dev, c->d_cellrow,
                           c->s_post);
     return post_end(c, cst, n, slots);  // the caller may read, overwrite or free the outputs on `stream` straight after the call
@@ -2867,10 +2864,8 @@ int ffl_import_flows(ffl_ctx *c, int n, const int *slots, const ffl_dev_flow *f,
     if (!c) return FFL_ERR_INVALID;
     std::unique_lock<std::mutex> pl(c->post_mu);  // stream `post` and post_ring, as ffl_radial / ffl_export_flows
     CtxLock lk(c->mu);
-    if (n < 1 || n > c->max_batch)
-        return set_err(c, FFL_ERR_INVALID, "%s: n = %d fields outside 1..%d (the context's max_batch)", fn, n, c->max_batch);
-    if (!slots) return set_err(c, FFL_ERR_INVALID, "%s: NULL flow_slots", fn);
-    if (int rc = check_flow_slots(c, fn, n, slots, nullptr, "repeated in one call")) return rc;
+    ExportTab t;
+    if (int rc = open_slot_list(c, fn, "fields", n, slots, nullptr, &t)) return rc;
     int mode;
     size_t bytes;
     if (int rc = dev_flow_check(c, fn, dtype, n, c->w, c->h, f, &mode, &bytes)) return rc;
@@ -2880,8 +2875,6 @@ int ffl_import_flows(ffl_ctx *c, int n, const int *slots, const ffl_dev_flow *f,
     if (int rc = post_begin(c, fn, stream, &cst, &reg, 1, n, slots)) return rc;
     const ImportArgs a{(const char *)f->base, (long long)f->item_stride, (long long)f->row_pitch, (long long)f->pixel_stride,
                        (long long)f->channel_stride, c->d_flow, c->d_res};
-    ExportTab t;
-    for (int i = 0; i < n; i++) t.slot[i] = slots[i];
     {
         ProfScope ps(c, FFL_K_PASS1, c->s_post);
         ffl_launch_import_pass1(a, t, n, dtype, mode, c->w, c->h, pov_mode ? 1 : 0, c->opt.import_fused, c->d_ptab, c->d_pskey,

@@ -247,7 +247,7 @@ int ffl_pass1_blocks(int w, int h);
 void ffl_launch_pass1(const PairTab *pt, int nB, int w, int h, int pov_mode, unsigned long long *pkey, double *psum,
                       hipStream_t st);
 
-// pass 2 (k_radial, k_radial_final) and the plan of ffl_radial_window (k_window_plan)
+// pass 2 (the k_radial / k_radial_final templates) and the plan of ffl_radial_window (k_window_plan)
 #define FFL_WINDOW_MAX_RADIUS 32     // = FFL_MAX_RADIUS of include/ffl.h
 struct WindowSeq {   // the flow slots of the call's consecutive pairs; travels as a kernel argument (1280 bytes)
     int slot[FFL_MAXB + 2 * FFL_WINDOW_MAX_RADIUS];
@@ -269,33 +269,28 @@ struct AxesRecord {  // = ffl_axes_record of include/ffl.h (ffl_api.hip asserts 
 #define FFL_NAXES 4                  // = FFL_N_AXES of include/ffl.h
 // workgroups (= partial results per component) of a pass-2 grid per item
 int ffl_radial_blocks(int w, int h);
-// items tab[0..n) -> out[i].dot (+0.0 for a cut item); psum holds the partials of n items, ffl_pass1_blocks(w, h) each at most
 // wytab: 2 * h doubles, [y] = (double)(h - y) / h, [h + y] = (double)y / h (the row weights of FF:780-783)
-void ffl_launch_radial(const WindowItem *tab, int n, int w, int h, int pov_mode, const double *wytab, double *psum,
-                       Pass2Record *out, hipStream_t st);
-// The four-component form (k_radial_axes, k_radial_axes_final): items tab[0..n) -> out[i].base.dot,
-// tangential, shift_x, shift_y and reserved = +0.0 (all +0.0 for a cut item).  psum: FFL_NAXES * ffl_radial_blocks(w, h)
-// doubles per item, component c of item b at psum[(b * FFL_NAXES + c) * nblk ..]
-void ffl_launch_radial_axes(const WindowItem *tab, int n, int w, int h, int pov_mode, const double *wytab, double *psum,
-                            AxesRecord *out, hipStream_t st);
-// The weighted forms.  Pass 1: the records of flow slots tab.slot[0..n) of `flow`
-// recomputed under the maps `wa`; psw: one more double per workgroup and item next to pkey / psum.  Pass 2: the
-// four-component pair with (FFL_NAXES + 1) * ffl_radial_blocks(w, h) doubles of psum per item.
+// The form of a radial launch: nc = 1 -> out is Pass2Record[n] and out[i].dot is written; nc = FFL_NAXES (DESIGN.md section
+// 15) -> AxesRecord[n]: base.dot, tangential, shift_x, shift_y and reserved = +0.0.  maps (with nc = FFL_NAXES; section 16,
+// appendix W): the items' weight maps, or NULL.  A cut item's means are +0.0.  psum holds ffl_radial_blocks(w, h) doubles per
+// sum and item, NS = nc (+ 1 under maps, SW) sums per item: sum c of item b at psum[(b * NS + c) * nblk ..].
+struct RadialForm {
+    int nc;
+    const WeightArgs *maps;
+};
+void ffl_launch_radial(const WindowItem *tab, int n, int w, int h, int pov_mode, const double *wytab, const RadialForm &form,
+                       double *psum, void *out, hipStream_t st);
+// Pass 1 under maps: the records of flow slots tab.slot[0..n) of `flow` recomputed under the maps `wa`; psw: one more double
+// per workgroup and item next to pkey / psum.
 void ffl_launch_pass1_weighted(const WeightArgs &wa, float *flow, Pass1Result *res, const ExportTab &tab, int n, int w, int h,
                                int pov_mode, PairTab *pt, unsigned long long *pkey, double *psum, double *psw, hipStream_t st);
-void ffl_launch_radial_axes_weighted(const WindowItem *tab, int n, int w, int h, int pov_mode, const double *wytab,
-                                     const WeightArgs &wa, double *psum, AxesRecord *out, hipStream_t st);
 // items first .. first+n-1 of seq -> tab[0..n) and every field but `dot` of the Pass2Record at the head of each of the n
-// records that start rec_stride bytes apart at out (sizeof(Pass2Record) or sizeof(AxesRecord))
+// records that start rec_stride bytes apart at out (sizeof(Pass2Record) or sizeof(AxesRecord)).  cen NULL: the window's
+// centres are the records' argmax; else (rule G6; AxesRecord only) they are read from n_seq entries of
+// device memory, two doubles (cx, cy) at the head of each, cstride bytes apart.
 void ffl_launch_window_plan(const WindowSeq &seq, int n_seq, int first, int n, int radius, float cut_threshold,
-                            const Pass1Result *res, const float *flow, int w, int h, WindowItem *tab, void *out,
-                            int rec_stride, hipStream_t st);
-
-// ffl_radial_window_axes_centres (rule G6): the plan with the window's centres read from n_seq entries
-// of device memory, two doubles (cx, cy) at the head of each, cstride bytes apart; the records are AxesRecord
-void ffl_launch_window_plan_centres(const WindowSeq &seq, int n_seq, int first, int n, int radius, float cut_threshold,
-                                    const Pass1Result *res, const float *flow, int w, int h, const void *cen, long long cstride,
-                                    WindowItem *tab, AxesRecord *out, hipStream_t st);
+                            const Pass1Result *res, const float *flow, int w, int h, const void *cen, long long cstride,
+                            WindowItem *tab, void *out, int rec_stride, hipStream_t st);
 
 // per-cell statistics and the variance centre (k_cell_stats, k_grid_centre)
 #define FFL_CELLS_MAX 64             // = FFL_MAX_CELLS of include/ffl.h

@@ -5,6 +5,7 @@
 // Reductions are wave-shuffle -> LDS -> one partial per workgroup -> a small second kernel, so sums
 // are reproducible run to run (no float atomics).
 #include "ffl_kernels.h"
+#include <cassert>
 #include <type_traits>
 
 #define P1_THREADS 256
@@ -15,8 +16,8 @@
 #define P1_STRIP 126      // useful pixels of a pass-1 strip: 64 lanes x 2 pixels minus one halo pixel per side
 #define P2_STRIP 128      // pass 2 needs no halo
 #ifndef P2_AXES_G
-#define P2_AXES_G 2        // rows in flight per lane in k_radial_axes: 58 VGPRs, 8 waves per SIMD (8 rows, k_radial's: 160 VGPRs, 3 waves;
-                           // 1080p n = 32: 140 us with 8 rows, 122 with 4, 109 with 2 -- DESIGN.md section 15)
+#define P2_AXES_G 2        // rows in flight per lane in the four-component k_radial: 48 VGPRs, 8 waves per SIMD (8 rows, the single
+                           // component's: 80 VGPRs, 6 waves); chosen by measurement over 8 and 4 rows -- DESIGN.md section 15
 #endif
 
 // Both passes walk the flow field in column strips: a wave owns 128 consecutive pixels of a row (two per
@@ -82,7 +83,7 @@ struct P1SlotSrc {   // a flow slot: (h, w, 2) float32, one 16-byte load
 };
 
 // Whether and where a pass reads per-pixel weights.  WtNone compiles every weighted
-// statement of the bodies away: k_pass1, k_import_pass1, k_radial and k_radial_axes are the kernels they were.  WtBytes is
+// statement away: k_pass1, k_import_pass1 and the k_radial instantiations without maps carry no trace of it.  WtBytes is
 // one item's (h, w) uint8 map with any base and row pitch: a lane reads the weight of each of its two pixels with a byte
 // load at the pixel's clamped (x, y), so no byte outside the `w` bytes of a row is read and nothing is asked of alignment
 // (pass 1's strips start at odd x).
@@ -295,20 +296,49 @@ void ffl_launch_pass1(const PairTab *pt, int nB, int w, int h, int pov_mode, uns
 // context on the host (IEEE division, the value the device's division yields).  The row index is wave-uniform, so the
 // weight comes with a scalar load instead of a 15-instruction f64 division per lane and row -- the kernel had
 // hoisted all 16 of them and needed 198 VGPRs (2 waves per SIMD).
-// The body of k_radial (NC = 1) and k_radial_axes (NC = FFL_NAXES): one per-lane order and one wave / workgroup reduction
-// order for every component, so ffl_radial, ffl_radial_window and component 0 of their _axes forms give the same bits for
-// the same slot, centre and pov_mode.  Components 1..3 reuse the pixel's u, v, dx, dy and weights:
+
+// One pixel's terms into the lane's sums without maps: radial ((u dx + v dy) wx) wy and, with NC = FFL_NAXES, the three further
+// components.  A pixel outside the image (`in` false) adds 0.0 by a select.
+template <int NC>
+__device__ __forceinline__ void ffl_radial_terms(double (&sum)[NC], bool in, float2 f, double dx, double dy, double wx, double wy) {
+    const double u = (double)f.x, v = (double)f.y;
+    sum[0] += in ? (u * dx + v * dy) * wx * wy : 0.0;
+    if constexpr (NC > 1) {
+        sum[1] += in ? (v * dx - u * dy) * wx * wy : 0.0;
+        sum[2] += in ? u * wx * wy : 0.0;
+        sum[3] += in ? v * wx * wy : 0.0;
+    }
+}
+
+// What a radial launch takes as its maps: WeightArgs, or NoWeights for the forms without.  ffl_item_weights is item b's policy.
+struct NoWeights {};
+__device__ __forceinline__ WtNone ffl_item_weights(const NoWeights &, int) { return WtNone{}; }
+__device__ __forceinline__ WtBytes ffl_item_weights(const WeightArgs &wa, int b) {
+    return WtBytes{wa.base + (long long)b * wa.item, wa.pitch};   // rows wa.pitch bytes apart
+}
+
+// The main kernel of the radial pair over a WindowItem table in device memory: ffl_radial copies one there, ffl_radial_window
+// has k_window_plan write it.  Three instantiations: <1, 8, NoWeights> (ffl_radial, ffl_radial_window), <FFL_NAXES, P2_AXES_G,
+// NoWeights> and <FFL_NAXES, P2_AXES_G, WeightArgs> (section 16).  One per-lane order and one wave /
+// workgroup reduction order for every component, so the single- and the four-component forms give the same bits in component
+// 0 for the same slot, centre and pov_mode.  Components 1..3 reuse the pixel's u, v, dx, dy and weights:
 // tangential ((v dx - u dy) wx) wy, shift_x (u wx) wy, shift_y (v wx) wy.  Component c of workgroup g of item b goes to
-// psum[(b * NC + c) * gridDim.x + g]; ssum holds NC * 4 doubles.  G: rows of the row group whose loads are in flight together.
-// Wt::on (k_radial_axes_weighted, rule W4): every term is today's, times (double)weight once more, and enters its sum only
-// where the weight is > 0 (a select); SW = sum of the weights is one more component, index NC, so psum and ssum hold
-// NC + 1 of them per item and workgroup.
-template <int NC, int G, class Wt>
-__device__ __forceinline__ void ffl_radial_body(const float2 *__restrict__ flow, const Wt &wt, double cx, double cy, int w, int h,
-                                                int pov_mode, int b, const double *__restrict__ wytab,
-                                                double *__restrict__ psum, double *ssum) {
+// psum[(b * NS + c) * gridDim.x + g], component-major per item, so the final kernel reads each component's partials with
+// consecutive lanes.  G: rows of the row group whose loads are in flight together.
+// Under maps (rule W4) SW = sum of the weights is one more component, index NC: NS = NC + 1 sums per item and workgroup.
+// The workgroups of a cut item leave on a workgroup-uniform branch before they load anything of the flow or of a map (FF:766-767,
+// rule W6), and the final kernel answers it +0.0.
+template <int NC, int G, class WA>
+__global__ __launch_bounds__(P1_THREADS) void k_radial(const WindowItem *__restrict__ tab, int w, int h, int pov_mode,
+                                                       const double *__restrict__ wytab, double *__restrict__ psum, const WA wa) {
+    using Wt = decltype(ffl_item_weights(wa, 0));
     constexpr int NS = NC + (Wt::on ? 1 : 0);   // sums per lane
-    const double dw = (double)w;
+    __shared__ double ssum[NS * (P1_THREADS / 64)];
+    const int b = blockIdx.y;
+    if (tab[b].cut) return;
+    const float2 *flow = reinterpret_cast<const float2 *>(tab[b].flow);
+    const Wt wt = ffl_item_weights(wa, b);
+    const double cx = tab[b].cx, cy = tab[b].cy, dw = (double)w;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int nstrips = (w + P2_STRIP - 1) / P2_STRIP, ngroups = (h + P1_RG - 1) / P1_RG;
     const int wid = blockIdx.x * (P1_THREADS / 64) + wv;  // wave-uniform
@@ -323,8 +353,8 @@ __device__ __forceinline__ void ffl_radial_body(const float2 *__restrict__ flow,
         const double dx0 = (double)x - cx, dx1 = (double)(x + 1) - cx;
         const double wx0 = pov_mode ? 1.0 : (((double)x > cx) ? (double)(w - x) / dw : (double)x / dw);
         const double wx1 = pov_mode ? 1.0 : (((double)(x + 1) > cx) ? (double)(w - x - 1) / dw : (double)(x + 1) / dw);
-        // two groups of 8 rows: 8 row loads in flight per lane are enough to cover the latency, and the unrolled body
-        // stays within 4 waves per SIMD (all 16 rows hoisted needed 191 VGPRs)
+        // G = 8, two groups of 8 rows: 8 row loads in flight per lane are enough to cover the latency, and the unrolled body
+        // holds 8 waves per SIMD (64 VGPRs; all 16 rows hoisted needed 191)
 #pragma unroll 1
         for (int g = 0; g < P1_RG; g += G) {
             float2 f0[G], f1[G];
@@ -341,15 +371,18 @@ __device__ __forceinline__ void ffl_radial_body(const float2 *__restrict__ flow,
 #pragma unroll
             for (int r = 0; r < G; r++) {
                 const int y = y0 + g + r;
-                const int yc = min(y, h - 1);  // rows past the image contribute nothing (predicated below)
+                const int yc = min(y, h - 1);  // rows past the image contribute nothing (selected out in the terms)
                 const double dy = (double)y - cy;
                 const double wy = pov_mode ? 1.0 : (((double)y > cy) ? wytab[yc] : wytab[h + yc]);
-                const double t0 = ((double)f0[r].x * dx0 + (double)f0[r].y * dy) * wx0 * wy;
-                const double t1 = ((double)f1[r].x * dx1 + (double)f1[r].y * dy) * wx1 * wy;
                 if constexpr (Wt::on) {
+                    // Rule W4, written out: stated through ffl_radial_terms with the predicate and the factor hoisted, this
+                    // instantiation measured behind at 256 items of 256x256 (profiles/r22_pass2_single_source.md).  Every term
+                    // is the unweighted one times (double)weight as its last factor, and enters only where the weight is > 0.
                     static_assert(NC == FFL_NAXES, "the weighted form is the four-component one");
                     const bool in0 = ok0 && y < h && q0[r] > 0u, in1 = ok1 && y < h && q1[r] > 0u;
                     const double p0 = (double)q0[r], p1 = (double)q1[r];
+                    const double t0 = ((double)f0[r].x * dx0 + (double)f0[r].y * dy) * wx0 * wy;
+                    const double t1 = ((double)f1[r].x * dx1 + (double)f1[r].y * dy) * wx1 * wy;
                     const double u0 = (double)f0[r].x, v0 = (double)f0[r].y, u1 = (double)f1[r].x, v1 = (double)f1[r].y;
                     const double a0 = (v0 * dx0 - u0 * dy) * wx0 * wy, a1 = (v1 * dx1 - u1 * dy) * wx1 * wy;
                     sum[0] += in0 ? t0 * p0 : 0.0;
@@ -363,18 +396,8 @@ __device__ __forceinline__ void ffl_radial_body(const float2 *__restrict__ flow,
                     sum[NC] += in0 ? p0 : 0.0;
                     sum[NC] += in1 ? p1 : 0.0;
                 } else {
-                    sum[0] += (ok0 && y < h) ? t0 : 0.0;
-                    sum[0] += (ok1 && y < h) ? t1 : 0.0;
-                    if constexpr (NC > 1) {
-                        const double u0 = (double)f0[r].x, v0 = (double)f0[r].y, u1 = (double)f1[r].x, v1 = (double)f1[r].y;
-                        const double a0 = (v0 * dx0 - u0 * dy) * wx0 * wy, a1 = (v1 * dx1 - u1 * dy) * wx1 * wy;
-                        sum[1] += (ok0 && y < h) ? a0 : 0.0;
-                        sum[1] += (ok1 && y < h) ? a1 : 0.0;
-                        sum[2] += (ok0 && y < h) ? u0 * wx0 * wy : 0.0;
-                        sum[2] += (ok1 && y < h) ? u1 * wx1 * wy : 0.0;
-                        sum[3] += (ok0 && y < h) ? v0 * wx0 * wy : 0.0;
-                        sum[3] += (ok1 && y < h) ? v1 * wx1 * wy : 0.0;
-                    }
+                    ffl_radial_terms<NC>(sum, ok0 && y < h, f0[r], dx0, dy, wx0, wy);
+                    ffl_radial_terms<NC>(sum, ok1 && y < h, f1[r], dx1, dy, wx1, wy);
                 }
             }
         }
@@ -394,158 +417,93 @@ __device__ __forceinline__ void ffl_radial_body(const float2 *__restrict__ flow,
     }
 }
 
-// The body of k_radial_final (NC = 1) and k_radial_axes_final (NC = FFL_NAXES): each component's nblk partials of item b
-// in one order; the means are valid in thread 0.  ssum holds NC * 4 doubles.
-// WT (k_radial_axes_weighted_final): NS = NC + 1 sums per item, the last one SW, which replaces the pixel count as the one
-// divisor; SW == 0 (rule W5) divides the all-zero sums by 1.0 instead, +0.0 without a division by zero.
-template <int NC, bool WT = false>
-__device__ __forceinline__ void ffl_radial_final_body(int w, int h, int nblk, int b, const double *__restrict__ psum,
-                                                      double *ssum, double (&sum)[NC + (WT ? 1 : 0)]) {
+// The final kernel of the pair: each component's nblk partials of item b in one order, then its means into out[b] -- `dot` of a
+// Pass2Record (NC = 1), or the four components of an AxesRecord and reserved = +0.0; whoever planned the item wrote the rest of
+// the record.  A cut item's partials were never written: its means are +0.0.
+// WT: NS = NC + 1 sums per item, the last one SW, which replaces the pixel count as the one divisor; SW == 0 (rule W5) divides
+// the all-zero sums by 1.0 instead, +0.0 without a division by zero.
+template <int NC, bool WT, class Rec>
+__global__ __launch_bounds__(P1_THREADS) void k_radial_final(const WindowItem *__restrict__ tab, int w, int h, int nblk,
+                                                             const double *__restrict__ psum, Rec *__restrict__ out) {
     constexpr int NS = NC + (WT ? 1 : 0);
+    __shared__ double ssum[NS * (P1_THREADS / 64)];
+    const int b = blockIdx.x;
+    double sum[NS];
 #pragma unroll
     for (int c = 0; c < NS; c++) sum[c] = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += P1_THREADS) {
+    if (!tab[b].cut) {   // workgroup-uniform
+        for (int i = threadIdx.x; i < nblk; i += P1_THREADS) {
 #pragma unroll
-        for (int c = 0; c < NS; c++) sum[c] += psum[((size_t)b * NS + c) * nblk + i];
-    }
-    int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+            for (int c = 0; c < NS; c++) sum[c] += psum[((size_t)b * NS + c) * nblk + i];
+        }
+        int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
-    for (int c = 0; c < NS; c++) {
-        sum[c] = ffl_wave_sum_f64(sum[c]);
-        if (lane == 0) ssum[c * (P1_THREADS / 64) + wv] = sum[c];
+        for (int c = 0; c < NS; c++) {
+            sum[c] = ffl_wave_sum_f64(sum[c]);
+            if (lane == 0) ssum[c * (P1_THREADS / 64) + wv] = sum[c];
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int c = 0; c < NS; c++)
+                for (int i = 1; i < P1_THREADS / 64; i++) sum[c] += ssum[c * (P1_THREADS / 64) + i];
+            double divisor = (double)w * (double)h;
+            if constexpr (WT) divisor = sum[NC] == 0.0 ? 1.0 : sum[NC];
+#pragma unroll
+            for (int c = 0; c < NC; c++) sum[c] = sum[c] / divisor;
+        }
     }
-    __syncthreads();
     if (threadIdx.x == 0) {
-#pragma unroll
-        for (int c = 0; c < NS; c++)
-            for (int i = 1; i < P1_THREADS / 64; i++) sum[c] += ssum[c * (P1_THREADS / 64) + i];
-        double divisor = (double)w * (double)h;
-        if constexpr (WT) divisor = sum[NC] == 0.0 ? 1.0 : sum[NC];
-#pragma unroll
-        for (int c = 0; c < NC; c++) sum[c] = sum[c] / divisor;
+        if constexpr (NC == 1) {
+            out[b].dot = sum[0];
+        } else {
+            out[b].base.dot = sum[0];
+            out[b].tangential = sum[1];
+            out[b].shift_x = sum[2];
+            out[b].shift_y = sum[3];
+            out[b].reserved = 0.0;
+        }
     }
 }
 
-// The radial pair over a WindowItem table in device memory: ffl_radial copies one there, ffl_radial_window has
-// k_window_plan write it.  The workgroups of a cut item leave on a workgroup-uniform branch before they load anything of the
-// flow, and k_radial_final answers it +0.0.
-__global__ __launch_bounds__(P1_THREADS) void k_radial(const WindowItem *__restrict__ tab, int w, int h, int pov_mode,
-                                                       const double *__restrict__ wytab, double *__restrict__ psum) {
-    __shared__ double ssum[P1_THREADS / 64];
-    const int b = blockIdx.y;
-    if (tab[b].cut) return;   // workgroup-uniform: FF:766-767, a cut is 0.0 without a look at the flow
-    ffl_radial_body<1, 8>(reinterpret_cast<const float2 *>(tab[b].flow), WtNone{}, tab[b].cx, tab[b].cy, w, h, pov_mode, b, wytab, psum, ssum);
-}
-
-__global__ __launch_bounds__(P1_THREADS) void k_radial_final(const WindowItem *__restrict__ tab, int w, int h, int nblk,
-                                                             const double *__restrict__ psum, Pass2Record *__restrict__ out) {
-    __shared__ double ssum[P1_THREADS / 64];
-    const int b = blockIdx.x;
-    if (tab[b].cut) {         // its partials were never written
-        if (threadIdx.x == 0) out[b].dot = 0.0;
-        return;
-    }
-    double mean[1];
-    ffl_radial_final_body<1>(w, h, nblk, b, psum, ssum, mean);
-    if (threadIdx.x == 0) out[b].dot = mean[0];
-}
-
-void ffl_launch_radial(const WindowItem *tab, int n, int w, int h, int pov_mode, const double *wytab, double *psum,
-                       Pass2Record *out, hipStream_t st) {
+template <int NC, int G, class Rec, class WA>
+static void ffl_radial_pair(const WindowItem *tab, int n, int w, int h, int pov_mode, const double *wytab, const WA &wa,
+                            double *psum, void *out, hipStream_t st) {
     const int nblk = ffl_radial_blocks(w, h);
-    hipLaunchKernelGGL(k_radial, dim3(nblk, n), dim3(P1_THREADS), 0, st, tab, w, h, pov_mode, wytab, psum);
-    hipLaunchKernelGGL(k_radial_final, dim3(n), dim3(P1_THREADS), 0, st, tab, w, h, nblk, psum, out);
+    hipLaunchKernelGGL((k_radial<NC, G, WA>), dim3(nblk, n), dim3(P1_THREADS), 0, st, tab, w, h, pov_mode, wytab, psum, wa);
+    hipLaunchKernelGGL((k_radial_final<NC, std::is_same<WA, WeightArgs>::value, Rec>), dim3(n), dim3(P1_THREADS), 0, st, tab, w, h,
+                       nblk, psum, (Rec *)out);
 }
 
-// The four-component pair: k_radial's grid, FFL_NAXES partials per workgroup, component-major per
-// item (see ffl_radial_body), so k_radial_axes_final reads each component's partials with consecutive lanes.  The records
-// are AxesRecord: whoever planned the item wrote the rest of `base`.
-__global__ __launch_bounds__(P1_THREADS) void k_radial_axes(const WindowItem *__restrict__ tab, int w, int h, int pov_mode,
-                                                            const double *__restrict__ wytab, double *__restrict__ psum) {
-    __shared__ double ssum[FFL_NAXES * (P1_THREADS / 64)];
-    const int b = blockIdx.y;
-    if (tab[b].cut) return;   // workgroup-uniform, as k_radial
-    ffl_radial_body<FFL_NAXES, P2_AXES_G>(reinterpret_cast<const float2 *>(tab[b].flow), WtNone{}, tab[b].cx, tab[b].cy, w, h, pov_mode, b, wytab, psum,
-                               ssum);
-}
-
-__global__ __launch_bounds__(P1_THREADS) void k_radial_axes_final(const WindowItem *__restrict__ tab, int w, int h, int nblk,
-                                                                  const double *__restrict__ psum, AxesRecord *__restrict__ out) {
-    __shared__ double ssum[FFL_NAXES * (P1_THREADS / 64)];
-    const int b = blockIdx.x;
-    double mean[FFL_NAXES] = {0.0, 0.0, 0.0, 0.0};   // a cut item: its partials were never written
-    if (!tab[b].cut) ffl_radial_final_body<FFL_NAXES>(w, h, nblk, b, psum, ssum, mean);   // workgroup-uniform
-    if (threadIdx.x == 0) {
-        out[b].base.dot = mean[0];
-        out[b].tangential = mean[1];
-        out[b].shift_x = mean[2];
-        out[b].shift_y = mean[3];
-        out[b].reserved = 0.0;
-    }
-}
-
-void ffl_launch_radial_axes(const WindowItem *tab, int n, int w, int h, int pov_mode, const double *wytab, double *psum,
-                            AxesRecord *out, hipStream_t st) {
-    const int nblk = ffl_radial_blocks(w, h);
-    hipLaunchKernelGGL(k_radial_axes, dim3(nblk, n), dim3(P1_THREADS), 0, st, tab, w, h, pov_mode, wytab, psum);
-    hipLaunchKernelGGL(k_radial_axes_final, dim3(n), dim3(P1_THREADS), 0, st, tab, w, h, nblk, psum, out);
-}
-
-// The weighted four-component pair: k_radial_axes' grid and bodies with the items' maps -- item b's
-// at wbase + b * witem, rows wpitch bytes apart -- and FFL_NAXES + 1 partials per workgroup.  A cut item reads neither its
-// flow nor its map (rule W6).
-__global__ __launch_bounds__(P1_THREADS) void k_radial_axes_weighted(const WindowItem *__restrict__ tab, int w, int h, int pov_mode,
-                                                                     const double *__restrict__ wytab, const char *__restrict__ wbase,
-                                                                     long long witem, long long wpitch, double *__restrict__ psum) {
-    __shared__ double ssum[(FFL_NAXES + 1) * (P1_THREADS / 64)];
-    const int b = blockIdx.y;
-    if (tab[b].cut) return;   // workgroup-uniform, as k_radial
-    const WtBytes wt{wbase + (long long)b * witem, wpitch};
-    ffl_radial_body<FFL_NAXES, P2_AXES_G>(reinterpret_cast<const float2 *>(tab[b].flow), wt, tab[b].cx, tab[b].cy, w, h, pov_mode, b, wytab,
-                                          psum, ssum);
-}
-
-__global__ __launch_bounds__(P1_THREADS) void k_radial_axes_weighted_final(const WindowItem *__restrict__ tab, int w, int h, int nblk,
-                                                                           const double *__restrict__ psum,
-                                                                           AxesRecord *__restrict__ out) {
-    __shared__ double ssum[(FFL_NAXES + 1) * (P1_THREADS / 64)];
-    const int b = blockIdx.x;
-    double mean[FFL_NAXES + 1] = {0.0, 0.0, 0.0, 0.0, 0.0};   // a cut item: its partials were never written
-    if (!tab[b].cut) ffl_radial_final_body<FFL_NAXES, true>(w, h, nblk, b, psum, ssum, mean);   // workgroup-uniform
-    if (threadIdx.x == 0) {
-        out[b].base.dot = mean[0];
-        out[b].tangential = mean[1];
-        out[b].shift_x = mean[2];
-        out[b].shift_y = mean[3];
-        out[b].reserved = 0.0;
-    }
-}
-
-void ffl_launch_radial_axes_weighted(const WindowItem *tab, int n, int w, int h, int pov_mode, const double *wytab,
-                                     const WeightArgs &wa, double *psum, AxesRecord *out, hipStream_t st) {
-    const int nblk = ffl_radial_blocks(w, h);
-    hipLaunchKernelGGL(k_radial_axes_weighted, dim3(nblk, n), dim3(P1_THREADS), 0, st, tab, w, h, pov_mode, wytab, wa.base, wa.item,
-                       wa.pitch, psum);
-    hipLaunchKernelGGL(k_radial_axes_weighted_final, dim3(n), dim3(P1_THREADS), 0, st, tab, w, h, nblk, psum, out);
+void ffl_launch_radial(const WindowItem *tab, int n, int w, int h, int pov_mode, const double *wytab, const RadialForm &form,
+                       double *psum, void *out, hipStream_t st) {
+    assert((form.nc == 1 && !form.maps) || form.nc == FFL_NAXES);   // the three forms that exist
+    if (form.maps)
+        ffl_radial_pair<FFL_NAXES, P2_AXES_G, AxesRecord>(tab, n, w, h, pov_mode, wytab, *form.maps, psum, out, st);
+    else if (form.nc == FFL_NAXES)
+        ffl_radial_pair<FFL_NAXES, P2_AXES_G, AxesRecord>(tab, n, w, h, pov_mode, wytab, NoWeights{}, psum, out, st);
+    else
+        ffl_radial_pair<1, 8, Pass2Record>(tab, n, w, h, pov_mode, wytab, NoWeights{}, psum, out, st);
 }
 
 // ---- pass 2 behind the batches, host-free (ffl_radial_window) ---------------------------------
-// k_window_plan, then the radial pair.  One thread per item forms the clipped centre window, mean_mag and cut out of the
-// pass-1 records and writes the device-resident WindowItem table plus every field of the record but `dot` (STRIDE: bytes
+// k_window_plan<STRIDE, CEN>, then the radial pair.  One thread per item forms the clipped centre window, mean_mag and cut out of
+// the pass-1 records and writes the device-resident WindowItem table plus every field of the record but `dot` (STRIDE: bytes
 // from one record to the next; each starts with a Pass2Record).  The records
 // are mapped pinned memory: a workgroup stages the (x, y) of the <= 64 + 2 * radius records its items' windows span in
 // LDS, so the window costs one (x, y) read per record and workgroup instead of 2 * radius + 1 per item; each item then
 // reads mag_sum and div_val of its own record once more.  Nothing of a record is read by the radial grid.
 #define W2_THREADS 64
 
-// CEN (k_window_plan_centres, DESIGN.md section 17 rule G6): the window's centres are the caller's, two doubles at the head
+// CEN (k_window_plan<80, true>, DESIGN.md section 17 rule G6): the window's centres are the caller's, two doubles at the head
 // of each of n_seq entries cstride bytes apart at cen, staged the same way and added in the order numpy adds the rows of
 // FF:1205-1213's list -- item j, then j - i before j + i for i = 1..radius.  x and y of the record are still the slot's.
 template <int STRIDE, bool CEN>
-__device__ __forceinline__ void ffl_window_plan_body(const WindowSeq &seq, int n_seq, int first, int n, int radius,
-                                                     float cut_threshold, double npx, const Pass1Result *__restrict__ res,
-                                                     const float *__restrict__ flow, size_t N, const char *__restrict__ cen,
-                                                     long long cstride, WindowItem *__restrict__ tab, char *__restrict__ out) {
+__global__ __launch_bounds__(W2_THREADS) void k_window_plan(const WindowSeq seq, int n_seq, int first, int n, int radius,
+                                                            float cut_threshold, double npx, const Pass1Result *__restrict__ res,
+                                                            const float *__restrict__ flow, size_t N, const char *__restrict__ cen,
+                                                            long long cstride, WindowItem *__restrict__ tab,
+                                                            char *__restrict__ out) {
     using T = typename std::conditional<CEN, double, int>::type;
     __shared__ T sx[W2_THREADS + 2 * FFL_WINDOW_MAX_RADIUS], sy[W2_THREADS + 2 * FFL_WINDOW_MAX_RADIUS];
     const int i0 = blockIdx.x * W2_THREADS;                      // the workgroup's first item
@@ -618,43 +576,15 @@ __device__ __forceinline__ void ffl_window_plan_body(const WindowSeq &seq, int n
     o->pad = 0;
 }
 
-template <int STRIDE>
-__global__ __launch_bounds__(W2_THREADS) void k_window_plan(const WindowSeq seq, int n_seq, int first, int n, int radius,
-                                                            float cut_threshold, double npx,
-                                                            const Pass1Result *__restrict__ res, const float *__restrict__ flow,
-                                                            size_t N, WindowItem *__restrict__ tab,
-                                                            char *__restrict__ out) {
-    ffl_window_plan_body<STRIDE, false>(seq, n_seq, first, n, radius, cut_threshold, npx, res, flow, N, nullptr, 0, tab, out);
-}
-
-__global__ __launch_bounds__(W2_THREADS) void k_window_plan_centres(const WindowSeq seq, int n_seq, int first, int n, int radius,
-                                                                    float cut_threshold, double npx,
-                                                                    const Pass1Result *__restrict__ res,
-                                                                    const float *__restrict__ flow, size_t N,
-                                                                    const char *__restrict__ cen, long long cstride,
-                                                                    WindowItem *__restrict__ tab, char *__restrict__ out) {
-    ffl_window_plan_body<(int)sizeof(AxesRecord), true>(seq, n_seq, first, n, radius, cut_threshold, npx, res, flow, N, cen, cstride,
-                                                        tab, out);
-}
-
+// cen NULL: the centres are the records' argmax, rec_stride sizeof(Pass2Record) or sizeof(AxesRecord); else the caller's, the
+// records AxesRecord
 void ffl_launch_window_plan(const WindowSeq &seq, int n_seq, int first, int n, int radius, float cut_threshold,
-                            const Pass1Result *res, const float *flow, int w, int h, WindowItem *tab, void *out,
-                            int rec_stride, hipStream_t st) {
-    const dim3 grid((n + W2_THREADS - 1) / W2_THREADS);
-    const double npx = (double)w * (double)h;
-    if (rec_stride == (int)sizeof(AxesRecord))
-        hipLaunchKernelGGL(k_window_plan<(int)sizeof(AxesRecord)>, grid, dim3(W2_THREADS), 0, st, seq, n_seq, first, n, radius,
-                           cut_threshold, npx, res, flow, (size_t)w * h, tab, (char *)out);
-    else
-        hipLaunchKernelGGL(k_window_plan<(int)sizeof(Pass2Record)>, grid, dim3(W2_THREADS), 0, st, seq, n_seq, first, n, radius,
-                           cut_threshold, npx, res, flow, (size_t)w * h, tab, (char *)out);
-}
-
-void ffl_launch_window_plan_centres(const WindowSeq &seq, int n_seq, int first, int n, int radius, float cut_threshold,
-                                    const Pass1Result *res, const float *flow, int w, int h, const void *cen, long long cstride,
-                                    WindowItem *tab, AxesRecord *out, hipStream_t st) {
-    hipLaunchKernelGGL(k_window_plan_centres, dim3((n + W2_THREADS - 1) / W2_THREADS), dim3(W2_THREADS), 0, st, seq, n_seq, first,
-                       n, radius, cut_threshold, (double)w * (double)h, res, flow, (size_t)w * h, (const char *)cen, cstride, tab,
+                            const Pass1Result *res, const float *flow, int w, int h, const void *cen, long long cstride,
+                            WindowItem *tab, void *out, int rec_stride, hipStream_t st) {
+    constexpr int P2 = (int)sizeof(Pass2Record), AX = (int)sizeof(AxesRecord);
+    const auto plan = cen ? k_window_plan<AX, true> : rec_stride == AX ? k_window_plan<AX, false> : k_window_plan<P2, false>;
+    hipLaunchKernelGGL(plan, dim3((n + W2_THREADS - 1) / W2_THREADS), dim3(W2_THREADS), 0, st, seq, n_seq, first, n, radius,
+                       cut_threshold, (double)w * (double)h, res, flow, (size_t)w * h, (const char *)cen, cstride, tab,
                        (char *)out);
 }
 

@@ -353,18 +353,11 @@ class PairEngine:
         device memory (grid_buffer) that receives every pair's cells x cells cell records.  Not combined with `weights`."""
         ctx, B = self.ctx, self.B
         n = len(frames) - 1
-        grid = _chunk_grid(ctx, center, cells, grid_out, weights, n)
-        if grid is not None:
-            axes, post_out = True, True if post_out is None else post_out
         maps = weights   # the tensor stays referenced while the calls that read it are queued
-        if weights is not None and n >= 1:
-            weights, axes, post_out = _chunk_weights(ctx, maps, n), True, True if post_out is None else post_out
-        elif weights is not None:
-            weights, axes, post_out = None, True, True if post_out is None else post_out
+        post_out, axes, weights, grid = _chunk_post_args(ctx, n, post_out, axes, weights, center, cells, grid_out,
+                                                         check_empty=False)
         if n < 1:
-            return (_no_scalars(axes), []) if post_out is None else (post_buffer(ctx, 0, axes) if post_out is True else post_out)
-        if post_out is True:
-            post_out = post_buffer(ctx, n, axes)
+            return (_no_scalars(axes), []) if post_out is None else post_out
         layout = None
         if flows_out is not None:
             shp = tuple(flows_out.shape)
@@ -430,13 +423,7 @@ class PairEngine:
             segs.append((desc, dt, n, k))
             n += k
         maps = weights   # the tensor stays referenced while the calls that read it are queued
-        grid = _chunk_grid(ctx, center, cells, grid_out, weights, n)
-        if grid is not None:
-            axes, post_out = True, True if post_out is None else post_out
-        if weights is not None:
-            weights, axes, post_out = _chunk_weights(ctx, maps, n), True, True if post_out is None else post_out
-        if post_out is True:
-            post_out = post_buffer(ctx, n, axes)
+        post_out, axes, weights, grid = _chunk_post_args(ctx, n, post_out, axes, weights, center, cells, grid_out)
         if n < 1:
             return (_no_scalars(axes), []) if post_out is None else post_out
         post = (_ChunkPost(ctx, n, B, pov_mode, axes) if post_out is None else
@@ -512,6 +499,20 @@ def _chunk_grid(ctx, center, cells, grid_out, weights, n):
         if nbytes < need:
             raise ValueError(f"grid_out holds {nbytes} bytes, the chunk's {n} grids of {cells} x {cells} cells need {need}")
     return cells, centres, base
+
+
+def _chunk_post_args(ctx, n, post_out, axes, weights, center, cells, grid_out, check_empty=True):
+    """The keywords of process_chunk / process_flows as what the schedule of a chunk of n pairs needs: (post_out, axes, the
+    chunk's _capi.DevWeights or None, _chunk_grid's tuple or None).  weights= and center= each put the chunk on the device
+    schedule with 80-byte records: axes is True and post_out defaults to a new buffer; post_out=True is that buffer from
+    here on (no records for a chunk without pairs, n <= 0).  check_empty=False: the maps of such a chunk are not looked at."""
+    grid = _chunk_grid(ctx, center, cells, grid_out, weights, n)
+    desc = _chunk_weights(ctx, weights, n) if weights is not None and (n >= 1 or check_empty) else None
+    if grid is not None or weights is not None:
+        axes, post_out = True, True if post_out is None else post_out
+    if post_out is True:
+        post_out = post_buffer(ctx, max(n, 0), axes)
+    return post_out, axes, desc, grid
 
 
 def _no_sharded_center(center, who):
@@ -699,20 +700,6 @@ def _weighted_scalars(buf, axes):
     return (comps if axes else comps[:, 0]), recs
 
 
-def _flow_scalars(engine, flows, params, axes=False):
-    """(dots or comps, records) of one chunk of caller flows under params (see _chunk_scalars)"""
-    pov, thr = bool(params.get("pov_mode", False)), float(params.get("cut_threshold", 7))
-    cen = center_kwargs(params)
-    if cen:   # params["hip_center"]: the device schedule about that centre
-        return _weighted_scalars(engine.process_flows(flows, pov, thr, **cen), axes)
-    wts = static_weights(engine, params)
-    if wts is not None:   # params["hip_weights"]: the device schedule under the static map
-        return _weighted_scalars(engine.process_flows(flows, pov, thr, weights=wts), axes)
-    if _pass2_mode(params):   # params["hip_pass2"] = "device": one buffer and one read per chunk
-        return post_records(engine.process_flows(flows, pov, thr, post_out=True, **_axes_kw(axes)), **_axes_kw(axes))
-    return engine.process_flows(flows, pov, thr, **_axes_kw(axes))
-
-
 def _axes_kw(axes):
     """axes=True only where it is asked for: an engine without the keyword keeps serving the single script"""
     return {"axes": True} if axes else {}
@@ -724,7 +711,7 @@ def _flow_chunks(engine, chunk_flows, fps, total_frames, params, axes, who):
         raise ValueError(f"{who}: {len(chunk_flows)} chunks of flows for a plan of {len(plan)} chunks")
     out = []
     for chunk, flows in zip(plan, chunk_flows):
-        d, recs = _flow_scalars(engine, flows, params, axes)
+        d, recs = _chunk_scalars(engine, flows, params, axes, run=engine.process_flows)
         if len(d) != len(chunk) - 1:
             raise ValueError(f"{who}: a chunk of {len(chunk)} frames needs {len(chunk) - 1} fields, got {len(d)}")
         out.append((chunk[:-1], d, recs))
@@ -752,20 +739,22 @@ def flows_to_scripts(engine, chunk_flows, fps, total_frames, params):
                                 fps, params)
 
 
-def _chunk_scalars(engine, frames, params, axes=False, **kw):
-    """(dots, records) of one chunk under params: engine.process_chunk, or -- params["hip_pass2"] = "device" -- its device
-    pass 2 with one buffer and one read for the chunk; axes=True: (comps float64[n, 4], records)"""
+def _chunk_scalars(engine, items, params, axes=False, run=None, **kw):
+    """(dots, records) of one chunk under params: `run` -- engine.process_chunk (the default; items: the chunk's frames) or
+    engine.process_flows (its flow fields) -- or, with params["hip_pass2"] = "device", its device pass 2 with one buffer and
+    one read for the chunk; axes=True: (comps float64[n, 4], records).  kw: further keywords of `run`."""
+    run = run or engine.process_chunk
     pov, thr = bool(params.get("pov_mode", False)), float(params.get("cut_threshold", 7))
     cen = center_kwargs(params)
     if cen:   # params["hip_center"]: the device schedule about that centre
-        return _weighted_scalars(engine.process_chunk(frames, pov, thr, **cen, **kw), axes)
+        return _weighted_scalars(run(items, pov, thr, **cen, **kw), axes)
     wts = static_weights(engine, params)
     if wts is not None:   # params["hip_weights"]: the device schedule under the static map
-        return _weighted_scalars(engine.process_chunk(frames, pov, thr, weights=wts, **kw), axes)
+        return _weighted_scalars(run(items, pov, thr, weights=wts, **kw), axes)
     kw.update(_axes_kw(axes))
     if not _pass2_mode(params):
-        return engine.process_chunk(frames, pov, thr, **kw)
-    return post_records(engine.process_chunk(frames, pov, thr, post_out=True, **kw), **_axes_kw(axes))
+        return run(items, pov, thr, **kw)
+    return post_records(run(items, pov, thr, post_out=True, **kw), **_axes_kw(axes))
 
 
 def _frame_chunks(engine, frames, fps, params, axes):

@@ -468,7 +468,7 @@ int ffl_radial_axes(ffl_ctx *ctx, int n, const int *flow_slots, const double *cx
 
 /* ffl_radial_window with ffl_axes_record records: the same windows, cut test, refusals (out_dev must hold n records of 80
  * bytes inside one allocation), stream contract and use of every seq slot; never captured, no host wait.  Its three
- * launches are k_window_plan, k_radial_axes and k_radial_axes_final. */
+ * launches are k_window_plan and the four-component k_radial and k_radial_final. */
 int ffl_radial_window_axes(ffl_ctx *ctx, int n_seq, const int *seq_slots, int first, int n, int radius, float cut_threshold,
                            int pov_mode, ffl_axes_record *out_dev, uint64_t stream);
 
@@ -519,7 +519,7 @@ int ffl_pass1_weighted(ffl_ctx *ctx, int n, const int *flow_slots, const ffl_dev
  * first + i); neighbours contribute their records only.  Windows, the centre mean and the cut test are
  * ffl_radial_window's, from whatever records the seq slots hold -- normally those of ffl_pass1_weighted; unweighted ones
  * are allowed.  The same refusals and stream contract, plus the map rules of ffl_pass1_weighted; out_dev is checked
- * before the maps.  Its three launches are k_window_plan, k_radial_axes_weighted and k_radial_axes_weighted_final. */
+ * before the maps.  Its three launches are k_window_plan and the weighted k_radial and k_radial_final. */
 int ffl_radial_window_axes_weighted(ffl_ctx *ctx, int n_seq, const int *seq_slots, int first, int n, int radius,
                                     float cut_threshold, int pov_mode, const ffl_dev_weights *w, ffl_axes_record *out_dev,
                                     uint64_t stream);
@@ -580,7 +580,8 @@ int ffl_cell_stats(ffl_ctx *ctx, int n, const int *flow_slots, int cells, ffl_ce
  * the four components, the cut rule and the stream contract are ffl_radial_window_axes'.  Further refusals: a NULL or
  * misaligned centres_dev; a stride below 16 or no multiple of 8; centres that are not device memory of the context's
  * device inside one allocation over (n_seq - 1) * stride + 16 bytes (page-locked host memory is refused); out_dev is
- * checked before the centres.  Its three launches are k_window_plan_centres, k_radial_axes and k_radial_axes_final. */
+ * checked before the centres.  Its three launches are k_window_plan over the centres and the four-component k_radial and
+ * k_radial_final. */
 int ffl_radial_window_axes_centres(ffl_ctx *ctx, int n_seq, const int *seq_slots, int first, int n, int radius,
                                    float cut_threshold, int pov_mode, const void *centres_dev, ptrdiff_t centre_stride_bytes,
                                    ffl_axes_record *out_dev, uint64_t stream);

@@ -145,6 +145,24 @@ def test_frames_to_scripts_against_a_fake_engine():
         pipeline.flows_to_scripts(FakeEngine(), chunk_flows[:1], fps, total, PARAMS)
 
 
+@pytest.mark.parametrize("frames", [[], [np.zeros((16, 16), np.uint8)]], ids=["no frame", "one frame"])
+def test_a_chunk_without_pairs_on_the_device_schedule(frames, monkeypatch):
+    """post_out=True, or weights=, which implies it: a buffer for no records (never a negative size), whatever the keyword;
+    without either, empty scalars and no records"""
+    asked = []
+    monkeypatch.setattr(pipeline, "post_buffer", lambda ctx, n, axes=False: asked.append((n, axes)) or ("buffer", n, axes))
+    eng = pipeline.PairEngine.__new__(pipeline.PairEngine)
+    eng.ctx, eng.B = type("Ctx", (), {"width": 16, "height": 16, "device": 0, "flow_slots": 8})(), 4
+    assert eng.process_chunk(frames, post_out=True) == ("buffer", 0, False)
+    assert eng.process_chunk(frames, post_out=True, axes=True) == ("buffer", 0, True)
+    assert eng.process_chunk(frames, weights=object()) == ("buffer", 0, True)      # the maps of no pairs are not looked at
+    assert eng.process_chunk(frames, post_out="mine", weights=object()) == "mine"
+    assert asked == [(0, False), (0, True), (0, True)]
+    for axes, shape in ((False, (0,)), (True, (0, 4))):
+        d, recs = eng.process_chunk(frames, axes=axes)
+        assert d.shape == shape and recs == []
+
+
 def test_script_axes_refusals():
     frames = [np.zeros((48, 64), np.uint8)] * 10
     eng = FakeEngine()

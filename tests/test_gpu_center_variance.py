@@ -1,4 +1,4 @@
-"""GPU side of the centre window over caller centres (ffl_radial_window_axes_centres: k_window_plan_centres) and of the
+"""GPU side of the centre window over caller centres (ffl_radial_window_axes_centres: k_window_plan<80, true>) and of the
 schedule about the variance centre (process_chunk / process_flows with center="variance", params["hip_center"]; DESIGN.md
 section 17): records byte for byte against the composition download_flow -> grid_ref centres -> grid_ref.window ->
 radial_axes, with pass1_results for the fields of a record that still come from the slots."""

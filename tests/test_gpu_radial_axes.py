@@ -274,6 +274,104 @@ def test_shared_post_scratch_between_the_two_forms():
         assert r1 == want["r1"] and r1b == want["r1"] and r4 == want["r4"] and r4b == want["r4"]
 
 
+def test_shared_post_scratch_between_all_eight_users():
+    """The sibling of the test above for every user of stream `post`: radial, radial_axes, radial_window, radial_window_axes,
+    radial_window_axes_weighted (a random uint8 map per item, a fifth of it zeros), cell_stats into a centre buffer (cells =
+    8), radial_window_axes_centres out of that buffer, and pass1_weighted.  They alternate on one context, the device-ordered
+    ones with no host wait in between; nothing is read back before the end.  257x40, three workgroups per item: the partials
+    of item b start at 3 * b (one component), 12 * b (four) and 15 * b (four and SW).  Every result equals, byte for byte, what
+    the same call gives on a context of its own.  pass1_weighted rewrites the slots' records, so it comes last, followed by
+    one radial_window and one radial_window_axes_weighted whose expected bytes come from a fresh context that replays
+    import_flows, pass1_weighted and that call.
+    A context of its own runs the same code, so two exact relations tie the expected bytes to something outside it.  The
+    maps are below 128: doubled maps double every term, every sum and SW exactly, so the quotients by SW keep their bits
+    (a quotient by anything else does not).  And the centres read out of cell_stats' 32-byte records equal the same centres
+    handed over as a float64 (6, 2) tensor, 16 bytes apart."""
+    w, h, cells = 257, 40, 8
+    f = np.stack([field(w, h, 30 + i) for i in range(6)])
+    cen = [(0.3 * w + i, 0.6 * h - i) for i in range(6)]
+    seq = list(range(6))
+    rng = np.random.default_rng(8)
+    maps = rng.integers(1, 128, (6, h, w)).astype(np.uint8)
+    maps[rng.random((6, h, w)) < 0.2] = 0
+    assert all((m == 0).any() and (m != 0).any() for m in maps)
+    wts, wts2 = dev(maps), dev(maps * np.uint8(2))
+    csize = _capi.GRID_CENTRE_DTYPE.itemsize
+
+    def win(ctx, kind, centres=None):
+        out = torch.empty(6 * (ITEM1 if kind == "w1" else ITEM), dtype=torch.uint8, device=DEV)
+        if kind == "w1":
+            ctx.radial_window(seq, 0, 6, out, 2)
+        elif kind == "w4":
+            ctx.radial_window_axes(seq, 0, 6, out, 2)
+        elif kind in ("ww", "ww2"):
+            ctx.radial_window_axes_weighted(seq, 0, 6, wts if kind == "ww" else wts2, out, 2)
+        else:
+            ctx.radial_window_axes_centres(seq, 0, 6, centres, out, 2)
+        return out
+
+    def grid(ctx):
+        out = torch.empty(6 * csize, dtype=torch.uint8, device=DEV)
+        ctx.cell_stats(seq, cells, None, out)
+        return out
+
+    def raw(t):
+        return t.cpu().numpy().tobytes()
+
+    def alone(what, reweight=False):
+        with context(w, h, mb=8) as ctx:
+            ctx.import_flows(dev(f), seq)
+            if reweight:
+                ctx.pass1_weighted(seq, wts)
+            return what(ctx)
+
+    def centred(ctx):
+        g = grid(ctx)
+        rec = np.frombuffer(raw(g), _capi.GRID_CENTRE_DTYPE, 6)
+        plain = dev(np.stack([rec["cx"], rec["cy"]], axis=1))   # float64 (6, 2)
+        return raw(g), raw(win(ctx, "wc", g)), raw(win(ctx, "wc", plain))
+
+    want = {k: alone(lambda c, k=k: raw(win(c, k))) for k in ("w1", "w4", "ww", "ww2")}
+    assert want["ww2"] == want["ww"]
+    want["cs"], want["wc"], plain = alone(centred)
+    assert plain == want["wc"]
+    want["r1"] = alone(lambda c: np.asarray(c.radial(seq, cen, [False] * 6)).tobytes())
+    want["r4"] = alone(lambda c: c.radial_axes(seq, cen, [False] * 6).tobytes())
+    want["p1"] = alone(lambda c: [tuple(r) for r in c.pass1_results(seq)], reweight=True)
+    want["z1"] = alone(lambda c: raw(win(c, "w1")), reweight=True)
+    want["zw"] = alone(lambda c: raw(win(c, "ww")), reweight=True)
+    assert want["cs"] != bytes(len(want["cs"])) and want["ww"] != want["w4"] and want["wc"] != want["w4"] and want["z1"] != want["w1"]
+    got = []   # (key, device tensor or bytes)
+    with context(w, h, mb=8) as ctx:
+        ctx.import_flows(dev(f), seq)
+        got.append(("w4", win(ctx, "w4")))
+        got.append(("ww", win(ctx, "ww")))
+        g1 = grid(ctx)
+        got.append(("wc", win(ctx, "wc", g1)))
+        got.append(("w1", win(ctx, "w1")))
+        got.append(("ww", win(ctx, "ww")))
+        got.append(("r1", np.asarray(ctx.radial(seq, cen, [False] * 6)).tobytes()))
+        g2 = grid(ctx)
+        got.append(("w4", win(ctx, "w4")))
+        got.append(("wc", win(ctx, "wc", g2)))
+        got.append(("ww", win(ctx, "ww")))
+        got.append(("r4", ctx.radial_axes(seq, cen, [False] * 6).tobytes()))
+        got.append(("w1", win(ctx, "w1")))
+        got.append(("wc", win(ctx, "wc", g1)))
+        g3 = grid(ctx)
+        got.append(("w4", win(ctx, "w4")))
+        got.append(("r1", np.asarray(ctx.radial(seq, cen, [False] * 6)).tobytes()))
+        got.append(("r4", ctx.radial_axes(seq[::-1], cen[::-1], [False] * 6)[::-1].tobytes()))
+        got += [("cs", g1), ("cs", g2), ("cs", g3)]
+        ctx.pass1_weighted(seq, wts)
+        got.append(("z1", win(ctx, "w1")))
+        got.append(("zw", win(ctx, "ww")))
+        assert ctx.graph_stats()["capture_failures"] == 0
+        for i, (k, v) in enumerate(got):
+            assert (v if isinstance(v, bytes) else raw(v)) == want[k], (i, k)
+        assert [tuple(r) for r in ctx.pass1_results(seq)] == want["p1"]
+
+
 # ---- refusals -------------------------------------------------------------------------------------------------------------
 class Span:
     """`nbytes` bytes at `ptr` as a __cuda_array_interface__ object, whatever memory that is"""
