@@ -31,6 +31,7 @@ EXPORTS = ["ffl_device_count", "ffl_create", "ffl_destroy", "ffl_last_error", "f
            "ffl_radial_axes", "ffl_radial_window_axes", "ffl_axes_extra_bytes",
            "ffl_dev_weights_check", "ffl_pass1_weighted", "ffl_radial_window_axes_weighted", "ffl_weights_extra_bytes",
            "ffl_cell_grid_check", "ffl_cell_stats", "ffl_radial_window_axes_centres", "ffl_cells_extra_bytes",
+           "ffl_consistency_default_params", "ffl_consistency_params_check", "ffl_consistency_weights",
            "ffl_upload_frames_raw_src", "ffl_upload_frames_yuv_src", "ffl_upload_frames_yuv16_src", "ffl_frontend_yuv_window_src",
            "ffl_frontend_yuv16_window_src", "ffl_dev_frame_check_src", "ffl_dev_frame_check16_src",
            "ffl_upload_frames_device_src", "ffl_upload_frames_device16_src"]
@@ -485,6 +486,38 @@ def dev_weights_check(n, width, height, desc):
         raise ValueError(L.ffl_last_error(None).decode())
 
 
+class ConsistencyParams(C.Structure):
+    """ffl_consistency_params: thr = alpha * (|F|^2 + |B|^2) + beta, soft 1 (a ramp) or 0 (a
+    threshold).  ConsistencyParams() holds the library's defaults; keywords override single fields."""
+    _fields_ = [("alpha", C.c_float), ("beta", C.c_float), ("soft", C.c_int)]
+
+    def __init__(self, **over):
+        super().__init__()
+        load().ffl_consistency_default_params(C.byref(self))
+        for k, v in over.items():
+            if k not in ("alpha", "beta", "soft"):
+                raise ValueError(f"unknown consistency parameter {k!r} (alpha, beta, soft)")
+            setattr(self, k, v)
+
+    def as_dict(self):
+        return {"alpha": self.alpha, "beta": self.beta, "soft": self.soft}
+
+
+def consistency_params_check(params):
+    """ffl_consistency_params_check: ValueError with the library's rule when it refuses (pure host check)."""
+    L = load()
+    if L.ffl_consistency_params_check(None if params is None else C.byref(params)) != FFL_OK:
+        raise ValueError(L.ffl_last_error(None).decode())
+
+
+def consistency_choice(params):
+    """a ConsistencyParams out of None (the defaults), a dict of its fields or a ConsistencyParams; checked"""
+    if not isinstance(params, ConsistencyParams):
+        params = ConsistencyParams(**dict(params or {}))
+    consistency_params_check(params)
+    return params
+
+
 def stream_handle(stream, device=0):
     """hipStream_t of `stream` as an int: None = torch's current stream on `device` when torch is already imported (else
     0, the null stream); a torch.cuda.Stream; or an int as it is."""
@@ -620,6 +653,9 @@ def load():
     L.ffl_radial_window_axes_centres.argtypes = [vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, C.c_ssize_t,
                                                  vp, C.c_uint64]
     L.ffl_cells_extra_bytes.argtypes = [C.c_int] * 3 + [C.POINTER(C.c_size_t)]
+    L.ffl_consistency_default_params.argtypes = [vp]
+    L.ffl_consistency_params_check.argtypes = [vp]
+    L.ffl_consistency_weights.argtypes = [vp, C.c_int, ip, ip, vp, vp, vp, C.c_uint64]
     for name in EXPORTS:   # every _src sibling: the plain call's arguments plus const ffl_source_info *
         if name.endswith("_src"):
             getattr(L, name).argtypes = getattr(L, name[:-4]).argtypes + [vp]
@@ -1112,6 +1148,23 @@ class Context:
         desc = self._weights("radial_window_axes_weighted", weights, n)
         return self._radial_window(self.L.ffl_radial_window_axes_weighted, "radial_window_axes_weighted", PASS2_AXES_DTYPE,
                                    seq_slots, first, n, out, radius, cut_threshold, pov_mode, stream, weights=(C.byref(desc),))
+
+    def consistency_weights(self, fwd_slots, bwd_slots, out, params=None, gate=None, stream=None):
+        """Forward-backward consistency maps (ffl_consistency_weights): item i from the forward field in
+        flow slot fwd_slots[i] and the backward field in bwd_slots[i], written into `out`, a uint8 device tensor (n, H, W)
+        (or a DevWeights; (H, W) for one item).  `params`: a ConsistencyParams, a dict of its fields or None (the defaults);
+        `gate`: maps S of rule K6 as pass1_weighted takes maps, (H, W) or (n, H, W).  Queued behind the work on `stream` and
+        the slots' last users; `stream` waits for it.  Returns `out`."""
+        pf, fs = _iarr(fwd_slots)
+        pb, bs = _iarr(bwd_slots)
+        if len(fs) != len(bs):
+            raise ValueError(f"consistency_weights: {len(fs)} forward slots for {len(bs)} backward slots")
+        prm = params if isinstance(params, ConsistencyParams) else ConsistencyParams(**dict(params or {}))
+        odesc = self._weights("consistency_weights", out, len(fs))
+        gdesc = None if gate is None else self._weights("consistency_weights", gate, len(fs))
+        self._chk(self.L.ffl_consistency_weights(self._h, len(fs), pf, pb, C.byref(prm), None if gdesc is None else C.byref(gdesc),
+                                                 C.byref(odesc), stream_handle(stream, self.device)))
+        return out
 
     def cell_stats(self, flow_slots, cells=32, cells_out=None, centres_out=None, stream=None):
         """The cells x cells grid of regional mean flow, mean magnitude and magnitude variance of every slot and / or its

@@ -2665,7 +2665,72 @@ int ffl_pass1_weighted(ffl_ctx *c, int n, const int *slots, const ffl_dev_weight
     return post_end(c, cst, n, slots);  // the caller may overwrite or free the maps straight after the call
 }
 
-static const char *kHostCentres = "centres live in device memory (ffl_cell_stats' records, or a float64 (n_seq, 2) tensor)";
+// ---- forward-backward consistency maps ----------------------------------------------
+int ffl_consistency_default_params(ffl_consistency_params *out) {
+    if (!out) return FFL_ERR_INVALID;
+    *out = ffl_consistency_params{0.01f, 0.5f, 1};
+    return FFL_OK;
+}
+
+// The accepted parameters of appendix K.  The comparisons are written so that a NaN fails them.
+static int consistency_params_check(ffl_ctx *c, const char *fn, const ffl_consistency_params *p) {
+    if (!p) return set_err(c, FFL_ERR_INVALID, "%s: NULL parameters", fn);
+    if (!(p->alpha >= 0.0f && p->alpha <= 1.0f))
+        return set_err(c, FFL_ERR_INVALID, "%s: alpha = %g outside 0..1 (finite)", fn, (double)p->alpha);
+    if (!(p->beta > 0.0f && p->beta <= 1e6f))
+        return set_err(c, FFL_ERR_INVALID, "%s: beta = %g outside 0 < beta <= 1e6 (finite)", fn, (double)p->beta);
+    if (p->soft != 0 && p->soft != 1) return set_err(c, FFL_ERR_INVALID, "%s: soft = %d is neither 0 (hard) nor 1 (soft)", fn, p->soft);
+    return FFL_OK;
+}
+
+int ffl_consistency_params_check(const ffl_consistency_params *p) {
+    return consistency_params_check(nullptr, "ffl_consistency_params_check", p);
+}
+
+// n maps from n forward and n backward fields by ONE k_consistency launch on stream `post`: ffl_pass1_weighted's protocol
+// over all 2n slots, with the flows and their records only read.
+int ffl_consistency_weights(ffl_ctx *c, int n, const int *fwd_slots, const int *bwd_slots, const ffl_consistency_params *p,
+                            const ffl_dev_weights *gate, const ffl_dev_weights *out, uint64_t stream) {
+    static const char *fn = "ffl_consistency_weights";
+    if (!c) return FFL_ERR_INVALID;
+    std::unique_lock<std::mutex> pl(c->post_mu);  // stream `post`, as ffl_pass1_weighted
+    CtxLock lk(c->mu);
+    if (n < 1 || n > c->max_batch)
+        return set_err(c, FFL_ERR_INVALID, "%s: n = %d items outside 1..%d (the context's max_batch)", fn, n, c->max_batch);
+    if (!fwd_slots || !bwd_slots) return set_err(c, FFL_ERR_INVALID, "%s: NULL %s", fn, !fwd_slots ? "fwd_slots" : "bwd_slots");
+    int all[2 * FFL_MAXB];   // the forward slots, then the backward ones: what the call uses
+    ExportTab tf, tb;
+    for (int i = 0; i < n; i++) {
+        all[i] = tf.slot[i] = fwd_slots[i];
+        all[n + i] = tb.slot[i] = bwd_slots[i];
+    }
+    if (int rc = check_flow_slots(c, fn, 2 * n, all, "flow", "repeated among the forward and backward slots of one call")) return rc;
+    ffl_consistency_params prm;
+    ffl_consistency_default_params(&prm);
+    if (p) prm = *p;
+    if (int rc = consistency_params_check(c, fn, &prm)) return rc;
+    size_t obytes, gbytes = 0;
+    if (!out) return set_err(c, FFL_ERR_INVALID, "%s: NULL out descriptor", fn);
+    if (int rc = dev_weights_check(c, fn, n, c->w, c->h, out, &obytes)) return rc;
+    if (n > 1 && out->item_stride == 0)
+        return set_err(c, FFL_ERR_INVALID, "%s: overlap: out item stride 0 with n = %d maps to write (one map per item)", fn, n);
+    if (gate) {
+        if (int rc = dev_weights_check(c, fn, n, c->w, c->h, gate, &gbytes)) return rc;
+        const uintptr_t o0 = (uintptr_t)out->base, g0 = (uintptr_t)gate->base;
+        if (o0 < g0 + gbytes && g0 < o0 + obytes)
+            return set_err(c, FFL_ERR_INVALID, "%s: overlap: out (%zu bytes) and gate (%zu bytes) share memory", fn, obytes, gbytes);
+    }
+    hipStream_t cst;
+    PostRegion reg[2] = {{"out", out->base, obytes, kHostWeights}, {"the gate maps", gate ? gate->base : nullptr, gbytes, kHostWeights}};
+    if (int rc = post_begin(c, fn, stream, &cst, reg, gate ? 2 : 1, 2 * n, all)) return rc;
+    WeightArgs ga;
+    if (gate) ga = WeightArgs{(const char *)gate->base, (long long)gate->item_stride, (long long)gate->row_pitch};
+    ffl_launch_consistency(c->d_flow, tf, tb, n, c->w, c->h, prm.alpha, prm.beta, prm.soft, gate ? &ga : nullptr, (char *)out->base,
+                           (long long)out->item_stride, (long long)out->row_pitch, c->s_post);
+    return post_end(c, cst, 2 * n, all);  // the caller may read the maps, or overwrite the gate, on `stream` straight after the call
+}
+
+static const char *kHostCentres ="centres live in device memory (ffl_cell_stats' records, or a float64 (n_seq, 2) tensor)";
 
 // What a window call computes: ffl_radial_window (axes = false: ffl_pass2_record) or one of the three ffl_radial_window_axes*
 // (ffl_axes_record).  weighted / centred name the entry point, since a NULL descriptor or NULL centres_dev from the caller

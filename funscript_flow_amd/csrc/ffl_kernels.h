@@ -306,6 +306,13 @@ struct GridCentre {  // = ffl_grid_centre
 void ffl_launch_cell_stats(const float *flow, const ExportTab &tab, int n, int w, int h, int G, CellRecord *cells,
                            GridCentre *centres, double *rowsum, hipStream_t st);
 
+// forward-backward consistency maps (k_consistency): item b's map, from the forward field
+// in flow slot fwd.slot[b] and the backward field in bwd.slot[b], goes to out + b * out_item, rows out_pitch bytes apart; gate
+// (may be NULL): the maps of rule K6
+void ffl_launch_consistency(const float *flow, const ExportTab &fwd, const ExportTab &bwd, int n, int w, int h, float alpha,
+                            float beta, int soft, const WeightArgs *gate, char *out, long long out_item, long long out_pitch,
+                            hipStream_t st);
+
 // ---- index rules shared by the kernel files ----------------------------------------------------------------------
 __device__ __forceinline__ int ffl_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 

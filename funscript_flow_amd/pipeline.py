@@ -242,7 +242,7 @@ class PairEngine:
                                 farneback=farneback, window=window)
 
     def pass1_pairs(self, frames, pairs, slot_of, pov_mode=False, cut_threshold=7.0, on_batch=None, algo=None,
-                    farneback=OWN, window=OWN, queued=None):
+                    farneback=OWN, window=OWN, queued=None, batch=None, reverse_slot_of=None):
         """Pass 1 for an arbitrary ascending list of pair indices (pair j = frames[j], frames[j+1]) in batches of
         max_batch; the flow of the l-th listed pair stays resident in flow slot slot_of(l).  Frames go to the
         device once per run of batches that needs them: a ring over the frame slots, frames of the batch being
@@ -254,8 +254,11 @@ class PairEngine:
         `window` ("box" | "gaussian", as _capi.farneback_mode returns it) their window.
         `queued(local_indices, pair_indices)`: called straight after every batch has been QUEUED; the records are then never
         collected (no pass1_results, no on_batch, no frame release -- the device pass 2 of process_chunk) and the list
-        returned holds None."""
-        ctx, B, S = self.ctx, self.B, self.ctx.frame_slots
+        returned holds None.
+        `batch`: listed pairs per batch (default max_batch).  `reverse_slot_of(l)`: every batch is queued as ONE flow call of
+        its pairs and then the same pairs reversed, (frames[j + 1], frames[j]) -> flow slot reverse_slot_of(l), so the
+        frames' expansions are shared (2 * batch <= max_batch); records and callbacks are those of the forward pairs."""
+        ctx, B, S = self.ctx, (self.B if batch is None else int(batch)), self.ctx.frame_slots
         algo, dis = algo if algo is not None else (getattr(self, "flow", "farneback"), getattr(self, "dis", None))
         fb = getattr(self, "farneback", None) if farneback is OWN else farneback
         win = getattr(self, "window", "box") if window is OWN else window
@@ -292,6 +295,8 @@ class PairEngine:
             js = [pairs[l] for l in ls]
             stage(sorted({j for j in js} | {j + 1 for j in js}))
             f0, f1, fl = [resident[j] for j in js], [resident[j + 1] for j in js], [slot_of(l) for l in ls]
+            if reverse_slot_of is not None:   # forward, then reversed
+                f0, f1, fl = f0 + f1, f1 + f0, fl + [reverse_slot_of(l) for l in ls]
             if algo == "dis":
                 ctx.flow_pairs_dis(f0, f1, fl, pov_mode, dis)
             elif win != "box":
@@ -328,7 +333,8 @@ class PairEngine:
         return recs
 
     def process_chunk(self, frames, pov_mode=False, cut_threshold=7.0, algo=None, farneback=OWN, flows_out=None, window=OWN,
-                      post_out=None, axes=False, weights=None, center=None, cells=32, grid_out=None):
+                      post_out=None, axes=False, weights=None, center=None, cells=32, grid_out=None, consistency=None,
+                      weights_out=None, weights_gate=None):
         """One whole chunk on one GPU: returns (dots float64[n], records) with n = len(frames)-1.  `algo`, `farneback`,
         `window`: see pass1_pairs (default: the engine's own flow algorithm, parameters and window).  `flows_out`: a float32 device array of
         (n, H, W, 2) or (n, 2, H, W) that receives every pair's flow field (Context.export_flows, on torch's current stream)
@@ -350,9 +356,19 @@ class PairEngine:
         `cells` x `cells` grid instead of the |div| argmax.  The chunk then runs the device schedule as
         with weights: post_out defaults to a new buffer, the records are the 80-byte form, and behind each batch
         Context.cell_stats is queued on its slots, then its window calls as Context.radial_window_axes_centres.  `grid_out`:
-        device memory (grid_buffer) that receives every pair's cells x cells cell records.  Not combined with `weights`."""
+        device memory (grid_buffer) that receives every pair's cells x cells cell records.  Not combined with `weights`.
+        `weights` = "consistency": the maps are made on the device by the forward-backward check of every pair (DESIGN.md
+        section 18; `consistency`: a _capi.ConsistencyParams, a dict of its fields or None for the defaults; `weights_gate`:
+        an (H, W) uint8 / bool device tensor, the static gate of rule K6).  A batch is then max_batch // 2 pairs, queued as
+        one flow call of the pairs and the same pairs reversed; behind it Context.consistency_weights, then the calls of
+        `weights`.  The chunk's maps live in one (n, H, W) uint8 device tensor: a new one, or `weights_out`, filled in
+        place.  flows_out still receives the forward fields."""
         ctx, B = self.ctx, self.B
         n = len(frames) - 1
+        cons = _chunk_consistency(self, n, weights, consistency, weights_out, weights_gate)
+        if cons is not None:
+            weights, B = cons.maps, cons.B
+        ring = ctx.flow_slots if cons is None else cons.ring
         maps = weights   # the tensor stays referenced while the calls that read it are queued
         post_out, axes, weights, grid = _chunk_post_args(ctx, n, post_out, axes, weights, center, cells, grid_out,
                                                          check_empty=False)
@@ -367,13 +383,13 @@ class PairEngine:
                 raise ValueError(f"flows_out must be ({n}, {ctx.height}, {ctx.width}, 2) or ({n}, 2, {ctx.height}, "
                                  f"{ctx.width}), got {shp}")
         if post_out is not None:
-            post = _DevicePost(ctx, n, B, pov_mode, cut_threshold, post_out, axes, weights, grid)
+            post = _DevicePost(ctx, n, B, pov_mode, cut_threshold, post_out, axes, weights, grid, ring, cons)
             release = getattr(frames, "release", None)
             marks = []   # (event, frames that have left the host once it completes), oldest first
 
             def queued(ls, js):
                 if layout is not None:   # before the window calls below let later batches recycle these slots
-                    ctx.export_flows([j % ctx.flow_slots for j in js], flows_out[js[0]:js[-1] + 1], layout)
+                    ctx.export_flows([j % ring for j in js], flows_out[js[0]:js[-1] + 1], layout)
                 done = post.after_batch(js[0] // B)
                 if release is None:
                     return
@@ -388,8 +404,9 @@ class PairEngine:
                     ev.synchronize()
                     release(upto)
 
-            self.pass1_pairs(frames, range(n), lambda l: l % ctx.flow_slots, pov_mode, cut_threshold, algo=algo,
-                             farneback=farneback, window=window, queued=queued)
+            self.pass1_pairs(frames, range(n), lambda l: l % ring, pov_mode, cut_threshold, algo=algo,
+                             farneback=farneback, window=window, queued=queued,
+                             **({} if cons is None else {"batch": B, "reverse_slot_of": cons.bwd_slot}))
             if marks:
                 marks[-1][0].synchronize()   # the ring's slots may be reused by the next chunk: every transfer is over
             post.finish()
@@ -416,6 +433,9 @@ class PairEngine:
         weights: the device schedule, 80-byte records, pass1_weighted behind each import).  `center`, `cells`, `grid_out`:
         as in process_chunk (center="variance": the device schedule, 80-byte records, cell_stats behind each import)."""
         ctx, B, fs = self.ctx, self.B, self.ctx.flow_slots
+        if isinstance(weights, str):
+            raise ValueError(f"process_flows: weights={weights!r} needs the backward fields, which a chunk of caller flows does "
+                             "not have; Context.consistency_weights serves callers with their own estimator")
         segs = []   # (descriptor, dtype, first pair, count): one per source array
         n = 0
         for a in (flows if isinstance(flows, (list, tuple)) else [flows]):
@@ -472,6 +492,49 @@ def _chunk_weights(ctx, weights, n):
     return desc
 
 
+WEIGHT_MODES = ("consistency",)   # weights= / params["hip_weights"] as a string: maps the library makes itself
+
+
+class _ChunkConsistency:
+    """What weights="consistency" adds to a chunk of n pairs on `engine` (DESIGN.md section 18): B = max_batch // 2 pairs per
+    batch; the forward fields keep a ring over the first `ring` = flow_slots - (depth + 1) * B flow slots, the backward field
+    of the l-th pair goes to bwd_slot(l) in the region behind it; maps: the chunk's (n, H, W) uint8 device tensor; params: the
+    checked _capi.ConsistencyParams; gate: the static gate's _capi.DevWeights or None (its tensor stays referenced)."""
+
+    def __init__(self, engine, n, params, maps_out, gate):
+        import torch
+        ctx = engine.ctx
+        self.B = ctx.max_batch // 2
+        if self.B < 1:
+            raise ValueError("weights='consistency' needs max_batch >= 2: a batch is max_batch // 2 pairs, queued forward and reversed")
+        self.params = _capi.consistency_choice(params)
+        region = (getattr(engine, "depth", 1) + 1) * self.B
+        self.ring = ctx.flow_slots - region   # >= (depth + 1) * B + 13 on any engine: min_flow_slots(max_batch, depth)
+        self.bwd_slot = lambda l: self.ring + l % region
+        shape = (max(n, 0), ctx.height, ctx.width)
+        if maps_out is None:
+            maps_out = torch.empty(shape, dtype=torch.uint8, device=torch.device("cuda", ctx.device))
+        elif not isinstance(maps_out, torch.Tensor) or maps_out.dtype != torch.uint8 or tuple(maps_out.shape) != shape:
+            raise ValueError(f"weights_out must be a uint8 device tensor of shape {shape}")
+        self.maps = maps_out
+        self.gate_tensor, self.gate = gate, None
+        if gate is not None:
+            self.gate, m = _capi.device_weights(gate, ctx.width, ctx.height)
+            if m != 0:
+                raise ValueError("weights_gate: one static (H, W) map")
+
+
+def _chunk_consistency(engine, n, weights, params, maps_out, gate):
+    """None unless weights names a mode of WEIGHT_MODES; the keywords that belong to it are refused without it"""
+    if not isinstance(weights, str):
+        if params is not None or maps_out is not None or gate is not None:
+            raise ValueError("consistency=, weights_out= and weights_gate= need weights='consistency'")
+        return None
+    if weights not in WEIGHT_MODES:
+        raise ValueError(f"weights must be a device tensor of maps or one of {WEIGHT_MODES}, got {weights!r}")
+    return _ChunkConsistency(engine, n, params, maps_out, gate)
+
+
 def chunk_center(center):
     """center= / params["hip_center"]: None (the |div| argmax of pass 1) or one of _capi.CENTERS"""
     if center is not None and center not in _capi.CENTERS:
@@ -513,6 +576,12 @@ def _chunk_post_args(ctx, n, post_out, axes, weights, center, cells, grid_out, c
     if post_out is True:
         post_out = post_buffer(ctx, max(n, 0), axes)
     return post_out, axes, desc, grid
+
+
+def _no_sharded_weights(weights, who):
+    if weights is not None:
+        raise ValueError(f"{who}: the sharded schedules run unweighted; weights= (maps, or 'consistency') needs "
+                         "PairEngine.process_chunk on one device")
 
 
 def _no_sharded_center(center, who):
@@ -569,11 +638,15 @@ class _DevicePost:
     Context.radial_window_axes_weighted with the maps of their computed pairs.  grid (_chunk_grid's, with axes): after_batch(k)
     first queues Context.cell_stats on batch k's slots, which writes the pairs' centre records into a chunk-long buffer at
     their absolute indices (and their cell records into grid_out), and its calls are Context.radial_window_axes_centres
-    with the centres of their seq read from that buffer -- a neighbour's recycled slot is never re-read for its centre."""
+    with the centres of their seq read from that buffer -- a neighbour's recycled slot is never re-read for its centre.
+    ring: the length of the flow-slot ring the pairs live in (default: every flow slot of the context).  cons (a
+    _ChunkConsistency, with weights = the descriptor of its maps): after_batch(k) first of all queues
+    Context.consistency_weights, which writes batch k's maps from its forward slots and cons.bwd_slot's backward ones."""
 
-    def __init__(self, ctx, n, B, pov_mode, cut_threshold, out, axes=False, weights=None, grid=None):
+    def __init__(self, ctx, n, B, pov_mode, cut_threshold, out, axes=False, weights=None, grid=None, ring=None, cons=None):
         self.ctx, self.pov_mode, self.cut_threshold = ctx, pov_mode, cut_threshold
         self.n, self.B, self.weights, self.grid = n, B, weights, grid
+        self.ring, self.cons = (ctx.flow_slots if ring is None else int(ring)), cons
         self.window, self.item = (ctx.radial_window_axes if axes else ctx.radial_window), _post_dtype(axes).itemsize
         self.base, nbytes = _capi._device_span(out)
         if nbytes < n * self.item:
@@ -585,7 +658,11 @@ class _DevicePost:
 
     def after_batch(self, k):
         """queue batch k's calls; returns the number of leading pairs whose batches these calls have waited for (0: none)"""
-        fs, item, done = self.ctx.flow_slots, self.item, 0
+        fs, item, done = self.ring, self.item, 0
+        if self.cons is not None:   # the batch's maps, before pass1_weighted reads them
+            j0, j1 = k * self.B, min((k + 1) * self.B, self.n)
+            self.ctx.consistency_weights([j % fs for j in range(j0, j1)], [self.cons.bwd_slot(j) for j in range(j0, j1)],
+                                         self._maps(j0), self.cons.params, self.cons.gate, self.stream)
         if self.weights is not None:   # the batch's records under the maps, before any window call reads them
             j0, j1 = k * self.B, min((k + 1) * self.B, self.n)
             self.ctx.pass1_weighted([j % fs for j in range(j0, j1)], self._maps(j0), self.pov_mode, self.stream)
@@ -670,17 +747,35 @@ def _scripts_from_chunks(chunks, extra, fps, params):
 def static_weights(engine, params):
     """params["hip_weights"], an (H, W) uint8 / bool numpy array or torch tensor, as a device tensor on the engine's
     device: the static weight map of every pair; None without the key."""
-    w = params.get("hip_weights")
+    return _static_map(engine, params, "hip_weights")
+
+
+def _static_map(engine, params, key):
+    """params[key] as an (H, W) uint8 / bool device tensor on the engine's device; None without the key"""
+    w = params.get(key)
     if w is None:
         return None
     import torch
     t = w if isinstance(w, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(w))
     if t.dtype not in (torch.uint8, torch.bool):
-        raise ValueError(f"hip_weights: dtype {t.dtype} is not supported, weight maps are uint8 or bool")
+        raise ValueError(f"{key}: dtype {t.dtype} is not supported, weight maps are uint8 or bool")
     ctx = engine.ctx
     if tuple(t.shape) != (ctx.height, ctx.width):
-        raise ValueError(f"hip_weights: shape {tuple(t.shape)} is not (H, W) = ({ctx.height}, {ctx.width})")
+        raise ValueError(f"{key}: shape {tuple(t.shape)} is not (H, W) = ({ctx.height}, {ctx.width})")
     return t.to(torch.device("cuda", ctx.device)).contiguous()
+
+
+def consistency_kwargs(engine, params):
+    """The keywords of process_chunk when params["hip_weights"] names a mode of WEIGHT_MODES -- params["hip_consistency"] (a dict
+    of _capi.ConsistencyParams fields) and params["hip_weights_gate"] (a static (H, W) map) go with it -- else {}; the two
+    further keys are refused without it."""
+    if not isinstance(params.get("hip_weights"), str):
+        for key in ("hip_consistency", "hip_weights_gate"):
+            if params.get(key) is not None:
+                raise ValueError(f"{key} needs hip_weights = 'consistency'")
+        return {}
+    return {"weights": params["hip_weights"], "consistency": params.get("hip_consistency"),
+            "weights_gate": _static_map(engine, params, "hip_weights_gate")}
 
 
 def center_kwargs(params):
@@ -707,6 +802,9 @@ def _axes_kw(axes):
 
 def _flow_chunks(engine, chunk_flows, fps, total_frames, params, axes, who):
     plan = pair_plan(fps, total_frames, params)
+    if isinstance(params.get("hip_weights"), str):
+        raise ValueError(f"{who}: hip_weights = {params['hip_weights']!r} needs the backward fields, which caller flows do not "
+                         "have; Context.consistency_weights serves callers with their own estimator")
     if len(chunk_flows) != len(plan):
         raise ValueError(f"{who}: {len(chunk_flows)} chunks of flows for a plan of {len(plan)} chunks")
     out = []
@@ -748,6 +846,9 @@ def _chunk_scalars(engine, items, params, axes=False, run=None, **kw):
     cen = center_kwargs(params)
     if cen:   # params["hip_center"]: the device schedule about that centre
         return _weighted_scalars(run(items, pov, thr, **cen, **kw), axes)
+    ckw = consistency_kwargs(engine, params)
+    if ckw:   # params["hip_weights"] = "consistency": the device schedule under maps made from the chunk's own flow
+        return _weighted_scalars(run(items, pov, thr, **ckw, **kw), axes)
     wts = static_weights(engine, params)
     if wts is not None:   # params["hip_weights"]: the device schedule under the static map
         return _weighted_scalars(run(items, pov, thr, weights=wts, **kw), axes)
@@ -829,7 +930,7 @@ def _no_sharded_axes(axes, who):
 
 
 def process_chunk_sharded(engine, frames, rank, world, allgather, pov_mode=False, cut_threshold=7.0,
-                          assign="contiguous", block=1, axes=False, center=None):
+                          assign="contiguous", block=1, axes=False, center=None, weights=None):
     """Multi-GPU form of one chunk: rank r owns the pairs shard_pairs(n, world, r, assign, block).
 
     `engine` provides pass1(frames, pair_indices, pov_mode, cut_threshold) -> records (its l-th listed pair is
@@ -840,6 +941,7 @@ def process_chunk_sharded(engine, frames, rank, world, allgather, pov_mode=False
     axes=True is refused: the sharded schedules keep the single component."""
     _no_sharded_axes(axes, "process_chunk_sharded")
     _no_sharded_center(center, "process_chunk_sharded")
+    _no_sharded_weights(weights, "process_chunk_sharded")
     n = len(frames) - 1
     mine = shard_pairs(n, world, rank, assign, block)
     allrecs = _merge_records(allgather(_shard_pass1(engine, frames, mine, pov_mode, cut_threshold)), n)
@@ -856,7 +958,7 @@ def halo_rows(rows, radius=SMOOTH_RADIUS):
 
 
 def process_chunk_sharded_halo(engine, frames, rank, world, allgather, pov_mode=False, cut_threshold=7.0, axes=False,
-                               center=None):
+                               center=None, weights=None):
     """Streaming multi-GPU form of one chunk for CONTIGUOUS blocks: the only exchange between the passes is the halo.
 
     process_chunk_sharded gathers every pass-1 record of the chunk before any pass 2 starts, so all ranks idle until the
@@ -875,6 +977,7 @@ def process_chunk_sharded_halo(engine, frames, rank, world, allgather, pov_mode=
     rank.  axes=True is refused, as in process_chunk_sharded."""
     _no_sharded_axes(axes, "process_chunk_sharded_halo")
     _no_sharded_center(center, "process_chunk_sharded_halo")
+    _no_sharded_weights(weights, "process_chunk_sharded_halo")
     n = len(frames) - 1
     R = SMOOTH_RADIUS
     lo, hi = shard_range(n, world, rank)
@@ -938,12 +1041,13 @@ def process_chunk_sharded_halo(engine, frames, rank, world, allgather, pov_mode=
 
 
 def process_chunk_local_ranks(engines, frames, pov_mode=False, cut_threshold=7.0, assign="contiguous", block=1, axes=False,
-                              center=None):
+                              center=None, weights=None):
     """The same schedule with every rank driven from THIS process (one engine / context per device, or several
     contexts on one device): phase by phase, no process group.  Equivalent to world = len(engines) processes
     running process_chunk_sharded (axes=True is refused there and here)."""
     _no_sharded_axes(axes, "process_chunk_local_ranks")
     _no_sharded_center(center, "process_chunk_local_ranks")
+    _no_sharded_weights(weights, "process_chunk_local_ranks")
     n, world = len(frames) - 1, len(engines)
     mine = [shard_pairs(n, world, r, assign, block) for r in range(world)]
     allrecs = _merge_records([_shard_pass1(e, frames, m, pov_mode, cut_threshold) for e, m in zip(engines, mine)], n)

@@ -36,6 +36,9 @@
  *                           
  *   ffl_radial_window_axes_centres  ffl_radial_window_axes with the centre list of FF:1203-1214 read from device memory:
  *                           the variance centres of ffl_cell_stats, or any other estimator's
+ *   ffl_consistency_weights replaces nothing (the reference's detect_cut is dead and nothing in it weights pixels): the
+ *                           forward-backward check of a pair's two fields as a weight map for ffl_pass1_weighted and
+ *                           ffl_radial_window_axes_weighted
  *   ffl_download_flow       the "flow" entry of that dict (tests / callers that want the array)
  *   ffl_upload_frames_device  ffl_upload_frames_raw / _yuv / ffl_upload_frames for frames already in device memory (a GPU
  *                           decoder's surfaces, torch tensors); ffl_export_flows: ffl_download_flow into device memory
@@ -528,6 +531,45 @@ int ffl_radial_window_axes_weighted(ffl_ctx *ctx, int n_seq, const int *seq_slot
  * ffl_destroy: FFL_N_AXES + 1 partial sums per workgroup of the radial grid for FFL_MAX_BATCH items, which pass 1's one
  * extra partial per workgroup shares (ffl_estimate_bytes does not count it).  Needs no device. */
 int ffl_weights_extra_bytes(int width, int height, size_t *bytes);
+
+/* ---- Forward-backward consistency weight maps ----
+ * A confidence map of the flow itself, made on the device in the form rules W1 to W6 consume: follow the forward flow F
+ * (pair f0 -> f1, components u, v) from a pixel, read the backward flow B (pair f1 -> f0) there, and see whether the two
+ * cancel.  Both fields are resident flow slots of the context's size w x h.  All arithmetic is float32, one rounding per
+ * written operation, no contraction.  For pixel (x, y):
+ *   K1  landing: px = (float)x + u, py = (float)y + v; inside = px >= 0 && px <= (float)(w-1) && py >= 0 && py <= (float)(h-1)
+ *       (a NaN or inf fails the test).  Not inside: W = 0, and nothing of B is read for that pixel.
+ *   K2  sample: x0 = (int)floorf(px), x1 = min(x0 + 1, w - 1), ax = px - floorf(px), the same in y.  Per component of B with
+ *       corners b00 = B[y0][x0], b01 = B[y0][x1], b10 = B[y1][x0], b11 = B[y1][x1]:  t = b00 + ax*(b01 - b00),
+ *       s = b10 + ax*(b11 - b10), bc = t + ay*(s - t); this yields bu, bv.
+ *   K3  ex = u + bu, ey = v + bv, e2 = ex*ex + ey*ey;  thr = alpha*((u*u + v*v) + (bu*bu + bv*bv)) + beta.
+ *   K4  soft = 1: q = 1 - e2 / thr; q = q > 0 ? q : 0 (a select: a NaN gives 0); W = (int)(q*255 + 0.5f).
+ *   K5  soft = 0: W = e2 < thr ? 255 : 0.  No division is executed.
+ *   K6  with a gate map S (a weight descriptor, the rules of any map): W = min(W, S).
+ * Accepted: 0 <= alpha <= 1, 0 < beta <= 1e6, both finite, soft in {0, 1}; the defaults are 0.01, 0.5, 1.  Non-finite
+ * fields follow the IEEE result of these expressions; a NaN anywhere in a pixel's chain gives 0. */
+typedef struct ffl_consistency_params {
+    float alpha, beta;
+    int soft;
+} ffl_consistency_params;
+int ffl_consistency_default_params(ffl_consistency_params *out);
+/* Pure host check: no device or context needed.  FFL_ERR_INVALID with the rule in ffl_last_error(NULL). */
+int ffl_consistency_params_check(const ffl_consistency_params *p);
+
+/* The maps of n pairs of fields: item i is made from the forward field in flow slot fwd_slots[i] and the backward field in
+ * bwd_slots[i].  `out` describes the n maps the call WRITES (the descriptor type is reused: base is written through, byte
+ * (x, y) of item i at base + i*item_stride + y*row_pitch + x; bytes between rows and items are left alone); `gate` (NULL: none)
+ * the maps S of rule K6, item_stride 0 for one static gate; p NULL: the defaults.  Refused before any device work, each with
+ * its rule in the message: n outside 1..max_batch; a NULL list; a slot out of range, or repeated among the 2n; a slot that
+ * holds no flow (FFL_ERR_STATE); any rule of ffl_consistency_params_check; any rule of ffl_dev_weights_check for out and for
+ * gate; out with item_stride == 0 when n > 1; out or gate that is not device memory of the context's device inside one
+ * allocation; out overlapping gate; a capturing `stream` (FFL_ERR_STATE).
+ * ffl_pass1_weighted's protocol: ONE k_consistency launch, queued on the library's stream behind the work queued on
+ * `stream` and the last users of all 2n slots; `stream` then waits for it, so the maps may be read, and the gate
+ * overwritten, on `stream` straight after the call; it counts as a use of all 2n slots; never captured; the host does not
+ * wait.  Flows and pass-1 records are only read.  No scratch memory: there is no *_extra_bytes call. */
+int ffl_consistency_weights(ffl_ctx *ctx, int n, const int *fwd_slots, const int *bwd_slots, const ffl_consistency_params *p,
+                            const ffl_dev_weights *gate, const ffl_dev_weights *out, uint64_t stream);
 
 /* ---- Per-cell flow statistics and the variance centre ----
  * center_of_mass_variance(flow, num_cells) of FF:721-746 and the grid it is formed from, on resident flow fields.  With
