@@ -1,13 +1,13 @@
 // C ABI (include/ffl.h) of the gfx950 pair-motion path: context, slots, streams, batch schedule.
 //
 // Streams: `copy` carries the pinned H2D frame transfers (+ the BGR->gray kernel); every compute lane
-// has its own stream (+ side streams for the optional run-ahead schedules) and work buffers; `post`
-// carries pass 2.  A batch waits on its frames' upload events; an upload into a frame slot waits on
-// the batch events of the lanes that last read it; each batch records ONE event that stands for "slots
-// ready / frames released / lane buffers free".  Result records are stored by the reduction kernels
-// straight into mapped pinned memory, so no tiny D2H copies are queued.  No host synchronisation
-// happens inside ffl_upload_frame / ffl_flow_pairs, so uploads of the next frames overlap the kernels
-// of the previous batch (north_star: "staged to HBM via pinned hipMemcpyAsync on a side stream").
+// has its own stream and work buffers; `post` carries pass 2.  A batch waits on its frames' upload
+// events; an upload into a frame slot waits on the batch events of the lanes that last read it; each
+// batch records ONE event that stands for "slots ready / frames released / lane buffers free".  Result
+// records are stored by the reduction kernels straight into mapped pinned memory, so no tiny D2H
+// copies are queued.  No host synchronisation happens inside ffl_upload_frame / ffl_flow_pairs, so
+// uploads of the next frames overlap the kernels of the previous batch (north_star: "staged to HBM via
+// pinned hipMemcpyAsync on a side stream").
 #include "../../include/ffl.h"
 #include "ffl_kernels.h"
 
@@ -58,8 +58,6 @@ static thread_local std::string g_create_error = "";
 // The process-wide option set (ffl_set_option): the defaults of contexts created AFTERWARDS.  Every context copies it at
 // ffl_create (ffl_ctx::opt) and is from then on only changed through ffl_ctx_set_option, which bumps that context's own
 // graph epoch -- two contexts of one process (one per GPU) share no knob and do not invalidate each other's graphs.
-//   run_ahead   schedule of the frame-only kernels (see enqueue_batch).  Measured at 1080p, B = 8 (pairs/s with 1 / 2
-//               lanes): 0 serial 3840 / 4063, 2 fork-join 3641 / 4101, 1 run-ahead 3943 / 4159.
 //   fuse_first  a level's initial UpdateMatrices runs inside its first blur+solve launch when the level has at least this
 //               many 64x16 tiles over the batch (0: never).  The folded launch saves an M write + read but runs its extra
 //               phase at 3 workgroups per CU: worth it only where the launch is long enough to be bandwidth-bound (1080p,
@@ -264,11 +262,6 @@ struct ffl_ctx {
     // filter with another's bandwidth-bound UpdateMatrices / PolyExp.
     struct Lane {
         Stream st;
-        // Frame-only work (pyramid + PolyExp of every level) runs ahead on `st_aux` and overlaps the
-        // flow chain of the coarser levels, whose small grids leave most of the device idle; the
-        // chain on `st` waits for ev_R[k] before touching level k.  R holds all levels at once.
-        Stream st_aux[4];
-        Event ev_R[8], ev_fork;
         EvRing ring;  // one "batch finished" event per batch (FFL_EV_RING entries)
         DevBuf<float> d_gen;  // general-path work area (ffl_flow_pairs_farneback), allocated when d_R is too small
         size_t gen_cap = 0;   // its floats: the largest request seen
@@ -906,12 +899,7 @@ static int create_resources(ffl_ctx *c) {
     c->lanes.resize(num_lanes);
     for (auto &L : c->lanes) {
         HIPCHK(nullptr, hipStreamCreateWithFlags(L.st.put(), hipStreamNonBlocking));
-        // st_aux (run-ahead / fork-join schedules only) are created on first use: HIP multiplexes streams
-        // onto a few hardware queues, and idle extra streams make the latency-critical `post` / `copy`
-        // streams share a queue with a compute lane (pass 2 then waits behind whole queued batches)
-        HIPCHK(nullptr, hipEventCreateWithFlags(L.ev_fork.put(), hipEventDisableTiming));
         HIPCHK(nullptr, L.ring.create(FFL_EV_RING));
-        for (int k = 0; k <= geo.levels; k++) HIPCHK(nullptr, hipEventCreateWithFlags(L.ev_R[k].put(), hipEventDisableTiming));
         HIPCHK_ALLOC(nullptr, hipMalloc, L.d_I, lay.I);
         HIPCHK_ALLOC(nullptr, hipMalloc, L.d_T, lay.T);
         HIPCHK_ALLOC(nullptr, hipMalloc, L.d_R, lay.R);
@@ -1461,65 +1449,28 @@ struct DebugCapture {
 
 // The launches of one batch (frame expansion, the level loop, pass 1) on the lane's stream.  Everything that
 // differs between two batches of the same shape is read by the kernels from the lane's device table, so this
-// sequence can be captured into a hipGraph (cap == nullptr, no timing events, serial schedule).
+// sequence can be captured into a hipGraph (cap == nullptr, no timing events).
 static int enqueue_batch(ffl_ctx *c, ffl_ctx::Lane &L, const BatchTab &T, int n, int nU, int pov_mode, const DebugCapture *cap) {
     hipStream_t st = L.st;
     const size_t N = c->N;
     const UTab *ut = &L.d_tab->ut;
     const PairTab *pt = &L.d_tab->pt;
-    // frame-only expansion of level k (level image + PolyExp of the nU unique frames) on stream s
-    auto pyr_level = [&](int k, hipStream_t s) { ffl_launch_pyr_level(c->d_gray, N, ut, nU, L.pyr[c->geo.levels - k], s); };
-    auto expand_level = [&](int k, hipStream_t s) {
-        {
-            ProfScope ps(c, FFL_K_PYRAMID, s);
-            pyr_level(k, s);
-        }
-        {
-            ProfScope ps(c, FFL_K_POLYEXP, s);
-            ffl_launch_polyexp(L.poly[c->geo.levels - k], nU, c->pc, s);
-        }
-    };
-    // Frame-only expansion schedule (ffl_set_option "run_ahead"):
-    //   0  serial, on the lane's stream, level by level (also used for debug capture)
-    //   2  fork/join: the 4 levels expand concurrently on side streams (their small grids and serial
-    //      LDS phases leave most of the device idle when run one after the other), and the flow chain
-    //      starts only after all of them -- it is never co-scheduled with anything
-    //   1  run-ahead: one side stream, the chain waits per level, so coarse-level flow kernels overlap
-    //      the finer levels' expansion (fastest with one lane, but stretches those launches)
-    const int mode = cap ? 0 : c->opt.run_ahead;
-    if (mode) {
-        for (int k = 0; k < (mode == 2 ? 4 : 1); k++)
-            if (!L.st_aux[k]) HIPCHK(c, hipStreamCreateWithFlags(L.st_aux[k].put(), hipStreamNonBlocking));
-        HIPCHK(c, hipEventRecord(L.ev_fork, st));  // after the uploads and after the lane's previous batch
-        for (int k = c->geo.levels; k >= 0; k--) {
-            hipStream_t sa = L.st_aux[mode == 2 ? k : 0];
-            if (mode == 2 || k == c->geo.levels) HIPCHK(c, hipStreamWaitEvent(sa, L.ev_fork, 0));
-            expand_level(k, sa);
-            HIPCHK(c, hipEventRecord(L.ev_R[k], sa));
-        }
-        if (mode == 2)
-            for (int k = c->geo.levels; k >= 0; k--) HIPCHK(c, hipStreamWaitEvent(st, L.ev_R[k], 0));
+    // The frame-only work (level images + PolyExp of the nU unique frames) of ALL levels up front in three launches
+    // (pyramid phase A + B, PolyExp) instead of ten small ones whose ramps and tails leave the device idle.
+    // fuse_l0_blur: PolyExp forms level 0's image (the last job) from the gray frame, so nothing reads that level's I
+    // plane but the debug capture, and the pyramid leaves the level out unless one is running
+    const PyrJob *l0 = &L.pyr[L.n_jobs - 1];
+    const bool fuse_l0 = c->opt.fuse_l0_blur && ffl_polyexp_from_gray_ok(*l0);
+    const int skip_l0 = fuse_l0 && !cap;
+    {
+        ProfScope ps(c, FFL_K_PYRAMID, st);
+        if (!ffl_launch_pyr_multi(c->d_gray, N, ut, nU, L.pyr, L.n_jobs - skip_l0, c->opt, st))
+            for (int k = c->geo.levels; k >= skip_l0; k--)  // a level outside the merged kinds: per-level kernels
+                ffl_launch_pyr_level(c->d_gray, N, ut, nU, L.pyr[c->geo.levels - k], st);
     }
-    const bool run_ahead = mode == 1;
-    bool expanded = mode != 0;
-    if (mode == 0 && c->opt.merge_expand) {
-        // serial schedule, merged form: the frame-only work of ALL levels up front in three launches
-        // (pyramid phase A + B, PolyExp) instead of ten small ones whose ramps and tails leave the device idle
-        // fuse_l0_blur: PolyExp forms level 0's image (the last job) from the gray frame, so nothing reads that level's I
-        // plane but the debug capture, and the pyramid leaves the level out unless one is running
-        const PyrJob *l0 = &L.pyr[L.n_jobs - 1];
-        const bool fuse_l0 = c->opt.fuse_l0_blur && ffl_polyexp_from_gray_ok(*l0);
-        const int skip_l0 = fuse_l0 && !cap;
-        {
-            ProfScope ps(c, FFL_K_PYRAMID, st);
-            if (!ffl_launch_pyr_multi(c->d_gray, N, ut, nU, L.pyr, L.n_jobs - skip_l0, c->opt, st))
-                for (int k = c->geo.levels; k >= skip_l0; k--) pyr_level(k, st);  // a level outside the merged kinds: per-level kernels
-        }
-        {
-            ProfScope ps(c, FFL_K_POLYEXP, st);
-            ffl_launch_polyexp_multi(L.poly, L.n_jobs, nU, c->pc, c->d_gray, N, ut, fuse_l0 ? l0 : nullptr, st);
-        }
-        expanded = true;
+    {
+        ProfScope ps(c, FFL_K_POLYEXP, st);
+        ffl_launch_polyexp_multi(L.poly, L.n_jobs, nU, c->pc, c->d_gray, N, ut, fuse_l0 ? l0 : nullptr, st);
     }
 
     int pw = 0, ph = 0;
@@ -1533,8 +1484,6 @@ static int enqueue_batch(ffl_ctx *c, ffl_ctx::Lane &L, const BatchTab &T, int n,
         // so) and the debug capture, so it is only materialised for the latter
         if (pw == 0 && cap)
             for (int i = 0; i < n; i++) HIPCHK(c, hipMemsetAsync(T.pt.flow[k][i], 0, sizeof(float) * 2 * plane, st));
-        if (run_ahead) HIPCHK(c, hipStreamWaitEvent(st, L.ev_R[k], 0));
-        else if (!expanded) expand_level(k, st);
         int mi = 0;
         // fuse_first: the level's initial UpdateMatrices (and flow upsample) run inside the first blur+solve
         // launch; the debug capture wants the initial flow and M in memory, so it keeps the separate launch
@@ -1684,7 +1633,7 @@ static int queue_batch(ffl_ctx *c, ffl_ctx::Lane &L, BatchTab &T, int *nU_out, i
         }
         ProfScope ps(c, FFL_K_PASS1, st);
         ffl_launch_pass1(&L.d_tab->pt, n, c->w, c->h, pov_mode, L.d_pkey, L.d_psum, st);
-    } else if (c->opt.use_graph && !cap && c->prof_mask == 0 && c->opt.run_ahead == 0) {
+    } else if (c->opt.use_graph && !cap && c->prof_mask == 0) {
         ffl_ctx::Lane::GraphEntry *ge;
         if (int rc = batch_graph(c, L, T, n, nU, pov_mode, &ge)) return rc;
         if (ge) {
@@ -2942,8 +2891,8 @@ int ffl_import_flows(ffl_ctx *c, int n, const int *slots, const ffl_dev_flow *f,
                        (long long)f->channel_stride, c->d_flow, c->d_res};
     {
         ProfScope ps(c, FFL_K_PASS1, c->s_post);
-        ffl_launch_import_pass1(a, t, n, dtype, mode, c->w, c->h, pov_mode ? 1 : 0, c->opt.import_fused, c->d_ptab, c->d_pskey,
-                                c->d_rpsum, c->s_post);
+        ffl_launch_import_pass1(a, t, n, dtype, mode, c->w, c->h, pov_mode ? 1 : 0, c->d_ptab, c->d_pskey, c->d_rpsum,
+                                c->s_post);
     }
     return post_end(c, cst, n, slots);  // the caller's later work (overwriting or freeing the sources) runs after the fields have been read
 }
@@ -3011,9 +2960,17 @@ int ffl_sync(ffl_ctx *c) {
 }
 
 // one knob of an option set, described by its row of kFflOptionRows; `live`: the set belongs to an existing context (its
-// lane count is fixed).  The two knobs that are more than a row: "blur_tile_h" is fixed at 16 (the box-sum order is
-// anchored to blocks of 16 rows) and is no member of the set; "lanes" is a property of a live context's buffers.
-static const char kFixedTileH[] = "blur_tile_h";
+// lane count is fixed).  What is more than a row: the fixed knobs, names that accept and read back one value and are no
+// member of the set ("blur_tile_h": the box-sum order is anchored to blocks of 16 rows; "run_ahead" and "merge_expand":
+// the frame-only kernels have one schedule, serial in the merged launches); "lanes" is a property of a live context's
+// buffers.
+static constexpr struct { const char *name; int value; } kFixedKnobs[] = {
+    {"blur_tile_h", 16}, {"run_ahead", 0}, {"merge_expand", 1}};
+static const int *fixed_knob(const char *name) {
+    for (const auto &k : kFixedKnobs)
+        if (!strcmp(name, k.name)) return &k.value;
+    return nullptr;
+}
 static const FflOptionRow *option_row(const char *name) {
     for (const FflOptionRow &r : kFflOptionRows)
         if (!strcmp(name, r.name)) return &r;
@@ -3021,7 +2978,7 @@ static const FflOptionRow *option_row(const char *name) {
 }
 
 static int set_option_impl(FflOptions &o, const char *name, int value, bool live) {
-    if (!strcmp(name, kFixedTileH)) return value == 16 ? FFL_OK : FFL_ERR_INVALID;
+    if (const int *fixed = fixed_knob(name)) return value == *fixed ? FFL_OK : FFL_ERR_INVALID;
     const FflOptionRow *r = option_row(name);
     if (!r || value < r->lo || value > r->hi) return FFL_ERR_INVALID;
     if (live && r->member == &FflOptions::lanes) return value == o.lanes ? FFL_OK : FFL_ERR_STATE;
@@ -3030,9 +2987,10 @@ static int set_option_impl(FflOptions &o, const char *name, int value, bool live
 }
 
 static int get_option_impl(const FflOptions &o, const char *name, int *value) {
+    const int *fixed = fixed_knob(name);
     const FflOptionRow *r = option_row(name);
-    if (!r && strcmp(name, kFixedTileH)) return FFL_ERR_INVALID;
-    *value = r ? o.*r->member : 16;
+    if (!fixed && !r) return FFL_ERR_INVALID;
+    *value = fixed ? *fixed : o.*r->member;
     return FFL_OK;
 }
 

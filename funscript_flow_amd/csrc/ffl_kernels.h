@@ -146,9 +146,7 @@ struct PolyJobs {
 // process (one per GPU, or several on one device) neither share a knob nor invalidate each other's captured graphs.
 struct FflOptions {
     int lanes = 2;          // compute lanes (co-scheduled batches) -- fixed once the context exists
-    int run_ahead = 0;      // schedule of the frame-only kernels: 0 serial, 1 run-ahead, 2 fork/join
     int fuse_first = 10000; // minimum tiles x pairs of a level for the folded first blur+solve launch (0: never)
-    int merge_expand = 1;   // pyramid + PolyExp of all levels in three merged launches
     int use_graph = 1;      // replay a batch's launches from a captured hipGraph
     int copy_threads = 4;   // host threads sharing a staging copy
     int blur_rows = 0;      // tiles a k_blur_solve workgroup walks down (0: automatic)
@@ -157,7 +155,6 @@ struct FflOptions {
     int pyr_coarse = 1;     // one-pass kernel for the x1/4 and x1/8 pyramid levels where sizes allow
     int fuse_l0_blur = 1;   // merged expansion: PolyExp forms level 0's image from the gray frame itself; its I plane is not written
     int fb_general = 0;     // 1: ffl_flow_pairs_farneback runs the reference's parameters through the general kernels too
-    int import_fused = 1;   // ffl_import_flows: 1 k_import_pass1 (conversion + pass 1 in one read), 0 conversion, then pass 1
 };
 // The knobs by name (host only; ffl_api.hip sets and reads them through this table): accepted values lo..hi, and `flag`
 // when any value is accepted and stored as != 0.  A new knob is a member above and a row here.
@@ -169,9 +166,7 @@ struct FflOptionRow {
 };
 inline constexpr FflOptionRow kFflOptionRows[] = {
     {"lanes", &FflOptions::lanes, 1, 4, false},
-    {"run_ahead", &FflOptions::run_ahead, 0, 2, false},
     {"fuse_first", &FflOptions::fuse_first, 0, INT_MAX, false},
-    {"merge_expand", &FflOptions::merge_expand, INT_MIN, INT_MAX, true},
     {"graph", &FflOptions::use_graph, INT_MIN, INT_MAX, true},
     {"copy_threads", &FflOptions::copy_threads, 1, 16, false},
     {"blur_rows", &FflOptions::blur_rows, 0, 64, false},
@@ -180,7 +175,6 @@ inline constexpr FflOptionRow kFflOptionRows[] = {
     {"pyr_coarse", &FflOptions::pyr_coarse, INT_MIN, INT_MAX, true},
     {"fuse_l0_blur", &FflOptions::fuse_l0_blur, INT_MIN, INT_MAX, true},
     {"fb_general", &FflOptions::fb_general, 0, 1, false},
-    {"import_fused", &FflOptions::import_fused, 0, 1, false},
 };
 
 // ---- launchers (each enqueues on `st` and returns; no synchronisation) ----------------------
@@ -198,16 +192,15 @@ void ffl_launch_frontend_dev(const FrameDesc *tab, int n, uint8_t *gray_base, si
 void ffl_launch_export_flows(const float *flow, const ExportTab &tab, int n, size_t N, char *dst, long long item_stride,
                              int layout, hipStream_t st);
 // n (<= FFL_MAXB) caller fields -> flow slots tab.slot[0..n) + their pass-1 records (through pt, which the import fills);
-// fused = 0: the two-launch form (conversion kernel, then ffl_launch_pass1); dtype FFL_IMP_*, mode FFL_IMP_* (host-checked)
+// dtype FFL_IMP_*, mode FFL_IMP_* (host-checked)
 void ffl_launch_import_pass1(const ImportArgs &a, const ExportTab &tab, int n, int dtype, int mode, int w, int h, int pov_mode,
-                             int fused, PairTab *pt, unsigned long long *pkey, double *psum, hipStream_t st);
+                             PairTab *pt, unsigned long long *pkey, double *psum, hipStream_t st);
 void ffl_launch_gray(const uint8_t *bgr, uint8_t *gray, int n_pixels, hipStream_t st);
 size_t ffl_pyr_tmp_floats(int w, int h, int lw);  // per-frame size of the level's horizontal-pass buffer
 // one level on its own; ffl_pyr_level_ok: the level has one of the forms this serves (checked by ffl_create)
 bool ffl_pyr_level_ok(int w, int h, int lw, int lh, int ksize);
 void ffl_launch_pyr_level(const uint8_t *gray_base, size_t gray_stride, const UTab *ut, int nU, const PyrJob &level,
                           hipStream_t st);
-void ffl_launch_polyexp(const PolyJob &level, int nU, PolyConsts pc, hipStream_t st);
 // pw > 0: the level's initial flow = x2 bilinear upsample of pt.prev (pw x ph), used from registers (and written
 // to pt.flow only when store_flow != 0: nothing but the debug capture reads it);
 // pw == 0: the flow is read from pt.flow, or taken as zero without touching memory when zero_flow != 0

@@ -831,10 +831,6 @@ __device__ __forceinline__ void k_polyexp_body(const unsigned bx, const unsigned
         }
     }
 }
-__global__ __launch_bounds__(256) void k_polyexp(const float *__restrict__ I, size_t I_stride, float *__restrict__ R,
-                                                 size_t R_stride, size_t plane, int w, int h, PolyConsts pc) {
-    k_polyexp_body(blockIdx.x, blockIdx.y, blockIdx.z, I, I_stride, R, R_stride, plane, w, h, pc);
-}
 
 // All levels' PolyExp in ONE launch (a 1-D grid cut into per-level ranges): the coarse levels' small grids
 // run inside the level-0 launch instead of paying a launch ramp and tail each.
@@ -880,11 +876,6 @@ void ffl_launch_polyexp_multi(const PolyJob *jobs_in, int n, int nU, PolyConsts 
         jobs.j[n - 1].gk1 = l0->gk.k[2];
     }
     hipLaunchKernelGGL(k_polyexp_multi, dim3(total), dim3(256), 0, st, jobs, pc, gray_base, gray_stride, ut);
-}
-
-void ffl_launch_polyexp(const PolyJob &J, int nU, PolyConsts pc, hipStream_t st) {
-    dim3 grid((J.w + PE_TW - 1) / PE_TW, (J.h + PE_TH - 1) / PE_TH, nU);
-    hipLaunchKernelGGL(k_polyexp, grid, dim3(256), 0, st, J.I, J.I_stride, J.R, J.R_stride, J.plane, J.w, J.h, pc);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -982,50 +982,19 @@ __global__ __launch_bounds__(P1_THREADS) void k_import_pass1(const ImportArgs a,
     ffl_pass1_body(src, WtNone{}, w, h, pov_mode, b, pkey, psum, skey, ssum);
 }
 
-// The two-launch form (ffl_ctx option import_fused = 0, the A/B of DESIGN.md section 13): a plain conversion into the
-// slots, then ffl_launch_pass1 over them.  A lane converts FFL_EXP_UNROLL pixels of one item, 256 pixels apart.
 template <int DT, int MODE>
-__global__ __launch_bounds__(256) void k_import_convert(const ImportArgs a, const ExportTab tab, int w, int h,
-                                                        PairTab *__restrict__ pt) {
-    const int b = blockIdx.y;
-    const size_t N = (size_t)w * h;
-    ffl_import_publish(a, tab, N, pt, b);
-    const P1ImportSrc<DT, MODE> src{a.base + (long long)b * a.item, a.pitch, a.ps, a.cs, nullptr, w};
-    float *slot = a.flow + (size_t)tab.slot[b] * 2 * N;
-    const unsigned base = blockIdx.x * (256 * FFL_EXP_UNROLL) + threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < FFL_EXP_UNROLL; k++) {
-        const unsigned i = base + k * 256u;
-        if (i < N) {
-            const int y = i / (unsigned)w, x = i - y * w;
-            const char *row = src.item + (long long)y * a.pitch;
-            const long long o = (long long)x * a.ps;
-            ffl_v2f v = {src.elem(row, o), src.elem(row, o + a.cs)};
-            *(FFL_GLOBAL ffl_v2f *)((char *)slot + 8u * i) = v;
-        }
-    }
-}
-
-template <int DT, int MODE>
-static void ffl_import_launch(const ImportArgs &a, const ExportTab &tab, int n, int w, int h, int pov_mode, int fused,
-                              PairTab *pt, unsigned long long *pkey, double *psum, hipStream_t st) {
+static void ffl_import_launch(const ImportArgs &a, const ExportTab &tab, int n, int w, int h, int pov_mode, PairTab *pt,
+                              unsigned long long *pkey, double *psum, hipStream_t st) {
     const int nblk = ffl_pass1_blocks(w, h);
-    if (fused) {
-        hipLaunchKernelGGL((k_import_pass1<DT, MODE>), dim3(nblk, n), dim3(P1_THREADS), 0, st, a, tab, w, h, pov_mode, pt,
-                           pkey, psum);
-        hipLaunchKernelGGL(k_pass1_final, dim3(n), dim3(P1_THREADS), 0, st, pt, w, h, pov_mode, nblk, pkey, psum);
-    } else {
-        const size_t N = (size_t)w * h;
-        hipLaunchKernelGGL((k_import_convert<DT, MODE>), dim3((unsigned)((N + 256 * FFL_EXP_UNROLL - 1) / (256 * FFL_EXP_UNROLL)), n),
-                           dim3(256), 0, st, a, tab, w, h, pt);
-        ffl_launch_pass1(pt, n, w, h, pov_mode, pkey, psum, st);
-    }
+    hipLaunchKernelGGL((k_import_pass1<DT, MODE>), dim3(nblk, n), dim3(P1_THREADS), 0, st, a, tab, w, h, pov_mode, pt, pkey,
+                       psum);
+    hipLaunchKernelGGL(k_pass1_final, dim3(n), dim3(P1_THREADS), 0, st, pt, w, h, pov_mode, nblk, pkey, psum);
 }
 
 void ffl_launch_import_pass1(const ImportArgs &a, const ExportTab &tab, int n, int dtype, int mode, int w, int h, int pov_mode,
-                             int fused, PairTab *pt, unsigned long long *pkey, double *psum, hipStream_t st) {
+                             PairTab *pt, unsigned long long *pkey, double *psum, hipStream_t st) {
 #define FFL_IMP_CASE(DT, MODE)                                                                                   \
-    if (dtype == DT && mode == MODE) return ffl_import_launch<DT, MODE>(a, tab, n, w, h, pov_mode, fused, pt, pkey, psum, st);
+    if (dtype == DT && mode == MODE) return ffl_import_launch<DT, MODE>(a, tab, n, w, h, pov_mode, pt, pkey, psum, st);
     FFL_IMP_CASE(FFL_IMP_F32, FFL_IMP_NHWC)
     FFL_IMP_CASE(FFL_IMP_F32, FFL_IMP_NCHW)
     FFL_IMP_CASE(FFL_IMP_F32, FFL_IMP_ANY)

@@ -764,12 +764,11 @@ int ffl_debug_pair(ffl_ctx *ctx, int f0, int f1, int level, int iter, float *I0,
  *   "fuse_first"  = N >= 0   a level's flow init + first UpdateMatrices run inside its first k_blur_solve launch
  *                            when the level has at least N 64x16 tiles over the batch (default 10000; 0 = never,
  *                            1 = always)
- *   "merge_expand" = 0|1     1 (default): pyramid + PolyExp of all levels in three merged launches per batch;
- *                            0: one set of launches per level
  *   "lanes"       = 1..4     compute lanes (co-scheduled batches, each on its own stream and work
  *                            buffers) of contexts created afterwards; default 2
- *   "run_ahead"   = 0|1|2    schedule of the frame-only kernels: 0 serial (default), 1 run-ahead on a
- *                            side stream, 2 fork/join over per-level side streams
+ *   "run_ahead"   = 0,       schedule of the frame-only kernels.  Fixed: they run serially on the lane's stream,
+ *   "merge_expand" = 1       pyramid + PolyExp of all levels in three merged launches per batch (other values
+ *                            are refused)
  *   "copy_threads" = 1..16   host threads that share a staging copy of 1 MiB or more (the caller + helpers owned by
  *                            the context); default 4.  One thread moves ~22 GB/s, a 1080p BGR stream at 5 k pairs/s
  *                            needs 31
@@ -778,7 +777,7 @@ int ffl_debug_pair(ffl_ctx *ctx, int f0, int f1, int level, int iter, float *I0,
  *                            capture always launch one by one)
  *   "pyr_coarse"  = 0|1      1 (default): the x1/4 and x1/8 pyramid levels of frames whose sides are multiples of 8
  *                            come from one LDS-staged pass (k_pyr_coarse); 0: horizontal + vertical kernel pairs
- *   "fuse_l0_blur" = 0|1     1 (default): in the merged expansion PolyExp forms level 0's image (the 3-tap blur of the
+ *   "fuse_l0_blur" = 0|1     1 (default): PolyExp forms level 0's image (the 3-tap blur of the
  *                            gray frame) in its own tile loader and the level-0 image plane is neither written nor
  *                            read; 0: the pyramid launch writes it (the debug capture always does)
  *   "tile_order"  = 0|1      k_blur_solve / k_update_matrices workgroup order: 0 pair-major (default), 1 tile-major

@@ -2,10 +2,9 @@
 warm-up, as the median of interleaved repetitions:
 
   import  ms per Context.import_flows call for 256 fields at 256x256 and 32 at 1080p, float32 NHWC, float32 NCHW and
-          float16 NHWC, in the fused form (k_import_pass1, option import_fused = 1) and the two-launch form (conversion
-          kernel, then pass 1; import_fused = 0).  The call makes the caller's stream wait for the import, so the interval
-          ends when the slots and records are complete.  Bytes moved: the source once + the slot written (+ the slot read
-          again by pass 1 in the two-launch form); the share is of the 6.3 TB/s copy ceiling of DESIGN.md section 12.
+          float16 NHWC (k_import_pass1: conversion + pass 1 in one read).  The call makes the caller's stream wait for
+          the import, so the interval ends when the slots and records are complete.  Bytes moved: the source once + the
+          slot written; the share is of the 6.3 TB/s copy ceiling of DESIGN.md section 12.
   host    the route without the import for the same float32 NHWC fields: download to host memory, one upload_flow per
           field, then the records (host clock around work that ends in a device synchronise)
 
@@ -50,10 +49,9 @@ def main():
         srcs = {"f32_nhwc": f32, "f32_nchw": f32.permute(0, 3, 1, 2).contiguous(), "f16_nhwc": f32.half()}
         slots = list(range(n))
         want = None
-        ms = {(k, fused): [] for k in srcs for fused in (1, 0)}
+        ms = {k: [] for k in srcs}
         for r in range(a.reps + 1):           # repetition 0 is the warm-up
-            for (k, fused), v in ms.items():
-                ctx.set_option("import_fused", fused)
+            for k, v in ms.items():
                 t = timed(lambda: ctx.import_flows(srcs[k], slots))
                 if k == "f32_nhwc":
                     recs = ctx.pass1_results(slots)
@@ -61,17 +59,16 @@ def main():
                     assert recs == want, "imports differ"
                 if r:
                     v.append(t)
-        for (k, fused), v in ms.items():
+        for k, v in ms.items():
             med = float(np.median(v))
             src_b = 4 if k.startswith("f16") else 8
-            moved = n * w * h * (src_b + 8 + (0 if fused else 8))
+            moved = n * w * h * (src_b + 8)
             rec = {"what": "import", "size": f"{w}x{h}", "fields": n, "source": k,
-                   "form": "fused" if fused else "two-launch", "median_ms": round(med, 4),
+                   "form": "fused", "median_ms": round(med, 4),
                    "bytes_moved": moved, "GBps": round(moved / med / 1e6, 1),
                    "share_of_copy_ceiling": round(moved / med * 1e3 / CEILING, 3), "reps": a.reps}
             print(json.dumps(rec), flush=True)
             out.append(rec)
-        ctx.set_option("import_fused", 1)
         host_s = []
         for r in range(a.reps + 1):
             torch.cuda.synchronize()

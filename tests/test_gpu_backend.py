@@ -156,15 +156,14 @@ def test_results_do_not_depend_on_batching_or_slots():
 
 
 def test_results_do_not_depend_on_schedule_options():
-    """Compute lanes (co-scheduled batches) and the frame-expansion schedules are speed knobs only: many small batches in flight on recycled frame/flow slots give identical bits."""
+    """Compute lanes (co-scheduled batches) are a speed knob only: many small batches in flight on recycled frame/flow slots give identical bits."""
     w, h = 192, 144
     n = 21
     fr = sine_translate_frames(n + 1, w, h, seed=33, amp=(2.0, 1.0), period=9)
     want = None
     try:
-        for lanes, run_ahead, tile in [(1, 0, 16), (2, 0, 16), (2, 1, 16), (3, 2, 16), (1, 1, 16)]:
+        for lanes, tile in [(1, 16), (2, 16), (3, 16)]:
             _capi.set_option("lanes", lanes)
-            _capi.set_option("run_ahead", run_ahead)
             _capi.set_option("blur_tile_h", tile)
             with _capi.Context(w, h, max_batch=3, frame_slots=8, flow_slots=3 * 3 + 13) as ctx:
                 dots, recs = pipeline.PairEngine(ctx).process_chunk(fr)
@@ -177,7 +176,6 @@ def test_results_do_not_depend_on_schedule_options():
                 assert np.array_equal(got[0], want[0]) and got[1] == want[1] and np.array_equal(got[2], want[2])
     finally:
         _capi.set_option("lanes", 2)
-        _capi.set_option("run_ahead", 0)
         _capi.set_option("blur_tile_h", 16)
 
 
@@ -254,18 +252,14 @@ def test_long_stream_recycles_every_ring_and_slot():
     fr = sine_translate_frames(n + 1, w, h, seed=77, amp=(3.0, 2.0), period=23, zoom=0.02)
     out = []
     try:
-        for lanes, run_ahead, merge, fuse in [(1, 0, 1, 0), (2, 0, 1, 1), (2, 1, 0, 1), (3, 2, 1, 10000)]:
+        for lanes, fuse in [(1, 0), (2, 1), (3, 10000)]:
             _capi.set_option("lanes", lanes)
-            _capi.set_option("run_ahead", run_ahead)
-            _capi.set_option("merge_expand", merge)
             _capi.set_option("fuse_first", fuse)
             with _capi.Context(w, h, max_batch=4, frame_slots=10, flow_slots=3 * 4 + 13) as ctx:
                 dots, recs = pipeline.PairEngine(ctx).process_chunk(fr)
             out.append((np.array(dots), [tuple(r) for r in recs]))
     finally:
         _capi.set_option("lanes", 2)
-        _capi.set_option("run_ahead", 0)
-        _capi.set_option("merge_expand", 1)
         _capi.set_option("fuse_first", 10000)
     for d, r in out[1:]:
         assert np.array_equal(d, out[0][0]) and r == out[0][1]

@@ -648,6 +648,13 @@ def test_options_belong_to_a_context_not_to_the_process():
             ga2, gb2 = a.graph_stats(), b.graph_stats()
             assert ga2["captured"] == ga["captured"] + 1 and gb2["captured"] == gb["captured"], (ga, ga2, gb, gb2)
             assert gb2["replayed"] == gb["replayed"] + 2 and ga2["capture_failures"] == gb2["capture_failures"] == 0
+            with pytest.raises(_capi.FFLError):         # a fixed knob: the refusal changes nothing, so a replays its graph
+                a.set_option("run_ahead", 1)
+            assert a.get_option("run_ahead") == 0
+            for got, w_ in zip(step(a), want):
+                assert np.array_equal(got, w_)
+            ga3 = a.graph_stats()
+            assert ga3["captured"] == ga2["captured"] and ga3["replayed"] == ga2["replayed"] + 1, (ga2, ga3)
             with pytest.raises(_capi.FFLError, match="lanes"):
                 a.set_option("lanes", 2)
             a.set_option("lanes", 1)                    # the value it has is accepted

@@ -140,8 +140,8 @@ def test_coarser_level_images_and_expansions(w, h):
 
 
 def test_whole_results_do_not_depend_on_the_form():
-    """256x144, B = 3: records, scalars and every flow field by their bytes -- fuse_l0_blur on / off, merge_expand 1 / 0,
-    graph replay / eager launches"""
+    """256x144, B = 3: records, scalars and every flow field by their bytes -- fuse_l0_blur on / off, graph replay / eager
+    launches"""
     w, h, B = 256, 144, 3
     fr = sine_translate_frames(B + 1, w, h, seed=11, amp=(3.0, 2.0), period=6)
 
@@ -162,6 +162,5 @@ def test_whole_results_do_not_depend_on_the_form():
 
     ref = run()
     assert ref[2][0] == orc.farneback(fr[0], fr[1]).tobytes()
-    for opts in ({"fuse_l0_blur": 0}, {"merge_expand": 0}, {"graph": 0}, {"graph": 0, "fuse_l0_blur": 0},
-                 {"merge_expand": 0, "fuse_l0_blur": 0}):
+    for opts in ({"fuse_l0_blur": 0}, {"graph": 0}, {"graph": 0, "fuse_l0_blur": 0}):
         assert run(**opts) == ref, opts

@@ -65,13 +65,9 @@ def test_goldens(post, name, layout):
             for pov in (False, True):
                 pr.check_radial(ctx.radial([1], [c], [False], pov)[0], flow, c, pov)
             assert ctx.radial([1], [c], [True], False)[0] == gc == 0.0
-        # pov_mode as in upload_flow; the two-launch form gives the same records
+        # pov_mode as in upload_flow
         ctx.import_flows(t, [2], pov_mode=True)
         assert ctx.pass1_result(2) == uploaded_records(ctx, [flow], 3, pov=True)[0]
-        ctx.set_option("import_fused", 0)
-        ctx.import_flows(t, [4])
-        assert ctx.pass1_result(4) == want
-        assert np.array_equal(bits(ctx.download_flow(4)), bits(flow))
 
 
 def engines(B, w=256, h=256):

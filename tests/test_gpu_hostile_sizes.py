@@ -18,9 +18,10 @@ import post_ref as pr
 from funscript_flow_amd import _capi
 from funscript_flow_amd.synth import sine_translate_frames
 
-# FflOptions' initialisers (ffl_kernels.h); "lanes" is the one knob a test here chooses
+# FflOptions' initialisers (ffl_kernels.h) and the fixed "run_ahead" and "merge_expand"; "lanes" is the one knob a test
+# here chooses
 DEFAULTS = dict(run_ahead=0, fuse_first=10000, merge_expand=1, graph=1, copy_threads=4, blur_rows=0, blur_min_wgs=3500,
-                tile_order=0, pyr_coarse=1, fb_general=0, import_fused=1)
+                tile_order=0, pyr_coarse=1, fb_general=0)
 
 
 def rotate_zoom(img, degrees, zoom, about):

@@ -283,7 +283,7 @@ def test_one_pass_coarse_pyramid_levels_bit_exact(w, h):
             assert np.array_equal(got[0][lvl][key], want), (lvl, key)
 
 
-# ------------------------------------------------------------------ per-level launchers under every schedule
+# ------------------------------------------------------------------ per-level pyramid launchers (the size-chosen fallback)
 # (258, 257): w % 4 != 0, so the merged pyramid launch refuses and every level is launched on its own -- level 0 by the
 # unaligned x1 instantiation of the fused kernel (byte-wise taps, a two-pixel tail lane), level 1 (129 x 128, h odd:
 # inexact) by the R = 1 H + V pair, levels 2 and 3 (64 x 64, 32 x 32) by the R = 4 / R = 9 pairs with byte-wise taps; the
@@ -291,13 +291,11 @@ def test_one_pass_coarse_pyramid_levels_bit_exact(w, h):
 # but lw = 66 is not -- level 0 by the aligned x1 instantiation, level 1 by the unaligned x2 one with the word-wise
 # fetch and a two-pixel tail lane whose taps pass the row's end.
 AWKWARD_SIZES = [(258, 257), (130, 66), (132, 68)]
-SCHEDULES = {"default": {}, "merge_expand=0": {"merge_expand": 0}, "run_ahead=1": {"run_ahead": 1},
-             "run_ahead=2": {"run_ahead": 2}}
 _awkward_cache = {}
 
 
 def awkward_case(w, h):
-    """frames and oracle flows of one size, computed once for all schedules"""
+    """frames and oracle flows of one size, computed once for the tests that use it"""
     if (w, h) not in _awkward_cache:
         fr = frames(3, w, h, seed=3 * w + h, amp=(2.5, 1.5), period=6)
         fr.setflags(write=False)
@@ -305,23 +303,16 @@ def awkward_case(w, h):
     return _awkward_cache[(w, h)]
 
 
-@pytest.mark.parametrize("sched", list(SCHEDULES))
 @pytest.mark.parametrize("w,h", AWKWARD_SIZES)
-def test_per_level_launches_every_schedule_bit_exact(w, h, sched):
-    """Sizes whose levels the merged launches do not take, under the serial merged, serial per-level, run-ahead and
-    fork/join schedules of the frame-only work: both flows of a 2-pair batch equal the oracle bit for bit."""
+def test_per_level_launches_every_schedule_bit_exact(w, h):
+    """Sizes whose levels the merged pyramid launch does not take, so that the library falls back to the per-level
+    launchers: both flows of a 2-pair batch equal the oracle bit for bit."""
     fr, want = awkward_case(w, h)
-    try:
-        for k, v in SCHEDULES[sched].items():
-            _capi.set_option(k, v)
-        with _capi.Context(w, h, max_batch=2, frame_slots=4, flow_slots=4) as ctx:
-            for i in range(3):
-                ctx.upload_frame(i, fr[i])
-            ctx.flow_pairs([0, 1], [1, 2], [0, 1])
-            got = [ctx.download_flow(0), ctx.download_flow(1)]
-    finally:
-        _capi.set_option("merge_expand", 1)
-        _capi.set_option("run_ahead", 0)
+    with _capi.Context(w, h, max_batch=2, frame_slots=4, flow_slots=4) as ctx:
+        for i in range(3):
+            ctx.upload_frame(i, fr[i])
+        ctx.flow_pairs([0, 1], [1, 2], [0, 1])
+        got = [ctx.download_flow(0), ctx.download_flow(1)]
     for j in range(2):
         assert np.array_equal(got[j], want[j]), (j, np.abs(got[j] - want[j]).max())
 

@@ -415,9 +415,8 @@ def layouts(t):
     return {"nhwc": t, "nchw": t.permute(0, 3, 1, 2).contiguous(), "padded": pad[:, 2:2 + h, 1:1 + w], "strided": wide[..., ::2]}
 
 
-@pytest.mark.parametrize("fused", [1, 0])
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
-def test_every_half_precision_pattern_widens_exactly(dtype, fused):
+def test_every_half_precision_pattern_widens_exactly(dtype):
     w, h = 256, 128
     pat = all_patterns()
     want = widen(pat, dtype)
@@ -432,8 +431,6 @@ def test_every_half_precision_pattern_widens_exactly(dtype, fused):
     t = torch.from_numpy(np.stack([pat, pat2]).view(np.int16)).to(DEV).view(dtype)
     cs = centres(w, h)
     with _capi.Context(w, h, max_batch=2, frame_slots=2, flow_slots=8) as ctx:
-        ctx.set_option("import_fused", fused)
-        assert ctx.get_option("import_fused") == fused
         for name, view in layouts(t).items():
             ctx.import_flows(view, [0, 1])
             recs = ctx.pass1_results([0, 1])

@@ -535,10 +535,8 @@ _OPTION_TABLE = {  # knob: (default, legal values, lowest accepted or None, high
     "blur_min_wgs": (3500, (1, 1 << 30), 1, None),
     "tile_order": (0, (1, 0), 0, 1),
     "fb_general": (0, (1, 0), 0, 1),
-    "import_fused": (1, (0, 1), 0, 1),
     "copy_threads": (4, (1, 16), 1, 16),
     "lanes": (2, (1, 4), 1, 4),
-    "run_ahead": (0, (2, 1, 0), 0, 2),
 }
 
 
@@ -550,12 +548,14 @@ def test_process_wide_option_defaults_without_a_device():
         _capi.set_option("lanes", 3)
         _capi.set_option("blur_min_wgs", 777)
         assert _capi.get_option("lanes") == 3 and _capi.get_option("blur_min_wgs") == 777
-        for bad in (("lanes", 9), ("blur_rows", 65), ("copy_threads", 0), ("nope", 1), ("blur_tile_h", 8)):
+        for bad in (("lanes", 9), ("blur_rows", 65), ("copy_threads", 0), ("nope", 1), ("blur_tile_h", 8), ("import_fused", 0),
+                    ("import_fused", 1), ("run_ahead", 1), ("merge_expand", 0)):
             with pytest.raises(_capi.FFLError):
                 _capi.set_option(*bad)
         assert _capi.get_option("lanes") == 3
-        with pytest.raises(_capi.FFLError):
-            _capi.get_option("nope")
+        for gone in ("nope", "import_fused"):
+            with pytest.raises(_capi.FFLError):
+                _capi.get_option(gone)
         _capi.set_option("lanes", 2)
         _capi.set_option("blur_min_wgs", 3500)
         # every knob: a legal value round-trips, the first value outside a bounded range is refused and changes nothing
@@ -569,16 +569,28 @@ def test_process_wide_option_defaults_without_a_device():
                 with pytest.raises(_capi.FFLError):
                     _capi.set_option(name, bad)
                 assert _capi.get_option(name) == default, (name, bad)
-        for name in ("merge_expand", "pyr_coarse", "graph"):       # stored as != 0
+        for name in ("pyr_coarse", "graph"):                         # stored as != 0
             for v, want in ((7, 1), (0, 0), (-3, 1)):
                 _capi.set_option(name, v)
                 assert _capi.get_option(name) == want, (name, v)
         _capi.set_option("blur_tile_h", 16)                          # fixed: only 16 is accepted, and it reads back 16
         assert _capi.get_option("blur_tile_h") == 16
+        assert _capi.get_option("run_ahead") == 0                    # fixed: the frame-only kernels have one schedule
+        _capi.set_option("run_ahead", 0)
+        for bad in (1, 2, -1):
+            with pytest.raises(_capi.FFLError):
+                _capi.set_option("run_ahead", bad)
+            assert _capi.get_option("run_ahead") == 0, bad
+        assert _capi.get_option("merge_expand") == 1                 # fixed: the frame-only work runs in the merged launches
+        _capi.set_option("merge_expand", 1)
+        for bad in (0, 2, -1):
+            with pytest.raises(_capi.FFLError):
+                _capi.set_option("merge_expand", bad)
+            assert _capi.get_option("merge_expand") == 1, bad
     finally:
         for name, (default, _, _, _) in _OPTION_TABLE.items():
             _capi.set_option(name, default)
-        for name in ("merge_expand", "pyr_coarse", "graph"):
+        for name in ("pyr_coarse", "graph"):
             _capi.set_option(name, 1)
 
 
