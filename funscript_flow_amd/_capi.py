@@ -14,34 +14,14 @@ FFL_MAX_BATCH = 256
 # kernel classes of ffl_profile_read
 KERNEL_CLASSES = ["k_gray", "k_pyr_level", "k_polyexp", "k_frontend", "k_update_matrices", "k_blur_solve",
                   "k_pass1", "k_radial"]
+FFL_PROFILE_ALL = 0xFF
 
-# every symbol include/ffl.h declares (tests check that the library exports all of them)
-EXPORTS = ["ffl_device_count", "ffl_create", "ffl_destroy", "ffl_last_error", "ffl_upload_frame", "ffl_upload_frames", "ffl_upload_frames_raw", "ffl_host_alloc", "ffl_host_free",
-           "ffl_flow_pairs",
-           "ffl_pass1_result", "ffl_pass1_results", "ffl_radial", "ffl_download_flow", "ffl_upload_flow", "ffl_submit_pair", "ffl_sync",
-           "ffl_num_levels", "ffl_level_size", "ffl_download_frame", "ffl_debug_pair", "ffl_set_option", "ffl_ctx_set_option", "ffl_ctx_get_option", "ffl_graph_stats", "ffl_profile_enable",
-           "ffl_profile_read", "ffl_kernel_name", "ffl_device_mem_info", "ffl_estimate_bytes",
-           "ffl_dis_default_params", "ffl_dis_geometry", "ffl_flow_pairs_dis", "ffl_debug_dis_pair",
-           "ffl_farneback_default_params", "ffl_farneback_geometry", "ffl_farneback_extra_bytes", "ffl_flow_pairs_farneback",
-           "ffl_flow_pairs_farneback_ex",
-           "ffl_upload_frames_yuv", "ffl_frontend_yuv_window",
-           "ffl_upload_frames_yuv16", "ffl_frontend_yuv16_window", "ffl_dev_frame_check16", "ffl_upload_frames_device16",
-           "ffl_dev_frame_check", "ffl_upload_frames_device", "ffl_export_flows",
-           "ffl_dev_flow_check", "ffl_import_flows", "ffl_radial_window",
-           "ffl_radial_axes", "ffl_radial_window_axes", "ffl_axes_extra_bytes",
-           "ffl_dev_weights_check", "ffl_pass1_weighted", "ffl_radial_window_axes_weighted", "ffl_weights_extra_bytes",
-           "ffl_cell_grid_check", "ffl_cell_stats", "ffl_radial_window_axes_centres", "ffl_cells_extra_bytes",
-           "ffl_consistency_default_params", "ffl_consistency_params_check", "ffl_consistency_weights",
-           "ffl_upload_frames_raw_src", "ffl_upload_frames_yuv_src", "ffl_upload_frames_yuv16_src", "ffl_frontend_yuv_window_src",
-           "ffl_frontend_yuv16_window_src", "ffl_dev_frame_check_src", "ffl_dev_frame_check16_src",
-           "ffl_upload_frames_device_src", "ffl_upload_frames_device16_src"]
-
+# The records the library writes are numpy dtypes in the header's field order.  None of them has padding, so the packed
+# dtype is the C layout; tests/test_abi_host.py compares every offset and size with the compiled header.
 # the per-cell statistics grid and the variance centre: ffl_cell_record, ffl_grid_centre, FFL_MAX_CELLS
 FFL_MAX_CELLS = 64
-CELL_DTYPE = np.dtype({"names": ["mean_u", "mean_v", "mean_mag", "var_mag"], "formats": ["<f8"] * 4,
-                       "offsets": [0, 8, 16, 24], "itemsize": 32})
-GRID_CENTRE_DTYPE = np.dtype({"names": ["cx", "cy", "total_var", "cells", "empty"],
-                              "formats": ["<f8", "<f8", "<f8", "<i4", "<i4"], "offsets": [0, 8, 16, 24, 28], "itemsize": 32})
+CELL_DTYPE = np.dtype([(k, "<f8") for k in ("mean_u", "mean_v", "mean_mag", "var_mag")])
+GRID_CENTRE_DTYPE = np.dtype([("cx", "<f8"), ("cy", "<f8"), ("total_var", "<f8"), ("cells", "<i4"), ("empty", "<i4")])
 CENTERS = ("variance",)   # params["hip_center"] / center=: estimators beside the default |div| argmax
 
 # 4:2:0 layouts of ffl_upload_frames_yuv (FFL_YUV_I420, FFL_YUV_NV12): cv2's single-array (3h/2, w) uint8 frames
@@ -62,17 +42,13 @@ FFL_ERR_INVALID, FFL_ERR_STATE = 1, 4
 FLOW_DTYPES = {"<f4": 0, "<f2": 1, "bfloat16": 2}
 
 # ffl_radial_window: ffl_pass2_record as a numpy structured dtype, and FFL_MAX_RADIUS
-PASS2_DTYPE = np.dtype({"names": ["dot", "cx", "cy", "mean_mag", "div_val", "x", "y", "cut", "pad"],
-                        "formats": ["<f8", "<f8", "<f8", "<f4", "<f4", "<i4", "<i4", "<i4", "<i4"],
-                        "offsets": [0, 8, 16, 24, 28, 32, 36, 40, 44], "itemsize": 48})
+PASS2_DTYPE = np.dtype([("dot", "<f8"), ("cx", "<f8"), ("cy", "<f8"), ("mean_mag", "<f4"), ("div_val", "<f4"), ("x", "<i4"),
+                        ("y", "<i4"), ("cut", "<i4"), ("pad", "<i4")])
 FFL_MAX_RADIUS = 32
 # the four motion components about the centre: FFL_AXIS_* in order, and ffl_axes_record -- a
 # PASS2_DTYPE record, then components 1..3 and `reserved`
 AXES = ("radial", "tangential", "shift_x", "shift_y")
-PASS2_AXES_DTYPE = np.dtype({"names": PASS2_DTYPE.names + AXES[1:] + ("reserved",),
-                             "formats": [PASS2_DTYPE.fields[k][0] for k in PASS2_DTYPE.names] + ["<f8"] * 4,
-                             "offsets": [PASS2_DTYPE.fields[k][1] for k in PASS2_DTYPE.names] + [48, 56, 64, 72],
-                             "itemsize": 80})
+PASS2_AXES_DTYPE = np.dtype(PASS2_DTYPE.descr + [(k, "<f8") for k in AXES[1:] + ("reserved",)])
 
 FLOWS = ("farneback", "dis")   # params["hip_flow"]: the reference's CPU/CUDA/OpenCL branch, or its "DNN" branch (FF:948-980)
 DIS_STAGES = {"pass1": 0, "pass2": 1, "dense": 2, "refined": 3, "images": 4}   # ffl_debug_dis_pair stages
@@ -132,9 +108,37 @@ class FarnebackParams(C.Structure):
         return bytes(self) == bytes(FarnebackParams())
 
 
-def _farneback_error(prefix):
-    msg = load().ffl_last_error(None)
-    return ValueError(f"{prefix}: {msg.decode() if msg else 'refused'}")
+class FFLError(RuntimeError):
+    """A refused or failed library call; `code` is the FFL_ERR_* status (None where Python refused it)."""
+    code = None
+
+
+def _check(rc, ctx=None, exc=None, prefix=""):
+    """The one place a non-zero status becomes an exception, with the message the library recorded for `ctx` (None: the
+    calling thread's).  exc None: FFLError "ffl error <rc>: <message>" carrying `.code`; else exc(prefix + message)."""
+    if rc == FFL_OK:
+        return
+    msg = load().ffl_last_error(ctx)
+    msg = msg.decode() if msg else "refused"
+    if exc is not None:
+        raise exc(prefix + msg)
+    err = FFLError(f"ffl error {rc}: {msg}")
+    err.code = rc
+    raise err
+
+
+def _sizes(name, *args, outs=1):
+    """the size_t results of a sizing call `name(ints..., size_t *...)`; FFLError "<name> failed: ..." when it refuses"""
+    out = [C.c_size_t() for _ in range(outs)]
+    _check(getattr(load(), name)(*map(int, args), *map(C.byref, out)), exc=FFLError, prefix=f"{name} failed: ")
+    return out[0].value if outs == 1 else tuple(o.value for o in out)
+
+
+def _src_call(L, name, info, *args):
+    """name(*args), or its _src sibling with the SourceInfo appended when the stream has metadata (source_info)"""
+    if info is None:
+        return getattr(L, name)(*args)
+    return getattr(L, name + "_src")(*args, C.byref(info))
 
 
 def farneback_geometry(width, height, params=None):
@@ -142,16 +146,16 @@ def farneback_geometry(width, height, params=None):
     the parameters or the size are refused."""
     p = params if params is not None else FarnebackParams()
     n, b = C.c_int(), C.c_size_t()
-    if load().ffl_farneback_geometry(int(width), int(height), C.byref(p), C.byref(n), C.byref(b)) != FFL_OK:
-        raise _farneback_error(f"Farneback at {width}x{height} with {p.as_dict()}")
+    _check(load().ffl_farneback_geometry(int(width), int(height), C.byref(p), C.byref(n), C.byref(b)), exc=ValueError,
+           prefix=f"Farneback at {width}x{height} with {p.as_dict()}: ")
     return n.value, b.value
 
 
 def farneback_extra_bytes(width, height, max_batch, params):
     """device bytes ffl_flow_pairs_farneback(params) may add to ffl_estimate_bytes (0 when the lane buffers suffice)"""
     b = C.c_size_t()
-    if load().ffl_farneback_extra_bytes(int(width), int(height), int(max_batch), C.byref(params), C.byref(b)) != FFL_OK:
-        raise _farneback_error(f"Farneback at {width}x{height} with {params.as_dict()}")
+    _check(load().ffl_farneback_extra_bytes(int(width), int(height), int(max_batch), C.byref(params), C.byref(b)),
+           exc=ValueError, prefix=f"Farneback at {width}x{height} with {params.as_dict()}: ")
     return b.value
 
 
@@ -170,8 +174,7 @@ def farneback_choice(params):
                 raise ValueError(f"Farneback parameter {name} must be an integer, got {v!r}")
             over[name] = int(v)
     p = FarnebackParams(**over)
-    if load().ffl_farneback_geometry(64, 64, C.byref(p), None, None) != FFL_OK:
-        raise _farneback_error(f"hip_farneback {dict(over)}")
+    _check(load().ffl_farneback_geometry(64, 64, C.byref(p), None, None), exc=ValueError, prefix=f"hip_farneback {dict(over)}: ")
     return None if p.is_default() else p
 
 
@@ -204,16 +207,10 @@ def dis_geometry(width, height, params=None):
     """(coarsest, finest) DIS scales of a frame size; ValueError when the size or the parameters are not supported."""
     c, f = C.c_int(), C.c_int()
     p = params if params is not None else DisParams()
-    if load().ffl_dis_geometry(int(width), int(height), C.byref(p), C.byref(c), C.byref(f)) != FFL_OK:
-        msg = load().ffl_last_error(None)
-        raise ValueError(f"DIS does not support {width}x{height} with {p.as_dict()} (DESIGN.md appendix D2: patch_size 8, "
-                         f"sides divisible by 2^coarsest): {msg.decode() if msg else 'refused'}")
+    _check(load().ffl_dis_geometry(int(width), int(height), C.byref(p), C.byref(c), C.byref(f)), exc=ValueError,
+           prefix=f"DIS does not support {width}x{height} with {p.as_dict()} (DESIGN.md appendix D2: patch_size 8, "
+                  "sides divisible by 2^coarsest): ")
     return c.value, f.value
-
-
-class FFLError(RuntimeError):
-    """A refused or failed library call; `code` is the FFL_ERR_* status (None where Python refused it)."""
-    code = None
 
 
 class DevFrame(C.Structure):
@@ -381,18 +378,14 @@ def dev_frame_check(fmt, frame, resize, crop, out_size, depth=8, rotate=0, mirro
     """ffl_dev_frame_check (depth > 8: ffl_dev_frame_check16) for a DevFrame: ValueError with the library's rule when it
     refuses (pure host check).  rotate, mirror, yuv_range: see source_info (the _src siblings; resize and crop are then in
     upright terms)."""
-    L = load()
     info = source_info(rotate, mirror, yuv_range)
     geom = (frame.width, frame.height, C.byref(frame), int(resize[0]), int(resize[1]), int(crop[0]), int(crop[1]),
             int(out_size[0]), int(out_size[1]))
-    if info is not None:
-        geom += (C.byref(info),)
-        rc = (L.ffl_dev_frame_check_src(dev_format(fmt), *geom) if depth == 8 else
-              L.ffl_dev_frame_check16_src(dev_format(fmt), int(depth), *geom))
+    if depth == 8:
+        rc = _src_call(load(), "ffl_dev_frame_check", info, dev_format(fmt), *geom)
     else:
-        rc = L.ffl_dev_frame_check(dev_format(fmt), *geom) if depth == 8 else L.ffl_dev_frame_check16(dev_format(fmt), int(depth), *geom)
-    if rc != FFL_OK:
-        raise ValueError(L.ffl_last_error(None).decode())
+        rc = _src_call(load(), "ffl_dev_frame_check16", info, dev_format(fmt), int(depth), *geom)
+    _check(rc, exc=ValueError)
 
 
 class DevFlow(C.Structure):
@@ -442,9 +435,7 @@ def device_flows(obj, width, height):
 
 def dev_flow_check(dtype, n, width, height, desc):
     """ffl_dev_flow_check: ValueError with the library's rule when it refuses (pure host check)."""
-    L = load()
-    if L.ffl_dev_flow_check(int(dtype), int(n), int(width), int(height), C.byref(desc)) != FFL_OK:
-        raise ValueError(L.ffl_last_error(None).decode())
+    _check(load().ffl_dev_flow_check(int(dtype), int(n), int(width), int(height), C.byref(desc)), exc=ValueError)
 
 
 class DevWeights(C.Structure):
@@ -481,9 +472,7 @@ def device_weights(obj, width, height):
 
 def dev_weights_check(n, width, height, desc):
     """ffl_dev_weights_check: ValueError with the library's rule when it refuses (pure host check)."""
-    L = load()
-    if L.ffl_dev_weights_check(int(n), int(width), int(height), None if desc is None else C.byref(desc)) != FFL_OK:
-        raise ValueError(L.ffl_last_error(None).decode())
+    _check(load().ffl_dev_weights_check(int(n), int(width), int(height), None if desc is None else C.byref(desc)), exc=ValueError)
 
 
 class ConsistencyParams(C.Structure):
@@ -505,9 +494,7 @@ class ConsistencyParams(C.Structure):
 
 def consistency_params_check(params):
     """ffl_consistency_params_check: ValueError with the library's rule when it refuses (pure host check)."""
-    L = load()
-    if L.ffl_consistency_params_check(None if params is None else C.byref(params)) != FFL_OK:
-        raise ValueError(L.ffl_last_error(None).decode())
+    _check(load().ffl_consistency_params_check(None if params is None else C.byref(params)), exc=ValueError)
 
 
 def consistency_choice(params):
@@ -551,22 +538,119 @@ def frontend_yuv_window(src_size, layout, resize, crop, out_size, stride=None, d
     siblings): src_size and the rectangle stay in stored terms, resize and crop are in upright ones."""
     sw, sh = int(src_size[0]), int(src_size[1])
     win, b = (C.c_int * 4)(), C.c_size_t()
-    L = load()
     code = layout if isinstance(layout, int) else yuv_layout(layout)
     info = source_info(rotate, mirror, yuv_range)
     geom = (int(resize[0]), int(resize[1]), int(crop[0]), int(crop[1]), int(out_size[0]), int(out_size[1]), win, C.byref(b))
-    src = "_src" if info is not None else ""
-    if info is not None:
-        geom += (C.byref(info),)
     if depth == 8:
-        rc = getattr(L, "ffl_frontend_yuv_window" + src)(sw, sh, code, int(sw if stride is None else stride), *geom)
+        rc = _src_call(load(), "ffl_frontend_yuv_window", info, sw, sh, code, int(sw if stride is None else stride), *geom)
     else:
-        rc = getattr(L, "ffl_frontend_yuv16_window" + src)(sw, sh, code, int(2 * sw if stride is None else stride), int(depth),
-                                                            *geom)
-    if rc != FFL_OK:
-        raise ValueError(L.ffl_last_error(None).decode())
+        rc = _src_call(load(), "ffl_frontend_yuv16_window", info, sw, sh, code, int(2 * sw if stride is None else stride),
+                       int(depth), *geom)
+    _check(rc, exc=ValueError)
     return tuple(win), b.value
 
+
+# ---- the C ABI, stated once --------------------------------------------------------------------------------------------------
+# SIGNATURES holds every entry point of include/ffl.h, in the header's order, as (return type, parameter types).  load()
+# applies it, EXPORTS is its keys, and tests/test_abi_host.py holds it against the prototypes parsed from the header, parameter
+# by parameter.  A new entry point is added to the header and here, nowhere else.  Structs that Python passes with byref() are
+# typed pointers; integer addresses (device pointers, numpy's .ctypes.data, descriptor rows) stay c_void_p.
+_i, _u, _f, _pd, _sz, _u64, _vp, _str = C.c_int, C.c_uint, C.c_float, C.c_ssize_t, C.c_size_t, C.c_uint64, C.c_void_p, C.c_char_p
+_ip, _i32p, _fp, _dp, _szp, _vpp = (C.POINTER(t) for t in (C.c_int, C.c_int32, C.c_float, C.c_double, C.c_size_t, C.c_void_p))
+_P = C.POINTER
+_ctx = _vp                                        # ffl_ctx *
+_FRAMES = (_ctx, _i, _i, _vpp, _i, _i, _pd)       # ctx, first_slot, n, frames, src_width, src_height, stride_bytes
+_DEVICE = (_ctx, _i, _i, _vp, _i)                 # ctx, first_slot, n, frames (rows of ffl_dev_frame), format
+_YUV_WIN = (_i, _i, _i, _pd)                      # src_w, src_h, layout, stride_bytes
+_PAIRS = (_ctx, _i, _ip, _ip, _ip, _i)            # ctx, n, fslot0, fslot1, flow_slots, pov_mode
+_RADIAL = (_ctx, _i, _ip, _dp, _dp, _ip, _i, _dp)   # ctx, n, flow_slots, cx, cy, is_cut, pov_mode, out
+_WINDOW = (_ctx, _i, _ip, _i, _i, _i, _f, _i)     # ctx, n_seq, seq_slots, first, n, radius, cut_threshold, pov_mode
+_SRC = "_src"   # a front-end call's sibling: the parameters of the name without the suffix, then const ffl_source_info *
+SIGNATURES = {
+    "ffl_device_count": (_i, ()),
+    "ffl_create": (_i, (_i,) * 6 + (_vpp,)),
+    "ffl_destroy": (None, (_ctx,)),
+    "ffl_last_error": (_str, (_ctx,)),
+    "ffl_device_mem_info": (_i, (_i, _szp, _szp)),
+    "ffl_estimate_bytes": (_i, (_i,) * 5 + (_szp, _szp)),
+    "ffl_upload_frame": (_i, (_ctx, _i, _vp, _i, _i, _i, _pd)),
+    "ffl_upload_frames": (_i, (_ctx, _i, _i, _vpp, _i, _i, _i, _pd)),
+    "ffl_upload_frames_raw": (_i, _FRAMES + (_i,) * 5),
+    "ffl_upload_frames_raw_src": _SRC,
+    "ffl_upload_frames_yuv": (_i, _FRAMES + (_i,) * 5),
+    "ffl_frontend_yuv_window": (_i, _YUV_WIN + (_i,) * 6 + (_ip, _szp)),
+    "ffl_upload_frames_yuv_src": _SRC,
+    "ffl_frontend_yuv_window_src": _SRC,
+    "ffl_upload_frames_yuv16": (_i, _FRAMES + (_i,) * 7),
+    "ffl_frontend_yuv16_window": (_i, _YUV_WIN + (_i,) * 7 + (_ip, _szp)),
+    "ffl_upload_frames_yuv16_src": _SRC,
+    "ffl_frontend_yuv16_window_src": _SRC,
+    "ffl_dev_frame_check": (_i, (_i,) * 3 + (_P(DevFrame),) + (_i,) * 6),
+    "ffl_upload_frames_device": (_i, _DEVICE + (_i,) * 6 + (_u64,)),
+    "ffl_dev_frame_check16": (_i, (_i,) * 4 + (_P(DevFrame),) + (_i,) * 6),
+    "ffl_upload_frames_device16": (_i, _DEVICE + (_i,) * 8 + (_u64,)),
+    "ffl_dev_frame_check_src": _SRC,
+    "ffl_dev_frame_check16_src": _SRC,
+    "ffl_upload_frames_device_src": _SRC,
+    "ffl_upload_frames_device16_src": _SRC,
+    "ffl_export_flows": (_i, (_ctx, _i, _ip, _vp, _i, _pd, _u64)),
+    "ffl_dev_flow_check": (_i, (_i,) * 4 + (_P(DevFlow),)),
+    "ffl_import_flows": (_i, (_ctx, _i, _ip, _P(DevFlow), _i, _i, _u64)),
+    "ffl_host_alloc": (_i, (_ctx, _sz, _vpp)),
+    "ffl_host_free": (_i, (_ctx, _vp)),
+    "ffl_flow_pairs": (_i, _PAIRS),
+    "ffl_pass1_result": (_i, (_ctx, _i, _f, _i32p, _i32p, _fp, _fp, _ip)),
+    "ffl_pass1_results": (_i, (_ctx, _i, _ip, _f, _i32p, _i32p, _fp, _fp, _ip)),
+    "ffl_radial": (_i, _RADIAL),
+    "ffl_radial_window": (_i, _WINDOW + (_vp, _u64)),
+    "ffl_radial_axes": (_i, _RADIAL),
+    "ffl_radial_window_axes": (_i, _WINDOW + (_vp, _u64)),
+    "ffl_axes_extra_bytes": (_i, (_i, _i, _szp)),
+    "ffl_dev_weights_check": (_i, (_i,) * 3 + (_P(DevWeights),)),
+    "ffl_pass1_weighted": (_i, (_ctx, _i, _ip, _P(DevWeights), _i, _u64)),
+    "ffl_radial_window_axes_weighted": (_i, _WINDOW + (_P(DevWeights), _vp, _u64)),
+    "ffl_weights_extra_bytes": (_i, (_i, _i, _szp)),
+    "ffl_consistency_default_params": (_i, (_P(ConsistencyParams),)),
+    "ffl_consistency_params_check": (_i, (_P(ConsistencyParams),)),
+    "ffl_consistency_weights": (_i, (_ctx, _i, _ip, _ip, _P(ConsistencyParams), _P(DevWeights), _P(DevWeights), _u64)),
+    "ffl_cell_grid_check": (_i, (_i,) * 3 + (_ip, _ip)),
+    "ffl_cell_stats": (_i, (_ctx, _i, _ip, _i, _vp, _vp, _u64)),
+    "ffl_radial_window_axes_centres": (_i, _WINDOW + (_vp, _pd, _vp, _u64)),
+    "ffl_cells_extra_bytes": (_i, (_i,) * 3 + (_szp,)),
+    "ffl_download_flow": (_i, (_ctx, _i, _vp)),
+    "ffl_upload_flow": (_i, (_ctx, _i, _vp, _i)),
+    "ffl_submit_pair": (_i, (_ctx, _i, _vp, _vp, _i, _i, _i, _pd, _i)),
+    "ffl_sync": (_i, (_ctx,)),
+    "ffl_dis_default_params": (_i, (_P(DisParams),)),
+    "ffl_dis_geometry": (_i, (_i, _i, _P(DisParams), _ip, _ip)),
+    "ffl_flow_pairs_dis": (_i, _PAIRS + (_P(DisParams),)),
+    "ffl_debug_dis_pair": (_i, (_ctx, _i, _i, _P(DisParams), _i, _i, _vp)),
+    "ffl_farneback_default_params": (_i, (_P(FarnebackParams),)),
+    "ffl_farneback_geometry": (_i, (_i, _i, _P(FarnebackParams), _ip, _szp)),
+    "ffl_farneback_extra_bytes": (_i, (_i,) * 3 + (_P(FarnebackParams), _szp)),
+    "ffl_flow_pairs_farneback": (_i, _PAIRS + (_P(FarnebackParams),)),
+    "ffl_flow_pairs_farneback_ex": (_i, _PAIRS + (_P(FarnebackParams), _u)),
+    "ffl_num_levels": (_i, (_ctx,)),
+    "ffl_level_size": (_i, (_ctx, _i, _ip)),
+    "ffl_download_frame": (_i, (_ctx, _i, _vp)),
+    "ffl_debug_pair": (_i, (_ctx,) + (_i,) * 4 + (_vp,) * 6),
+    "ffl_set_option": (_i, (_str, _i)),
+    "ffl_ctx_set_option": (_i, (_ctx, _str, _i)),
+    "ffl_ctx_get_option": (_i, (_ctx, _str, _ip)),
+    "ffl_graph_stats": (_i, (_ctx, _ip, _ip, _ip)),
+    "ffl_profile_enable": (_i, (_ctx, _u)),
+    "ffl_profile_read": (_i, (_ctx, _i, _ip, _dp)),
+    "ffl_kernel_name": (_str, (_i,)),
+}
+for _name, _sig in SIGNATURES.items():
+    if _sig is _SRC:
+        SIGNATURES[_name] = (SIGNATURES[_name[:-4]][0], SIGNATURES[_name[:-4]][1] + (_P(SourceInfo),))
+EXPORTS = list(SIGNATURES)   # every symbol include/ffl.h declares
+# the header's records and their Python statements (the test takes the struct names from the header: none can be forgotten)
+RECORDS = {"ffl_source_info": SourceInfo, "ffl_dev_frame": DevFrame, "ffl_dev_flow": DevFlow, "ffl_pass2_record": PASS2_DTYPE,
+           "ffl_axes_record": PASS2_AXES_DTYPE, "ffl_dev_weights": DevWeights, "ffl_consistency_params": ConsistencyParams,
+           "ffl_cell_record": CELL_DTYPE, "ffl_grid_centre": GRID_CENTRE_DTYPE, "ffl_dis_params": DisParams,
+           "ffl_farneback_params": FarnebackParams}
 
 _lib = None
 
@@ -580,85 +664,9 @@ def load():
         raise FFLError(f"{LIB_PATH} is missing: build it with `make -C funscript_flow_amd/csrc` "
                        "(there is no CPU fallback for the HIP backend)")
     L = C.CDLL(LIB_PATH)
-    vp, ip, dp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double)
-    L.ffl_device_count.restype = C.c_int
-    L.ffl_create.argtypes = [C.c_int] * 6 + [C.POINTER(vp)]
-    L.ffl_destroy.argtypes = [vp]
-    L.ffl_destroy.restype = None
-    L.ffl_last_error.argtypes = [vp]
-    L.ffl_last_error.restype = C.c_char_p
-    L.ffl_upload_frame.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_ssize_t]
-    L.ffl_upload_frames.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_ssize_t]
-    L.ffl_upload_frames_raw.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.c_ssize_t, C.c_int,
-                                        C.c_int, C.c_int, C.c_int, C.c_int]
-    L.ffl_upload_frames_yuv.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.c_ssize_t, C.c_int,
-                                        C.c_int, C.c_int, C.c_int, C.c_int]
-    L.ffl_frontend_yuv_window.argtypes = [C.c_int, C.c_int, C.c_int, C.c_ssize_t] + [C.c_int] * 6 + [ip, C.POINTER(C.c_size_t)]
-    L.ffl_upload_frames_yuv16.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.c_ssize_t] + [C.c_int] * 7
-    L.ffl_frontend_yuv16_window.argtypes = [C.c_int, C.c_int, C.c_int, C.c_ssize_t] + [C.c_int] * 7 + [ip, C.POINTER(C.c_size_t)]
-    L.ffl_flow_pairs.argtypes = [vp, C.c_int, ip, ip, ip, C.c_int]
-    L.ffl_pass1_result.argtypes = [vp, C.c_int, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
-                                   C.POINTER(C.c_float), C.POINTER(C.c_float), ip]
-    L.ffl_pass1_results.argtypes = [vp, C.c_int, ip, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
-                                    C.POINTER(C.c_float), C.POINTER(C.c_float), ip]
-    L.ffl_radial.argtypes = [vp, C.c_int, ip, dp, dp, ip, C.c_int, dp]
-    L.ffl_host_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
-    L.ffl_host_free.argtypes = [vp, vp]
-    L.ffl_download_flow.argtypes = [vp, C.c_int, vp]
-    L.ffl_download_frame.argtypes = [vp, C.c_int, vp]
-    L.ffl_upload_flow.argtypes = [vp, C.c_int, vp, C.c_int]
-    L.ffl_submit_pair.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_ssize_t, C.c_int]
-    L.ffl_sync.argtypes = [vp]
-    L.ffl_num_levels.argtypes = [vp]
-    L.ffl_level_size.argtypes = [vp, C.c_int, ip]
-    L.ffl_debug_pair.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int] + [vp] * 6
-    L.ffl_profile_enable.argtypes = [vp, C.c_uint]
-    L.ffl_profile_read.argtypes = [vp, C.c_int, ip, dp]
-    L.ffl_kernel_name.argtypes = [C.c_int]
-    L.ffl_kernel_name.restype = C.c_char_p
-    L.ffl_set_option.argtypes = [C.c_char_p, C.c_int]
-    L.ffl_ctx_set_option.argtypes = [vp, C.c_char_p, C.c_int]
-    L.ffl_ctx_get_option.argtypes = [vp, C.c_char_p, ip]
-    L.ffl_graph_stats.argtypes = [vp, ip, ip, ip]
-    L.ffl_device_mem_info.argtypes = [C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
-    L.ffl_estimate_bytes.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
-    dp_ = C.POINTER(DisParams)
-    L.ffl_dis_default_params.argtypes = [dp_]
-    L.ffl_dis_geometry.argtypes = [C.c_int, C.c_int, dp_, ip, ip]
-    L.ffl_flow_pairs_dis.argtypes = [vp, C.c_int, ip, ip, ip, C.c_int, dp_]
-    L.ffl_debug_dis_pair.argtypes = [vp, C.c_int, C.c_int, dp_, C.c_int, C.c_int, vp]
-    fp_ = C.POINTER(FarnebackParams)
-    L.ffl_farneback_default_params.argtypes = [fp_]
-    L.ffl_farneback_geometry.argtypes = [C.c_int, C.c_int, fp_, ip, C.POINTER(C.c_size_t)]
-    L.ffl_farneback_extra_bytes.argtypes = [C.c_int, C.c_int, C.c_int, fp_, C.POINTER(C.c_size_t)]
-    L.ffl_flow_pairs_farneback.argtypes = [vp, C.c_int, ip, ip, ip, C.c_int, fp_]
-    L.ffl_flow_pairs_farneback_ex.argtypes = [vp, C.c_int, ip, ip, ip, C.c_int, fp_, C.c_uint]
-    L.ffl_dev_frame_check.argtypes = [C.c_int, C.c_int, C.c_int, vp] + [C.c_int] * 6
-    L.ffl_upload_frames_device.argtypes = [vp, C.c_int, C.c_int, vp] + [C.c_int] * 7 + [C.c_uint64]
-    L.ffl_dev_frame_check16.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp] + [C.c_int] * 6
-    L.ffl_upload_frames_device16.argtypes = [vp, C.c_int, C.c_int, vp] + [C.c_int] * 9 + [C.c_uint64]
-    L.ffl_export_flows.argtypes = [vp, C.c_int, ip, vp, C.c_int, C.c_ssize_t, C.c_uint64]
-    L.ffl_dev_flow_check.argtypes = [C.c_int] * 4 + [vp]
-    L.ffl_import_flows.argtypes = [vp, C.c_int, ip, vp, C.c_int, C.c_int, C.c_uint64]
-    L.ffl_radial_window.argtypes = [vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, C.c_uint64]
-    L.ffl_radial_axes.argtypes = L.ffl_radial.argtypes
-    L.ffl_radial_window_axes.argtypes = L.ffl_radial_window.argtypes
-    L.ffl_axes_extra_bytes.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_size_t)]
-    L.ffl_dev_weights_check.argtypes = [C.c_int] * 3 + [vp]
-    L.ffl_pass1_weighted.argtypes = [vp, C.c_int, ip, vp, C.c_int, C.c_uint64]
-    L.ffl_radial_window_axes_weighted.argtypes = [vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, C.c_uint64]
-    L.ffl_weights_extra_bytes.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_size_t)]
-    L.ffl_cell_grid_check.argtypes = [C.c_int] * 3 + [ip, ip]
-    L.ffl_cell_stats.argtypes = [vp, C.c_int, ip, C.c_int, vp, vp, C.c_uint64]
-    L.ffl_radial_window_axes_centres.argtypes = [vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, C.c_ssize_t,
-                                                 vp, C.c_uint64]
-    L.ffl_cells_extra_bytes.argtypes = [C.c_int] * 3 + [C.POINTER(C.c_size_t)]
-    L.ffl_consistency_default_params.argtypes = [vp]
-    L.ffl_consistency_params_check.argtypes = [vp]
-    L.ffl_consistency_weights.argtypes = [vp, C.c_int, ip, ip, vp, vp, vp, C.c_uint64]
-    for name in EXPORTS:   # every _src sibling: the plain call's arguments plus const ffl_source_info *
-        if name.endswith("_src"):
-            getattr(L, name).argtypes = getattr(L, name[:-4]).argtypes + [vp]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -684,62 +692,37 @@ def device_count():
 
 def device_mem_info(device=0):
     """(free, total) bytes of device memory (hipMemGetInfo)."""
-    f, t = C.c_size_t(), C.c_size_t()
-    L = load()
-    if L.ffl_device_mem_info(int(device), C.byref(f), C.byref(t)) != FFL_OK:
-        raise FFLError(f"ffl_device_mem_info failed: {L.ffl_last_error(None).decode()}")
-    return f.value, t.value
+    return _sizes("ffl_device_mem_info", device, outs=2)
 
 
 def estimate_bytes(width, height, frame_slots, flow_slots, max_batch):
     """(device, pinned host) bytes a Context with these arguments allocates under the current "lanes" option."""
-    d, p = C.c_size_t(), C.c_size_t()
-    L = load()
-    if L.ffl_estimate_bytes(int(width), int(height), int(frame_slots), int(flow_slots), int(max_batch), C.byref(d), C.byref(p)) != FFL_OK:
-        raise FFLError(f"ffl_estimate_bytes failed: {L.ffl_last_error(None).decode()}")
-    return d.value, p.value
+    return _sizes("ffl_estimate_bytes", width, height, frame_slots, flow_slots, max_batch, outs=2)
 
 
 def axes_extra_bytes(width, height):
     """Device bytes the first radial_axes / radial_window_axes call of a Context of this size allocates (estimate_bytes does
     not count them)."""
-    b = C.c_size_t()
-    L = load()
-    if L.ffl_axes_extra_bytes(int(width), int(height), C.byref(b)) != FFL_OK:
-        raise FFLError(f"ffl_axes_extra_bytes failed: {L.ffl_last_error(None).decode()}")
-    return b.value
+    return _sizes("ffl_axes_extra_bytes", width, height)
 
 
 def weights_extra_bytes(width, height):
     """Device bytes the first pass1_weighted / radial_window_axes_weighted call of a Context of this size allocates
     (estimate_bytes does not count them)."""
-    b = C.c_size_t()
-    L = load()
-    if L.ffl_weights_extra_bytes(int(width), int(height), C.byref(b)) != FFL_OK:
-        raise FFLError(f"ffl_weights_extra_bytes failed: {L.ffl_last_error(None).decode()}")
-    return b.value
+    return _sizes("ffl_weights_extra_bytes", width, height)
+
+
+def cells_extra_bytes(width, height, cells):
+    """Device bytes the first cell_stats call of a Context allocates (estimate_bytes does not count them)."""
+    return _sizes("ffl_cells_extra_bytes", width, height, cells)
 
 
 def cell_grid(width, height, cells):
     """(cell_w, cell_h) of a cells x cells grid on a width x height field (ffl_cell_grid_check; rule G1 of DESIGN.md section
     17); FFLError with the rule where the grid is refused.  Needs no device."""
     gw, gh = C.c_int(), C.c_int()
-    L = load()
-    rc = L.ffl_cell_grid_check(int(width), int(height), int(cells), C.byref(gw), C.byref(gh))
-    if rc != FFL_OK:
-        err = FFLError(f"ffl error {rc}: {L.ffl_last_error(None).decode()}")
-        err.code = rc
-        raise err
+    _check(load().ffl_cell_grid_check(int(width), int(height), int(cells), C.byref(gw), C.byref(gh)))
     return gw.value, gh.value
-
-
-def cells_extra_bytes(width, height, cells):
-    """Device bytes the first cell_stats call of a Context allocates (estimate_bytes does not count them)."""
-    b = C.c_size_t()
-    L = load()
-    if L.ffl_cells_extra_bytes(int(width), int(height), int(cells), C.byref(b)) != FFL_OK:
-        raise FFLError(f"ffl_cells_extra_bytes failed: {L.ffl_last_error(None).decode()}")
-    return b.value
 
 
 def _centre_entries(centres, n_seq):
@@ -797,10 +780,8 @@ class Context:
         self.close()
 
     def _chk(self, rc):
-        if rc != FFL_OK:
-            e = FFLError(f"ffl error {rc}: {self.L.ffl_last_error(self._h).decode()}")
-            e.code = rc
-            raise e
+        if rc != FFL_OK:   # tested here: the per-batch calls pay one comparison
+            _check(rc, self._h)
 
     # ---- frames -------------------------------------------------------------------------------
     def upload_frame(self, fslot, frame):
@@ -876,12 +857,8 @@ class Context:
                f.strides[0] != f0.strides[0] for f in fr):
             raise FFLError("upload_frames_raw needs (h, w, 3) uint8 frames of one shape and row stride")
         ptrs = (C.c_void_p * len(fr))(*[f.ctypes.data for f in fr])
-        args = (self._h, first_slot, len(fr), ptrs, f0.shape[1], f0.shape[0], f0.strides[0], int(bool(rgb_order)),
-                int(resize[0]), int(resize[1]), int(crop[0]), int(crop[1]))
-        if info is not None:
-            self._chk(self.L.ffl_upload_frames_raw_src(*args, C.byref(info)))
-        else:
-            self._chk(self.L.ffl_upload_frames_raw(*args))
+        self._chk(_src_call(self.L, "ffl_upload_frames_raw", info, self._h, first_slot, len(fr), ptrs, f0.shape[1], f0.shape[0],
+                            f0.strides[0], int(bool(rgb_order)), int(resize[0]), int(resize[1]), int(crop[0]), int(crop[1])))
 
     def upload_frames_yuv(self, first_slot, frames, layout, resize, crop=(0, 0), depth=8, msb=None, rotate=0, mirror=False,
                           yuv_range="limited"):
@@ -909,13 +886,10 @@ class Context:
         ptrs = (C.c_void_p * len(fr))(*[f.ctypes.data for f in fr])
         head = (self._h, first_slot, len(fr), ptrs, f0.shape[1], f0.shape[0] * 2 // 3, f0.strides[0], code)
         geom = (int(resize[0]), int(resize[1]), int(crop[0]), int(crop[1]))
-        src = "_src" if info is not None else ""
-        if info is not None:
-            geom += (C.byref(info),)
         if es == 2:
-            self._chk(getattr(self.L, "ffl_upload_frames_yuv16" + src)(*head, depth, msb, *geom))
+            self._chk(_src_call(self.L, "ffl_upload_frames_yuv16", info, *head, depth, msb, *geom))
         else:
-            self._chk(getattr(self.L, "ffl_upload_frames_yuv" + src)(*head, *geom))
+            self._chk(_src_call(self.L, "ffl_upload_frames_yuv", info, *head, *geom))
 
     def upload_frames_device(self, first_slot, frames, fmt, resize=None, crop=(0, 0), stream=None, depth=8, msb=None,
                              rotate=0, mirror=False, yuv_range="limited"):
@@ -936,13 +910,10 @@ class Context:
         rw, rh = ((size[::-1] if info is not None and info.rotate in (90, 270) else size) if resize is None else resize)
         head = (self._h, int(first_slot), len(descs), descs.ctypes.data, code)
         geom = (size[0], size[1], int(rw), int(rh), int(crop[0]), int(crop[1]), stream_handle(stream, self.device))
-        src = "_src" if info is not None else ""
-        if info is not None:
-            geom += (C.byref(info),)
         if depth > 8:
-            self._chk(getattr(self.L, "ffl_upload_frames_device16" + src)(*head, depth, msb, *geom))
+            self._chk(_src_call(self.L, "ffl_upload_frames_device16", info, *head, depth, msb, *geom))
         else:
-            self._chk(getattr(self.L, "ffl_upload_frames_device" + src)(*head, *geom))
+            self._chk(_src_call(self.L, "ffl_upload_frames_device", info, *head, *geom))
 
     @staticmethod
     def _device_rows(frames, code, depth=8):
@@ -1268,7 +1239,7 @@ class Context:
     def profile_enable(self, classes=True):
         """classes: True (all), False/None (off) or an iterable of kernel-class names."""
         if classes is True:
-            mask = 0xFF
+            mask = FFL_PROFILE_ALL
         elif not classes:
             mask = 0
         else:
