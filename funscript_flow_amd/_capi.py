@@ -50,6 +50,13 @@ FFL_MAX_RADIUS = 32
 AXES = ("radial", "tangential", "shift_x", "shift_y")
 PASS2_AXES_DTYPE = np.dtype(PASS2_DTYPE.descr + [(k, "<f8") for k in AXES[1:] + ("reserved",)])
 
+# global-motion fit and compensation: FFL_MOTION_* models in order, the statuses, the
+# twelve sums of rule C4 in order, and ffl_motion_record
+MOTION_MODELS = ("translation", "rigid", "similarity", "affine")
+MOTION_STATUS = ("ok", "empty", "degenerate")
+MOTION_SUMS = ("S", "Sx", "Sy", "Sxx", "Sxy", "Syy", "Su", "Sux", "Suy", "Sv", "Svx", "Svy")
+MOTION_DTYPE = np.dtype([(k, "<f8") for k in ("a0", "a1", "a2", "b0", "b1", "b2", "sw")] + [("model", "<i4"), ("status", "<i4")])
+
 FLOWS = ("farneback", "dis")   # params["hip_flow"]: the reference's CPU/CUDA/OpenCL branch, or its "DNN" branch (FF:948-980)
 DIS_STAGES = {"pass1": 0, "pass2": 1, "dense": 2, "refined": 3, "images": 4}   # ffl_debug_dis_pair stages
 
@@ -505,6 +512,73 @@ def consistency_choice(params):
     return params
 
 
+class MotionParams(C.Structure):
+    """ffl_motion_params: the sub-model of rule C2 (a name of MOTION_MODELS or its code), the passes of
+    rule C7 and the Cauchy scale tau of rule C3 in pixels.  MotionParams() holds the library's defaults (rule C9: translation,
+    3 passes, tau 1.0 -- the project's own choice, not tuned on footage); keywords override single fields."""
+    _fields_ = [("model", C.c_int), ("iterations", C.c_int), ("tau", C.c_float)]
+
+    def __init__(self, **over):
+        super().__init__()
+        load().ffl_motion_default_params(C.byref(self))
+        for k, v in over.items():
+            if k not in ("model", "iterations", "tau"):
+                raise ValueError(f"unknown motion parameter {k!r} (model, iterations, tau)")
+            setattr(self, k, motion_model(v) if k == "model" else v)
+
+    def as_dict(self):
+        return {"model": MOTION_MODELS[self.model], "iterations": self.iterations, "tau": self.tau}
+
+
+def motion_model(model):
+    """FFL_MOTION_* code of a name of MOTION_MODELS (or of the code itself); ValueError for anything else"""
+    if isinstance(model, str) and model.lower() in MOTION_MODELS:
+        return MOTION_MODELS.index(model.lower())
+    if not isinstance(model, (str, bool)) and model in range(len(MOTION_MODELS)):
+        return int(model)
+    raise ValueError(f"motion model must be one of {MOTION_MODELS}, got {model!r}")
+
+
+def motion_params_check(params):
+    """ffl_motion_params_check: ValueError with the library's rule when it refuses (pure host check)."""
+    _check(load().ffl_motion_params_check(None if params is None else C.byref(params)), exc=ValueError)
+
+
+def motion_choice(compensate):
+    """a checked MotionParams out of a model name, a dict of its fields or a MotionParams (compensate= / params["hip_compensate"])"""
+    if isinstance(compensate, str):
+        compensate = {"model": compensate}
+    if not isinstance(compensate, MotionParams):
+        compensate = MotionParams(**dict(compensate))
+    motion_params_check(compensate)
+    return compensate
+
+
+def motion_solve(sums, model):
+    """ffl_motion_solve: rules C5 and C6 on twelve float64 sums in MOTION_SUMS' order -> one MOTION_DTYPE record (a numpy
+    array of shape ()).  The host compiles the source of the device's solve, so these are the device's bits.  Needs no device."""
+    ps, keep = _darr(sums)
+    if keep.shape != (len(MOTION_SUMS),):
+        raise ValueError(f"motion_solve: {len(MOTION_SUMS)} sums are needed, got shape {keep.shape}")
+    out = np.zeros((), MOTION_DTYPE)
+    _check(load().ffl_motion_solve(ps, motion_model(model), out.ctypes.data), exc=ValueError)
+    return out
+
+
+def _model_entries(models, n, name):
+    """(pointer, byte stride) of n models in device memory: a float64 (n, 6) array, rows any multiple of 8 bytes apart, or a
+    contiguous buffer of n MOTION_DTYPE records"""
+    ptr, shp, st, ts = _array_view(models)
+    if ts in ("<f8", "torch.float64") and len(shp) == 2:
+        if shp != (n, 6) or st[1] != 8:
+            raise ValueError(f"{name}: float64 shape {shp} with byte strides {st}, ({n}, 6) with adjacent coefficients is needed")
+        return ptr, (st[0] if n > 1 else 48)
+    ptr, extent = _device_span(models)
+    if extent < n * MOTION_DTYPE.itemsize:
+        raise ValueError(f"{name}: {extent} bytes, {n} motion records need {n * MOTION_DTYPE.itemsize}")
+    return ptr, MOTION_DTYPE.itemsize
+
+
 def stream_handle(stream, device=0):
     """hipStream_t of `stream` as an int: None = torch's current stream on `device` when torch is already imported (else
     0, the null stream); a torch.cuda.Stream; or an int as it is."""
@@ -617,6 +691,12 @@ SIGNATURES = {
     "ffl_cell_stats": (_i, (_ctx, _i, _ip, _i, _vp, _vp, _u64)),
     "ffl_radial_window_axes_centres": (_i, _WINDOW + (_vp, _pd, _vp, _u64)),
     "ffl_cells_extra_bytes": (_i, (_i,) * 3 + (_szp,)),
+    "ffl_motion_default_params": (_i, (_P(MotionParams),)),
+    "ffl_motion_params_check": (_i, (_P(MotionParams),)),
+    "ffl_motion_solve": (_i, (_dp, _i, _vp)),
+    "ffl_motion_extra_bytes": (_i, (_i, _i, _szp)),
+    "ffl_motion_fit": (_i, (_ctx, _i, _ip, _P(MotionParams), _P(DevWeights), _vp, _pd, _vp, _vp, _u64)),
+    "ffl_motion_subtract": (_i, (_ctx, _i, _ip, _ip, _vp, _pd, _i, _u64)),
     "ffl_download_flow": (_i, (_ctx, _i, _vp)),
     "ffl_upload_flow": (_i, (_ctx, _i, _vp, _i)),
     "ffl_submit_pair": (_i, (_ctx, _i, _vp, _vp, _i, _i, _i, _pd, _i)),
@@ -649,7 +729,8 @@ EXPORTS = list(SIGNATURES)   # every symbol include/ffl.h declares
 # the header's records and their Python statements (the test takes the struct names from the header: none can be forgotten)
 RECORDS = {"ffl_source_info": SourceInfo, "ffl_dev_frame": DevFrame, "ffl_dev_flow": DevFlow, "ffl_pass2_record": PASS2_DTYPE,
            "ffl_axes_record": PASS2_AXES_DTYPE, "ffl_dev_weights": DevWeights, "ffl_consistency_params": ConsistencyParams,
-           "ffl_cell_record": CELL_DTYPE, "ffl_grid_centre": GRID_CENTRE_DTYPE, "ffl_dis_params": DisParams,
+           "ffl_cell_record": CELL_DTYPE, "ffl_grid_centre": GRID_CENTRE_DTYPE, "ffl_motion_params": MotionParams,
+           "ffl_motion_record": MOTION_DTYPE, "ffl_dis_params": DisParams,
            "ffl_farneback_params": FarnebackParams}
 
 _lib = None
@@ -715,6 +796,11 @@ def weights_extra_bytes(width, height):
 def cells_extra_bytes(width, height, cells):
     """Device bytes the first cell_stats call of a Context allocates (estimate_bytes does not count them)."""
     return _sizes("ffl_cells_extra_bytes", width, height, cells)
+
+
+def motion_extra_bytes(width, height):
+    """Device bytes the first motion_fit call of a Context of this size allocates (estimate_bytes does not count them)."""
+    return _sizes("ffl_motion_extra_bytes", width, height)
 
 
 def cell_grid(width, height, cells):
@@ -1165,6 +1251,48 @@ class Context:
         ptr, stride = _centre_entries(centres, len(seq_slots))
         return self._radial_window(self.L.ffl_radial_window_axes_centres, "radial_window_axes_centres", PASS2_AXES_DTYPE,
                                    seq_slots, first, n, out, radius, cut_threshold, pov_mode, stream, weights=(ptr, stride))
+
+    def motion_fit(self, slots, model="translation", iterations=3, tau=1.0, weights=None, prior=None, out=None, sums_out=None,
+                   stream=None):
+        """Fit a camera model to the field of every slot (ffl_motion_fit): `model` a name of
+        MOTION_MODELS -- or a MotionParams, which then also gives iterations and tau -- fitted by `iterations` passes of
+        Cauchy-weighted least squares with scale `tau` px.  "similarity" and "affine" contain a zoom term, which is the radial
+        signal itself (rule C9).  `weights`: maps as pass1_weighted takes them, (H, W) or (n, H, W), which also weight the fit;
+        `prior`: the first pass's prior per slot in device memory, a float64 (n, 6) tensor or a buffer of MOTION_DTYPE records;
+        `out`: device memory for n MOTION_DTYPE records (None: a new torch buffer); `sums_out`: device memory for n * 12
+        float64, the last pass's sums.  The flow is only read.  Queued behind the work on `stream` (None: torch's current
+        stream), which waits for it; the host does not wait.  Returns `out`."""
+        ps, ks = _iarr(slots)
+        n = len(ks)
+        prm = model if isinstance(model, MotionParams) else MotionParams(model=model, iterations=int(iterations), tau=float(tau))
+        wdesc = None if weights is None else self._weights("motion_fit", weights, n)
+        pptr, pstride = (None, 0) if prior is None else _model_entries(prior, n, "motion_fit: prior")
+        if out is None:
+            import torch
+            out = torch.empty(n * MOTION_DTYPE.itemsize, dtype=torch.uint8, device=torch.device("cuda", self.device))
+        optr, extent = _device_span(out)
+        if extent < n * MOTION_DTYPE.itemsize:
+            raise ValueError(f"motion_fit: out holds {extent} bytes, {n} records need {n * MOTION_DTYPE.itemsize}")
+        sptr = None
+        if sums_out is not None:
+            sptr, extent = _device_span(sums_out)
+            if extent < n * len(MOTION_SUMS) * 8:
+                raise ValueError(f"motion_fit: sums_out holds {extent} bytes, {n} items need {n * len(MOTION_SUMS) * 8}")
+        self._chk(self.L.ffl_motion_fit(self._h, n, ps, C.byref(prm), None if wdesc is None else C.byref(wdesc), pptr, pstride,
+                                        optr, sptr, stream_handle(stream, self.device)))
+        return out
+
+    def motion_subtract(self, src, dst, models, pov_mode=False, stream=None):
+        """Subtract item i's model from the field of slot src[i] into slot dst[i] (ffl_motion_subtract, rule C8), then the
+        pass-1 reductions of the dst slots: their records are upload_flow's for the compensated field.  dst[i] == src[i] is in
+        place.  `models`: device memory, motion_fit's records or a float64 (n, 6) tensor.  Queued behind the work on `stream`
+        (None: torch's current stream), which waits for it; the host does not wait."""
+        (ps, ks), (pd, kd) = _iarr(src), _iarr(dst)
+        if len(ks) != len(kd):
+            raise ValueError(f"motion_subtract: {len(ks)} src slots for {len(kd)} dst slots")
+        mptr, mstride = _model_entries(models, len(ks), "motion_subtract: models")
+        self._chk(self.L.ffl_motion_subtract(self._h, len(ks), ps, pd, mptr, mstride, int(bool(pov_mode)),
+                                             stream_handle(stream, self.device)))
 
     def download_frame(self, fslot):
         out = np.empty((self.height, self.width), np.uint8)

@@ -10,7 +10,9 @@ Same names, argument meaning and result shape as the reference's pair functions:
     (params["hip_flow"] = "dis" runs DIS -- the reference's "DNN" branch, FF:948-980 -- instead of Farneback;
     params["hip_dis"] = {field: value} overrides single _capi.DisParams fields; params["hip_farneback"] = {cv2 keyword: value}
     sets calcOpticalFlowFarneback's parameters and params["hip_farneback_window"] = "gaussian" its
-    OPTFLOW_FARNEBACK_GAUSSIAN window)
+    OPTFLOW_FARNEBACK_GAUSSIAN window; params["hip_compensate"] = "translation" | "rigid" |
+    "similarity" | "affine", or a dict of the three _capi.MotionParams fields, fits a camera model to every pair's field and
+    subtracts it before anything is reduced -- "flow" is then the compensated field)
     radial_all(precomputed, centers, pov_mode)   the whole ProcessPoolExecutor loop of FF:1232-1236
     get_available_backends()               FF:32-63  (reports "HIP" when a device is usable)
 
@@ -252,6 +254,10 @@ def precompute_all(pairs, params):
     eng.depth = 2 if ctx.frame_slots >= pipeline.min_frame_slots(B, 2) else 1
     out = [None] * len(pairs)
     serial = ctx._chunk_serial
+    # "hip_compensate": the fit and the subtraction in place behind every batch, before its records are collected
+    comp = pipeline._chunk_motion(ctx, len(pairs), pipeline.compensate_kwargs(params).get("compensate"), None, None,
+                                  ctx.flow_slots, pov)
+    hook = pipeline._behind_kw(comp)
 
     def on_batch(ls, js, got):   # the dicts of a finished batch are built while the device runs the next ones
         for l, (x, y, val, mean_mag, cut) in zip(ls, got):
@@ -261,10 +267,10 @@ def precompute_all(pairs, params):
                       "val_pos": val_pos, "val_neg": val_pos, "cut": cut, "cut_center": pos_center[0], "mean_mag": mean_mag}
 
     if stream:
-        eng.pass1_pairs(frames, range(len(pairs)), lambda l: l, pov, thr, on_batch=on_batch)
+        eng.pass1_pairs(frames, range(len(pairs)), lambda l: l, pov, thr, on_batch=on_batch, **hook)
     else:  # arbitrary pairs: every pair brings its own two frames
         flat = [f for p in pairs for f in p]
-        eng.pass1_pairs(flat, range(0, 2 * len(pairs), 2), lambda l: l, pov, thr, on_batch=on_batch)
+        eng.pass1_pairs(flat, range(0, 2 * len(pairs), 2), lambda l: l, pov, thr, on_batch=on_batch, **hook)
     return out
 
 

@@ -348,6 +348,8 @@ struct ffl_ctx {
     DevBuf<double> d_wpsum;
     // ffl_cell_stats: t_i and x_i of rule G5 per cell row, FFL_MAX_CELLS rows per item.
     DevBuf<double> d_cellrow;
+    // ffl_motion_fit: FFL_MOTION_NSUMS partials per workgroup of the radial grid.
+    DevBuf<double> d_mpsum;
     int p1_blocks = 0;
     // profiling
     unsigned prof_mask = 0;   // bit k set: bracket every launch of kernel class k with HIP events
@@ -2075,9 +2077,9 @@ int ffl_pass1_results(ffl_ctx *c, int n, const int *slots, float cut_threshold, 
 }
 
 // The extra scratch of stream `post` (the DevBuf<double> members of ffl_ctx under "extra scratch"): what a context gains with
-// the first four-component, weighted or ffl_cell_stats call, in doubles for FFL_MAXB items.  The ffl_*_extra_bytes entry points
+// the first four-component, weighted, ffl_cell_stats or ffl_motion_fit call, in doubles for FFL_MAXB items.  The ffl_*_extra_bytes entry points
 // report a row, post_scratch allocates it.
-enum { SCR_AXES = 0, SCR_WEIGHTS, SCR_CELLS };
+enum { SCR_AXES = 0, SCR_WEIGHTS, SCR_CELLS, SCR_MOTION };
 struct PostScratchRow {
     size_t (*doubles)(int w, int h);
     const char *name;               // in the message of a failed allocation
@@ -2094,6 +2096,9 @@ static const PostScratchRow kPostScratch[] = {
      }, "weighted", &ffl_ctx::d_wpsum},
     // the row sums of rule G5, whatever the size and the grid
     {[](int, int) { return (size_t)2 * FFL_MAX_CELLS * FFL_MAXB; }, "cell-row", &ffl_ctx::d_cellrow},
+    // the twelve sums of rule C4 per workgroup of the radial grid
+    {[](int w, int h) { return (size_t)FFL_MOTION_NSUMS * (size_t)ffl_radial_blocks(w, h) * FFL_MAXB; }, "motion-fit",
+     &ffl_ctx::d_mpsum},
 };
 
 static int cell_grid_check(ffl_ctx *c, const char *fn, int width, int height, int cells, int *cell_w, int *cell_h);
@@ -2119,6 +2124,10 @@ int ffl_weights_extra_bytes(int width, int height, size_t *bytes) {
 
 int ffl_cells_extra_bytes(int width, int height, int cells, size_t *bytes) {
     return post_scratch_bytes("ffl_cells_extra_bytes", SCR_CELLS, width, height, cells, bytes);
+}
+
+int ffl_motion_extra_bytes(int width, int height, size_t *bytes) {
+    return post_scratch_bytes("ffl_motion_extra_bytes", SCR_MOTION, width, height, 0, bytes);
 }
 
 // The first call that needs a row allocates it (the caller holds post_mu and the context lock).  The axes row comes with
@@ -2827,6 +2836,149 @@ int ffl_cell_stats(ffl_ctx *c, int n, const int *slots, int cells, ffl_cell_reco
     ffl_launch_cell_stats(c->d_flow, t, n, c->w, c->h, cells, (CellRecord *)cells_dev, (GridCentre *)centres_dev, c->d_cellrow,
                           c->s_post);
     return post_end(c, cst, n, slots);  // the caller may read, overwrite or free the outputs on `stream` straight after the call
+}
+
+// ---- global-motion fit and compensation ---------------------------------------------
+static_assert(sizeof(ffl_motion_record) == 64 && sizeof(MotionRecord) == 64 && offsetof(ffl_motion_record, a0) == 0 &&
+              offsetof(MotionRecord, a0) == 0 && offsetof(ffl_motion_record, b0) == 24 && offsetof(MotionRecord, b0) == 24 &&
+              offsetof(ffl_motion_record, sw) == 48 && offsetof(MotionRecord, sw) == 48 && offsetof(ffl_motion_record, model) == 56 &&
+              offsetof(MotionRecord, model) == 56 && offsetof(ffl_motion_record, status) == 60 && offsetof(MotionRecord, status) == 60 &&
+              alignof(ffl_motion_record) == 8, "MotionRecord mirrors ffl_motion_record");
+static_assert(FFL_MOTION_N_SUMS == FFL_MOTION_NSUMS && FFL_MOTION_TRANSLATION == MOT_TRANSLATION && FFL_MOTION_RIGID == MOT_RIGID &&
+              FFL_MOTION_SIMILARITY == MOT_SIMILARITY && FFL_MOTION_AFFINE == MOT_AFFINE && FFL_MOTION_OK == MOT_OK &&
+              FFL_MOTION_EMPTY == MOT_EMPTY && FFL_MOTION_DEGENERATE == MOT_DEGENERATE, "ffl.h and ffl_kernels.h agree");
+
+int ffl_motion_default_params(ffl_motion_params *out) {   // rule C9
+    if (!out) return FFL_ERR_INVALID;
+    *out = ffl_motion_params{FFL_MOTION_TRANSLATION, 3, 1.0f};
+    return FFL_OK;
+}
+
+// The accepted parameters of appendix C.  The comparisons are written so that a NaN fails them.
+static int motion_params_check(ffl_ctx *c, const char *fn, const ffl_motion_params *p) {
+    if (!p) return set_err(c, FFL_ERR_INVALID, "%s: NULL parameters", fn);
+    if (p->model < FFL_MOTION_TRANSLATION || p->model > FFL_MOTION_AFFINE)
+        return set_err(c, FFL_ERR_INVALID, "%s: rule C2: model = %d is none of FFL_MOTION_TRANSLATION 0, RIGID 1, SIMILARITY 2, AFFINE 3",
+                       fn, p->model);
+    if (p->iterations < 1 || p->iterations > 8)
+        return set_err(c, FFL_ERR_INVALID, "%s: rule C7: iterations = %d outside 1..8", fn, p->iterations);
+    if (!(p->tau > 0.0f && p->tau <= 1e6f))
+        return set_err(c, FFL_ERR_INVALID, "%s: rule C3: tau = %g outside 0 < tau <= 1e6 (finite)", fn, (double)p->tau);
+    return FFL_OK;
+}
+
+int ffl_motion_params_check(const ffl_motion_params *p) { return motion_params_check(nullptr, "ffl_motion_params_check", p); }
+
+int ffl_motion_solve(const double *sums, int model, ffl_motion_record *out) {
+    static const char *fn = "ffl_motion_solve";
+    if (!sums || !out) return set_err(nullptr, FFL_ERR_INVALID, "%s: NULL %s", fn, !sums ? "sums" : "out");
+    if (model < FFL_MOTION_TRANSLATION || model > FFL_MOTION_AFFINE)
+        return set_err(nullptr, FFL_ERR_INVALID, "%s: rule C2: model = %d is none of FFL_MOTION_TRANSLATION 0, RIGID 1, SIMILARITY 2, "
+                                                 "AFFINE 3", fn, model);
+    MotionRecord r;
+    ffl_motion_solve_body(sums, model, &r);
+    memcpy(out, &r, sizeof r);
+    return FFL_OK;
+}
+
+static const char *kHostModels = "models, sums and priors live in device memory (torch / hipMalloc)";
+
+// six doubles per item at `stride` bytes: rule C2's model as ffl_motion_fit's prior and ffl_motion_subtract's models read it
+static int model_array_check(ffl_ctx *c, const char *fn, const char *what, const void *p, ptrdiff_t stride) {
+    if ((uintptr_t)p % 8) return set_err(c, FFL_ERR_INVALID, "%s: %s must be 8-byte aligned", fn, what);
+    if (stride < 48 || stride % 8 || stride > ((ptrdiff_t)1 << 40))
+        return set_err(c, FFL_ERR_INVALID, "%s: %s stride %td: a multiple of 8 bytes, at least 48 (six doubles)", fn, what, stride);
+    return FFL_OK;
+}
+
+// `iterations` times k_motion_fit + k_motion_solve over n slots that hold a flow, on stream `post`: ffl_pass1_weighted's protocol
+// with the flow and its records only read.  Pass k + 1 reads the records pass k wrote (rule C7), on the one stream.
+int ffl_motion_fit(ffl_ctx *c, int n, const int *slots, const ffl_motion_params *p, const ffl_dev_weights *w, const void *prior_dev,
+                   ptrdiff_t prior_stride, ffl_motion_record *models_dev, double *sums_dev, uint64_t stream) {
+    static const char *fn = "ffl_motion_fit";
+    if (!c) return FFL_ERR_INVALID;
+    std::unique_lock<std::mutex> pl(c->post_mu);  // stream `post` and d_mpsum
+    CtxLock lk(c->mu);
+    ExportTab t;
+    if (int rc = open_slot_list(c, fn, "slots", n, slots, "flow", &t)) return rc;
+    ffl_motion_params prm;
+    ffl_motion_default_params(&prm);
+    if (p) prm = *p;
+    if (int rc = motion_params_check(c, fn, &prm)) return rc;
+    size_t wbytes = 0;
+    if (w)
+        if (int rc = dev_weights_check(c, fn, n, c->w, c->h, w, &wbytes)) return rc;
+    if (!models_dev) return set_err(c, FFL_ERR_INVALID, "%s: NULL models_dev", fn);
+    if ((uintptr_t)models_dev % 8 || (uintptr_t)sums_dev % 8) return set_err(c, FFL_ERR_INVALID, "%s: models_dev and sums_dev must be 8-byte aligned", fn);
+    const size_t mbytes = sizeof(ffl_motion_record) * (size_t)n;
+    size_t pbytes = 0;
+    if (prior_dev) {
+        if (int rc = model_array_check(c, fn, "prior_dev", prior_dev, prior_stride)) return rc;
+        pbytes = (size_t)(n - 1) * (size_t)prior_stride + 48;
+        const uintptr_t m0 = (uintptr_t)models_dev, p0 = (uintptr_t)prior_dev;
+        if (prm.iterations > 1 && m0 < p0 + pbytes && p0 < m0 + mbytes)
+            return set_err(c, FFL_ERR_INVALID, "%s: rule C7: overlap: models_dev (%zu bytes) and prior_dev (%zu bytes) share memory "
+                                               "with iterations = %d (pass 2 reads models_dev as its prior)", fn, mbytes, pbytes, prm.iterations);
+    }
+    PostRegion reg[4];
+    int nreg = 0;
+    reg[nreg++] = PostRegion{"models_dev", models_dev, mbytes, kHostModels};
+    if (sums_dev) reg[nreg++] = PostRegion{"sums_dev", sums_dev, sizeof(double) * FFL_MOTION_N_SUMS * (size_t)n, kHostModels};
+    if (prior_dev) reg[nreg++] = PostRegion{"prior_dev", prior_dev, pbytes, kHostModels};
+    if (w) reg[nreg++] = PostRegion{"the weight maps", w->base, wbytes, kHostWeights};
+    hipStream_t cst;
+    if (int rc = post_begin(c, fn, stream, &cst, reg, nreg, n, slots)) return rc;
+    if (int rc = post_scratch(c, fn, SCR_MOTION)) return rc;
+    WeightArgs wa{};
+    if (w) wa = WeightArgs{(const char *)w->base, (long long)w->item_stride, (long long)w->row_pitch};
+    for (int k = 0; k < prm.iterations; k++) {
+        const MotionPrior pr = k == 0 ? MotionPrior{(const char *)prior_dev, (long long)prior_stride}
+                                      : MotionPrior{(const char *)models_dev, (long long)sizeof(ffl_motion_record)};
+        ffl_launch_motion_fit(c->d_flow, t, n, c->w, c->h, w ? &wa : nullptr, pr, prm.tau, prm.model, c->d_mpsum,
+                              (MotionRecord *)models_dev, k == prm.iterations - 1 ? sums_dev : nullptr, c->s_post);
+    }
+    return post_end(c, cst, n, slots);  // the caller may read the records, or overwrite the maps, on `stream` straight after the call
+}
+
+// k_motion_subtract into the dst slots, then the k_pass1 / k_pass1_final pair over them, on stream `post`: ffl_pass1_weighted's
+// protocol over the src and the dst slots.  The dst slots hold a flow and an ordinary record afterwards.
+int ffl_motion_subtract(ffl_ctx *c, int n, const int *src_slots, const int *dst_slots, const void *models_dev, ptrdiff_t model_stride,
+                        int pov_mode, uint64_t stream) {
+    static const char *fn = "ffl_motion_subtract";
+    if (!c) return FFL_ERR_INVALID;
+    std::unique_lock<std::mutex> pl(c->post_mu);  // stream `post`, d_ptab and the pass-1 partials, as ffl_import_flows
+    CtxLock lk(c->mu);
+    if (n < 1 || n > c->max_batch)
+        return set_err(c, FFL_ERR_INVALID, "%s: n = %d items outside 1..%d (the context's max_batch)", fn, n, c->max_batch);
+    if (!src_slots || !dst_slots) return set_err(c, FFL_ERR_INVALID, "%s: NULL %s", fn, !src_slots ? "src_slots" : "dst_slots");
+    if (int rc = check_flow_slots(c, fn, n, src_slots, "flow", "repeated among the src slots of one call")) return rc;
+    if (int rc = check_flow_slots(c, fn, n, dst_slots, nullptr, "repeated among the dst slots of one call")) return rc;
+    // the src slots are distinct: a dst slot that is a src slot and not its own item's is another item's
+    int clash = -1;
+    for (int i = 0; i < n; i++) c->slot_mark[src_slots[i]] = 1;
+    for (int i = 0; i < n; i++)
+        if (c->slot_mark[dst_slots[i]] && dst_slots[i] != src_slots[i] && clash < 0) clash = dst_slots[i];
+    for (int i = 0; i < n; i++) c->slot_mark[src_slots[i]] = 0;
+    if (clash >= 0) return set_err(c, FFL_ERR_INVALID, "%s: dst flow slot %d is another item's src slot", fn, clash);
+    if (!models_dev) return set_err(c, FFL_ERR_INVALID, "%s: NULL models_dev", fn);
+    if (int rc = model_array_check(c, fn, "models_dev", models_dev, model_stride)) return rc;
+    int all[2 * FFL_MAXB], m = 0;   // every slot the call reads or writes, once
+    ExportTab ts, td;
+    for (int i = 0; i < n; i++) all[m++] = ts.slot[i] = src_slots[i];
+    for (int i = 0; i < n; i++) {
+        td.slot[i] = dst_slots[i];
+        if (dst_slots[i] != src_slots[i]) all[m++] = dst_slots[i];
+    }
+    hipStream_t cst;
+    const PostRegion reg{"models_dev", models_dev, (size_t)(n - 1) * (size_t)model_stride + 48, kHostModels};
+    if (int rc = post_begin(c, fn, stream, &cst, &reg, 1, m, all)) return rc;
+    ffl_launch_motion_subtract(c->d_flow, c->d_res, ts, td, n, c->w, c->h, (const char *)models_dev, (long long)model_stride, c->d_ptab,
+                               c->s_post);
+    {
+        ProfScope ps(c, FFL_K_PASS1, c->s_post);
+        ffl_launch_pass1(c->d_ptab, n, c->w, c->h, pov_mode ? 1 : 0, c->d_pskey, c->d_rpsum, c->s_post);
+    }
+    return post_end(c, cst, m, all);
 }
 
 // ---- flow import -------------------------------------------------------------------------------

@@ -306,6 +306,109 @@ void ffl_launch_consistency(const float *flow, const ExportTab &fwd, const Expor
                             float beta, int soft, const WeightArgs *gate, char *out, long long out_item, long long out_pitch,
                             hipStream_t st);
 
+// ---- global-motion fit and compensation (kernels_post.hip) -----------------------
+#define FFL_MOTION_NSUMS 12          // = FFL_MOTION_N_SUMS of include/ffl.h; the order of rule C4
+enum { MOT_S = 0, MOT_SX, MOT_SY, MOT_SXX, MOT_SXY, MOT_SYY, MOT_SU, MOT_SUX, MOT_SUY, MOT_SV, MOT_SVX, MOT_SVY };
+enum { MOT_TRANSLATION = 0, MOT_RIGID = 1, MOT_SIMILARITY = 2, MOT_AFFINE = 3 };   // = FFL_MOTION_* of include/ffl.h
+enum { MOT_OK = 0, MOT_EMPTY = 1, MOT_DEGENERATE = 2 };
+struct MotionRecord {  // = ffl_motion_record of include/ffl.h (ffl_api.hip asserts the layout)
+    double a0, a1, a2, b0, b1, b2;   // rule C2
+    double sw;                       // S of the last pass
+    int model, status;
+};
+struct MotionPrior {   // the six doubles of n priors in device memory, `stride` bytes apart (NULL base: none)
+    const char *base;
+    long long stride;
+};
+
+// Rules C5 and C6: the weighted least-squares model of `model` out of the twelve sums s[] (rule C4's order), line for line the
+// text of DESIGN.md appendix C.  ONE body for ffl_motion_solve on the host and k_motion_solve on the device; both are compiled
+// with -ffp-contract=off, so every line is one rounding per written operation on either side.  A pivot passes when it is
+// > 1e-12 * its diagonal entry before elimination (a NaN does not).
+__host__ __device__ inline void ffl_motion_solve_body(const double *s, int model, MotionRecord *out) {
+    const double S = s[MOT_S], Sx = s[MOT_SX], Sy = s[MOT_SY], Sxx = s[MOT_SXX], Sxy = s[MOT_SXY], Syy = s[MOT_SYY];
+    const double Su = s[MOT_SU], Sux = s[MOT_SUX], Suy = s[MOT_SUY], Sv = s[MOT_SV], Svx = s[MOT_SVX], Svy = s[MOT_SVY];
+    MotionRecord r;
+    r.a0 = r.a1 = r.a2 = r.b0 = r.b1 = r.b2 = 0.0;
+    r.sw = S;
+    r.model = model;
+    r.status = MOT_EMPTY;
+    if (S == 0.0) {   // C6: no division is executed
+        *out = r;
+        return;
+    }
+    const double ta = Su / S, tb = Sv / S;   // C5.T
+    r.a0 = ta;
+    r.b0 = tb;
+    r.status = MOT_OK;
+    const double eps = 1e-12;
+    if (model == MOT_RIGID || model == MOT_SIMILARITY) {   // C5.R / C5.S: one pivot D behind the two pivots S
+        const double Q = Sxx + Syy;
+        const double q = Sx / S, p = Sy / S;
+        const double D = (Q - q * Sx) - p * Sy;
+        if (!(S > eps * S) || !(D > eps * Q)) {
+            r.status = MOT_DEGENERATE;
+        } else {
+            const double g3 = Svx - Suy;
+            const double z3 = (g3 + p * Su) - q * Sv;
+            const double rot = z3 / D;
+            double sc = 0.0;
+            if (model == MOT_SIMILARITY) {
+                const double g2 = Sux + Svy;
+                const double z2 = (g2 - q * Su) - p * Sv;
+                sc = z2 / D;
+            }
+            r.a0 = (ta - q * sc) + p * rot;
+            r.b0 = (tb - p * sc) - q * rot;
+            r.a1 = sc;
+            r.a2 = -rot;
+            r.b1 = rot;
+            r.b2 = sc;
+        }
+    } else if (model == MOT_AFFINE) {   // C5.A: LDL^T of [[S, Sx, Sy], [Sx, Sxx, Sxy], [Sy, Sxy, Syy]], two right-hand sides
+        bool ok = S > eps * S;
+        double l10 = 0.0, l20 = 0.0, l21 = 0.0, d1 = 0.0, d2 = 0.0;
+        if (ok) {
+            l10 = Sx / S;
+            l20 = Sy / S;
+            d1 = Sxx - l10 * Sx;
+            ok = d1 > eps * Sxx;
+        }
+        if (ok) {
+            const double m21 = Sxy - l20 * Sx;
+            l21 = m21 / d1;
+            d2 = (Syy - l20 * Sy) - l21 * m21;
+            ok = d2 > eps * Syy;
+        }
+        if (!ok) {
+            r.status = MOT_DEGENERATE;
+        } else {
+            const double za1 = Sux - l10 * Su, za2 = (Suy - l20 * Su) - l21 * za1;
+            const double zb1 = Svx - l10 * Sv, zb2 = (Svy - l20 * Sv) - l21 * zb1;
+            r.a2 = za2 / d2;
+            r.a1 = za1 / d1 - l21 * r.a2;
+            r.a0 = (ta - l10 * r.a1) - l20 * r.a2;
+            r.b2 = zb2 / d2;
+            r.b1 = zb1 / d1 - l21 * r.b2;
+            r.b0 = (tb - l10 * r.b1) - l20 * r.b2;
+        }
+    }
+    *out = r;
+}
+
+// One fit pass: the twelve sums of rule C4 of flow slots tab.slot[0..n) into psum (FFL_MOTION_NSUMS * ffl_radial_blocks(w, h)
+// doubles per item), then per item the solve into the record at models + b * sizeof(MotionRecord) and, when sums != NULL, its
+// twelve sums at sums + 12 * b.  maps NULL: no map.  prior.base NULL: no prior; else item b's prior is six doubles at
+// prior.base + b * prior.stride.
+void ffl_launch_motion_fit(const float *flow, const ExportTab &tab, int n, int w, int h, const WeightArgs *maps,
+                           const MotionPrior &prior, float tau, int model, double *psum, MotionRecord *models, double *sums,
+                           hipStream_t st);
+// Rule C8: slot dst.slot[b] = slot src.slot[b] minus the model of item b (six doubles at models + b * stride); dst.slot[b] ==
+// src.slot[b] is in place.  The launch also names the dst slots and their records (res + slot) in pt, for the ffl_launch_pass1
+// the caller queues behind it.
+void ffl_launch_motion_subtract(float *flow, Pass1Result *res, const ExportTab &src, const ExportTab &dst, int n, int w, int h,
+                                const char *models, long long stride, PairTab *pt, hipStream_t st);
+
 // ---- index rules shared by the kernel files ----------------------------------------------------------------------
 __device__ __forceinline__ int ffl_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 

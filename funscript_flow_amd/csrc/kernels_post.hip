@@ -6,6 +6,7 @@
 // are reproducible run to run (no float atomics).
 #include "ffl_kernels.h"
 #include <cassert>
+#include <cfloat>
 #include <type_traits>
 
 #define P1_THREADS 256
@@ -1036,4 +1037,250 @@ void ffl_launch_pass1_weighted(const WeightArgs &wa, float *flow, Pass1Result *r
     const ImportArgs a{wa.base, wa.item, wa.pitch, 1, 0, flow, res};
     hipLaunchKernelGGL(k_pass1_weighted, dim3(nblk, n), dim3(P1_THREADS), 0, st, a, tab, w, h, pov_mode, pt, pkey, psum, psw);
     hipLaunchKernelGGL(k_pass1_weighted_final, dim3(n), dim3(P1_THREADS), 0, st, pt, w, h, pov_mode, nblk, pkey, psum, psw);
+}
+
+// ---- global-motion fit and compensation (ffl_motion_fit, ffl_motion_subtract) --------
+// k_motion_fit is k_radial's walk -- P2_STRIP columns per wave, one 16-byte load for a lane's two pixels, a row group of P1_RG
+// rows, WtNone / WtBytes for the map -- with the twelve float64 sums of rule C4 per lane instead of four.  MOT_G: rows of the
+// row group whose loads are in flight together; 2 as for the four-component k_radial (the compiler's report for gfx950, no
+// scratch: DESIGN.md section 19).
+#ifndef MOT_G
+#define MOT_G 2
+#endif
+
+// One pixel's twelve terms (rules C3, C4) into the lane's sums.  mux, mvx: (a0 + a1 * xc) and (b0 + b1 * xc) of the prior, formed
+// once per column.  The exclusion is three selects, not twelve: `in` false replaces the pixel's omega, u and v by +0.0 BEFORE
+// any term is formed, so nothing of its flow or of its weight reaches a term, each of its twelve terms is +0.0 or -0.0 (a zero
+// times a coordinate), and adding either to a sum that started at +0.0 leaves the sum's bits as they were -- the sums are
+// those of adding +0.0.  (Selecting each term instead cost 24 v_cndmask per pixel in a kernel that is VALU-bound: DESIGN.md
+// section 19.)
+template <bool PRIOR>
+__device__ __forceinline__ void ffl_motion_terms(double (&sum)[FFL_MOTION_NSUMS], bool in, float2 f, double wt, double xc, double yc,
+                                                 double mux, double mvx, double a2, double b2, double t2) {
+    double om = wt;
+    if constexpr (PRIOR) {
+        const double ru = (double)f.x - (mux + a2 * yc), rv = (double)f.y - (mvx + b2 * yc);
+        const double r2 = ru * ru + rv * rv;
+        const double rho = t2 / (t2 + r2);   // the one division of rule C3
+        om = wt * rho;
+    }
+    om = in ? om : 0.0;
+    const double u = (double)(in ? f.x : 0.0f), v = (double)(in ? f.y : 0.0f);
+    const double ox = om * xc, oy = om * yc, ou = om * u, ov = om * v;
+    sum[MOT_S] += om;
+    sum[MOT_SX] += ox;
+    sum[MOT_SY] += oy;
+    sum[MOT_SXX] += ox * xc;
+    sum[MOT_SXY] += ox * yc;
+    sum[MOT_SYY] += oy * yc;
+    sum[MOT_SU] += ou;
+    sum[MOT_SUX] += ou * xc;
+    sum[MOT_SUY] += ou * yc;
+    sum[MOT_SV] += ov;
+    sum[MOT_SVX] += ov * xc;
+    sum[MOT_SVY] += ov * yc;
+}
+
+// ffl_wave_sum_f64's tree -- offsets 32, 16, 8, 4, 2, 1, hence its bits -- with the four steps inside a row of 16 lanes as DPP
+// row shifts (lane i reads lane i + N of its row; a lane past the row's end reads 0 and feeds nothing lane 0 consumes) instead
+// of ds_bpermute: twelve sums cost 144 ds_bpermute_b32 per wave the plain way, a third of a wave's life in k_motion_fit.
+template <int N>
+__device__ __forceinline__ double ffl_row_down(double v) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(b & 0xFFFFFFFFull), 0x100 | N, 0xF, 0xF, false);   // row_shl:N
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), 0x100 | N, 0xF, 0xF, false);
+    return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned long long)(unsigned)lo));
+}
+__device__ __forceinline__ double ffl_wave_sum_f64_rows(double v) {
+    v += __shfl_down(v, 32, 64);
+    v += __shfl_down(v, 16, 64);
+    v += ffl_row_down<8>(v);
+    v += ffl_row_down<4>(v);
+    v += ffl_row_down<2>(v);
+    v += ffl_row_down<1>(v);
+    return v;
+}
+
+__device__ __forceinline__ bool ffl_flow_finite(float2 f) { return fabsf(f.x) <= FLT_MAX && fabsf(f.y) <= FLT_MAX; }
+
+// Sum c of workgroup g of item b goes to psum[(b * FFL_MOTION_NSUMS + c) * gridDim.x + g], k_radial's layout.  The prior's six
+// doubles are read with the wave-uniform item index.  Four instantiations: {NoWeights, WeightArgs} x {no prior, prior}.
+template <class WA, bool PRIOR>
+__global__ __launch_bounds__(P1_THREADS) void k_motion_fit(const float *__restrict__ flow, const ExportTab tab, int w, int h,
+                                                           const WA wa, const MotionPrior prior, double t2,
+                                                           double *__restrict__ psum) {
+    using Wt = decltype(ffl_item_weights(wa, 0));
+    constexpr int NS = FFL_MOTION_NSUMS;
+    __shared__ double ssum[NS * (P1_THREADS / 64)];
+    const int b = blockIdx.y;
+    const float2 *f = reinterpret_cast<const float2 *>(flow + (size_t)tab.slot[b] * 2 * ((size_t)w * h));
+    const Wt wt = ffl_item_weights(wa, b);
+    [[maybe_unused]] double pa0 = 0.0, pa1 = 0.0, pa2 = 0.0, pb0 = 0.0, pb1 = 0.0, pb2 = 0.0;
+    if constexpr (PRIOR) {
+        const double *p = reinterpret_cast<const double *>(prior.base + (long long)b * prior.stride);
+        pa0 = p[0], pa1 = p[1], pa2 = p[2], pb0 = p[3], pb1 = p[4], pb2 = p[5];
+    }
+    const double hx = (double)(w - 1) / 2.0, hy = (double)(h - 1) / 2.0;   // rule C1
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int nstrips = (w + P2_STRIP - 1) / P2_STRIP, ngroups = (h + P1_RG - 1) / P1_RG;
+    const int wid = blockIdx.x * (P1_THREADS / 64) + wv;  // wave-uniform
+    double sum[NS];
+#pragma unroll
+    for (int c = 0; c < NS; c++) sum[c] = 0.0;
+    if (wid < nstrips * ngroups) {
+        const int grp = wid / nstrips, strip = wid - grp * nstrips;
+        const int x = strip * P2_STRIP + 2 * lane, y0 = grp * P1_RG;  // the lane's pixels: x, x+1
+        const bool ok0 = x < w, ok1 = x + 1 < w;
+        const double xc0 = (double)x - hx, xc1 = (double)(x + 1) - hx;
+        const double mux0 = pa0 + pa1 * xc0, mvx0 = pb0 + pb1 * xc0, mux1 = pa0 + pa1 * xc1, mvx1 = pb0 + pb1 * xc1;
+#pragma unroll 1
+        for (int g = 0; g < P1_RG; g += MOT_G) {
+            float2 f0[MOT_G], f1[MOT_G];
+            [[maybe_unused]] unsigned q0[MOT_G], q1[MOT_G];
+#pragma unroll
+            for (int r = 0; r < MOT_G; r++) {
+                ffl_load_pair(f, w, h, x, y0 + g + r, f0[r], f1[r]);
+                if constexpr (Wt::on) {   // the flow's clamps; in flight with the flow rows
+                    const int yq = min(y0 + g + r, h - 1);
+                    q0[r] = wt.load(yq, min(x, w - 1));
+                    q1[r] = wt.load(yq, min(x + 1, w - 1));
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < MOT_G; r++) {
+                const int y = y0 + g + r;
+                const double yc = (double)y - hy;
+                bool in0 = ok0 && y < h && ffl_flow_finite(f0[r]), in1 = ok1 && y < h && ffl_flow_finite(f1[r]);
+                double w0 = 1.0, w1 = 1.0;
+                if constexpr (Wt::on) {
+                    in0 = in0 && q0[r] > 0u;
+                    in1 = in1 && q1[r] > 0u;
+                    w0 = (double)q0[r];
+                    w1 = (double)q1[r];
+                }
+                ffl_motion_terms<PRIOR>(sum, in0, f0[r], w0, xc0, yc, mux0, mvx0, pa2, pb2, t2);
+                ffl_motion_terms<PRIOR>(sum, in1, f1[r], w1, xc1, yc, mux1, mvx1, pa2, pb2, t2);
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < NS; c++) {
+        sum[c] = ffl_wave_sum_f64_rows(sum[c]);
+        if (lane == 0) ssum[c * (P1_THREADS / 64) + wv] = sum[c];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < NS; c++) {
+            for (int i = 1; i < P1_THREADS / 64; i++) sum[c] += ssum[c * (P1_THREADS / 64) + i];
+            psum[((size_t)b * NS + c) * gridDim.x + blockIdx.x] = sum[c];
+        }
+    }
+}
+
+// One workgroup per item: its nblk partials of every sum in k_radial_final's tree, then thread 0 runs the solve of rules C5 and
+// C6 (ffl_motion_solve_body, the source ffl_motion_solve compiles for the host) and writes the record, and the sums when asked.
+__global__ __launch_bounds__(P1_THREADS) void k_motion_solve(int nblk, int model, const double *__restrict__ psum,
+                                                             MotionRecord *__restrict__ models, double *__restrict__ sums) {
+    constexpr int NS = FFL_MOTION_NSUMS;
+    __shared__ double ssum[NS * (P1_THREADS / 64)];
+    const int b = blockIdx.x;
+    double sum[NS];
+#pragma unroll
+    for (int c = 0; c < NS; c++) sum[c] = 0.0;
+    for (int i = threadIdx.x; i < nblk; i += P1_THREADS) {
+#pragma unroll
+        for (int c = 0; c < NS; c++) sum[c] += psum[((size_t)b * NS + c) * nblk + i];
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < NS; c++) {
+        sum[c] = ffl_wave_sum_f64(sum[c]);
+        if (lane == 0) ssum[c * (P1_THREADS / 64) + wv] = sum[c];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < NS; c++)
+            for (int i = 1; i < P1_THREADS / 64; i++) sum[c] += ssum[c * (P1_THREADS / 64) + i];
+        MotionRecord r;
+        ffl_motion_solve_body(sum, model, &r);
+        models[b] = r;
+        if (sums) {
+#pragma unroll
+            for (int c = 0; c < NS; c++) sums[(size_t)b * NS + c] = sum[c];
+        }
+    }
+}
+
+void ffl_launch_motion_fit(const float *flow, const ExportTab &tab, int n, int w, int h, const WeightArgs *maps,
+                           const MotionPrior &prior, float tau, int model, double *psum, MotionRecord *models, double *sums,
+                           hipStream_t st) {
+    const int nblk = ffl_radial_blocks(w, h);
+    const dim3 grid(nblk, n), block(P1_THREADS);
+    const double t2 = (double)tau * (double)tau;
+    if (maps && prior.base)
+        hipLaunchKernelGGL((k_motion_fit<WeightArgs, true>), grid, block, 0, st, flow, tab, w, h, *maps, prior, t2, psum);
+    else if (maps)
+        hipLaunchKernelGGL((k_motion_fit<WeightArgs, false>), grid, block, 0, st, flow, tab, w, h, *maps, prior, t2, psum);
+    else if (prior.base)
+        hipLaunchKernelGGL((k_motion_fit<NoWeights, true>), grid, block, 0, st, flow, tab, w, h, NoWeights{}, prior, t2, psum);
+    else
+        hipLaunchKernelGGL((k_motion_fit<NoWeights, false>), grid, block, 0, st, flow, tab, w, h, NoWeights{}, prior, t2, psum);
+    hipLaunchKernelGGL(k_motion_solve, dim3(n), block, 0, st, nblk, model, psum, models, sums);
+}
+
+// Rule C8, element-wise: grid = (blocks per item, items) in k_export_flows' style, a lane handles FFL_EXP_UNROLL units of one
+// item 256 units apart.  A unit is two consecutive pixels of the row-major field (one 16-byte load and store) where the field
+// has an even number of pixels -- every slot is then 16-byte aligned -- else one pixel.  Each pixel is read and written by the
+// same lane only, so dst may be src (in place).  Workgroup (0, b) names the dst slot and its record in `pt` for the k_pass1 /
+// k_pass1_final pair that follows on the stream, as the import does.
+__device__ __forceinline__ float2 ffl_motion_sub(float2 f, int x, int y, double hx, double hy, const double (&m)[6]) {
+    const double xc = (double)x - hx, yc = (double)y - hy;
+    const double mu = (m[0] + m[1] * xc) + m[2] * yc, mv = (m[3] + m[4] * xc) + m[5] * yc;
+    return make_float2((float)((double)f.x - mu), (float)((double)f.y - mv));
+}
+
+__global__ __launch_bounds__(256) void k_motion_subtract(float *__restrict__ flow, Pass1Result *__restrict__ res, const ExportTab src,
+                                                         const ExportTab dst, int w, int h, const char *__restrict__ models,
+                                                         long long stride, int vec, PairTab *__restrict__ pt) {
+    const int b = blockIdx.y;
+    const size_t N = (size_t)w * h;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        pt->flow[0][b] = flow + (size_t)dst.slot[b] * 2 * N;
+        pt->res[b] = res + dst.slot[b];
+    }
+    const float *s = flow + (size_t)src.slot[b] * 2 * N;   // may alias d: no __restrict__
+    float *d = flow + (size_t)dst.slot[b] * 2 * N;
+    const double *mp = reinterpret_cast<const double *>(models + (long long)b * stride);   // wave-uniform
+    const double m[6] = {mp[0], mp[1], mp[2], mp[3], mp[4], mp[5]};
+    const double hx = (double)(w - 1) / 2.0, hy = (double)(h - 1) / 2.0;   // rule C1
+    const unsigned base = blockIdx.x * (256u * FFL_EXP_UNROLL) + threadIdx.x;   // units < 2^31: 20 * w * h < 2^32
+    const unsigned units = (unsigned)(vec ? N / 2 : N);
+#pragma unroll
+    for (int k = 0; k < FFL_EXP_UNROLL; k++) {
+        const unsigned u = base + (unsigned)k * 256u;
+        if (u >= units) continue;
+        if (vec) {
+            const unsigned p = 2u * u;
+            const int y = (int)(p / (unsigned)w), x = (int)(p - (unsigned)y * (unsigned)w);
+            const int x1 = x + 1 == w ? 0 : x + 1, y1 = x + 1 == w ? y + 1 : y;   // an odd width: the pair may end a row
+            const float4 t = ((const float4 *)s)[u];
+            const float2 a = ffl_motion_sub(make_float2(t.x, t.y), x, y, hx, hy, m);
+            const float2 c = ffl_motion_sub(make_float2(t.z, t.w), x1, y1, hx, hy, m);
+            ((float4 *)d)[u] = make_float4(a.x, a.y, c.x, c.y);
+        } else {
+            const int y = (int)(u / (unsigned)w), x = (int)(u - (unsigned)y * (unsigned)w);
+            ((float2 *)d)[u] = ffl_motion_sub(((const float2 *)s)[u], x, y, hx, hy, m);
+        }
+    }
+}
+
+void ffl_launch_motion_subtract(float *flow, Pass1Result *res, const ExportTab &src, const ExportTab &dst, int n, int w, int h,
+                                const char *models, long long stride, PairTab *pt, hipStream_t st) {
+    const size_t N = (size_t)w * h;
+    const int vec = N % 2 == 0;   // slot bases are 8N bytes apart
+    const size_t units = vec ? N / 2 : N;
+    dim3 grid((unsigned)((units + 256 * FFL_EXP_UNROLL - 1) / (256 * FFL_EXP_UNROLL)), n);
+    hipLaunchKernelGGL(k_motion_subtract, grid, dim3(256), 0, st, flow, res, src, dst, w, h, models, stride, vec, pt);
 }

@@ -119,6 +119,28 @@ def grid_records(buf, cells=32, n=None, device=None):
     return np.frombuffer(raw.tobytes(), _capi.CELL_DTYPE, n * cells * cells).reshape(n, cells, cells)
 
 
+def motion_buffer(ctx, n):
+    """a device buffer for the n 64-byte motion records of a chunk (torch uint8 on the context's device), as motion_out= and
+    Context.motion_fit(out=) take it: pair j's record at byte 64 * j"""
+    import torch
+    return torch.empty(n * _capi.MOTION_DTYPE.itemsize, dtype=torch.uint8, device=torch.device("cuda", ctx.device))
+
+
+def motion_records(buf, n=None, device=None):
+    """The motion records of a chunk run with motion_out= (or of Context.motion_fit) as a numpy array (n,) of
+    _capi.MOTION_DTYPE (fields a0, a1, a2, b0, b1, b2 of rule C2, sw, model, status): the camera path, one model per pair.
+    The copy runs on torch's current stream, behind the calls that filled `buf` there, and waits for them (see post_records
+    for `device`)."""
+    import torch
+    if not isinstance(buf, torch.Tensor):
+        buf = torch.as_tensor(buf, device=torch.device("cuda", torch.cuda.current_device() if device is None else device))
+    item = _capi.MOTION_DTYPE.itemsize
+    raw = buf.contiguous().view(torch.uint8).reshape(-1)
+    n = raw.numel() // item if n is None else n
+    raw = raw[:n * item].cpu().numpy()
+    return np.frombuffer(raw.tobytes(), _capi.MOTION_DTYPE, n)
+
+
 def _stream_event(ctx, stream=None):
     """an event recorded on `stream` (None: torch's current stream of the context's device): query() / synchronize()"""
     import torch
@@ -233,16 +255,16 @@ class PairEngine:
                              f"flow_slots >= 2B+13 = {min_flow_slots(self.B)}")
 
     def pass1(self, frames, pair_lo, pair_hi, pov_mode=False, cut_threshold=7.0, on_batch=None, algo=None, farneback=OWN,
-              window=OWN):
+              window=OWN, behind=None):
         """Run pass 1 for pairs [pair_lo, pair_hi) of `frames`; flows stay resident in slot
         (j - pair_lo) % flow_slots.  Returns the list of (x, y, val, mean_mag, cut)."""
         fs = self.ctx.flow_slots
         return self.pass1_pairs(frames, range(pair_lo, pair_hi), lambda l: l % fs, pov_mode, cut_threshold,
                                 on_batch=(lambda ls, js, got: on_batch(js, got)) if on_batch else None, algo=algo,
-                                farneback=farneback, window=window)
+                                farneback=farneback, window=window, behind=behind)
 
     def pass1_pairs(self, frames, pairs, slot_of, pov_mode=False, cut_threshold=7.0, on_batch=None, algo=None,
-                    farneback=OWN, window=OWN, queued=None, batch=None, reverse_slot_of=None):
+                    farneback=OWN, window=OWN, queued=None, batch=None, reverse_slot_of=None, behind=None):
         """Pass 1 for an arbitrary ascending list of pair indices (pair j = frames[j], frames[j+1]) in batches of
         max_batch; the flow of the l-th listed pair stays resident in flow slot slot_of(l).  Frames go to the
         device once per run of batches that needs them: a ring over the frame slots, frames of the batch being
@@ -257,7 +279,10 @@ class PairEngine:
         returned holds None.
         `batch`: listed pairs per batch (default max_batch).  `reverse_slot_of(l)`: every batch is queued as ONE flow call of
         its pairs and then the same pairs reversed, (frames[j + 1], frames[j]) -> flow slot reverse_slot_of(l), so the
-        frames' expansions are shared (2 * batch <= max_batch); records and callbacks are those of the forward pairs."""
+        frames' expansions are shared (2 * batch <= max_batch); records and callbacks are those of the forward pairs.
+        `behind(local_indices, pair_indices)`: called straight after every batch has been queued and before anything reads
+        its records or fields (queued= included): what it queues on the batch's slots -- the motion compensation of
+        process_chunk -- is what every later reader sees."""
         ctx, B, S = self.ctx, (self.B if batch is None else int(batch)), self.ctx.frame_slots
         algo, dis = algo if algo is not None else (getattr(self, "flow", "farneback"), getattr(self, "dis", None))
         fb = getattr(self, "farneback", None) if farneback is OWN else farneback
@@ -305,6 +330,8 @@ class PairEngine:
                 ctx.flow_pairs_farneback(f0, f1, fl, pov_mode, fb)
             else:
                 ctx.flow_pairs(f0, f1, fl, pov_mode)
+            if behind is not None:
+                behind(ls, js)
             return ls, js
 
         release = getattr(frames, "release", None)  # prefetch.PrefetchRing views: frames may be recycled once consumed
@@ -334,7 +361,7 @@ class PairEngine:
 
     def process_chunk(self, frames, pov_mode=False, cut_threshold=7.0, algo=None, farneback=OWN, flows_out=None, window=OWN,
                       post_out=None, axes=False, weights=None, center=None, cells=32, grid_out=None, consistency=None,
-                      weights_out=None, weights_gate=None):
+                      weights_out=None, weights_gate=None, compensate=None, motion_out=None):
         """One whole chunk on one GPU: returns (dots float64[n], records) with n = len(frames)-1.  `algo`, `farneback`,
         `window`: see pass1_pairs (default: the engine's own flow algorithm, parameters and window).  `flows_out`: a float32 device array of
         (n, H, W, 2) or (n, 2, H, W) that receives every pair's flow field (Context.export_flows, on torch's current stream)
@@ -362,9 +389,20 @@ class PairEngine:
         an (H, W) uint8 / bool device tensor, the static gate of rule K6).  A batch is then max_batch // 2 pairs, queued as
         one flow call of the pairs and the same pairs reversed; behind it Context.consistency_weights, then the calls of
         `weights`.  The chunk's maps live in one (n, H, W) uint8 device tensor: a new one, or `weights_out`, filled in
-        place.  flows_out still receives the forward fields."""
+        place.  flows_out still receives the forward fields.
+        `compensate`: a model name of _capi.MOTION_MODELS, a dict of _capi.MotionParams fields or a MotionParams (DESIGN.md
+        section 19).  Behind each batch, and before anything reads its records or fields, Context.motion_fit is queued on the
+        batch's slots -- under `weights` when that is a map -- and then Context.motion_subtract in place: pass 1, pass 2,
+        cell_stats, pass1_weighted and the window calls all see the compensated fields, and flows_out RECEIVES THE COMPENSATED
+        FIELDS.  "similarity" and "affine" contain a zoom term, which is the radial signal itself (rule C9).  `motion_out`:
+        device memory for n 64-byte records (motion_buffer; motion_records reads it), the fitted model of every pair -- the
+        camera path.  Not combined with weights="consistency" (the maps need both raw directions, and the ring holds the
+        reversed pairs).  Without compensate= nothing of this runs."""
         ctx, B = self.ctx, self.B
         n = len(frames) - 1
+        if compensate is not None and isinstance(weights, str):
+            raise ValueError(f"compensate= together with weights={weights!r} is not supported: the consistency maps need both "
+                             "raw directions of every pair, and the slot ring holds the reversed pairs")
         cons = _chunk_consistency(self, n, weights, consistency, weights_out, weights_gate)
         if cons is not None:
             weights, B = cons.maps, cons.B
@@ -372,6 +410,7 @@ class PairEngine:
         maps = weights   # the tensor stays referenced while the calls that read it are queued
         post_out, axes, weights, grid = _chunk_post_args(ctx, n, post_out, axes, weights, center, cells, grid_out,
                                                          check_empty=False)
+        comp = _chunk_motion(ctx, n, compensate, motion_out, weights, ring, pov_mode)
         if n < 1:
             return (_no_scalars(axes), []) if post_out is None else post_out
         layout = None
@@ -386,6 +425,9 @@ class PairEngine:
             post = _DevicePost(ctx, n, B, pov_mode, cut_threshold, post_out, axes, weights, grid, ring, cons)
             release = getattr(frames, "release", None)
             marks = []   # (event, frames that have left the host once it completes), oldest first
+
+            if comp is not None:
+                comp.stream = post.stream
 
             def queued(ls, js):
                 if layout is not None:   # before the window calls below let later batches recycle these slots
@@ -405,7 +447,7 @@ class PairEngine:
                     release(upto)
 
             self.pass1_pairs(frames, range(n), lambda l: l % ring, pov_mode, cut_threshold, algo=algo,
-                             farneback=farneback, window=window, queued=queued,
+                             farneback=farneback, window=window, queued=queued, **_behind_kw(comp),
                              **({} if cons is None else {"batch": B, "reverse_slot_of": cons.bwd_slot}))
             if marks:
                 marks[-1][0].synchronize()   # the ring's slots may be reused by the next chunk: every transfer is over
@@ -418,11 +460,12 @@ class PairEngine:
                 ctx.export_flows([j % ctx.flow_slots for j in js], flows_out[js[0]:js[-1] + 1], layout)
             post.add(js, got)
 
-        self.pass1(frames, 0, n, pov_mode, cut_threshold, on_batch, algo=algo, farneback=farneback, window=window)
+        self.pass1(frames, 0, n, pov_mode, cut_threshold, on_batch, algo=algo, farneback=farneback, window=window,
+                   **_behind_kw(comp))
         return post.finish()
 
     def process_flows(self, flows, pov_mode=False, cut_threshold=7.0, post_out=None, axes=False, weights=None, center=None,
-                      cells=32, grid_out=None):
+                      cells=32, grid_out=None, compensate=None, motion_out=None):
         """One whole chunk from flow fields the caller computed: returns (dots float64[n], records), the contract of
         process_chunk.  `flows` holds the chunk's n pair fields in device memory: one array (n, H, W, 2) or (n, 2, H, W)
         (float32, float16 or bfloat16, any strides; see _capi.device_flows) or a sequence of such arrays (single (H, W, 2)
@@ -431,7 +474,9 @@ class PairEngine:
         `post_out`: as in process_chunk (a buffer, or True for a new one) -- pass 2 is queued on the device behind each
         import, nothing waits, and the buffer is returned for post_records.  `axes`, `weights`: as in process_chunk (with
         weights: the device schedule, 80-byte records, pass1_weighted behind each import).  `center`, `cells`, `grid_out`:
-        as in process_chunk (center="variance": the device schedule, 80-byte records, cell_stats behind each import)."""
+        as in process_chunk (center="variance": the device schedule, 80-byte records, cell_stats behind each import).
+        `compensate`, `motion_out`: as in process_chunk -- motion_fit and motion_subtract in place behind each import, before
+        anything reads the imported fields' records."""
         ctx, B, fs = self.ctx, self.B, self.ctx.flow_slots
         if isinstance(weights, str):
             raise ValueError(f"process_flows: weights={weights!r} needs the backward fields, which a chunk of caller flows does "
@@ -448,6 +493,9 @@ class PairEngine:
             return (_no_scalars(axes), []) if post_out is None else post_out
         post = (_ChunkPost(ctx, n, B, pov_mode, axes) if post_out is None else
                 _DevicePost(ctx, n, B, pov_mode, cut_threshold, post_out, axes, weights, grid))
+        comp = _chunk_motion(ctx, n, compensate, motion_out, weights, fs, pov_mode)
+        if comp is not None and post_out is not None:
+            comp.stream = post.stream
 
         def enqueue(j0):
             j1 = min(j0 + B, n)
@@ -458,7 +506,10 @@ class PairEngine:
                 part = _capi.DevFlow(desc.base + (lo - first) * desc.item_stride, desc.item_stride, desc.row_pitch,
                                      desc.pixel_stride, desc.channel_stride)
                 ctx.import_flows_desc(part, dt, [j % fs for j in range(lo, hi)], pov_mode)
-            return list(range(j0, j1))
+            js = list(range(j0, j1))
+            if comp is not None:
+                comp.behind(js, js)
+            return js
 
         def collect(js):
             post.add(js, ctx.pass1_results([j % fs for j in js], cut_threshold))
@@ -576,6 +627,59 @@ def _chunk_post_args(ctx, n, post_out, axes, weights, center, cells, grid_out, c
     if post_out is True:
         post_out = post_buffer(ctx, max(n, 0), axes)
     return post_out, axes, desc, grid
+
+
+class _ChunkMotion:
+    """compensate= of a chunk of n pairs: behind(ls, js) queues Context.motion_fit on the slots of the
+    chunk's pairs ls (the l-th pair in flow slot l % ring) -- under the chunk's maps when it has any -- with pair l's record
+    at byte 64 * l of the chunk's buffer (motion_out, or a new one), then Context.motion_subtract in place.  stream: where the
+    calls are queued (None: torch's current stream; the device schedule sets its side stream)."""
+
+    def __init__(self, ctx, n, params, out, weights, ring, pov_mode):
+        self.ctx, self.params, self.weights, self.ring, self.pov_mode = ctx, params, weights, int(ring), pov_mode
+        self.out = motion_buffer(ctx, max(n, 1)) if out is None else out   # stays referenced while the calls are queued
+        self.base, nbytes = _capi._device_span(self.out)
+        self.item = _capi.MOTION_DTYPE.itemsize
+        if nbytes < n * self.item:
+            raise ValueError(f"motion_out holds {nbytes} bytes, the chunk's {n} records need {n * self.item}")
+        self.stream = None
+
+    def behind(self, ls, js):
+        slots, w = [l % self.ring for l in ls], self.weights
+        maps = None if w is None else _capi.DevWeights(w.base + ls[0] * w.item_stride, w.item_stride, w.row_pitch)
+        recs = _capi._DeviceSpan(self.base + ls[0] * self.item, len(ls) * self.item)
+        self.ctx.motion_fit(slots, self.params, weights=maps, out=recs, stream=self.stream)
+        self.ctx.motion_subtract(slots, slots, recs, self.pov_mode, self.stream)
+
+
+def _chunk_motion(ctx, n, compensate, motion_out, weights, ring, pov_mode):
+    """None without compensate= (motion_out= is then refused), else the chunk's _ChunkMotion; weights: the chunk's
+    _capi.DevWeights or None"""
+    if compensate is None:
+        if motion_out is not None:
+            raise ValueError("motion_out needs compensate=")
+        return None
+    return _ChunkMotion(ctx, n, _capi.motion_choice(compensate), motion_out, weights, ring, pov_mode)
+
+
+def _behind_kw(comp):
+    """behind= only where there is something to queue: an engine without the keyword keeps serving the plain chunk"""
+    return {} if comp is None else {"behind": comp.behind}
+
+
+def compensate_kwargs(params):
+    """{"compensate": ...} when params names "hip_compensate" -- a model name of _capi.MOTION_MODELS or a dict of the three
+    _capi.MotionParams fields -- else {}: the keyword of process_chunk / process_flows, checked here"""
+    comp = params.get("hip_compensate")
+    if comp is None:
+        return {}
+    return {"compensate": _capi.motion_choice(comp)}
+
+
+def _no_sharded_compensate(compensate, who):
+    if compensate is not None:
+        raise ValueError(f"{who}: the sharded schedules run on the raw fields; compensate= needs PairEngine.process_chunk / "
+                         "process_flows on one device")
 
 
 def _no_sharded_weights(weights, who):
@@ -843,6 +947,7 @@ def _chunk_scalars(engine, items, params, axes=False, run=None, **kw):
     one read for the chunk; axes=True: (comps float64[n, 4], records).  kw: further keywords of `run`."""
     run = run or engine.process_chunk
     pov, thr = bool(params.get("pov_mode", False)), float(params.get("cut_threshold", 7))
+    kw.update(compensate_kwargs(params))   # params["hip_compensate"]: the fit and the subtraction behind every batch
     cen = center_kwargs(params)
     if cen:   # params["hip_center"]: the device schedule about that centre
         return _weighted_scalars(run(items, pov, thr, **cen, **kw), axes)
@@ -930,7 +1035,7 @@ def _no_sharded_axes(axes, who):
 
 
 def process_chunk_sharded(engine, frames, rank, world, allgather, pov_mode=False, cut_threshold=7.0,
-                          assign="contiguous", block=1, axes=False, center=None, weights=None):
+                          assign="contiguous", block=1, axes=False, center=None, weights=None, compensate=None):
     """Multi-GPU form of one chunk: rank r owns the pairs shard_pairs(n, world, r, assign, block).
 
     `engine` provides pass1(frames, pair_indices, pov_mode, cut_threshold) -> records (its l-th listed pair is
@@ -942,6 +1047,7 @@ def process_chunk_sharded(engine, frames, rank, world, allgather, pov_mode=False
     _no_sharded_axes(axes, "process_chunk_sharded")
     _no_sharded_center(center, "process_chunk_sharded")
     _no_sharded_weights(weights, "process_chunk_sharded")
+    _no_sharded_compensate(compensate, "process_chunk_sharded")
     n = len(frames) - 1
     mine = shard_pairs(n, world, rank, assign, block)
     allrecs = _merge_records(allgather(_shard_pass1(engine, frames, mine, pov_mode, cut_threshold)), n)
@@ -958,7 +1064,7 @@ def halo_rows(rows, radius=SMOOTH_RADIUS):
 
 
 def process_chunk_sharded_halo(engine, frames, rank, world, allgather, pov_mode=False, cut_threshold=7.0, axes=False,
-                               center=None, weights=None):
+                               center=None, weights=None, compensate=None):
     """Streaming multi-GPU form of one chunk for CONTIGUOUS blocks: the only exchange between the passes is the halo.
 
     process_chunk_sharded gathers every pass-1 record of the chunk before any pass 2 starts, so all ranks idle until the
@@ -978,6 +1084,7 @@ def process_chunk_sharded_halo(engine, frames, rank, world, allgather, pov_mode=
     _no_sharded_axes(axes, "process_chunk_sharded_halo")
     _no_sharded_center(center, "process_chunk_sharded_halo")
     _no_sharded_weights(weights, "process_chunk_sharded_halo")
+    _no_sharded_compensate(compensate, "process_chunk_sharded_halo")
     n = len(frames) - 1
     R = SMOOTH_RADIUS
     lo, hi = shard_range(n, world, rank)
@@ -1041,13 +1148,14 @@ def process_chunk_sharded_halo(engine, frames, rank, world, allgather, pov_mode=
 
 
 def process_chunk_local_ranks(engines, frames, pov_mode=False, cut_threshold=7.0, assign="contiguous", block=1, axes=False,
-                              center=None, weights=None):
+                              center=None, weights=None, compensate=None):
     """The same schedule with every rank driven from THIS process (one engine / context per device, or several
     contexts on one device): phase by phase, no process group.  Equivalent to world = len(engines) processes
     running process_chunk_sharded (axes=True is refused there and here)."""
     _no_sharded_axes(axes, "process_chunk_local_ranks")
     _no_sharded_center(center, "process_chunk_local_ranks")
     _no_sharded_weights(weights, "process_chunk_local_ranks")
+    _no_sharded_compensate(compensate, "process_chunk_local_ranks")
     n, world = len(frames) - 1, len(engines)
     mine = [shard_pairs(n, world, r, assign, block) for r in range(world)]
     allrecs = _merge_records([_shard_pass1(e, frames, m, pov_mode, cut_threshold) for e, m in zip(engines, mine)], n)

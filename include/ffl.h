@@ -39,6 +39,11 @@
  *   ffl_consistency_weights replaces nothing (the reference's detect_cut is dead and nothing in it weights pixels): the
  *                           forward-backward check of a pair's two fields as a weight map for ffl_pass1_weighted and
  *                           ffl_radial_window_axes_weighted
+ *   ffl_motion_fit, ffl_motion_subtract  replace nothing: the reference cancels global motion only by the quadrant weights
+ *                           of radial_motion_weighted ("Cancel out global motion by balancing the averages", FF:779-783), which
+ *                           cancel a pan only about the image centre.  These fit a per-pair camera model (translation, rigid,
+ *                           similarity or affine) to a field robustly and subtract it, ahead of pass 1 and pass 2 (DESIGN.md
+ *                           section 19, appendix C)
  *   ffl_download_flow       the "flow" entry of that dict (tests / callers that want the array)
  *   ffl_upload_frames_device  ffl_upload_frames_raw / _yuv / ffl_upload_frames for frames already in device memory (a GPU
  *                           decoder's surfaces, torch tensors); ffl_export_flows: ffl_download_flow into device memory
@@ -632,6 +637,94 @@ int ffl_radial_window_axes_centres(ffl_ctx *ctx, int n_seq, const int *seq_slots
  * of rule G5 for FFL_MAX_CELLS rows of FFL_MAX_BATCH items (256 KiB whatever the size and the grid; the cell sums
  * themselves stay in LDS; ffl_estimate_bytes does not count it).  Needs no device. */
 int ffl_cells_extra_bytes(int width, int height, int cells, size_t *bytes);
+
+/* ---- Global-motion fit and compensation ----
+ * A per-pair parametric camera model, fitted robustly to a resident flow field and subtracted from it, so that what pass 1
+ * and pass 2 reduce is the subject's motion without the camera's.  The rules are the project's own (the reference has no
+ * such function).  All arithmetic is float64, one rounding per written operation, left to right, no contraction; u, v are
+ * widened exactly.
+ *   C1  xc = (double)x - (width - 1) / 2.0, yc = (double)y - (height - 1) / 2.0 (both exact).
+ *   C2  a model is six doubles; its flow at a pixel is mu = (a0 + a1*xc) + a2*yc, mv = (b0 + b1*xc) + b2*yc.
+ *       TRANSLATION: a0, b0, the rest 0.  RIGID: a0, b0, r with a2 = -r, b1 = r, a1 = b2 = 0.  SIMILARITY: a0, b0, s, r with
+ *       a1 = b2 = s, a2 = -r, b1 = r.  AFFINE: all six.
+ *   C3  wt = (double)W[y][x] under a map (rule W1), else 1.  A pixel is excluded by a select, never a multiplication, when
+ *       W == 0 or !(fabsf(u) <= FLT_MAX && fabsf(v) <= FLT_MAX): nothing of it reaches a sum.  With a prior model p:
+ *       ru = u - mu_p, rv = v - mv_p, r2 = ru*ru + rv*rv, t2 = (double)tau * (double)tau, rho = t2 / (t2 + r2),
+ *       omega = wt * rho (the Cauchy weight; one division).  Without a prior omega = wt.
+ *   C4  the twelve sums, in this order: S = sum omega, Sx = sum omega*xc, Sy = sum omega*yc, Sxx = sum (omega*xc)*xc,
+ *       Sxy = sum (omega*xc)*yc, Syy = sum (omega*yc)*yc, Su = sum omega*u, Sux = sum (omega*u)*xc, Suy = sum (omega*u)*yc,
+ *       Sv, Svx, Svy alike.  Only the order of addition is the kernel's own (ffl_radial's); every sum starts at +0.0; no
+ *       float atomics: the same bits from run to run.
+ *   C5  the weighted least-squares normal equations of the sub-model over the twelve sums, solved by an LDL^T elimination
+ *       without pivoting whose operation order DESIGN.md appendix C writes out line for line (ffl_motion_solve).
+ *   C6  S == 0: all six +0.0, status EMPTY, no division executed.  A pivot that is not > 1e-12 * its diagonal entry before
+ *       elimination (a NaN included): the TRANSLATION solution, status DEGENERATE.  Otherwise OK.
+ *   C7  pass 1 uses the caller's prior or none, pass k + 1 the model of pass k: `iterations` passes are, bit for bit,
+ *       `iterations` chained calls of one pass each.
+ *   C8  u' = (float)((double)u - mu), v' alike: one rounding to float32; non-finite samples follow IEEE; a model of all
+ *       zeros gives u' = u bit for bit.
+ *   C9  SIMILARITY and AFFINE contain a zoom term (s; a1 and b2), and a zoom about the centre IS the radial signal pass 2
+ *       measures: compensating with them removes part of what the scripts are made from.  The defaults -- TRANSLATION, 3
+ *       iterations, tau = 1.0 px -- are the project's own choice and are not tuned on footage. */
+enum { FFL_MOTION_TRANSLATION = 0, FFL_MOTION_RIGID = 1, FFL_MOTION_SIMILARITY = 2, FFL_MOTION_AFFINE = 3 };
+enum { FFL_MOTION_OK = 0, FFL_MOTION_EMPTY = 1, FFL_MOTION_DEGENERATE = 2 };
+enum { FFL_MOTION_N_SUMS = 12 };
+typedef struct ffl_motion_params {   /* model FFL_MOTION_*; iterations 1..8; 0 < tau <= 1e6, finite */
+    int model, iterations;
+    float tau;
+} ffl_motion_params;
+typedef struct ffl_motion_record {   /* 64 bytes */
+    double a0, a1, a2, b0, b1, b2;   /* rule C2 */
+    double sw;                       /* S of the last pass */
+    int32_t model, status;           /* FFL_MOTION_* */
+} ffl_motion_record;
+
+/* The defaults of rule C9. */
+int ffl_motion_default_params(ffl_motion_params *out);
+/* Pure host check: no device or context needed.  FFL_ERR_INVALID with the rule in ffl_last_error(NULL). */
+int ffl_motion_params_check(const ffl_motion_params *p);
+
+/* Rules C5 and C6 on twelve sums in rule C4's order: a pure host function, no device or context needed.  It compiles the
+ * same source as the device's k_motion_solve, so out is, bit for bit, the record ffl_motion_fit writes for these sums.
+ * FFL_ERR_INVALID for a NULL pointer or an unknown model. */
+int ffl_motion_solve(const double *sums, int model, ffl_motion_record *out);
+
+/* Device memory the fit adds to a context of this size, allocated by the first ffl_motion_fit and freed by ffl_destroy:
+ * FFL_MOTION_N_SUMS float64 partial sums per workgroup of the radial grid for FFL_MAX_BATCH items (ffl_estimate_bytes does
+ * not count it).  Needs no device. */
+int ffl_motion_extra_bytes(int width, int height, size_t *bytes);
+
+/* Fit the model of p (NULL: the defaults) to each of flow slots flow_slots[0..n) by p->iterations passes of rules C3 to C7.
+ * weights: the maps of the n items (rule W1's descriptor), or NULL.  prior_dev: NULL, or the prior of item i as six doubles
+ * (a0, a1, a2, b0, b1, b2) at prior_dev + i * prior_stride_bytes -- a stride of 64 reads ffl_motion_record's as this call
+ * left them, a stride of 48 a plain (n, 6) float64 array of any estimator's.  models_dev: n records, written.  sums_dev:
+ * NULL, or n * FFL_MOTION_N_SUMS doubles, the last pass's sums.  The flow and the pass-1 records are only read.
+ * Refused before any device work, each with its rule in the message: n outside 1..max_batch; a NULL list; a slot out of
+ * range or repeated; a slot that holds no flow (FFL_ERR_STATE); any rule of ffl_motion_params_check; any rule of
+ * ffl_dev_weights_check; models_dev NULL; models_dev, sums_dev or prior_dev that is not 8-byte aligned device memory of the
+ * context's device inside one allocation (page-locked host memory is refused); a prior stride below 48 or no multiple of 8;
+ * models_dev overlapping prior_dev when iterations > 1; a capturing `stream` (FFL_ERR_STATE).
+ * ffl_pass1_weighted's protocol: per pass one k_motion_fit launch for all n items plus k_motion_solve, queued on the
+ * library's stream behind the work queued on `stream` and the slots' last users; `stream` then waits for it, so the records
+ * may be read on `stream` straight after the call; it counts as a use of the slots; never captured; the host does not wait.
+ * The first call of a context allocates what ffl_motion_extra_bytes reports. */
+int ffl_motion_fit(ffl_ctx *ctx, int n, const int *flow_slots, const ffl_motion_params *p, const ffl_dev_weights *weights,
+                   const void *prior_dev, ptrdiff_t prior_stride_bytes, ffl_motion_record *models_dev, double *sums_dev,
+                   uint64_t stream);
+
+/* Rule C8: flow slot dst_slots[i] = the field of src_slots[i] minus the model of item i, six doubles at models_dev + i *
+ * model_stride_bytes (64: ffl_motion_fit's records; 48: a plain (n, 6) float64 array), then the pass-1 reductions of the dst
+ * slots by the k_pass1 / k_pass1_final pair: each dst record is bit-identical to ffl_upload_flow's for the same float32 field
+ * and replaces the slot's record, as ffl_pass1_weighted's does.  dst_slots[i] == src_slots[i] is allowed (in place: every
+ * pixel is read and written by one lane); otherwise the dst slots are distinct among themselves and none is another item's
+ * src.  Refused before any device work: n outside 1..max_batch; a NULL list; a src or dst slot out of range; a repeated src or
+ * dst slot, or a dst slot that is another item's src; a src slot that holds no flow (FFL_ERR_STATE); models_dev that is NULL or
+ * not 8-byte aligned device memory of the context's device inside one allocation; a stride below 48 or no multiple of 8; a
+ * capturing `stream` (FFL_ERR_STATE).  ffl_pass1_weighted's protocol: k_motion_subtract, k_pass1 and k_pass1_final queued on
+ * the library's stream behind `stream`'s work and the last users of all the slots; `stream` waits for it; it counts as a write
+ * of the dst slots and a use of the src slots; never captured; the host does not wait. */
+int ffl_motion_subtract(ffl_ctx *ctx, int n, const int *src_slots, const int *dst_slots, const void *models_dev,
+                        ptrdiff_t model_stride_bytes, int pov_mode, uint64_t stream);
 
 /* Copy a finished flow field to host memory as (height, width, 2) float32, cv2 layout. */
 int ffl_download_flow(ffl_ctx *ctx, int flow_slot, float *dst);
