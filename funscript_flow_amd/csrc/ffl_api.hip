@@ -2891,7 +2891,7 @@ static int model_array_check(ffl_ctx *c, const char *fn, const char *what, const
     return FFL_OK;
 }
 
-// `iterations` times k_motion_fit + k_motion_solve over n slots that hold a flow, on stream `post`: ffl_pass1_weighted's protocol
+// `iterations` times the fit's k_strip_sums + k_motion_solve over n slots that hold a flow, on stream `post`: ffl_pass1_weighted's protocol
 // with the flow and its records only read.  Pass k + 1 reads the records pass k wrote (rule C7), on the one stream.
 int ffl_motion_fit(ffl_ctx *c, int n, const int *slots, const ffl_motion_params *p, const ffl_dev_weights *w, const void *prior_dev,
                    ptrdiff_t prior_stride, ffl_motion_record *models_dev, double *sums_dev, uint64_t stream) {

@@ -240,7 +240,7 @@ int ffl_pass1_blocks(int w, int h);
 void ffl_launch_pass1(const PairTab *pt, int nB, int w, int h, int pov_mode, unsigned long long *pkey, double *psum,
                       hipStream_t st);
 
-// pass 2 (the k_radial / k_radial_final templates) and the plan of ffl_radial_window (k_window_plan)
+// pass 2 (k_strip_sums<RadialSums<..>>, k_radial_final) and the plan of ffl_radial_window (k_window_plan)
 #define FFL_WINDOW_MAX_RADIUS 32     // = FFL_MAX_RADIUS of include/ffl.h
 struct WindowSeq {   // the flow slots of the call's consecutive pairs; travels as a kernel argument (1280 bytes)
     int slot[FFL_MAXB + 2 * FFL_WINDOW_MAX_RADIUS];

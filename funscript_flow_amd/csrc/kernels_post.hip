@@ -17,7 +17,7 @@
 #define P1_STRIP 126      // useful pixels of a pass-1 strip: 64 lanes x 2 pixels minus one halo pixel per side
 #define P2_STRIP 128      // pass 2 needs no halo
 #ifndef P2_AXES_G
-#define P2_AXES_G 2        // rows in flight per lane in the four-component k_radial: 48 VGPRs, 8 waves per SIMD (8 rows, the single
+#define P2_AXES_G 2        // rows in flight per lane in the four-component RadialSums: 48 VGPRs, 8 waves per SIMD (8 rows, the single
                            // component's: 80 VGPRs, 6 waves); chosen by measurement over 8 and 4 rows -- DESIGN.md section 15
 #endif
 
@@ -84,7 +84,7 @@ struct P1SlotSrc {   // a flow slot: (h, w, 2) float32, one 16-byte load
 };
 
 // Whether and where a pass reads per-pixel weights.  WtNone compiles every weighted
-// statement away: k_pass1, k_import_pass1 and the k_radial instantiations without maps carry no trace of it.  WtBytes is
+// statement away: k_pass1, k_import_pass1 and the k_strip_sums instantiations without maps carry no trace of it.  WtBytes is
 // one item's (h, w) uint8 map with any base and row pitch: a lane reads the weight of each of its two pixels with a byte
 // load at the pixel's clamped (x, y), so no byte outside the `w` bytes of a row is read and nothing is asked of alignment
 // (pass 1's strips start at odd x).
@@ -311,112 +311,179 @@ __device__ __forceinline__ void ffl_radial_terms(double (&sum)[NC], bool in, flo
     }
 }
 
-// What a radial launch takes as its maps: WeightArgs, or NoWeights for the forms without.  ffl_item_weights is item b's policy.
+// What a launch takes as its maps: WeightArgs, or NoWeights for the forms without.  ffl_item_weights is item b's policy.
 struct NoWeights {};
 __device__ __forceinline__ WtNone ffl_item_weights(const NoWeights &, int) { return WtNone{}; }
 __device__ __forceinline__ WtBytes ffl_item_weights(const WeightArgs &wa, int b) {
     return WtBytes{wa.base + (long long)b * wa.item, wa.pitch};   // rows wa.pitch bytes apart
 }
 
-// The main kernel of the radial pair over a WindowItem table in device memory: ffl_radial copies one there, ffl_radial_window
-// has k_window_plan write it.  Three instantiations: <1, 8, NoWeights> (ffl_radial, ffl_radial_window), <FFL_NAXES, P2_AXES_G,
-// NoWeights> and <FFL_NAXES, P2_AXES_G, WeightArgs> (section 16).  One per-lane order and one wave /
-// workgroup reduction order for every component, so the single- and the four-component forms give the same bits in component
-// 0 for the same slot, centre and pov_mode.  Components 1..3 reuse the pixel's u, v, dx, dy and weights:
-// tangential ((v dx - u dy) wx) wy, shift_x (u wx) wy, shift_y (v wx) wy.  Component c of workgroup g of item b goes to
-// psum[(b * NS + c) * gridDim.x + g], component-major per item, so the final kernel reads each component's partials with
-// consecutive lanes.  G: rows of the row group whose loads are in flight together.
-// Under maps (rule W4) SW = sum of the weights is one more component, index NC: NS = NC + 1 sums per item and workgroup.
-// The workgroups of a cut item leave on a workgroup-uniform branch before they load anything of the flow or of a map (FF:766-767,
-// rule W6), and the final kernel answers it +0.0.
-template <int NC, int G, class WA>
-__global__ __launch_bounds__(P1_THREADS) void k_radial(const WindowItem *__restrict__ tab, int w, int h, int pov_mode,
-                                                       const double *__restrict__ wytab, double *__restrict__ psum, const WA wa) {
-    using Wt = decltype(ffl_item_weights(wa, 0));
-    constexpr int NS = NC + (Wt::on ? 1 : 0);   // sums per lane
-    __shared__ double ssum[NS * (P1_THREADS / 64)];
-    const int b = blockIdx.y;
-    if (tab[b].cut) return;
-    const float2 *flow = reinterpret_cast<const float2 *>(tab[b].flow);
-    const Wt wt = ffl_item_weights(wa, b);
-    const double cx = tab[b].cx, cy = tab[b].cy, dw = (double)w;
+// ---- the partial protocol of the strip sums: NS float64 sums per item, one partial of each per workgroup ----------------
+// Sum c of workgroup g of item b of nblk workgroups: sum-major per item, so a collecting kernel reads a sum's partials with
+// consecutive lanes.
+template <int NS>
+__device__ __forceinline__ size_t ffl_partial_index(int b, int c, int nblk, int g) {
+    return ((size_t)b * NS + c) * nblk + g;
+}
+
+// The workgroup's tree: the wave sum of each of the lane's sums, then the four waves' through LDS (ssum: NS * 4 doubles), added
+// in wave order by thread 0, which ends up holding the totals.
+template <int NS, class WaveSum>
+__device__ __forceinline__ void ffl_block_sums(double (&sum)[NS], double *ssum, WaveSum wave_sum) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int nstrips = (w + P2_STRIP - 1) / P2_STRIP, ngroups = (h + P1_RG - 1) / P1_RG;
-    const int wid = blockIdx.x * (P1_THREADS / 64) + wv;  // wave-uniform
-    double sum[NS];
-#pragma unroll
-    for (int c = 0; c < NS; c++) sum[c] = 0.0;
-    if (wid < nstrips * ngroups) {
-        const int grp = wid / nstrips, strip = wid - grp * nstrips;
-        const int x = strip * P2_STRIP + 2 * lane, y0 = grp * P1_RG;  // the lane's pixels: x, x+1
-        const bool ok0 = x < w, ok1 = x + 1 < w;
-        // per-column terms once per lane: dx and the quadrant weight (w - x) / w or x / w  (FF:776-779)
-        const double dx0 = (double)x - cx, dx1 = (double)(x + 1) - cx;
-        const double wx0 = pov_mode ? 1.0 : (((double)x > cx) ? (double)(w - x) / dw : (double)x / dw);
-        const double wx1 = pov_mode ? 1.0 : (((double)(x + 1) > cx) ? (double)(w - x - 1) / dw : (double)(x + 1) / dw);
-        // G = 8, two groups of 8 rows: 8 row loads in flight per lane are enough to cover the latency, and the unrolled body
-        // holds 8 waves per SIMD (64 VGPRs; all 16 rows hoisted needed 191)
-#pragma unroll 1
-        for (int g = 0; g < P1_RG; g += G) {
-            float2 f0[G], f1[G];
-            [[maybe_unused]] unsigned q0[G], q1[G];
-#pragma unroll
-            for (int r = 0; r < G; r++) {
-                ffl_load_pair(flow, w, h, x, y0 + g + r, f0[r], f1[r]);
-                if constexpr (Wt::on) {   // the flow's clamps; in flight with the flow rows
-                    const int yq = min(y0 + g + r, h - 1);
-                    q0[r] = wt.load(yq, min(x, w - 1));
-                    q1[r] = wt.load(yq, min(x + 1, w - 1));
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < G; r++) {
-                const int y = y0 + g + r;
-                const int yc = min(y, h - 1);  // rows past the image contribute nothing (selected out in the terms)
-                const double dy = (double)y - cy;
-                const double wy = pov_mode ? 1.0 : (((double)y > cy) ? wytab[yc] : wytab[h + yc]);
-                if constexpr (Wt::on) {
-                    // Rule W4, written out: stated through ffl_radial_terms with the predicate and the factor hoisted, this
-                    // instantiation measured behind at 256 items of 256x256 (profiles/r22_pass2_single_source.md).  Every term
-                    // is the unweighted one times (double)weight as its last factor, and enters only where the weight is > 0.
-                    static_assert(NC == FFL_NAXES, "the weighted form is the four-component one");
-                    const bool in0 = ok0 && y < h && q0[r] > 0u, in1 = ok1 && y < h && q1[r] > 0u;
-                    const double p0 = (double)q0[r], p1 = (double)q1[r];
-                    const double t0 = ((double)f0[r].x * dx0 + (double)f0[r].y * dy) * wx0 * wy;
-                    const double t1 = ((double)f1[r].x * dx1 + (double)f1[r].y * dy) * wx1 * wy;
-                    const double u0 = (double)f0[r].x, v0 = (double)f0[r].y, u1 = (double)f1[r].x, v1 = (double)f1[r].y;
-                    const double a0 = (v0 * dx0 - u0 * dy) * wx0 * wy, a1 = (v1 * dx1 - u1 * dy) * wx1 * wy;
-                    sum[0] += in0 ? t0 * p0 : 0.0;
-                    sum[0] += in1 ? t1 * p1 : 0.0;
-                    sum[1] += in0 ? a0 * p0 : 0.0;
-                    sum[1] += in1 ? a1 * p1 : 0.0;
-                    sum[2] += in0 ? u0 * wx0 * wy * p0 : 0.0;
-                    sum[2] += in1 ? u1 * wx1 * wy * p1 : 0.0;
-                    sum[3] += in0 ? v0 * wx0 * wy * p0 : 0.0;
-                    sum[3] += in1 ? v1 * wx1 * wy * p1 : 0.0;
-                    sum[NC] += in0 ? p0 : 0.0;
-                    sum[NC] += in1 ? p1 : 0.0;
-                } else {
-                    ffl_radial_terms<NC>(sum, ok0 && y < h, f0[r], dx0, dy, wx0, wy);
-                    ffl_radial_terms<NC>(sum, ok1 && y < h, f1[r], dx1, dy, wx1, wy);
-                }
-            }
-        }
-    }
 #pragma unroll
     for (int c = 0; c < NS; c++) {
-        sum[c] = ffl_wave_sum_f64(sum[c]);
+        sum[c] = wave_sum(sum[c]);
         if (lane == 0) ssum[c * (P1_THREADS / 64) + wv] = sum[c];
     }
     __syncthreads();
     if (threadIdx.x == 0) {
 #pragma unroll
-        for (int c = 0; c < NS; c++) {
+        for (int c = 0; c < NS; c++)
             for (int i = 1; i < P1_THREADS / 64; i++) sum[c] += ssum[c * (P1_THREADS / 64) + i];
-            psum[((size_t)b * NS + c) * gridDim.x + blockIdx.x] = sum[c];
-        }
     }
 }
+
+// A main kernel's end: the workgroup's sums become its partials of item b.
+template <int NS, class WaveSum>
+__device__ __forceinline__ void ffl_block_partials(double (&sum)[NS], double *ssum, double *__restrict__ psum, int b,
+                                                   WaveSum wave_sum) {
+    ffl_block_sums<NS>(sum, ssum, wave_sum);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < NS; c++) psum[ffl_partial_index<NS>(b, c, gridDim.x, blockIdx.x)] = sum[c];
+    }
+}
+
+// A collecting kernel's start (one workgroup per item): item b's nblk partials of each sum strided over the workgroup's threads
+// into sum[], which enters zeroed, then the same tree.
+template <int NS>
+__device__ __forceinline__ void ffl_collect_partials(double (&sum)[NS], double *ssum, const double *__restrict__ psum, int b,
+                                                     int nblk) {
+    for (int i = threadIdx.x; i < nblk; i += P1_THREADS) {
+#pragma unroll
+        for (int c = 0; c < NS; c++) sum[c] += psum[ffl_partial_index<NS>(b, c, nblk, i)];
+    }
+    ffl_block_sums<NS>(sum, ssum, ffl_wave_sum_f64);
+}
+
+// ---- the strip-sum walk: the main kernel of pass 2 (RadialSums) and of the motion fit (MotionSums, further down) --------------
+// A wave owns P2_STRIP columns of a row group of P1_RG rows; a lane its two pixels x, x + 1 (one 16-byte load per row), whose
+// terms enter the lane's P::NS float64 sums pixel x, then x + 1, row by row.  P::G rows of the row group have their loads in
+// flight together: all G flow loads and, under maps, the byte loads at the flow's clamps are issued before any arithmetic.
+// The policy P states what differs: skip(b), a workgroup-uniform way out before anything of the item is loaded; the item's
+// field(b, w, h), weights(b) (WtNone / WtBytes) and scalars item(b, w, h), read with the wave-uniform item index; columns(), the
+// per-column terms of the lane's two pixels, formed once; row(), row y's terms (ok0 / ok1: the column is in the image); wave_sum.
+// It is a plain struct of what the launcher has to hand and is itself the kernel's argument: built inside the kernel or handed
+// to a helper, the single-component form compiled to 5 waves per SIMD instead of 8 (profiles/r24_strip_sums_single_source.md).
+template <class P>
+__global__ __launch_bounds__(P1_THREADS) void k_strip_sums(const P p, int w, int h, double *__restrict__ psum) {
+    constexpr int NS = P::NS, G = P::G;
+    __shared__ double ssum[NS * (P1_THREADS / 64)];
+    const int b = blockIdx.y;
+    if (p.skip(b)) return;
+    const float2 *flow = p.field(b, w, h);
+    const auto wt = p.weights(b);
+    const auto item = p.item(b, w, h);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int nstrips = (w + P2_STRIP - 1) / P2_STRIP, ngroups = (h + P1_RG - 1) / P1_RG;
+    const int wid = blockIdx.x * (P1_THREADS / 64) + wv;  // wave-uniform
+    double sum[NS] = {};
+    if (wid < nstrips * ngroups) {
+        const int grp = wid / nstrips, strip = wid - grp * nstrips;
+        const int x = strip * P2_STRIP + 2 * lane, y0 = grp * P1_RG;  // the lane's pixels: x, x+1
+        const bool ok0 = x < w, ok1 = x + 1 < w;
+        const auto col = p.columns(item, x, w);
+#pragma unroll 1
+        for (int g = 0; g < P1_RG; g += G) {
+            float2 f0[G], f1[G];
+            unsigned q0[G], q1[G];
+#pragma unroll
+            for (int r = 0; r < G; r++) {
+                ffl_load_pair(flow, w, h, x, y0 + g + r, f0[r], f1[r]);
+                const int yq = min(y0 + g + r, h - 1);   // the flow's clamps; in flight with the flow rows
+                q0[r] = wt.load(yq, min(x, w - 1));
+                q1[r] = wt.load(yq, min(x + 1, w - 1));
+            }
+            // Nothing is scheduled across this line.  Without it the compiler sinks row 1's loads of the fit's kernels behind row 0's
+            // arithmetic, and the prior forms measured 2 to 5 % behind; pass 2's kernels compile to the same code either way.
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int r = 0; r < G; r++) p.row(sum, item, col, y0 + g + r, h, ok0, ok1, f0[r], f1[r], q0[r], q1[r]);
+        }
+    }
+    ffl_block_partials<NS>(sum, ssum, psum, b, P::wave_sum);
+}
+
+template <class P>
+static void ffl_launch_strip_sums(const P &p, int n, int w, int h, double *psum, hipStream_t st) {
+    hipLaunchKernelGGL(k_strip_sums<P>, dim3(ffl_radial_blocks(w, h), n), dim3(P1_THREADS), 0, st, p, w, h, psum);
+}
+
+// Pass 2's sums over a WindowItem table in device memory: ffl_radial copies one there, ffl_radial_window has k_window_plan write
+// it.  Three instantiations: <1, 8, NoWeights> (ffl_radial, ffl_radial_window), <FFL_NAXES, P2_AXES_G, NoWeights> (DESIGN.md
+// section 15) and <FFL_NAXES, P2_AXES_G, WeightArgs> (section 16).  One per-lane order and one wave / workgroup reduction order
+// for every component, so the single- and the four-component forms give the same bits in component 0 for the same slot, centre
+// and pov_mode.  Components 1..3 reuse the pixel's u, v, dx, dy and weights: tangential ((v dx - u dy) wx)
+// wy, shift_x (u wx) wy, shift_y (v wx) wy.
+// Under maps (rule W4) SW = sum of the weights is one more component, index NC: NS = NC + 1 sums per item and workgroup.  A cut
+// item is skipped (FF:766-767, rule W6), and the final kernel answers it +0.0.
+// G = 8 for the single component, two groups of 8 rows: 8 row loads in flight per lane are enough to cover the latency, and the
+// unrolled body holds 8 waves per SIMD (64 VGPRs; all 16 rows hoisted needed 191).
+template <int NC, int G_, class WA>
+struct RadialSums {
+    using Wt = decltype(ffl_item_weights(WA{}, 0));
+    static constexpr int G = G_, NS = NC + (Wt::on ? 1 : 0);   // sums per lane
+    const WindowItem *tab;
+    int pov_mode;
+    const double *wytab;
+    WA wa;
+    struct Item { double cx, cy; };
+    struct Columns { double dx0, dx1, wx0, wx1; };   // dx and the quadrant weight (w - x) / w or x / w (FF:776-779)
+    __device__ __forceinline__ bool skip(int b) const { return tab[b].cut; }
+    __device__ __forceinline__ const float2 *field(int b, int, int) const { return reinterpret_cast<const float2 *>(tab[b].flow); }
+    __device__ __forceinline__ Wt weights(int b) const { return ffl_item_weights(wa, b); }
+    __device__ __forceinline__ Item item(int b, int, int) const { return Item{tab[b].cx, tab[b].cy}; }
+    __device__ __forceinline__ Columns columns(const Item &it, int x, int w) const {
+        const double cx = it.cx, dw = (double)w;
+        return Columns{(double)x - cx, (double)(x + 1) - cx,
+                       pov_mode ? 1.0 : (((double)x > cx) ? (double)(w - x) / dw : (double)x / dw),
+                       pov_mode ? 1.0 : (((double)(x + 1) > cx) ? (double)(w - x - 1) / dw : (double)(x + 1) / dw)};
+    }
+    __device__ __forceinline__ void row(double (&sum)[NS], const Item &it, const Columns &c, int y, int h, bool ok0, bool ok1,
+                                        float2 f0, float2 f1, unsigned q0, unsigned q1) const {
+        const int yc = min(y, h - 1);  // rows past the image contribute nothing (selected out in the terms)
+        const double dx0 = c.dx0, dx1 = c.dx1, wx0 = c.wx0, wx1 = c.wx1, cy = it.cy;
+        const double dy = (double)y - cy;
+        const double wy = pov_mode ? 1.0 : (((double)y > cy) ? wytab[yc] : wytab[h + yc]);
+        if constexpr (Wt::on) {
+            // Rule W4, written out: stated through ffl_radial_terms with the predicate and the factor hoisted, this
+            // instantiation measured behind at 256 items of 256x256 (profiles/r22_pass2_single_source.md).  Every term
+            // is the unweighted one times (double)weight as its last factor, and enters only where the weight is > 0.
+            static_assert(NC == FFL_NAXES, "the weighted form is the four-component one");
+            const bool in0 = ok0 && y < h && q0 > 0u, in1 = ok1 && y < h && q1 > 0u;
+            const double p0 = (double)q0, p1 = (double)q1;
+            const double t0 = ((double)f0.x * dx0 + (double)f0.y * dy) * wx0 * wy;
+            const double t1 = ((double)f1.x * dx1 + (double)f1.y * dy) * wx1 * wy;
+            const double u0 = (double)f0.x, v0 = (double)f0.y, u1 = (double)f1.x, v1 = (double)f1.y;
+            const double a0 = (v0 * dx0 - u0 * dy) * wx0 * wy, a1 = (v1 * dx1 - u1 * dy) * wx1 * wy;
+            sum[0] += in0 ? t0 * p0 : 0.0;
+            sum[0] += in1 ? t1 * p1 : 0.0;
+            sum[1] += in0 ? a0 * p0 : 0.0;
+            sum[1] += in1 ? a1 * p1 : 0.0;
+            sum[2] += in0 ? u0 * wx0 * wy * p0 : 0.0;
+            sum[2] += in1 ? u1 * wx1 * wy * p1 : 0.0;
+            sum[3] += in0 ? v0 * wx0 * wy * p0 : 0.0;
+            sum[3] += in1 ? v1 * wx1 * wy * p1 : 0.0;
+            sum[NC] += in0 ? p0 : 0.0;
+            sum[NC] += in1 ? p1 : 0.0;
+        } else {
+            ffl_radial_terms<NC>(sum, ok0 && y < h, f0, dx0, dy, wx0, wy);
+            ffl_radial_terms<NC>(sum, ok1 && y < h, f1, dx1, dy, wx1, wy);
+        }
+    }
+    static __device__ __forceinline__ double wave_sum(double v) { return ffl_wave_sum_f64(v); }
+};
 
 // The final kernel of the pair: each component's nblk partials of item b in one order, then its means into out[b] -- `dot` of a
 // Pass2Record (NC = 1), or the four components of an AxesRecord and reserved = +0.0; whoever planned the item wrote the rest of
@@ -429,25 +496,10 @@ __global__ __launch_bounds__(P1_THREADS) void k_radial_final(const WindowItem *_
     constexpr int NS = NC + (WT ? 1 : 0);
     __shared__ double ssum[NS * (P1_THREADS / 64)];
     const int b = blockIdx.x;
-    double sum[NS];
-#pragma unroll
-    for (int c = 0; c < NS; c++) sum[c] = 0.0;
+    double sum[NS] = {};
     if (!tab[b].cut) {   // workgroup-uniform
-        for (int i = threadIdx.x; i < nblk; i += P1_THREADS) {
-#pragma unroll
-            for (int c = 0; c < NS; c++) sum[c] += psum[((size_t)b * NS + c) * nblk + i];
-        }
-        int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-        for (int c = 0; c < NS; c++) {
-            sum[c] = ffl_wave_sum_f64(sum[c]);
-            if (lane == 0) ssum[c * (P1_THREADS / 64) + wv] = sum[c];
-        }
-        __syncthreads();
+        ffl_collect_partials<NS>(sum, ssum, psum, b, nblk);
         if (threadIdx.x == 0) {
-#pragma unroll
-            for (int c = 0; c < NS; c++)
-                for (int i = 1; i < P1_THREADS / 64; i++) sum[c] += ssum[c * (P1_THREADS / 64) + i];
             double divisor = (double)w * (double)h;
             if constexpr (WT) divisor = sum[NC] == 0.0 ? 1.0 : sum[NC];
 #pragma unroll
@@ -470,10 +522,9 @@ __global__ __launch_bounds__(P1_THREADS) void k_radial_final(const WindowItem *_
 template <int NC, int G, class Rec, class WA>
 static void ffl_radial_pair(const WindowItem *tab, int n, int w, int h, int pov_mode, const double *wytab, const WA &wa,
                             double *psum, void *out, hipStream_t st) {
-    const int nblk = ffl_radial_blocks(w, h);
-    hipLaunchKernelGGL((k_radial<NC, G, WA>), dim3(nblk, n), dim3(P1_THREADS), 0, st, tab, w, h, pov_mode, wytab, psum, wa);
+    ffl_launch_strip_sums(RadialSums<NC, G, WA>{tab, pov_mode, wytab, wa}, n, w, h, psum, st);
     hipLaunchKernelGGL((k_radial_final<NC, std::is_same<WA, WeightArgs>::value, Rec>), dim3(n), dim3(P1_THREADS), 0, st, tab, w, h,
-                       nblk, psum, (Rec *)out);
+                       ffl_radial_blocks(w, h), psum, (Rec *)out);
 }
 
 void ffl_launch_radial(const WindowItem *tab, int n, int w, int h, int pov_mode, const double *wytab, const RadialForm &form,
@@ -1040,10 +1091,10 @@ void ffl_launch_pass1_weighted(const WeightArgs &wa, float *flow, Pass1Result *r
 }
 
 // ---- global-motion fit and compensation (ffl_motion_fit, ffl_motion_subtract) --------
-// k_motion_fit is k_radial's walk -- P2_STRIP columns per wave, one 16-byte load for a lane's two pixels, a row group of P1_RG
-// rows, WtNone / WtBytes for the map -- with the twelve float64 sums of rule C4 per lane instead of four.  MOT_G: rows of the
-// row group whose loads are in flight together; 2 as for the four-component k_radial (the compiler's report for gfx950, no
-// scratch: DESIGN.md section 19).
+// The fit's main kernel is k_strip_sums<MotionSums<WA, PRIOR>>: pass 2's walk with the twelve float64 sums of rule C4 per lane
+// instead of four, in four instantiations, {NoWeights, WeightArgs} x {no prior, prior}.  MOT_G: rows of the row group whose loads
+// are in flight together; 2 as for the four-component RadialSums (the compiler's report for gfx950, no scratch: DESIGN.md
+// section 19).
 #ifndef MOT_G
 #define MOT_G 2
 #endif
@@ -1083,7 +1134,7 @@ __device__ __forceinline__ void ffl_motion_terms(double (&sum)[FFL_MOTION_NSUMS]
 
 // ffl_wave_sum_f64's tree -- offsets 32, 16, 8, 4, 2, 1, hence its bits -- with the four steps inside a row of 16 lanes as DPP
 // row shifts (lane i reads lane i + N of its row; a lane past the row's end reads 0 and feeds nothing lane 0 consumes) instead
-// of ds_bpermute: twelve sums cost 144 ds_bpermute_b32 per wave the plain way, a third of a wave's life in k_motion_fit.
+// of ds_bpermute: twelve sums cost 144 ds_bpermute_b32 per wave the plain way, a third of a wave's life in the fit's k_strip_sums.
 template <int N>
 __device__ __forceinline__ double ffl_row_down(double v) {
     const unsigned long long b = (unsigned long long)__double_as_longlong(v);
@@ -1103,80 +1154,42 @@ __device__ __forceinline__ double ffl_wave_sum_f64_rows(double v) {
 
 __device__ __forceinline__ bool ffl_flow_finite(float2 f) { return fabsf(f.x) <= FLT_MAX && fabsf(f.y) <= FLT_MAX; }
 
-// Sum c of workgroup g of item b goes to psum[(b * FFL_MOTION_NSUMS + c) * gridDim.x + g], k_radial's layout.  The prior's six
-// doubles are read with the wave-uniform item index.  Four instantiations: {NoWeights, WeightArgs} x {no prior, prior}.
 template <class WA, bool PRIOR>
-__global__ __launch_bounds__(P1_THREADS) void k_motion_fit(const float *__restrict__ flow, const ExportTab tab, int w, int h,
-                                                           const WA wa, const MotionPrior prior, double t2,
-                                                           double *__restrict__ psum) {
-    using Wt = decltype(ffl_item_weights(wa, 0));
-    constexpr int NS = FFL_MOTION_NSUMS;
-    __shared__ double ssum[NS * (P1_THREADS / 64)];
-    const int b = blockIdx.y;
-    const float2 *f = reinterpret_cast<const float2 *>(flow + (size_t)tab.slot[b] * 2 * ((size_t)w * h));
-    const Wt wt = ffl_item_weights(wa, b);
-    [[maybe_unused]] double pa0 = 0.0, pa1 = 0.0, pa2 = 0.0, pb0 = 0.0, pb1 = 0.0, pb2 = 0.0;
-    if constexpr (PRIOR) {
-        const double *p = reinterpret_cast<const double *>(prior.base + (long long)b * prior.stride);
-        pa0 = p[0], pa1 = p[1], pa2 = p[2], pb0 = p[3], pb1 = p[4], pb2 = p[5];
+struct MotionSums {
+    using Wt = decltype(ffl_item_weights(WA{}, 0));
+    static constexpr int G = MOT_G, NS = FFL_MOTION_NSUMS;
+    const float *flow;
+    ExportTab tab;
+    WA wa;
+    MotionPrior prior;
+    double t2;
+    struct Item { double a0, a1, a2, b0, b1, b2, hx, hy; };
+    struct Columns { double xc0, xc1, mux0, mvx0, mux1, mvx1; };   // centred x and the prior's (a0 + a1 * xc), (b0 + b1 * xc)
+    __device__ __forceinline__ bool skip(int) const { return false; }
+    __device__ __forceinline__ const float2 *field(int b, int w, int h) const {
+        return reinterpret_cast<const float2 *>(flow + (size_t)tab.slot[b] * 2 * ((size_t)w * h));
     }
-    const double hx = (double)(w - 1) / 2.0, hy = (double)(h - 1) / 2.0;   // rule C1
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int nstrips = (w + P2_STRIP - 1) / P2_STRIP, ngroups = (h + P1_RG - 1) / P1_RG;
-    const int wid = blockIdx.x * (P1_THREADS / 64) + wv;  // wave-uniform
-    double sum[NS];
-#pragma unroll
-    for (int c = 0; c < NS; c++) sum[c] = 0.0;
-    if (wid < nstrips * ngroups) {
-        const int grp = wid / nstrips, strip = wid - grp * nstrips;
-        const int x = strip * P2_STRIP + 2 * lane, y0 = grp * P1_RG;  // the lane's pixels: x, x+1
-        const bool ok0 = x < w, ok1 = x + 1 < w;
-        const double xc0 = (double)x - hx, xc1 = (double)(x + 1) - hx;
-        const double mux0 = pa0 + pa1 * xc0, mvx0 = pb0 + pb1 * xc0, mux1 = pa0 + pa1 * xc1, mvx1 = pb0 + pb1 * xc1;
-#pragma unroll 1
-        for (int g = 0; g < P1_RG; g += MOT_G) {
-            float2 f0[MOT_G], f1[MOT_G];
-            [[maybe_unused]] unsigned q0[MOT_G], q1[MOT_G];
-#pragma unroll
-            for (int r = 0; r < MOT_G; r++) {
-                ffl_load_pair(f, w, h, x, y0 + g + r, f0[r], f1[r]);
-                if constexpr (Wt::on) {   // the flow's clamps; in flight with the flow rows
-                    const int yq = min(y0 + g + r, h - 1);
-                    q0[r] = wt.load(yq, min(x, w - 1));
-                    q1[r] = wt.load(yq, min(x + 1, w - 1));
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < MOT_G; r++) {
-                const int y = y0 + g + r;
-                const double yc = (double)y - hy;
-                bool in0 = ok0 && y < h && ffl_flow_finite(f0[r]), in1 = ok1 && y < h && ffl_flow_finite(f1[r]);
-                double w0 = 1.0, w1 = 1.0;
-                if constexpr (Wt::on) {
-                    in0 = in0 && q0[r] > 0u;
-                    in1 = in1 && q1[r] > 0u;
-                    w0 = (double)q0[r];
-                    w1 = (double)q1[r];
-                }
-                ffl_motion_terms<PRIOR>(sum, in0, f0[r], w0, xc0, yc, mux0, mvx0, pa2, pb2, t2);
-                ffl_motion_terms<PRIOR>(sum, in1, f1[r], w1, xc1, yc, mux1, mvx1, pa2, pb2, t2);
-            }
-        }
+    __device__ __forceinline__ Wt weights(int b) const { return ffl_item_weights(wa, b); }
+    __device__ __forceinline__ Item item(int b, int w, int h) const {
+        const double hx = (double)(w - 1) / 2.0, hy = (double)(h - 1) / 2.0;   // rule C1
+        const double *p = reinterpret_cast<const double *>(prior.base + (long long)b * prior.stride);   // wave-uniform
+        if constexpr (PRIOR) return Item{p[0], p[1], p[2], p[3], p[4], p[5], hx, hy};
+        return Item{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, hx, hy};
     }
-#pragma unroll
-    for (int c = 0; c < NS; c++) {
-        sum[c] = ffl_wave_sum_f64_rows(sum[c]);
-        if (lane == 0) ssum[c * (P1_THREADS / 64) + wv] = sum[c];
+    __device__ __forceinline__ Columns columns(const Item &it, int x, int) const {
+        const double xc0 = (double)x - it.hx, xc1 = (double)(x + 1) - it.hx;
+        return Columns{xc0, xc1, it.a0 + it.a1 * xc0, it.b0 + it.b1 * xc0, it.a0 + it.a1 * xc1, it.b0 + it.b1 * xc1};
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int c = 0; c < NS; c++) {
-            for (int i = 1; i < P1_THREADS / 64; i++) sum[c] += ssum[c * (P1_THREADS / 64) + i];
-            psum[((size_t)b * NS + c) * gridDim.x + blockIdx.x] = sum[c];
-        }
+    __device__ __forceinline__ void row(double (&sum)[NS], const Item &it, const Columns &c, int y, int h, bool ok0, bool ok1,
+                                        float2 f0, float2 f1, unsigned q0, unsigned q1) const {
+        const double yc = (double)y - it.hy;
+        // without maps q0 = q1 = 1 (WtNone): the weight's test and its factor fold away
+        const bool in0 = ok0 && y < h && ffl_flow_finite(f0) && q0 > 0u, in1 = ok1 && y < h && ffl_flow_finite(f1) && q1 > 0u;
+        ffl_motion_terms<PRIOR>(sum, in0, f0, (double)q0, c.xc0, yc, c.mux0, c.mvx0, it.a2, it.b2, t2);
+        ffl_motion_terms<PRIOR>(sum, in1, f1, (double)q1, c.xc1, yc, c.mux1, c.mvx1, it.a2, it.b2, t2);
     }
-}
+    static __device__ __forceinline__ double wave_sum(double v) { return ffl_wave_sum_f64_rows(v); }
+};
 
 // One workgroup per item: its nblk partials of every sum in k_radial_final's tree, then thread 0 runs the solve of rules C5 and
 // C6 (ffl_motion_solve_body, the source ffl_motion_solve compiles for the host) and writes the record, and the sums when asked.
@@ -1185,24 +1198,9 @@ __global__ __launch_bounds__(P1_THREADS) void k_motion_solve(int nblk, int model
     constexpr int NS = FFL_MOTION_NSUMS;
     __shared__ double ssum[NS * (P1_THREADS / 64)];
     const int b = blockIdx.x;
-    double sum[NS];
-#pragma unroll
-    for (int c = 0; c < NS; c++) sum[c] = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += P1_THREADS) {
-#pragma unroll
-        for (int c = 0; c < NS; c++) sum[c] += psum[((size_t)b * NS + c) * nblk + i];
-    }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < NS; c++) {
-        sum[c] = ffl_wave_sum_f64(sum[c]);
-        if (lane == 0) ssum[c * (P1_THREADS / 64) + wv] = sum[c];
-    }
-    __syncthreads();
+    double sum[NS] = {};
+    ffl_collect_partials<NS>(sum, ssum, psum, b, nblk);
     if (threadIdx.x == 0) {
-#pragma unroll
-        for (int c = 0; c < NS; c++)
-            for (int i = 1; i < P1_THREADS / 64; i++) sum[c] += ssum[c * (P1_THREADS / 64) + i];
         MotionRecord r;
         ffl_motion_solve_body(sum, model, &r);
         models[b] = r;
@@ -1216,18 +1214,16 @@ __global__ __launch_bounds__(P1_THREADS) void k_motion_solve(int nblk, int model
 void ffl_launch_motion_fit(const float *flow, const ExportTab &tab, int n, int w, int h, const WeightArgs *maps,
                            const MotionPrior &prior, float tau, int model, double *psum, MotionRecord *models, double *sums,
                            hipStream_t st) {
-    const int nblk = ffl_radial_blocks(w, h);
-    const dim3 grid(nblk, n), block(P1_THREADS);
     const double t2 = (double)tau * (double)tau;
     if (maps && prior.base)
-        hipLaunchKernelGGL((k_motion_fit<WeightArgs, true>), grid, block, 0, st, flow, tab, w, h, *maps, prior, t2, psum);
+        ffl_launch_strip_sums(MotionSums<WeightArgs, true>{flow, tab, *maps, prior, t2}, n, w, h, psum, st);
     else if (maps)
-        hipLaunchKernelGGL((k_motion_fit<WeightArgs, false>), grid, block, 0, st, flow, tab, w, h, *maps, prior, t2, psum);
+        ffl_launch_strip_sums(MotionSums<WeightArgs, false>{flow, tab, *maps, prior, t2}, n, w, h, psum, st);
     else if (prior.base)
-        hipLaunchKernelGGL((k_motion_fit<NoWeights, true>), grid, block, 0, st, flow, tab, w, h, NoWeights{}, prior, t2, psum);
+        ffl_launch_strip_sums(MotionSums<NoWeights, true>{flow, tab, NoWeights{}, prior, t2}, n, w, h, psum, st);
     else
-        hipLaunchKernelGGL((k_motion_fit<NoWeights, false>), grid, block, 0, st, flow, tab, w, h, NoWeights{}, prior, t2, psum);
-    hipLaunchKernelGGL(k_motion_solve, dim3(n), block, 0, st, nblk, model, psum, models, sums);
+        ffl_launch_strip_sums(MotionSums<NoWeights, false>{flow, tab, NoWeights{}, prior, t2}, n, w, h, psum, st);
+    hipLaunchKernelGGL(k_motion_solve, dim3(n), dim3(P1_THREADS), 0, st, ffl_radial_blocks(w, h), model, psum, models, sums);
 }
 
 // Rule C8, element-wise: grid = (blocks per item, items) in k_export_flows' style, a lane handles FFL_EXP_UNROLL units of one

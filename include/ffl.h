@@ -437,7 +437,7 @@ typedef struct ffl_pass2_record {
  *   - a stream that is capturing a graph is refused with FFL_ERR_STATE; that check is the first HIP call made on it;
  *   - the library's stream waits for the batch, import or upload that produced every seq slot and for the work queued on
  *     `stream` before the call (out_dev may still be being read), then writes out_dev with three launches (k_window_plan,
- *     k_radial, k_radial_final), and `stream` is made to wait for that;
+ *     k_strip_sums<RadialSums<..>>, k_radial_final), and `stream` is made to wait for that;
  *   - the call counts as a use of every seq slot, the neighbours whose records alone are read included: a later batch that
  *     recycles one of them waits for it on the device;
  *   - the host never waits for the device, except where settling the library's event ring makes every call wait.
@@ -476,7 +476,7 @@ int ffl_radial_axes(ffl_ctx *ctx, int n, const int *flow_slots, const double *cx
 
 /* ffl_radial_window with ffl_axes_record records: the same windows, cut test, refusals (out_dev must hold n records of 80
  * bytes inside one allocation), stream contract and use of every seq slot; never captured, no host wait.  Its three
- * launches are k_window_plan and the four-component k_radial and k_radial_final. */
+ * launches are k_window_plan and the four-component k_strip_sums<RadialSums<..>> and k_radial_final. */
 int ffl_radial_window_axes(ffl_ctx *ctx, int n_seq, const int *seq_slots, int first, int n, int radius, float cut_threshold,
                            int pov_mode, ffl_axes_record *out_dev, uint64_t stream);
 
@@ -527,7 +527,7 @@ int ffl_pass1_weighted(ffl_ctx *ctx, int n, const int *flow_slots, const ffl_dev
  * first + i); neighbours contribute their records only.  Windows, the centre mean and the cut test are
  * ffl_radial_window's, from whatever records the seq slots hold -- normally those of ffl_pass1_weighted; unweighted ones
  * are allowed.  The same refusals and stream contract, plus the map rules of ffl_pass1_weighted; out_dev is checked
- * before the maps.  Its three launches are k_window_plan and the weighted k_radial and k_radial_final. */
+ * before the maps.  Its three launches are k_window_plan and the weighted k_strip_sums<RadialSums<..>> and k_radial_final. */
 int ffl_radial_window_axes_weighted(ffl_ctx *ctx, int n_seq, const int *seq_slots, int first, int n, int radius,
                                     float cut_threshold, int pov_mode, const ffl_dev_weights *w, ffl_axes_record *out_dev,
                                     uint64_t stream);
@@ -627,8 +627,8 @@ int ffl_cell_stats(ffl_ctx *ctx, int n, const int *flow_slots, int cells, ffl_ce
  * the four components, the cut rule and the stream contract are ffl_radial_window_axes'.  Further refusals: a NULL or
  * misaligned centres_dev; a stride below 16 or no multiple of 8; centres that are not device memory of the context's
  * device inside one allocation over (n_seq - 1) * stride + 16 bytes (page-locked host memory is refused); out_dev is
- * checked before the centres.  Its three launches are k_window_plan over the centres and the four-component k_radial and
- * k_radial_final. */
+ * checked before the centres.  Its three launches are k_window_plan over the centres and the four-component
+ * k_strip_sums<RadialSums<..>> and k_radial_final. */
 int ffl_radial_window_axes_centres(ffl_ctx *ctx, int n_seq, const int *seq_slots, int first, int n, int radius,
                                    float cut_threshold, int pov_mode, const void *centres_dev, ptrdiff_t centre_stride_bytes,
                                    ffl_axes_record *out_dev, uint64_t stream);
@@ -704,8 +704,8 @@ int ffl_motion_extra_bytes(int width, int height, size_t *bytes);
  * ffl_dev_weights_check; models_dev NULL; models_dev, sums_dev or prior_dev that is not 8-byte aligned device memory of the
  * context's device inside one allocation (page-locked host memory is refused); a prior stride below 48 or no multiple of 8;
  * models_dev overlapping prior_dev when iterations > 1; a capturing `stream` (FFL_ERR_STATE).
- * ffl_pass1_weighted's protocol: per pass one k_motion_fit launch for all n items plus k_motion_solve, queued on the
- * library's stream behind the work queued on `stream` and the slots' last users; `stream` then waits for it, so the records
+ * ffl_pass1_weighted's protocol: per pass one k_strip_sums<MotionSums<..>> launch for all n items plus k_motion_solve, queued
+ * on the library's stream behind the work queued on `stream` and the slots' last users; `stream` then waits for it, so the records
  * may be read on `stream` straight after the call; it counts as a use of the slots; never captured; the host does not wait.
  * The first call of a context allocates what ffl_motion_extra_bytes reports. */
 int ffl_motion_fit(ffl_ctx *ctx, int n, const int *flow_slots, const ffl_motion_params *p, const ffl_dev_weights *weights,
@@ -899,7 +899,7 @@ int ffl_profile_enable(ffl_ctx *ctx, unsigned class_mask);
 #define FFL_K_UPDATE_MATRICES 4
 #define FFL_K_BLUR_SOLVE 5
 #define FFL_K_PASS1 6
-#define FFL_K_RADIAL 7   /* k_radial + k_radial_final of ffl_radial; ffl_radial_window's three launches belong to no class */
+#define FFL_K_RADIAL 7   /* ffl_radial's pair of launches; ffl_radial_window's three launches belong to no class */
 #define FFL_K_COUNT 8
 /* Read and reset the accumulated (launch count, total milliseconds) of one kernel class.
  * Synchronises the context. */

@@ -6,8 +6,8 @@
 
 --kernels is the workload of a profiler run of its own: N resident random fields of W x H, then `--calls` calls each of
 motion_fit with one pass in its four forms ({no map, map} x {no prior, prior}), of the four-component radial_window_axes on
-the same slots (k_radial<4, 2, NoWeights>, the yardstick of the fit), of motion_subtract in place and of export_flows (the
-yardstick of the subtraction).  Every kernel form has a name of its own in the trace.  --chunk times
+the same slots (k_strip_sums<RadialSums<4, 2, NoWeights>>, the yardstick of the fit), of motion_subtract in place and of
+export_flows (the yardstick of the subtraction).  Every kernel form has a name of its own in the trace.  --chunk times
 PairEngine.process_chunk() on a synthetic clip of 3 * B pairs against the same call with compensate="translation" at one and
 three passes, alternating `--reps` times; a timed sample is `--rounds` runs of the chunk back to back and a device
 synchronise, and the rate is pairs per second of that wall time.  Nothing runs on import."""
@@ -22,7 +22,7 @@ import time
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, HERE)
 
-KERNELS = ("k_motion_fit", "k_motion_solve", "k_motion_subtract", "k_radial", "k_export_flows", "k_pass1")
+KERNELS = ("k_strip_sums", "k_motion_solve", "k_motion_subtract", "k_radial_final", "k_export_flows", "k_pass1")
 
 
 def kernels(w, h, n, calls):

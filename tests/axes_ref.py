@@ -1,4 +1,4 @@
-"""Exact reference for the four motion components about the centre (the four-component k_radial), importable
+"""Exact reference for the four motion components about the centre (the four-component pass 2), importable
 without a GPU: plain numpy and post_ref's exact sum, no ctypes.
 
 The rule, per pixel (x, y) of an h x w field with float32 flow (u, v) widened to float64 and centre (cx, cy):

@@ -15,10 +15,10 @@ plain numpy for the per-pixel terms, post_ref.fsum for their exact sums, Python 
 
 Error bounds, from the code (kernels_post.hip), not from device output:
 
-  sums   k_motion_fit forms every term with the operations written above, in float64 without contraction, and numpy's
+  sums   the fit's k_strip_sums forms every term with the operations written above, in float64 without contraction, and numpy's
          elementwise float64 operations are those operations (the division of C3 is one correctly rounded IEEE division on
          both sides): the restated terms ARE the kernel's, bit for bit -- 0 roundings per term.  What differs is the order of
-         the additions.  The walk is k_radial's (P2_STRIP = 128 columns per wave, two pixels per lane, a row group of 16 rows,
+         the additions.  The walk is pass 2's (P2_STRIP = 128 columns per wave, two pixels per lane, a row group of 16 rows,
          wave shuffle, four waves through LDS, then k_motion_solve adds the workgroup partials in k_radial_final's tree), so
          the longest chain of additions a term passes through is post_ref.radial_depth(w, h): 2 * 16 + 6 + 3 + trips + 6 + 3,
          and the 2 that function adds for radial's two divisions, which the fit does not have, only loosen the bound by 2 u.

@@ -1,7 +1,7 @@
 """Exact references for the post kernels (kernels_post.hip), importable without a GPU: plain numpy and math.fsum, no
 ctypes, no oracle library.
 
-The reference's radial_motion_weighted (FF:761-785) is float64 throughout and so is k_radial, so the two differ only in how
+The reference's radial_motion_weighted (FF:761-785) is float64 throughout and so is pass 2's k_strip_sums, so the two differ only in how
 each term is rounded and in the order the terms are added.  Both are bounded here from the code, not from device output:
 
   per term   reference  ((dot * (w - x)) / w * (h - y)) / h           4 roundings after `dot`
@@ -9,7 +9,7 @@ each term is rounded and in the order the terms are added.  Both are bounded her
              `dot` = u * dx + v * dy is formed the same way by both (the library is built with -ffp-contract=off), so it
              cancels; each rounding moves a term by at most u * |term| (u = 2^-53, first order): 8 * u * |term| in all.
   summation  every addition a term passes through multiplies it by (1 + d), |d| <= u.  The longest chain of additions
-             in k_radial / k_radial_final (and equally k_pass1 / k_pass1_final for the magnitude sum) is
+             in k_strip_sums / k_radial_final (and equally k_pass1 / k_pass1_final for the magnitude sum) is
                2 * 16   a lane adds its two pixels of each of the 16 rows of its row group, in sequence
                6        __shfl_down steps of the wave sum
                3        thread 0 adds the other three waves' sums
@@ -18,7 +18,7 @@ each term is rounded and in the order the terms are added.  Both are bounded her
              plus one rounding for the kernel's division by w * h (radial) or the host's division by w * h (mean
              magnitude) and one for the reference's own division of the exactly rounded fsum:
                depth = 32 + 6 + 3 + trips + 6 + 3 + 2
-             which is 56 for k_radial at 3840x2160 (nblk = 1013, 4 trips) and 61 for k_pass1 at 5760x2880 (nblk = 2070,
+             which is 56 for pass 2 at 3840x2160 (nblk = 1013, 4 trips) and 61 for k_pass1 at 5760x2880 (nblk = 2070,
              9 trips).
   so         |kernel - radial_exact| <= sum_bound(8, depth) * S,   S = sum |term| / (w * h),
              about 7e-15 * S.  The bound is relative to S, not to the result: a field whose terms cancel is held to the

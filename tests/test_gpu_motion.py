@@ -195,6 +195,53 @@ def test_three_iterations_are_three_chained_calls(size):
                     mr.check_sums(sums3[i], fields[i], W, mr.six(two[i]), 2.0)
 
 
+# ---- 2b. the fit's sums and pass 2's are one walk --------------------------------------------------------------------------------
+@pytest.mark.parametrize("size", [(16, 16), (129, 17), (258, 35)], ids=gid)
+def test_motion_sums_are_pass2_sums(size):
+    """An exact relation between the two families that run the strip-sum walk, so that an edit to one policy that reorders its
+    sums is seen.  In POV mode pass 2's quadrant weights are 1.0, so its shift_x term is (u * 1) * 1 [* p] and the fit's,
+    without a prior, (p * 1) * u: the same products of the same pixels, which both add pixel x, then x + 1, row by row, through
+    one wave tree, one LDS order and one collect.  An excluded pixel adds +0.0 in pass 2 and +-0.0 in the fit, neither of which
+    changes a bit of a sum that started at +0.0; one IEEE division on either side.  The fields mix two scales, 1 and 2^30, under
+    random signs: with flow of one magnitude every float64 addition here is exact and no order could be seen, and without
+    cancellation a lane's rounding is lost in the total.  129x17: a last strip of one column and a last row group of one row;
+    258x35: three strips and three row groups."""
+    w, h = size
+    n = 3
+    rng = np.random.default_rng(w)
+    scale = rng.choice([-1.0, 1.0], (n, h, w, 2)) * np.exp2(rng.choice([0, 30], (n, h, w, 2)))
+    fields = np.stack([field(w, h, 70 + i) for i in range(n)]) * scale.astype(np.float32)
+    fields[1][rng.random((h, w, 2)) < 0.05] = np.float32(-0.0)
+    assert np.isfinite(fields).all() and np.signbit(fields[1][fields[1] == 0]).any()
+    slots, centres = [4, 0, 2], [(0.0, 0.0), (w / 3.0, h / 2.0), (w - 1.0, 5.5)]
+    S, SU, SV = (_capi.MOTION_SUMS.index(k) for k in ("S", "Su", "Sv"))
+    bits = lambda a: np.ascontiguousarray(a, np.float64).tobytes()
+
+    def window(maps):
+        out = torch.full((n * _capi.PASS2_AXES_DTYPE.itemsize,), 0xA5, dtype=torch.uint8, device=DEV)
+        ctx.radial_window_axes_weighted(slots, 0, n, maps, out, 1, BIG, True)
+        return np.frombuffer(out.cpu().numpy().tobytes(), _capi.PASS2_AXES_DTYPE, n)
+
+    with context(w, h) as ctx:
+        ctx.import_flows(dev(fields), slots, pov_mode=True)
+        sums = fit(ctx, slots)[1]
+        axes = ctx.radial_axes(slots, centres, [False] * n, pov_mode=True)
+        npx = np.float64(w) * np.float64(h)
+        assert bits(sums[:, S]) == bits(np.full(n, w * h))
+        assert bits(axes[:, 2]) == bits(sums[:, SU] / npx)
+        assert bits(axes[:, 3]) == bits(sums[:, SV] / npx)
+        per_item = np.stack([random_map(w, h, 70), np.zeros((h, w), np.uint8), random_map(w, h, 72)])
+        for maps, live in ((padded(per_item), [0, 2]), (dev(random_map(w, h, 73)), [0, 1, 2])):
+            sums = fit(ctx, slots, weights=maps)[1]
+            rec = window(maps)
+            assert not rec["cut"].any() and (sums[live, S] > 0).all()
+            assert bits(rec["shift_x"][live]) == bits(sums[live, SU] / sums[live, S])
+            assert bits(rec["shift_y"][live]) == bits(sums[live, SV] / sums[live, S])
+            if len(live) < n:                             # the all-zero map: rule W5
+                assert bits(sums[1]) == bits(np.zeros(12))
+                assert bits([rec["shift_x"][1], rec["shift_y"][1]]) == bits(np.zeros(2))
+
+
 # ---- 3. the subtraction ---------------------------------------------------------------------------------------------------------
 def rec_bytes(recs):
     return [(x, y, np.float32(d).tobytes(), np.float32(m).tobytes(), c) for x, y, d, m, c in recs]

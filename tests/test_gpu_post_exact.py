@@ -1,4 +1,4 @@
-"""The post kernels (k_pass1 / k_pass1_final, k_radial / k_radial_final, ffl_div_at, the importing loader) against the exact
+"""The post kernels (k_pass1 / k_pass1_final, k_strip_sums / k_radial_final, ffl_div_at, the importing loader) against the exact
 references of tests/post_ref.py, at the sizes the library ships for and at sizes chosen against the kernels' constants, on
 fields built to go wrong: winners planted on every kind of edge, exact ties across lanes / strips / row groups / workgroups /
 final-loop trips, NaN and infinities, sums that cancel, magnitudes from float32 denormals to 1e4, and every bit pattern of
