@@ -1,0 +1,272 @@
+"""The composed chunk schedules under slot recycling, on the device, against by-hand runs (tests/chunk_by_hand.py): bytes, no
+tolerance anywhere.
+
+One aperiodic clip -- 41 pairs of 64x48 whose period (53) is longer than the chunk, so no two pairs are the same bytes and a
+read of a stale slot, of another pair's map or of another pair's centre cannot hide -- goes through two engine contexts that
+both wrap their flow-slot ring:
+
+    R1   B = 3, depth 1, 8 frame slots, 19 flow slots: 14 batches, a ragged last batch of 2, the ring wraps twice;
+    R2   B = 4, depth 2, 15 frame slots, 25 flow slots: 11 batches, the last batch is one pair.
+
+Every case of CASES runs through process_chunk (device schedule; the host schedule where the keywords allow one) and, K1-K5,
+through process_flows fed with the by-hand raw fields, once as one array and once as segments (5, 1, 35).  Post records,
+motion records, cell grids, ALL n flows_out fields and the pass-1 records are compared with by_hand's on bytes.
+
+The cut thresholds put about half the pairs on either side of the cut test, so the cut path, its zero records and the uncut
+path all run.  They come from CPU references (oracle.farneback, fb_flags_ref and dis_ref fields, motion_ref fits, the exact
+mean of weights_ref), not from a device run: 0.44 for raw fields (CPU mean_mag 0.225 .. 0.629, median 0.441), 0.145 for
+compensated ones (0.079 .. 0.205, medians 0.141 .. 0.150 over the four models and maps), 0.18 for compensated Gaussian-window
+fields (median 0.180) and 0.10 for compensated DIS fields (median 0.1035).  The conditions themselves are asserted on the
+by-hand result (test_the_clip_and_the_thresholds_do_their_work).
+
+DIS refuses 64x48 (rule D2: the coarsest scale would lie below the finest), so its row runs the same clip at 128x96, the
+smallest size of this aspect it accepts.
+
+What turns these tests red, tried with pipeline.py edited by hand (plain Python, every slot index still checked by the
+library): _ChunkMotion.behind taking its slots % (ring + 1) -- every compensated case, the library refuses slot `ring`;
+_DevicePost._maps(j0) -> _maps(0) -- K3, K5 and the leak test on the bytes of nearly every record; the window calls queued
+before cell_stats -- K4 on bytes (not on every context: the schedule's centre buffer may be handed the memory of the chunk
+before it, with the same centres in it; the host ledger test sees it always); flows_out exported before the subtraction --
+every flows_out of K1, K2, K4 and K6.  A flow ring ONE slot shorter than min_flow_slots changes no byte here: the bound has
+that one slot to spare (test_chunk_schedule_host.py derives it), and a ring short enough to hand the device schedule's
+window call a stale neighbour also repeats a slot inside that call's seq, which the library refuses."""
+import functools
+import random
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+import chunk_by_hand as bh
+from funscript_flow_amd import _capi, pipeline
+from funscript_flow_amd.synth import sine_translate_frames
+
+DEV = "cuda:0"
+W, H, N = 64, 48, 41
+CELLS = 8
+CONTEXTS = {"R1": dict(B=3, depth=1, frame_slots=2 * 3 + 2, flow_slots=pipeline.min_flow_slots(3)),
+            "R2": dict(B=4, depth=2, frame_slots=pipeline.min_frame_slots(4, 2), flow_slots=pipeline.min_flow_slots(4, 2))}
+RAW, COMP = 0.44, 0.145
+CASES = {
+    "K0": dict(kw=dict(axes=True), thr=RAW, povs=(False, True), host=True, contexts=("R1", "R2")),
+    "K1": dict(kw=dict(axes=True, compensate="translation"), flows_out="nhwc", thr=COMP, povs=(False, True), host=True, contexts=("R1", "R2")),
+    "K2": dict(kw=dict(compensate={"model": "affine", "iterations": 2, "tau": 0.5}), maps="static", flows_out="nchw", thr=COMP,
+               povs=(False, True), contexts=("R1", "R2")),
+    "K3": dict(kw=dict(compensate="rigid"), maps="padded", thr=COMP, povs=(False,), contexts=("R1", "R2")),
+    "K4": dict(kw=dict(compensate="similarity", center="variance", cells=CELLS), grid=True, flows_out="nhwc", thr=COMP,
+               povs=(False, True), contexts=("R1", "R2")),
+    "K5": dict(kw=dict(), maps="pair", thr=RAW, povs=(False, True), contexts=("R1", "R2")),
+    "K6-dis": dict(kw=dict(axes=True, compensate="translation"), flows_out="nhwc", thr=0.10, povs=(False,), contexts=("R1",),
+                   engine=dict(flow="dis"), size=(128, 96)),
+    "K6-gaussian": dict(kw=dict(axes=True, compensate="translation"), flows_out="nhwc", thr=0.18, povs=(False,), contexts=("R1",),
+                        engine=dict(window="gaussian")),
+}
+FLOWS_CASES = ("K1", "K2", "K3", "K4", "K5")
+SHORT = (1, 5, 7, 13)      # one pair; shorter than the radius; radius + 1; exactly one full window
+
+
+def dev(a):
+    return torch.from_numpy(np.array(a, order="C")).to(DEV)
+
+
+@functools.lru_cache(maxsize=None)
+def clip(w=W, h=H):
+    fr = sine_translate_frames(N + 1, w, h, seed=3, zoom=0.03, period=53, amp=(6.0, 3.0))
+    fr.setflags(write=False)
+    return fr
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_raw():
+    return bh.oracle_fields(clip())
+
+
+def size_of(case):
+    return CASES[case].get("size", (W, H))
+
+
+@functools.lru_cache(maxsize=None)
+def maps_of(kind, w, h, n):
+    """the case's maps as a host array: one static map, or one per pair (a different seed each)"""
+    m = bh.random_map(w, h, 500) if kind == "static" else bh.pair_maps(w, h, N, 600)[:n]
+    m.setflags(write=False)
+    return m
+
+
+def device_maps(kind, w, h, n):
+    if kind is None:
+        return None
+    m = maps_of(kind, w, h, n)
+    return bh.padded(m, DEV) if kind == "padded" else dev(m)
+
+
+def hand_kw(case):
+    c, kw = CASES[case], dict(CASES[case]["kw"])
+    kw.pop("axes", None)
+    eng = c.get("engine", {})
+    if "flow" in eng:
+        kw["algo"] = (eng["flow"], None)
+    if "window" in eng:
+        kw["window"] = eng["window"]
+    return kw
+
+
+@functools.lru_cache(maxsize=None)
+def hand(case, pov, n=N):
+    """by_hand of the case's first n pairs, computed once and left unchanged"""
+    c = CASES[case]
+    w, h = size_of(case)
+    with bh.hand_context(w, h, n) as one:
+        kind = c.get("maps")
+        maps = None if kind is None else dev(maps_of(kind, w, h, n))        # contiguous here, whatever view the engine gets
+        res = bh.by_hand(one, clip(w, h)[:n + 1], pov=pov, thr=c["thr"], weights=maps, **hand_kw(case))
+        assert one.graph_stats()["capture_failures"] == 0
+    for v in (res["flows"], res["raw"]):
+        v.setflags(write=False)
+    return res
+
+
+def engine_context(name, case):
+    c = CONTEXTS[name]
+    w, h = size_of(case)
+    return _capi.Context(w, h, max_batch=c["B"], frame_slots=c["frame_slots"], flow_slots=c["flow_slots"])
+
+
+def same(got, want, item, what):
+    """bytes against bytes; names the records that differ"""
+    if got == want:
+        return
+    assert len(got) == len(want), f"{what}: {len(got)} bytes, by hand {len(want)}"
+    g, w = np.frombuffer(got, np.uint8).reshape(-1, item), np.frombuffer(want, np.uint8).reshape(-1, item)
+    raise AssertionError(f"{what}: items {np.flatnonzero((g != w).any(axis=1)).tolist()} of {len(g)} differ from the by-hand run")
+
+
+def run(eng, ctx, case, pov, schedule, entry, n=N):
+    """one chunk through the engine, every output against by_hand's"""
+    c, want = CASES[case], hand(case, pov, n)
+    w, h = size_of(case)
+    what = f"{case} pov={pov} {schedule} {entry} n={n}"
+    kw = dict(c["kw"])
+    kind = c.get("maps")
+    if kind is not None:
+        kw["weights"] = device_maps(kind, w, h, n)
+    mo = grid = T = None
+    if "compensate" in kw:
+        mo = kw["motion_out"] = torch.full((n * 64,), 0xA5, dtype=torch.uint8, device=DEV)
+    if c.get("grid"):
+        grid = kw["grid_out"] = torch.full((n * CELLS * CELLS * _capi.CELL_DTYPE.itemsize,), 0xA5, dtype=torch.uint8, device=DEV)
+    if entry == "chunk":
+        src = list(clip(w, h)[:n + 1])
+        if c.get("flows_out"):
+            T = kw["flows_out"] = torch.full((n, h, w, 2) if c["flows_out"] == "nhwc" else (n, 2, h, w), float("nan"), device=DEV)
+        call = eng.process_chunk
+    else:
+        raw = dev(want["raw"])
+        src = raw if entry == "flows" else [raw[:5], raw[5], raw[6:]]
+        if entry == "segments":
+            assert [len(raw[:5]), 1, len(raw[6:])] == [5, 1, 35]
+        call = eng.process_flows
+    item = _capi.PASS2_AXES_DTYPE.itemsize
+    if schedule == "device":
+        buf = call(src, pov, c["thr"], post_out=True, **kw)
+        same(buf.cpu().numpy().tobytes(), want["post"], item, what + ": post records")
+    else:
+        comps, recs = call(src, pov, c["thr"], **kw)
+        rec = bh.records(want["post"])
+        cols = np.stack([rec[k] for k in ("dot", "tangential", "shift_x", "shift_y")], axis=1)
+        same(np.ascontiguousarray(comps).tobytes(), np.ascontiguousarray(cols).tobytes(), 32, what + ": components")
+        assert bh.rec_bytes(recs) == bh.rec_bytes(want["pass1"]), what + ": pass-1 records"
+    if mo is not None:
+        same(mo.cpu().numpy().tobytes(), want["motion"], 64, what + ": motion records")
+    if grid is not None:
+        same(grid.cpu().numpy().tobytes(), want["grid"], CELLS * CELLS * _capi.CELL_DTYPE.itemsize, what + ": cell grids")
+    if T is not None:
+        got = T.cpu().numpy() if c["flows_out"] == "nhwc" else T.permute(0, 2, 3, 1).contiguous().cpu().numpy()
+        same(got.tobytes(), want["flows"].tobytes(), h * w * 8, what + ": flows_out")
+
+
+def plain_chunk(eng, case):
+    return eng.process_chunk(list(clip(*size_of(case))), post_out=True, axes=True).cpu().numpy().tobytes()
+
+
+def runs_of(case):
+    c = CASES[case]
+    runs = [(pov, "device", "chunk") for pov in c["povs"]]
+    if c.get("host"):
+        runs += [(pov, "host", "chunk") for pov in c["povs"]]
+    if case in FLOWS_CASES:
+        runs += [(pov, "device", entry) for pov in c["povs"] for entry in ("flows", "segments")]
+    random.Random(case).shuffle(runs)      # a fixed shuffled order
+    return runs
+
+
+# ---- the by-hand runs themselves ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case,pov", [(k, p) for k, c in CASES.items() for p in c["povs"]], ids=lambda v: str(v))
+def test_the_clip_and_the_thresholds_do_their_work(case, pov, capsys):
+    """the conditions the clip and the thresholds were chosen for, on the by-hand result, and its two CPU anchors"""
+    res = hand(case, pov)
+    tuned = "engine" not in CASES[case]
+    bh.check_anchors(res, oracle_raw() if tuned else None)
+    rec = bh.records(res["post"])
+    assert len(rec) == N
+    assert len({f.tobytes() for f in res["raw"]}) == N and len({f.tobytes() for f in res["flows"]}) == N    # no two pairs alike
+    centres = len(set(zip(rec["x"].tolist(), rec["y"].tolist())))
+    cuts = int((rec["cut"] != 0).sum())
+    with capsys.disabled():
+        print(f"\n  {case} pov={pov} thr={CASES[case]['thr']}: {cuts} of {N} pairs cut, {centres} distinct centres, mean_mag "
+              f"{float(rec['mean_mag'].min()):.4f} .. {float(rec['mean_mag'].max()):.4f}")
+    if not pov:
+        assert centres >= N / 2
+    assert N / 4 <= cuts <= 3 * N / 4
+    if res["motion"] is not None:
+        models = np.frombuffer(res["motion"], _capi.MOTION_DTYPE)
+        assert (models["status"] == 0).all() and len({m.tobytes() for m in models}) == N
+
+
+# ---- the engine against them ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case,name", [(k, r) for k, c in CASES.items() for r in c["contexts"]], ids=lambda v: str(v))
+def test_composed_chunk_on_a_wrapping_ring_is_the_by_hand_run(case, name):
+    c = CONTEXTS[name]
+    assert c["flow_slots"] < N and -(-N // c["B"]) == {"R1": 14, "R2": 11}[name] and N % c["B"] == {"R1": 2, "R2": 1}[name]
+    with engine_context(name, case) as ctx:
+        eng = pipeline.PairEngine(ctx, depth=c["depth"], **CASES[case].get("engine", {}))
+        before = plain_chunk(eng, case)
+        for pov, schedule, entry in runs_of(case):
+            run(eng, ctx, case, pov, schedule, entry)
+        assert plain_chunk(eng, case) == before
+        assert ctx.graph_stats()["capture_failures"] == 0
+    # the rings are the smallest the engine accepts: R1 wraps twice, R2 once and most of a second time
+    assert (c["frame_slots"], c["flow_slots"]) == {"R1": (8, 19), "R2": (15, 25)}[name]
+
+
+@pytest.mark.parametrize("name", list(CONTEXTS))
+def test_cases_leave_nothing_behind_for_the_next(name):
+    """every 64x48 case of the tuned engine on ONE context, in a fixed shuffled order; the plain chunk before and after"""
+    c = CONTEXTS[name]
+    runs = [(case, pov) for case in ("K0", "K1", "K2", "K3", "K4", "K5") for pov in CASES[case]["povs"]]
+    random.Random(name).shuffle(runs)
+    with engine_context(name, "K0") as ctx:
+        eng = pipeline.PairEngine(ctx, depth=c["depth"])
+        before = plain_chunk(eng, "K0")
+        for i, (case, pov) in enumerate(runs):
+            run(eng, ctx, case, pov, "device", ("chunk", "flows")[i % 2] if case in FLOWS_CASES else "chunk")
+        assert plain_chunk(eng, "K0") == before
+        assert ctx.graph_stats()["capture_failures"] == 0
+
+
+@pytest.mark.parametrize("case", ["K1", "K4"])
+def test_short_chunks(case):
+    """one pair; shorter than the radius; radius + 1; exactly one full window -- none of them fills the ring"""
+    c = CONTEXTS["R1"]
+    with engine_context("R1", case) as ctx:
+        eng = pipeline.PairEngine(ctx, depth=c["depth"])
+        before = plain_chunk(eng, case)
+        for n in SHORT:
+            for pov in CASES[case]["povs"]:
+                run(eng, ctx, case, pov, "device", "chunk", n)
+                run(eng, ctx, case, pov, "device", "flows", n)
+        assert plain_chunk(eng, case) == before
+        assert ctx.graph_stats()["capture_failures"] == 0
