@@ -36,6 +36,10 @@ YUV_RANGES = {"limited": 0, "full": 1}
 
 # device-memory I/O (ffl_upload_frames_device / ffl_export_flows): FFL_DEV_* and FFL_FLOW_* codes
 DEV_FORMATS = {"gray": 0, "bgr": 1, "rgb": 2, "i420": 3, "nv12": 4}
+# source maps of the front-end: the header's enum
+FFL_MAX_REMAPS = 8
+REMAP_NO_SOURCE = -2 ** 31   # FFL_REMAP_NO_SOURCE: qx of a sample with no source (rule R1)
+REMAP_SUPERSAMPLES = (1, 2, 4)
 FLOW_LAYOUTS = {"nhwc": 0, "nchw": 1}
 FFL_ERR_INVALID, FFL_ERR_STATE = 1, 4
 # flow import (ffl_import_flows): FFL_F32, FFL_F16, FFL_BF16 by __cuda_array_interface__ typestr
@@ -624,6 +628,47 @@ def frontend_yuv_window(src_size, layout, resize, crop, out_size, stride=None, d
     return tuple(win), b.value
 
 
+def _map_array(map, out_size, supersample):
+    """a source map as the C-contiguous (S*oh, S*ow, 2) int32 array the library reads; ValueError for another shape or S"""
+    if supersample not in REMAP_SUPERSAMPLES or isinstance(supersample, bool):
+        raise ValueError(f"supersample must be one of {REMAP_SUPERSAMPLES}, got {supersample!r}")
+    m = np.asarray(map)
+    want = (supersample * int(out_size[1]), supersample * int(out_size[0]), 2)
+    if m.dtype != np.int32 or m.shape != want:
+        raise ValueError(f"a source map for a {out_size[0]}x{out_size[1]} operand at supersample={supersample} is an int32 array of "
+                         f"shape {want} holding (qx, qy) in 1/32 px, got {m.dtype} {m.shape}")
+    return np.ascontiguousarray(m)
+
+
+def remap_check(map, out_size, src_size, supersample=1, rotate=0, mirror=False, yuv_range="limited"):
+    """ffl_remap_check: rules R1 and R6 of DESIGN.md appendix R for `map` (see Context.remap_create) over a STORED
+    src_size = (w, h) source with the stream metadata of source_info -> (upright tap window (x, y, w, h), the stored window
+    a host 4:2:0 frame transfers, number of valid entries).  Pure host check; ValueError with the library's rule."""
+    info = source_info(rotate, mirror, yuv_range)
+    m = _map_array(map, out_size, supersample)
+    up, st, valid = (C.c_int * 4)(), (C.c_int * 4)(), C.c_size_t()
+    _check(load().ffl_remap_check(m.ctypes.data, int(out_size[0]), int(out_size[1]), int(supersample), int(src_size[0]),
+                                  int(src_size[1]), C.byref(info) if info is not None else None, up, st, C.byref(valid)),
+           exc=ValueError)
+    return tuple(up), tuple(st), valid.value
+
+
+def remap_bytes(out_size, supersample=1):
+    """device bytes one source map adds to a context of out_size (ffl_remap_bytes)"""
+    return _sizes("ffl_remap_bytes", out_size[0], out_size[1], supersample)
+
+
+class Remap:
+    """A source map resident in a context (Context.remap_create): `id`, the upright `src_size` = (w, h) it addresses, its
+    `supersample`, `window` = the upright bounding box (x, y, w, h) of every tap (rule R6) and `valid`, its valid entries."""
+
+    def __init__(self, id, src_size, supersample, window, valid):
+        self.id, self.src_size, self.supersample, self.window, self.valid = id, tuple(src_size), supersample, window, valid
+
+    def __repr__(self):
+        return f"Remap(id={self.id}, src_size={self.src_size}, supersample={self.supersample}, window={self.window})"
+
+
 # ---- the C ABI, stated once --------------------------------------------------------------------------------------------------
 # SIGNATURES holds every entry point of include/ffl.h, in the header's order, as (return type, parameter types).  load()
 # applies it, EXPORTS is its keys, and tests/test_abi_host.py holds it against the prototypes parsed from the header, parameter
@@ -667,6 +712,12 @@ SIGNATURES = {
     "ffl_dev_frame_check16_src": _SRC,
     "ffl_upload_frames_device_src": _SRC,
     "ffl_upload_frames_device16_src": _SRC,
+    "ffl_remap_check": (_i, (_vp,) + (_i,) * 5 + (_P(SourceInfo), _ip, _ip, _szp)),
+    "ffl_remap_bytes": (_i, (_i,) * 3 + (_szp,)),
+    "ffl_remap_create": (_i, (_ctx, _vp, _i, _i, _i, _ip)),
+    "ffl_remap_destroy": (_i, (_ctx, _i)),
+    "ffl_upload_frames_remap": (_i, (_ctx, _i, _i, _vpp, _i, _i, _i, _pd, _i, _i, _i, _P(SourceInfo))),
+    "ffl_upload_frames_device_remap": (_i, _DEVICE + (_i,) * 5 + (_u64, _P(SourceInfo))),
     "ffl_export_flows": (_i, (_ctx, _i, _ip, _vp, _i, _pd, _u64)),
     "ffl_dev_flow_check": (_i, (_i,) * 4 + (_P(DevFlow),)),
     "ffl_import_flows": (_i, (_ctx, _i, _ip, _P(DevFlow), _i, _i, _u64)),
@@ -1000,6 +1051,66 @@ class Context:
             self._chk(_src_call(self.L, "ffl_upload_frames_device16", info, *head, depth, msb, *geom))
         else:
             self._chk(_src_call(self.L, "ffl_upload_frames_device", info, *head, *geom))
+
+    # ---- source maps -----------------------------------------------------
+    def remap_create(self, map, src_size, supersample=1):
+        """A source map for this context: an (S*height, S*width, 2) int32 array of (qx, qy), upright source coordinates in
+        1/32 px of an upright src_size = (w, h) source, REMAP_NO_SOURCE in qx where a sample has none (frontend.view_map,
+        frontend.identity_map build them).  Checked (rule R1), copied to the device; the array is not needed afterwards.
+        Returns a Remap; at most FFL_MAX_REMAPS are alive per context."""
+        m = _map_array(map, (self.width, self.height), supersample)
+        window, _, valid = remap_check(m, (self.width, self.height), src_size, supersample)
+        rid = C.c_int(-1)
+        self._chk(self.L.ffl_remap_create(self._h, m.ctypes.data, int(supersample), int(src_size[0]), int(src_size[1]), C.byref(rid)))
+        return Remap(rid.value, (int(src_size[0]), int(src_size[1])), int(supersample), window, valid)
+
+    def remap_destroy(self, remap):
+        """frees the map (a Remap or its id); safe straight after an upload call that used it"""
+        self._chk(self.L.ffl_remap_destroy(self._h, int(getattr(remap, "id", remap))))
+
+    def upload_frames_remap(self, first_slot, frames, remap, fmt="bgr", depth=8, msb=None, rotate=0, mirror=False,
+                            yuv_range="limited"):
+        """Host frames -> the operand `remap` gathers from them, in consecutive slots (ffl_upload_frames_remap; rules R2 to R6):
+        fmt "bgr" / "rgb": (h, w, 3) uint8 frames, which travel whole; "i420" / "nv12": (3h/2, w) 4:2:0 arrays of uint8, or
+        of uint16 with depth=9..16 and msb as upload_frames_yuv takes them -- only the rectangle the map's taps touch is
+        transferred.  rotate, mirror, yuv_range: how the frames are STORED (see source_info); the map is in upright terms."""
+        code = dev_format(fmt)
+        info = source_info(rotate, mirror, yuv_range)
+        yuv = code in (DEV_FORMATS["i420"], DEV_FORMATS["nv12"])
+        depth, msb = yuv_depth(depth, fmt if yuv else None, msb)
+        if yuv:
+            dt = np.uint16 if depth > 8 else np.uint8
+            fr = [f if (f.ndim == 2 and f.strides[1] == f.itemsize) else np.ascontiguousarray(f) for f in frames]
+            f0 = fr[0]
+            if any(f.dtype != dt or f.ndim != 2 or f.shape != f0.shape or f.strides[0] != f0.strides[0] for f in fr) or f0.shape[0] % 3:
+                raise FFLError(f"upload_frames_remap needs (3h/2, w) {np.dtype(dt).name} frames of one shape and row stride for "
+                               f"fmt={fmt!r}, depth={depth}")
+            size = (f0.shape[1], f0.shape[0] * 2 // 3)
+        else:
+            fr = [f if (f.ndim == 3 and f.strides[2] == 1 and f.strides[1] == 3) else np.ascontiguousarray(f) for f in frames]
+            f0 = fr[0]
+            if any(f.dtype != np.uint8 or f.ndim != 3 or f.shape != f0.shape or f.shape[2] != 3 or f.strides[0] != f0.strides[0]
+                   for f in fr):
+                raise FFLError(f"upload_frames_remap needs (h, w, 3) uint8 frames of one shape and row stride for fmt={fmt!r}")
+            size = (f0.shape[1], f0.shape[0])
+        ptrs = (C.c_void_p * len(fr))(*[f.ctypes.data for f in fr])
+        self._chk(self.L.ffl_upload_frames_remap(self._h, int(first_slot), len(fr), ptrs, code, size[0], size[1], f0.strides[0], depth,
+                                                 msb, int(getattr(remap, "id", remap)), C.byref(info) if info is not None else None))
+
+    def upload_frames_device_remap(self, first_slot, frames, fmt, remap, stream=None, depth=8, msb=None, rotate=0, mirror=False,
+                                   yuv_range="limited"):
+        """upload_frames_device through a source map (ffl_upload_frames_device_remap): device frames of any DEV_FORMATS
+        format -- a "gray" frame of any size is gathered like a channel -- in one launch, under the stream contract of
+        upload_frames_device."""
+        code = dev_format(fmt)
+        depth, msb = yuv_depth(depth, fmt, msb)
+        info = source_info(rotate, mirror, yuv_range)
+        rows, size = self._device_rows(frames, code, depth)
+        descs = np.ascontiguousarray(rows, np.int64)
+        self._chk(self.L.ffl_upload_frames_device_remap(self._h, int(first_slot), len(descs), descs.ctypes.data, code, depth, msb,
+                                                        size[0], size[1], int(getattr(remap, "id", remap)),
+                                                        stream_handle(stream, self.device),
+                                                        C.byref(info) if info is not None else None))
 
     @staticmethod
     def _device_rows(frames, code, depth=8):

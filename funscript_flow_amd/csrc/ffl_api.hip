@@ -313,6 +313,16 @@ struct ffl_ctx {
     // k_frontend_dev reads (`copy`)
     Event ev_caller;
     PinBuf<FrameDesc> h_dtab; DevBuf<FrameDesc> d_dtab;
+    // the source maps of ffl_remap_create: the device copy, what the upload calls check a source
+    // against, the upright bounding box of its taps (rule R6) and the upload call that read it last (ffl_remap_destroy
+    // waits for it).  Users hold up_mu, as every uploader does.
+    struct Remap {
+        DevBuf<int2> d;
+        int ss = 0, sw = 0, sh = 0;   // supersampling; the upright source size
+        int ux[2] = {0, 0}, uy[2] = {0, 0};
+        EvRef last;
+    };
+    Remap remaps[FFL_MAX_REMAPS];
     // flow slots
     DevBuf<float> d_flow;             // [n_slots][2N]
     // Result records live in pinned, device-mapped host memory: the reduction kernels store their
@@ -747,8 +757,9 @@ static int open_slot_list(ffl_ctx *c, const char *fn, const char *what, int n, c
 // it is, so its upright size is the output's).  Fills everything of *p but kind and rgb (the caller sets them) and the
 // 16-bit reduction (front_depth()); fn prefixes the message.  si NULL: no metadata.
 enum { FRONT_BGR = 0, FRONT_YUV = 1, FRONT_GRAY = 2 };
-static int front_geometry(ffl_ctx *c, const char *fn, int cls, int sw, int sh, const ffl_source_info *si, int rw, int rh, int cx,
-                          int cy, int ow, int oh, FrontParams *p) {
+// The part of it that describes the source alone, which the map-driven calls (ffl_upload_frames_remap) share: the metadata
+// rules, the upright size (p->sw x p->sh), the map of rule Y6 and rule Y7's flag.
+static int front_source(ffl_ctx *c, const char *fn, int cls, int sw, int sh, const ffl_source_info *si, FrontParams *p) {
     static const ffl_source_info none = {0, 0, 0};
     if (!si) si = &none;
     if (si->rotate != 0 && si->rotate != 90 && si->rotate != 180 && si->rotate != 270)
@@ -763,21 +774,7 @@ static int front_geometry(ffl_ctx *c, const char *fn, int cls, int sw, int sh, c
                                            "no colour range", fn);
     const int rot = si->rotate / 90;
     const int uw = rot & 1 ? sh : sw, uh = rot & 1 ? sw : sh;  // the upright size
-    if (cls == FRONT_GRAY && (rw != uw || rh != uh))
-        return set_err(c, FFL_ERR_INVALID, "%s: gray frames are copied as they are: a resize (%dx%d -> %dx%d) is refused", fn, uw, uh,
-                       rw, rh);
-    if (cls == FRONT_GRAY && (uw != ow || uh != oh))
-        return set_err(c, FFL_ERR_INVALID, "%s: a gray frame must be the context size %dx%d, got %dx%d", fn, ow, oh, uw, uh);
-    if (sw < 1 || sh < 1 || sw > 32768 || sh > 32768 || rw < 1 || rh < 1 || rw > 32768 || rh > 32768 || ow < 1 || oh < 1)
-        return set_err(c, FFL_ERR_INVALID, "%s: unsupported source %dx%d / resize %dx%d / output %dx%d", fn, sw, sh, rw, rh, ow, oh);
-    if (cx < 0 || cy < 0 || cx + ow > rw || cy + oh > rh)
-        return set_err(c, FFL_ERR_INVALID, "%s: crop window (%d, %d) + %dx%d does not fit the %dx%d resized frame", fn, cx, cy, ow,
-                       oh, rw, rh);
     p->sw = uw; p->sh = uh;
-    p->cx = cx; p->cy = cy; p->ow = ow; p->oh = oh;
-    p->scale_x = 1. / ((double)rw / uw);
-    p->scale_y = 1. / ((double)rh / uh);
-    p->mode = (rw == uw && rh == uh) ? FFL_FRONT_IDENTITY : (uw == 2 * rw && uh == 2 * rh) ? FFL_FRONT_AREA2 : FFL_FRONT_GENERIC;
     p->shift16 = p->round16 = 0;  // front_depth() sets them for 16-bit sources
     // rule Y6: the mirror first (ux <- uw - 1 - ux = mx * ux + m0), then the row of the table for the rotation
     const int mx = si->mirror ? -1 : 1, m0 = si->mirror ? uw - 1 : 0;
@@ -793,13 +790,35 @@ static int front_geometry(ffl_ctx *c, const char *fn, int cls, int sw, int sh, c
     return FFL_OK;
 }
 
+static int front_geometry(ffl_ctx *c, const char *fn, int cls, int sw, int sh, const ffl_source_info *si, int rw, int rh, int cx,
+                          int cy, int ow, int oh, FrontParams *p) {
+    if (int rc = front_source(c, fn, cls, sw, sh, si, p)) return rc;
+    const int uw = p->sw, uh = p->sh;  // the upright size
+    if (cls == FRONT_GRAY && (rw != uw || rh != uh))
+        return set_err(c, FFL_ERR_INVALID, "%s: gray frames are copied as they are: a resize (%dx%d -> %dx%d) is refused", fn, uw, uh,
+                       rw, rh);
+    if (cls == FRONT_GRAY && (uw != ow || uh != oh))
+        return set_err(c, FFL_ERR_INVALID, "%s: a gray frame must be the context size %dx%d, got %dx%d", fn, ow, oh, uw, uh);
+    if (sw < 1 || sh < 1 || sw > 32768 || sh > 32768 || rw < 1 || rh < 1 || rw > 32768 || rh > 32768 || ow < 1 || oh < 1)
+        return set_err(c, FFL_ERR_INVALID, "%s: unsupported source %dx%d / resize %dx%d / output %dx%d", fn, sw, sh, rw, rh, ow, oh);
+    if (cx < 0 || cy < 0 || cx + ow > rw || cy + oh > rh)
+        return set_err(c, FFL_ERR_INVALID, "%s: crop window (%d, %d) + %dx%d does not fit the %dx%d resized frame", fn, cx, cy, ow,
+                       oh, rw, rh);
+    p->cx = cx; p->cy = cy; p->ow = ow; p->oh = oh;
+    p->scale_x = 1. / ((double)rw / uw);
+    p->scale_y = 1. / ((double)rh / uh);
+    p->mode = (rw == uw && rh == uh) ? FFL_FRONT_IDENTITY : (uw == 2 * rw && uh == 2 * rh) ? FFL_FRONT_AREA2 : FFL_FRONT_GENERIC;
+    return FFL_OK;
+}
+
 // The frame-by-frame loop of ffl_upload_frames_raw and ffl_upload_frames_yuv, called with up_mu and the context lock held.
 // Frame i takes the next buffer pair of the raw-frame ring; direct(i) says whether its fbytes go to the device straight
 // out of caller memory (send_direct(i, d)) or are first staged into the pinned buffer (stage(i, h, copy_threads), run
-// WITHOUT the context lock) and sent as one transfer; one k_frontend launch then reads desc(d) into frame slot first + i.
+// WITHOUT the context lock) and sent as one transfer; one k_frontend launch (rp: k_frontend_remap with that map) then reads
+// desc(d) into frame slot first + i.
 template <class Direct, class Stage, class SendDirect, class Desc>
 static int upload_staged(ffl_ctx *c, CtxLock &lk, int first, int n, size_t fbytes, const FrontParams &fp, Direct direct,
-                         Stage stage, SendDirect send_direct, Desc desc) {
+                         Stage stage, SendDirect send_direct, Desc desc, const RemapParams *rp = nullptr) {
     for (int i = 0; i < n; i++) {
         const int fs = first + i;
         auto &rb = c->raw[c->raw_next++ % FFL_RAW_RING];
@@ -834,7 +853,8 @@ static int upload_staged(ffl_ctx *c, CtxLock &lk, int first, int n, size_t fbyte
         }
         {
             ProfScope ps(c, FFL_K_FRONTEND, c->s_copy);
-            ffl_launch_frontend(desc(rb.d), c->d_gray + (size_t)fs * c->N, fp, c->s_copy);
+            if (rp) ffl_launch_frontend_remap(desc(rb.d), c->d_gray + (size_t)fs * c->N, fp, *rp, c->s_copy);  // the map instead of
+            else ffl_launch_frontend(desc(rb.d), c->d_gray + (size_t)fs * c->N, fp, c->s_copy);              // resize + crop
         }
         HIPCHK(c, hipEventRecord(rb.ev, c->s_copy));
         rb.busy = true;
@@ -1169,17 +1189,10 @@ int ffl_upload_frames(ffl_ctx *c, int first, int n, const uint8_t *const *frames
     return publish_frames(c, first, n);
 }
 
-// Decoded frames -> gray frame slots through k_frontend (resize + crop + luma in one pass).  Frame by
-// frame: tight copy into a pinned ring buffer, H2D, kernel -- the 3 * src_w * src_h byte transfer is the
-// cost, so there is nothing to gain from batching the launches.
-static int upload_raw(ffl_ctx *c, const char *fn, int first, int n, const uint8_t *const *frames, int sw, int sh,
-                      ptrdiff_t stride_bytes, int rgb_order, int rw, int rh, int crop_x, int crop_y, const ffl_source_info *si) {
-    if (!c) return FFL_ERR_INVALID;
-    std::unique_lock<std::mutex> ul(c->up_mu);
-    CtxLock lk(c->mu);
-    if (int rc = check_frame_run(c, fn, first, n, frames, frames)) return rc;
-    FrontParams fp;
-    if (int rc = front_geometry(c, fn, FRONT_BGR, sw, sh, si, rw, rh, crop_x, crop_y, c->w, c->h, &fp)) return rc;
+// What ffl_upload_frames_raw and the 3-channel formats of ffl_upload_frames_remap share once the geometry is known: the stride
+// rule and the whole stored frame's way through upload_staged.
+static int send_raw(ffl_ctx *c, CtxLock &lk, const char *fn, int first, int n, const uint8_t *const *frames, int sw, int sh,
+                    ptrdiff_t stride_bytes, int rgb_order, FrontParams &fp, const RemapParams *rp) {
     if (stride_bytes < (ptrdiff_t)sw * 3)
         return set_err(c, FFL_ERR_INVALID, "%s: stride %td < row bytes %d", fn, stride_bytes, sw * 3);
     HIPCHK(c, hipSetDevice(c->device));
@@ -1201,7 +1214,21 @@ static int upload_raw(ffl_ctx *c, const char *fn, int first, int n, const uint8_
         s.cs = 1;
         return s;
     };
-    return upload_staged(c, lk, first, n, fbytes, fp, direct, stage, send_direct, desc);
+    return upload_staged(c, lk, first, n, fbytes, fp, direct, stage, send_direct, desc, rp);
+}
+
+// Decoded frames -> gray frame slots through k_frontend (resize + crop + luma in one pass).  Frame by
+// frame: tight copy into a pinned ring buffer, H2D, kernel -- the 3 * src_w * src_h byte transfer is the
+// cost, so there is nothing to gain from batching the launches.
+static int upload_raw(ffl_ctx *c, const char *fn, int first, int n, const uint8_t *const *frames, int sw, int sh,
+                      ptrdiff_t stride_bytes, int rgb_order, int rw, int rh, int crop_x, int crop_y, const ffl_source_info *si) {
+    if (!c) return FFL_ERR_INVALID;
+    std::unique_lock<std::mutex> ul(c->up_mu);
+    CtxLock lk(c->mu);
+    if (int rc = check_frame_run(c, fn, first, n, frames, frames)) return rc;
+    FrontParams fp;
+    if (int rc = front_geometry(c, fn, FRONT_BGR, sw, sh, si, rw, rh, crop_x, crop_y, c->w, c->h, &fp)) return rc;
+    return send_raw(c, lk, fn, first, n, frames, sw, sh, stride_bytes, rgb_order, fp, nullptr);
 }
 
 int ffl_upload_frames_raw(ffl_ctx *c, int first, int n, const uint8_t *const *frames, int sw, int sh,
@@ -1253,12 +1280,8 @@ static void front_depth(FrontParams *p, int depth, int msb) {
     p->round16 = 1 << (p->shift16 - 1);
 }
 
-// Every refusal of the YUV path (messages name the rule); fn prefixes the message.  Fills the geometry of *fp and the
-// window.  es: bytes per sample (1; 2: the 16-bit frames of rule Y5, whose depth is checked here too); the stride is in
-// bytes, the window in samples.
-static int yuv_window(ffl_ctx *c, const char *fn, int sw, int sh, int layout, ptrdiff_t stride, int es, int depth,
-                      const ffl_source_info *si, int rw, int rh, int crop_x, int crop_y, int ow, int oh, FrontParams *fp,
-                      YuvWin *out) {
+// the rules of a 4:2:0 single-array frame that need no geometry (es: bytes per sample; the stride is in bytes)
+static int yuv_layout_rules(ffl_ctx *c, const char *fn, int sw, int sh, int layout, ptrdiff_t stride, int es, int depth) {
     const char *twice = es == 2 ? "2 * " : "";
     if (es == 2 && (depth < 9 || depth > 16))
         return set_err(c, FFL_ERR_INVALID, "%s: depth %d outside 9..16 (8-bit frames go through ffl_upload_frames_yuv)", fn, depth);
@@ -1273,15 +1296,30 @@ static int yuv_window(ffl_ctx *c, const char *fn, int sw, int sh, int layout, pt
                        fn, twice, stride, sw);
     if (layout == FFL_YUV_NV12 && stride < (ptrdiff_t)sw * es)
         return set_err(c, FFL_ERR_INVALID, "%s: NV12 needs stride >= %swidth, got %td for width %d", fn, twice, stride, sw);
+    return FFL_OK;
+}
+
+// the upright span ux x uy (inclusive) of a stored sw x sh frame -> the stored rectangle that travels (rule R6 uses it too)
+static void yuv_stored_window(const FrontParams &p, int sw, int sh, const int ux[2], const int uy[2], YuvWin *out) {
+    // rule Y6 is affine with one unit coefficient per stored axis: two opposite corners of the span bound its image
+    const int px[2] = {p.ax * ux[0] + p.bx * uy[0] + p.cx0, p.ax * ux[1] + p.bx * uy[1] + p.cx0};
+    const int py[2] = {p.ay * ux[0] + p.by * uy[0] + p.cy0, p.ay * ux[1] + p.by * uy[1] + p.cy0};
+    yuv_round(std::min(px[0], px[1]), std::max(px[0], px[1]), sw, 16, &out->x0, &out->w);
+    yuv_round(std::min(py[0], py[1]), std::max(py[0], py[1]), sh, 2, &out->y0, &out->h);
+}
+
+// Every refusal of the YUV path (messages name the rule); fn prefixes the message.  Fills the geometry of *fp and the
+// window.  es: bytes per sample (1; 2: the 16-bit frames of rule Y5, whose depth is checked here too); the stride is in
+// bytes, the window in samples.
+static int yuv_window(ffl_ctx *c, const char *fn, int sw, int sh, int layout, ptrdiff_t stride, int es, int depth,
+                      const ffl_source_info *si, int rw, int rh, int crop_x, int crop_y, int ow, int oh, FrontParams *fp,
+                      YuvWin *out) {
+    if (int rc = yuv_layout_rules(c, fn, sw, sh, layout, stride, es, depth)) return rc;
     if (int rc = front_geometry(c, fn, FRONT_YUV, sw, sh, si, rw, rh, crop_x, crop_y, ow, oh, fp)) return rc;
     int ux[2], uy[2];  // the upright span, inclusive
     yuv_span(crop_x, crop_x + ow - 1, fp->sw, fp->scale_x, fp->mode, &ux[0], &ux[1]);
     yuv_span(crop_y, crop_y + oh - 1, fp->sh, fp->scale_y, fp->mode, &uy[0], &uy[1]);
-    // rule Y6 is affine with one unit coefficient per stored axis: two opposite corners of the span bound its image
-    const int px[2] = {fp->ax * ux[0] + fp->bx * uy[0] + fp->cx0, fp->ax * ux[1] + fp->bx * uy[1] + fp->cx0};
-    const int py[2] = {fp->ay * ux[0] + fp->by * uy[0] + fp->cy0, fp->ay * ux[1] + fp->by * uy[1] + fp->cy0};
-    yuv_round(std::min(px[0], px[1]), std::max(px[0], px[1]), sw, 16, &out->x0, &out->w);
-    yuv_round(std::min(py[0], py[1]), std::max(py[0], py[1]), sh, 2, &out->y0, &out->h);
+    yuv_stored_window(*fp, sw, sh, ux, uy, out);
     return FFL_OK;
 }
 
@@ -1325,23 +1363,11 @@ int ffl_frontend_yuv16_window_src(int src_w, int src_h, int layout, ptrdiff_t st
                            crop_x, crop_y, out_w, out_h, win, bytes);
 }
 
-// Decoded 4:2:0 frames -> gray frame slots through k_frontend: the body of ffl_upload_frames_yuv (es = 1) and
-// ffl_upload_frames_yuv16 (es = 2 bytes per sample, reduced by rule Y5).  Frame by frame, as ffl_upload_frames_raw: only
-// the window the crop samples travels -- out of ffl_host_alloc memory one 2-D copy per plane (when every plane's rows
-// start 4-byte aligned and are a multiple of 4 bytes long: unaligned ones take a slow path in the runtime's copy),
-// otherwise copied into the pinned ring buffer and sent as one transfer.  On the device the window is packed: Y (w x h),
-// then U and V (w/2 x h/2 each, I420) or the interleaved UV rows (w x h/2, NV12), es bytes per sample.
-static int upload_yuv(ffl_ctx *c, const char *fn, int first, int n, const uint8_t *const *frames, int sw, int sh,
-                      ptrdiff_t stride_bytes, int layout, int es, int depth, int msb, int rw, int rh, int crop_x, int crop_y,
-                      const ffl_source_info *si) {
-    if (!c) return FFL_ERR_INVALID;
-    std::unique_lock<std::mutex> ul(c->up_mu);
-    CtxLock lk(c->mu);
-    if (int rc = check_frame_run(c, fn, first, n, frames, frames)) return rc;
-    FrontParams fp;
-    YuvWin yw;
-    if (int rc = yuv_window(c, fn, sw, sh, layout, stride_bytes, es, depth, si, rw, rh, crop_x, crop_y, c->w, c->h, &fp, &yw))
-        return rc;
+// What ffl_upload_frames_yuv(16) and the 4:2:0 formats of ffl_upload_frames_remap share once the window is known: the
+// alignment rule of 16-bit frames and the window's way through upload_staged.
+static int send_yuv(ffl_ctx *c, CtxLock &lk, const char *fn, int first, int n, const uint8_t *const *frames, int sw, int sh,
+                    ptrdiff_t stride_bytes, int layout, int es, int depth, int msb, FrontParams &fp, const YuvWin &yw,
+                    const RemapParams *rp) {
     for (int i = 0; es == 2 && i < n; i++)
         if ((uintptr_t)frames[i] & 1) return set_err(c, FFL_ERR_INVALID, "%s: frame %d is not 2-byte aligned", fn, i);
     HIPCHK(c, hipSetDevice(c->device));
@@ -1400,7 +1426,27 @@ static int upload_yuv(ffl_ctx *c, const char *fn, int first, int n, const uint8_
         s.wy = yw.y0;
         return s;
     };
-    return upload_staged(c, lk, first, n, fbytes, fp, direct, stage, send_direct, desc);
+    return upload_staged(c, lk, first, n, fbytes, fp, direct, stage, send_direct, desc, rp);
+}
+
+// Decoded 4:2:0 frames -> gray frame slots through k_frontend: the body of ffl_upload_frames_yuv (es = 1) and
+// ffl_upload_frames_yuv16 (es = 2 bytes per sample, reduced by rule Y5).  Frame by frame, as ffl_upload_frames_raw: only
+// the window the crop samples travels -- out of ffl_host_alloc memory one 2-D copy per plane (when every plane's rows
+// start 4-byte aligned and are a multiple of 4 bytes long: unaligned ones take a slow path in the runtime's copy),
+// otherwise copied into the pinned ring buffer and sent as one transfer.  On the device the window is packed: Y (w x h),
+// then U and V (w/2 x h/2 each, I420) or the interleaved UV rows (w x h/2, NV12), es bytes per sample.
+static int upload_yuv(ffl_ctx *c, const char *fn, int first, int n, const uint8_t *const *frames, int sw, int sh,
+                      ptrdiff_t stride_bytes, int layout, int es, int depth, int msb, int rw, int rh, int crop_x, int crop_y,
+                      const ffl_source_info *si) {
+    if (!c) return FFL_ERR_INVALID;
+    std::unique_lock<std::mutex> ul(c->up_mu);
+    CtxLock lk(c->mu);
+    if (int rc = check_frame_run(c, fn, first, n, frames, frames)) return rc;
+    FrontParams fp;
+    YuvWin yw;
+    if (int rc = yuv_window(c, fn, sw, sh, layout, stride_bytes, es, depth, si, rw, rh, crop_x, crop_y, c->w, c->h, &fp, &yw))
+        return rc;
+    return send_yuv(c, lk, fn, first, n, frames, sw, sh, stride_bytes, layout, es, depth, msb, fp, yw, nullptr);
 }
 
 int ffl_upload_frames_yuv(ffl_ctx *c, int first, int n, const uint8_t *const *frames, int sw, int sh, ptrdiff_t stride_bytes,
@@ -2234,11 +2280,8 @@ int ffl_download_flow(ffl_ctx *c, int slot, float *dst) {
 }
 
 // ---- device-memory I/O -------------------------------------------------------------------------
-// Every geometry rule of a device frame (ffl.h, ffl_dev_frame_check / ffl_dev_frame_check16); fn and frame index prefix the
-// message.  Fills the geometry of *p.  es: bytes per sample (2: the 16-bit 4:2:0 frames of rule Y5, whose depth is checked
-// here too).
-static int dev_frame_check(ffl_ctx *c, const char *fn, int idx, int fmt, int es, int depth, int sw, int sh, const ffl_dev_frame *f,
-                           const ffl_source_info *si, int rw, int rh, int cx, int cy, int ow, int oh, FrontParams *p) {
+// the rules of a device frame's format, sample size and depth (the map-driven call shares them and the plane rules)
+static int dev_format_rules(ffl_ctx *c, const char *fn, int idx, int fmt, int es, int depth, int sw, int sh, const ffl_dev_frame *f) {
     if (!f) return set_err(c, FFL_ERR_INVALID, "%s: frame %d: NULL descriptor", fn, idx);
     if (fmt < FFL_DEV_GRAY || fmt > FFL_DEV_NV12)
         return set_err(c, FFL_ERR_INVALID, "%s: unknown format %d (FFL_DEV_GRAY 0, BGR 1, RGB 2, I420 3, NV12 4)", fn, fmt);
@@ -2250,10 +2293,12 @@ static int dev_frame_check(ffl_ctx *c, const char *fn, int idx, int fmt, int es,
         return set_err(c, FFL_ERR_INVALID, "%s: depth %d outside 9..16 (8-bit frames go through ffl_upload_frames_device)", fn, depth);
     if (yuv && ((sw & 1) || (sh & 1)))
         return set_err(c, FFL_ERR_INVALID, "%s: 4:2:0 needs an even width and height, source is %dx%d", fn, sw, sh);
-    // the metadata, gray's two rules (in upright terms) and the crop; everything below is about the stored planes
-    if (int rc = front_geometry(c, fn, fmt == FFL_DEV_GRAY ? FRONT_GRAY : yuv ? FRONT_YUV : FRONT_BGR, sw, sh, si, rw, rh, cx, cy, ow,
-                                oh, p))
-        return rc;
+    return FFL_OK;
+}
+
+// the rules of the stored planes of a frame whose format passed dev_format_rules
+static int dev_plane_rules(ffl_ctx *c, const char *fn, int idx, int fmt, int es, int sw, int sh, const ffl_dev_frame *f) {
+    const bool yuv = fmt == FFL_DEV_I420 || fmt == FFL_DEV_NV12;
     const ptrdiff_t big = (ptrdiff_t)1 << 40;
     const ptrdiff_t p0 = f->pitch[0], ps = f->pixel_stride, cs = f->channel_stride;
     if (!f->plane[0] || (yuv && !f->plane[1]) || (fmt == FFL_DEV_I420 && !f->plane[2]))
@@ -2297,6 +2342,21 @@ static int dev_frame_check(ffl_ctx *c, const char *fn, int idx, int fmt, int es,
     return FFL_OK;
 }
 
+static int dev_front_class(int fmt) {  // what front_source / front_geometry call the format
+    return fmt == FFL_DEV_GRAY ? FRONT_GRAY : (fmt == FFL_DEV_I420 || fmt == FFL_DEV_NV12) ? FRONT_YUV : FRONT_BGR;
+}
+
+// Every geometry rule of a device frame (ffl.h, ffl_dev_frame_check / ffl_dev_frame_check16); fn and frame index prefix the
+// message.  Fills the geometry of *p.  es: bytes per sample (2: the 16-bit 4:2:0 frames of rule Y5, whose depth is checked
+// here too).
+static int dev_frame_check(ffl_ctx *c, const char *fn, int idx, int fmt, int es, int depth, int sw, int sh, const ffl_dev_frame *f,
+                           const ffl_source_info *si, int rw, int rh, int cx, int cy, int ow, int oh, FrontParams *p) {
+    if (int rc = dev_format_rules(c, fn, idx, fmt, es, depth, sw, sh, f)) return rc;
+    // the metadata, gray's two rules (in upright terms) and the crop; everything after it is about the stored planes
+    if (int rc = front_geometry(c, fn, dev_front_class(fmt), sw, sh, si, rw, rh, cx, cy, ow, oh, p)) return rc;
+    return dev_plane_rules(c, fn, idx, fmt, es, sw, sh, f);
+}
+
 // bytes of each plane a checked frame spans from plane[k] (0: unused)
 static void dev_frame_extents(int fmt, int es, int sw, int sh, const ffl_dev_frame *f, size_t ext[3]) {
     ext[0] = ext[1] = ext[2] = 0;
@@ -2318,6 +2378,7 @@ static void dev_frame_extents(int fmt, int es, int sw, int sh, const ffl_dev_fra
 // [p, p + bytes) must be device memory of the context's device inside one allocation
 static const char *kHostFrames = "host frames go through ffl_upload_frames, ffl_upload_frames_raw, ffl_upload_frames_yuv or "
                                  "ffl_upload_frames_yuv16";
+static const char *kHostFramesRemap = "host frames go through ffl_upload_frames_remap";
 static int dev_mem_check(ffl_ctx *c, const char *fn, const char *what, const void *p, size_t bytes,
                          const char *host_hint = kHostFrames) {
     hipPointerAttribute_t a;
@@ -2427,19 +2488,11 @@ int ffl_dev_frame_check16_src(int format, int depth, int sw, int sh, const ffl_d
     return dev_frame_check(nullptr, "ffl_dev_frame_check16", 0, format, 2, depth, sw, sh, f, si, rw, rh, cx, cy, out_w, out_h, &p);
 }
 
-// Device frames -> gray frame slots through ONE k_frontend_dev launch on stream `copy`, ordered after the caller's queued
-// work and before the caller's later work (the stream contract of ffl.h): the body of ffl_upload_frames_device (es = 1)
-// and ffl_upload_frames_device16 (es = 2 bytes per sample, reduced by rule Y5).  The descriptors travel in the pinned
-// table of the up_ring entry the call records (publish_frames), copied to the device table on the same stream.
-static int upload_device(ffl_ctx *c, const char *fn, int first, int n, const ffl_dev_frame *frames, int fmt, int es, int depth,
-                         int msb, int sw, int sh, int rw, int rh, int cx, int cy, uint64_t stream, const ffl_source_info *si) {
-    if (!c) return FFL_ERR_INVALID;
-    std::unique_lock<std::mutex> ul(c->up_mu);
-    CtxLock lk(c->mu);
-    if (int rc = check_frame_run(c, fn, first, n, frames)) return rc;
-    FrontParams p;
-    for (int i = 0; i < n; i++)
-        if (int rc = dev_frame_check(c, fn, i, fmt, es, depth, sw, sh, &frames[i], si, rw, rh, cx, cy, c->w, c->h, &p)) return rc;
+// What ffl_upload_frames_device(16) and ffl_upload_frames_device_remap share once every frame has passed its rules: the
+// stream contract, the memory checks, the descriptor table, the one launch (rp: k_frontend_remap_dev with that map) and the
+// publishing of the slots.
+static int send_device(ffl_ctx *c, const char *fn, int first, int n, const ffl_dev_frame *frames, int fmt, int es, int depth,
+                       int msb, int sw, int sh, uint64_t stream, FrontParams &p, const RemapParams *rp) {
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t cst;
     if (int rc = caller_stream(c, fn, stream, &cst)) return rc;
@@ -2449,7 +2502,7 @@ static int upload_device(ffl_ctx *c, const char *fn, int first, int n, const ffl
         dev_frame_extents(fmt, es, sw, sh, &frames[i], ext);
         for (int k = 0; k < 3; k++)
             if (ext[k])
-                if (int rc = dev_mem_check(c, fn, names[k], frames[i].plane[k], ext[k])) return rc;
+                if (int rc = dev_mem_check(c, fn, names[k], frames[i].plane[k], ext[k], rp ? kHostFramesRemap : kHostFrames)) return rc;
     }
     const size_t ring = c->up_ring.ev.size();
     if (!c->d_dtab) {
@@ -2493,13 +2546,30 @@ static int upload_device(ffl_ctx *c, const char *fn, int first, int n, const ffl
     HIPCHK(c, hipMemcpyAsync(c->d_dtab, T, sizeof(FrameDesc) * n, hipMemcpyHostToDevice, c->s_copy));
     {
         ProfScope ps(c, FFL_K_FRONTEND, c->s_copy);
-        ffl_launch_frontend_dev(c->d_dtab, n, c->d_gray, c->N, p, c->s_copy);
+        if (rp) ffl_launch_frontend_remap_dev(c->d_dtab, n, c->d_gray, c->N, p, *rp, c->s_copy);
+        else ffl_launch_frontend_dev(c->d_dtab, n, c->d_gray, c->N, p, c->s_copy);
     }
     HIPCHK(c, hipGetLastError());
     if (int rc = publish_frames(c, first, n)) return rc;
     // the caller's later work (overwriting the sources, the allocator reusing them) runs after the frames have been read
     HIPCHK(c, hipStreamWaitEvent(cst, ev_latest(c->up_ring).get(), 0));
     return FFL_OK;
+}
+
+// Device frames -> gray frame slots through ONE k_frontend_dev launch on stream `copy`, ordered after the caller's queued
+// work and before the caller's later work (the stream contract of ffl.h): the body of ffl_upload_frames_device (es = 1)
+// and ffl_upload_frames_device16 (es = 2 bytes per sample, reduced by rule Y5).  The descriptors travel in the pinned
+// table of the up_ring entry the call records (publish_frames), copied to the device table on the same stream.
+static int upload_device(ffl_ctx *c, const char *fn, int first, int n, const ffl_dev_frame *frames, int fmt, int es, int depth,
+                         int msb, int sw, int sh, int rw, int rh, int cx, int cy, uint64_t stream, const ffl_source_info *si) {
+    if (!c) return FFL_ERR_INVALID;
+    std::unique_lock<std::mutex> ul(c->up_mu);
+    CtxLock lk(c->mu);
+    if (int rc = check_frame_run(c, fn, first, n, frames)) return rc;
+    FrontParams p;
+    for (int i = 0; i < n; i++)
+        if (int rc = dev_frame_check(c, fn, i, fmt, es, depth, sw, sh, &frames[i], si, rw, rh, cx, cy, c->w, c->h, &p)) return rc;
+    return send_device(c, fn, first, n, frames, fmt, es, depth, msb, sw, sh, stream, p, nullptr);
 }
 
 int ffl_upload_frames_device(ffl_ctx *c, int first, int n, const ffl_dev_frame *frames, int fmt, int sw, int sh, int rw, int rh,
@@ -2522,6 +2592,218 @@ int ffl_upload_frames_device16_src(ffl_ctx *c, int first, int n, const ffl_dev_f
                                    int sw, int sh, int rw, int rh, int cx, int cy, uint64_t stream, const ffl_source_info *si) {
     return upload_device(c, "ffl_upload_frames_device16", first, n, frames, fmt, 2, depth, msb_aligned != 0, sw, sh, rw, rh, cx, cy,
                          stream, si);
+}
+
+// ---- map-driven reprojection --------------------------------------------------------
+static int remap_log2(int ss) { return ss == 1 ? 0 : ss == 2 ? 1 : ss == 4 ? 2 : -1; }
+
+// Rule R1 for a map of an upright uw x uh source, and the upright bounding box of its taps (rule R6's first half).
+static int remap_scan(ffl_ctx *c, const char *fn, const int32_t *map, int ow, int oh, int ss, int uw, int uh, int ux[2], int uy[2],
+                      size_t *valid) {
+    if (!map) return set_err(c, FFL_ERR_INVALID, "%s: NULL map", fn);
+    if (remap_log2(ss) < 0) return set_err(c, FFL_ERR_INVALID, "%s: supersample %d is not one of 1, 2, 4", fn, ss);
+    if (ow < 1 || oh < 1 || ow > 32768 || oh > 32768 || uw < 1 || uh < 1 || uw > 32768 || uh > 32768)
+        return set_err(c, FFL_ERR_INVALID, "%s: unsupported output %dx%d / source %dx%d", fn, ow, oh, uw, uh);
+    const size_t W = (size_t)ss * ow, H = (size_t)ss * oh;
+    const int qxmax = 32 * (uw - 1), qymax = 32 * (uh - 1);
+    int x0 = INT32_MAX, x1 = -1, y0 = INT32_MAX, y1 = -1;
+    size_t nv = 0;
+    for (size_t k = 0; k < W * H; k++) {
+        const int qx = map[2 * k], qy = map[2 * k + 1];
+        if (qx == FFL_REMAP_NO_SOURCE) continue;
+        if (qx < 0 || qx > qxmax || qy < 0 || qy > qymax)
+            return set_err(c, FFL_ERR_INVALID, "%s: map entry %zu (sample row %zu, column %zu) is (%d, %d), outside 0..%d x 0..%d "
+                                               "(1/32 px of the upright %dx%d source; rule R1)", fn, k, k / W, k % W, qx, qy, qxmax,
+                           qymax, uw, uh);
+        x0 = std::min(x0, qx); x1 = std::max(x1, qx);
+        y0 = std::min(y0, qy); y1 = std::max(y1, qy);
+        nv++;
+    }
+    if (!nv) return set_err(c, FFL_ERR_INVALID, "%s: the map has no valid entry (every sample is FFL_REMAP_NO_SOURCE; rule R1)", fn);
+    ux[0] = x0 >> 5; ux[1] = std::min((x1 >> 5) + 1, uw - 1);   // rule R2: the second tap is loaded whatever its weight
+    uy[0] = y0 >> 5; uy[1] = std::min((y1 >> 5) + 1, uh - 1);
+    if (valid) *valid = nv;
+    return FFL_OK;
+}
+
+int ffl_remap_check(const int32_t *map, int ow, int oh, int ss, int sw, int sh, const ffl_source_info *si, int win_upright[4],
+                    int win_stored[4], size_t *valid) {
+    static const char *fn = "ffl_remap_check";
+    FrontParams p;
+    if (sw < 1 || sh < 1 || sw > 32768 || sh > 32768)
+        return set_err(nullptr, FFL_ERR_INVALID, "%s: unsupported source %dx%d", fn, sw, sh);
+    if (int rc = front_source(nullptr, fn, FRONT_YUV, sw, sh, si, &p)) return rc;  // full_range: the format is not known here
+    int ux[2], uy[2];
+    if (int rc = remap_scan(nullptr, fn, map, ow, oh, ss, p.sw, p.sh, ux, uy, valid)) return rc;
+    if (win_upright) {
+        win_upright[0] = ux[0]; win_upright[1] = uy[0]; win_upright[2] = ux[1] - ux[0] + 1; win_upright[3] = uy[1] - uy[0] + 1;
+    }
+    if (win_stored) {
+        YuvWin yw;
+        yuv_stored_window(p, sw, sh, ux, uy, &yw);
+        win_stored[0] = yw.x0; win_stored[1] = yw.y0; win_stored[2] = yw.w; win_stored[3] = yw.h;
+    }
+    return FFL_OK;
+}
+
+int ffl_remap_bytes(int ow, int oh, int ss, size_t *bytes) {
+    if (remap_log2(ss) < 0 || ow < 1 || oh < 1 || ow > 32768 || oh > 32768 || !bytes)
+        return set_err(nullptr, FFL_ERR_INVALID, "ffl_remap_bytes: bad arguments (supersample is one of 1, 2, 4)");
+    *bytes = (size_t)8 * ss * ss * ow * oh;
+    return FFL_OK;
+}
+
+// Nothing of a create but the table entry needs the context's locks: the scan (rule R1) and the copy to the device run
+// without them, so that a large map does not hold up the other entry points.  A failure there is worded into the calling
+// thread's buffer and becomes the context's message under the lock.
+static int remap_fail(ffl_ctx *c, int rc) {
+    const std::string msg = g_create_error;
+    CtxLock lk(c->mu);
+    return set_err(c, rc, "%s", msg.c_str());
+}
+static int remap_free_entry(const ffl_ctx *c) {
+    int k = 0;
+    while (k < FFL_MAX_REMAPS && c->remaps[k].d) k++;
+    return k;
+}
+
+int ffl_remap_create(ffl_ctx *c, const int32_t *map, int ss, int sw, int sh, int *id) {
+    static const char *fn = "ffl_remap_create";
+    static const char *full = "%s: %d maps are alive already (FFL_MAX_REMAPS); destroy one first";
+    if (!c) return FFL_ERR_INVALID;
+    if (!id) return remap_fail(c, set_err(nullptr, FFL_ERR_INVALID, "%s: NULL id", fn));
+    int ux[2], uy[2];
+    if (int rc = remap_scan(nullptr, fn, map, c->w, c->h, ss, sw, sh, ux, uy, nullptr)) return remap_fail(c, rc);  // w, h never change
+    {
+        CtxLock lk(c->mu);  // a ninth map is refused before any device work
+        if (remap_free_entry(c) == FFL_MAX_REMAPS) return set_err(c, FFL_ERR_INVALID, full, fn, FFL_MAX_REMAPS);
+    }
+    const size_t count = (size_t)ss * ss * c->N;
+    DevBuf<int2> d;
+    hipError_t e = hipSetDevice(c->device);
+    if (e == hipSuccess) e = d.alloc(count);
+    if (e == hipSuccess) e = hipMemcpy(d, map, count * sizeof(int2), hipMemcpyHostToDevice);  // resident once this returns
+    if (e != hipSuccess)
+        return remap_fail(c, set_err(nullptr, FFL_ERR_HIP, "%s: copying the map to the device failed: %s", fn, hipGetErrorString(e)));
+    std::unique_lock<std::mutex> ul(c->up_mu);
+    CtxLock lk(c->mu);
+    const int k = remap_free_entry(c);
+    if (k == FFL_MAX_REMAPS) return set_err(c, FFL_ERR_INVALID, full, fn, FFL_MAX_REMAPS);  // another thread took the last entry
+    ffl_ctx::Remap &m = c->remaps[k];
+    m.d = std::move(d);
+    m.ss = ss; m.sw = sw; m.sh = sh;
+    m.ux[0] = ux[0]; m.ux[1] = ux[1]; m.uy[0] = uy[0]; m.uy[1] = uy[1];
+    m.last = EvRef();
+    *id = k;
+    return FFL_OK;
+}
+
+// The end of an upload call that named map `id`: the event ffl_remap_destroy waits for.  A call that succeeded has just
+// recorded it (publish_frames).  One that failed part-way may have queued launches that read the map and published
+// nothing, so an event of its own is recorded behind them on stream `copy`; if even that fails the stream is drained.
+static void remap_used(ffl_ctx *c, int id, int rc) {
+    if (!c->remaps[id].d) return;
+    if (rc == FFL_OK) {
+        c->remaps[id].last = ev_latest(c->up_ring);
+        return;
+    }
+    EvRef ev;
+    if (c->up_ring.record(c->s_copy, &ev) == hipSuccess) c->remaps[id].last = ev;
+    else (void)hipStreamSynchronize(c->s_copy);
+}
+
+// the map an upload call names, checked against the call's upright source size (fp->sw x fp->sh)
+static int remap_open(ffl_ctx *c, const char *fn, int id, const FrontParams &fp, ffl_ctx::Remap **m, RemapParams *rp) {
+    if (id < 0 || id >= FFL_MAX_REMAPS || !c->remaps[id].d)
+        return set_err(c, FFL_ERR_INVALID, "%s: remap id %d names no map (never created, or destroyed)", fn, id);
+    *m = &c->remaps[id];
+    if ((*m)->sw != fp.sw || (*m)->sh != fp.sh)
+        return set_err(c, FFL_ERR_INVALID, "%s: the upright source is %dx%d, map %d was created for %dx%d", fn, fp.sw, fp.sh, id,
+                       (*m)->sw, (*m)->sh);
+    rp->map = (*m)->d;
+    rp->ss = (*m)->ss;
+    rp->lg = remap_log2((*m)->ss);
+    return FFL_OK;
+}
+
+int ffl_remap_destroy(ffl_ctx *c, int id) {
+    static const char *fn = "ffl_remap_destroy";
+    if (!c) return FFL_ERR_INVALID;
+    std::unique_lock<std::mutex> ul(c->up_mu);  // no upload call can start using the map meanwhile
+    CtxLock lk(c->mu);
+    if (id < 0 || id >= FFL_MAX_REMAPS || !c->remaps[id].d)
+        return set_err(c, FFL_ERR_INVALID, "%s: remap id %d names no map (never created, or destroyed)", fn, id);
+    hipEvent_t ev = c->remaps[id].last.get();  // the last launch that reads it; nullptr: long over
+    if (int rc = wait_unlocked(c, lk, &ev, 1)) return rc;
+    HIPCHK(c, c->remaps[id].d.reset());
+    c->remaps[id] = ffl_ctx::Remap();
+    return FFL_OK;
+}
+
+int ffl_upload_frames_remap(ffl_ctx *c, int first, int n, const uint8_t *const *frames, int fmt, int sw, int sh,
+                            ptrdiff_t stride_bytes, int depth, int msb, int id, const ffl_source_info *si) {
+    static const char *fn = "ffl_upload_frames_remap";
+    if (!c) return FFL_ERR_INVALID;
+    std::unique_lock<std::mutex> ul(c->up_mu);
+    CtxLock lk(c->mu);
+    if (int rc = check_frame_run(c, fn, first, n, frames, frames)) return rc;
+    if (fmt < FFL_DEV_BGR || fmt > FFL_DEV_NV12)
+        return set_err(c, FFL_ERR_INVALID, "%s: format %d is not one of FFL_DEV_BGR 1, RGB 2, I420 3, NV12 4 (host gray frames have "
+                                           "no map path)", fn, fmt);
+    const bool yuv = fmt == FFL_DEV_I420 || fmt == FFL_DEV_NV12;
+    if (depth != 8 && !yuv)
+        return set_err(c, FFL_ERR_INVALID, "%s: depth %d: 3-channel frames are 8-bit (9..16 describe 4:2:0 frames)", fn, depth);
+    // both depths are this call's own: refused here, so that the depth texts of the shared rules below, which send a caller
+    // to the 8-bit entry points, are never reached from it
+    if (yuv && depth != 8 && (depth < 9 || depth > 16))
+        return set_err(c, FFL_ERR_INVALID, "%s: depth %d is neither 8 nor 9..16", fn, depth);
+    if (sw < 1 || sh < 1 || sw > 32768 || sh > 32768) return set_err(c, FFL_ERR_INVALID, "%s: unsupported source %dx%d", fn, sw, sh);
+    const int es = depth == 8 ? 1 : 2, layout = fmt == FFL_DEV_NV12 ? FFL_YUV_NV12 : FFL_YUV_I420;
+    if (yuv)
+        if (int rc = yuv_layout_rules(c, fn, sw, sh, layout, stride_bytes, es, depth)) return rc;
+    FrontParams fp = {};
+    if (int rc = front_source(c, fn, yuv ? FRONT_YUV : FRONT_BGR, sw, sh, si, &fp)) return rc;
+    fp.ow = c->w; fp.oh = c->h;
+    ffl_ctx::Remap *m;
+    RemapParams rp;
+    if (int rc = remap_open(c, fn, id, fp, &m, &rp)) return rc;
+    int rc;
+    if (yuv) {
+        YuvWin yw;  // rule R6
+        yuv_stored_window(fp, sw, sh, m->ux, m->uy, &yw);
+        rc = send_yuv(c, lk, fn, first, n, frames, sw, sh, stride_bytes, layout, es, depth, msb != 0, fp, yw, &rp);
+    } else {
+        rc = send_raw(c, lk, fn, first, n, frames, sw, sh, stride_bytes, fmt == FFL_DEV_RGB, fp, &rp);
+    }
+    remap_used(c, id, rc);
+    return rc;
+}
+
+int ffl_upload_frames_device_remap(ffl_ctx *c, int first, int n, const ffl_dev_frame *frames, int fmt, int depth, int msb, int sw,
+                                   int sh, int id, uint64_t stream, const ffl_source_info *si) {
+    static const char *fn = "ffl_upload_frames_device_remap";
+    if (!c) return FFL_ERR_INVALID;
+    std::unique_lock<std::mutex> ul(c->up_mu);
+    CtxLock lk(c->mu);
+    if (int rc = check_frame_run(c, fn, first, n, frames)) return rc;
+    // as in ffl_upload_frames_remap: the shared rules' depth texts name other entry points and are never reached from here
+    if (depth != 8 && (depth < 9 || depth > 16)) return set_err(c, FFL_ERR_INVALID, "%s: depth %d is neither 8 nor 9..16", fn, depth);
+    if (sw < 1 || sh < 1 || sw > 32768 || sh > 32768) return set_err(c, FFL_ERR_INVALID, "%s: unsupported source %dx%d", fn, sw, sh);
+    const int es = depth == 8 ? 1 : 2;
+    FrontParams p = {};
+    for (int i = 0; i < n; i++) {
+        if (int rc = dev_format_rules(c, fn, i, fmt, es, depth, sw, sh, &frames[i])) return rc;
+        if (i == 0)
+            if (int rc = front_source(c, fn, dev_front_class(fmt), sw, sh, si, &p)) return rc;
+        if (int rc = dev_plane_rules(c, fn, i, fmt, es, sw, sh, &frames[i])) return rc;
+    }
+    p.ow = c->w; p.oh = c->h;
+    ffl_ctx::Remap *m;
+    RemapParams rp;
+    if (int rc = remap_open(c, fn, id, p, &m, &rp)) return rc;
+    const int rc = send_device(c, fn, first, n, frames, fmt, es, depth, msb != 0, sw, sh, stream, p, &rp);
+    remap_used(c, id, rc);
+    return rc;
 }
 
 // Flow slots -> caller device memory on stream `post`, ordered after the batches that produced them and the caller's

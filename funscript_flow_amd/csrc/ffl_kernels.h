@@ -87,6 +87,13 @@ struct FrontParams {  // what the frames of one launch share
     int ax, bx, cx0, ay, by, cy0;  // rule Y6: upright (x, y) is stored (ax x + bx y + cx0, ay x + by y + cy0)
     int full;                    // rule Y7: full-range 4:2:0
 };
+// k_frontend_remap, k_frontend_remap_dev: what a map-driven launch carries beside FrontParams, of
+// which it reads only the source description -- nothing here is seen by the resize kernels.
+#define FFL_REMAP_NONE (-2147483647 - 1)  // qx of a sample without a source (rule R1; FFL_REMAP_NO_SOURCE of include/ffl.h)
+struct RemapParams {
+    const int2 *map;  // [ss * oh][ss * ow] entries (qx, qy): upright source coordinates in 1/32 px
+    int ss, lg;       // supersampling per axis (1, 2, 4) and its log2
+};
 // k_export_flows: the flow slots of one launch (at most FFL_MAXB) travel as a kernel argument
 struct ExportTab {
     int slot[FFL_MAXB];
@@ -188,6 +195,9 @@ void ffl_launch_polyexp_multi(const PolyJob *levels, int n, int nU, PolyConsts p
 // host paths: one frame, its descriptor a kernel argument; device path: n frames, descriptors tab[0..n) in device memory
 void ffl_launch_frontend(const FrameDesc &d, uint8_t *gray, const FrontParams &p, hipStream_t st);
 void ffl_launch_frontend_dev(const FrameDesc *tab, int n, uint8_t *gray_base, size_t N, const FrontParams &p, hipStream_t st);
+void ffl_launch_frontend_remap(const FrameDesc &d, uint8_t *gray, const FrontParams &p, const RemapParams &r, hipStream_t st);
+void ffl_launch_frontend_remap_dev(const FrameDesc *tab, int n, uint8_t *gray_base, size_t N, const FrontParams &p,
+                                   const RemapParams &r, hipStream_t st);
 // n (<= FFL_MAXB) flow slots of `flow` (2N floats each) -> dst + i * item_stride bytes; layout 0 (H, W, 2), 1 (2, H, W)
 void ffl_launch_export_flows(const float *flow, const ExportTab &tab, int n, size_t N, char *dst, long long item_stride,
                              int layout, hipStream_t st);

@@ -12,6 +12,8 @@
 // the one per-pixel body; they differ only in where the descriptor comes from:
 //   k_frontend      ffl_upload_frames_raw / ffl_upload_frames_yuv / _yuv16: one frame in a staging buffer, descriptor by value
 //   k_frontend_dev  ffl_upload_frames_device / _device16: one launch for n frames in caller memory, descriptor tab[blockIdx.z]
+// k_frontend_remap / k_frontend_remap_dev are the same pair for ffl_upload_frames_remap / _device_remap: the operand is
+// gathered through a per-pixel source map instead of the resize + crop (a pinhole view, an undistortion; section 20).
 // Roofline: HBM / PCIe -- the kernel touches at most 12 source bytes per output pixel; on the host paths the frame's
 // H2D transfer is what bounds the path.
 #include "ffl_kernels.h"
@@ -156,6 +158,82 @@ __global__ __launch_bounds__(256) void k_frontend_dev(const FrameDesc *__restric
     }
 }
 
+// Map-driven reprojection (rules R2 to R5 are stated in include/ffl.h): output pixel
+// (x, y) is the rounded mean of its ss x ss samples, each a bilinear blend (5 fractional bits, 10-bit weight products) of the
+// four taps a map entry names in upright 1/32 px -- the taps are ffl_front_fetch's, so rules Y5, Y6 and Y7 apply where a tap
+// is loaded and the map never sees how a frame is stored.  The map was checked on the host (rule R1): no tap is
+// range-checked here.  An entry is one 8-byte load; the lanes of a wave read consecutive entries of a sample row (ss = 1)
+// or entries ss apart.  Nothing the resize kernels read was added for this: the map and ss travel in RemapParams, and of
+// FrontParams only the source description (kind, rgb, sw, sh, ow, oh, rules Y5 to Y7) is used.  Gray sources have one channel,
+// stored as it is.
+template <int K, bool S>
+__device__ __forceinline__ void ffl_front_remap(const FrameDesc &d, const FrontParams &p, const RemapParams &r, uint8_t *gray,
+                                                int x, int y) {
+    const int kind = K == FFL_SRC_ANY ? p.kind : K;
+    const int NC = 3;
+    int acc[NC] = {0, 0, 0};
+    const size_t W = (size_t)r.ss * p.ow;
+    const int2 *row = r.map + (size_t)y * r.ss * W + (size_t)x * r.ss;
+    for (int j = 0; j < r.ss; j++, row += W) {
+        for (int i = 0; i < r.ss; i++) {
+            const int2 q = row[i];
+            if (q.x == FFL_REMAP_NONE) continue;  // rule R4: no source, 0 in every channel
+            const int x0 = q.x >> 5, fx = q.x & 31, x1 = min(x0 + 1, p.sw - 1);
+            const int y0 = q.y >> 5, fy = q.y & 31, y1 = min(y0 + 1, p.sh - 1);
+            const int w00 = (32 - fx) * (32 - fy), w01 = fx * (32 - fy), w10 = (32 - fx) * fy, w11 = fx * fy;
+            if (kind == FFL_SRC_GRAY) {
+                int tx[4] = {x0, x1, x0, x1}, ty[4] = {y0, y0, y1, y1}, s[4];
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    ffl_front_map<S>(p, tx[k], ty[k]);
+                    s[k] = d.p0[(long long)ty[k] * d.pitch0 + (long long)tx[k] * d.ps];
+                }
+                acc[0] += (s[0] * w00 + s[1] * w01 + s[2] * w10 + s[3] * w11 + 512) >> 10;
+            } else {
+                int s00[3], s01[3], s10[3], s11[3];
+                ffl_front_fetch<K, S>(d, p, x0, y0, s00);
+                ffl_front_fetch<K, S>(d, p, x1, y0, s01);
+                ffl_front_fetch<K, S>(d, p, x0, y1, s10);
+                ffl_front_fetch<K, S>(d, p, x1, y1, s11);
+#pragma unroll
+                for (int c = 0; c < NC; c++) acc[c] += (s00[c] * w00 + s01[c] * w01 + s10[c] * w10 + s11[c] * w11 + 512) >> 10;
+            }
+        }
+    }
+    const int half = (r.ss * r.ss) >> 1, sh = 2 * r.lg;  // rule R5
+    int v[NC];
+#pragma unroll
+    for (int c = 0; c < NC; c++) v[c] = (acc[c] + half) >> sh;
+    if (kind == FFL_SRC_GRAY) {
+        gray[(size_t)y * p.ow + x] = (uint8_t)v[0];
+        return;
+    }
+    const int rr = p.rgb ? v[0] : v[2], b = p.rgb ? v[2] : v[0];
+    gray[(size_t)y * p.ow + x] = (uint8_t)((rr * 9798 + v[1] * 19235 + b * 3735 + 16384) >> 15);
+}
+
+// The two entry points mirror k_frontend / k_frontend_dev: the same 64x4 workgroups, one output pixel per lane, the
+// descriptor by value (host frames, a body per kind without metadata) or tab[blockIdx.z] (device frames, the kind tested in
+// each fetch).
+template <bool S>
+__global__ __launch_bounds__(256) void k_frontend_remap(FrameDesc d, uint8_t *__restrict__ gray, FrontParams p, RemapParams r) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= p.ow || y >= p.oh) return;
+    if (S) ffl_front_remap<FFL_SRC_ANY, true>(d, p, r, gray, x, y);
+    else if (p.kind == FFL_SRC_YUV) ffl_front_remap<FFL_SRC_YUV, false>(d, p, r, gray, x, y);
+    else if (p.kind == FFL_SRC_YUV16) ffl_front_remap<FFL_SRC_YUV16, false>(d, p, r, gray, x, y);
+    else ffl_front_remap<FFL_SRC_BGR, false>(d, p, r, gray, x, y);
+}
+
+template <bool S>
+__global__ __launch_bounds__(256) void k_frontend_remap_dev(const FrameDesc *__restrict__ tab, uint8_t *__restrict__ gray_base,
+                                                            size_t N, FrontParams p, RemapParams r) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= p.ow || y >= p.oh) return;
+    const FrameDesc d = tab[blockIdx.z];
+    ffl_front_remap<FFL_SRC_ANY, S>(d, p, r, gray_base + (size_t)d.fslot * N, x, y);
+}
+
 void ffl_launch_frontend(const FrameDesc &d, uint8_t *gray, const FrontParams &p, hipStream_t st) {
     dim3 grid((p.ow + 63) / 64, (p.oh + 3) / 4);
     if (p.src) hipLaunchKernelGGL(k_frontend<true>, grid, dim3(256), 0, st, d, gray, p);
@@ -166,4 +244,17 @@ void ffl_launch_frontend_dev(const FrameDesc *tab, int n, uint8_t *gray_base, si
     dim3 grid((p.ow + 63) / 64, (p.oh + 3) / 4, n);
     if (p.src) hipLaunchKernelGGL(k_frontend_dev<true>, grid, dim3(256), 0, st, tab, gray_base, N, p);
     else hipLaunchKernelGGL(k_frontend_dev<false>, grid, dim3(256), 0, st, tab, gray_base, N, p);
+}
+
+void ffl_launch_frontend_remap(const FrameDesc &d, uint8_t *gray, const FrontParams &p, const RemapParams &r, hipStream_t st) {
+    dim3 grid((p.ow + 63) / 64, (p.oh + 3) / 4);
+    if (p.src) hipLaunchKernelGGL(k_frontend_remap<true>, grid, dim3(256), 0, st, d, gray, p, r);
+    else hipLaunchKernelGGL(k_frontend_remap<false>, grid, dim3(256), 0, st, d, gray, p, r);
+}
+
+void ffl_launch_frontend_remap_dev(const FrameDesc *tab, int n, uint8_t *gray_base, size_t N, const FrontParams &p,
+                                   const RemapParams &r, hipStream_t st) {
+    dim3 grid((p.ow + 63) / 64, (p.oh + 3) / 4, n);
+    if (p.src) hipLaunchKernelGGL(k_frontend_remap_dev<true>, grid, dim3(256), 0, st, tab, gray_base, N, p, r);
+    else hipLaunchKernelGGL(k_frontend_remap_dev<false>, grid, dim3(256), 0, st, tab, gray_base, N, p, r);
 }

@@ -219,6 +219,43 @@ def yuv_params(params):
     return params.get("hip_yuv"), deep
 
 
+VIEW_KEYS = ("projection", "fov", "yaw", "pitch", "roll", "stereo", "eye", "src_hfov", "src_vfov", "supersample")
+
+
+def view_remap(ctx, capture, params):
+    """params["hip_view"] -> the keyword of frontend.DecodedUploader that carries it ({} without the key, so that nothing
+    changes): a dict with "projection" ("equirect" | "fisheye") and "fov" (degrees) and, optionally, "yaw", "pitch", "roll",
+    "stereo" (None | "sbs" | "tb"), "eye" ("left" | "right"), "src_hfov", "src_vfov", "supersample" -- the pinhole view of
+    frontend.view_map into one eye of the stream.  The map is built once, for the capture's stored
+    size turned upright by params["hip_rotate"], and made resident in `ctx`, which is the caller's: whoever calls this
+    destroys the map once the video is done (drop_remap), or a context reused over many videos runs out of maps.  Refused
+    together with params["vr_mode"], which answers the same question by a crop (FF:1076-1079).  The values are the
+    caller's: none is tuned on footage."""
+    view = params.get("hip_view")
+    if view is None:
+        return {}
+    from . import frontend
+    if params.get("vr_mode"):
+        raise ValueError("params[\"hip_view\"] and params[\"vr_mode\"] are two answers to one question: the view replaces the "
+                         "reference's resize and quadrant crop (FF:1076-1079) -- set one of them")
+    unknown = sorted(set(view) - set(VIEW_KEYS))
+    if unknown or "projection" not in view or "fov" not in view:
+        raise ValueError(f"params[\"hip_view\"] needs \"projection\" and \"fov\" and knows {VIEW_KEYS}; got {sorted(view)}")
+    w, h = int(capture.get(CAP_PROP_FRAME_WIDTH)), int(capture.get(CAP_PROP_FRAME_HEIGHT))
+    src = (h, w) if int(params.get("hip_rotate") or 0) in (90, 270) else (w, h)   # the map is in upright terms
+    S = int(view.get("supersample", 1))
+    kw = {k: view[k] for k in ("yaw", "pitch", "roll", "src_hfov", "src_vfov") if view.get(k) is not None}
+    m = frontend.view_map(src, (ctx.width, ctx.height), view["projection"], view["fov"], supersample=S,
+                          rect=frontend.eye_rect(src, view.get("stereo"), view.get("eye", "left")), **kw)
+    return {"remap": ctx.remap_create(m, src, S)}
+
+
+def drop_remap(ctx, view):
+    """frees the map view_remap created (`view`: what it returned); safe straight after the last upload that used it"""
+    if view.get("remap") is not None:
+        ctx.remap_destroy(view["remap"])
+
+
 def ring_depth(deep):
     """the depth keyword of PrefetchRing out of yuv_params' keywords: only when the frames are not uint8"""
     return {"depth": deep["depth"]} if deep.get("depth", 8) != 8 else {}
@@ -234,22 +271,29 @@ def video_to_actions(ctx, capture, params, engine=None, ring_frames=None):
     # params["hip_yuv"] = "i420" | "nv12": the capture yields 4:2:0 frames; a caller's engine must
     # then have been built with frontend.DecodedUploader(ctx, yuv=...).  params["hip_yuv_depth"] = 9..16 and the optional
     # params["hip_yuv_msb"]: those frames are uint16 (rule Y5)
+    # params["hip_view"]: a pinhole view through a source map instead of resize + crop (view_remap); a caller's engine is
+    # left as it is
     yuv, deep = yuv_params(params)
-    engine = engine or pipeline.PairEngine(ctx, frontend.DecodedUploader(ctx, bool(params.get("vr_mode")), False, yuv=yuv, **deep))
+    view = view_remap(ctx, capture, params) if engine is None else {}   # this call's own map: freed below
+    engine = engine or pipeline.PairEngine(ctx, frontend.DecodedUploader(ctx, bool(params.get("vr_mode")), False, yuv=yuv, **deep,
+                                                                         **view))
     # params["hip_flow"] / ["hip_dis"] pick the flow algorithm for this call (a caller's engine is left as it is)
     algo = _capi.flow_choice(params) if ("hip_flow" in params or "hip_dis" in params) else None
     fbk = pipeline.farneback_kwargs(params, ctx.width, ctx.height)   # params["hip_farneback"], ["hip_farneback_window"]: this call's
-    ring = PrefetchRing(ctx, capture, indices, bracket, ring_frames or 4 * ctx.max_batch + 2, yuv=yuv, **ring_depth(deep))
     dots, cuts, frame_idx = [], [], []
+    ring = None
     try:
-        for view, fidx in ring.chunks():
+        ring = PrefetchRing(ctx, capture, indices, bracket, ring_frames or 4 * ctx.max_batch + 2, yuv=yuv, **ring_depth(deep))
+        for chunk, fidx in ring.chunks():
             # params["hip_pass2"] = "device": the chunk's window, cut test and pass 2 on the device, one read per chunk
-            d, recs = pipeline._chunk_scalars(engine, view, params, **({"algo": algo} if algo is not None else {}), **fbk)
+            d, recs = pipeline._chunk_scalars(engine, chunk, params, **({"algo": algo} if algo is not None else {}), **fbk)
             dots += [float(v) for v in d]
             cuts += [bool(r[4]) for r in recs]
             frame_idx += fidx
     finally:
-        ring.close()
+        if ring is not None:
+            ring.close()
+        drop_remap(ctx, view)
     return postchain.actions_from_scalars(dots, cuts, frame_idx, fps, params)
 
 
@@ -290,11 +334,13 @@ def process_video(video_path, params, log_func, open_capture, make_context, prog
     log_func("Using backend: HIP")
     error_occurred = False
     ctx = ring = None
+    own = {}   # the map this call creates in the caller's context (view_remap)
     try:
         ctx = make_context(cap)
         flow, dis = _capi.flow_choice(params)
         yuv, deep = yuv_params(params)   # "i420" | "nv12": open_capture's read() yields (3h/2, w) 4:2:0 frames
-        engine = pipeline.PairEngine(ctx, frontend.DecodedUploader(ctx, bool(params.get("vr_mode")), False, yuv=yuv, **deep),
+        own = view_remap(ctx, cap, params)   # this video's map: freed below
+        engine = pipeline.PairEngine(ctx, frontend.DecodedUploader(ctx, bool(params.get("vr_mode")), False, yuv=yuv, **deep, **own),
                                      flow=flow, dis=dis, farneback=_capi.farneback_choice(params),
                                      window=_capi.farneback_mode(params))
         ring = PrefetchRing(ctx, cap, indices, int(params.get("batch_size", 3000.0)), 4 * ctx.max_batch + 2, yuv=yuv,
@@ -321,6 +367,11 @@ def process_video(video_path, params, log_func, open_capture, make_context, prog
     finally:
         if ring is not None:
             ring.close()
+        try:
+            drop_remap(ctx, own)
+        except Exception as e:  # noqa: BLE001
+            log_func(f"ERROR: {e}")
+            error_occurred = True
         if hasattr(cap, "release"):
             cap.release()
     log_func(f"Processing time: {time.time() - start:.2f} seconds")

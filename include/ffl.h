@@ -47,6 +47,11 @@
  *   ffl_download_flow       the "flow" entry of that dict (tests / callers that want the array)
  *   ffl_upload_frames_device  ffl_upload_frames_raw / _yuv / ffl_upload_frames for frames already in device memory (a GPU
  *                           decoder's surfaces, torch tensors); ffl_export_flows: ffl_download_flow into device memory
+ *   ffl_remap_create, ffl_upload_frames_remap, ffl_upload_frames_device_remap  replace nothing: the reference's VR mode is a
+ *                           resize of the whole side-by-side frame and a crop, FF:1076-1079, which leaves the operand
+ *                           equirectangular.  These form it through a per-pixel source map instead -- a pinhole view of one
+ *                           eye, an undistortion; ffl_remap_check, ffl_remap_bytes and
+ *                           ffl_remap_destroy belong to them
  *   ffl_import_flows        ffl_upload_flow for n fields already in device memory (float32, float16 or bfloat16, any
  *                           strides): the reductions of FF:884-894 on a flow the caller computed
  *   ffl_submit_pair         precompute_wrapper((p0, p1), params)                    FF:1019-1021
@@ -324,6 +329,73 @@ int ffl_upload_frames_device_src(ffl_ctx *ctx, int first_slot, int n, const ffl_
 int ffl_upload_frames_device16_src(ffl_ctx *ctx, int first_slot, int n, const ffl_dev_frame *frames, int format, int depth,
                                    int msb_aligned, int src_w, int src_h, int resize_w, int resize_h, int crop_x, int crop_y,
                                    uint64_t stream, const ffl_source_info *src);
+
+/* ---- Map-driven reprojection -------------------------------------------------------
+ * Every path above has one geometry: resize, an axis-aligned crop, luma.  The reference's VR mode is that too -- the whole
+ * side-by-side equirectangular frame resized to 512 x 512 and a quadrant kept (FF:1076-1079) -- and everything behind the
+ * operand assumes a rectilinear image, which a quadrant of an equirect or fisheye frame is not.  A per-output-pixel source
+ * map, built once per stream on the host (frontend.view_map: a pinhole view of one eye; as well lens undistortion, a
+ * rotation by any angle, an ROI zoom), is applied by a gather kernel where the operand is formed.  Nothing in the reference
+ * does this: the rules are the library's own, in the fixed-point form of cv2.remap (5 fractional bits); parity with cv2 is
+ * unpinned.
+ *
+ * A map serves a context of ow x oh with supersampling S in {1, 2, 4}: an (S*oh, S*ow, 2) array of int32 (qx, qy), upright
+ * source coordinates in 1/32 px of an upright src_w x src_h source.
+ *   R1  validity: qx == FFL_REMAP_NO_SOURCE marks a sample with no source (its qy is ignored).  Every other entry must
+ *       satisfy 0 <= qx <= 32 * (src_w - 1) and 0 <= qy <= 32 * (src_h - 1).  Creation refuses a map with any other entry
+ *       and names the first offender; it also refuses a map with no valid entry.  The kernel never range-checks.
+ *   R2  taps: x0 = qx >> 5, fx = qx & 31, x1 = min(x0 + 1, src_w - 1); the same in y.
+ *   R3  sample, per channel: r = (s00 (32-fx)(32-fy) + s01 fx (32-fy) + s10 (32-fx) fy + s11 fx fy + 512) >> 10.  The
+ *       channels of a tap are those the resize paths fetch: BGR and RGB as stored; 4:2:0 converted per tap by appendix Y (by
+ *       Y7 under full_range), after Y5's reduction of 16-bit samples; gray has one channel.  Rule Y6 (rotation, mirror)
+ *       applies at the fetch: the map is in upright terms.
+ *   R4  a sample with no source is 0 in every channel.
+ *   R5  pixel: the channel value is (sum of the pixel's S*S samples + S*S/2) >> (2 log2 S); luma is then the 15-bit
+ *       expression of every other path; a gray source stores the channel as it is.
+ *   R6  window: the bounding box of all taps of valid entries (upright), mapped through Y6 and rounded out as the 4:2:0
+ *       window is everywhere (columns to 16, rows to 2, clamped to the stored frame), is the only part of a host 4:2:0
+ *       frame that is transferred, under the zero-copy and staging rule of ffl_upload_frames_yuv.  Host BGR / RGB frames
+ *       travel whole.
+ * An S = 1 map of integer coordinates gives the identity-mode operand of the resize paths, an S = 2 map of the integer
+ * samples (2x + i, 2y + j) their 2x2-mean operand, bit for bit. */
+enum { FFL_MAX_REMAPS = 8,                          /* maps alive per context */
+       FFL_REMAP_NO_SOURCE = -2147483647 - 1 };     /* INT32_MIN: rule R1 */
+
+/* Rules R1 and R6 for a map, and the rules of ffl_source_info.  Pure host function: no device or context needed; messages
+ * through ffl_last_error(NULL).  src_w x src_h is the STORED size (src NULL: upright already).  win_upright = {x, y, w, h}
+ * is the bounding box of the taps in the upright frame, win_stored the rectangle of the stored frame R6 names, *valid the
+ * number of valid entries; any output may be NULL.  FFL_ERR_INVALID: a NULL map, supersample outside {1, 2, 4}, sizes
+ * outside 1..32768, an entry outside R1 (named by its index), a map with no valid entry. */
+int ffl_remap_check(const int32_t *map, int out_w, int out_h, int supersample, int src_w, int src_h /*stored*/,
+                    const ffl_source_info *src, int win_upright[4], int win_stored[4], size_t *valid);
+
+/* Device bytes one map adds to a context (8 * S * S * out_w * out_h); ffl_estimate_bytes does not count them. */
+int ffl_remap_bytes(int out_w, int out_h, int supersample, size_t *bytes);
+
+/* A map for this context (out size = the context's) over an upright src_w x src_h source: checked on the host (R1), copied
+ * to the device; *id names it once it is resident, and the caller's array is no longer needed.  At most FFL_MAX_REMAPS are
+ * alive per context: one more is refused.  ffl_remap_destroy frees one; it may follow an upload call that used the map at
+ * once, for it waits for the last launch that reads the map.  ffl_destroy frees what is left. */
+int ffl_remap_create(ffl_ctx *ctx, const int32_t *map, int supersample, int src_w, int src_h /*upright*/, int *id);
+int ffl_remap_destroy(ffl_ctx *ctx, int id);
+
+/* n host frames -> frame slots first_slot .. first_slot+n-1 through the map remap_id (rules R2 to R6; k_frontend_remap).
+ * format: FFL_DEV_BGR or FFL_DEV_RGB ((h, w, 3) uint8 rows stride_bytes apart, depth 8) or FFL_DEV_I420 / FFL_DEV_NV12 (the
+ * single-array layouts of ffl_upload_frames_yuv; depth 8, or 9..16 for uint16 samples with msb_aligned as
+ * ffl_upload_frames_yuv16 takes them).  src_w x src_h is the STORED size; its upright size under `src` must be the map's.
+ * Slot publishing, staging and direct transfer, locks and refusals are those of ffl_upload_frames_raw_src and
+ * ffl_upload_frames_yuv_src / _yuv16_src.  Refused before any device work too: an unknown or destroyed id, an upright
+ * source size other than the map's, FFL_DEV_GRAY (a host gray frame has no map path). */
+int ffl_upload_frames_remap(ffl_ctx *ctx, int first_slot, int n, const uint8_t *const *frames, int format, int src_w,
+                            int src_h /*stored*/, ptrdiff_t stride_bytes, int depth, int msb_aligned, int remap_id,
+                            const ffl_source_info *src);
+
+/* The same for n device-resident frames of any FFL_DEV_* format (a gray frame of any size is gathered like a channel), in
+ * ONE k_frontend_remap_dev launch: the plane rules, memory checks and stream contract of ffl_upload_frames_device_src /
+ * _device16_src (a capturing stream is refused with FFL_ERR_STATE) and the map refusals of ffl_upload_frames_remap. */
+int ffl_upload_frames_device_remap(ffl_ctx *ctx, int first_slot, int n, const ffl_dev_frame *frames, int format, int depth,
+                                   int msb_aligned, int src_w, int src_h, int remap_id, uint64_t stream,
+                                   const ffl_source_info *src);
 
 /* The finished flow fields of flow_slots[0..n) -> dst + i * item_stride_bytes, as (H, W, 2) float32 (FFL_FLOW_NHWC) or as
  * (2, H, W) float32 (FFL_FLOW_NCHW); each item is contiguous, items may be anywhere apart (|stride| >= 8 * W * H bytes).
