@@ -516,6 +516,37 @@ def consistency_choice(params):
     return params
 
 
+class ResidualParams(C.Structure):
+    """ffl_residual_params: thr = alpha * (|gx| + |gy|) + beta in grey levels, soft 1 (a ramp) or 0 (a
+    threshold).  ResidualParams() holds the library's defaults (the project's own choice, not tuned on footage); keywords
+    override single fields."""
+    _fields_ = [("alpha", C.c_float), ("beta", C.c_float), ("soft", C.c_int)]
+
+    def __init__(self, **over):
+        super().__init__()
+        load().ffl_residual_default_params(C.byref(self))
+        for k, v in over.items():
+            if k not in ("alpha", "beta", "soft"):
+                raise ValueError(f"unknown residual parameter {k!r} (alpha, beta, soft)")
+            setattr(self, k, v)
+
+    def as_dict(self):
+        return {"alpha": self.alpha, "beta": self.beta, "soft": self.soft}
+
+
+def residual_params_check(params):
+    """ffl_residual_params_check: ValueError with the library's rule when it refuses (pure host check)."""
+    _check(load().ffl_residual_params_check(None if params is None else C.byref(params)), exc=ValueError)
+
+
+def residual_choice(params):
+    """a ResidualParams out of None (the defaults), a dict of its fields or a ResidualParams; checked"""
+    if not isinstance(params, ResidualParams):
+        params = ResidualParams(**dict(params or {}))
+    residual_params_check(params)
+    return params
+
+
 class MotionParams(C.Structure):
     """ffl_motion_params: the sub-model of rule C2 (a name of MOTION_MODELS or its code), the passes of
     rule C7 and the Cauchy scale tau of rule C3 in pixels.  MotionParams() holds the library's defaults (rule C9: translation,
@@ -738,6 +769,9 @@ SIGNATURES = {
     "ffl_consistency_default_params": (_i, (_P(ConsistencyParams),)),
     "ffl_consistency_params_check": (_i, (_P(ConsistencyParams),)),
     "ffl_consistency_weights": (_i, (_ctx, _i, _ip, _ip, _P(ConsistencyParams), _P(DevWeights), _P(DevWeights), _u64)),
+    "ffl_residual_default_params": (_i, (_P(ResidualParams),)),
+    "ffl_residual_params_check": (_i, (_P(ResidualParams),)),
+    "ffl_residual_weights": (_i, (_ctx, _i, _ip, _ip, _ip, _P(ResidualParams), _P(DevWeights), _P(DevWeights), _u64)),
     "ffl_cell_grid_check": (_i, (_i,) * 3 + (_ip, _ip)),
     "ffl_cell_stats": (_i, (_ctx, _i, _ip, _i, _vp, _vp, _u64)),
     "ffl_radial_window_axes_centres": (_i, _WINDOW + (_vp, _pd, _vp, _u64)),
@@ -780,6 +814,7 @@ EXPORTS = list(SIGNATURES)   # every symbol include/ffl.h declares
 # the header's records and their Python statements (the test takes the struct names from the header: none can be forgotten)
 RECORDS = {"ffl_source_info": SourceInfo, "ffl_dev_frame": DevFrame, "ffl_dev_flow": DevFlow, "ffl_pass2_record": PASS2_DTYPE,
            "ffl_axes_record": PASS2_AXES_DTYPE, "ffl_dev_weights": DevWeights, "ffl_consistency_params": ConsistencyParams,
+           "ffl_residual_params": ResidualParams,
            "ffl_cell_record": CELL_DTYPE, "ffl_grid_centre": GRID_CENTRE_DTYPE, "ffl_motion_params": MotionParams,
            "ffl_motion_record": MOTION_DTYPE, "ffl_dis_params": DisParams,
            "ffl_farneback_params": FarnebackParams}
@@ -1332,6 +1367,25 @@ class Context:
         gdesc = None if gate is None else self._weights("consistency_weights", gate, len(fs))
         self._chk(self.L.ffl_consistency_weights(self._h, len(fs), pf, pb, C.byref(prm), None if gdesc is None else C.byref(gdesc),
                                                  C.byref(odesc), stream_handle(stream, self.device)))
+        return out
+
+    def residual_weights(self, fslot0, fslot1, flow_slots, out, params=None, gate=None, stream=None):
+        """Photometric-residual maps (ffl_residual_weights): item i from the gray frames in frame slots
+        fslot0[i] and fslot1[i] (which may repeat between items) and the forward field in flow slot flow_slots[i], written into
+        `out`, a uint8 device tensor (n, H, W) (or a DevWeights; (H, W) for one item).  `params`: a ResidualParams, a dict of
+        its fields or None (the defaults, which are not tuned on footage); `gate`: maps S of rule P6 as pass1_weighted takes
+        maps, (H, W) or (n, H, W).  Queued behind the work on `stream`, the frames' uploads and the flow slots' last users;
+        `stream` waits for it, and a later upload into one of the frame slots runs behind it.  Returns `out`."""
+        p0, f0 = _iarr(fslot0)
+        p1, f1 = _iarr(fslot1)
+        pf, fl = _iarr(flow_slots)
+        if not len(f0) == len(f1) == len(fl):
+            raise ValueError(f"residual_weights: {len(f0)} and {len(f1)} frame slots for {len(fl)} flow slots")
+        prm = params if isinstance(params, ResidualParams) else ResidualParams(**dict(params or {}))
+        odesc = self._weights("residual_weights", out, len(fl))
+        gdesc = None if gate is None else self._weights("residual_weights", gate, len(fl))
+        self._chk(self.L.ffl_residual_weights(self._h, len(fl), p0, p1, pf, C.byref(prm), None if gdesc is None else C.byref(gdesc),
+                                              C.byref(odesc), stream_handle(stream, self.device)))
         return out
 
     def cell_stats(self, flow_slots, cells=32, cells_out=None, centres_out=None, stream=None):

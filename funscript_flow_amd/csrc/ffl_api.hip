@@ -291,7 +291,10 @@ struct ffl_ctx {
     PinBuf<uint8_t> h_stage_bgr;   // pinned [n_fslots][3N]
     std::vector<EvRef> ev_uploaded;  // per frame slot: the upload call that filled it (one event per call, up_ring)
     EvRing up_ring;                  // 2 * FFL_EV_RING entries
-    std::vector<EvRef> ev_last_use;  // [frame slot * n_lanes + lane]: the last batch of that lane that read the slot
+    // [frame slot * frame_readers() + r]: the last reader of the slot on stream r -- r < n_lanes: that lane's last batch (the
+    // lane's ring); r = n_lanes: the last ffl_residual_weights call, on stream `post` (post_ring).  An upload waits for all
+    std::vector<EvRef> ev_last_use;
+    size_t frame_readers() const { return lanes.size() + 1; }
     std::vector<char> frame_valid;
     std::vector<int> u_of_fslot;      // scratch of run_batch: frame slot -> index among the batch's unique frames (-1 outside)
     std::vector<char> slot_mark;      // scratch of check_flow_slots: flow slot already named in this call
@@ -671,9 +674,10 @@ static int wait_unlocked(ffl_ctx *c, CtxLock &lk, const hipEvent_t *evs, int n) 
     return FFL_OK;
 }
 
-// Stream `copy` waits for the batches (of every lane) that may still read frame slot fs, before a transfer overwrites it.
+// Stream `copy` waits for the batches (of every lane) and the residual call (stream `post`) that may still read frame slot fs,
+// before a transfer overwrites it.
 static int wait_frame_free(ffl_ctx *c, WaitOnce &wait_copy, int fs) {
-    const size_t nl = c->lanes.size();
+    const size_t nl = c->frame_readers();
     for (size_t l = 0; l < nl; l++) HIPCHK(c, wait_copy(c->ev_last_use[(size_t)fs * nl + l].get()));
     return FFL_OK;
 }
@@ -968,7 +972,7 @@ static int create_resources(ffl_ctx *c) {
     HIPCHK_ALLOC(nullptr, hipHostMalloc, c->h_radial, FFL_MAXB, hipHostMallocMapped);
     HIPCHK(nullptr, hipHostGetDevicePointer((void **)&c->d_radial, c->h_radial, 0));
     c->ev_uploaded.assign(n_frame_slots, EvRef{});
-    c->ev_last_use.assign((size_t)n_frame_slots * num_lanes, EvRef{});  // references into the lanes' rings
+    c->ev_last_use.assign((size_t)n_frame_slots * c->frame_readers(), EvRef{});  // references into the lanes' rings and post_ring
     c->frame_valid.assign(n_frame_slots, 0);
     c->u_of_fslot.assign(n_frame_slots, -1);
     c->slot_mark.assign(n_flow_slots, 0);
@@ -1713,7 +1717,7 @@ static int run_batch(ffl_ctx *c, int li, int n, const int *f0, const int *f1, co
     // slots hold no result.
     EvRef ev;
     HIPCHK(c, L.ring.record(L.st, &ev));
-    for (int i = 0; i < nU; i++) c->ev_last_use[(size_t)T.ut.fslot[i] * c->lanes.size() + li] = ev;
+    for (int i = 0; i < nU; i++) c->ev_last_use[(size_t)T.ut.fslot[i] * c->frame_readers() + li] = ev;
     publish_slots(c, n, slots, ev, rc == FFL_OK);
     return rc;
 }
@@ -2968,6 +2972,101 @@ int ffl_consistency_weights(ffl_ctx *c, int n, const int *fwd_slots, const int *
     ffl_launch_consistency(c->d_flow, tf, tb, n, c->w, c->h, prm.alpha, prm.beta, prm.soft, gate ? &ga : nullptr, (char *)out->base,
                            (long long)out->item_stride, (long long)out->row_pitch, c->s_post);
     return post_end(c, cst, 2 * n, all);  // the caller may read the maps, or overwrite the gate, on `stream` straight after the call
+}
+
+// ---- photometric-residual maps -------------------------------------------------------
+int ffl_residual_default_params(ffl_residual_params *out) {
+    if (!out) return FFL_ERR_INVALID;
+    *out = ffl_residual_params{0.5f, 4.0f, 1};   // the project's own choice, not tuned on footage
+    return FFL_OK;
+}
+
+// The accepted parameters of appendix P.  The comparisons are written so that a NaN fails them.
+static int residual_params_check(ffl_ctx *c, const char *fn, const ffl_residual_params *p) {
+    if (!p) return set_err(c, FFL_ERR_INVALID, "%s: NULL parameters", fn);
+    if (!(p->alpha >= 0.0f && p->alpha <= 16.0f))
+        return set_err(c, FFL_ERR_INVALID, "%s: alpha = %g outside 0..16 (finite)", fn, (double)p->alpha);
+    if (!(p->beta > 0.0f && p->beta <= 255.0f))
+        return set_err(c, FFL_ERR_INVALID, "%s: beta = %g outside 0 < beta <= 255 (finite)", fn, (double)p->beta);
+    if (p->soft != 0 && p->soft != 1) return set_err(c, FFL_ERR_INVALID, "%s: soft = %d is neither 0 (hard) nor 1 (soft)", fn, p->soft);
+    return FFL_OK;
+}
+
+int ffl_residual_params_check(const ffl_residual_params *p) {
+    return residual_params_check(nullptr, "ffl_residual_params_check", p);
+}
+
+// n maps from n pairs of frames and their forward fields by ONE k_residual launch on stream `post`: ffl_consistency_weights'
+// protocol over the n flow slots, and a reader's protocol over the frame slots -- stream `post` waits for the uploads that
+// filled them (ev_uploaded, as a batch does), and the call's event becomes their last reader on stream `post` (ev_last_use's
+// last column), which every later upload into one of them waits for (wait_frame_free).  An upload looks that column up under
+// the context lock right before it queues its transfer, and this call holds the lock from its waits to its event, so the two
+// cannot interleave.
+int ffl_residual_weights(ffl_ctx *c, int n, const int *fslot0, const int *fslot1, const int *flow_slots, const ffl_residual_params *p,
+                         const ffl_dev_weights *gate, const ffl_dev_weights *out, uint64_t stream) {
+    static const char *fn = "ffl_residual_weights";
+    if (!c) return FFL_ERR_INVALID;
+    std::unique_lock<std::mutex> pl(c->post_mu);  // stream `post`, as ffl_consistency_weights
+    CtxLock lk(c->mu);
+    if (n < 1 || n > c->max_batch)
+        return set_err(c, FFL_ERR_INVALID, "%s: n = %d items outside 1..%d (the context's max_batch)", fn, n, c->max_batch);
+    if (!fslot0 || !fslot1 || !flow_slots)
+        return set_err(c, FFL_ERR_INVALID, "%s: NULL %s", fn, !fslot0 ? "fslot0" : !fslot1 ? "fslot1" : "flow_slots");
+    ExportTab t0, t1, tf;
+    for (int i = 0; i < n; i++) {
+        for (int fs : {fslot0[i], fslot1[i]}) {   // frame slots may repeat between items
+            if (fs < 0 || fs >= c->n_fslots) return set_err(c, FFL_ERR_INVALID, "%s: item %d: frame slot %d out of range", fn, i, fs);
+            if (!c->frame_valid[fs]) return set_err(c, FFL_ERR_STATE, "%s: item %d: frame slot %d was never uploaded", fn, i, fs);
+        }
+        t0.slot[i] = fslot0[i];
+        t1.slot[i] = fslot1[i];
+        tf.slot[i] = flow_slots[i];
+    }
+    if (int rc = check_flow_slots(c, fn, n, flow_slots, "flow", "repeated among the flow slots of one call")) return rc;
+    ffl_residual_params prm;
+    ffl_residual_default_params(&prm);
+    if (p) prm = *p;
+    if (int rc = residual_params_check(c, fn, &prm)) return rc;
+    size_t obytes, gbytes = 0;
+    if (!out) return set_err(c, FFL_ERR_INVALID, "%s: NULL out descriptor", fn);
+    if (int rc = dev_weights_check(c, fn, n, c->w, c->h, out, &obytes)) return rc;
+    if (n > 1 && out->item_stride == 0)
+        return set_err(c, FFL_ERR_INVALID, "%s: overlap: out item stride 0 with n = %d maps to write (one map per item)", fn, n);
+    if (gate) {
+        if (int rc = dev_weights_check(c, fn, n, c->w, c->h, gate, &gbytes)) return rc;
+        const uintptr_t o0 = (uintptr_t)out->base, g0 = (uintptr_t)gate->base;
+        if (o0 < g0 + gbytes && g0 < o0 + obytes)
+            return set_err(c, FFL_ERR_INVALID, "%s: overlap: out (%zu bytes) and gate (%zu bytes) share memory", fn, obytes, gbytes);
+    }
+    hipStream_t cst;
+    PostRegion reg[2] = {{"out", out->base, obytes, kHostWeights}, {"the gate maps", gate ? gate->base : nullptr, gbytes, kHostWeights}};
+    if (int rc = post_begin(c, fn, stream, &cst, reg, gate ? 2 : 1, n, flow_slots)) return rc;
+    {
+        WaitOnce wait_post(c->s_post);   // the frames: a run of slots shares one or two upload events
+        for (int i = 0; i < n; i++) {
+            HIPCHK(c, wait_post(c->ev_uploaded[fslot0[i]].get()));
+            HIPCHK(c, wait_post(c->ev_uploaded[fslot1[i]].get()));
+        }
+    }
+    WeightArgs ga;
+    if (gate) ga = WeightArgs{(const char *)gate->base, (long long)gate->item_stride, (long long)gate->row_pitch};
+    ffl_launch_residual(c->d_gray, c->d_flow, t0, t1, tf, n, c->w, c->h, prm.alpha, prm.beta, prm.soft, gate ? &ga : nullptr,
+                        (char *)out->base, (long long)out->item_stride, (long long)out->row_pitch, c->s_post);
+    // The frame slots' reader is recorded whether or not post_end succeeds: an event of its own if post_end recorded none, so
+    // that a launch that was queued is never overtaken by an upload (if even that fails the stream is drained)
+    const unsigned long long before = c->post_ring.next;
+    const int rc = post_end(c, cst, n, flow_slots);
+    EvRef done = ev_latest(c->post_ring);
+    if (c->post_ring.next == before && c->post_ring.record(c->s_post, &done) != hipSuccess) {
+        (void)hipStreamSynchronize(c->s_post);
+        done = EvRef{};
+    }
+    const size_t nr = c->frame_readers();
+    for (int i = 0; i < n; i++) {
+        c->ev_last_use[(size_t)fslot0[i] * nr + (nr - 1)] = done;
+        c->ev_last_use[(size_t)fslot1[i] * nr + (nr - 1)] = done;
+    }
+    return rc;  // the caller may read the maps, or overwrite the gate, on `stream` straight after the call
 }
 
 static const char *kHostCentres ="centres live in device memory (ffl_cell_stats' records, or a float64 (n_seq, 2) tensor)";

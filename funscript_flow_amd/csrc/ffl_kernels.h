@@ -316,6 +316,13 @@ void ffl_launch_consistency(const float *flow, const ExportTab &fwd, const Expor
                             float beta, int soft, const WeightArgs *gate, char *out, long long out_item, long long out_pitch,
                             hipStream_t st);
 
+// photometric-residual maps (k_residual): item b's map, from the gray frames in frame slots
+// fr0.slot[b] and fr1.slot[b] of `gray` (N = w * h bytes each) and the forward field in flow slot fl.slot[b], goes to
+// out + b * out_item, rows out_pitch bytes apart; gate (may be NULL): the maps of rule P6
+void ffl_launch_residual(const unsigned char *gray, const float *flow, const ExportTab &fr0, const ExportTab &fr1, const ExportTab &fl,
+                         int n, int w, int h, float alpha, float beta, int soft, const WeightArgs *gate, char *out,
+                         long long out_item, long long out_pitch, hipStream_t st);
+
 // ---- global-motion fit and compensation (kernels_post.hip) -----------------------
 #define FFL_MOTION_NSUMS 12          // = FFL_MOTION_N_SUMS of include/ffl.h; the order of rule C4
 enum { MOT_S = 0, MOT_SX, MOT_SY, MOT_SXX, MOT_SXY, MOT_SYY, MOT_SU, MOT_SUX, MOT_SUY, MOT_SV, MOT_SVX, MOT_SVY };

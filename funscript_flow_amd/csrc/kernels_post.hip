@@ -956,6 +956,120 @@ void ffl_launch_consistency(const float *flow, const ExportTab &fwd, const Expor
                        soft, g, out, out_item, out_pitch);
 }
 
+// ---- photometric-residual maps ---------------------------------------------------
+// k_residual writes one uint8 weight per pixel from the gray operands I0, I1 of a pair and its forward field F: I1 sampled
+// where F lands, against I0's pixel, measured by I0's local gradient.  k_consistency's form: grid = (blocks per item, items), a
+// lane owns a quad of a row, F is 32 streamed bytes, gate and output 4 bytes each where their addresses allow.  The uint8 side:
+// I0's centre quad and the quads of the rows above and below are one 4-byte load each where the address allows (bytes
+// otherwise; a frame slot's rows are w bytes apart, so a width that is no multiple of 4 takes the byte form on most rows), its
+// left and right neighbours one byte each, all with clamped edges; the four corners of I1 are four byte gathers at clamped
+// coordinates, so that no access leaves the frame (rule P1: a pixel that lands outside reads nothing of I1).  No LDS, no loop,
+// plain vector loads and stores, 32-bit pixel offsets inside a frame.  Bound by the address path of the byte gathers and
+// loads, with the arithmetic close behind (1080p n = 32: TA 82 % busy, VALU 69 %, 2.1 TB/s fetched; 1.29 x k_export_flows'
+// time, 0.71 x k_consistency's).
+__device__ __forceinline__ unsigned ffl_load_quad_u8(const unsigned char *__restrict__ p, int np) {   // bytes p[0..np) packed
+    if (np == 4 && ((uintptr_t)p & 3) == 0) return *(const unsigned *)p;
+    unsigned r = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        if (k < np) r |= (unsigned)p[k] << (8 * k);
+    return r;
+}
+
+__device__ __forceinline__ unsigned ffl_residual_pixel(const unsigned char *__restrict__ I1, float2 f, int i0, int gx, int gy, int x,
+                                                       int y, int w, int h, float alpha, float beta, int soft) {
+    const float px = (float)x + f.x, py = (float)y + f.y;
+    const bool inside = px >= 0.0f && px <= (float)(w - 1) && py >= 0.0f && py <= (float)(h - 1);   // P1: NaN / inf fail
+    if (!inside) return 0u;
+    const float fx = floorf(px), fy = floorf(py);                                                     // P2
+    const int x0 = (int)fx, y0 = (int)fy;
+    const int x1 = x0 + 1 < w - 1 ? x0 + 1 : w - 1, y1 = y0 + 1 < h - 1 ? y0 + 1 : h - 1;
+    const float ax = px - fx, ay = py - fy;
+    const unsigned r0 = (unsigned)y0 * (unsigned)w, r1 = (unsigned)y1 * (unsigned)w;   // 0 <= x0 <= x1 <= w-1, 0 <= y0 <= y1 <= h-1
+    const float i00 = (float)I1[r0 + (unsigned)x0], i01 = (float)I1[r0 + (unsigned)x1];
+    const float i10 = (float)I1[r1 + (unsigned)x0], i11 = (float)I1[r1 + (unsigned)x1];
+    const float t = i00 + ax * (i01 - i00), s = i10 + ax * (i11 - i10);
+    const float ic = t + ay * (s - t);
+    const float a = fabsf(ic - (float)i0);                                                            // P3
+    const float g = fabsf((float)gx) + fabsf((float)gy);
+    const float thr = alpha * g + beta;
+    if (!soft) return a < thr ? 255u : 0u;                                                            // P5: no division
+    float q = 1.0f - a / thr;                                                                         // P4
+    q = q > 0.0f ? q : 0.0f;   // a select: a NaN gives 0
+    return (unsigned)(int)(q * 255.0f + 0.5f);
+}
+
+__global__ __launch_bounds__(256) void k_residual(const unsigned char *__restrict__ gray, const float *__restrict__ flow, ExportTab fr0,
+                                                  ExportTab fr1, ExportTab fl, int w, int h, float alpha, float beta, int soft,
+                                                  WeightArgs gate, char *__restrict__ out, long long out_item, long long out_pitch) {
+    const int qw = (w + 3) >> 2;   // quads per row
+    const unsigned q = blockIdx.x * 256u + threadIdx.x;
+    if (q >= (unsigned)qw * (unsigned)h) return;
+    const int y = (int)(q / (unsigned)qw), x = (int)(q % (unsigned)qw) * 4;
+    const int b = blockIdx.y, np = w - x < 4 ? w - x : 4;   // pixels of this quad
+    const size_t N = (size_t)w * h;
+    const float2 *F = (const float2 *)(flow + (size_t)fl.slot[b] * 2 * N) + ((unsigned)y * (unsigned)w + (unsigned)x);
+    const unsigned char *I0 = gray + (size_t)fr0.slot[b] * N, *I1 = gray + (size_t)fr1.slot[b] * N;
+    float2 f[4];
+    if (np == 4 && ((uintptr_t)F & 15) == 0) {
+        const float4 a = ((const float4 *)F)[0], c = ((const float4 *)F)[1];
+        f[0] = make_float2(a.x, a.y), f[1] = make_float2(a.z, a.w), f[2] = make_float2(c.x, c.y), f[3] = make_float2(c.z, c.w);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) f[k] = k < np ? F[k] : make_float2(0.0f, 0.0f);
+    }
+    // I0: rows max(y-1, 0), y, min(y+1, h-1) at columns x .. x+np-1, and row y's columns max(x-1, 0) and min(x+np, w-1)
+    const unsigned row = (unsigned)y * (unsigned)w + (unsigned)x;
+    const unsigned up = (unsigned)(y > 0 ? y - 1 : 0) * (unsigned)w + (unsigned)x;
+    const unsigned dn = (unsigned)(y + 1 < h ? y + 1 : h - 1) * (unsigned)w + (unsigned)x;
+    const unsigned c4 = ffl_load_quad_u8(I0 + row, np), u4 = ffl_load_quad_u8(I0 + up, np), d4 = ffl_load_quad_u8(I0 + dn, np);
+    const int left = x > 0 ? (int)I0[row - 1] : (int)(c4 & 255u);
+    const int right = x + np < w ? (int)I0[row + (unsigned)np] : (int)((c4 >> (8 * (np - 1))) & 255u);
+    int ce[6];   // row y at columns x-1 .. x+4, clamped
+    ce[0] = left;
+#pragma unroll
+    for (int k = 0; k < 4; k++) ce[k + 1] = (int)((c4 >> (8 * k)) & 255u);
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        if (k == np) ce[k + 1] = right;
+    ce[5] = right;
+    unsigned wt[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int gx = ce[k + 2] - ce[k], gy = (int)((d4 >> (8 * k)) & 255u) - (int)((u4 >> (8 * k)) & 255u);
+        wt[k] = k < np ? ffl_residual_pixel(I1, f[k], ce[k + 1], gx, gy, x + k, y, w, h, alpha, beta, soft) : 0u;
+    }
+    if (gate.base) {   // P6
+        const unsigned char *g = (const unsigned char *)gate.base + (long long)b * gate.item + (long long)y * gate.pitch + x;
+        if (np == 4 && ((uintptr_t)g & 3) == 0) {
+            const unsigned s = *(const unsigned *)g;
+#pragma unroll
+            for (int k = 0; k < 4; k++) wt[k] = min(wt[k], (s >> (8 * k)) & 255u);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (k < np) wt[k] = min(wt[k], (unsigned)g[k]);
+        }
+    }
+    unsigned char *o = (unsigned char *)out + (long long)b * out_item + (long long)y * out_pitch + x;
+    if (np == 4 && ((uintptr_t)o & 3) == 0) {
+        *(unsigned *)o = wt[0] | (wt[1] << 8) | (wt[2] << 16) | (wt[3] << 24);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (k < np) o[k] = (unsigned char)wt[k];
+    }
+}
+
+void ffl_launch_residual(const unsigned char *gray, const float *flow, const ExportTab &fr0, const ExportTab &fr1, const ExportTab &fl,
+                         int n, int w, int h, float alpha, float beta, int soft, const WeightArgs *gate, char *out,
+                         long long out_item, long long out_pitch, hipStream_t st) {
+    const size_t quads = (size_t)((w + 3) / 4) * h;   // below 2^30: 20 * w * h < 2^32
+    const WeightArgs g = gate ? *gate : WeightArgs{nullptr, 0, 0};
+    hipLaunchKernelGGL(k_residual, dim3((unsigned)((quads + 255) / 256), n), dim3(256), 0, st, gray, flow, fr0, fr1, fl, w, h, alpha, beta,
+                       soft, g, out, out_item, out_pitch);
+}
+
 // ---- flow import -----------------------------------------------------------------------------
 // k_import_pass1 reads n caller fields once: every pixel is widened to float32, stored into its flow slot by the lane that
 // owns it in pass 1's walk (halo loads never store), and fed to the pass-1 body in k_pass1's order, so the partials -- and

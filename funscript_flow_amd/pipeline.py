@@ -264,7 +264,7 @@ class PairEngine:
                                 farneback=farneback, window=window, behind=behind)
 
     def pass1_pairs(self, frames, pairs, slot_of, pov_mode=False, cut_threshold=7.0, on_batch=None, algo=None,
-                    farneback=OWN, window=OWN, queued=None, batch=None, reverse_slot_of=None, behind=None):
+                    farneback=OWN, window=OWN, queued=None, batch=None, reverse_slot_of=None, behind=None, with_frames=None):
         """Pass 1 for an arbitrary ascending list of pair indices (pair j = frames[j], frames[j+1]) in batches of
         max_batch; the flow of the l-th listed pair stays resident in flow slot slot_of(l).  Frames go to the
         device once per run of batches that needs them: a ring over the frame slots, frames of the batch being
@@ -282,7 +282,11 @@ class PairEngine:
         frames' expansions are shared (2 * batch <= max_batch); records and callbacks are those of the forward pairs.
         `behind(local_indices, pair_indices)`: called straight after every batch has been queued and before anything reads
         its records or fields (queued= included): what it queues on the batch's slots -- the motion compensation of
-        process_chunk -- is what every later reader sees."""
+        process_chunk -- is what every later reader sees.
+        `with_frames(local_indices, pair_indices, fslot0, fslot1)`: called straight after every batch has been queued, ahead of
+        behind=, with the frame slots the batch's pairs were queued from (frames[j] in fslot0, frames[j + 1] in fslot1): what
+        reads the batch's frames next to its raw fields -- the residual maps of process_chunk.  The slots stay the frames'
+        until a later batch is staged, and the library orders that upload behind whatever the hook queued on them."""
         ctx, B, S = self.ctx, (self.B if batch is None else int(batch)), self.ctx.frame_slots
         algo, dis = algo if algo is not None else (getattr(self, "flow", "farneback"), getattr(self, "dis", None))
         fb = getattr(self, "farneback", None) if farneback is OWN else farneback
@@ -330,6 +334,8 @@ class PairEngine:
                 ctx.flow_pairs_farneback(f0, f1, fl, pov_mode, fb)
             else:
                 ctx.flow_pairs(f0, f1, fl, pov_mode)
+            if with_frames is not None:
+                with_frames(ls, js, f0[:len(ls)], f1[:len(ls)])
             if behind is not None:
                 behind(ls, js)
             return ls, js
@@ -361,7 +367,7 @@ class PairEngine:
 
     def process_chunk(self, frames, pov_mode=False, cut_threshold=7.0, algo=None, farneback=OWN, flows_out=None, window=OWN,
                       post_out=None, axes=False, weights=None, center=None, cells=32, grid_out=None, consistency=None,
-                      weights_out=None, weights_gate=None, compensate=None, motion_out=None):
+                      weights_out=None, weights_gate=None, compensate=None, motion_out=None, residual=None):
         """One whole chunk on one GPU: returns (dots float64[n], records) with n = len(frames)-1.  `algo`, `farneback`,
         `window`: see pass1_pairs (default: the engine's own flow algorithm, parameters and window).  `flows_out`: a float32 device array of
         (n, H, W, 2) or (n, 2, H, W) that receives every pair's flow field (Context.export_flows, on torch's current stream)
@@ -390,6 +396,11 @@ class PairEngine:
         one flow call of the pairs and the same pairs reversed; behind it Context.consistency_weights, then the calls of
         `weights`.  The chunk's maps live in one (n, H, W) uint8 device tensor: a new one, or `weights_out`, filled in
         place.  flows_out still receives the forward fields.
+        `weights` = "residual": the maps are the photometric residual of every pair under its own forward field (DESIGN.md
+        section 21; `residual`: a _capi.ResidualParams, a dict of its fields or None for the defaults, which are not tuned on
+        footage; `weights_gate`: the static gate of rule P6; `weights_out` as above).  The batch stays max_batch pairs and the
+        ring every flow slot, nothing is queued reversed: behind each batch's flow call Context.residual_weights writes the
+        batch's maps from its frame slots and raw fields, then the calls of `weights` run.
         `compensate`: a model name of _capi.MOTION_MODELS, a dict of _capi.MotionParams fields or a MotionParams (DESIGN.md
         section 19).  Behind each batch, and before anything reads its records or fields, Context.motion_fit is queued on the
         batch's slots -- under `weights` when that is a map -- and then Context.motion_subtract in place: pass 1, pass 2,
@@ -397,15 +408,19 @@ class PairEngine:
         FIELDS.  "similarity" and "affine" contain a zoom term, which is the radial signal itself (rule C9).  `motion_out`:
         device memory for n 64-byte records (motion_buffer; motion_records reads it), the fitted model of every pair -- the
         camera path.  Not combined with weights="consistency" (the maps need both raw directions, and the ring holds the
-        reversed pairs).  Without compensate= nothing of this runs."""
+        reversed pairs).  With weights="residual" the order behind a batch is: the maps from the raw fields, the fit (which
+        the maps weight), the subtraction.  Without compensate= nothing of this runs."""
         ctx, B = self.ctx, self.B
         n = len(frames) - 1
-        if compensate is not None and isinstance(weights, str):
+        if compensate is not None and isinstance(weights, str) and weights == "consistency":
             raise ValueError(f"compensate= together with weights={weights!r} is not supported: the consistency maps need both "
                              "raw directions of every pair, and the slot ring holds the reversed pairs")
-        cons = _chunk_consistency(self, n, weights, consistency, weights_out, weights_gate)
+        resid = _chunk_residual(self, n, weights, residual, consistency, weights_out, weights_gate)
+        cons = None if resid is not None else _chunk_consistency(self, n, weights, consistency, weights_out, weights_gate)
         if cons is not None:
             weights, B = cons.maps, cons.B
+        if resid is not None:
+            weights = resid.maps
         ring = ctx.flow_slots if cons is None else cons.ring
         maps = weights   # the tensor stays referenced while the calls that read it are queued
         post_out, axes, weights, grid = _chunk_post_args(ctx, n, post_out, axes, weights, center, cells, grid_out,
@@ -428,6 +443,8 @@ class PairEngine:
 
             if comp is not None:
                 comp.stream = post.stream
+            if resid is not None:
+                resid.stream = post.stream
 
             def queued(ls, js):
                 if layout is not None:   # before the window calls below let later batches recycle these slots
@@ -447,7 +464,7 @@ class PairEngine:
                     release(upto)
 
             self.pass1_pairs(frames, range(n), lambda l: l % ring, pov_mode, cut_threshold, algo=algo,
-                             farneback=farneback, window=window, queued=queued, **_behind_kw(comp),
+                             farneback=farneback, window=window, queued=queued, **_behind_kw(comp), **_frames_kw(resid),
                              **({} if cons is None else {"batch": B, "reverse_slot_of": cons.bwd_slot}))
             if marks:
                 marks[-1][0].synchronize()   # the ring's slots may be reused by the next chunk: every transfer is over
@@ -478,6 +495,9 @@ class PairEngine:
         `compensate`, `motion_out`: as in process_chunk -- motion_fit and motion_subtract in place behind each import, before
         anything reads the imported fields' records."""
         ctx, B, fs = self.ctx, self.B, self.ctx.flow_slots
+        if isinstance(weights, str) and weights == "residual":
+            raise ValueError("process_flows: weights='residual' needs the frames, which a chunk of caller flows does not have; "
+                             "Context.residual_weights serves callers who hold the frames in the context's frame slots")
         if isinstance(weights, str):
             raise ValueError(f"process_flows: weights={weights!r} needs the backward fields, which a chunk of caller flows does "
                              "not have; Context.consistency_weights serves callers with their own estimator")
@@ -543,7 +563,10 @@ def _chunk_weights(ctx, weights, n):
     return desc
 
 
-WEIGHT_MODES = ("consistency",)   # weights= / params["hip_weights"] as a string: maps the library makes itself
+# weights= / params["hip_weights"] as a string: maps the library makes itself.  WEIGHT_MODES keeps the value its users know: the
+# modes made from both flow directions of a pair, which halve the batch and exclude compensate=; MAP_MODES is every mode
+WEIGHT_MODES = ("consistency",)
+MAP_MODES = WEIGHT_MODES + ("residual",)
 
 
 class _ChunkConsistency:
@@ -553,7 +576,6 @@ class _ChunkConsistency:
     checked _capi.ConsistencyParams; gate: the static gate's _capi.DevWeights or None (its tensor stays referenced)."""
 
     def __init__(self, engine, n, params, maps_out, gate):
-        import torch
         ctx = engine.ctx
         self.B = ctx.max_batch // 2
         if self.B < 1:
@@ -562,28 +584,77 @@ class _ChunkConsistency:
         region = (getattr(engine, "depth", 1) + 1) * self.B
         self.ring = ctx.flow_slots - region   # >= (depth + 1) * B + 13 on any engine: min_flow_slots(max_batch, depth)
         self.bwd_slot = lambda l: self.ring + l % region
-        shape = (max(n, 0), ctx.height, ctx.width)
-        if maps_out is None:
-            maps_out = torch.empty(shape, dtype=torch.uint8, device=torch.device("cuda", ctx.device))
-        elif not isinstance(maps_out, torch.Tensor) or maps_out.dtype != torch.uint8 or tuple(maps_out.shape) != shape:
-            raise ValueError(f"weights_out must be a uint8 device tensor of shape {shape}")
-        self.maps = maps_out
-        self.gate_tensor, self.gate = gate, None
-        if gate is not None:
-            self.gate, m = _capi.device_weights(gate, ctx.width, ctx.height)
-            if m != 0:
-                raise ValueError("weights_gate: one static (H, W) map")
+        self.maps = _chunk_maps(ctx, n, maps_out)
+        self.gate_tensor, self.gate = gate, _static_gate(ctx, gate)
+
+
+def _chunk_maps(ctx, n, maps_out):
+    """the (n, H, W) uint8 device tensor a mode of MAP_MODES fills: weights_out, checked, or a new one"""
+    import torch
+    shape = (max(n, 0), ctx.height, ctx.width)
+    if maps_out is None:
+        return torch.empty(shape, dtype=torch.uint8, device=torch.device("cuda", ctx.device))
+    if not isinstance(maps_out, torch.Tensor) or maps_out.dtype != torch.uint8 or tuple(maps_out.shape) != shape:
+        raise ValueError(f"weights_out must be a uint8 device tensor of shape {shape}")
+    return maps_out
+
+
+def _static_gate(ctx, gate):
+    """weights_gate= as a _capi.DevWeights: one static (H, W) map, or None"""
+    if gate is None:
+        return None
+    desc, m = _capi.device_weights(gate, ctx.width, ctx.height)
+    if m != 0:
+        raise ValueError("weights_gate: one static (H, W) map")
+    return desc
 
 
 def _chunk_consistency(engine, n, weights, params, maps_out, gate):
-    """None unless weights names a mode of WEIGHT_MODES; the keywords that belong to it are refused without it"""
+    """None unless weights is a string, which must then name a mode of WEIGHT_MODES ("residual" never arrives here: _chunk_residual
+    takes it first); the keywords that belong to a mode are refused without one"""
     if not isinstance(weights, str):
         if params is not None or maps_out is not None or gate is not None:
-            raise ValueError("consistency=, weights_out= and weights_gate= need weights='consistency'")
+            raise ValueError("consistency=, weights_out= and weights_gate= need weights='consistency' (the latter two: or 'residual')")
         return None
     if weights not in WEIGHT_MODES:
-        raise ValueError(f"weights must be a device tensor of maps or one of {WEIGHT_MODES}, got {weights!r}")
+        raise ValueError(f"weights must be a device tensor of maps or one of {WEIGHT_MODES}, got {weights!r}; or 'residual', the "
+                         "mode that needs no backward flow")
     return _ChunkConsistency(engine, n, params, maps_out, gate)
+
+
+class _ChunkResidual:
+    """What weights="residual" adds to a chunk of n pairs on `engine`: nothing about its batches or its
+    slot ring; with_frames(ls, js, f0, f1), pass1_pairs' hook, queues Context.residual_weights on the batch's frame slots and
+    raw fields (the l-th pair in flow slot l % flow_slots), which writes the pairs' maps into the chunk's (n, H, W) uint8 device
+    tensor `maps`.  params: the checked _capi.ResidualParams; gate: the static gate's _capi.DevWeights or None (its tensor
+    stays referenced); stream: where the call is queued (the device schedule sets its side stream)."""
+
+    def __init__(self, engine, n, params, maps_out, gate):
+        self.ctx = engine.ctx
+        self.params = _capi.residual_choice(params)
+        self.maps = _chunk_maps(self.ctx, n, maps_out)
+        self.gate_tensor, self.gate = gate, _static_gate(self.ctx, gate)
+        self.stream = None
+
+    def with_frames(self, ls, js, f0, f1):
+        self.ctx.residual_weights(f0, f1, [l % self.ctx.flow_slots for l in ls], self.maps[js[0]:js[-1] + 1], self.params,
+                                  self.gate, self.stream)
+
+
+def _chunk_residual(engine, n, weights, params, consistency, maps_out, gate):
+    """None unless weights is "residual"; residual= is refused without it, and consistency= with it"""
+    if not (isinstance(weights, str) and weights == "residual"):
+        if params is not None:
+            raise ValueError("residual= needs weights='residual'")
+        return None
+    if consistency is not None:
+        raise ValueError("consistency= needs weights='consistency', not weights='residual' (its parameters are residual=)")
+    return _ChunkResidual(engine, n, params, maps_out, gate)
+
+
+def _frames_kw(resid):
+    """with_frames= only where there is something to queue: an engine without the keyword keeps serving the plain chunk"""
+    return {} if resid is None else {"with_frames": resid.with_frames}
 
 
 def chunk_center(center):
@@ -684,7 +755,7 @@ def _no_sharded_compensate(compensate, who):
 
 def _no_sharded_weights(weights, who):
     if weights is not None:
-        raise ValueError(f"{who}: the sharded schedules run unweighted; weights= (maps, or 'consistency') needs "
+        raise ValueError(f"{who}: the sharded schedules run unweighted; weights= (maps, 'consistency' or 'residual') needs "
                          "PairEngine.process_chunk on one device")
 
 
@@ -870,16 +941,21 @@ def _static_map(engine, params, key):
 
 
 def consistency_kwargs(engine, params):
-    """The keywords of process_chunk when params["hip_weights"] names a mode of WEIGHT_MODES -- params["hip_consistency"] (a dict
+    """The keywords of process_chunk when params["hip_weights"] names a mode of MAP_MODES -- params["hip_consistency"] (a dict
     of _capi.ConsistencyParams fields) and params["hip_weights_gate"] (a static (H, W) map) go with it -- else {}; the two
-    further keys are refused without it."""
-    if not isinstance(params.get("hip_weights"), str):
-        for key in ("hip_consistency", "hip_weights_gate"):
+    further keys are refused without it.  With "residual" the parameters are params["hip_residual"] (a dict of
+    _capi.ResidualParams fields); each mode refuses the other's parameters."""
+    mode = params.get("hip_weights")
+    if not isinstance(mode, str):
+        for key, needs in (("hip_consistency", "'consistency'"), ("hip_residual", "'residual'"),
+                           ("hip_weights_gate", "'consistency' or 'residual'")):
             if params.get(key) is not None:
-                raise ValueError(f"{key} needs hip_weights = 'consistency'")
+                raise ValueError(f"{key} needs hip_weights = {needs}")
         return {}
-    return {"weights": params["hip_weights"], "consistency": params.get("hip_consistency"),
-            "weights_gate": _static_map(engine, params, "hip_weights_gate")}
+    own, other = ("residual", "consistency") if mode == "residual" else ("consistency", "residual")
+    if params.get("hip_" + other) is not None:
+        raise ValueError(f"hip_{other} needs hip_weights = {other!r}, got {mode!r}")
+    return {"weights": mode, own: params.get("hip_" + own), "weights_gate": _static_map(engine, params, "hip_weights_gate")}
 
 
 def center_kwargs(params):
@@ -906,6 +982,9 @@ def _axes_kw(axes):
 
 def _flow_chunks(engine, chunk_flows, fps, total_frames, params, axes, who):
     plan = pair_plan(fps, total_frames, params)
+    if isinstance(params.get("hip_weights"), str) and params["hip_weights"] == "residual":
+        raise ValueError(f"{who}: hip_weights = 'residual' needs the frames, which caller flows do not have; "
+                         "Context.residual_weights serves callers who hold the frames in the context's frame slots")
     if isinstance(params.get("hip_weights"), str):
         raise ValueError(f"{who}: hip_weights = {params['hip_weights']!r} needs the backward fields, which caller flows do not "
                          "have; Context.consistency_weights serves callers with their own estimator")
@@ -952,7 +1031,7 @@ def _chunk_scalars(engine, items, params, axes=False, run=None, **kw):
     if cen:   # params["hip_center"]: the device schedule about that centre
         return _weighted_scalars(run(items, pov, thr, **cen, **kw), axes)
     ckw = consistency_kwargs(engine, params)
-    if ckw:   # params["hip_weights"] = "consistency": the device schedule under maps made from the chunk's own flow
+    if ckw:   # params["hip_weights"] = "consistency" / "residual": the device schedule under maps made from the chunk's own flow
         return _weighted_scalars(run(items, pov, thr, **ckw, **kw), axes)
     wts = static_weights(engine, params)
     if wts is not None:   # params["hip_weights"]: the device schedule under the static map

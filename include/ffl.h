@@ -39,6 +39,9 @@
  *   ffl_consistency_weights replaces nothing (the reference's detect_cut is dead and nothing in it weights pixels): the
  *                           forward-backward check of a pair's two fields as a weight map for ffl_pass1_weighted and
  *                           ffl_radial_window_axes_weighted
+ *   ffl_residual_weights    replaces nothing either: the photometric residual of a pair under its forward field (frame 1
+ *                           sampled where the flow lands, against frame 0 and its local gradient) as such a weight map; needs
+ *                           no backward field
  *   ffl_motion_fit, ffl_motion_subtract  replace nothing: the reference cancels global motion only by the quadrant weights
  *                           of radial_motion_weighted ("Cancel out global motion by balancing the averages", FF:779-783), which
  *                           cancel a pan only about the image centre.  These fit a per-pair camera model (translation, rigid,
@@ -647,6 +650,49 @@ int ffl_consistency_params_check(const ffl_consistency_params *p);
  * wait.  Flows and pass-1 records are only read.  No scratch memory: there is no *_extra_bytes call. */
 int ffl_consistency_weights(ffl_ctx *ctx, int n, const int *fwd_slots, const int *bwd_slots, const ffl_consistency_params *p,
                             const ffl_dev_weights *gate, const ffl_dev_weights *out, uint64_t stream);
+
+/* ---- Photometric-residual weight maps ----
+ * A second confidence map in the form rules W1 to W6 consume, which needs no backward field: follow the forward flow F (pair
+ * f0 -> f1, components u, v) from a pixel of frame 0, sample frame 1 there bilinearly, and see how well the grey values agree,
+ * measured against the local gradient of frame 0.  I0 and I1 are the uint8 gray operands in frame slots f0 and f1, F a
+ * resident flow slot, all of the context's size w x h.  All arithmetic is float32 unless stated otherwise, one rounding per
+ * written operation, no contraction; integer steps are exact.  For pixel (x, y):
+ *   P1  landing: px = (float)x + u, py = (float)y + v; inside = px >= 0 && px <= (float)(w-1) && py >= 0 && py <= (float)(h-1)
+ *       (a NaN or inf fails the test).  Not inside: W = 0, and nothing of I1 is read for that pixel.
+ *   P2  sample: x0 = (int)floorf(px), x1 = min(x0 + 1, w - 1), ax = px - floorf(px), the same in y.  The corners
+ *       i00 = I1[y0][x0], i01 = I1[y0][x1], i10 = I1[y1][x0], i11 = I1[y1][x1] are converted to float exactly;
+ *       t = i00 + ax*(i01 - i00), s = i10 + ax*(i11 - i10), ic = t + ay*(s - t).
+ *   P3  a = fabsf(ic - (float)I0[y][x]);  gx = I0[y][min(x+1,w-1)] - I0[y][max(x-1,0)] and
+ *       gy = I0[min(y+1,h-1)][x] - I0[max(y-1,0)][x], both as integers;  g = fabsf((float)gx) + fabsf((float)gy);
+ *       thr = alpha*g + beta.
+ *   P4  soft = 1: q = 1 - a / thr; q = q > 0 ? q : 0 (a select: a NaN gives 0); W = (int)(q*255 + 0.5f).
+ *   P5  soft = 0: W = a < thr ? 255 : 0.  No division is executed.
+ *   P6  with a gate map S (a weight descriptor, the rules of any map): W = min(W, S).
+ * Accepted: 0 <= alpha <= 16, 0 < beta <= 255, both finite, soft in {0, 1}; the defaults are 0.5, 4, 1.  The defaults are
+ * the project's own choice and are NOT tuned on footage.  Non-finite fields follow the IEEE result of these expressions. */
+typedef struct ffl_residual_params {
+    float alpha, beta;
+    int soft;
+} ffl_residual_params;
+int ffl_residual_default_params(ffl_residual_params *out);
+/* Pure host check: no device or context needed.  FFL_ERR_INVALID with the rule in ffl_last_error(NULL). */
+int ffl_residual_params_check(const ffl_residual_params *p);
+
+/* The maps of n pairs: item i is made from the frames in frame slots fslot0[i] and fslot1[i] and the forward field in flow slot
+ * flow_slots[i].  `out`, `gate` and p are ffl_consistency_weights' (gate: the maps S of rule P6).  Refused before any device
+ * work, each with its rule in the message: n outside 1..max_batch; a NULL list; a flow slot out of range or repeated, or one
+ * that holds no flow (FFL_ERR_STATE); a frame slot out of range, or one that was never uploaded (FFL_ERR_STATE) -- frame slots
+ * MAY repeat between items (frame j+1 of pair j is frame j of pair j+1); any rule of ffl_residual_params_check; any rule of
+ * ffl_dev_weights_check for out and for gate; out with item_stride == 0 when n > 1; out or gate that is not device memory of
+ * the context's device inside one allocation; out overlapping gate; a capturing `stream` (FFL_ERR_STATE).
+ * ffl_consistency_weights' protocol: ONE k_residual launch, queued on the library's stream behind the work queued on `stream`,
+ * the uploads that filled the frame slots and the last users of the n flow slots; `stream` then waits for it, so the maps may
+ * be read, and the gate overwritten, on `stream` straight after the call; never captured; the host does not wait.  It counts
+ * as a use of the n flow slots AND of the frame slots it reads: a later upload into one of those frame slots is ordered behind
+ * it, as behind a flow call.  Frames, flows and pass-1 records are only read.  No scratch memory: there is no *_extra_bytes
+ * call. */
+int ffl_residual_weights(ffl_ctx *ctx, int n, const int *fslot0, const int *fslot1, const int *flow_slots,
+                         const ffl_residual_params *p, const ffl_dev_weights *gate, const ffl_dev_weights *out, uint64_t stream);
 
 /* ---- Per-cell flow statistics and the variance centre ----
  * center_of_mass_variance(flow, num_cells) of FF:721-746 and the grid it is formed from, on resident flow fields.  With
