@@ -547,6 +547,38 @@ def residual_choice(params):
     return params
 
 
+class TextureParams(C.Structure):
+    """ffl_texture_params: the window radius r (1..8, the window is (2r+1)^2), tau, the cornerness per
+    window pixel at which the weight saturates (soft) or switches (hard), and soft 1 (a ramp) or 0 (a threshold).
+    TextureParams() holds the library's defaults (the project's own choice, not tuned on footage); keywords override single
+    fields."""
+    _fields_ = [("radius", C.c_int), ("tau", C.c_float), ("soft", C.c_int)]
+
+    def __init__(self, **over):
+        super().__init__()
+        load().ffl_texture_default_params(C.byref(self))
+        for k, v in over.items():
+            if k not in ("radius", "tau", "soft"):
+                raise ValueError(f"unknown texture parameter {k!r} (radius, tau, soft)")
+            setattr(self, k, v)
+
+    def as_dict(self):
+        return {"radius": self.radius, "tau": self.tau, "soft": self.soft}
+
+
+def texture_params_check(params):
+    """ffl_texture_params_check: ValueError with the library's rule when it refuses (pure host check)."""
+    _check(load().ffl_texture_params_check(None if params is None else C.byref(params)), exc=ValueError)
+
+
+def texture_choice(params):
+    """a TextureParams out of None or True (the defaults), a dict of its fields or a TextureParams; checked"""
+    if not isinstance(params, TextureParams):
+        params = TextureParams(**dict({} if params is None or params is True else params))
+    texture_params_check(params)
+    return params
+
+
 class MotionParams(C.Structure):
     """ffl_motion_params: the sub-model of rule C2 (a name of MOTION_MODELS or its code), the passes of
     rule C7 and the Cauchy scale tau of rule C3 in pixels.  MotionParams() holds the library's defaults (rule C9: translation,
@@ -772,6 +804,9 @@ SIGNATURES = {
     "ffl_residual_default_params": (_i, (_P(ResidualParams),)),
     "ffl_residual_params_check": (_i, (_P(ResidualParams),)),
     "ffl_residual_weights": (_i, (_ctx, _i, _ip, _ip, _ip, _P(ResidualParams), _P(DevWeights), _P(DevWeights), _u64)),
+    "ffl_texture_default_params": (_i, (_P(TextureParams),)),
+    "ffl_texture_params_check": (_i, (_P(TextureParams),)),
+    "ffl_texture_weights": (_i, (_ctx, _i, _ip, _P(TextureParams), _P(DevWeights), _P(DevWeights), _u64)),
     "ffl_cell_grid_check": (_i, (_i,) * 3 + (_ip, _ip)),
     "ffl_cell_stats": (_i, (_ctx, _i, _ip, _i, _vp, _vp, _u64)),
     "ffl_radial_window_axes_centres": (_i, _WINDOW + (_vp, _pd, _vp, _u64)),
@@ -814,7 +849,7 @@ EXPORTS = list(SIGNATURES)   # every symbol include/ffl.h declares
 # the header's records and their Python statements (the test takes the struct names from the header: none can be forgotten)
 RECORDS = {"ffl_source_info": SourceInfo, "ffl_dev_frame": DevFrame, "ffl_dev_flow": DevFlow, "ffl_pass2_record": PASS2_DTYPE,
            "ffl_axes_record": PASS2_AXES_DTYPE, "ffl_dev_weights": DevWeights, "ffl_consistency_params": ConsistencyParams,
-           "ffl_residual_params": ResidualParams,
+           "ffl_residual_params": ResidualParams, "ffl_texture_params": TextureParams,
            "ffl_cell_record": CELL_DTYPE, "ffl_grid_centre": GRID_CENTRE_DTYPE, "ffl_motion_params": MotionParams,
            "ffl_motion_record": MOTION_DTYPE, "ffl_dis_params": DisParams,
            "ffl_farneback_params": FarnebackParams}
@@ -1386,6 +1421,22 @@ class Context:
         gdesc = None if gate is None else self._weights("residual_weights", gate, len(fl))
         self._chk(self.L.ffl_residual_weights(self._h, len(fl), p0, p1, pf, C.byref(prm), None if gdesc is None else C.byref(gdesc),
                                               C.byref(odesc), stream_handle(stream, self.device)))
+        return out
+
+    def texture_weights(self, fslots, out, params=None, gate=None, stream=None):
+        """Texture (structure-tensor) maps (ffl_texture_weights): item i from the gray frame in frame slot
+        fslots[i] (slots may repeat between items; for a pair, its frame 0), written into `out`, a uint8 device tensor
+        (n, H, W) (or a DevWeights; (H, W) for one item).  `params`: a TextureParams, a dict of its fields or None (the
+        defaults, which are not tuned on footage); `gate`: maps S of rule T6 as pass1_weighted takes maps, (H, W) or (n, H, W)
+        -- or `out` itself, which min-combines the texture into the maps that are already there, in place.  Queued behind the
+        work on `stream` and the frames' uploads; `stream` waits for it, and a later upload into one of the frame slots runs
+        behind it.  Returns `out`."""
+        pf, fs = _iarr(fslots)
+        prm = params if isinstance(params, TextureParams) else TextureParams(**dict({} if params is None or params is True else params))
+        odesc = self._weights("texture_weights", out, len(fs))
+        gdesc = None if gate is None else odesc if gate is out else self._weights("texture_weights", gate, len(fs))
+        self._chk(self.L.ffl_texture_weights(self._h, len(fs), pf, C.byref(prm), None if gdesc is None else C.byref(gdesc),
+                                             C.byref(odesc), stream_handle(stream, self.device)))
         return out
 
     def cell_stats(self, flow_slots, cells=32, cells_out=None, centres_out=None, stream=None):

@@ -292,7 +292,7 @@ struct ffl_ctx {
     std::vector<EvRef> ev_uploaded;  // per frame slot: the upload call that filled it (one event per call, up_ring)
     EvRing up_ring;                  // 2 * FFL_EV_RING entries
     // [frame slot * frame_readers() + r]: the last reader of the slot on stream r -- r < n_lanes: that lane's last batch (the
-    // lane's ring); r = n_lanes: the last ffl_residual_weights call, on stream `post` (post_ring).  An upload waits for all
+    // lane's ring); r = n_lanes: the last ffl_residual_weights or ffl_texture_weights call, on stream `post` (post_ring).  An upload waits for all
     std::vector<EvRef> ev_last_use;
     size_t frame_readers() const { return lanes.size() + 1; }
     std::vector<char> frame_valid;
@@ -2469,6 +2469,27 @@ static int post_end(ffl_ctx *c, hipStream_t cst, int n, const int *slots) {
     return FFL_OK;
 }
 
+// post_end() for a call that also read frame slots on stream `post` (ffl_residual_weights, ffl_texture_weights): its event
+// becomes the last reader on stream `post` of the nf slots of fs0 and (unless NULL) fs1 -- ev_last_use's last column, which
+// every later upload into one of them waits for (wait_frame_free).  The reader is recorded whether or not post_end succeeds:
+// an event of its own if post_end recorded none, so that a launch that was queued is never overtaken by an upload (if even that
+// fails the stream is drained).
+static int post_end_frames(ffl_ctx *c, hipStream_t cst, int n, const int *slots, int nf, const int *fs0, const int *fs1) {
+    const unsigned long long before = c->post_ring.next;
+    const int rc = post_end(c, cst, n, slots);
+    EvRef done = ev_latest(c->post_ring);
+    if (c->post_ring.next == before && c->post_ring.record(c->s_post, &done) != hipSuccess) {
+        (void)hipStreamSynchronize(c->s_post);
+        done = EvRef{};
+    }
+    const size_t nr = c->frame_readers();
+    for (int i = 0; i < nf; i++) {
+        c->ev_last_use[(size_t)fs0[i] * nr + (nr - 1)] = done;
+        if (fs1) c->ev_last_use[(size_t)fs1[i] * nr + (nr - 1)] = done;
+    }
+    return rc;
+}
+
 int ffl_dev_frame_check(int format, int sw, int sh, const ffl_dev_frame *f, int rw, int rh, int cx, int cy, int out_w, int out_h) {
     FrontParams p;
     return dev_frame_check(nullptr, "ffl_dev_frame_check", 0, format, 1, 8, sw, sh, f, nullptr, rw, rh, cx, cy, out_w, out_h, &p);
@@ -3052,21 +3073,83 @@ int ffl_residual_weights(ffl_ctx *c, int n, const int *fslot0, const int *fslot1
     if (gate) ga = WeightArgs{(const char *)gate->base, (long long)gate->item_stride, (long long)gate->row_pitch};
     ffl_launch_residual(c->d_gray, c->d_flow, t0, t1, tf, n, c->w, c->h, prm.alpha, prm.beta, prm.soft, gate ? &ga : nullptr,
                         (char *)out->base, (long long)out->item_stride, (long long)out->row_pitch, c->s_post);
-    // The frame slots' reader is recorded whether or not post_end succeeds: an event of its own if post_end recorded none, so
-    // that a launch that was queued is never overtaken by an upload (if even that fails the stream is drained)
-    const unsigned long long before = c->post_ring.next;
-    const int rc = post_end(c, cst, n, flow_slots);
-    EvRef done = ev_latest(c->post_ring);
-    if (c->post_ring.next == before && c->post_ring.record(c->s_post, &done) != hipSuccess) {
-        (void)hipStreamSynchronize(c->s_post);
-        done = EvRef{};
+    // the caller may read the maps, or overwrite the gate, on `stream` straight after the call
+    return post_end_frames(c, cst, n, flow_slots, n, fslot0, fslot1);
+}
+
+// ---- texture (structure-tensor) maps --------------------------------------------------
+int ffl_texture_default_params(ffl_texture_params *out) {
+    if (!out) return FFL_ERR_INVALID;
+    *out = ffl_texture_params{7, 16.0f, 1};   // the project's own choice, not tuned on footage
+    return FFL_OK;
+}
+
+// The accepted parameters of appendix T.  The comparisons are written so that a NaN fails them.
+static int texture_params_check(ffl_ctx *c, const char *fn, const ffl_texture_params *p) {
+    if (!p) return set_err(c, FFL_ERR_INVALID, "%s: NULL parameters", fn);
+    if (p->radius < 1 || p->radius > 8) return set_err(c, FFL_ERR_INVALID, "%s: radius = %d outside 1..8", fn, p->radius);
+    if (!(p->tau > 0.0f && p->tau <= 65025.0f))
+        return set_err(c, FFL_ERR_INVALID, "%s: tau = %g outside 0 < tau <= 65025 (finite)", fn, (double)p->tau);
+    if (p->soft != 0 && p->soft != 1) return set_err(c, FFL_ERR_INVALID, "%s: soft = %d is neither 0 (hard) nor 1 (soft)", fn, p->soft);
+    return FFL_OK;
+}
+
+int ffl_texture_params_check(const ffl_texture_params *p) {
+    return texture_params_check(nullptr, "ffl_texture_params_check", p);
+}
+
+// n maps from n frames by ONE k_texture launch on stream `post`: ffl_residual_weights' protocol without the flow slots -- stream
+// `post` runs behind the caller's queued work and the uploads that filled the frame slots, and the call's event becomes their
+// last reader on stream `post`.  gate may be exactly out (same base, item stride and row pitch): the in-place form, in which
+// the lane that owns a pixel reads its gate byte and then writes it.
+int ffl_texture_weights(ffl_ctx *c, int n, const int *fslots, const ffl_texture_params *p, const ffl_dev_weights *gate,
+                        const ffl_dev_weights *out, uint64_t stream) {
+    static const char *fn = "ffl_texture_weights";
+    if (!c) return FFL_ERR_INVALID;
+    std::unique_lock<std::mutex> pl(c->post_mu);  // stream `post`, as ffl_residual_weights
+    CtxLock lk(c->mu);
+    if (n < 1 || n > c->max_batch)
+        return set_err(c, FFL_ERR_INVALID, "%s: n = %d items outside 1..%d (the context's max_batch)", fn, n, c->max_batch);
+    if (!fslots) return set_err(c, FFL_ERR_INVALID, "%s: NULL fslots", fn);
+    ExportTab tf;
+    for (int i = 0; i < n; i++) {   // frame slots may repeat between items
+        const int fs = fslots[i];
+        if (fs < 0 || fs >= c->n_fslots) return set_err(c, FFL_ERR_INVALID, "%s: item %d: frame slot %d out of range", fn, i, fs);
+        if (!c->frame_valid[fs]) return set_err(c, FFL_ERR_STATE, "%s: item %d: frame slot %d was never uploaded", fn, i, fs);
+        tf.slot[i] = fs;
     }
-    const size_t nr = c->frame_readers();
-    for (int i = 0; i < n; i++) {
-        c->ev_last_use[(size_t)fslot0[i] * nr + (nr - 1)] = done;
-        c->ev_last_use[(size_t)fslot1[i] * nr + (nr - 1)] = done;
+    ffl_texture_params prm;
+    ffl_texture_default_params(&prm);
+    if (p) prm = *p;
+    if (int rc = texture_params_check(c, fn, &prm)) return rc;
+    size_t obytes, gbytes = 0;
+    if (!out) return set_err(c, FFL_ERR_INVALID, "%s: NULL out descriptor", fn);
+    if (int rc = dev_weights_check(c, fn, n, c->w, c->h, out, &obytes)) return rc;
+    if (n > 1 && out->item_stride == 0)
+        return set_err(c, FFL_ERR_INVALID, "%s: overlap: out item stride 0 with n = %d maps to write (one map per item)", fn, n);
+    bool in_place = false;
+    if (gate) {
+        if (int rc = dev_weights_check(c, fn, n, c->w, c->h, gate, &gbytes)) return rc;
+        in_place = gate->base == out->base && gate->item_stride == out->item_stride && gate->row_pitch == out->row_pitch;
+        const uintptr_t o0 = (uintptr_t)out->base, g0 = (uintptr_t)gate->base;
+        if (!in_place && o0 < g0 + gbytes && g0 < o0 + obytes)
+            return set_err(c, FFL_ERR_INVALID, "%s: overlap: out (%zu bytes) and gate (%zu bytes) share memory, and gate is not "
+                                               "exactly out (same base, item stride and row pitch: the in-place form)",
+                           fn, obytes, gbytes);
     }
-    return rc;  // the caller may read the maps, or overwrite the gate, on `stream` straight after the call
+    hipStream_t cst;
+    PostRegion reg[2] = {{"out", out->base, obytes, kHostWeights}, {"the gate maps", gate ? gate->base : nullptr, gbytes, kHostWeights}};
+    if (int rc = post_begin(c, fn, stream, &cst, reg, gate && !in_place ? 2 : 1, 0, nullptr)) return rc;
+    {
+        WaitOnce wait_post(c->s_post);   // the frames: a run of slots shares one upload event
+        for (int i = 0; i < n; i++) HIPCHK(c, wait_post(c->ev_uploaded[fslots[i]].get()));
+    }
+    WeightArgs ga;
+    if (gate) ga = WeightArgs{(const char *)gate->base, (long long)gate->item_stride, (long long)gate->row_pitch};
+    ffl_launch_texture(c->d_gray, tf, n, c->w, c->h, prm.radius, prm.tau, prm.soft, gate ? &ga : nullptr, (char *)out->base,
+                       (long long)out->item_stride, (long long)out->row_pitch, c->s_post);
+    // the caller may read the maps, or overwrite the gate, on `stream` straight after the call
+    return post_end_frames(c, cst, 0, nullptr, n, fslots, nullptr);
 }
 
 static const char *kHostCentres ="centres live in device memory (ffl_cell_stats' records, or a float64 (n_seq, 2) tensor)";

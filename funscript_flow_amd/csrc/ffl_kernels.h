@@ -323,6 +323,12 @@ void ffl_launch_residual(const unsigned char *gray, const float *flow, const Exp
                          int n, int w, int h, float alpha, float beta, int soft, const WeightArgs *gate, char *out,
                          long long out_item, long long out_pitch, hipStream_t st);
 
+// texture (structure-tensor) maps (k_texture): item b's map, from the gray frame in frame slot
+// fr.slot[b] of `gray` (w * h bytes each), goes to out + b * out_item, rows out_pitch bytes apart; radius 1..8 (host-checked)
+// picks the instantiation; gate (may be NULL): the maps of rule T6, which may be exactly `out` (min-combined in place)
+void ffl_launch_texture(const unsigned char *gray, const ExportTab &fr, int n, int w, int h, int radius, float tau, int soft,
+                        const WeightArgs *gate, char *out, long long out_item, long long out_pitch, hipStream_t st);
+
 // ---- global-motion fit and compensation (kernels_post.hip) -----------------------
 #define FFL_MOTION_NSUMS 12          // = FFL_MOTION_N_SUMS of include/ffl.h; the order of rule C4
 enum { MOT_S = 0, MOT_SX, MOT_SY, MOT_SXX, MOT_SXY, MOT_SYY, MOT_SU, MOT_SUX, MOT_SUY, MOT_SV, MOT_SVX, MOT_SVY };

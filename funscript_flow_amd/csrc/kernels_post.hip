@@ -1394,3 +1394,163 @@ void ffl_launch_motion_subtract(float *flow, Pass1Result *res, const ExportTab &
     dim3 grid((unsigned)((units + 256 * FFL_EXP_UNROLL - 1) / (256 * FFL_EXP_UNROLL)), n);
     hipLaunchKernelGGL(k_motion_subtract, grid, dim3(256), 0, st, flow, res, src, dst, w, h, models, stride, vec, pt);
 }
+
+// ---- texture (structure-tensor) maps ---------------------------------------------
+// (This section stands at the end of the file on purpose: the kernels above keep the order, and with it the offsets inside the
+// code object, that they had before it was added.  With it behind k_residual the plain 1080p chunk, which launches none of it,
+// ran 3 % low against the parent build; here it does not: profiles/texture_unchanged_paths.md.)
+// k_texture writes one uint8 weight per pixel from the gray operand I of one frame slot: Noble's cornerness det / tr of the
+// structure tensor summed over a (2R+1)^2 window, against tau.  Unlike its two siblings it has a stencil, so it goes through
+// LDS.  grid = (tiles per item, items); a workgroup of 256 lanes owns a tile of 64 x 16 output pixels and runs four steps
+// with a barrier between them:
+//   1  the tile's gray bytes plus a halo of R + 1, (66 + 2R) x (18 + 2R), read once from global memory at clamped coordinates;
+//   2  (gx, gy) of rule T1 at every position of the (64 + 2R) x (16 + 2R) window region, taken AT THE CLAMPED POSITION (rule T2
+//      -- not the gradient of the clamped image, which would be 0 outside the frame), packed as two int16 in one dword;
+//   3  per row of that region and quad of columns the three horizontal window sums: 4 + 2R packed gradients come in as
+//      ceil((4 + 2R) / 4) 16-byte LDS reads (conflict-free: consecutive lanes read consecutive 16 bytes), the first window is
+//      summed, the other three slide; three int4 go out;
+//   4  lane (quad, row) adds the 2R + 1 rows above and below as int4, applies T3 to T6 and stores 4 bytes where the address
+//      allows and bytes otherwise, as k_residual does.
+// The sums are integers, so their order is free (rule T2) and the bits do not depend on R being a template parameter.  det is
+// a 64-bit product (rule T3: at R = 8 Sxx * Syy reaches 3.5e14).  gate may alias out exactly (ffl_texture_weights' in-place
+// form): a lane reads the gate bytes of its own quad before it writes them, so out carries no __restrict__.
+#define FFL_TEX_TW 64
+#define FFL_TEX_TH 16
+
+template <int R>
+__global__ __launch_bounds__(256) void k_texture(const unsigned char *__restrict__ gray, ExportTab fr, int w, int h, int tiles_x,
+                                                 double tn, int soft, WeightArgs gate, char *out, long long out_item,
+                                                 long long out_pitch) {
+    constexpr int TW = FFL_TEX_TW, TH = FFL_TEX_TH;
+    constexpr int GW = TW + 2 * R + 2, GH = TH + 2 * R + 2, GP = (GW + 3) & ~3;   // gray tile and its pitch in bytes
+    constexpr int PW = TW + 2 * R, PH = TH + 2 * R;                               // window region
+    constexpr int NV = (4 + 2 * R + 3) / 4;                                       // 16-byte reads per quad in step 3
+    constexpr int PP = TW - 4 + 4 * NV;                                           // pitch of the region in dwords, >= PW
+    __shared__ unsigned char s_gray[GH * GP];
+    __shared__ __attribute__((aligned(16))) unsigned s_grad[PH * PP];
+    __shared__ __attribute__((aligned(16))) int s_h[3][PH][TW];
+    const int tid = threadIdx.x, b = blockIdx.y;
+    const int ox = (int)(blockIdx.x % (unsigned)tiles_x) * TW, oy = (int)(blockIdx.x / (unsigned)tiles_x) * TH;
+    const unsigned char *I = gray + (size_t)fr.slot[b] * ((size_t)w * h);
+    // 1: gray, clamped: no access leaves the frame
+    for (int i = tid; i < GW * GH; i += 256) {
+        const int ty = i / GW, tx = i - ty * GW;
+        int sx = ox - (R + 1) + tx, sy = oy - (R + 1) + ty;
+        sx = sx < 0 ? 0 : sx > w - 1 ? w - 1 : sx;
+        sy = sy < 0 ? 0 : sy > h - 1 ? h - 1 : sy;
+        s_gray[ty * GP + tx] = I[(unsigned)sy * (unsigned)w + (unsigned)sx];
+    }
+    __syncthreads();
+    // 2: gradients at the clamped position.  The region contains a pixel of the frame (the tile's origin), so the clamped
+    // position stays inside the region and its four neighbours inside the gray tile.
+    for (int i = tid; i < PW * PH; i += 256) {
+        const int py = i / PW, px = i - py * PW;
+        int X = ox - R + px, Y = oy - R + py;
+        X = X < 0 ? 0 : X > w - 1 ? w - 1 : X;
+        Y = Y < 0 ? 0 : Y > h - 1 ? h - 1 : Y;
+        const int tx = X - (ox - (R + 1)), ty = Y - (oy - (R + 1));   // 1 <= tx <= GW - 2, 1 <= ty <= GH - 2
+        const int gx = (int)s_gray[ty * GP + tx + 1] - (int)s_gray[ty * GP + tx - 1];
+        const int gy = (int)s_gray[(ty + 1) * GP + tx] - (int)s_gray[(ty - 1) * GP + tx];
+        s_grad[py * PP + px] = ((unsigned)gx & 0xffffu) | ((unsigned)gy << 16);
+    }
+    __syncthreads();
+    // 3: horizontal window sums of gx^2, gx*gy, gy^2 for the quad's four columns
+    for (int t = tid; t < PH * (TW / 4); t += 256) {
+        const int q = t & (TW / 4 - 1), j = t / (TW / 4);
+        unsigned g[4 * NV];
+#pragma unroll
+        for (int m = 0; m < NV; m++) {
+            const uint4 v = *(const uint4 *)&s_grad[j * PP + 4 * q + 4 * m];   // words past 4q + 3 + 2R are read and never used
+            g[4 * m] = v.x, g[4 * m + 1] = v.y, g[4 * m + 2] = v.z, g[4 * m + 3] = v.w;
+        }
+        int sxx[4], sxy[4], syy[4];   // only the packed words stay in registers: the products are formed where they are added
+        sxx[0] = sxy[0] = syy[0] = 0;
+#pragma unroll
+        for (int k = 0; k <= 2 * R; k++) {
+            const int gx = (int)(short)(g[k] & 0xffffu), gy = (int)g[k] >> 16;
+            sxx[0] += gx * gx, sxy[0] += gx * gy, syy[0] += gy * gy;
+        }
+#pragma unroll
+        for (int k = 1; k < 4; k++) {
+            const int ax = (int)(short)(g[k - 1] & 0xffffu), ay = (int)g[k - 1] >> 16;               // leaves the window
+            const int bx = (int)(short)(g[k + 2 * R] & 0xffffu), by = (int)g[k + 2 * R] >> 16;       // enters it
+            sxx[k] = sxx[k - 1] - ax * ax + bx * bx;
+            sxy[k] = sxy[k - 1] - ax * ay + bx * by;
+            syy[k] = syy[k - 1] - ay * ay + by * by;
+        }
+        *(int4 *)&s_h[0][j][4 * q] = make_int4(sxx[0], sxx[1], sxx[2], sxx[3]);
+        *(int4 *)&s_h[1][j][4 * q] = make_int4(sxy[0], sxy[1], sxy[2], sxy[3]);
+        *(int4 *)&s_h[2][j][4 * q] = make_int4(syy[0], syy[1], syy[2], syy[3]);
+    }
+    __syncthreads();
+    // 4: vertical sums, T3 to T6, the store
+    const int q = tid & (TW / 4 - 1), ly = tid / (TW / 4);
+    const int x = ox + 4 * q, y = oy + ly;
+    if (x >= w || y >= h) return;
+    int4 a = make_int4(0, 0, 0, 0), c = a, d = a;
+#pragma unroll 3   // a full unroll keeps all 3 * (2R + 1) int4 in flight: 196 VGPRs at R = 7 against 2 waves per SIMD
+    for (int j = 0; j <= 2 * R; j++) {
+        const int4 u = *(const int4 *)&s_h[0][ly + j][4 * q], v = *(const int4 *)&s_h[1][ly + j][4 * q],
+                   z = *(const int4 *)&s_h[2][ly + j][4 * q];
+        a.x += u.x, a.y += u.y, a.z += u.z, a.w += u.w;
+        c.x += v.x, c.y += v.y, c.z += v.z, c.w += v.w;
+        d.x += z.x, d.y += z.y, d.z += z.z, d.w += z.w;
+    }
+    const int Sxx[4] = {a.x, a.y, a.z, a.w}, Sxy[4] = {c.x, c.y, c.z, c.w}, Syy[4] = {d.x, d.y, d.z, d.w};
+    const int np = w - x < 4 ? w - x : 4;   // pixels of this quad
+    unsigned wt[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int tr = Sxx[k] + Syy[k];                                                               // T3
+        const long long det = (long long)Sxx[k] * (long long)Syy[k] - (long long)Sxy[k] * (long long)Sxy[k];
+        if (!soft) {
+            wt[k] = (double)det >= tn * (double)tr && tr != 0 ? 255u : 0u;                            // T5: no division
+        } else if (tr == 0) {
+            wt[k] = 0u;
+        } else {
+            double qv = ((double)det / (double)tr) / tn;                                              // T4
+            qv = qv < 1.0 ? qv : 1.0;
+            wt[k] = (unsigned)(int)(qv * 255.0 + 0.5);
+        }
+    }
+    if (gate.base) {   // T6
+        const unsigned char *g = (const unsigned char *)gate.base + (long long)b * gate.item + (long long)y * gate.pitch + x;
+        if (np == 4 && ((uintptr_t)g & 3) == 0) {
+            const unsigned s = *(const unsigned *)g;
+#pragma unroll
+            for (int k = 0; k < 4; k++) wt[k] = min(wt[k], (s >> (8 * k)) & 255u);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (k < np) wt[k] = min(wt[k], (unsigned)g[k]);
+        }
+    }
+    unsigned char *o = (unsigned char *)out + (long long)b * out_item + (long long)y * out_pitch + x;
+    if (np == 4 && ((uintptr_t)o & 3) == 0) {
+        *(unsigned *)o = wt[0] | (wt[1] << 8) | (wt[2] << 16) | (wt[3] << 24);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (k < np) o[k] = (unsigned char)wt[k];
+    }
+}
+
+template <int R>
+static void ffl_launch_texture_r(const unsigned char *gray, const ExportTab &fr, int n, int w, int h, double tn, int soft,
+                                 const WeightArgs &g, char *out, long long out_item, long long out_pitch, hipStream_t st) {
+    const int tx = (w + FFL_TEX_TW - 1) / FFL_TEX_TW, ty = (h + FFL_TEX_TH - 1) / FFL_TEX_TH;   // at most 512 * 2048 tiles
+    hipLaunchKernelGGL(k_texture<R>, dim3((unsigned)tx * (unsigned)ty, n), dim3(256), 0, st, gray, fr, w, h, tx, tn, soft, g, out,
+                       out_item, out_pitch);
+}
+
+void ffl_launch_texture(const unsigned char *gray, const ExportTab &fr, int n, int w, int h, int radius, float tau, int soft,
+                        const WeightArgs *gate, char *out, long long out_item, long long out_pitch, hipStream_t st) {
+    const WeightArgs g = gate ? *gate : WeightArgs{nullptr, 0, 0};
+    const double tn = (double)tau * (double)((2 * radius + 1) * (2 * radius + 1));   // rule T4's tn, formed once
+    switch (radius) {   // 1..8, host-checked
+#define FFL_TEX_CASE(R) \
+    case R: ffl_launch_texture_r<R>(gray, fr, n, w, h, tn, soft, g, out, out_item, out_pitch, st); break;
+        FFL_TEX_CASE(1) FFL_TEX_CASE(2) FFL_TEX_CASE(3) FFL_TEX_CASE(4) FFL_TEX_CASE(5) FFL_TEX_CASE(6) FFL_TEX_CASE(7) FFL_TEX_CASE(8)
+#undef FFL_TEX_CASE
+    }
+}

@@ -367,7 +367,7 @@ class PairEngine:
 
     def process_chunk(self, frames, pov_mode=False, cut_threshold=7.0, algo=None, farneback=OWN, flows_out=None, window=OWN,
                       post_out=None, axes=False, weights=None, center=None, cells=32, grid_out=None, consistency=None,
-                      weights_out=None, weights_gate=None, compensate=None, motion_out=None, residual=None):
+                      weights_out=None, weights_gate=None, compensate=None, motion_out=None, residual=None, texture=None):
         """One whole chunk on one GPU: returns (dots float64[n], records) with n = len(frames)-1.  `algo`, `farneback`,
         `window`: see pass1_pairs (default: the engine's own flow algorithm, parameters and window).  `flows_out`: a float32 device array of
         (n, H, W, 2) or (n, 2, H, W) that receives every pair's flow field (Context.export_flows, on torch's current stream)
@@ -401,6 +401,15 @@ class PairEngine:
         footage; `weights_gate`: the static gate of rule P6; `weights_out` as above).  The batch stays max_batch pairs and the
         ring every flow slot, nothing is queued reversed: behind each batch's flow call Context.residual_weights writes the
         batch's maps from its frame slots and raw fields, then the calls of `weights` run.
+        `weights` = "texture": the maps are the structure-tensor cornerness of every pair's frame 0 (DESIGN.md section 22;
+        `texture`: a _capi.TextureParams, a dict of its fields or None for the defaults, which are not tuned on footage;
+        `weights_gate`: the static gate of rule T6; `weights_out` as above) -- low on flat regions and pure stripes, where the
+        flow is unconstrained and both checks above approve of it.  The schedule is that of "residual", with
+        Context.texture_weights on the batch's f0 slots; it combines with compensate= in the same order.
+        `weights` = "residual" with `texture` (parameters, or True for the defaults): both.  Behind each batch the residual
+        maps are made from the raw fields, then Context.texture_weights min-combines frame 0's texture into them in place
+        (gate = out = the batch's maps), then the fit, the subtraction and the calls of `weights` run.  `texture` is refused
+        with weights="consistency" (that mode has no frames hook) and without a mode.
         `compensate`: a model name of _capi.MOTION_MODELS, a dict of _capi.MotionParams fields or a MotionParams (DESIGN.md
         section 19).  Behind each batch, and before anything reads its records or fields, Context.motion_fit is queued on the
         batch's slots -- under `weights` when that is a map -- and then Context.motion_subtract in place: pass 1, pass 2,
@@ -415,7 +424,7 @@ class PairEngine:
         if compensate is not None and isinstance(weights, str) and weights == "consistency":
             raise ValueError(f"compensate= together with weights={weights!r} is not supported: the consistency maps need both "
                              "raw directions of every pair, and the slot ring holds the reversed pairs")
-        resid = _chunk_residual(self, n, weights, residual, consistency, weights_out, weights_gate)
+        resid = _chunk_residual(self, n, weights, residual, consistency, weights_out, weights_gate, texture)
         cons = None if resid is not None else _chunk_consistency(self, n, weights, consistency, weights_out, weights_gate)
         if cons is not None:
             weights, B = cons.maps, cons.B
@@ -498,6 +507,9 @@ class PairEngine:
         if isinstance(weights, str) and weights == "residual":
             raise ValueError("process_flows: weights='residual' needs the frames, which a chunk of caller flows does not have; "
                              "Context.residual_weights serves callers who hold the frames in the context's frame slots")
+        if isinstance(weights, str) and weights == "texture":
+            raise ValueError("process_flows: weights='texture' needs the frames, which a chunk of caller flows does not have; "
+                             "Context.texture_weights serves callers who hold the frames in the context's frame slots")
         if isinstance(weights, str):
             raise ValueError(f"process_flows: weights={weights!r} needs the backward fields, which a chunk of caller flows does "
                              "not have; Context.consistency_weights serves callers with their own estimator")
@@ -567,6 +579,8 @@ def _chunk_weights(ctx, weights, n):
 # modes made from both flow directions of a pair, which halve the batch and exclude compensate=; MAP_MODES is every mode
 WEIGHT_MODES = ("consistency",)
 MAP_MODES = WEIGHT_MODES + ("residual",)
+FRAME_MAP_MODES = ("residual", "texture")       # made behind a batch from its frame slots (pass1_pairs' with_frames hook)
+ALL_MAP_MODES = MAP_MODES + ("texture",)        # every mode; MAP_MODES keeps the value its users know as well
 
 
 class _ChunkConsistency:
@@ -627,29 +641,58 @@ class _ChunkResidual:
     slot ring; with_frames(ls, js, f0, f1), pass1_pairs' hook, queues Context.residual_weights on the batch's frame slots and
     raw fields (the l-th pair in flow slot l % flow_slots), which writes the pairs' maps into the chunk's (n, H, W) uint8 device
     tensor `maps`.  params: the checked _capi.ResidualParams; gate: the static gate's _capi.DevWeights or None (its tensor
-    stays referenced); stream: where the call is queued (the device schedule sets its side stream)."""
+    stays referenced); stream: where the call is queued (the device schedule sets its side stream).  texture: None, or the
+    checked _capi.TextureParams of the combination -- Context.texture_weights is then queued behind the
+    residual call with gate = out = the batch's maps, which min-combines frame 0's texture into them in place."""
 
-    def __init__(self, engine, n, params, maps_out, gate):
+    def __init__(self, engine, n, params, maps_out, gate, texture=None):
         self.ctx = engine.ctx
         self.params = _capi.residual_choice(params)
+        self.texture = None if texture is None else _capi.texture_choice(texture)
         self.maps = _chunk_maps(self.ctx, n, maps_out)
         self.gate_tensor, self.gate = gate, _static_gate(self.ctx, gate)
         self.stream = None
 
     def with_frames(self, ls, js, f0, f1):
-        self.ctx.residual_weights(f0, f1, [l % self.ctx.flow_slots for l in ls], self.maps[js[0]:js[-1] + 1], self.params,
-                                  self.gate, self.stream)
+        maps = self.maps[js[0]:js[-1] + 1]
+        self.ctx.residual_weights(f0, f1, [l % self.ctx.flow_slots for l in ls], maps, self.params, self.gate, self.stream)
+        if self.texture is not None:
+            self.ctx.texture_weights(f0, maps, self.texture, maps, self.stream)
 
 
-def _chunk_residual(engine, n, weights, params, consistency, maps_out, gate):
-    """None unless weights is "residual"; residual= is refused without it, and consistency= with it"""
-    if not (isinstance(weights, str) and weights == "residual"):
-        if params is not None:
-            raise ValueError("residual= needs weights='residual'")
+class _ChunkTexture:
+    """What weights="texture" adds to a chunk of n pairs on `engine`: _ChunkResidual's form without a
+    flow -- with_frames queues Context.texture_weights on the batch's f0 slots (the frame the flow is defined on), which writes
+    the pairs' maps into `maps`.  params: the checked _capi.TextureParams; gate: the static gate of rule T6 or None."""
+
+    def __init__(self, engine, n, params, maps_out, gate):
+        self.ctx = engine.ctx
+        self.params = _capi.texture_choice(params)
+        self.maps = _chunk_maps(self.ctx, n, maps_out)
+        self.gate_tensor, self.gate = gate, _static_gate(self.ctx, gate)
+        self.stream = None
+
+    def with_frames(self, ls, js, f0, f1):
+        self.ctx.texture_weights(f0, self.maps[js[0]:js[-1] + 1], self.params, self.gate, self.stream)
+
+
+def _chunk_residual(engine, n, weights, params, consistency, maps_out, gate, texture=None):
+    """None unless weights is "residual" or "texture", the modes of FRAME_MAP_MODES; residual= is refused without "residual",
+    texture= without either, and consistency= with both.  texture= next to "residual" (parameters, or True for the defaults) is
+    the combination of the two maps."""
+    mode = weights if isinstance(weights, str) and weights in FRAME_MAP_MODES else None
+    if mode != "residual" and params is not None:
+        raise ValueError("residual= needs weights='residual'")
+    if mode is None:
+        if texture is not None:
+            raise ValueError("texture= needs weights='texture', or weights='residual' for the combination of the two maps"
+                             + (" (weights='consistency' has no frames hook to queue it from)" if isinstance(weights, str) and weights == "consistency" else ""))
         return None
     if consistency is not None:
-        raise ValueError("consistency= needs weights='consistency', not weights='residual' (its parameters are residual=)")
-    return _ChunkResidual(engine, n, params, maps_out, gate)
+        raise ValueError(f"consistency= needs weights='consistency', not weights={mode!r} (its parameters are {mode}=)")
+    if mode == "texture":
+        return _ChunkTexture(engine, n, texture, maps_out, gate)
+    return _ChunkResidual(engine, n, params, maps_out, gate, texture)
 
 
 def _frames_kw(resid):
@@ -944,18 +987,25 @@ def consistency_kwargs(engine, params):
     """The keywords of process_chunk when params["hip_weights"] names a mode of MAP_MODES -- params["hip_consistency"] (a dict
     of _capi.ConsistencyParams fields) and params["hip_weights_gate"] (a static (H, W) map) go with it -- else {}; the two
     further keys are refused without it.  With "residual" the parameters are params["hip_residual"] (a dict of
-    _capi.ResidualParams fields); each mode refuses the other's parameters."""
+    _capi.ResidualParams fields), with "texture" params["hip_texture"] (a dict of _capi.TextureParams fields); each mode refuses
+    the others' parameters, but for params["hip_texture"] next to "residual" (a dict, or True for the defaults): the
+    combination of the two maps."""
     mode = params.get("hip_weights")
     if not isinstance(mode, str):
         for key, needs in (("hip_consistency", "'consistency'"), ("hip_residual", "'residual'"),
+                           ("hip_texture", "'texture' (or 'residual', for the combination of the two maps)"),
                            ("hip_weights_gate", "'consistency' or 'residual'")):
             if params.get(key) is not None:
                 raise ValueError(f"{key} needs hip_weights = {needs}")
         return {}
-    own, other = ("residual", "consistency") if mode == "residual" else ("consistency", "residual")
-    if params.get("hip_" + other) is not None:
-        raise ValueError(f"hip_{other} needs hip_weights = {other!r}, got {mode!r}")
-    return {"weights": mode, own: params.get("hip_" + own), "weights_gate": _static_map(engine, params, "hip_weights_gate")}
+    own = mode if mode in FRAME_MAP_MODES else "consistency"
+    for other in ("consistency", "residual", "texture"):
+        if other != own and (own, other) != ("residual", "texture") and params.get("hip_" + other) is not None:
+            raise ValueError(f"hip_{other} needs hip_weights = {other!r}, got {mode!r}")
+    kw = {"weights": mode, own: params.get("hip_" + own), "weights_gate": _static_map(engine, params, "hip_weights_gate")}
+    if own == "residual" and params.get("hip_texture") is not None:
+        kw["texture"] = params["hip_texture"]
+    return kw
 
 
 def center_kwargs(params):
@@ -985,6 +1035,9 @@ def _flow_chunks(engine, chunk_flows, fps, total_frames, params, axes, who):
     if isinstance(params.get("hip_weights"), str) and params["hip_weights"] == "residual":
         raise ValueError(f"{who}: hip_weights = 'residual' needs the frames, which caller flows do not have; "
                          "Context.residual_weights serves callers who hold the frames in the context's frame slots")
+    if isinstance(params.get("hip_weights"), str) and params["hip_weights"] == "texture":
+        raise ValueError(f"{who}: hip_weights = 'texture' needs the frames, which caller flows do not have; "
+                         "Context.texture_weights serves callers who hold the frames in the context's frame slots")
     if isinstance(params.get("hip_weights"), str):
         raise ValueError(f"{who}: hip_weights = {params['hip_weights']!r} needs the backward fields, which caller flows do not "
                          "have; Context.consistency_weights serves callers with their own estimator")

@@ -42,6 +42,10 @@
  *   ffl_residual_weights    replaces nothing either: the photometric residual of a pair under its forward field (frame 1
  *                           sampled where the flow lands, against frame 0 and its local gradient) as such a weight map; needs
  *                           no backward field
+ *   ffl_texture_weights     replaces nothing either: the local structure tensor of one frame (Noble's cornerness over a
+ *                           window) as such a weight map or as the gate of the two above -- low on flat regions and on pure
+ *                           stripes, where dense flow is unconstrained and both checks above approve of it; needs no flow
+ *                           at all
  *   ffl_motion_fit, ffl_motion_subtract  replace nothing: the reference cancels global motion only by the quadrant weights
  *                           of radial_motion_weighted ("Cancel out global motion by balancing the averages", FF:779-783), which
  *                           cancel a pan only about the image centre.  These fit a per-pair camera model (translation, rigid,
@@ -693,6 +697,52 @@ int ffl_residual_params_check(const ffl_residual_params *p);
  * call. */
 int ffl_residual_weights(ffl_ctx *ctx, int n, const int *fslot0, const int *fslot1, const int *flow_slots,
                          const ffl_residual_params *p, const ffl_dev_weights *gate, const ffl_dev_weights *out, uint64_t stream);
+
+/* ---- Texture (structure-tensor) weight maps ----
+ * A third confidence map in the form rules W1 to W6 consume, which needs no flow at all: the local structure tensor of one
+ * frame.  A flat region matches itself at any displacement and an edge or stripe pattern pins one flow component only (the
+ * aperture problem); the consistency and the residual check approve of both, this map does not.  I is the uint8 gray operand
+ * in one frame slot, of the context's size w x h.  All integer steps are exact; the float64 steps round once per written
+ * operation, left to right, no contraction.  For pixel (x, y):
+ *   T1  gradients, rule P3's clamped central differences, as integers:
+ *       gx = I[y][min(x+1,w-1)] - I[y][max(x-1,0)],  gy = I[min(y+1,h-1)][x] - I[max(y-1,0)][x].
+ *   T2  window sums Sxx = sum gx*gx, Sxy = sum gx*gy, Syy = sum gy*gy over the (2r+1)^2 offsets (i, j), |i|, |j| <= r, the
+ *       gradient taken AT the clamped position (min(max(x+i,0),w-1), min(max(y+j,0),h-1)); N = (2r+1)^2 always.  The sums fit
+ *       int32 (r = 8: at most 289 * 65025 = 18 792 225) and, being integers, have no order.
+ *   T3  tr = Sxx + Syy (int32); det = Sxx*Syy - Sxy*Sxy in 64-BIT integers (>= 0 by Cauchy-Schwarz, at most 3.6e14 < 2^53,
+ *       hence exact as a double).  tr == 0: c = 0 and no division is executed; otherwise c = (double)det / (double)tr, one IEEE
+ *       division.  This is Noble's measure l1*l2 / (l1 + l2) of the tensor's eigenvalues: between lmin/2 and lmin, 0 for a
+ *       flat patch and for a pure stripe pattern, no square root.
+ *   T4  soft = 1: tn = (double)tau * (double)N; q = c / tn; q = q < 1.0 ? q : 1.0; W = (int)(q*255.0 + 0.5).
+ *   T5  soft = 0: W = tr != 0 && (double)det >= tn * (double)tr ? 255 : 0.  No division is executed.
+ *   T6  with a gate map S (a weight descriptor, the rules of any map): W = min(W, S).
+ * Accepted: radius 1..8, 0 < tau <= 65025 and finite, soft in {0, 1}; the defaults are 7, 16, 1: the 15 x 15 window the
+ * default Farneback call averages over at level 0, and about fifteen times the c / N that sensor noise of sigma 1 produces
+ * (about 1.1).  The defaults are the project's own choice and are NOT tuned on footage. */
+typedef struct ffl_texture_params {
+    int radius;
+    float tau;
+    int soft;
+} ffl_texture_params;
+int ffl_texture_default_params(ffl_texture_params *out);
+/* Pure host check: no device or context needed.  FFL_ERR_INVALID with the rule in ffl_last_error(NULL). */
+int ffl_texture_params_check(const ffl_texture_params *p);
+
+/* The maps of n frames: item i is the map of the frame in frame slot fslots[i] -- for a pair that is its frame 0, on whose
+ * pixels the flow is defined.  No flow slot is involved.  `out`, `gate` and p are ffl_residual_weights' (gate: the maps S of
+ * rule T6).  Refused before any device work, each with its rule in the message: n outside 1..max_batch; a NULL list; a frame
+ * slot out of range, or one that was never uploaded (FFL_ERR_STATE) -- frame slots MAY repeat between items; any rule of
+ * ffl_texture_params_check; any rule of ffl_dev_weights_check for out and for gate; out with item_stride == 0 when n > 1; out or
+ * gate that is not device memory of the context's device inside one allocation; a capturing `stream` (FFL_ERR_STATE); out
+ * overlapping gate -- with ONE exception: gate may be EXACTLY out (the same base, item stride and row pitch).  The call then
+ * min-combines the texture into maps that are already there, in place: every byte is read and written by the lane that owns
+ * the pixel.  ffl_residual_weights' protocol: ONE k_texture launch, queued on the library's stream behind the work queued on
+ * `stream` and the uploads that filled the frame slots; `stream` then waits for it, so the maps may be read, and the gate
+ * overwritten, on `stream` straight after the call; never captured; the host does not wait.  It counts as a reader of the frame
+ * slots: a later upload into one of them is ordered behind it, as behind a flow call.  Frames are only read.  No scratch
+ * memory: there is no *_extra_bytes call. */
+int ffl_texture_weights(ffl_ctx *ctx, int n, const int *fslots, const ffl_texture_params *p, const ffl_dev_weights *gate,
+                        const ffl_dev_weights *out, uint64_t stream);
 
 /* ---- Per-cell flow statistics and the variance centre ----
  * center_of_mass_variance(flow, num_cells) of FF:721-746 and the grid it is formed from, on resident flow fields.  With

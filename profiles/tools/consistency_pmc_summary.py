@@ -10,7 +10,7 @@ for path in glob.glob(os.path.join(sys.argv[1], "pmc_*", "**", "*counter_collect
     with open(path, newline="") as f:
         for r in csv.DictReader(f):
             name = r.get("Kernel_Name", "?")
-            if not any(k in name for k in ("consistency", "residual", "export_flows")):
+            if not any(k in name for k in ("consistency", "residual", "texture", "export_flows")):
                 continue
             grid = r.get("Grid_Size", "") or "x".join(r.get(k, "") for k in ("Grid_Size_X", "Grid_Size_Y", "Grid_Size_Z"))
             rows.setdefault((name.split("(")[0], grid, r.get("Counter_Name", "?")), []).append(float(r.get("Counter_Value", "nan")))

@@ -10,7 +10,7 @@ for path in glob.glob(os.path.join(sys.argv[1], "**", "*kernel_trace.csv"), recu
     with open(path, newline="") as f:
         for r in csv.DictReader(f):
             name = r.get("Kernel_Name") or r.get("Name") or "?"
-            if not any(k in name for k in ("consistency", "residual", "export_flows")):
+            if not any(k in name for k in ("consistency", "residual", "texture", "export_flows")):
                 continue
             grid = tuple(r.get(k, "") for k in ("Grid_Size_X", "Grid_Size_Y", "Grid_Size_Z"))
             dur = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
