@@ -834,6 +834,7 @@ SIGNATURES = {
     "ffl_level_size": (_i, (_ctx, _i, _ip)),
     "ffl_download_frame": (_i, (_ctx, _i, _vp)),
     "ffl_debug_pair": (_i, (_ctx,) + (_i,) * 4 + (_vp,) * 6),
+    "ffl_debug_blur_plan": (_i, (_i,) * 9 + (_ip, _ip, _ip, _ip, _i)),
     "ffl_set_option": (_i, (_str, _i)),
     "ffl_ctx_set_option": (_i, (_ctx, _str, _i)),
     "ffl_ctx_get_option": (_i, (_ctx, _str, _ip)),
@@ -886,6 +887,24 @@ def get_option(name):
     if load().ffl_ctx_get_option(None, name.encode(), C.byref(v)) != FFL_OK:
         raise FFLError(f"unknown option {name!r}")
     return v.value
+
+
+def blur_plan(tiles_x, tiles_y, n_pairs, slots, blur_rows=0, blur_min_wgs=3500, blur_taper=0, blur_taper_pairs=0,
+              tile_order=0, blocks=True):
+    """ffl_debug_blur_plan: the launch plan of k_blur_solve for a level of tiles_x x tiles_y tiles and n_pairs pairs on
+    `slots` workgroup slots -> (segments, grid, blocks).  segments: rows of (first workgroup, first pair, pairs, tiles per
+    strip, strips per column); blocks: int32 (grid, 4) of (pair, tile column, first tile row, tiles) with pair -1 for padding
+    workgroups, enumerated on the host with the kernel's own mapping (None with blocks=False).  Needs no device."""
+    L = load()
+    args = [int(v) for v in (tiles_x, tiles_y, n_pairs, slots, blur_rows, blur_min_wgs, blur_taper, blur_taper_pairs, tile_order)]
+    seg, n, grid = (C.c_int * 15)(), C.c_int(), C.c_int()
+    _check(L.ffl_debug_blur_plan(*args, seg, C.byref(n), C.byref(grid), None, 0), exc=ValueError)
+    segments = [tuple(seg[5 * i:5 * i + 5]) for i in range(n.value)]
+    if not blocks:
+        return segments, grid.value, None
+    out = np.zeros((grid.value, 4), np.int32)
+    _check(L.ffl_debug_blur_plan(*args, seg, C.byref(n), C.byref(grid), out.ctypes.data_as(_ip), grid.value), exc=ValueError)
+    return segments, grid.value, out
 
 
 def device_count():

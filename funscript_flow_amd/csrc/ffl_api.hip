@@ -250,6 +250,7 @@ struct ffl_ctx {
     FflOptions opt;      // this context's own option set (copied from the process-wide defaults at ffl_create)
     int opt_epoch = 0;   // bumped by every applied ffl_ctx_set_option: a graph is only replayed under the options it was captured with
     int graph_captured = 0, graph_replayed = 0, graph_failed = 0;  // ffl_graph_stats
+    BlurSlots blur_slots = {};  // resident workgroups of the k_blur_solve instantiations on this device (ffl_blur_plan's taper)
     CopyPool pool;
     int n_fslots = 0, n_slots = 0, max_batch = 0;
     size_t N = 0;
@@ -922,6 +923,7 @@ static int create_resources(ffl_ctx *c) {
     HIPCHK_ALLOC(nullptr, hipHostMalloc, c->h_stage_gray, lay.gray, hipHostMallocDefault);
     HIPCHK_ALLOC(nullptr, hipHostMalloc, c->h_stage_bgr, lay.bgr, hipHostMallocDefault);
     c->p1_blocks = ffl_pass1_blocks(width, height);
+    if (!ffl_blur_slots(&c->blur_slots)) return set_err(nullptr, FFL_ERR_HIP, "ffl_create: the occupancy of k_blur_solve could not be queried");
     c->lanes.resize(num_lanes);
     for (auto &L : c->lanes) {
         HIPCHK(nullptr, hipStreamCreateWithFlags(L.st.put(), hipStreamNonBlocking));
@@ -1566,10 +1568,10 @@ static int enqueue_batch(ffl_ctx *c, ffl_ctx::Lane &L, const BatchTab &T, int n,
             {
                 ProfScope ps(c, FFL_K_BLUR_SOLVE, st, it > 0 && !cap);  // the three iterations are queued back to back
                 if (it == 0 && fuse_first)
-                    ffl_launch_blur_solve_first(L.d_M[mi ^ 1], M_stride, Rk, R_stride, plane, pt, k, n, lw, lh, pw, ph, c->opt, st);
+                    ffl_launch_blur_solve_first(L.d_M[mi ^ 1], M_stride, Rk, R_stride, plane, pt, k, n, lw, lh, pw, ph, c->opt, c->blur_slots, st);
                 else
                     ffl_launch_blur_solve(L.d_M[mi], L.d_M[mi ^ 1], M_stride, Rk, R_stride, plane, pt, k, n, lw, lh,
-                                          update, cap != nullptr, c->opt, st);
+                                          update, cap != nullptr, c->opt, c->blur_slots, st);
             }
             if (update) mi ^= 1;
         }
@@ -3607,6 +3609,39 @@ static int get_option_impl(const FflOptions &o, const char *name, int *value) {
     const FflOptionRow *r = option_row(name);
     if (!fixed && !r) return FFL_ERR_INVALID;
     *value = fixed ? *fixed : o.*r->member;
+    return FFL_OK;
+}
+
+int ffl_debug_blur_plan(int tiles_x, int tiles_y, int n_pairs, int slots, int blur_rows, int blur_min_wgs, int blur_taper,
+                        int blur_taper_pairs, int tile_order, int *segments, int *n_segments, int *grid, int *blocks,
+                        int max_blocks) {
+    FflOptions o;
+    if (tiles_x < 1 || tiles_y < 1 || n_pairs < 1 || n_pairs > FFL_MAXB || slots < 0 || !segments || !n_segments || !grid ||
+        set_option_impl(o, "blur_rows", blur_rows, false) || set_option_impl(o, "blur_min_wgs", blur_min_wgs, false) ||
+        set_option_impl(o, "blur_taper", blur_taper, false) || set_option_impl(o, "blur_taper_pairs", blur_taper_pairs, false) ||
+        set_option_impl(o, "tile_order", tile_order, false))
+        return set_err(nullptr, FFL_ERR_INVALID, "ffl_debug_blur_plan: bad size, pair count, slot count, option value or NULL output");
+    BlurPlan plan;
+    const unsigned g = ffl_blur_plan(tiles_x, tiles_y, n_pairs, slots, o, &plan);
+    *n_segments = plan.n;
+    *grid = (int)g;
+    for (int i = 0; i < FFL_BLUR_SEGS; i++) {
+        const BlurSeg &s = plan.s[i];
+        const int row[5] = {s.first_block, s.first_pair, s.pairs, s.nrb, s.strips};
+        memcpy(segments + 5 * i, row, sizeof(row));
+    }
+    if (!blocks) return FFL_OK;
+    if ((unsigned)max_blocks < g)
+        return set_err(nullptr, FFL_ERR_INVALID, "ffl_debug_blur_plan: %u workgroups, room for %d", g, max_blocks);
+    for (unsigned blk = 0; blk < g; blk++) {
+        int b, tile_x, row0, nrb;
+        int *out = blocks + 4 * (size_t)blk;
+        if (ffl_blur_block(plan, blk, tiles_x, tile_order, b, tile_x, row0, nrb)) {
+            out[0] = b; out[1] = tile_x; out[2] = row0; out[3] = std::max(0, std::min(nrb, tiles_y - row0));
+        } else {
+            out[0] = -1; out[1] = out[2] = out[3] = 0;
+        }
+    }
     return FFL_OK;
 }
 

@@ -159,6 +159,8 @@ struct FflOptions {
     int blur_rows = 0;      // tiles a k_blur_solve workgroup walks down (0: automatic)
     int blur_min_wgs = 3500; // automatic strip length: the longest strips that still give this many workgroups
     int tile_order = 0;     // 0 pair-major, 1 tile-major (ffl_tile_coord)
+    int blur_taper = 1;     // 1: the pairs a k_blur_solve launch deals last get shorter strips (ffl_blur_plan), sized from the slots
+    int blur_taper_pairs = 0; // > 0: that many pairs in each of the two taper segments, whatever blur_taper says (tests, sweeps)
     int pyr_coarse = 1;     // one-pass kernel for the x1/4 and x1/8 pyramid levels where sizes allow
     int fuse_l0_blur = 1;   // merged expansion: PolyExp forms level 0's image from the gray frame itself; its I plane is not written
     int fb_general = 0;     // 1: ffl_flow_pairs_farneback runs the reference's parameters through the general kernels too
@@ -179,9 +181,29 @@ inline constexpr FflOptionRow kFflOptionRows[] = {
     {"blur_rows", &FflOptions::blur_rows, 0, 64, false},
     {"blur_min_wgs", &FflOptions::blur_min_wgs, 1, INT_MAX, false},
     {"tile_order", &FflOptions::tile_order, 0, 1, false},
+    {"blur_taper", &FflOptions::blur_taper, 0, 1, false},
+    {"blur_taper_pairs", &FflOptions::blur_taper_pairs, 0, FFL_MAXB, false},
     {"pyr_coarse", &FflOptions::pyr_coarse, INT_MIN, INT_MAX, true},
     {"fuse_l0_blur", &FflOptions::fuse_l0_blur, INT_MIN, INT_MAX, true},
     {"fb_general", &FflOptions::fb_general, 0, 1, false},
+};
+
+// The launch plan of k_blur_solve (ffl_blur_plan, kernels_farneback.hip): up to three segments of consecutive pairs, each
+// a uniform grid of strips dealt by ffl_tile_map.  The bulk walks strips of `nrb` tiles; with taper on, the pairs dealt
+// last walk strips of ceil(nrb / 2) and then ceil(nrb / 4) tiles, so the workgroups that start last are also the shortest
+// and the launch drains faster.  Every segment starts at a multiple of 8 workgroups (the XCD round-robin).  One segment
+// is the launch without taper: same grid, same mapping.  Passed to the kernel by value.
+#define FFL_BLUR_SEGS 3
+struct BlurSeg {
+    int first_block, first_pair, pairs, nrb, strips;  // strips: per tile column
+};
+struct BlurPlan {
+    BlurSeg s[FFL_BLUR_SEGS];
+    int n;
+};
+// workgroup slots of the device per k_blur_solve instantiation (occupancy x compute units), cached by the context
+struct BlurSlots {
+    int first, first_zero, update, last;  // folded first launch (upsampled / zero initial flow), fused update, a level's last
 };
 
 // ---- launchers (each enqueues on `st` and returns; no synchronisation) ----------------------
@@ -221,12 +243,17 @@ void ffl_launch_update_matrices(const float *R, size_t R_stride, size_t plane, c
 // (it is dead until the level's last iteration, which always stores it)
 void ffl_launch_blur_solve(const float *Min, float *Mout, size_t M_stride, const float *R, size_t R_stride,
                            size_t plane, const PairTab *pt, int level, int nB, int lw, int lh, int update, int store_flow,
-                           const FflOptions &opt, hipStream_t st);
+                           const FflOptions &opt, const BlurSlots &slots, hipStream_t st);
 
 
 void ffl_launch_blur_solve_first(float *Mout, size_t M_stride, const float *R, size_t R_stride, size_t plane,
                                  const PairTab *pt, int level, int nB, int lw, int lh, int pw, int ph, const FflOptions &opt,
-                                 hipStream_t st);
+                                 const BlurSlots &slots, hipStream_t st);
+// the slots of the current device; false when the occupancy query fails
+bool ffl_blur_slots(BlurSlots *out);
+// the plan of one launch over tiles_x x tiles_y tiles and nB pairs on `slots` workgroup slots (host only, no device);
+// returns the grid size
+unsigned ffl_blur_plan(int tiles_x, int tiles_y, int nB, int slots, const FflOptions &opt, BlurPlan *plan);
 
 // ---- DIS (kernels_dis.hip) ----------------------------------------------------------------
 #define DIS_MAX_PATCHES 4096   // patch flows of one scale in LDS (float2 each)
@@ -484,25 +511,53 @@ static inline unsigned ffl_tile_grid(int tiles_x, int tiles_y, int nB) {
 //   stream, frame j's expansion R is R1 of pair j-1 and R0 of pair j: with the same tile of consecutive pairs
 //   resident on one XCD at the same time, the second of those reads is served by that XCD's L2 instead of the
 //   fabric (the R planes are 40 of the 68 bytes per pixel an UpdateMatrices pass moves).
-__device__ __forceinline__ bool ffl_tile_coord(int tiles_x, int tiles_y, int nB, int order, int &b, int &tile_x,
-                                               int &tile_y) {
+// ffl_tile_map: the same for workgroup `blk` of the grid, on the host as well (ffl_debug_blur_plan enumerates a launch).
+__host__ __device__ __forceinline__ bool ffl_tile_map(unsigned blk, int tiles_x, int tiles_y, int nB, int order, int &b,
+                                                      int &tile_x, int &tile_y) {
     const int T = tiles_x * tiles_y, chunk = (T + 7) >> 3;
     int t;
     if (order == 0) {
-        b = blockIdx.x / (chunk * 8);
-        const int l = blockIdx.x - b * (chunk * 8);
+        b = blk / (chunk * 8);
+        const int l = blk - b * (chunk * 8);
         t = (l & 7) * chunk + (l >> 3);
     } else {
-        const int pos = blockIdx.x >> 3, tt = pos / nB;
+        const int pos = blk >> 3, tt = pos / nB;
         b = pos - tt * nB;
-        t = (blockIdx.x & 7) * chunk + tt;
+        t = (blk & 7) * chunk + tt;
     }
     if (t >= T) return false;
     const int per_panel = FFL_PANEL_W * tiles_y;
     const int panel = t / per_panel, within = t - panel * per_panel;
-    const int pw = min(FFL_PANEL_W, tiles_x - panel * FFL_PANEL_W);  // the last panel may be narrower
+    const int left = tiles_x - panel * FFL_PANEL_W;
+    const int pw = left < FFL_PANEL_W ? left : FFL_PANEL_W;  // the last panel may be narrower
     tile_y = within / pw;
     tile_x = panel * FFL_PANEL_W + (within - tile_y * pw);
+    return true;
+}
+__device__ __forceinline__ bool ffl_tile_coord(int tiles_x, int tiles_y, int nB, int order, int &b, int &tile_x,
+                                               int &tile_y) {
+    return ffl_tile_map(blockIdx.x, tiles_x, tiles_y, nB, order, b, tile_x, tile_y);
+}
+
+// workgroup `blk` of a planned k_blur_solve launch (BlurPlan) -> its pair, tile column, first tile row and strip length (rows past tiles_y are the
+// caller's to clip); false for a padding workgroup.  The segment is found with scalar compares, as k_polyexp_multi's job.
+__host__ __device__ __forceinline__ bool ffl_blur_block(const BlurPlan &p, unsigned blk, int tiles_x, int order, int &b,
+                                                        int &tile_x, int &row0, int &nrb) {
+    int first = 0, pair0 = 0, pairs = p.s[0].pairs, strips = p.s[0].strips;
+    nrb = p.s[0].nrb;
+#pragma unroll
+    for (int i = 1; i < FFL_BLUR_SEGS; i++)
+        if (i < p.n && blk >= (unsigned)p.s[i].first_block) {
+            first = p.s[i].first_block;
+            pair0 = p.s[i].first_pair;
+            pairs = p.s[i].pairs;
+            strips = p.s[i].strips;
+            nrb = p.s[i].nrb;
+        }
+    int strip_y;
+    if (!ffl_tile_map(blk - first, tiles_x, strips, pairs, order, b, tile_x, strip_y)) return false;
+    b += pair0;
+    row0 = strip_y * nrb;
     return true;
 }
 

@@ -23,6 +23,8 @@
 // gathers, 16 bytes for streams, never 8.  DESIGN.md section 4, "Round 2".
 #include "ffl_kernels.h"
 
+#include <algorithm>
+
 // ------------------------------------------------------------------------------------------------
 // K0: BGR -> gray, OpenCV 8-bit fixed point (15-bit coefficients).  4 pixels per lane.
 // ------------------------------------------------------------------------------------------------
@@ -1122,6 +1124,16 @@ __device__ unsigned long long g_stamp[64][FFL_NSTAMP];
 extern "C" int ffl_debug_read_stamps(unsigned long long *out) {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamp), sizeof(unsigned long long) * 64 * FFL_NSTAMP);
 }
+// Drain timeline: thread 0 of every workgroup of the three level-0 launches (w >= 1024; 0 folded first, 1 fused update,
+// 2 last) leaves the device-wide clock (wall_clock64, 100 MHz) at entry and exit; profiles/tools/k5_drain.py derives the
+// resident workgroups over time and the slot-time the launch leaves empty while it drains.
+#define FFL_DRAIN_MAX 8192
+__device__ unsigned long long g_drain[3][FFL_DRAIN_MAX][2];
+extern "C" int ffl_debug_read_drain(unsigned long long *out) {
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_drain), sizeof(unsigned long long) * 3 * FFL_DRAIN_MAX * 2);
+}
+#define FFL_DRAIN(e)                                                          \
+    if (w >= 1024 && tid == 0 && blockIdx.x < FFL_DRAIN_MAX) g_drain[FIRST ? 0 : UPDATE ? 1 : 2][blockIdx.x][e] = wall_clock64();
 #define FFL_T(i)                                                              \
     if (FFL_STAMP_ON && tid == 0) {                                           \
         const unsigned long long t_ = __builtin_readcyclecounter();          \
@@ -1130,6 +1142,7 @@ extern "C" int ffl_debug_read_stamps(unsigned long long *out) {
     }
 #else
 #define FFL_T(i)
+#define FFL_DRAIN(e)
 #endif
 
 
@@ -1141,9 +1154,8 @@ extern "C" int ffl_debug_read_stamps(unsigned long long *out) {
 template <bool UPDATE, int FIRST>
 __global__ __launch_bounds__(256, FIRST ? FFL_K5_WAVES_FIRST : FFL_K5_WAVES) void k_blur_solve(
     const float *__restrict__ Min, float *__restrict__ Mout, size_t M_stride, const float *__restrict__ R, size_t R_stride,
-    size_t plane, const PairTab *__restrict__ pt, int level, int w, int h, int nrb, int pw, int ph, double usx, double usy,
-    int store_flow, int nB,
-    int order) {
+    size_t plane, const PairTab *__restrict__ pt, int level, int w, int h, BlurPlan plan, int pw, int ph, double usx, double usy,
+    int store_flow, int order) {
     constexpr int TW = 64, TH = 16, LW = TW + 2 * FFL_WIN_R, LH = TH + 2 * FFL_WIN_R;
     constexpr int PX = 4;  // consecutive pixels per lane in phase H
     constexpr int NCARRY = LH - TH;  // rows of a tile's 30 that the tile below needs again
@@ -1167,9 +1179,11 @@ __global__ __launch_bounds__(256, FIRST ? FFL_K5_WAVES_FIRST : FFL_K5_WAVES) voi
     // A workgroup walks down `nrb` vertically adjacent tiles (a column strip of 64 x 16*nrb pixels) and
     // keeps the 14 rows two consecutive tiles share in registers: phase V then loads 16 new rows per tile
     // instead of 30 -- its halo re-reads (30 rows for 16 outputs) were the kernel's largest single cost.
-    int b, tile_x, strip_y;  // XCD-aware panel order over the strips, see ffl_tile_coord
-    const int tiles_y = (h + TH - 1) / TH;
-    if (!ffl_tile_coord((w + TW - 1) / TW, (tiles_y + nrb - 1) / nrb, nB, order, b, tile_x, strip_y)) return;
+    // The strip length belongs to the workgroup's segment of the launch plan (BlurPlan): the pairs dealt last may walk
+    // shorter strips.
+    int b, tile_x, row0, nrb;  // XCD-aware panel order over the segment's strips, see ffl_tile_map
+    if (!ffl_blur_block(plan, blockIdx.x, (w + TW - 1) / TW, order, b, tile_x, row0, nrb)) return;
+    FFL_DRAIN(0)
     const int x0 = tile_x * TW;
     const float *Mb = Min + (size_t)b * M_stride;
 
@@ -1297,7 +1311,7 @@ __global__ __launch_bounds__(256, FIRST ? FFL_K5_WAVES_FIRST : FFL_K5_WAVES) voi
 
 #pragma unroll 1
     for (int rb = 0; rb < nrb; rb++) {
-        const int y0 = (strip_y * nrb + rb) * TH;
+        const int y0 = (row0 + rb) * TH;
         if (y0 >= h) break;
         double acc[5][PX];
         if (FIRST) {
@@ -1462,6 +1476,7 @@ __global__ __launch_bounds__(256, FIRST ? FFL_K5_WAVES_FIRST : FFL_K5_WAVES) voi
     if (FFL_STAMP_ON && tid == 0)
         for (int i = 0; i < FFL_NSTAMP; i++) g_stamp[blockIdx.x & 63][i] = sStamp[i];
 #endif
+    FFL_DRAIN(1)
 }
 
 // Tiles a workgroup walks down.  The strip walk saves 14 of 30 row loads per tile after a strip's first, so long strips
@@ -1485,31 +1500,89 @@ static int ffl_blur_rows_per_wg(int tiles_x, int tiles_y, int nB, int min_wgs) {
     return 1;
 }
 
-// one k_blur_solve launch: the strip length and grid of the level, then kernel `k` (pw, ph: the coarser level's size
-// for the folded first iteration's upsample, else 0)
+// The plan of one launch (BlurPlan, ffl_kernels.h).  The bulk is today's launch: strips of `nrb` tiles.  A launch is several
+// rounds of long-lived workgroups (1080p level 0, B = 32: 3840 strips of 17 tiles on 768 or 1024 slots), and while the ones
+// dealt last finish the device runs part-empty for up to a workgroup's lifetime.  With taper, the last 2 P pairs -- tiles
+// are dealt pair-major, so they start last -- walk strips of ceil(nrb / 2) and, the last P, ceil(nrb / 4) tiles.
+// P: "blur_taper_pairs" when > 0; else with "blur_taper" = 1 the pairs whose bulk workgroups fill a quarter round of `slots`
+// (both tapers together: half a round -- a whole round, P = 4 at 1080p, measured worse than P = 2: the shorter strips'
+// extra halo rows then cost what the drain saves, profiles/blur_taper.md), on levels whose bulk strips exceed 2 tiles.
+// The quotient is rounded to the nearest count and capped at nB / 4, so the tapers never hold more than half the launch;
+// where that gives 0 -- fewer than 4 pairs, or a single pair's workgroups already exceed half a round (4K with a few
+// pairs) -- there is no taper: such shapes were not measured and keep the launch they had.  P = 0: one segment, the launch
+// as it always was.  Segments without pairs are left out (a forced P with nB <= 2 P leaves no bulk).  Results do not
+// depend on the plan: the box sums are anchored to 16-row blocks, not to strips.
+unsigned ffl_blur_plan(int tiles_x, int tiles_y, int nB, int slots, const FflOptions &opt, BlurPlan *plan) {
+    const int nrb = opt.blur_rows > 0 ? opt.blur_rows : ffl_blur_rows_per_wg(tiles_x, tiles_y, nB, opt.blur_min_wgs);
+    int P = opt.blur_taper_pairs;
+    if (P == 0 && opt.blur_taper && nrb > 2 && slots > 0) {
+        const long per_pair = (long)tiles_x * ((tiles_y + nrb - 1) / nrb);
+        P = (int)std::min((slots + 2 * per_pair) / (4 * per_pair), (long)(nB / 4));
+    }
+    const int p2 = std::min(P, nB), p1 = std::min(P, nB - p2);
+    const int pairs[FFL_BLUR_SEGS] = {nB - p1 - p2, p1, p2};
+    const int rows[FFL_BLUR_SEGS] = {nrb, (nrb + 1) / 2, std::max(1, (nrb + 3) / 4)};
+    *plan = BlurPlan{};
+    unsigned grid = 0;
+    int pair0 = 0;
+    for (int i = 0; i < FFL_BLUR_SEGS; i++) {
+        if (pairs[i] == 0) continue;
+        const int strips = (tiles_y + rows[i] - 1) / rows[i];
+        plan->s[plan->n++] = BlurSeg{(int)grid, pair0, pairs[i], rows[i], strips};
+        grid += ffl_tile_grid(tiles_x, strips, pairs[i]);
+        pair0 += pairs[i];
+    }
+    return grid;
+}
+
+template <typename K>
+static int ffl_k5_slots(K k, int cus) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 256, 0) != hipSuccess) return 0;
+    return per_cu * cus;
+}
+bool ffl_blur_slots(BlurSlots *out) {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+        return false;
+    *out = BlurSlots{ffl_k5_slots(k_blur_solve<true, 1>, cus), ffl_k5_slots(k_blur_solve<true, 2>, cus),
+                     ffl_k5_slots(k_blur_solve<true, 0>, cus), ffl_k5_slots(k_blur_solve<false, 0>, cus)};
+    return out->first > 0 && out->first_zero > 0 && out->update > 0 && out->last > 0;
+}
+#ifdef FFL_STAMP
+// diagnostic build: the slots of the current device as (first, first_zero, update, last), for profiles/tools/k5_drain.py
+extern "C" int ffl_debug_blur_slots(int *out) {
+    BlurSlots s;
+    if (!ffl_blur_slots(&s)) return 1;
+    out[0] = s.first; out[1] = s.first_zero; out[2] = s.update; out[3] = s.last;
+    return 0;
+}
+#endif
+
+// one k_blur_solve launch: the plan and grid of the level on `slots` workgroup slots, then kernel `k` (pw, ph: the coarser
+// level's size for the folded first iteration's upsample, else 0)
 template <typename K>
 static void ffl_launch_k5(K k, const float *Min, float *Mout, size_t M_stride, const float *R, size_t R_stride, size_t plane,
                           const PairTab *pt, int level, int nB, int lw, int lh, int pw, int ph, int store_flow,
-                          const FflOptions &opt, hipStream_t st) {
-    const int tiles_x = (lw + 63) / 64, tiles_y = (lh + 15) / 16;
-    const int nrb = opt.blur_rows > 0 ? opt.blur_rows : ffl_blur_rows_per_wg(tiles_x, tiles_y, nB, opt.blur_min_wgs);
-    dim3 grid(ffl_tile_grid(tiles_x, (tiles_y + nrb - 1) / nrb, nB));
-    hipLaunchKernelGGL(k, grid, dim3(256), 0, st, Min, Mout, M_stride, R, R_stride, plane, pt, level, lw, lh, nrb, pw, ph,
-                       pw > 0 ? (double)pw / lw : 1.0, pw > 0 ? (double)ph / lh : 1.0, store_flow, nB, opt.tile_order);
+                          const FflOptions &opt, int slots, hipStream_t st) {
+    BlurPlan plan;
+    dim3 grid(ffl_blur_plan((lw + 63) / 64, (lh + 15) / 16, nB, slots, opt, &plan));
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, st, Min, Mout, M_stride, R, R_stride, plane, pt, level, lw, lh, plan, pw, ph,
+                       pw > 0 ? (double)pw / lw : 1.0, pw > 0 ? (double)ph / lh : 1.0, store_flow, opt.tile_order);
 }
 
 void ffl_launch_blur_solve(const float *Min, float *Mout, size_t M_stride, const float *R, size_t R_stride,
                            size_t plane, const PairTab *pt, int level, int nB, int lw, int lh, int update, int store_flow,
-                           const FflOptions &opt, hipStream_t st) {
+                           const FflOptions &opt, const BlurSlots &slots, hipStream_t st) {
     ffl_launch_k5(update ? k_blur_solve<true, 0> : k_blur_solve<false, 0>, Min, Mout, M_stride, R, R_stride, plane, pt, level,
-                  nB, lw, lh, 0, 0, update ? store_flow : 1, opt, st);
+                  nB, lw, lh, 0, 0, update ? store_flow : 1, opt, update ? slots.update : slots.last, st);
 }
 
 // first iteration of a level with the initial UpdateMatrices folded in (pw > 0: initial flow = x2 upsample of
 // pt.prev, pw x ph; pw == 0: zero flow); writes the solved flow to pt.flow and the next M to Mout
 void ffl_launch_blur_solve_first(float *Mout, size_t M_stride, const float *R, size_t R_stride, size_t plane,
                                  const PairTab *pt, int level, int nB, int lw, int lh, int pw, int ph, const FflOptions &opt,
-                                 hipStream_t st) {
+                                 const BlurSlots &slots, hipStream_t st) {
     ffl_launch_k5(pw > 0 ? k_blur_solve<true, 1> : k_blur_solve<true, 2>, (const float *)nullptr, Mout, M_stride, R, R_stride,
-                  plane, pt, level, nB, lw, lh, pw, ph, 0, opt, st);
+                  plane, pt, level, nB, lw, lh, pw, ph, 0, opt, pw > 0 ? slots.first : slots.first_zero, st);
 }

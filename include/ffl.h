@@ -1010,6 +1010,16 @@ int ffl_download_frame(ffl_ctx *ctx, int fslot, uint8_t *dst);
 int ffl_debug_pair(ffl_ctx *ctx, int f0, int f1, int level, int iter, float *I0, float *I1, float *R0, float *R1,
                    float *M, float *flow);
 
+/* The launch plan of k_blur_solve for a level of tiles_x x tiles_y tiles (64 x 16 pixels) and n_pairs pairs on a device
+ * with `slots` resident workgroups, under the given values of the options "blur_rows", "blur_min_wgs", "blur_taper",
+ * "blur_taper_pairs" and "tile_order" (below).  Needs no device: the host runs the kernel's own mapping.
+ * segments: 3 rows of (first workgroup, first pair, pairs, tiles per strip, strips per tile column), *n_segments of them
+ * used; *grid: workgroups of the launch; blocks (may be NULL; max_blocks >= *grid rows of 4 ints): workgroup ->
+ * (pair, tile column, first tile row, tiles), pair -1 for a padding workgroup. */
+int ffl_debug_blur_plan(int tiles_x, int tiles_y, int n_pairs, int slots, int blur_rows, int blur_min_wgs, int blur_taper,
+                        int blur_taper_pairs, int tile_order, int *segments, int *n_segments, int *grid, int *blocks,
+                        int max_blocks);
+
 /* ---- measurement hooks (bench.py) -------------------------------------------------------------- */
 
 /* Tuning knobs (results never depend on them).  ffl_set_option sets the process-wide default that contexts created
@@ -1043,6 +1053,13 @@ int ffl_debug_pair(ffl_ctx *ctx, int f0, int f1, int level, int iter, float *I0,
  *                            read; 0: the pyramid launch writes it (the debug capture always does)
  *   "tile_order"  = 0|1      k_blur_solve / k_update_matrices workgroup order: 0 pair-major (default), 1 tile-major
  *                            (every tile for all pairs of the batch back to back; less fabric traffic, not faster)
+ *   "blur_taper"  = 0|1      1: the pairs a k_blur_solve launch deals last walk shorter strips (half, then a quarter of
+ *                            the bulk's), about half a round of the device's workgroup slots in all, so that the launch
+ *                            drains faster; levels whose strips are 1 or 2 tiles, batches of fewer than 4 pairs and levels on which one pair
+ *                            alone exceeds half a round are left alone.  Default 1 (+1.3 to
+ *                            +3.3 % per step at the four bench shapes, profiles/blur_taper.md); 0: one uniform grid
+ *   "blur_taper_pairs" = 0..256  P > 0: P pairs in each of the two taper segments, whatever "blur_taper" says (tests
+ *                            and sweeps); default 0
  *   "fb_general"  = 0|1      1: ffl_flow_pairs_farneback runs the default parameters through the general kernels as well
  *                            (test and measurement hook; the results are the same bits) */
 int ffl_set_option(const char *name, int value);

@@ -22,9 +22,11 @@ runner = bench.StepRunner(ctx, B, False, SMOOTH_RADIUS)
 
 def apply(cfg):
     ctx.set_option("blur_rows", 0); ctx.set_option("blur_min_wgs", 3500)   # options belong to the context (ffl_ctx_set_option)
+    ctx.set_option("blur_taper", 0); ctx.set_option("blur_taper_pairs", 0)
     for kv in cfg.split(","):
         k, v = kv.split("=")
-        ctx.set_option({"rows": "blur_rows", "minwgs": "blur_min_wgs", "order": "tile_order", "fuse": "fuse_first"}[k], int(v))
+        ctx.set_option({"rows": "blur_rows", "minwgs": "blur_min_wgs", "order": "tile_order", "fuse": "fuse_first",
+                        "taper": "blur_taper", "pairs": "blur_taper_pairs"}[k], int(v))
 
 
 res = {c: [] for c in cfgs}
