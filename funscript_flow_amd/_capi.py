@@ -22,7 +22,14 @@ FFL_PROFILE_ALL = 0xFF
 FFL_MAX_CELLS = 64
 CELL_DTYPE = np.dtype([(k, "<f8") for k in ("mean_u", "mean_v", "mean_mag", "var_mag")])
 GRID_CENTRE_DTYPE = np.dtype([("cx", "<f8"), ("cy", "<f8"), ("total_var", "<f8"), ("cells", "<i4"), ("empty", "<i4")])
-CENTERS = ("variance",)   # params["hip_center"] / center=: estimators beside the default |div| argmax
+CENTERS = ("variance", "track")   # params["hip_center"] / center=: estimators beside the default |div| argmax
+# region tracking and ROI maps (appendices Q and E): the header's enums, ffl_track_state, ffl_track_record
+FFL_MAX_TRACKS, FFL_MAX_TRACK_RADIUS = 8, 32
+TRACK_ON_CUT = ("hold", "home")                            # FFL_TRACK_HOLD, FFL_TRACK_HOME
+TRACK_OK, TRACK_CUT, TRACK_LOST, TRACK_CLAMPED = 0, 1, 2, 4   # status bits of a record
+TRACK_STATE_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("home_x", "<f8"), ("home_y", "<f8"), ("steps", "<i8"),
+                              ("lost_run", "<i4"), ("pad", "<i4")])
+TRACK_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("du", "<f8"), ("dv", "<f8"), ("sw", "<f8"), ("count", "<i4"), ("status", "<i4")])
 
 # 4:2:0 layouts of ffl_upload_frames_yuv (FFL_YUV_I420, FFL_YUV_NV12): cv2's single-array (3h/2, w) uint8 frames
 YUV_LAYOUTS = {"i420": 0, "nv12": 1}
@@ -579,6 +586,79 @@ def texture_choice(params):
     return params
 
 
+def track_on_cut(on_cut):
+    """FFL_TRACK_HOLD / FFL_TRACK_HOME of a name of TRACK_ON_CUT (or the code itself)"""
+    if isinstance(on_cut, str):
+        if on_cut not in TRACK_ON_CUT:
+            raise ValueError(f"on_cut must be one of {TRACK_ON_CUT}, got {on_cut!r}")
+        return TRACK_ON_CUT.index(on_cut)
+    return int(on_cut)
+
+
+class TrackParams(C.Structure):
+    """ffl_track_params: the window radius r (1..32, the window is (2r+1)^2, clipped to the image),
+    on_cut ("hold": the track stays where it is over a cut, "home": it returns to its home position) and the cut threshold of
+    rule Q5.  TrackParams() holds the library's defaults (the radius is the project's own choice, not tuned on footage);
+    keywords override single fields."""
+    _fields_ = [("radius", C.c_int), ("on_cut", C.c_int), ("cut_threshold", C.c_float)]
+
+    def __init__(self, **over):
+        super().__init__()
+        load().ffl_track_default_params(C.byref(self))
+        for k, v in over.items():
+            if k not in ("radius", "on_cut", "cut_threshold"):
+                raise ValueError(f"unknown track parameter {k!r} (radius, on_cut, cut_threshold)")
+            setattr(self, k, track_on_cut(v) if k == "on_cut" else v)
+
+    def as_dict(self):
+        return {"radius": self.radius, "on_cut": TRACK_ON_CUT[self.on_cut] if self.on_cut in (0, 1) else self.on_cut,
+                "cut_threshold": self.cut_threshold}
+
+
+def track_params_check(params):
+    """ffl_track_params_check: ValueError with the library's rule when it refuses (pure host check)."""
+    _check(load().ffl_track_params_check(None if params is None else C.byref(params)), exc=ValueError)
+
+
+def track_choice(params):
+    """a TrackParams out of None (the defaults), a dict of its fields or a TrackParams; checked"""
+    if not isinstance(params, TrackParams):
+        params = TrackParams(**dict(params or {}))
+    track_params_check(params)
+    return params
+
+
+class RoiParams(C.Structure):
+    """ffl_roi_params: the ellipse's half-axes ax, ay in pixels (0.5..32768) and soft 1 (a paraboloid
+    that falls from 255 at the centre to 0 at the ellipse) or 0 (255 inside, 0 outside).  RoiParams() holds the library's
+    defaults (the project's own choice, not tuned on footage); keywords override single fields."""
+    _fields_ = [("ax", C.c_float), ("ay", C.c_float), ("soft", C.c_int)]
+
+    def __init__(self, **over):
+        super().__init__()
+        load().ffl_roi_default_params(C.byref(self))
+        for k, v in over.items():
+            if k not in ("ax", "ay", "soft"):
+                raise ValueError(f"unknown ROI parameter {k!r} (ax, ay, soft)")
+            setattr(self, k, v)
+
+    def as_dict(self):
+        return {"ax": self.ax, "ay": self.ay, "soft": self.soft}
+
+
+def roi_params_check(params):
+    """ffl_roi_params_check: ValueError with the library's rule when it refuses (pure host check)."""
+    _check(load().ffl_roi_params_check(None if params is None else C.byref(params)), exc=ValueError)
+
+
+def roi_choice(params):
+    """a RoiParams out of None (the defaults), a dict of its fields or a RoiParams; checked"""
+    if not isinstance(params, RoiParams):
+        params = RoiParams(**dict(params or {}))
+    roi_params_check(params)
+    return params
+
+
 class MotionParams(C.Structure):
     """ffl_motion_params: the sub-model of rule C2 (a name of MOTION_MODELS or its code), the passes of
     rule C7 and the Cauchy scale tau of rule C3 in pixels.  MotionParams() holds the library's defaults (rule C9: translation,
@@ -811,6 +891,13 @@ SIGNATURES = {
     "ffl_cell_stats": (_i, (_ctx, _i, _ip, _i, _vp, _vp, _u64)),
     "ffl_radial_window_axes_centres": (_i, _WINDOW + (_vp, _pd, _vp, _u64)),
     "ffl_cells_extra_bytes": (_i, (_i,) * 3 + (_szp,)),
+    "ffl_track_default_params": (_i, (_P(TrackParams),)),
+    "ffl_track_params_check": (_i, (_P(TrackParams),)),
+    "ffl_track_advance": (_i, (_ctx, _i, _ip, _i, _P(TrackParams), _P(DevWeights), _vp, _vp, _u64)),
+    "ffl_roi_default_params": (_i, (_P(RoiParams),)),
+    "ffl_roi_params_check": (_i, (_P(RoiParams),)),
+    "ffl_roi_weights": (_i, (_ctx, _i, _vp, _pd, _P(RoiParams), _P(DevWeights), _P(DevWeights), _u64)),
+    "ffl_radial_window_axes_weighted_centres": (_i, _WINDOW + (_P(DevWeights), _vp, _pd, _vp, _u64)),
     "ffl_motion_default_params": (_i, (_P(MotionParams),)),
     "ffl_motion_params_check": (_i, (_P(MotionParams),)),
     "ffl_motion_solve": (_i, (_dp, _i, _vp)),
@@ -852,7 +939,8 @@ RECORDS = {"ffl_source_info": SourceInfo, "ffl_dev_frame": DevFrame, "ffl_dev_fl
            "ffl_axes_record": PASS2_AXES_DTYPE, "ffl_dev_weights": DevWeights, "ffl_consistency_params": ConsistencyParams,
            "ffl_residual_params": ResidualParams, "ffl_texture_params": TextureParams,
            "ffl_cell_record": CELL_DTYPE, "ffl_grid_centre": GRID_CENTRE_DTYPE, "ffl_motion_params": MotionParams,
-           "ffl_motion_record": MOTION_DTYPE, "ffl_dis_params": DisParams,
+           "ffl_motion_record": MOTION_DTYPE, "ffl_dis_params": DisParams, "ffl_track_params": TrackParams,
+           "ffl_track_state": TRACK_STATE_DTYPE, "ffl_track_record": TRACK_DTYPE, "ffl_roi_params": RoiParams,
            "ffl_farneback_params": FarnebackParams}
 
 _lib = None
@@ -953,7 +1041,11 @@ def cell_grid(width, height, cells):
 
 def _centre_entries(centres, n_seq):
     """(pointer, byte stride) of n_seq centres in device memory: a float64 (n_seq, 2) array, rows any multiple of 8 bytes
-    apart, or a contiguous buffer of n_seq GRID_CENTRE_DTYPE records"""
+    apart, a contiguous buffer of n_seq GRID_CENTRE_DTYPE records, or an explicit span (pointer or device buffer, byte
+    stride) -- (track_buffer, 48 * tracks) reads track 0 of ffl_track_advance's records; the library checks such a span"""
+    if isinstance(centres, tuple) and len(centres) == 2 and isinstance(centres[1], (int, np.integer)):
+        base, stride = centres
+        return (int(base) if isinstance(base, (int, np.integer)) else _array_view(base)[0]), int(stride)
     ptr, shp, st, ts = _array_view(centres)
     if ts in ("<f8", "torch.float64") and len(shp) == 2:
         if shp != (n_seq, 2) or st[1] != 8:
@@ -1486,6 +1578,56 @@ class Context:
         ptr, stride = _centre_entries(centres, len(seq_slots))
         return self._radial_window(self.L.ffl_radial_window_axes_centres, "radial_window_axes_centres", PASS2_AXES_DTYPE,
                                    seq_slots, first, n, out, radius, cut_threshold, pov_mode, stream, weights=(ptr, stride))
+
+    def radial_window_axes_weighted_centres(self, seq_slots, first, n, weights, centres, out, radius=6, cut_threshold=7.0,
+                                            pov_mode=False, stream=None):
+        """The fifth window form (ffl_radial_window_axes_weighted_centres): radial_window_axes_weighted's terms about
+        radial_window_axes_centres' centres.  `weights` as in pass1_weighted, (H, W) or (n, H, W); `centres` as in
+        radial_window_axes_centres, or a (buffer, byte stride) span such as (track_buffer, 48 * tracks)."""
+        desc = self._weights("radial_window_axes_weighted_centres", weights, n)
+        ptr, stride = _centre_entries(centres, len(seq_slots))
+        return self._radial_window(self.L.ffl_radial_window_axes_weighted_centres, "radial_window_axes_weighted_centres",
+                                   PASS2_AXES_DTYPE, seq_slots, first, n, out, radius, cut_threshold, pov_mode, stream,
+                                   weights=(C.byref(desc), ptr, stride))
+
+    def track_advance(self, seq_slots, state, out, params=None, weights=None, stream=None):
+        """Advect the tracks of `state` through the fields in flow slots seq_slots, in that order (ffl_track_advance, DESIGN.md
+        section 23): `state` is device memory of T TRACK_STATE_DTYPE records (pipeline.track_state makes one), read and
+        written; `out` device memory for at least len(seq_slots) * T TRACK_DTYPE records, record (i, t) at index i * T + t
+        (a slice of a longer buffer serves a batch of a chunk).  `params`: a TrackParams, a dict of its fields or None
+        (the defaults); `weights`: maps of the items as pass1_weighted takes them, or None.  Queued behind the work on
+        `stream` (None: torch's current stream) and the slots' last writers; `stream` waits for it; the host does not wait.
+        Returns `out`."""
+        ps, slots = _iarr(seq_slots)
+        n = len(slots)
+        prm = params if isinstance(params, TrackParams) else TrackParams(**dict(params or {}))
+        sptr, sbytes = _device_span(state)
+        tracks = sbytes // TRACK_STATE_DTYPE.itemsize
+        if tracks < 1 or sbytes % TRACK_STATE_DTYPE.itemsize:
+            raise ValueError(f"track_advance: state holds {sbytes} bytes, no whole number of {TRACK_STATE_DTYPE.itemsize}-byte records")
+        optr, extent = _device_span(out)
+        if extent < n * tracks * TRACK_DTYPE.itemsize:
+            raise ValueError(f"track_advance: out holds {extent} bytes, {n} x {tracks} records need {n * tracks * TRACK_DTYPE.itemsize}")
+        wdesc = None if weights is None else self._weights("track_advance", weights, n)
+        self._chk(self.L.ffl_track_advance(self._h, n, ps, tracks, C.byref(prm), None if wdesc is None else C.byref(wdesc), sptr, optr,
+                                           stream_handle(stream, self.device)))
+        return out
+
+    def roi_weights(self, n, centres, out, params=None, gate=None, stream=None):
+        """Elliptical ROI maps (ffl_roi_weights): item i about the centre `centres` holds for it, as
+        radial_window_axes_centres takes centres (n of them) or a (buffer, byte stride) span, written into `out`, a uint8
+        device tensor (n, H, W) (or a DevWeights; (H, W) for one item).  `params`: a RoiParams, a dict of its fields or None
+        (the defaults, which are not tuned on footage); `gate`: maps S of rule E5 as pass1_weighted takes maps -- or `out`
+        itself, which min-combines the ellipse into the maps that are already there, in place.  Queued behind the work on
+        `stream`, which waits for it.  Returns `out`."""
+        n = int(n)
+        prm = params if isinstance(params, RoiParams) else RoiParams(**dict(params or {}))
+        ptr, stride = _centre_entries(centres, n)
+        odesc = self._weights("roi_weights", out, n)
+        gdesc = None if gate is None else odesc if gate is out else self._weights("roi_weights", gate, n)
+        self._chk(self.L.ffl_roi_weights(self._h, n, ptr, stride, C.byref(prm), None if gdesc is None else C.byref(gdesc),
+                                         C.byref(odesc), stream_handle(stream, self.device)))
+        return out
 
     def motion_fit(self, slots, model="translation", iterations=3, tau=1.0, weights=None, prior=None, out=None, sums_out=None,
                    stream=None):

@@ -3156,10 +3156,10 @@ int ffl_texture_weights(ffl_ctx *c, int n, const int *fslots, const ffl_texture_
 
 static const char *kHostCentres ="centres live in device memory (ffl_cell_stats' records, or a float64 (n_seq, 2) tensor)";
 
-// What a window call computes: ffl_radial_window (axes = false: ffl_pass2_record) or one of the three ffl_radial_window_axes*
+// What a window call computes: ffl_radial_window (axes = false: ffl_pass2_record) or one of the four ffl_radial_window_axes*
 // (ffl_axes_record).  weighted / centred name the entry point, since a NULL descriptor or NULL centres_dev from the caller
-// is refused, not taken for another form.  Either brings a second region of caller memory: the maps of the n computed
-// items, or the n_seq centres.
+// is refused, not taken for another form.  Either brings one more region of caller memory: the maps of the n computed
+// items, or the n_seq centres; ffl_radial_window_axes_weighted_centres sets both.
 struct WindowForm {
     bool axes, weighted, centred;
     const ffl_dev_weights *wts;
@@ -3167,7 +3167,7 @@ struct WindowForm {
     ptrdiff_t cstride;
 };
 
-// One protocol for the four.
+// One protocol for the five.
 static int radial_window_call(ffl_ctx *c, const char *fn, const WindowForm &form, int n_seq, const int *seq, int first, int n,
                               int radius, float cut_threshold, int pov_mode, void *out, uint64_t stream) {
     if (!c) return FFL_ERR_INVALID;
@@ -3187,7 +3187,7 @@ static int radial_window_call(ffl_ctx *c, const char *fn, const WindowForm &form
     // a slot's state stands for its record and its flow alike, so one check covers the neighbours and the computed items
     if (int rc = check_flow_slots(c, fn, n_seq, seq, "result", "repeated in one call")) return rc;
     if ((uintptr_t)out % 8) return set_err(c, FFL_ERR_INVALID, "%s: out_dev must be 8-byte aligned", fn);
-    PostRegion reg[2] = {
+    PostRegion reg[3] = {
         {"out_dev", out, rec_bytes * (size_t)n, "results in host memory come from ffl_pass1_results and ffl_radial"}};
     int nreg = 1;
     const ffl_dev_weights *wts = form.wts;
@@ -3247,6 +3247,13 @@ int ffl_radial_window_axes_centres(ffl_ctx *c, int n_seq, const int *seq, int fi
                               n_seq, seq, first, n, radius, cut_threshold, pov_mode, out, stream);
 }
 
+int ffl_radial_window_axes_weighted_centres(ffl_ctx *c, int n_seq, const int *seq, int first, int n, int radius, float cut_threshold,
+                                            int pov_mode, const ffl_dev_weights *w, const void *centres_dev,
+                                            ptrdiff_t centre_stride_bytes, ffl_axes_record *out, uint64_t stream) {
+    return radial_window_call(c, "ffl_radial_window_axes_weighted_centres", {true, true, true, w, centres_dev, centre_stride_bytes},
+                              n_seq, seq, first, n, radius, cut_threshold, pov_mode, out, stream);
+}
+
 // ---- per-cell statistics and the variance centre -----------------------------------
 static_assert(sizeof(ffl_cell_record) == 32 && sizeof(CellRecord) == 32 && offsetof(ffl_cell_record, mean_u) == offsetof(CellRecord, mean_u) &&
               offsetof(ffl_cell_record, mean_v) == offsetof(CellRecord, mean_v) && offsetof(ffl_cell_record, mean_mag) == offsetof(CellRecord, mean_mag) &&
@@ -3302,6 +3309,145 @@ int ffl_cell_stats(ffl_ctx *c, int n, const int *slots, int cells, ffl_cell_reco
     ffl_launch_cell_stats(c->d_flow, t, n, c->w, c->h, cells, (CellRecord *)cells_dev, (GridCentre *)centres_dev, c->d_cellrow,
                           c->s_post);
     return post_end(c, cst, n, slots);  // the caller may read, overwrite or free the outputs on `stream` straight after the call
+}
+
+// ---- region tracking and ROI maps (appendices Q and E) -------------------------------------------
+static_assert(sizeof(ffl_track_state) == 48 && sizeof(TrackState) == 48 && offsetof(ffl_track_state, home_x) == offsetof(TrackState, home_x) &&
+              offsetof(ffl_track_state, steps) == 32 && offsetof(TrackState, steps) == 32 && offsetof(ffl_track_state, lost_run) == 40 &&
+              offsetof(TrackState, lost_run) == 40 && alignof(ffl_track_state) == 8, "TrackState mirrors ffl_track_state");
+static_assert(sizeof(ffl_track_record) == 48 && sizeof(TrackRecord) == 48 && offsetof(ffl_track_record, x) == 0 && offsetof(TrackRecord, x) == 0 &&
+              offsetof(ffl_track_record, y) == 8 && offsetof(TrackRecord, y) == 8 && offsetof(ffl_track_record, du) == offsetof(TrackRecord, du) &&
+              offsetof(ffl_track_record, sw) == 32 && offsetof(TrackRecord, sw) == 32 && offsetof(ffl_track_record, count) == 40 &&
+              offsetof(TrackRecord, count) == 40 && offsetof(ffl_track_record, status) == 44 && offsetof(TrackRecord, status) == 44 &&
+              alignof(ffl_track_record) == 8, "TrackRecord mirrors ffl_track_record");
+static_assert((int)FFL_MAX_TRACKS == FFL_TRACK_MAX_T && (int)FFL_MAX_TRACK_RADIUS == FFL_TRACK_MAX_R && (int)FFL_TRACK_HOLD == TRK_HOLD &&
+              (int)FFL_TRACK_HOME == TRK_HOME && (int)FFL_TRACK_OK == TRK_OK && (int)FFL_TRACK_CUT == TRK_CUT && (int)FFL_TRACK_LOST == TRK_LOST &&
+              (int)FFL_TRACK_CLAMPED == TRK_CLAMPED, "ffl.h and ffl_kernels.h agree");
+
+int ffl_track_default_params(ffl_track_params *out) {
+    if (!out) return FFL_ERR_INVALID;
+    *out = ffl_track_params{12, FFL_TRACK_HOLD, 7.0f};   // the radius: the project's own choice, not tuned on footage; 7.0f: FF:876
+    return FFL_OK;
+}
+
+// The accepted parameters of appendix Q.
+static int track_params_check(ffl_ctx *c, const char *fn, const ffl_track_params *p) {
+    if (!p) return set_err(c, FFL_ERR_INVALID, "%s: NULL parameters", fn);
+    if (p->radius < 1 || p->radius > FFL_MAX_TRACK_RADIUS)
+        return set_err(c, FFL_ERR_INVALID, "%s: radius = %d outside 1..%d (FFL_MAX_TRACK_RADIUS)", fn, p->radius, (int)FFL_MAX_TRACK_RADIUS);
+    if (p->on_cut != FFL_TRACK_HOLD && p->on_cut != FFL_TRACK_HOME)
+        return set_err(c, FFL_ERR_INVALID, "%s: on_cut = %d is neither 0 (FFL_TRACK_HOLD) nor 1 (FFL_TRACK_HOME)", fn, p->on_cut);
+    if (p->cut_threshold != p->cut_threshold) return set_err(c, FFL_ERR_INVALID, "%s: cut_threshold is NaN", fn);
+    return FFL_OK;
+}
+
+int ffl_track_params_check(const ffl_track_params *p) { return track_params_check(nullptr, "ffl_track_params_check", p); }
+
+// n_tracks points through n slots that hold a flow, by ONE k_track launch of n_tracks workgroups on stream `post`:
+// ffl_cell_stats' protocol, with the flow, its records and the maps only read.
+int ffl_track_advance(ffl_ctx *c, int n, const int *slots, int n_tracks, const ffl_track_params *p, const ffl_dev_weights *w,
+                      ffl_track_state *state_dev, ffl_track_record *out_dev, uint64_t stream) {
+    static const char *fn = "ffl_track_advance";
+    static const char *hint = "the track's state and records live in device memory (torch / hipMalloc)";
+    if (!c) return FFL_ERR_INVALID;
+    std::unique_lock<std::mutex> pl(c->post_mu);  // stream `post`
+    CtxLock lk(c->mu);
+    ExportTab t;
+    if (int rc = open_slot_list(c, fn, "items", n, slots, "flow", &t)) return rc;
+    if (n_tracks < 1 || n_tracks > FFL_MAX_TRACKS)
+        return set_err(c, FFL_ERR_INVALID, "%s: n_tracks = %d outside 1..%d (FFL_MAX_TRACKS)", fn, n_tracks, (int)FFL_MAX_TRACKS);
+    ffl_track_params prm;
+    ffl_track_default_params(&prm);
+    if (p) prm = *p;
+    if (int rc = track_params_check(c, fn, &prm)) return rc;
+    size_t wbytes = 0;
+    if (w)
+        if (int rc = dev_weights_check(c, fn, n, c->w, c->h, w, &wbytes)) return rc;
+    if (!state_dev || !out_dev) return set_err(c, FFL_ERR_INVALID, "%s: NULL %s", fn, !state_dev ? "state_dev" : "out_dev");
+    if ((uintptr_t)state_dev % 8 || (uintptr_t)out_dev % 8)
+        return set_err(c, FFL_ERR_INVALID, "%s: state_dev and out_dev must be 8-byte aligned", fn);
+    const size_t sbytes = sizeof(ffl_track_state) * (size_t)n_tracks, obytes = sizeof(ffl_track_record) * (size_t)n * (size_t)n_tracks;
+    const uintptr_t s0 = (uintptr_t)state_dev, o0 = (uintptr_t)out_dev;
+    if (s0 < o0 + obytes && o0 < s0 + sbytes)
+        return set_err(c, FFL_ERR_INVALID, "%s: overlap: state_dev (%zu bytes) and out_dev (%zu bytes) share memory", fn, sbytes, obytes);
+    PostRegion reg[3] = {{"state_dev", state_dev, sbytes, hint}, {"out_dev", out_dev, obytes, hint}};
+    int nreg = 2;
+    if (w) reg[nreg++] = PostRegion{"the weight maps", w->base, wbytes, kHostWeights};
+    hipStream_t cst;
+    if (int rc = post_begin(c, fn, stream, &cst, reg, nreg, n, slots)) return rc;
+    WeightArgs wa{};
+    if (w) wa = WeightArgs{(const char *)w->base, (long long)w->item_stride, (long long)w->row_pitch};
+    ffl_launch_track(c->d_flow, c->d_res, t, n, n_tracks, c->w, c->h, prm.radius, prm.on_cut, prm.cut_threshold, w ? &wa : nullptr,
+                     (TrackState *)state_dev, (TrackRecord *)out_dev, c->s_post);
+    return post_end(c, cst, n, slots);  // the caller may read the records, or re-seed the state, on `stream` straight after the call
+}
+
+int ffl_roi_default_params(ffl_roi_params *out) {
+    if (!out) return FFL_ERR_INVALID;
+    *out = ffl_roi_params{48.0f, 48.0f, 1};   // the project's own choice, not tuned on footage
+    return FFL_OK;
+}
+
+// The accepted parameters of appendix E.  The comparisons are written so that a NaN fails them.
+static int roi_params_check(ffl_ctx *c, const char *fn, const ffl_roi_params *p) {
+    if (!p) return set_err(c, FFL_ERR_INVALID, "%s: NULL parameters", fn);
+    if (!(p->ax >= 0.5f && p->ax <= 32768.0f) || !(p->ay >= 0.5f && p->ay <= 32768.0f))
+        return set_err(c, FFL_ERR_INVALID, "%s: half-axes (%g, %g) outside 0.5..32768 (finite)", fn, (double)p->ax, (double)p->ay);
+    if (p->soft != 0 && p->soft != 1) return set_err(c, FFL_ERR_INVALID, "%s: soft = %d is neither 0 (hard) nor 1 (soft)", fn, p->soft);
+    return FFL_OK;
+}
+
+int ffl_roi_params_check(const ffl_roi_params *p) { return roi_params_check(nullptr, "ffl_roi_params_check", p); }
+
+// n maps about n centres by ONE k_roi_weights launch on stream `post`: ffl_texture_weights' protocol without frame slots.  The
+// call names no slot; post_end() records its event all the same (publish_post records before it publishes), and that event is
+// what the caller's stream waits for.
+int ffl_roi_weights(ffl_ctx *c, int n, const void *centres_dev, ptrdiff_t cstride, const ffl_roi_params *p, const ffl_dev_weights *gate,
+                    const ffl_dev_weights *out, uint64_t stream) {
+    static const char *fn = "ffl_roi_weights";
+    if (!c) return FFL_ERR_INVALID;
+    std::unique_lock<std::mutex> pl(c->post_mu);  // stream `post`, as ffl_texture_weights
+    CtxLock lk(c->mu);
+    if (n < 1 || n > c->max_batch)
+        return set_err(c, FFL_ERR_INVALID, "%s: n = %d items outside 1..%d (the context's max_batch)", fn, n, c->max_batch);
+    ffl_roi_params prm;
+    ffl_roi_default_params(&prm);
+    if (p) prm = *p;
+    if (int rc = roi_params_check(c, fn, &prm)) return rc;
+    size_t obytes, gbytes = 0;
+    if (!out) return set_err(c, FFL_ERR_INVALID, "%s: NULL out descriptor", fn);
+    if (int rc = dev_weights_check(c, fn, n, c->w, c->h, out, &obytes)) return rc;
+    if (n > 1 && out->item_stride == 0)
+        return set_err(c, FFL_ERR_INVALID, "%s: overlap: out item stride 0 with n = %d maps to write (one map per item)", fn, n);
+    bool in_place = false;
+    const uintptr_t o0 = (uintptr_t)out->base;
+    if (gate) {
+        if (int rc = dev_weights_check(c, fn, n, c->w, c->h, gate, &gbytes)) return rc;
+        in_place = gate->base == out->base && gate->item_stride == out->item_stride && gate->row_pitch == out->row_pitch;
+        const uintptr_t g0 = (uintptr_t)gate->base;
+        if (!in_place && o0 < g0 + gbytes && g0 < o0 + obytes)
+            return set_err(c, FFL_ERR_INVALID, "%s: overlap: out (%zu bytes) and gate (%zu bytes) share memory, and gate is not "
+                                               "exactly out (same base, item stride and row pitch: the in-place form)",
+                           fn, obytes, gbytes);
+    }
+    if (!centres_dev) return set_err(c, FFL_ERR_INVALID, "%s: NULL centres_dev", fn);   // rule E1
+    if ((uintptr_t)centres_dev % 8) return set_err(c, FFL_ERR_INVALID, "%s: centres_dev must be 8-byte aligned", fn);
+    if (cstride < 16 || cstride % 8 || cstride > ((ptrdiff_t)1 << 40))
+        return set_err(c, FFL_ERR_INVALID, "%s: centre stride %td: a multiple of 8 bytes, at least 16 (two doubles)", fn, cstride);
+    const size_t cbytes = (size_t)(n - 1) * (size_t)cstride + 16;
+    const uintptr_t c0 = (uintptr_t)centres_dev;
+    if (o0 < c0 + cbytes && c0 < o0 + obytes)
+        return set_err(c, FFL_ERR_INVALID, "%s: overlap: out (%zu bytes) and the centres (%zu bytes) share memory", fn, obytes, cbytes);
+    hipStream_t cst;
+    PostRegion reg[3] = {{"out", out->base, obytes, kHostWeights}, {"centres_dev", centres_dev, cbytes, kHostCentres}};
+    int nreg = 2;
+    if (gate && !in_place) reg[nreg++] = PostRegion{"the gate maps", gate->base, gbytes, kHostWeights};
+    if (int rc = post_begin(c, fn, stream, &cst, reg, nreg, 0, nullptr)) return rc;
+    WeightArgs ga;
+    if (gate) ga = WeightArgs{(const char *)gate->base, (long long)gate->item_stride, (long long)gate->row_pitch};
+    ffl_launch_roi_weights((const char *)centres_dev, (long long)cstride, n, c->w, c->h, prm.ax, prm.ay, prm.soft, gate ? &ga : nullptr,
+                           (char *)out->base, (long long)out->item_stride, (long long)out->row_pitch, c->s_post);
+    return post_end(c, cst, 0, nullptr);  // the caller may read the maps, or overwrite the gate or the centres, on `stream` straight after
 }
 
 // ---- global-motion fit and compensation ---------------------------------------------

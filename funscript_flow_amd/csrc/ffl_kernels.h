@@ -356,6 +356,30 @@ void ffl_launch_residual(const unsigned char *gray, const float *flow, const Exp
 void ffl_launch_texture(const unsigned char *gray, const ExportTab &fr, int n, int w, int h, int radius, float tau, int soft,
                         const WeightArgs *gate, char *out, long long out_item, long long out_pitch, hipStream_t st);
 
+// ---- region tracking and ROI maps (kernels_track.hip; DESIGN.md section 23, appendices Q and E) --------------------
+#define FFL_TRACK_MAX_R 32           // = FFL_MAX_TRACK_RADIUS of include/ffl.h
+#define FFL_TRACK_MAX_T 8            // = FFL_MAX_TRACKS
+enum { TRK_HOLD = 0, TRK_HOME = 1 };                             // = FFL_TRACK_HOLD, FFL_TRACK_HOME
+enum { TRK_OK = 0, TRK_CUT = 1, TRK_LOST = 2, TRK_CLAMPED = 4 }; // = FFL_TRACK_* status bits
+struct TrackState {  // = ffl_track_state of include/ffl.h (ffl_api.hip asserts the layout)
+    double x, y, home_x, home_y;
+    long long steps;
+    int lost_run, pad;
+};
+struct TrackRecord { // = ffl_track_record
+    double x, y, du, dv, sw;
+    int count, status;
+};
+// n_tracks points through flow slots tab.slot[0..n) of `flow` in order (k_track, one workgroup per track): record (i, t) to
+// out[i * n_tracks + t], state[t] read and written.  res: the slots' pass-1 records (rule Q5).  maps.base NULL: no map.
+void ffl_launch_track(const float *flow, const Pass1Result *res, const ExportTab &tab, int n, int n_tracks, int w, int h,
+                      int radius, int on_cut, float cut_threshold, const WeightArgs *maps, TrackState *state, TrackRecord *out,
+                      hipStream_t st);
+// item b's elliptical map about the two doubles at cen + b * cstride (k_roi_weights) goes to out + b * out_item, rows
+// out_pitch bytes apart; gate (may be NULL): the maps of rule E5, which may be exactly `out` (min-combined in place)
+void ffl_launch_roi_weights(const char *cen, long long cstride, int n, int w, int h, float ax, float ay, int soft,
+                            const WeightArgs *gate, char *out, long long out_item, long long out_pitch, hipStream_t st);
+
 // ---- global-motion fit and compensation (kernels_post.hip) -----------------------
 #define FFL_MOTION_NSUMS 12          // = FFL_MOTION_N_SUMS of include/ffl.h; the order of rule C4
 enum { MOT_S = 0, MOT_SX, MOT_SY, MOT_SXX, MOT_SXY, MOT_SYY, MOT_SU, MOT_SUX, MOT_SUY, MOT_SV, MOT_SVX, MOT_SVY };

@@ -141,6 +141,54 @@ def motion_records(buf, n=None, device=None):
     return np.frombuffer(raw.tobytes(), _capi.MOTION_DTYPE, n)
 
 
+def track_buffer(ctx, n, tracks=1):
+    """a device buffer for the n * tracks 48-byte track records of a chunk (torch uint8 on the context's device), as track_out=
+    and Context.track_advance(out=) take it: record (pair j, track t) at byte 48 * (j * tracks + t)"""
+    import torch
+    return torch.empty(n * int(tracks) * _capi.TRACK_DTYPE.itemsize, dtype=torch.uint8, device=torch.device("cuda", ctx.device))
+
+
+def track_records(buf, tracks=1, n=None, device=None):
+    """The track records of a chunk run with center="track" (or of Context.track_advance) as a numpy array (n, tracks) of
+    _capi.TRACK_DTYPE (fields x, y -- the track's place in frame 0 of the pair --, du, dv, sw, count, status).  The copy runs on
+    torch's current stream, behind the calls that filled `buf` there, and waits for them (see post_records for `device`)."""
+    import torch
+    if not isinstance(buf, torch.Tensor):
+        buf = torch.as_tensor(buf, device=torch.device("cuda", torch.cuda.current_device() if device is None else device))
+    item = int(tracks) * _capi.TRACK_DTYPE.itemsize
+    raw = buf.contiguous().view(torch.uint8).reshape(-1)
+    n = raw.numel() // item if n is None else n
+    raw = raw[:n * item].cpu().numpy()
+    return np.frombuffer(raw.tobytes(), _capi.TRACK_DTYPE, n * int(tracks)).reshape(n, int(tracks))
+
+
+def track_state_array(points, home=None):
+    """(T,) _capi.TRACK_STATE_DTYPE records on the host out of `points`, (x, y) or (T, 2): the tracks' positions; `home`
+    (the same form, default: the points) is where on_cut="home" sends a track.  steps and lost_run start at 0."""
+    p = np.asarray(points, np.float64).reshape(-1, 2)
+    hm = p if home is None else np.asarray(home, np.float64).reshape(-1, 2)
+    if not 1 <= len(p) <= _capi.FFL_MAX_TRACKS or hm.shape != p.shape:
+        raise ValueError(f"track: {len(p)} points and {len(hm)} home points; 1..{_capi.FFL_MAX_TRACKS} (x, y) pairs, as many of each")
+    st = np.zeros(len(p), _capi.TRACK_STATE_DTYPE)
+    st["x"], st["y"], st["home_x"], st["home_y"] = p[:, 0], p[:, 1], hm[:, 0], hm[:, 1]
+    return st
+
+
+def track_state(ctx, points, home=None):
+    """a device tensor (torch uint8, 48 bytes per track) of ffl_track_state records for Context.track_advance and
+    track={"state": ...}: see track_state_array.  The library reads and writes it, so it carries a track from call to call and
+    from chunk to chunk; a detector may overwrite it in between."""
+    import torch
+    st = track_state_array(points, home)
+    return torch.from_numpy(st.view(np.uint8).copy()).to(torch.device("cuda", ctx.device))
+
+
+def track_state_records(state):
+    """the ffl_track_state records of a device state tensor as a numpy array (T,) of _capi.TRACK_STATE_DTYPE"""
+    raw = state.contiguous().view(-1).cpu().numpy()
+    return np.frombuffer(raw.tobytes(), _capi.TRACK_STATE_DTYPE)
+
+
 def _stream_event(ctx, stream=None):
     """an event recorded on `stream` (None: torch's current stream of the context's device): query() / synchronize()"""
     import torch
@@ -367,7 +415,8 @@ class PairEngine:
 
     def process_chunk(self, frames, pov_mode=False, cut_threshold=7.0, algo=None, farneback=OWN, flows_out=None, window=OWN,
                       post_out=None, axes=False, weights=None, center=None, cells=32, grid_out=None, consistency=None,
-                      weights_out=None, weights_gate=None, compensate=None, motion_out=None, residual=None, texture=None):
+                      weights_out=None, weights_gate=None, compensate=None, motion_out=None, residual=None, texture=None,
+                      track=None, track_out=None):
         """One whole chunk on one GPU: returns (dots float64[n], records) with n = len(frames)-1.  `algo`, `farneback`,
         `window`: see pass1_pairs (default: the engine's own flow algorithm, parameters and window).  `flows_out`: a float32 device array of
         (n, H, W, 2) or (n, 2, H, W) that receives every pair's flow field (Context.export_flows, on torch's current stream)
@@ -418,9 +467,23 @@ class PairEngine:
         device memory for n 64-byte records (motion_buffer; motion_records reads it), the fitted model of every pair -- the
         camera path.  Not combined with weights="consistency" (the maps need both raw directions, and the ring holds the
         reversed pairs).  With weights="residual" the order behind a batch is: the maps from the raw fields, the fit (which
-        the maps weight), the subtraction.  Without compensate= nothing of this runs."""
+        the maps weight), the subtraction.  Without compensate= nothing of this runs.
+        `center` = "track" (DESIGN.md section 23): every pass-2 term about a point that follows the flow from pair to pair.
+        `track`: a dict -- "state" (a track_state tensor of 1..8 tracks, read and written: hand it to the next chunk) or "start"
+        ((x, y) or (T, 2), with "home" alike); "radius" and "on_cut" ("hold" | "home") of _capi.TrackParams, whose cut
+        threshold is the chunk's; "roi": None or the half-axes (ax, ay) of an elliptical map about the track, "roi_soft" its
+        form.  The chunk runs the device schedule with 80-byte records.  Behind each batch Context.track_advance is queued on
+        its slots in pair order -- on the raw fields, ahead of compensate='s fit and subtraction -- and writes into the
+        chunk-long buffer of 48-byte records (`track_out`, a track_buffer, or a new one; track_records reads it).  Without
+        "roi" the window calls are Context.radial_window_axes_centres about track 0's records; with it Context.roi_weights
+        writes the batch's maps into an (n, H, W) tensor (`weights_out`, or a new one; `weights_gate`: the static gate of rule
+        E5), Context.pass1_weighted follows and the window calls are Context.radial_window_axes_weighted_centres.  weights= of
+        any form is refused next to it."""
         ctx, B = self.ctx, self.B
         n = len(frames) - 1
+        trk = _chunk_track(ctx, n, center, track, track_out, weights, weights_out, weights_gate, ctx.flow_slots, cut_threshold)
+        if trk is not None and trk.roi is not None:   # the keywords are the track's
+            weights_out = weights_gate = None
         if compensate is not None and isinstance(weights, str) and weights == "consistency":
             raise ValueError(f"compensate= together with weights={weights!r} is not supported: the consistency maps need both "
                              "raw directions of every pair, and the slot ring holds the reversed pairs")
@@ -430,11 +493,14 @@ class PairEngine:
             weights, B = cons.maps, cons.B
         if resid is not None:
             weights = resid.maps
+        if trk is not None:
+            weights = trk.maps
         ring = ctx.flow_slots if cons is None else cons.ring
         maps = weights   # the tensor stays referenced while the calls that read it are queued
         post_out, axes, weights, grid = _chunk_post_args(ctx, n, post_out, axes, weights, center, cells, grid_out,
-                                                         check_empty=False)
-        comp = _chunk_motion(ctx, n, compensate, motion_out, weights, ring, pov_mode)
+                                                         check_empty=False, device=trk is not None)
+        # the ROI maps say where the subject is, not what is reliable, and are written behind the fit's place: it runs unweighted
+        comp = _chunk_motion(ctx, n, compensate, motion_out, None if trk is not None else weights, ring, pov_mode)
         if n < 1:
             return (_no_scalars(axes), []) if post_out is None else post_out
         layout = None
@@ -446,7 +512,7 @@ class PairEngine:
                 raise ValueError(f"flows_out must be ({n}, {ctx.height}, {ctx.width}, 2) or ({n}, 2, {ctx.height}, "
                                  f"{ctx.width}), got {shp}")
         if post_out is not None:
-            post = _DevicePost(ctx, n, B, pov_mode, cut_threshold, post_out, axes, weights, grid, ring, cons)
+            post = _DevicePost(ctx, n, B, pov_mode, cut_threshold, post_out, axes, weights, grid, ring, cons, trk)
             release = getattr(frames, "release", None)
             marks = []   # (event, frames that have left the host once it completes), oldest first
 
@@ -454,6 +520,8 @@ class PairEngine:
                 comp.stream = post.stream
             if resid is not None:
                 resid.stream = post.stream
+            if trk is not None:
+                trk.stream = post.stream
 
             def queued(ls, js):
                 if layout is not None:   # before the window calls below let later batches recycle these slots
@@ -473,7 +541,8 @@ class PairEngine:
                     release(upto)
 
             self.pass1_pairs(frames, range(n), lambda l: l % ring, pov_mode, cut_threshold, algo=algo,
-                             farneback=farneback, window=window, queued=queued, **_behind_kw(comp), **_frames_kw(resid),
+                             farneback=farneback, window=window, queued=queued,
+                             **_chain(trk and trk.behind, comp and comp.behind), **_frames_kw(resid),
                              **({} if cons is None else {"batch": B, "reverse_slot_of": cons.bwd_slot}))
             if marks:
                 marks[-1][0].synchronize()   # the ring's slots may be reused by the next chunk: every transfer is over
@@ -491,7 +560,8 @@ class PairEngine:
         return post.finish()
 
     def process_flows(self, flows, pov_mode=False, cut_threshold=7.0, post_out=None, axes=False, weights=None, center=None,
-                      cells=32, grid_out=None, compensate=None, motion_out=None):
+                      cells=32, grid_out=None, compensate=None, motion_out=None, track=None, track_out=None, weights_out=None,
+                      weights_gate=None):
         """One whole chunk from flow fields the caller computed: returns (dots float64[n], records), the contract of
         process_chunk.  `flows` holds the chunk's n pair fields in device memory: one array (n, H, W, 2) or (n, 2, H, W)
         (float32, float16 or bfloat16, any strides; see _capi.device_flows) or a sequence of such arrays (single (H, W, 2)
@@ -502,7 +572,8 @@ class PairEngine:
         weights: the device schedule, 80-byte records, pass1_weighted behind each import).  `center`, `cells`, `grid_out`:
         as in process_chunk (center="variance": the device schedule, 80-byte records, cell_stats behind each import).
         `compensate`, `motion_out`: as in process_chunk -- motion_fit and motion_subtract in place behind each import, before
-        anything reads the imported fields' records."""
+        anything reads the imported fields' records.  `center` = "track", `track`, `track_out`, and with track["roi"]
+        `weights_out` and `weights_gate`: as in process_chunk -- track_advance behind each import, ahead of the fit."""
         ctx, B, fs = self.ctx, self.B, self.ctx.flow_slots
         if isinstance(weights, str) and weights == "residual":
             raise ValueError("process_flows: weights='residual' needs the frames, which a chunk of caller flows does not have; "
@@ -519,15 +590,23 @@ class PairEngine:
             desc, dt, k = _capi.device_flows(a, ctx.width, ctx.height)
             segs.append((desc, dt, n, k))
             n += k
+        trk = _chunk_track(ctx, n, center, track, track_out, weights, weights_out, weights_gate, fs, cut_threshold)
+        if trk is None and (weights_out is not None or weights_gate is not None):
+            raise ValueError("process_flows: weights_out= and weights_gate= need center='track' with track['roi']")
+        if trk is not None:
+            weights = trk.maps
         maps = weights   # the tensor stays referenced while the calls that read it are queued
-        post_out, axes, weights, grid = _chunk_post_args(ctx, n, post_out, axes, weights, center, cells, grid_out)
+        post_out, axes, weights, grid = _chunk_post_args(ctx, n, post_out, axes, weights, center, cells, grid_out,
+                                                         device=trk is not None)
         if n < 1:
             return (_no_scalars(axes), []) if post_out is None else post_out
         post = (_ChunkPost(ctx, n, B, pov_mode, axes) if post_out is None else
-                _DevicePost(ctx, n, B, pov_mode, cut_threshold, post_out, axes, weights, grid))
-        comp = _chunk_motion(ctx, n, compensate, motion_out, weights, fs, pov_mode)
+                _DevicePost(ctx, n, B, pov_mode, cut_threshold, post_out, axes, weights, grid, track=trk))
+        comp = _chunk_motion(ctx, n, compensate, motion_out, None if trk is not None else weights, fs, pov_mode)
         if comp is not None and post_out is not None:
             comp.stream = post.stream
+        if trk is not None:
+            trk.stream = post.stream
 
         def enqueue(j0):
             j1 = min(j0 + B, n)
@@ -539,6 +618,8 @@ class PairEngine:
                                      desc.pixel_stride, desc.channel_stride)
                 ctx.import_flows_desc(part, dt, [j % fs for j in range(lo, hi)], pov_mode)
             js = list(range(j0, j1))
+            if trk is not None:
+                trk.behind(js, js)
             if comp is not None:
                 comp.behind(js, js)
             return js
@@ -707,10 +788,96 @@ def chunk_center(center):
     return center
 
 
+TRACK_KEYS = ("state", "start", "home", "radius", "on_cut", "roi", "roi_soft")
+
+
+class _ChunkTrack:
+    """center="track" of a chunk of n pairs: behind(ls, js) queues Context.track_advance on the slots of
+    the chunk's pairs ls (the l-th pair in flow slot l % ring), in pair order, with the records of pair l at byte 48 * T * l of
+    the chunk's buffer (track_out, or a new one) -- on the RAW fields, ahead of compensate='s fit and subtraction and of
+    pass1_weighted, so rule Q5's cut is the unweighted whole-frame mean magnitude.  With roi, Context.roi_weights then writes
+    the pairs' maps about track 0's records into the chunk's (n, H, W) uint8 tensor `maps` (weights_out, or a new one; gate:
+    the static gate of rule E5).  state: the device tensor of T ffl_track_state records, read and written, which the caller
+    carries to the next chunk.  stream: where the calls are queued (the device schedule sets its side stream)."""
+
+    def __init__(self, ctx, n, track, track_out, maps_out, gate, ring, cut_threshold):
+        if not isinstance(track, dict) or not (("state" in track) ^ ("start" in track)):
+            raise ValueError("center='track' needs track= {'state': a track_state tensor} or {'start': (x, y) or (T, 2)}, one of "
+                             "the two")
+        unknown = [k for k in track if k not in TRACK_KEYS]
+        if unknown:
+            raise ValueError(f"track=: unknown key {unknown[0]!r} (one of {TRACK_KEYS})")
+        self.ctx, self.n, self.ring = ctx, n, int(ring)
+        over = {k: track[k] for k in ("radius", "on_cut") if track.get(k) is not None}
+        self.params = _capi.track_choice(_capi.TrackParams(cut_threshold=float(cut_threshold), **over))
+        if "state" in track:
+            if "home" in track:
+                raise ValueError("track=: 'home' goes with 'start' (a state carries its own home position)")
+            self.state = track["state"]
+        else:
+            self.state = track_state(ctx, track["start"], track.get("home"))
+        _, sbytes = _capi._device_span(self.state)
+        item = _capi.TRACK_STATE_DTYPE.itemsize
+        self.T = sbytes // item
+        if sbytes % item or not 1 <= self.T <= _capi.FFL_MAX_TRACKS:
+            raise ValueError(f"track=: the state holds {sbytes} bytes, 1..{_capi.FFL_MAX_TRACKS} records of {item} are needed")
+        self.item = self.T * _capi.TRACK_DTYPE.itemsize
+        self.out = track_buffer(ctx, max(n, 1), self.T) if track_out is None else track_out   # stays referenced
+        self.base, nbytes = _capi._device_span(self.out)
+        if nbytes < n * self.item:
+            raise ValueError(f"track_out holds {nbytes} bytes, the chunk's {n} x {self.T} records need {n * self.item}")
+        self.roi = self.maps = self.gate = self.gate_tensor = None
+        if track.get("roi") is not None:
+            ax, ay = track["roi"]
+            self.roi = _capi.roi_choice({"ax": float(ax), "ay": float(ay), "soft": int(bool(track.get("roi_soft", True)))})
+            self.maps = _chunk_maps(ctx, n, maps_out)
+            self.gate_tensor, self.gate = gate, _static_gate(ctx, gate)
+        elif maps_out is not None or gate is not None or track.get("roi_soft") is not None:
+            raise ValueError("weights_out=, weights_gate= and track['roi_soft'] need track['roi'] = (ax, ay) with center='track'")
+        self.stream = None
+
+    def centres(self, lo, hi):
+        """the centres of pairs lo .. hi-1 for a window call: track 0's records, one every 48 * T bytes"""
+        return _capi._DeviceSpan(self.base + lo * self.item, (hi - lo) * self.item), self.item
+
+    def behind(self, ls, js):
+        recs = _capi._DeviceSpan(self.base + ls[0] * self.item, len(ls) * self.item)
+        self.ctx.track_advance([l % self.ring for l in ls], self.state, recs, self.params, None, self.stream)
+        if self.roi is not None:
+            self.ctx.roi_weights(len(ls), (recs, self.item), self.maps[ls[0]:ls[-1] + 1], self.roi, self.gate, self.stream)
+
+
+def _chunk_track(ctx, n, center, track, track_out, weights, maps_out, gate, ring, cut_threshold):
+    """None unless center == "track" (track= and track_out= are then refused), else the chunk's _ChunkTrack; weights= of any
+    form is refused next to it"""
+    if center != "track":
+        if track is not None or track_out is not None:
+            raise ValueError("track= and track_out= need center='track'")
+        return None
+    if weights is not None:
+        raise ValueError("center='track' together with weights= (a map or a mode) is not supported: the region's own map is "
+                         "track={'roi': (ax, ay)}, and weights_gate= is its static gate")
+    return _ChunkTrack(ctx, n, track, track_out, maps_out, gate, ring, cut_threshold)
+
+
+def _chain(*hooks):
+    """behind= of several parts of a chunk, in order; None without any"""
+    hooks = [h for h in hooks if h is not None]
+    if not hooks:
+        return {}
+    if len(hooks) == 1:
+        return {"behind": hooks[0]}
+
+    def behind(ls, js):
+        for h in hooks:
+            h(ls, js)
+    return {"behind": behind}
+
+
 def _chunk_grid(ctx, center, cells, grid_out, weights, n):
     """None without center=, else what _DevicePost needs for a chunk of n pairs about the variance centre: (cells, the chunk's
     centre records -- a new device buffer of n 32-byte records -- and grid_out's base address or None)"""
-    if chunk_center(center) is None:
+    if chunk_center(center) is None or center == "track":   # the tracked centres are _chunk_track's
         if grid_out is not None:
             raise ValueError("grid_out needs center='variance'")
         return None
@@ -729,14 +896,15 @@ def _chunk_grid(ctx, center, cells, grid_out, weights, n):
     return cells, centres, base
 
 
-def _chunk_post_args(ctx, n, post_out, axes, weights, center, cells, grid_out, check_empty=True):
+def _chunk_post_args(ctx, n, post_out, axes, weights, center, cells, grid_out, check_empty=True, device=False):
     """The keywords of process_chunk / process_flows as what the schedule of a chunk of n pairs needs: (post_out, axes, the
     chunk's _capi.DevWeights or None, _chunk_grid's tuple or None).  weights= and center= each put the chunk on the device
     schedule with 80-byte records: axes is True and post_out defaults to a new buffer; post_out=True is that buffer from
-    here on (no records for a chunk without pairs, n <= 0).  check_empty=False: the maps of such a chunk are not looked at."""
+    here on (no records for a chunk without pairs, n <= 0).  check_empty=False: the maps of such a chunk are not looked at.
+    device=True (center="track"): the device schedule with 80-byte records whether or not there are maps."""
     grid = _chunk_grid(ctx, center, cells, grid_out, weights, n)
     desc = _chunk_weights(ctx, weights, n) if weights is not None and (n >= 1 or check_empty) else None
-    if grid is not None or weights is not None:
+    if grid is not None or weights is not None or device:
         axes, post_out = True, True if post_out is None else post_out
     if post_out is True:
         post_out = post_buffer(ctx, max(n, 0), axes)
@@ -859,10 +1027,14 @@ class _DevicePost:
     with the centres of their seq read from that buffer -- a neighbour's recycled slot is never re-read for its centre.
     ring: the length of the flow-slot ring the pairs live in (default: every flow slot of the context).  cons (a
     _ChunkConsistency, with weights = the descriptor of its maps): after_batch(k) first of all queues
-    Context.consistency_weights, which writes batch k's maps from its forward slots and cons.bwd_slot's backward ones."""
+    Context.consistency_weights, which writes batch k's maps from its forward slots and cons.bwd_slot's backward ones.
+    track (a _ChunkTrack, with axes; its behind() hook has queued the batch's records, and with roi its maps, which are then
+    `weights`): the calls are Context.radial_window_axes_centres about track 0's records of their seq, read from the track's
+    chunk-long buffer, or with maps Context.radial_window_axes_weighted_centres."""
 
-    def __init__(self, ctx, n, B, pov_mode, cut_threshold, out, axes=False, weights=None, grid=None, ring=None, cons=None):
-        self.ctx, self.pov_mode, self.cut_threshold = ctx, pov_mode, cut_threshold
+    def __init__(self, ctx, n, B, pov_mode, cut_threshold, out, axes=False, weights=None, grid=None, ring=None, cons=None,
+                 track=None):
+        self.ctx, self.pov_mode, self.cut_threshold, self.track = ctx, pov_mode, cut_threshold, track
         self.n, self.B, self.weights, self.grid = n, B, weights, grid
         self.ring, self.cons = (ctx.flow_slots if ring is None else int(ring)), cons
         self.window, self.item = (ctx.radial_window_axes if axes else ctx.radial_window), _post_dtype(axes).itemsize
@@ -894,7 +1066,13 @@ class _DevicePost:
         for lo, hi, first, count, _ in self.calls.get(k, ()):
             out = _capi._DeviceSpan(self.base + (lo + first) * item, count * item)
             seq = [j % fs for j in range(lo, hi)]
-            if self.grid is not None:
+            if self.track is not None and self.weights is not None:
+                self.ctx.radial_window_axes_weighted_centres(seq, first, count, self._maps(lo + first), self.track.centres(lo, hi),
+                                                             out, SMOOTH_RADIUS, self.cut_threshold, self.pov_mode, self.stream)
+            elif self.track is not None:
+                self.ctx.radial_window_axes_centres(seq, first, count, self.track.centres(lo, hi), out, SMOOTH_RADIUS,
+                                                    self.cut_threshold, self.pov_mode, self.stream)
+            elif self.grid is not None:
                 citem = _capi.GRID_CENTRE_DTYPE.itemsize
                 self.ctx.radial_window_axes_centres(seq, first, count,
                                                     _capi._DeviceSpan(self.grid[1].data_ptr() + lo * citem, (hi - lo) * citem), out,
@@ -1010,13 +1188,36 @@ def consistency_kwargs(engine, params):
 
 def center_kwargs(params):
     """{"center": ..., "cells": ...} when params names "hip_center" (params["hip_center_cells"], default 32, its grid), else
-    {}: the keywords of process_chunk / process_flows.  Together with "hip_weights" it is refused."""
+    {}: the keywords of process_chunk / process_flows.  Together with "hip_weights" it is refused.  "hip_center" = "track":
+    {"center": "track", "track": params["hip_track"]} (see process_chunk)."""
     center = chunk_center(params.get("hip_center"))
     if center is None:
+        if params.get("hip_track") is not None:
+            raise ValueError("hip_track needs hip_center = 'track'")
         return {}
     if params.get("hip_weights") is not None:
         raise ValueError("hip_center together with hip_weights is not supported")
+    if center == "track":   # params["hip_track"]: the track= dict of process_chunk / process_flows
+        track = params.get("hip_track")
+        if not isinstance(track, dict):
+            raise ValueError("hip_center = 'track' needs hip_track, a dict such as {'start': (x, y), 'radius': 12, 'roi': (48, 48)}")
+        unknown = [k for k in track if k not in TRACK_KEYS]
+        if unknown:
+            raise ValueError(f"hip_track: unknown key {unknown[0]!r} (one of {TRACK_KEYS})")
+        return {"center": center, "track": dict(track)}
+    if params.get("hip_track") is not None:
+        raise ValueError("hip_track needs hip_center = 'track'")
     return {"center": center, "cells": int(params.get("hip_center_cells", 32))}
+
+
+def _track_carry(engine, params):
+    """{"track_carry": the video's track state} with params["hip_center"] = "track" and a "start" in params["hip_track"], else
+    {}: pairs never span chunks, but the subject does, so one state tensor serves every chunk of a video (a "state" of the
+    caller's does so by itself)"""
+    cen = center_kwargs(params)
+    if cen.get("center") != "track" or "start" not in cen["track"]:
+        return {}
+    return {"track_carry": track_state(engine.ctx, cen["track"]["start"], cen["track"].get("home"))}
 
 
 def _weighted_scalars(buf, axes):
@@ -1043,9 +1244,9 @@ def _flow_chunks(engine, chunk_flows, fps, total_frames, params, axes, who):
                          "have; Context.consistency_weights serves callers with their own estimator")
     if len(chunk_flows) != len(plan):
         raise ValueError(f"{who}: {len(chunk_flows)} chunks of flows for a plan of {len(plan)} chunks")
-    out = []
+    out, carry = [], _track_carry(engine, params)
     for chunk, flows in zip(plan, chunk_flows):
-        d, recs = _chunk_scalars(engine, flows, params, axes, run=engine.process_flows)
+        d, recs = _chunk_scalars(engine, flows, params, axes, run=engine.process_flows, **carry)
         if len(d) != len(chunk) - 1:
             raise ValueError(f"{who}: a chunk of {len(chunk)} frames needs {len(chunk) - 1} fields, got {len(d)}")
         out.append((chunk[:-1], d, recs))
@@ -1080,7 +1281,10 @@ def _chunk_scalars(engine, items, params, axes=False, run=None, **kw):
     run = run or engine.process_chunk
     pov, thr = bool(params.get("pov_mode", False)), float(params.get("cut_threshold", 7))
     kw.update(compensate_kwargs(params))   # params["hip_compensate"]: the fit and the subtraction behind every batch
+    carry = kw.pop("track_carry", None)    # the video's track state, carried from chunk to chunk (_track_carry)
     cen = center_kwargs(params)
+    if carry is not None:
+        cen["track"] = {**{k: v for k, v in cen["track"].items() if k not in ("start", "home")}, "state": carry}
     if cen:   # params["hip_center"]: the device schedule about that centre
         return _weighted_scalars(run(items, pov, thr, **cen, **kw), axes)
     ckw = consistency_kwargs(engine, params)
@@ -1102,10 +1306,10 @@ def _frame_chunks(engine, frames, fps, params, axes):
     algo = _capi.flow_choice(params) if ("hip_flow" in params or "hip_dis" in params) else None
     # params["hip_farneback"] / ["hip_farneback_window"] likewise set the Farneback parameters and window of this call
     fbk = farneback_kwargs(params, frames[0].shape[1], frames[0].shape[0]) if len(frames) else {}
-    out = []
+    out, carry = [], _track_carry(engine, params)
     for chunk in pair_plan(fps, len(frames), params):
         d, recs = _chunk_scalars(engine, [frames[i] for i in chunk], params, axes, **({"algo": algo} if algo is not None else {}),
-                                 **fbk)
+                                 **fbk, **carry)
         out.append((chunk[:-1], d, recs))
     return out
 

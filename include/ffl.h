@@ -46,6 +46,14 @@
  *                           window) as such a weight map or as the gate of the two above -- low on flat regions and on pure
  *                           stripes, where dense flow is unconstrained and both checks above approve of it; needs no flow
  *                           at all
+ *   ffl_track_advance       replaces nothing: the reference finds a centre afresh for every pair (FF:748-758, or FF:721-746)
+ *                           and has no way to say "the subject is here, follow it".  It advects caller-chosen points through
+ *                           the fields of consecutive pairs; its records are centres for ffl_radial_window_axes_centres
+ *                           
+ *   ffl_roi_weights         replaces nothing either: an elliptical weight map about such a centre, which confines pass 1 and
+ *                           pass 2 to the tracked region -- which pixels are the subject, not which are reliable (appendix E)
+ *   ffl_radial_window_axes_weighted_centres  ffl_radial_window_axes_weighted about the centres of
+ *                           ffl_radial_window_axes_centres: the two flags of the window form set together
  *   ffl_motion_fit, ffl_motion_subtract  replace nothing: the reference cancels global motion only by the quadrant weights
  *                           of radial_motion_weighted ("Cancel out global motion by balancing the averages", FF:779-783), which
  *                           cancel a pan only about the image centre.  These fit a per-pair camera model (translation, rigid,
@@ -805,6 +813,108 @@ int ffl_radial_window_axes_centres(ffl_ctx *ctx, int n_seq, const int *seq_slots
  * of rule G5 for FFL_MAX_CELLS rows of FFL_MAX_BATCH items (256 KiB whatever the size and the grid; the cell sums
  * themselves stay in LDS; ffl_estimate_bytes does not count it).  Needs no device. */
 int ffl_cells_extra_bytes(int width, int height, int cells, size_t *bytes);
+
+/* ---- Region tracking through the flow and ROI maps (appendices Q and E) ----
+ * The argmax of pass 1 and the variance centre are found afresh for every pair and have no memory.  ffl_track_advance is the
+ * estimator with one: it advects caller-chosen points through the flow fields of n consecutive pairs, in time order, and its
+ * records are rule G6's centres.  The rules are the project's own (the reference has no such function).  For a context of
+ * w x h; all arithmetic is float64, one rounding per written operation, left to right, no contraction; u, v widen exactly.
+ *   Q1  sanitise: on load, each of x, home_x becomes c >= 0 ? (c <= w-1 ? c : w-1) : 0, and y, home_y likewise with h-1.
+ *       Both steps are selects, so a NaN becomes 0: any bit pattern in caller memory gives an in-range anchor, and the kernel
+ *       reads nothing outside a field whatever the state holds.
+ *   Q2  window: ix = (int)floor(x + 0.5), iy alike.  Members are the pixels of columns max(ix-r, 0) .. min(ix+r, w-1) and
+ *       rows max(iy-r, 0) .. min(iy+r, h-1): clipped, not clamped -- a pixel outside the image is no member.
+ *   Q3  member weight: wt = 1.0 without a map, (double)W[y][x] with one (rule W1).  A member is dropped by a select when
+ *       W == 0 or !(fabsf(u) <= FLT_MAX && fabsf(v) <= FLT_MAX) (rule C3's test): nothing of it reaches a sum.
+ *   Q4  sums, each starting at +0.0.  Per window column, rows top to bottom: cS += wt; cU += wt*(double)u; cV += wt*(double)v.
+ *       The column sums are then added left to right into S, U, V.  count is the number of kept members.
+ *   Q5  cut: mean_mag is ffl_pass1_results' expression on the record the slot holds when the call runs;
+ *       cut = mean_mag > cut_threshold.  A NaN is no cut, and a threshold of +inf never cuts.
+ *   Q6  step.  Cut: du = dv = +0.0, sw = +0.0, count = 0, status gets CUT, and none of the item's flow or map is read.
+ *       Otherwise, if S == 0: du = dv = +0.0, status gets LOST, lost_run += 1, and no division is executed.  Otherwise
+ *       du = U / S, dv = V / S, lost_run = 0.  (lost_run and steps wrap as two's complement.)
+ *   Q7  record (i, t) holds the sanitised position BEFORE the step -- the track's place in frame 0 of pair i, on whose pixels
+ *       the field is defined, hence the centre for that pair's radial terms -- and du, dv, sw = S, count and status.
+ *   Q8  move.  Cut with on_cut == FFL_TRACK_HOME: the position becomes (home_x, home_y).  Otherwise x' = x + du, y' = y + dv,
+ *       each passed through Q1's select; a select whose result does not equal its operand sets CLAMPED in this item's status.
+ *       In every case steps += 1.
+ *   Q9  chaining and independence: one call of n items is, bit for bit, any split into consecutive calls that hand the state
+ *       on; track t's records do not depend on n_tracks or on the other tracks.
+ * Accepted: radius 1..FFL_MAX_TRACK_RADIUS, on_cut FFL_TRACK_HOLD or FFL_TRACK_HOME, a cut_threshold that is not NaN.  The
+ * defaults are 12, HOLD and 7.0f (the reference's cut threshold, FF:876); the radius is the project's own choice and is NOT
+ * tuned on footage.  Integrating a flow drifts: re-detection is the caller's, which is why the state lives in caller memory. */
+enum { FFL_MAX_TRACKS = 8, FFL_MAX_TRACK_RADIUS = 32 };
+enum { FFL_TRACK_HOLD = 0, FFL_TRACK_HOME = 1 };                                            /* on_cut */
+enum { FFL_TRACK_OK = 0, FFL_TRACK_CUT = 1, FFL_TRACK_LOST = 2, FFL_TRACK_CLAMPED = 4 };    /* status bits */
+typedef struct ffl_track_params {
+    int radius, on_cut;
+    float cut_threshold;
+} ffl_track_params;
+typedef struct ffl_track_state {    /* 48 bytes; one per track, in device memory, read and written by every call */
+    double x, y, home_x, home_y;
+    int64_t steps;
+    int32_t lost_run, pad;
+} ffl_track_state;
+typedef struct ffl_track_record {   /* 48 bytes; rule Q7.  Its head (x, y) is a centre of rule G6 / E1 */
+    double x, y, du, dv, sw;
+    int32_t count, status;
+} ffl_track_record;
+int ffl_track_default_params(ffl_track_params *out);
+/* Pure host check: no device or context needed.  FFL_ERR_INVALID with the rule in ffl_last_error(NULL). */
+int ffl_track_params_check(const ffl_track_params *p);
+
+/* n_tracks points through the fields in flow slots seq_slots[0..n), in that order.  p NULL: the defaults.  weights: the maps
+ * of the n items (rule Q3), or NULL.  state_dev: n_tracks states.  out_dev: n * n_tracks records, record (i, t) at index
+ * i * n_tracks + t, so that a stride of 48 * n_tracks bytes reads one track.  Refused before any device work, each with its
+ * rule in the message: n outside 1..max_batch or n_tracks outside 1..FFL_MAX_TRACKS; a NULL list; a slot out of range or
+ * repeated; a slot that holds no flow (FFL_ERR_STATE); any rule of ffl_track_params_check; any rule of ffl_dev_weights_check
+ * for the maps; state_dev or out_dev that is NULL, not 8-byte aligned or, like the maps, not device memory of the context's
+ * device inside one allocation (page-locked host memory is refused); state_dev overlapping out_dev; a capturing `stream`
+ * (FFL_ERR_STATE).  ffl_cell_stats' protocol: ONE k_track launch of n_tracks workgroups, queued on the library's stream
+ * behind the work queued on `stream` and the slots' last writers; `stream` then waits for it; it counts as a use of the
+ * slots; never captured; the host does not wait.  No scratch memory: there is no *_extra_bytes call. */
+int ffl_track_advance(ffl_ctx *ctx, int n, const int *seq_slots, int n_tracks, const ffl_track_params *p,
+                      const ffl_dev_weights *weights, ffl_track_state *state_dev, ffl_track_record *out_dev, uint64_t stream);
+
+/* An elliptical weight map per item about a centre read from device memory, in the form rules W1 to W6 consume: it says
+ * which pixels are the SUBJECT, where the maps of sections 16, 18, 21 and 22 say which are reliable.  Float64, one rounding
+ * per written operation, no contraction.  For item i and pixel (x, y):
+ *   E1  the centre (cx, cy) is two doubles at centres_dev + i * centre_stride_bytes; the stride is a multiple of 8 and at
+ *       least 16: 48 * n_tracks reads one track's ffl_track_records, 32 ffl_grid_centre, 16 a plain (n, 2) array.
+ *   E2  dx = ((double)x - cx) / (double)ax, dy = ((double)y - cy) / (double)ay, e = dx*dx + dy*dy.
+ *   E3  soft = 1: q = 1.0 - e; q = q > 0.0 ? q : 0.0; W = (int)(q*255.0 + 0.5).  The second step is a select, so a NaN centre
+ *       gives an all-zero map.
+ *   E4  soft = 0: W = e <= 1.0 ? 255 : 0.
+ *   E5  with a gate map S: W = min(W, S).
+ * Accepted: 0.5 <= ax, ay <= 32768 and finite, soft in {0, 1}; the defaults are 48, 48, 1, the project's own choice and NOT
+ * tuned on footage. */
+typedef struct ffl_roi_params {
+    float ax, ay;
+    int soft;
+} ffl_roi_params;
+int ffl_roi_default_params(ffl_roi_params *out);
+/* Pure host check: no device or context needed.  FFL_ERR_INVALID with the rule in ffl_last_error(NULL). */
+int ffl_roi_params_check(const ffl_roi_params *p);
+
+/* The maps of n items.  `out`, `gate` and the in-place exception (gate EXACTLY out) are ffl_texture_weights'; bytes between
+ * rows and between items are left alone.  Refused before any device work, each with its rule in the message: n outside
+ * 1..max_batch; any rule of ffl_roi_params_check; any rule of ffl_dev_weights_check for out and for gate; out with
+ * item_stride == 0 when n > 1; out overlapping gate unless gate is exactly out; a NULL or misaligned centres_dev; a stride
+ * below 16 or no multiple of 8; centres overlapping out; out, gate or the centres, over (n - 1) * stride + 16 bytes, that
+ * are not device memory of the context's device inside one allocation; a capturing `stream` (FFL_ERR_STATE).
+ * ffl_texture_weights' protocol without frame slots: ONE k_roi_weights launch, queued on the library's stream behind the
+ * work queued on `stream`; `stream` then waits for it; never captured; the host does not wait.  It names no slot. */
+int ffl_roi_weights(ffl_ctx *ctx, int n, const void *centres_dev, ptrdiff_t centre_stride_bytes, const ffl_roi_params *p,
+                    const ffl_dev_weights *gate, const ffl_dev_weights *out, uint64_t stream);
+
+/* The fifth window form: rule W4's terms about rule G6's centres -- ffl_radial_window_axes_weighted with the centres of
+ * ffl_radial_window_axes_centres.  out_dev is checked first, then the maps, then the centres.  Its launches are
+ * k_window_plan over the centres and the weighted four-component pair; no new kernel body.  An all-ones map gives the bits
+ * of ffl_radial_window_axes_centres. */
+int ffl_radial_window_axes_weighted_centres(ffl_ctx *ctx, int n_seq, const int *seq_slots, int first, int n, int radius,
+                                            float cut_threshold, int pov_mode, const ffl_dev_weights *w,
+                                            const void *centres_dev, ptrdiff_t centre_stride_bytes, ffl_axes_record *out_dev,
+                                            uint64_t stream);
 
 /* ---- Global-motion fit and compensation ----
  * A per-pair parametric camera model, fitted robustly to a resident flow field and subtracted from it, so that what pass 1
