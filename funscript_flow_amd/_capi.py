@@ -30,6 +30,12 @@ TRACK_OK, TRACK_CUT, TRACK_LOST, TRACK_CLAMPED = 0, 1, 2, 4   # status bits of a
 TRACK_STATE_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("home_x", "<f8"), ("home_y", "<f8"), ("steps", "<i8"),
                               ("lost_run", "<i4"), ("pad", "<i4")])
 TRACK_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("du", "<f8"), ("dv", "<f8"), ("sw", "<f8"), ("count", "<i4"), ("status", "<i4")])
+# template matching about tracked centres: the header's enums and ffl_match_record
+FFL_MAX_MATCH_P, FFL_MAX_MATCH_S = 16, 16
+MATCH_MODES = ("ssd", "zssd")                                 # FFL_MATCH_SSD, FFL_MATCH_ZSSD
+MATCH_FLAT, MATCH_POOR, MATCH_AMBIGUOUS = 1, 2, 4             # status bits of a record; 0: accepted
+MATCH_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("dx", "<i4"), ("dy", "<i4"), ("cost", "<i8"), ("second", "<i8"),
+                        ("status", "<i4"), ("pad", "<i4")])
 
 # 4:2:0 layouts of ffl_upload_frames_yuv (FFL_YUV_I420, FFL_YUV_NV12): cv2's single-array (3h/2, w) uint8 frames
 YUV_LAYOUTS = {"i420": 0, "nv12": 1}
@@ -659,6 +665,54 @@ def roi_choice(params):
     return params
 
 
+def match_mode(mode):
+    """FFL_MATCH_SSD / FFL_MATCH_ZSSD of a name of MATCH_MODES (or the code itself)"""
+    if isinstance(mode, str):
+        if mode not in MATCH_MODES:
+            raise ValueError(f"mode must be one of {MATCH_MODES}, got {mode!r}")
+        return MATCH_MODES.index(mode)
+    return int(mode)
+
+
+MATCH_FIELDS = ("p", "s", "mode", "min_var", "max_mse", "ratio")
+
+
+class MatchParams(C.Structure):
+    """ffl_match_params: the template's half-side p (1..16, the template is (2p+1)^2), the search range
+    s (1..16, |dx|, |dy| <= s), mode ("ssd" | "zssd": the zero-mean form, invariant to a brightness offset), and the three
+    thresholds of rule N6: min_var (the template's own variance below which it is FLAT), max_mse (the mean squared
+    difference above which the best match is POOR) and ratio (the best cost above ratio * the runner-up's is AMBIGUOUS).
+    MatchParams() holds the library's defaults (the project's own choice, not tuned on footage); keywords override single
+    fields."""
+    _fields_ = [("p", C.c_int), ("s", C.c_int), ("mode", C.c_int), ("reserved", C.c_int), ("min_var", C.c_double),
+                ("max_mse", C.c_double), ("ratio", C.c_double)]
+
+    def __init__(self, **over):
+        super().__init__()
+        load().ffl_match_default_params(C.byref(self))
+        for k, v in over.items():
+            if k not in MATCH_FIELDS:
+                raise ValueError(f"unknown match parameter {k!r} {MATCH_FIELDS}")
+            setattr(self, k, match_mode(v) if k == "mode" else v)
+
+    def as_dict(self):
+        return {"p": self.p, "s": self.s, "mode": MATCH_MODES[self.mode] if self.mode in (0, 1) else self.mode,
+                "min_var": self.min_var, "max_mse": self.max_mse, "ratio": self.ratio}
+
+
+def match_params_check(params):
+    """ffl_match_params_check: ValueError with the library's rule when it refuses (pure host check)."""
+    _check(load().ffl_match_params_check(None if params is None else C.byref(params)), exc=ValueError)
+
+
+def match_choice(params):
+    """a MatchParams out of None (the defaults), a dict of its fields or a MatchParams; checked"""
+    if not isinstance(params, MatchParams):
+        params = MatchParams(**dict(params or {}))
+    match_params_check(params)
+    return params
+
+
 class MotionParams(C.Structure):
     """ffl_motion_params: the sub-model of rule C2 (a name of MOTION_MODELS or its code), the passes of
     rule C7 and the Cauchy scale tau of rule C3 in pixels.  MotionParams() holds the library's defaults (rule C9: translation,
@@ -898,6 +952,10 @@ SIGNATURES = {
     "ffl_roi_params_check": (_i, (_P(RoiParams),)),
     "ffl_roi_weights": (_i, (_ctx, _i, _vp, _pd, _P(RoiParams), _P(DevWeights), _P(DevWeights), _u64)),
     "ffl_radial_window_axes_weighted_centres": (_i, _WINDOW + (_P(DevWeights), _vp, _pd, _vp, _u64)),
+    "ffl_match_default_params": (_i, (_P(MatchParams),)),
+    "ffl_match_params_check": (_i, (_P(MatchParams),)),
+    "ffl_track_template": (_i, (_ctx, _i, _i, _vp, _i, _vp, _u64)),
+    "ffl_track_match": (_i, (_ctx, _i, _ip, _i, _P(MatchParams), _vp, _vp, _pd, _i, _vp, _u64)),
     "ffl_motion_default_params": (_i, (_P(MotionParams),)),
     "ffl_motion_params_check": (_i, (_P(MotionParams),)),
     "ffl_motion_solve": (_i, (_dp, _i, _vp)),
@@ -941,6 +999,7 @@ RECORDS = {"ffl_source_info": SourceInfo, "ffl_dev_frame": DevFrame, "ffl_dev_fl
            "ffl_cell_record": CELL_DTYPE, "ffl_grid_centre": GRID_CENTRE_DTYPE, "ffl_motion_params": MotionParams,
            "ffl_motion_record": MOTION_DTYPE, "ffl_dis_params": DisParams, "ffl_track_params": TrackParams,
            "ffl_track_state": TRACK_STATE_DTYPE, "ffl_track_record": TRACK_DTYPE, "ffl_roi_params": RoiParams,
+           "ffl_match_params": MatchParams, "ffl_match_record": MATCH_DTYPE,
            "ffl_farneback_params": FarnebackParams}
 
 _lib = None
@@ -1627,6 +1686,43 @@ class Context:
         gdesc = None if gate is None else odesc if gate is out else self._weights("roi_weights", gate, n)
         self._chk(self.L.ffl_roi_weights(self._h, n, ptr, stride, C.byref(prm), None if gdesc is None else C.byref(gdesc),
                                          C.byref(odesc), stream_handle(stream, self.device)))
+        return out
+
+    def track_template(self, fslot, centres, templates, p=None, tracks=None, stream=None):
+        """Capture the tracks' templates out of frame slot `fslot` (ffl_track_template, DESIGN.md section 24, rule N10):
+        `centres` is device memory that holds track t's centre as two doubles at byte 48 * t -- a track_state tensor, or one
+        item's track records; `templates` device memory for T * (2p+1)^2 bytes (pipeline.match_templates makes one).  `p`:
+        the half-side (None: the default of MatchParams); `tracks`: T (None: the 48-byte records `centres` holds).  Queued
+        behind the work on `stream` (None: torch's current stream) and the upload that filled the slot; `stream` waits for
+        it.  Returns `templates`."""
+        p = MatchParams().p if p is None else int(p)
+        cptr, cbytes = _device_span(centres)
+        T = (cbytes + 32) // 48 if tracks is None else int(tracks)
+        tptr, tbytes = _device_span(templates)
+        if 1 <= p <= FFL_MAX_MATCH_P and tbytes < T * (2 * p + 1) ** 2:
+            raise ValueError(f"track_template: templates holds {tbytes} bytes, {T} templates of {(2 * p + 1) ** 2} are needed")
+        self._chk(self.L.ffl_track_template(self._h, int(fslot), T, cptr, p, tptr, stream_handle(stream, self.device)))
+        return templates
+
+    def track_match(self, fslots, templates, centres, out, params=None, tracks=1, write_back=True, stream=None):
+        """Search frame slot fslots[i] for every track's template about item i's centres and correct them in place
+        (ffl_track_match): `templates` as track_template filled it; `centres` a (buffer, byte stride)
+        span -- (track records of the batch, 48 * tracks), (a track_state tensor, 48 * tracks) with one item -- or a float64
+        (n, 2) device array for one track; `out` device memory for len(fslots) * tracks MATCH_DTYPE records, record (i, t) at
+        index i * tracks + t.  `params`: a MatchParams, a dict of its fields or None (the defaults, which are not tuned on
+        footage); `write_back`: an accepted match overwrites its centre (rule N8).  Queued behind the work on `stream` and
+        the uploads that filled the slots; `stream` waits for it; the host does not wait.  Returns `out`."""
+        ps, slots = _iarr(fslots)
+        n, T = len(slots), int(tracks)
+        prm = params if isinstance(params, MatchParams) else MatchParams(**dict(params or {}))
+        cptr, stride = _centre_entries(centres, n)
+        tptr, _ = _device_span(templates)
+        optr, extent = _device_span(out)
+        if extent < n * T * MATCH_DTYPE.itemsize:
+            raise ValueError(f"track_match: out holds {extent} bytes, {n} x {T} records need {n * T * MATCH_DTYPE.itemsize}")
+        wb = int(write_back) if isinstance(write_back, (bool, int, np.integer)) else -1
+        self._chk(self.L.ffl_track_match(self._h, n, ps, T, C.byref(prm), tptr, cptr, stride, wb, optr,
+                                         stream_handle(stream, self.device)))
         return out
 
     def motion_fit(self, slots, model="translation", iterations=3, tau=1.0, weights=None, prior=None, out=None, sums_out=None,

@@ -3450,6 +3450,140 @@ int ffl_roi_weights(ffl_ctx *c, int n, const void *centres_dev, ptrdiff_t cstrid
     return post_end(c, cst, 0, nullptr);  // the caller may read the maps, or overwrite the gate or the centres, on `stream` straight after
 }
 
+// ---- template matching about tracked centres -----------------------------------------
+static_assert(sizeof(ffl_match_record) == 48 && sizeof(MatchRecord) == 48 && offsetof(ffl_match_record, x) == 0 && offsetof(MatchRecord, x) == 0 &&
+              offsetof(ffl_match_record, y) == 8 && offsetof(MatchRecord, y) == 8 && offsetof(ffl_match_record, dx) == 16 &&
+              offsetof(MatchRecord, dx) == 16 && offsetof(ffl_match_record, dy) == 20 && offsetof(MatchRecord, dy) == 20 &&
+              offsetof(ffl_match_record, cost) == 24 && offsetof(MatchRecord, cost) == 24 && offsetof(ffl_match_record, second) == 32 &&
+              offsetof(MatchRecord, second) == 32 && offsetof(ffl_match_record, status) == 40 && offsetof(MatchRecord, status) == 40 &&
+              alignof(ffl_match_record) == 8, "MatchRecord mirrors ffl_match_record");
+static_assert((int)FFL_MAX_MATCH_P == FFL_MATCH_MAX_P && (int)FFL_MAX_MATCH_S == FFL_MATCH_MAX_S && (int)FFL_MATCH_SSD == MCH_SSD &&
+              (int)FFL_MATCH_ZSSD == MCH_ZSSD && (int)FFL_MATCH_FLAT == MCH_FLAT && (int)FFL_MATCH_POOR == MCH_POOR &&
+              (int)FFL_MATCH_AMBIGUOUS == MCH_AMBIGUOUS && sizeof(ffl_track_state) == sizeof(ffl_match_record),
+              "ffl.h and ffl_kernels.h agree; a state and a record are 48 bytes, the track pitch of rule N1");
+
+int ffl_match_default_params(ffl_match_params *out) {
+    if (!out) return FFL_ERR_INVALID;
+    *out = ffl_match_params{8, 8, FFL_MATCH_ZSSD, 0, 25.0, 400.0, 0.8};   // the project's own choice, not tuned on footage
+    return FFL_OK;
+}
+
+// The accepted parameters of appendix N.  The comparisons are written so that a NaN fails them.
+static int match_params_check(ffl_ctx *c, const char *fn, const ffl_match_params *p) {
+    if (!p) return set_err(c, FFL_ERR_INVALID, "%s: NULL parameters", fn);
+    if (p->p < 1 || p->p > FFL_MAX_MATCH_P)
+        return set_err(c, FFL_ERR_INVALID, "%s: p = %d outside 1..%d (FFL_MAX_MATCH_P; the template is (2p+1)^2)", fn, p->p, (int)FFL_MAX_MATCH_P);
+    if (p->s < 1 || p->s > FFL_MAX_MATCH_S)
+        return set_err(c, FFL_ERR_INVALID, "%s: s = %d outside 1..%d (FFL_MAX_MATCH_S; the search is |dx|, |dy| <= s)", fn, p->s, (int)FFL_MAX_MATCH_S);
+    if (p->mode != FFL_MATCH_SSD && p->mode != FFL_MATCH_ZSSD)
+        return set_err(c, FFL_ERR_INVALID, "%s: mode = %d is neither 0 (FFL_MATCH_SSD) nor 1 (FFL_MATCH_ZSSD)", fn, p->mode);
+    if (!(p->min_var >= 0.0 && p->min_var < HUGE_VAL)) return set_err(c, FFL_ERR_INVALID, "%s: min_var = %g outside 0 <= min_var (finite)", fn, p->min_var);
+    if (!(p->max_mse >= 0.0 && p->max_mse <= 65025.0))
+        return set_err(c, FFL_ERR_INVALID, "%s: max_mse = %g outside 0..65025 (finite)", fn, p->max_mse);
+    if (!(p->ratio > 0.0 && p->ratio <= 1.0)) return set_err(c, FFL_ERR_INVALID, "%s: ratio = %g outside 0 < ratio <= 1 (finite)", fn, p->ratio);
+    return FFL_OK;
+}
+
+int ffl_match_params_check(const ffl_match_params *p) { return match_params_check(nullptr, "ffl_match_params_check", p); }
+
+static const char *kHostMatch = "templates, centres and match records live in device memory (torch / hipMalloc)";
+
+// what both calls refuse of their track count, their pointers and the three regions (templates, centres, records; obytes 0: no
+// records): NULL, alignment, the centre stride of rule N1 and any overlap
+static int match_regions_check(ffl_ctx *c, const char *fn, int n, int n_tracks, int p, const void *tmpl, const void *cen, ptrdiff_t cstride,
+                               const void *out, bool has_out, size_t *tbytes, size_t *cbytes, size_t *obytes) {
+    if (n_tracks < 1 || n_tracks > FFL_MAX_TRACKS)
+        return set_err(c, FFL_ERR_INVALID, "%s: n_tracks = %d outside 1..%d (FFL_MAX_TRACKS)", fn, n_tracks, (int)FFL_MAX_TRACKS);
+    if (!tmpl || !cen || (has_out && !out))
+        return set_err(c, FFL_ERR_INVALID, "%s: NULL %s", fn, !tmpl ? "templates_dev" : !cen ? "centres_dev" : "out_dev");
+    if ((uintptr_t)cen % 8 || (has_out && (uintptr_t)out % 8))
+        return set_err(c, FFL_ERR_INVALID, "%s: centres_dev and out_dev must be 8-byte aligned", fn);
+    const ptrdiff_t span = 48 * (ptrdiff_t)(n_tracks - 1) + 16;   // rule N1: track t's centre at + 48 t
+    if (cstride % 8 || cstride < span || cstride > ((ptrdiff_t)1 << 40))
+        return set_err(c, FFL_ERR_INVALID, "%s: centre stride %td: a multiple of 8 bytes, at least 48 * (n_tracks - 1) + 16 = %td (rule N1)",
+                       fn, cstride, span);
+    const size_t side = 2 * (size_t)p + 1;
+    *tbytes = side * side * (size_t)n_tracks;
+    *cbytes = (size_t)(n - 1) * (size_t)cstride + (size_t)span;
+    *obytes = has_out ? sizeof(ffl_match_record) * (size_t)n * (size_t)n_tracks : 0;
+    const struct { const char *what; uintptr_t a; size_t b; } r[3] = {
+        {"templates_dev", (uintptr_t)tmpl, *tbytes}, {"centres_dev", (uintptr_t)cen, *cbytes}, {"out_dev", (uintptr_t)out, *obytes}};
+    for (int i = 0; i < 3; i++)
+        for (int j = i + 1; j < 3; j++)
+            if (r[i].b && r[j].b && r[i].a < r[j].a + r[j].b && r[j].a < r[i].a + r[i].b)
+                return set_err(c, FFL_ERR_INVALID, "%s: overlap: %s (%zu bytes) and %s (%zu bytes) share memory", fn, r[i].what, r[i].b,
+                               r[j].what, r[j].b);
+    return FFL_OK;
+}
+
+// n_tracks templates out of one frame slot by ONE k_track_template launch on stream `post`: ffl_texture_weights' protocol.
+int ffl_track_template(ffl_ctx *c, int fslot, int n_tracks, const void *centres_dev, int p, void *templates_dev, uint64_t stream) {
+    static const char *fn = "ffl_track_template";
+    if (!c) return FFL_ERR_INVALID;
+    std::unique_lock<std::mutex> pl(c->post_mu);  // stream `post`, as ffl_texture_weights
+    CtxLock lk(c->mu);
+    if (fslot < 0 || fslot >= c->n_fslots) return set_err(c, FFL_ERR_INVALID, "%s: frame slot %d out of range", fn, fslot);
+    if (!c->frame_valid[fslot]) return set_err(c, FFL_ERR_STATE, "%s: frame slot %d was never uploaded", fn, fslot);
+    if (p < 1 || p > FFL_MAX_MATCH_P)
+        return set_err(c, FFL_ERR_INVALID, "%s: p = %d outside 1..%d (FFL_MAX_MATCH_P; the template is (2p+1)^2)", fn, p, (int)FFL_MAX_MATCH_P);
+    size_t tbytes, cbytes, obytes;
+    if (int rc = match_regions_check(c, fn, 1, n_tracks, p, templates_dev, centres_dev, 48 * (ptrdiff_t)n_tracks, nullptr, false, &tbytes,
+                                     &cbytes, &obytes))
+        return rc;
+    hipStream_t cst;
+    PostRegion reg[2] = {{"templates_dev", templates_dev, tbytes, kHostMatch}, {"centres_dev", centres_dev, cbytes, kHostMatch}};
+    if (int rc = post_begin(c, fn, stream, &cst, reg, 2, 0, nullptr)) return rc;
+    {
+        WaitOnce wait_post(c->s_post);   // the upload that filled the frame slot
+        HIPCHK(c, wait_post(c->ev_uploaded[fslot].get()));
+    }
+    ffl_launch_track_template(c->d_gray + (size_t)fslot * c->N, n_tracks, c->w, c->h, p, (const char *)centres_dev,
+                              (unsigned char *)templates_dev, c->s_post);
+    return post_end_frames(c, cst, 0, nullptr, 1, &fslot, nullptr);  // the caller may read the templates on `stream` straight after
+}
+
+// n x n_tracks searches by ONE k_track_match launch of (n_tracks, n) workgroups on stream `post`: ffl_texture_weights' protocol,
+// with the frames and the templates only read and the centres read and, with write_back, written.
+int ffl_track_match(ffl_ctx *c, int n, const int *fslots, int n_tracks, const ffl_match_params *p, const void *templates_dev,
+                    void *centres_dev, ptrdiff_t cstride, int write_back, ffl_match_record *out_dev, uint64_t stream) {
+    static const char *fn = "ffl_track_match";
+    if (!c) return FFL_ERR_INVALID;
+    std::unique_lock<std::mutex> pl(c->post_mu);  // stream `post`, as ffl_texture_weights
+    CtxLock lk(c->mu);
+    if (n < 1 || n > c->max_batch)
+        return set_err(c, FFL_ERR_INVALID, "%s: n = %d items outside 1..%d (the context's max_batch)", fn, n, c->max_batch);
+    if (!fslots) return set_err(c, FFL_ERR_INVALID, "%s: NULL fslots", fn);
+    ExportTab tf;
+    for (int i = 0; i < n; i++) {   // frame slots may repeat between items
+        const int fs = fslots[i];
+        if (fs < 0 || fs >= c->n_fslots) return set_err(c, FFL_ERR_INVALID, "%s: item %d: frame slot %d out of range", fn, i, fs);
+        if (!c->frame_valid[fs]) return set_err(c, FFL_ERR_STATE, "%s: item %d: frame slot %d was never uploaded", fn, i, fs);
+        tf.slot[i] = fs;
+    }
+    ffl_match_params prm;
+    ffl_match_default_params(&prm);
+    if (p) prm = *p;
+    if (int rc = match_params_check(c, fn, &prm)) return rc;
+    if (write_back != 0 && write_back != 1)
+        return set_err(c, FFL_ERR_INVALID, "%s: write_back = %d is neither 0 nor 1 (rule N8)", fn, write_back);
+    size_t tbytes, cbytes, obytes;
+    if (int rc = match_regions_check(c, fn, n, n_tracks, prm.p, templates_dev, centres_dev, cstride, out_dev, true, &tbytes, &cbytes, &obytes))
+        return rc;
+    hipStream_t cst;
+    PostRegion reg[3] = {{"out_dev", out_dev, obytes, kHostMatch}, {"templates_dev", templates_dev, tbytes, kHostMatch},
+                         {"centres_dev", centres_dev, cbytes, kHostMatch}};
+    if (int rc = post_begin(c, fn, stream, &cst, reg, 3, 0, nullptr)) return rc;
+    {
+        WaitOnce wait_post(c->s_post);   // the frames: a run of slots shares one upload event
+        for (int i = 0; i < n; i++) HIPCHK(c, wait_post(c->ev_uploaded[fslots[i]].get()));
+    }
+    ffl_launch_track_match(c->d_gray, c->N, tf, n, n_tracks, c->w, c->h, prm.p, prm.s, prm.mode, prm.min_var, prm.max_mse, prm.ratio,
+                           (const unsigned char *)templates_dev, (char *)centres_dev, (long long)cstride, write_back,
+                           (MatchRecord *)out_dev, c->s_post);
+    // the caller may read the records and the corrected centres on `stream` straight after the call
+    return post_end_frames(c, cst, 0, nullptr, n, fslots, nullptr);
+}
+
 // ---- global-motion fit and compensation ---------------------------------------------
 static_assert(sizeof(ffl_motion_record) == 64 && sizeof(MotionRecord) == 64 && offsetof(ffl_motion_record, a0) == 0 &&
               offsetof(MotionRecord, a0) == 0 && offsetof(ffl_motion_record, b0) == 24 && offsetof(MotionRecord, b0) == 24 &&

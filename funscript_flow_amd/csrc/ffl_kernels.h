@@ -380,6 +380,27 @@ void ffl_launch_track(const float *flow, const Pass1Result *res, const ExportTab
 void ffl_launch_roi_weights(const char *cen, long long cstride, int n, int w, int h, float ax, float ay, int soft,
                             const WeightArgs *gate, char *out, long long out_item, long long out_pitch, hipStream_t st);
 
+// ---- template matching about tracked centres (kernels_match.hip) ------------------
+#define FFL_MATCH_MAX_P 16           // = FFL_MAX_MATCH_P of include/ffl.h
+#define FFL_MATCH_MAX_S 16           // = FFL_MAX_MATCH_S
+enum { MCH_SSD = 0, MCH_ZSSD = 1 };                     // = FFL_MATCH_SSD, FFL_MATCH_ZSSD
+enum { MCH_FLAT = 1, MCH_POOR = 2, MCH_AMBIGUOUS = 4 }; // = FFL_MATCH_* status bits
+struct MatchRecord { // = ffl_match_record of include/ffl.h (ffl_api.hip asserts the layout)
+    double x, y;
+    int dx, dy;
+    long long cost, second;
+    int status, pad;
+};
+// item i searches frame slot fr.slot[i] of `gray` (N bytes each) for n_tracks templates of (2p+1)^2 bytes at tmpl, about the
+// two doubles at cen + i * cstride + t * 48 (k_track_match, one workgroup per (track, item)): record (i, t) to
+// out[i * n_tracks + t]; write_back 1: an accepted match also overwrites those two doubles
+void ffl_launch_track_match(const unsigned char *gray, size_t N, const ExportTab &fr, int n, int n_tracks, int w, int h, int p,
+                            int s, int mode, double min_var, double max_mse, double ratio, const unsigned char *tmpl, char *cen,
+                            long long cstride, int write_back, MatchRecord *out, hipStream_t st);
+// n_tracks templates of (2p+1)^2 bytes out of one frame about the two doubles at cen + t * 48 (k_track_template, rule N10)
+void ffl_launch_track_template(const unsigned char *frame, int n_tracks, int w, int h, int p, const char *cen, unsigned char *tmpl,
+                               hipStream_t st);
+
 // ---- global-motion fit and compensation (kernels_post.hip) -----------------------
 #define FFL_MOTION_NSUMS 12          // = FFL_MOTION_N_SUMS of include/ffl.h; the order of rule C4
 enum { MOT_S = 0, MOT_SX, MOT_SY, MOT_SXX, MOT_SXY, MOT_SYY, MOT_SU, MOT_SUX, MOT_SUY, MOT_SV, MOT_SVX, MOT_SVY };

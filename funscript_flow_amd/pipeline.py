@@ -162,6 +162,28 @@ def track_records(buf, tracks=1, n=None, device=None):
     return np.frombuffer(raw.tobytes(), _capi.TRACK_DTYPE, n * int(tracks)).reshape(n, int(tracks))
 
 
+def match_buffer(ctx, n, tracks=1):
+    """a device buffer for the n * tracks 48-byte match records of a chunk (torch uint8 on the context's device), as match_out=
+    and Context.track_match(out=) take it: record (pair j, track t) at byte 48 * (j * tracks + t)"""
+    import torch
+    return torch.empty(n * int(tracks) * _capi.MATCH_DTYPE.itemsize, dtype=torch.uint8, device=torch.device("cuda", ctx.device))
+
+
+def match_records(buf, tracks=1, n=None, device=None):
+    """The match records of a chunk run with track["match"] (or of Context.track_match) as a numpy array (n, tracks) of
+    _capi.MATCH_DTYPE (fields x, y, dx, dy, cost, second, status, pad); the copy runs as track_records' does."""
+    raw = track_records(buf, tracks, n, device)
+    return np.frombuffer(raw.tobytes(), _capi.MATCH_DTYPE).reshape(raw.shape)
+
+
+def match_templates(ctx, tracks=1, p=None):
+    """a device tensor (torch uint8, (tracks, 2p+1, 2p+1)) for the templates of Context.track_template / track_match and
+    track["match"]["templates"]; p None: the default of _capi.MatchParams"""
+    import torch
+    side = 2 * (_capi.MatchParams().p if p is None else int(p)) + 1
+    return torch.zeros((int(tracks), side, side), dtype=torch.uint8, device=torch.device("cuda", ctx.device))
+
+
 def track_state_array(points, home=None):
     """(T,) _capi.TRACK_STATE_DTYPE records on the host out of `points`, (x, y) or (T, 2): the tracks' positions; `home`
     (the same form, default: the points) is where on_cut="home" sends a track.  steps and lost_run start at 0."""
@@ -416,7 +438,7 @@ class PairEngine:
     def process_chunk(self, frames, pov_mode=False, cut_threshold=7.0, algo=None, farneback=OWN, flows_out=None, window=OWN,
                       post_out=None, axes=False, weights=None, center=None, cells=32, grid_out=None, consistency=None,
                       weights_out=None, weights_gate=None, compensate=None, motion_out=None, residual=None, texture=None,
-                      track=None, track_out=None):
+                      track=None, track_out=None, match_out=None):
         """One whole chunk on one GPU: returns (dots float64[n], records) with n = len(frames)-1.  `algo`, `farneback`,
         `window`: see pass1_pairs (default: the engine's own flow algorithm, parameters and window).  `flows_out`: a float32 device array of
         (n, H, W, 2) or (n, 2, H, W) that receives every pair's flow field (Context.export_flows, on torch's current stream)
@@ -478,10 +500,20 @@ class PairEngine:
         "roi" the window calls are Context.radial_window_axes_centres about track 0's records; with it Context.roi_weights
         writes the batch's maps into an (n, H, W) tensor (`weights_out`, or a new one; `weights_gate`: the static gate of rule
         E5), Context.pass1_weighted follows and the window calls are Context.radial_window_axes_weighted_centres.  weights= of
-        any form is refused next to it."""
+        any form is refused next to it.
+        track["match"]: a dict of _capi.MatchParams' fields ("p", "s", "mode", "min_var", "max_mse",
+        "ratio"; the defaults are not tuned on footage), optionally "templates" (a match_templates tensor the caller carries
+        from chunk to chunk) and "capture" (fill the templates from the chunk's first frame about the state; default: only
+        when no "templates" are given).  Behind each batch, between track_advance and roi_weights, Context.track_match
+        corrects the batch's records on their f0 frames and then the state on the batch's last f1 frame, both in place, so
+        every centre read afterwards is a corrected one; `match_out` (a match_buffer, or a new one; match_records reads it)
+        receives the n x T 48-byte match records of the first.  A rejected match (FLAT, POOR, AMBIGUOUS) leaves its centre
+        alone: after a scene cut the template is stale, matches read POOR and the track is pure advection until the caller
+        re-captures (Context.track_template).  Without the key the chunk queues exactly the calls it queued before."""
         ctx, B = self.ctx, self.B
         n = len(frames) - 1
-        trk = _chunk_track(ctx, n, center, track, track_out, weights, weights_out, weights_gate, ctx.flow_slots, cut_threshold)
+        trk = _chunk_track(ctx, n, center, track, track_out, weights, weights_out, weights_gate, ctx.flow_slots, cut_threshold,
+                           match_out)
         if trk is not None and trk.roi is not None:   # the keywords are the track's
             weights_out = weights_gate = None
         if compensate is not None and isinstance(weights, str) and weights == "consistency":
@@ -542,7 +574,8 @@ class PairEngine:
 
             self.pass1_pairs(frames, range(n), lambda l: l % ring, pov_mode, cut_threshold, algo=algo,
                              farneback=farneback, window=window, queued=queued,
-                             **_chain(trk and trk.behind, comp and comp.behind), **_frames_kw(resid),
+                             **_chain(trk and trk.behind, comp and comp.behind),
+                             **_frames_kw(trk if trk is not None and trk.match is not None else resid),
                              **({} if cons is None else {"batch": B, "reverse_slot_of": cons.bwd_slot}))
             if marks:
                 marks[-1][0].synchronize()   # the ring's slots may be reused by the next chunk: every transfer is over
@@ -590,7 +623,7 @@ class PairEngine:
             desc, dt, k = _capi.device_flows(a, ctx.width, ctx.height)
             segs.append((desc, dt, n, k))
             n += k
-        trk = _chunk_track(ctx, n, center, track, track_out, weights, weights_out, weights_gate, fs, cut_threshold)
+        trk = _chunk_track(ctx, n, center, track, track_out, weights, weights_out, weights_gate, fs, cut_threshold, frames=False)
         if trk is None and (weights_out is not None or weights_gate is not None):
             raise ValueError("process_flows: weights_out= and weights_gate= need center='track' with track['roi']")
         if trk is not None:
@@ -788,7 +821,8 @@ def chunk_center(center):
     return center
 
 
-TRACK_KEYS = ("state", "start", "home", "radius", "on_cut", "roi", "roi_soft")
+TRACK_KEYS = ("state", "start", "home", "radius", "on_cut", "roi", "roi_soft", "match")
+MATCH_KEYS = _capi.MATCH_FIELDS + ("templates", "capture", "match_out")
 
 
 class _ChunkTrack:
@@ -798,9 +832,15 @@ class _ChunkTrack:
     pass1_weighted, so rule Q5's cut is the unweighted whole-frame mean magnitude.  With roi, Context.roi_weights then writes
     the pairs' maps about track 0's records into the chunk's (n, H, W) uint8 tensor `maps` (weights_out, or a new one; gate:
     the static gate of rule E5).  state: the device tensor of T ffl_track_state records, read and written, which the caller
-    carries to the next chunk.  stream: where the calls are queued (the device schedule sets its side stream)."""
+    carries to the next chunk.  stream: where the calls are queued (the device schedule sets its side stream).
+    With track["match"] with_frames(ls, js, f0, f1), pass1_pairs' hook, keeps the batch's frame slots, and
+    where the templates are to be captured queues Context.track_template on f0[0] about the state, once, before the first
+    advance; behind() then queues, between track_advance and roi_weights, Context.track_match on the f0 slots about the batch's
+    records and Context.track_match with one item on f1[last] about the state, both with write-back: the window calls and the
+    ROI maps read corrected centres, and the next batch starts from a corrected state.  Without the key nothing of this is
+    queued."""
 
-    def __init__(self, ctx, n, track, track_out, maps_out, gate, ring, cut_threshold):
+    def __init__(self, ctx, n, track, track_out, maps_out, gate, ring, cut_threshold, match_out=None):
         if not isinstance(track, dict) or not (("state" in track) ^ ("start" in track)):
             raise ValueError("center='track' needs track= {'state': a track_state tensor} or {'start': (x, y) or (T, 2)}, one of "
                              "the two")
@@ -810,6 +850,14 @@ class _ChunkTrack:
         self.ctx, self.n, self.ring = ctx, n, int(ring)
         over = {k: track[k] for k in ("radius", "on_cut") if track.get(k) is not None}
         self.params = _capi.track_choice(_capi.TrackParams(cut_threshold=float(cut_threshold), **over))
+        self.match, m = None, track.get("match")
+        if m is not None:
+            unknown = [k for k in m if k not in MATCH_KEYS] if isinstance(m, dict) else ["match"]
+            if unknown:
+                raise ValueError(f"track['match']: a dict of {MATCH_KEYS}; unknown key {unknown[0]!r}")
+            self.match = _capi.match_choice({k: m[k] for k in _capi.MATCH_FIELDS if m.get(k) is not None})
+        elif match_out is not None:
+            raise ValueError("match_out= needs track['match'] with center='track'")
         if "state" in track:
             if "home" in track:
                 raise ValueError("track=: 'home' goes with 'start' (a state carries its own home position)")
@@ -835,6 +883,29 @@ class _ChunkTrack:
         elif maps_out is not None or gate is not None or track.get("roi_soft") is not None:
             raise ValueError("weights_out=, weights_gate= and track['roi_soft'] need track['roi'] = (ax, ay) with center='track'")
         self.stream = None
+        self.templates = self.match_out = self.frames = None
+        self.capture = False
+        if self.match is not None:
+            self.templates = m.get("templates")
+            self.capture = bool(m.get("capture", self.templates is None))
+            if self.templates is None:
+                self.templates = match_templates(ctx, self.T, self.match.p)
+            need = self.T * (2 * self.match.p + 1) ** 2
+            if _capi._device_span(self.templates)[1] < need:
+                raise ValueError(f"track['match']['templates'] holds {_capi._device_span(self.templates)[1]} bytes, {self.T} "
+                                 f"templates of p = {self.match.p} need {need}")
+            match_out = m.get("match_out") if match_out is None else match_out
+            self.match_out = match_buffer(ctx, max(n, 1), self.T) if match_out is None else match_out   # stays referenced
+            self.mbase, nbytes = _capi._device_span(self.match_out)
+            if nbytes < n * self.item:
+                raise ValueError(f"match_out holds {nbytes} bytes, the chunk's {n} x {self.T} records need {n * self.item}")
+            self.state_match = match_buffer(ctx, 1, self.T)   # the records of the latest search about the state
+
+    def with_frames(self, ls, js, f0, f1):
+        self.frames = (list(f0), list(f1))
+        if self.capture:   # the first batch: the subject as the state sees it in the chunk's first frame
+            self.ctx.track_template(f0[0], self.state, self.templates, self.match.p, self.T, self.stream)
+            self.capture = False
 
     def centres(self, lo, hi):
         """the centres of pairs lo .. hi-1 for a window call: track 0's records, one every 48 * T bytes"""
@@ -843,21 +914,32 @@ class _ChunkTrack:
     def behind(self, ls, js):
         recs = _capi._DeviceSpan(self.base + ls[0] * self.item, len(ls) * self.item)
         self.ctx.track_advance([l % self.ring for l in ls], self.state, recs, self.params, None, self.stream)
+        if self.match is not None:
+            f0, f1 = self.frames
+            out = _capi._DeviceSpan(self.mbase + ls[0] * self.item, len(ls) * self.item)
+            self.ctx.track_match(f0, self.templates, (recs, self.item), out, self.match, self.T, True, self.stream)
+            self.ctx.track_match([f1[-1]], self.templates, (self.state, self.item), self.state_match, self.match, self.T, True,
+                                 self.stream)
         if self.roi is not None:
             self.ctx.roi_weights(len(ls), (recs, self.item), self.maps[ls[0]:ls[-1] + 1], self.roi, self.gate, self.stream)
 
 
-def _chunk_track(ctx, n, center, track, track_out, weights, maps_out, gate, ring, cut_threshold):
-    """None unless center == "track" (track= and track_out= are then refused), else the chunk's _ChunkTrack; weights= of any
-    form is refused next to it"""
+def _chunk_track(ctx, n, center, track, track_out, weights, maps_out, gate, ring, cut_threshold, match_out=None, frames=True):
+    """None unless center == "track" (track=, track_out= and match_out= are then refused), else the chunk's _ChunkTrack;
+    weights= of any form is refused next to it, and track["match"] by a chunk without frames (frames=False)"""
     if center != "track":
         if track is not None or track_out is not None:
             raise ValueError("track= and track_out= need center='track'")
+        if match_out is not None:
+            raise ValueError("match_out= needs center='track' with track['match']")
         return None
+    if not frames and isinstance(track, dict) and track.get("match") is not None:
+        raise ValueError("process_flows: track['match'] needs the frames, which a chunk of caller flows does not have; "
+                         "Context.track_match serves callers who hold frames in the context's frame slots")
     if weights is not None:
         raise ValueError("center='track' together with weights= (a map or a mode) is not supported: the region's own map is "
                          "track={'roi': (ax, ay)}, and weights_gate= is its static gate")
-    return _ChunkTrack(ctx, n, track, track_out, maps_out, gate, ring, cut_threshold)
+    return _ChunkTrack(ctx, n, track, track_out, maps_out, gate, ring, cut_threshold, match_out)
 
 
 def _chain(*hooks):
@@ -1213,11 +1295,22 @@ def center_kwargs(params):
 def _track_carry(engine, params):
     """{"track_carry": the video's track state} with params["hip_center"] = "track" and a "start" in params["hip_track"], else
     {}: pairs never span chunks, but the subject does, so one state tensor serves every chunk of a video (a "state" of the
-    caller's does so by itself)"""
+    caller's does so by itself); with a "match" in it that names no "templates", also {"match_carry": the video's templates
+    and whether the next chunk captures them}: the first chunk does, every later one reuses them"""
     cen = center_kwargs(params)
-    if cen.get("center") != "track" or "start" not in cen["track"]:
+    if cen.get("center") != "track":
         return {}
-    return {"track_carry": track_state(engine.ctx, cen["track"]["start"], cen["track"].get("home"))}
+    track, carry = cen["track"], {}
+    if "start" in track:
+        carry["track_carry"] = track_state(engine.ctx, track["start"], track.get("home"))
+    m = track.get("match")
+    state = carry.get("track_carry", track.get("state"))
+    if isinstance(m, dict) and m.get("templates") is None and state is not None:
+        # the templates are the video's too: captured in the first chunk (unless "capture" says otherwise), carried to the rest
+        tracks = _capi._device_span(state)[1] // _capi.TRACK_STATE_DTYPE.itemsize
+        p = _capi.match_choice({k: m[k] for k in _capi.MATCH_FIELDS if m.get(k) is not None}).p
+        carry["match_carry"] = {"templates": match_templates(engine.ctx, tracks, p), "capture": bool(m.get("capture", True))}
+    return carry
 
 
 def _weighted_scalars(buf, axes):
@@ -1244,6 +1337,9 @@ def _flow_chunks(engine, chunk_flows, fps, total_frames, params, axes, who):
                          "have; Context.consistency_weights serves callers with their own estimator")
     if len(chunk_flows) != len(plan):
         raise ValueError(f"{who}: {len(chunk_flows)} chunks of flows for a plan of {len(plan)} chunks")
+    if isinstance(params.get("hip_track"), dict) and params["hip_track"].get("match") is not None:
+        raise ValueError(f"{who}: hip_track['match'] needs the frames, which caller flows do not have; Context.track_match "
+                         "serves callers who hold the frames in the context's frame slots")
     out, carry = [], _track_carry(engine, params)
     for chunk, flows in zip(plan, chunk_flows):
         d, recs = _chunk_scalars(engine, flows, params, axes, run=engine.process_flows, **carry)
@@ -1283,8 +1379,12 @@ def _chunk_scalars(engine, items, params, axes=False, run=None, **kw):
     kw.update(compensate_kwargs(params))   # params["hip_compensate"]: the fit and the subtraction behind every batch
     carry = kw.pop("track_carry", None)    # the video's track state, carried from chunk to chunk (_track_carry)
     cen = center_kwargs(params)
+    mcarry = kw.pop("match_carry", None)   # the video's templates, likewise: the first chunk captures them
     if carry is not None:
         cen["track"] = {**{k: v for k, v in cen["track"].items() if k not in ("start", "home")}, "state": carry}
+    if mcarry is not None:
+        cen["track"] = {**cen["track"], "match": {**cen["track"]["match"], **mcarry}}
+        mcarry["capture"] = False
     if cen:   # params["hip_center"]: the device schedule about that centre
         return _weighted_scalars(run(items, pov, thr, **cen, **kw), axes)
     ckw = consistency_kwargs(engine, params)

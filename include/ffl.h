@@ -54,6 +54,11 @@
  *                           pass 2 to the tracked region -- which pixels are the subject, not which are reliable (appendix E)
  *   ffl_radial_window_axes_weighted_centres  ffl_radial_window_axes_weighted about the centres of
  *                           ffl_radial_window_axes_centres: the two flags of the window form set together
+ *   ffl_track_template, ffl_track_match  replace nothing: integrating a flow drifts, and these pull a tracked centre back
+ *                           onto a template of the gray frame captured about it -- an integer SSD / zero-mean SSD search
+ *                           within +-s pixels, verdicts FLAT / POOR / AMBIGUOUS, the centre overwritten in place so that
+ *                           every call that reads centres from device memory reads corrected ones (DESIGN.md section 24,
+ *                           appendix N)
  *   ffl_motion_fit, ffl_motion_subtract  replace nothing: the reference cancels global motion only by the quadrant weights
  *                           of radial_motion_weighted ("Cancel out global motion by balancing the averages", FF:779-783), which
  *                           cancel a pan only about the image centre.  These fit a per-pair camera model (translation, rigid,
@@ -842,7 +847,9 @@ int ffl_cells_extra_bytes(int width, int height, int cells, size_t *bytes);
  *       on; track t's records do not depend on n_tracks or on the other tracks.
  * Accepted: radius 1..FFL_MAX_TRACK_RADIUS, on_cut FFL_TRACK_HOLD or FFL_TRACK_HOME, a cut_threshold that is not NaN.  The
  * defaults are 12, HOLD and 7.0f (the reference's cut threshold, FF:876); the radius is the project's own choice and is NOT
- * tuned on footage.  Integrating a flow drifts: re-detection is the caller's, which is why the state lives in caller memory. */
+ * tuned on footage.  Integrating a flow drifts: ffl_track_template and ffl_track_match below (appendix N) pull a track back
+ * onto the appearance it started from, in place; choosing the start point, and re-capturing a template after a scene cut,
+ * stay the caller's, which is why the state lives in caller memory. */
 enum { FFL_MAX_TRACKS = 8, FFL_MAX_TRACK_RADIUS = 32 };
 enum { FFL_TRACK_HOLD = 0, FFL_TRACK_HOME = 1 };                                            /* on_cut */
 enum { FFL_TRACK_OK = 0, FFL_TRACK_CUT = 1, FFL_TRACK_LOST = 2, FFL_TRACK_CLAMPED = 4 };    /* status bits */
@@ -915,6 +922,86 @@ int ffl_radial_window_axes_weighted_centres(ffl_ctx *ctx, int n_seq, const int *
                                             float cut_threshold, int pov_mode, const ffl_dev_weights *w,
                                             const void *centres_dev, ptrdiff_t centre_stride_bytes, ffl_axes_record *out_dev,
                                             uint64_t stream);
+
+/* ---- Template-matching drift correction for tracked regions ----
+ * ffl_track_advance integrates the flow, and a sub-pixel bias of the flow accumulates.  ffl_track_match searches the gray
+ * frame in a frame slot for a template captured about the track (ffl_track_template) and overwrites the centre in place, so
+ * that everything that reads centres from device memory (ffl_roi_weights, the *_centres window forms, the next
+ * ffl_track_advance) reads corrected ones.  The rules are the project's own (the reference has no such function) and are
+ * integer-exact: costs are integers, so there is no order of summation.  For a context of w x h: I is the uint8 gray operand
+ * in a frame slot; Tm is track t's template, (2p+1)^2 uint8, row-major and tight, at templates_dev + t * (2p+1)^2;
+ * N = (2p+1)^2.
+ *   N1  anchor: the centre of (item i, track t) is two doubles at centres_dev + i * centre_stride_bytes + t * 48.  It passes
+ *       through rule Q1's selects (any bit pattern is safe), and (ix, iy) is rule Q2's rounding, floor(c + 0.5).
+ *   N2  samples: for candidate (dx, dy), |dx|, |dy| <= s, and template pixel (i, j) in 0..2p:
+ *       d = I[clamp(iy+dy+j-p, 0, h-1)][clamp(ix+dx+i-p, 0, w-1)] - Tm[j][i], an integer.  Coordinates are clamped, never
+ *       clipped; nothing outside the frame is read.
+ *   N3  cost: S1 = sum d, S2 = sum d^2 in int32 (at p = 16 at most 277695 and 70812225).  FFL_MATCH_SSD: cost = N * S2.
+ *       FFL_MATCH_ZSSD: cost = N * S2 - S1^2, which is >= 0 and invariant to a brightness offset.  Both in int64.
+ *   N4  best: the lexicographic minimum of (cost, dx^2 + dy^2, dy, dx): on exact ties the smallest move wins, and an
+ *       all-equal surface gives (0, 0).
+ *   N5  runner-up: second = the minimum cost over candidates with max(|dx - bdx|, |dy - bdy|) > 1; if there are none (s = 1
+ *       with the best at the centre) second = -1 and N6's ambiguity test is skipped.
+ *   N6  verdict, float64, one rounding per written operation, left to right:
+ *       FLAT       if (double)(N * sum Tm^2 - (sum Tm)^2) < min_var * (double)N * (double)N   (the sums in int64);
+ *       POOR       if (double)cost > max_mse * (double)N * (double)N;
+ *       AMBIGUOUS  if second >= 0 && (double)cost > ratio * (double)second.
+ *       A match is accepted iff status == 0.  The cost surface is always evaluated: records are complete whatever the verdict.
+ *   N7  record (i, t), at index i * n_tracks + t: x, y = ((double)(ix + bdx), (double)(iy + bdy)) through Q1's selects when
+ *       accepted, else the sanitised centre unchanged; dx, dy the best offset, also when rejected; cost, second; status;
+ *       pad = 0.  Its head is again a centre of rule G6 / E1.
+ *   N8  write-back: with write_back = 1 an accepted match also stores x, y into the two doubles the centre was read from.  A
+ *       rejected one stores nothing, not even the sanitised value.
+ *   N9  independence: record (i, t) depends on item i's frame, track t's template and that one centre only.
+ *   N10 capture: Tm[j][i] = I[clamp(iy+j-p, 0, h-1)][clamp(ix+i-p, 0, w-1)] about the anchor of rule N1.
+ * Accepted: p 1..FFL_MAX_MATCH_P, s 1..FFL_MAX_MATCH_S, mode FFL_MATCH_SSD or FFL_MATCH_ZSSD, 0 <= min_var, 0 <= max_mse <=
+ * 65025, 0 < ratio <= 1, all finite.  The defaults are 8, 8, ZSSD, 25, 400 and 0.8: the project's own choice, NOT tuned on
+ * footage.  After a scene cut the template is stale: matches then read POOR and the track falls back to pure advection;
+ * re-capture (ffl_track_template) is the caller's. */
+enum { FFL_MAX_MATCH_P = 16, FFL_MAX_MATCH_S = 16 };
+enum { FFL_MATCH_SSD = 0, FFL_MATCH_ZSSD = 1 };                                   /* mode */
+enum { FFL_MATCH_FLAT = 1, FFL_MATCH_POOR = 2, FFL_MATCH_AMBIGUOUS = 4 };         /* status bits; 0: accepted */
+typedef struct ffl_match_params {
+    int p, s, mode, reserved;   /* reserved: not read */
+    double min_var, max_mse, ratio;
+} ffl_match_params;
+typedef struct ffl_match_record {   /* 48 bytes; rule N7.  Its head (x, y) is a centre of rule G6 / E1 */
+    double x, y;
+    int32_t dx, dy;
+    int64_t cost, second;
+    int32_t status, pad;
+} ffl_match_record;
+int ffl_match_default_params(ffl_match_params *out);
+/* Pure host check: no device or context needed.  FFL_ERR_INVALID with the rule in ffl_last_error(NULL). */
+int ffl_match_params_check(const ffl_match_params *p);
+
+/* n_tracks templates of (2p+1)^2 bytes out of frame slot fslot (rule N10): track t's centre is the two doubles at
+ * centres_dev + t * 48, so an ffl_track_state array, or one item's ffl_track_records, is a valid argument.  Refused before
+ * any device work, each with its rule in the message: n_tracks outside 1..FFL_MAX_TRACKS; a frame slot out of range, or never
+ * uploaded (FFL_ERR_STATE); p outside 1..FFL_MAX_MATCH_P; a NULL pointer; a centres_dev that is not 8-byte aligned; the
+ * centres (48 * (n_tracks - 1) + 16 bytes) or the templates (n_tracks * (2p+1)^2 bytes) that are not device memory of the
+ * context's device inside one allocation, or that overlap; a capturing `stream` (FFL_ERR_STATE).  ffl_texture_weights'
+ * protocol: ONE k_track_template launch, queued on the library's stream behind the work queued on `stream` and the upload that
+ * filled the frame slot; `stream` then waits for it; it counts as a reader of the frame slot; never captured; the host does
+ * not wait.  No scratch memory. */
+int ffl_track_template(ffl_ctx *ctx, int fslot, int n_tracks, const void *centres_dev, int p, void *templates_dev,
+                       uint64_t stream);
+
+/* Item i searches frame slot fslots[i] (slots may repeat) for each of the n_tracks templates about its centre (rules N1 to
+ * N9); p NULL: the defaults.  With n = 1, centres_dev = a state array, centre_stride_bytes = 48 * n_tracks and write_back = 1
+ * the call corrects a track state in place; with centres_dev = a batch's track records (the same stride) it corrects the
+ * centres that ffl_roi_weights and the window calls read afterwards.  Refused before any device work, each with its rule in
+ * the message: n outside 1..max_batch or n_tracks outside 1..FFL_MAX_TRACKS; a NULL list; a frame slot out of range, or never
+ * uploaded (FFL_ERR_STATE); any rule of ffl_match_params_check; a write_back that is not 0 or 1; a NULL pointer; centres_dev
+ * or out_dev that is not 8-byte aligned; a stride that is no multiple of 8 or below 48 * (n_tracks - 1) + 16; any overlap
+ * among the templates, the centres ((n - 1) * stride + 48 * (n_tracks - 1) + 16 bytes) and out_dev (n * n_tracks records);
+ * any of the three that is not device memory of the context's device inside one allocation; a capturing `stream`
+ * (FFL_ERR_STATE).  ffl_texture_weights' protocol: ONE k_track_match launch of (n_tracks, n) workgroups, queued on the
+ * library's stream behind the work queued on `stream` and the uploads that filled the frame slots; `stream` then waits for
+ * it; it counts as a reader of the frame slots; never captured; the host does not wait.  No scratch memory. */
+int ffl_track_match(ffl_ctx *ctx, int n, const int *fslots, int n_tracks, const ffl_match_params *p, const void *templates_dev,
+                    void *centres_dev, ptrdiff_t centre_stride_bytes, int write_back, ffl_match_record *out_dev,
+                    uint64_t stream);
 
 /* ---- Global-motion fit and compensation ----
  * A per-pair parametric camera model, fitted robustly to a resident flow field and subtracted from it, so that what pass 1
