@@ -629,8 +629,9 @@ class PairEngine:
         if trk is not None:
             weights = trk.maps
         maps = weights   # the tensor stays referenced while the calls that read it are queued
+        # the ROI maps are the schedule's own tensor: a chunk without pairs has none to look at, as in process_chunk
         post_out, axes, weights, grid = _chunk_post_args(ctx, n, post_out, axes, weights, center, cells, grid_out,
-                                                         device=trk is not None)
+                                                         check_empty=trk is None, device=trk is not None)
         if n < 1:
             return (_no_scalars(axes), []) if post_out is None else post_out
         post = (_ChunkPost(ctx, n, B, pov_mode, axes) if post_out is None else

@@ -6,17 +6,26 @@ max_batch >= n -- so nothing recycles and every step is ONE documented _capi.Con
 process_chunk's docstring promises:
 
     1. the flow call (flow_pairs / flow_pairs_dis / flow_pairs_farneback(..., window=)), or import_flows of given fields;
-    2. compensate=: motion_fit (under the maps when there are maps), then motion_subtract in place;
-    3. weights=: pass1_weighted            -- or --   center=: cell_stats;
+       weights="consistency": the same call also queues the pairs reversed, into a second block of slots n .. 2n-1;
+    1a. weights="residual" | "texture" | "consistency": residual_weights and / or texture_weights (the combination with gate =
+        out, in place, behind the residual call) or consistency_weights over all n pairs, from the RAW fields;
+    1b. center="track": track_template from frame 0 about the state when capturing; then per batch of `batch` pairs
+        track_advance on the raw fields, with match track_match on the batch's f0 frames about its records and track_match
+        with one item on the batch's last f1 frame about the state, with roi roi_weights.  The state's match happens at batch
+        borders, so its outcome depends on the engine's B: by_hand takes batch=;
+    2. compensate=: motion_fit (under the maps when there are maps, unweighted under a track), then motion_subtract in place;
+    3. weights= (and the track's roi): pass1_weighted            -- or --   center="variance": cell_stats;
     4. one window call over the whole chunk (seq = range(n), first = 0, count = n, radius 6): radial_window[_axes],
-       radial_window_axes_weighted or radial_window_axes_centres.
+       radial_window_axes_weighted, radial_window_axes_centres or radial_window_axes_weighted_centres.
 
 One whole-chunk window call has the bits of the engine's chunked calls (pipeline.window_calls: every computed item's clipped
 window lies inside its call's seq); the per-feature tests rely on that and so does this.
 
-The helper is anchored to the CPU at two points (check_anchors), so that by-hand and engine cannot agree on a wrong answer
-upstream: every raw field of the tuned Farneback path is oracle.farneback of its pair, and every compensated field is
-motion_ref.subtract(raw, model), both on bytes.  No pytest marks: test_gpu_chunk_compose.py compares the engine with it on
+The helper is anchored to the CPU (check_anchors), so that by-hand and engine cannot agree on a wrong answer upstream: every
+raw field of the tuned Farneback path is oracle.farneback of its pair, and every compensated field is
+motion_ref.subtract(raw, model); the maps a mode makes are residual_ref / texture_ref / consistency_ref of the raw fields and
+the clip's frames; track records and the final state are track_ref's over the raw fields, match records, corrected records
+and templates match_ref's (corrected_batch per batch, template), ROI maps track_ref's -- all on bytes, for all n pairs.  No pytest marks: test_gpu_chunk_compose.py compares the engine with it on
 bytes, and test_chunk_schedule_host.py holds the engine's schedules to the same order without a device."""
 import numpy as np
 
@@ -48,9 +57,10 @@ def padded(maps, device):
     return view
 
 
-def hand_context(w, h, n, device=0):
-    """a context on which a chunk of n pairs never recycles anything"""
-    return _capi.Context(w, h, device=device, max_batch=max(n, 1), frame_slots=n + 1, flow_slots=max(n, 1))
+def hand_context(w, h, n, device=0, reverse=False):
+    """a context on which a chunk of n pairs never recycles anything; reverse: with room for the n reversed pairs as well"""
+    k = 2 if reverse else 1
+    return _capi.Context(w, h, device=device, max_batch=k * max(n, 1), frame_slots=n + 1, flow_slots=k * max(n, 1))
 
 
 def _fields(ctx, slots):
@@ -58,47 +68,109 @@ def _fields(ctx, slots):
 
 
 def by_hand(ctx, frames_or_fields, *, pov, thr, axes=True, weights=None, center=None, cells=8, compensate=None, algo=None,
-            window="box"):
+            window="box", residual=None, texture=None, consistency=None, gate=None, track=None, batch=None):
     """The chunk of `frames_or_fields` -- n + 1 gray frames (a list or an (n + 1, H, W) uint8 array), or the n pair fields as a
-    device array (n, H, W, 2) -- on `ctx`, which holds it whole.  weights: None, or an (H, W) / (n, H, W) uint8 device tensor;
-    center: None or "variance" over cells x cells; compensate: as process_chunk takes it; algo: None (Farneback) or ("dis",
-    DisParams or None); window: "box" or "gaussian".  Returns dict(post = the n records as bytes, motion = the n 64-byte
-    records as bytes or None, grid = the cell records as bytes or None, flows = (n, H, W, 2) float32 as left in the slots,
-    pass1 = pass1_results' tuples of the slots as left, raw = (n, H, W, 2) float32 as the flow call left them)."""
+    device array (n, H, W, 2) -- on `ctx`, which holds it whole.  weights: None, an (H, W) / (n, H, W) uint8 device tensor, or
+    "residual" | "texture" | "consistency" with residual= / texture= / consistency= (parameters; texture= next to "residual":
+    the combination) and gate (the static gate, a device tensor); center: None, "variance" over cells x cells, or "track" with
+    track = dict(state = (T,) TRACK_STATE_DTYPE host records, radius, on_cut, roi = (ax, ay) or None, roi_soft, match = a dict
+    of MatchParams fields or None, capture, templates = host bytes when not capturing) and batch, the engine's B; compensate: as
+    process_chunk takes it; algo: None (Farneback) or ("dis", DisParams or None); window: "box" or "gaussian".  Returns dict(post
+    = the n records as bytes, motion = the n 64-byte records as bytes or None, grid = the cell records as bytes or None, flows =
+    (n, H, W, 2) float32 as left in the slots, pass1 = pass1_results' tuples of the slots as left, raw = (n, H, W, 2) float32
+    as the flow call left them, raw_pass1 = pass1_results of the raw fields, raw_bwd = the reversed pairs' raw fields or None,
+    maps / track / state / match / templates = bytes or None)."""
     import torch
     dev = torch.device("cuda", ctx.device)
     given = not isinstance(frames_or_fields, (list, tuple)) and getattr(frames_or_fields, "ndim", 0) == 4
     n = len(frames_or_fields) - (0 if given else 1)
-    assert 1 <= n <= min(ctx.flow_slots, ctx.max_batch), "by_hand needs a context that holds the whole chunk"
+    mode = weights if isinstance(weights, str) else None
+    k = 2 if mode == "consistency" else 1
+    assert 1 <= n and k * n <= min(ctx.flow_slots, ctx.max_batch), "by_hand needs a context that holds the whole chunk"
     assert weights is None or center is None
     assert axes or (weights is None and center is None)
+    assert mode is None or not given, "the modes that make maps read the frames"
     slots = list(range(n))
+    f0, f1 = list(range(n)), list(range(1, n + 1))
     # 1. the flow call
     if given:
         ctx.import_flows(frames_or_fields, slots, pov)
     else:
         assert ctx.frame_slots >= n + 1
         ctx.upload_frames(0, [np.ascontiguousarray(f) for f in frames_or_fields])
-        f0, f1 = list(range(n)), list(range(1, n + 1))
+        a, b, fl = (f0 + f1, f1 + f0, slots + [n + j for j in slots]) if k == 2 else (f0, f1, slots)
         if algo is not None and algo[0] == "dis":
-            ctx.flow_pairs_dis(f0, f1, slots, pov, algo[1])
+            ctx.flow_pairs_dis(a, b, fl, pov, algo[1])
         elif window != "box":
-            ctx.flow_pairs_farneback(f0, f1, slots, pov, None, window=window)
+            ctx.flow_pairs_farneback(a, b, fl, pov, None, window=window)
         else:
-            ctx.flow_pairs(f0, f1, slots, pov)
+            ctx.flow_pairs(a, b, fl, pov)
     raw = _fields(ctx, slots)
+    raw_pass1 = ctx.pass1_results(slots, thr)
+    raw_bwd = _fields(ctx, [n + j for j in slots]) if k == 2 else None
+    # 1a. the maps a mode makes, from the raw fields
+    maps = None
+    if mode is not None:
+        maps = weights = torch.full((n, ctx.height, ctx.width), 0xA5, dtype=torch.uint8, device=dev)
+        if mode == "residual":
+            ctx.residual_weights(f0, f1, slots, maps, _capi.residual_choice(residual), gate)
+            if texture is not None:
+                ctx.texture_weights(f0, maps, _capi.texture_choice(texture), maps)
+        elif mode == "texture":
+            ctx.texture_weights(f0, maps, _capi.texture_choice(texture), gate)
+        else:
+            assert mode == "consistency" and compensate is None
+            ctx.consistency_weights(slots, [n + j for j in slots], maps, _capi.consistency_choice(consistency), gate)
+    # 1b. the track, on the raw fields
+    trk = sd = mout = tmpl = None
+    if center == "track":
+        T = len(track["state"])
+        item = T * _capi.TRACK_DTYPE.itemsize
+        sd = torch.from_numpy(np.array(track["state"], _capi.TRACK_STATE_DTYPE).view(np.uint8).copy()).to(dev)
+        trk = torch.full((n * item,), 0xA5, dtype=torch.uint8, device=dev)
+        tprm = {"radius": track.get("radius", 12), "on_cut": track.get("on_cut", "hold"), "cut_threshold": thr}
+        prm = None
+        if track.get("match") is not None:
+            assert not given, "the match reads the frames"
+            prm = _capi.match_choice(track["match"])
+            mout = torch.full((n * item,), 0xA5, dtype=torch.uint8, device=dev)
+            sout = pipeline.match_buffer(ctx, 1, T)
+            if track.get("capture", track.get("templates") is None):
+                tmpl = pipeline.match_templates(ctx, T, prm.p)
+                ctx.track_template(0, sd, tmpl, prm.p, T)
+            else:
+                tmpl = torch.from_numpy(np.frombuffer(track["templates"], np.uint8).copy()).to(dev)
+        if track.get("roi") is not None:
+            maps = weights = torch.full((n, ctx.height, ctx.width), 0xA5, dtype=torch.uint8, device=dev)
+        for lo in range(0, n, int(batch)):
+            hi = min(lo + int(batch), n)
+            part = trk[lo * item:hi * item]
+            ctx.track_advance(slots[lo:hi], sd, part, tprm)
+            if prm is not None:
+                ctx.track_match(f0[lo:hi], tmpl, (part, item), mout[lo * item:hi * item], prm, T, True)
+                ctx.track_match([f1[hi - 1]], tmpl, (sd, item), sout, prm, T, True)
+            if maps is not None:
+                ctx.roi_weights(hi - lo, (part, item), maps[lo:hi], {"ax": track["roi"][0], "ay": track["roi"][1],
+                                                                     "soft": int(bool(track.get("roi_soft", True)))}, gate=gate)
     # 2. the fit, then the subtraction in place
     motion = None
     if compensate is not None:
         mo = pipeline.motion_buffer(ctx, n)
-        ctx.motion_fit(slots, _capi.motion_choice(compensate), weights=weights, out=mo)
+        ctx.motion_fit(slots, _capi.motion_choice(compensate), weights=None if trk is not None else weights, out=mo)
         ctx.motion_subtract(slots, slots, mo, pov)
         motion = mo.cpu().numpy().tobytes()
     # 3. the records under the maps, or the cell grid and its centres
     item = (_capi.PASS2_AXES_DTYPE if axes else _capi.PASS2_DTYPE).itemsize
     out = torch.full((n * item,), 0xA5, dtype=torch.uint8, device=dev)
     grid = None
-    if weights is not None:
+    if trk is not None:
+        centres = (trk, len(track["state"]) * _capi.TRACK_DTYPE.itemsize)
+        if weights is not None:
+            ctx.pass1_weighted(slots, weights, pov)
+            ctx.radial_window_axes_weighted_centres(slots, 0, n, weights, centres, out, RADIUS, thr, pov)
+        else:
+            ctx.radial_window_axes_centres(slots, 0, n, centres, out, RADIUS, thr, pov)
+    elif weights is not None:
         ctx.pass1_weighted(slots, weights, pov)
         ctx.radial_window_axes_weighted(slots, 0, n, weights, out, RADIUS, thr, pov)
     elif center is not None:
@@ -113,8 +185,9 @@ def by_hand(ctx, frames_or_fields, *, pov, thr, axes=True, weights=None, center=
         ctx.radial_window_axes(slots, 0, n, out, RADIUS, thr, pov)
     else:
         ctx.radial_window(slots, 0, n, out, RADIUS, thr, pov)
-    return dict(post=out.cpu().numpy().tobytes(), motion=motion, grid=grid, flows=_fields(ctx, slots),
-                pass1=ctx.pass1_results(slots, thr), raw=raw)
+    b = lambda t: None if t is None else t.cpu().numpy().tobytes()   # noqa: E731
+    return dict(post=b(out), motion=motion, grid=grid, flows=_fields(ctx, slots), pass1=ctx.pass1_results(slots, thr), raw=raw,
+                raw_pass1=raw_pass1, raw_bwd=raw_bwd, maps=b(maps), track=b(trk), state=b(sd), match=b(mout), templates=b(tmpl))
 
 
 def records(post, axes=True):
@@ -148,3 +221,77 @@ def check_anchors(res, oracle=None):
     models = np.frombuffer(res["motion"], _capi.MOTION_DTYPE, n)
     for j in range(n):
         assert res["flows"][j].tobytes() == mr.subtract(res["raw"][j], mr.six(models[j])).tobytes(), f"compensated field {j}"
+
+
+def mode_maps(frames, raw, mode, residual=None, texture=None, consistency=None, gate=None, raw_bwd=None):
+    """(n, H, W) uint8: the maps of weights=mode on the CPU -- residual_ref / texture_ref / consistency_ref of the raw fields and
+    the frames, the combination as texture_ref under gate = the residual map; gate: the static gate as a host array or None"""
+    import consistency_ref
+    import residual_ref
+    import texture_ref
+    out = []
+    for j in range(len(raw)):
+        if mode == "residual":
+            m = residual_ref.residual(frames[j], frames[j + 1], raw[j], gate=gate, **_capi.residual_choice(residual).as_dict())
+            if texture is not None:
+                m = texture_ref.texture_map(frames[j], gate=m, **_capi.texture_choice(texture).as_dict())
+        elif mode == "texture":
+            m = texture_ref.texture_map(frames[j], gate=gate, **_capi.texture_choice(texture).as_dict())
+        else:
+            m = consistency_ref.consistency(raw[j], raw_bwd[j], gate=gate, **_capi.consistency_choice(consistency).as_dict())
+        out.append(m)
+    return np.stack(out)
+
+
+def track_run(frames, raw, mean_mag, thr, track, batch, gate=None):
+    """The track of a chunk on the CPU: track_ref.advance over the raw fields, per batch of `batch` pairs, its cuts rule Q5 on the
+    raw records' float32 mean magnitudes; with track["match"] match_ref.corrected_batch per batch and match_ref.template.
+    Returns dict(track, state, match, templates, maps) as bytes or None."""
+    import match_ref
+    import track_ref
+    n, (h, w) = len(raw), raw[0].shape[:2]
+    cuts = track_ref.mean_mag_cut(mean_mag, thr)
+    st = np.array(track["state"], track_ref.STATE_DTYPE)
+    radius, on_cut = track.get("radius", 12), _capi.TRACK_ON_CUT.index(track.get("on_cut", "hold"))
+    prm = tm = None
+    if track.get("match") is not None:
+        assert on_cut == track_ref.HOLD, "match_ref.corrected_batch advances with on_cut='hold'"
+        prm = _capi.match_choice(track["match"]).as_dict()
+        prm["mode"] = _capi.MATCH_MODES.index(prm["mode"])
+        if track.get("capture", track.get("templates") is None):
+            tm = match_ref.template(frames[0], np.stack([st["x"], st["y"]], axis=-1), prm["p"])
+        else:
+            side = 2 * prm["p"] + 1
+            tm = np.frombuffer(track["templates"], np.uint8).reshape(len(st), side, side)
+    recs, mrecs = [], []
+    for lo in range(0, n, int(batch)):
+        hi = min(lo + int(batch), n)
+        if prm is None:
+            rec, st = track_ref.advance(raw[lo:hi], cuts[lo:hi], st, radius, on_cut)
+        else:
+            rec, mrec, _, st = match_ref.corrected_batch(track_ref, frames[lo:hi + 1], raw[lo:hi], st, tm, radius, prm, cuts[lo:hi])
+            mrecs.append(mrec)
+        recs.append(rec)
+    rec = np.concatenate(recs)
+    maps = None
+    if track.get("roi") is not None:
+        maps = track_ref.roi_maps(w, h, np.stack([rec["x"][:, 0], rec["y"][:, 0]], axis=-1), track["roi"][0], track["roi"][1],
+                                  bool(track.get("roi_soft", True)), gate).tobytes()
+    return dict(track=rec.tobytes(), state=st.tobytes(), match=np.concatenate(mrecs).tobytes() if mrecs else None,
+                templates=None if tm is None else tm.tobytes(), maps=maps)
+
+
+def check_mode_anchors(res, frames, *, thr, weights=None, residual=None, texture=None, consistency=None, gate=None, center=None,
+                       track=None, batch=None):
+    """The CPU anchors of what by_hand made behind the flow call, on bytes, for all n pairs: the maps of a mode (mode_maps), and
+    under a track its records, final state, match records, templates and ROI maps (track_run).  `gate`: the host array."""
+    if isinstance(weights, str):
+        want = mode_maps(frames, res["raw"], weights, residual, texture, consistency, gate, res["raw_bwd"])
+        got = np.frombuffer(res["maps"], np.uint8).reshape(want.shape)
+        bad = [j for j in range(len(want)) if got[j].tobytes() != want[j].tobytes()]
+        assert not bad, f"the {weights} maps of pairs {bad} are not the restatement's"
+    if center == "track":
+        want = track_run(frames, res["raw"], [r[3] for r in res["raw_pass1"]], thr, track, batch, gate)
+        for key in ("templates", "match", "track", "state", "maps"):
+            assert (res[key] is None) == (want[key] is None), key
+            assert res[key] == want[key], f"the track's {key} are not the restatement's"

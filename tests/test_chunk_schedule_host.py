@@ -13,10 +13,48 @@ map or a centre of another pair, a record read before it was rewritten all show 
 The order held is the one tests/chunk_by_hand.py states for the device: flow -> motion_fit -> motion_subtract ->
 pass1_weighted | cell_stats -> window, with flows_out exported behind the subtraction.
 
+The modes that read FRAME slots behind a batch (pass1_pairs' with_frames hook: weights="residual" | "texture", their
+combination, track["match"]) and the track add three ledgers.  Frames: upload_frames records which frame a frame slot holds,
+and residual_weights, texture_weights, track_match and track_template assert that slot k still holds frame js[k] (f0) or
+js[k] + 1 (f1) of the pair whose flow slot, map address and record address they are given -- a slot re-staged too early, or a
+hook handed another batch's slots, shows as the wrong frame.  Maps: a state machine per pair, unwritten -> residual (from a
+field with no fit and no subtraction) -> texture combined (gate = out, behind the residual write); "texture" alone and the
+ROI map are one write; motion_fit, pass1_weighted and the weighted window forms meet a map only in its final state.  Track: one
+counter "next pair to advance"; track_advance takes consecutive raw pairs from it and writes at first * 48 * T, track_template
+runs at most once, before the first advance, on the slot of frame 0; the records' match runs on the f0 slots of records
+advanced and not yet matched, the state's match is one item on the slot of frame last + 1 straight behind it, roi_weights
+comes after both; the fit under a track is unweighted; the window forms about the track buffer (base lo * 48 * T, stride
+48 * T) find every pair of their seq advanced, matched and mapped.
+
 The cross product n x B x depth x spare slots x schedule x entry point x keyword set x flows_out layout x engine flavour is
 some 10^6 chunks; every AXIS is swept whole, the product is trimmed: every (n, B, depth, spare) context runs a rotating
-choice of four keyword sets, each on a rotating schedule, entry point, layout and flavour, and the test asserts that every
-keyword set met every n, every B, every (depth, spare), both schedules, every entry point and every layout."""
+choice of five keyword sets (PER_CONTEXT; four reached every axis value while there were thirteen sets, not with
+twenty-seven), each on a rotating schedule, entry point, layout and flavour, and the test asserts that every keyword set met
+every n, every B, every (depth, spare), both schedules, every entry point and every layout.  12311 chunks; the file takes 12
+to 17 s on the CPU where its thirteen sets in 9936 chunks took 8: the chunks grew by a quarter, and a chunk of the new sets
+issues up to five more calls per batch (template, advance, two matches, ROI map), each with its own address lookups --
+nothing in the profile stands out, the time is spread over the same functions as before.
+
+What turns these tests red, tried with pipeline.py edited by hand, one edit at a time (every keyword set the edit reaches
+goes red; none of the eleven stays green):
+ 1. _ChunkResidual.with_frames takes its flow slots % (flow_slots - 1) -- residual, residual-gate, residual-texture,
+    compensate-residual, compensate-residual-texture (once the ring wraps: the slot holds another pair, or a fitted field);
+ 2. its maps slice is js[0]:js[-1] -- the same five sets, every chunk: one map too few for the batch;
+ 3. the texture combine queued ahead of the residual call -- residual-texture, compensate-residual-texture: the combination
+    meets an unwritten map;
+ 4. _chain(comp.behind, trk.behind) -- compensate-track-roi-match: the fit runs before the advance of its pairs (and the
+    advance would meet a fitted field);
+ 5. _chunk_motion given the ROI maps -- compensate-track-roi-match: a weighted fit under a track;
+ 6. the records' match on f1 -- track-match, track-match-capture, track-roi-match, compensate-track-roi-match: frame j + 1
+    where pair j needs frame j;
+ 7. the state's match on f0[-1] -- the same four: frame last where the state stands in frame last + 1;
+ 8. roi_weights queued ahead of track_match -- track-roi-match, compensate-track-roi-match: the map is made behind the
+    advance, not behind the state's match;
+ 9. self.capture never cleared -- track-match-capture, track-roi-match, compensate-track-roi-match, from the second batch
+    on: track_template a second time;
+10. centres() with an item of 48 -- track3-home, track-match, track-roi-match (the sets with T > 1): the stride is not 48 * T;
+11. with_frames handed the previous batch's f0 / f1 -- every frame-reading set (the seven residual / texture sets and the
+    four match sets), from the second batch on: the slots hold the previous pairs' frames."""
 import itertools
 import os
 import re
@@ -40,6 +78,7 @@ class Arena:
 
     def __init__(self):
         self.next, self.allocs = 1 << 20, []
+        self.uploaded, self.zeroed = [], []     # tensors made by torch.from_numpy(...).to(device) and by torch.zeros
 
     def take(self, nbytes):
         base = self.next
@@ -123,7 +162,22 @@ def fake_torch(arena):
         shape = tuple(size[0]) if isinstance(size[0], (tuple, list)) else tuple(size)
         return FakeTensor(arena.take(int(np.prod(shape, dtype=np.int64)) * dtype.size), shape, dtype)
 
-    t.empty = empty
+    class Host:
+        """torch.from_numpy(array): all that is asked of it is .to(device)"""
+
+        def __init__(self, array):
+            self.array = array
+
+        def to(self, device):
+            dt = next(d for d in DTYPES.values() if d.typestr == self.array.dtype.str)
+            arena.uploaded.append(FakeTensor(arena.take(self.array.nbytes), self.array.shape, dt))
+            return arena.uploaded[-1]
+
+    def zeros(*size, dtype=None, device=None):
+        arena.zeroed.append(empty(*size, dtype=dtype, device=device))
+        return arena.zeroed[-1]
+
+    t.empty, t.zeros, t.from_numpy = empty, zeros, Host
     return t
 
 
@@ -149,7 +203,9 @@ class Slot:
 class LedgerCtx:
     """Stands in for _capi.Context under every schedule.  `want` is what the chunk was asked for: n, device (schedule), comp,
     maps (None | ("static", base) | ("pair", base, stride)), variance, grid (tensor or None), cons (None | dict(maps, gate)),
-    flows_out ((tensor, layout) or None), motion (tensor or None), item, axes, pov, thr, src (the source arrays of process_flows)."""
+    flows_out ((tensor, layout) or None), motion (tensor or None), item, axes, pov, thr, src (the source arrays of process_flows),
+    frame_maps (None | dict(mode, texture, gate, params): weights="residual" | "texture"), track (None | dict(T, state, on_cut,
+    roi, gate, match, capture, templates, p, track_out, match_out): center="track"; a tensor the caller did not give is None)."""
 
     def __init__(self, arena, max_batch, frame_slots, flow_slots):
         self.arena, self.width, self.height, self.device = arena, W, H, 0
@@ -162,8 +218,73 @@ class LedgerCtx:
         self.centres, self.maps = [0] * n, [0] * n
         self.buffers = {}                       # role -> allocation: one buffer per role and chunk
         self.fwd_slots, self.bwd_slots, self.flow_calls = set(), set(), set()
+        # the maps a mode makes behind a batch, per pair: [] unwritten -> ["residual"] -> ["residual", "texture"], ["texture"], ["roi"]
+        self.made = [[] for _ in range(n)]
+        self.advanced, self.matched = [0] * n, [0] * n
+        self.next_advance = self.templates = self.state_matches = 0
+        self.last = None                        # the latest call queued behind a batch
 
     # -- helpers
+    def _frames(self, fslots, first, who, shift=0):
+        """frame slot k still holds frame first + k + shift of the chunk"""
+        for k, s in enumerate(fslots):
+            assert 0 <= s < self.frame_slots, f"{who}: frame slot {s} out of range"
+            assert self.frames.get(s) == first + k + shift, \
+                f"{who}: frame slot {s} holds frame {self.frames.get(s)}, pair {first + k} needs frame {first + k + shift} there"
+
+    def _map_index(self, out, count, who):
+        """the pair whose map `out` -- a slice of the chunk's (n, H, W) tensor -- starts at; it holds `count` maps"""
+        kind = self.want["maps"]
+        assert isinstance(out, FakeTensor) and kind is not None and kind[0] == "pair", who
+        assert out.shape == (count, H, W) and out.stride() == (kind[2], W, 1), f"{who}: {out.shape[0]} maps for {count} pairs"
+        j, rest = divmod(out.data_ptr() - kind[1], kind[2])
+        assert rest == 0 and 0 <= j and j + count <= self.want["n"], f"{who}: maps outside the chunk's tensor"
+        return j
+
+    def _final(self, first, count, who):
+        """a reader of the maps a mode makes meets them complete: written once, and combined where the chunk combines"""
+        w = self.want
+        if w["frame_maps"] is None and not (w["track"] and w["track"]["roi"]):
+            return
+        final = (["roi"] if w["track"] else ["texture"] if w["frame_maps"]["mode"] == "texture" else
+                 ["residual", "texture"] if w["frame_maps"]["texture"] else ["residual"])
+        for p in range(first, first + count):
+            assert self.made[p] == final, f"{who}: the map of pair {p} is {self.made[p] or 'unwritten'}, meant {final}"
+
+    def _gate(self, gate, want, who):
+        if want is None:
+            assert gate is None, f"{who}: a gate nobody gave"
+        else:
+            assert isinstance(gate, _capi.DevWeights) and (gate.base, gate.item_stride) == (want.data_ptr(), 0), f"{who}: not the static gate"
+
+    def _raw(self, slots, who):
+        for s in slots:
+            assert (self.slots[s].fits, self.slots[s].subtractions, self.slots[s].weighted) == (0, 0, 0), \
+                f"{who}: the field of pair {self.slots[s].pair} is not raw"
+
+    def _tracked(self, first, count, who, maps=False):
+        """records (and ROI maps) of pairs a centre reader meets: advanced, corrected where the chunk matches, written once"""
+        t = self.want["track"]
+        for p in range(first, first + count):
+            assert self.advanced[p] == 1, f"{who}: the record of pair {p} was advanced {self.advanced[p]} times"
+            assert self.matched[p] == (1 if t["match"] else 0), f"{who}: the record of pair {p} was matched {self.matched[p]} times"
+            if maps:
+                assert self.made[p] == ["roi"], f"{who}: the ROI map of pair {p} is {self.made[p] or 'unwritten'}"
+
+    def _track_records(self, centres, who):
+        """(buffer, byte stride) about the chunk's track records: the pair the span starts at and the pairs it holds"""
+        t = self.want["track"]
+        assert isinstance(centres, tuple) and len(centres) == 2 and centres[1] == 48 * t["T"], f"{who}: a stride of {centres[1:]}, meant 48 * T = {48 * t['T']}"
+        ptr, nbytes = _capi._device_span(centres[0])
+        assert nbytes % (48 * t["T"]) == 0, who
+        return self._where("track", ptr, 48 * t["T"], t["track_out"]), nbytes // (48 * t["T"])
+
+    def _state(self, obj, who):
+        t = self.want["track"]
+        made = self.arena.uploaded
+        want = t["state"] if t["state"] is not None else made[0] if len(made) == 1 else None
+        assert want is not None and obj is want, f"{who}: not the chunk's state tensor"
+
     def _stream(self, stream):
         assert stream == ("side" if self.want["device"] else None), f"stream {stream!r}"
 
@@ -268,7 +389,13 @@ class LedgerCtx:
         for s in slots:
             assert (self.slots[s].fits, self.slots[s].subtractions, self.slots[s].weighted) == (0, 0, 0), f"motion_fit: pair {self.slots[s].pair} is not raw"
             self.slots[s].fits += 1
-        self._maps(weights, first, "motion_fit")
+        self.last = "motion_fit"
+        if self.want["track"] is not None:     # the ROI maps say where the subject is, not what is reliable
+            assert weights is None, "motion_fit: weighted under a track"
+            self._tracked(first, len(slots), "motion_fit (behind the advance)")
+        else:
+            self._maps(weights, first, "motion_fit")
+            self._final(first, len(slots), "motion_fit")
         assert self._where("motion", span(out), 64, self.want["motion"]) == first, "motion_out record j is written by the fit of pair j"
         for p in range(first, first + len(slots)):
             self.motion[p] += 1
@@ -289,6 +416,10 @@ class LedgerCtx:
         first = self._held(slots, who="pass1_weighted")
         self._compensated(slots, "pass1_weighted")
         self._maps(weights, first, "pass1_weighted")
+        self._final(first, len(slots), "pass1_weighted")
+        self.last = "pass1_weighted"
+        if self.want["track"] is not None:
+            self._tracked(first, len(slots), "pass1_weighted", maps=True)
         if self.want["cons"] is not None:
             assert all(self.maps[p] == 1 for p in range(first, first + len(slots))), "pass1_weighted before the batch's consistency maps"
         for s in slots:
@@ -323,11 +454,134 @@ class LedgerCtx:
         for p in range(first, first + len(fwd)):
             self.maps[p] += 1
 
+    # -- maps made from the batch's frame slots (pass1_pairs' with_frames hook)
+    def residual_weights(self, fslot0, fslot1, flow_slots, out, params=None, gate=None, stream=None):
+        self._stream(stream)
+        fm = self.want["frame_maps"]
+        assert fm is not None and fm["mode"] == "residual" and isinstance(params, _capi.ResidualParams)
+        assert len(fslot0) == len(fslot1) == len(flow_slots)
+        first = self._held(flow_slots, who="residual_weights")
+        self._raw(flow_slots, "residual_weights")            # before the fit: the maps are those of the estimator's field
+        assert self._map_index(out, len(flow_slots), "residual_weights") == first, "residual_weights: the maps of other pairs"
+        self._frames(fslot0, first, "residual_weights (f0)")
+        self._frames(fslot1, first, "residual_weights (f1)", shift=1)
+        self._gate(gate, fm["gate"], "residual_weights")
+        if fm["params"] is not None:
+            assert {k: pytest.approx(v) for k, v in fm["params"].items()} == {k: params.as_dict()[k] for k in fm["params"]}
+        for p in range(first, first + len(flow_slots)):
+            assert self.made[p] == [], f"residual_weights: the map of pair {p} is already {self.made[p]}"
+            self.made[p].append("residual")
+        self.last = "residual_weights"
+
+    def texture_weights(self, fslots, out, params=None, gate=None, stream=None):
+        self._stream(stream)
+        fm = self.want["frame_maps"]
+        assert fm is not None and isinstance(params, _capi.TextureParams)
+        first = self._map_index(out, len(fslots), "texture_weights")
+        self._frames(fslots, first, "texture_weights")      # frame 0 of the pair the map belongs to
+        if fm["mode"] == "residual":     # the combination: in place, behind the residual call
+            assert fm["texture"], "texture_weights without texture="
+            assert isinstance(gate, FakeTensor) and (gate.data_ptr(), gate.shape, gate.stride()) == (out.data_ptr(), out.shape, out.stride()), \
+                "texture_weights: the combination is gate = out"
+            before = ["residual"]
+        else:
+            self._gate(gate, fm["gate"], "texture_weights")
+            before = []
+        for p in range(first, first + len(fslots)):
+            assert self.made[p] == before, f"texture_weights: the map of pair {p} is {self.made[p] or 'unwritten'}, meant {before or 'unwritten'}"
+            self.made[p].append("texture")
+        self.last = "texture_weights"
+
+    # -- the track
+    def track_template(self, fslot, centres, templates, p=None, tracks=None, stream=None):
+        self._stream(stream)
+        t = self.want["track"]
+        assert t is not None and t["match"] and t["capture"], "track_template without capture"
+        assert self.templates == 0, "track_template a second time"
+        assert self.next_advance == 0 and self.last is None, "track_template behind an advance"
+        self._frames([fslot], 0, "track_template")
+        self._state(centres, "track_template")
+        self._templates(templates, "track_template")
+        assert (p, tracks) == (t["p"], t["T"])
+        self.templates += 1
+
+    def _templates(self, templates, who):
+        t = self.want["track"]
+        made = self.arena.zeroed
+        want = t["templates"] if t["templates"] is not None else made[0] if len(made) == 1 else None
+        assert want is not None and templates is want, f"{who}: not the chunk's templates"
+
+    def track_advance(self, seq_slots, state, out, params=None, weights=None, stream=None):
+        self._stream(stream)
+        t = self.want["track"]
+        assert t is not None and weights is None and isinstance(params, _capi.TrackParams)
+        assert params.as_dict()["on_cut"] == t["on_cut"] and params.cut_threshold == np.float32(self.want["thr"])
+        first = self._held(seq_slots, self.next_advance, who="track_advance")
+        self._raw(seq_slots, "track_advance")               # rule Q5's cut is the raw whole-frame mean magnitude
+        self._state(state, "track_advance")
+        ptr, nbytes = _capi._device_span(out)
+        assert self._where("track", ptr, 48 * t["T"], t["track_out"]) == first, "track_advance: its records are not at first * 48 * T"
+        assert nbytes == len(seq_slots) * 48 * t["T"]
+        assert self.templates == (1 if t["match"] and t["capture"] else 0), "track_advance: the template is captured before the first advance, or never"
+        for p in range(first, first + len(seq_slots)):
+            self.advanced[p] += 1
+        self.next_advance += len(seq_slots)
+        self.last = ("track_advance", first, len(seq_slots))
+
+    def track_match(self, fslots, templates, centres, out, params=None, tracks=1, write_back=True, stream=None):
+        self._stream(stream)
+        t = self.want["track"]
+        assert t is not None and t["match"] and isinstance(params, _capi.MatchParams) and write_back is True
+        assert (params.p, tracks) == (t["p"], t["T"])
+        self._templates(templates, "track_match")
+        assert isinstance(centres, tuple) and len(centres) == 2
+        if isinstance(centres[0], FakeTensor) and self.arena.find(centres[0].data_ptr()) == self.arena.find(self._state_ptr()):
+            # about the state: one item on the frame the state stands in, straight behind the records' match of the batch
+            self._state(centres[0], "track_match (state)")
+            assert centres[1] == 48 * t["T"] and len(fslots) == 1
+            assert self.last is not None and self.last[0] == "records_match" and self.last[1] + self.last[2] == self.next_advance, \
+                f"track_match (state): behind {self.last}, not behind the records' match of its batch"
+            self._frames(fslots, self.next_advance, "track_match (state)")       # frame last + 1
+            assert self.arena.find(span(out))[0] not in (self.buffers.get("track"), self.buffers.get("match")), "track_match (state): its records go to a buffer of their own"
+            self.state_matches += 1
+            self.last = ("state_match",)
+            return
+        first, count = self._track_records(centres, "track_match")
+        assert count == len(fslots), f"track_match: {len(fslots)} frame slots for the records of {count} pairs"
+        assert self.last == ("track_advance", first, count), f"track_match of pairs {first}..{first + count - 1}: behind {self.last}, not behind their advance"
+        self._frames(fslots, first, "track_match")          # the f0 slots: a record is the track's place in frame 0 of its pair
+        ptr, nbytes = _capi._device_span(out)
+        assert self._where("match", ptr, 48 * t["T"], t["match_out"]) == first and nbytes == count * 48 * t["T"]
+        for p in range(first, first + count):
+            assert (self.advanced[p], self.matched[p]) == (1, 0), f"track_match: pair {p} advanced {self.advanced[p]}, matched {self.matched[p]} times"
+            self.matched[p] += 1
+        self.last = ("records_match", first, count)
+
+    def _state_ptr(self):
+        t = self.want["track"]
+        return (t["state"] if t["state"] is not None else self.arena.uploaded[0]).data_ptr()
+
+    def roi_weights(self, n, centres, out, params=None, gate=None, stream=None):
+        self._stream(stream)
+        t = self.want["track"]
+        assert t is not None and t["roi"] and isinstance(params, _capi.RoiParams)
+        first, count = self._track_records(centres, "roi_weights")
+        assert count == n and self._map_index(out, n, "roi_weights") == first, "roi_weights: the maps of other pairs"
+        assert self.last == (("state_match",) if t["match"] else ("track_advance", first, n)), \
+            f"roi_weights of pairs {first}..{first + n - 1}: behind {self.last}"
+        self._tracked(first, n, "roi_weights")
+        self._gate(gate, t["gate"], "roi_weights")
+        for p in range(first, first + n):
+            assert self.made[p] == [], f"roi_weights: the map of pair {p} is already written"
+            self.made[p].append("roi")
+        self.last = "roi_weights"
+
     # -- the window calls
     def _window(self, form, seq, first, count, out, radius, thr, pov, stream, weights=None, centres=None):
         self._stream(stream)
         w, n = self.want, self.want["n"]
-        want_form = ("centres" if w["variance"] else "weighted" if w["maps"] is not None else "axes" if w["axes"] else "plain")
+        want_form = ("weighted_centres" if w["track"] and w["track"]["roi"] else "centres" if w["variance"] or w["track"] else
+                     "weighted" if w["maps"] is not None else "axes" if w["axes"] else "plain")
         assert form == want_form, f"radial_window form {form}, meant {want_form}"
         assert (radius, thr, pov) == (RADIUS, w["thr"], w["pov"]) and 1 <= count and 0 <= first and first + count <= len(seq)
         j0 = self._where("post", span(out), w["item"], w["post"])
@@ -338,9 +592,15 @@ class LedgerCtx:
         for j in range(j0, j0 + count):
             assert lo <= max(0, j - RADIUS) and min(n, j + RADIUS + 1) <= lo + len(seq), f"the window of pair {j} is clipped by its call"
             self.post[j] += 1
-        if form == "weighted":
-            self._maps(weights, j0, "radial_window_axes_weighted")
-        if form == "centres":
+        self.last = "window"
+        if form in ("weighted", "weighted_centres"):
+            self._maps(weights, j0, "radial_window_axes_" + form)
+            self._final(j0, count, "radial_window_axes_" + form)
+        if w["track"] is not None:      # about the track buffer: base lo * 48 * T, stride 48 * T, every pair of the seq complete
+            got = self._track_records(centres, "radial_window_axes_" + form)
+            assert got == (lo, len(seq)), f"radial_window_axes_{form}: centres of pairs {got[0]}.. for a seq of pairs {lo}.."
+            self._tracked(lo, len(seq), "radial_window_axes_" + form, maps=bool(w["track"]["roi"]))
+        elif form == "centres":
             assert self._where("centres", span(centres), _capi.GRID_CENTRE_DTYPE.itemsize) == lo
             assert all(self.centres[p] == 1 for p in range(lo, lo + len(seq))), "a centre read before cell_stats of its pair wrote it"
         return out
@@ -356,6 +616,9 @@ class LedgerCtx:
 
     def radial_window_axes_centres(self, seq, first, n, centres, out, radius=6, thr=7.0, pov=False, stream=None):
         return self._window("centres", seq, first, n, out, radius, thr, pov, stream, centres=centres)
+
+    def radial_window_axes_weighted_centres(self, seq, first, n, weights, centres, out, radius=6, thr=7.0, pov=False, stream=None):
+        return self._window("weighted_centres", seq, first, n, out, radius, thr, pov, stream, weights=weights, centres=centres)
 
     # -- flows_out and the host schedule
     def export_flows(self, slots, out=None, layout="nhwc", stream=None):
@@ -411,6 +674,21 @@ class LedgerCtx:
         assert self.centres == (ones if w["variance"] else [0] * n)
         assert self.maps == (ones if w["cons"] is not None else [0] * n)
         assert not (self.fwd_slots & self.bwd_slots), "a flow slot held forward and reversed pairs"
+        t, fm = w["track"], w["frame_maps"]
+        assert self.advanced == (ones if t else [0] * n), f"pairs advanced {self.advanced}"
+        assert self.matched == (ones if t and t["match"] else [0] * n), f"pairs matched {self.matched}"
+        assert self.next_advance == (n if t else 0)
+        assert self.state_matches == (-(-n // self.max_batch) if t and t["match"] else 0), f"{self.state_matches} state matches"
+        assert self.templates == (1 if t and t["match"] and t["capture"] and n else 0), f"{self.templates} template captures"
+        if t or fm:
+            self._final(0, n, "the chunk's end")
+        else:
+            assert self.made == [[] for _ in range(n)]
+        if t and n:
+            for role, given in (("track", t["track_out"]), ("match", t["match_out"] if t["match"] else None)):
+                if given is not None:
+                    assert self.buffers[role] == self.arena.find(given.data_ptr())[0], f"{role}_out is not the caller's buffer"
+            assert ("match" in self.buffers) == bool(t["match"])
         if w["device"]:
             assert self.collected == [0] * n and isinstance(result, FakeTensor)
             if w["post"] is not None:
@@ -473,6 +751,47 @@ def compensate(arena, n, model="translation", out=True):
     return kw, want
 
 
+def frame_maps(arena, n, mode="residual", texture=False, gate=False):
+    """weights="residual" | "texture"; gate=True: a static gate, the caller's own weights_out and explicit parameters"""
+    kw, want = {"weights": mode}, {"frame_maps": {"mode": mode, "texture": texture, "gate": None, "params": None}}
+    if texture:
+        kw["texture"] = True if not gate else {"radius": 3, "tau": 40.0}
+    if gate:
+        kw["weights_gate"] = want["frame_maps"]["gate"] = tensor(arena, (H, W))
+        kw["weights_out"] = tensor(arena, (n, H, W))
+        if mode == "residual":
+            kw["residual"] = want["frame_maps"]["params"] = {"alpha": 0.75, "beta": 3.0, "soft": 0}
+    return kw, want
+
+
+def track(arena, n, T=1, state=False, on_cut="hold", roi=False, match=None, out=False):
+    """center="track": T tracks from `start`, or from a state tensor of the caller's; roi: maps with a static gate into the
+    caller's weights_out; match: None, "templates" (the caller's, capture off) or "capture"; out: the caller's track_out
+    (and match_out)"""
+    tr = {"on_cut": on_cut, "radius": 5}
+    want = {"T": T, "state": None, "on_cut": on_cut, "roi": roi, "gate": None, "match": match is not None, "capture": False,
+            "templates": None, "p": None, "track_out": None, "match_out": None}
+    if state:
+        tr["state"] = want["state"] = tensor(arena, (T * _capi.TRACK_STATE_DTYPE.itemsize,))
+    else:
+        tr["start"] = [(20.0 + 7 * t, 30.0 - 5 * t) for t in range(T)] if T > 1 else (20.0, 30.0)
+    kw = {"center": "track", "track": tr}
+    if roi:
+        tr["roi"] = (12.0, 9.0)
+        kw["weights_gate"] = want["gate"] = tensor(arena, (H, W))
+        kw["weights_out"] = tensor(arena, (n, H, W))
+    if match is not None:
+        tr["match"] = {"p": 6, "s": 4}
+        want["p"], want["capture"] = 6, match == "capture"
+        if match == "templates":
+            tr["match"]["templates"] = want["templates"] = tensor(arena, (T, 13, 13))
+    if out:
+        kw["track_out"] = want["track_out"] = tensor(arena, (max(n, 1) * T * 48 + 16,))
+        if match is not None:
+            kw["match_out"] = want["match_out"] = tensor(arena, (max(n, 1) * T * 48,))
+    return kw, {"track": want}
+
+
 def both(a, b):
     def make(arena, n):
         (k1, w1), (k2, w2) = a(arena, n), b(arena, n)
@@ -495,8 +814,24 @@ KEYWORDS = {
     "compensate-static-map": both(lambda arena, n: compensate(arena, n, "rigid"), static_map),
     "compensate-pair-maps": both(lambda arena, n: compensate(arena, n, "similarity", out=False), pair_maps),
     "compensate-variance": both(lambda arena, n: compensate(arena, n, "affine"), lambda arena, n: variance(arena, n, grid=True)),
+    "residual": frame_maps,
+    "residual-gate": lambda arena, n: frame_maps(arena, n, gate=True),
+    "texture": lambda arena, n: frame_maps(arena, n, "texture"),
+    "residual-texture": lambda arena, n: frame_maps(arena, n, texture=True),
+    "compensate-residual": both(lambda arena, n: compensate(arena, n, "similarity"), frame_maps),
+    "compensate-texture": both(lambda arena, n: compensate(arena, n, "rigid", out=False), lambda arena, n: frame_maps(arena, n, "texture", gate=True)),
+    "compensate-residual-texture": both(compensate, lambda arena, n: frame_maps(arena, n, texture=True, gate=True)),
+    "track": track,
+    "track3-home": lambda arena, n: track(arena, n, T=3, state=True, on_cut="home", out=True),
+    "track-roi": lambda arena, n: track(arena, n, roi=True),
+    "track-match": lambda arena, n: track(arena, n, T=2, match="templates", out=True),
+    "track-match-capture": lambda arena, n: track(arena, n, match="capture"),
+    "track-roi-match": lambda arena, n: track(arena, n, T=2, state=True, roi=True, match="capture", out=True),
+    "compensate-track-roi-match": both(lambda arena, n: compensate(arena, n, "affine"), lambda arena, n: track(arena, n, roi=True, match="capture")),
 }
+FRAME_READERS = tuple(k for k in KEYWORDS if "residual" in k or "texture" in k or "match" in k)      # process_chunk only
 ENTRIES = ("chunk", "flows", "segments")
+PER_CONTEXT = 5                                 # keyword sets every (n, B, depth, spare) context runs
 LAYOUTS = (None, "nhwc", "nchw")
 FLAVOURS = {"tuned": {}, "dis": {"flow": "dis"}, "gaussian": {"window": "gaussian"},
             "params": {"farneback": _capi.FarnebackParams(winsize=13)}}
@@ -519,9 +854,9 @@ def run_chunk(n, B, depth, spare, device, entry, name, layout, flavour, turn=0):
         eng = pipeline.PairEngine(ctx, depth=depth, **(FLAVOURS[flavour] if entry == "chunk" else {}))
         kw, want = KEYWORDS[name](arena, n)
         pov, thr = bool((n + B) & 1), 0.5 + depth
-        forced = any(k in want for k in ("maps", "variance", "cons"))      # these run the device schedule whatever post_out says
+        forced = any(k in want for k in ("maps", "variance", "cons", "frame_maps", "track"))      # these run the device schedule whatever post_out says
         want = {"n": n, "comp": False, "maps": None, "variance": False, "grid": None, "cons": None, "flows_out": None, "motion": None,
-                "axes": False, "post": None, "src": (), "pov": pov, "thr": thr, **want}
+                "axes": False, "post": None, "src": (), "pov": pov, "thr": thr, "frame_maps": None, "track": None, **want}
         want["device"] = device or forced
         want["axes"] = want["axes"] or forced
         want["item"] = (_capi.PASS2_AXES_DTYPE if want["axes"] else _capi.PASS2_DTYPE).itemsize
@@ -529,15 +864,10 @@ def run_chunk(n, B, depth, spare, device, entry, name, layout, flavour, turn=0):
             kw["post_out"] = True
             if turn % 2:
                 kw["post_out"] = want["post"] = tensor(arena, (max(n, 1) * want["item"] + 16,))
-        if entry == "chunk":
-            if layout is not None:
-                t = tensor(arena, (n, H, W, 2) if layout == "nhwc" else (n, 2, H, W), "float32")
-                kw["flows_out"], want["flows_out"] = t, (t, layout)
-            if want["cons"] is not None:            # the chunk's maps: the caller's tensor, or one the schedule makes
-                own = kw.get("weights_out")
-                want["maps"] = ("pair", own.data_ptr(), H * W) if own is not None else ("pair-unknown",)
-            ctx.begin(want)
-            if want["maps"] == ("pair-unknown",):
+        if want["cons"] is not None or want["frame_maps"] is not None or (want["track"] is not None and want["track"]["roi"]):
+            own = kw.get("weights_out")             # the chunk's maps: the caller's tensor, or one the schedule makes
+            want["maps"] = ("pair", own.data_ptr(), H * W) if own is not None else ("pair-unknown",)
+            if own is None:
                 real = sys.modules["torch"].empty
 
                 def empty(*size, dtype=None, device=None):
@@ -546,6 +876,11 @@ def run_chunk(n, B, depth, spare, device, entry, name, layout, flavour, turn=0):
                         want["maps"] = ("pair", t.data_ptr(), H * W)
                     return t
                 sys.modules["torch"].empty = empty
+        if entry == "chunk":
+            if layout is not None:
+                t = tensor(arena, (n, H, W, 2) if layout == "nhwc" else (n, 2, H, W), "float32")
+                kw["flows_out"], want["flows_out"] = t, (t, layout)
+            ctx.begin(want)
             result = eng.process_chunk(list(range(n + 1)), pov, thr, **kw)
             if n:
                 assert ctx.flow_calls == {flavour}
@@ -584,6 +919,8 @@ def no_device(monkeypatch):
 def applicable(name, entry, n, B):
     if name.startswith("consistency"):
         return entry == "chunk" and B >= 2          # process_flows has no backward fields; a batch is max_batch // 2 pairs
+    if name in FRAME_READERS:
+        return entry == "chunk"                     # process_flows has no frames
     if "pair-maps" in name:
         return n >= 1                               # (0, H, W) is no tensor of maps
     return True
@@ -594,8 +931,8 @@ def test_every_schedule_keeps_every_slot_live_for_its_readers():
     seen = {k: set() for k in ("n", "B", "ctx", "device", "entry", "layout", "flavour")}
     chunks = 0
     for c, (n, B, depth, spare) in enumerate(itertools.product(NS, BS, DEPTHS, SPARE)):
-        for i in range(4):
-            t = c * 4 + i
+        for i in range(PER_CONTEXT):
+            t = c * PER_CONTEXT + i
             name = names[(c + 3 * i + n) % len(names)]
             entry = ENTRIES[(t // 2 + n) % 3]
             if not applicable(name, entry, n, B):
@@ -623,10 +960,18 @@ def test_every_schedule_keeps_every_slot_live_for_its_readers():
         assert {v for k, v in seen["B"] if k == name} == set(BS) - ({1} if cons else set()), name
         assert {v for k, v in seen["ctx"] if k == name} == set(itertools.product(DEPTHS, SPARE)), name
         assert {v for k, v in seen["device"] if k == name} == ({True} if forced else {True, False}), name
-        assert {v for k, v in seen["entry"] if k == name} == ({"chunk"} if cons else set(ENTRIES)), name
+        assert {v for k, v in seen["entry"] if k == name} == ({"chunk"} if cons or name in FRAME_READERS else set(ENTRIES)), name
         assert {v for k, v in seen["layout"] if k == name} == set(LAYOUTS), name
         assert {v for k, v in seen["flavour"] if k == name} == set(FLAVOURS), name
-    assert chunks > 9000
+    assert chunks > 12000
+
+
+@pytest.mark.parametrize("entry", ENTRIES)
+def test_a_chunk_without_pairs_under_a_track_with_roi(entry):
+    """the ROI maps are the schedule's own (0, H, W) tensor: process_flows once looked at it and refused the chunk, where
+    process_chunk returned the empty result (the sweep above meets n = 0 under every set, but not under every entry point)"""
+    for name in ("track", "track-roi"):
+        run_chunk(0, 3, 1, 0, True, entry, name, None, "tuned")
 
 
 # ---- window_calls, a pure function ------------------------------------------------------------------------------------------------
