@@ -34,6 +34,9 @@ TRACK_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("du", "<f8"), ("dv", "<f8")
 FFL_MAX_MATCH_P, FFL_MAX_MATCH_S = 16, 16
 MATCH_MODES = ("ssd", "zssd")                                 # FFL_MATCH_SSD, FFL_MATCH_ZSSD
 MATCH_FLAT, MATCH_POOR, MATCH_AMBIGUOUS = 1, 2, 4             # status bits of a record; 0: accepted
+# whole-frame re-detection: its records are MATCH_DTYPE
+FFL_MAX_REDETECT_EXCLUDE, REDETECT_SKIPPED = 32, 8            # rule L5's square at most; the status of a search that did not run
+MATCH_STATUS_OFFSET = 40                                      # a record's int32 `status`: rule L1's intended trigger word
 MATCH_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("dx", "<i4"), ("dy", "<i4"), ("cost", "<i8"), ("second", "<i8"),
                         ("status", "<i4"), ("pad", "<i4")])
 
@@ -713,6 +716,45 @@ def match_choice(params):
     return params
 
 
+REDETECT_FIELDS = ("p", "mode", "exclude", "reach", "trigger_mask", "min_var", "max_mse", "ratio")
+
+
+class RedetectParams(C.Structure):
+    """ffl_redetect_params: p, mode and the three thresholds as MatchParams has them; exclude (1..32:
+    the runner-up is the best candidate further than this, Chebyshev, from the best), reach (0: the whole frame; 1..32768:
+    candidates within +-reach of the centre) and trigger_mask (a search runs iff its trigger word & trigger_mask != 0).
+    RedetectParams() holds the library's defaults -- the match defaults with exclude = p, reach 0 and trigger_mask =
+    MATCH_POOR; the project's own choice, not tuned on footage; keywords override single fields."""
+    _fields_ = [("p", C.c_int), ("mode", C.c_int), ("exclude", C.c_int), ("reach", C.c_int), ("trigger_mask", C.c_int),
+                ("reserved", C.c_int), ("min_var", C.c_double), ("max_mse", C.c_double), ("ratio", C.c_double)]
+
+    def __init__(self, **over):
+        super().__init__()
+        load().ffl_redetect_default_params(C.byref(self))
+        for k, v in over.items():
+            if k not in REDETECT_FIELDS:
+                raise ValueError(f"unknown redetect parameter {k!r} {REDETECT_FIELDS}")
+            setattr(self, k, match_mode(v) if k == "mode" else v)
+
+    def as_dict(self):
+        return {"p": self.p, "mode": MATCH_MODES[self.mode] if self.mode in (0, 1) else self.mode, "exclude": self.exclude,
+                "reach": self.reach, "trigger_mask": self.trigger_mask, "min_var": self.min_var, "max_mse": self.max_mse,
+                "ratio": self.ratio}
+
+
+def redetect_params_check(params):
+    """ffl_redetect_params_check: ValueError with the library's rule when it refuses (pure host check)."""
+    _check(load().ffl_redetect_params_check(None if params is None else C.byref(params)), exc=ValueError)
+
+
+def redetect_choice(params):
+    """a RedetectParams out of None (the defaults), a dict of its fields or a RedetectParams; checked"""
+    if not isinstance(params, RedetectParams):
+        params = RedetectParams(**dict(params or {}))
+    redetect_params_check(params)
+    return params
+
+
 class MotionParams(C.Structure):
     """ffl_motion_params: the sub-model of rule C2 (a name of MOTION_MODELS or its code), the passes of
     rule C7 and the Cauchy scale tau of rule C3 in pixels.  MotionParams() holds the library's defaults (rule C9: translation,
@@ -956,6 +998,10 @@ SIGNATURES = {
     "ffl_match_params_check": (_i, (_P(MatchParams),)),
     "ffl_track_template": (_i, (_ctx, _i, _i, _vp, _i, _vp, _u64)),
     "ffl_track_match": (_i, (_ctx, _i, _ip, _i, _P(MatchParams), _vp, _vp, _pd, _i, _vp, _u64)),
+    "ffl_redetect_default_params": (_i, (_P(RedetectParams),)),
+    "ffl_redetect_params_check": (_i, (_P(RedetectParams),)),
+    "ffl_redetect_extra_bytes": (_i, (_i,) * 3 + (_szp,)),
+    "ffl_track_redetect": (_i, (_ctx, _i, _ip, _i, _P(RedetectParams), _vp, _vp, _pd, _vp, _pd, _i, _vp, _u64)),
     "ffl_motion_default_params": (_i, (_P(MotionParams),)),
     "ffl_motion_params_check": (_i, (_P(MotionParams),)),
     "ffl_motion_solve": (_i, (_dp, _i, _vp)),
@@ -999,7 +1045,7 @@ RECORDS = {"ffl_source_info": SourceInfo, "ffl_dev_frame": DevFrame, "ffl_dev_fl
            "ffl_cell_record": CELL_DTYPE, "ffl_grid_centre": GRID_CENTRE_DTYPE, "ffl_motion_params": MotionParams,
            "ffl_motion_record": MOTION_DTYPE, "ffl_dis_params": DisParams, "ffl_track_params": TrackParams,
            "ffl_track_state": TRACK_STATE_DTYPE, "ffl_track_record": TRACK_DTYPE, "ffl_roi_params": RoiParams,
-           "ffl_match_params": MatchParams, "ffl_match_record": MATCH_DTYPE,
+           "ffl_match_params": MatchParams, "ffl_match_record": MATCH_DTYPE, "ffl_redetect_params": RedetectParams,
            "ffl_farneback_params": FarnebackParams}
 
 _lib = None
@@ -1088,6 +1134,12 @@ def cells_extra_bytes(width, height, cells):
 def motion_extra_bytes(width, height):
     """Device bytes the first motion_fit call of a Context of this size allocates (estimate_bytes does not count them)."""
     return _sizes("ffl_motion_extra_bytes", width, height)
+
+
+def redetect_extra_bytes(width, height, max_batch):
+    """Device bytes the first track_redetect call of a Context of this size and max_batch allocates (estimate_bytes does not
+    count them).  Needs no device."""
+    return _sizes("ffl_redetect_extra_bytes", width, height, max_batch)
 
 
 def cell_grid(width, height, cells):
@@ -1723,6 +1775,38 @@ class Context:
         wb = int(write_back) if isinstance(write_back, (bool, int, np.integer)) else -1
         self._chk(self.L.ffl_track_match(self._h, n, ps, T, C.byref(prm), tptr, cptr, stride, wb, optr,
                                          stream_handle(stream, self.device)))
+        return out
+
+    def track_redetect(self, fslots, templates, centres, out, params=None, tracks=1, trigger=None, write_back=True, stream=None):
+        """Search frame slot fslots[i] as a whole (or within params' reach) for every track's template and put item i's
+        centres onto it (ffl_track_redetect): `templates`, `centres`, `out`, `tracks` and `write_back`
+        as track_match takes them; the records are MATCH_DTYPE, with status REDETECT_SKIPPED for a search that did not run.
+        `trigger`: None (every search runs), a buffer of len(fslots) * tracks match records -- a search runs iff its record's
+        status & params.trigger_mask != 0 -- or an explicit (pointer or device buffer, byte stride) span of int32 words, track
+        t's at + 48 t.  `params`: a RedetectParams, a dict of its fields or None (the defaults, which are not tuned on
+        footage).  Queued behind the work on `stream` and the uploads that filled the slots; `stream` waits for it; the host
+        does not wait.  Returns `out`."""
+        ps, slots = _iarr(fslots)
+        n, T = len(slots), int(tracks)
+        prm = params if isinstance(params, RedetectParams) else RedetectParams(**dict(params or {}))
+        cptr, stride = _centre_entries(centres, n)
+        tptr, _ = _device_span(templates)
+        optr, extent = _device_span(out)
+        if extent < n * T * MATCH_DTYPE.itemsize:
+            raise ValueError(f"track_redetect: out holds {extent} bytes, {n} x {T} records need {n * T * MATCH_DTYPE.itemsize}")
+        gptr, gstride = None, 0
+        if isinstance(trigger, tuple) and len(trigger) == 2 and isinstance(trigger[1], (int, np.integer)):
+            gptr, gstride = trigger
+            gptr = int(gptr) if isinstance(gptr, (int, np.integer)) else _array_view(gptr)[0]
+        elif trigger is not None:
+            gptr, gbytes = _device_span(trigger)
+            if gbytes < n * T * MATCH_DTYPE.itemsize:
+                raise ValueError(f"track_redetect: trigger holds {gbytes} bytes, {n} x {T} match records need "
+                                 f"{n * T * MATCH_DTYPE.itemsize}")
+            gptr, gstride = gptr + MATCH_STATUS_OFFSET, T * MATCH_DTYPE.itemsize
+        wb = int(write_back) if isinstance(write_back, (bool, int, np.integer)) else -1
+        self._chk(self.L.ffl_track_redetect(self._h, n, ps, T, C.byref(prm), tptr, cptr, stride, gptr, int(gstride), wb, optr,
+                                            stream_handle(stream, self.device)))
         return out
 
     def motion_fit(self, slots, model="translation", iterations=3, tau=1.0, weights=None, prior=None, out=None, sums_out=None,

@@ -364,6 +364,8 @@ struct ffl_ctx {
     DevBuf<double> d_cellrow;
     // ffl_motion_fit: FFL_MOTION_NSUMS partials per workgroup of the radial grid.
     DevBuf<double> d_mpsum;
+    // ffl_track_redetect: ffl_redetect_words 64-bit words per search, max_batch x FFL_MAX_TRACKS searches.
+    DevBuf<double> d_rdscr;
     int p1_blocks = 0;
     // profiling
     unsigned prof_mask = 0;   // bit k set: bracket every launch of kernel class k with HIP events
@@ -2131,38 +2133,41 @@ int ffl_pass1_results(ffl_ctx *c, int n, const int *slots, float cut_threshold, 
 // The extra scratch of stream `post` (the DevBuf<double> members of ffl_ctx under "extra scratch"): what a context gains with
 // the first four-component, weighted, ffl_cell_stats or ffl_motion_fit call, in doubles for FFL_MAXB items.  The ffl_*_extra_bytes entry points
 // report a row, post_scratch allocates it.
-enum { SCR_AXES = 0, SCR_WEIGHTS, SCR_CELLS, SCR_MOTION };
+enum { SCR_AXES = 0, SCR_WEIGHTS, SCR_CELLS, SCR_MOTION, SCR_REDETECT };
 struct PostScratchRow {
-    size_t (*doubles)(int w, int h);
+    size_t (*doubles)(int w, int h, int max_batch);   // max_batch: read by the rows that are not sized for FFL_MAXB items
     const char *name;               // in the message of a failed allocation
     DevBuf<double> ffl_ctx::*buf;
 };
 static const PostScratchRow kPostScratch[] = {
-    {[](int w, int h) { return (size_t)FFL_NAXES * (size_t)ffl_radial_blocks(w, h) * FFL_MAXB; }, "four-component",
+    {[](int w, int h, int) { return (size_t)FFL_NAXES * (size_t)ffl_radial_blocks(w, h) * FFL_MAXB; }, "four-component",
      &ffl_ctx::d_apsum},
     // one buffer for whichever of the two runs: pass 2's FFL_NAXES + 1 partials per workgroup of the radial grid, or pass 1's SW
     // per workgroup of its grid
-    {[](int w, int h) {
+    {[](int w, int h, int) {
          const size_t p2 = (size_t)(FFL_NAXES + 1) * (size_t)ffl_radial_blocks(w, h), p1 = (size_t)ffl_pass1_blocks(w, h);
          return (p2 > p1 ? p2 : p1) * FFL_MAXB;
      }, "weighted", &ffl_ctx::d_wpsum},
     // the row sums of rule G5, whatever the size and the grid
-    {[](int, int) { return (size_t)2 * FFL_MAX_CELLS * FFL_MAXB; }, "cell-row", &ffl_ctx::d_cellrow},
+    {[](int, int, int) { return (size_t)2 * FFL_MAX_CELLS * FFL_MAXB; }, "cell-row", &ffl_ctx::d_cellrow},
     // the twelve sums of rule C4 per workgroup of the radial grid
-    {[](int w, int h) { return (size_t)FFL_MOTION_NSUMS * (size_t)ffl_radial_blocks(w, h) * FFL_MAXB; }, "motion-fit",
+    {[](int w, int h, int) { return (size_t)FFL_MOTION_NSUMS * (size_t)ffl_radial_blocks(w, h) * FFL_MAXB; }, "motion-fit",
      &ffl_ctx::d_mpsum},
+    // the tile keys, the pick and the re-walked keys of max_batch x FFL_MAX_TRACKS searches (64-bit words, held as doubles' bytes)
+    {[](int w, int h, int mb) { return ffl_redetect_words(w, h) * (size_t)mb * FFL_TRACK_MAX_T; }, "re-detection",
+     &ffl_ctx::d_rdscr},
 };
 
 static int cell_grid_check(ffl_ctx *c, const char *fn, int width, int height, int cells, int *cell_w, int *cell_h);
 
 // cells: the grid of the SCR_CELLS row, whose size check is rule G1's
-static int post_scratch_bytes(const char *fn, int row, int width, int height, int cells, size_t *bytes) {
+static int post_scratch_bytes(const char *fn, int row, int width, int height, int cells, size_t *bytes, int max_batch = FFL_MAXB) {
     if (!bytes) return set_err(nullptr, FFL_ERR_INVALID, "%s: bytes is NULL", fn);
     if (row == SCR_CELLS) {
         if (int rc = cell_grid_check(nullptr, fn, width, height, cells, nullptr, nullptr)) return rc;
     } else if (!frame_size_ok(width, height))
         return set_err(nullptr, FFL_ERR_INVALID, "%s: " FFL_FRAME_SIZE_RULE, fn, width, height);
-    *bytes = sizeof(double) * kPostScratch[row].doubles(width, height);
+    *bytes = sizeof(double) * kPostScratch[row].doubles(width, height, max_batch);
     return FFL_OK;
 }
 
@@ -2182,13 +2187,20 @@ int ffl_motion_extra_bytes(int width, int height, size_t *bytes) {
     return post_scratch_bytes("ffl_motion_extra_bytes", SCR_MOTION, width, height, 0, bytes);
 }
 
+int ffl_redetect_extra_bytes(int width, int height, int max_batch, size_t *bytes) {
+    if (max_batch < 1 || max_batch > FFL_MAX_BATCH)
+        return set_err(nullptr, FFL_ERR_INVALID, "ffl_redetect_extra_bytes: max_batch = %d outside 1..%d (FFL_MAX_BATCH)", max_batch,
+                       (int)FFL_MAX_BATCH);
+    return post_scratch_bytes("ffl_redetect_extra_bytes", SCR_REDETECT, width, height, 0, bytes, max_batch);
+}
+
 // The first call that needs a row allocates it (the caller holds post_mu and the context lock).  The axes row comes with
 // ffl_radial_axes' mapped pinned records.
 static int post_scratch(ffl_ctx *c, const char *fn, int row) {
     const PostScratchRow &r = kPostScratch[row];
     DevBuf<double> &buf = c->*r.buf;
     if (buf && (row != SCR_AXES || c->h_axes)) return FFL_OK;
-    const size_t doubles = r.doubles(c->w, c->h);
+    const size_t doubles = r.doubles(c->w, c->h, c->max_batch);
     hipError_t e = buf ? hipSuccess : buf.alloc(doubles);
     if (e != hipSuccess) buf.release();  // nothing was allocated
     if (e == hipSuccess && row == SCR_AXES && !c->h_axes) {
@@ -3581,6 +3593,128 @@ int ffl_track_match(ffl_ctx *c, int n, const int *fslots, int n_tracks, const ff
                            (const unsigned char *)templates_dev, (char *)centres_dev, (long long)cstride, write_back,
                            (MatchRecord *)out_dev, c->s_post);
     // the caller may read the records and the corrected centres on `stream` straight after the call
+    return post_end_frames(c, cst, 0, nullptr, n, fslots, nullptr);
+}
+
+// ---- whole-frame template re-detection -------------------------------------------------
+static_assert((int)FFL_MAX_REDETECT_EXCLUDE == FFL_REDETECT_MAX_EXCLUDE && (int)FFL_REDETECT_SKIPPED == RDT_SKIPPED &&
+              (FFL_REDETECT_SKIPPED & (FFL_MATCH_FLAT | FFL_MATCH_POOR | FFL_MATCH_AMBIGUOUS)) == 0 &&
+              2 * FFL_REDETECT_MAX_EXCLUDE + 1 <= 64 * (RDT_EXCL_NX - 1) + 1 && 2 * FFL_REDETECT_MAX_EXCLUDE + 1 <= 16 * (RDT_EXCL_NY - 1) + 1,
+              "ffl.h and ffl_kernels.h agree; the exclusion square fits the re-walked tiles");
+
+int ffl_redetect_default_params(ffl_redetect_params *out) {
+    if (!out) return FFL_ERR_INVALID;
+    ffl_match_params m;
+    ffl_match_default_params(&m);   // the match defaults with exclude = p, the whole frame, triggered by POOR: not tuned on footage
+    *out = ffl_redetect_params{m.p, m.mode, m.p, 0, FFL_MATCH_POOR, 0, m.min_var, m.max_mse, m.ratio};
+    return FFL_OK;
+}
+
+// The accepted parameters of appendix L.  The comparisons are written so that a NaN fails them.
+static int redetect_params_check(ffl_ctx *c, const char *fn, const ffl_redetect_params *p) {
+    if (!p) return set_err(c, FFL_ERR_INVALID, "%s: NULL parameters", fn);
+    if (p->p < 1 || p->p > FFL_MAX_MATCH_P)
+        return set_err(c, FFL_ERR_INVALID, "%s: p = %d outside 1..%d (FFL_MAX_MATCH_P; the template is (2p+1)^2)", fn, p->p, (int)FFL_MAX_MATCH_P);
+    if (p->mode != FFL_MATCH_SSD && p->mode != FFL_MATCH_ZSSD)
+        return set_err(c, FFL_ERR_INVALID, "%s: mode = %d is neither 0 (FFL_MATCH_SSD) nor 1 (FFL_MATCH_ZSSD)", fn, p->mode);
+    if (p->exclude < 1 || p->exclude > FFL_MAX_REDETECT_EXCLUDE)
+        return set_err(c, FFL_ERR_INVALID, "%s: exclude = %d outside 1..%d (FFL_MAX_REDETECT_EXCLUDE; rule L5's square)", fn, p->exclude,
+                       (int)FFL_MAX_REDETECT_EXCLUDE);
+    if (p->reach < 0 || p->reach > 32768)
+        return set_err(c, FFL_ERR_INVALID, "%s: reach = %d outside 0 (the whole frame) or 1..32768 (rule L2)", fn, p->reach);
+    if (!(p->min_var >= 0.0 && p->min_var < HUGE_VAL)) return set_err(c, FFL_ERR_INVALID, "%s: min_var = %g outside 0 <= min_var (finite)", fn, p->min_var);
+    if (!(p->max_mse >= 0.0 && p->max_mse <= 65025.0))
+        return set_err(c, FFL_ERR_INVALID, "%s: max_mse = %g outside 0..65025 (finite)", fn, p->max_mse);
+    if (!(p->ratio > 0.0 && p->ratio <= 1.0)) return set_err(c, FFL_ERR_INVALID, "%s: ratio = %g outside 0 < ratio <= 1 (finite)", fn, p->ratio);
+    return FFL_OK;
+}
+
+int ffl_redetect_params_check(const ffl_redetect_params *p) { return redetect_params_check(nullptr, "ffl_redetect_params_check", p); }
+
+// n x n_tracks searches by four launches on stream `post`: ffl_track_match's protocol, with the trigger words as a fourth
+// caller region and the tile keys in the SCR_REDETECT scratch.
+int ffl_track_redetect(ffl_ctx *c, int n, const int *fslots, int n_tracks, const ffl_redetect_params *p, const void *templates_dev,
+                       void *centres_dev, ptrdiff_t cstride, const void *trigger_dev, ptrdiff_t tstride, int write_back,
+                       ffl_match_record *out_dev, uint64_t stream) {
+    static const char *fn = "ffl_track_redetect";
+    if (!c) return FFL_ERR_INVALID;
+    std::unique_lock<std::mutex> pl(c->post_mu);  // stream `post` and d_rdscr
+    CtxLock lk(c->mu);
+    if (n < 1 || n > c->max_batch)
+        return set_err(c, FFL_ERR_INVALID, "%s: n = %d items outside 1..%d (the context's max_batch)", fn, n, c->max_batch);
+    if (!fslots) return set_err(c, FFL_ERR_INVALID, "%s: NULL fslots", fn);
+    RedetectArgs a;
+    for (int i = 0; i < n; i++) {   // frame slots may repeat between items
+        const int fs = fslots[i];
+        if (fs < 0 || fs >= c->n_fslots) return set_err(c, FFL_ERR_INVALID, "%s: item %d: frame slot %d out of range", fn, i, fs);
+        if (!c->frame_valid[fs]) return set_err(c, FFL_ERR_STATE, "%s: item %d: frame slot %d was never uploaded", fn, i, fs);
+        a.fr.slot[i] = fs;
+    }
+    ffl_redetect_params prm;
+    ffl_redetect_default_params(&prm);
+    if (p) prm = *p;
+    if (int rc = redetect_params_check(c, fn, &prm)) return rc;
+    if (write_back != 0 && write_back != 1)
+        return set_err(c, FFL_ERR_INVALID, "%s: write_back = %d is neither 0 nor 1 (rule L8)", fn, write_back);
+    size_t tbytes, cbytes, obytes, gbytes = 0;
+    if (int rc = match_regions_check(c, fn, n, n_tracks, prm.p, templates_dev, centres_dev, cstride, out_dev, true, &tbytes, &cbytes, &obytes))
+        return rc;
+    if (trigger_dev) {
+        if ((uintptr_t)trigger_dev % 4) return set_err(c, FFL_ERR_INVALID, "%s: trigger_dev must be 4-byte aligned (rule L1)", fn);
+        const ptrdiff_t span = 48 * (ptrdiff_t)(n_tracks - 1) + 4;   // rule L1: track t's word at + 48 t
+        if (tstride % 4 || tstride < span || tstride > ((ptrdiff_t)1 << 40))
+            return set_err(c, FFL_ERR_INVALID, "%s: trigger stride %td: a multiple of 4 bytes, at least 48 * (n_tracks - 1) + 4 = %td (rule L1)",
+                           fn, tstride, span);
+        gbytes = (size_t)(n - 1) * (size_t)tstride + (size_t)span;
+        const struct { const char *what; uintptr_t a; size_t b; } r[3] = {
+            {"centres_dev", (uintptr_t)centres_dev, cbytes}, {"templates_dev", (uintptr_t)templates_dev, tbytes}, {"out_dev", (uintptr_t)out_dev, obytes}};
+        const uintptr_t g = (uintptr_t)trigger_dev;
+        for (int i = 0; i < 3; i++)
+            if (g < r[i].a + r[i].b && r[i].a < g + gbytes)
+                return set_err(c, FFL_ERR_INVALID, "%s: overlap: trigger_dev (%zu bytes) and %s (%zu bytes) share memory", fn, gbytes, r[i].what,
+                               r[i].b);
+    }
+    hipStream_t cst;
+    PostRegion reg[4] = {{"out_dev", out_dev, obytes, kHostMatch}, {"templates_dev", templates_dev, tbytes, kHostMatch},
+                         {"centres_dev", centres_dev, cbytes, kHostMatch}, {"trigger_dev", trigger_dev, gbytes, kHostMatch}};
+    if (int rc = post_begin(c, fn, stream, &cst, reg, trigger_dev ? 4 : 3, 0, nullptr)) return rc;
+    if (int rc = post_scratch(c, fn, SCR_REDETECT)) return rc;
+    {
+        WaitOnce wait_post(c->s_post);   // the frames: a run of slots shares one upload event
+        for (int i = 0; i < n; i++) HIPCHK(c, wait_post(c->ev_uploaded[fslots[i]].get()));
+    }
+    a.gray = c->d_gray;
+    a.N = c->N;
+    a.n_tracks = n_tracks;
+    a.w = c->w;
+    a.h = c->h;
+    a.p = prm.p;
+    a.mode = prm.mode;
+    a.exclude = prm.exclude;
+    a.reach = prm.reach;
+    a.mask = prm.trigger_mask;
+    a.write_back = write_back;
+    a.min_var = prm.min_var;
+    a.max_mse = prm.max_mse;
+    a.ratio = prm.ratio;
+    a.tmpl = (const unsigned char *)templates_dev;
+    a.cen = (char *)centres_dev;
+    a.cstride = (long long)cstride;
+    a.trig = (const char *)trigger_dev;
+    a.tstride = (long long)tstride;
+    a.scr = reinterpret_cast<unsigned long long *>((double *)c->d_rdscr);
+    a.sstride = (long long)ffl_redetect_words(c->w, c->h);
+    a.TX = ffl_redetect_tiles_x(c->w);
+    a.TY = ffl_redetect_tiles_y(c->h);
+    // L columns touch at most ceil(L / 64) + 1 tile columns wherever they start; rows alike with 16
+    const int side = 2 * prm.reach + 1, eside = 2 * prm.exclude + 1;
+    a.gx = prm.reach ? std::min(a.TX, (side + 63) / 64 + 1) : a.TX;
+    a.gy = prm.reach ? std::min(a.TY, (side + 15) / 16 + 1) : a.TY;
+    a.ex = std::min(RDT_EXCL_NX, (eside + 63) / 64 + 1);
+    a.ey = std::min(RDT_EXCL_NY, (eside + 15) / 16 + 1);
+    a.out = (MatchRecord *)out_dev;
+    ffl_launch_track_redetect(a, n, c->s_post);
+    // the caller may read the records and the re-detected centres on `stream` straight after the call
     return post_end_frames(c, cst, 0, nullptr, n, fslots, nullptr);
 }
 

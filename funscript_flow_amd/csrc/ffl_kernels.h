@@ -401,6 +401,39 @@ void ffl_launch_track_match(const unsigned char *gray, size_t N, const ExportTab
 void ffl_launch_track_template(const unsigned char *frame, int n_tracks, int w, int h, int p, const char *cen, unsigned char *tmpl,
                                hipStream_t st);
 
+// ---- whole-frame template re-detection (kernels_redetect.hip) ----------------------
+#define FFL_REDETECT_MAX_EXCLUDE 32  // = FFL_MAX_REDETECT_EXCLUDE of include/ffl.h
+#define RDT_SKIPPED 8                // = FFL_REDETECT_SKIPPED
+#define RDT_EXCL_NX 3                // a square of 2 * 32 + 1 columns touches at most 3 tile columns of 64
+#define RDT_EXCL_NY 6                // and at most 6 tile rows of 16
+// the candidate tiles of a w x h frame (64 x 16), and the 64-bit words of scratch one search takes: a key per tile of the
+// frame, the pick's two words, a key per re-walked tile
+static inline int ffl_redetect_tiles_x(int w) { return (w + 63) / 64; }
+static inline int ffl_redetect_tiles_y(int h) { return (h + 15) / 16; }
+static inline size_t ffl_redetect_words(int w, int h) {
+    return (size_t)ffl_redetect_tiles_x(w) * (size_t)ffl_redetect_tiles_y(h) + 2 + RDT_EXCL_NX * RDT_EXCL_NY;
+}
+struct RedetectArgs {   // one call's arguments, the same for its four launches
+    const unsigned char *gray;      // the frame slots, N bytes each; item i reads slot fr.slot[i]
+    size_t N;
+    ExportTab fr;
+    int n_tracks, w, h, p, mode, exclude, reach, mask, write_back;
+    double min_var, max_mse, ratio;
+    const unsigned char *tmpl;      // n_tracks templates of (2p+1)^2 bytes
+    char *cen;                      // the two doubles of (item i, track t) at cen + i * cstride + t * 48
+    long long cstride;
+    const char *trig;               // NULL, or the int32 of (i, t) at trig + i * tstride + t * 48 (rule L1)
+    long long tstride;
+    unsigned long long *scr;        // sstride words per search i * n_tracks + t
+    long long sstride;
+    int TX, TY;                     // ffl_redetect_tiles_x / _y of the frame
+    int gx, gy;                     // the sweep's grid per search: TX x TY, or what 2 * reach + 1 columns / rows can touch
+    int ex, ey;                     // the exclusion sweep's grid per search: what 2 * exclude + 1 columns / rows can touch
+    MatchRecord *out;
+};
+// the four launches of ffl_track_redetect for n items (k_redetect_sweep, k_redetect_pick, k_redetect_sweep masked, k_redetect_final)
+void ffl_launch_track_redetect(const RedetectArgs &a, int n, hipStream_t st);
+
 // ---- global-motion fit and compensation (kernels_post.hip) -----------------------
 #define FFL_MOTION_NSUMS 12          // = FFL_MOTION_N_SUMS of include/ffl.h; the order of rule C4
 enum { MOT_S = 0, MOT_SX, MOT_SY, MOT_SXX, MOT_SXY, MOT_SYY, MOT_SU, MOT_SUX, MOT_SUY, MOT_SV, MOT_SVX, MOT_SVY };

@@ -438,7 +438,7 @@ class PairEngine:
     def process_chunk(self, frames, pov_mode=False, cut_threshold=7.0, algo=None, farneback=OWN, flows_out=None, window=OWN,
                       post_out=None, axes=False, weights=None, center=None, cells=32, grid_out=None, consistency=None,
                       weights_out=None, weights_gate=None, compensate=None, motion_out=None, residual=None, texture=None,
-                      track=None, track_out=None, match_out=None):
+                      track=None, track_out=None, match_out=None, redetect_out=None):
         """One whole chunk on one GPU: returns (dots float64[n], records) with n = len(frames)-1.  `algo`, `farneback`,
         `window`: see pass1_pairs (default: the engine's own flow algorithm, parameters and window).  `flows_out`: a float32 device array of
         (n, H, W, 2) or (n, 2, H, W) that receives every pair's flow field (Context.export_flows, on torch's current stream)
@@ -509,11 +509,19 @@ class PairEngine:
         every centre read afterwards is a corrected one; `match_out` (a match_buffer, or a new one; match_records reads it)
         receives the n x T 48-byte match records of the first.  A rejected match (FLAT, POOR, AMBIGUOUS) leaves its centre
         alone: after a scene cut the template is stale, matches read POOR and the track is pure advection until the caller
-        re-captures (Context.track_template).  Without the key the chunk queues exactly the calls it queued before."""
+        re-captures (Context.track_template).  Without the key the chunk queues exactly the calls it queued before.
+        track["match"]["redetect"]: True, or a dict of "reach" (0: the whole frame), "exclude" and
+        "mask" (the trigger mask; default MATCH_POOR) -- p, mode and the thresholds are the match's; the defaults are not
+        tuned on footage.  Straight behind the batch's search about the state, Context.track_redetect is queued with one
+        item on the same frame about the state, triggered by the status words of that search, with write-back: where the
+        local search failed the whole frame is searched, and the next batch starts from a re-detected state (the batch
+        already advanced keeps its records).  `redetect_out` (a match_buffer of n x T records) receives that call's T records
+        at the index of the batch's last pair; its other entries are not written.  Whole pixels, no scale or rotation, no
+        template update; after a scene cut a global search reads POOR as well.  Without the key nothing of this is queued."""
         ctx, B = self.ctx, self.B
         n = len(frames) - 1
         trk = _chunk_track(ctx, n, center, track, track_out, weights, weights_out, weights_gate, ctx.flow_slots, cut_threshold,
-                           match_out)
+                           match_out, redetect_out=redetect_out)
         if trk is not None and trk.roi is not None:   # the keywords are the track's
             weights_out = weights_gate = None
         if compensate is not None and isinstance(weights, str) and weights == "consistency":
@@ -823,7 +831,25 @@ def chunk_center(center):
 
 
 TRACK_KEYS = ("state", "start", "home", "radius", "on_cut", "roi", "roi_soft", "match")
-MATCH_KEYS = _capi.MATCH_FIELDS + ("templates", "capture", "match_out")
+MATCH_KEYS = _capi.MATCH_FIELDS + ("templates", "capture", "match_out", "redetect")
+REDETECT_KEYS = ("reach", "exclude", "mask")
+
+
+def _redetect_choice(match, r):
+    """the RedetectParams of track["match"]["redetect"] = r (True or a dict of REDETECT_KEYS) next to the MatchParams `match`,
+    whose p, mode and thresholds it takes; exclude defaults to p"""
+    if r is True:
+        r = {}
+    unknown = [k for k in r if k not in REDETECT_KEYS] if isinstance(r, dict) else ["redetect"]
+    if unknown:
+        raise ValueError(f"track['match']['redetect']: True or a dict of {REDETECT_KEYS}; unknown key {unknown[0]!r}")
+    over = {"exclude": match.p if r.get("exclude") is None else r["exclude"]}
+    if r.get("reach") is not None:
+        over["reach"] = r["reach"]
+    if r.get("mask") is not None:
+        over["trigger_mask"] = r["mask"]
+    return _capi.redetect_choice({"p": match.p, "mode": match.mode, "min_var": match.min_var, "max_mse": match.max_mse,
+                                  "ratio": match.ratio, **over})
 
 
 class _ChunkTrack:
@@ -839,9 +865,12 @@ class _ChunkTrack:
     advance; behind() then queues, between track_advance and roi_weights, Context.track_match on the f0 slots about the batch's
     records and Context.track_match with one item on f1[last] about the state, both with write-back: the window calls and the
     ROI maps read corrected centres, and the next batch starts from a corrected state.  Without the key nothing of this is
-    queued."""
+    queued.
+    With track["match"]["redetect"] behind() queues, straight after the search about the state,
+    Context.track_redetect with one item on the same frame about the state, triggered by the status words of that search, with
+    write-back; its T records go to redetect_out (or a new buffer) at the index of the batch's last pair."""
 
-    def __init__(self, ctx, n, track, track_out, maps_out, gate, ring, cut_threshold, match_out=None):
+    def __init__(self, ctx, n, track, track_out, maps_out, gate, ring, cut_threshold, match_out=None, redetect_out=None):
         if not isinstance(track, dict) or not (("state" in track) ^ ("start" in track)):
             raise ValueError("center='track' needs track= {'state': a track_state tensor} or {'start': (x, y) or (T, 2)}, one of "
                              "the two")
@@ -859,6 +888,11 @@ class _ChunkTrack:
             self.match = _capi.match_choice({k: m[k] for k in _capi.MATCH_FIELDS if m.get(k) is not None})
         elif match_out is not None:
             raise ValueError("match_out= needs track['match'] with center='track'")
+        self.redetect, r = None, m.get("redetect") if isinstance(m, dict) else None
+        if r is not None and r is not False:
+            self.redetect = _redetect_choice(self.match, r)
+        elif redetect_out is not None:
+            raise ValueError("redetect_out= needs track['match']['redetect'] with center='track'")
         if "state" in track:
             if "home" in track:
                 raise ValueError("track=: 'home' goes with 'start' (a state carries its own home position)")
@@ -901,6 +935,11 @@ class _ChunkTrack:
             if nbytes < n * self.item:
                 raise ValueError(f"match_out holds {nbytes} bytes, the chunk's {n} x {self.T} records need {n * self.item}")
             self.state_match = match_buffer(ctx, 1, self.T)   # the records of the latest search about the state
+        if self.redetect is not None:
+            self.redetect_out = match_buffer(ctx, max(n, 1), self.T) if redetect_out is None else redetect_out   # stays referenced
+            self.rbase, nbytes = _capi._device_span(self.redetect_out)
+            if nbytes < n * self.item:
+                raise ValueError(f"redetect_out holds {nbytes} bytes, the chunk's {n} x {self.T} records need {n * self.item}")
 
     def with_frames(self, ls, js, f0, f1):
         self.frames = (list(f0), list(f1))
@@ -921,11 +960,16 @@ class _ChunkTrack:
             self.ctx.track_match(f0, self.templates, (recs, self.item), out, self.match, self.T, True, self.stream)
             self.ctx.track_match([f1[-1]], self.templates, (self.state, self.item), self.state_match, self.match, self.T, True,
                                  self.stream)
+            if self.redetect is not None:
+                out = _capi._DeviceSpan(self.rbase + ls[-1] * self.item, self.item)
+                self.ctx.track_redetect([f1[-1]], self.templates, (self.state, self.item), out, self.redetect, self.T,
+                                        self.state_match, True, self.stream)
         if self.roi is not None:
             self.ctx.roi_weights(len(ls), (recs, self.item), self.maps[ls[0]:ls[-1] + 1], self.roi, self.gate, self.stream)
 
 
-def _chunk_track(ctx, n, center, track, track_out, weights, maps_out, gate, ring, cut_threshold, match_out=None, frames=True):
+def _chunk_track(ctx, n, center, track, track_out, weights, maps_out, gate, ring, cut_threshold, match_out=None, frames=True,
+                 redetect_out=None):
     """None unless center == "track" (track=, track_out= and match_out= are then refused), else the chunk's _ChunkTrack;
     weights= of any form is refused next to it, and track["match"] by a chunk without frames (frames=False)"""
     if center != "track":
@@ -933,6 +977,8 @@ def _chunk_track(ctx, n, center, track, track_out, weights, maps_out, gate, ring
             raise ValueError("track= and track_out= need center='track'")
         if match_out is not None:
             raise ValueError("match_out= needs center='track' with track['match']")
+        if redetect_out is not None:
+            raise ValueError("redetect_out= needs center='track' with track['match']['redetect']")
         return None
     if not frames and isinstance(track, dict) and track.get("match") is not None:
         raise ValueError("process_flows: track['match'] needs the frames, which a chunk of caller flows does not have; "
@@ -940,7 +986,9 @@ def _chunk_track(ctx, n, center, track, track_out, weights, maps_out, gate, ring
     if weights is not None:
         raise ValueError("center='track' together with weights= (a map or a mode) is not supported: the region's own map is "
                          "track={'roi': (ax, ay)}, and weights_gate= is its static gate")
-    return _ChunkTrack(ctx, n, track, track_out, maps_out, gate, ring, cut_threshold, match_out)
+    if isinstance(track, dict) and "redetect" in track:
+        raise ValueError("track=: 'redetect' is a key of track['match'] (it searches for the match's templates)")
+    return _ChunkTrack(ctx, n, track, track_out, maps_out, gate, ring, cut_threshold, match_out, redetect_out)
 
 
 def _chain(*hooks):

@@ -59,6 +59,12 @@
  *                           within +-s pixels, verdicts FLAT / POOR / AMBIGUOUS, the centre overwritten in place so that
  *                           every call that reads centres from device memory reads corrected ones (DESIGN.md section 24,
  *                           appendix N)
+ *   ffl_track_redetect      replaces nothing either: ffl_track_match looks only +-s <= 16 pixels about the centre, and a
+ *                           track further from its subject than that stays lost.  This searches the WHOLE frame (or a wide
+ *                           reach about the centre) for the template, only where a trigger word in device memory -- the
+ *                           status of a match record -- says the local search failed, and writes the centre back on the
+ *                           device.  Whole pixels, no scale or rotation, no template update (DESIGN.md section 25,
+ *                           appendix L)
  *   ffl_motion_fit, ffl_motion_subtract  replace nothing: the reference cancels global motion only by the quadrant weights
  *                           of radial_motion_weighted ("Cancel out global motion by balancing the averages", FF:779-783), which
  *                           cancel a pan only about the image centre.  These fit a per-pair camera model (translation, rigid,
@@ -1002,6 +1008,66 @@ int ffl_track_template(ffl_ctx *ctx, int fslot, int n_tracks, const void *centre
 int ffl_track_match(ffl_ctx *ctx, int n, const int *fslots, int n_tracks, const ffl_match_params *p, const void *templates_dev,
                     void *centres_dev, ptrdiff_t centre_stride_bytes, int write_back, ffl_match_record *out_dev,
                     uint64_t stream);
+
+/* ---- Whole-frame template re-detection for tracked regions ----
+ * ffl_track_match searches +-s <= 16 pixels about the advected centre.  Once the subject is further away than that (an
+ * occlusion, a fast move the flow under-reads, a few POOR batches of pure advection) every local search reads POOR and the
+ * track is gone.  ffl_track_redetect searches a whole frame, or a wide reach about the centre, for a track's template, decides
+ * on the device and writes the centre back there; a trigger word per search, in device memory, says whether it runs at all,
+ * so that the call can be queued behind every ffl_track_match without the host ever reading a status.  The rules are the
+ * project's own and integer-exact; they reuse N1 to N3 and N6's thresholds.  I, Tm and N = (2p+1)^2 are appendix N's.
+ *   L1  anchor and trigger: the centre of (item i, track t) is N1's: two doubles at centres_dev + i * centre_stride_bytes +
+ *       t * 48, through Q1's selects and Q2's rounding to (ix, iy).  With a non-NULL trigger_dev the int32 word at trigger_dev
+ *       + i * trigger_stride_bytes + t * 48 is read, and the search runs iff (word & trigger_mask) != 0; with NULL it always
+ *       runs.  The `status` field of an ffl_match_record array (byte 40 of a 48-byte record) is the intended trigger.  A search
+ *       that does not run writes the record of L7 with status FFL_REDETECT_SKIPPED, reads no frame byte and stores no centre.
+ *   L2  candidates: all integer (cx, cy) with 0 <= cx < w, 0 <= cy < h and, when reach > 0, |cx - ix| <= reach and
+ *       |cy - iy| <= reach.  reach = 0: the whole frame.  The set is never empty: the anchor lies in the frame.
+ *   L3  samples and cost: N2 about the candidate, d = I[clamp(cy+j-p, 0, h-1)][clamp(cx+i-p, 0, w-1)] - Tm[j][i] (the frame
+ *       edge-padded by p; clamped, never clipped); the cost is N3's: S1, S2 in int32, SSD N * S2 or ZSSD N * S2 - S1^2 in int64.
+ *   L4  best: the lexicographic minimum of (cost, cy, cx): on exact ties the first candidate in row-major order wins.
+ *   L5  runner-up: second = the minimum cost over candidates with max(|cx - bx|, |cy - by|) > exclude; -1 if there are none.
+ *   L6  verdict, float64, one rounding per written operation, left to right: FLAT and POOR exactly N6's; AMBIGUOUS if
+ *       second >= 0 && (double)cost >= ratio * (double)second.  The >= is deliberate and differs from N6: two exact copies of
+ *       the template (cost 0 against second 0) must not be accepted silently by a global search.  Accepted iff status == 0.
+ *   L7  record (i, t), an ffl_match_record at index i * n_tracks + t: x, y = ((double)bx, (double)by) through Q1's selects
+ *       when accepted, else the sanitised centre; dx = bx - ix, dy = by - iy, also when rejected; cost, second, status;
+ *       pad = 0.  Skipped (L1): x, y the sanitised centre, dx = dy = 0, cost = second = -1, status 8.
+ *   L8  write-back: as N8.  With write_back = 1 an accepted search stores x, y into the two doubles it read; anything else
+ *       stores nothing.
+ *   L9  independence: record (i, t) depends on item i's frame, track t's template, that one centre and that one trigger
+ *       word only.
+ * Accepted: p 1..FFL_MAX_MATCH_P, mode FFL_MATCH_SSD or FFL_MATCH_ZSSD, exclude 1..FFL_MAX_REDETECT_EXCLUDE, reach 0 or
+ * 1..32768, N6's ranges for min_var, max_mse and ratio.  The defaults are the match defaults (8, ZSSD, 25, 400, 0.8) with
+ * exclude = p = 8, reach 0 and trigger_mask = FFL_MATCH_POOR: the project's own choice, NOT tuned on footage.
+ * What this is NOT: whole pixels only; no scale or rotation; no template update.  After a scene cut the template is stale
+ * and a global search reads POOR as well: re-capture (ffl_track_template) stays the caller's. */
+enum { FFL_MAX_REDETECT_EXCLUDE = 32, FFL_REDETECT_SKIPPED = 8 };
+typedef struct ffl_redetect_params {
+    int p, mode, exclude, reach, trigger_mask, reserved;   /* reserved: not read */
+    double min_var, max_mse, ratio;
+} ffl_redetect_params;
+int ffl_redetect_default_params(ffl_redetect_params *out);
+/* Pure host check: no device or context needed.  FFL_ERR_INVALID with the rule in ffl_last_error(NULL). */
+int ffl_redetect_params_check(const ffl_redetect_params *p);
+/* The device memory a context of this size gains with its first ffl_track_redetect: one 64-bit word per 64 x 16 candidate
+ * tile of the frame plus 20, for max_batch items x FFL_MAX_TRACKS tracks.  Needs no device.  ffl_estimate_bytes does not
+ * count it. */
+int ffl_redetect_extra_bytes(int width, int height, int max_batch, size_t *bytes);
+
+/* Item i searches frame slot fslots[i] for each of the n_tracks templates (rules L1 to L9); p NULL: the defaults.
+ * trigger_dev NULL: every search runs (trigger_stride_bytes is then not read).  Refused before any device work, each with its
+ * rule in the message: everything ffl_track_match refuses; any rule of ffl_redetect_params_check; a trigger_dev that is not
+ * 4-byte aligned; a trigger stride that is no multiple of 4 or below 48 * (n_tracks - 1) + 4; trigger words ((n - 1) * stride
+ * + 48 * (n_tracks - 1) + 4 bytes) that are not device memory of the context's device inside one allocation, or that overlap
+ * the centres, the templates or out_dev.  ffl_track_match's protocol: four launches (k_redetect_sweep over the candidate
+ * tiles, k_redetect_pick, k_redetect_sweep over the tiles about the best with its neighbourhood masked, k_redetect_final),
+ * queued on the library's stream behind the work queued on `stream` and the uploads that filled the frame slots; `stream`
+ * then waits for them; the call counts as a reader of the frame slots; never captured; the host does not wait.  Scratch:
+ * ffl_redetect_extra_bytes, allocated by the first call and freed by ffl_destroy. */
+int ffl_track_redetect(ffl_ctx *ctx, int n, const int *fslots, int n_tracks, const ffl_redetect_params *p,
+                       const void *templates_dev, void *centres_dev, ptrdiff_t centre_stride_bytes, const void *trigger_dev,
+                       ptrdiff_t trigger_stride_bytes, int write_back, ffl_match_record *out_dev, uint64_t stream);
 
 /* ---- Global-motion fit and compensation ----
  * A per-pair parametric camera model, fitted robustly to a resident flow field and subtracted from it, so that what pass 1
