@@ -8,13 +8,19 @@ pass 1 (|div| argmax + mean magnitude), the +-6 centre smoothing on the host and
 weighted mean).  Batches are software-pipelined (batch s+1 is queued before batch s is finalised)
 so the device never waits for the host.
 
-After the timed region the results of the timed steps are compared with golden scalars the CPU oracle
-produced in the build container (tests/golden/bench_*.json: argmax index + value bit-exact, reductions to
-1e-4, three flow fields by crc32) -> "checked"; then, on rank 0 at N = 1, three short extra passes add
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline figure needs: it sets up,
+warms up, times the K steps, writes --dump-outputs and prints the line ("checked" is null, the roofline of
+the dominant kernel comes from the HIP events of the timed steps themselves).  Everything else is behind
+--full.  With --full the results of the timed steps are compared, after the timed region, with golden scalars
+the CPU oracle produced in the build container (tests/golden/bench_*.json: argmax index + value bit-exact,
+reductions to 1e-4, three flow fields by crc32) -> "checked"; then, on rank 0 at N = 1, extra passes add
   "kernel_classes"   HIP events around every kernel class (per-class ms, algorithmic bytes, roofline fraction)
   "pcie_inclusive"   host numpy frames (gray and BGR) -> scalars, uploads included (never `value`)
   "small_image"      the reference's own operating point, 256x256 pairs in large batches (FF:1057)
-and "cpu_baseline" times the C oracle on the host cores.
+  "large_image"      3840x2160 and one 2880x2880 eye, resident
+and "cpu_baseline" times the C oracle on the host cores (before the first GPU call).  --no-extras and
+--no-cpu-baseline leave those parts out of a --full run.  The timed steps are the same with and without --full.
+(--one-clip is a mode of its own: it times one chunk and always makes its check.)
 
 N > 1: one process per GPU (torchrun), every rank streams its own clip (weak scaling, pairs are
 independent); the only exchange is the barrier/MAX around the timed region and a host (gloo) gather
@@ -565,8 +571,13 @@ def main():
     ap.add_argument("--batch", type=int, default=32,
                     help="pairs per ffl_flow_pairs call (a step); 32 fills the device at every pyramid level: "
                          "1080p 4450 / 4700 / 5030 / 4880 pairs/s at B = 8 / 16 / 32 / 64")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the kernel_classes / pcie_inclusive / small_image passes")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: compare their results with the oracle goldens (`checked`), time the CPU "
+                         "baseline and run the kernel_classes / pcie_inclusive / small_image / large_image passes; off by "
+                         "default, a plain run only sets up, warms up, times and prints")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full without the kernel_classes / pcie_inclusive / small_image / large_image passes")
     ap.add_argument("--cpu-pairs", type=int, default=0, help="pairs per worker process of the CPU sample (default 2)")
     ap.add_argument("--cpu-workers", type=int, default=0, help="widest pool of the cpu_baseline sweep (default os.cpu_count())")
     ap.add_argument("--independent", action="store_true", help="2B frames per batch (no frame sharing)")
@@ -630,7 +641,7 @@ def main():
     from funscript_flow_amd.synth import sine_translate_frames
     frames0 = None
     cpu_base = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         if any("rocprof" in os.environ.get(k, "").lower() for k in ("LD_PRELOAD", "ROCP_TOOL_LIBRARIES", "HSA_TOOLS_LIB")):
             cpu_base = {"value": None, "skipped": "running under rocprofv3: the GPU is already initialised, no fork"}
         else:
@@ -737,7 +748,10 @@ def main():
         d = np.diff(np.array(runner.trace[-args.steps:])) * 1e3
         print("step ms:", " ".join(f"{v:.2f}" for v in d), file=sys.stderr)
     plain = not args.independent and args.zoom == 0.0
-    checked, check_detail = verify(runner, frames, W, H, B, seed, ctx) if plain else (None, "non-default clip")
+    if not args.full:
+        checked, check_detail = None, "not compared with the oracle goldens (--full compares)"
+    else:
+        checked, check_detail = verify(runner, frames, W, H, B, seed, ctx) if plain else (None, "non-default clip")
     dumped = last_step_outputs(runner, ctx, W, H) if args.dump_outputs and rank == 0 else None
     results = runner.results
     graphs = ctx.graph_stats()
@@ -795,7 +809,7 @@ def main():
             "whole_path": {"alg_bytes_per_pair": sum(alg.values()) / B,
                            "achieved_GBps": sum(alg.values()) / B * (pairs / world) / dt / 1e9},
         }
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             # (1) every kernel class under HIP events, in a pass of its own (the events cost ~0.2 ms per step), one batch
             # at a time (depth 0) so that pass 2 is not co-scheduled with the next batch's kernels: every class alone
             ksteps = max(3, min(args.steps, 6))

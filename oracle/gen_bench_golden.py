@@ -4,7 +4,7 @@ Golden scalars for the EXACT workload bench.py times (and the `-m gpu` tests of 
 one step = B consecutive pairs of the synthetic sine-translate stream (funscript_flow_amd.synth, seed 1 at
 N = 1), pass 1 per pair, the +-6 centre smoothing inside the batch, pass 2 -- all computed here by the CPU
 oracle (C restatement of cv2.calcOpticalFlowFarneback FF:878-879 + numpy restatement of FF:748-785,
-FF:1203-1214).  bench.py compares its device results with this file after the timed region and reports
+FF:1203-1214).  bench.py --full compares its device results with this file after the timed region and reports
 `"checked": true`; the oracle itself never runs on the GPU box for that.
 
     python oracle/gen_bench_golden.py [W H B [seed]]      default: every golden the repo commits

@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT"
 TAG=${1:-cap}
 O=gpurun_out
-B="python bench.py --no-cpu-baseline --no-extras"
+B="python bench.py --full --no-cpu-baseline --no-extras"
 $B --width 3840 --height 2160 --steps 8 > $O/${TAG}_bench_4k.json 2>/dev/null &&
 $B --width 2880 --height 2880 --steps 8 > $O/${TAG}_bench_2880_eye.json 2>/dev/null &&
 $B --lanes 2 > $O/${TAG}_bench_lanes2.json 2>/dev/null &&

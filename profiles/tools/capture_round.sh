@@ -32,7 +32,7 @@ for WL in "3840 2160 32" "2880 2880 32" "256 256 256"; do
 done
 cp profiles/traffic.json $O/${TAG}_traffic.json
 # the bench line last, so that it already carries this capture's traffic (profiles/traffic.json, same kernel signature)
-python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 python profiles/summarize_trace.py $O/${TAG}_stats/s_kernel_trace.csv > $O/${TAG}_kernel_trace_by_grid.txt
 cp $O/${TAG}_stats/s_kernel_stats.csv $O/${TAG}_kernel_stats.csv
 (python profiles/summarize_pmc.py $O/${TAG}_F/f_counter_collection.csv k_; python profiles/summarize_pmc.py $O/${TAG}_W/w_counter_collection.csv k_) > $O/${TAG}_pmc_fetch_write.txt

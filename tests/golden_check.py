@@ -1,5 +1,5 @@
 """Compare one finished batch of the HIP path with committed golden scalars (tests/golden/bench_*.json, made
-in the build container by oracle/gen_bench_golden.py).  Used by bench.py after its timed region and by the
+in the build container by oracle/gen_bench_golden.py).  Used by bench.py --full after its timed region and by the
 `-m gpu` tests of the shipped configuration; this module only reads numbers -- it never runs a CPU version
 of the path.  Test infrastructure: it lives beside the goldens it reads, outside the product package
 (bench.py puts tests/ on its import path for it).

@@ -256,7 +256,7 @@ def test_bench_launches_its_own_ranks_from_a_plain_shell():
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"]
     r = subprocess.run(cmd + ["--rehearse-gloo"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -408,12 +408,13 @@ def test_largest_baseline_frame_5760x2880_whole():
 
 
 def test_bench_prints_exactly_one_json_line():
-    """the driver's contract: stdout of bench.py is ONE JSON line (native libraries' chatter goes to stderr)"""
+    """the driver's contract: stdout of bench.py is ONE JSON line (native libraries' chatter goes to stderr); `checked`
+    is the comparison with the oracle goldens that --full makes"""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-extras",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-extras",
                         "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.split("\n") if l.strip()]
@@ -425,6 +426,39 @@ def test_bench_prints_exactly_one_json_line():
     assert d["steps"] == 2 and d["n_gpus"] == 1 and d["checked"] is True
 
 
+def test_bench_plain_run_times_and_dumps_only(tmp_path):
+    """Without --full the benchmark sets up, warms up, times, dumps and prints, nothing else: the line has the headline
+    fields and no result of a check, a CPU baseline or an extra pass.  What it dumps is still the oracle golden's
+    workload (records bit for bit), and the time the whole process spends outside its steps (start to exit, less
+    (steps + warmup) x ms_per_step) stays under the 30 s a plain run may take there."""
+    import json
+    import time
+    W, H, B, steps, warmup = 256, 256, 64, 2, 1
+    d = tmp_path / "plain"
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                        "--width", str(W), "--height", str(H), "--batch", str(B), "--dump-outputs", str(d)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.split("\n") if l.strip()]
+    assert len(lines) == 1, r.stdout[:2000]
+    line = json.loads(lines[0])
+    assert line["metric"] == f"{W}x{H} frame-pairs/sec" and line["unit"] == "pairs/s" and line["dtype"] == "f32"
+    assert line["higher_is_better"] is True and line["steps"] == steps and line["warmup"] == warmup
+    assert line["ms_per_step"] > 0 and abs(line["value"] - B / (line["ms_per_step"] * 1e-3)) <= 1e-9 * line["value"]
+    assert line["checked"] is None and "--full" in line["check_detail"]
+    for k in ("cpu_baseline", "kernel_classes", "pcie_inclusive", "small_image", "large_image"):
+        assert k not in line, k
+    outside = wall - (steps + warmup) * line["ms_per_step"] * 1e-3
+    print(f"plain run: {wall:.2f} s wall, {outside:.2f} s outside its steps")
+    assert outside <= 30.0, outside
+    a = {p.stem: np.load(p) for p in d.iterdir()}
+    gold = golden_check.load_golden(W, H, B, 1)
+    assert a["argmax_x"].tolist() == gold["x"] and a["argmax_y"].tolist() == gold["y"]
+    assert a["max_divergence"].view(np.uint32).tolist() == gold["val_bits"] and a["cut"].astype(bool).tolist() == gold["cut"]
+
+
 def test_bench_dump_outputs_repeat_and_match_the_golden(tmp_path):
     """--dump-outputs: two runs with the same arguments write the same arrays (bit for bit), --steps sets the number of
     timed steps, and the dumped records / scalars of the last step are those of the oracle golden of that workload."""
@@ -434,7 +468,7 @@ def test_bench_dump_outputs_repeat_and_match_the_golden(tmp_path):
     for run, steps in enumerate((2, 3)):
         d = tmp_path / f"run{run}"
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "1",
-                            "--width", str(W), "--height", str(H), "--batch", str(B), "--no-extras", "--no-cpu-baseline",
+                            "--width", str(W), "--height", str(H), "--batch", str(B), "--full", "--no-extras", "--no-cpu-baseline",
                             "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
         assert r.returncode == 0, r.stderr[-2000:]
         line = json.loads([l for l in r.stdout.split("\n") if l.strip()][0])
