@@ -852,6 +852,9 @@ def _redetect_choice(match, r):
                                   "ratio": match.ratio, **over})
 
 
+redetect_choice = _redetect_choice   # the public name: callers who queue Context.track_redetect themselves form the same parameters
+
+
 class _ChunkTrack:
     """center="track" of a chunk of n pairs: behind(ls, js) queues Context.track_advance on the slots of
     the chunk's pairs ls (the l-th pair in flow slot l % ring), in pair order, with the records of pair l at byte 48 * T * l of

@@ -11,8 +11,10 @@ process_chunk's docstring promises:
         out, in place, behind the residual call) or consistency_weights over all n pairs, from the RAW fields;
     1b. center="track": track_template from frame 0 about the state when capturing; then per batch of `batch` pairs
         track_advance on the raw fields, with match track_match on the batch's f0 frames about its records and track_match
-        with one item on the batch's last f1 frame about the state, with roi roi_weights.  The state's match happens at batch
-        borders, so its outcome depends on the engine's B: by_hand takes batch=;
+        with one item on the batch's last f1 frame about the state, with match["redetect"] track_redetect with one item on that
+        same frame about the state, triggered by the records the state's match just wrote, with write-back, its T records at
+        index hi - 1 of an (n x T)-record buffer pre-filled with 0xA5, with roi roi_weights.  The state's match and the
+        re-detection happen at batch borders, so their outcome depends on the engine's B: by_hand takes batch=;
     2. compensate=: motion_fit (under the maps when there are maps, unweighted under a track), then motion_subtract in place;
     3. weights= (and the track's roi): pass1_weighted            -- or --   center="variance": cell_stats;
     4. one window call over the whole chunk (seq = range(n), first = 0, count = n, radius 6): radial_window[_axes],
@@ -25,8 +27,10 @@ The helper is anchored to the CPU (check_anchors), so that by-hand and engine ca
 raw field of the tuned Farneback path is oracle.farneback of its pair, and every compensated field is
 motion_ref.subtract(raw, model); the maps a mode makes are residual_ref / texture_ref / consistency_ref of the raw fields and
 the clip's frames; track records and the final state are track_ref's over the raw fields, match records, corrected records
-and templates match_ref's (corrected_batch per batch, template), ROI maps track_ref's -- all on bytes, for all n pairs.  No pytest marks: test_gpu_chunk_compose.py compares the engine with it on
-bytes, and test_chunk_schedule_host.py holds the engine's schedules to the same order without a device."""
+and templates match_ref's (corrected_batch per batch, template), re-detection records and the state they move redetect_ref's
+(found_batch per batch; every record that is not a batch's last pair stays 0xA5), ROI maps track_ref's -- all on bytes, for
+all n pairs.  No pytest marks: test_gpu_chunk_compose.py compares the engine with it on bytes, and
+test_chunk_schedule_host.py holds the engine's schedules to the same order without a device."""
 import numpy as np
 
 from funscript_flow_amd import _capi, pipeline
@@ -57,6 +61,100 @@ def padded(maps, device):
     return view
 
 
+def suite_clip(frames, w, h):
+    """the composed-chunk suites' clip: aperiodic over `frames` frames (period 53), so that no two pairs are the same bytes"""
+    from funscript_flow_amd.synth import sine_translate_frames
+    return sine_translate_frames(frames, w, h, seed=3, zoom=0.03, period=53, amp=(6.0, 3.0))
+
+
+# The lost-and-found clip of the re-detection cases: a square of random bytes pasted over the suite's clip.  It walks + 1 px
+# per frame in x and turns round at the ends of `span` (its centre's x), jumps to the centres of `jumps` at those frames and
+# walks on from there in the direction it had, and is not pasted into the frames of `absent` (its walk goes on unseen).
+LOST = dict(seed=1300, side=13, start=(14, 20), span=(8, 55), absent=(12, 28),
+            jumps={7: (34, 12), 16: (12, 34), 22: (50, 30), 30: (20, 10), 37: (44, 36)})
+
+
+def lost_path(frames, lost=LOST):
+    """the square's centre (x, y) in every frame, the absent ones included"""
+    (x, y), d, path = lost["start"], 1, []
+    for k in range(frames):
+        if k in lost["jumps"]:
+            x, y = lost["jumps"][k]
+        elif k:
+            if not lost["span"][0] <= x + d <= lost["span"][1]:
+                d = -d
+            x += d
+        path.append((x, y))
+    return path
+
+
+def lost_clip(base, lost=LOST):
+    """`base` (frames, H, W) uint8 with the square pasted about lost_path's centres"""
+    out, r = np.array(base), lost["side"] // 2
+    square = np.random.default_rng(lost["seed"]).integers(0, 256, (lost["side"], lost["side"])).astype(np.uint8)
+    for k, (x, y) in enumerate(lost_path(len(out), lost)):
+        if k not in lost["absent"]:
+            out[k, y - r:y + r + 1, x - r:x + r + 1] = square
+    return out
+
+
+def border_searches(redetect, n, T, batch):
+    """What the re-detection did at the chunk's batch borders, from the bytes of by_hand's or track_run's `redetect`: per track
+    (skipped, accepted and moved the state, triggered and rejected, the statuses of the rejected ones); the records of every
+    pair that is not a batch's last must be untouched 0xA5 bytes."""
+    rec = np.frombuffer(redetect, _capi.MATCH_DTYPE).reshape(n, T)
+    last = [min(lo + int(batch), n) - 1 for lo in range(0, n, int(batch))]
+    rest = np.delete(np.frombuffer(redetect, np.uint8).reshape(n, -1), last, axis=0)
+    assert (rest == 0xA5).all(), "a re-detection record that is no batch's last pair was written"
+    out = []
+    for t in range(T):
+        r = rec[last, t]
+        ran = r["status"] != _capi.REDETECT_SKIPPED
+        moved = (r["status"] == 0) & ((r["dx"] != 0) | (r["dy"] != 0))
+        out.append((int((~ran).sum()), int(moved.sum()), int((ran & (r["status"] != 0)).sum()),
+                    sorted({int(s) for s in r["status"][ran & (r["status"] != 0)]})))
+    return out
+
+
+# The two re-detection cases of test_gpu_chunk_compose.py on the lost-and-found clip (64x48, 41 pairs), as plain data: the host
+# test test_chunk_redetect_host.py derives their thresholds and meets their conditions on the CPU restatements alone.
+#   K13  one track on the square, the library's default thresholds, redetect=True (the whole frame);
+#   K14  the dict form with a reach that some jumps exceed, a second track on the background whose trigger words differ from
+#        track 0's, ROI maps about track 0 under a static gate.  Track 1 starts at (18, 32), not at the (20, 30) first meant
+#        for it: a 13x13 template about (20, 30) holds a corner of the square in frame 0 (21 of its 169 pixels), follows the
+#        square and is lost with it at the first jump -- on the restatements it was skipped at 3 of 14 (B = 3) and 2 of 11
+#        (B = 4) borders, whatever the reach and wherever the jumps go.  (18, 32) is the nearest point on a 2 px grid whose
+#        template is background only and which is still triggered at a border or two on either context.
+LOST_TRACKS = {
+    "K13": dict(state=pipeline.track_state_array([(14.0, 20.0)]), radius=9, on_cut="hold", match={"p": 6, "s": 4, "redetect": True},
+                capture=True),
+    "K14": dict(state=pipeline.track_state_array([(14.0, 20.0), (18.0, 32.0)]), radius=9, on_cut="hold", roi=(20.0, 12.0),
+                match={"p": 6, "s": 4, "redetect": {"reach": 20, "exclude": 4}}, capture=True),
+}
+LOST_THR = {"K13": 0.614, "K14": 0.68}
+LOST_GATE_SEED = 1400
+
+
+def check_redetect_conditions(case, redetect, track, n, batch):
+    """What K13 and K14 were chosen for, on a `redetect` buffer of n pairs (by_hand's or track_run's) and the `track` records:
+    K13 at least 3 skipped searches, at least 3 accepted ones that move the state, at least 1 triggered and rejected, and rule
+    Q5 cuts between a quarter and three quarters of the pairs; K14 track 0 at least 2 accepted ones that move the state and at
+    least 1 triggered and rejected, track 1 skipped at three quarters of the borders or more."""
+    T = len(LOST_TRACKS[case]["state"])
+    got = border_searches(redetect, n, T, batch)
+    borders = -(-n // int(batch))
+    skipped, moved, rejected, _ = got[0]
+    assert skipped + rejected + moved <= borders
+    if case == "K13":
+        assert skipped >= 3 and moved >= 3 and rejected >= 1, got
+        cuts = int(((np.frombuffer(track, _capi.TRACK_DTYPE).reshape(n, T)["status"][:, 0] & 1) != 0).sum())
+        assert n / 4 <= cuts <= 3 * n / 4, cuts
+    else:
+        assert moved >= 2 and rejected >= 1, got
+        assert got[1][0] >= 3 * borders / 4, got
+    return got
+
+
 def hand_context(w, h, n, device=0, reverse=False):
     """a context on which a chunk of n pairs never recycles anything; reverse: with room for the n reversed pairs as well"""
     k = 2 if reverse else 1
@@ -74,12 +172,12 @@ def by_hand(ctx, frames_or_fields, *, pov, thr, axes=True, weights=None, center=
     "residual" | "texture" | "consistency" with residual= / texture= / consistency= (parameters; texture= next to "residual":
     the combination) and gate (the static gate, a device tensor); center: None, "variance" over cells x cells, or "track" with
     track = dict(state = (T,) TRACK_STATE_DTYPE host records, radius, on_cut, roi = (ax, ay) or None, roi_soft, match = a dict
-    of MatchParams fields or None, capture, templates = host bytes when not capturing) and batch, the engine's B; compensate: as
-    process_chunk takes it; algo: None (Farneback) or ("dis", DisParams or None); window: "box" or "gaussian".  Returns dict(post
+    of MatchParams fields or None, next to them "redetect" = True or a dict as process_chunk takes it, capture, templates = host
+    bytes when not capturing) and batch, the engine's B; compensate: as process_chunk takes it; algo: None (Farneback) or ("dis", DisParams or None); window: "box" or "gaussian".  Returns dict(post
     = the n records as bytes, motion = the n 64-byte records as bytes or None, grid = the cell records as bytes or None, flows =
     (n, H, W, 2) float32 as left in the slots, pass1 = pass1_results' tuples of the slots as left, raw = (n, H, W, 2) float32
     as the flow call left them, raw_pass1 = pass1_results of the raw fields, raw_bwd = the reversed pairs' raw fields or None,
-    maps / track / state / match / templates = bytes or None)."""
+    maps / track / state / match / templates / redetect = bytes or None)."""
     import torch
     dev = torch.device("cuda", ctx.device)
     given = not isinstance(frames_or_fields, (list, tuple)) and getattr(frames_or_fields, "ndim", 0) == 4
@@ -122,7 +220,7 @@ def by_hand(ctx, frames_or_fields, *, pov, thr, axes=True, weights=None, center=
             assert mode == "consistency" and compensate is None
             ctx.consistency_weights(slots, [n + j for j in slots], maps, _capi.consistency_choice(consistency), gate)
     # 1b. the track, on the raw fields
-    trk = sd = mout = tmpl = None
+    trk = sd = mout = tmpl = rout = None
     if center == "track":
         T = len(track["state"])
         item = T * _capi.TRACK_DTYPE.itemsize
@@ -132,7 +230,11 @@ def by_hand(ctx, frames_or_fields, *, pov, thr, axes=True, weights=None, center=
         prm = None
         if track.get("match") is not None:
             assert not given, "the match reads the frames"
-            prm = _capi.match_choice(track["match"])
+            prm = _capi.match_choice({k: v for k, v in track["match"].items() if k in _capi.MATCH_FIELDS})
+            rprm = None
+            if track["match"].get("redetect") not in (None, False):
+                rprm = pipeline.redetect_choice(prm, track["match"]["redetect"])
+                rout = torch.full((n * item,), 0xA5, dtype=torch.uint8, device=dev)
             mout = torch.full((n * item,), 0xA5, dtype=torch.uint8, device=dev)
             sout = pipeline.match_buffer(ctx, 1, T)
             if track.get("capture", track.get("templates") is None):
@@ -149,6 +251,8 @@ def by_hand(ctx, frames_or_fields, *, pov, thr, axes=True, weights=None, center=
             if prm is not None:
                 ctx.track_match(f0[lo:hi], tmpl, (part, item), mout[lo * item:hi * item], prm, T, True)
                 ctx.track_match([f1[hi - 1]], tmpl, (sd, item), sout, prm, T, True)
+                if rprm is not None:
+                    ctx.track_redetect([f1[hi - 1]], tmpl, (sd, item), rout[(hi - 1) * item:hi * item], rprm, T, sout, True)
             if maps is not None:
                 ctx.roi_weights(hi - lo, (part, item), maps[lo:hi], {"ax": track["roi"][0], "ay": track["roi"][1],
                                                                      "soft": int(bool(track.get("roi_soft", True)))}, gate=gate)
@@ -187,7 +291,8 @@ def by_hand(ctx, frames_or_fields, *, pov, thr, axes=True, weights=None, center=
         ctx.radial_window(slots, 0, n, out, RADIUS, thr, pov)
     b = lambda t: None if t is None else t.cpu().numpy().tobytes()   # noqa: E731
     return dict(post=b(out), motion=motion, grid=grid, flows=_fields(ctx, slots), pass1=ctx.pass1_results(slots, thr), raw=raw,
-                raw_pass1=raw_pass1, raw_bwd=raw_bwd, maps=b(maps), track=b(trk), state=b(sd), match=b(mout), templates=b(tmpl))
+                raw_pass1=raw_pass1, raw_bwd=raw_bwd, maps=b(maps), track=b(trk), state=b(sd), match=b(mout), templates=b(tmpl),
+                redetect=b(rout))
 
 
 def records(post, axes=True):
@@ -245,19 +350,28 @@ def mode_maps(frames, raw, mode, residual=None, texture=None, consistency=None, 
 
 def track_run(frames, raw, mean_mag, thr, track, batch, gate=None):
     """The track of a chunk on the CPU: track_ref.advance over the raw fields, per batch of `batch` pairs, its cuts rule Q5 on the
-    raw records' float32 mean magnitudes; with track["match"] match_ref.corrected_batch per batch and match_ref.template.
-    Returns dict(track, state, match, templates, maps) as bytes or None."""
+    raw records' float32 mean magnitudes; with track["match"] match_ref.corrected_batch per batch and match_ref.template; with
+    track["match"]["redetect"] redetect_ref.found_batch per batch instead: corrected_batch with the batch's cuts, then
+    redetect_ref.redetect of the state on the batch's last f1 frame, triggered by the state's match records, with write-back.
+    Returns dict(track, state, match, templates, maps, redetect) as bytes or None; redetect: (n, T) records, every index that
+    is not a batch's last pair 0xA5 bytes."""
     import match_ref
+    import redetect_ref
     import track_ref
     n, (h, w) = len(raw), raw[0].shape[:2]
     cuts = track_ref.mean_mag_cut(mean_mag, thr)
     st = np.array(track["state"], track_ref.STATE_DTYPE)
     radius, on_cut = track.get("radius", 12), _capi.TRACK_ON_CUT.index(track.get("on_cut", "hold"))
-    prm = tm = None
+    prm = tm = rprm = rrecs = None
     if track.get("match") is not None:
         assert on_cut == track_ref.HOLD, "match_ref.corrected_batch advances with on_cut='hold'"
-        prm = _capi.match_choice(track["match"]).as_dict()
+        choice = _capi.match_choice({k: v for k, v in track["match"].items() if k in _capi.MATCH_FIELDS})
+        prm = choice.as_dict()
         prm["mode"] = _capi.MATCH_MODES.index(prm["mode"])
+        if track["match"].get("redetect") not in (None, False):
+            rprm = pipeline.redetect_choice(choice, track["match"]["redetect"]).as_dict()
+            rprm["mode"] = _capi.MATCH_MODES.index(rprm["mode"])
+            rrecs = np.full((n, len(st) * redetect_ref.RECORD_DTYPE.itemsize), 0xA5, np.uint8)
         if track.get("capture", track.get("templates") is None):
             tm = match_ref.template(frames[0], np.stack([st["x"], st["y"]], axis=-1), prm["p"])
         else:
@@ -268,9 +382,14 @@ def track_run(frames, raw, mean_mag, thr, track, batch, gate=None):
         hi = min(lo + int(batch), n)
         if prm is None:
             rec, st = track_ref.advance(raw[lo:hi], cuts[lo:hi], st, radius, on_cut)
-        else:
+        elif rprm is None:
             rec, mrec, _, st = match_ref.corrected_batch(track_ref, frames[lo:hi + 1], raw[lo:hi], st, tm, radius, prm, cuts[lo:hi])
             mrecs.append(mrec)
+        else:
+            rec, mrec, _, rrec, st = redetect_ref.found_batch(track_ref, frames[lo:hi + 1], raw[lo:hi], st, tm, radius, prm, rprm,
+                                                              cuts[lo:hi])
+            mrecs.append(mrec)
+            rrecs[hi - 1] = np.frombuffer(rrec.tobytes(), np.uint8)
         recs.append(rec)
     rec = np.concatenate(recs)
     maps = None
@@ -278,13 +397,14 @@ def track_run(frames, raw, mean_mag, thr, track, batch, gate=None):
         maps = track_ref.roi_maps(w, h, np.stack([rec["x"][:, 0], rec["y"][:, 0]], axis=-1), track["roi"][0], track["roi"][1],
                                   bool(track.get("roi_soft", True)), gate).tobytes()
     return dict(track=rec.tobytes(), state=st.tobytes(), match=np.concatenate(mrecs).tobytes() if mrecs else None,
-                templates=None if tm is None else tm.tobytes(), maps=maps)
+                templates=None if tm is None else tm.tobytes(), maps=maps, redetect=None if rrecs is None else rrecs.tobytes())
 
 
 def check_mode_anchors(res, frames, *, thr, weights=None, residual=None, texture=None, consistency=None, gate=None, center=None,
                        track=None, batch=None):
     """The CPU anchors of what by_hand made behind the flow call, on bytes, for all n pairs: the maps of a mode (mode_maps), and
-    under a track its records, final state, match records, templates and ROI maps (track_run).  `gate`: the host array."""
+    under a track its records, final state, match records, templates, re-detection records -- the whole (n, T) buffer, so the
+    entries that are no batch's last pair are held to their 0xA5 fill -- and ROI maps (track_run).  `gate`: the host array."""
     if isinstance(weights, str):
         want = mode_maps(frames, res["raw"], weights, residual, texture, consistency, gate, res["raw_bwd"])
         got = np.frombuffer(res["maps"], np.uint8).reshape(want.shape)
@@ -292,6 +412,6 @@ def check_mode_anchors(res, frames, *, thr, weights=None, residual=None, texture
         assert not bad, f"the {weights} maps of pairs {bad} are not the restatement's"
     if center == "track":
         want = track_run(frames, res["raw"], [r[3] for r in res["raw_pass1"]], thr, track, batch, gate)
-        for key in ("templates", "match", "track", "state", "maps"):
+        for key in ("templates", "match", "redetect", "track", "state", "maps"):
             assert (res[key] is None) == (want[key] is None), key
             assert res[key] == want[key], f"the track's {key} are not the restatement's"

@@ -152,11 +152,11 @@ def lost_scene():
     return frames, flows, true
 
 
-def found_batch(track_ref, frames, flows, st, templates, radius, prm, rprm=None):
-    """match_ref.corrected_batch, then (rprm not None) the re-detection of the state on frames[nb] triggered by the state's match
-    records, with write-back.  Returns (track records, match records, the state's match records, the state's re-detection
-    records or None, the new state)."""
-    rec, mrec, srec, st = match_ref.corrected_batch(track_ref, frames, flows, st, templates, radius, prm)
+def found_batch(track_ref, frames, flows, st, templates, radius, prm, rprm=None, cuts=None):
+    """match_ref.corrected_batch (cuts: rule Q5's outcome per field, None: no cut), then (rprm not None) the re-detection of the
+    state on frames[nb] triggered by the state's match records, with write-back.  Returns (track records, match records, the
+    state's match records, the state's re-detection records or None, the new state)."""
+    rec, mrec, srec, st = match_ref.corrected_batch(track_ref, frames, flows, st, templates, radius, prm, cuts)
     rrec = None
     if rprm is not None:
         scen = np.stack([st["x"], st["y"]], axis=-1)[None]

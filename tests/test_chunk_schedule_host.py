@@ -24,16 +24,24 @@ counter "next pair to advance"; track_advance takes consecutive raw pairs from i
 runs at most once, before the first advance, on the slot of frame 0; the records' match runs on the f0 slots of records
 advanced and not yet matched, the state's match is one item on the slot of frame last + 1 straight behind it, roi_weights
 comes after both; the fit under a track is unweighted; the window forms about the track buffer (base lo * 48 * T, stride
-48 * T) find every pair of their seq advanced, matched and mapped.
+48 * T) find every pair of their seq advanced, matched and mapped.  With track["match"]["redetect"] track_redetect is one item
+on the slot of frame last + 1 about the state tensor (stride 48 * T) with the chunk's templates, straight behind the state's
+match of the batch just advanced and at most once per batch -- every advance but the first finds one re-detection per batch
+before it --, its trigger is the span the state's match of THIS batch wrote (a mark the next advance clears), write_back is
+true, and its 48 * T bytes go to record `last` of redetect_out, each record written at most once per chunk and no other record
+ever; roi_weights then comes behind it.
 
 The cross product n x B x depth x spare slots x schedule x entry point x keyword set x flows_out layout x engine flavour is
 some 10^6 chunks; every AXIS is swept whole, the product is trimmed: every (n, B, depth, spare) context runs a rotating
 choice of five keyword sets (PER_CONTEXT; four reached every axis value while there were thirteen sets, not with
-twenty-seven), each on a rotating schedule, entry point, layout and flavour, and the test asserts that every keyword set met
-every n, every B, every (depth, spare), both schedules, every entry point and every layout.  12311 chunks; the file takes 12
-to 17 s on the CPU where its thirteen sets in 9936 chunks took 8: the chunks grew by a quarter, and a chunk of the new sets
-issues up to five more calls per batch (template, advance, two matches, ROI map), each with its own address lookups --
-nothing in the profile stands out, the time is spread over the same functions as before.
+twenty-seven; five still do with thirty-one), each on a rotating schedule, entry point, layout and flavour, and the test
+asserts that every keyword set met every n, every B, every (depth, spare), both schedules, every entry point and every layout.
+12309 chunks; the file takes 12 to 17 s on the CPU where its thirteen sets in 9936 chunks took 8: the chunks grew by a quarter,
+and a chunk of the new sets issues up to five more calls per batch (template, advance, two matches, ROI map), each with its
+own address lookups -- nothing in the profile stands out, the time is spread over the same functions as before.  With the four
+re-detection sets the chunk count stays (PER_CONTEXT did not have to rise: the rotation spreads the same contexts over more
+sets) and the file takes 14.2 s where its twenty-seven sets took 11.4 s on the same machine: about one chunk in eight now
+runs a re-detection set, the sets with the most calls per batch.
 
 What turns these tests red, tried with pipeline.py edited by hand, one edit at a time (every keyword set the edit reaches
 goes red; none of the eleven stays green):
@@ -54,7 +62,17 @@ goes red; none of the eleven stays green):
     on: track_template a second time;
 10. centres() with an item of 48 -- track3-home, track-match, track-roi-match (the sets with T > 1): the stride is not 48 * T;
 11. with_frames handed the previous batch's f0 / f1 -- every frame-reading set (the seven residual / texture sets and the
-    four match sets), from the second batch on: the slots hold the previous pairs' frames."""
+    four match sets), from the second batch on: the slots hold the previous pairs' frames.
+Six more, on the re-detection call of _ChunkTrack.behind, with the four re-detection sets (track-match-redetect,
+track-roi-match-redetect, compensate-track-roi-match-redetect, track-match-redetect-dict); none stays green:
+ a. the re-detection on f0[-1] -- all four, every chunk: frame last where the state stands in frame last + 1;
+ b. its output at ls[0] -- all four, in every chunk with a batch of two pairs or more: not the batch's last record;
+ c. its trigger the batch's match_out span instead of state_match -- all four, every chunk: not what the state's match of
+    this batch wrote;
+ d. the re-detection queued ahead of the state's match -- all four, every chunk: behind the records' match;
+ e. its centres the batch's records -- all four, every chunk: not the state tensor;
+ f. _ChunkTrack.with_frames handed the previous batch's f0 / f1 -- all four and the four match sets, from the second batch
+    on (the records' match meets the wrong frames first)."""
 import itertools
 import os
 import re
@@ -205,7 +223,8 @@ class LedgerCtx:
     maps (None | ("static", base) | ("pair", base, stride)), variance, grid (tensor or None), cons (None | dict(maps, gate)),
     flows_out ((tensor, layout) or None), motion (tensor or None), item, axes, pov, thr, src (the source arrays of process_flows),
     frame_maps (None | dict(mode, texture, gate, params): weights="residual" | "texture"), track (None | dict(T, state, on_cut,
-    roi, gate, match, capture, templates, p, track_out, match_out): center="track"; a tensor the caller did not give is None)."""
+    roi, gate, match, capture, templates, p, track_out, match_out, redetect, redetect_params, redetect_out): center="track"; a
+    tensor the caller did not give is None)."""
 
     def __init__(self, arena, max_batch, frame_slots, flow_slots):
         self.arena, self.width, self.height, self.device = arena, W, H, 0
@@ -221,7 +240,9 @@ class LedgerCtx:
         # the maps a mode makes behind a batch, per pair: [] unwritten -> ["residual"] -> ["residual", "texture"], ["texture"], ["roi"]
         self.made = [[] for _ in range(n)]
         self.advanced, self.matched = [0] * n, [0] * n
-        self.next_advance = self.templates = self.state_matches = 0
+        self.next_advance = self.templates = self.state_matches = self.redetects = 0
+        self.redetected = [0] * n               # writes per record of redetect_out
+        self.state_written = None               # the span the state's match of THIS batch wrote; the next advance clears it
         self.last = None                        # the latest call queued behind a batch
 
     # -- helpers
@@ -523,6 +544,9 @@ class LedgerCtx:
         assert self._where("track", ptr, 48 * t["T"], t["track_out"]) == first, "track_advance: its records are not at first * 48 * T"
         assert nbytes == len(seq_slots) * 48 * t["T"]
         assert self.templates == (1 if t["match"] and t["capture"] else 0), "track_advance: the template is captured before the first advance, or never"
+        batches = -(-first // self.max_batch)
+        assert self.redetects == (batches if t["redetect"] else 0), f"track_advance of batch {batches}: {self.redetects} re-detections so far"
+        self.state_written = None
         for p in range(first, first + len(seq_slots)):
             self.advanced[p] += 1
         self.next_advance += len(seq_slots)
@@ -542,8 +566,11 @@ class LedgerCtx:
             assert self.last is not None and self.last[0] == "records_match" and self.last[1] + self.last[2] == self.next_advance, \
                 f"track_match (state): behind {self.last}, not behind the records' match of its batch"
             self._frames(fslots, self.next_advance, "track_match (state)")       # frame last + 1
-            assert self.arena.find(span(out))[0] not in (self.buffers.get("track"), self.buffers.get("match")), "track_match (state): its records go to a buffer of their own"
+            assert self.arena.find(span(out))[0] not in (self.buffers.get("track"), self.buffers.get("match"), self.buffers.get("redetect")), \
+                "track_match (state): its records go to a buffer of their own"
+            assert _capi._device_span(out)[1] == 48 * t["T"]
             self.state_matches += 1
+            self.state_written = _capi._device_span(out)
             self.last = ("state_match",)
             return
         first, count = self._track_records(centres, "track_match")
@@ -557,6 +584,34 @@ class LedgerCtx:
             self.matched[p] += 1
         self.last = ("records_match", first, count)
 
+    def track_redetect(self, fslots, templates, centres, out, params=None, tracks=1, trigger=None, write_back=True, stream=None):
+        self._stream(stream)
+        t = self.want["track"]
+        assert t is not None and t["match"] and t["redetect"], "track_redetect without track['match']['redetect']"
+        assert isinstance(params, _capi.RedetectParams) and write_back is True and (params.p, tracks) == (t["p"], t["T"])
+        got = params.as_dict()
+        assert {k: got[k] for k in t["redetect_params"]} == t["redetect_params"], f"track_redetect: parameters {got}, meant {t['redetect_params']}"
+        # one item, straight behind the state's match of the batch just advanced, once per batch
+        assert len(fslots) == 1, f"track_redetect: {len(fslots)} items"
+        assert self.last == ("state_match",), f"track_redetect: behind {self.last}, not behind the state's match of its batch"
+        last = self.next_advance - 1
+        self._frames(fslots, last + 1, "track_redetect")                   # the frame the state stands in
+        assert isinstance(centres, tuple) and len(centres) == 2 and isinstance(centres[0], FakeTensor), "track_redetect: not the state tensor"
+        self._state(centres[0], "track_redetect")
+        assert centres[1] == 48 * t["T"]
+        self._templates(templates, "track_redetect")
+        assert self.templates == (1 if t["capture"] else 0)
+        assert trigger is not None and self.state_written is not None and _capi._device_span(trigger) == self.state_written, \
+            "track_redetect: the trigger is not what the state's match of this batch wrote"
+        ptr, nbytes = _capi._device_span(out)
+        at = self._where("redetect", ptr, 48 * t["T"], t["redetect_out"])
+        assert at == last and nbytes == 48 * t["T"], f"track_redetect: {nbytes} bytes at record {at}, meant {48 * t['T']} at the batch's last pair {last}"
+        assert self.arena.find(ptr)[0] not in (self.buffers.get("track"), self.buffers.get("match"), self.arena.find(self.state_written[0])[0])
+        self.redetected[at] += 1
+        assert self.redetected[at] == 1, f"track_redetect: record {at} written a second time"
+        self.redetects += 1
+        self.last = ("redetect",)
+
     def _state_ptr(self):
         t = self.want["track"]
         return (t["state"] if t["state"] is not None else self.arena.uploaded[0]).data_ptr()
@@ -567,7 +622,7 @@ class LedgerCtx:
         assert t is not None and t["roi"] and isinstance(params, _capi.RoiParams)
         first, count = self._track_records(centres, "roi_weights")
         assert count == n and self._map_index(out, n, "roi_weights") == first, "roi_weights: the maps of other pairs"
-        assert self.last == (("state_match",) if t["match"] else ("track_advance", first, n)), \
+        assert self.last == (("redetect",) if t["redetect"] else ("state_match",) if t["match"] else ("track_advance", first, n)), \
             f"roi_weights of pairs {first}..{first + n - 1}: behind {self.last}"
         self._tracked(first, n, "roi_weights")
         self._gate(gate, t["gate"], "roi_weights")
@@ -680,15 +735,19 @@ class LedgerCtx:
         assert self.next_advance == (n if t else 0)
         assert self.state_matches == (-(-n // self.max_batch) if t and t["match"] else 0), f"{self.state_matches} state matches"
         assert self.templates == (1 if t and t["match"] and t["capture"] and n else 0), f"{self.templates} template captures"
+        batches = -(-n // self.max_batch)
+        assert self.redetects == (batches if t and t["redetect"] else 0), f"{self.redetects} re-detections"
+        assert self.redetected == [int(bool(t and t["redetect"]) and (p + 1 == n or (p + 1) % self.max_batch == 0)) for p in range(n)]
         if t or fm:
             self._final(0, n, "the chunk's end")
         else:
             assert self.made == [[] for _ in range(n)]
         if t and n:
-            for role, given in (("track", t["track_out"]), ("match", t["match_out"] if t["match"] else None)):
+            for role, given in (("track", t["track_out"]), ("match", t["match_out"] if t["match"] else None),
+                                ("redetect", t["redetect_out"] if t["redetect"] else None)):
                 if given is not None:
                     assert self.buffers[role] == self.arena.find(given.data_ptr())[0], f"{role}_out is not the caller's buffer"
-            assert ("match" in self.buffers) == bool(t["match"])
+            assert ("match" in self.buffers) == bool(t["match"]) and ("redetect" in self.buffers) == bool(t["redetect"])
         if w["device"]:
             assert self.collected == [0] * n and isinstance(result, FakeTensor)
             if w["post"] is not None:
@@ -764,13 +823,14 @@ def frame_maps(arena, n, mode="residual", texture=False, gate=False):
     return kw, want
 
 
-def track(arena, n, T=1, state=False, on_cut="hold", roi=False, match=None, out=False):
+def track(arena, n, T=1, state=False, on_cut="hold", roi=False, match=None, out=False, redetect=None):
     """center="track": T tracks from `start`, or from a state tensor of the caller's; roi: maps with a static gate into the
     caller's weights_out; match: None, "templates" (the caller's, capture off) or "capture"; out: the caller's track_out
-    (and match_out)"""
+    (and match_out, redetect_out); redetect: None, True or the dict form of track["match"]["redetect"]"""
     tr = {"on_cut": on_cut, "radius": 5}
     want = {"T": T, "state": None, "on_cut": on_cut, "roi": roi, "gate": None, "match": match is not None, "capture": False,
-            "templates": None, "p": None, "track_out": None, "match_out": None}
+            "templates": None, "p": None, "track_out": None, "match_out": None, "redetect": redetect is not None,
+            "redetect_params": None, "redetect_out": None}
     if state:
         tr["state"] = want["state"] = tensor(arena, (T * _capi.TRACK_STATE_DTYPE.itemsize,))
     else:
@@ -785,10 +845,17 @@ def track(arena, n, T=1, state=False, on_cut="hold", roi=False, match=None, out=
         want["p"], want["capture"] = 6, match == "capture"
         if match == "templates":
             tr["match"]["templates"] = want["templates"] = tensor(arena, (T, 13, 13))
+        if redetect is not None:     # p, mode and thresholds are the match's; exclude defaults to p, reach to the whole frame, the mask to POOR
+            tr["match"]["redetect"] = redetect
+            r = {} if redetect is True else redetect
+            want["redetect_params"] = {"p": 6, "mode": "zssd", "exclude": r.get("exclude", 6), "reach": r.get("reach", 0),
+                                       "trigger_mask": r.get("mask", 2), "max_mse": 400.0, "ratio": 0.8}
     if out:
         kw["track_out"] = want["track_out"] = tensor(arena, (max(n, 1) * T * 48 + 16,))
         if match is not None:
             kw["match_out"] = want["match_out"] = tensor(arena, (max(n, 1) * T * 48,))
+        if redetect is not None:
+            kw["redetect_out"] = want["redetect_out"] = tensor(arena, (max(n, 1) * T * 48 + 48,))
     return kw, {"track": want}
 
 
@@ -828,6 +895,12 @@ KEYWORDS = {
     "track-match-capture": lambda arena, n: track(arena, n, match="capture"),
     "track-roi-match": lambda arena, n: track(arena, n, T=2, state=True, roi=True, match="capture", out=True),
     "compensate-track-roi-match": both(lambda arena, n: compensate(arena, n, "affine"), lambda arena, n: track(arena, n, roi=True, match="capture")),
+    "track-match-redetect": lambda arena, n: track(arena, n, T=2, match="templates", out=True, redetect=True),
+    "track-roi-match-redetect": lambda arena, n: track(arena, n, T=2, state=True, roi=True, match="capture", redetect=True),
+    "compensate-track-roi-match-redetect": both(lambda arena, n: compensate(arena, n, "affine"),
+                                                lambda arena, n: track(arena, n, roi=True, match="capture", out=True, redetect=True)),
+    "track-match-redetect-dict": lambda arena, n: track(arena, n, T=3, state=True, match="capture", out=True,
+                                                        redetect={"reach": 20, "exclude": 4, "mask": 6}),
 }
 FRAME_READERS = tuple(k for k in KEYWORDS if "residual" in k or "texture" in k or "match" in k)      # process_chunk only
 ENTRIES = ("chunk", "flows", "segments")

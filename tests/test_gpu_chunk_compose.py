@@ -19,8 +19,8 @@ compensated ones (0.079 .. 0.205, medians 0.141 .. 0.150 over the four models an
 fields (median 0.180) and 0.10 for compensated DIS fields (median 0.1035).  The conditions themselves are asserted on the
 by-hand result (test_the_clip_and_the_thresholds_do_their_work).
 
-K7-K12 are the modes that make their maps or their centres behind a batch (DESIGN.md sections 18, 21-24), K7, K8 and K11 from
-the batch's FRAME slots: K7 weights="residual" with texture=, a static gate and compensate="translation"; K8 weights="texture"
+K7-K14 are the modes that make their maps or their centres behind a batch (DESIGN.md sections 18, 21-25), K7, K8, K11, K13 and
+K14 from the batch's FRAME slots: K7 weights="residual" with texture=, a static gate and compensate="translation"; K8 weights="texture"
 with explicit parameters and compensate="affine"; K9 weights="consistency" with a gate (the batch is halved: one pair per
 batch on R1, two on R2, and the split ring wraps); K10 center="track", three tracks from a state tensor, on_cut="home", also
 through process_flows; K11 center="track" with roi, a gate and match (p = 6, s = 4, accept-everything thresholds so that
@@ -36,6 +36,20 @@ mean under the ROI maps of chunk_by_hand.track_run (0.2653 .. 0.7451, median 0.5
 0.48 lies between the two medians and cuts 18 of 41 pairs for the track and 24 of 41 for the window.  K12 runs at 0.145: every
 raw mean_mag lies above it, so the track, which reads the raw fields, must see EVERY pair as cut while the window cuts about
 half -- an advance queued behind the subtraction would cut about half and change the bytes.
+
+K13 and K14 are track["match"]["redetect"].  The suite's clip never loses its subject -- with a template
+from frame 0 every search about the state reads OK and every re-detection is SKIPPED -- so they run on a clip of their own,
+chunk_by_hand.lost_clip: the suite's clip with a 13x13 square of random bytes that walks 1 px per frame, jumps at frames 7, 16,
+22, 30 and 37 and is absent from frames 12 and 28 (both batch borders of R1, and of R2).  K13: one track on the square, radius
+9, on_cut="hold", match p = 6, s = 4 with the library's default thresholds, redetect=True, capture on; K14: the dict form
+(reach 20, exclude 4), a second track on the background whose trigger words differ from track 0's, and roi with a static
+gate.  redetect_out is pre-filled with 0xA5 and compared whole, so the records and "no other entry is written" are one
+comparison.  What the CPU restatements give on this clip -- the counts of skipped, accepted and rejected searches on either
+context, the thresholds 0.614 (K13: the raw means' median 0.6117 and its neighbour 0.6162 on either side) and 0.68 (K14: between
+the raw median and the 0.88 of the means under the ROI maps, as K11's) -- is derived and asserted without a device in
+tests/test_chunk_redetect_host.py; the conditions are asserted again here on the by-hand result
+(chunk_by_hand.check_redetect_conditions).  K13 also runs as two chunks split at pair 21 with the state and the templates
+carried over (test_a_carried_state_re_detects_as_the_one_chunk_run), and among the short chunks.
 
 DIS refuses 64x48 (rule D2: the coarsest scale would lie below the finest), so its row runs the same clip at 128x96, the
 smallest size of this aspect it accepts.
@@ -53,7 +67,15 @@ hook's flow slots % (flow_slots - 1), its maps slice one short, the texture comb
 leak test, as under every edit below); the fit chained ahead of the advance -- K12; the records' match on f1, the state's
 match on f0[-1], roi_weights ahead of track_match, capture never cleared -- K11; centres() with an item of 48 -- K10 and K11;
 with_frames handed the previous batch's slots -- K7, K8 and K11.  The fit handed the ROI maps under a track changes no byte
-here (no case fits under a track WITH roi); the host ledger's compensate-track-roi-match set sees it."""
+here (no case fits under a track WITH roi); the host ledger's compensate-track-roi-match set sees it.
+Four of the six edits of the re-detection call that the host file lists, tried here as well; the library refuses none of them
+(every slot, span and stride is a valid one), the bytes show each: (a) the re-detection on f0[-1] -- K13 and K14 on both
+contexts from the first jump on (post records from pair 6, the track records of the batches behind a search that found the
+square one frame early), K13 among the short chunks on the final state at n = 7, and the two-chunk run; (b) the output at
+ls[0] -- the same tests on redetect_out alone: every batch's first record is written and its last keeps 0xA5 (the batches of
+one pair agree); (c) the trigger the batch's match_out span -- the same tests, post records from pair 2 or 3 on and the state;
+(e) the centres the batch's records -- the same tests, every post record, and redetect_out at n = 1.  Under each of the four
+the leak test is red on both contexts as well, and nothing else of the file."""
 import functools
 import random
 
@@ -76,7 +98,8 @@ CONTEXTS = {"R1": dict(B=3, depth=1, frame_slots=2 * 3 + 2, flow_slots=pipeline.
 RAW, COMP = 0.44, 0.145
 
 
-# ---- the parameters of K7-K12 (plain data and host arrays: the thresholds below derive from them on the CPU, without a device) ---
+# ---- the parameters of K7-K14 (plain data and host arrays: the thresholds below derive from them on the CPU, without a device;
+# K13's and K14's tracks and thresholds are chunk_by_hand.LOST_TRACKS and LOST_THR, which the host test shares) ---------------------
 def GATE7():
     return bh.random_map(W, H, 700)
 
@@ -87,6 +110,10 @@ def GATE9():
 
 def GATE11():
     return bh.random_map(W, H, 1100)
+
+
+def GATE14():
+    return bh.random_map(W, H, bh.LOST_GATE_SEED)
 
 
 TEXTURE8 = {"radius": 3, "tau": 8.0, "soft": 1}
@@ -119,6 +146,10 @@ CASES = {
     "K10": dict(kw=dict(center="track"), track=TRACK10, thr=RAW, povs=(False,), contexts=("R1", "R2")),
     "K11": dict(kw=dict(center="track"), track=TRACK11, gate=GATE11, thr=THR11, povs=(False,), contexts=("R1", "R2")),
     "K12": dict(kw=dict(center="track", compensate="rigid"), track=TRACK12, thr=COMP, povs=(False,), contexts=("R1", "R2")),
+    "K13": dict(kw=dict(center="track"), track=bh.LOST_TRACKS["K13"], clip="lost", thr=bh.LOST_THR["K13"], povs=(False,),
+                contexts=("R1", "R2")),
+    "K14": dict(kw=dict(center="track"), track=bh.LOST_TRACKS["K14"], clip="lost", gate=GATE14, thr=bh.LOST_THR["K14"], povs=(False,),
+                contexts=("R1", "R2")),
 }
 FLOWS_CASES = {"K1": ("flows", "segments"), "K2": ("flows", "segments"), "K3": ("flows", "segments"), "K4": ("flows", "segments"),
                "K5": ("flows", "segments"), "K10": ("flows", "segments"), "K12": ("flows",)}
@@ -137,8 +168,21 @@ def clip(w=W, h=H):
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_raw():
-    return bh.oracle_fields(clip())
+def lost():
+    """the clip of K13 and K14: the suite's with the lost-and-found square pasted in (chunk_by_hand.lost_clip)"""
+    assert bh.suite_clip(N + 1, W, H).tobytes() == clip().tobytes()
+    fr = bh.lost_clip(clip())
+    fr.setflags(write=False)
+    return fr
+
+
+def frames_of(case):
+    return lost() if CASES[case].get("clip") == "lost" else clip(*size_of(case))
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_raw(kind=None):
+    return bh.oracle_fields(lost() if kind == "lost" else clip())
 
 
 def size_of(case):
@@ -194,7 +238,7 @@ def hand(case, pov, n=N, batch=None):
             kw["weights"] = dev(maps_of(kind, w, h, n))        # contiguous here, whatever view the engine gets
         if "gate" in c:
             kw["gate"] = dev(c["gate"]())
-        res = bh.by_hand(one, clip(w, h)[:n + 1], pov=pov, thr=c["thr"], batch=batch, **kw)
+        res = bh.by_hand(one, frames_of(case)[:n + 1], pov=pov, thr=c["thr"], batch=batch, **kw)
         assert one.graph_stats()["capture_failures"] == 0
     for v in (res["flows"], res["raw"]):
         v.setflags(write=False)
@@ -246,12 +290,15 @@ def run(eng, ctx, case, pov, schedule, entry, n=N):
             kw["track"]["match"] = {**track["match"], "templates": tmpl, "capture": True}
             kw["match_out"] = fill(n * nt)
             outs["match"], outs["templates"] = (kw["match_out"], nt), (tmpl, (2 * track["match"]["p"] + 1) ** 2)
+            if track["match"].get("redetect"):      # pre-filled: the records that are no batch's last pair must stay untouched
+                kw["redetect_out"] = fill(n * nt)
+                outs["redetect"] = (kw["redetect_out"], nt)
     if "compensate" in kw:
         mo = kw["motion_out"] = torch.full((n * 64,), 0xA5, dtype=torch.uint8, device=DEV)
     if c.get("grid"):
         grid = kw["grid_out"] = torch.full((n * CELLS * CELLS * _capi.CELL_DTYPE.itemsize,), 0xA5, dtype=torch.uint8, device=DEV)
     if entry == "chunk":
-        src = list(clip(w, h)[:n + 1])
+        src = list(frames_of(case)[:n + 1])
         if c.get("flows_out"):
             T = kw["flows_out"] = torch.full((n, h, w, 2) if c["flows_out"] == "nhwc" else (n, 2, h, w), float("nan"), device=DEV)
         call = eng.process_chunk
@@ -298,12 +345,16 @@ def runs_of(case):
     return runs
 
 
-def check_track_conditions(case, res):
-    """what the tracked cases were chosen for: K10 and K11 meet rule Q5's cut and the uncut step on at least a quarter of their
-    records each; K11 stores matches on both sides of a cut; K12's track, which reads the RAW fields against the compensated
-    threshold, sees every pair as cut (an advance queued behind the subtraction would see about half)"""
+def check_track_conditions(case, res, batch=None):
+    """what the tracked cases were chosen for: K10, K11, K13 and K14 meet rule Q5's cut and the uncut step on at least a quarter
+    of their records each; K11, K13 and K14 store matches on both sides of a cut; K12's track, which reads the RAW fields against
+    the compensated threshold, sees every pair as cut (an advance queued behind the subtraction would see about half); K13 and
+    K14 skip, accept and reject whole-frame searches at the borders of batches of `batch` pairs
+    (chunk_by_hand.check_redetect_conditions)"""
     if res["track"] is None:
         return
+    if res["redetect"] is not None:
+        bh.check_redetect_conditions(case, res["redetect"], res["track"], N, batch)
     T = len(CASES[case]["track"]["state"])
     cut = (np.frombuffer(res["track"], _capi.TRACK_DTYPE).reshape(N, T)["status"] & 1) != 0
     if case == "K12":
@@ -323,10 +374,11 @@ def test_the_clip_and_the_thresholds_do_their_work(case, pov, capsys):
     tuned = "engine" not in c
     for batch in sorted({hand_batch(case, r["B"]) for r in CONTEXTS.values()}, key=str):
         res = hand(case, pov, N, batch)
-        bh.check_anchors(res, oracle_raw() if tuned else None)
-        bh.check_mode_anchors(res, clip(*size_of(case)), thr=c["thr"], gate=c["gate"]() if "gate" in c else None, track=c.get("track"),
+        bh.check_anchors(res, oracle_raw(c.get("clip")) if tuned else None)
+        bh.check_mode_anchors(res, frames_of(case), thr=c["thr"], gate=c["gate"]() if "gate" in c else None, track=c.get("track"),
                               batch=batch, **{k: v for k, v in c["kw"].items() if k in ("weights", "residual", "texture", "consistency", "center")})
-        check_track_conditions(case, res)
+        assert (res["redetect"] is not None) == (case in ("K13", "K14"))
+        check_track_conditions(case, res, batch)
         rec = bh.records(res["post"])
         assert len(rec) == N
         assert len({f.tobytes() for f in res["raw"]}) == N and len({f.tobytes() for f in res["flows"]}) == N    # no two pairs alike
@@ -364,7 +416,7 @@ def test_cases_leave_nothing_behind_for_the_next(name):
     """every 64x48 case of the tuned engine on ONE context, in a fixed shuffled order; the plain chunk before and after"""
     c = CONTEXTS[name]
     runs = [(case, pov) for case in CASES if "engine" not in CASES[case] for pov in CASES[case]["povs"]]
-    assert {case for case, _ in runs} == {f"K{i}" for i in (0, 1, 2, 3, 4, 5, 7, 8, 9, 10, 11, 12)}
+    assert {case for case, _ in runs} == {f"K{i}" for i in (0, 1, 2, 3, 4, 5, 7, 8, 9, 10, 11, 12, 13, 14)}
     random.Random(name).shuffle(runs)
     with engine_context(name, "K0") as ctx:
         eng = pipeline.PairEngine(ctx, depth=c["depth"])
@@ -375,7 +427,7 @@ def test_cases_leave_nothing_behind_for_the_next(name):
         assert ctx.graph_stats()["capture_failures"] == 0
 
 
-@pytest.mark.parametrize("case", ["K1", "K4", "K7", "K11"])
+@pytest.mark.parametrize("case", ["K1", "K4", "K7", "K11", "K13"])
 def test_short_chunks(case):
     """one pair; shorter than the radius; radius + 1; exactly one full window -- none of them fills the ring"""
     c = CONTEXTS["R1"]
@@ -388,4 +440,31 @@ def test_short_chunks(case):
                 if case in FLOWS_CASES:
                     run(eng, ctx, case, pov, "device", "flows", n)
         assert plain_chunk(eng, case) == before
+        assert ctx.graph_stats()["capture_failures"] == 0
+
+
+def test_a_carried_state_re_detects_as_the_one_chunk_run():
+    """K13 on R1 as two chunks split at pair 21, a batch border of B = 3: the first captures, the second gets the same state
+    tensor and the templates with capture off, and both write into the two halves of the same track_out / match_out /
+    redetect_out.  Track, match and re-detection records, the final state and the templates are the one-chunk by-hand run's on
+    bytes (the post records are not: the smoothing window does not cross chunks)."""
+    c, track, split = CONTEXTS["R1"], CASES["K13"]["track"], 21
+    assert split % c["B"] == 0 and 0 < split < N
+    want = hand("K13", False, N, c["B"])
+    T, p = len(track["state"]), track["match"]["p"]
+    nt = T * 48
+    with engine_context("R1", "K13") as ctx:
+        eng = pipeline.PairEngine(ctx, depth=c["depth"])
+        state, tmpl = dev(np.array(track["state"]).view(np.uint8)), pipeline.match_templates(ctx, T, p)
+        outs = {k: torch.full((N * nt,), 0xA5, dtype=torch.uint8, device=DEV) for k in ("track", "match", "redetect")}
+        for lo, hi, capture in ((0, split, True), (split, N, False)):
+            part = {k: t[lo * nt:hi * nt] for k, t in outs.items()}
+            eng.process_chunk(list(lost()[lo:hi + 1]), False, CASES["K13"]["thr"], post_out=True, center="track",
+                              track={"state": state, "radius": track["radius"], "on_cut": track["on_cut"],
+                                     "match": {**track["match"], "templates": tmpl, "capture": capture}},
+                              track_out=part["track"], match_out=part["match"], redetect_out=part["redetect"])
+        for k, t in outs.items():
+            same(t.cpu().numpy().tobytes(), want[k], nt, f"two chunks: {k}")
+        same(state.cpu().numpy().tobytes(), want["state"], nt, "two chunks: state")
+        same(tmpl.cpu().numpy().tobytes(), want["templates"], (2 * p + 1) ** 2, "two chunks: templates")
         assert ctx.graph_stats()["capture_failures"] == 0
